@@ -64,7 +64,35 @@ def parse():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="N>1 collective backend; gloo (hits staged through host memory) only to rehearse the "
                          "multi-rank flow on a 1-GPU box together with AHA_BENCH_ONE_DEVICE=1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64; "
+                         "arrays longer than 2^19 rows as a fixed, seeded sample of rows, with the sampled row numbers "
+                         "beside them), so that two builds can be compared output for output")
     return ap.parse_args()
+
+
+DUMP_ROWS = 1 << 19  # per dumped array: 2^19 rows of hit triples + their row numbers = 16 MiB in float64, < 64 MB in all
+DUMP_SEED = 0
+
+
+def dump_outputs(d, arrays, log):
+    """arrays: name -> tensor (CPU or device) of one of the timed path's outputs.  Writes d/<name>.npy in float64 (exact:
+    hit fields are int32, offsets and counts stay far below 2^53); an array of more than DUMP_ROWS rows is written as the
+    rows a generator seeded with DUMP_SEED picks (sorted; the same rows for the same length), and d/<name>_rows.npy holds
+    which rows those are."""
+    os.makedirs(d, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        n = int(t.shape[0])
+        if n > DUMP_ROWS:
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=DUMP_ROWS, replace=False))
+            t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+            np.save(os.path.join(d, f"{name}_rows.npy"), rows.astype(np.float64))
+            total += rows.size * 8
+        a = t.cpu().numpy().astype(np.float64)
+        np.save(os.path.join(d, f"{name}.npy"), a)
+        total += a.nbytes
+    log(f"outputs of the last timed step: {', '.join(arrays)} in {d} ({total / 1e6:.1f} MB)")
 
 
 def lib_fingerprint():
@@ -309,6 +337,7 @@ def main():
     if overlap:
         d_outs.append(torch.zeros_like(d_out))
     step_no = [0]
+    gathered = [None]  # (all ranks' hits, counts) of the last exchange that completed
 
     def step():
         i = step_no[0]
@@ -316,7 +345,7 @@ def main():
         if not overlap:
             n = ac.match_batch_device(d_corpus, d_doc, d_out, d_dho, chars=args.chars)
             if gather is not None:
-                gather.all_gatherv(d_out if cdev == dev else d_out[:n].cpu(), n)
+                gathered[0] = gather.all_gatherv(d_out if cdev == dev else d_out[:n].cpu(), n)
             return n
         slot = i & 1
         gather.finish(slot)  # the exchange that last read d_outs[slot] (step i-2) must be done
@@ -326,8 +355,8 @@ def main():
 
     def drain():
         if overlap:
-            gather.finish(0)
-            gather.finish(1)
+            done = [gather.finish(0), gather.finish(1)]
+            gathered[0] = done[(step_no[0] - 1) & 1]  # the last step's exchange
 
     def fence():
         torch.cuda.synchronize()
@@ -342,13 +371,20 @@ def main():
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        n_last = step()
         t = ac.last_timing()
         for k in kern:
             kern[k].append(t[k])
     drain()  # every exchange issued in the timed region completes inside it
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # before any later leg runs the match again
+        outs = {"hits": d_outs[(step_no[0] - 1) & 1 if overlap else 0][:n_last], "doc_hit_offsets": d_dho,
+                "n_hits": torch.tensor([n_last], dtype=torch.int64)}
+        if gather is not None:
+            outs["gathered_hits"] = gathered[0][0]
+            outs["gathered_counts"] = torch.tensor(gathered[0][1], dtype=torch.int64)
+        dump_outputs(args.dump_outputs, outs, log)
     tmax = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
     tot_bytes = torch.tensor([float(n_bytes)], dtype=torch.float64, device=cdev)
     tot_hits = torch.tensor([float(n_hits)], dtype=torch.float64, device=cdev)
