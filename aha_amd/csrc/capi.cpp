@@ -26,6 +26,10 @@ void free_scratch(Scratch *sc, bool all) {
     *p = nullptr;
   }
   sc->cap_chunks = sc->cap_blocks = sc->cap_docs = 0;
+  // the counter block went with v2buf[9]: a block allocated later -- even at the same address -- holds words nobody knows
+  sc->cursor_buf = nullptr;
+  sc->cursor_dirty = true;
+  sc->cursor_phase = 0;
   if (!all) return;
   if (sc->d_totals) (void)hipFree(sc->d_totals);
   if (sc->h_totals) (void)hipHostFree(sc->h_totals);
@@ -597,7 +601,10 @@ int32_t aha_ac_info(const aha_ac *ac, aha_ac_info_t *caller_info) {
   info->n_keys = ac->aut.n_keys;
   info->n_states = ac->aut.n_states;
   info->n_slots = ac->n_slots;
-  info->image_bytes = ac->image_bytes;
+  {
+    std::lock_guard<std::mutex> lk(const_cast<aha_ac *>(ac)->alloc_mu);
+    info->image_bytes = ac->image_bytes;
+  }
   info->max_key_len = ac->aut.max_key_len;
   info->slot_bytes = ac->slot_bytes;
   info->lds_slots = ac->v2_lds_slots;

@@ -169,6 +169,11 @@ int32_t v2_reserve(aha_ac *ac, Scratch *sc, int i, size_t bytes) {
   b.p = nullptr;
   b.bytes = 0;
   size_t want = bytes + bytes / 8 + 256;
+  if (i == 9) {  // a new counter block (see Scratch::cursor_dirty): cleared in full by the next call, whatever its address
+    sc->cursor_buf = nullptr;
+    sc->cursor_dirty = true;
+    sc->cursor_phase = 0;
+  }
   HIPCHK(ac, hipMalloc(&b.p, want));
   b.bytes = want;
   return AHA_OK;

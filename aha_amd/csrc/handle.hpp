@@ -65,6 +65,9 @@ struct aha_ac {
   int device = -1;
   DevAut dev{};
   std::vector<void *> dev_allocs;
+  // dev_allocs / image_bytes once the handle is in use (upload_late): a call that holds its scratch set takes it, so it is
+  // never pool_mu -- aha_ac_release_scratch holds pool_mu while it waits for the sets
+  std::mutex alloc_mu;
   // per-call scratch sets: a match call leases one for its duration (Lease below); concurrent calls on one handle
   // get different sets, up to kMaxScratch of them, then wait
   std::mutex pool_mu;
@@ -181,14 +184,14 @@ int32_t upload(aha_ac *ac, const std::vector<T> &v, const T **out) {
 
 // upload() for tables that appear after compile (the first match_longest call), possibly while other threads match on the
 // handle: the copy goes over a private non-blocking stream (no call of the library touches the NULL stream), the handle's
-// allocation list is touched under the pool mutex.
+// allocation list is touched under alloc_mu.
 template <class T>
 int32_t upload_late(aha_ac *ac, const std::vector<T> &v, const T **out) {
   void *d = nullptr;
   const size_t bytes = std::max<size_t>(v.size() * sizeof(T), 16);
   HIPCHK(ac, hipMalloc(&d, bytes));
   {
-    std::lock_guard<std::mutex> lk(ac->pool_mu);
+    std::lock_guard<std::mutex> lk(ac->alloc_mu);
     ac->dev_allocs.push_back(d);
     ac->image_bytes += v.size() * sizeof(T);
   }

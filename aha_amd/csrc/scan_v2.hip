@@ -354,8 +354,9 @@ __global__ __launch_bounds__(kV2Threads, AHA_V2_WAVES_PER_SIMD) void k2_traverse
           } else {
             if (__any(ev && pev)) flush_events();
             if (ev) {
-              // rel was already advanced: the hit ended at rel-1
-              const uint32_t last = (rel == nb_rel) ? kLastFlag : 0u;
+              // rel was already advanced: the hit ended at rel-1 (a document that ends at the piece's end has no
+              // piece-relative boundary, nb_rel = ~0u: its end is compared in absolute offsets)
+              const uint32_t last = (pb + (int64_t)rel == nb) ? kLastFlag : 0u;
               pev = true;
               p_y = (seq << 16) | last | (chunk_rel0 + rel - 1u);
               p_z = (uint32_t)(docrel + (int32_t)rel);

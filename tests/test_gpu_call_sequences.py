@@ -1,0 +1,611 @@
+"""Call sequences on ONE handle, every call against the CPU oracle.
+
+A handle carries state from one call to the next: each leased scratch set keeps its buffers, and v2buf[9] holds two
+blocks of counter words -- a call counts in one of them and its last kernel clears the other for the call behind it
+(engine.cpp, match_v2); calls that do not publish leave the block dirty, hand-backs retry on the same set, and
+release_scratch frees the buffers.  The parity suite compiles fresh handles and makes a call or two on each, so none of
+that is exercised there.  Here one handle per engine variant and key set walks through every ordered pair of call kinds
+(a de Bruijn walk), and each call is checked bit-exact: hit triples in order, per-document offsets, and the rows and
+entries behind what the call may write still hold their sentinels."""
+import ctypes as C
+import gc
+import random
+import threading
+import time
+
+import numpy as np
+import pytest
+
+import pyoracle as orc
+from aha_amd import AC, AhaError, BitArray, DeviceBuffer
+from aha_amd import _native as N
+from aha_amd.ac import _params
+
+pytestmark = pytest.mark.gpu
+
+# the engine variants of test_gpu_parity.py's fixture (the opt-in skip and pair engines left out); read at compile time
+ENGINE_VARS = ("AHA_ENGINE", "AHA_UNIT_HEADER_BESIDE", "AHA_UNIT_BASE_BITS", "AHA_UNIT_POST", "AHA_LDS_SLOTS")
+VARIANTS = {
+    "auto": {},
+    "v2": {"AHA_ENGINE": "v2"},
+    "v1": {"AHA_ENGINE": "v1"},
+    "u": {"AHA_ENGINE": "unit", "AHA_UNIT_HEADER_BESIDE": "0"},
+    "ur": {"AHA_ENGINE": "unit", "AHA_UNIT_POST": "regroup"},
+    "uh": {"AHA_ENGINE": "unit", "AHA_UNIT_HEADER_BESIDE": "1"},
+    "f": {"AHA_ENGINE": "filter"},
+}
+
+HOST, DEV_DHO, DEV_NODHO, STREAM, KEEP, CHARS, SEP, LONG1, LONG2, SINGLE, CAP, BADOFF, EMPTY, UNALIGNED, RELEASE, PROFILE = range(16)
+KIND_NAMES = ["host", "dev_dho", "dev_nodho", "stream", "keep", "chars", "sep", "longest1", "longest2", "single", "capacity",
+              "bad_offsets", "empty", "unaligned", "release", "profiling"]
+K = len(KIND_NAMES)
+ZERO_HIT_KINDS = {EMPTY}          # their count is 0 whatever the text
+NO_DOC_KINDS = {SINGLE}           # one sequence, no document offsets
+TIMED = {HOST, DEV_DHO, DEV_NODHO, STREAM, KEEP, CHARS, SEP, SINGLE, UNALIGNED, PROFILE}  # match_longest and empty batches publish no timing
+
+S32 = -7                          # sentinel of the int32 hit rows
+S64 = 0xFFFFFFFFFFFFFFFB          # sentinel of the uint64 per-document offsets
+PAD = 64                          # rows / entries behind what a call may write
+SEP_BITS = [32]                   # a space separates
+
+
+def de_bruijn_walk(k):
+    """Kinds 0 .. k-1 in an order in which every ordered pair (a, b) stands next to each other once: k^2 + 1 steps."""
+    a = [0] * (2 * k)
+    seq = []
+
+    def db(t, p):
+        if t > 2:
+            if 2 % p == 0:
+                seq.extend(a[1:p + 1])
+        else:
+            a[t] = a[t - p]
+            db(t + 1, p)
+            for j in range(a[t - p] + 1, k):
+                a[t] = j
+                db(t + 1, t)
+
+    db(1, 1)
+    return seq + seq[:1]
+
+
+# ---- key sets and their texts ------------------------------------------------
+
+class Text:
+    def __init__(self, docs):
+        self.docs = [d.encode() if isinstance(d, str) else d for d in docs]
+        self.corpus = np.frombuffer(b"".join(self.docs), dtype=np.uint8).copy()
+        self.offs = np.cumsum([0] + [len(d) for d in self.docs]).astype(np.uint64)
+        self.D = len(self.docs)
+        self._dev = None
+
+    def dev(self):
+        import torch
+
+        if self._dev is None:
+            self._dev = (torch.from_numpy(self.corpus).cuda(), torch.from_numpy(self.offs.astype(np.int64)).cuda())
+        return self._dev
+
+
+def _docs(rng, tokens, sep, shape, density, fill):
+    out = []
+    for n in shape:
+        out.append(sep.join(rng.choice(tokens) if rng.random() < density else rng.choice(fill) for _ in range(n)))
+    return out
+
+
+def _pool(rng, tokens, sep, fill, extra=()):
+    """Five texts of different size, document count and density (plus extras): consecutive calls can always pick a
+    text whose count and document count differ from the call before."""
+    return [
+        Text(_docs(rng, tokens, sep, [300] * 12, 0.05, fill)),
+        Text(_docs(rng, tokens, sep, [60] * 40, 0.3, fill)),
+        Text(_docs(rng, tokens, sep, [8000] * 3, 0.6, fill)),
+        Text(_docs(rng, tokens, sep, [200, 0, 200, 0, 200, 200, 200], 0.2, fill)),
+        Text(_docs(rng, tokens, sep, [rng.randint(0, 8) for _ in range(100)], 0.5, fill)),
+    ] + list(extra)
+
+
+def _ascii_set():
+    """(a) a keyword list of ASCII keys of 3 to 64 bytes (the prefix-filter engine's) over text with a few non-ASCII
+    characters; keys nested six deep on one walk and a document dense with them: kf_walk hands the batch back."""
+    rng = random.Random(31)
+    keys = set()
+    while len(keys) < 150:
+        keys.add("".join(rng.choice("abcdefghijkl") for _ in range(rng.randint(3, 8))))
+    keys = sorted(keys) + ["".join(rng.choice("abcdefghijklmnopqrstuvwxyz") for _ in range(n)) for n in (20, 33, 64)]
+    nested = ["qrstuvwxy"[:n] for n in range(4, 10)]
+    keys = list(dict.fromkeys(keys + nested))
+    fill = ["zz", "é", "ü9", "0", "mn"]
+    dense = Text(["qrstuvwxy " * 3000, "ab qrstuvwxy", "é" * 40 + "qrstuvwxy" * 700])
+    return keys, _pool(rng, keys + nested * 4, " ", fill, [dense])
+
+
+def _cjk_set():
+    """(b) CJK / mixed UTF-8 keys of 1 to 4 characters: the character-level image (engine 4) under `auto`."""
+    rng = random.Random(32)
+    cps = [chr(c) for c in list(range(0x4E00, 0x4E30)) + list(range(97, 105)) + list(range(0x430, 0x438))]
+    keys, seen = [], set()
+    while len(keys) < 150:
+        k = "".join(rng.choice(cps) for _ in range(rng.randint(1, 4)))
+        if k not in seen:
+            seen.add(k)
+            keys.append(k)
+    fill = ["ä", "ß", "\U0001F600", "x", "é"]
+    return keys, _pool(rng, cps + keys + [" "] * 20, "", fill)
+
+
+def _nested_set():
+    """(c) a small nested alphabet: long output chains, the dense expansion, a batch whose hits crowd the first chunks (a
+    region overflows for a capacity near the count: the repeated pass) and, for the capacity kind, 3 MB of "a" (more events
+    than the slab pipeline's temp holds: the two-pass engine counts)."""
+    rng = random.Random(33)
+    keys = ["a", "aa", "ab", "b", "中", "中国"]
+    fill = ["x", " ", "y"]
+    crowd = Text([("ab" * 20000 + "中国" * 20000), "x" * 3_000_000])
+    return keys, _pool(rng, ["a", "b", "中", "国", "aa", "ab", " "], "", fill, [crowd])
+
+
+KEY_SETS = {"ascii": _ascii_set, "cjk": _cjk_set, "nested": _nested_set}
+_SETS = {}
+_ORACLE = {}
+
+
+def key_set(name):
+    if name not in _SETS:
+        keys, texts = KEY_SETS[name]()
+        _SETS[name] = (keys, texts, orc.AC.compile(keys))
+    return _SETS[name]
+
+
+def expect(name, ti, flag, text=None):
+    """The oracle's (hits, per-document offsets) of text ti of key set `name`, cached per (key set, text, flag)."""
+    key = (name, ti, flag)
+    if key not in _ORACLE:
+        _, texts, o = key_set(name)
+        t = text if text is not None else texts[ti]
+        if flag in ("plain", "chars"):
+            h, d = o.match_batch(t.corpus, t.offs, chars=flag == "chars")
+        elif flag == "single":
+            h, d = o.match(t.corpus.tobytes(), chars=False), None
+        else:
+            parts = []
+            for doc in t.docs:
+                if flag == "sep":
+                    parts.append(o.match(doc, chars=False, sep=(256, SEP_BITS)))
+                else:
+                    parts.append(o.match_longest(doc, flag == "long2", chars=False))
+            d = np.cumsum([0] + [len(p) for p in parts]).astype(np.uint64)
+            h = np.concatenate(parts) if parts else np.zeros(0, dtype=orc.HIT_DTYPE)
+        _ORACLE[key] = (np.ascontiguousarray(h, dtype=orc.HIT_DTYPE), d)
+    return _ORACLE[key]
+
+
+FLAG_OF = {HOST: "plain", DEV_DHO: "plain", DEV_NODHO: "plain", STREAM: "plain", KEEP: "plain", CHARS: "chars", SEP: "sep",
+           LONG1: "long1", LONG2: "long2", SINGLE: "single", CAP: "plain", BADOFF: "plain", UNALIGNED: "plain",
+           PROFILE: "plain"}
+
+
+def expected_nd(name, kind, ti):
+    h, _ = expect(name, ti, FLAG_OF[kind])
+    return len(h), (None if kind in NO_DOC_KINDS else key_set(name)[1][ti].D)
+
+
+def plan_walk(name):
+    """The walk for key set `name`: (kind, text index) per step.  Consecutive successful calls differ in hit count
+    (unless both are empty-batch calls, which have none) and in document count (unless both are single sequences); the
+    text rotates over the pool so every text meets every transition."""
+    walk = de_bruijn_walk(K)
+    pairs = set(zip(walk, walk[1:]))
+    assert len(walk) == K * K + 1 and pairs == {(a, b) for a in range(K) for b in range(K)}, "the walk misses a pair"
+    texts = key_set(name)[1]
+    plan, last, rot = [], None, 0
+    n_empty = 0
+    for kind in walk:
+        if kind == RELEASE:
+            plan.append((kind, None))
+            continue
+        if kind == EMPTY:  # no text: a batch of no document, or of five empty ones, by turns (D = 0 or 5)
+            D = 5 * (n_empty % 2)
+            n_empty += 1
+            assert all(t.D not in (0, 5) for t in texts)
+            plan.append((kind, D))
+            last = (0, D, kind)
+            continue
+        chosen = None
+        for j in range(len(texts)):
+            ti = (rot + j) % len(texts)
+            if name == "nested" and ti == len(texts) - 1 and kind not in (DEV_DHO, DEV_NODHO, CAP):
+                continue  # (the 3 MB text: through the device entry, where a capacity near the count makes a region overflow)
+            if kind in (BADOFF, CAP):
+                chosen = ti
+                break
+            n, D = expected_nd(name, kind, ti)
+            if n == 0:
+                continue  # (a zero count would not tell a stale counter from a fresh one)
+            if last is not None:
+                ln, lD, lk = last
+                if n == ln and not (kind in ZERO_HIT_KINDS and lk in ZERO_HIT_KINDS):
+                    continue
+                if D == lD and not (kind in NO_DOC_KINDS and lk in NO_DOC_KINDS):
+                    continue
+            chosen = ti
+            break
+        assert chosen is not None, (name, kind, last)
+        rot += 1
+        plan.append((kind, chosen))
+        if kind not in (BADOFF, CAP):
+            n, D = expected_nd(name, kind, chosen)
+            last = (n, D, kind)
+    return plan
+
+
+# ---- one call of each kind ---------------------------------------------------
+
+def _hits_np(cap):
+    out = np.empty(cap + PAD, dtype=orc.HIT_DTYPE)
+    out["start"] = out["end"] = out["value"] = S32
+    return out
+
+
+def _check_np(out, n, want, limit):
+    """hits [0, n) are the oracle's, rows [limit, end) untouched."""
+    assert n == len(want)
+    assert out[:n].tobytes() == want.tobytes()
+    tail = out[limit:]
+    assert (tail["start"] == S32).all() and (tail["end"] == S32).all() and (tail["value"] == S32).all()
+
+
+def _check_dev(big, n, want, limit):
+    import torch
+
+    assert n == len(want)
+    assert big[:n].cpu().numpy().tobytes() == want.tobytes()
+    assert bool((big[limit:] == S32).all())
+
+
+def _dho_dev(D):
+    import torch
+
+    return torch.full((D + 1 + PAD,), S64 - (1 << 64), dtype=torch.int64, device="cuda")
+
+
+def _check_dho(dho, D, want):
+    got = dho.cpu().numpy().astype(np.uint64) if not isinstance(dho, np.ndarray) else dho
+    assert np.array_equal(got[:D + 1], want)
+    assert (got[D + 1:] == np.uint64(S64)).all()
+
+
+def _host_batch(g, t, cap, chars=False, sep=None, longest=0, keep=None):
+    """aha_ac_match_batch / _keep on the caller's own buffers (prefilled with sentinels)."""
+    p = _params(chars, sep, longest)
+    out = _hits_np(cap)
+    dho = np.full(t.D + 1 + PAD, S64, dtype=np.uint64)
+    n = C.c_uint64(0)
+    cp = t.corpus.ctypes.data if t.corpus.size else None
+    if keep is None:
+        rc = N.lib().aha_ac_match_batch(g._h, cp, t.offs.ctypes.data, t.D, C.byref(p), out.ctypes.data, cap,
+                                        dho.ctypes.data, C.byref(n))
+    else:
+        rc = N.lib().aha_ac_match_batch_keep(g._h, cp, t.offs.ctypes.data, t.D, C.byref(p), keep.data_ptr(), cap,
+                                             dho.ctypes.data, C.byref(n))
+    return rc, int(n.value), out, dho
+
+
+def _sep():
+    s = BitArray(256)
+    for b in SEP_BITS:
+        s[b] = True
+    return s
+
+
+def run_kind(g, name, kind, ti, st, state):
+    """One step: the call, every check; returns (n, D) of a successful match call, else None."""
+    import torch
+
+    keys, texts, o = key_set(name)
+    t = texts[ti] if ti is not None and kind != EMPTY else None  # (an empty-batch step carries its document count)
+    stream = st.cuda_stream
+
+    def device_call(chars=False, dho=True, words=False, unaligned=False, cap_rows=None, offs=None, text=None):
+        tt = text or t
+        want, want_off = expect(name, ti, "chars" if chars else "plain")
+        cap = cap_rows if cap_rows is not None else len(want) + 37
+        with torch.cuda.stream(st):
+            dc, dd = tt.dev()
+            if offs is not None:
+                dd = offs
+            if unaligned:
+                holder = torch.full((tt.corpus.size + 64,), 0xEE, dtype=torch.uint8, device="cuda")
+                dc_u = holder[1:1 + tt.corpus.size]
+                dc_u.copy_(dc)
+                assert dc_u.data_ptr() % 16 == 1
+                dc = dc_u
+            big = torch.full((cap + PAD, 3), S32, dtype=torch.int32, device="cuda")
+            d_dho = _dho_dev(tt.D) if dho else None
+            w = nw = None
+            if words:
+                w = torch.full((2 * cap + cap // 1024 + 2,), S32, dtype=torch.int32, device="cuda")
+                nw = torch.zeros(1, dtype=torch.int64, device="cuda")
+        st.synchronize()
+        err = None
+        try:
+            n = g.match_batch_device(dc, dd, big[:cap], d_dho, chars=chars, stream=stream, words=w, n_words=nw)
+        except AhaError as e:
+            err, n = e, None
+        return dict(err=err, n=n, big=big, dho=d_dho, cap=cap, want=want, want_off=want_off, words=w, n_words=nw)
+
+    if kind == RELEASE:
+        g.release_scratch()
+        assert g.scratch_bytes() == 0
+        return None
+    if kind == PROFILE:
+        state["prof"] = not state["prof"]
+        g.set_profiling(state["prof"])
+        kind = DEV_DHO  # ... and a device call right behind it (the first profiled call on a set creates its events)
+    if kind in (HOST, SEP, LONG1, LONG2):
+        flag = FLAG_OF[kind]
+        want, want_off = expect(name, ti, flag)
+        cap = len(want) + 37
+        rc, n, out, dho = _host_batch(g, t, cap, sep=_sep() if kind == SEP else None,
+                                      longest={LONG1: 1, LONG2: 2}.get(kind, 0))
+        assert rc == N.AHA_OK, (rc, N.lib().aha_last_error(g._h))
+        _check_np(out, n, want, n)
+        _check_dho(dho, t.D, want_off)
+        return n, t.D
+    if kind == KEEP:
+        want, want_off = expect(name, ti, "plain")
+        cap = len(want) + 37
+        with torch.cuda.stream(st):
+            big = torch.full((cap + PAD, 3), S32, dtype=torch.int32, device="cuda")
+        st.synchronize()
+        rc, n, _, dho = _host_batch(g, t, cap, keep=big)
+        assert rc == N.AHA_OK, (rc, N.lib().aha_last_error(g._h))
+        _check_dev(big, n, want, n)
+        _check_dho(dho, t.D, want_off)
+        return n, t.D
+    if kind == SINGLE:
+        want, _ = expect(name, ti, "single")
+        cap = len(want) + 37
+        out = _hits_np(cap)
+        n = C.c_uint64(0)
+        p = _params(False, None)
+        rc = N.lib().aha_ac_match_bytes(g._h, t.corpus.ctypes.data, t.corpus.size, C.byref(p), out.ctypes.data, cap,
+                                        C.byref(n))
+        assert rc == N.AHA_OK, (rc, N.lib().aha_last_error(g._h))
+        _check_np(out, int(n.value), want, int(n.value))
+        return int(n.value), None
+    if kind in (DEV_DHO, DEV_NODHO, STREAM, CHARS, UNALIGNED):
+        r = device_call(chars=kind == CHARS, dho=kind != DEV_NODHO, words=kind == STREAM, unaligned=kind == UNALIGNED)
+        assert r["err"] is None, (r["err"], r["err"].code)
+        n = r["n"]
+        _check_dev(r["big"], n, r["want"], n)
+        if r["dho"] is not None:
+            _check_dho(r["dho"], t.D, r["want_off"])
+        if kind == STREAM:  # the 4-byte exchange stream of the same call, unpacked again
+            with torch.cuda.stream(st):
+                back = torch.full((n + 1, 3), S32, dtype=torch.int32, device="cuda")
+                g.hits_unpack4_device(r["words"], n, back, stream=stream)
+            st.synchronize()
+            assert n == 0 or int(r["n_words"].item()) > 0
+            assert back[:n].cpu().numpy().tobytes() == r["want"].tobytes()
+        return n, t.D
+    if kind == CAP:
+        state["caps"] = state.get("caps", 0) + 1
+        if name == "nested" and state["caps"] % 2 == 0:
+            # 3 MB of "a" and room for 4 hits: more events than the slab pipeline's temp -- the count comes from the two-pass engine
+            big_t = state.setdefault("aaa", np.full(3_000_000, ord("a"), dtype=np.uint8))
+            out = _hits_np(4)
+            n = C.c_uint64(0)
+            rc = N.lib().aha_ac_match_bytes(g._h, big_t.ctypes.data, big_t.size, None, out.ctypes.data, 4, C.byref(n))
+            assert rc == N.AHA_E_CAPACITY and n.value == 2 * big_t.size - 1
+            assert out[:4].tolist() == [(0, 1, 0), (0, 2, 1), (1, 2, 0), (1, 3, 1)]
+            assert (out[4:]["end"] == S32).all()
+            return None
+        want, _ = expect(name, ti, "plain")
+        cap = [len(want) - 1, len(want) // 2, 3][state["caps"] % 3]
+        r = device_call(cap_rows=max(cap, 0))
+        assert r["err"] is not None and r["err"].code == N.AHA_E_CAPACITY, r["err"]
+        assert r["err"].required == len(want)
+        assert bool((r["big"][r["cap"]:] == S32).all())  # nothing at or beyond cap
+        return None
+    if kind == BADOFF:
+        state["bad"] = state.get("bad", 0) + 1
+        offs = t.offs.astype(np.int64).copy()
+        which = state["bad"] % 4
+        if which == 0:
+            offs[0] = 1
+        elif which == 1:
+            offs[-1] -= 1
+        elif which == 2:
+            offs[1] = offs[-1] + 44
+        else:
+            offs[1] = 1 << 40
+        with torch.cuda.stream(st):
+            bad = torch.from_numpy(offs).cuda()
+        r = device_call(offs=bad)
+        assert r["err"] is not None and r["err"].code == N.AHA_E_INVALID, r["err"]
+        assert bool((r["big"] == S32).all())  # nothing indexed with the bad offsets
+        assert bool((r["dho"] == S64 - (1 << 64)).all())
+        return None
+    if kind == EMPTY:
+        if ti == 0:
+            e = Text([])  # no document at all: the host entry
+            rc, n, out, dho = _host_batch(g, e, 16)
+            assert rc == N.AHA_OK and n == 0
+            _check_np(out, 0, np.zeros(0, dtype=orc.HIT_DTYPE), 0)
+            _check_dho(dho, 0, np.zeros(1, dtype=np.uint64))
+            return 0, 0
+        with torch.cuda.stream(st):  # only empty documents: the device entry
+            dc = torch.zeros(16, dtype=torch.uint8, device="cuda")[:0]
+            dd = torch.zeros(6, dtype=torch.int64, device="cuda")
+            big = torch.full((16 + PAD, 3), S32, dtype=torch.int32, device="cuda")
+            dho = _dho_dev(5)
+        st.synchronize()
+        assert g.match_batch_device(dc, dd, big[:16], dho, stream=stream) == 0
+        _check_dev(big, 0, np.zeros(0, dtype=orc.HIT_DTYPE), 0)
+        _check_dho(dho, 5, np.zeros(6, dtype=np.uint64))
+        return 0, 5
+    raise AssertionError(kind)
+
+
+def compile_under(monkeypatch, variant, keys):
+    for v in ENGINE_VARS:
+        monkeypatch.delenv(v, raising=False)
+    for k, v in VARIANTS[variant].items():
+        monkeypatch.setenv(k, v)
+    return AC.compile(keys)
+
+
+def multi_range_call(g, name):
+    """One host call above the host entry's range (64 MiB, capi.cpp kHostRange) made of small documents: two ranges run
+    back to back on one scratch set, so the counter block changes halves inside one API call."""
+    keys, texts, o = key_set(name)
+    rng = random.Random(44)
+    pieces = [d for t in texts[:5] for d in t.docs if d]
+    doc_bytes = 4096
+    n_docs = (68 << 20) // doc_bytes
+    filler = b"\x01" * doc_bytes
+    docs = []
+    for i in range(n_docs):
+        p = pieces[rng.randrange(len(pieces))][:200] if i % 3 == 0 else b""
+        docs.append(p + filler[: doc_bytes - len(p)])
+    t = Text(docs)
+    want, want_off = expect(name, "multi", "plain", text=t)
+    rc, n, out, dho = _host_batch(g, t, len(want) + 37)
+    assert rc == N.AHA_OK, (rc, N.lib().aha_last_error(g._h))
+    _check_np(out, n, want, n)
+    _check_dho(dho, t.D, want_off)
+
+
+@pytest.mark.parametrize("name", list(KEY_SETS))
+@pytest.mark.parametrize("variant", list(VARIANTS))
+def test_call_sequence_on_one_handle(variant, name, monkeypatch):
+    """Every ordered pair of call kinds on one handle, each call against the oracle; with profiling on, aha_timing.n_hits is
+    the call's own count (not the call's before it)."""
+    import torch
+
+    keys, _, _ = key_set(name)
+    g = compile_under(monkeypatch, variant, keys)
+    plan = plan_walk(name)
+    st = torch.cuda.Stream()
+    state = {"prof": False}
+    t0 = time.perf_counter()
+    for i, (kind, ti) in enumerate(plan):
+        if variant == "auto" and i == len(plan) // 2:
+            multi_range_call(g, name)
+        try:
+            res = run_kind(g, name, kind, ti, st, state)
+        except AssertionError as e:
+            raise AssertionError(f"step {i} ({KIND_NAMES[kind]}, text {ti}) after {KIND_NAMES[plan[i - 1][0]] if i else '-'}: {e}") from e
+        if res is not None and state["prof"] and kind in TIMED:
+            assert g.last_timing()["n_hits"] == res[0], (i, KIND_NAMES[kind])
+    print(f"{variant}/{name}: {len(plan)} steps in {time.perf_counter() - t0:.1f} s")
+
+
+def test_release_resets_the_counter_block(monkeypatch):
+    """release_scratch frees the counter block; the block the next call allocates -- possibly at the same address -- holds
+    words nobody knows and must be cleared, whatever the call before the release left behind.  The blocks freed just before
+    the call hold a bad-offsets verdict (17) in cursor[1] of both halves: every kernel of the region pipelines returns on a
+    non-zero cursor[1] before it touches anything else, so a call that trusted the stale block is refused (AHA_E_INVALID)
+    instead of writing anywhere."""
+    keys, texts, _ = key_set("cjk")
+    g = compile_under(monkeypatch, "auto", keys)
+    t = texts[1]
+    want, want_off = expect("cjk", 1, "plain")
+
+    def call():
+        rc, n, out, dho = _host_batch(g, t, len(want) + 37)
+        assert rc == N.AHA_OK, (rc, N.lib().aha_last_error(g._h))
+        _check_np(out, n, want, n)
+        _check_dho(dho, t.D, want_off)
+
+    call()  # a publishing call: it clears the other half and leaves the block clean
+    g.release_scratch()
+    assert g.scratch_bytes() == 0
+    words = (3 * 16 * 8 + 3 * 16 * 8 // 8 + 256) // 8  # what v2_reserve(9, kCursorBytes) allocates: 688 bytes
+    poison = np.zeros(words, dtype=np.uint64)
+    poison[1] = poison[17] = 17
+    bufs = [DeviceBuffer(0, words * 8) for _ in range(16)]
+    for b in bufs:
+        b.upload(poison)
+    del bufs, b
+    gc.collect()
+    call()
+
+
+def test_calls_on_one_handle_beside_release(monkeypatch):
+    """Two threads run call sequences of their own on one handle (each lease its own scratch set) while a third releases
+    the scratch between their calls: every result is the oracle's, and only the steps that expect an error fail."""
+    import torch
+
+    keys, texts, _ = key_set("ascii")
+    g = compile_under(monkeypatch, "auto", keys)
+    kinds = [HOST, DEV_DHO, DEV_NODHO, CHARS, SEP, LONG1, SINGLE, UNALIGNED, STREAM, KEEP, CAP, BADOFF, EMPTY, LONG2]
+    for ti in range(5):  # oracle answers and device copies ahead of the threads
+        for f in ("plain", "chars", "sep", "long1", "long2", "single"):
+            expect("ascii", ti, f)
+        texts[ti].dev()
+    torch.cuda.synchronize()
+    errs, done, counts = [], threading.Event(), [0, 0, 0]
+    deadline = time.perf_counter() + 25
+
+    def work(w):
+        try:
+            st = torch.cuda.Stream()
+            state = {"prof": False}
+            rng = random.Random(70 + w)
+            for r in range(6):
+                order = kinds[:]
+                rng.shuffle(order)
+                for i, kind in enumerate(order):
+                    run_kind(g, "ascii", kind, (i + r + w) % 5, st, state)
+                    counts[w] += 1
+                if time.perf_counter() > deadline:
+                    break
+        except Exception as e:  # noqa: BLE001
+            errs.append((w, repr(e)))
+
+    def releaser():
+        while not done.is_set():
+            g.release_scratch()
+            counts[2] += 1
+            time.sleep(0.003)
+
+    ths = [threading.Thread(target=work, args=(w,)) for w in (0, 1)]
+    rel = threading.Thread(target=releaser)
+    rel.start()
+    for th in ths:
+        th.start()
+    for th in ths:
+        th.join()
+    done.set()
+    rel.join()
+    assert not errs, errs
+    assert counts[0] >= len(kinds) and counts[1] >= len(kinds) and counts[2] > 1, counts
+
+
+@pytest.mark.parametrize("variant", list(VARIANTS))
+def test_separator_at_a_document_end_on_a_piece_boundary(variant, monkeypatch):
+    """match(seq, sep) in a batch: a hit that ends its document has no right neighbour (src/aha/ac.cr:324-329, documents are
+    independent: ac.cr:177).  The single-traversal engine stages the text in pieces of 32 bytes and flags an event as its
+    document's last by the boundary's offset inside the piece -- a document that ends exactly at the piece's end has none
+    there, so the flag must come from the absolute offsets, or the next document's first byte (or the byte behind the text)
+    is taken for the neighbour and the hit is dropped."""
+    keys = ["ab", "b", "abc"]
+    g = compile_under(monkeypatch, variant, keys)
+    o = orc.AC.compile(keys)
+    docs = [b"ab" + b" " * 28 + b"ab"] * 6 + [b"ab" + b" " * 60 + b"ab", b"b" * 32, b"", b"ab " + b" " * 90 + b"abc"] + \
+           [b"ab" + b" " * 28 + b"ab"] * 3
+    t = Text(docs)
+    assert all(int(x) % 32 == 0 for x in t.offs)  # every document ends on a piece boundary, the last one at the text's end
+    want, want_off = [], [0]
+    for d in docs:
+        h = o.match(d, chars=False, sep=(256, SEP_BITS))
+        want.append(h)
+        want_off.append(want_off[-1] + len(h))
+    want = np.concatenate(want)
+    rc, n, out, dho = _host_batch(g, t, len(want) + 8, sep=_sep())
+    assert rc == N.AHA_OK
+    _check_np(out, n, want, n)
+    _check_dho(dho, t.D, np.array(want_off, dtype=np.uint64))
