@@ -11,13 +11,14 @@ import pytest
 import pyoracle as orc
 from aha_amd import AC, AhaError, BitArray, Hit, synth
 from aha_amd import _native as N
+from engine_variants import VARIANTS, use_variant
 from pymodel import ModelAC
 from test_oracle_vs_model import as_list, rand_keys
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(params=["v2", "v1", "v2p", "u", "ur", "u23", "uh", "k", "p", "f", "auto"], autouse=True)
+@pytest.fixture(params=VARIANTS, autouse=True)
 def engine(request, monkeypatch):
     """Every parity test runs on the single-traversal engine (scan_v2.hip, byte level), on the two-pass engine
     (kernels.hip: the fallback for tiny capacities and very long keys), on the single-traversal engine with its LDS
@@ -37,31 +38,8 @@ def engine(request, monkeypatch):
     AHA_ENGINE=pair -- the pair engine, scan_pair.hip: the unit image likewise, byte-offset calls answered by the stateless pair
     pass + deep walks wherever the key set admits it).  "auto" sets
     no variable: the library decides per key set, which is what a caller and bench.py get.  The variables are read when a
-    handle is compiled."""
-    only = os.environ.get("AHA_TEST_ENGINES")  # (development: run the suite on some variants only, e.g. AHA_TEST_ENGINES=f,auto)
-    if only and request.param not in only.split(","):
-        pytest.skip("variant not selected by AHA_TEST_ENGINES")
-    if request.param == "auto":
-        monkeypatch.delenv("AHA_ENGINE", raising=False)
-    else:
-        monkeypatch.setenv("AHA_ENGINE", {"v1": "v1", "u": "unit", "ur": "unit", "u23": "unit", "uh": "unit", "f": "filter", "k": "skip", "p": "pair"}.get(request.param, "v2"))
-    if request.param in ("u", "uh"):
-        monkeypatch.setenv("AHA_UNIT_HEADER_BESIDE", "1" if request.param == "uh" else "0")
-    else:
-        monkeypatch.delenv("AHA_UNIT_HEADER_BESIDE", raising=False)
-    if request.param == "u23":
-        monkeypatch.setenv("AHA_UNIT_BASE_BITS", "23")
-    else:
-        monkeypatch.delenv("AHA_UNIT_BASE_BITS", raising=False)
-    if request.param == "ur":
-        monkeypatch.setenv("AHA_UNIT_POST", "regroup")
-    else:
-        monkeypatch.delenv("AHA_UNIT_POST", raising=False)
-    if request.param == "v2p":
-        monkeypatch.setenv("AHA_LDS_SLOTS", "1024")
-    else:
-        monkeypatch.delenv("AHA_LDS_SLOTS", raising=False)
-    return request.param
+    handle is compiled (engine_variants.py sets them)."""
+    return use_variant(request.param, monkeypatch)
 
 
 G = os.path.join(os.path.dirname(__file__), "golden")
