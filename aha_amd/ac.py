@@ -364,6 +364,81 @@ class AC:
             self._check(rc)
             return out.download(np.zeros(int(n.value), dtype=HIT_DTYPE)), dho.download(np.zeros(D + 1, dtype=np.uint64))
 
+    # -- counts without the hit list (aha_ac_count_batch*) -------------------------------------------
+    def count_batch(self, corpus, doc_offsets, sep=None, chars=False, per_key=True, accumulate_into=None):
+        """Hits per key and per document of match_batch(corpus, doc_offsets, sep) without the hit list:
+        -> (key_counts uint64[K] or None, doc_hit_offsets uint64[D+1]).  chars changes no count (accepted for symmetry).
+        accumulate_into: a uint64[K] array the counts are added to (AHA_COUNT_ACCUMULATE); it is also what is returned."""
+        if isinstance(corpus, (bytes, bytearray)):
+            corpus = np.frombuffer(bytes(corpus), dtype=np.uint8)
+        corpus = np.ascontiguousarray(corpus, dtype=np.uint8)
+        doc_offsets = np.ascontiguousarray(doc_offsets, dtype=np.uint64)
+        D = doc_offsets.size - 1
+        p = _params(chars, sep)
+        dho = np.zeros(D + 1, dtype=np.uint64)
+        flags = 0
+        kc = None
+        if accumulate_into is not None:
+            kc = accumulate_into
+            if not (isinstance(kc, np.ndarray) and kc.dtype == np.uint64 and kc.flags.c_contiguous and kc.flags.writeable
+                    and kc.size == self.n_keys):
+                raise ValueError(f"accumulate_into must be a writeable C-contiguous uint64 array of {self.n_keys} entries")
+            flags = N.AHA_COUNT_ACCUMULATE
+        elif per_key:
+            kc = np.zeros(self.n_keys, dtype=np.uint64)
+        n = C.c_uint64(0)
+        rc = N.lib().aha_ac_count_batch(self._h, _ptr(corpus), _ptr(doc_offsets), D, C.byref(p), flags, _ptr(kc), _ptr(dho),
+                                        C.byref(n))
+        self._check(rc)
+        return kc, dho
+
+    def count(self, seq, sep=None):
+        """Hits per key of match(seq, sep) on one sequence: uint64[K]."""
+        b = _b(seq)
+        kc, _ = self.count_batch(np.frombuffer(b, dtype=np.uint8), np.array([0, len(b)], dtype=np.uint64), sep=sep)
+        return kc
+
+    def count_batch_device(self, corpus, doc_offsets, key_counts=None, doc_hit_offsets=None, sep=None, chars=False,
+                           accumulate=False, stream=None):
+        """Device-resident count on torch CUDA tensors (uint8 corpus, int64/uint64 doc offsets; key_counts int64/uint64 [K] or
+        None; doc_hit_offsets int64/uint64 [D+1] or None).  Returns the hit count.  accumulate: add into key_counts."""
+        import torch
+
+        assert corpus.is_cuda and corpus.dtype == torch.uint8 and corpus.is_contiguous()
+        assert doc_offsets.is_cuda and doc_offsets.dtype in (torch.int64, torch.uint64)
+        if key_counts is not None and not (key_counts.is_cuda and key_counts.dtype in (torch.int64, torch.uint64)
+                                           and key_counts.is_contiguous() and key_counts.numel() >= self.n_keys):
+            raise ValueError(f"key_counts must be a contiguous int64/uint64 CUDA tensor of at least {self.n_keys} entries")
+        if doc_hit_offsets is not None and not (doc_hit_offsets.is_cuda and doc_hit_offsets.dtype in (torch.int64, torch.uint64)
+                                                and doc_hit_offsets.is_contiguous()
+                                                and doc_hit_offsets.numel() >= doc_offsets.numel()):
+            raise ValueError("doc_hit_offsets must be a contiguous int64/uint64 CUDA tensor of at least D + 1 entries")
+        D = doc_offsets.numel() - 1
+        p = _params(chars, sep)
+        n = C.c_uint64(0)
+        s = stream if stream is not None else torch.cuda.current_stream(corpus.device).cuda_stream
+        kc = key_counts.data_ptr() if key_counts is not None else None
+        dho = doc_hit_offsets.data_ptr() if doc_hit_offsets is not None else None
+        rc = N.lib().aha_ac_count_batch_device(self._h, corpus.data_ptr(), doc_offsets.data_ptr(), D, corpus.numel(), C.byref(p),
+                                               N.AHA_COUNT_ACCUMULATE if accumulate else 0, kc, dho, C.byref(n), C.c_void_p(s))
+        self._check(rc)
+        return int(n.value)
+
+    def count_corpus(self, corpus, sep=None, chars=False, per_key=True):
+        """Counts a batch that already lives in HBM (DeviceCorpus) and downloads the results:
+        -> (key_counts uint64[K] or None, doc_hit_offsets uint64[D+1], n_hits)."""
+        D = corpus.n_docs
+        p = _params(chars, sep)
+        dev = corpus.device
+        dho = DeviceBuffer(dev, (D + 1) * 8)
+        kc = DeviceBuffer(dev, max(1, self.n_keys) * 8) if per_key else None
+        n = C.c_uint64(0)
+        rc = N.lib().aha_ac_count_batch_device(self._h, corpus.ptr, corpus.doc_ptr, D, corpus.n_bytes, C.byref(p), 0,
+                                               kc.ptr if kc else None, dho.ptr, C.byref(n), None)
+        self._check(rc)
+        counts = kc.download(np.zeros(self.n_keys, dtype=np.uint64)) if kc else None
+        return counts, dho.download(np.zeros(D + 1, dtype=np.uint64)), int(n.value)
+
     # -- exchange format of the multi-GPU all-gatherv: {end, value} pairs <-> Hit triples ------------
     def hits_pack_device(self, hits, n, pairs, stream=None):
         """hits [>=n,3] int32 -> pairs [>=n,2] int32, both on the handle's device (asynchronous)."""

@@ -19,6 +19,10 @@ void free_scratch(Scratch *sc, bool all) {
     if (b.p) (void)hipFree(b.p);
     b = Buf();
   }
+  for (auto &b : sc->cntbuf) {
+    if (b.p) (void)hipFree(b.p);
+    b = Buf();
+  }
   void **scratch[] = {(void **)&sc->d_counts, (void **)&sc->d_leads, (void **)&sc->d_blk_hits, (void **)&sc->d_blk_leads,
                       (void **)&sc->d_docg};
   for (void **p : scratch) {
@@ -51,6 +55,7 @@ uint64_t scratch_bytes(const Scratch *sc) {
   uint64_t n = 0;
   for (auto &b : sc->v2buf) n += b.bytes;
   for (auto &b : sc->hostbuf) n += b.bytes;
+  for (auto &b : sc->cntbuf) n += b.bytes;
   n += sc->cap_chunks * 8 + sc->cap_blocks * 16 + sc->cap_docs * 8;
   return n;
 }
@@ -885,6 +890,13 @@ struct HostPipe {
   }
 };
 
+// a count call through the host entry (aha_ac_count_batch): the ranges are counted instead of matched, into one device vector
+// of key counts that comes back at the end
+struct CountReq {
+  uint32_t flags;
+  uint64_t *key_counts;  // host, K entries, or null
+};
+
 static bool host_streams(Scratch *sc) {
   for (auto &st : sc->hs)
     if (!st && hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return false;
@@ -899,7 +911,8 @@ static bool host_streams(Scratch *sc) {
 // they fit; what a shard of a group calls.  The place may become known while the call runs: the copies wait for hc->ready.)
 static int32_t match_batch_host(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc_offsets, uint64_t n_docs,
                                 const aha_match_params *params, aha_hit *out, aha_hit *d_keep, uint64_t cap,
-                                uint64_t *doc_hit_offsets, uint64_t *n_hits, aha_internal_host_copy *hc = nullptr);
+                                uint64_t *doc_hit_offsets, uint64_t *n_hits, aha_internal_host_copy *hc = nullptr,
+                                const CountReq *cq = nullptr);
 
 int32_t aha_ac_match_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc_offsets,
                            uint64_t n_docs, const aha_match_params *params, aha_hit *out,
@@ -936,7 +949,8 @@ int32_t aha_internal_match_batch_keep_copy(aha_ac *ac, const uint8_t *corpus, co
 
 static int32_t match_batch_host(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc_offsets, uint64_t n_docs,
                                 const aha_match_params *params, aha_hit *out, aha_hit *d_keep, uint64_t cap,
-                                uint64_t *doc_hit_offsets, uint64_t *n_hits, aha_internal_host_copy *hc) {
+                                uint64_t *doc_hit_offsets, uint64_t *n_hits, aha_internal_host_copy *hc,
+                                const CountReq *cq) {
   if (!ac || !doc_offsets || !n_hits) return AHA_E_INVALID;
   if (ac->device < 0) {
     tls_err = aha_strerror(AHA_E_NO_DEVICE);
@@ -999,7 +1013,9 @@ static int32_t match_batch_host(aha_ac *ac, const uint8_t *corpus, const uint64_
   uint64_t *d_doc = (uint64_t *)reserve(1, (n_docs + R + 1) * sizeof(uint64_t));
   uint64_t *d_dho = (uint64_t *)reserve(2, (n_docs + R + 1) * sizeof(uint64_t));
   aha_hit *d_out = !cap ? nullptr : d_keep ? d_keep : (aha_hit *)reserve(3, cap * sizeof(aha_hit));
-  if (!d_corpus || !d_doc || !d_dho || (cap && !d_out) || !host_streams(sc)) {
+  const uint64_t K = ac->aut.n_keys;
+  uint64_t *d_kc = (cq && cq->key_counts) ? (uint64_t *)reserve(3, std::max<uint64_t>(K, 1) * 8) : nullptr;  // (a count: no hits)
+  if (!d_corpus || !d_doc || !d_dho || (cap && !d_out) || (cq && cq->key_counts && !d_kc) || !host_streams(sc)) {
     tls_err = "hipMalloc / hipStreamCreate failed for the staging buffers";
     return AHA_E_HIP;
   }
@@ -1086,9 +1102,11 @@ static int32_t match_batch_host(aha_ac *ac, const uint8_t *corpus, const uint64_
     const uint64_t D = bounds[k + 1] - bounds[k], nb = doc_offsets[bounds[k + 1]] - doc_offsets[bounds[k]];
     const uint64_t room = (!overflow && cap > total) ? cap - total : 0;
     uint64_t nh = 0;
-    int32_t rc = match_batch_device_impl(ac, sc, d_corpus + dev_off[k], d_doc + bounds[k] + k, D, nb, params,
-                                         room ? d_out + total : nullptr, room, d_dho + bounds[k] + k, &nh, s_match,
-                                         true);  // the offsets were checked on the host above
+    int32_t rc = cq ? device_count(ac, sc, d_corpus + dev_off[k], d_doc + bounds[k] + k, D, nb, params, k ? AHA_COUNT_ACCUMULATE : 0u,
+                                   d_kc, d_dho + bounds[k] + k, &nh, s_match, true)
+                    : match_batch_device_impl(ac, sc, d_corpus + dev_off[k], d_doc + bounds[k] + k, D, nb, params,
+                                              room ? d_out + total : nullptr, room, d_dho + bounds[k] + k, &nh, s_match,
+                                              true);  // the offsets were checked on the host above
     if (rc != AHA_OK && rc != AHA_E_CAPACITY) {
       P.fail(rc, tls_err);
       break;
@@ -1110,11 +1128,62 @@ static int32_t match_batch_host(aha_ac *ac, const uint8_t *corpus, const uint64_
     return P.rc;
   }
   *n_hits = total;
+  if (cq) {
+    if (d_kc) {
+      std::vector<uint64_t> kc;
+      try {
+        kc.resize(K);
+      } catch (...) {
+        return AHA_E_NOMEM;
+      }
+      if (K && (hipMemcpyAsync(kc.data(), d_kc, K * 8, hipMemcpyDeviceToHost, s_match) != hipSuccess ||
+                hipStreamSynchronize(s_match) != hipSuccess)) {
+        tls_err = "download of the key counts failed";
+        return AHA_E_HIP;
+      }
+      if (cq->flags & AHA_COUNT_ACCUMULATE)
+        for (uint64_t j = 0; j < K; j++) cq->key_counts[j] += kc[j];
+      else
+        std::copy(kc.begin(), kc.end(), cq->key_counts);
+    }
+    return AHA_OK;
+  }
   if (total > cap) {
     tls_err = "output buffer too small";
     return AHA_E_CAPACITY;
   }
   return AHA_OK;
+}
+
+int32_t aha_ac_count_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc_offsets, uint64_t n_docs,
+                           const aha_match_params *params, uint32_t flags, uint64_t *key_counts, uint64_t *doc_hit_offsets,
+                           uint64_t *n_hits) {
+  if (!ac || !n_hits || !doc_offsets || (flags & ~AHA_COUNT_ACCUMULATE)) return AHA_E_INVALID;
+  MatchArgs M{};
+  int longest = 0;
+  int32_t rc = fill_params(ac, params, M, &longest);
+  if (rc) return rc;
+  if (longest) return AHA_E_INVALID;
+  const CountReq cq{flags, key_counts};
+  return match_batch_host(ac, corpus, doc_offsets, n_docs, params, nullptr, nullptr, 0, doc_hit_offsets, n_hits, nullptr, &cq);
+}
+
+int32_t aha_ac_count_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                                  uint64_t n_bytes, const aha_match_params *params, uint32_t flags, uint64_t *d_key_counts,
+                                  uint64_t *d_doc_hit_offsets, uint64_t *n_hits, void *stream) {
+  if (!ac || !n_hits || !d_doc_offsets || (flags & ~AHA_COUNT_ACCUMULATE)) return AHA_E_INVALID;
+  MatchArgs M{};
+  int longest = 0;
+  int32_t rc = fill_params(ac, params, M, &longest);
+  if (rc) return rc;
+  if (longest) return AHA_E_INVALID;
+  if (ac->device < 0) {
+    tls_err = aha_strerror(AHA_E_NO_DEVICE);
+    return AHA_E_NO_DEVICE;
+  }
+  Lease lease(ac);
+  return device_count(ac, lease.get(), d_corpus, d_doc_offsets, n_docs, n_bytes, params, flags, d_key_counts, d_doc_hit_offsets,
+                      n_hits, stream, false);
 }
 
 // ---- device buffers behind the C ABI (include/aha_hip.h) ---------------------------------------------------------

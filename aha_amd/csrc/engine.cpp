@@ -223,6 +223,10 @@ int32_t ensure_h_v2(aha_ac *ac, Scratch *sc) {
 int32_t match_v2(aha_ac *ac, Scratch *sc, MatchArgs &M1, hipStream_t s, uint64_t *n_hits, V2Mode mode) {
   const uint64_t N = M1.n_bytes;
   const uint32_t Lmax = ac->aut.max_key_len;
+  // a count call (device_count): full-size regions -- sized from the text, there is no capacity -- and the count passes instead
+  // of the expansion; where they are beyond the bound or cannot be allocated the pass returns 4 before it launches anything,
+  // and the caller counts the batch in document ranges (count_ranges)
+  const bool counting = M1.count_only != 0;
   uint64_t s_min = std::max<uint64_t>(64, ((8ull * Lmax + 63) / 64) * 64);
   if (s_min > kV2MaxS) return 1;
   const char *de = getenv("AHA_DIRECT");
@@ -274,12 +278,19 @@ int32_t match_v2(aha_ac *ac, Scratch *sc, MatchArgs &M1, hipStream_t s, uint64_t
   // events too, so a handle that has it keeps the regions for sparse batches)
   if (M.sep || (mode == kRegions && sparse && !ac->unit_ok && !filt)) mode = kSlabs;
   if (mode == kRegions && dense) mode = kFullRegions;
+  if (counting) mode = kFullRegions;
   uint64_t stride = S;
   // twice the average the caller allows for, plus a slack of 1/64 of the chunk (64 events at 4 KiB): 16 bytes per hit of
   // capacity + 1/8 byte per input byte
   if (mode == kRegions) stride = std::min<uint64_t>(S, 2 * (M1.cap / M.n_chunks) + std::max<uint64_t>(16, S / 64));
   // bytes per event of the regions: 8 (byte-level engine), 12 (character-level, fused expansion), 12 + 8 (general passes)
   const uint64_t rec_bytes = want_pair ? 8 : (ac->unit_ok ? (ac->unit_fused ? 12 : 20) : 8);
+  if (counting) {
+    // (AHA_COUNT_REGION_BYTES: a lower bound for the tests, which reach the document ranges with small batches)
+    const char *rb = getenv("AHA_COUNT_REGION_BYTES");
+    const uint64_t bound = rb && atoll(rb) > 0 ? std::min<uint64_t>((uint64_t)atoll(rb), kV2MaxRegionBytes) : kV2MaxRegionBytes;
+    if (M.n_chunks * stride * rec_bytes > bound) return 4;
+  }
   if (mode != kSlabs && M.n_chunks * stride * rec_bytes > kV2MaxRegionBytes) mode = kSlabs;
   const bool direct = mode != kSlabs;
   const uint64_t waves = (uint64_t)ac->v2_grid * (kV2Threads / 64);
@@ -317,6 +328,7 @@ int32_t match_v2(aha_ac *ac, Scratch *sc, MatchArgs &M1, hipStream_t s, uint64_t
       // no room for the event regions (someone else holds the HBM): the slab pipeline needs far less temp
       if ((i == 16 || i == 21) && mode != kSlabs) {
         (void)hipGetLastError();
+        if (counting) return 4;
         return match_v2(ac, sc, M1, s, n_hits, kSlabs);
       }
       return rc;
@@ -364,6 +376,7 @@ int32_t match_v2(aha_ac *ac, Scratch *sc, MatchArgs &M1, hipStream_t s, uint64_t
   // device-resident offsets nobody has looked at yet: validated here, in front of the traversal; a bad verdict lands in
   // cursor[1], where the traversal and every post pass look first (no read-back before the launch: -30 us per call)
   if (M1.check_docs) launch_check_docs(M.doc_off, M.n_docs, N, nullptr, M.cursor + 1, s);
+  if (M1.kc_visits) HIPCHK(ac, hipMemsetAsync(M1.kc_visits, 0, (size_t)ac->aut.n_keys * 8, s));  // (this pass's events only)
   if (prof) HIPCHK(ac, hipEventRecord(sc->ev[0], s));
   const uint64_t n_tiles = (M.n_chunks + kV2Threads - 1) / kV2Threads;
   DevAut post = ac->dev;
@@ -392,7 +405,30 @@ int32_t match_v2(aha_ac *ac, Scratch *sc, MatchArgs &M1, hipStream_t s, uint64_t
     v2_launch_traverse(ac->dev, M, (uint32_t)std::min<uint64_t>(ac->v2_grid, n_tiles), s);
   }
   if (prof) HIPCHK(ac, hipEventRecord(sc->ev[1], s));
-  if (direct) {
+  if (counting) {
+    // the count path: the hits per chunk and their scan as in a match (total, documents' offsets), the events per head key
+    // instead of the expansion, then the chains (scan_count.hip)
+    const unsigned long long *abortf = (const unsigned long long *)(M.cursor + 1);
+    // workgroups of the visit count: four per CU.  The kernel is bound by its LDS table's atomics, not by the flushes' global
+    // adds: 64 / 256 / 1024 workgroups took 4.29 / 1.09 / 0.71 ms on cfg 3 at 1 GiB (AHA_COUNT_BLOCKS: lab)
+    static const long count_blocks_env = getenv("AHA_COUNT_BLOCKS") ? atol(getenv("AHA_COUNT_BLOCKS")) : 0;
+    const uint32_t count_blocks = count_blocks_env > 0 ? (uint32_t)count_blocks_env : 4u * ac->v2_grid;
+    if (unit && ac->unit_fused) {
+      v2_launch_hit_scan(M, s);
+      if (prof) HIPCHK(ac, hipEventRecord(sc->ev[3], s));
+      if (M1.kc_visits) count_launch_visits(post, M, ac->d_unit_end, M1.kc_visits, count_blocks, s);
+    } else {
+      if (unit) unit_launch_regroup(post, M, s);
+      v2_launch_count_post(post, M, s, unit || filt || pair);
+      if (prof) HIPCHK(ac, hipEventRecord(sc->ev[3], s));
+      if (M1.kc_visits) count_launch_visits(post, M, nullptr, M1.kc_visits, count_blocks, s);
+    }
+    if (M1.kc_visits) count_launch_chain(ac->dev.key_ln, ac->aut.n_keys, M1.kc_visits, M1.kc_out, abortf, s);
+    if (unit && ac->unit_fused)
+      unit_launch_doc_offsets(M, s);
+    else
+      v2_launch_doc_offsets(post, M, s);
+  } else if (direct) {
     // (no event between the traversal and the post passes of this pipeline: a record costs ~5 us of stream time, and ev[1]
     // stands for ev[2] in the timing below)
     if (unit && ac->unit_fused) {  // the traversal counted the hits: bases, then the expansion straight from the wave-ordered events
@@ -453,7 +489,8 @@ int32_t match_v2(aha_ac *ac, Scratch *sc, MatchArgs &M1, hipStream_t s, uint64_t
     return AHA_E_TOO_LONG;
   }
   if (sc->h_v2[1] == 3 && pair) {  // the pair engine gave the batch up (documents of a few bytes, a piece dense with events): engine 4 takes it
-    ac->pair_off.fetch_add(1, std::memory_order_relaxed);  // (three times: the handle stops trying)
+    if (!counting) ac->pair_off.fetch_add(1, std::memory_order_relaxed);  // (three times: the handle stops trying; a count call
+                                                                           // leaves the handle's history as it found it)
     M1.no_pair = 1;
   }
   if (sc->h_v2[1] == 3) return 3;  // the prefix-filter engine gave up (candidates too dense, nested keys): the caller repeats without it
@@ -500,6 +537,30 @@ int32_t ready_events(aha_ac *ac, Scratch *sc) {
   return AHA_OK;
 }
 
+// the offsets live in HBM: one small kernel and an 4-byte read-back before anything indexes with them (device_match and
+// device_count, where no single-traversal pass validates them on the device)
+static int32_t check_docs_now(aha_ac *ac, Scratch *sc, const uint64_t *d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
+                              hipStream_t s) {
+  int32_t rc2;
+  if ((rc2 = v2_reserve(ac, sc, 9, kCursorBytes))) return rc2;
+  if ((rc2 = ensure_h_v2(ac, sc))) return rc2;
+  uint32_t *flag = (uint32_t *)sc->v2buf[9].p + 64;  // (the third block: odd words)
+  HIPCHK(ac, hipMemsetAsync(flag, 0, 4, s));
+  launch_check_docs(d_doc_offsets, n_docs, n_bytes, flag, nullptr, s);
+  HIPCHK(ac, hipMemcpyAsync(sc->h_v2, flag, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  const uint32_t bad = (uint32_t)sc->h_v2[0];
+  if (bad & 1u) {
+    tls_err = "doc offsets: need doc_offsets[0] = 0, ascending, doc_offsets[n_docs] = n_bytes";
+    return AHA_E_INVALID;
+  }
+  if (bad & 2u) {
+    tls_err = aha_strerror(AHA_E_TOO_LONG);
+    return AHA_E_TOO_LONG;
+  }
+  return AHA_OK;
+}
+
 int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
                      uint64_t n_bytes, const aha_match_params *params, aha_hit *d_out, uint64_t cap, uint64_t *d_doc_hit_offsets,
                      uint64_t *n_hits, void *stream, bool offsets_checked, const PackOut *pk, bool *packed) {
@@ -517,27 +578,7 @@ int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
   if (rc) return rc;
   if ((rc = ready_events(ac, sc))) return rc;
   *n_hits = 0;
-  auto check_now = [&]() -> int32_t {
-    // the offsets live in HBM: one small kernel and an 4-byte read-back before anything indexes with them
-    int32_t rc2;
-    if ((rc2 = v2_reserve(ac, sc, 9, kCursorBytes))) return rc2;
-    if ((rc2 = ensure_h_v2(ac, sc))) return rc2;
-    uint32_t *flag = (uint32_t *)sc->v2buf[9].p + 64;  // (the third block: odd words)
-    HIPCHK(ac, hipMemsetAsync(flag, 0, 4, s));
-    launch_check_docs(d_doc_offsets, n_docs, n_bytes, flag, nullptr, s);
-    HIPCHK(ac, hipMemcpyAsync(sc->h_v2, flag, 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(ac, hipStreamSynchronize(s));
-    const uint32_t bad = (uint32_t)sc->h_v2[0];
-    if (bad & 1u) {
-      tls_err = "doc offsets: need doc_offsets[0] = 0, ascending, doc_offsets[n_docs] = n_bytes";
-      return AHA_E_INVALID;
-    }
-    if (bad & 2u) {
-      tls_err = aha_strerror(AHA_E_TOO_LONG);
-      return AHA_E_TOO_LONG;
-    }
-    return AHA_OK;
-  };
+  auto check_now = [&]() { return check_docs_now(ac, sc, d_doc_offsets, n_docs, n_bytes, s); };
   // The single-traversal pipelines validate on the device in front of their traversal (match_v2); every other path -- an
   // empty batch, match_longest, the two-pass engine -- reads the verdict back first.
   const bool defer_check = !offsets_checked && ac->v2_ok && !longest && n_bytes != 0;
@@ -718,6 +759,260 @@ int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
     return AHA_E_CAPACITY;
   }
   return AHA_OK;
+}
+
+// ---- count calls (aha_ac_count_batch*) ------------------------------------------------------------------------------
+// The two-pass engine's counting form over one batch: ONE traversal (k_count with per-key adds; it notes every document's
+// hits before its start within its chunk, k_count_doc_offsets adds the chunks' bases), the scan, the chain pass.
+static int32_t count_two_pass(aha_ac *ac, Scratch *sc, MatchArgs M, hipStream_t s, uint64_t *n_hits, uint32_t repeats) {
+  M.chunk = ac->chunk;
+  // warm-up is Lmax-1 bytes per chunk: keep it a small fraction of the chunk
+  while (M.chunk < 8ull * ac->aut.max_key_len && M.chunk < (1u << 20)) M.chunk *= 2;
+  M.n_chunks = (M.n_bytes + M.chunk - 1) / M.chunk;
+  const uint64_t n_blocks = (M.n_chunks + kBlock - 1) / kBlock;
+  int32_t rc;
+  if ((rc = ensure_scratch(ac, sc, M.n_chunks, n_blocks, M.n_docs))) return rc;
+  M.counts = sc->d_counts;
+  M.leads = sc->d_leads;
+  M.blk_hits = sc->d_blk_hits;
+  M.blk_leads = sc->d_blk_leads;
+  M.docg = sc->d_docg;
+  M.totals = sc->d_totals;
+  const bool prof = ac->profiling.load() && sc->ev_ready;
+  if (M.kc_visits) HIPCHK(ac, hipMemsetAsync(M.kc_visits, 0, (size_t)ac->aut.n_keys * 8, s));
+  if (prof) HIPCHK(ac, hipEventRecord(sc->ev[0], s));
+  launch_count(ac->dev, M, s);
+  if (prof) HIPCHK(ac, hipEventRecord(sc->ev[1], s));
+  launch_scan_blocks(M, n_blocks, s);
+  if (prof) HIPCHK(ac, hipEventRecord(sc->ev[3], s));
+  if (M.kc_visits) count_launch_chain(ac->dev.key_ln, ac->aut.n_keys, M.kc_visits, M.kc_out, nullptr, s);
+  if (M.doc_hit_off) launch_count_doc_offsets(M, s);
+  if (prof) HIPCHK(ac, hipEventRecord(sc->ev[4], s));
+  HIPCHK(ac, hipGetLastError());
+  HIPCHK(ac, hipMemcpyAsync(sc->h_totals, sc->d_totals, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  *n_hits = sc->h_totals[0];
+  if (prof) {
+    aha_timing t;
+    memset(&t, 0, sizeof(t));
+    t.struct_size = sizeof(t);
+    t.n_kernels = 3 + (M.kc_visits ? 1 : 0) + (M.doc_hit_off ? 1 : 0);
+    (void)hipEventElapsedTime(&t.ms_total, sc->ev[0], sc->ev[4]);
+    (void)hipEventElapsedTime(&t.ms_count, sc->ev[0], sc->ev[1]);
+    (void)hipEventElapsedTime(&t.ms_scan, sc->ev[1], sc->ev[3]);
+    (void)hipEventElapsedTime(&t.ms_write, sc->ev[3], sc->ev[4]);
+    t.n_chunks = M.n_chunks;
+    t.n_hits = *n_hits;
+    t.engine = 1;
+    t.chunk_bytes = M.chunk;
+    t.repeats = repeats;
+    publish_timing(ac, t);
+  }
+  return AHA_OK;
+}
+
+// One batch through the single-traversal engines' count pipeline: AHA_OK, < 0, 1 (the two-pass engine takes it: as a match
+// of the batch would) or 4 (the full-size regions do not fit: count_ranges).  The handle's back-off state is read, not written.
+static int32_t count_single(aha_ac *ac, Scratch *sc, MatchArgs &M, hipStream_t s, uint64_t *n_hits) {
+  uint32_t repeats = 0;
+  if (ac->pf_ok && ac->pf_skip[0].load(std::memory_order_relaxed)) M.no_filter = 1;  // (as the next match call would)
+  int32_t rc = match_v2(ac, sc, M, s, n_hits, kFullRegions);
+  for (int i = 0; i < 2 && rc == 3; i++) {  // handed back by the prefix-filter or the pair engine: once more without it
+    repeats++;
+    M.no_filter = 1;
+    rc = match_v2(ac, sc, M, s, n_hits, kFullRegions);
+  }
+  if (rc == 3) rc = 1;
+  if (rc == AHA_OK && repeats) note_repeats(ac, repeats);
+  return rc;
+}
+
+static void *count_reserve(Scratch *sc, int i, size_t bytes) {
+  Buf &b = sc->cntbuf[i];
+  if (b.bytes < bytes) {
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr;
+    b.bytes = 0;
+    const size_t want = bytes + bytes / 4 + 4096;
+    if (hipMalloc(&b.p, want) != hipSuccess) {
+      (void)hipGetLastError();
+      return nullptr;
+    }
+    b.bytes = want;
+  }
+  return b.p;
+}
+
+// A batch whose full-size regions are beyond the bound or cannot be allocated (HBM held elsewhere): counted in ranges of whole
+// documents, one after another, each through the same pipeline -- the key counts add up in the caller's vector as they do
+// for running totals, the documents' offsets are rebased on the host.  A range that still does not fit is halved; a single
+// document that does not (its regions: up to 20 bytes per byte of a document below 2 GiB) is the only batch that goes to the
+// two-pass engine's counting form here.
+static int32_t count_ranges(aha_ac *ac, Scratch *sc, const MatchArgs &M0, hipStream_t s, uint64_t *n_hits) {
+  const uint64_t D = M0.n_docs;
+  std::vector<uint64_t> off, hd, tmp, rel;
+  try {
+    off.resize(D + 1);
+    if (M0.doc_hit_off) hd.resize(D + 1);
+  } catch (...) {
+    return AHA_E_NOMEM;
+  }
+  HIPCHK(ac, hipMemcpyAsync(off.data(), M0.doc_off, (D + 1) * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  uint64_t limit = std::max<uint64_t>(M0.n_bytes / 2, 1), base = 0;
+  uint32_t ranges = 0;
+  for (uint64_t d0 = 0; d0 < D;) {
+    uint64_t d1 = d0 + 1;
+    while (d1 < D && off[d1 + 1] - off[d0] <= limit) d1++;
+    const uint64_t nd = d1 - d0, nb = off[d1] - off[d0];
+    try {
+      rel.resize(nd + 1);
+      tmp.resize(nd + 1);
+    } catch (...) {
+      return AHA_E_NOMEM;
+    }
+    for (uint64_t d = 0; d <= nd; d++) rel[d] = off[d0 + d] - off[d0];
+    uint64_t *d_rel = (uint64_t *)count_reserve(sc, 0, (nd + 1) * 8);
+    uint64_t *d_dho = M0.doc_hit_off ? (uint64_t *)count_reserve(sc, 2, (nd + 1) * 8) : nullptr;
+    if (!d_rel || (M0.doc_hit_off && !d_dho)) {
+      tls_err = "hipMalloc failed for a document range of a count call";
+      return AHA_E_HIP;
+    }
+    HIPCHK(ac, hipMemcpyAsync(d_rel, rel.data(), (nd + 1) * 8, hipMemcpyHostToDevice, s));
+    const uint8_t *text = M0.text + off[d0];
+    if (nb && reinterpret_cast<uintptr_t>(text) % 16 != 0) {  // (the kernels read aligned 16-byte pieces)
+      uint8_t *t = (uint8_t *)count_reserve(sc, 1, nb + 64);
+      if (!t) {
+        tls_err = "hipMalloc failed for a document range of a count call";
+        return AHA_E_HIP;
+      }
+      HIPCHK(ac, hipMemcpyAsync(t, text, nb, hipMemcpyDeviceToDevice, s));
+      text = t;
+    }
+    MatchArgs M = M0;
+    M.text = text;
+    M.doc_off = d_rel;
+    M.n_docs = nd;
+    M.n_bytes = nb;
+    M.doc_hit_off = d_dho;
+    M.check_docs = 0;
+    uint64_t nh = 0;
+    int32_t rc = AHA_OK;
+    if (nb == 0) {
+      if (d_dho) HIPCHK(ac, hipMemsetAsync(d_dho, 0, (nd + 1) * 8, s));
+    } else {
+      rc = count_single(ac, sc, M, s, &nh);
+      if (rc == 4 && nd > 1) {  // nothing was launched: the same documents in smaller ranges
+        limit = std::max<uint64_t>(limit / 2, 1);
+        continue;
+      }
+      if (rc == 4 || rc == 1) {
+        M = M0;
+        M.text = text;
+        M.doc_off = d_rel;
+        M.n_docs = nd;
+        M.n_bytes = nb;
+        M.doc_hit_off = d_dho;
+        M.check_docs = 0;
+        rc = count_two_pass(ac, sc, M, s, &nh, 1);
+      }
+    }
+    if (rc != AHA_OK) return rc;
+    if (d_dho) {
+      HIPCHK(ac, hipMemcpyAsync(tmp.data(), d_dho, (nd + 1) * 8, hipMemcpyDeviceToHost, s));
+      HIPCHK(ac, hipStreamSynchronize(s));
+      for (uint64_t d = 0; d <= nd; d++) hd[d0 + d] = base + tmp[d];
+    }
+    base += nh;
+    d0 = d1;
+    ranges++;
+  }
+  if (M0.doc_hit_off) {
+    HIPCHK(ac, hipMemcpyAsync(M0.doc_hit_off, hd.data(), (D + 1) * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(ac, hipStreamSynchronize(s));
+  }
+  *n_hits = base;
+  note_repeats(ac, ranges - 1);  // (aha_timing.repeats: the passes of the call beside its last one, the earlier ranges)
+  return AHA_OK;
+}
+
+// One device-resident batch counted (aha_ac_count_batch_device): the match's engine and pipeline with the count passes in
+// place of the expansion (match_v2, `counting`); document ranges where its full-size regions do not fit (count_ranges); the
+// two-pass engine's counting form where a match of the batch takes that engine, and for a separator filter (a test per hit).
+// Byte offsets throughout: char offsets change no count.  The handle's history (the prefix filter's back-off, the pair
+// engine's give-ups) is read, never written: the next match call behaves as if this call had not happened.
+int32_t device_count(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                     uint64_t n_bytes, const aha_match_params *params, uint32_t flags, uint64_t *d_key_counts,
+                     uint64_t *d_doc_hit_offsets, uint64_t *n_hits, void *stream, bool offsets_checked) {
+  if (!ac || !n_hits || !d_doc_offsets) return AHA_E_INVALID;
+  if (ac->device < 0) {
+    tls_err = aha_strerror(AHA_E_NO_DEVICE);
+    return AHA_E_NO_DEVICE;
+  }
+  if (flags & ~AHA_COUNT_ACCUMULATE) return AHA_E_INVALID;
+  DeviceGuard g(ac->device);
+  hipStream_t s = (hipStream_t)stream;
+  MatchArgs M{};
+  int longest = 0;
+  int32_t rc = fill_params(ac, params, M, &longest);
+  if (rc) return rc;
+  if (longest) {
+    tls_err = "count calls have no match_longest form";
+    return AHA_E_INVALID;
+  }
+  if ((rc = ready_events(ac, sc))) return rc;
+  *n_hits = 0;
+  M.chars = 0;
+  const uint32_t K = ac->aut.n_keys;
+  auto check_now = [&]() { return check_docs_now(ac, sc, d_doc_offsets, n_docs, n_bytes, s); };
+  const bool single = ac->v2_ok && !M.sep && n_bytes != 0;
+  const bool defer_check = !offsets_checked && single;
+  if (!offsets_checked && !defer_check && (rc = check_now())) return rc;
+  M.check_docs = defer_check ? 1 : 0;
+  // the caller's counts: cleared unless it keeps running totals (then only added to, by the passes that run to their end)
+  if (d_key_counts && !(flags & AHA_COUNT_ACCUMULATE)) HIPCHK(ac, hipMemsetAsync(d_key_counts, 0, (size_t)K * 8, s));
+  if (n_bytes == 0) {
+    if (d_doc_hit_offsets) HIPCHK(ac, hipMemsetAsync(d_doc_hit_offsets, 0, (n_docs + 1) * sizeof(uint64_t), s));
+    HIPCHK(ac, hipStreamSynchronize(s));
+    return AHA_OK;
+  }
+  if (!d_corpus) return AHA_E_INVALID;
+  if (reinterpret_cast<uintptr_t>(d_corpus) % 16 != 0) {
+    if ((rc = v2_reserve(ac, sc, 17, n_bytes + 64))) return rc;
+    HIPCHK(ac, hipMemcpyAsync(sc->v2buf[17].p, d_corpus, n_bytes, hipMemcpyDeviceToDevice, s));
+    d_corpus = (const uint8_t *)sc->v2buf[17].p;
+  }
+  M.text = d_corpus;
+  M.doc_off = d_doc_offsets;
+  M.n_docs = n_docs;
+  M.n_bytes = n_bytes;
+  M.out = nullptr;
+  M.cap = 0;
+  M.doc_hit_off = d_doc_hit_offsets;
+  M.count_only = 1;
+  M.kc_out = reinterpret_cast<unsigned long long *>(d_key_counts);
+  if (d_key_counts) {
+    if (M.sep) {
+      M.kc_hits = M.kc_out;  // (a test per hit: straight into the caller's counts)
+    } else {
+      if ((rc = v2_reserve(ac, sc, 25, (size_t)std::max<uint32_t>(K, 1) * 8))) return rc;
+      M.kc_visits = (unsigned long long *)sc->v2buf[25].p;
+    }
+  }
+  if (single) {
+    const MatchArgs M0 = M;
+    rc = count_single(ac, sc, M, s, n_hits);
+    if (rc <= AHA_OK) return rc;
+    *n_hits = 0;
+    if (M.check_docs && (rc = check_now())) return rc;  // (no single-traversal pass has looked at the offsets)
+    M.check_docs = 0;
+    if (rc == 4) {
+      MatchArgs Mr = M0;
+      Mr.check_docs = 0;
+      return count_ranges(ac, sc, Mr, s, n_hits);
+    }
+  }
+  return count_two_pass(ac, sc, M, s, n_hits, single ? 1 : 0);
 }
 
 }  // namespace ahai

@@ -37,7 +37,8 @@ struct Scratch {
   hipEvent_t ev[6] = {};
   bool ev_ready = false;
   Buf v2buf[26];
-  Buf hostbuf[4];  // device staging of the host-buffer entry points (corpus, doc offsets, doc hit offsets, hits)
+  Buf hostbuf[4];
+  Buf cntbuf[3];   // count calls in document ranges (engine.cpp count_ranges): relative offsets, an aligned text, offsets  // device staging of the host-buffer entry points (corpus, doc offsets, doc hit offsets, hits)
   hipStream_t hs[3] = {};  // host-buffer entry: private non-blocking streams for upload, match, download
   unsigned long long *h_v2 = nullptr;  // pinned: cursor[2] + totals[3]
   unsigned long long *h_v2_dev = nullptr;  // the same words as the device addresses them
@@ -243,4 +244,8 @@ struct PackOut {
 int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
                      uint64_t n_bytes, const aha_match_params *params, aha_hit *d_out, uint64_t cap, uint64_t *d_doc_hit_offsets,
                      uint64_t *n_hits, void *stream, bool offsets_checked, const PackOut *pk, bool *packed);
+// one device-resident batch counted (aha_ac_count_batch_device): the match's engine, the count passes instead of the expansion
+int32_t device_count(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                     uint64_t n_bytes, const aha_match_params *params, uint32_t flags, uint64_t *d_key_counts,
+                     uint64_t *d_doc_hit_offsets, uint64_t *n_hits, void *stream, bool offsets_checked);
 }  // namespace ahai

@@ -66,6 +66,11 @@ struct MatchArgs {
   aha_hit *out;
   uint64_t cap;
   uint64_t *doc_hit_off;     // [D+1] or null
+  // count calls (aha_ac_count_batch*): no hit is written; the pipelines add per key instead (scan_count.hip)
+  int32_t count_only;                // host side: the call counts (its pipeline, its repeats: engine.cpp device_count)
+  unsigned long long *kc_visits;     // [K] events per head key (the two-pass engine's k_count<.., true> without a separator filter)
+  unsigned long long *kc_hits;       // [K] hits per key (k_count<.., true> with a separator filter: per hit, both neighbour tests)
+  unsigned long long *kc_out;        // [K] the caller's key counts (the chain pass adds into them)
 };
 
 constexpr int kBlock = 256;  // threads per block in the traversal kernels
@@ -220,6 +225,16 @@ void v2_launch_sort(const DevAut &A, const V2Args &M, uint64_t n_records, void *
 void v2_launch_expand(const DevAut &A, const V2Args &M, uint64_t n_events, void *stream);
 // direct pipeline (plain mode): per-chunk hit counts, their scan, expansion and document offsets
 void v2_launch_direct_post(const DevAut &A, const V2Args &M, void *stream, void *ev_mid, bool counted = false);
+// the count path of the same pipeline: per-chunk hit counts (unless counted) and their scan; then the documents' offsets
+void v2_launch_count_post(const DevAut &A, const V2Args &M, void *stream, bool counted);
+void v2_launch_doc_offsets(const DevAut &A, const V2Args &M, void *stream);
+void unit_launch_doc_offsets(const V2Args &M, void *stream);  // the fused path's document offsets (ku_doc_offsets)
+// count path (scan_count.hip): events per head key from the region records (uend null) or the character-level traversal's
+// wave-ordered records (uend = its END table); then key_counts[j] += visits[h] for every j on chain(h)
+void count_launch_visits(const DevAut &A, const V2Args &M, const uint2 *uend, unsigned long long *visits, uint32_t max_blocks,
+                         void *stream);
+void count_launch_chain(const uint2 *key_ln, uint32_t n_keys, const unsigned long long *visits, unsigned long long *out,
+                        const unsigned long long *abortf, void *stream);
 
 // exchange format of the multi-GPU all-gatherv (kernels.hip): {end, value} pairs <-> Hit triples
 void launch_hits_pack(const int32_t *hits, uint64_t n, int32_t *pairs, void *stream);
@@ -247,6 +262,7 @@ void launch_check_docs(const uint64_t *doc_off, uint64_t n_docs, uint64_t n_byte
 // launchers (kernels.hip)
 void launch_count(const DevAut &A, const MatchArgs &M, void *stream);
 void launch_scan_blocks(const MatchArgs &M, uint64_t n_blocks, void *stream);
+void launch_count_doc_offsets(const MatchArgs &M, void *stream);  // count calls: k_count's per-document notes + chunk bases
 void launch_docg(const MatchArgs &M, void *stream);
 void launch_write(const DevAut &A, const MatchArgs &M, void *stream);
 // match_longest (ac.cr:118-143): mode 1 = intersectable false (a thread per document), 2 = true (a thread per chunk,

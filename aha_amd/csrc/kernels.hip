@@ -26,7 +26,11 @@ namespace aha {
 
 // ------------------------------------------------------------- count kernel
 // Pass 1: per-chunk number of hits (and UTF-8 lead bytes in chars mode).
-template <bool COMPACT>
+// KEYS (count calls): also one add per event into kc_visits[head key] (the chain pass spreads them over the chains) or, with
+// a separator filter, one per hit that passes both neighbour tests into kc_hits[key].  Count calls also note, for every
+// document that starts in the chunk, the chunk's hits before its start (k_count_doc_offsets then adds the chunk's base): the
+// documents' offsets without the second traversal of k_write.
+template <bool COMPACT, bool KEYS_OR_DOCS, bool KEYS = KEYS_OR_DOCS>
 __global__ __launch_bounds__(kBlock) void k_count(DevAut A, MatchArgs M) {
   __shared__ uint64_t sm[kBlock / 64];
   const uint64_t c = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -47,6 +51,7 @@ __global__ __launch_bounds__(kBlock) void k_count(DevAut A, MatchArgs M) {
     for (uint64_t p = a; p < e; p++) {
       if (p == nb) {
         do {
+          if (KEYS_OR_DOCS && M.count_only && M.doc_hit_off) M.doc_hit_off[dn] = hits;  // (k_count_doc_offsets adds the chunk's base)
           dn++;
           nb = dn <= D ? M.doc_off[dn] : ~0ull;
         } while (nb == p);
@@ -58,6 +63,7 @@ __global__ __launch_bounds__(kBlock) void k_count(DevAut A, MatchArgs M) {
       if (aut_step<COMPACT>(A, B, M.text + p, key)) {
         if (!M.sep) {
           hits += A.key_cnt[key];
+          if (KEYS) atomicAdd(&M.kc_visits[key], 1ull);
         } else {
           // match(seq, sep): right neighbour of the end position (ac.cr:324-329)
           if (p + 1 < nb && sep_blocked(M, M.text[p + 1])) continue;
@@ -66,7 +72,10 @@ __global__ __launch_bounds__(kBlock) void k_count(DevAut A, MatchArgs M) {
             uint2 ln = A.key_ln[k];
             uint64_t s = p + 1 - ln.x;  // absolute start
             // left neighbour of the hit (ac.cr:331-336)
-            if (!(s > doc_start && sep_blocked(M, M.text[s - 1]))) hits++;
+            if (!(s > doc_start && sep_blocked(M, M.text[s - 1]))) {
+              hits++;
+              if (KEYS) atomicAdd(&M.kc_hits[k], 1ull);
+            }
             k = (int32_t)ln.y;
           } while (k >= 0);
         }
@@ -116,6 +125,22 @@ __global__ __launch_bounds__(1024) void k_scan_blocks(uint64_t *blk_hits, uint64
     }
     if (threadIdx.x == 0) totals[which] = carry;
   }
+}
+
+// Count calls: doc_hit_off[d] holds the hits of d's chunk before d's start (k_count); + the chunk's base = the hits before
+// the document (k_write's idx at the same boundary).  Documents that start at n_bytes: the total.
+__global__ __launch_bounds__(256) void k_count_doc_offsets(MatchArgs M) {
+  const uint64_t d = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (d > M.n_docs) return;
+  const uint64_t q = M.doc_off[d];
+  if (q >= M.n_bytes) {
+    M.doc_hit_off[d] = M.totals[0];
+    return;
+  }
+  const uint64_t c = q / M.chunk;
+  uint64_t base = M.blk_hits[c / kBlock];
+  for (uint64_t cc = (c / kBlock) * kBlock; cc < c; cc++) base += M.counts[cc];
+  M.doc_hit_off[d] += base;
 }
 
 // -------------------------------------------------------------- docg kernel
@@ -825,10 +850,28 @@ static inline uint32_t blocks_for(uint64_t n_chunks) {
 void launch_count(const DevAut &A, const MatchArgs &M, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   uint32_t g = blocks_for(M.n_chunks);
-  if (A.compact)
-    hipLaunchKernelGGL(k_count<true>, dim3(g), dim3(kBlock), 0, s, A, M);
-  else
-    hipLaunchKernelGGL(k_count<false>, dim3(g), dim3(kBlock), 0, s, A, M);
+  const bool keys = M.kc_visits || M.kc_hits;  // (a count call that wants the key counts)
+  const bool docs = M.count_only && M.doc_hit_off;  // (... or the documents' offsets)
+  if (A.compact) {
+    if (keys)
+      hipLaunchKernelGGL((k_count<true, true>), dim3(g), dim3(kBlock), 0, s, A, M);
+    else if (docs)
+      hipLaunchKernelGGL((k_count<true, true, false>), dim3(g), dim3(kBlock), 0, s, A, M);
+    else
+      hipLaunchKernelGGL((k_count<true, false>), dim3(g), dim3(kBlock), 0, s, A, M);
+  } else {
+    if (keys)
+      hipLaunchKernelGGL((k_count<false, true>), dim3(g), dim3(kBlock), 0, s, A, M);
+    else if (docs)
+      hipLaunchKernelGGL((k_count<false, true, false>), dim3(g), dim3(kBlock), 0, s, A, M);
+    else
+      hipLaunchKernelGGL((k_count<false, false>), dim3(g), dim3(kBlock), 0, s, A, M);
+  }
+}
+
+void launch_count_doc_offsets(const MatchArgs &M, void *stream) {
+  const uint64_t n = M.n_docs + 1;
+  hipLaunchKernelGGL(k_count_doc_offsets, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, M);
 }
 
 void launch_scan_blocks(const MatchArgs &M, uint64_t n_blocks, void *stream) {

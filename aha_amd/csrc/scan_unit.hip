@@ -726,6 +726,11 @@ void unit_launch_traverse(const UnitDev &U, const V2Args &M, uint32_t grid, void
 #undef AHA_LAUNCH_KU
 }
 
+void unit_launch_doc_offsets(const V2Args &M, void *stream) {
+  if (M.doc_hit_off)
+    hipLaunchKernelGGL(ku_doc_offsets, dim3((uint32_t)((M.n_docs + 1 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, M);
+}
+
 void unit_launch_regroup(const DevAut &A, const V2Args &M, void *stream) {
   const uint64_t n_groups = (M.n_chunks + 63) / 64;
   hipLaunchKernelGGL(ku_regroup, dim3((uint32_t)std::min<uint64_t>(n_groups, 1u << 16)), dim3(kRgThreads), 0,

@@ -1467,6 +1467,28 @@ void v2_launch_lead_scan(const V2Args &M, void *stream) {  // lead_cnt -> lead_b
               (hipStream_t)stream);
 }
 
+void v2_launch_count_post(const DevAut &A, const V2Args &M, void *stream, bool counted) {
+  hipStream_t s = (hipStream_t)stream;
+  const uint32_t gw = grid_for(M.n_chunks, 4, 8192);
+  if (counted) {
+  } else if (A.compact) {
+    hipLaunchKernelGGL(k2d_count<true>, dim3(gw), dim3(256), 0, s, A, M);
+  } else {
+    hipLaunchKernelGGL(k2d_count<false>, dim3(gw), dim3(256), 0, s, A, M);
+  }
+  launch_scan(M.chunk_hits, M.n_chunks, M.blk_a, M.hit_base, M.totals + 0, (const unsigned long long *)(M.cursor + 1), s);
+}
+
+void v2_launch_doc_offsets(const DevAut &A, const V2Args &M, void *stream) {
+  if (!M.doc_hit_off) return;
+  hipStream_t s = (hipStream_t)stream;
+  const uint64_t nd = M.n_docs + 1;
+  if (nd <= 4 * M.n_chunks)
+    hipLaunchKernelGGL(k2d_doc_offsets<16>, dim3((uint32_t)((nd * 16 + 255) / 256)), dim3(256), 0, s, A, M);
+  else
+    hipLaunchKernelGGL(k2d_doc_offsets<1>, dim3((uint32_t)((nd + 255) / 256)), dim3(256), 0, s, A, M);
+}
+
 void v2_launch_direct_post(const DevAut &A, const V2Args &M0, void *stream, void *ev_mid, bool counted) {
   V2Args M = M0;
   hipStream_t s = (hipStream_t)stream;

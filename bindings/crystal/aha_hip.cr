@@ -173,6 +173,13 @@ lib LibAhaHip
   fun aha_ac_match_batch_device(ac : Ac, d_corpus : UInt8*, d_doc_offsets : UInt64*, n_docs : UInt64, n_bytes : UInt64,
                                 params : MatchParams*, d_out : Hit*, cap : UInt64, d_doc_hit_offsets : UInt64*,
                                 n_hits : UInt64*, stream : Void*) : Int32
+  # hits per key and per document without the hit list (flags: COUNT_ACCUMULATE adds into key_counts)
+  COUNT_ACCUMULATE = 1_u32
+  fun aha_ac_count_batch(ac : Ac, corpus : UInt8*, doc_offsets : UInt64*, n_docs : UInt64, params : MatchParams*,
+                         flags : UInt32, key_counts : UInt64*, doc_hit_offsets : UInt64*, n_hits : UInt64*) : Int32
+  fun aha_ac_count_batch_device(ac : Ac, d_corpus : UInt8*, d_doc_offsets : UInt64*, n_docs : UInt64, n_bytes : UInt64,
+                                params : MatchParams*, flags : UInt32, d_key_counts : UInt64*, d_doc_hit_offsets : UInt64*,
+                                n_hits : UInt64*, stream : Void*) : Int32
   fun aha_buffer_alloc(device : Int32, bytes : UInt64, d_ptr : Void**) : Int32
   fun aha_buffer_free(device : Int32, d_ptr : Void*) : Int32
   fun aha_buffer_upload(device : Int32, d_dst : Void*, src : Void*, bytes : UInt64) : Int32
@@ -301,6 +308,37 @@ module Aha
         break
       end
       result
+    end
+
+    # K: the number of keys (the length of a key-count array)
+    def n_keys : Int32
+      info = LibAhaHip::Info.new
+      info.struct_size = sizeof(LibAhaHip::Info).to_u32
+      rc = LibAhaHip.aha_ac_info(@handle, pointerof(info))
+      raise String.new(LibAhaHip.aha_strerror(rc)) if rc != 0
+      info.n_keys.to_i32
+    end
+
+    # Hits per key of match_batch(docs, sep: sep) without the hit list: {key_counts (K entries), doc_hit_offsets}.
+    # accumulate: a K-entry array the counts are added to (running totals over many batches); it is what is returned.
+    def count_batch(docs : Array(String) | Array(Bytes), sep : BitArray? = nil,
+                    accumulate : Array(UInt64)? = nil) : {Array(UInt64), Array(UInt64)}
+      corpus = IO::Memory.new
+      offs = Array(UInt64).new(docs.size + 1)
+      offs << 0_u64
+      docs.each do |d|
+        corpus.write(d.is_a?(String) ? d.to_slice : d)
+        offs << corpus.pos.to_u64
+      end
+      params = AC.params(false, sep)
+      dho = Array(UInt64).new(docs.size + 1, 0_u64)
+      kc = accumulate || Array(UInt64).new(n_keys, 0_u64)
+      raise ArgumentError.new("accumulate holds #{n_keys} counts") if kc.size != n_keys
+      flags = accumulate ? LibAhaHip::COUNT_ACCUMULATE : 0_u32
+      rc = LibAhaHip.aha_ac_count_batch(@handle, corpus.to_slice.to_unsafe, offs.to_unsafe, docs.size.to_u64,
+        pointerof(params), flags, kc.to_unsafe, dho.to_unsafe, out n)
+      raise String.new(LibAhaHip.aha_last_error(@handle)) if rc != 0
+      {kc, dho}
     end
 
     private def run(seq : Bytes, chars : Bool, sep : BitArray?, longest : Int32 = 0, &block)

@@ -193,6 +193,67 @@ class AC {
     return out;
   }
 
+  // K: the number of keys (the length of a key-count vector)
+  uint32_t n_keys() const {
+    aha_ac_info_t i{};
+    i.struct_size = sizeof(i);
+    const int32_t rc = aha_ac_info(h_, &i);
+    if (rc != AHA_OK) throw Error(rc, aha_strerror(rc));
+    return i.n_keys;
+  }
+
+  // Hits per key of match_batch without the hit list (aha_ac_count_batch): key_counts[k] = hits with value k.  accumulate:
+  // add into *key_counts (which then must hold K entries) instead of overwriting it -- running totals over many batches.
+  uint64_t count_batch(std::string_view corpus, const std::vector<uint64_t> &doc_offsets, std::vector<uint64_t> *key_counts,
+                       std::vector<uint64_t> *doc_hit_offsets = nullptr, bool accumulate = false) const {
+    if (doc_offsets.empty()) throw Error(AHA_E_INVALID, "doc_offsets holds D + 1 entries");
+    aha_match_params p{};
+    p.struct_size = sizeof(p);
+    const uint64_t D = doc_offsets.size() - 1;
+    std::vector<uint64_t> dho(D + 1);
+    if (key_counts && !accumulate) key_counts->assign(n_keys(), 0);
+    if (key_counts && key_counts->size() != n_keys()) throw Error(AHA_E_INVALID, "key_counts holds K entries");
+    uint64_t n = 0;
+    const int32_t rc = aha_ac_count_batch(h_, reinterpret_cast<const uint8_t *>(corpus.data()), doc_offsets.data(), D, &p,
+                                          accumulate ? AHA_COUNT_ACCUMULATE : 0u, key_counts ? key_counts->data() : nullptr,
+                                          dho.data(), &n);
+    if (rc != AHA_OK) {
+      const char *m = aha_last_error(h_);
+      throw Error(rc, (m && *m) ? m : aha_strerror(rc));
+    }
+    if (doc_hit_offsets) *doc_hit_offsets = std::move(dho);
+    return n;
+  }
+
+  // The same on a batch resident in HBM (aha_ac_count_batch_device): d_key_counts is device memory of K uint64 (or null) and
+  // keeps running totals there with accumulate; returns the hit count.
+  uint64_t count_resident(const Corpus &c, uint64_t *d_key_counts, bool accumulate = false,
+                          std::vector<uint64_t> *doc_hit_offsets = nullptr) const {
+    const aha_corpus *h = c.handle();
+    const int dev = aha_corpus_device(h);
+    const uint64_t D = aha_corpus_n_docs(h);
+    aha_match_params p{};
+    p.struct_size = sizeof(p);
+    void *d_dho = nullptr;
+    int32_t rc = AHA_OK;
+    if (doc_hit_offsets && (rc = aha_buffer_alloc(dev, (D + 1) * sizeof(uint64_t), &d_dho)) != AHA_OK)
+      throw Error(rc, aha_last_error(nullptr));
+    uint64_t n = 0;
+    rc = aha_ac_count_batch_device(h_, aha_corpus_bytes(h), aha_corpus_doc_offsets(h), D, aha_corpus_n_bytes(h), &p,
+                                   accumulate ? AHA_COUNT_ACCUMULATE : 0u, d_key_counts, static_cast<uint64_t *>(d_dho), &n,
+                                   nullptr);
+    if (rc == AHA_OK && doc_hit_offsets) {
+      doc_hit_offsets->resize(D + 1);
+      rc = aha_buffer_download(dev, doc_hit_offsets->data(), d_dho, (D + 1) * sizeof(uint64_t));
+    }
+    if (d_dho) aha_buffer_free(dev, d_dho);
+    if (rc != AHA_OK) {
+      const char *m = aha_last_error(h_);
+      throw Error(rc, (m && *m) ? m : aha_strerror(rc));
+    }
+    return n;
+  }
+
   // AC#[](sid : Int) : String ;  AC#[](key) : Int (IndexError when absent)
   std::string operator[](int32_t id) const {
     int32_t n = aha_ac_key(h_, id, nullptr, 0);

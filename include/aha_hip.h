@@ -29,6 +29,13 @@
  * 8-byte regions above with the general post passes.
  * Prefix-filter engine (aha_ac_info_t.filter_prefix_bytes; aha_timing.engine = 5): the region pipeline's records in chunks
  * of 4 .. 32 KiB (16 bytes per hit of capacity + N/8 as above) + one bit per input byte (N/8) + 16 bytes per chunk.
+ * A count call (aha_ac_count_batch*) has no capacity and holds nothing per hit: the full-size regions of its engine (one
+ * record per input byte: 8 N bytes, 12 N with the fused character-level expansion, 20 N with its general passes) + 8 bytes
+ * per key (the events per head key) + the per-chunk and per-document words above.  Where those regions are beyond the 48 GiB
+ * bound or cannot be allocated, the call counts ranges of whole documents one after another (halved until they fit: the
+ * regions of one range + its offsets; aha_timing.repeats = the ranges before the last); only a single document whose regions
+ * do not fit goes to the two-pass engine.  With a separator filter, or where a match would take the two-pass engine, it
+ * takes that engine's counting pass: ~24 bytes per chunk of 256+ bytes, 8 per document.
  */
 #ifndef AHA_HIP_H
 #define AHA_HIP_H
@@ -354,6 +361,30 @@ int64_t aha_ac_export(const aha_ac *ac, int32_t which, void *buf, uint64_t cap_b
  * buffer, else whatever aha_ac_compile returns. */
 int64_t aha_ac_save(const aha_ac *ac, void *buf, uint64_t cap_bytes);
 int32_t aha_ac_load(const void *buf, uint64_t n_bytes, const aha_options *opts, aha_ac **out);
+
+/* ---- counts without the hit list (pure additions to ABI 8) ---------------------------------------------------------
+ * The same batch, params and results as aha_ac_match_batch, but instead of the hits: key_counts[k] = hits with value k
+ * (k < K; uint64, exactly K entries written), doc_hit_offsets (D+1 entries, optional) = the match call's offsets, *n_hits =
+ * its hit count.  key_counts == NULL: only the total and the offsets (no per-key pass).  No capacity, so no AHA_E_CAPACITY.
+ * char_offsets changes no count (the call takes the byte-offset route); a separator filter counts the filtered hits;
+ * longest != 0 is AHA_E_INVALID.  AHA_COUNT_ACCUMULATE adds into key_counts instead of overwriting it: running totals over
+ * a corpus streamed through in batches.  Errors, device validation of d_doc_offsets, threading (a call leases a scratch
+ * set) and the host entry's range-by-range uploads are those of the match entries.  A count call changes nothing a later
+ * match call of the handle depends on.  Pipeline: the match's engine with full-size event regions (document ranges where
+ * they do not fit: device scratch above); one add per EVENT (END position) into an LDS table per workgroup instead of the
+ * expansion, then the keys' output chains (aha_amd/csrc/scan_count.hip).  A separator filter -- a test per hit -- and
+ * whatever a match would give the two-pass engine take that engine's counting pass: one traversal with per-key adds, the
+ * documents' offsets noted on the way (a match with a separator filter takes the slab pipeline instead).  aha_ac_last_timing: engine = the engine that traversed, n_hits = the
+ * total, ms_write = the counting passes. */
+#define AHA_COUNT_ACCUMULATE 1u /* add into key_counts / d_key_counts instead of overwriting them */
+int32_t aha_ac_count_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc_offsets, uint64_t n_docs,
+                           const aha_match_params *params, uint32_t flags, uint64_t *key_counts /* K or NULL */,
+                           uint64_t *doc_hit_offsets /* D+1 or NULL */, uint64_t *n_hits);
+/* Device-resident form: d_ pointers are HBM on the handle's device; *n_hits is host memory; blocks until final. */
+int32_t aha_ac_count_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                                  uint64_t n_bytes, const aha_match_params *params, uint32_t flags,
+                                  uint64_t *d_key_counts /* K or NULL */, uint64_t *d_doc_hit_offsets /* or NULL */,
+                                  uint64_t *n_hits, void *stream);
 
 /* Frees the handle's device scratch (it grows with the largest batch seen and is otherwise kept for reuse). */
 int32_t aha_ac_release_scratch(aha_ac *ac);
