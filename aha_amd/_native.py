@@ -30,6 +30,7 @@ AHA_E_NOMEM = -12
 AHA_OPT_HOST_ONLY = 1
 AHA_OPT_FORCE_WIDE = 2
 AHA_COUNT_ACCUMULATE = 1
+AHA_FEED_CHARS = 1
 AHA_IMG_SLOTS, AHA_IMG_END_KEY, AHA_IMG_KEY_LN, AHA_IMG_KEY_CNT, AHA_IMG_KEY_KC = 0, 1, 2, 3, 4
 AHA_IMG_STALE_ENDS = 5
 AHA_IMG_UNIT_SLOTS, AHA_IMG_UNIT_ROOT, AHA_IMG_UNIT_END_KEY, AHA_IMG_UNIT_TABLES = 6, 7, 8, 9
@@ -139,6 +140,12 @@ SIGNATURES = {
     "aha_ac_count_batch": (_i32, [_vp, _vp, _vp, _u64, C.POINTER(aha_match_params), _u32, _vp, _vp, C.POINTER(_u64)]),
     "aha_ac_count_batch_device": (_i32, [_vp, _vp, _vp, _u64, _u64, C.POINTER(aha_match_params), _u32, _vp, _vp,
                                          C.POINTER(_u64), _vp]),
+    "aha_feed_open": (_i32, [_vp, _u32, _u32, C.POINTER(_vp)]),
+    "aha_feed_free": (None, [_vp]),
+    "aha_feed_reset": (_i32, [_vp, _u32]),
+    "aha_feed_position": (_i32, [_vp, _u32, C.POINTER(_u64), C.POINTER(_u64)]),
+    "aha_feed_match_batch": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, C.POINTER(_u64)]),
+    "aha_feed_match_batch_device": (_i32, [_vp, _vp, _vp, _vp, _u64, _u64, _vp, _u64, _vp, _vp, C.POINTER(_u64), _vp]),
 }
 
 _lib = None

@@ -522,6 +522,14 @@ class AC:
             N.lib().aha_ac_export(self._h, which, _ptr(buf), int(n))
         return buf
 
+    # -- feeds: sequences that arrive in pieces (aha_feed_*) -----------------------------------------
+    def feed(self, n_seqs, chars=False):
+        """n_seqs open sequences matched piece by piece (aha_feed_open): see Feed.  chars: offsets and bases in characters."""
+        h = C.c_void_p()
+        rc = N.lib().aha_feed_open(self._h, int(n_seqs), N.AHA_FEED_CHARS if chars else 0, C.byref(h))
+        self._check(rc)
+        return Feed(self, h, int(n_seqs), chars)
+
     def set_profiling(self, enabled=True):
         self._check(N.lib().aha_ac_set_profiling(self._h, 1 if enabled else 0))
 
@@ -538,6 +546,102 @@ class AC:
         t.struct_size = C.sizeof(t)
         self._check(N.lib().aha_ac_last_timing(self._h, C.byref(t)))
         return {f: getattr(t, f) for f, _ in t._fields_ if f != "struct_size"}
+
+
+class Feed:
+    """Sequences that arrive in pieces across calls (aha_feed_*).  Each call matches a batch of pieces -- piece d is the next
+    part of sequence seq_ids[d] -- and yields exactly the hits one plain match over the whole sequence so far would report with
+    an end inside the piece.  Offsets are relative to the piece (start may be negative: the hit began in an earlier piece);
+    piece_bases[d] is the sequence's length before it, so base + offset is absolute."""
+
+    def __init__(self, ac, handle, n_seqs, chars):
+        self._ac, self._h, self.n_seqs, self.chars = ac, handle, n_seqs, chars
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                N.lib().aha_feed_free(h)
+            except Exception:  # interpreter shutdown
+                pass
+
+    __del__ = close
+
+    def _check(self, rc):
+        if self._h is None:
+            raise AhaError(N.AHA_E_INVALID, "feed is closed")
+        self._ac._check(rc)
+
+    def reset(self, seq=None):
+        """Sequence seq (None: every sequence) starts again from length 0."""
+        self._check(N.lib().aha_feed_reset(self._h, 0xFFFFFFFF if seq is None else int(seq)))
+
+    def position(self, seq):
+        """(bytes, chars) fed to sequence seq so far (chars counted on char feeds only)."""
+        b, c = C.c_uint64(0), C.c_uint64(0)
+        self._check(N.lib().aha_feed_position(self._h, int(seq), C.byref(b), C.byref(c)))
+        return int(b.value), int(c.value)
+
+    def match_batch(self, corpus, piece_offsets, seq_ids, cap=None):
+        """Host buffers: -> (hits, piece_hit_offsets uint64[D+1], piece_bases uint64[D])."""
+        if isinstance(corpus, (bytes, bytearray)):
+            corpus = np.frombuffer(bytes(corpus), dtype=np.uint8)
+        corpus = np.ascontiguousarray(corpus, dtype=np.uint8)
+        piece_offsets = np.ascontiguousarray(piece_offsets, dtype=np.uint64)
+        seq_ids = np.ascontiguousarray(seq_ids, dtype=np.uint32)
+        D = piece_offsets.size - 1
+        if seq_ids.size != D:
+            raise ValueError("one sequence id per piece")
+        pho = np.zeros(D + 1, dtype=np.uint64)
+        bases = np.zeros(max(D, 1), dtype=np.uint64)
+        if cap is None:
+            cap = max(64, corpus.size // 8)
+        while True:
+            out = np.zeros(max(cap, 1), dtype=HIT_DTYPE)
+            n = C.c_uint64(0)
+            rc = N.lib().aha_feed_match_batch(self._h, _ptr(corpus), _ptr(piece_offsets), _ptr(seq_ids), D, _ptr(out), cap,
+                                              _ptr(pho), _ptr(bases), C.byref(n))
+            if rc == N.AHA_E_CAPACITY:
+                cap = int(n.value)
+                continue
+            self._check(rc)
+            return out[: n.value], pho, bases[:D]
+
+    def match_batch_device(self, corpus, piece_offsets, seq_ids, out, piece_hit_offsets=None, piece_bases=None, stream=None):
+        """Device-resident form on torch CUDA tensors (uint8 corpus, int64/uint64 piece offsets, int32/uint32 sequence ids,
+        int32 [cap, 3] out, int64/uint64 [D+1] / [D] or None).  Returns the hit count; raises AhaError(AHA_E_CAPACITY) with
+        .required when out is too small (the feed is then unchanged)."""
+        import torch
+
+        assert corpus.is_cuda and corpus.dtype == torch.uint8 and corpus.is_contiguous()
+        assert piece_offsets.is_cuda and piece_offsets.dtype in (torch.int64, torch.uint64) and piece_offsets.is_contiguous()
+        assert seq_ids.is_cuda and seq_ids.dtype in (torch.int32, torch.uint32) and seq_ids.is_contiguous()
+        assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous()
+        D = piece_offsets.numel() - 1
+        assert seq_ids.numel() >= D
+        for t, n in ((piece_hit_offsets, D + 1), (piece_bases, D)):
+            assert t is None or (t.is_cuda and t.dtype in (torch.int64, torch.uint64) and t.is_contiguous() and t.numel() >= n)
+        cap = out.numel() // 3
+        n = C.c_uint64(0)
+        s = stream if stream is not None else torch.cuda.current_stream(corpus.device).cuda_stream
+        rc = N.lib().aha_feed_match_batch_device(
+            self._h, corpus.data_ptr(), piece_offsets.data_ptr(), seq_ids.data_ptr(), D, corpus.numel(), out.data_ptr(), cap,
+            piece_hit_offsets.data_ptr() if piece_hit_offsets is not None else None,
+            piece_bases.data_ptr() if piece_bases is not None else None, C.byref(n), C.c_void_p(s))
+        if rc == N.AHA_E_CAPACITY:
+            e = AhaError(rc)
+            e.required = int(n.value)
+            raise e
+        self._check(rc)
+        return int(n.value)
+
+    def match(self, seq, piece):
+        """The next piece of one sequence: its hits as Hits with absolute offsets."""
+        b = _b(piece)
+        hits, _, bases = self.match_batch(np.frombuffer(b, dtype=np.uint8), np.array([0, len(b)], dtype=np.uint64),
+                                          np.array([seq], dtype=np.uint32))
+        base = int(bases[0])
+        return [Hit(int(h["start"]) + base, int(h["end"]) + base, int(h["value"])) for h in hits]
 
 
 # Aha::ACBig = ACX(Int64) (src/aha/ac.cr:9): node ids of 64 bits, the same Hit with an Int32 value (ac.cr:273) -- the

@@ -563,7 +563,7 @@ static int32_t check_docs_now(aha_ac *ac, Scratch *sc, const uint64_t *d_doc_off
 
 int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
                      uint64_t n_bytes, const aha_match_params *params, aha_hit *d_out, uint64_t cap, uint64_t *d_doc_hit_offsets,
-                     uint64_t *n_hits, void *stream, bool offsets_checked, const PackOut *pk, bool *packed) {
+                     uint64_t *n_hits, void *stream, bool offsets_checked, const PackOut *pk, bool *packed, bool quiet) {
   if (!ac || !n_hits || !d_doc_offsets) return AHA_E_INVALID;
   if (ac->device < 0) {
     tls_err = aha_strerror(AHA_E_NO_DEVICE);
@@ -577,6 +577,7 @@ int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
   int32_t rc = fill_params(ac, params, M, &longest);
   if (rc) return rc;
   if ((rc = ready_events(ac, sc))) return rc;
+  if (quiet) M.no_filter = M.no_pair = 1;  // (neither engine that keeps a history of hand-backs)
   *n_hits = 0;
   auto check_now = [&]() { return check_docs_now(ac, sc, d_doc_offsets, n_docs, n_bytes, s); };
   // The single-traversal pipelines validate on the device in front of their traversal (match_v2); every other path -- an
@@ -668,7 +669,7 @@ int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
     // a handle whose batches keep coming back from the prefix-filter engine (text dense with key starts) skips it for 2, 4,
     // .. 64 calls before it tries again: a batch that is handed back has paid for the filter and part of the walks
     const int pm = M.chars ? 1 : 0;  // (calls with char offsets keep their own count)
-    if (ac->pf_ok) {  // (calls on one handle may run side by side: the count goes down by compare-exchange, never below 0)
+    if (ac->pf_ok && !quiet) {  // (calls on one handle may run side by side: the count goes down by compare-exchange, never below 0)
       uint32_t v = ac->pf_skip[pm].load(std::memory_order_relaxed);
       while (v && !ac->pf_skip[pm].compare_exchange_weak(v, v - 1, std::memory_order_relaxed)) {
       }

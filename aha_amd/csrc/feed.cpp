@@ -1,0 +1,330 @@
+// feed.cpp -- feeds (aha_feed_*, include/aha_hip.h): sequences that arrive in pieces across calls.
+//
+// A call on D pieces (scan_feed.hip has the two facts it rests on):
+//   kfd_check + kfd_scan   validate offsets and ids; the window lengths into their offsets (one read-back: verdict, size)
+//   kfd_windows            the window batch [X_d | ctx_d | P'_d] (+ kfd_leads: leads(P_d) on char feeds)
+//   device_match, quiet    the window batch (3D documents)                     -> x_d, y_d, z_d
+//   device_match           the caller's pieces as they are, from the root       -> m_d (the engine a plain match takes)
+//   the host               total = (nX - nY) + (nM - nZ) from block totals: above cap -> AHA_E_CAPACITY, nothing committed
+//   kfd_scan + kfd_merge   piece_hit_offsets, the kept hits into the caller's buffer
+//   kfd_commit             bases, counters, the new contexts
+// Calls on one feed are serialised by its mutex; its scratch is its own.  The two matches lease one of the handle's scratch
+// sets like any call, so different feeds and plain calls on the same handle run side by side.
+#include "feed.hpp"
+
+#include "handle.hpp"
+
+using namespace ahai;
+
+struct aha_feed {
+  aha_ac *ac = nullptr;
+  uint32_t n_seqs = 0;
+  uint32_t W = 0;
+  bool chars = false;
+  std::mutex mu;
+  FeedSeq *d_seqs = nullptr;
+  uint8_t *d_ctx = nullptr;
+  uint32_t stamp = 0;
+  // grow-only scratch: 0 verdict + window size, 1 window bytes, 2 window offsets, 3 window hit offsets, 4 window hits,
+  // 5 main hit offsets, 6 main hits, 7 piece hit offsets, 8 leads(ctx), 9 leads(P); 10 .. 15 the host entry's staging
+  // (corpus, offsets, ids, hits, piece hit offsets, bases)
+  Buf buf[16];
+  uint64_t *h_pin = nullptr;  // pinned: read-backs
+  hipStream_t hs = nullptr;   // the host entry's stream (and position / reset)
+};
+
+namespace {
+enum { kMisc, kWin, kWoff, kWdho, kWhits, kMdho, kMhits, kPho, kLeadCtx, kLeadP, kHCorpus, kHOff, kHIds, kHOut, kHPho, kHBases };
+
+void *reserve(aha_feed *f, int i, size_t bytes) {
+  Buf &b = f->buf[i];
+  bytes = std::max<size_t>(bytes, 16);
+  if (b.bytes >= bytes) return b.p;
+  const size_t grown = std::max(bytes, b.bytes + b.bytes / 4);
+  if (b.p) (void)hipFree(b.p);
+  b = Buf();
+  if (hipMalloc(&b.p, grown) != hipSuccess) {
+    (void)hipGetLastError();
+    b.p = nullptr;
+    return nullptr;
+  }
+  b.bytes = grown;
+  return b.p;
+}
+
+int32_t no_memory(const char *what) {
+  tls_err = std::string("hipMalloc failed for the feed's ") + what;
+  return AHA_E_HIP;
+}
+
+// the part of a call before anything is written for the caller: checks, windows, both matches.  *total = the call's hits;
+// AHA_E_CAPACITY when they are more than cap.
+int32_t feed_prepare(aha_feed *f, Scratch *sc, FeedArgs &F, uint64_t cap, hipStream_t s, uint64_t *total) {
+  aha_ac *ac = f->ac;
+  const uint64_t D = F.D;
+  if (++f->stamp == 0) f->stamp = 1;  // (a stamp comes back after 2^32 calls; a sequence must be named in neither)
+  F.stamp = f->stamp;
+  F.seqs = f->d_seqs;
+  F.ctx = f->d_ctx;
+  F.n_seqs = f->n_seqs;
+  F.W = f->W;
+  F.chars = f->chars ? 1 : 0;
+  F.max_piece = (1ull << 31) - std::max<uint64_t>(ac->aut.max_key_len, 1);
+  uint64_t *misc = (uint64_t *)reserve(f, kMisc, 16);
+  F.woff = (uint64_t *)reserve(f, kWoff, (3 * D + 1) * 8);
+  F.lead_ctx = (uint64_t *)reserve(f, kLeadCtx, D * 8);
+  F.lead_p = (unsigned long long *)reserve(f, kLeadP, D * 8);
+  uint64_t *wdho = (uint64_t *)reserve(f, kWdho, (3 * D + 1) * 8);
+  uint64_t *mdho = (uint64_t *)reserve(f, kMdho, (D + 1) * 8);
+  if (!misc || !F.woff || !F.lead_ctx || !F.lead_p || !wdho || !mdho) return no_memory("offsets");
+  F.verdict = (uint32_t *)misc;
+  F.win_total = misc + 1;
+  F.wdho = wdho;
+  F.mdho = mdho;
+  HIPCHK(ac, hipMemsetAsync(F.verdict, 0, 4, s));
+  feed_launch_check(F, s);
+  HIPCHK(ac, hipGetLastError());
+  HIPCHK(ac, hipMemcpyAsync(f->h_pin, misc, 16, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  const uint32_t bad = (uint32_t)f->h_pin[0];
+  if (bad & 1u) {
+    tls_err = "feed: need piece_offsets[0] = 0, ascending, piece_offsets[n_pieces] = n_bytes, seq_ids below n_seqs and each once";
+    return AHA_E_INVALID;
+  }
+  if (bad & 2u) {
+    tls_err = "feed: a piece must be shorter than 2^31 bytes minus the longest key";
+    return AHA_E_TOO_LONG;
+  }
+  const uint64_t n_win = f->h_pin[1];
+  F.win = (uint8_t *)reserve(f, kWin, n_win + 64);
+  if (!F.win) return no_memory("windows");
+  if (F.chars && D) HIPCHK(ac, hipMemsetAsync(F.lead_p, 0, D * 8, s));
+  feed_launch_windows(F, s);
+  HIPCHK(ac, hipGetLastError());
+
+  aha_match_params p{};
+  p.struct_size = sizeof(p);
+  p.char_offsets = F.chars;
+  bool packed = false;
+  // the window batch: at most 4 W bytes per piece; its hit scratch grows to what it needed once
+  uint64_t n_w = 0;
+  for (int attempt = 0;; attempt++) {
+    const uint64_t cap_w = f->buf[kWhits].bytes / sizeof(aha_hit);
+    int32_t rc = device_match(ac, sc, F.win, F.woff, 3 * D, n_win, &p, cap_w ? (aha_hit *)f->buf[kWhits].p : nullptr, cap_w, wdho,
+                              &n_w, s, true, nullptr, &packed, true);
+    if (rc == AHA_E_CAPACITY && attempt == 0) {
+      if (!reserve(f, kWhits, std::max<uint64_t>(n_w, 1024) * sizeof(aha_hit))) return no_memory("window hits");
+      continue;
+    }
+    if (rc) return rc;
+    break;
+  }
+  F.whits = (const int32_t *)f->buf[kWhits].p;
+  uint64_t nz = 0, nx = 0, ny = 0;
+  if (D) {
+    HIPCHK(ac, hipMemcpyAsync(f->h_pin, wdho + D, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(ac, hipMemcpyAsync(f->h_pin + 1, wdho + 2 * D, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(ac, hipStreamSynchronize(s));
+    nx = f->h_pin[0];
+    ny = f->h_pin[1] - nx;
+    nz = n_w - f->h_pin[1];
+  }
+  // the main pass: what the caller's buffer can take plus the hits it drops
+  const uint64_t cap_m = cap + nz;
+  aha_hit *mh = cap_m ? (aha_hit *)reserve(f, kMhits, cap_m * sizeof(aha_hit)) : nullptr;
+  if (cap_m && !mh) return no_memory("hits");
+  uint64_t n_m = 0;
+  int32_t rc = device_match(ac, sc, F.text, F.off, D, F.n_bytes, &p, mh, cap_m, mdho, &n_m, s, true, nullptr, &packed);
+  if (rc && rc != AHA_E_CAPACITY) return rc;
+  F.mhits = (const int32_t *)mh;
+  *total = (nx - ny) + (n_m - nz);
+  F.total = *total;
+  if (rc == AHA_E_CAPACITY || *total > cap) {
+    tls_err = "output buffer too small";
+    return AHA_E_CAPACITY;
+  }
+  return AHA_OK;
+}
+
+// the part that writes: the caller's hits and offsets, then the feed's own state
+int32_t feed_finish(aha_feed *f, FeedArgs &F, hipStream_t s) {
+  if (!F.pho) {
+    F.pho = (uint64_t *)reserve(f, kPho, (F.D + 1) * 8);
+    if (!F.pho) return no_memory("piece hit offsets");
+  }
+  feed_launch_merge(F, s);
+  feed_launch_commit(F, s);
+  HIPCHK(f->ac, hipGetLastError());
+  HIPCHK(f->ac, hipStreamSynchronize(s));
+  return AHA_OK;
+}
+
+bool bad_feed(const aha_feed *f) { return !f || !f->ac || f->ac->device < 0; }
+}  // namespace
+
+int32_t aha_feed_open(aha_ac *ac, uint32_t n_seqs, uint32_t flags, aha_feed **out) {
+  if (!ac || !out || n_seqs == 0 || (flags & ~AHA_FEED_CHARS)) return AHA_E_INVALID;
+  *out = nullptr;
+  if (ac->device < 0) {
+    tls_err = aha_strerror(AHA_E_NO_DEVICE);
+    return AHA_E_NO_DEVICE;
+  }
+  DeviceGuard g(ac->device);
+  std::unique_ptr<aha_feed> f(new (std::nothrow) aha_feed());
+  if (!f) return AHA_E_NOMEM;
+  f->ac = ac;
+  f->n_seqs = n_seqs;
+  f->W = ac->aut.max_key_len ? ac->aut.max_key_len - 1 : 0;
+  f->chars = (flags & AHA_FEED_CHARS) != 0;
+  const size_t ctx_bytes = std::max<size_t>(2ull * n_seqs * f->W, 16);
+  int32_t rc = AHA_OK;
+  if (hipMalloc((void **)&f->d_seqs, (size_t)n_seqs * sizeof(FeedSeq)) != hipSuccess ||
+      hipMalloc((void **)&f->d_ctx, ctx_bytes) != hipSuccess || hipHostMalloc((void **)&f->h_pin, 32) != hipSuccess ||
+      hipStreamCreateWithFlags(&f->hs, hipStreamNonBlocking) != hipSuccess) {
+    tls_err = "aha_feed_open: device allocation failed";
+    rc = AHA_E_HIP;
+  } else if (hipMemsetAsync(f->d_seqs, 0, (size_t)n_seqs * sizeof(FeedSeq), f->hs) != hipSuccess ||
+             hipStreamSynchronize(f->hs) != hipSuccess) {
+    tls_err = "aha_feed_open: clearing the sequences failed";
+    rc = AHA_E_HIP;
+  }
+  if (rc) {
+    aha_feed_free(f.release());
+    return rc;
+  }
+  *out = f.release();
+  return AHA_OK;
+}
+
+void aha_feed_free(aha_feed *f) {
+  if (!f) return;
+  {
+    std::lock_guard<std::mutex> lk(f->mu);  // (waits for a call in flight)
+    DeviceGuard g(f->ac->device);
+    for (auto &b : f->buf)
+      if (b.p) (void)hipFree(b.p);
+    if (f->d_seqs) (void)hipFree(f->d_seqs);
+    if (f->d_ctx) (void)hipFree(f->d_ctx);
+    if (f->h_pin) (void)hipHostFree(f->h_pin);
+    if (f->hs) (void)hipStreamDestroy(f->hs);
+  }
+  delete f;
+}
+
+int32_t aha_feed_reset(aha_feed *f, uint32_t seq) {
+  if (!f) return AHA_E_INVALID;
+  if (seq != UINT32_MAX && seq >= f->n_seqs) return AHA_E_INVALID;
+  std::lock_guard<std::mutex> lk(f->mu);
+  aha_ac *ac = f->ac;
+  DeviceGuard g(ac->device);
+  // a sequence of length 0 has an empty context: only the counters are cleared (a stamp of 0 is never a call's)
+  if (seq == UINT32_MAX)
+    HIPCHK(ac, hipMemsetAsync(f->d_seqs, 0, (size_t)f->n_seqs * sizeof(FeedSeq), f->hs));
+  else
+    HIPCHK(ac, hipMemsetAsync(f->d_seqs + seq, 0, 2 * sizeof(uint64_t), f->hs));
+  HIPCHK(ac, hipStreamSynchronize(f->hs));
+  return AHA_OK;
+}
+
+int32_t aha_feed_position(const aha_feed *cf, uint32_t seq, uint64_t *bytes, uint64_t *chars) {
+  aha_feed *f = const_cast<aha_feed *>(cf);
+  if (!f || seq >= f->n_seqs) return AHA_E_INVALID;
+  std::lock_guard<std::mutex> lk(f->mu);
+  aha_ac *ac = f->ac;
+  DeviceGuard g(ac->device);
+  HIPCHK(ac, hipMemcpyAsync(f->h_pin, f->d_seqs + seq, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, f->hs));
+  HIPCHK(ac, hipStreamSynchronize(f->hs));
+  if (bytes) *bytes = f->h_pin[0];
+  if (chars) *chars = f->h_pin[1];
+  return AHA_OK;
+}
+
+int32_t aha_feed_match_batch_device(aha_feed *f, const uint8_t *d_corpus, const uint64_t *d_piece_offsets,
+                                    const uint32_t *d_seq_ids, uint64_t n_pieces, uint64_t n_bytes, aha_hit *d_out,
+                                    uint64_t cap, uint64_t *d_piece_hit_offsets, uint64_t *d_piece_bases, uint64_t *n_hits,
+                                    void *stream) {
+  if (!f || !n_hits || !d_piece_offsets || (n_pieces && !d_seq_ids) || (cap && !d_out) || (n_bytes && !d_corpus))
+    return AHA_E_INVALID;
+  if (bad_feed(f)) return AHA_E_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(f->mu);
+  DeviceGuard g(f->ac->device);
+  Lease lease(f->ac);
+  hipStream_t s = (hipStream_t)stream;
+  FeedArgs F{};
+  F.text = d_corpus;
+  F.off = d_piece_offsets;
+  F.ids = d_seq_ids;
+  F.D = n_pieces;
+  F.n_bytes = n_bytes;
+  F.out = reinterpret_cast<int32_t *>(d_out);
+  F.pho = d_piece_hit_offsets;
+  F.bases = d_piece_bases;
+  uint64_t total = 0;
+  *n_hits = 0;
+  int32_t rc = feed_prepare(f, lease.get(), F, cap, s, &total);
+  if (rc == AHA_E_CAPACITY) *n_hits = total;
+  if (rc) return rc;
+  if ((rc = feed_finish(f, F, s))) return rc;
+  *n_hits = total;
+  return AHA_OK;
+}
+
+int32_t aha_feed_match_batch(aha_feed *f, const uint8_t *corpus, const uint64_t *piece_offsets, const uint32_t *seq_ids,
+                             uint64_t n_pieces, aha_hit *out, uint64_t cap, uint64_t *piece_hit_offsets,
+                             uint64_t *piece_bases, uint64_t *n_hits) {
+  if (!f || !n_hits || !piece_offsets || (n_pieces && !seq_ids) || (cap && !out)) return AHA_E_INVALID;
+  if (bad_feed(f)) return AHA_E_NO_DEVICE;
+  aha_ac *ac = f->ac;
+  // the checks kfd_check makes, on the host
+  if (piece_offsets[0] != 0) return AHA_E_INVALID;
+  const uint64_t max_piece = (1ull << 31) - std::max<uint64_t>(ac->aut.max_key_len, 1);
+  std::vector<uint8_t> seen;
+  try {
+    seen.assign(f->n_seqs, 0);
+  } catch (...) {
+    return AHA_E_NOMEM;
+  }
+  for (uint64_t d = 0; d < n_pieces; d++) {
+    if (piece_offsets[d + 1] < piece_offsets[d] || seq_ids[d] >= f->n_seqs || seen[seq_ids[d]]++) return AHA_E_INVALID;
+    if (piece_offsets[d + 1] - piece_offsets[d] >= max_piece) return AHA_E_TOO_LONG;
+  }
+  const uint64_t n_bytes = piece_offsets[n_pieces];
+  if (n_bytes && !corpus) return AHA_E_INVALID;
+  std::lock_guard<std::mutex> lk(f->mu);
+  DeviceGuard g(ac->device);
+  Lease lease(ac);
+  hipStream_t s = f->hs;
+  const uint64_t D = n_pieces;
+  uint8_t *d_corpus = (uint8_t *)reserve(f, kHCorpus, n_bytes + 64);
+  uint64_t *d_off = (uint64_t *)reserve(f, kHOff, (D + 1) * 8);
+  uint32_t *d_ids = (uint32_t *)reserve(f, kHIds, D * 4);
+  uint64_t *d_pho = (uint64_t *)reserve(f, kHPho, (D + 1) * 8);
+  uint64_t *d_bases = (uint64_t *)reserve(f, kHBases, D * 8);
+  if (!d_corpus || !d_off || !d_ids || !d_pho || !d_bases) return no_memory("staging buffers");
+  if (n_bytes) HIPCHK(ac, hipMemcpyAsync(d_corpus, corpus, n_bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(ac, hipMemcpyAsync(d_off, piece_offsets, (D + 1) * 8, hipMemcpyHostToDevice, s));
+  if (D) HIPCHK(ac, hipMemcpyAsync(d_ids, seq_ids, D * 4, hipMemcpyHostToDevice, s));
+  FeedArgs F{};
+  F.text = d_corpus;
+  F.off = d_off;
+  F.ids = d_ids;
+  F.D = D;
+  F.n_bytes = n_bytes;
+  F.pho = d_pho;
+  F.bases = d_bases;
+  uint64_t total = 0;
+  *n_hits = 0;
+  int32_t rc = feed_prepare(f, lease.get(), F, cap, s, &total);
+  if (rc == AHA_E_CAPACITY) *n_hits = total;
+  if (rc) return rc;
+  aha_hit *d_out = (aha_hit *)reserve(f, kHOut, total * sizeof(aha_hit));
+  if (!d_out) return no_memory("hits");
+  F.out = reinterpret_cast<int32_t *>(d_out);
+  if ((rc = feed_finish(f, F, s))) return rc;
+  if (total) HIPCHK(ac, hipMemcpyAsync(out, d_out, total * sizeof(aha_hit), hipMemcpyDeviceToHost, s));
+  if (piece_hit_offsets) HIPCHK(ac, hipMemcpyAsync(piece_hit_offsets, d_pho, (D + 1) * 8, hipMemcpyDeviceToHost, s));
+  if (piece_bases && D) HIPCHK(ac, hipMemcpyAsync(piece_bases, d_bases, D * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  *n_hits = total;
+  return AHA_OK;
+}

@@ -1,0 +1,46 @@
+// feed.hpp -- what feed.cpp (the feed entry points of the C ABI) and scan_feed.hip (its kernels) share.  Library-internal.
+#pragma once
+#include <cstdint>
+
+namespace aha {
+// one open sequence of a feed, on the device (24 bytes)
+struct FeedSeq {
+  unsigned long long bytes;  // bytes consumed since open / reset
+  unsigned long long chars;  // lead bytes among them (char feeds)
+  uint32_t stamp;            // the last call that named the sequence (kfd_check: duplicates within a call)
+  uint32_t bank;             // which of the two context banks holds its last min(W, bytes) bytes
+};
+
+// the arguments every feed kernel takes (by value)
+struct FeedArgs {
+  const uint8_t *text;         // the caller's pieces
+  const uint64_t *off;         // [D+1] piece offsets
+  const uint32_t *ids;         // [D] sequence ids
+  uint64_t D, n_bytes, n_seqs;
+  uint32_t W;                  // max(Lmax - 1, 0)
+  uint32_t stamp;              // this call's stamp (never 0)
+  uint64_t max_piece;          // a piece must be shorter than this
+  int32_t chars;
+  FeedSeq *seqs;               // [n_seqs]
+  uint8_t *ctx;                // [2][n_seqs][W]
+  uint32_t *verdict;           // [1]: bit 0 invalid offsets or ids, bit 1 a piece too long
+  uint64_t *win_total;         // [1]: bytes of the window batch
+  uint8_t *win;                // the window batch [X_0..X_{D-1} | ctx_0.. | P'_0..]
+  uint64_t *woff;              // [3D+1] its document offsets
+  const uint64_t *wdho;        // [3D+1] its per-document hit offsets
+  const int32_t *whits;        // its hits (3 words each)
+  const uint64_t *mdho;        // [D+1] the main pass's per-document hit offsets
+  const int32_t *mhits;        // its hits
+  uint64_t *lead_ctx;          // [D] leads(ctx_d) (char feeds)
+  unsigned long long *lead_p;  // [D] leads(P_d) (char feeds)
+  uint64_t *pho;               // [D+1] hits per piece, scanned (the caller's piece_hit_offsets or feed scratch)
+  uint64_t *bases;             // [D] the sequence's length before the piece, or null
+  int32_t *out;                // the caller's hits
+  uint64_t total;              // hits of the call
+};
+
+void feed_launch_check(const FeedArgs &F, void *stream);    // kfd_check, then kfd_scan of the window lengths
+void feed_launch_windows(const FeedArgs &F, void *stream);  // kfd_windows (+ kfd_leads on char feeds)
+void feed_launch_merge(const FeedArgs &F, void *stream);    // kfd_scan of the hits per piece, kfd_merge
+void feed_launch_commit(const FeedArgs &F, void *stream);   // kfd_commit: bases, counters, the new contexts
+}  // namespace aha

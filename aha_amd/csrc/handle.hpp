@@ -240,10 +240,12 @@ struct PackOut {
   uint64_t cap_words;
   uint64_t *d_n_words;
 };
-// one device-resident batch through whichever engine takes it (retries, hand-backs, the two-pass engine as the last resort)
+// one device-resident batch through whichever engine takes it (retries, hand-backs, the two-pass engine as the last resort).
+// quiet: neither the prefix-filter nor the pair engine, so the handle's back-off state is neither read nor written (a feed's
+// window batch, feed.cpp: an internal batch must not change which engine the caller's next call takes)
 int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
                      uint64_t n_bytes, const aha_match_params *params, aha_hit *d_out, uint64_t cap, uint64_t *d_doc_hit_offsets,
-                     uint64_t *n_hits, void *stream, bool offsets_checked, const PackOut *pk, bool *packed);
+                     uint64_t *n_hits, void *stream, bool offsets_checked, const PackOut *pk, bool *packed, bool quiet = false);
 // one device-resident batch counted (aha_ac_count_batch_device): the match's engine, the count passes instead of the expansion
 int32_t device_count(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
                      uint64_t n_bytes, const aha_match_params *params, uint32_t flags, uint64_t *d_key_counts,

@@ -1,0 +1,265 @@
+// scan_feed.hip -- the feed path (aha_feed_match_batch*): sequences that arrive in pieces across calls.
+//
+// The state after a byte is the longest suffix of the text that is a trie path, so it -- and what is emitted there -- depends
+// only on the last Lmax bytes.  With W = max(Lmax - 1, 0) and ctx = the last min(W, consumed) bytes of the sequence, the hits
+// of a piece P whose end lies in P are:
+//   boundary hits  the hits of X = ctx || P[0 .. min(W, |P|)) matched alone, without its first y (y = the hits of ctx alone),
+//                  shifted by |ctx| (or leads(ctx) on a char feed);
+//   main hits      the hits of P matched alone, without its first z (z = the hits of P[0 .. min(W, |P|)) alone).
+// Both selections are by count: each document's hits are in end order, so what is dropped is a prefix.  The matches themselves
+// are plain device_match calls (engine.cpp); the kernels here only check, cut the windows, merge and commit:
+//   kfd_check    the piece offsets and sequence ids, before anything is indexed with them (a verdict word the host reads)
+//   kfd_scan     one block: the window lengths into their offsets, or the hits per piece into piece_hit_offsets
+//   kfd_windows  the window batch [X_0..X_{D-1} | ctx_0.. | P'_0..] and leads(ctx)
+//   kfd_leads    leads(P) per piece (char feeds), a reduction over the pieces
+//   kfd_merge    the kept hits into the caller's buffer, rebased; one thread per 4 output hits (3 x 16-byte stores)
+//   kfd_commit   after success only: bases, the counters, the new contexts (written to the other bank)
+#include <hip/hip_runtime.h>
+
+#include "feed.hpp"
+
+namespace aha {
+namespace {
+
+constexpr int kFdThreads = 256;
+constexpr int kFdScanThreads = 1024;
+constexpr uint64_t kFdSpan = 64 * 1024;  // kfd_leads: bytes per workgroup trip
+
+__device__ __forceinline__ uint32_t is_lead(uint8_t b) { return (b & 0xC0u) != 0x80u ? 1u : 0u; }
+
+__global__ void kfd_check(FeedArgs F) {
+  uint32_t bad = 0;
+  for (uint64_t d = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; d <= F.D; d += (uint64_t)gridDim.x * blockDim.x) {
+    if (d == 0 && F.off[0] != 0) bad |= 1u;
+    if (d == F.D) {
+      if (F.off[F.D] != F.n_bytes) bad |= 1u;
+      continue;
+    }
+    const uint64_t a = F.off[d], b = F.off[d + 1];
+    if (b < a)
+      bad |= 1u;
+    else if (b - a >= F.max_piece)
+      bad |= 2u;
+    const uint32_t id = F.ids[d];
+    if (id >= F.n_seqs)
+      bad |= 1u;
+    else if (atomicExch(&F.seqs[id].stamp, F.stamp) == F.stamp)  // named twice in this call
+      bad |= 1u;
+  }
+  if (bad) atomicOr(F.verdict, bad);
+}
+
+// per-piece quantities of the two scans
+__device__ __forceinline__ uint64_t win_len(const FeedArgs &F, uint64_t i) {
+  const uint64_t part = i / F.D, d = i - part * F.D;
+  const uint64_t lc = min((uint64_t)F.W, F.seqs[F.ids[d]].bytes);
+  const uint64_t lp = min((uint64_t)F.W, F.off[d + 1] - F.off[d]);
+  return part == 0 ? lc + lp : (part == 1 ? lc : lp);
+}
+__device__ __forceinline__ uint64_t kept_hits(const FeedArgs &F, uint64_t d) {
+  const uint64_t D = F.D;
+  const uint64_t x = F.wdho[d + 1] - F.wdho[d], y = F.wdho[D + d + 1] - F.wdho[D + d];
+  const uint64_t z = F.wdho[2 * D + d + 1] - F.wdho[2 * D + d], m = F.mdho[d + 1] - F.mdho[d];
+  return (x - y) + (m - z);
+}
+
+// one block of kFdScanThreads: exclusive scan of n per-piece values into out[0..n], out[n] = the total.  Each thread takes a
+// contiguous run; the run sums are scanned in LDS.
+template <int kMode>
+__global__ void __launch_bounds__(kFdScanThreads) kfd_scan(FeedArgs F) {
+  __shared__ uint64_t s[kFdScanThreads];
+  if (*F.verdict) return;
+  const uint64_t n = kMode == 0 ? 3 * F.D : F.D;
+  uint64_t *out = kMode == 0 ? F.woff : F.pho;
+  const uint64_t per = (n + kFdScanThreads - 1) / kFdScanThreads;
+  const uint64_t i0 = min(n, threadIdx.x * per), i1 = min(n, i0 + per);
+  uint64_t mine = 0;
+  for (uint64_t i = i0; i < i1; i++) mine += kMode == 0 ? win_len(F, i) : kept_hits(F, i);
+  s[threadIdx.x] = mine;
+  __syncthreads();
+  for (int k = 1; k < kFdScanThreads; k <<= 1) {
+    const uint64_t v = threadIdx.x >= (unsigned)k ? s[threadIdx.x - k] : 0;
+    __syncthreads();
+    s[threadIdx.x] += v;
+    __syncthreads();
+  }
+  uint64_t run = s[threadIdx.x] - mine;
+  for (uint64_t i = i0; i < i1; i++) {
+    out[i] = run;
+    run += kMode == 0 ? win_len(F, i) : kept_hits(F, i);
+  }
+  if (threadIdx.x == kFdScanThreads - 1) {
+    out[n] = s[threadIdx.x];
+    if (kMode == 0) *F.win_total = s[threadIdx.x];
+  }
+}
+
+__global__ void __launch_bounds__(kFdThreads) kfd_windows(FeedArgs F) {
+  __shared__ uint32_t s_leads;
+  const uint64_t D = F.D;
+  for (uint64_t d = blockIdx.x; d < D; d += gridDim.x) {
+    const uint32_t id = F.ids[d];
+    const FeedSeq sq = F.seqs[id];
+    const uint32_t lc = (uint32_t)min((uint64_t)F.W, sq.bytes);
+    const uint32_t lp = (uint32_t)min((uint64_t)F.W, F.off[d + 1] - F.off[d]);
+    const uint8_t *c = F.ctx + ((uint64_t)sq.bank * F.n_seqs + id) * F.W;
+    const uint8_t *p = F.text + F.off[d];
+    uint8_t *x = F.win + F.woff[d], *cw = F.win + F.woff[D + d], *pw = F.win + F.woff[2 * D + d];
+    if (threadIdx.x == 0) s_leads = 0;
+    __syncthreads();
+    uint32_t leads = 0;
+    for (uint32_t i = threadIdx.x; i < lc; i += kFdThreads) {
+      const uint8_t b = c[i];
+      x[i] = b;
+      cw[i] = b;
+      leads += is_lead(b);
+    }
+    for (uint32_t i = threadIdx.x; i < lp; i += kFdThreads) {
+      const uint8_t b = p[i];
+      x[lc + i] = b;
+      pw[i] = b;
+    }
+    if (F.chars) {
+      if (leads) atomicAdd(&s_leads, leads);
+      __syncthreads();
+      if (threadIdx.x == 0) F.lead_ctx[d] = s_leads;
+    }
+    __syncthreads();
+  }
+}
+
+// leads(P_d) += the lead bytes of the piece within each 64 KiB span (lead_p cleared by the host)
+__global__ void __launch_bounds__(kFdThreads) kfd_leads(FeedArgs F) {
+  __shared__ uint32_t s_cnt;
+  for (uint64_t a0 = blockIdx.x * kFdSpan; a0 < F.n_bytes; a0 += (uint64_t)gridDim.x * kFdSpan) {
+    const uint64_t b = min(F.n_bytes, a0 + kFdSpan);
+    uint64_t lo = 0, hi = F.D - 1;  // the last piece that starts at or before a0
+    while (lo < hi) {
+      const uint64_t mid = (lo + hi + 1) / 2;
+      if (F.off[mid] <= a0)
+        lo = mid;
+      else
+        hi = mid - 1;
+    }
+    uint64_t d = lo, a = a0;
+    while (a < b) {
+      while (F.off[d + 1] <= a) d++;  // (empty pieces)
+      const uint64_t e = min(b, F.off[d + 1]);
+      if (threadIdx.x == 0) s_cnt = 0;
+      __syncthreads();
+      uint32_t n = 0;
+      for (uint64_t i = a + threadIdx.x; i < e; i += kFdThreads) n += is_lead(F.text[i]);
+      if (n) atomicAdd(&s_cnt, n);
+      __syncthreads();
+      if (threadIdx.x == 0 && s_cnt) atomicAdd(&F.lead_p[d], (unsigned long long)s_cnt);
+      __syncthreads();
+      a = e;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kFdThreads) kfd_merge(FeedArgs F) {
+  const uint64_t D = F.D;
+  const uint64_t i0 = (blockIdx.x * (uint64_t)kFdThreads + threadIdx.x) * 4;
+  if (i0 >= F.total) return;
+  uint64_t lo = 0, hi = D - 1;  // the last piece whose first output hit is at or before i0
+  while (lo < hi) {
+    const uint64_t mid = (lo + hi + 1) / 2;
+    if (F.pho[mid] <= i0)
+      lo = mid;
+    else
+      hi = mid - 1;
+  }
+  uint64_t d = lo;
+  int32_t h[12];
+  const int n = (int)min((uint64_t)4, F.total - i0);
+  for (int k = 0; k < n; k++) {
+    const uint64_t i = i0 + k;
+    while (F.pho[d + 1] <= i) d++;
+    const uint64_t j = i - F.pho[d];
+    const uint64_t y = F.wdho[D + d + 1] - F.wdho[D + d];
+    const uint64_t xy = (F.wdho[d + 1] - F.wdho[d]) - y;
+    const int32_t *src;
+    int32_t sh = 0;
+    if (j < xy) {  // a boundary hit: X's offsets less the context
+      src = F.whits + 3 * (F.wdho[d] + y + j);
+      sh = F.chars ? (int32_t)F.lead_ctx[d] : (int32_t)(F.woff[D + d + 1] - F.woff[D + d]);
+    } else {  // a main hit: already relative to the piece
+      const uint64_t z = F.wdho[2 * D + d + 1] - F.wdho[2 * D + d];
+      src = F.mhits + 3 * (F.mdho[d] + z + (j - xy));
+    }
+    h[3 * k] = src[0] - sh;
+    h[3 * k + 1] = src[1] - sh;
+    h[3 * k + 2] = src[2];
+  }
+  int32_t *o = F.out + 3 * i0;
+  if (n == 4 && (reinterpret_cast<uintptr_t>(o) & 15u) == 0) {
+    uint4 *o4 = reinterpret_cast<uint4 *>(o);
+    o4[0] = make_uint4(h[0], h[1], h[2], h[3]);
+    o4[1] = make_uint4(h[4], h[5], h[6], h[7]);
+    o4[2] = make_uint4(h[8], h[9], h[10], h[11]);
+  } else {
+    for (int k = 0; k < 3 * n; k++) o[k] = h[k];
+  }
+}
+
+__global__ void __launch_bounds__(kFdThreads) kfd_commit(FeedArgs F) {
+  __shared__ FeedSeq s_sq;
+  for (uint64_t d = blockIdx.x; d < F.D; d += gridDim.x) {
+    const uint32_t id = F.ids[d];
+    if (threadIdx.x == 0) s_sq = F.seqs[id];
+    __syncthreads();
+    const FeedSeq sq = s_sq;
+    const uint64_t L = F.off[d + 1] - F.off[d];
+    const uint64_t lc = min((uint64_t)F.W, sq.bytes), ln = min((uint64_t)F.W, sq.bytes + L);
+    const uint64_t skip = lc + L - ln;  // the new context: the last ln bytes of old context || P
+    const uint8_t *old = F.ctx + ((uint64_t)sq.bank * F.n_seqs + id) * F.W;
+    uint8_t *nw = F.ctx + ((uint64_t)(1u - sq.bank) * F.n_seqs + id) * F.W;
+    const uint8_t *p = F.text + F.off[d];
+    for (uint64_t i = threadIdx.x; i < ln; i += kFdThreads) {
+      const uint64_t src = skip + i;
+      nw[i] = src < lc ? old[src] : p[src - lc];
+    }
+    if (threadIdx.x == 0) {
+      if (F.bases) F.bases[d] = F.chars ? sq.chars : sq.bytes;
+      FeedSeq ns = sq;
+      ns.bytes = sq.bytes + L;
+      if (F.chars) ns.chars = sq.chars + F.lead_p[d];
+      ns.bank = 1u - sq.bank;
+      F.seqs[id] = ns;
+    }
+    __syncthreads();
+  }
+}
+
+uint32_t grid_for(uint64_t units, uint64_t per_block, uint32_t cap) {
+  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((units + per_block - 1) / per_block, cap));
+}
+
+}  // namespace
+
+void feed_launch_check(const FeedArgs &F, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(kfd_check, dim3(grid_for(F.D + 1, kFdThreads, 1024)), dim3(kFdThreads), 0, s, F);
+  hipLaunchKernelGGL(kfd_scan<0>, dim3(1), dim3(kFdScanThreads), 0, s, F);
+}
+
+void feed_launch_windows(const FeedArgs &F, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(kfd_windows, dim3(grid_for(F.D, 1, 4096)), dim3(kFdThreads), 0, s, F);
+  if (F.chars && F.n_bytes) hipLaunchKernelGGL(kfd_leads, dim3(grid_for(F.n_bytes, kFdSpan, 4096)), dim3(kFdThreads), 0, s, F);
+}
+
+void feed_launch_merge(const FeedArgs &F, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(kfd_scan<1>, dim3(1), dim3(kFdScanThreads), 0, s, F);
+  if (F.total) {
+    const uint64_t groups = (F.total + 3) / 4;
+    hipLaunchKernelGGL(kfd_merge, dim3((uint32_t)((groups + kFdThreads - 1) / kFdThreads)), dim3(kFdThreads), 0, s, F);
+  }
+}
+
+void feed_launch_commit(const FeedArgs &F, void *stream) {
+  hipLaunchKernelGGL(kfd_commit, dim3(grid_for(F.D, 1, 4096)), dim3(kFdThreads), 0, (hipStream_t)stream, F);
+}
+}  // namespace aha

@@ -180,6 +180,20 @@ lib LibAhaHip
   fun aha_ac_count_batch_device(ac : Ac, d_corpus : UInt8*, d_doc_offsets : UInt64*, n_docs : UInt64, n_bytes : UInt64,
                                 params : MatchParams*, flags : UInt32, d_key_counts : UInt64*, d_doc_hit_offsets : UInt64*,
                                 n_hits : UInt64*, stream : Void*) : Int32
+  # feeds: sequences that arrive in pieces across calls (offsets relative to the piece; FEED_CHARS: in characters)
+  type Feed = Void*
+  FEED_CHARS = 1_u32
+  fun aha_feed_open(ac : Ac, n_seqs : UInt32, flags : UInt32, out : Feed*) : Int32
+  fun aha_feed_free(f : Feed) : Void
+  fun aha_feed_reset(f : Feed, seq : UInt32) : Int32
+  fun aha_feed_position(f : Feed, seq : UInt32, bytes : UInt64*, chars : UInt64*) : Int32
+  fun aha_feed_match_batch(f : Feed, corpus : UInt8*, piece_offsets : UInt64*, seq_ids : UInt32*, n_pieces : UInt64,
+                           out : Hit*, cap : UInt64, piece_hit_offsets : UInt64*, piece_bases : UInt64*,
+                           n_hits : UInt64*) : Int32
+  fun aha_feed_match_batch_device(f : Feed, d_corpus : UInt8*, d_piece_offsets : UInt64*, d_seq_ids : UInt32*,
+                                  n_pieces : UInt64, n_bytes : UInt64, d_out : Hit*, cap : UInt64,
+                                  d_piece_hit_offsets : UInt64*, d_piece_bases : UInt64*, n_hits : UInt64*,
+                                  stream : Void*) : Int32
   fun aha_buffer_alloc(device : Int32, bytes : UInt64, d_ptr : Void**) : Int32
   fun aha_buffer_free(device : Int32, d_ptr : Void*) : Int32
   fun aha_buffer_upload(device : Int32, d_dst : Void*, src : Void*, bytes : UInt64) : Int32
@@ -218,6 +232,8 @@ module Aha
   class AC
     E_DUP_KEY  = -4
     E_CAPACITY = -6
+
+    getter handle : LibAhaHip::Ac
 
     def initialize(@handle : LibAhaHip::Ac)
     end
@@ -452,6 +468,55 @@ module Aha
   # is the same `Hit` with an Int32 value (`val.to_i32`, ac.cr:273).  The library's own numbering has no such limit below
   # 2^31 keys, so one class answers for both names.
   alias ACBig = AC
+
+  # n_seqs sequences matched piece by piece (aha_feed_*): #match(seq, piece) yields exactly the hits one match over the whole
+  # sequence so far reports with an end inside the piece, with absolute offsets.  (Uncompiled: no Crystal toolchain was at
+  # hand when it was written; tests/test_feed_host.py checks that the lib block binds every entry point.)  Hit holds Int32
+  # offsets: past 2^31 bytes of a sequence use aha_feed_match_batch, whose offsets are relative to the piece.
+  class Feed
+    def initialize(ac : AC, n_seqs : Int, chars : Bool = false)
+      @ac = ac
+      rc = LibAhaHip.aha_feed_open(ac.handle, n_seqs.to_u32, chars ? LibAhaHip::FEED_CHARS : 0_u32, out h)
+      raise String.new(LibAhaHip.aha_strerror(rc)) if rc != 0
+      @handle = h
+    end
+
+    def finalize
+      LibAhaHip.aha_feed_free(@handle)
+    end
+
+    def reset(seq : Int? = nil)
+      rc = LibAhaHip.aha_feed_reset(@handle, seq ? seq.to_u32 : UInt32::MAX)
+      raise String.new(LibAhaHip.aha_strerror(rc)) if rc != 0
+    end
+
+    # {bytes, chars} fed to the sequence so far
+    def position(seq : Int) : {UInt64, UInt64}
+      rc = LibAhaHip.aha_feed_position(@handle, seq.to_u32, out b, out c)
+      raise String.new(LibAhaHip.aha_strerror(rc)) if rc != 0
+      {b, c}
+    end
+
+    def match(seq : Int, piece : Bytes | String) : Array(Hit)
+      bytes = piece.is_a?(String) ? piece.to_slice : piece
+      offs = [0_u64, bytes.size.to_u64]
+      ids = [seq.to_u32]
+      cap = (bytes.size / 4 + 64).to_u64
+      loop do
+        buf = Slice(LibAhaHip::Hit).new(cap.to_i32)
+        base = 0_u64
+        rc = LibAhaHip.aha_feed_match_batch(@handle, bytes.to_unsafe, offs.to_unsafe, ids.to_unsafe, 1_u64, buf.to_unsafe,
+          cap, nil, pointerof(base), out n)
+        if rc == -6 # AHA_E_CAPACITY: n is the exact count, the feed is unchanged
+          cap = n
+          next
+        end
+        raise String.new(LibAhaHip.aha_last_error(@ac.handle)) if rc != 0
+        b = base.to_i32 # (raises OverflowError past 2^31)
+        return Array(Hit).new(n.to_i32) { |i| Hit.new(buf[i].start + b, buf[i].end_ + b, buf[i].value) }
+      end
+    end
+  end
 
   # Several GPUs of one node behind one object: the batch is cut into contiguous, byte-balanced document ranges (one
   # per device), every device matches its range, the hit buffers are exchanged with an all-gatherv (RCCL over xGMI

@@ -321,6 +321,75 @@ class AC {
 // Aha::ACBig = ACX(Int64) (src/aha/ac.cr:9): wider node ids, the same Hit with an Int32 value (ac.cr:273)
 using ACBig = AC;
 
+// Sequences that arrive in pieces across calls (aha_feed_*): a call matches a batch of pieces, piece d the next part of
+// sequence seq_ids[d], and gives exactly the hits one match over the whole sequence so far reports with an end inside the
+// piece.  Offsets are relative to the piece (start may be negative); bases[d] is the sequence's length before it.  Free the
+// feed before its AC.
+class Feed {
+ public:
+  Feed(const AC &ac, uint32_t n_seqs, bool chars = false) : ac_(ac.handle()) {
+    const int32_t rc = aha_feed_open(ac_, n_seqs, chars ? AHA_FEED_CHARS : 0u, &f_);
+    if (rc != AHA_OK) throw Error(rc, aha_strerror(rc));
+  }
+  Feed(const Feed &) = delete;
+  Feed &operator=(const Feed &) = delete;
+  Feed(Feed &&o) noexcept : ac_(o.ac_), f_(o.f_) { o.f_ = nullptr; }
+  ~Feed() { aha_feed_free(f_); }
+
+  // host buffers: the hits of the call; piece_hit_offsets (D+1) and bases (D) when asked for
+  std::vector<Hit> match_batch(std::string_view corpus, const std::vector<uint64_t> &piece_offsets,
+                               const std::vector<uint32_t> &seq_ids, std::vector<uint64_t> *piece_hit_offsets = nullptr,
+                               std::vector<uint64_t> *bases = nullptr) {
+    const uint64_t D = piece_offsets.empty() ? 0 : piece_offsets.size() - 1;
+    if (seq_ids.size() != D) throw Error(AHA_E_INVALID, "one sequence id per piece");
+    if (piece_hit_offsets) piece_hit_offsets->assign(D + 1, 0);
+    if (bases) bases->assign(D, 0);
+    std::vector<Hit> out(corpus.size() / 8 + 64);
+    uint64_t n = 0;
+    for (;;) {
+      const int32_t rc = aha_feed_match_batch(f_, reinterpret_cast<const uint8_t *>(corpus.data()), piece_offsets.data(),
+                                              seq_ids.data(), D, out.data(), out.size(),
+                                              piece_hit_offsets ? piece_hit_offsets->data() : nullptr,
+                                              bases ? bases->data() : nullptr, &n);
+      if (rc == AHA_E_CAPACITY) {  // (the feed is unchanged: the same call again)
+        out.resize(n);
+        continue;
+      }
+      check(rc);
+      break;
+    }
+    out.resize(n);
+    return out;
+  }
+  // the next piece of one sequence: its hits with absolute offsets (they must fit Int32)
+  std::vector<Hit> match(uint32_t seq, std::string_view piece) {
+    std::vector<uint64_t> bases;
+    auto hits = match_batch(piece, {0, piece.size()}, {seq}, nullptr, &bases);
+    for (auto &h : hits) {
+      h.start += (int32_t)bases[0];
+      h.end += (int32_t)bases[0];
+    }
+    return hits;
+  }
+  void reset(uint32_t seq = UINT32_MAX) { check(aha_feed_reset(f_, seq)); }
+  // {bytes, chars} fed to the sequence so far
+  std::pair<uint64_t, uint64_t> position(uint32_t seq) const {
+    uint64_t b = 0, c = 0;
+    check(aha_feed_position(f_, seq, &b, &c));
+    return {b, c};
+  }
+  aha_feed *handle() const { return f_; }
+
+ private:
+  void check(int32_t rc) const {
+    if (rc == AHA_OK) return;
+    const char *m = aha_last_error(ac_);
+    throw Error(rc, (m && *m) ? m : aha_strerror(rc));
+  }
+  aha_ac *ac_;
+  aha_feed *f_ = nullptr;
+};
+
 // Several GPUs of one node behind one object (aha_group_*): contiguous byte-balanced document ranges, one per device entry,
 // all-gatherv of the hit buffers.  match_batch: host buffers in and out; upload + match_resident: the batch stays on the
 // devices, the hits too (shard_hits reads one device's copy of the whole ordered stream).

@@ -386,6 +386,47 @@ int32_t aha_ac_count_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uin
                                   uint64_t *d_key_counts /* K or NULL */, uint64_t *d_doc_hit_offsets /* or NULL */,
                                   uint64_t *n_hits, void *stream);
 
+/* ---- feeds: sequences that arrive in pieces across calls (pure additions to ABI 8) ----------------------------------
+ * A feed is n_seqs open sequences bound to one device handle.  A call matches a batch of D pieces: piece d =
+ * corpus[piece_offsets[d] .. piece_offsets[d+1]) is the next part of sequence seq_ids[d].  Its hits are exactly those that one
+ * plain match over the whole sequence so far (every piece since open or reset, concatenated) reports with an end inside the
+ * piece, in the same order, bit for bit; the hits of piece d are out[piece_hit_offsets[d] .. piece_hit_offsets[d+1]).
+ * Offsets are int32 and relative to the piece's first byte -- or, on a char feed (AHA_FEED_CHARS at open), its first
+ * character under the lead-byte rule, as the whole sequence's char map has it where a piece begins inside a character --;
+ * start may be negative down to -(Lmax-1): the hit began in an earlier piece.  piece_bases[d] (uint64) = the sequence's length
+ * before the piece (bytes, or lead bytes on a char feed): absolute offset = base + relative.  A sequence has no length
+ * limit; a piece must be shorter than 2^31 bytes minus Lmax (AHA_E_TOO_LONG).  Within one call a sequence appears at most
+ * once (AHA_E_INVALID); pieces may come in any order and a call may name any subset of the sequences.  A call that fails
+ * changes nothing, AHA_E_CAPACITY included: *n_hits is then the exact count and the same call with a larger buffer gives what
+ * the first would have.  No separator filter, no match_longest, no counts (follow-ups).  Errors: aha_last_error(ac).  Calls
+ * on one feed are serialised (a mutex in the feed); different feeds and plain calls on the handle run side by side.
+ * Pipeline (aha_amd/csrc/feed.cpp, scan_feed.hip): with W = max(Lmax-1, 0) the feed keeps the last
+ * min(W, length) bytes of every sequence on the device.  A call matches one window batch of at most 4 W bytes per piece (the
+ * hits that straddle or follow a cut), then the pieces as they are (the engine a plain match of them takes: aha_ac_last_timing
+ * reports it), and merges the two by count.  Device memory of a feed: 2 W + 24 bytes per sequence; per call, the window
+ * batch, 12 bytes per hit of (cap + the hits of the pieces' first W bytes) for the main pass, ~100 bytes per piece, and the
+ * handle's scratch set for the two matches; the host entry stages the corpus and the hits on the device as well. */
+typedef struct aha_feed aha_feed;
+#define AHA_FEED_CHARS 1u /* offsets and bases in characters (the lead-byte rule) instead of bytes */
+/* AHA_E_NO_DEVICE on a host-only handle; AHA_E_INVALID for NULL arguments, n_seqs = 0 or unknown flags. */
+int32_t aha_feed_open(aha_ac *ac, uint32_t n_seqs, uint32_t flags, aha_feed **out);
+/* Frees the feed (waits for a call in flight); before aha_ac_free of its handle. */
+void aha_feed_free(aha_feed *f);
+/* The sequence starts again from length 0; UINT32_MAX: every sequence. */
+int32_t aha_feed_reset(aha_feed *f, uint32_t seq);
+/* Length of a sequence so far, in bytes and in lead bytes (the latter counted on char feeds only); either may be NULL. */
+int32_t aha_feed_position(const aha_feed *f, uint32_t seq, uint64_t *bytes, uint64_t *chars);
+/* Host buffers (the pieces are uploaded to feed scratch; offsets and ids are checked on the host). */
+int32_t aha_feed_match_batch(aha_feed *f, const uint8_t *corpus, const uint64_t *piece_offsets, const uint32_t *seq_ids,
+                             uint64_t n_pieces, aha_hit *out, uint64_t cap, uint64_t *piece_hit_offsets /* D+1 or NULL */,
+                             uint64_t *piece_bases /* D or NULL */, uint64_t *n_hits);
+/* Device-resident form: d_ pointers are HBM on the handle's device, validated on the device before anything is indexed with
+ * them; *n_hits is host memory; blocks until final. */
+int32_t aha_feed_match_batch_device(aha_feed *f, const uint8_t *d_corpus, const uint64_t *d_piece_offsets,
+                                    const uint32_t *d_seq_ids, uint64_t n_pieces, uint64_t n_bytes, aha_hit *d_out,
+                                    uint64_t cap, uint64_t *d_piece_hit_offsets /* D+1 or NULL */,
+                                    uint64_t *d_piece_bases /* D or NULL */, uint64_t *n_hits, void *stream);
+
 /* Frees the handle's device scratch (it grows with the largest batch seen and is otherwise kept for reuse). */
 int32_t aha_ac_release_scratch(aha_ac *ac);
 /* Device bytes currently held as scratch by the handle (all sets); waits for running calls. */
