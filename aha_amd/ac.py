@@ -551,7 +551,7 @@ class AC:
 class Feed:
     """Sequences that arrive in pieces across calls (aha_feed_*).  Each call matches a batch of pieces -- piece d is the next
     part of sequence seq_ids[d] -- and yields exactly the hits one plain match over the whole sequence so far would report with
-    an end inside the piece.  Offsets are relative to the piece (start may be negative: the hit began in an earlier piece);
+    an end inside the piece; a count call (count_batch, count) gives the same hits per key.  Offsets are relative to the piece (start may be negative: the hit began in an earlier piece);
     piece_bases[d] is the sequence's length before it, so base + offset is absolute."""
 
     def __init__(self, ac, handle, n_seqs, chars):
@@ -634,6 +634,73 @@ class Feed:
             raise e
         self._check(rc)
         return int(n.value)
+
+    def count_batch(self, corpus, piece_offsets, seq_ids, per_key=True, accumulate_into=None):
+        """Hits per key of match_batch on the same pieces, without the hit list (aha_feed_count_batch): -> (key_counts
+        uint64[K] or None, piece_hit_offsets uint64[D+1], piece_bases uint64[D]).  The sequences move on as a match call would
+        move them.  accumulate_into: a uint64[K] array the counts are added to (AHA_COUNT_ACCUMULATE); it is also what is
+        returned, and a call that fails leaves it as it was."""
+        if isinstance(corpus, (bytes, bytearray)):
+            corpus = np.frombuffer(bytes(corpus), dtype=np.uint8)
+        corpus = np.ascontiguousarray(corpus, dtype=np.uint8)
+        piece_offsets = np.ascontiguousarray(piece_offsets, dtype=np.uint64)
+        seq_ids = np.ascontiguousarray(seq_ids, dtype=np.uint32)
+        D = piece_offsets.size - 1
+        if seq_ids.size != D:
+            raise ValueError("one sequence id per piece")
+        K = self._ac.n_keys
+        flags = 0
+        kc = None
+        if accumulate_into is not None:
+            kc = accumulate_into
+            if not (isinstance(kc, np.ndarray) and kc.dtype == np.uint64 and kc.flags.c_contiguous and kc.flags.writeable
+                    and kc.size == K):
+                raise ValueError(f"accumulate_into must be a writeable C-contiguous uint64 array of {K} entries")
+            flags = N.AHA_COUNT_ACCUMULATE
+        elif per_key:
+            kc = np.zeros(K, dtype=np.uint64)
+        pho = np.zeros(D + 1, dtype=np.uint64)
+        bases = np.zeros(max(D, 1), dtype=np.uint64)
+        n = C.c_uint64(0)
+        rc = N.lib().aha_feed_count_batch(self._h, _ptr(corpus), _ptr(piece_offsets), _ptr(seq_ids), D, flags, _ptr(kc),
+                                          _ptr(pho), _ptr(bases), C.byref(n))
+        self._check(rc)
+        return kc, pho, bases[:D]
+
+    def count_batch_device(self, corpus, piece_offsets, seq_ids, key_counts=None, piece_hit_offsets=None, piece_bases=None,
+                           accumulate=False, stream=None):
+        """Device-resident count on torch CUDA tensors (uint8 corpus, int64/uint64 piece offsets, int32/uint32 sequence ids;
+        key_counts int64/uint64 [K] or None; int64/uint64 [D+1] / [D] or None).  Returns the hit count.  accumulate: add into
+        key_counts."""
+        import torch
+
+        assert corpus.is_cuda and corpus.dtype == torch.uint8 and corpus.is_contiguous()
+        assert piece_offsets.is_cuda and piece_offsets.dtype in (torch.int64, torch.uint64) and piece_offsets.is_contiguous()
+        assert seq_ids.is_cuda and seq_ids.dtype in (torch.int32, torch.uint32) and seq_ids.is_contiguous()
+        K = self._ac.n_keys
+        if key_counts is not None and not (key_counts.is_cuda and key_counts.dtype in (torch.int64, torch.uint64)
+                                           and key_counts.is_contiguous() and key_counts.numel() >= K):
+            raise ValueError(f"key_counts must be a contiguous int64/uint64 CUDA tensor of at least {K} entries")
+        D = piece_offsets.numel() - 1
+        assert seq_ids.numel() >= D
+        for t, n in ((piece_hit_offsets, D + 1), (piece_bases, D)):
+            assert t is None or (t.is_cuda and t.dtype in (torch.int64, torch.uint64) and t.is_contiguous() and t.numel() >= n)
+        n = C.c_uint64(0)
+        s = stream if stream is not None else torch.cuda.current_stream(corpus.device).cuda_stream
+        rc = N.lib().aha_feed_count_batch_device(
+            self._h, corpus.data_ptr(), piece_offsets.data_ptr(), seq_ids.data_ptr(), D, corpus.numel(),
+            N.AHA_COUNT_ACCUMULATE if accumulate else 0, key_counts.data_ptr() if key_counts is not None else None,
+            piece_hit_offsets.data_ptr() if piece_hit_offsets is not None else None,
+            piece_bases.data_ptr() if piece_bases is not None else None, C.byref(n), C.c_void_p(s))
+        self._check(rc)
+        return int(n.value)
+
+    def count(self, seq, piece):
+        """The next piece of one sequence: the hits per key that match(seq, piece) would give, uint64[K]."""
+        b = _b(piece)
+        kc, _, _ = self.count_batch(np.frombuffer(b, dtype=np.uint8), np.array([0, len(b)], dtype=np.uint64),
+                                    np.array([seq], dtype=np.uint32))
+        return kc
 
     def match(self, seq, piece):
         """The next piece of one sequence: its hits as Hits with absolute offsets."""

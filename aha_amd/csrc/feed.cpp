@@ -8,6 +8,10 @@
 //   the host               total = (nX - nY) + (nM - nZ) from block totals: above cap -> AHA_E_CAPACITY, nothing committed
 //   kfd_scan + kfd_merge   piece_hit_offsets, the kept hits into the caller's buffer
 //   kfd_commit             bases, counters, the new contexts
+// A count call (aha_feed_count_batch*) shares the first three steps (feed_windows), then
+//   device_count           the caller's pieces, from the root, into the feed's K-word vector   -> m_d (a plain count's engine)
+//   kfd_count_windows      + the window hits: +1 for the X block, -1 for the ctx and P' blocks
+//   kfd_scan + kfd_count_finish + kfd_commit   piece_hit_offsets, then the caller's key counts, then the feed's state
 // Calls on one feed are serialised by its mutex; its scratch is its own.  The two matches lease one of the handle's scratch
 // sets like any call, so different feeds and plain calls on the same handle run side by side.
 #include "feed.hpp"
@@ -27,14 +31,14 @@ struct aha_feed {
   uint32_t stamp = 0;
   // grow-only scratch: 0 verdict + window size, 1 window bytes, 2 window offsets, 3 window hit offsets, 4 window hits,
   // 5 main hit offsets, 6 main hits, 7 piece hit offsets, 8 leads(ctx), 9 leads(P); 10 .. 15 the host entry's staging
-  // (corpus, offsets, ids, hits, piece hit offsets, bases)
-  Buf buf[16];
+  // (corpus, offsets, ids, hits, piece hit offsets, bases), 16 key counts (a count call's sums), 17 the host entry's key counts
+  Buf buf[18];
   uint64_t *h_pin = nullptr;  // pinned: read-backs
   hipStream_t hs = nullptr;   // the host entry's stream (and position / reset)
 };
 
 namespace {
-enum { kMisc, kWin, kWoff, kWdho, kWhits, kMdho, kMhits, kPho, kLeadCtx, kLeadP, kHCorpus, kHOff, kHIds, kHOut, kHPho, kHBases };
+enum { kMisc, kWin, kWoff, kWdho, kWhits, kMdho, kMhits, kPho, kLeadCtx, kLeadP, kHCorpus, kHOff, kHIds, kHOut, kHPho, kHBases, kKc, kHKc };
 
 void *reserve(aha_feed *f, int i, size_t bytes) {
   Buf &b = f->buf[i];
@@ -57,9 +61,11 @@ int32_t no_memory(const char *what) {
   return AHA_E_HIP;
 }
 
-// the part of a call before anything is written for the caller: checks, windows, both matches.  *total = the call's hits;
-// AHA_E_CAPACITY when they are more than cap.
-int32_t feed_prepare(aha_feed *f, Scratch *sc, FeedArgs &F, uint64_t cap, hipStream_t s, uint64_t *total) {
+// the first half of every call: checks, the window batch and its match.  hits: the window batch's hit list is needed (a match,
+// or a count with key counts); otherwise only its per-document offsets (a count without: device_count of the windows).
+// -> *n_w, and the hits of the three blocks nx (X), ny (ctx), nz (P').
+int32_t feed_windows(aha_feed *f, Scratch *sc, FeedArgs &F, hipStream_t s, bool hits, uint64_t *n_w, uint64_t *nx,
+                     uint64_t *ny, uint64_t *nz) {
   aha_ac *ac = f->ac;
   const uint64_t D = F.D;
   if (++f->stamp == 0) f->stamp = 1;  // (a stamp comes back after 2^32 calls; a sequence must be named in neither)
@@ -106,35 +112,55 @@ int32_t feed_prepare(aha_feed *f, Scratch *sc, FeedArgs &F, uint64_t cap, hipStr
   p.struct_size = sizeof(p);
   p.char_offsets = F.chars;
   bool packed = false;
-  // the window batch: at most 4 W bytes per piece; its hit scratch grows to what it needed once
-  uint64_t n_w = 0;
-  for (int attempt = 0;; attempt++) {
-    const uint64_t cap_w = f->buf[kWhits].bytes / sizeof(aha_hit);
-    int32_t rc = device_match(ac, sc, F.win, F.woff, 3 * D, n_win, &p, cap_w ? (aha_hit *)f->buf[kWhits].p : nullptr, cap_w, wdho,
-                              &n_w, s, true, nullptr, &packed, true);
-    if (rc == AHA_E_CAPACITY && attempt == 0) {
-      if (!reserve(f, kWhits, std::max<uint64_t>(n_w, 1024) * sizeof(aha_hit))) return no_memory("window hits");
-      continue;
+  *n_w = 0;
+  if (hits) {
+    // the window batch: at most 4 W bytes per piece; its hit scratch grows to what it needed once
+    for (int attempt = 0;; attempt++) {
+      const uint64_t cap_w = f->buf[kWhits].bytes / sizeof(aha_hit);
+      int32_t rc = device_match(ac, sc, F.win, F.woff, 3 * D, n_win, &p, cap_w ? (aha_hit *)f->buf[kWhits].p : nullptr, cap_w,
+                                wdho, n_w, s, true, nullptr, &packed, true);
+      if (rc == AHA_E_CAPACITY && attempt == 0) {
+        if (!reserve(f, kWhits, std::max<uint64_t>(*n_w, 1024) * sizeof(aha_hit))) return no_memory("window hits");
+        continue;
+      }
+      if (rc) return rc;
+      break;
     }
+  } else {
+    // (a count call never writes the handle's back-off state, so it needs no quiet form)
+    int32_t rc = device_count(ac, sc, F.win, F.woff, 3 * D, n_win, &p, 0, nullptr, wdho, n_w, s, true);
     if (rc) return rc;
-    break;
   }
   F.whits = (const int32_t *)f->buf[kWhits].p;
-  uint64_t nz = 0, nx = 0, ny = 0;
+  *nx = *ny = *nz = 0;
   if (D) {
     HIPCHK(ac, hipMemcpyAsync(f->h_pin, wdho + D, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(ac, hipMemcpyAsync(f->h_pin + 1, wdho + 2 * D, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(ac, hipStreamSynchronize(s));
-    nx = f->h_pin[0];
-    ny = f->h_pin[1] - nx;
-    nz = n_w - f->h_pin[1];
+    *nx = f->h_pin[0];
+    *ny = f->h_pin[1] - *nx;
+    *nz = *n_w - f->h_pin[1];
   }
+  return AHA_OK;
+}
+
+// the part of a match call before anything is written for the caller: the windows, then the main pass.  *total = the call's
+// hits; AHA_E_CAPACITY when they are more than cap.
+int32_t feed_prepare(aha_feed *f, Scratch *sc, FeedArgs &F, uint64_t cap, hipStream_t s, uint64_t *total) {
+  aha_ac *ac = f->ac;
+  uint64_t n_w = 0, nx = 0, ny = 0, nz = 0;
+  int32_t rc = feed_windows(f, sc, F, s, true, &n_w, &nx, &ny, &nz);
+  if (rc) return rc;
+  aha_match_params p{};
+  p.struct_size = sizeof(p);
+  p.char_offsets = F.chars;
+  bool packed = false;
   // the main pass: what the caller's buffer can take plus the hits it drops
   const uint64_t cap_m = cap + nz;
   aha_hit *mh = cap_m ? (aha_hit *)reserve(f, kMhits, cap_m * sizeof(aha_hit)) : nullptr;
   if (cap_m && !mh) return no_memory("hits");
   uint64_t n_m = 0;
-  int32_t rc = device_match(ac, sc, F.text, F.off, D, F.n_bytes, &p, mh, cap_m, mdho, &n_m, s, true, nullptr, &packed);
+  rc = device_match(ac, sc, F.text, F.off, F.D, F.n_bytes, &p, mh, cap_m, (uint64_t *)F.mdho, &n_m, s, true, nullptr, &packed);
   if (rc && rc != AHA_E_CAPACITY) return rc;
   F.mhits = (const int32_t *)mh;
   *total = (nx - ny) + (n_m - nz);
@@ -143,6 +169,34 @@ int32_t feed_prepare(aha_feed *f, Scratch *sc, FeedArgs &F, uint64_t cap, hipStr
     tls_err = "output buffer too small";
     return AHA_E_CAPACITY;
   }
+  return AHA_OK;
+}
+
+// a whole count call on device-resident pieces: the windows, the main pass into the feed's vector, the window hits added,
+// then -- nothing the caller owns is written before -- the caller's key counts and offsets and the feed's state
+int32_t feed_count(aha_feed *f, Scratch *sc, FeedArgs &F, hipStream_t s, uint64_t *total) {
+  aha_ac *ac = f->ac;
+  const bool per_key = F.key_counts != nullptr;
+  uint64_t n_w = 0, nx = 0, ny = 0, nz = 0;
+  int32_t rc = feed_windows(f, sc, F, s, per_key, &n_w, &nx, &ny, &nz);
+  if (rc) return rc;
+  F.n_whits = per_key ? n_w : 0;
+  F.K = ac->aut.n_keys;
+  F.kc = per_key ? (unsigned long long *)reserve(f, kKc, (size_t)std::max<uint32_t>(F.K, 1) * 8) : nullptr;
+  if (per_key && !F.kc) return no_memory("key counts");
+  if (!F.pho && !(F.pho = (uint64_t *)reserve(f, kPho, (F.D + 1) * 8))) return no_memory("piece hit offsets");
+  // the main pass: the engine and count path a plain count of the pieces takes (its timing is the call's)
+  aha_match_params p{};
+  p.struct_size = sizeof(p);
+  uint64_t n_m = 0;
+  rc = device_count(ac, sc, F.text, F.off, F.D, F.n_bytes, &p, 0, (uint64_t *)F.kc, (uint64_t *)F.mdho, &n_m, s, true);
+  if (rc) return rc;
+  *total = (nx - ny) + (n_m - nz);
+  F.total = *total;
+  feed_launch_count(F, s);
+  feed_launch_commit(F, s);
+  HIPCHK(ac, hipGetLastError());
+  HIPCHK(ac, hipStreamSynchronize(s));
   return AHA_OK;
 }
 
@@ -160,6 +214,23 @@ int32_t feed_finish(aha_feed *f, FeedArgs &F, hipStream_t s) {
 }
 
 bool bad_feed(const aha_feed *f) { return !f || !f->ac || f->ac->device < 0; }
+
+// the checks kfd_check makes, on the host (the host entries)
+int32_t check_pieces_host(const aha_feed *f, const uint64_t *piece_offsets, const uint32_t *seq_ids, uint64_t n_pieces) {
+  if (piece_offsets[0] != 0) return AHA_E_INVALID;
+  const uint64_t max_piece = (1ull << 31) - std::max<uint64_t>(f->ac->aut.max_key_len, 1);
+  std::vector<uint8_t> seen;
+  try {
+    seen.assign(f->n_seqs, 0);
+  } catch (...) {
+    return AHA_E_NOMEM;
+  }
+  for (uint64_t d = 0; d < n_pieces; d++) {
+    if (piece_offsets[d + 1] < piece_offsets[d] || seq_ids[d] >= f->n_seqs || seen[seq_ids[d]]++) return AHA_E_INVALID;
+    if (piece_offsets[d + 1] - piece_offsets[d] >= max_piece) return AHA_E_TOO_LONG;
+  }
+  return AHA_OK;
+}
 }  // namespace
 
 int32_t aha_feed_open(aha_ac *ac, uint32_t n_seqs, uint32_t flags, aha_feed **out) {
@@ -275,19 +346,8 @@ int32_t aha_feed_match_batch(aha_feed *f, const uint8_t *corpus, const uint64_t 
   if (!f || !n_hits || !piece_offsets || (n_pieces && !seq_ids) || (cap && !out)) return AHA_E_INVALID;
   if (bad_feed(f)) return AHA_E_NO_DEVICE;
   aha_ac *ac = f->ac;
-  // the checks kfd_check makes, on the host
-  if (piece_offsets[0] != 0) return AHA_E_INVALID;
-  const uint64_t max_piece = (1ull << 31) - std::max<uint64_t>(ac->aut.max_key_len, 1);
-  std::vector<uint8_t> seen;
-  try {
-    seen.assign(f->n_seqs, 0);
-  } catch (...) {
-    return AHA_E_NOMEM;
-  }
-  for (uint64_t d = 0; d < n_pieces; d++) {
-    if (piece_offsets[d + 1] < piece_offsets[d] || seq_ids[d] >= f->n_seqs || seen[seq_ids[d]]++) return AHA_E_INVALID;
-    if (piece_offsets[d + 1] - piece_offsets[d] >= max_piece) return AHA_E_TOO_LONG;
-  }
+  int32_t rc = check_pieces_host(f, piece_offsets, seq_ids, n_pieces);
+  if (rc) return rc;
   const uint64_t n_bytes = piece_offsets[n_pieces];
   if (n_bytes && !corpus) return AHA_E_INVALID;
   std::lock_guard<std::mutex> lk(f->mu);
@@ -314,7 +374,7 @@ int32_t aha_feed_match_batch(aha_feed *f, const uint8_t *corpus, const uint64_t 
   F.bases = d_bases;
   uint64_t total = 0;
   *n_hits = 0;
-  int32_t rc = feed_prepare(f, lease.get(), F, cap, s, &total);
+  rc = feed_prepare(f, lease.get(), F, cap, s, &total);
   if (rc == AHA_E_CAPACITY) *n_hits = total;
   if (rc) return rc;
   aha_hit *d_out = (aha_hit *)reserve(f, kHOut, total * sizeof(aha_hit));
@@ -322,6 +382,85 @@ int32_t aha_feed_match_batch(aha_feed *f, const uint8_t *corpus, const uint64_t 
   F.out = reinterpret_cast<int32_t *>(d_out);
   if ((rc = feed_finish(f, F, s))) return rc;
   if (total) HIPCHK(ac, hipMemcpyAsync(out, d_out, total * sizeof(aha_hit), hipMemcpyDeviceToHost, s));
+  if (piece_hit_offsets) HIPCHK(ac, hipMemcpyAsync(piece_hit_offsets, d_pho, (D + 1) * 8, hipMemcpyDeviceToHost, s));
+  if (piece_bases && D) HIPCHK(ac, hipMemcpyAsync(piece_bases, d_bases, D * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  *n_hits = total;
+  return AHA_OK;
+}
+
+
+int32_t aha_feed_count_batch_device(aha_feed *f, const uint8_t *d_corpus, const uint64_t *d_piece_offsets,
+                                    const uint32_t *d_seq_ids, uint64_t n_pieces, uint64_t n_bytes, uint32_t flags,
+                                    uint64_t *d_key_counts, uint64_t *d_piece_hit_offsets, uint64_t *d_piece_bases,
+                                    uint64_t *n_hits, void *stream) {
+  if (!f || !n_hits || !d_piece_offsets || (n_pieces && !d_seq_ids) || (n_bytes && !d_corpus) || (flags & ~AHA_COUNT_ACCUMULATE))
+    return AHA_E_INVALID;
+  if (bad_feed(f)) return AHA_E_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(f->mu);
+  DeviceGuard g(f->ac->device);
+  Lease lease(f->ac);
+  FeedArgs F{};
+  F.text = d_corpus;
+  F.off = d_piece_offsets;
+  F.ids = d_seq_ids;
+  F.D = n_pieces;
+  F.n_bytes = n_bytes;
+  F.pho = d_piece_hit_offsets;
+  F.bases = d_piece_bases;
+  F.key_counts = d_key_counts;
+  F.accumulate = (flags & AHA_COUNT_ACCUMULATE) ? 1u : 0u;
+  uint64_t total = 0;
+  *n_hits = 0;
+  int32_t rc = feed_count(f, lease.get(), F, (hipStream_t)stream, &total);
+  if (rc) return rc;
+  *n_hits = total;
+  return AHA_OK;
+}
+
+int32_t aha_feed_count_batch(aha_feed *f, const uint8_t *corpus, const uint64_t *piece_offsets, const uint32_t *seq_ids,
+                             uint64_t n_pieces, uint32_t flags, uint64_t *key_counts, uint64_t *piece_hit_offsets,
+                             uint64_t *piece_bases, uint64_t *n_hits) {
+  if (!f || !n_hits || !piece_offsets || (n_pieces && !seq_ids) || (flags & ~AHA_COUNT_ACCUMULATE)) return AHA_E_INVALID;
+  if (bad_feed(f)) return AHA_E_NO_DEVICE;
+  aha_ac *ac = f->ac;
+  int32_t rc = check_pieces_host(f, piece_offsets, seq_ids, n_pieces);
+  if (rc) return rc;
+  const uint64_t n_bytes = piece_offsets[n_pieces];
+  if (n_bytes && !corpus) return AHA_E_INVALID;
+  std::lock_guard<std::mutex> lk(f->mu);
+  DeviceGuard g(ac->device);
+  Lease lease(ac);
+  hipStream_t s = f->hs;
+  const uint64_t D = n_pieces;
+  const size_t kc_bytes = (size_t)ac->aut.n_keys * 8;
+  uint8_t *d_corpus = (uint8_t *)reserve(f, kHCorpus, n_bytes + 64);
+  uint64_t *d_off = (uint64_t *)reserve(f, kHOff, (D + 1) * 8);
+  uint32_t *d_ids = (uint32_t *)reserve(f, kHIds, D * 4);
+  uint64_t *d_pho = (uint64_t *)reserve(f, kHPho, (D + 1) * 8);
+  uint64_t *d_bases = (uint64_t *)reserve(f, kHBases, D * 8);
+  uint64_t *d_kc = key_counts ? (uint64_t *)reserve(f, kHKc, kc_bytes) : nullptr;
+  if (!d_corpus || !d_off || !d_ids || !d_pho || !d_bases || (key_counts && !d_kc)) return no_memory("staging buffers");
+  if (n_bytes) HIPCHK(ac, hipMemcpyAsync(d_corpus, corpus, n_bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(ac, hipMemcpyAsync(d_off, piece_offsets, (D + 1) * 8, hipMemcpyHostToDevice, s));
+  if (D) HIPCHK(ac, hipMemcpyAsync(d_ids, seq_ids, D * 4, hipMemcpyHostToDevice, s));
+  // running totals: the caller's vector goes up first and comes back only from a call that succeeded
+  if (d_kc && (flags & AHA_COUNT_ACCUMULATE) && kc_bytes)
+    HIPCHK(ac, hipMemcpyAsync(d_kc, key_counts, kc_bytes, hipMemcpyHostToDevice, s));
+  FeedArgs F{};
+  F.text = d_corpus;
+  F.off = d_off;
+  F.ids = d_ids;
+  F.D = D;
+  F.n_bytes = n_bytes;
+  F.pho = d_pho;
+  F.bases = d_bases;
+  F.key_counts = d_kc;
+  F.accumulate = (flags & AHA_COUNT_ACCUMULATE) ? 1u : 0u;
+  uint64_t total = 0;
+  *n_hits = 0;
+  if ((rc = feed_count(f, lease.get(), F, s, &total))) return rc;
+  if (d_kc && kc_bytes) HIPCHK(ac, hipMemcpyAsync(key_counts, d_kc, kc_bytes, hipMemcpyDeviceToHost, s));
   if (piece_hit_offsets) HIPCHK(ac, hipMemcpyAsync(piece_hit_offsets, d_pho, (D + 1) * 8, hipMemcpyDeviceToHost, s));
   if (piece_bases && D) HIPCHK(ac, hipMemcpyAsync(piece_bases, d_bases, D * 8, hipMemcpyDeviceToHost, s));
   HIPCHK(ac, hipStreamSynchronize(s));

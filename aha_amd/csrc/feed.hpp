@@ -37,10 +37,18 @@ struct FeedArgs {
   uint64_t *bases;             // [D] the sequence's length before the piece, or null
   int32_t *out;                // the caller's hits
   uint64_t total;              // hits of the call
+  // count calls (aha_feed_count_batch*)
+  uint64_t n_whits;            // hits of the window batch: [0, wdho[D]) count +1, the rest -1
+  uint32_t K;                  // keys
+  uint32_t accumulate;         // kfd_count_finish adds into key_counts instead of copying
+  unsigned long long *kc;      // [K] the feed's per-key sums: the main pass's, then the window hits added
+  uint64_t *key_counts;        // [K] the caller's, or null
 };
 
 void feed_launch_check(const FeedArgs &F, void *stream);    // kfd_check, then kfd_scan of the window lengths
 void feed_launch_windows(const FeedArgs &F, void *stream);  // kfd_windows (+ kfd_leads on char feeds)
 void feed_launch_merge(const FeedArgs &F, void *stream);    // kfd_scan of the hits per piece, kfd_merge
 void feed_launch_commit(const FeedArgs &F, void *stream);   // kfd_commit: bases, counters, the new contexts
+// count calls: kfd_count_windows (F.kc), kfd_scan of the hits per piece, kfd_count_finish (F.key_counts)
+void feed_launch_count(const FeedArgs &F, void *stream);
 }  // namespace aha

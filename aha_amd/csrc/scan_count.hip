@@ -9,12 +9,14 @@
 //              character-level traversal's wave-ordered records (the END state's base; uend[base] holds the key).
 //   kc_chain   key_counts[j] += visits[h] for every j on chain(h): O(sum of the chain lengths of the keys seen), not of the text.
 // Events pile up on few keys (cfg 5: a few short keys take most of them), so neither step adds into global memory per event:
-// a workgroup sums into an LDS table of {id, 64-bit count} (open addressing, a few probes; what does not find a place adds
-// to global memory at once) and flushes it with one global add per distinct id at its end.  In kc_visits a wave first takes
+// a workgroup sums into an LDS table of {id, 64-bit count} (count_table.hpp, shared with scan_feed.hip: open addressing, a
+// few probes; what does not find a place adds to global memory at once) and flushes it with one global add per distinct id
+// at its end.  In kc_visits a wave first takes
 // its most frequent id out by ballot (one LDS add for all lanes that hold it), so the table's atomics do not queue on it.
 #include <hip/hip_runtime.h>
 
 #include "automaton.hpp"
+#include "count_table.hpp"
 #include "devcommon.hpp"
 #include "image.hpp"
 #include "unit.hpp"
@@ -23,38 +25,6 @@ namespace aha {
 namespace {
 
 constexpr int kCtThreads = 256;
-constexpr int kCtLog2 = 12;
-constexpr uint32_t kCtSlots = 1u << kCtLog2;  // 48 KiB of LDS: 4 B id + 8 B count per slot
-constexpr uint32_t kCtEmpty = 0xFFFFFFFFu;
-constexpr int kCtProbes = 8;
-
-struct CtTable {
-  uint32_t *id;
-  unsigned long long *cnt;
-};
-
-__device__ __forceinline__ void ct_clear(const CtTable &t) {
-  for (uint32_t i = threadIdx.x; i < kCtSlots; i += kCtThreads) {
-    t.id[i] = kCtEmpty;
-    t.cnt[i] = 0ull;
-  }
-}
-
-// adds v to id's slot; false: no slot within kCtProbes (the caller adds to global memory)
-__device__ __forceinline__ bool ct_add(const CtTable &t, uint32_t id, unsigned long long v) {
-  const uint32_t h = (id * 0x9E3779B1u) >> (32 - kCtLog2);
-  for (int p = 0; p < kCtProbes; p++) {
-    const uint32_t s = (h + (uint32_t)p) & (kCtSlots - 1u);
-    uint32_t k = t.id[s];
-    if (k == kCtEmpty) k = atomicCAS(&t.id[s], kCtEmpty, id);
-    if (k == kCtEmpty || k == id) {
-      atomicAdd(&t.cnt[s], v);
-      return true;
-    }
-  }
-  return false;
-}
-
 // Record sources of kc_visits.  REGIONS: the chunks' event regions after the count pass (id = key id or chain offset).
 // UNIT: the character-level traversal's wave-ordered records (id = base of the END state).
 enum { kSrcRegions = 0, kSrcUnit = 1 };
@@ -65,21 +35,12 @@ __device__ __forceinline__ uint32_t ct_key(const DevAut &A, const uint2 *uend, u
   return A.chain ? A.chain[id].y : id;
 }
 
-// one event per live lane: the wave's first id is taken out by ballot for all lanes that hold it, then every other lane
-// adds its own (all 64 lanes reach this call: the ballots need them)
+// one event per live lane (count_table.hpp); what finds no slot goes to visits[] at once
 template <int SRC>
-__device__ __forceinline__ void ct_event(const CtTable &t, const DevAut &A, const uint2 *uend, unsigned long long *visits,
+__device__ __forceinline__ void ct_visit(const CtTable &t, const DevAut &A, const uint2 *uend, unsigned long long *visits,
                                          bool live, uint32_t id) {
-  const int lane = threadIdx.x & 63;
-  const unsigned long long m = __ballot(live);
-  if (!m) return;
-  const int leader = __ffsll((long long)m) - 1;
-  const uint32_t lid = (uint32_t)__shfl((int)id, leader, 64);
-  const bool same = live && id == lid;
-  const unsigned long long ms = __ballot(same);
-  if (lane == leader && !ct_add(t, lid, (unsigned long long)__popcll(ms)))
-    atomicAdd(&visits[ct_key<SRC>(A, uend, lid)], (unsigned long long)__popcll(ms));
-  if (live && !same && !ct_add(t, id, 1ull)) atomicAdd(&visits[ct_key<SRC>(A, uend, id)], 1ull);
+  ct_event<false>(t, live, id, false,
+                  [&](uint32_t i, unsigned long long v) { atomicAdd(&visits[ct_key<SRC>(A, uend, i)], v); });
 }
 
 template <int SRC>
@@ -108,7 +69,7 @@ __global__ __launch_bounds__(kCtThreads) void kc_visits(DevAut A, V2Args M, cons
         const uint32_t i = i0 + threadIdx.x;
         const uint32_t x = i < n ? reg[i].x : 0u;
         // (count 0: a record that stands for no hit -- the pair engine's voided events)
-        ct_event<SRC>(t, A, uend, visits, (x >> 24) != 0u, x & 0xFFFFFFu);
+        ct_visit<SRC>(t, A, uend, visits, (x >> 24) != 0u, x & 0xFFFFFFu);
       }
     }
   } else {
@@ -133,7 +94,7 @@ __global__ __launch_bounds__(kCtThreads) void kc_visits(DevAut A, V2Args M, cons
           x = src[(size_t)i * 3];
           z = src[(size_t)i * 3 + 2];
         }
-        ct_event<SRC>(t, A, uend, visits, i < total && u_rec_n(x, z, bb) != 0u, x & bmask);
+        ct_visit<SRC>(t, A, uend, visits, i < total && u_rec_n(x, z, bb) != 0u, x & bmask);
       }
     }
   }

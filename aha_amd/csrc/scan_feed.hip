@@ -14,8 +14,16 @@
 //   kfd_leads    leads(P) per piece (char feeds), a reduction over the pieces
 //   kfd_merge    the kept hits into the caller's buffer, rebased; one thread per 4 output hits (3 x 16-byte stores)
 //   kfd_commit   after success only: bases, the counters, the new contexts (written to the other bank)
+// A count call (aha_feed_count_batch*) sums the same selection per key instead: per piece, as multisets of key ids,
+//   hits(piece) = hits(X) - hits(ctx) + hits(P) - hits(P')        (P' = P[0 .. min(W, |P|)))
+// The main pass counts the pieces (device_count) into the feed's vector kc; then
+//   kfd_count_windows  kc += +1 per hit of the X block, -1 per hit of the ctx and P' blocks (uint64, wrapping), summed per
+//                      workgroup in the LDS table of count_table.hpp first
+//   kfd_scan           the hits per piece into piece_hit_offsets, as for a match
+//   kfd_count_finish   the caller's key_counts = kc (or += kc): the first write the caller sees, after everything succeeded
 #include <hip/hip_runtime.h>
 
+#include "count_table.hpp"
 #include "feed.hpp"
 
 namespace aha {
@@ -24,6 +32,7 @@ namespace {
 constexpr int kFdThreads = 256;
 constexpr int kFdScanThreads = 1024;
 constexpr uint64_t kFdSpan = 64 * 1024;  // kfd_leads: bytes per workgroup trip
+constexpr uint64_t kFdCountSpan = 16 * 1024;  // kfd_count_windows: window hits per workgroup trip (at least)
 
 __device__ __forceinline__ uint32_t is_lead(uint8_t b) { return (b & 0xC0u) != 0x80u ? 1u : 0u; }
 
@@ -232,6 +241,37 @@ __global__ void __launch_bounds__(kFdThreads) kfd_commit(FeedArgs F) {
   }
 }
 
+// kc[value] += 1 for a hit of the X block, -= 1 for one of the ctx or P' blocks.  The terms are not each non-negative per
+// key, but their sum with the main pass's count is (it is the piece's count), so the wrapping uint64 sums are exact.
+__global__ void __launch_bounds__(kFdThreads) kfd_count_windows(FeedArgs F) {
+  __shared__ uint32_t s_id[kCtSlots];
+  __shared__ unsigned long long s_cnt[kCtSlots];
+  const CtTable t{s_id, s_cnt};
+  ct_clear(t);
+  __syncthreads();
+  const uint64_t n = F.n_whits, plus = F.wdho[F.D];
+  unsigned long long *kc = F.kc;
+  auto spill = [kc](uint32_t id, unsigned long long v) { atomicAdd(&kc[id], v); };
+  for (uint64_t i0 = blockIdx.x * (uint64_t)kFdThreads; i0 < n; i0 += (uint64_t)gridDim.x * kFdThreads) {
+    const uint64_t i = i0 + threadIdx.x;
+    const bool live = i < n;
+    const uint32_t id = live ? (uint32_t)F.whits[3 * i + 2] : 0u;
+    ct_event<true>(t, live, id, i >= plus, spill);
+  }
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < kCtSlots; i += kFdThreads) {
+    const uint32_t id = s_id[i];
+    if (id != kCtEmpty && s_cnt[i]) atomicAdd(&kc[id], s_cnt[i]);
+  }
+}
+
+__global__ void __launch_bounds__(kFdThreads) kfd_count_finish(FeedArgs F) {
+  for (uint64_t k = blockIdx.x * (uint64_t)kFdThreads + threadIdx.x; k < F.K; k += (uint64_t)gridDim.x * kFdThreads) {
+    const uint64_t v = F.kc[k];
+    F.key_counts[k] = F.accumulate ? F.key_counts[k] + v : v;
+  }
+}
+
 uint32_t grid_for(uint64_t units, uint64_t per_block, uint32_t cap) {
   return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((units + per_block - 1) / per_block, cap));
 }
@@ -257,6 +297,15 @@ void feed_launch_merge(const FeedArgs &F, void *stream) {
     const uint64_t groups = (F.total + 3) / 4;
     hipLaunchKernelGGL(kfd_merge, dim3((uint32_t)((groups + kFdThreads - 1) / kFdThreads)), dim3(kFdThreads), 0, s, F);
   }
+}
+
+void feed_launch_count(const FeedArgs &F, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (F.kc && F.n_whits)
+    hipLaunchKernelGGL(kfd_count_windows, dim3(grid_for(F.n_whits, kFdCountSpan, 1024)), dim3(kFdThreads), 0, s, F);
+  hipLaunchKernelGGL(kfd_scan<1>, dim3(1), dim3(kFdScanThreads), 0, s, F);
+  if (F.key_counts && F.K)
+    hipLaunchKernelGGL(kfd_count_finish, dim3(grid_for(F.K, kFdThreads, 1024)), dim3(kFdThreads), 0, s, F);
 }
 
 void feed_launch_commit(const FeedArgs &F, void *stream) {

@@ -194,6 +194,14 @@ lib LibAhaHip
                                   n_pieces : UInt64, n_bytes : UInt64, d_out : Hit*, cap : UInt64,
                                   d_piece_hit_offsets : UInt64*, d_piece_bases : UInt64*, n_hits : UInt64*,
                                   stream : Void*) : Int32
+  # feed counts: hits per key of the same pieces, the sequences moved on as a match call moves them
+  fun aha_feed_count_batch(f : Feed, corpus : UInt8*, piece_offsets : UInt64*, seq_ids : UInt32*, n_pieces : UInt64,
+                           flags : UInt32, key_counts : UInt64*, piece_hit_offsets : UInt64*, piece_bases : UInt64*,
+                           n_hits : UInt64*) : Int32
+  fun aha_feed_count_batch_device(f : Feed, d_corpus : UInt8*, d_piece_offsets : UInt64*, d_seq_ids : UInt32*,
+                                  n_pieces : UInt64, n_bytes : UInt64, flags : UInt32, d_key_counts : UInt64*,
+                                  d_piece_hit_offsets : UInt64*, d_piece_bases : UInt64*, n_hits : UInt64*,
+                                  stream : Void*) : Int32
   fun aha_buffer_alloc(device : Int32, bytes : UInt64, d_ptr : Void**) : Int32
   fun aha_buffer_free(device : Int32, d_ptr : Void*) : Int32
   fun aha_buffer_upload(device : Int32, d_dst : Void*, src : Void*, bytes : UInt64) : Int32
@@ -515,6 +523,33 @@ module Aha
         b = base.to_i32 # (raises OverflowError past 2^31)
         return Array(Hit).new(n.to_i32) { |i| Hit.new(buf[i].start + b, buf[i].end_ + b, buf[i].value) }
       end
+    end
+
+    # Hits per key of match on the same pieces, without the hit list: {key_counts (K entries), piece_hit_offsets,
+    # piece_bases}.  pieces: {seq, piece} pairs, each sequence at most once.  accumulate: a K-entry array the counts are
+    # added to (running totals over a stream); it is what is returned, and a call that raises leaves it as it was.
+    def count_batch(pieces : Array({Int32, Bytes | String}),
+                    accumulate : Array(UInt64)? = nil) : {Array(UInt64), Array(UInt64), Array(UInt64)}
+      corpus = IO::Memory.new
+      offs = Array(UInt64).new(pieces.size + 1)
+      offs << 0_u64
+      ids = Array(UInt32).new(pieces.size)
+      pieces.each do |(seq, piece)|
+        corpus.write(piece.is_a?(String) ? piece.to_slice : piece)
+        offs << corpus.pos.to_u64
+        ids << seq.to_u32
+      end
+      k = @ac.n_keys
+      kc = accumulate ? accumulate.dup : Array(UInt64).new(k, 0_u64)
+      raise ArgumentError.new("accumulate holds #{k} counts") if kc.size != k
+      pho = Array(UInt64).new(pieces.size + 1, 0_u64)
+      bases = Array(UInt64).new(pieces.size, 0_u64)
+      flags = accumulate ? LibAhaHip::COUNT_ACCUMULATE : 0_u32
+      rc = LibAhaHip.aha_feed_count_batch(@handle, corpus.to_slice.to_unsafe, offs.to_unsafe, ids.to_unsafe,
+        pieces.size.to_u64, flags, kc.to_unsafe, pho.to_unsafe, bases.to_unsafe, out n)
+      raise String.new(LibAhaHip.aha_last_error(@ac.handle)) if rc != 0
+      accumulate.replace(kc) if accumulate
+      {accumulate || kc, pho, bases}
     end
   end
 

@@ -371,6 +371,38 @@ class Feed {
     }
     return hits;
   }
+  // hits per key of match_batch on the same pieces without the hit list (aha_feed_count_batch); the sequences move on as a
+  // match call would move them.  accumulate: add into *key_counts (which then must hold K entries) instead of overwriting
+  // it; a call that throws leaves it as it was.  Returns the hit count.
+  uint64_t count_batch(std::string_view corpus, const std::vector<uint64_t> &piece_offsets, const std::vector<uint32_t> &seq_ids,
+                       std::vector<uint64_t> *key_counts, std::vector<uint64_t> *piece_hit_offsets = nullptr,
+                       std::vector<uint64_t> *bases = nullptr, bool accumulate = false) {
+    const uint64_t D = piece_offsets.empty() ? 0 : piece_offsets.size() - 1;
+    if (piece_offsets.empty()) throw Error(AHA_E_INVALID, "piece_offsets holds D + 1 entries");
+    if (seq_ids.size() != D) throw Error(AHA_E_INVALID, "one sequence id per piece");
+    std::vector<uint64_t> kc, pho(D + 1), b(D);
+    if (key_counts) {
+      aha_ac_info_t i{};
+      i.struct_size = sizeof(i);
+      check(aha_ac_info(ac_, &i));
+      if (accumulate && key_counts->size() != i.n_keys) throw Error(AHA_E_INVALID, "key_counts holds K entries");
+      kc = accumulate ? *key_counts : std::vector<uint64_t>(i.n_keys, 0);
+    }
+    uint64_t n = 0;
+    check(aha_feed_count_batch(f_, reinterpret_cast<const uint8_t *>(corpus.data()), piece_offsets.data(), seq_ids.data(), D,
+                               accumulate ? AHA_COUNT_ACCUMULATE : 0u, key_counts ? kc.data() : nullptr, pho.data(), b.data(),
+                               &n));
+    if (key_counts) *key_counts = std::move(kc);
+    if (piece_hit_offsets) *piece_hit_offsets = std::move(pho);
+    if (bases) *bases = std::move(b);
+    return n;
+  }
+  // the next piece of one sequence: its hits per key (K entries)
+  std::vector<uint64_t> count(uint32_t seq, std::string_view piece) {
+    std::vector<uint64_t> kc;
+    count_batch(piece, {0, piece.size()}, {seq}, &kc);
+    return kc;
+  }
   void reset(uint32_t seq = UINT32_MAX) { check(aha_feed_reset(f_, seq)); }
   // {bytes, chars} fed to the sequence so far
   std::pair<uint64_t, uint64_t> position(uint32_t seq) const {

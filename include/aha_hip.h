@@ -398,7 +398,8 @@ int32_t aha_ac_count_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uin
  * limit; a piece must be shorter than 2^31 bytes minus Lmax (AHA_E_TOO_LONG).  Within one call a sequence appears at most
  * once (AHA_E_INVALID); pieces may come in any order and a call may name any subset of the sequences.  A call that fails
  * changes nothing, AHA_E_CAPACITY included: *n_hits is then the exact count and the same call with a larger buffer gives what
- * the first would have.  No separator filter, no match_longest, no counts (follow-ups).  Errors: aha_last_error(ac).  Calls
+ * the first would have.  Counts: aha_feed_count_batch* below.  No separator filter, no match_longest (follow-ups).
+ * Errors: aha_last_error(ac).  Calls
  * on one feed are serialised (a mutex in the feed); different feeds and plain calls on the handle run side by side.
  * Pipeline (aha_amd/csrc/feed.cpp, scan_feed.hip): with W = max(Lmax-1, 0) the feed keeps the last
  * min(W, length) bytes of every sequence on the device.  A call matches one window batch of at most 4 W bytes per piece (the
@@ -425,6 +426,29 @@ int32_t aha_feed_match_batch(aha_feed *f, const uint8_t *corpus, const uint64_t 
 int32_t aha_feed_match_batch_device(aha_feed *f, const uint8_t *d_corpus, const uint64_t *d_piece_offsets,
                                     const uint32_t *d_seq_ids, uint64_t n_pieces, uint64_t n_bytes, aha_hit *d_out,
                                     uint64_t cap, uint64_t *d_piece_hit_offsets /* D+1 or NULL */,
+                                    uint64_t *d_piece_bases /* D or NULL */, uint64_t *n_hits, void *stream);
+/* Feed counts: the same pieces as aha_feed_match_batch*, and what a match call of them would give as hits per key --
+ * key_counts[k] = its hits with value k (uint64, exactly K entries written) -- with its piece_hit_offsets, piece_bases and
+ * *n_hits, but without the hit list.  The sequences move on exactly as the match call would move them, so match and count
+ * calls may be mixed freely on one feed (a char feed counts its lead bytes here too).  AHA_COUNT_ACCUMULATE adds into
+ * key_counts instead of overwriting it: running totals over a stream of any length; any other flag bit is AHA_E_INVALID.
+ * key_counts == NULL: only the total, the offsets and the bases (no per-key pass; the feed still moves on).  No capacity, so
+ * no AHA_E_CAPACITY.  A call that fails changes nothing: neither the feed nor key_counts.  Errors and validation are those of
+ * the match entries.  Like a count call it writes none of the handle's back-off state; aha_ac_last_timing reports the main
+ * pass, which takes the engine aha_ac_count_batch of the same pieces takes.  Pipeline: the window batch
+ * matched as for a match call; the pieces counted as by aha_ac_count_batch_device into the feed's own K-word vector; the
+ * window hits added with sign (+1 for the context-and-head windows, -1 for the context alone and the head alone); only then
+ * the caller's key_counts, offsets and bases, and the feed's state.  Device memory beyond a match call's: 8 bytes per key
+ * (16 for the host entry), and no hit buffer for the pieces. */
+int32_t aha_feed_count_batch(aha_feed *f, const uint8_t *corpus, const uint64_t *piece_offsets, const uint32_t *seq_ids,
+                             uint64_t n_pieces, uint32_t flags, uint64_t *key_counts /* K or NULL */,
+                             uint64_t *piece_hit_offsets /* D+1 or NULL */, uint64_t *piece_bases /* D or NULL */,
+                             uint64_t *n_hits);
+/* Device-resident form: d_ pointers are HBM on the handle's device, validated on the device before anything is indexed with
+ * them; *n_hits is host memory; blocks until final. */
+int32_t aha_feed_count_batch_device(aha_feed *f, const uint8_t *d_corpus, const uint64_t *d_piece_offsets,
+                                    const uint32_t *d_seq_ids, uint64_t n_pieces, uint64_t n_bytes, uint32_t flags,
+                                    uint64_t *d_key_counts /* K or NULL */, uint64_t *d_piece_hit_offsets /* D+1 or NULL */,
                                     uint64_t *d_piece_bases /* D or NULL */, uint64_t *n_hits, void *stream);
 
 /* Frees the handle's device scratch (it grows with the largest batch seen and is otherwise kept for reuse). */
