@@ -284,10 +284,11 @@ class AC:
             return out[: n.value], dho
 
     def match_batch_device(self, corpus, doc_offsets, out, doc_hit_offsets=None, sep=None, chars=False,
-                           stream=None, words=None, n_words=None):
+                           stream=None, words=None, n_words=None, longest=0):
         """Device-resident batch match on torch CUDA tensors (uint8 corpus,
         int64/uint64 doc offsets, int32 [cap,3] out).  Returns the hit count;
         raises AhaError(AHA_E_CAPACITY) with .required when out is too small.
+        longest: as in match_batch.
         words (int32, >= 2 cap + cap / 1024 + 2 elements) + n_words (int64[1]): the hits also as the 4-byte exchange stream
         (aha_ac_match_batch_device_stream: written by the expansion itself where the character-level engine runs)."""
         import torch
@@ -297,7 +298,7 @@ class AC:
         assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous()
         D = doc_offsets.numel() - 1
         cap = out.numel() // 3
-        p = _params(chars, sep)
+        p = _params(chars, sep, longest)
         n = C.c_uint64(0)
         s = stream if stream is not None else torch.cuda.current_stream(corpus.device).cuda_stream
         dho = doc_hit_offsets.data_ptr() if doc_hit_offsets is not None else None
@@ -820,13 +821,14 @@ class ACGroup:
             raise AhaError(rc)
         return bounds
 
-    def match_batch(self, corpus, doc_offsets, chars=False, cap=None):
+    def match_batch(self, corpus, doc_offsets, chars=False, cap=None, longest=0):
+        """AC.match_batch over the group's shards (longest: as there)."""
         if isinstance(corpus, (bytes, bytearray)):
             corpus = np.frombuffer(bytes(corpus), dtype=np.uint8)
         corpus = np.ascontiguousarray(corpus, dtype=np.uint8)
         doc_offsets = np.ascontiguousarray(doc_offsets, dtype=np.uint64)
         D = doc_offsets.size - 1
-        p = _params(chars, None)
+        p = _params(chars, None, longest)
         dho = np.zeros(D + 1, dtype=np.uint64)
         if cap is None:
             cap = max(64, corpus.size // 8)

@@ -299,6 +299,18 @@ def test_stale_end_replay_matches_the_oracles_cedar():
         assert _stale_paths_of(AC.compile_packed(blob, offs, host_only=True), keys) == want
 
 
+def test_stale_end_replay_on_the_full_headline_key_set():
+    """The replay on cfg 3's whole key set (100 000 keys, 10 826 stale END nodes): the compact image that the GPU
+    longest tests run; cfg 5's million keys (108 504) are checked in tests/test_gpu_longest.py."""
+    from aha_amd import synth
+
+    blob, offs, _nf = synth.keys(3)
+    keys = [bytes(blob[offs[i]:offs[i + 1]]) for i in range(offs.size - 1)]
+    want = orc.AC.compile_packed(blob, offs).stale_paths()
+    assert len(want) == 10_826
+    assert _stale_paths_of(AC.compile_packed(blob, offs, host_only=True), keys) == want
+
+
 def test_compile_time_of_the_headline_key_set():
     """Row a7 (src/aha/ac.cr:62-112): compile is the drop-in's first call.  cfg 3's 100k keys with the character-level
     image: 0.6 s here (round 3: 21 s, the unit image's first-fit scan); the bound leaves room for a loaded CI host."""
