@@ -62,6 +62,10 @@ class aha_ac_info_t(C.Structure):
                 ("pair_engine", C.c_uint32)]
 
 
+class aha_key_count(C.Structure):
+    _fields_ = [("key", C.c_int32), ("count", C.c_uint32)]
+
+
 class aha_timing(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_kernels", C.c_uint32), ("ms_total", C.c_float),
                 ("ms_count", C.c_float), ("ms_scan", C.c_float), ("ms_write", C.c_float),
@@ -137,6 +141,10 @@ SIGNATURES = {
     "aha_corpus_device": (_i32, [_vp]),
     "aha_ac_set_profiling": (_i32, [_vp, _i32]),
     "aha_ac_last_timing": (_i32, [_vp, C.POINTER(aha_timing)]),
+    "aha_ac_doc_counts_batch": (_i32, [_vp, _vp, _vp, _u64, C.POINTER(aha_match_params), _vp, _u64, _vp, C.POINTER(_u64),
+                                       C.POINTER(_u64)]),
+    "aha_ac_doc_counts_batch_device": (_i32, [_vp, _vp, _vp, _u64, _u64, C.POINTER(aha_match_params), _vp, _u64, _vp,
+                                              C.POINTER(_u64), C.POINTER(_u64), _vp]),
     "aha_ac_count_batch": (_i32, [_vp, _vp, _vp, _u64, C.POINTER(aha_match_params), _u32, _vp, _vp, C.POINTER(_u64)]),
     "aha_ac_count_batch_device": (_i32, [_vp, _vp, _vp, _u64, _u64, C.POINTER(aha_match_params), _u32, _vp, _vp,
                                          C.POINTER(_u64), _vp]),

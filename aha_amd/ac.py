@@ -24,6 +24,7 @@ from . import _native as N
 Hit = namedtuple("Hit", ["start", "end", "value"])
 
 HIT_DTYPE = np.dtype([("start", "<i4"), ("end", "<i4"), ("value", "<i4")])
+KEY_COUNT_DTYPE = np.dtype([("key", "<i4"), ("count", "<u4")])  # aha_key_count (document counts)
 
 
 class AhaError(RuntimeError):
@@ -439,6 +440,96 @@ class AC:
         self._check(rc)
         counts = kc.download(np.zeros(self.n_keys, dtype=np.uint64)) if kc else None
         return counts, dho.download(np.zeros(D + 1, dtype=np.uint64)), int(n.value)
+
+    # -- document counts: hits per key within each document (aha_ac_doc_counts_batch*) ---------------
+    def doc_counts_batch(self, corpus, doc_offsets, sep=None, chars=False, cap=None):
+        """The document x key table of match_batch(corpus, doc_offsets, sep) without the hit list:
+        -> (pairs, doc_pair_offsets uint64[D+1]); pairs[doc_pair_offsets[d]:doc_pair_offsets[d+1]] holds document d's
+        {key, count}, ascending by key.  cap None: a sizing call first.  chars changes no count."""
+        if isinstance(corpus, (bytes, bytearray)):
+            corpus = np.frombuffer(bytes(corpus), dtype=np.uint8)
+        corpus = np.ascontiguousarray(corpus, dtype=np.uint8)
+        doc_offsets = np.ascontiguousarray(doc_offsets, dtype=np.uint64)
+        D = doc_offsets.size - 1
+        p = _params(chars, sep)
+        dpo = np.zeros(D + 1, dtype=np.uint64)
+        n = C.c_uint64(0)
+        L = N.lib()
+        if cap is None:
+            rc = L.aha_ac_doc_counts_batch(self._h, _ptr(corpus), _ptr(doc_offsets), D, C.byref(p), None, 0, _ptr(dpo),
+                                           C.byref(n), None)
+            if rc != N.AHA_E_CAPACITY:
+                self._check(rc)
+                return np.zeros(0, dtype=KEY_COUNT_DTYPE), dpo
+            cap = int(n.value)
+        out = np.zeros(max(int(cap), 1), dtype=KEY_COUNT_DTYPE)
+        rc = L.aha_ac_doc_counts_batch(self._h, _ptr(corpus), _ptr(doc_offsets), D, C.byref(p), _ptr(out), int(cap), _ptr(dpo),
+                                       C.byref(n), None)
+        self._check(rc)
+        return out[: int(n.value)], dpo
+
+    def doc_counts(self, seq, sep=None):
+        """Hits per key of match(seq, sep) on one sequence: {key id: count}."""
+        b = _b(seq)
+        pairs, _ = self.doc_counts_batch(np.frombuffer(b, dtype=np.uint8), np.array([0, len(b)], dtype=np.uint64), sep=sep)
+        return {int(k): int(c) for k, c in zip(pairs["key"], pairs["count"])}
+
+    def doc_counts_batch_device(self, corpus, doc_offsets, out, doc_pair_offsets=None, sep=None, chars=False, cap=None,
+                                stream=None):
+        """Device-resident document counts on torch CUDA tensors: uint8 corpus, int64/uint64 doc offsets, out int32 [cap, 2]
+        ({key, count} rows) or None (a sizing call), doc_pair_offsets int64/uint64 [D+1] or None.
+        -> (n_pairs, n_hits); raises AhaError(AHA_E_CAPACITY) when out is too small (e.n_required = the pairs needed)."""
+        import torch
+
+        assert corpus.is_cuda and corpus.dtype == torch.uint8 and corpus.is_contiguous()
+        assert doc_offsets.is_cuda and doc_offsets.dtype in (torch.int64, torch.uint64)
+        if out is not None:
+            if not (out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.dim() == 2 and out.shape[1] == 2):
+                raise ValueError("out must be a contiguous int32 CUDA tensor of shape [cap, 2]")
+            cap = out.shape[0] if cap is None else min(int(cap), out.shape[0])
+        else:
+            cap = 0
+        if doc_pair_offsets is not None and not (doc_pair_offsets.is_cuda and doc_pair_offsets.dtype in (torch.int64, torch.uint64)
+                                                 and doc_pair_offsets.is_contiguous()
+                                                 and doc_pair_offsets.numel() >= doc_offsets.numel()):
+            raise ValueError("doc_pair_offsets must be a contiguous int64/uint64 CUDA tensor of at least D + 1 entries")
+        D = doc_offsets.numel() - 1
+        p = _params(chars, sep)
+        n, nh = C.c_uint64(0), C.c_uint64(0)
+        s = stream if stream is not None else torch.cuda.current_stream(corpus.device).cuda_stream
+        rc = N.lib().aha_ac_doc_counts_batch_device(
+            self._h, corpus.data_ptr(), doc_offsets.data_ptr(), D, corpus.numel(), C.byref(p),
+            out.data_ptr() if out is not None and cap else None, cap,
+            doc_pair_offsets.data_ptr() if doc_pair_offsets is not None else None, C.byref(n), C.byref(nh), C.c_void_p(s))
+        if rc == N.AHA_E_CAPACITY:
+            e = AhaError(rc, N.lib().aha_strerror(rc).decode())
+            e.n_required = int(n.value)
+            e.n_hits = int(nh.value)
+            raise e
+        self._check(rc)
+        return int(n.value), int(nh.value)
+
+    def doc_counts_corpus(self, corpus, sep=None, chars=False):
+        """Document counts of a batch that already lives in HBM (DeviceCorpus), downloaded:
+        -> (pairs, doc_pair_offsets uint64[D+1], n_hits)."""
+        D = corpus.n_docs
+        p = _params(chars, sep)
+        dev = corpus.device
+        dpo = DeviceBuffer(dev, (D + 1) * 8)
+        n, nh = C.c_uint64(0), C.c_uint64(0)
+        L = N.lib()
+        rc = L.aha_ac_doc_counts_batch_device(self._h, corpus.ptr, corpus.doc_ptr, D, corpus.n_bytes, C.byref(p), None, 0,
+                                              dpo.ptr, C.byref(n), C.byref(nh), None)
+        if rc != N.AHA_E_CAPACITY:
+            self._check(rc)
+            return np.zeros(0, dtype=KEY_COUNT_DTYPE), dpo.download(np.zeros(D + 1, dtype=np.uint64)), int(nh.value)
+        cap = int(n.value)
+        out = DeviceBuffer(dev, cap * 8)
+        rc = L.aha_ac_doc_counts_batch_device(self._h, corpus.ptr, corpus.doc_ptr, D, corpus.n_bytes, C.byref(p), out.ptr, cap,
+                                              dpo.ptr, C.byref(n), C.byref(nh), None)
+        self._check(rc)
+        return (out.download(np.zeros(cap, dtype=KEY_COUNT_DTYPE)), dpo.download(np.zeros(D + 1, dtype=np.uint64)),
+                int(nh.value))
 
     # -- exchange format of the multi-GPU all-gatherv: {end, value} pairs <-> Hit triples ------------
     def hits_pack_device(self, hits, n, pairs, stream=None):

@@ -23,6 +23,11 @@ void free_scratch(Scratch *sc, bool all) {
     if (b.p) (void)hipFree(b.p);
     b = Buf();
   }
+  for (auto &b : sc->dcbuf) {
+    if (b.p) (void)hipFree(b.p);
+    b = Buf();
+  }
+  sc->dc_rows_clear = false;
   void **scratch[] = {(void **)&sc->d_counts, (void **)&sc->d_leads, (void **)&sc->d_blk_hits, (void **)&sc->d_blk_leads,
                       (void **)&sc->d_docg};
   for (void **p : scratch) {
@@ -56,6 +61,7 @@ uint64_t scratch_bytes(const Scratch *sc) {
   for (auto &b : sc->v2buf) n += b.bytes;
   for (auto &b : sc->hostbuf) n += b.bytes;
   for (auto &b : sc->cntbuf) n += b.bytes;
+  for (auto &b : sc->dcbuf) n += b.bytes;
   n += sc->cap_chunks * 8 + sc->cap_blocks * 16 + sc->cap_docs * 8;
   return n;
 }
@@ -1184,6 +1190,91 @@ int32_t aha_ac_count_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uin
   Lease lease(ac);
   return device_count(ac, lease.get(), d_corpus, d_doc_offsets, n_docs, n_bytes, params, flags, d_key_counts, d_doc_hit_offsets,
                       n_hits, stream, false);
+}
+
+// ---- document counts (aha_ac_doc_counts_batch*) --------------------------------------------------------------------
+// the argument checks both entries share: before any device work, so they hold on a host-only handle
+static int32_t doc_counts_args(aha_ac *ac, const uint64_t *doc_offsets, const aha_match_params *params, uint64_t *n_pairs) {
+  if (!ac || !n_pairs || !doc_offsets) return AHA_E_INVALID;
+  MatchArgs M{};
+  int longest = 0;
+  int32_t rc = fill_params(ac, params, M, &longest);
+  if (rc) return rc;
+  if (longest) {
+    tls_err = "document counts have no match_longest form";
+    return AHA_E_INVALID;
+  }
+  if (ac->device < 0) {
+    tls_err = aha_strerror(AHA_E_NO_DEVICE);
+    return AHA_E_NO_DEVICE;
+  }
+  return AHA_OK;
+}
+
+int32_t aha_ac_doc_counts_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                                       uint64_t n_bytes, const aha_match_params *params, aha_key_count *d_out, uint64_t cap,
+                                       uint64_t *d_doc_pair_offsets, uint64_t *n_pairs, uint64_t *n_hits, void *stream) {
+  int32_t rc = doc_counts_args(ac, d_doc_offsets, params, n_pairs);
+  if (rc) return rc;
+  if (cap && !d_out) return AHA_E_INVALID;
+  Lease lease(ac);
+  return device_doc_counts(ac, lease.get(), d_corpus, d_doc_offsets, n_docs, n_bytes, params, d_out, cap, d_doc_pair_offsets,
+                           n_pairs, n_hits, stream, false);
+}
+
+// The host entry: the batch goes up in one piece into the staging buffers of the leased scratch set (the match entry's), over
+// its private stream; the pairs below the capacity and the offsets come back.
+int32_t aha_ac_doc_counts_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc_offsets, uint64_t n_docs,
+                                const aha_match_params *params, aha_key_count *out, uint64_t cap, uint64_t *doc_pair_offsets,
+                                uint64_t *n_pairs, uint64_t *n_hits) {
+  int32_t rc = doc_counts_args(ac, doc_offsets, params, n_pairs);
+  if (rc) return rc;
+  if (cap && !out) return AHA_E_INVALID;
+  if (doc_offsets[0] != 0) return AHA_E_INVALID;
+  for (uint64_t d = 0; d < n_docs; d++) {
+    if (doc_offsets[d + 1] < doc_offsets[d]) return AHA_E_INVALID;
+    if (doc_offsets[d + 1] - doc_offsets[d] >= 0x7FFFFFFFull) return AHA_E_TOO_LONG;
+  }
+  const uint64_t n_bytes = doc_offsets[n_docs];
+  if (n_bytes && !corpus) return AHA_E_INVALID;
+  *n_pairs = 0;
+  DeviceGuard g(ac->device);
+  Lease lease(ac);
+  Scratch *sc = lease.get();
+  auto reserve = [&](int i, size_t bytes) -> void * {
+    Buf &b = sc->hostbuf[i];
+    if (b.bytes < bytes) {
+      if (b.p) (void)hipFree(b.p);
+      b.p = nullptr;
+      b.bytes = 0;
+      const size_t want = bytes + bytes / 4 + 4096;
+      if (hipMalloc(&b.p, want) != hipSuccess) return nullptr;
+      b.bytes = want;
+    }
+    return b.p;
+  };
+  uint8_t *d_corpus = (uint8_t *)reserve(0, n_bytes + 64);
+  uint64_t *d_doc = (uint64_t *)reserve(1, (n_docs + 1) * 8);
+  uint64_t *d_dpo = (uint64_t *)reserve(2, (n_docs + 1) * 8);
+  aha_key_count *d_out = cap ? (aha_key_count *)reserve(3, cap * sizeof(aha_key_count)) : nullptr;
+  if (!d_corpus || !d_doc || !d_dpo || (cap && !d_out) || !host_streams(sc)) {
+    tls_err = "hipMalloc / hipStreamCreate failed for the staging buffers";
+    return AHA_E_HIP;
+  }
+  hipStream_t s = sc->hs[1];
+  HIPCHK(ac, hipMemcpyAsync(d_doc, doc_offsets, (n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+  if (n_bytes) HIPCHK(ac, hipMemcpyAsync(d_corpus, corpus, n_bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  rc = device_doc_counts(ac, sc, d_corpus, d_doc, n_docs, n_bytes, params, d_out, cap, d_dpo, n_pairs, n_hits, s,
+                         true);  // the offsets were checked on the host above
+  if (rc != AHA_OK && rc != AHA_E_CAPACITY) return rc;
+  const std::string err = tls_err;
+  const uint64_t n_back = std::min(*n_pairs, cap);
+  if (n_back) HIPCHK(ac, hipMemcpyAsync(out, d_out, n_back * sizeof(aha_key_count), hipMemcpyDeviceToHost, s));
+  if (doc_pair_offsets) HIPCHK(ac, hipMemcpyAsync(doc_pair_offsets, d_dpo, (n_docs + 1) * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  if (rc) tls_err = err;
+  return rc;
 }
 
 // ---- device buffers behind the C ABI (include/aha_hip.h) ---------------------------------------------------------

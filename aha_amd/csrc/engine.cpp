@@ -4,10 +4,13 @@
 // to the two-pass engine).  The C ABI around it is capi.cpp; what they share is handle.hpp.
 #include "handle.hpp"
 
+#include <chrono>
+
 namespace ahai {
 
 // ---- single-traversal engine: sizing, scratch, orchestration ----------------
 constexpr size_t kLdsPerCU = 160 * 1024;
+constexpr uint64_t kV2MaxRegionBytes = 48ull << 30;
 
 // The skip-ahead traversal (scan_skip.hip) can take a handle's plain byte-offset matches when the unit image has 22-bit
 // bases and no key is a single unit.  It is OPT-IN (AHA_ENGINE=skip -- the unit image for every eligible key set like "unit" --
@@ -64,7 +67,25 @@ void plan_engine(aha_ac *ac, const Placement &pl) {
   ac->v2_lds_slots = (uint32_t)std::min<size_t>(std::min<size_t>(budget / slot, cap_slots), ac->n_slots) & ~3u;
 }
 
+// Document counts: the bounds and thresholds of device_doc_counts, read once per handle (tests lower them to reach every form
+// and the document ranges with small batches; DESIGN.md sections 4.11 and 7).
+static void doccount_setup(aha_ac *ac) {
+  auto env = [](const char *name, uint64_t dflt, uint64_t lo, uint64_t hi) {
+    const char *v = getenv(name);
+    if (!v || atoll(v) <= 0) return dflt;
+    return std::min(std::max<uint64_t>((uint64_t)atoll(v), lo), hi);
+  };
+  const uint64_t K = ac->aut.n_keys;
+  ac->dc_hit_bytes = env("AHA_DOCCOUNT_HIT_BYTES", kV2MaxRegionBytes, 12, kV2MaxRegionBytes);
+  ac->dc_row_bytes = env("AHA_DOCCOUNT_ROW_BYTES", 1ull << 30, 4, 1ull << 34);
+  ac->dc_sort_max = (uint32_t)env("AHA_DOCCOUNT_SORT_MAX", kDcSortMax, 1, kDcSortMax);
+  ac->dc_range_keys = (uint32_t)env("AHA_DOCCOUNT_RANGE_KEYS", kDcRangeKeys, 1, kDcRangeKeys);
+  // the dense form costs O(K) per document: from K / 8 hits on
+  ac->dc_dense_min = (uint32_t)env("AHA_DOCCOUNT_DENSE_MIN", std::max<uint64_t>(ac->dc_sort_max + 1ull, K / 8), 1, 0x7FFFFFFFull);
+}
+
 void v2_setup(aha_ac *ac) {
+  doccount_setup(ac);
   const char *eng = getenv("AHA_ENGINE");
   if (eng && strcmp(eng, "v1") == 0) return;
   int cus = 0;
@@ -205,8 +226,6 @@ StreamFmt stream_fmt(const aha_ac *ac) {
   if (vb + lb + 10 <= 32) return StreamFmt{std::min(12u, 32 - vb - lb), lb};
   return StreamFmt{12, 0};
 }
-
-constexpr uint64_t kV2MaxRegionBytes = 48ull << 30;
 
 // returns AHA_OK, an error, +1 when the caller must fall back to the two-pass engine, +2 when a region overflowed
 // the pinned words a call's verdict and totals come back in, and their device address
@@ -489,7 +508,7 @@ int32_t match_v2(aha_ac *ac, Scratch *sc, MatchArgs &M1, hipStream_t s, uint64_t
     return AHA_E_TOO_LONG;
   }
   if (sc->h_v2[1] == 3 && pair) {  // the pair engine gave the batch up (documents of a few bytes, a piece dense with events): engine 4 takes it
-    if (!counting) ac->pair_off.fetch_add(1, std::memory_order_relaxed);  // (three times: the handle stops trying; a count call
+    if (!counting && !M1.neutral) ac->pair_off.fetch_add(1, std::memory_order_relaxed);  // (three times: the handle stops trying; a count call
                                                                            // leaves the handle's history as it found it)
     M1.no_pair = 1;
   }
@@ -563,7 +582,7 @@ static int32_t check_docs_now(aha_ac *ac, Scratch *sc, const uint64_t *d_doc_off
 
 int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
                      uint64_t n_bytes, const aha_match_params *params, aha_hit *d_out, uint64_t cap, uint64_t *d_doc_hit_offsets,
-                     uint64_t *n_hits, void *stream, bool offsets_checked, const PackOut *pk, bool *packed, bool quiet) {
+                     uint64_t *n_hits, void *stream, bool offsets_checked, const PackOut *pk, bool *packed, bool quiet, bool neutral) {
   if (!ac || !n_hits || !d_doc_offsets) return AHA_E_INVALID;
   if (ac->device < 0) {
     tls_err = aha_strerror(AHA_E_NO_DEVICE);
@@ -578,6 +597,7 @@ int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
   if (rc) return rc;
   if ((rc = ready_events(ac, sc))) return rc;
   if (quiet) M.no_filter = M.no_pair = 1;  // (neither engine that keeps a history of hand-backs)
+  M.neutral = neutral ? 1 : 0;
   *n_hits = 0;
   auto check_now = [&]() { return check_docs_now(ac, sc, d_doc_offsets, n_docs, n_bytes, s); };
   // The single-traversal pipelines validate on the device in front of their traversal (match_v2); every other path -- an
@@ -669,7 +689,9 @@ int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
     // a handle whose batches keep coming back from the prefix-filter engine (text dense with key starts) skips it for 2, 4,
     // .. 64 calls before it tries again: a batch that is handed back has paid for the filter and part of the walks
     const int pm = M.chars ? 1 : 0;  // (calls with char offsets keep their own count)
-    if (ac->pf_ok && !quiet) {  // (calls on one handle may run side by side: the count goes down by compare-exchange, never below 0)
+    if (ac->pf_ok && neutral) {  // (as the next match call would, without counting down)
+      if (ac->pf_skip[pm].load(std::memory_order_relaxed)) M.no_filter = 1;
+    } else if (ac->pf_ok && !quiet) {  // (calls on one handle may run side by side: the count goes down by compare-exchange, never below 0)
       uint32_t v = ac->pf_skip[pm].load(std::memory_order_relaxed);
       while (v && !ac->pf_skip[pm].compare_exchange_weak(v, v - 1, std::memory_order_relaxed)) {
       }
@@ -680,10 +702,12 @@ int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
     if (rc == 3) {  // the prefix-filter engine handed the batch back: once more on the byte-level engine
       repeats++;
       M.no_filter = 1;
-      const uint32_t streak = std::min(ac->pf_streak[pm].fetch_add(1, std::memory_order_relaxed) + 1, 6u);
-      ac->pf_skip[pm].store(1u << streak, std::memory_order_relaxed);
+      if (!neutral) {
+        const uint32_t streak = std::min(ac->pf_streak[pm].fetch_add(1, std::memory_order_relaxed) + 1, 6u);
+        ac->pf_skip[pm].store(1u << streak, std::memory_order_relaxed);
+      }
       rc = match_v2(ac, sc, M, s, n_hits, kRegions);
-    } else if (tried && rc == AHA_OK) {
+    } else if (tried && rc == AHA_OK && !neutral) {
       ac->pf_streak[pm].store(0, std::memory_order_relaxed);
     }
     if (rc == 2) {  // denser than cap said: regions of one event per byte
@@ -1014,6 +1038,296 @@ int32_t device_count(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
     }
   }
   return count_two_pass(ac, sc, M, s, n_hits, single ? 1 : 0);
+}
+
+
+// ---- document counts (aha_ac_doc_counts_batch*) ----------------------------------------------------------------------
+static void *dc_reserve(Scratch *sc, int i, size_t bytes) {
+  Buf &b = sc->dcbuf[i];
+  if (b.bytes < bytes) {
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr;
+    b.bytes = 0;
+    if (i == 6) sc->dc_rows_clear = false;
+    const size_t want = bytes + bytes / 8 + 256;
+    if (hipMalloc(&b.p, want) != hipSuccess && ((void)hipGetLastError(), hipMalloc(&b.p, bytes) != hipSuccess)) {
+      (void)hipGetLastError();
+      b.p = nullptr;
+      return nullptr;
+    }
+    b.bytes = bytes;  // (what is known to be there)
+  }
+  return b.p;
+}
+
+// One device-resident batch as {key, count} pairs per document (aha_ac_doc_counts_batch_device).
+//   1. device_count without key counts: the hits per document and their total, no capacity (and the offsets' validation).
+//   2. Ranges of whole documents whose hits fit the bound of the hit buffer (one range, as a rule): a match of the range with
+//      cap = its hits into the call's scratch -- every engine, the handle's back-off state read and never written.
+//   3. Per document one of the three forms of scan_doccount.hip, chosen from its hit count; the pairs per document come back,
+//      the host adds them up (the offsets, the capacity check), kdc_gather writes the pairs below the capacity.
+// A single document whose hits are beyond the bound is never matched: a count call over it alone gives its key counts -- the
+// dense form's row --, which are compacted like one.
+int32_t device_doc_counts(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                          uint64_t n_bytes, const aha_match_params *params, aha_key_count *d_out, uint64_t cap,
+                          uint64_t *d_doc_pair_offsets, uint64_t *n_pairs, uint64_t *n_hits_out, void *stream, bool offsets_checked) {
+  if (!ac || !n_pairs || !d_doc_offsets) return AHA_E_INVALID;
+  {
+    MatchArgs M{};
+    int longest = 0;
+    int32_t rc0 = fill_params(ac, params, M, &longest);
+    if (rc0) return rc0;
+    if (longest) {
+      tls_err = "document counts have no match_longest form";
+      return AHA_E_INVALID;
+    }
+  }
+  if (ac->device < 0) {
+    tls_err = aha_strerror(AHA_E_NO_DEVICE);
+    return AHA_E_NO_DEVICE;
+  }
+  if (cap && !d_out) return AHA_E_INVALID;
+  DeviceGuard g(ac->device);
+  hipStream_t s = (hipStream_t)stream;
+  const uint64_t D = n_docs, K = ac->aut.n_keys;
+  *n_pairs = 0;
+  if (n_hits_out) *n_hits_out = 0;
+  // byte offsets throughout: char offsets change no count
+  aha_match_params pb;
+  memset(&pb, 0, sizeof(pb));
+  if (params) memcpy(&pb, params, std::min<size_t>(params->struct_size, sizeof(pb)));
+  pb.char_offsets = 0;
+  const aha_match_params *p = params ? &pb : nullptr;
+  auto nomem = [&]() {
+    tls_err = "hipMalloc failed for the scratch of a document-count call";
+    return AHA_E_HIP;
+  };
+  int32_t rc;
+  uint64_t *d_dho = (uint64_t *)dc_reserve(sc, 0, (D + 1) * 8);
+  if (!d_dho) return nomem();
+  uint64_t n_hits = 0;
+  if ((rc = device_count(ac, sc, d_corpus, d_doc_offsets, D, n_bytes, p, 0, nullptr, d_dho, &n_hits, stream, offsets_checked))) return rc;
+  if (n_hits_out) *n_hits_out = n_hits;
+  std::vector<uint64_t> off, hd, dpo, rel;
+  std::vector<uint32_t> np;
+  std::vector<DcItem> items;
+  std::vector<const uint32_t *> srcs;
+  try {
+    hd.resize(D + 1);
+    dpo.assign(D + 1, 0);
+  } catch (...) {
+    return AHA_E_NOMEM;
+  }
+  HIPCHK(ac, hipMemcpyAsync(hd.data(), d_dho, (D + 1) * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  const auto t_all0 = std::chrono::steady_clock::now();
+  double ms_match = 0.0;
+  aha_timing t_trav;  // the timing of a pass that traversed (profiling)
+  memset(&t_trav, 0, sizeof(t_trav));
+  if (ac->profiling.load()) {
+    std::lock_guard<std::mutex> lk(ac->last_mu);
+    t_trav = ac->last;
+  }
+  const uint32_t sort_max = ac->dc_sort_max, dense_min = ac->dc_dense_min;
+  // what a document holds in scratch while its range is worked on: its hits, and in the range form its pairs beside them
+  auto form = [&](uint64_t h) { return h <= sort_max ? 0 : (h < dense_min ? 1 : 2); };
+  auto doc_bytes = [&](uint64_t h) { return h * sizeof(aha_hit) + (form(h) == 1 ? std::min<uint64_t>(h, K) * 8 : 0); };
+  uint64_t total = 0;
+  uint32_t ranges = 0;
+  for (uint64_t d0 = 0; d0 < D;) {
+    uint64_t d1 = d0, bytes = 0;
+    while (d1 < D && (d1 == d0 || bytes + doc_bytes(hd[d1 + 1] - hd[d1]) <= ac->dc_hit_bytes)) {
+      bytes += doc_bytes(hd[d1 + 1] - hd[d1]);
+      d1++;
+    }
+    const uint64_t nd = d1 - d0, rh = hd[d1] - hd[d0];
+    const bool solo = nd == 1 && bytes > ac->dc_hit_bytes;
+    if (rh == 0) {  // (no hit: the documents' offsets stand as they are)
+      for (uint64_t d = d0; d < d1; d++) dpo[d + 1] = total;
+      d0 = d1;
+      continue;
+    }
+    if (off.empty() && (d0 != 0 || d1 != D)) {
+      try {
+        off.resize(D + 1);
+      } catch (...) {
+        return AHA_E_NOMEM;
+      }
+      HIPCHK(ac, hipMemcpyAsync(off.data(), d_doc_offsets, (D + 1) * 8, hipMemcpyDeviceToHost, s));
+      HIPCHK(ac, hipStreamSynchronize(s));
+    }
+    // the range as a batch of its own: the caller's arrays where it is the whole batch
+    const uint8_t *text = d_corpus;
+    const uint64_t *d_rel = d_doc_offsets;
+    uint64_t nb = n_bytes;
+    if (d0 != 0 || d1 != D) {
+      nb = off[d1] - off[d0];
+      try {
+        rel.resize(nd + 1);
+      } catch (...) {
+        return AHA_E_NOMEM;
+      }
+      for (uint64_t d = 0; d <= nd; d++) rel[d] = off[d0 + d] - off[d0];
+      uint64_t *r = (uint64_t *)dc_reserve(sc, 2, (nd + 1) * 8);
+      if (!r) return nomem();
+      HIPCHK(ac, hipMemcpyAsync(r, rel.data(), (nd + 1) * 8, hipMemcpyHostToDevice, s));
+      d_rel = r;
+      text = d_corpus + off[d0];
+      if (reinterpret_cast<uintptr_t>(text) % 16 != 0) {  // (the kernels read aligned 16-byte pieces)
+        uint8_t *t = (uint8_t *)dc_reserve(sc, 3, nb + 64);
+        if (!t) return nomem();
+        HIPCHK(ac, hipMemcpyAsync(t, text, nb, hipMemcpyDeviceToDevice, s));
+        text = t;
+      }
+      HIPCHK(ac, hipStreamSynchronize(s));  // (rel is the host's until the copy has run)
+    }
+    uint32_t *d_np = (uint32_t *)dc_reserve(sc, 5, nd * 4);
+    if (!d_np) return nomem();
+    HIPCHK(ac, hipMemsetAsync(d_np, 0, nd * 4, s));
+    try {
+      srcs.assign(nd, nullptr);
+      np.resize(nd);
+      items.clear();
+    } catch (...) {
+      return AHA_E_NOMEM;
+    }
+    const auto t_m0 = std::chrono::steady_clock::now();
+    if (solo) {
+      unsigned long long *row = (unsigned long long *)dc_reserve(sc, 9, std::max<uint64_t>(K, 1) * 8);
+      uint32_t *tmp = (uint32_t *)dc_reserve(sc, 7, std::max<uint64_t>(K, 1) * 8);
+      DcItem *d_items = (DcItem *)dc_reserve(sc, 4, sizeof(DcItem));
+      if (!row || !tmp || !d_items) return nomem();
+      uint64_t got = 0;
+      if ((rc = device_count(ac, sc, text, d_rel, 1, nb, p, 0, (uint64_t *)row, nullptr, &got, stream, true))) return rc;
+      ms_match += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_m0).count();
+      items.assign(1, DcItem{0, tmp, 0, 0});
+      HIPCHK(ac, hipMemcpyAsync(d_items, items.data(), sizeof(DcItem), hipMemcpyHostToDevice, s));
+      doccount_launch_compact64(d_items, row, (uint32_t)K, d_np, s);
+      srcs[0] = tmp;
+    } else {
+      aha_hit *d_hits = (aha_hit *)dc_reserve(sc, 1, rh * sizeof(aha_hit));
+      if (!d_hits) return nomem();
+      uint64_t got = 0;
+      rc = device_match(ac, sc, text, d_rel, nd, nb, p, d_hits, rh, nullptr, &got, stream, true, nullptr, nullptr, false, true);
+      if (rc) return rc;
+      if (got != rh) {
+        tls_err = "document counts: the match and the count of a range disagree";
+        return AHA_E_HIP;
+      }
+      ms_match += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_m0).count();
+      // the work items: [sort | range | dense documents (a row each, in groups) | slices of the dense documents' hits]
+      uint32_t n_form[3] = {0, 0, 0};
+      uint64_t range_pairs = 0, n_slices = 0;
+      for (uint64_t d = 0; d < nd; d++) {
+        const uint64_t h = hd[d0 + d + 1] - hd[d0 + d];
+        if (!h) continue;
+        const int f = form(h);
+        n_form[f]++;
+        if (f == 1) range_pairs += std::min<uint64_t>(h, K);
+        if (f == 2) n_slices += (h + kDcSliceHits - 1) / kDcSliceHits;
+      }
+      const uint64_t rows_max = std::max<uint64_t>(1, ac->dc_row_bytes / (std::max<uint64_t>(K, 1) * 4));
+      const uint64_t n_rows = std::min<uint64_t>(n_form[2], rows_max);
+      uint32_t *d_rtmp = range_pairs ? (uint32_t *)dc_reserve(sc, 7, range_pairs * 8) : nullptr;
+      uint32_t *d_rows = n_rows ? (uint32_t *)dc_reserve(sc, 6, n_rows * K * 4) : nullptr;
+      if ((range_pairs && !d_rtmp) || (n_rows && !d_rows)) return nomem();
+      if (n_rows && !sc->dc_rows_clear) HIPCHK(ac, hipMemsetAsync(d_rows, 0, sc->dcbuf[6].bytes, s));
+      const size_t o_range = n_form[0], o_dense = o_range + n_form[1], o_slice = o_dense + n_form[2];
+      try {
+        items.resize(o_slice + n_slices);
+      } catch (...) {
+        return AHA_E_NOMEM;
+      }
+      size_t at[3] = {0, o_range, o_dense}, at_slice = o_slice;
+      uint64_t rt = 0;
+      uint32_t *hw = reinterpret_cast<uint32_t *>(d_hits);
+      for (uint64_t d = 0; d < nd; d++) {
+        const uint64_t b = hd[d0 + d] - hd[d0], h = hd[d0 + d + 1] - hd[d0 + d];
+        if (!h) continue;
+        const int f = form(h);
+        uint32_t *out = hw + b * 3;  // over the document's own hits
+        if (f == 1) {
+          out = d_rtmp + 2 * rt;
+          rt += std::min<uint64_t>(h, K);
+        }
+        srcs[d] = out;
+        if (f == 2) {
+          const uint32_t row = (uint32_t)((at[2] - o_dense) % rows_max);
+          for (uint64_t x = 0; x < h; x += kDcSliceHits)
+            items[at_slice++] = DcItem{b + x, nullptr, (uint32_t)std::min<uint64_t>(kDcSliceHits, h - x), row};
+        }
+        items[at[f]++] = DcItem{b, out, (uint32_t)h, (uint32_t)d};
+      }
+      DcItem *d_items = (DcItem *)dc_reserve(sc, 4, std::max<size_t>(items.size(), 1) * sizeof(DcItem));
+      if (!d_items) return nomem();
+      HIPCHK(ac, hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(DcItem), hipMemcpyHostToDevice, s));
+      doccount_launch_sort(d_items, n_form[0], d_hits, d_np, s);
+      doccount_launch_range(d_items + o_range, n_form[1], d_hits, (uint32_t)K, ac->dc_range_keys, d_np, s);
+      if (n_form[2]) sc->dc_rows_clear = false;  // (until the last compaction has run)
+      size_t sl = o_slice;
+      for (uint64_t g0 = 0; g0 < n_form[2]; g0 += rows_max) {  // the dense documents, as many at a time as there are rows
+        const uint32_t gn = (uint32_t)std::min<uint64_t>(rows_max, n_form[2] - g0);
+        size_t sl1 = sl;
+        for (uint32_t r = 0; r < gn; r++) sl1 += (items[o_dense + g0 + r].n + kDcSliceHits - 1) / kDcSliceHits;
+        doccount_launch_add(d_items + sl, (uint32_t)(sl1 - sl), d_hits, d_rows, (uint32_t)K, 3u * ac->v2_grid + 3u, s);
+        doccount_launch_compact(d_items + o_dense + g0, gn, d_rows, (uint32_t)K, d_np, s);
+        sl = sl1;
+      }
+    }
+    HIPCHK(ac, hipGetLastError());
+    HIPCHK(ac, hipMemcpyAsync(np.data(), d_np, nd * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(ac, hipStreamSynchronize(s));
+    sc->dc_rows_clear = true;
+    // the range's pair offsets; the pairs below the capacity to their place
+    try {
+      rel.resize(nd + 1);
+    } catch (...) {
+      return AHA_E_NOMEM;
+    }
+    rel[0] = 0;
+    for (uint64_t d = 0; d < nd; d++) {
+      rel[d + 1] = rel[d] + np[d];
+      dpo[d0 + d + 1] = total + rel[d + 1];
+    }
+    const uint64_t room = cap > total ? cap - total : 0, n_write = std::min<uint64_t>(room, rel[nd]);
+    if (n_write) {
+      uint64_t *d_po = (uint64_t *)dc_reserve(sc, 8, (nd + 1) * 8 + nd * sizeof(uint32_t *));
+      if (!d_po) return nomem();
+      const uint32_t **d_src = reinterpret_cast<const uint32_t **>(d_po + nd + 1);
+      HIPCHK(ac, hipMemcpyAsync(d_po, rel.data(), (nd + 1) * 8, hipMemcpyHostToDevice, s));
+      HIPCHK(ac, hipMemcpyAsync(d_src, srcs.data(), nd * sizeof(uint32_t *), hipMemcpyHostToDevice, s));
+      doccount_launch_gather(d_po, d_src, nd, n_write, d_out + total, s);
+      HIPCHK(ac, hipGetLastError());
+      HIPCHK(ac, hipStreamSynchronize(s));
+    }
+    total += rel[nd];
+    if (ac->profiling.load() && !ranges) {
+      std::lock_guard<std::mutex> lk(ac->last_mu);
+      t_trav = ac->last;
+    }
+    ranges++;
+    d0 = d1;
+  }
+  if (d_doc_pair_offsets) {
+    HIPCHK(ac, hipMemcpyAsync(d_doc_pair_offsets, dpo.data(), (D + 1) * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(ac, hipStreamSynchronize(s));
+  }
+  *n_pairs = total;
+  if (ac->profiling.load()) {
+    // the engine that traversed, the call's hits; ms_write = the passes of this file (the call from its first range on, less
+    // its matches); repeats = the ranges before the last
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_all0).count();
+    t_trav.struct_size = sizeof(t_trav);
+    t_trav.n_hits = n_hits;
+    t_trav.ms_write = (float)std::max(0.0, ms - ms_match);
+    t_trav.repeats = ranges ? ranges - 1 : 0;
+    publish_timing(ac, t_trav);
+  }
+  if (total > cap) {
+    tls_err = "output buffer too small";
+    return AHA_E_CAPACITY;
+  }
+  return AHA_OK;
 }
 
 }  // namespace ahai

@@ -39,6 +39,10 @@ struct Scratch {
   Buf v2buf[26];
   Buf hostbuf[4];
   Buf cntbuf[3];   // count calls in document ranges (engine.cpp count_ranges): relative offsets, an aligned text, offsets  // device staging of the host-buffer entry points (corpus, doc offsets, doc hit offsets, hits)
+  // document counts (engine.cpp device_doc_counts): 0 hit offsets, 1 hits, 2 relative offsets, 3 an aligned text, 4 work items,
+  // 5 pairs per document, 6 dense rows, 7 the range form's pairs, 8 pair offsets + sources of the gather, 9 one document's key counts
+  Buf dcbuf[10];
+  bool dc_rows_clear = false;  // every word of dcbuf[6] is zero (kdc_compact clears what kdc_add wrote; a call that failed may not have)
   hipStream_t hs[3] = {};  // host-buffer entry: private non-blocking streams for upload, match, download
   unsigned long long *h_v2 = nullptr;  // pinned: cursor[2] + totals[3]
   unsigned long long *h_v2_dev = nullptr;  // the same words as the device addresses them
@@ -109,6 +113,9 @@ struct aha_ac {
   bool pair_ok = false;
   PairDev pdev{};
   std::atomic<uint32_t> pair_off{0};  // batches it gave up (three: the handle stops trying)
+  // document counts: read from the environment when the handle is compiled (engine.cpp doccount_setup)
+  uint64_t dc_hit_bytes = 0, dc_row_bytes = 0;  // bounds of a range's hit buffer and of the dense rows in flight
+  uint32_t dc_sort_max = 0, dc_dense_min = 0, dc_range_keys = 0;
   uint32_t seg2 = 0;  // slots below it: the root's and the depth-1 states' rows
   // match_longest only (cedar_replay.cpp): the states that carry one of Cedar's stale END flags, derived on the first
   // match_longest call (it replays every insert: as long again as the rest of compile); dev_longest = dev + the bitmap
@@ -241,13 +248,20 @@ struct PackOut {
   uint64_t *d_n_words;
 };
 // one device-resident batch through whichever engine takes it (retries, hand-backs, the two-pass engine as the last resort).
+// neutral: every engine, but the back-off state is only read (the match inside a document-count call).
 // quiet: neither the prefix-filter nor the pair engine, so the handle's back-off state is neither read nor written (a feed's
 // window batch, feed.cpp: an internal batch must not change which engine the caller's next call takes)
 int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
                      uint64_t n_bytes, const aha_match_params *params, aha_hit *d_out, uint64_t cap, uint64_t *d_doc_hit_offsets,
-                     uint64_t *n_hits, void *stream, bool offsets_checked, const PackOut *pk, bool *packed, bool quiet = false);
+                     uint64_t *n_hits, void *stream, bool offsets_checked, const PackOut *pk, bool *packed, bool quiet = false,
+                     bool neutral = false);
 // one device-resident batch counted (aha_ac_count_batch_device): the match's engine, the count passes instead of the expansion
 int32_t device_count(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
                      uint64_t n_bytes, const aha_match_params *params, uint32_t flags, uint64_t *d_key_counts,
                      uint64_t *d_doc_hit_offsets, uint64_t *n_hits, void *stream, bool offsets_checked);
+// one device-resident batch as {key, count} pairs per document (aha_ac_doc_counts_batch_device): a count call for the hits per
+// document, the match into scratch, the per-document reduction (scan_doccount.hip)
+int32_t device_doc_counts(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                          uint64_t n_bytes, const aha_match_params *params, aha_key_count *d_out, uint64_t cap,
+                          uint64_t *d_doc_pair_offsets, uint64_t *n_pairs, uint64_t *n_hits, void *stream, bool offsets_checked);
 }  // namespace ahai

@@ -71,6 +71,7 @@ struct MatchArgs {
   unsigned long long *kc_visits;     // [K] events per head key (the two-pass engine's k_count<.., true> without a separator filter)
   unsigned long long *kc_hits;       // [K] hits per key (k_count<.., true> with a separator filter: per hit, both neighbour tests)
   unsigned long long *kc_out;        // [K] the caller's key counts (the chain pass adds into them)
+  int32_t neutral;                   // host side: a match inside a document-count call -- the handle's back-off state is read, not written
 };
 
 constexpr int kBlock = 256;  // threads per block in the traversal kernels
@@ -235,6 +236,28 @@ void count_launch_visits(const DevAut &A, const V2Args &M, const uint2 *uend, un
                          void *stream);
 void count_launch_chain(const uint2 *key_ln, uint32_t n_keys, const unsigned long long *visits, unsigned long long *out,
                         const unsigned long long *abortf, void *stream);
+
+// document counts (scan_doccount.hip; engine.cpp device_doc_counts).  One unit of work of its kernels: `n` hits from hit
+// `begin` of the range's hit buffer; `doc` = the document within the range (kdc_add: the row of the slice's document); `out`
+// = where the document's pairs go for the time being.
+struct DcItem {
+  uint64_t begin;
+  uint32_t *out;
+  uint32_t n;
+  uint32_t doc;
+};
+constexpr uint32_t kDcSortMax = 4096;      // ids kdc_sort holds in LDS
+constexpr uint32_t kDcRangeKeys = 8192;    // counts kdc_range holds in LDS
+constexpr uint32_t kDcSliceHits = 1u << 16;  // hits of one slice of kdc_add
+void doccount_launch_sort(const DcItem *items, uint32_t n_items, const void *hits, uint32_t *n_pairs, void *stream);
+void doccount_launch_range(const DcItem *items, uint32_t n_items, const void *hits, uint32_t n_keys, uint32_t range_keys,
+                           uint32_t *n_pairs, void *stream);
+void doccount_launch_add(const DcItem *slices, uint32_t n_slices, const void *hits, uint32_t *rows, uint32_t n_keys,
+                         uint32_t max_blocks, void *stream);
+void doccount_launch_compact(const DcItem *docs, uint32_t n_rows, uint32_t *rows, uint32_t n_keys, uint32_t *n_pairs, void *stream);
+void doccount_launch_compact64(const DcItem *doc, unsigned long long *row, uint32_t n_keys, uint32_t *n_pairs, void *stream);
+void doccount_launch_gather(const uint64_t *pair_off, const uint32_t *const *src, uint64_t n_docs, uint64_t n, void *out,
+                            void *stream);
 
 // exchange format of the multi-GPU all-gatherv (kernels.hip): {end, value} pairs <-> Hit triples
 void launch_hits_pack(const int32_t *hits, uint64_t n, int32_t *pairs, void *stream);

@@ -180,6 +180,17 @@ lib LibAhaHip
   fun aha_ac_count_batch_device(ac : Ac, d_corpus : UInt8*, d_doc_offsets : UInt64*, n_docs : UInt64, n_bytes : UInt64,
                                 params : MatchParams*, flags : UInt32, d_key_counts : UInt64*, d_doc_hit_offsets : UInt64*,
                                 n_hits : UInt64*, stream : Void*) : Int32
+  # document counts: per document one {key, count} pair per distinct hit value, ascending by key (cap in pairs)
+  struct KeyCount
+    key : Int32
+    count : UInt32
+  end
+  fun aha_ac_doc_counts_batch(ac : Ac, corpus : UInt8*, doc_offsets : UInt64*, n_docs : UInt64, params : MatchParams*,
+                              out : KeyCount*, cap : UInt64, doc_pair_offsets : UInt64*, n_pairs : UInt64*,
+                              n_hits : UInt64*) : Int32
+  fun aha_ac_doc_counts_batch_device(ac : Ac, d_corpus : UInt8*, d_doc_offsets : UInt64*, n_docs : UInt64, n_bytes : UInt64,
+                                     params : MatchParams*, d_out : KeyCount*, cap : UInt64, d_doc_pair_offsets : UInt64*,
+                                     n_pairs : UInt64*, n_hits : UInt64*, stream : Void*) : Int32
   # feeds: sequences that arrive in pieces across calls (offsets relative to the piece; FEED_CHARS: in characters)
   type Feed = Void*
   FEED_CHARS = 1_u32
@@ -363,6 +374,31 @@ module Aha
         pointerof(params), flags, kc.to_unsafe, dho.to_unsafe, out n)
       raise String.new(LibAhaHip.aha_last_error(@handle)) if rc != 0
       {kc, dho}
+    end
+
+    # The document x key table of match_batch(docs, sep: sep) without the hit list: per document its {key id, count} pairs,
+    # ascending by key id.
+    def doc_counts_batch(docs : Array(String) | Array(Bytes), sep : BitArray? = nil) : Array(Array({Int32, UInt32}))
+      corpus = IO::Memory.new
+      offs = Array(UInt64).new(docs.size + 1)
+      offs << 0_u64
+      docs.each do |d|
+        corpus.write(d.is_a?(String) ? d.to_slice : d)
+        offs << corpus.pos.to_u64
+      end
+      params = AC.params(false, sep)
+      dpo = Array(UInt64).new(docs.size + 1, 0_u64)
+      rc = LibAhaHip.aha_ac_doc_counts_batch(@handle, corpus.to_slice.to_unsafe, offs.to_unsafe, docs.size.to_u64,
+        pointerof(params), Pointer(LibAhaHip::KeyCount).null, 0_u64, dpo.to_unsafe, out n, Pointer(UInt64).null)
+      pairs = Pointer(LibAhaHip::KeyCount).malloc(n + 1)
+      if rc == E_CAPACITY # n is the required count
+        rc = LibAhaHip.aha_ac_doc_counts_batch(@handle, corpus.to_slice.to_unsafe, offs.to_unsafe, docs.size.to_u64,
+          pointerof(params), pairs, n, dpo.to_unsafe, out n2, Pointer(UInt64).null)
+      end
+      raise String.new(LibAhaHip.aha_last_error(@handle)) if rc != 0
+      Array.new(docs.size) do |d|
+        Array.new((dpo[d + 1] - dpo[d]).to_i) { |i| p = pairs[dpo[d] + i]; {p.key, p.count} }
+      end
     end
 
     private def run(seq : Bytes, chars : Bool, sep : BitArray?, longest : Int32 = 0, &block)

@@ -225,6 +225,32 @@ class AC {
     return n;
   }
 
+  // The document x key table of match_batch without the hit list (aha_ac_doc_counts_batch): document d's {key, count} pairs,
+  // ascending by key, are [(*doc_pair_offsets)[d], (*doc_pair_offsets)[d + 1]) of what is returned.  A sizing call first.
+  std::vector<aha_key_count> doc_counts_batch(std::string_view corpus, const std::vector<uint64_t> &doc_offsets,
+                                              std::vector<uint64_t> *doc_pair_offsets = nullptr, uint64_t *n_hits = nullptr) const {
+    if (doc_offsets.empty()) throw Error(AHA_E_INVALID, "doc_offsets holds D + 1 entries");
+    aha_match_params p{};
+    p.struct_size = sizeof(p);
+    const uint64_t D = doc_offsets.size() - 1;
+    const uint8_t *text = reinterpret_cast<const uint8_t *>(corpus.data());
+    std::vector<uint64_t> dpo(D + 1);
+    std::vector<aha_key_count> pairs;
+    uint64_t n = 0, nh = 0;
+    int32_t rc = aha_ac_doc_counts_batch(h_, text, doc_offsets.data(), D, &p, nullptr, 0, dpo.data(), &n, &nh);
+    if (rc == AHA_E_CAPACITY) {
+      pairs.resize(n);
+      rc = aha_ac_doc_counts_batch(h_, text, doc_offsets.data(), D, &p, pairs.data(), pairs.size(), dpo.data(), &n, &nh);
+    }
+    if (rc != AHA_OK) {
+      const char *m = aha_last_error(h_);
+      throw Error(rc, (m && *m) ? m : aha_strerror(rc));
+    }
+    if (doc_pair_offsets) *doc_pair_offsets = std::move(dpo);
+    if (n_hits) *n_hits = nh;
+    return pairs;
+  }
+
   // The same on a batch resident in HBM (aha_ac_count_batch_device): d_key_counts is device memory of K uint64 (or null) and
   // keeps running totals there with accumulate; returns the hit count.
   uint64_t count_resident(const Corpus &c, uint64_t *d_key_counts, bool accumulate = false,

@@ -451,6 +451,40 @@ int32_t aha_feed_count_batch_device(aha_feed *f, const uint8_t *d_corpus, const 
                                     uint64_t *d_key_counts /* K or NULL */, uint64_t *d_piece_hit_offsets /* D+1 or NULL */,
                                     uint64_t *d_piece_bases /* D or NULL */, uint64_t *n_hits, void *stream);
 
+/* ---- document counts: hits per key within each document, no hit list (pure additions to ABI 8) -----------------------
+ * The same batch, params, validation and errors as aha_ac_match_batch / _device.  For document d,
+ * out[doc_pair_offsets[d] .. doc_pair_offsets[d+1]) holds one pair per distinct `value` among the hits the match call
+ * reports for d, ASCENDING BY KEY ID, count = the number of those hits (numpy: np.unique(values, return_counts=True));
+ * documents in order; two calls give identical bytes.  count is uint32: a key ends at most once per byte and a document
+ * is shorter than 2^31 bytes.  *n_pairs = all pairs; *n_hits (optional) = the match call's hit count.  Summing count per
+ * key over all pairs gives aha_ac_count_batch's key_counts, summing it per document the differences of its
+ * doc_hit_offsets.  cap is in pairs.  AHA_E_CAPACITY: *n_pairs is the required count, all offsets are valid, the first
+ * cap pairs are valid; out == NULL with cap == 0 is a sizing call.  char_offsets changes no count (the byte route); a
+ * separator filter counts the filtered hits; longest != 0 is AHA_E_INVALID.  n_pairs == NULL or a NULL handle:
+ * AHA_E_INVALID; a host-only handle: AHA_E_NO_DEVICE; the argument checks come before any device work.  The call reads
+ * the handle's back-off state and never writes it: a later match call behaves as if it had not happened.
+ * Pipeline (aha_amd/csrc/scan_doccount.hip): a count call without key counts (hits per document), the
+ * match with cap = hits into the call's scratch, then per document one of three forms chosen from its hit count: a sort
+ * in LDS (up to 4096 hits), counting passes over ranges of 8192 key ids in LDS (up to K / 8 hits), a row of K counts in
+ * scratch (above).  Device scratch: the match's + 12 bytes per hit (+ 8 per pair of the middle form) + 4 K per dense
+ * document in flight (1 GiB at most) + ~40 bytes per document.  Where the hits are beyond 48 GiB the call works through
+ * ranges of whole documents one after another (aha_timing.repeats = the ranges before the last); a single document
+ * beyond the bound is counted per key instead of matched.  The host entry uploads the batch in one piece.
+ * aha_ac_last_timing: engine = the engine that traversed, n_hits, ms_write = the passes after the match.
+ * Feeds and groups have no such call yet. */
+typedef struct {
+  int32_t key;
+  uint32_t count;
+} aha_key_count;
+int32_t aha_ac_doc_counts_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc_offsets, uint64_t n_docs,
+                                const aha_match_params *params, aha_key_count *out, uint64_t cap,
+                                uint64_t *doc_pair_offsets /* D+1 or NULL */, uint64_t *n_pairs, uint64_t *n_hits /* or NULL */);
+/* Device-resident form: d_ pointers are HBM on the handle's device; *n_pairs, *n_hits are host memory; blocks until final. */
+int32_t aha_ac_doc_counts_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                                       uint64_t n_bytes, const aha_match_params *params, aha_key_count *d_out, uint64_t cap,
+                                       uint64_t *d_doc_pair_offsets /* D+1 or NULL */, uint64_t *n_pairs,
+                                       uint64_t *n_hits /* or NULL */, void *stream);
+
 /* Frees the handle's device scratch (it grows with the largest batch seen and is otherwise kept for reuse). */
 int32_t aha_ac_release_scratch(aha_ac *ac);
 /* Device bytes currently held as scratch by the handle (all sets); waits for running calls. */
