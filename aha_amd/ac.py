@@ -531,6 +531,114 @@ class AC:
         return (out.download(np.zeros(cap, dtype=KEY_COUNT_DTYPE)), dpo.download(np.zeros(D + 1, dtype=np.uint64)),
                 int(nh.value))
 
+    # -- cover: which bytes lie inside a hit, and a redacted copy (aha_ac_cover_batch*) ---------------
+    def _cover_host(self, corpus, doc_offsets, sep, want_mask, want_redacted, fill):
+        if isinstance(corpus, (bytes, bytearray)):
+            corpus = np.frombuffer(bytes(corpus), dtype=np.uint8)
+        corpus = np.ascontiguousarray(corpus, dtype=np.uint8)
+        doc_offsets = np.ascontiguousarray(doc_offsets, dtype=np.uint64)
+        D = doc_offsets.size - 1
+        n_bytes = int(doc_offsets[-1]) if doc_offsets.size else 0
+        p = _params(False, sep)
+        mask = np.zeros((n_bytes + 31) // 32, dtype=np.uint32) if want_mask else None
+        red = np.zeros(n_bytes, dtype=np.uint8) if want_redacted else None
+        cov = np.zeros(max(D, 0), dtype=np.uint64)
+        nc, nh = C.c_uint64(0), C.c_uint64(0)
+        rc = N.lib().aha_ac_cover_batch(self._h, _ptr(corpus), _ptr(doc_offsets), D, C.byref(p), 0, _ptr(mask), _ptr(red),
+                                        int(fill) & 0xFF, _ptr(cov), C.byref(nc), C.byref(nh))
+        self._check(rc)
+        return mask, red, cov
+
+    def cover_batch(self, corpus, doc_offsets, sep=None):
+        """Which bytes of the batch lie inside a hit of match_batch(corpus, doc_offsets, sep), without the hit list:
+        -> (mask uint32[ceil(N / 32)], doc_covered uint64[D]).  Bit j of the batch is word j >> 5, bit j & 31
+        (np.unpackbits(mask.view(np.uint8), bitorder="little")[:N]); doc_covered[d] = covered bytes of document d."""
+        mask, _, cov = self._cover_host(corpus, doc_offsets, sep, True, False, 0)
+        return mask, cov
+
+    def redact_batch(self, corpus, doc_offsets, fill=0x2A, sep=None):
+        """The batch with every byte inside a hit replaced by `fill`: -> (redacted uint8[N], doc_covered uint64[D])."""
+        _, red, cov = self._cover_host(corpus, doc_offsets, sep, False, True, fill)
+        return red, cov
+
+    def cover(self, seq, sep=None):
+        """np.bool_[n_bytes]: True where the byte of `seq` (bytes, or str as UTF-8) lies inside a hit of match(seq, sep)."""
+        b = _b(seq)
+        mask, _ = self.cover_batch(np.frombuffer(b, dtype=np.uint8), np.array([0, len(b)], dtype=np.uint64), sep=sep)
+        return np.unpackbits(mask.view(np.uint8), bitorder="little")[: len(b)].astype(np.bool_)
+
+    def redact(self, seq, fill="*", sep=None):
+        """`seq` with what the keys cover blanked out.  bytes in, bytes out: every covered byte becomes `fill` (a byte, an int
+        or a one-character str).  str in, str out: every character that has a covered byte becomes `fill` (a str)."""
+        if isinstance(seq, str):
+            b = seq.encode("utf-8")
+            cov = self.cover(b, sep=sep)
+            raw = np.frombuffer(b, dtype=np.uint8)
+            lead = (raw & 0xC0) != 0x80  # a character starts here
+            hit = np.zeros(int(lead.sum()), dtype=np.int64)
+            np.add.at(hit, np.cumsum(lead) - 1, cov)
+            f = fill if isinstance(fill, str) else bytes([int(fill) & 0xFF]).decode("latin-1")
+            return "".join(f if h else ch for ch, h in zip(seq, hit))
+        f = fill
+        if isinstance(f, str):
+            f = f.encode("utf-8")
+        if isinstance(f, (bytes, bytearray)):
+            if len(f) != 1:
+                raise ValueError("fill must be one byte for a bytes sequence")
+            f = f[0]
+        b = _b(seq)
+        red, _ = self.redact_batch(np.frombuffer(b, dtype=np.uint8), np.array([0, len(b)], dtype=np.uint64), fill=f, sep=sep)
+        return red.tobytes()
+
+    def cover_batch_device(self, corpus, doc_offsets, mask=None, redacted=None, fill=0x2A, doc_covered=None, sep=None,
+                           stream=None):
+        """Device-resident cover on torch CUDA tensors: uint8 corpus, int64/uint64 doc offsets; mask int32/uint32
+        [ceil(N / 32)] or None; redacted uint8 [N] or None (the corpus tensor itself: redaction in place); doc_covered
+        int64/uint64 [D] or None.  -> (n_covered, n_hits)."""
+        import torch
+
+        assert corpus.is_cuda and corpus.dtype == torch.uint8 and corpus.is_contiguous()
+        assert doc_offsets.is_cuda and doc_offsets.dtype in (torch.int64, torch.uint64)
+        n_bytes, D = corpus.numel(), doc_offsets.numel() - 1
+        if mask is not None and not (mask.is_cuda and mask.dtype in (torch.int32, torch.uint32) and mask.is_contiguous()
+                                     and mask.numel() >= (n_bytes + 31) // 32):
+            raise ValueError("mask must be a contiguous int32/uint32 CUDA tensor of at least ceil(N / 32) entries")
+        if redacted is not None and not (redacted.is_cuda and redacted.dtype == torch.uint8 and redacted.is_contiguous()
+                                         and redacted.numel() >= n_bytes):
+            raise ValueError("redacted must be a contiguous uint8 CUDA tensor of at least N entries")
+        if doc_covered is not None and not (doc_covered.is_cuda and doc_covered.dtype in (torch.int64, torch.uint64)
+                                            and doc_covered.is_contiguous() and doc_covered.numel() >= D):
+            raise ValueError("doc_covered must be a contiguous int64/uint64 CUDA tensor of at least D entries")
+        p = _params(False, sep)
+        nc, nh = C.c_uint64(0), C.c_uint64(0)
+        s = stream if stream is not None else torch.cuda.current_stream(corpus.device).cuda_stream
+        rc = N.lib().aha_ac_cover_batch_device(
+            self._h, corpus.data_ptr(), doc_offsets.data_ptr(), D, n_bytes, C.byref(p), 0,
+            mask.data_ptr() if mask is not None else None, redacted.data_ptr() if redacted is not None else None,
+            int(fill) & 0xFF, doc_covered.data_ptr() if doc_covered is not None else None, C.byref(nc), C.byref(nh), C.c_void_p(s))
+        self._check(rc)
+        return int(nc.value), int(nh.value)
+
+    def cover_corpus(self, corpus, sep=None, redacted=False, fill=0x2A):
+        """Cover of a batch that already lives in HBM (DeviceCorpus), downloaded:
+        -> (mask uint32[ceil(N / 32)], redacted uint8[N] or None, doc_covered uint64[D], n_covered, n_hits).  The corpus on the
+        device stays as it is (the redacted copy goes to a buffer of its own)."""
+        D, n_bytes = corpus.n_docs, corpus.n_bytes
+        n_words = (n_bytes + 31) // 32
+        p = _params(False, sep)
+        dev = corpus.device
+        d_mask = DeviceBuffer(dev, max(n_words, 1) * 4)
+        d_cov = DeviceBuffer(dev, max(D, 1) * 8)
+        d_red = DeviceBuffer(dev, max(n_bytes, 1)) if redacted else None
+        nc, nh = C.c_uint64(0), C.c_uint64(0)
+        rc = N.lib().aha_ac_cover_batch_device(self._h, corpus.ptr, corpus.doc_ptr, D, n_bytes, C.byref(p), 0, d_mask.ptr,
+                                               d_red.ptr if d_red else None, int(fill) & 0xFF, d_cov.ptr, C.byref(nc),
+                                               C.byref(nh), None)
+        self._check(rc)
+        mask = d_mask.download(np.zeros(n_words, dtype=np.uint32))
+        red = d_red.download(np.zeros(n_bytes, dtype=np.uint8)) if d_red else None
+        return mask, red, d_cov.download(np.zeros(D, dtype=np.uint64)), int(nc.value), int(nh.value)
+
     # -- exchange format of the multi-GPU all-gatherv: {end, value} pairs <-> Hit triples ------------
     def hits_pack_device(self, hits, n, pairs, stream=None):
         """hits [>=n,3] int32 -> pairs [>=n,2] int32, both on the handle's device (asynchronous)."""

@@ -27,6 +27,10 @@ void free_scratch(Scratch *sc, bool all) {
     if (b.p) (void)hipFree(b.p);
     b = Buf();
   }
+  for (auto &b : sc->covbuf) {
+    if (b.p) (void)hipFree(b.p);
+    b = Buf();
+  }
   sc->dc_rows_clear = false;
   void **scratch[] = {(void **)&sc->d_counts, (void **)&sc->d_leads, (void **)&sc->d_blk_hits, (void **)&sc->d_blk_leads,
                       (void **)&sc->d_docg};
@@ -62,6 +66,7 @@ uint64_t scratch_bytes(const Scratch *sc) {
   for (auto &b : sc->hostbuf) n += b.bytes;
   for (auto &b : sc->cntbuf) n += b.bytes;
   for (auto &b : sc->dcbuf) n += b.bytes;
+  for (auto &b : sc->covbuf) n += b.bytes;
   n += sc->cap_chunks * 8 + sc->cap_blocks * 16 + sc->cap_docs * 8;
   return n;
 }
@@ -1275,6 +1280,91 @@ int32_t aha_ac_doc_counts_batch(aha_ac *ac, const uint8_t *corpus, const uint64_
   HIPCHK(ac, hipStreamSynchronize(s));
   if (rc) tls_err = err;
   return rc;
+}
+
+// ---- cover calls (aha_ac_cover_batch*) -----------------------------------------------------------------------------
+// the argument checks both entries share: before any device work, so they hold on a host-only handle
+static int32_t cover_args(aha_ac *ac, const uint64_t *doc_offsets, const aha_match_params *params, uint32_t flags,
+                          uint64_t *n_covered) {
+  if (!ac || !n_covered || !doc_offsets || flags) return AHA_E_INVALID;
+  MatchArgs M{};
+  int longest = 0;
+  int32_t rc = fill_params(ac, params, M, &longest);
+  if (rc) return rc;
+  if (longest) {
+    tls_err = "cover calls have no match_longest form";
+    return AHA_E_INVALID;
+  }
+  if (ac->device < 0) {
+    tls_err = aha_strerror(AHA_E_NO_DEVICE);
+    return AHA_E_NO_DEVICE;
+  }
+  return AHA_OK;
+}
+
+int32_t aha_ac_cover_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                                  uint64_t n_bytes, const aha_match_params *params, uint32_t flags, uint32_t *d_mask,
+                                  uint8_t *d_redacted, uint8_t fill, uint64_t *d_doc_covered, uint64_t *n_covered, uint64_t *n_hits,
+                                  void *stream) {
+  int32_t rc = cover_args(ac, d_doc_offsets, params, flags, n_covered);
+  if (rc) return rc;
+  Lease lease(ac);
+  return device_cover(ac, lease.get(), d_corpus, d_doc_offsets, n_docs, n_bytes, params, flags, d_mask, d_redacted, fill,
+                      d_doc_covered, n_covered, n_hits, stream, false);
+}
+
+// The host entry: the batch goes up in one piece into the staging buffers of the leased scratch set, over its private stream; it
+// is redacted in place there; what was asked for comes back once the call has succeeded.
+int32_t aha_ac_cover_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc_offsets, uint64_t n_docs,
+                           const aha_match_params *params, uint32_t flags, uint32_t *mask, uint8_t *redacted, uint8_t fill,
+                           uint64_t *doc_covered, uint64_t *n_covered, uint64_t *n_hits) {
+  int32_t rc = cover_args(ac, doc_offsets, params, flags, n_covered);
+  if (rc) return rc;
+  if (doc_offsets[0] != 0) return AHA_E_INVALID;
+  for (uint64_t d = 0; d < n_docs; d++) {
+    if (doc_offsets[d + 1] < doc_offsets[d]) return AHA_E_INVALID;
+    if (doc_offsets[d + 1] - doc_offsets[d] >= 0x7FFFFFFFull) return AHA_E_TOO_LONG;
+  }
+  const uint64_t n_bytes = doc_offsets[n_docs], n_words = (n_bytes + 31) / 32;
+  if (n_bytes && !corpus) return AHA_E_INVALID;
+  DeviceGuard g(ac->device);
+  Lease lease(ac);
+  Scratch *sc = lease.get();
+  auto reserve = [&](int i, size_t bytes) -> void * {
+    Buf &b = sc->hostbuf[i];
+    if (b.bytes < bytes) {
+      if (b.p) (void)hipFree(b.p);
+      b.p = nullptr;
+      b.bytes = 0;
+      const size_t want = bytes + bytes / 4 + 4096;
+      if (hipMalloc(&b.p, want) != hipSuccess) return nullptr;
+      b.bytes = want;
+    }
+    return b.p;
+  };
+  uint8_t *d_corpus = (uint8_t *)reserve(0, n_bytes + 64);
+  uint64_t *d_doc = (uint64_t *)reserve(1, (n_docs + 1) * 8);
+  uint64_t *d_cov = doc_covered ? (uint64_t *)reserve(2, (n_docs + 1) * 8) : nullptr;
+  uint32_t *d_mask = mask ? (uint32_t *)reserve(3, n_words * 4 + 16) : nullptr;
+  if (!d_corpus || !d_doc || (doc_covered && !d_cov) || (mask && !d_mask) || !host_streams(sc)) {
+    tls_err = "hipMalloc / hipStreamCreate failed for the staging buffers";
+    return AHA_E_HIP;
+  }
+  hipStream_t s = sc->hs[1];
+  HIPCHK(ac, hipMemcpyAsync(d_doc, doc_offsets, (n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+  if (n_bytes) HIPCHK(ac, hipMemcpyAsync(d_corpus, corpus, n_bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  uint64_t nc = 0, nh = 0;
+  rc = device_cover(ac, sc, d_corpus, d_doc, n_docs, n_bytes, params, flags, d_mask, redacted ? d_corpus : nullptr, fill, d_cov, &nc,
+                    &nh, s, true);  // the offsets were checked on the host above
+  if (rc != AHA_OK) return rc;
+  if (mask && n_words) HIPCHK(ac, hipMemcpyAsync(mask, d_mask, n_words * 4, hipMemcpyDeviceToHost, s));
+  if (redacted && n_bytes) HIPCHK(ac, hipMemcpyAsync(redacted, d_corpus, n_bytes, hipMemcpyDeviceToHost, s));
+  if (doc_covered && n_docs) HIPCHK(ac, hipMemcpyAsync(doc_covered, d_cov, n_docs * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  *n_covered = nc;
+  if (n_hits) *n_hits = nh;
+  return AHA_OK;
 }
 
 // ---- device buffers behind the C ABI (include/aha_hip.h) ---------------------------------------------------------

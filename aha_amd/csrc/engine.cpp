@@ -239,6 +239,24 @@ int32_t ensure_h_v2(aha_ac *ac, Scratch *sc) {
   return AHA_OK;
 }
 
+// scratch of a cover call (Scratch::covbuf), grow-only; null: no memory
+static void *cover_reserve(Scratch *sc, int i, size_t bytes) {
+  Buf &b = sc->covbuf[i];
+  if (b.bytes < bytes) {
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr;
+    b.bytes = 0;
+    const size_t want = bytes + bytes / 8 + 256;
+    if (hipMalloc(&b.p, want) != hipSuccess) {
+      (void)hipGetLastError();
+      b.p = nullptr;
+      return nullptr;
+    }
+    b.bytes = want;
+  }
+  return b.p;
+}
+
 int32_t match_v2(aha_ac *ac, Scratch *sc, MatchArgs &M1, hipStream_t s, uint64_t *n_hits, V2Mode mode) {
   const uint64_t N = M1.n_bytes;
   const uint32_t Lmax = ac->aut.max_key_len;
@@ -432,15 +450,26 @@ int32_t match_v2(aha_ac *ac, Scratch *sc, MatchArgs &M1, hipStream_t s, uint64_t
     // adds: 64 / 256 / 1024 workgroups took 4.29 / 1.09 / 0.71 ms on cfg 3 at 1 GiB (AHA_COUNT_BLOCKS: lab)
     static const long count_blocks_env = getenv("AHA_COUNT_BLOCKS") ? atol(getenv("AHA_COUNT_BLOCKS")) : 0;
     const uint32_t count_blocks = count_blocks_env > 0 ? (uint32_t)count_blocks_env : 4u * ac->v2_grid;
+    // a cover call: the mask cleared (unless the pass was aborted), then one span per event from the same records
+    uint64_t *cdoc = nullptr;
+    if (M1.cover_mask) {
+      if (!(cdoc = (uint64_t *)cover_reserve(sc, 1, (M.n_chunks + 1) * 8))) {
+        tls_err = "hipMalloc failed for the scratch of a cover call";
+        return AHA_E_HIP;
+      }
+      if (M1.cover_clear) cover_launch_clear(M1.cover_mask, (N + 31) / 32, abortf, 8u * ac->v2_grid, s);
+    }
     if (unit && ac->unit_fused) {
       v2_launch_hit_scan(M, s);
       if (prof) HIPCHK(ac, hipEventRecord(sc->ev[3], s));
       if (M1.kc_visits) count_launch_visits(post, M, ac->d_unit_end, M1.kc_visits, count_blocks, s);
+      if (cdoc) cover_launch_spans(post, M, ac->d_unit_end, cdoc, M1.cover_mask, M1.cover_bit0, count_blocks, s);
     } else {
       if (unit) unit_launch_regroup(post, M, s);
       v2_launch_count_post(post, M, s, unit || filt || pair);
       if (prof) HIPCHK(ac, hipEventRecord(sc->ev[3], s));
       if (M1.kc_visits) count_launch_visits(post, M, nullptr, M1.kc_visits, count_blocks, s);
+      if (cdoc) cover_launch_spans(post, M, nullptr, cdoc, M1.cover_mask, M1.cover_bit0, count_blocks, s);
     }
     if (M1.kc_visits) count_launch_chain(ac->dev.key_ln, ac->aut.n_keys, M1.kc_visits, M1.kc_out, abortf, s);
     if (unit && ac->unit_fused)
@@ -805,6 +834,8 @@ static int32_t count_two_pass(aha_ac *ac, Scratch *sc, MatchArgs M, hipStream_t 
   M.totals = sc->d_totals;
   const bool prof = ac->profiling.load() && sc->ev_ready;
   if (M.kc_visits) HIPCHK(ac, hipMemsetAsync(M.kc_visits, 0, (size_t)ac->aut.n_keys * 8, s));
+  // (a cover call: the offsets have been looked at by now -- device_count -- so the mask may be touched)
+  if (M.cover_mask && M.cover_clear) HIPCHK(ac, hipMemsetAsync(M.cover_mask, 0, (size_t)((M.n_bytes + 31) / 32) * 4, s));
   if (prof) HIPCHK(ac, hipEventRecord(sc->ev[0], s));
   launch_count(ac->dev, M, s);
   if (prof) HIPCHK(ac, hipEventRecord(sc->ev[1], s));
@@ -886,6 +917,9 @@ static int32_t count_ranges(aha_ac *ac, Scratch *sc, const MatchArgs &M0, hipStr
   HIPCHK(ac, hipStreamSynchronize(s));
   uint64_t limit = std::max<uint64_t>(M0.n_bytes / 2, 1), base = 0;
   uint32_t ranges = 0;
+  // a cover call: the ranges share one mask (they run one after another on the stream, so a word two of them touch is safe);
+  // it is cleared once, here -- the offsets have been validated
+  if (M0.cover_mask) HIPCHK(ac, hipMemsetAsync(M0.cover_mask, 0, (size_t)((M0.n_bytes + 31) / 32) * 4, s));
   for (uint64_t d0 = 0; d0 < D;) {
     uint64_t d1 = d0 + 1;
     while (d1 < D && off[d1 + 1] - off[d0] <= limit) d1++;
@@ -921,6 +955,8 @@ static int32_t count_ranges(aha_ac *ac, Scratch *sc, const MatchArgs &M0, hipStr
     M.n_bytes = nb;
     M.doc_hit_off = d_dho;
     M.check_docs = 0;
+    M.cover_bit0 = M0.cover_bit0 + off[d0];
+    M.cover_clear = 0;
     uint64_t nh = 0;
     int32_t rc = AHA_OK;
     if (nb == 0) {
@@ -939,6 +975,8 @@ static int32_t count_ranges(aha_ac *ac, Scratch *sc, const MatchArgs &M0, hipStr
         M.n_bytes = nb;
         M.doc_hit_off = d_dho;
         M.check_docs = 0;
+        M.cover_bit0 = M0.cover_bit0 + off[d0];
+        M.cover_clear = 0;
         rc = count_two_pass(ac, sc, M, s, &nh, 1);
       }
     }
@@ -968,7 +1006,7 @@ static int32_t count_ranges(aha_ac *ac, Scratch *sc, const MatchArgs &M0, hipStr
 // engine's give-ups) is read, never written: the next match call behaves as if this call had not happened.
 int32_t device_count(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
                      uint64_t n_bytes, const aha_match_params *params, uint32_t flags, uint64_t *d_key_counts,
-                     uint64_t *d_doc_hit_offsets, uint64_t *n_hits, void *stream, bool offsets_checked) {
+                     uint64_t *d_doc_hit_offsets, uint64_t *n_hits, void *stream, bool offsets_checked, uint32_t *cover_mask) {
   if (!ac || !n_hits || !d_doc_offsets) return AHA_E_INVALID;
   if (ac->device < 0) {
     tls_err = aha_strerror(AHA_E_NO_DEVICE);
@@ -1015,6 +1053,8 @@ int32_t device_count(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
   M.cap = 0;
   M.doc_hit_off = d_doc_hit_offsets;
   M.count_only = 1;
+  M.cover_mask = cover_mask;  // (a cover call, device_cover: every pass that runs to its end leaves its events' spans there)
+  M.cover_clear = cover_mask ? 1 : 0;
   M.kc_out = reinterpret_cast<unsigned long long *>(d_key_counts);
   if (d_key_counts) {
     if (M.sep) {
@@ -1040,6 +1080,74 @@ int32_t device_count(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
   return count_two_pass(ac, sc, M, s, n_hits, single ? 1 : 0);
 }
 
+
+// ---- cover calls (aha_ac_cover_batch*) ---------------------------------------------------------------------------------
+// One device-resident batch covered.  device_count without key counts and with a mask: the engine a match would take, document
+// ranges, the two-pass engine's form for a separator filter -- each pass leaves one span per event in the mask (scan_cover.hip;
+// k_count's cover mode).  Then, over the finished mask and only where asked for: the redacted copy, the documents' covered
+// bytes; the total always.  Scratch beyond the count call's: N / 8 bytes where the caller gives no mask, 8 bytes per chunk,
+// nothing per hit.
+int32_t device_cover(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                     uint64_t n_bytes, const aha_match_params *params, uint32_t flags, uint32_t *d_mask, uint8_t *d_redacted,
+                     uint8_t fill, uint64_t *d_doc_covered, uint64_t *n_covered, uint64_t *n_hits_out, void *stream, bool offsets_checked) {
+  if (!ac || !n_covered || !d_doc_offsets || flags) return AHA_E_INVALID;
+  {
+    MatchArgs M{};
+    int longest = 0;
+    int32_t rc0 = fill_params(ac, params, M, &longest);
+    if (rc0) return rc0;
+    if (longest) {
+      tls_err = "cover calls have no match_longest form";
+      return AHA_E_INVALID;
+    }
+  }
+  if (ac->device < 0) {
+    tls_err = aha_strerror(AHA_E_NO_DEVICE);
+    return AHA_E_NO_DEVICE;
+  }
+  DeviceGuard g(ac->device);
+  hipStream_t s = (hipStream_t)stream;
+  *n_covered = 0;
+  if (n_hits_out) *n_hits_out = 0;
+  const uint64_t n_words = (n_bytes + 31) / 32;
+  auto nomem = [&]() {
+    tls_err = "hipMalloc failed for the scratch of a cover call";
+    return AHA_E_HIP;
+  };
+  uint32_t *mask = d_mask;
+  if (!mask && n_words && !(mask = (uint32_t *)cover_reserve(sc, 0, n_words * 4))) return nomem();
+  uint64_t *d_total = (uint64_t *)cover_reserve(sc, 2, 8);
+  if (!d_total) return nomem();
+  int32_t rc;
+  uint64_t n_hits = 0;
+  if ((rc = device_count(ac, sc, d_corpus, d_doc_offsets, n_docs, n_bytes, params, 0, nullptr, nullptr, &n_hits, stream, offsets_checked,
+                         mask)))
+    return rc;
+  const bool prof = ac->profiling.load();
+  const auto t0 = std::chrono::steady_clock::now();
+  const uint32_t blocks = 8u * std::max<uint32_t>(ac->v2_grid, 64u);
+  uint64_t total = 0;
+  if (n_bytes) {
+    HIPCHK(ac, hipMemsetAsync(d_total, 0, 8, s));
+    cover_launch_total(mask, n_words, d_total, blocks, s);
+    if (d_redacted) cover_launch_redact(d_corpus, d_redacted, mask, n_bytes, fill, blocks, s);
+    if (d_doc_covered && n_docs) cover_launch_doc_covered(mask, d_doc_offsets, n_docs, d_doc_covered, blocks, s);
+    HIPCHK(ac, hipGetLastError());
+    HIPCHK(ac, hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, s));
+  } else if (d_doc_covered && n_docs) {
+    HIPCHK(ac, hipMemsetAsync(d_doc_covered, 0, n_docs * 8, s));
+  }
+  HIPCHK(ac, hipStreamSynchronize(s));
+  *n_covered = total;
+  if (n_hits_out) *n_hits_out = n_hits;
+  if (prof) {  // ms_write: the passes after the traversal -- the spans (the pass's own figure) and the passes over the mask
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    std::lock_guard<std::mutex> lk(ac->last_mu);
+    ac->last.ms_write += (float)ms;
+    ac->last.n_hits = n_hits;
+  }
+  return AHA_OK;
+}
 
 // ---- document counts (aha_ac_doc_counts_batch*) ----------------------------------------------------------------------
 static void *dc_reserve(Scratch *sc, int i, size_t bytes) {

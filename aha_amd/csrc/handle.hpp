@@ -42,6 +42,7 @@ struct Scratch {
   // document counts (engine.cpp device_doc_counts): 0 hit offsets, 1 hits, 2 relative offsets, 3 an aligned text, 4 work items,
   // 5 pairs per document, 6 dense rows, 7 the range form's pairs, 8 pair offsets + sources of the gather, 9 one document's key counts
   Buf dcbuf[10];
+  Buf covbuf[3];   // cover calls (engine.cpp device_cover): 0 the mask where the caller gives none, 1 the chunks' first documents, 2 the total
   bool dc_rows_clear = false;  // every word of dcbuf[6] is zero (kdc_compact clears what kdc_add wrote; a call that failed may not have)
   hipStream_t hs[3] = {};  // host-buffer entry: private non-blocking streams for upload, match, download
   unsigned long long *h_v2 = nullptr;  // pinned: cursor[2] + totals[3]
@@ -258,10 +259,15 @@ int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
 // one device-resident batch counted (aha_ac_count_batch_device): the match's engine, the count passes instead of the expansion
 int32_t device_count(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
                      uint64_t n_bytes, const aha_match_params *params, uint32_t flags, uint64_t *d_key_counts,
-                     uint64_t *d_doc_hit_offsets, uint64_t *n_hits, void *stream, bool offsets_checked);
+                     uint64_t *d_doc_hit_offsets, uint64_t *n_hits, void *stream, bool offsets_checked, uint32_t *cover_mask = nullptr);
 // one device-resident batch as {key, count} pairs per document (aha_ac_doc_counts_batch_device): a count call for the hits per
 // document, the match into scratch, the per-document reduction (scan_doccount.hip)
 int32_t device_doc_counts(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
                           uint64_t n_bytes, const aha_match_params *params, aha_key_count *d_out, uint64_t cap,
                           uint64_t *d_doc_pair_offsets, uint64_t *n_pairs, uint64_t *n_hits, void *stream, bool offsets_checked);
+// one device-resident batch covered (aha_ac_cover_batch_device): the count call's pipeline without key counts, one span per
+// event into the mask (scan_cover.hip), then the redacted copy and the documents' covered bytes where asked for
+int32_t device_cover(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                     uint64_t n_bytes, const aha_match_params *params, uint32_t flags, uint32_t *d_mask, uint8_t *d_redacted,
+                     uint8_t fill, uint64_t *d_doc_covered, uint64_t *n_covered, uint64_t *n_hits, void *stream, bool offsets_checked);
 }  // namespace ahai

@@ -72,6 +72,11 @@ struct MatchArgs {
   unsigned long long *kc_hits;       // [K] hits per key (k_count<.., true> with a separator filter: per hit, both neighbour tests)
   unsigned long long *kc_out;        // [K] the caller's key counts (the chain pass adds into them)
   int32_t neutral;                   // host side: a match inside a document-count call -- the handle's back-off state is read, not written
+  // cover calls (aha_ac_cover_batch*): a count call without key counts whose events leave one span each in a bit mask
+  // (scan_cover.hip; the two-pass engine: k_count's cover mode)
+  uint32_t *cover_mask;              // bit cover_bit0 + j = byte j of this batch; null: not a cover call
+  uint64_t cover_bit0;               // the batch's first byte in the mask (a document range of a larger batch)
+  int32_t cover_clear;               // host side: the pass clears the mask itself, once it knows the offsets are good
 };
 
 constexpr int kBlock = 256;  // threads per block in the traversal kernels
@@ -236,6 +241,17 @@ void count_launch_visits(const DevAut &A, const V2Args &M, const uint2 *uend, un
                          void *stream);
 void count_launch_chain(const uint2 *key_ln, uint32_t n_keys, const unsigned long long *visits, unsigned long long *out,
                         const unsigned long long *abortf, void *stream);
+
+// cover path (scan_cover.hip): the mask's words cleared unless *abortf; one span per event of the pass into mask (records as
+// for count_launch_visits; cdoc: n_chunks + 1 words of scratch, the chunks' first documents); the passes over the finished mask
+void cover_launch_clear(uint32_t *words, uint64_t n_words, const unsigned long long *abortf, uint32_t max_blocks, void *stream);
+void cover_launch_spans(const DevAut &A, const V2Args &M, const uint2 *uend, uint64_t *cdoc, uint32_t *mask, uint64_t bit0,
+                        uint32_t max_blocks, void *stream);
+void cover_launch_redact(const uint8_t *src, uint8_t *dst, const uint32_t *mask, uint64_t n_bytes, uint8_t fill, uint32_t max_blocks,
+                         void *stream);
+void cover_launch_doc_covered(const uint32_t *mask, const uint64_t *doc_off, uint64_t n_docs, uint64_t *doc_covered,
+                              uint32_t max_blocks, void *stream);
+void cover_launch_total(const uint32_t *mask, uint64_t n_words, uint64_t *total, uint32_t max_blocks, void *stream);
 
 // document counts (scan_doccount.hip; engine.cpp device_doc_counts).  One unit of work of its kernels: `n` hits from hit
 // `begin` of the range's hit buffer; `doc` = the document within the range (kdc_add: the row of the slice's document); `out`

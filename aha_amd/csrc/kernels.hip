@@ -19,6 +19,7 @@
 #include <algorithm>
 
 #include "automaton.hpp"
+#include "cover_span.hpp"
 #include "devcommon.hpp"
 #include "image.hpp"
 
@@ -30,6 +31,9 @@ namespace aha {
 // a separator filter, one per hit that passes both neighbour tests into kc_hits[key].  Count calls also note, for every
 // document that starts in the chunk, the chunk's hits before its start (k_count_doc_offsets then adds the chunk's base): the
 // documents' offsets without the second traversal of k_write.
+// Cover calls (M.cover_mask, the KEYS_OR_DOCS instantiations): one span per event into the mask -- the head key's, the longest
+// of the event; with a separator filter the first key on the chain that passes the left-neighbour test (the longest survivor:
+// the others lie inside it).
 template <bool COMPACT, bool KEYS_OR_DOCS, bool KEYS = KEYS_OR_DOCS>
 __global__ __launch_bounds__(kBlock) void k_count(DevAut A, MatchArgs M) {
   __shared__ uint64_t sm[kBlock / 64];
@@ -64,10 +68,13 @@ __global__ __launch_bounds__(kBlock) void k_count(DevAut A, MatchArgs M) {
         if (!M.sep) {
           hits += A.key_cnt[key];
           if (KEYS) atomicAdd(&M.kc_visits[key], 1ull);
+          if (KEYS_OR_DOCS && M.cover_mask)
+            cover_or_global(M.cover_mask, M.cover_bit0 + max(p + 1 - min<uint64_t>(p + 1, A.key_ln[key].x), doc_start), M.cover_bit0 + p + 1);
         } else {
           // match(seq, sep): right neighbour of the end position (ac.cr:324-329)
           if (p + 1 < nb && sep_blocked(M, M.text[p + 1])) continue;
           int32_t k = (int32_t)key;
+          bool covered = false;
           do {
             uint2 ln = A.key_ln[k];
             uint64_t s = p + 1 - ln.x;  // absolute start
@@ -75,6 +82,10 @@ __global__ __launch_bounds__(kBlock) void k_count(DevAut A, MatchArgs M) {
             if (!(s > doc_start && sep_blocked(M, M.text[s - 1]))) {
               hits++;
               if (KEYS) atomicAdd(&M.kc_hits[k], 1ull);
+              if (KEYS_OR_DOCS && M.cover_mask && !covered) {
+                cover_or_global(M.cover_mask, M.cover_bit0 + max(s, doc_start), M.cover_bit0 + p + 1);
+                covered = true;
+              }
             }
             k = (int32_t)ln.y;
           } while (k >= 0);
@@ -851,7 +862,7 @@ void launch_count(const DevAut &A, const MatchArgs &M, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   uint32_t g = blocks_for(M.n_chunks);
   const bool keys = M.kc_visits || M.kc_hits;  // (a count call that wants the key counts)
-  const bool docs = M.count_only && M.doc_hit_off;  // (... or the documents' offsets)
+  const bool docs = M.count_only && (M.doc_hit_off || M.cover_mask);  // (... or the documents' offsets, or a cover call)
   if (A.compact) {
     if (keys)
       hipLaunchKernelGGL((k_count<true, true>), dim3(g), dim3(kBlock), 0, s, A, M);

@@ -191,6 +191,13 @@ lib LibAhaHip
   fun aha_ac_doc_counts_batch_device(ac : Ac, d_corpus : UInt8*, d_doc_offsets : UInt64*, n_docs : UInt64, n_bytes : UInt64,
                                      params : MatchParams*, d_out : KeyCount*, cap : UInt64, d_doc_pair_offsets : UInt64*,
                                      n_pairs : UInt64*, n_hits : UInt64*, stream : Void*) : Int32
+  # cover: which bytes lie inside a hit (bit j = word j >> 5, bit j & 31), and a redacted copy; no hit list
+  fun aha_ac_cover_batch(ac : Ac, corpus : UInt8*, doc_offsets : UInt64*, n_docs : UInt64, params : MatchParams*,
+                         flags : UInt32, mask : UInt32*, redacted : UInt8*, fill : UInt8, doc_covered : UInt64*,
+                         n_covered : UInt64*, n_hits : UInt64*) : Int32
+  fun aha_ac_cover_batch_device(ac : Ac, d_corpus : UInt8*, d_doc_offsets : UInt64*, n_docs : UInt64, n_bytes : UInt64,
+                                params : MatchParams*, flags : UInt32, d_mask : UInt32*, d_redacted : UInt8*, fill : UInt8,
+                                d_doc_covered : UInt64*, n_covered : UInt64*, n_hits : UInt64*, stream : Void*) : Int32
   # feeds: sequences that arrive in pieces across calls (offsets relative to the piece; FEED_CHARS: in characters)
   type Feed = Void*
   FEED_CHARS = 1_u32
@@ -374,6 +381,27 @@ module Aha
         pointerof(params), flags, kc.to_unsafe, dho.to_unsafe, out n)
       raise String.new(LibAhaHip.aha_last_error(@handle)) if rc != 0
       {kc, dho}
+    end
+
+    # The documents with every byte inside a hit of match_batch(docs, sep: sep) replaced by `fill`, without the hit list
+    # (Aha::AC has no such method; CedarX#gsub is the reference's nearest): -> {redacted documents, covered bytes per document}
+    def redact_batch(docs : Array(String) | Array(Bytes), fill : UInt8 = 0x2A_u8, sep : BitArray? = nil) : {Array(Bytes), Array(UInt64)}
+      corpus = IO::Memory.new
+      offs = Array(UInt64).new(docs.size + 1)
+      offs << 0_u64
+      docs.each do |d|
+        corpus.write(d.is_a?(String) ? d.to_slice : d)
+        offs << corpus.pos.to_u64
+      end
+      params = AC.params(false, sep)
+      red = Bytes.new(corpus.pos + 1)
+      cov = Array(UInt64).new(docs.size + 1, 0_u64)
+      rc = LibAhaHip.aha_ac_cover_batch(@handle, corpus.to_slice.to_unsafe, offs.to_unsafe, docs.size.to_u64,
+        pointerof(params), 0_u32, Pointer(UInt32).null, red.to_unsafe, fill, cov.to_unsafe, out n_covered,
+        Pointer(UInt64).null)
+      raise String.new(LibAhaHip.aha_last_error(@handle)) if rc != 0
+      cov.pop
+      {(0...docs.size).map { |d| red[offs[d], offs[d + 1] - offs[d]] }, cov}
     end
 
     # The document x key table of match_batch(docs, sep: sep) without the hit list: per document its {key id, count} pairs,

@@ -225,6 +225,29 @@ class AC {
     return n;
   }
 
+  // (the call behind cover_batch / redact_batch: returns *n_covered)
+  uint64_t cover_call(std::string_view corpus, const std::vector<uint64_t> &doc_offsets, std::vector<uint32_t> *mask,
+                      std::string *redacted, uint8_t fill, std::vector<uint64_t> *doc_covered, uint64_t *n_hits) const {
+    if (doc_offsets.empty()) throw Error(AHA_E_INVALID, "doc_offsets holds D + 1 entries");
+    aha_match_params p{};
+    p.struct_size = sizeof(p);
+    const uint64_t D = doc_offsets.size() - 1, N = doc_offsets.back();
+    if (mask) mask->assign((N + 31) / 32, 0u);
+    if (redacted) redacted->assign(N, '\0');
+    if (doc_covered) doc_covered->assign(D, 0);
+    uint64_t nc = 0, nh = 0;
+    const int32_t rc = aha_ac_cover_batch(h_, reinterpret_cast<const uint8_t *>(corpus.data()), doc_offsets.data(), D, &p, 0,
+                                          mask && !mask->empty() ? mask->data() : nullptr,
+                                          redacted && N ? reinterpret_cast<uint8_t *>(&(*redacted)[0]) : nullptr, fill,
+                                          doc_covered && D ? doc_covered->data() : nullptr, &nc, &nh);
+    if (rc != AHA_OK) {
+      const char *m = aha_last_error(h_);
+      throw Error(rc, (m && *m) ? m : aha_strerror(rc));
+    }
+    if (n_hits) *n_hits = nh;
+    return nc;
+  }
+
   // The document x key table of match_batch without the hit list (aha_ac_doc_counts_batch): document d's {key, count} pairs,
   // ascending by key, are [(*doc_pair_offsets)[d], (*doc_pair_offsets)[d + 1]) of what is returned.  A sizing call first.
   std::vector<aha_key_count> doc_counts_batch(std::string_view corpus, const std::vector<uint64_t> &doc_offsets,
@@ -250,6 +273,23 @@ class AC {
     if (n_hits) *n_hits = nh;
     return pairs;
   }
+
+  // Which bytes of the batch lie inside a hit of match_batch, without the hit list (aha_ac_cover_batch): bit j of the batch is
+  // word j >> 5, bit j & 31 of what is returned; doc_covered (optional): covered bytes per document.
+  std::vector<uint32_t> cover_batch(std::string_view corpus, const std::vector<uint64_t> &doc_offsets,
+                                    std::vector<uint64_t> *doc_covered = nullptr, uint64_t *n_hits = nullptr) const {
+    std::vector<uint32_t> mask;
+    cover_call(corpus, doc_offsets, &mask, nullptr, 0, doc_covered, n_hits);
+    return mask;
+  }
+  // The batch with every byte inside a hit replaced by `fill`.
+  std::string redact_batch(std::string_view corpus, const std::vector<uint64_t> &doc_offsets, char fill = '*',
+                           std::vector<uint64_t> *doc_covered = nullptr) const {
+    std::string red;
+    cover_call(corpus, doc_offsets, nullptr, &red, static_cast<uint8_t>(fill), doc_covered, nullptr);
+    return red;
+  }
+  std::string redact(std::string_view seq, char fill = '*') const { return redact_batch(seq, {0, seq.size()}, fill); }
 
   // The same on a batch resident in HBM (aha_ac_count_batch_device): d_key_counts is device memory of K uint64 (or null) and
   // keeps running totals there with accumulate; returns the hit count.

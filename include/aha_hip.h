@@ -485,6 +485,46 @@ int32_t aha_ac_doc_counts_batch_device(aha_ac *ac, const uint8_t *d_corpus, cons
                                        uint64_t *d_doc_pair_offsets /* D+1 or NULL */, uint64_t *n_pairs,
                                        uint64_t *n_hits /* or NULL */, void *stream);
 
+/* ---- cover: which bytes lie inside a hit, and a redacted copy, no hit list (pure additions to ABI 8) --------------------
+ * The same batch, params, validation and errors as aha_ac_count_batch / _device.
+ * mask: bit j of the batch (word j >> 5, bit j & 31) = 1 iff corpus byte j lies in [start, end) of at least one hit that
+ * aha_ac_match_batch reports for this batch and these params (byte offsets).  ceil(N / 32) words, every bit >= N is 0.  It
+ * is in 32-bit words so that the kernels may use word atomics without touching a byte the caller does not own; read as bytes
+ * it is LSB-first (numpy: np.unpackbits(mask.view(np.uint8), bitorder="little")[:N]).
+ * redacted[j] = fill where bit j is set, corpus[j] elsewhere.  In the device entry d_redacted == d_corpus is allowed
+ * (redaction in place); any other overlap is the caller's error.
+ * doc_covered[d] = set bits in document d's range (D entries); *n_covered = their sum; *n_hits (optional) = the match call's
+ * hit count.  Any of mask, redacted, doc_covered may be NULL; with all three NULL the call still gives the two totals.
+ * n_covered == NULL, a NULL handle, unknown flag bits (flags is 0): AHA_E_INVALID; sep_size > 256: AHA_E_SEP_SIZE;
+ * longest != 0: AHA_E_INVALID (a follow-up); a host-only handle: AHA_E_NO_DEVICE; all before any device work.
+ * char_offsets changes nothing (the byte route, as for counts).  A separator filter covers the hits that survive it.  No
+ * capacity, so no AHA_E_CAPACITY.  A call that fails writes none of the caller's buffers.  Threading (a call leases a scratch
+ * set), the device-side checking of d_doc_offsets and the host entry's staging are those of the count and document-count
+ * entries (the host entry uploads the batch in one piece and redacts it in place there).  Like a count call it reads the
+ * handle's back-off state and never writes it.  N = 0, D = 0 and empty documents are valid.  Hits never cross a document
+ * boundary, so neither does a span.  Two calls give identical bytes.
+ * Pipeline (aha_amd/csrc/scan_cover.hip): all hits of one END position end at the same byte and the first --
+ * the END state's own key -- is the longest, so the union of the hits' spans is the union of one span per event.  The call
+ * is a count call without key counts (the engine a match would take, full-size event regions, document ranges where they do
+ * not fit: aha_timing.repeats) whose events each OR [end - len(head key), end) into the mask: a bit tile in LDS per group of
+ * chunks, vector atomicOr for what lies outside it.  A separator filter and keys beyond 4096 bytes take the two-pass engine's
+ * counting traversal, where the first key on an event's chain that passes the left-neighbour test gives the span.  Then a
+ * streaming pass writes redacted and popcounts give doc_covered and the total, each only when asked for.
+ * Device scratch: the count call's + N / 8 bytes when the caller gives no mask + 8 bytes per chunk; NOTHING proportional to
+ * the hits (a match of a dense batch holds 16 bytes per hit of capacity).  The host entry stages the corpus, the offsets, the
+ * mask and the D counts on the device as well.
+ * aha_ac_last_timing: engine = the engine that traversed, n_hits, ms_write = the passes after the traversal.
+ * Out of scope so far: feeds, groups, coverage of match_longest, masks indexed by character. */
+int32_t aha_ac_cover_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc_offsets, uint64_t n_docs,
+                           const aha_match_params *params, uint32_t flags /* 0 */, uint32_t *mask /* ceil(N/32) words or NULL */,
+                           uint8_t *redacted /* N bytes or NULL */, uint8_t fill, uint64_t *doc_covered /* D or NULL */,
+                           uint64_t *n_covered, uint64_t *n_hits /* or NULL */);
+/* Device-resident form: d_ pointers are HBM on the handle's device; *n_covered, *n_hits are host memory; blocks until final. */
+int32_t aha_ac_cover_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                                  uint64_t n_bytes, const aha_match_params *params, uint32_t flags, uint32_t *d_mask,
+                                  uint8_t *d_redacted, uint8_t fill, uint64_t *d_doc_covered /* D or NULL */,
+                                  uint64_t *n_covered, uint64_t *n_hits /* or NULL */, void *stream);
+
 /* Frees the handle's device scratch (it grows with the largest batch seen and is otherwise kept for reuse). */
 int32_t aha_ac_release_scratch(aha_ac *ac);
 /* Device bytes currently held as scratch by the handle (all sets); waits for running calls. */
