@@ -29,6 +29,7 @@ AHA_E_NOMEM = -12
 
 AHA_OPT_HOST_ONLY = 1
 AHA_OPT_FORCE_WIDE = 2
+AHA_OPT_FOLD_ASCII = 4
 AHA_COUNT_ACCUMULATE = 1
 AHA_FEED_CHARS = 1
 AHA_IMG_SLOTS, AHA_IMG_END_KEY, AHA_IMG_KEY_LN, AHA_IMG_KEY_CNT, AHA_IMG_KEY_KC = 0, 1, 2, 3, 4
@@ -93,6 +94,7 @@ SIGNATURES = {
     "aha_ac_compile": (_i32, [_vp, _vp, _u32, C.POINTER(aha_options), C.POINTER(_vp), C.POINTER(_u32)]),
     "aha_ac_free": (None, [_vp]),
     "aha_ac_info": (_i32, [_vp, C.POINTER(aha_ac_info_t)]),
+    "aha_ac_flags": (_u32, [_vp]),
     "aha_ac_key": (_i32, [_vp, _i32, _vp, _i32]),
     "aha_ac_id": (_i32, [_vp, _vp, _i32]),
     "aha_ac_match_bytes": (_i32, [_vp, _vp, _u64, C.POINTER(aha_match_params), _vp, _u64, C.POINTER(_u64)]),

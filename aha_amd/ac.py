@@ -106,18 +106,22 @@ class AC:
 
     # -- Aha::AC.compile(keys) src/aha/ac.cr:62-69 ---------------------------
     @classmethod
-    def compile(cls, keys, device=-1, host_only=False, force_wide=False):
+    def compile(cls, keys, device=-1, host_only=False, force_wide=False, fold_ascii=False):
+        """fold_ascii: an ASCII case-insensitive handle (AHA_OPT_FOLD_ASCII, include/aha_hip.h): every call gives what a plain
+        handle compiled from the lower-cased keys gives over the lower-cased text ('A'..'Z' only; offsets are the original
+        text's); `redact` keeps the original bytes outside the hits, `m[id]` the keys as spelled here."""
         blob, offs = _pack_keys(keys)
-        return cls.compile_packed(blob, offs, device, host_only, force_wide)
+        return cls.compile_packed(blob, offs, device, host_only, force_wide, fold_ascii)
 
     @classmethod
-    def compile_packed(cls, blob, offs, device=-1, host_only=False, force_wide=False):
+    def compile_packed(cls, blob, offs, device=-1, host_only=False, force_wide=False, fold_ascii=False):
         blob = np.ascontiguousarray(blob, dtype=np.uint8)
         offs = np.ascontiguousarray(offs, dtype=np.uint64)
         opts = N.aha_options()
         opts.struct_size = C.sizeof(N.aha_options)
         opts.device = device
-        opts.flags = (N.AHA_OPT_HOST_ONLY if host_only else 0) | (N.AHA_OPT_FORCE_WIDE if force_wide else 0)
+        opts.flags = ((N.AHA_OPT_HOST_ONLY if host_only else 0) | (N.AHA_OPT_FORCE_WIDE if force_wide else 0) |
+                      (N.AHA_OPT_FOLD_ASCII if fold_ascii else 0))
         h = C.c_void_p()
         ek = C.c_uint32(0)
         rc = N.lib().aha_ac_compile(_ptr(blob), _ptr(offs), len(offs) - 1, C.byref(opts), C.byref(h),
@@ -150,12 +154,14 @@ class AC:
                 f.write(data)
 
     @classmethod
-    def from_bytes(cls, data, device=-1, host_only=False, force_wide=False):
+    def from_bytes(cls, data, device=-1, host_only=False, force_wide=False, fold_ascii=False):
+        """The container stores the keys as they were spelled and no options: say fold_ascii again, like force_wide."""
         buf = np.frombuffer(bytes(data), dtype=np.uint8)
         opts = N.aha_options()
         opts.struct_size = C.sizeof(N.aha_options)
         opts.device = device
-        opts.flags = (N.AHA_OPT_HOST_ONLY if host_only else 0) | (N.AHA_OPT_FORCE_WIDE if force_wide else 0)
+        opts.flags = ((N.AHA_OPT_HOST_ONLY if host_only else 0) | (N.AHA_OPT_FORCE_WIDE if force_wide else 0) |
+                      (N.AHA_OPT_FOLD_ASCII if fold_ascii else 0))
         h = C.c_void_p()
         rc = N.lib().aha_ac_load(_ptr(buf), buf.size, C.byref(opts), C.byref(h))
         if rc != N.AHA_OK:
@@ -180,6 +186,11 @@ class AC:
         i.struct_size = C.sizeof(i)  # (in: the bytes this binding's struct has; the library fills no more)
         self._check(N.lib().aha_ac_info(self._h, C.byref(i)))
         return {f: getattr(i, f) for f, _ in i._fields_ if f != "struct_size"}
+
+    @property
+    def fold_ascii(self):
+        """True for a handle compiled (or loaded) with fold_ascii=True."""
+        return bool(N.lib().aha_ac_flags(self._h) & N.AHA_OPT_FOLD_ASCII)
 
     # -- delegate :[] src/aha/ac.cr:41-43 ------------------------------------
     def __getitem__(self, x):
@@ -994,19 +1005,20 @@ class ACGroup:
                 pass
 
     @classmethod
-    def compile(cls, keys, devices, host_only=False):
+    def compile(cls, keys, devices, host_only=False, fold_ascii=False):
         blob, offs = _pack_keys(keys)
-        return cls.compile_packed(blob, offs, devices, host_only)
+        return cls.compile_packed(blob, offs, devices, host_only, fold_ascii)
 
     @classmethod
-    def compile_packed(cls, blob, offs, devices, host_only=False):
+    def compile_packed(cls, blob, offs, devices, host_only=False, fold_ascii=False):
         blob = np.ascontiguousarray(blob, dtype=np.uint8)
         offs = np.ascontiguousarray(offs, dtype=np.uint64)
         dev = np.ascontiguousarray(devices, dtype=np.int32)
         h = C.c_void_p()
         ek = C.c_uint32(0)
         rc = N.lib().aha_group_compile(_ptr(blob), _ptr(offs), offs.size - 1, _ptr(dev), dev.size,
-                                       N.AHA_OPT_HOST_ONLY if host_only else 0, C.byref(h), C.byref(ek))
+                                       (N.AHA_OPT_HOST_ONLY if host_only else 0) | (N.AHA_OPT_FOLD_ASCII if fold_ascii else 0),
+                                       C.byref(h), C.byref(ek))
         if rc != N.AHA_OK:
             raise AhaError(rc, key_index=ek.value)
         return cls(h)

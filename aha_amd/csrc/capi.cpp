@@ -3,6 +3,7 @@
 // matching fallback in this library: without a usable HIP device every match
 // entry point fails with AHA_E_NO_DEVICE.
 #include "handle.hpp"
+#include "fold.hpp"
 
 using namespace ahai;
 
@@ -308,13 +309,37 @@ int32_t aha_ac_compile(const uint8_t *key_bytes, const uint64_t *key_offsets, ui
   uint32_t flags = opts ? opts->flags : 0;
   int device = opts ? opts->device : -1;
   aha_ac *ac = new aha_ac();
+  ac->opt_flags = flags & (AHA_OPT_HOST_ONLY | AHA_OPT_FORCE_WIDE | AHA_OPT_FOLD_ASCII);
   BuildError be;
   static const uint8_t dummy = 0;
-  if (!build_automaton(key_bytes ? key_bytes : &dummy, key_offsets, n_keys, ac->aut, be)) {
+  // AHA_OPT_FOLD_ASCII: the automaton -- and with it both images, the filter, the stale ends and the duplicate check (two keys
+  // equal after folding: AHA_E_DUP_KEY at the second) -- is built from a folded copy of the keys; the handle keeps the
+  // caller's spelling beside it
+  // (only the keys' own bytes [offs[0], offs[K]) are copied, with the offsets rebased as build_automaton rebases them)
+  std::vector<uint8_t> folded;
+  std::vector<uint64_t> rebased;
+  const uint8_t *build_from = key_bytes ? key_bytes : &dummy;
+  const uint64_t *build_offs = key_offsets;
+  if (ac->fold() && key_bytes && n_keys && key_offsets[n_keys] >= key_offsets[0]) {
+    try {
+      ac->key_spelling.assign(key_bytes + key_offsets[0], key_bytes + key_offsets[n_keys]);
+      folded = ac->key_spelling;
+      rebased.assign(key_offsets, key_offsets + n_keys + 1);
+    } catch (...) {
+      delete ac;
+      return AHA_E_NOMEM;
+    }
+    fold_bytes(folded.data(), folded.size());
+    for (auto &o : rebased) o -= key_offsets[0];
+    build_from = folded.data();
+    build_offs = rebased.data();
+  }
+  if (!build_automaton(build_from, build_offs, n_keys, ac->aut, be)) {
     if (err_key) *err_key = be.key_index;
     delete ac;
     return be.code;
   }
+  std::vector<uint8_t>().swap(folded);
   Placement pl;
   Image &img = ac->img;
   // Shadow fail links (default): fail links of depth <= 2 targets are recomputed from the last two input bytes, so
@@ -421,6 +446,8 @@ int32_t aha_ac_replicate(const aha_ac *src, int32_t device, aha_ac **out) {
   try {
     ac = new aha_ac();
     ac->aut = src->aut;
+    ac->opt_flags = src->opt_flags & ~AHA_OPT_HOST_ONLY;
+    ac->key_spelling = src->key_spelling;
     ac->img = src->img;
     ac->n_slots = src->n_slots;
     ac->slot_bytes = src->slot_bytes;
@@ -561,7 +588,7 @@ int64_t aha_ac_save(const aha_ac *ac, void *buf, uint64_t cap_bytes) {
   put(&K, 4);
   put(&blob_bytes, 8);
   put(ac->aut.offs.data(), 8ull * (K + 1));
-  put(ac->aut.blob.data(), blob_bytes);
+  put(ac->fold() ? ac->key_spelling.data() : ac->aut.blob.data(), blob_bytes);  // (the keys as the caller spelled them)
   const uint64_t h = fnv1a(w, o);
   put(&h, 8);
   return (int64_t)o;
@@ -661,13 +688,27 @@ int32_t aha_ac_key(const aha_ac *ac, int32_t id, uint8_t *buf, int32_t cap) {
   if (!ac) return AHA_E_INVALID;
   if (id < 0 || (uint32_t)id >= ac->aut.n_keys) return AHA_E_NOT_FOUND;
   uint64_t o = ac->aut.offs[id], n = ac->aut.offs[id + 1] - o;
-  if (buf && cap > 0) memcpy(buf, ac->aut.blob.data() + o, std::min<uint64_t>(n, (uint64_t)cap));
+  const uint8_t *keys = ac->fold() ? ac->key_spelling.data() : ac->aut.blob.data();  // (as the caller spelled them)
+  if (buf && cap > 0 && n) memcpy(buf, keys + o, std::min<uint64_t>(n, (uint64_t)cap));
   return (int32_t)n;
 }
 
+uint32_t aha_ac_flags(const aha_ac *ac) { return ac ? ac->opt_flags : 0u; }
+
 int32_t aha_ac_id(const aha_ac *ac, const uint8_t *key, int32_t len) {
   if (!ac || (!key && len > 0)) return AHA_E_INVALID;
-  int32_t k = ac->aut.find_key(key, len);
+  int32_t k;
+  if (ac->fold() && len > 0) {
+    try {
+      std::vector<uint8_t> q(key, key + len);
+      fold_bytes(q.data(), q.size());
+      k = ac->aut.find_key(q.data(), len);
+    } catch (...) {
+      return AHA_E_NOMEM;
+    }
+  } else {
+    k = ac->aut.find_key(key, len);
+  }
   return k < 0 ? AHA_E_NOT_FOUND : k;
 }
 

@@ -257,6 +257,26 @@ static void *cover_reserve(Scratch *sc, int i, size_t bytes) {
   return b.p;
 }
 
+// A folded handle (AHA_OPT_FOLD_ASCII): the folded copy of a batch, in the scratch slot of the "aligned copy of an unaligned
+// corpus" (v2buf[17]) -- one streaming pass does both jobs (scan_fold.hip), and the caller's text is only read.
+static int32_t fold_into_scratch(aha_ac *ac, Scratch *sc, const uint8_t *src, uint64_t n_bytes, hipStream_t s, const uint8_t **out) {
+  int32_t rc;
+  if ((rc = v2_reserve(ac, sc, 17, n_bytes + 64))) return rc;
+  fold_launch_copy(src, (uint8_t *)sc->v2buf[17].p, n_bytes, 8u * std::max<uint32_t>(ac->v2_grid, 64u), s);
+  HIPCHK(ac, hipGetLastError());
+  *out = (const uint8_t *)sc->v2buf[17].p;
+  return AHA_OK;
+}
+// M.fold: M.text is still the caller's.  Only the prefix-filter engine takes it like that (it folds in its own loads); every
+// other path -- the byte-level and character-level engines, the opt-in ones, the two-pass engine, match_longest, a pass
+// behind a hand-back of the filter -- calls this first: the copy is made at that moment, once per call.
+static int32_t stage_folded(aha_ac *ac, Scratch *sc, MatchArgs &M, hipStream_t s) {
+  if (!M.fold) return AHA_OK;
+  const int32_t rc = fold_into_scratch(ac, sc, M.text, M.n_bytes, s, &M.text);
+  if (rc == AHA_OK) M.fold = 0;
+  return rc;
+}
+
 int32_t match_v2(aha_ac *ac, Scratch *sc, MatchArgs &M1, hipStream_t s, uint64_t *n_hits, V2Mode mode) {
   const uint64_t N = M1.n_bytes;
   const uint32_t Lmax = ac->aut.max_key_len;
@@ -292,7 +312,6 @@ int32_t match_v2(aha_ac *ac, Scratch *sc, MatchArgs &M1, hipStream_t s, uint64_t
                          ac->pair_off.load(std::memory_order_relaxed) < 3;
   if (want_pair) S = pair_tile_bytes();
   V2Args M{};
-  M.text = M1.text;
   M.doc_off = M1.doc_off;
   M.n_docs = M1.n_docs;
   M.n_bytes = N;
@@ -371,6 +390,9 @@ int32_t match_v2(aha_ac *ac, Scratch *sc, MatchArgs &M1, hipStream_t s, uint64_t
       return rc;
     }
   }
+  if (M1.fold && !filt && (rc = stage_folded(ac, sc, M1, s))) return rc;
+  const bool fold_loads = filt && M1.fold;  // (the filter engine on the caller's own text)
+  M.text = M1.text;
   M.ev = (uint4 *)sc->v2buf[0].p;
   M.sorted_ev = (uint4 *)sc->v2buf[1].p;
   M.sorted_cnt = (uint32_t *)sc->v2buf[2].p;
@@ -435,9 +457,9 @@ int32_t match_v2(aha_ac *ac, Scratch *sc, MatchArgs &M1, hipStream_t s, uint64_t
   } else if (filt) {
     // filter (one bit per byte position), then the candidates' goto walks, a wave per chunk
     unsigned long long *non_ascii = M1.chars ? M.cursor + 6 : nullptr;
-    filter_launch_filter(ac->fdev, M, sc->v2buf[22].p, sc->v2buf[23].p, non_ascii, ac->pf_cus, s);
+    (fold_loads ? filter_launch_filter_fold : filter_launch_filter)(ac->fdev, M, sc->v2buf[22].p, sc->v2buf[23].p, non_ascii, ac->pf_cus, s);
     if (prof) HIPCHK(ac, hipEventRecord(sc->ev[2], s));  // (profiling only: ms_count = the filter, ms_scan = the walks)
-    filter_launch_walk(ac->dev, M, sc->v2buf[22].p, sc->v2buf[23].p, non_ascii, ac->pf_cus, s);
+    (fold_loads ? filter_launch_walk_fold : filter_launch_walk)(ac->dev, M, sc->v2buf[22].p, sc->v2buf[23].p, non_ascii, ac->pf_cus, s);
   } else {
     v2_launch_traverse(ac->dev, M, (uint32_t)std::min<uint64_t>(ac->v2_grid, n_tiles), s);
   }
@@ -644,9 +666,15 @@ int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
   if (reinterpret_cast<uintptr_t>(d_corpus) % 16 != 0) {
     // the kernels read the corpus in aligned 16-byte pieces: an unaligned view (a slice of a larger buffer) is copied
     // once, device to device, into the handle's scratch (~0.7 ms per GiB: about a fifth of the match itself)
-    if ((rc = v2_reserve(ac, sc, 17, n_bytes + 64))) return rc;
-    HIPCHK(ac, hipMemcpyAsync(sc->v2buf[17].p, d_corpus, n_bytes, hipMemcpyDeviceToDevice, s));
-    d_corpus = (const uint8_t *)sc->v2buf[17].p;
+    if (ac->fold()) {  // (folded on the way: the one pass does both jobs)
+      if ((rc = fold_into_scratch(ac, sc, d_corpus, n_bytes, s, &d_corpus))) return rc;
+    } else {
+      if ((rc = v2_reserve(ac, sc, 17, n_bytes + 64))) return rc;
+      HIPCHK(ac, hipMemcpyAsync(sc->v2buf[17].p, d_corpus, n_bytes, hipMemcpyDeviceToDevice, s));
+      d_corpus = (const uint8_t *)sc->v2buf[17].p;
+    }
+  } else if (ac->fold()) {
+    M.fold = 1;  // (the caller's text, aligned: the prefix-filter engine reads it where it lies, the others stage it)
   }
   M.text = d_corpus;
   M.doc_off = d_doc_offsets;
@@ -656,6 +684,8 @@ int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
   M.cap = cap;
   M.doc_hit_off = d_doc_hit_offsets;
   if (longest) {
+    if ((rc = stage_folded(ac, sc, M, s))) return rc;
+    d_corpus = M.text;
     // match_longest: count -> scan -> write, like the two-pass engine (kernels.hip)
     int mode = longest == 1 ? 1 : (M.chars ? 3 : 2);
     if ((rc = ensure_scratch(ac, sc, 1, 1, n_docs))) return rc;
@@ -761,6 +791,7 @@ int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
     repeats++;
     if (M.check_docs && (rc = check_now())) return rc;  // (no single-traversal pass has looked at the offsets)
   }
+  if ((rc = stage_folded(ac, sc, M, s))) return rc;
   M.chunk = ac->chunk;
   // warm-up is Lmax-1 bytes per chunk: keep it a small fraction of the chunk
   while (M.chunk < 8ull * ac->aut.max_key_len && M.chunk < (1u << 20)) M.chunk *= 2;
@@ -819,6 +850,7 @@ int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
 // The two-pass engine's counting form over one batch: ONE traversal (k_count with per-key adds; it notes every document's
 // hits before its start within its chunk, k_count_doc_offsets adds the chunks' bases), the scan, the chain pass.
 static int32_t count_two_pass(aha_ac *ac, Scratch *sc, MatchArgs M, hipStream_t s, uint64_t *n_hits, uint32_t repeats) {
+  if (int32_t rcf = stage_folded(ac, sc, M, s)) return rcf;
   M.chunk = ac->chunk;
   // warm-up is Lmax-1 bytes per chunk: keep it a small fraction of the chunk
   while (M.chunk < 8ull * ac->aut.max_key_len && M.chunk < (1u << 20)) M.chunk *= 2;
@@ -939,16 +971,26 @@ static int32_t count_ranges(aha_ac *ac, Scratch *sc, const MatchArgs &M0, hipStr
     }
     HIPCHK(ac, hipMemcpyAsync(d_rel, rel.data(), (nd + 1) * 8, hipMemcpyHostToDevice, s));
     const uint8_t *text = M0.text + off[d0];
-    if (nb && reinterpret_cast<uintptr_t>(text) % 16 != 0) {  // (the kernels read aligned 16-byte pieces)
+    // (the kernels read aligned 16-byte pieces; a folded handle whose text is still the caller's: an unaligned range is folded
+    // on the way, an aligned one stays the caller's -- the prefix-filter engine folds in its loads, the others stage it)
+    int32_t range_fold = M0.fold;
+    if (nb && reinterpret_cast<uintptr_t>(text) % 16 != 0) {
       uint8_t *t = (uint8_t *)count_reserve(sc, 1, nb + 64);
       if (!t) {
         tls_err = "hipMalloc failed for a document range of a count call";
         return AHA_E_HIP;
       }
-      HIPCHK(ac, hipMemcpyAsync(t, text, nb, hipMemcpyDeviceToDevice, s));
+      if (M0.fold) {
+        fold_launch_copy(text, t, nb, 8u * std::max<uint32_t>(ac->v2_grid, 64u), s);
+        HIPCHK(ac, hipGetLastError());
+      } else {
+        HIPCHK(ac, hipMemcpyAsync(t, text, nb, hipMemcpyDeviceToDevice, s));
+      }
       text = t;
+      range_fold = 0;
     }
     MatchArgs M = M0;
+    M.fold = range_fold;
     M.text = text;
     M.doc_off = d_rel;
     M.n_docs = nd;
@@ -969,6 +1011,7 @@ static int32_t count_ranges(aha_ac *ac, Scratch *sc, const MatchArgs &M0, hipStr
       }
       if (rc == 4 || rc == 1) {
         M = M0;
+        M.fold = range_fold;
         M.text = text;
         M.doc_off = d_rel;
         M.n_docs = nd;
@@ -1041,9 +1084,15 @@ int32_t device_count(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
   }
   if (!d_corpus) return AHA_E_INVALID;
   if (reinterpret_cast<uintptr_t>(d_corpus) % 16 != 0) {
-    if ((rc = v2_reserve(ac, sc, 17, n_bytes + 64))) return rc;
-    HIPCHK(ac, hipMemcpyAsync(sc->v2buf[17].p, d_corpus, n_bytes, hipMemcpyDeviceToDevice, s));
-    d_corpus = (const uint8_t *)sc->v2buf[17].p;
+    if (ac->fold()) {  // (folded on the way: the one pass does both jobs)
+      if ((rc = fold_into_scratch(ac, sc, d_corpus, n_bytes, s, &d_corpus))) return rc;
+    } else {
+      if ((rc = v2_reserve(ac, sc, 17, n_bytes + 64))) return rc;
+      HIPCHK(ac, hipMemcpyAsync(sc->v2buf[17].p, d_corpus, n_bytes, hipMemcpyDeviceToDevice, s));
+      d_corpus = (const uint8_t *)sc->v2buf[17].p;
+    }
+  } else if (ac->fold()) {
+    M.fold = 1;  // (the caller's text, aligned: the prefix-filter engine reads it where it lies, the others stage it)
   }
   M.text = d_corpus;
   M.doc_off = d_doc_offsets;
@@ -1281,7 +1330,8 @@ int32_t device_doc_counts(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, cons
       HIPCHK(ac, hipMemcpyAsync(r, rel.data(), (nd + 1) * 8, hipMemcpyHostToDevice, s));
       d_rel = r;
       text = d_corpus + off[d0];
-      if (reinterpret_cast<uintptr_t>(text) % 16 != 0) {  // (the kernels read aligned 16-byte pieces)
+      // (the kernels read aligned 16-byte pieces; a folded handle's match and count make their own folded -- and aligned -- copy)
+      if (!ac->fold() && reinterpret_cast<uintptr_t>(text) % 16 != 0) {
         uint8_t *t = (uint8_t *)dc_reserve(sc, 3, nb + 64);
         if (!t) return nomem();
         HIPCHK(ac, hipMemcpyAsync(t, text, nb, hipMemcpyDeviceToDevice, s));

@@ -63,6 +63,12 @@ extern thread_local std::string tls_err;
 using namespace aha;  // (the library's own translation units only)
 struct aha_ac {
   Automaton aut;
+  // AHA_OPT_* the handle was compiled with (aha_ac_flags).  With AHA_OPT_FOLD_ASCII `aut` -- its blob included -- is that of the
+  // FOLDED keys (fold.hpp): everything derived from it (images, filter, stale ends, find_key) is what a plain handle compiled
+  // from fold(keys) has; key_spelling holds the keys as the caller wrote them (same offsets) for aha_ac_key and aha_ac_save
+  uint32_t opt_flags = 0;
+  std::vector<uint8_t> key_spelling;
+  bool fold() const { return (opt_flags & AHA_OPT_FOLD_ASCII) != 0; }
   Image img;  // host copy of the device image (export / debugging)
   uint32_t n_slots = 0;
   uint32_t slot_bytes = 0;

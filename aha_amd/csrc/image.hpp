@@ -77,6 +77,10 @@ struct MatchArgs {
   uint32_t *cover_mask;              // bit cover_bit0 + j = byte j of this batch; null: not a cover call
   uint64_t cover_bit0;               // the batch's first byte in the mask (a document range of a larger batch)
   int32_t cover_clear;               // host side: the pass clears the mask itself, once it knows the offsets are good
+  // host side, a handle compiled with AHA_OPT_FOLD_ASCII: `text` is still the caller's (16-byte aligned) and not folded yet.  The
+  // prefix-filter engine reads it as it is and folds in its loads; every other path takes the folded copy first (engine.cpp
+  // stage_folded), which clears this
+  int32_t fold;
 };
 
 constexpr int kBlock = 256;  // threads per block in the traversal kernels
@@ -221,6 +225,14 @@ void filter_launch_filter(const FilterDev &F, const V2Args &M, void *bitmap, voi
                           uint32_t cus, void *stream);
 void filter_launch_walk(const DevAut &A, const V2Args &M, const void *bitmap, const void *chunk_rec, const unsigned long long *non_ascii,
                         uint32_t cus, void *stream);
+
+// the same two launches for a folded handle (AHA_OPT_FOLD_ASCII): every text load folds (fold.hpp), M.text is the caller's
+void filter_launch_filter_fold(const FilterDev &F, const V2Args &M, void *bitmap, void *chunk_rec, unsigned long long *non_ascii,
+                               uint32_t cus, void *stream);
+void filter_launch_walk_fold(const DevAut &A, const V2Args &M, const void *bitmap, const void *chunk_rec,
+                             const unsigned long long *non_ascii, uint32_t cus, void *stream);
+// scan_fold.hip: dst[j] = fold(src[j]) for j < n_bytes; src any byte address, dst 16-byte aligned; src is only read
+void fold_launch_copy(const uint8_t *src, uint8_t *dst, uint64_t n_bytes, uint32_t max_blocks, void *stream);
 
 size_t v2_lds_bytes(uint32_t lds_slots, bool compact);
 int v2_prepare(bool compact, size_t lds_bytes);  // raises the dynamic-LDS limit; hipError_t as int

@@ -25,6 +25,7 @@
 
 #include "automaton.hpp"
 #include "devcommon.hpp"
+#include "fold.hpp"
 #include "image.hpp"
 
 namespace aha {
@@ -62,7 +63,9 @@ __device__ __forceinline__ void kf_chunk_doc(const V2Args &M, KfChunk *rec, uint
 // w * 0x9E3779B1 of the D bytes (little endian, D < 4: the upper bytes masked off) selects a word with its top log2 bits and
 // two bits of that word with the ten bits below (capi.cpp sets them: filter_entry) -- no fold of the product: its upper half is
 // where a multiplicative hash has mixed all of w's bytes, and the word index carries the discrimination.
-template <bool D4>
+// FOLD (a handle compiled with AHA_OPT_FOLD_ASCII; fold.hpp): the text is folded as it is loaded -- the window's five words, its
+// byte-wise tail -- so the filter and the walks see fold(text) while the caller's bytes are read where they lie.
+template <bool D4, bool FOLD>
 __global__ __launch_bounds__(1024) void kf_filter(FilterDev F, const uint8_t *__restrict__ text, uint64_t n_bytes,
                                                    uint16_t *__restrict__ bitmap, unsigned long long *non_ascii, V2Args M,
                                                    KfChunk *chunk_rec, uint32_t filter_blocks) {
@@ -94,6 +97,10 @@ __global__ __launch_bounds__(1024) void kf_filter(FilterDev F, const uint8_t *__
     } else {
       for (int j = 0; j < 20 && g + j < n_bytes; j++) d[j >> 2] |= (uint32_t)text[g + j] << ((j & 3) * 8);
     }
+    if (FOLD) {
+#pragma unroll
+      for (int j = 0; j < 5; j++) d[j] = fold32(d[j]);
+    }
     uint32_t bits = 0;
 #pragma unroll
     for (int k = 0; k < 16; k++) {
@@ -113,6 +120,7 @@ __global__ __launch_bounds__(1024) void kf_filter(FilterDev F, const uint8_t *__
 typedef uint32_t kf_v4u __attribute__((ext_vector_type(4)));
 
 // 16 text bytes from any byte address (gfx950 global loads take unaligned addresses); bytes beyond the text read as 0
+template <bool FOLD>
 __device__ __forceinline__ kf_v4u kf_text16(const uint8_t *__restrict__ text, int64_t g, int64_t N) {
   kf_v4u v = {0u, 0u, 0u, 0u};
   if (g + 16 <= N) {
@@ -130,6 +138,7 @@ __device__ __forceinline__ kf_v4u kf_text16(const uint8_t *__restrict__ text, in
     }
     v = kf_v4u{w0, w1, w2, w3};
   }
+  if (FOLD) v = kf_v4u{fold32(v[0]), fold32(v[1]), fold32(v[2]), fold32(v[3])};
   return v;
 }
 
@@ -141,7 +150,7 @@ __device__ __forceinline__ kf_v4u kf_text16(const uint8_t *__restrict__ text, in
 // leaves for k2d_expand<.., true>.  A character = a byte that is no continuation byte (10xxxxxx), as there.  While the batch
 // is plain ASCII (kf_filter has looked at every byte: *non_ascii) the count IS the offset; otherwise the wave reads its chunk
 // once more, coalesced, and keeps the continuation bytes' mask and running count per 64 bytes in LDS.
-template <bool IMG, bool CHARS>
+template <bool IMG, bool CHARS, bool FOLD>
 __global__ __launch_bounds__(IMG ? 1024 : 256) void kf_walk(DevAut A, V2Args M, const unsigned long long *__restrict__ bitmap,
                                                              const KfChunk *__restrict__ chunk_rec,
                                                              const unsigned long long *non_ascii) {
@@ -210,7 +219,7 @@ __global__ __launch_bounds__(IMG ? 1024 : 256) void kf_walk(DevAut A, V2Args M, 
       for (uint32_t j = 0; j < M.S / 1024u; j++) {
         const uint32_t P = j * 64u + (uint32_t)lane;
         const int64_t g = a + (int64_t)P * 16;
-        const kf_v4u v = g < N ? kf_text16(M.text, g, N) : kf_v4u{0u, 0u, 0u, 0u};
+        const kf_v4u v = g < N ? kf_text16<FOLD>(M.text, g, N) : kf_v4u{0u, 0u, 0u, 0u};
         uint32_t bits = 0;
 #pragma unroll
         for (int k = 0; k < 4; k++) {
@@ -286,7 +295,7 @@ __global__ __launch_bounds__(IMG ? 1024 : 256) void kf_walk(DevAut A, V2Args M, 
     // (the text of a batch's candidates, 16 bytes each straight from memory -- they are too few to stage the chunk for
     // them -- is asked for a batch ahead)
     uint32_t qn = (uint32_t)lane < total ? list[lane] : 0u;
-    kf_v4u tn = (uint32_t)lane < total ? kf_text16(M.text, g0 + (int64_t)qn, N) : kf_v4u{0u, 0u, 0u, 0u};
+    kf_v4u tn = (uint32_t)lane < total ? kf_text16<FOLD>(M.text, g0 + (int64_t)qn, N) : kf_v4u{0u, 0u, 0u, 0u};
     for (uint32_t first = 0; first < total; first += 64) {
       const bool have = first + (uint32_t)lane < total;
       const uint32_t q = qn;
@@ -294,7 +303,7 @@ __global__ __launch_bounds__(IMG ? 1024 : 256) void kf_walk(DevAut A, V2Args M, 
       if (first + 64 < total) {
         const bool hn = first + 64 + (uint32_t)lane < total;
         qn = hn ? list[first + 64 + lane] : 0u;
-        tn = hn ? kf_text16(M.text, g0 + (int64_t)qn, N) : kf_v4u{0u, 0u, 0u, 0u};
+        tn = hn ? kf_text16<FOLD>(M.text, g0 + (int64_t)qn, N) : kf_v4u{0u, 0u, 0u, 0u};
       }
       // ---- the candidate's document: [ds, de) as offsets (a start in a document that ends before the chunk is dead)
       int32_t ds = 0;  // the document's first byte (negative: it starts before offset 0)
@@ -328,7 +337,7 @@ __global__ __launch_bounds__(IMG ? 1024 : 256) void kf_walk(DevAut A, V2Args M, 
       for (uint32_t blk = 0; blk * 16 < A.max_len; blk++) {
         if (!__builtin_amdgcn_ballot_w64(alive & p < de)) break;
         kf_v4u t = t0;
-        if (blk) t = alive ? kf_text16(M.text, g0 + (int64_t)q + (int64_t)blk * 16, N) : kf_v4u{0u, 0u, 0u, 0u};
+        if (blk) t = alive ? kf_text16<FOLD>(M.text, g0 + (int64_t)q + (int64_t)blk * 16, N) : kf_v4u{0u, 0u, 0u, 0u};
         bool run = true;  // (wave-uniform; looked at again every four steps)
 #pragma unroll
         for (int i = 0; i < 16; i++) {
@@ -457,22 +466,32 @@ static size_t walk_lds(bool img, uint32_t n_slots, uint32_t W, bool chars) {
   return (size_t)(img ? 16 : 4) * kf_wave_lds(W, chars) + (img ? (size_t)n_slots * 4 : 0);
 }
 
-void filter_launch_filter(const FilterDev &F, const V2Args &M, void *bitmap, void *chunk_rec, unsigned long long *non_ascii,
-                          uint32_t cus, void *stream) {
+template <bool FOLD>
+static void launch_filter(const FilterDev &F, const V2Args &M, void *bitmap, void *chunk_rec, unsigned long long *non_ascii, uint32_t cus,
+                          void *stream) {
   // two blocks per CU (2 x 64 KiB of LDS): the loop is VALU work, eight waves per SIMD hide its loads; behind them the
   // blocks that write the chunk records (1024 chunks each)
   const uint32_t fb = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((M.n_bytes + 16383) / 16384, (uint64_t)cus * 2));
   const uint32_t grid = fb + (uint32_t)((M.n_chunks + 1023) / 1024);
   if (F.d >= 4)
-    hipLaunchKernelGGL(kf_filter<true>, dim3(grid), dim3(1024), 0, (hipStream_t)stream, F, M.text, M.n_bytes, (uint16_t *)bitmap,
+    hipLaunchKernelGGL((kf_filter<true, FOLD>), dim3(grid), dim3(1024), 0, (hipStream_t)stream, F, M.text, M.n_bytes, (uint16_t *)bitmap,
                        non_ascii, M, (KfChunk *)chunk_rec, fb);
   else
-    hipLaunchKernelGGL(kf_filter<false>, dim3(grid), dim3(1024), 0, (hipStream_t)stream, F, M.text, M.n_bytes, (uint16_t *)bitmap,
+    hipLaunchKernelGGL((kf_filter<false, FOLD>), dim3(grid), dim3(1024), 0, (hipStream_t)stream, F, M.text, M.n_bytes, (uint16_t *)bitmap,
                        non_ascii, M, (KfChunk *)chunk_rec, fb);
+}
+void filter_launch_filter(const FilterDev &F, const V2Args &M, void *bitmap, void *chunk_rec, unsigned long long *non_ascii,
+                          uint32_t cus, void *stream) {
+  launch_filter<false>(F, M, bitmap, chunk_rec, non_ascii, cus, stream);
+}
+void filter_launch_filter_fold(const FilterDev &F, const V2Args &M, void *bitmap, void *chunk_rec, unsigned long long *non_ascii,
+                               uint32_t cus, void *stream) {
+  launch_filter<true>(F, M, bitmap, chunk_rec, non_ascii, cus, stream);
 }
 
 // M.S: the chunk, 4096 << {0, 1, 2, 3}; cus: the device's compute units (a block per CU when the image sits in LDS)
-void filter_launch_walk(const DevAut &A, const V2Args &M, const void *bitmap, const void *chunk_rec, const unsigned long long *non_ascii,
+template <bool FOLD>
+static void launch_walk(const DevAut &A, const V2Args &M, const void *bitmap, const void *chunk_rec, const unsigned long long *non_ascii,
                         uint32_t cus, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   const bool chars = M.chars != 0;
@@ -484,21 +503,31 @@ void filter_launch_walk(const DevAut &A, const V2Args &M, const void *bitmap, co
     const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((M.n_chunks + 15) / 16, cus));
     const size_t lds = walk_lds(true, A.n_slots, W, chars);
     if (chars)
-      hipLaunchKernelGGL((kf_walk<true, true>), dim3(grid), dim3(1024), lds, s, A, M, bm, cr, non_ascii);
+      hipLaunchKernelGGL((kf_walk<true, true, FOLD>), dim3(grid), dim3(1024), lds, s, A, M, bm, cr, non_ascii);
     else
-      hipLaunchKernelGGL((kf_walk<true, false>), dim3(grid), dim3(1024), lds, s, A, M, bm, cr, non_ascii);
+      hipLaunchKernelGGL((kf_walk<true, false, FOLD>), dim3(grid), dim3(1024), lds, s, A, M, bm, cr, non_ascii);
   } else {
     const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((M.n_chunks + 3) / 4, (uint64_t)cus * 5));
     const size_t lds = walk_lds(false, 0, W, chars);
     if (chars)
-      hipLaunchKernelGGL((kf_walk<false, true>), dim3(grid), dim3(256), lds, s, A, M, bm, cr, non_ascii);
+      hipLaunchKernelGGL((kf_walk<false, true, FOLD>), dim3(grid), dim3(256), lds, s, A, M, bm, cr, non_ascii);
     else
-      hipLaunchKernelGGL((kf_walk<false, false>), dim3(grid), dim3(256), lds, s, A, M, bm, cr, non_ascii);
+      hipLaunchKernelGGL((kf_walk<false, false, FOLD>), dim3(grid), dim3(256), lds, s, A, M, bm, cr, non_ascii);
   }
 }
 
+void filter_launch_walk(const DevAut &A, const V2Args &M, const void *bitmap, const void *chunk_rec, const unsigned long long *non_ascii,
+                        uint32_t cus, void *stream) {
+  launch_walk<false>(A, M, bitmap, chunk_rec, non_ascii, cus, stream);
+}
+void filter_launch_walk_fold(const DevAut &A, const V2Args &M, const void *bitmap, const void *chunk_rec,
+                             const unsigned long long *non_ascii, uint32_t cus, void *stream) {
+  launch_walk<true>(A, M, bitmap, chunk_rec, non_ascii, cus, stream);
+}
+
 int filter_prepare() {
-  const void *fs[2] = {reinterpret_cast<const void *>(&kf_walk<true, false>), reinterpret_cast<const void *>(&kf_walk<true, true>)};
+  const void *fs[4] = {reinterpret_cast<const void *>(&kf_walk<true, false, false>), reinterpret_cast<const void *>(&kf_walk<true, true, false>),
+                       reinterpret_cast<const void *>(&kf_walk<true, false, true>), reinterpret_cast<const void *>(&kf_walk<true, true, true>)};
   for (const void *f : fs)
     if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kfLdsBudget) != hipSuccess) {
       (void)hipGetLastError();  // (not left for the next call's check to find)

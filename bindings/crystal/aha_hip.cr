@@ -38,6 +38,8 @@ lib LibAhaHip
     value : Int32
   end
 
+  OPT_FOLD_ASCII = 4_u32 # compile-time flag: 'A'..'Z' of keys and text match as 'a'..'z' (include/aha_hip.h)
+
   struct Options
     struct_size : UInt32
     device : Int32
@@ -134,6 +136,8 @@ lib LibAhaHip
   # a second handle for the same keys on another device: nothing is compiled again (what aha_group_compile does)
   fun aha_ac_replicate(ac : Ac, device : Int32, out : Ac*) : Int32
   fun aha_ac_info(ac : Ac, info : Info*) : Int32
+  # the AHA_OPT_* bits the handle was compiled with (OPT_FOLD_ASCII: an ASCII case-insensitive handle)
+  fun aha_ac_flags(ac : Ac) : UInt32
   fun aha_ac_set_profiling(ac : Ac, enabled : Int32) : Int32
   fun aha_ac_last_timing(ac : Ac, t : Timing*) : Int32
   # ABI 7: the device match that also leaves the hits as the 4-byte exchange stream
@@ -268,11 +272,14 @@ module Aha
       LibAhaHip.aha_ac_free(@handle)
     end
 
-    def self.compile(keys : Array(String) | Array(Array(UInt8)) | Array(Bytes)) : self
+    # fold_ascii: an ASCII case-insensitive handle -- every call gives what a plain handle compiled from the lower-cased keys
+    # gives over the lower-cased text ('A'..'Z' only); ac[id] keeps the spelling given here
+    def self.compile(keys : Array(String) | Array(Array(UInt8)) | Array(Bytes), fold_ascii : Bool = false) : self
       blob, offs = pack_keys(keys)
       opts = LibAhaHip::Options.new
       opts.struct_size = sizeof(LibAhaHip::Options).to_u32
       opts.device = -1
+      opts.flags = fold_ascii ? LibAhaHip::OPT_FOLD_ASCII : 0_u32
       rc = LibAhaHip.aha_ac_compile(blob.to_slice.to_unsafe, offs.to_unsafe, keys.size.to_u32,
         pointerof(opts), out handle, out bad)
       if rc == E_DUP_KEY
@@ -514,11 +521,20 @@ module Aha
       io.write buf
     end
 
-    def self.from_io(io : IO, format : IO::ByteFormat = IO::ByteFormat::LittleEndian) : self
+    # (the container stores the keys as spelled and no options: say fold_ascii again)
+    def self.from_io(io : IO, format : IO::ByteFormat = IO::ByteFormat::LittleEndian, fold_ascii : Bool = false) : self
       data = io.gets_to_end.to_slice
-      rc = LibAhaHip.aha_ac_load(data.to_unsafe.as(Void*), data.size.to_u64, Pointer(LibAhaHip::Options).null, out h)
+      opts = LibAhaHip::Options.new
+      opts.struct_size = sizeof(LibAhaHip::Options).to_u32
+      opts.device = -1
+      opts.flags = fold_ascii ? LibAhaHip::OPT_FOLD_ASCII : 0_u32
+      rc = LibAhaHip.aha_ac_load(data.to_unsafe.as(Void*), data.size.to_u64, pointerof(opts), out h)
       raise String.new(LibAhaHip.aha_strerror(rc)) if rc != 0
       new(h)
+    end
+
+    def fold_ascii? : Bool
+      (LibAhaHip.aha_ac_flags(@handle) & LibAhaHip::OPT_FOLD_ASCII) != 0
     end
 
     def [](sid : Int) : String
@@ -628,10 +644,10 @@ module Aha
       LibAhaHip.aha_group_free(@group)
     end
 
-    def self.compile(keys : Array(String) | Array(Bytes), devices : Array(Int32)) : self
+    def self.compile(keys : Array(String) | Array(Bytes), devices : Array(Int32), fold_ascii : Bool = false) : self
       blob, offs = AC.pack_keys(keys)
       rc = LibAhaHip.aha_group_compile(blob.to_slice.to_unsafe, offs.to_unsafe, keys.size.to_u32,
-        devices.to_unsafe, devices.size, 0_u32, out group, out bad)
+        devices.to_unsafe, devices.size, fold_ascii ? LibAhaHip::OPT_FOLD_ASCII : 0_u32, out group, out bad)
       if rc == AC::E_DUP_KEY
         raise "key:#{keys[bad]} appear twice."
       elsif rc != 0

@@ -79,8 +79,9 @@ class AC {
   AC(AC &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
   ~AC() { aha_ac_free(h_); }
 
-  // Aha::AC.compile(keys)
-  static AC compile(const std::vector<std::string> &keys, int device = -1) {
+  // Aha::AC.compile(keys).  fold_ascii: an ASCII case-insensitive handle (AHA_OPT_FOLD_ASCII, aha_hip.h): every call gives what a
+  // plain handle compiled from the lower-cased keys gives over the lower-cased text; key(id) keeps the spelling given here
+  static AC compile(const std::vector<std::string> &keys, int device = -1, bool fold_ascii = false) {
     std::vector<uint8_t> blob;
     std::vector<uint64_t> offs(keys.size() + 1, 0);
     for (size_t i = 0; i < keys.size(); i++) {
@@ -90,6 +91,7 @@ class AC {
     aha_options o{};
     o.struct_size = sizeof(o);
     o.device = device;
+    o.flags = fold_ascii ? AHA_OPT_FOLD_ASCII : 0u;
     aha_ac *h = nullptr;
     uint32_t bad = 0;
     int32_t rc = aha_ac_compile(blob.data(), offs.data(), (uint32_t)keys.size(), &o, &h, &bad);
@@ -341,15 +343,18 @@ class AC {
     aha_ac_save(h_, v.data(), (uint64_t)n);
     return v;
   }
-  static AC from_bytes(const std::vector<uint8_t> &data, int device = -1) {
+  // (the container stores the keys as spelled and no options: say fold_ascii again)
+  static AC from_bytes(const std::vector<uint8_t> &data, int device = -1, bool fold_ascii = false) {
     aha_options o{};
     o.struct_size = sizeof(o);
     o.device = device;
+    o.flags = fold_ascii ? AHA_OPT_FOLD_ASCII : 0u;
     aha_ac *h = nullptr;
     int32_t rc = aha_ac_load(data.data(), data.size(), &o, &h);
     if (rc != AHA_OK) throw Error(rc, aha_strerror(rc));
     return AC(h);
   }
+  bool fold_ascii() const { return (aha_ac_flags(h_) & AHA_OPT_FOLD_ASCII) != 0; }
   aha_ac *handle() const { return h_; }
 
  private:
@@ -497,7 +502,7 @@ class Group {
   Group &operator=(const Group &) = delete;
   ~Group() { aha_group_free(g_); }
 
-  static Group compile(const std::vector<std::string> &keys, const std::vector<int32_t> &devices) {
+  static Group compile(const std::vector<std::string> &keys, const std::vector<int32_t> &devices, bool fold_ascii = false) {
     if (aha_abi_version() != AHA_ABI_VERSION) throw Error(AHA_E_INVALID, "libaha_hip.so is not the ABI this header declares");
     std::vector<uint8_t> blob;
     std::vector<uint64_t> offs(keys.size() + 1, 0);
@@ -507,8 +512,8 @@ class Group {
     }
     aha_group *g = nullptr;
     uint32_t bad = 0;
-    int32_t rc = aha_group_compile(blob.data(), offs.data(), (uint32_t)keys.size(), devices.data(), (int32_t)devices.size(), 0, &g,
-                                   &bad);
+    int32_t rc = aha_group_compile(blob.data(), offs.data(), (uint32_t)keys.size(), devices.data(), (int32_t)devices.size(),
+                                   fold_ascii ? AHA_OPT_FOLD_ASCII : 0u, &g, &bad);
     if (rc == AHA_E_DUP_KEY) throw Error(rc, "key:" + keys[bad] + " appear twice.", bad);
     if (rc != AHA_OK) throw Error(rc, aha_strerror(rc), bad);
     return Group(g);

@@ -24,6 +24,8 @@
  * (8 N bytes, bounded at 48 GiB) only when `cap` announces more than one hit per 4 input bytes or a chunk
  * overflowed its region (aha_timing.repeats then says that the call ran twice).  Plus ~24 bytes per chunk and 4 bytes per
  * document.  A device corpus that is not 16-byte aligned is first copied into scratch (N bytes).
+ * A handle compiled with AHA_OPT_FOLD_ASCII: every engine but the prefix filter reads a folded copy of the batch in scratch
+ * (N bytes, aligned or not: the same pass as that copy, not a second one); the prefix-filter engine holds nothing extra.
  * Character-level engine (aha_ac_info_t.unit_enabled; aha_timing.engine = 4): its records are 12 bytes and go straight to
  * the expansion -- 24 bytes per hit of capacity + 3N/16 with the fused expansion (output chains of at most 15 keys), + the
  * 8-byte regions above with the general post passes.
@@ -88,6 +90,26 @@ typedef struct {
 
 #define AHA_OPT_HOST_ONLY 1u /* build the automaton image but do not touch the GPU (tests of host logic) */
 #define AHA_OPT_FORCE_WIDE 2u /* always use the 8-byte slot format (default: compact 4-byte when it fits) */
+/* ASCII case-insensitive handle (a pure addition to ABI 8).  fold(b) = b + 32 for 0x41 <= b <= 0x5A ('A' .. 'Z'), b
+ * otherwise: bytes >= 0x80, '@', '[', '`' and '{' are untouched, lengths and UTF-8 lead bytes never change, so byte and char
+ * offsets are those of the original text.  THE RULE: every call on a handle compiled with the flag gives, bit for bit, what
+ * the same call gives on an ordinary handle compiled from fold(keys) and run over fold(text) -- match, match_longest in both
+ * modes, a separator filter, char offsets, counts, document counts, cover, feeds and feed counts, the pack / unpack exchange,
+ * groups, replicate and export.  Exactly three exceptions:
+ *   1. redacted[j] is `fill` where the mask bit is set and the ORIGINAL corpus[j] elsewhere, not the folded byte; redaction
+ *      in place (d_redacted == d_corpus) writes the fill bytes only.
+ *   2. aha_ac_key(id) and aha_ac_save give the keys as the caller spelled them; aha_ac_id(key) folds its argument first.
+ *   3. No device entry ever writes the caller's d_corpus, apart from the fill bytes of exception 1.
+ * What the rule means in detail: two keys equal after folding are AHA_E_DUP_KEY, *err_key = the index of the second (where
+ * the reference would raise on the folded list); a separator filter tests the FOLDED neighbour bytes (clear a letter's
+ * lower-case bit to make it a non-separator); the stale END flags of match_longest come from the Cedar replay of the folded
+ * keys; the engine choice (unit image, prefix filter, wide or compact) is the one the folded key set would get.
+ * aha_ac_load stores nothing new (container format 1): pass the flag in `opts` again, as for AHA_OPT_FORCE_WIDE.
+ * aha_ac_replicate copies the flag; aha_group_compile takes it in `flags` and every shard gets it; a feed opened on a folded
+ * handle is folded (a straddling hit matches whatever the case of the bytes on either side of the cut).  aha_ac_flags reads it.
+ * Cost: the prefix-filter engine folds inside its own text loads (no copy, no extra scratch); every other engine reads a
+ * folded copy made by one streaming pass into scratch (N bytes; aha_amd/csrc/scan_fold.hip). */
+#define AHA_OPT_FOLD_ASCII 4u
 
 /* Per-call options mirroring the reference's overloads:
  *   char_offsets = 0: match(seq : Bytes)        src/aha/ac.cr:280-286  (byte offsets)
@@ -230,6 +252,9 @@ void aha_ac_free(aha_ac *ac);
  * is one call (src/aha/ac.cr:62-69), so n devices must not cost n compiles. */
 int32_t aha_ac_replicate(const aha_ac *ac, int32_t device, aha_ac **out);
 int32_t aha_ac_info(const aha_ac *ac, aha_ac_info_t *info);
+/* The AHA_OPT_* bits the handle was compiled with (AHA_OPT_FOLD_ASCII among them); 0 for a NULL handle.  A pure addition
+ * to ABI 8. */
+uint32_t aha_ac_flags(const aha_ac *ac);
 
 /* AC#[](sid : Int) : String and AC#[](key) : Int -- delegated to the trie in
  * the reference (src/aha/ac.cr:41-43, src/aha/cedar.cr:747-749, 817-834).
