@@ -162,6 +162,10 @@ SIGNATURES = {
     "aha_feed_match_batch_device": (_i32, [_vp, _vp, _vp, _vp, _u64, _u64, _vp, _u64, _vp, _vp, C.POINTER(_u64), _vp]),
     "aha_feed_count_batch": (_i32, [_vp, _vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, C.POINTER(_u64)]),
     "aha_feed_count_batch_device": (_i32, [_vp, _vp, _vp, _vp, _u64, _u64, _u32, _vp, _vp, _vp, C.POINTER(_u64), _vp]),
+    "aha_feed_cover_batch": (_i32, [_vp, _vp, _vp, _vp, _u64, _u32, _vp, _vp, C.c_uint8, _vp, _vp, _vp, _vp, C.POINTER(_u64),
+                                  C.POINTER(_u64)]),
+    "aha_feed_cover_batch_device": (_i32, [_vp, _vp, _vp, _vp, _u64, _u64, _u32, _vp, _vp, C.c_uint8, _vp, _vp, _vp, _vp,
+                                         C.POINTER(_u64), C.POINTER(_u64), _vp]),
 }
 
 _lib = None

@@ -72,6 +72,17 @@ def _pack_keys(keys):
     return blob, offs
 
 
+def _fill_byte(fill):
+    """a fill given as an int, one byte or a one-byte str -> 0 .. 255"""
+    if isinstance(fill, str):
+        fill = fill.encode("utf-8")
+    if isinstance(fill, (bytes, bytearray)):
+        if len(fill) != 1:
+            raise ValueError("fill must be one byte")
+        return fill[0]
+    return int(fill) & 0xFF
+
+
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
 
@@ -762,7 +773,8 @@ class AC:
 class Feed:
     """Sequences that arrive in pieces across calls (aha_feed_*).  Each call matches a batch of pieces -- piece d is the next
     part of sequence seq_ids[d] -- and yields exactly the hits one plain match over the whole sequence so far would report with
-    an end inside the piece; a count call (count_batch, count) gives the same hits per key.  Offsets are relative to the piece (start may be negative: the hit began in an earlier piece);
+    an end inside the piece; a count call (count_batch, count) gives the same hits per key, a cover call (cover_batch,
+    redact_batch, cover, redact, redactor) the bytes they cover.  Offsets are relative to the piece (start may be negative: the hit began in an earlier piece);
     piece_bases[d] is the sequence's length before it, so base + offset is absolute."""
 
     def __init__(self, ac, handle, n_seqs, chars):
@@ -913,6 +925,100 @@ class Feed:
                                     np.array([seq], dtype=np.uint32))
         return kc
 
+    # -- feed cover: the mask and the redacted copy of pieces, straddling hits included (aha_feed_cover_batch*) ---------
+    def _cover_host(self, corpus, piece_offsets, seq_ids, want_mask, want_redacted, fill):
+        if isinstance(corpus, (bytes, bytearray)):
+            corpus = np.frombuffer(bytes(corpus), dtype=np.uint8)
+        corpus = np.ascontiguousarray(corpus, dtype=np.uint8)
+        piece_offsets = np.ascontiguousarray(piece_offsets, dtype=np.uint64)
+        seq_ids = np.ascontiguousarray(seq_ids, dtype=np.uint32)
+        D = piece_offsets.size - 1
+        if seq_ids.size != D:
+            raise ValueError("one sequence id per piece")
+        n_bytes = int(piece_offsets[-1])
+        mask = np.zeros((n_bytes + 31) // 32, dtype=np.uint32) if want_mask else None
+        red = np.zeros(n_bytes, dtype=np.uint8) if want_redacted else None
+        back = np.zeros(max(D, 1), dtype=np.uint32)
+        cov = np.zeros(max(D, 1), dtype=np.uint64)
+        pho = np.zeros(D + 1, dtype=np.uint64)
+        bases = np.zeros(max(D, 1), dtype=np.uint64)
+        nc, nh = C.c_uint64(0), C.c_uint64(0)
+        rc = N.lib().aha_feed_cover_batch(self._h, _ptr(corpus), _ptr(piece_offsets), _ptr(seq_ids), D, 0, _ptr(mask), _ptr(red),
+                                          _fill_byte(fill), _ptr(back), _ptr(cov), _ptr(pho), _ptr(bases), C.byref(nc),
+                                          C.byref(nh))
+        self._check(rc)
+        return mask, red, {"piece_back": back[:D], "piece_covered": cov[:D], "piece_hit_offsets": pho, "piece_bases": bases[:D],
+                           "n_covered": int(nc.value), "n_hits": int(nh.value)}
+
+    def cover_batch(self, corpus, piece_offsets, seq_ids):
+        """Which bytes of the pieces lie inside a hit of their sequences, without the hit list (aha_feed_cover_batch):
+        -> (mask uint32[ceil(N / 32)], info) in the layout of AC.cover_batch.  info: piece_back uint32[D] (the bytes in front
+        of the piece that lie inside a hit ending in it: they belong to earlier pieces), piece_covered uint64[D],
+        piece_hit_offsets uint64[D + 1], piece_bases uint64[D], n_covered, n_hits.  The sequences move on as a match call
+        would move them."""
+        mask, _, info = self._cover_host(corpus, piece_offsets, seq_ids, True, False, 0)
+        return mask, info
+
+    def redact_batch(self, corpus, piece_offsets, seq_ids, fill=0x2A):
+        """The pieces with every byte inside a hit replaced by `fill`: -> (redacted uint8[N], info as for cover_batch).  The
+        last info["piece_back"][d] bytes of the sequence in front of piece d are covered as well."""
+        _, red, info = self._cover_host(corpus, piece_offsets, seq_ids, False, True, fill)
+        return red, info
+
+    def cover_batch_device(self, corpus, piece_offsets, seq_ids, mask=None, redacted=None, fill=0x2A, piece_back=None,
+                           piece_covered=None, piece_hit_offsets=None, piece_bases=None, stream=None):
+        """Device-resident feed cover on torch CUDA tensors: uint8 corpus, int64/uint64 piece offsets, int32/uint32 sequence
+        ids; mask int32/uint32 [ceil(N / 32)] or None; redacted uint8 [N] or None (the corpus tensor itself: in place);
+        piece_back int32/uint32 [D], piece_covered and piece_bases int64/uint64 [D], piece_hit_offsets [D + 1], each or None.
+        -> (n_covered, n_hits)."""
+        import torch
+
+        assert corpus.is_cuda and corpus.dtype == torch.uint8 and corpus.is_contiguous()
+        assert piece_offsets.is_cuda and piece_offsets.dtype in (torch.int64, torch.uint64) and piece_offsets.is_contiguous()
+        assert seq_ids.is_cuda and seq_ids.dtype in (torch.int32, torch.uint32) and seq_ids.is_contiguous()
+        n_bytes, D = corpus.numel(), piece_offsets.numel() - 1
+        assert seq_ids.numel() >= D
+        if mask is not None and not (mask.is_cuda and mask.dtype in (torch.int32, torch.uint32) and mask.is_contiguous()
+                                     and mask.numel() >= (n_bytes + 31) // 32):
+            raise ValueError("mask must be a contiguous int32/uint32 CUDA tensor of at least ceil(N / 32) entries")
+        if redacted is not None and not (redacted.is_cuda and redacted.dtype == torch.uint8 and redacted.is_contiguous()
+                                         and redacted.numel() >= n_bytes):
+            raise ValueError("redacted must be a contiguous uint8 CUDA tensor of at least N entries")
+        if piece_back is not None and not (piece_back.is_cuda and piece_back.dtype in (torch.int32, torch.uint32)
+                                           and piece_back.is_contiguous() and piece_back.numel() >= D):
+            raise ValueError("piece_back must be a contiguous int32/uint32 CUDA tensor of at least D entries")
+        for t, n in ((piece_covered, D), (piece_hit_offsets, D + 1), (piece_bases, D)):
+            assert t is None or (t.is_cuda and t.dtype in (torch.int64, torch.uint64) and t.is_contiguous() and t.numel() >= n)
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        nc, nh = C.c_uint64(0), C.c_uint64(0)
+        s = stream if stream is not None else torch.cuda.current_stream(corpus.device).cuda_stream
+        rc = N.lib().aha_feed_cover_batch_device(
+            self._h, corpus.data_ptr(), piece_offsets.data_ptr(), seq_ids.data_ptr(), D, n_bytes, 0, ptr(mask), ptr(redacted),
+            _fill_byte(fill), ptr(piece_back), ptr(piece_covered), ptr(piece_hit_offsets), ptr(piece_bases), C.byref(nc),
+            C.byref(nh), C.c_void_p(s))
+        self._check(rc)
+        return int(nc.value), int(nh.value)
+
+    def cover(self, seq, piece):
+        """The next piece of one sequence: -> (np.bool_[len(piece)], back).  True where the byte lies inside a hit of the
+        sequence; the `back` bytes in front of the piece lie inside a hit that ends in it."""
+        b = _b(piece)
+        mask, info = self.cover_batch(np.frombuffer(b, dtype=np.uint8), np.array([0, len(b)], dtype=np.uint64),
+                                      np.array([seq], dtype=np.uint32))
+        return np.unpackbits(mask.view(np.uint8), bitorder="little")[: len(b)].astype(np.bool_), int(info["piece_back"][0])
+
+    def redact(self, seq, piece, fill="*"):
+        """The next piece of one sequence with what the keys cover blanked out: -> (bytes, back).  The last `back` bytes
+        handed out before for this sequence are covered too (Feed.redactor keeps them back until they are final)."""
+        b = _b(piece)
+        red, info = self.redact_batch(np.frombuffer(b, dtype=np.uint8), np.array([0, len(b)], dtype=np.uint64),
+                                      np.array([seq], dtype=np.uint32), fill=fill)
+        return red.tobytes(), int(info["piece_back"][0])
+
+    def redactor(self, fill="*"):
+        """A Redactor over this feed: push(seq, piece) / finish(seq) give the redacted stream of every sequence."""
+        return Redactor(self, fill)
+
     def match(self, seq, piece):
         """The next piece of one sequence: its hits as Hits with absolute offsets."""
         b = _b(piece)
@@ -920,6 +1026,34 @@ class Feed:
                                           np.array([seq], dtype=np.uint32))
         base = int(bases[0])
         return [Hit(int(h["start"]) + base, int(h["end"]) + base, int(h["value"])) for h in hits]
+
+
+class Redactor:
+    """Redaction of sequences that arrive in pieces (Feed.redactor).  A hit that straddles a cut covers up to W = Lmax - 1
+    bytes of what came before, so the last min(W, length) redacted bytes of every sequence are held on the host:
+    push(seq, piece) returns only bytes that can no longer change, finish(seq) the rest, and
+    b"".join(pushes) + finish(seq) == matcher.redact(whole sequence)."""
+
+    def __init__(self, feed, fill="*"):
+        self._feed, self._fill = feed, _fill_byte(fill)
+        self._W = max(int(feed._ac.info["max_key_len"]) - 1, 0)
+        self._held = {}
+
+    def push(self, seq, piece):
+        red, back = self._feed.redact(seq, piece, fill=self._fill)
+        held = bytearray(self._held.get(seq, b""))
+        if back:
+            held[len(held) - back:] = bytes([self._fill]) * back
+        held += red
+        keep = min(self._W, len(held))
+        self._held[seq] = bytes(held[len(held) - keep:])
+        return bytes(held[: len(held) - keep])
+
+    def finish(self, seq):
+        """The bytes still held for seq; the sequence starts again from length 0."""
+        out = self._held.pop(seq, b"")
+        self._feed.reset(seq)
+        return out
 
 
 # Aha::ACBig = ACX(Int64) (src/aha/ac.cr:9): node ids of 64 bits, the same Hit with an Int32 value (ac.cr:273) -- the

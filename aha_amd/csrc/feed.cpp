@@ -12,6 +12,13 @@
 //   device_count           the caller's pieces, from the root, into the feed's K-word vector   -> m_d (a plain count's engine)
 //   kfd_count_windows      + the window hits: +1 for the X block, -1 for the ctx and P' blocks
 //   kfd_scan + kfd_count_finish + kfd_commit   piece_hit_offsets, then the caller's key counts, then the feed's state
+// A cover call (aha_feed_cover_batch*) widens the head windows to 2 W bytes of the piece (X2, P'2; scan_feed.hip), then
+//   device_match, quiet    the window batch, byte offsets on char feeds too: its hit list is at most 3 W bytes of text per piece
+//   device_count + mask    the caller's pieces, from the root: their hits per piece and one span per event into a mask in the
+//                          feed's scratch (a plain cover's engine; nothing is held per hit of this pass)
+//   kfd_cover_clear + kfd_cover_windows + kfd_scan   the mask corrected at the cuts, piece_back, piece_hit_offsets
+//   kfd_commit             the new contexts -- from the caller's text, so before an in-place redaction
+//   kv_total, kv_doc_covered, the mask's copy, kv_redact (scan_cover.hip)   each only where asked for; the redaction last
 // Calls on one feed are serialised by its mutex; its scratch is its own.  The two matches lease one of the handle's scratch
 // sets like any call, so different feeds and plain calls on the same handle run side by side.
 #include "feed.hpp"
@@ -31,14 +38,15 @@ struct aha_feed {
   uint32_t stamp = 0;
   // grow-only scratch: 0 verdict + window size, 1 window bytes, 2 window offsets, 3 window hit offsets, 4 window hits,
   // 5 main hit offsets, 6 main hits, 7 piece hit offsets, 8 leads(ctx), 9 leads(P); 10 .. 15 the host entry's staging
-  // (corpus, offsets, ids, hits, piece hit offsets, bases), 16 key counts (a count call's sums), 17 the host entry's key counts
-  Buf buf[18];
+  // (corpus, offsets, ids, hits, piece hit offsets, bases), 16 key counts (a count call's sums), 17 the host entry's key counts,
+  // 18 a cover call's mask, 19 / 20 the host entry's piece_back and piece_covered
+  Buf buf[21];
   uint64_t *h_pin = nullptr;  // pinned: read-backs
   hipStream_t hs = nullptr;   // the host entry's stream (and position / reset)
 };
 
 namespace {
-enum { kMisc, kWin, kWoff, kWdho, kWhits, kMdho, kMhits, kPho, kLeadCtx, kLeadP, kHCorpus, kHOff, kHIds, kHOut, kHPho, kHBases, kKc, kHKc };
+enum { kMisc, kWin, kWoff, kWdho, kWhits, kMdho, kMhits, kPho, kLeadCtx, kLeadP, kHCorpus, kHOff, kHIds, kHOut, kHPho, kHBases, kKc, kHKc, kMask, kHBack, kHCov };
 
 void *reserve(aha_feed *f, int i, size_t bytes) {
   Buf &b = f->buf[i];
@@ -63,9 +71,10 @@ int32_t no_memory(const char *what) {
 
 // the first half of every call: checks, the window batch and its match.  hits: the window batch's hit list is needed (a match,
 // or a count with key counts); otherwise only its per-document offsets (a count without: device_count of the windows).
+// wide: a cover call -- the head windows take 2 W bytes of the piece, and the window hits are in bytes on a char feed too.
 // -> *n_w, and the hits of the three blocks nx (X), ny (ctx), nz (P').
 int32_t feed_windows(aha_feed *f, Scratch *sc, FeedArgs &F, hipStream_t s, bool hits, uint64_t *n_w, uint64_t *nx,
-                     uint64_t *ny, uint64_t *nz) {
+                     uint64_t *ny, uint64_t *nz, bool wide = false) {
   aha_ac *ac = f->ac;
   const uint64_t D = F.D;
   if (++f->stamp == 0) f->stamp = 1;  // (a stamp comes back after 2^32 calls; a sequence must be named in neither)
@@ -74,9 +83,10 @@ int32_t feed_windows(aha_feed *f, Scratch *sc, FeedArgs &F, hipStream_t s, bool 
   F.ctx = f->d_ctx;
   F.n_seqs = f->n_seqs;
   F.W = f->W;
+  F.Wp = wide ? 2 * f->W : f->W;
   F.chars = f->chars ? 1 : 0;
   F.max_piece = (1ull << 31) - std::max<uint64_t>(ac->aut.max_key_len, 1);
-  uint64_t *misc = (uint64_t *)reserve(f, kMisc, 16);
+  uint64_t *misc = (uint64_t *)reserve(f, kMisc, 24);  // (the third word: a cover call's total)
   F.woff = (uint64_t *)reserve(f, kWoff, (3 * D + 1) * 8);
   F.lead_ctx = (uint64_t *)reserve(f, kLeadCtx, D * 8);
   F.lead_p = (unsigned long long *)reserve(f, kLeadP, D * 8);
@@ -110,11 +120,11 @@ int32_t feed_windows(aha_feed *f, Scratch *sc, FeedArgs &F, hipStream_t s, bool 
 
   aha_match_params p{};
   p.struct_size = sizeof(p);
-  p.char_offsets = F.chars;
+  p.char_offsets = wide ? 0 : F.chars;
   bool packed = false;
   *n_w = 0;
   if (hits) {
-    // the window batch: at most 4 W bytes per piece; its hit scratch grows to what it needed once
+    // the window batch: at most 4 W bytes per piece (6 W: a cover call); its hit scratch grows to what it needed once
     for (int attempt = 0;; attempt++) {
       const uint64_t cap_w = f->buf[kWhits].bytes / sizeof(aha_hit);
       int32_t rc = device_match(ac, sc, F.win, F.woff, 3 * D, n_win, &p, cap_w ? (aha_hit *)f->buf[kWhits].p : nullptr, cap_w,
@@ -197,6 +207,51 @@ int32_t feed_count(aha_feed *f, Scratch *sc, FeedArgs &F, hipStream_t s, uint64_
   feed_launch_commit(F, s);
   HIPCHK(ac, hipGetLastError());
   HIPCHK(ac, hipStreamSynchronize(s));
+  return AHA_OK;
+}
+
+// a whole cover call on device-resident pieces.  Everything up to the main pass writes feed scratch only; what the caller owns
+// -- piece_back, piece_hit_offsets, bases, piece_covered, the mask, and last the redacted bytes (d_redacted may be the corpus:
+// the new contexts are taken from it first) -- is written once nothing can be refused any more.
+int32_t feed_cover(aha_feed *f, Scratch *sc, FeedArgs &F, hipStream_t s, uint32_t *d_mask, uint8_t *d_redacted, uint8_t fill,
+                   uint64_t *d_piece_covered, uint64_t *total, uint64_t *n_covered) {
+  aha_ac *ac = f->ac;
+  uint64_t n_w = 0, nx = 0, ny = 0, nz = 0;
+  int32_t rc = feed_windows(f, sc, F, s, true, &n_w, &nx, &ny, &nz, true);
+  if (rc) return rc;
+  F.n_whits = nx;
+  const uint64_t n_words = (F.n_bytes + 31) / 32;
+  F.mask = (uint32_t *)reserve(f, kMask, n_words * 4 + 16);
+  if (!F.mask) return no_memory("mask");
+  if (!F.pho && !(F.pho = (uint64_t *)reserve(f, kPho, (F.D + 1) * 8))) return no_memory("piece hit offsets");
+  // the main pass: the engine and cover path a plain cover of the pieces takes; it clears the mask's words itself
+  aha_match_params p{};
+  p.struct_size = sizeof(p);
+  uint64_t n_m = 0;
+  rc = device_count(ac, sc, F.text, F.off, F.D, F.n_bytes, &p, 0, nullptr, (uint64_t *)F.mdho, &n_m, s, true, F.mask);
+  if (rc) return rc;
+  *total = (nx - ny) + (n_m - nz);
+  F.total = *total;
+  if (F.back && F.D) HIPCHK(ac, hipMemsetAsync(F.back, 0, F.D * 4, s));
+  feed_launch_cover(F, s);
+  feed_launch_commit(F, s);
+  HIPCHK(ac, hipGetLastError());
+  uint64_t *d_total = (uint64_t *)f->buf[kMisc].p + 2;
+  f->h_pin[0] = 0;
+  if (F.n_bytes) {
+    const uint32_t blocks = 8u * std::max<uint32_t>(ac->v2_grid, 64u);
+    HIPCHK(ac, hipMemsetAsync(d_total, 0, 8, s));
+    cover_launch_total(F.mask, n_words, d_total, blocks, s);
+    if (d_piece_covered && F.D) cover_launch_doc_covered(F.mask, F.off, F.D, d_piece_covered, blocks, s);
+    if (d_mask) HIPCHK(ac, hipMemcpyAsync(d_mask, F.mask, n_words * 4, hipMemcpyDeviceToDevice, s));
+    if (d_redacted) cover_launch_redact(F.text, d_redacted, F.mask, F.n_bytes, fill, blocks, s);
+    HIPCHK(ac, hipGetLastError());
+    HIPCHK(ac, hipMemcpyAsync(f->h_pin, d_total, 8, hipMemcpyDeviceToHost, s));
+  } else if (d_piece_covered && F.D) {
+    HIPCHK(ac, hipMemsetAsync(d_piece_covered, 0, F.D * 8, s));
+  }
+  HIPCHK(ac, hipStreamSynchronize(s));
+  *n_covered = f->h_pin[0];
   return AHA_OK;
 }
 
@@ -465,5 +520,89 @@ int32_t aha_feed_count_batch(aha_feed *f, const uint8_t *corpus, const uint64_t 
   if (piece_bases && D) HIPCHK(ac, hipMemcpyAsync(piece_bases, d_bases, D * 8, hipMemcpyDeviceToHost, s));
   HIPCHK(ac, hipStreamSynchronize(s));
   *n_hits = total;
+  return AHA_OK;
+}
+
+int32_t aha_feed_cover_batch_device(aha_feed *f, const uint8_t *d_corpus, const uint64_t *d_piece_offsets,
+                                    const uint32_t *d_seq_ids, uint64_t n_pieces, uint64_t n_bytes, uint32_t flags,
+                                    uint32_t *d_mask, uint8_t *d_redacted, uint8_t fill, uint32_t *d_piece_back,
+                                    uint64_t *d_piece_covered, uint64_t *d_piece_hit_offsets, uint64_t *d_piece_bases,
+                                    uint64_t *n_covered, uint64_t *n_hits, void *stream) {
+  if (!f || !n_covered || !d_piece_offsets || (n_pieces && !d_seq_ids) || (n_bytes && !d_corpus) || flags) return AHA_E_INVALID;
+  if (bad_feed(f)) return AHA_E_NO_DEVICE;
+  std::lock_guard<std::mutex> lk(f->mu);
+  DeviceGuard g(f->ac->device);
+  Lease lease(f->ac);
+  FeedArgs F{};
+  F.text = d_corpus;
+  F.off = d_piece_offsets;
+  F.ids = d_seq_ids;
+  F.D = n_pieces;
+  F.n_bytes = n_bytes;
+  F.pho = d_piece_hit_offsets;
+  F.bases = d_piece_bases;
+  F.back = d_piece_back;
+  uint64_t total = 0, covered = 0;
+  *n_covered = 0;
+  if (n_hits) *n_hits = 0;
+  int32_t rc = feed_cover(f, lease.get(), F, (hipStream_t)stream, d_mask, d_redacted, fill, d_piece_covered, &total, &covered);
+  if (rc) return rc;
+  *n_covered = covered;
+  if (n_hits) *n_hits = total;
+  return AHA_OK;
+}
+
+// The host entry: the pieces go up into the feed's staging buffers and are redacted in place there; what was asked for comes
+// back once the call has succeeded.
+int32_t aha_feed_cover_batch(aha_feed *f, const uint8_t *corpus, const uint64_t *piece_offsets, const uint32_t *seq_ids,
+                             uint64_t n_pieces, uint32_t flags, uint32_t *mask, uint8_t *redacted, uint8_t fill,
+                             uint32_t *piece_back, uint64_t *piece_covered, uint64_t *piece_hit_offsets, uint64_t *piece_bases,
+                             uint64_t *n_covered, uint64_t *n_hits) {
+  if (!f || !n_covered || !piece_offsets || (n_pieces && !seq_ids) || flags) return AHA_E_INVALID;
+  if (bad_feed(f)) return AHA_E_NO_DEVICE;
+  aha_ac *ac = f->ac;
+  int32_t rc = check_pieces_host(f, piece_offsets, seq_ids, n_pieces);
+  if (rc) return rc;
+  const uint64_t n_bytes = piece_offsets[n_pieces], n_words = (n_bytes + 31) / 32;
+  if (n_bytes && !corpus) return AHA_E_INVALID;
+  std::lock_guard<std::mutex> lk(f->mu);
+  DeviceGuard g(ac->device);
+  Lease lease(ac);
+  hipStream_t s = f->hs;
+  const uint64_t D = n_pieces;
+  uint8_t *d_corpus = (uint8_t *)reserve(f, kHCorpus, n_bytes + 64);
+  uint64_t *d_off = (uint64_t *)reserve(f, kHOff, (D + 1) * 8);
+  uint32_t *d_ids = (uint32_t *)reserve(f, kHIds, D * 4);
+  uint64_t *d_pho = (uint64_t *)reserve(f, kHPho, (D + 1) * 8);
+  uint64_t *d_bases = (uint64_t *)reserve(f, kHBases, D * 8);
+  uint32_t *d_back = piece_back ? (uint32_t *)reserve(f, kHBack, D * 4) : nullptr;
+  uint64_t *d_cov = piece_covered ? (uint64_t *)reserve(f, kHCov, D * 8) : nullptr;
+  if (!d_corpus || !d_off || !d_ids || !d_pho || !d_bases || (piece_back && !d_back) || (piece_covered && !d_cov))
+    return no_memory("staging buffers");
+  if (n_bytes) HIPCHK(ac, hipMemcpyAsync(d_corpus, corpus, n_bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(ac, hipMemcpyAsync(d_off, piece_offsets, (D + 1) * 8, hipMemcpyHostToDevice, s));
+  if (D) HIPCHK(ac, hipMemcpyAsync(d_ids, seq_ids, D * 4, hipMemcpyHostToDevice, s));
+  FeedArgs F{};
+  F.text = d_corpus;
+  F.off = d_off;
+  F.ids = d_ids;
+  F.D = D;
+  F.n_bytes = n_bytes;
+  F.pho = d_pho;
+  F.bases = d_bases;
+  F.back = d_back;
+  uint64_t total = 0, covered = 0;
+  *n_covered = 0;
+  if (n_hits) *n_hits = 0;
+  if ((rc = feed_cover(f, lease.get(), F, s, nullptr, redacted ? d_corpus : nullptr, fill, d_cov, &total, &covered))) return rc;
+  if (mask && n_words) HIPCHK(ac, hipMemcpyAsync(mask, F.mask, n_words * 4, hipMemcpyDeviceToHost, s));
+  if (redacted && n_bytes) HIPCHK(ac, hipMemcpyAsync(redacted, d_corpus, n_bytes, hipMemcpyDeviceToHost, s));
+  if (piece_back && D) HIPCHK(ac, hipMemcpyAsync(piece_back, d_back, D * 4, hipMemcpyDeviceToHost, s));
+  if (piece_covered && D) HIPCHK(ac, hipMemcpyAsync(piece_covered, d_cov, D * 8, hipMemcpyDeviceToHost, s));
+  if (piece_hit_offsets) HIPCHK(ac, hipMemcpyAsync(piece_hit_offsets, d_pho, (D + 1) * 8, hipMemcpyDeviceToHost, s));
+  if (piece_bases && D) HIPCHK(ac, hipMemcpyAsync(piece_bases, d_bases, D * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  *n_covered = covered;
+  if (n_hits) *n_hits = total;
   return AHA_OK;
 }

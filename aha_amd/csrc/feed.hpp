@@ -18,6 +18,7 @@ struct FeedArgs {
   const uint32_t *ids;         // [D] sequence ids
   uint64_t D, n_bytes, n_seqs;
   uint32_t W;                  // max(Lmax - 1, 0)
+  uint32_t Wp;                 // bytes of the piece in the head windows X and P': W, or 2 W for a cover call
   uint32_t stamp;              // this call's stamp (never 0)
   uint64_t max_piece;          // a piece must be shorter than this
   int32_t chars;
@@ -43,6 +44,9 @@ struct FeedArgs {
   uint32_t accumulate;         // kfd_count_finish adds into key_counts instead of copying
   unsigned long long *kc;      // [K] the feed's per-key sums: the main pass's, then the window hits added
   uint64_t *key_counts;        // [K] the caller's, or null
+  // cover calls (aha_feed_cover_batch*): the head windows are X2 = ctx || P[0 .. min(2 W, |P|)) and P'2 = P[0 .. min(2 W, |P|))
+  uint32_t *mask;              // bit j = byte j of the batch: the main pass's cover of the pieces, then corrected at the cuts
+  uint32_t *back;              // [D] bytes in front of the piece inside a hit that ends in it, or null (cleared by the host)
 };
 
 void feed_launch_check(const FeedArgs &F, void *stream);    // kfd_check, then kfd_scan of the window lengths
@@ -51,4 +55,7 @@ void feed_launch_merge(const FeedArgs &F, void *stream);    // kfd_scan of the h
 void feed_launch_commit(const FeedArgs &F, void *stream);   // kfd_commit: bases, counters, the new contexts
 // count calls: kfd_count_windows (F.kc), kfd_scan of the hits per piece, kfd_count_finish (F.key_counts)
 void feed_launch_count(const FeedArgs &F, void *stream);
+// cover calls: kfd_cover_clear (the first min(W, |P|) bits of every piece), kfd_cover_windows (the spans of the X2 hits that
+// end in the piece, F.back), kfd_scan of the hits per piece
+void feed_launch_cover(const FeedArgs &F, void *stream);
 }  // namespace aha

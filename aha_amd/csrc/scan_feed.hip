@@ -21,9 +21,20 @@
 //                      workgroup in the LDS table of count_table.hpp first
 //   kfd_scan           the hits per piece into piece_hit_offsets, as for a match
 //   kfd_count_finish   the caller's key_counts = kc (or += kc): the first write the caller sees, after everything succeeded
+// A cover call (aha_feed_cover_batch*) wants the bytes inside the piece's hits, not the hits.  The main pass covers the pieces
+// alone (device_count with a mask); every event of it that ends beyond P[0 .. W') is exact (W' = min(W, |P|)), the others set
+// bits only inside [0, W').  A hit that touches P[0 .. W') starts before W', so it ends at or before W' + W <= 2 W: the head
+// window is widened to X2 = ctx || P[0 .. min(2 W, |P|)), whose hits with end > |ctx| are exact hits of the sequence and hold
+// every hit that touches P[0 .. W') or reaches back into the context.  So
+//   mask(P) = (cover(P alone) with bits [0, W') cleared) OR the spans of { h in hits(X2): end > |ctx| }, clipped to the piece
+//   back(P) = max(0, |ctx| - the least start among them)
+// and, with P' widened to P[0 .. min(2 W, |P|)) as well, the hits per piece are x - y + m - z as for a count.
+//   kfd_cover_clear    bits [0, W') of every piece: pieces are not word-aligned and two may share a mask word
+//   kfd_cover_windows  the clipped spans with atomicOr; back with a wave reduction and one atomicMax per piece and wave
 #include <hip/hip_runtime.h>
 
 #include "count_table.hpp"
+#include "cover_span.hpp"
 #include "feed.hpp"
 
 namespace aha {
@@ -62,7 +73,7 @@ __global__ void kfd_check(FeedArgs F) {
 __device__ __forceinline__ uint64_t win_len(const FeedArgs &F, uint64_t i) {
   const uint64_t part = i / F.D, d = i - part * F.D;
   const uint64_t lc = min((uint64_t)F.W, F.seqs[F.ids[d]].bytes);
-  const uint64_t lp = min((uint64_t)F.W, F.off[d + 1] - F.off[d]);
+  const uint64_t lp = min((uint64_t)F.Wp, F.off[d + 1] - F.off[d]);
   return part == 0 ? lc + lp : (part == 1 ? lc : lp);
 }
 __device__ __forceinline__ uint64_t kept_hits(const FeedArgs &F, uint64_t d) {
@@ -110,7 +121,7 @@ __global__ void __launch_bounds__(kFdThreads) kfd_windows(FeedArgs F) {
     const uint32_t id = F.ids[d];
     const FeedSeq sq = F.seqs[id];
     const uint32_t lc = (uint32_t)min((uint64_t)F.W, sq.bytes);
-    const uint32_t lp = (uint32_t)min((uint64_t)F.W, F.off[d + 1] - F.off[d]);
+    const uint32_t lp = (uint32_t)min((uint64_t)F.Wp, F.off[d + 1] - F.off[d]);
     const uint8_t *c = F.ctx + ((uint64_t)sq.bank * F.n_seqs + id) * F.W;
     const uint8_t *p = F.text + F.off[d];
     uint8_t *x = F.win + F.woff[d], *cw = F.win + F.woff[D + d], *pw = F.win + F.woff[2 * D + d];
@@ -272,6 +283,72 @@ __global__ void __launch_bounds__(kFdThreads) kfd_count_finish(FeedArgs F) {
   }
 }
 
+// mask bits [off[d], off[d] + min(W, |P_d|)) = 0, a wave per piece.  The first and the last word lose only the piece's own bits
+// (a neighbour's bits may stand in them); the words between are the piece's alone.
+__global__ void __launch_bounds__(kFdThreads) kfd_cover_clear(FeedArgs F) {
+  const int lane = threadIdx.x & 63;
+  const uint64_t wave = ((uint64_t)blockIdx.x * kFdThreads + threadIdx.x) >> 6, n_waves = (uint64_t)gridDim.x * (kFdThreads / 64);
+  for (uint64_t d = wave; d < F.D; d += n_waves) {
+    const uint64_t a = F.off[d], b = a + min((uint64_t)F.W, F.off[d + 1] - a);
+    if (a >= b) continue;
+    const uint64_t w0 = a >> 5, w1 = (b - 1) >> 5;
+    const uint32_t m0 = ~0u << (uint32_t)(a & 31), m1 = ~0u >> (31u - (uint32_t)((b - 1) & 31));
+    for (uint64_t w = w0 + lane; w <= w1; w += 64) {
+      uint32_t bits = ~0u;
+      if (w == w0) bits &= m0;
+      if (w == w1) bits &= m1;
+      if (bits == ~0u)
+        F.mask[w] = 0u;
+      else
+        atomicAnd(F.mask + w, ~bits);
+    }
+  }
+}
+
+// the hits of the X2 block that end in the piece: their spans, clipped to the piece, into the mask; back[d] = the most bytes
+// one of them reaches into the context.  A lane takes a hit per trip; the hits of a wave belong to few pieces (they are in
+// document order), so back costs one reduction and one atomicMax per piece and wave.
+__global__ void __launch_bounds__(kFdThreads) kfd_cover_windows(FeedArgs F) {
+  const uint64_t D = F.D, n = F.wdho[D];
+  const int lane = threadIdx.x & 63;
+  for (uint64_t i0 = blockIdx.x * (uint64_t)kFdThreads + (threadIdx.x & ~63u); i0 < n; i0 += (uint64_t)gridDim.x * kFdThreads) {
+    const uint64_t i = i0 + lane;
+    uint64_t d = 0;
+    uint32_t bk = 0;
+    if (i < n) {
+      uint64_t lo = 0, hi = D - 1;  // the window whose hits hold i: the last one whose first hit is at or before i
+      while (lo < hi) {
+        const uint64_t mid = (lo + hi + 1) / 2;
+        if (F.wdho[mid] <= i)
+          lo = mid;
+        else
+          hi = mid - 1;
+      }
+      d = lo;
+      const int64_t lc = (int64_t)(F.woff[D + d + 1] - F.woff[D + d]);
+      const int64_t st = F.whits[3 * i], en = F.whits[3 * i + 1];
+      if (en > lc) {
+        const uint64_t a = F.off[d], L = F.off[d + 1] - a;
+        const uint64_t s = st > lc ? (uint64_t)(st - lc) : 0ull, e = min((uint64_t)(en - lc), L);
+        cover_or_global(F.mask, a + s, a + e);
+        if (st < lc) bk = (uint32_t)(lc - st);
+      }
+    }
+    if (!F.back) continue;
+    unsigned long long todo = __ballot(bk != 0);
+    while (todo) {
+      const int lead = __ffsll(todo) - 1;
+      const uint64_t dl = (uint64_t)__shfl((uint32_t)d, lead, 64) | (uint64_t)__shfl((uint32_t)(d >> 32), lead, 64) << 32;
+      const bool mine = bk != 0 && d == dl;
+      uint32_t v = mine ? bk : 0u;
+#pragma unroll
+      for (int k = 32; k >= 1; k >>= 1) v = max(v, (uint32_t)__shfl_xor(v, k, 64));
+      if (lane == lead) atomicMax(&F.back[dl], v);
+      todo &= ~__ballot(mine);
+    }
+  }
+}
+
 uint32_t grid_for(uint64_t units, uint64_t per_block, uint32_t cap) {
   return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((units + per_block - 1) / per_block, cap));
 }
@@ -306,6 +383,14 @@ void feed_launch_count(const FeedArgs &F, void *stream) {
   hipLaunchKernelGGL(kfd_scan<1>, dim3(1), dim3(kFdScanThreads), 0, s, F);
   if (F.key_counts && F.K)
     hipLaunchKernelGGL(kfd_count_finish, dim3(grid_for(F.K, kFdThreads, 1024)), dim3(kFdThreads), 0, s, F);
+}
+
+void feed_launch_cover(const FeedArgs &F, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (F.W && F.n_bytes) hipLaunchKernelGGL(kfd_cover_clear, dim3(grid_for(F.D * 64, kFdThreads, 4096)), dim3(kFdThreads), 0, s, F);
+  if (F.n_whits)
+    hipLaunchKernelGGL(kfd_cover_windows, dim3(grid_for(F.n_whits, 4 * kFdThreads, 1024)), dim3(kFdThreads), 0, s, F);
+  hipLaunchKernelGGL(kfd_scan<1>, dim3(1), dim3(kFdScanThreads), 0, s, F);
 }
 
 void feed_launch_commit(const FeedArgs &F, void *stream) {

@@ -224,6 +224,16 @@ lib LibAhaHip
                                   n_pieces : UInt64, n_bytes : UInt64, flags : UInt32, d_key_counts : UInt64*,
                                   d_piece_hit_offsets : UInt64*, d_piece_bases : UInt64*, n_hits : UInt64*,
                                   stream : Void*) : Int32
+  # feed cover: the mask and the redacted copy of the same pieces, straddling hits included
+  fun aha_feed_cover_batch(f : Feed, corpus : UInt8*, piece_offsets : UInt64*, seq_ids : UInt32*, n_pieces : UInt64,
+                           flags : UInt32, mask : UInt32*, redacted : UInt8*, fill : UInt8, piece_back : UInt32*,
+                           piece_covered : UInt64*, piece_hit_offsets : UInt64*, piece_bases : UInt64*,
+                           n_covered : UInt64*, n_hits : UInt64*) : Int32
+  fun aha_feed_cover_batch_device(f : Feed, d_corpus : UInt8*, d_piece_offsets : UInt64*, d_seq_ids : UInt32*,
+                                  n_pieces : UInt64, n_bytes : UInt64, flags : UInt32, d_mask : UInt32*,
+                                  d_redacted : UInt8*, fill : UInt8, d_piece_back : UInt32*, d_piece_covered : UInt64*,
+                                  d_piece_hit_offsets : UInt64*, d_piece_bases : UInt64*, n_covered : UInt64*,
+                                  n_hits : UInt64*, stream : Void*) : Int32
   fun aha_buffer_alloc(device : Int32, bytes : UInt64, d_ptr : Void**) : Int32
   fun aha_buffer_free(device : Int32, d_ptr : Void*) : Int32
   fun aha_buffer_upload(device : Int32, d_dst : Void*, src : Void*, bytes : UInt64) : Int32
@@ -630,6 +640,47 @@ module Aha
       raise String.new(LibAhaHip.aha_last_error(@ac.handle)) if rc != 0
       accumulate.replace(kc) if accumulate
       {accumulate || kc, pho, bases}
+    end
+
+    # (the call behind cover_batch / redact_batch) -> {mask, redacted, piece_back, piece_covered}
+    private def cover_call(pieces : Array({Int32, Bytes | String}), want_mask : Bool, want_redacted : Bool,
+                           fill : UInt8) : {Array(UInt32), Bytes, Array(UInt32), Array(UInt64)}
+      corpus = IO::Memory.new
+      offs = Array(UInt64).new(pieces.size + 1)
+      offs << 0_u64
+      ids = Array(UInt32).new(pieces.size)
+      pieces.each do |(seq, piece)|
+        corpus.write(piece.is_a?(String) ? piece.to_slice : piece)
+        offs << corpus.pos.to_u64
+        ids << seq.to_u32
+      end
+      n = corpus.pos
+      mask = Array(UInt32).new(want_mask ? (n + 31) // 32 : 0, 0_u32)
+      red = Bytes.new(want_redacted ? n : 0)
+      back = Array(UInt32).new(pieces.size, 0_u32)
+      cov = Array(UInt64).new(pieces.size, 0_u64)
+      rc = LibAhaHip.aha_feed_cover_batch(@handle, corpus.to_slice.to_unsafe, offs.to_unsafe, ids.to_unsafe,
+        pieces.size.to_u64, 0_u32, want_mask ? mask.to_unsafe : Pointer(UInt32).null,
+        want_redacted ? red.to_unsafe : Pointer(UInt8).null, fill, back.to_unsafe, cov.to_unsafe,
+        Pointer(UInt64).null, Pointer(UInt64).null, out n_covered, out n_hits)
+      raise String.new(LibAhaHip.aha_last_error(@ac.handle)) if rc != 0
+      {mask, red, back, cov}
+    end
+
+    # Which bytes of the pieces lie inside a hit of their sequences, without the hit list: {mask, piece_back,
+    # piece_covered}.  Bit j of the batch is word j >> 5, bit j & 31; piece_back[d]: the bytes in front of piece d that lie
+    # inside a hit ending in it.  pieces: {seq, piece} pairs, each sequence at most once.
+    def cover_batch(pieces : Array({Int32, Bytes | String})) : {Array(UInt32), Array(UInt32), Array(UInt64)}
+      mask, _, back, cov = cover_call(pieces, true, false, 0_u8)
+      {mask, back, cov}
+    end
+
+    # The pieces with every byte inside a hit replaced by fill: {redacted, piece_back, piece_covered}.  Written one behind
+    # the other, with the last piece_back[d] bytes already written overwritten by fill, the pieces of a sequence give
+    # AC#redact of the whole.
+    def redact_batch(pieces : Array({Int32, Bytes | String}), fill : UInt8 = 0x2A_u8) : {Bytes, Array(UInt32), Array(UInt64)}
+      _, red, back, cov = cover_call(pieces, false, true, fill)
+      {red, back, cov}
     end
   end
 

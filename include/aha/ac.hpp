@@ -474,6 +474,63 @@ class Feed {
     count_batch(piece, {0, piece.size()}, {seq}, &kc);
     return kc;
   }
+  // What a cover call of pieces gives beside the mask or the redacted bytes (aha_feed_cover_batch).
+  struct Cover {
+    std::vector<uint32_t> piece_back;         // bytes in front of piece d inside a hit that ends in it (earlier pieces' bytes)
+    std::vector<uint64_t> piece_covered;      // covered bytes inside piece d
+    std::vector<uint64_t> piece_hit_offsets;  // D + 1, as match_batch gives them
+    std::vector<uint64_t> bases;              // D
+    uint64_t n_covered = 0, n_hits = 0;
+  };
+  // (the call behind cover_batch / redact_batch)
+  Cover cover_call(std::string_view corpus, const std::vector<uint64_t> &piece_offsets, const std::vector<uint32_t> &seq_ids,
+                   std::vector<uint32_t> *mask, std::string *redacted, uint8_t fill) {
+    if (piece_offsets.empty()) throw Error(AHA_E_INVALID, "piece_offsets holds D + 1 entries");
+    const uint64_t D = piece_offsets.size() - 1, n = piece_offsets.back();
+    if (seq_ids.size() != D) throw Error(AHA_E_INVALID, "one sequence id per piece");
+    if (corpus.size() < n) throw Error(AHA_E_INVALID, "the corpus is shorter than the last offset");
+    Cover c;
+    c.piece_back.assign(D, 0);
+    c.piece_covered.assign(D, 0);
+    c.piece_hit_offsets.assign(D + 1, 0);
+    c.bases.assign(D, 0);
+    std::vector<uint32_t> m(mask ? (n + 31) / 32 : 0);
+    std::string red(redacted ? n : 0, '\0');
+    check(aha_feed_cover_batch(f_, reinterpret_cast<const uint8_t *>(corpus.data()), piece_offsets.data(), seq_ids.data(), D, 0,
+                               mask && !m.empty() ? m.data() : nullptr,
+                               redacted && n ? reinterpret_cast<uint8_t *>(&red[0]) : nullptr, fill,
+                               D ? c.piece_back.data() : nullptr, D ? c.piece_covered.data() : nullptr,
+                               c.piece_hit_offsets.data(), D ? c.bases.data() : nullptr, &c.n_covered, &c.n_hits));
+    if (mask) *mask = std::move(m);
+    if (redacted) *redacted = std::move(red);
+    return c;
+  }
+  // Which bytes of the pieces lie inside a hit of their sequences, without the hit list: bit j of the batch is word j >> 5,
+  // bit j & 31 of what is returned.  The sequences move on as a match call would move them.
+  std::vector<uint32_t> cover_batch(std::string_view corpus, const std::vector<uint64_t> &piece_offsets,
+                                    const std::vector<uint32_t> &seq_ids, Cover *info = nullptr) {
+    std::vector<uint32_t> mask;
+    Cover c = cover_call(corpus, piece_offsets, seq_ids, &mask, nullptr, 0);
+    if (info) *info = std::move(c);
+    return mask;
+  }
+  // The pieces with every byte inside a hit replaced by fill.  The last info->piece_back[d] bytes of the sequence in front of
+  // piece d lie inside a hit as well: written one behind the other with those bytes overwritten, the pieces of a sequence give
+  // AC::redact of the whole.
+  std::string redact_batch(std::string_view corpus, const std::vector<uint64_t> &piece_offsets,
+                           const std::vector<uint32_t> &seq_ids, char fill = '*', Cover *info = nullptr) {
+    std::string red;
+    Cover c = cover_call(corpus, piece_offsets, seq_ids, nullptr, &red, static_cast<uint8_t>(fill));
+    if (info) *info = std::move(c);
+    return red;
+  }
+  // the next piece of one sequence redacted; *back: how many bytes handed out before are covered too
+  std::string redact(uint32_t seq, std::string_view piece, char fill = '*', uint32_t *back = nullptr) {
+    Cover c;
+    std::string red = redact_batch(piece, {0, piece.size()}, {seq}, fill, &c);
+    if (back) *back = c.piece_back[0];
+    return red;
+  }
   void reset(uint32_t seq = UINT32_MAX) { check(aha_feed_reset(f_, seq)); }
   // {bytes, chars} fed to the sequence so far
   std::pair<uint64_t, uint64_t> position(uint32_t seq) const {

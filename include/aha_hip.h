@@ -539,7 +539,7 @@ int32_t aha_ac_doc_counts_batch_device(aha_ac *ac, const uint8_t *d_corpus, cons
  * the hits (a match of a dense batch holds 16 bytes per hit of capacity).  The host entry stages the corpus, the offsets, the
  * mask and the D counts on the device as well.
  * aha_ac_last_timing: engine = the engine that traversed, n_hits, ms_write = the passes after the traversal.
- * Out of scope so far: feeds, groups, coverage of match_longest, masks indexed by character. */
+ * Feeds: aha_feed_cover_batch* below.  Out of scope so far: groups, coverage of match_longest, masks indexed by character. */
 int32_t aha_ac_cover_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc_offsets, uint64_t n_docs,
                            const aha_match_params *params, uint32_t flags /* 0 */, uint32_t *mask /* ceil(N/32) words or NULL */,
                            uint8_t *redacted /* N bytes or NULL */, uint8_t fill, uint64_t *doc_covered /* D or NULL */,
@@ -549,6 +549,46 @@ int32_t aha_ac_cover_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uin
                                   uint64_t n_bytes, const aha_match_params *params, uint32_t flags, uint32_t *d_mask,
                                   uint8_t *d_redacted, uint8_t fill, uint64_t *d_doc_covered /* D or NULL */,
                                   uint64_t *n_covered, uint64_t *n_hits /* or NULL */, void *stream);
+
+/* Feed cover: the same pieces as aha_feed_match_batch*, and the cover of what a match call of them on a BYTE feed in the same
+ * state would report (H_d: the hits of piece d, offsets relative to the piece, start possibly negative), without the hit list.
+ * mask: the layout of aha_ac_cover_batch over the batch of pieces; bit j = 1 iff byte j lies in [max(start, 0), end) of a hit
+ * of its piece's H_d; every bit >= N is 0.  redacted[j] = fill where bit j is set, else corpus[j] -- the caller's bytes on a
+ * folded handle; the device entry allows d_redacted == d_corpus.
+ * piece_back[d] = max(0, max over H_d of -start): the bytes immediately in front of the piece, in its sequence, that lie inside
+ * a hit ending in this piece.  Every straddling hit reaches up to the cut, so they are one run [-back, 0);
+ * 0 <= back <= min(Lmax - 1, bytes of the sequence before the piece); in bytes on char feeds too.
+ * piece_covered[d] = the set bits inside piece d; *n_covered = their sum (the back bytes belong to earlier pieces and are not
+ * counted).  piece_hit_offsets, piece_bases (chars on a char feed) and *n_hits: what the feed match or count of the same pieces
+ * gives.  The feed moves on exactly as a match or count call moves it: the three kinds mix freely on one feed.
+ * The stream law: cut a sequence into pieces anywhere, write each piece's redacted behind the previous one, then overwrite the
+ * last piece_back bytes already written with fill -- the result is, byte for byte, redacted of aha_ac_cover_batch over the
+ * whole sequence as one document (and so for the mask bits).
+ * n_covered == NULL, a NULL feed, any flag bit (flags is 0): AHA_E_INVALID; a sequence named twice, bad offsets, an id out of
+ * range: AHA_E_INVALID (the device entry finds these on the device); a piece of 2^31 - Lmax bytes or more: AHA_E_TOO_LONG; no
+ * capacity, so no AHA_E_CAPACITY.  A call that fails changes nothing -- neither the feed nor a caller buffer; in place, no
+ * fill byte is written before the verdict is known.  Any output array may be NULL; N = 0, D = 0 and empty pieces are valid.
+ * Two calls on feeds in the same state give identical bytes.  Like count and cover calls it reads the handle's back-off state
+ * and never writes it.  No separator filter, no match_longest, as for every feed call.
+ * Pipeline (feed.cpp, scan_feed.hip; DESIGN.md 4.10 "Feed cover"): with W = Lmax - 1 and W' = min(W, |P|), the head windows
+ * are widened to X2 = ctx || P[0 .. min(2 W, |P|)) and P'2 = P[0 .. min(2 W, |P|)) (the window batch: at most 6 W bytes per
+ * piece, matched quietly, in bytes); the pieces are covered alone as by aha_ac_cover_batch_device into a mask in feed scratch
+ * (aha_ac_last_timing reports this pass); bits [0, W') of every piece are cleared and the spans of the X2 hits that end in the
+ * piece are ORed in, clipped to the piece (vector atomics); then the totals, piece_covered, the mask's copy, the new contexts
+ * and last the redaction.  Device memory beyond a feed count's: N / 8 bytes of mask and the window batch's hit list (12 bytes
+ * per hit of at most 3 W bytes of text per piece) -- nothing per hit of the main pass. */
+int32_t aha_feed_cover_batch(aha_feed *f, const uint8_t *corpus, const uint64_t *piece_offsets, const uint32_t *seq_ids,
+                             uint64_t n_pieces, uint32_t flags /* 0 */, uint32_t *mask /* ceil(N/32) words or NULL */,
+                             uint8_t *redacted /* N bytes or NULL */, uint8_t fill, uint32_t *piece_back /* D or NULL */,
+                             uint64_t *piece_covered /* D or NULL */, uint64_t *piece_hit_offsets /* D+1 or NULL */,
+                             uint64_t *piece_bases /* D or NULL */, uint64_t *n_covered, uint64_t *n_hits /* or NULL */);
+/* Device-resident form: d_ pointers are HBM on the handle's device, validated on the device before anything is indexed with
+ * them; *n_covered, *n_hits are host memory; blocks until final. */
+int32_t aha_feed_cover_batch_device(aha_feed *f, const uint8_t *d_corpus, const uint64_t *d_piece_offsets,
+                                    const uint32_t *d_seq_ids, uint64_t n_pieces, uint64_t n_bytes, uint32_t flags,
+                                    uint32_t *d_mask, uint8_t *d_redacted, uint8_t fill, uint32_t *d_piece_back,
+                                    uint64_t *d_piece_covered, uint64_t *d_piece_hit_offsets, uint64_t *d_piece_bases,
+                                    uint64_t *n_covered, uint64_t *n_hits, void *stream);
 
 /* Frees the handle's device scratch (it grows with the largest batch seen and is otherwise kept for reuse). */
 int32_t aha_ac_release_scratch(aha_ac *ac);
