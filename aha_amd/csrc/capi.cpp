@@ -11,27 +11,30 @@ namespace ahai {
 // last error text of the calling thread (aha_last_error): calls on one handle may run concurrently
 thread_local std::string tls_err;
 
+hipError_t reserve(Buf &b, size_t bytes, Grow grow) {
+  if (b.bytes >= bytes) return hipSuccess;
+  if (b.p) (void)hipFree(b.p);
+  b = Buf();
+  const size_t want = bytes + (grow == kGrowQuarter ? bytes / 4 + 4096 : bytes / 8 + 256);
+  hipError_t e = hipMalloc(&b.p, want);
+  if (e != hipSuccess && grow == kGrowOrExact) {
+    (void)hipGetLastError();
+    e = hipMalloc(&b.p, bytes);
+  }
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    b.p = nullptr;
+    return e;
+  }
+  b.bytes = grow == kGrowOrExact ? bytes : want;
+  return hipSuccess;
+}
+
 void free_scratch(Scratch *sc, bool all) {
-  for (auto &b : sc->v2buf) {
+  Scratch::each_buf(*sc, [](Buf &b) {
     if (b.p) (void)hipFree(b.p);
     b = Buf();
-  }
-  for (auto &b : sc->hostbuf) {
-    if (b.p) (void)hipFree(b.p);
-    b = Buf();
-  }
-  for (auto &b : sc->cntbuf) {
-    if (b.p) (void)hipFree(b.p);
-    b = Buf();
-  }
-  for (auto &b : sc->dcbuf) {
-    if (b.p) (void)hipFree(b.p);
-    b = Buf();
-  }
-  for (auto &b : sc->covbuf) {
-    if (b.p) (void)hipFree(b.p);
-    b = Buf();
-  }
+  });
   sc->dc_rows_clear = false;
   void **scratch[] = {(void **)&sc->d_counts, (void **)&sc->d_leads, (void **)&sc->d_blk_hits, (void **)&sc->d_blk_leads,
                       (void **)&sc->d_docg};
@@ -40,10 +43,8 @@ void free_scratch(Scratch *sc, bool all) {
     *p = nullptr;
   }
   sc->cap_chunks = sc->cap_blocks = sc->cap_docs = 0;
-  // the counter block went with v2buf[9]: a block allocated later -- even at the same address -- holds words nobody knows
-  sc->cursor_buf = nullptr;
-  sc->cursor_dirty = true;
-  sc->cursor_phase = 0;
+  // the counter block went with v2buf[kCursor]: a block allocated later -- even at the same address -- holds words nobody knows
+  sc->reset_cursor();
   if (!all) return;
   if (sc->d_totals) (void)hipFree(sc->d_totals);
   if (sc->h_totals) (void)hipHostFree(sc->h_totals);
@@ -63,11 +64,7 @@ void free_scratch(Scratch *sc, bool all) {
 
 uint64_t scratch_bytes(const Scratch *sc) {
   uint64_t n = 0;
-  for (auto &b : sc->v2buf) n += b.bytes;
-  for (auto &b : sc->hostbuf) n += b.bytes;
-  for (auto &b : sc->cntbuf) n += b.bytes;
-  for (auto &b : sc->dcbuf) n += b.bytes;
-  for (auto &b : sc->covbuf) n += b.bytes;
+  Scratch::each_buf(*sc, [&n](const Buf &b) { n += b.bytes; });
   n += sc->cap_chunks * 8 + sc->cap_blocks * 16 + sc->cap_docs * 8;
   return n;
 }
@@ -861,10 +858,7 @@ int32_t aha_ac_match_batch_device(aha_ac *ac, const uint8_t *d_corpus,
                                   aha_hit *d_out, uint64_t cap, uint64_t *d_doc_hit_offsets,
                                   uint64_t *n_hits, void *stream) {
   if (!ac || !n_hits || !d_doc_offsets) return AHA_E_INVALID;
-  if (ac->device < 0) {
-    tls_err = aha_strerror(AHA_E_NO_DEVICE);
-    return AHA_E_NO_DEVICE;
-  }
+  if (ac->device < 0) return no_device();
   Lease lease(ac);
   return match_batch_device_impl(ac, lease.get(), d_corpus, d_doc_offsets, n_docs, n_bytes, params, d_out, cap,
                                  d_doc_hit_offsets, n_hits, stream, false);
@@ -905,10 +899,7 @@ int32_t aha_ac_match_batch_device_stream(aha_ac *ac, const uint8_t *d_corpus, co
                                          uint64_t *d_doc_hit_offsets, uint64_t *n_hits, uint32_t *d_words, uint64_t cap_words,
                                          uint64_t *d_n_words, void *stream) {
   if (!ac) return AHA_E_INVALID;
-  if (ac->device < 0) {
-    tls_err = aha_strerror(AHA_E_NO_DEVICE);
-    return AHA_E_NO_DEVICE;
-  }
+  if (ac->device < 0) return no_device();
   Lease lease(ac);
   const PackOut pk{d_words, cap_words, d_n_words};
   return match_batch_device_impl(ac, lease.get(), d_corpus, d_doc_offsets, n_docs, n_bytes, params, d_out, cap, d_doc_hit_offsets,
@@ -953,6 +944,65 @@ static bool host_streams(Scratch *sc) {
   for (auto &st : sc->hs)
     if (!st && hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return false;
   return true;
+}
+
+// device staging buffers are kept in the leased scratch set (grow-only): the reference's usage is one #match per string, so
+// per-call hipMalloc/hipFree would dominate
+static void *host_reserve(Scratch *sc, HostSlot slot, size_t bytes) { return reserve_ptr(sc->hostbuf[slot], bytes, kGrowQuarter); }
+
+// a host batch before anything goes to the device: doc_offsets[0] = 0, ascending, every document below 2 GiB, a text where
+// there are bytes
+static int32_t check_host_batch(const uint8_t *corpus, const uint64_t *doc_offsets, uint64_t n_docs) {
+  if (doc_offsets[0] != 0) return AHA_E_INVALID;
+  for (uint64_t d = 0; d < n_docs; d++) {
+    if (doc_offsets[d + 1] < doc_offsets[d]) return AHA_E_INVALID;
+    if (doc_offsets[d + 1] - doc_offsets[d] >= 0x7FFFFFFFull) return AHA_E_TOO_LONG;
+  }
+  if (doc_offsets[n_docs] && !corpus) return AHA_E_INVALID;
+  return AHA_OK;
+}
+
+// The call families without a match_longest form: the parameters' own checks and the refusal, once per call and before any
+// device work, so they hold on a host-only handle.  what: the refusal's text (null: none)
+static int32_t no_longest_form(aha_ac *ac, const aha_match_params *params, const char *what) {
+  MatchArgs M{};
+  int longest = 0;
+  int32_t rc = fill_params(ac, params, M, &longest);
+  if (rc) return rc;
+  if (longest) {
+    if (what) tls_err = what;
+    return AHA_E_INVALID;
+  }
+  return AHA_OK;
+}
+
+// The prologue of the one-shot host entries (document counts, cover): the staging buffers of the leased scratch set -- the
+// text, its offsets, per_doc and per_call bytes for what comes back (0: not asked for) -- and the batch up in one piece over
+// the set's private stream B.s.
+struct HostBatch {
+  uint8_t *d_corpus;
+  uint64_t *d_doc;
+  void *d_per_doc, *d_per_call;
+  hipStream_t s;
+};
+static int32_t stage_host_batch(aha_ac *ac, Scratch *sc, const uint8_t *corpus, const uint64_t *doc_offsets, uint64_t n_docs,
+                                size_t per_doc, size_t per_call, HostBatch &B) {
+  const uint64_t n_bytes = doc_offsets[n_docs];
+  B.d_corpus = (uint8_t *)host_reserve(sc, kHostCorpus, n_bytes + 64);
+  B.d_doc = (uint64_t *)host_reserve(sc, kHostDocs, (n_docs + 1) * 8);
+  B.d_per_doc = per_doc ? host_reserve(sc, kHostOffsets, per_doc) : nullptr;
+  B.d_per_call = per_call ? host_reserve(sc, kHostOut, per_call) : nullptr;
+  if (!B.d_corpus || !B.d_doc || (per_doc && !B.d_per_doc) || (per_call && !B.d_per_call) || !host_streams(sc)) {
+    tls_err = "hipMalloc / hipStreamCreate failed for the staging buffers";
+    return AHA_E_HIP;
+  }
+  uint8_t *d_corpus = B.d_corpus;  // (the names HIPCHK quotes in aha_last_error, as the entries had them)
+  uint64_t *d_doc = B.d_doc;
+  hipStream_t s = B.s = sc->hs[1];
+  HIPCHK(ac, hipMemcpyAsync(d_doc, doc_offsets, (n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+  if (n_bytes) HIPCHK(ac, hipMemcpyAsync(d_corpus, corpus, n_bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  return AHA_OK;
 }
 }  // namespace
 
@@ -1004,35 +1054,13 @@ static int32_t match_batch_host(aha_ac *ac, const uint8_t *corpus, const uint64_
                                 uint64_t *doc_hit_offsets, uint64_t *n_hits, aha_internal_host_copy *hc,
                                 const CountReq *cq) {
   if (!ac || !doc_offsets || !n_hits) return AHA_E_INVALID;
-  if (ac->device < 0) {
-    tls_err = aha_strerror(AHA_E_NO_DEVICE);
-    return AHA_E_NO_DEVICE;
-  }
-  if (doc_offsets[0] != 0) return AHA_E_INVALID;
-  for (uint64_t d = 0; d < n_docs; d++) {
-    if (doc_offsets[d + 1] < doc_offsets[d]) return AHA_E_INVALID;
-    if (doc_offsets[d + 1] - doc_offsets[d] >= 0x7FFFFFFFull) return AHA_E_TOO_LONG;
-  }
+  if (ac->device < 0) return no_device();
+  if (int32_t rc = check_host_batch(corpus, doc_offsets, n_docs)) return rc;
   const uint64_t n_bytes = doc_offsets[n_docs];
-  if (n_bytes && !corpus) return AHA_E_INVALID;
   *n_hits = 0;
   DeviceGuard g(ac->device);
-  // device staging buffers are kept in the leased scratch set (grow-only): the reference's
-  // usage is one #match per string, so per-call hipMalloc/hipFree would dominate
   Lease lease(ac);
   Scratch *sc = lease.get();
-  auto reserve = [&](int i, size_t bytes) -> void * {
-    Buf &b = sc->hostbuf[i];
-    if (b.bytes < bytes) {
-      if (b.p) (void)hipFree(b.p);
-      b.p = nullptr;
-      b.bytes = 0;
-      size_t want = bytes + bytes / 4 + 4096;
-      if (hipMalloc(&b.p, want) != hipSuccess) return nullptr;
-      b.bytes = want;
-    }
-    return b.p;
-  };
   // ranges: document boundaries nearest to multiples of kHostRange (whole documents only)
   std::vector<uint64_t> bounds;
   try {
@@ -1061,12 +1089,12 @@ static int32_t match_batch_host(aha_ac *ac, const uint8_t *corpus, const uint64_
   } catch (...) {
     return AHA_E_NOMEM;
   }
-  uint8_t *d_corpus = (uint8_t *)reserve(0, dev_off[R] + 64);
-  uint64_t *d_doc = (uint64_t *)reserve(1, (n_docs + R + 1) * sizeof(uint64_t));
-  uint64_t *d_dho = (uint64_t *)reserve(2, (n_docs + R + 1) * sizeof(uint64_t));
-  aha_hit *d_out = !cap ? nullptr : d_keep ? d_keep : (aha_hit *)reserve(3, cap * sizeof(aha_hit));
+  uint8_t *d_corpus = (uint8_t *)host_reserve(sc, kHostCorpus, dev_off[R] + 64);
+  uint64_t *d_doc = (uint64_t *)host_reserve(sc, kHostDocs, (n_docs + R + 1) * sizeof(uint64_t));
+  uint64_t *d_dho = (uint64_t *)host_reserve(sc, kHostOffsets, (n_docs + R + 1) * sizeof(uint64_t));
+  aha_hit *d_out = !cap ? nullptr : d_keep ? d_keep : (aha_hit *)host_reserve(sc, kHostOut, cap * sizeof(aha_hit));
   const uint64_t K = ac->aut.n_keys;
-  uint64_t *d_kc = (cq && cq->key_counts) ? (uint64_t *)reserve(3, std::max<uint64_t>(K, 1) * 8) : nullptr;  // (a count: no hits)
+  uint64_t *d_kc = (cq && cq->key_counts) ? (uint64_t *)host_reserve(sc, kHostOut, std::max<uint64_t>(K, 1) * 8) : nullptr;  // (a count: no hits)
   if (!d_corpus || !d_doc || !d_dho || (cap && !d_out) || (cq && cq->key_counts && !d_kc) || !host_streams(sc)) {
     tls_err = "hipMalloc / hipStreamCreate failed for the staging buffers";
     return AHA_E_HIP;
@@ -1211,11 +1239,7 @@ int32_t aha_ac_count_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *do
                            const aha_match_params *params, uint32_t flags, uint64_t *key_counts, uint64_t *doc_hit_offsets,
                            uint64_t *n_hits) {
   if (!ac || !n_hits || !doc_offsets || (flags & ~AHA_COUNT_ACCUMULATE)) return AHA_E_INVALID;
-  MatchArgs M{};
-  int longest = 0;
-  int32_t rc = fill_params(ac, params, M, &longest);
-  if (rc) return rc;
-  if (longest) return AHA_E_INVALID;
+  if (int32_t rc = no_longest_form(ac, params, nullptr)) return rc;
   const CountReq cq{flags, key_counts};
   return match_batch_host(ac, corpus, doc_offsets, n_docs, params, nullptr, nullptr, 0, doc_hit_offsets, n_hits, nullptr, &cq);
 }
@@ -1224,15 +1248,8 @@ int32_t aha_ac_count_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uin
                                   uint64_t n_bytes, const aha_match_params *params, uint32_t flags, uint64_t *d_key_counts,
                                   uint64_t *d_doc_hit_offsets, uint64_t *n_hits, void *stream) {
   if (!ac || !n_hits || !d_doc_offsets || (flags & ~AHA_COUNT_ACCUMULATE)) return AHA_E_INVALID;
-  MatchArgs M{};
-  int longest = 0;
-  int32_t rc = fill_params(ac, params, M, &longest);
-  if (rc) return rc;
-  if (longest) return AHA_E_INVALID;
-  if (ac->device < 0) {
-    tls_err = aha_strerror(AHA_E_NO_DEVICE);
-    return AHA_E_NO_DEVICE;
-  }
+  if (int32_t rc = no_longest_form(ac, params, nullptr)) return rc;
+  if (ac->device < 0) return no_device();
   Lease lease(ac);
   return device_count(ac, lease.get(), d_corpus, d_doc_offsets, n_docs, n_bytes, params, flags, d_key_counts, d_doc_hit_offsets,
                       n_hits, stream, false);
@@ -1242,18 +1259,8 @@ int32_t aha_ac_count_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uin
 // the argument checks both entries share: before any device work, so they hold on a host-only handle
 static int32_t doc_counts_args(aha_ac *ac, const uint64_t *doc_offsets, const aha_match_params *params, uint64_t *n_pairs) {
   if (!ac || !n_pairs || !doc_offsets) return AHA_E_INVALID;
-  MatchArgs M{};
-  int longest = 0;
-  int32_t rc = fill_params(ac, params, M, &longest);
-  if (rc) return rc;
-  if (longest) {
-    tls_err = "document counts have no match_longest form";
-    return AHA_E_INVALID;
-  }
-  if (ac->device < 0) {
-    tls_err = aha_strerror(AHA_E_NO_DEVICE);
-    return AHA_E_NO_DEVICE;
-  }
+  if (int32_t rc = no_longest_form(ac, params, "document counts have no match_longest form")) return rc;
+  if (ac->device < 0) return no_device();
   return AHA_OK;
 }
 
@@ -1276,42 +1283,18 @@ int32_t aha_ac_doc_counts_batch(aha_ac *ac, const uint8_t *corpus, const uint64_
   int32_t rc = doc_counts_args(ac, doc_offsets, params, n_pairs);
   if (rc) return rc;
   if (cap && !out) return AHA_E_INVALID;
-  if (doc_offsets[0] != 0) return AHA_E_INVALID;
-  for (uint64_t d = 0; d < n_docs; d++) {
-    if (doc_offsets[d + 1] < doc_offsets[d]) return AHA_E_INVALID;
-    if (doc_offsets[d + 1] - doc_offsets[d] >= 0x7FFFFFFFull) return AHA_E_TOO_LONG;
-  }
+  if ((rc = check_host_batch(corpus, doc_offsets, n_docs))) return rc;
   const uint64_t n_bytes = doc_offsets[n_docs];
-  if (n_bytes && !corpus) return AHA_E_INVALID;
   *n_pairs = 0;
   DeviceGuard g(ac->device);
   Lease lease(ac);
   Scratch *sc = lease.get();
-  auto reserve = [&](int i, size_t bytes) -> void * {
-    Buf &b = sc->hostbuf[i];
-    if (b.bytes < bytes) {
-      if (b.p) (void)hipFree(b.p);
-      b.p = nullptr;
-      b.bytes = 0;
-      const size_t want = bytes + bytes / 4 + 4096;
-      if (hipMalloc(&b.p, want) != hipSuccess) return nullptr;
-      b.bytes = want;
-    }
-    return b.p;
-  };
-  uint8_t *d_corpus = (uint8_t *)reserve(0, n_bytes + 64);
-  uint64_t *d_doc = (uint64_t *)reserve(1, (n_docs + 1) * 8);
-  uint64_t *d_dpo = (uint64_t *)reserve(2, (n_docs + 1) * 8);
-  aha_key_count *d_out = cap ? (aha_key_count *)reserve(3, cap * sizeof(aha_key_count)) : nullptr;
-  if (!d_corpus || !d_doc || !d_dpo || (cap && !d_out) || !host_streams(sc)) {
-    tls_err = "hipMalloc / hipStreamCreate failed for the staging buffers";
-    return AHA_E_HIP;
-  }
-  hipStream_t s = sc->hs[1];
-  HIPCHK(ac, hipMemcpyAsync(d_doc, doc_offsets, (n_docs + 1) * 8, hipMemcpyHostToDevice, s));
-  if (n_bytes) HIPCHK(ac, hipMemcpyAsync(d_corpus, corpus, n_bytes, hipMemcpyHostToDevice, s));
-  HIPCHK(ac, hipStreamSynchronize(s));
-  rc = device_doc_counts(ac, sc, d_corpus, d_doc, n_docs, n_bytes, params, d_out, cap, d_dpo, n_pairs, n_hits, s,
+  HostBatch B;
+  if ((rc = stage_host_batch(ac, sc, corpus, doc_offsets, n_docs, (n_docs + 1) * 8, cap * sizeof(aha_key_count), B))) return rc;
+  uint64_t *d_dpo = (uint64_t *)B.d_per_doc;
+  aha_key_count *d_out = (aha_key_count *)B.d_per_call;
+  hipStream_t s = B.s;
+  rc = device_doc_counts(ac, sc, B.d_corpus, B.d_doc, n_docs, n_bytes, params, d_out, cap, d_dpo, n_pairs, n_hits, s,
                          true);  // the offsets were checked on the host above
   if (rc != AHA_OK && rc != AHA_E_CAPACITY) return rc;
   const std::string err = tls_err;
@@ -1328,18 +1311,8 @@ int32_t aha_ac_doc_counts_batch(aha_ac *ac, const uint8_t *corpus, const uint64_
 static int32_t cover_args(aha_ac *ac, const uint64_t *doc_offsets, const aha_match_params *params, uint32_t flags,
                           uint64_t *n_covered) {
   if (!ac || !n_covered || !doc_offsets || flags) return AHA_E_INVALID;
-  MatchArgs M{};
-  int longest = 0;
-  int32_t rc = fill_params(ac, params, M, &longest);
-  if (rc) return rc;
-  if (longest) {
-    tls_err = "cover calls have no match_longest form";
-    return AHA_E_INVALID;
-  }
-  if (ac->device < 0) {
-    tls_err = aha_strerror(AHA_E_NO_DEVICE);
-    return AHA_E_NO_DEVICE;
-  }
+  if (int32_t rc = no_longest_form(ac, params, "cover calls have no match_longest form")) return rc;
+  if (ac->device < 0) return no_device();
   return AHA_OK;
 }
 
@@ -1361,42 +1334,20 @@ int32_t aha_ac_cover_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *do
                            uint64_t *doc_covered, uint64_t *n_covered, uint64_t *n_hits) {
   int32_t rc = cover_args(ac, doc_offsets, params, flags, n_covered);
   if (rc) return rc;
-  if (doc_offsets[0] != 0) return AHA_E_INVALID;
-  for (uint64_t d = 0; d < n_docs; d++) {
-    if (doc_offsets[d + 1] < doc_offsets[d]) return AHA_E_INVALID;
-    if (doc_offsets[d + 1] - doc_offsets[d] >= 0x7FFFFFFFull) return AHA_E_TOO_LONG;
-  }
+  if ((rc = check_host_batch(corpus, doc_offsets, n_docs))) return rc;
   const uint64_t n_bytes = doc_offsets[n_docs], n_words = (n_bytes + 31) / 32;
-  if (n_bytes && !corpus) return AHA_E_INVALID;
   DeviceGuard g(ac->device);
   Lease lease(ac);
   Scratch *sc = lease.get();
-  auto reserve = [&](int i, size_t bytes) -> void * {
-    Buf &b = sc->hostbuf[i];
-    if (b.bytes < bytes) {
-      if (b.p) (void)hipFree(b.p);
-      b.p = nullptr;
-      b.bytes = 0;
-      const size_t want = bytes + bytes / 4 + 4096;
-      if (hipMalloc(&b.p, want) != hipSuccess) return nullptr;
-      b.bytes = want;
-    }
-    return b.p;
-  };
-  uint8_t *d_corpus = (uint8_t *)reserve(0, n_bytes + 64);
-  uint64_t *d_doc = (uint64_t *)reserve(1, (n_docs + 1) * 8);
-  uint64_t *d_cov = doc_covered ? (uint64_t *)reserve(2, (n_docs + 1) * 8) : nullptr;
-  uint32_t *d_mask = mask ? (uint32_t *)reserve(3, n_words * 4 + 16) : nullptr;
-  if (!d_corpus || !d_doc || (doc_covered && !d_cov) || (mask && !d_mask) || !host_streams(sc)) {
-    tls_err = "hipMalloc / hipStreamCreate failed for the staging buffers";
-    return AHA_E_HIP;
-  }
-  hipStream_t s = sc->hs[1];
-  HIPCHK(ac, hipMemcpyAsync(d_doc, doc_offsets, (n_docs + 1) * 8, hipMemcpyHostToDevice, s));
-  if (n_bytes) HIPCHK(ac, hipMemcpyAsync(d_corpus, corpus, n_bytes, hipMemcpyHostToDevice, s));
-  HIPCHK(ac, hipStreamSynchronize(s));
+  HostBatch B;
+  if ((rc = stage_host_batch(ac, sc, corpus, doc_offsets, n_docs, doc_covered ? (n_docs + 1) * 8 : 0, mask ? n_words * 4 + 16 : 0, B)))
+    return rc;
+  uint8_t *d_corpus = B.d_corpus;
+  uint64_t *d_cov = (uint64_t *)B.d_per_doc;
+  uint32_t *d_mask = (uint32_t *)B.d_per_call;
+  hipStream_t s = B.s;
   uint64_t nc = 0, nh = 0;
-  rc = device_cover(ac, sc, d_corpus, d_doc, n_docs, n_bytes, params, flags, d_mask, redacted ? d_corpus : nullptr, fill, d_cov, &nc,
+  rc = device_cover(ac, sc, d_corpus, B.d_doc, n_docs, n_bytes, params, flags, d_mask, redacted ? d_corpus : nullptr, fill, d_cov, &nc,
                     &nh, s, true);  // the offsets were checked on the host above
   if (rc != AHA_OK) return rc;
   if (mask && n_words) HIPCHK(ac, hipMemcpyAsync(mask, d_mask, n_words * 4, hipMemcpyDeviceToHost, s));
@@ -1415,10 +1366,7 @@ static std::vector<hipStream_t> g_copy_streams;  // one private non-blocking str
 
 static int32_t copy_stream(int device, hipStream_t *out) {
   int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-    tls_err = aha_strerror(AHA_E_NO_DEVICE);
-    return AHA_E_NO_DEVICE;
-  }
+  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return no_device();
   if (device < 0 || device >= n) {
     tls_err = "no such device";
     return AHA_E_INVALID;
@@ -1490,13 +1438,8 @@ int32_t aha_corpus_upload(int32_t device, const uint8_t *corpus, const uint64_t 
                           aha_corpus **out) {
   if (!out || !doc_offsets) return AHA_E_INVALID;
   *out = nullptr;
-  if (doc_offsets[0] != 0) return AHA_E_INVALID;
-  for (uint64_t d = 0; d < n_docs; d++) {
-    if (doc_offsets[d + 1] < doc_offsets[d]) return AHA_E_INVALID;
-    if (doc_offsets[d + 1] - doc_offsets[d] >= 0x7FFFFFFFull) return AHA_E_TOO_LONG;
-  }
+  if (int32_t rc0 = check_host_batch(corpus, doc_offsets, n_docs)) return rc0;
   const uint64_t n_bytes = doc_offsets[n_docs];
-  if (n_bytes && !corpus) return AHA_E_INVALID;
   aha_corpus *c = new (std::nothrow) aha_corpus();
   if (!c) return AHA_E_NOMEM;
   c->device = device;

@@ -183,20 +183,18 @@ void v2_setup(aha_ac *ac) {
   }
 }
 
-int32_t v2_reserve(aha_ac *ac, Scratch *sc, int i, size_t bytes) {
-  Buf &b = sc->v2buf[i];
+// a slot of v2buf (handle.hpp V2Slot), grow-only
+static int32_t v2_reserve(Scratch *sc, V2Slot slot, size_t bytes) {
+  Buf &b = sc->v2buf[slot];
   if (b.bytes >= bytes) return AHA_OK;
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.bytes = 0;
-  size_t want = bytes + bytes / 8 + 256;
-  if (i == 9) {  // a new counter block (see Scratch::cursor_dirty): cleared in full by the next call, whatever its address
-    sc->cursor_buf = nullptr;
-    sc->cursor_dirty = true;
-    sc->cursor_phase = 0;
+  // a new counter block (see Scratch::cursor_dirty): cleared in full by the next call, whatever its address
+  if (slot == kCursor) sc->reset_cursor();
+  const hipError_t e = reserve(b, bytes, kGrowEighth);
+  if (e != hipSuccess) {
+      // (the text HIPCHK gave this allocation before it went through reserve(): kept as it was for aha_last_error)
+    tls_err = std::string("hipMalloc(&b.p, want): ") + hipGetErrorString(e);
+    return AHA_E_HIP;
   }
-  HIPCHK(ac, hipMalloc(&b.p, want));
-  b.bytes = want;
   return AHA_OK;
 }
 
@@ -227,7 +225,11 @@ StreamFmt stream_fmt(const aha_ac *ac) {
   return StreamFmt{12, 0};
 }
 
-// returns AHA_OK, an error, +1 when the caller must fall back to the two-pass engine, +2 when a region overflowed
+// device-resident offsets that are not what the call says (k_check_docs): out of order, or a document of 2 GiB
+static int32_t bad_offsets(bool order) {
+  tls_err = order ? "doc offsets: need doc_offsets[0] = 0, ascending, doc_offsets[n_docs] = n_bytes" : aha_strerror(AHA_E_TOO_LONG);
+  return order ? AHA_E_INVALID : AHA_E_TOO_LONG;
+}
 // the pinned words a call's verdict and totals come back in, and their device address
 int32_t ensure_h_v2(aha_ac *ac, Scratch *sc) {
   if (sc->h_v2) return AHA_OK;
@@ -240,44 +242,96 @@ int32_t ensure_h_v2(aha_ac *ac, Scratch *sc) {
 }
 
 // scratch of a cover call (Scratch::covbuf), grow-only; null: no memory
-static void *cover_reserve(Scratch *sc, int i, size_t bytes) {
-  Buf &b = sc->covbuf[i];
-  if (b.bytes < bytes) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.bytes = 0;
-    const size_t want = bytes + bytes / 8 + 256;
-    if (hipMalloc(&b.p, want) != hipSuccess) {
-      (void)hipGetLastError();
-      b.p = nullptr;
-      return nullptr;
-    }
-    b.bytes = want;
-  }
-  return b.p;
-}
+static void *cover_reserve(Scratch *sc, CoverSlot slot, size_t bytes) { return reserve_ptr(sc->covbuf[slot], bytes, kGrowEighth); }
 
-// A folded handle (AHA_OPT_FOLD_ASCII): the folded copy of a batch, in the scratch slot of the "aligned copy of an unaligned
-// corpus" (v2buf[17]) -- one streaming pass does both jobs (scan_fold.hip), and the caller's text is only read.
-static int32_t fold_into_scratch(aha_ac *ac, Scratch *sc, const uint8_t *src, uint64_t n_bytes, hipStream_t s, const uint8_t **out) {
-  int32_t rc;
-  if ((rc = v2_reserve(ac, sc, 17, n_bytes + 64))) return rc;
-  fold_launch_copy(src, (uint8_t *)sc->v2buf[17].p, n_bytes, 8u * std::max<uint32_t>(ac->v2_grid, 64u), s);
-  HIPCHK(ac, hipGetLastError());
-  *out = (const uint8_t *)sc->v2buf[17].p;
+// The kernels read a text in aligned 16-byte pieces, and a folded handle (AHA_OPT_FOLD_ASCII) matches the folded text: *text
+// becomes its copy in `dst` (n_bytes + 64 bytes of scratch), a plain device-to-device copy (~0.7 ms per GiB: about a fifth of
+// a match) or, with `fold`, the one streaming pass that does both jobs (scan_fold.hip).  The caller's text is only read.
+static int32_t stage_text(aha_ac *ac, const uint8_t **text, uint64_t n_bytes, void *dst, bool fold, hipStream_t s) {
+  if (fold) {
+    fold_launch_copy(*text, (uint8_t *)dst, n_bytes, 8u * std::max<uint32_t>(ac->v2_grid, 64u), s);
+    HIPCHK(ac, hipGetLastError());
+  } else {
+    HIPCHK(ac, hipMemcpyAsync(dst, *text, n_bytes, hipMemcpyDeviceToDevice, s));
+  }
+  *text = (const uint8_t *)dst;
   return AHA_OK;
+}
+// ... of a whole batch, in v2buf[kText]
+static int32_t stage_batch(aha_ac *ac, Scratch *sc, const uint8_t **text, uint64_t n_bytes, bool fold, hipStream_t s) {
+  if (int32_t rc = v2_reserve(sc, kText, n_bytes + 64)) return rc;
+  return stage_text(ac, text, n_bytes, sc->v2buf[kText].p, fold, s);
 }
 // M.fold: M.text is still the caller's.  Only the prefix-filter engine takes it like that (it folds in its own loads); every
 // other path -- the byte-level and character-level engines, the opt-in ones, the two-pass engine, match_longest, a pass
 // behind a hand-back of the filter -- calls this first: the copy is made at that moment, once per call.
 static int32_t stage_folded(aha_ac *ac, Scratch *sc, MatchArgs &M, hipStream_t s) {
   if (!M.fold) return AHA_OK;
-  const int32_t rc = fold_into_scratch(ac, sc, M.text, M.n_bytes, s, &M.text);
+  const int32_t rc = stage_batch(ac, sc, &M.text, M.n_bytes, true, s);
   if (rc == AHA_OK) M.fold = 0;
   return rc;
 }
+// The text of a device-resident batch as the engines take it (device_match, device_count): an unaligned view (a slice of a
+// larger buffer) is copied once into scratch, folded on the way on a folded handle; an aligned text stays the caller's, and on
+// a folded handle M.fold says so: the prefix-filter engine reads it where it lies, the others stage it (stage_folded).
+static int32_t take_text(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, uint64_t n_bytes, MatchArgs &M, hipStream_t s) {
+  M.text = d_corpus;
+  if (reinterpret_cast<uintptr_t>(d_corpus) % 16 != 0) return stage_batch(ac, sc, &M.text, n_bytes, ac->fold(), s);
+  if (ac->fold()) M.fold = 1;
+  return AHA_OK;
+}
+// The two-pass engine's chunk: `chunk0`, doubled until the warm-up (a multiple of Lmax - 1 bytes) is a small fraction of it --
+// 8 * Lmax for its own passes, 16 * Lmax for match_longest's.
+static void two_pass_chunks(const aha_ac *ac, MatchArgs &M, uint32_t chunk0, uint64_t lmax_mul) {
+  M.chunk = chunk0;
+  while (M.chunk < lmax_mul * ac->aut.max_key_len && M.chunk < (1u << 20)) M.chunk *= 2;
+  M.n_chunks = (M.n_bytes + M.chunk - 1) / M.chunk;
+}
+// ... and its scratch for `units` counters (chunks or documents) and M.n_docs documents, bound to M
+static int32_t bind_two_pass(aha_ac *ac, Scratch *sc, MatchArgs &M, uint64_t units, uint64_t *n_blocks) {
+  *n_blocks = (units + kBlock - 1) / kBlock;
+  if (int32_t rc = ensure_scratch(ac, sc, units, *n_blocks, M.n_docs)) return rc;
+  M.counts = sc->d_counts;
+  M.leads = sc->d_leads;
+  M.blk_hits = sc->d_blk_hits;
+  M.blk_leads = sc->d_blk_leads;
+  M.docg = sc->d_docg;
+  M.totals = sc->d_totals;
+  return AHA_OK;
+}
+// One pass's aha_timing from the events of its scratch set, published: ms_total ev[0] .. ev[4], ms_count ev[0] .. ev[count_end],
+// ms_write ev[3] .. ev[4], ms_scan and ms_aux between the pairs given (first < 0: not measured); `t` carries the rest.
+static void publish_event_timing(aha_ac *ac, Scratch *sc, aha_timing t, int count_end, int scan0, int scan1, int aux0, int aux1) {
+  t.struct_size = sizeof(t);
+  (void)hipEventElapsedTime(&t.ms_total, sc->ev[0], sc->ev[4]);
+  (void)hipEventElapsedTime(&t.ms_count, sc->ev[0], sc->ev[count_end]);
+  if (scan0 >= 0) (void)hipEventElapsedTime(&t.ms_scan, sc->ev[scan0], sc->ev[scan1]);
+  if (aux0 >= 0) (void)hipEventElapsedTime(&t.ms_aux, sc->ev[aux0], sc->ev[aux1]);
+  (void)hipEventElapsedTime(&t.ms_write, sc->ev[3], sc->ev[4]);
+  publish_timing(ac, t);
+}
 
-int32_t match_v2(aha_ac *ac, Scratch *sc, MatchArgs &M1, hipStream_t s, uint64_t *n_hits, V2Mode mode) {
+// ---- one pass of the single-traversal engines: plan_v2 decides, launch_v2 reserves, binds and launches, verdict_v2 reads back
+// What a pass will do, decided before anything is allocated or launched.
+struct V2Plan {
+  V2Mode mode;         // the pipeline (the mode asked for, after the rules below)
+  bool direct;         // ... one of the region pipelines
+  bool dense;          // more than one hit per 4 input bytes expected
+  bool filt, want_pair, pair, unit, skip;  // the engine: prefix filter, pair (wanted / taken), character-level, ... behind the skip marks; none: byte-level
+  uint64_t S;          // chunk bytes
+  uint64_t n_chunks;
+  uint64_t stride;     // events per chunk region
+  uint64_t rec_bytes;  // bytes per event of the regions: 8 (byte-level engine), 12 (character-level, fused expansion), 12 + 8 (general passes)
+  uint64_t ev_cap;     // slab pipeline: events the temp holds
+  uint64_t cand_cap;   // deep candidates the pair engine has room for
+  size_t sizes[kV2Count];  // bytes per slot of v2buf (0: not used by this pass)
+};
+
+// The planner: a function of the handle's facts, the call's arguments and the lab / test overrides of the environment.
+// Returns 0 and the plan; 1 when the two-pass engine must take the batch; 4 when a count call's full-size regions are beyond the
+// bound (the caller counts in document ranges).  A plan with want_pair && !direct is not to be run: the pair engine's chunk gave
+// regions beyond the temp bound, and the caller plans again without that engine.
+static int32_t plan_v2(const aha_ac *ac, const MatchArgs &M1, V2Mode mode, V2Plan &P) {
   const uint64_t N = M1.n_bytes;
   const uint32_t Lmax = ac->aut.max_key_len;
   // a count call (device_count): full-size regions -- sized from the text, there is no capacity -- and the count passes instead
@@ -311,13 +365,85 @@ int32_t match_v2(aha_ac *ac, Scratch *sc, MatchArgs &M1, hipStream_t s, uint64_t
   const bool want_pair = ac->pair_ok && !M1.chars && !M1.sep && !M1.no_pair && mode != kSlabs && N >= 64 && !(de && strcmp(de, "0") == 0) &&
                          ac->pair_off.load(std::memory_order_relaxed) < 3;
   if (want_pair) S = pair_tile_bytes();
-  V2Args M{};
+  const uint64_t n_chunks = (N + S - 1) / S;
+  if (n_chunks > 0xFFFFFFFFull) return 1;
+  // plain mode (byte offsets or char offsets, no separator filter): per-chunk event regions, no sort
+  const bool dense = M1.cap / 4 > N / 16;        // more than one hit per 4 input bytes expected
+  const bool sparse = M1.cap < 16ull * n_chunks;  // fewer than 16 hits per chunk expected
+  if (de && strcmp(de, "0") == 0) mode = kSlabs;
+  // (the character-level engine leaves its events wave by wave and expands them group by group: its cost follows the
+  // events too, so a handle that has it keeps the regions for sparse batches)
+  if (M1.sep || (mode == kRegions && sparse && !ac->unit_ok && !filt)) mode = kSlabs;
+  if (mode == kRegions && dense) mode = kFullRegions;
+  if (counting) mode = kFullRegions;
+  uint64_t stride = S;
+  // twice the average the caller allows for, plus a slack of 1/64 of the chunk (64 events at 4 KiB): 16 bytes per hit of
+  // capacity + 1/8 byte per input byte
+  if (mode == kRegions) stride = std::min<uint64_t>(S, 2 * (M1.cap / n_chunks) + std::max<uint64_t>(16, S / 64));
+  const uint64_t rec_bytes = want_pair ? 8 : (ac->unit_ok ? (ac->unit_fused ? 12 : 20) : 8);
+  if (counting) {
+    // (AHA_COUNT_REGION_BYTES: a lower bound for the tests, which reach the document ranges with small batches)
+    const char *rb = getenv("AHA_COUNT_REGION_BYTES");
+    const uint64_t bound = rb && atoll(rb) > 0 ? std::min<uint64_t>((uint64_t)atoll(rb), kV2MaxRegionBytes) : kV2MaxRegionBytes;
+    if (n_chunks * stride * rec_bytes > bound) return 4;
+  }
+  if (mode != kSlabs && n_chunks * stride * rec_bytes > kV2MaxRegionBytes) mode = kSlabs;
+  const bool direct = mode != kSlabs;
+  const uint64_t waves = (uint64_t)ac->v2_grid * (kV2Threads / 64);
+  const uint64_t ev_cap = direct ? 0 : ((M1.cap + waves * kV2Slab + kV2Slab) / kV2Slab) * kV2Slab;
+  const bool chars = M1.chars != 0, pair = want_pair && direct;
+  // byte offsets through the event regions: the character-level traversal where the key set has a unit image
+  const bool unit = ac->unit_ok && direct && !pair;
+  // ... started only at the marks of a first, stateless pass where the handle has the filter for it (byte offsets)
+  // (not a batch below one piece of the marking pass: its lanes ask for 16-byte windows wherever they stand)
+  const bool skip = unit && ac->skip_ok && !chars && N >= 64;
+  // deep candidates the pair engine has room for (cfg 3: one per ~120 bytes), in segments of its waves: 256 each at least
+  const uint64_t cand_cap = pair ? std::max<uint64_t>(N / 48 + 4096, waves * 256) : 0;
+  P = V2Plan{mode, direct, dense, filt, want_pair, pair, unit, skip, S, n_chunks, stride, rec_bytes, ev_cap, cand_cap, {}};
+  if (want_pair && !direct) return 0;  // (regions beyond the temp bound: the chunk was the pair engine's)
+  const uint64_t n_slabs = ev_cap / kV2Slab + 2;
+  const uint64_t n_blk = std::max<uint64_t>((n_chunks + 255) / 256, (ev_cap + 255) / 256) + 2;
+  const uint64_t n_reg = direct ? n_chunks * stride : 0;
+  const uint64_t n_docs1 = M1.n_docs + 1;
+  size_t *z = P.sizes;
+  z[kEv] = z[kSortedEv] = ev_cap * 16;
+  z[kSortedCnt] = ev_cap * 4;
+  z[kSlabUsed] = direct ? 0 : n_slabs * 4;
+  z[kEvCnt] = n_chunks * 4;
+  z[kDocEvRank] = n_docs1 * 4;
+  z[kEvBase] = n_chunks * 8;
+  z[kBlkA] = z[kBlkB] = n_blk * 8;
+  z[kCursor] = kCursorBytes;
+  z[kEvAux] = z[kSortedAux] = chars ? ev_cap * 4 : 0;
+  z[kLeadCnt] = z[kChunkDoc0] = (chars || pair) ? n_chunks * 4 : 0;
+  z[kDocLeadRank] = chars ? n_docs1 * 4 : 0;
+  z[kLeadBase] = chars ? n_chunks * 8 : 0;
+  z[kEvRegions] = (unit && ac->unit_fused) ? 0 : n_reg * 8;
+  z[kText] = 0;  // (the callers' and stage_folded's)
+  z[kChunkHits] = direct ? n_chunks * 4 : 0;
+  z[kHitBase] = direct ? n_chunks * 8 : 0;
+  z[kDocHitRank] = unit ? n_docs1 * 4 : 0;
+  z[kEvGroups] = unit ? n_reg * 12 : 0;
+  z[kEngineA] = filt ? ((N + 63) / 64 + 2) * 8 : (skip ? skip_bitmap_bytes(N) : (pair ? n_chunks * 4 : 0));
+  z[kEngineB] = filt ? n_chunks * filter_chunk_rec_bytes() : (pair ? pair_cand_bytes(cand_cap) : 0);
+  z[kEngineC] = pair ? pair_walk_bytes(cand_cap) : 0;
+  z[kKeyVisits] = 0;  // (device_count's)
+  return 0;
+}
+
+// Bind and launch: the plan's scratch reserved and bound to the kernels' arguments, the counter block's phase, the traversal
+// and the post passes on the stream.  AHA_OK: everything is launched, M is what the kernels got; kNoRegions: no room for the
+// event regions (someone else holds the HBM), nothing was launched -- the slab pipeline needs far less temp.
+constexpr int32_t kNoRegions = 5;
+static int32_t launch_v2(aha_ac *ac, Scratch *sc, MatchArgs &M1, const V2Plan &P, V2Args &M, bool prof, hipStream_t s) {
+  const uint64_t N = M1.n_bytes;
+  const bool counting = M1.count_only != 0, direct = P.direct, filt = P.filt, pair = P.pair, unit = P.unit, skip = P.skip;
+  M = V2Args{};
   M.doc_off = M1.doc_off;
   M.n_docs = M1.n_docs;
   M.n_bytes = N;
-  M.S = (uint32_t)S;
-  M.n_chunks = (N + S - 1) / S;
-  if (M.n_chunks > 0xFFFFFFFFull) return 1;
+  M.S = (uint32_t)P.S;
+  M.n_chunks = P.n_chunks;
   M.lds_slots = ac->v2_lds_slots;
   M.chars = M1.chars;
   M.sep = M1.sep;
@@ -326,112 +452,57 @@ int32_t match_v2(aha_ac *ac, Scratch *sc, MatchArgs &M1, hipStream_t s, uint64_t
   M.cap = M1.cap;
   M.doc_hit_off = M1.doc_hit_off;
   M.unit_bb = ac->unit.base_bits;
-  // plain mode (byte offsets or char offsets, no separator filter): per-chunk event regions, no sort
-  const bool dense = M1.cap / 4 > N / 16;          // more than one hit per 4 input bytes expected
-  const bool sparse = M1.cap < 16ull * M.n_chunks;  // fewer than 16 hits per chunk expected
-  if (de && strcmp(de, "0") == 0) mode = kSlabs;
-  // (the character-level engine leaves its events wave by wave and expands them group by group: its cost follows the
-  // events too, so a handle that has it keeps the regions for sparse batches)
-  if (M.sep || (mode == kRegions && sparse && !ac->unit_ok && !filt)) mode = kSlabs;
-  if (mode == kRegions && dense) mode = kFullRegions;
-  if (counting) mode = kFullRegions;
-  uint64_t stride = S;
-  // twice the average the caller allows for, plus a slack of 1/64 of the chunk (64 events at 4 KiB): 16 bytes per hit of
-  // capacity + 1/8 byte per input byte
-  if (mode == kRegions) stride = std::min<uint64_t>(S, 2 * (M1.cap / M.n_chunks) + std::max<uint64_t>(16, S / 64));
-  // bytes per event of the regions: 8 (byte-level engine), 12 (character-level, fused expansion), 12 + 8 (general passes)
-  const uint64_t rec_bytes = want_pair ? 8 : (ac->unit_ok ? (ac->unit_fused ? 12 : 20) : 8);
-  if (counting) {
-    // (AHA_COUNT_REGION_BYTES: a lower bound for the tests, which reach the document ranges with small batches)
-    const char *rb = getenv("AHA_COUNT_REGION_BYTES");
-    const uint64_t bound = rb && atoll(rb) > 0 ? std::min<uint64_t>((uint64_t)atoll(rb), kV2MaxRegionBytes) : kV2MaxRegionBytes;
-    if (M.n_chunks * stride * rec_bytes > bound) return 4;
-  }
-  if (mode != kSlabs && M.n_chunks * stride * rec_bytes > kV2MaxRegionBytes) mode = kSlabs;
-  const bool direct = mode != kSlabs;
-  const uint64_t waves = (uint64_t)ac->v2_grid * (kV2Threads / 64);
   M.direct = direct ? 1 : 0;
-  M.dense_hits = dense ? 1 : 0;
-  M.ev_stride = (uint32_t)stride;
-  M.ev_cap = direct ? 0 : ((M1.cap + waves * kV2Slab + kV2Slab) / kV2Slab) * kV2Slab;
-  const uint64_t n_slabs = M.ev_cap / kV2Slab + 2;
-  const uint64_t n_blk = std::max<uint64_t>((M.n_chunks + 255) / 256, (M.ev_cap + 255) / 256) + 2;
-  const uint64_t n_reg = direct ? M.n_chunks * M.ev_stride : 0;
-  // byte offsets through the event regions: the character-level traversal where the key set has a unit image
-  const bool pair = want_pair && direct;
-  if (want_pair && !pair) return match_v2(ac, sc, (M1.no_pair = 1, M1), s, n_hits, mode);  // (regions beyond the temp bound: the chunk was the pair engine's)
-  const bool unit = ac->unit_ok && direct && !pair;
-  // ... started only at the marks of a first, stateless pass where the handle has the filter for it (byte offsets)
-  // (not a batch below one piece of the marking pass: its lanes ask for 16-byte windows wherever they stand)
-  const bool skip = unit && ac->skip_ok && !M.chars && N >= 64;
+  M.dense_hits = P.dense ? 1 : 0;
+  M.ev_stride = (uint32_t)P.stride;
+  M.ev_cap = P.ev_cap;
   int32_t rc;
-  // deep candidates the pair engine has room for (cfg 3: one per ~120 bytes), in segments of its waves: 256 each at least
-  const uint64_t cand_cap = pair ? std::max<uint64_t>(N / 48 + 4096, (uint64_t)ac->v2_grid * (kV2Threads / 64) * 256) : 0;
-  size_t sizes[26] = {M.ev_cap * 16,      M.ev_cap * 16,      M.ev_cap * 4,     direct ? 0 : n_slabs * 4,
-                      M.n_chunks * 4,     (M.n_docs + 1) * 4, M.n_chunks * 8,   n_blk * 8,
-                      n_blk * 8,          kCursorBytes,       M.chars ? M.ev_cap * 4 : 0, M.chars ? M.ev_cap * 4 : 0,
-                      (M.chars || pair) ? M.n_chunks * 4 : 0, (M.chars || pair) ? M.n_chunks * 4 : 0, M.chars ? (M.n_docs + 1) * 4 : 0,
-                      M.chars ? M.n_chunks * 8 : 0,
-                      (unit && ac->unit_fused) ? 0 : n_reg * 8, 0 /* [17]: aligned copy of an unaligned corpus */,
-                      direct ? M.n_chunks * 4 : 0, direct ? M.n_chunks * 8 : 0,
-                      unit ? (M.n_docs + 1) * 4 : 0, unit ? n_reg * 12 : 0,
-                      filt ? ((N + 63) / 64 + 2) * 8 : (skip ? skip_bitmap_bytes(N) : (pair ? M.n_chunks * 4 : 0)) /* [22]: candidate bitmap / marks / tile records */,
-                      filt ? M.n_chunks * filter_chunk_rec_bytes() : (pair ? pair_cand_bytes(cand_cap) : 0) /* [23] */,
-                      pair ? pair_walk_bytes(cand_cap) : 0 /* [24] */, 0};
-  for (int i = 0; i < 26; i++) {
-    if (!sizes[i]) continue;
-    if ((rc = v2_reserve(ac, sc, i, sizes[i]))) {
-      // no room for the event regions (someone else holds the HBM): the slab pipeline needs far less temp
-      if ((i == 16 || i == 21) && mode != kSlabs) {
-        (void)hipGetLastError();
-        if (counting) return 4;
-        return match_v2(ac, sc, M1, s, n_hits, kSlabs);
-      }
-      return rc;
-    }
+  for (int i = 0; i < kV2Count; i++) {
+    if (!P.sizes[i]) continue;
+    if ((rc = v2_reserve(sc, (V2Slot)i, P.sizes[i]))) return ((i == kEvRegions || i == kEvGroups) && P.mode != kSlabs) ? kNoRegions : rc;
   }
   if (M1.fold && !filt && (rc = stage_folded(ac, sc, M1, s))) return rc;
   const bool fold_loads = filt && M1.fold;  // (the filter engine on the caller's own text)
+  auto at = [sc](V2Slot slot) { return sc->v2buf[slot].p; };
   M.text = M1.text;
-  M.ev = (uint4 *)sc->v2buf[0].p;
-  M.sorted_ev = (uint4 *)sc->v2buf[1].p;
-  M.sorted_cnt = (uint32_t *)sc->v2buf[2].p;
-  M.slab_used = (uint32_t *)sc->v2buf[3].p;
-  M.ev_cnt = (uint32_t *)sc->v2buf[4].p;
-  M.doc_ev_rank = (uint32_t *)sc->v2buf[5].p;
-  M.ev_base = (uint64_t *)sc->v2buf[6].p;
-  M.blk_a = (uint64_t *)sc->v2buf[7].p;
-  M.blk_b = (uint64_t *)sc->v2buf[8].p;
-  if (sc->cursor_buf != sc->v2buf[9].p) {  // (a new buffer: nothing is known about its words)
-    sc->cursor_buf = sc->v2buf[9].p;
+  M.ev = (uint4 *)at(kEv);
+  M.sorted_ev = (uint4 *)at(kSortedEv);
+  M.sorted_cnt = (uint32_t *)at(kSortedCnt);
+  M.slab_used = (uint32_t *)at(kSlabUsed);
+  M.ev_cnt = (uint32_t *)at(kEvCnt);
+  M.doc_ev_rank = (uint32_t *)at(kDocEvRank);
+  M.ev_base = (uint64_t *)at(kEvBase);
+  M.blk_a = (uint64_t *)at(kBlkA);
+  M.blk_b = (uint64_t *)at(kBlkB);
+  if (sc->cursor_buf != at(kCursor)) {  // (a new buffer: nothing is known about its words)
+    sc->cursor_buf = at(kCursor);
     sc->cursor_dirty = true;
   }
-  M.ev_aux = (uint32_t *)sc->v2buf[10].p;
-  M.sorted_aux = (uint32_t *)sc->v2buf[11].p;
-  M.lead_cnt = (uint32_t *)sc->v2buf[12].p;
-  M.chunk_doc0 = (uint32_t *)sc->v2buf[13].p;
-  M.doc_lead_rank = (uint32_t *)sc->v2buf[14].p;
-  M.lead_base = (uint64_t *)sc->v2buf[15].p;
-  M.evd = (uint2 *)sc->v2buf[16].p;
-  M.evg = (uint32_t *)sc->v2buf[21].p;
-  M.doc_hit_rank = (uint32_t *)sc->v2buf[20].p;
-  M.chunk_hits = (uint32_t *)sc->v2buf[18].p;
-  M.hit_base = (uint64_t *)sc->v2buf[19].p;
+  M.ev_aux = (uint32_t *)at(kEvAux);
+  M.sorted_aux = (uint32_t *)at(kSortedAux);
+  M.lead_cnt = (uint32_t *)at(kLeadCnt);
+  M.chunk_doc0 = (uint32_t *)at(kChunkDoc0);
+  M.doc_lead_rank = (uint32_t *)at(kDocLeadRank);
+  M.lead_base = (uint64_t *)at(kLeadBase);
+  M.evd = (uint2 *)at(kEvRegions);
+  M.evg = (uint32_t *)at(kEvGroups);
+  M.doc_hit_rank = (uint32_t *)at(kDocHitRank);
+  M.chunk_hits = (uint32_t *)at(kChunkHits);
+  M.hit_base = (uint64_t *)at(kHitBase);
   if ((rc = ensure_h_v2(ac, sc))) return rc;
   // the region pipelines' last kernel -- the per-document offsets -- leaves the host's five words itself
   M.publish = (direct && M.doc_hit_off && sc->h_v2_dev) ? sc->h_v2_dev : nullptr;
   // the call's counter block; the kernel that publishes also clears the other block for the next call
   static const bool always_clear = getenv("AHA_CURSOR_MEMSET") != nullptr;  // (lab: the memset in front of every call, as before round 6)
   if (sc->cursor_dirty || always_clear) {
-    HIPCHK(ac, hipMemsetAsync(sc->v2buf[9].p, 0, kCursorBytes, s));
+    HIPCHK(ac, hipMemsetAsync(at(kCursor), 0, kCursorBytes, s));
     sc->cursor_phase = 0;
   }
-  M.cursor = (unsigned long long *)sc->v2buf[9].p + 16 * sc->cursor_phase;
+  M.cursor = (unsigned long long *)at(kCursor) + 16 * sc->cursor_phase;
   M.totals = (uint64_t *)M.cursor + 2;
-  M.clear_next = M.publish ? (unsigned long long *)sc->v2buf[9].p + 16 * (sc->cursor_phase ^ 1u) : nullptr;
+  M.clear_next = M.publish ? (unsigned long long *)at(kCursor) + 16 * (sc->cursor_phase ^ 1u) : nullptr;
   sc->cursor_dirty = true;  // (until this call has run to its end)
 
-  const bool prof = ac->profiling.load() && sc->ev_ready;
   // device-resident offsets nobody has looked at yet: validated here, in front of the traversal; a bad verdict lands in
   // cursor[1], where the traversal and every post pass look first (no read-back before the launch: -30 us per call)
   if (M1.check_docs) launch_check_docs(M.doc_off, M.n_docs, N, nullptr, M.cursor + 1, s);
@@ -442,24 +513,24 @@ int32_t match_v2(aha_ac *ac, Scratch *sc, MatchArgs &M1, hipStream_t s, uint64_t
   if (pair) {
     post.end_info = ac->d_unit_end_info;  // its deep events carry bases of the unit image
     post.compact = 1;
-    pair_launch(ac->pdev, ac->udev, post, M, sc->v2buf[22].p, sc->v2buf[23].p, sc->v2buf[24].p, cand_cap, ac->v2_grid,
+    pair_launch(ac->pdev, ac->udev, post, M, at(kEngineA), at(kEngineB), at(kEngineC), P.cand_cap, ac->v2_grid,
                 prof ? (void *)sc->ev[2] : nullptr, s);  // (profiling only: ms_count = the pair pass, ms_scan = the deep walks)
   } else if (unit) {
     post.end_info = ac->d_unit_end_info;  // events carry bases of the unit image
     post.compact = 1;
     if (skip) {
-      skip_launch_mark(ac->sdev, M, sc->v2buf[22].p, ac->v2_grid, s);
+      skip_launch_mark(ac->sdev, M, at(kEngineA), ac->v2_grid, s);
       if (prof) HIPCHK(ac, hipEventRecord(sc->ev[2], s));  // (profiling only: ms_count = the marks, ms_scan = the walk)
-      skip_launch_traverse(ac->udev, M, sc->v2buf[22].p, (uint32_t)std::min<uint64_t>(ac->v2_grid, n_tiles), s);
+      skip_launch_traverse(ac->udev, M, at(kEngineA), (uint32_t)std::min<uint64_t>(ac->v2_grid, n_tiles), s);
     } else {
       unit_launch_traverse(ac->udev, M, (uint32_t)std::min<uint64_t>(ac->v2_grid, n_tiles), s);
     }
   } else if (filt) {
     // filter (one bit per byte position), then the candidates' goto walks, a wave per chunk
     unsigned long long *non_ascii = M1.chars ? M.cursor + 6 : nullptr;
-    (fold_loads ? filter_launch_filter_fold : filter_launch_filter)(ac->fdev, M, sc->v2buf[22].p, sc->v2buf[23].p, non_ascii, ac->pf_cus, s);
+    (fold_loads ? filter_launch_filter_fold : filter_launch_filter)(ac->fdev, M, at(kEngineA), at(kEngineB), non_ascii, ac->pf_cus, s);
     if (prof) HIPCHK(ac, hipEventRecord(sc->ev[2], s));  // (profiling only: ms_count = the filter, ms_scan = the walks)
-    (fold_loads ? filter_launch_walk_fold : filter_launch_walk)(ac->dev, M, sc->v2buf[22].p, sc->v2buf[23].p, non_ascii, ac->pf_cus, s);
+    (fold_loads ? filter_launch_walk_fold : filter_launch_walk)(ac->dev, M, at(kEngineA), at(kEngineB), non_ascii, ac->pf_cus, s);
   } else {
     v2_launch_traverse(ac->dev, M, (uint32_t)std::min<uint64_t>(ac->v2_grid, n_tiles), s);
   }
@@ -475,7 +546,7 @@ int32_t match_v2(aha_ac *ac, Scratch *sc, MatchArgs &M1, hipStream_t s, uint64_t
     // a cover call: the mask cleared (unless the pass was aborted), then one span per event from the same records
     uint64_t *cdoc = nullptr;
     if (M1.cover_mask) {
-      if (!(cdoc = (uint64_t *)cover_reserve(sc, 1, (M.n_chunks + 1) * 8))) {
+      if (!(cdoc = (uint64_t *)cover_reserve(sc, kCovChunkDoc, (M.n_chunks + 1) * 8))) {
         tls_err = "hipMalloc failed for the scratch of a cover call";
         return AHA_E_HIP;
       }
@@ -519,6 +590,15 @@ int32_t match_v2(aha_ac *ac, Scratch *sc, MatchArgs &M1, hipStream_t s, uint64_t
   }
   if (prof) HIPCHK(ac, hipEventRecord(sc->ev[4], s));
   HIPCHK(ac, hipGetLastError());
+  return AHA_OK;
+}
+
+// The verdict: the call's five words read back, cursor[1] mapped to what match_v2 returns, the pair engine's give-ups counted,
+// the timing published.
+static int32_t verdict_v2(aha_ac *ac, Scratch *sc, MatchArgs &M1, const V2Plan &P, const V2Args &M, bool prof, hipStream_t s,
+                          uint64_t *n_hits) {
+  const bool counting = M1.count_only != 0, direct = P.direct, filt = P.filt, pair = P.pair, unit = P.unit, skip = P.skip;
+  [[maybe_unused]] const uint64_t N = M1.n_bytes;  // (the lab blocks below)
   if (M.publish) {
     // (done by k2d_doc_offsets / ku_doc_offsets)
   } else if (sc->h_v2_dev) {
@@ -550,14 +630,7 @@ int32_t match_v2(aha_ac *ac, Scratch *sc, MatchArgs &M1, hipStream_t s, uint64_t
             (double)w[8] / (double)N, w[9], w[11], w[10], 100.0 * (double)w[8] / (64.0 * (double)w[10]));
   }
 #endif
-  if (sc->h_v2[1] >= 16) {  // the offsets are not what the call says (k_check_docs): nothing was indexed with them
-    if (sc->h_v2[1] & 1) {
-      tls_err = "doc offsets: need doc_offsets[0] = 0, ascending, doc_offsets[n_docs] = n_bytes";
-      return AHA_E_INVALID;
-    }
-    tls_err = aha_strerror(AHA_E_TOO_LONG);
-    return AHA_E_TOO_LONG;
-  }
+  if (sc->h_v2[1] >= 16) return bad_offsets(sc->h_v2[1] & 1);  // (k_check_docs: nothing was indexed with them)
   if (sc->h_v2[1] == 3 && pair) {  // the pair engine gave the batch up (documents of a few bytes, a piece dense with events): engine 4 takes it
     if (!counting && !M1.neutral) ac->pair_off.fetch_add(1, std::memory_order_relaxed);  // (three times: the handle stops trying; a count call
                                                                            // leaves the handle's history as it found it)
@@ -570,28 +643,47 @@ int32_t match_v2(aha_ac *ac, Scratch *sc, MatchArgs &M1, hipStream_t s, uint64_t
   if (sc->h_v2[1] == 2) return 2;  // a chunk's event region overflowed: the caller repeats with full-size regions
   if (sc->h_v2[1]) return 1;  // event temp exhausted (cap too small): exact count via the two-pass engine
   *n_hits = sc->h_v2[2];
-  if (prof) {
-    aha_timing t;
-    memset(&t, 0, sizeof(t));
-    t.struct_size = sizeof(t);
+  if (prof) {  // (the events were recorded)
+    aha_timing t{};
     t.engine = pair ? 7 : (skip ? 6 : (unit ? 4 : (filt ? 5 : 2)));
     t.chunk_bytes = M.S;
     t.n_kernels = 9;
-    (void)hipEventElapsedTime(&t.ms_total, sc->ev[0], sc->ev[4]);
-    (void)hipEventElapsedTime(&t.ms_count, sc->ev[0], (filt || skip || pair) ? sc->ev[2] : sc->ev[1]);
-    if (filt || skip || pair) (void)hipEventElapsedTime(&t.ms_scan, sc->ev[2], sc->ev[1]);
-    if (direct) {
-      (void)hipEventElapsedTime(&t.ms_aux, sc->ev[1], sc->ev[3]);
-    } else {
-      (void)hipEventElapsedTime(&t.ms_scan, sc->ev[1], sc->ev[2]);
-      (void)hipEventElapsedTime(&t.ms_aux, sc->ev[2], sc->ev[3]);
-    }
-    (void)hipEventElapsedTime(&t.ms_write, sc->ev[3], sc->ev[4]);
     t.n_chunks = M.n_chunks;
     t.n_hits = *n_hits;
-    publish_timing(ac, t);
+    // an engine with a pass in front of its traversal (filter, marks, pairs): ms_count is that pass, ms_scan the traversal
+    const bool front = filt || skip || pair;
+    if (direct)
+      publish_event_timing(ac, sc, t, front ? 2 : 1, front ? 2 : -1, 1, 1, 3);
+    else
+      publish_event_timing(ac, sc, t, front ? 2 : 1, 1, 2, 2, 3);
   }
   return AHA_OK;
+}
+
+// One pass over a batch through the engine and pipeline the planner picks for `mode`.  Returns AHA_OK, an error, +1 when the
+// caller must fall back to the two-pass engine, +2 when a region overflowed, +3 when the prefix-filter or the pair engine
+// handed the batch back, +4 when a count call's regions do not fit (count_ranges).
+static int32_t match_v2(aha_ac *ac, Scratch *sc, MatchArgs &M1, hipStream_t s, uint64_t *n_hits, V2Mode mode) {
+  for (;;) {
+    V2Plan P;
+    int32_t rc = plan_v2(ac, M1, mode, P);
+    if (rc) return rc;
+    if (P.want_pair && !P.direct) {  // the same pipeline, planned again without the pair engine and its chunk
+      M1.no_pair = 1;
+      mode = P.mode;
+      continue;
+    }
+    V2Args M;
+    const bool prof = ac->profiling.load() && sc->ev_ready;  // (read once per pass: the verdict times what the launch recorded)
+    rc = launch_v2(ac, sc, M1, P, M, prof, s);
+    if (rc == kNoRegions) {  // planned again as the slab pipeline; a count call has none: document ranges
+      if (M1.count_only) return 4;
+      mode = kSlabs;
+      continue;
+    }
+    if (rc) return rc;
+    return verdict_v2(ac, sc, M1, P, M, prof, s, n_hits);
+  }
 }
 
 // the events of a scratch set are created by the first profiled call that leases it
@@ -612,33 +704,22 @@ int32_t ready_events(aha_ac *ac, Scratch *sc) {
 static int32_t check_docs_now(aha_ac *ac, Scratch *sc, const uint64_t *d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
                               hipStream_t s) {
   int32_t rc2;
-  if ((rc2 = v2_reserve(ac, sc, 9, kCursorBytes))) return rc2;
+  if ((rc2 = v2_reserve(sc, kCursor, kCursorBytes))) return rc2;
   if ((rc2 = ensure_h_v2(ac, sc))) return rc2;
-  uint32_t *flag = (uint32_t *)sc->v2buf[9].p + 64;  // (the third block: odd words)
+  uint32_t *flag = (uint32_t *)sc->v2buf[kCursor].p + 64;  // (the third block: odd words)
   HIPCHK(ac, hipMemsetAsync(flag, 0, 4, s));
   launch_check_docs(d_doc_offsets, n_docs, n_bytes, flag, nullptr, s);
   HIPCHK(ac, hipMemcpyAsync(sc->h_v2, flag, 4, hipMemcpyDeviceToHost, s));
   HIPCHK(ac, hipStreamSynchronize(s));
   const uint32_t bad = (uint32_t)sc->h_v2[0];
-  if (bad & 1u) {
-    tls_err = "doc offsets: need doc_offsets[0] = 0, ascending, doc_offsets[n_docs] = n_bytes";
-    return AHA_E_INVALID;
-  }
-  if (bad & 2u) {
-    tls_err = aha_strerror(AHA_E_TOO_LONG);
-    return AHA_E_TOO_LONG;
-  }
-  return AHA_OK;
+  return (bad & 3u) ? bad_offsets(bad & 1u) : AHA_OK;
 }
 
 int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
                      uint64_t n_bytes, const aha_match_params *params, aha_hit *d_out, uint64_t cap, uint64_t *d_doc_hit_offsets,
                      uint64_t *n_hits, void *stream, bool offsets_checked, const PackOut *pk, bool *packed, bool quiet, bool neutral) {
   if (!ac || !n_hits || !d_doc_offsets) return AHA_E_INVALID;
-  if (ac->device < 0) {
-    tls_err = aha_strerror(AHA_E_NO_DEVICE);
-    return AHA_E_NO_DEVICE;
-  }
+  if (ac->device < 0) return no_device();
   if (cap && !d_out) return AHA_E_INVALID;
   DeviceGuard g(ac->device);
   hipStream_t s = (hipStream_t)stream;
@@ -651,6 +732,11 @@ int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
   M.neutral = neutral ? 1 : 0;
   *n_hits = 0;
   auto check_now = [&]() { return check_docs_now(ac, sc, d_doc_offsets, n_docs, n_bytes, s); };
+  auto fits = [&]() {  // the call's verdict once the hits are counted
+    if (*n_hits <= cap) return (int32_t)AHA_OK;
+    tls_err = "output buffer too small";
+    return (int32_t)AHA_E_CAPACITY;
+  };
   // The single-traversal pipelines validate on the device in front of their traversal (match_v2); every other path -- an
   // empty batch, match_longest, the two-pass engine -- reads the verdict back first.
   const bool defer_check = !offsets_checked && ac->v2_ok && !longest && n_bytes != 0;
@@ -663,26 +749,13 @@ int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
     return AHA_OK;
   }
   if (!d_corpus) return AHA_E_INVALID;
-  if (reinterpret_cast<uintptr_t>(d_corpus) % 16 != 0) {
-    // the kernels read the corpus in aligned 16-byte pieces: an unaligned view (a slice of a larger buffer) is copied
-    // once, device to device, into the handle's scratch (~0.7 ms per GiB: about a fifth of the match itself)
-    if (ac->fold()) {  // (folded on the way: the one pass does both jobs)
-      if ((rc = fold_into_scratch(ac, sc, d_corpus, n_bytes, s, &d_corpus))) return rc;
-    } else {
-      if ((rc = v2_reserve(ac, sc, 17, n_bytes + 64))) return rc;
-      HIPCHK(ac, hipMemcpyAsync(sc->v2buf[17].p, d_corpus, n_bytes, hipMemcpyDeviceToDevice, s));
-      d_corpus = (const uint8_t *)sc->v2buf[17].p;
-    }
-  } else if (ac->fold()) {
-    M.fold = 1;  // (the caller's text, aligned: the prefix-filter engine reads it where it lies, the others stage it)
-  }
-  M.text = d_corpus;
   M.doc_off = d_doc_offsets;
   M.n_docs = n_docs;
   M.n_bytes = n_bytes;
   M.out = d_out;
   M.cap = cap;
   M.doc_hit_off = d_doc_hit_offsets;
+  if ((rc = take_text(ac, sc, d_corpus, n_bytes, M, s))) return rc;
   if (longest) {
     if ((rc = stage_folded(ac, sc, M, s))) return rc;
     d_corpus = M.text;
@@ -697,18 +770,9 @@ int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
       HIPCHK(ac, hipStreamSynchronize(s));
       M.has_nul = sc->h_totals[1] ? 1 : 0;  // the chunks' warm-ups then reach back past the NULs they cross (kernels.hip)
     }
-    M.chunk = 1024;
-    while (M.chunk < 16ull * ac->aut.max_key_len && M.chunk < (1u << 20)) M.chunk *= 2;  // the warm-up is 2 * Lmax
-    M.n_chunks = (n_bytes + M.chunk - 1) / M.chunk;
-    const uint64_t units = mode == 2 ? M.n_chunks : n_docs + 1;
-    uint64_t n_blocks = (units + kBlock - 1) / kBlock;
-    if ((rc = ensure_scratch(ac, sc, units, n_blocks, n_docs))) return rc;
-    M.counts = sc->d_counts;
-    M.leads = sc->d_leads;
-    M.blk_hits = sc->d_blk_hits;
-    M.blk_leads = sc->d_blk_leads;
-    M.docg = sc->d_docg;
-    M.totals = sc->d_totals;
+    two_pass_chunks(ac, M, 1024, 16);  // the warm-up is 2 * Lmax
+    uint64_t n_blocks;
+    if ((rc = bind_two_pass(ac, sc, M, mode == 2 ? M.n_chunks : n_docs + 1, &n_blocks))) return rc;
     const int chars = M.chars;
     if ((rc = ensure_stale(ac))) return rc;
     launch_longest(ac->dev_longest, M, mode, false, s);
@@ -717,15 +781,7 @@ int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
       HIPCHK(ac, hipStreamSynchronize(s));
       if (sc->h_totals[1] == 2) {
         mode = 3;
-        const uint64_t units3 = n_docs + 1, blocks3 = (units3 + kBlock - 1) / kBlock;
-        if ((rc = ensure_scratch(ac, sc, units3, blocks3, n_docs))) return rc;
-        M.counts = sc->d_counts;
-        M.leads = sc->d_leads;
-        M.blk_hits = sc->d_blk_hits;
-        M.blk_leads = sc->d_blk_leads;
-        M.docg = sc->d_docg;
-        M.totals = sc->d_totals;
-        n_blocks = blocks3;
+        if ((rc = bind_two_pass(ac, sc, M, n_docs + 1, &n_blocks))) return rc;
         launch_longest(ac->dev_longest, M, mode, false, s);
       }
     }
@@ -737,11 +793,7 @@ int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
     HIPCHK(ac, hipMemcpyAsync(sc->h_totals, sc->d_totals, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     HIPCHK(ac, hipStreamSynchronize(s));
     *n_hits = sc->h_totals[0];
-    if (*n_hits > cap) {
-      tls_err = "output buffer too small";
-      return AHA_E_CAPACITY;
-    }
-    return AHA_OK;
+    return fits();
   }
   uint32_t repeats = 0;  // passes thrown away (aha_timing.repeats)
   if (ac->v2_ok) {
@@ -780,33 +832,15 @@ int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
     if (rc == 2) rc = match_v2(ac, sc, M, s, n_hits, kSlabs);  // (not reached: full-size regions cannot overflow)
     if (rc == AHA_OK && repeats) note_repeats(ac, repeats);
     if (rc < 0) return rc;
-    if (rc == AHA_OK) {
-      if (*n_hits > cap) {
-        tls_err = "output buffer too small";
-        return AHA_E_CAPACITY;
-      }
-      return AHA_OK;
-    }
+    if (rc == AHA_OK) return fits();
     *n_hits = 0;  // rc == 1: fall through to the two-pass engine
     repeats++;
     if (M.check_docs && (rc = check_now())) return rc;  // (no single-traversal pass has looked at the offsets)
   }
   if ((rc = stage_folded(ac, sc, M, s))) return rc;
-  M.chunk = ac->chunk;
-  // warm-up is Lmax-1 bytes per chunk: keep it a small fraction of the chunk
-  while (M.chunk < 8ull * ac->aut.max_key_len && M.chunk < (1u << 20)) M.chunk *= 2;
-  M.n_chunks = (n_bytes + M.chunk - 1) / M.chunk;
-  const uint64_t n_blocks = (M.n_chunks + kBlock - 1) / kBlock;
-  if ((rc = ensure_scratch(ac, sc, M.n_chunks, n_blocks, n_docs))) return rc;
-  M.counts = sc->d_counts;
-  M.leads = sc->d_leads;
-  M.blk_hits = sc->d_blk_hits;
-  M.blk_leads = sc->d_blk_leads;
-  M.docg = sc->d_docg;
-  M.totals = sc->d_totals;
-  M.out = d_out;
-  M.cap = cap;
-  M.doc_hit_off = d_doc_hit_offsets;
+  two_pass_chunks(ac, M, ac->chunk, 8);  // warm-up is Lmax-1 bytes per chunk
+  uint64_t n_blocks;
+  if ((rc = bind_two_pass(ac, sc, M, M.n_chunks, &n_blocks))) return rc;
 
   const bool prof = ac->profiling.load() && sc->ev_ready;
   if (prof) HIPCHK(ac, hipEventRecord(sc->ev[0], s));
@@ -823,27 +857,16 @@ int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
   HIPCHK(ac, hipStreamSynchronize(s));
   *n_hits = sc->h_totals[0];
   if (prof) {
-    aha_timing t;
-    memset(&t, 0, sizeof(t));
-    t.struct_size = sizeof(t);
+    aha_timing t{};
     t.n_kernels = M.chars ? 4 : 3;
-    (void)hipEventElapsedTime(&t.ms_total, sc->ev[0], sc->ev[4]);
-    (void)hipEventElapsedTime(&t.ms_count, sc->ev[0], sc->ev[1]);
-    (void)hipEventElapsedTime(&t.ms_scan, sc->ev[1], sc->ev[2]);
-    (void)hipEventElapsedTime(&t.ms_aux, sc->ev[2], sc->ev[3]);
-    (void)hipEventElapsedTime(&t.ms_write, sc->ev[3], sc->ev[4]);
     t.n_chunks = M.n_chunks;
     t.n_hits = *n_hits;
     t.engine = 1;
     t.chunk_bytes = M.chunk;
     t.repeats = repeats;
-    publish_timing(ac, t);
+    publish_event_timing(ac, sc, t, 1, 1, 2, 2, 3);
   }
-  if (*n_hits > cap) {
-    tls_err = "output buffer too small";
-    return AHA_E_CAPACITY;
-  }
-  return AHA_OK;
+  return fits();
 }
 
 // ---- count calls (aha_ac_count_batch*) ------------------------------------------------------------------------------
@@ -851,19 +874,9 @@ int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
 // hits before its start within its chunk, k_count_doc_offsets adds the chunks' bases), the scan, the chain pass.
 static int32_t count_two_pass(aha_ac *ac, Scratch *sc, MatchArgs M, hipStream_t s, uint64_t *n_hits, uint32_t repeats) {
   if (int32_t rcf = stage_folded(ac, sc, M, s)) return rcf;
-  M.chunk = ac->chunk;
-  // warm-up is Lmax-1 bytes per chunk: keep it a small fraction of the chunk
-  while (M.chunk < 8ull * ac->aut.max_key_len && M.chunk < (1u << 20)) M.chunk *= 2;
-  M.n_chunks = (M.n_bytes + M.chunk - 1) / M.chunk;
-  const uint64_t n_blocks = (M.n_chunks + kBlock - 1) / kBlock;
-  int32_t rc;
-  if ((rc = ensure_scratch(ac, sc, M.n_chunks, n_blocks, M.n_docs))) return rc;
-  M.counts = sc->d_counts;
-  M.leads = sc->d_leads;
-  M.blk_hits = sc->d_blk_hits;
-  M.blk_leads = sc->d_blk_leads;
-  M.docg = sc->d_docg;
-  M.totals = sc->d_totals;
+  two_pass_chunks(ac, M, ac->chunk, 8);  // warm-up is Lmax-1 bytes per chunk
+  uint64_t n_blocks;
+  if (int32_t rc = bind_two_pass(ac, sc, M, M.n_chunks, &n_blocks)) return rc;
   const bool prof = ac->profiling.load() && sc->ev_ready;
   if (M.kc_visits) HIPCHK(ac, hipMemsetAsync(M.kc_visits, 0, (size_t)ac->aut.n_keys * 8, s));
   // (a cover call: the offsets have been looked at by now -- device_count -- so the mask may be touched)
@@ -881,20 +894,14 @@ static int32_t count_two_pass(aha_ac *ac, Scratch *sc, MatchArgs M, hipStream_t 
   HIPCHK(ac, hipStreamSynchronize(s));
   *n_hits = sc->h_totals[0];
   if (prof) {
-    aha_timing t;
-    memset(&t, 0, sizeof(t));
-    t.struct_size = sizeof(t);
+    aha_timing t{};
     t.n_kernels = 3 + (M.kc_visits ? 1 : 0) + (M.doc_hit_off ? 1 : 0);
-    (void)hipEventElapsedTime(&t.ms_total, sc->ev[0], sc->ev[4]);
-    (void)hipEventElapsedTime(&t.ms_count, sc->ev[0], sc->ev[1]);
-    (void)hipEventElapsedTime(&t.ms_scan, sc->ev[1], sc->ev[3]);
-    (void)hipEventElapsedTime(&t.ms_write, sc->ev[3], sc->ev[4]);
     t.n_chunks = M.n_chunks;
     t.n_hits = *n_hits;
     t.engine = 1;
     t.chunk_bytes = M.chunk;
     t.repeats = repeats;
-    publish_timing(ac, t);
+    publish_event_timing(ac, sc, t, 1, 1, 3, -1, -1);
   }
   return AHA_OK;
 }
@@ -915,21 +922,7 @@ static int32_t count_single(aha_ac *ac, Scratch *sc, MatchArgs &M, hipStream_t s
   return rc;
 }
 
-static void *count_reserve(Scratch *sc, int i, size_t bytes) {
-  Buf &b = sc->cntbuf[i];
-  if (b.bytes < bytes) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.bytes = 0;
-    const size_t want = bytes + bytes / 4 + 4096;
-    if (hipMalloc(&b.p, want) != hipSuccess) {
-      (void)hipGetLastError();
-      return nullptr;
-    }
-    b.bytes = want;
-  }
-  return b.p;
-}
+static void *count_reserve(Scratch *sc, CountSlot slot, size_t bytes) { return reserve_ptr(sc->cntbuf[slot], bytes, kGrowQuarter); }
 
 // A batch whose full-size regions are beyond the bound or cannot be allocated (HBM held elsewhere): counted in ranges of whole
 // documents, one after another, each through the same pipeline -- the key counts add up in the caller's vector as they do
@@ -949,6 +942,11 @@ static int32_t count_ranges(aha_ac *ac, Scratch *sc, const MatchArgs &M0, hipStr
   HIPCHK(ac, hipStreamSynchronize(s));
   uint64_t limit = std::max<uint64_t>(M0.n_bytes / 2, 1), base = 0;
   uint32_t ranges = 0;
+  int32_t rc;
+  auto nomem = [] {
+    tls_err = "hipMalloc failed for a document range of a count call";
+    return AHA_E_HIP;
+  };
   // a cover call: the ranges share one mask (they run one after another on the stream, so a word two of them touch is safe);
   // it is cleared once, here -- the offsets have been validated
   if (M0.cover_mask) HIPCHK(ac, hipMemsetAsync(M0.cover_mask, 0, (size_t)((M0.n_bytes + 31) / 32) * 4, s));
@@ -963,65 +961,40 @@ static int32_t count_ranges(aha_ac *ac, Scratch *sc, const MatchArgs &M0, hipStr
       return AHA_E_NOMEM;
     }
     for (uint64_t d = 0; d <= nd; d++) rel[d] = off[d0 + d] - off[d0];
-    uint64_t *d_rel = (uint64_t *)count_reserve(sc, 0, (nd + 1) * 8);
-    uint64_t *d_dho = M0.doc_hit_off ? (uint64_t *)count_reserve(sc, 2, (nd + 1) * 8) : nullptr;
-    if (!d_rel || (M0.doc_hit_off && !d_dho)) {
-      tls_err = "hipMalloc failed for a document range of a count call";
-      return AHA_E_HIP;
-    }
+    uint64_t *d_rel = (uint64_t *)count_reserve(sc, kCntRel, (nd + 1) * 8);
+    uint64_t *d_dho = M0.doc_hit_off ? (uint64_t *)count_reserve(sc, kCntDho, (nd + 1) * 8) : nullptr;
+    if (!d_rel || (M0.doc_hit_off && !d_dho)) return nomem();
     HIPCHK(ac, hipMemcpyAsync(d_rel, rel.data(), (nd + 1) * 8, hipMemcpyHostToDevice, s));
-    const uint8_t *text = M0.text + off[d0];
-    // (the kernels read aligned 16-byte pieces; a folded handle whose text is still the caller's: an unaligned range is folded
-    // on the way, an aligned one stays the caller's -- the prefix-filter engine folds in its loads, the others stage it)
-    int32_t range_fold = M0.fold;
-    if (nb && reinterpret_cast<uintptr_t>(text) % 16 != 0) {
-      uint8_t *t = (uint8_t *)count_reserve(sc, 1, nb + 64);
-      if (!t) {
-        tls_err = "hipMalloc failed for a document range of a count call";
-        return AHA_E_HIP;
-      }
-      if (M0.fold) {
-        fold_launch_copy(text, t, nb, 8u * std::max<uint32_t>(ac->v2_grid, 64u), s);
-        HIPCHK(ac, hipGetLastError());
-      } else {
-        HIPCHK(ac, hipMemcpyAsync(t, text, nb, hipMemcpyDeviceToDevice, s));
-      }
-      text = t;
-      range_fold = 0;
+    // the range as a batch of its own
+    MatchArgs Mr = M0;
+    Mr.text = M0.text + off[d0];
+    Mr.doc_off = d_rel;
+    Mr.n_docs = nd;
+    Mr.n_bytes = nb;
+    Mr.doc_hit_off = d_dho;
+    Mr.check_docs = 0;
+    Mr.cover_bit0 = M0.cover_bit0 + off[d0];
+    Mr.cover_clear = 0;
+    // (a folded handle whose text is still the caller's: an unaligned range is folded on the way, an aligned one stays the
+    // caller's -- the prefix-filter engine folds in its loads, the others stage it)
+    if (nb && reinterpret_cast<uintptr_t>(Mr.text) % 16 != 0) {
+      void *t = count_reserve(sc, kCntText, nb + 64);
+      if (!t) return nomem();
+      if ((rc = stage_text(ac, &Mr.text, nb, t, M0.fold != 0, s))) return rc;
+      Mr.fold = 0;
     }
-    MatchArgs M = M0;
-    M.fold = range_fold;
-    M.text = text;
-    M.doc_off = d_rel;
-    M.n_docs = nd;
-    M.n_bytes = nb;
-    M.doc_hit_off = d_dho;
-    M.check_docs = 0;
-    M.cover_bit0 = M0.cover_bit0 + off[d0];
-    M.cover_clear = 0;
     uint64_t nh = 0;
-    int32_t rc = AHA_OK;
+    rc = AHA_OK;
     if (nb == 0) {
       if (d_dho) HIPCHK(ac, hipMemsetAsync(d_dho, 0, (nd + 1) * 8, s));
     } else {
+      MatchArgs M = Mr;  // (a pass changes its arguments: the two-pass engine gets the range's own)
       rc = count_single(ac, sc, M, s, &nh);
       if (rc == 4 && nd > 1) {  // nothing was launched: the same documents in smaller ranges
         limit = std::max<uint64_t>(limit / 2, 1);
         continue;
       }
-      if (rc == 4 || rc == 1) {
-        M = M0;
-        M.fold = range_fold;
-        M.text = text;
-        M.doc_off = d_rel;
-        M.n_docs = nd;
-        M.n_bytes = nb;
-        M.doc_hit_off = d_dho;
-        M.check_docs = 0;
-        M.cover_bit0 = M0.cover_bit0 + off[d0];
-        M.cover_clear = 0;
-        rc = count_two_pass(ac, sc, M, s, &nh, 1);
-      }
+      if (rc == 4 || rc == 1) rc = count_two_pass(ac, sc, Mr, s, &nh, 1);
     }
     if (rc != AHA_OK) return rc;
     if (d_dho) {
@@ -1051,10 +1024,7 @@ int32_t device_count(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
                      uint64_t n_bytes, const aha_match_params *params, uint32_t flags, uint64_t *d_key_counts,
                      uint64_t *d_doc_hit_offsets, uint64_t *n_hits, void *stream, bool offsets_checked, uint32_t *cover_mask) {
   if (!ac || !n_hits || !d_doc_offsets) return AHA_E_INVALID;
-  if (ac->device < 0) {
-    tls_err = aha_strerror(AHA_E_NO_DEVICE);
-    return AHA_E_NO_DEVICE;
-  }
+  if (ac->device < 0) return no_device();
   if (flags & ~AHA_COUNT_ACCUMULATE) return AHA_E_INVALID;
   DeviceGuard g(ac->device);
   hipStream_t s = (hipStream_t)stream;
@@ -1062,7 +1032,7 @@ int32_t device_count(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
   int longest = 0;
   int32_t rc = fill_params(ac, params, M, &longest);
   if (rc) return rc;
-  if (longest) {
+  if (longest) {  // (the entry points refuse it with their own texts before any device work: capi.cpp no_longest_form)
     tls_err = "count calls have no match_longest form";
     return AHA_E_INVALID;
   }
@@ -1083,18 +1053,7 @@ int32_t device_count(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
     return AHA_OK;
   }
   if (!d_corpus) return AHA_E_INVALID;
-  if (reinterpret_cast<uintptr_t>(d_corpus) % 16 != 0) {
-    if (ac->fold()) {  // (folded on the way: the one pass does both jobs)
-      if ((rc = fold_into_scratch(ac, sc, d_corpus, n_bytes, s, &d_corpus))) return rc;
-    } else {
-      if ((rc = v2_reserve(ac, sc, 17, n_bytes + 64))) return rc;
-      HIPCHK(ac, hipMemcpyAsync(sc->v2buf[17].p, d_corpus, n_bytes, hipMemcpyDeviceToDevice, s));
-      d_corpus = (const uint8_t *)sc->v2buf[17].p;
-    }
-  } else if (ac->fold()) {
-    M.fold = 1;  // (the caller's text, aligned: the prefix-filter engine reads it where it lies, the others stage it)
-  }
-  M.text = d_corpus;
+  if ((rc = take_text(ac, sc, d_corpus, n_bytes, M, s))) return rc;
   M.doc_off = d_doc_offsets;
   M.n_docs = n_docs;
   M.n_bytes = n_bytes;
@@ -1109,8 +1068,8 @@ int32_t device_count(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
     if (M.sep) {
       M.kc_hits = M.kc_out;  // (a test per hit: straight into the caller's counts)
     } else {
-      if ((rc = v2_reserve(ac, sc, 25, (size_t)std::max<uint32_t>(K, 1) * 8))) return rc;
-      M.kc_visits = (unsigned long long *)sc->v2buf[25].p;
+      if ((rc = v2_reserve(sc, kKeyVisits, (size_t)std::max<uint32_t>(K, 1) * 8))) return rc;
+      M.kc_visits = (unsigned long long *)sc->v2buf[kKeyVisits].p;
     }
   }
   if (single) {
@@ -1140,20 +1099,7 @@ int32_t device_cover(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
                      uint64_t n_bytes, const aha_match_params *params, uint32_t flags, uint32_t *d_mask, uint8_t *d_redacted,
                      uint8_t fill, uint64_t *d_doc_covered, uint64_t *n_covered, uint64_t *n_hits_out, void *stream, bool offsets_checked) {
   if (!ac || !n_covered || !d_doc_offsets || flags) return AHA_E_INVALID;
-  {
-    MatchArgs M{};
-    int longest = 0;
-    int32_t rc0 = fill_params(ac, params, M, &longest);
-    if (rc0) return rc0;
-    if (longest) {
-      tls_err = "cover calls have no match_longest form";
-      return AHA_E_INVALID;
-    }
-  }
-  if (ac->device < 0) {
-    tls_err = aha_strerror(AHA_E_NO_DEVICE);
-    return AHA_E_NO_DEVICE;
-  }
+  if (ac->device < 0) return no_device();
   DeviceGuard g(ac->device);
   hipStream_t s = (hipStream_t)stream;
   *n_covered = 0;
@@ -1164,8 +1110,8 @@ int32_t device_cover(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
     return AHA_E_HIP;
   };
   uint32_t *mask = d_mask;
-  if (!mask && n_words && !(mask = (uint32_t *)cover_reserve(sc, 0, n_words * 4))) return nomem();
-  uint64_t *d_total = (uint64_t *)cover_reserve(sc, 2, 8);
+  if (!mask && n_words && !(mask = (uint32_t *)cover_reserve(sc, kCovMask, n_words * 4))) return nomem();
+  uint64_t *d_total = (uint64_t *)cover_reserve(sc, kCovTotal, 8);
   if (!d_total) return nomem();
   int32_t rc;
   uint64_t n_hits = 0;
@@ -1199,22 +1145,9 @@ int32_t device_cover(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
 }
 
 // ---- document counts (aha_ac_doc_counts_batch*) ----------------------------------------------------------------------
-static void *dc_reserve(Scratch *sc, int i, size_t bytes) {
-  Buf &b = sc->dcbuf[i];
-  if (b.bytes < bytes) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.bytes = 0;
-    if (i == 6) sc->dc_rows_clear = false;
-    const size_t want = bytes + bytes / 8 + 256;
-    if (hipMalloc(&b.p, want) != hipSuccess && ((void)hipGetLastError(), hipMalloc(&b.p, bytes) != hipSuccess)) {
-      (void)hipGetLastError();
-      b.p = nullptr;
-      return nullptr;
-    }
-    b.bytes = bytes;  // (what is known to be there)
-  }
-  return b.p;
+static void *dc_reserve(Scratch *sc, DocCountSlot slot, size_t bytes) {
+  if (slot == kDcRows && sc->dcbuf[slot].bytes < bytes) sc->dc_rows_clear = false;  // (new rows: nothing is known about their words)
+  return reserve_ptr(sc->dcbuf[slot], bytes, kGrowOrExact);
 }
 
 // One device-resident batch as {key, count} pairs per document (aha_ac_doc_counts_batch_device).
@@ -1229,20 +1162,7 @@ int32_t device_doc_counts(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, cons
                           uint64_t n_bytes, const aha_match_params *params, aha_key_count *d_out, uint64_t cap,
                           uint64_t *d_doc_pair_offsets, uint64_t *n_pairs, uint64_t *n_hits_out, void *stream, bool offsets_checked) {
   if (!ac || !n_pairs || !d_doc_offsets) return AHA_E_INVALID;
-  {
-    MatchArgs M{};
-    int longest = 0;
-    int32_t rc0 = fill_params(ac, params, M, &longest);
-    if (rc0) return rc0;
-    if (longest) {
-      tls_err = "document counts have no match_longest form";
-      return AHA_E_INVALID;
-    }
-  }
-  if (ac->device < 0) {
-    tls_err = aha_strerror(AHA_E_NO_DEVICE);
-    return AHA_E_NO_DEVICE;
-  }
+  if (ac->device < 0) return no_device();
   if (cap && !d_out) return AHA_E_INVALID;
   DeviceGuard g(ac->device);
   hipStream_t s = (hipStream_t)stream;
@@ -1260,7 +1180,7 @@ int32_t device_doc_counts(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, cons
     return AHA_E_HIP;
   };
   int32_t rc;
-  uint64_t *d_dho = (uint64_t *)dc_reserve(sc, 0, (D + 1) * 8);
+  uint64_t *d_dho = (uint64_t *)dc_reserve(sc, kDcHitOff, (D + 1) * 8);
   if (!d_dho) return nomem();
   uint64_t n_hits = 0;
   if ((rc = device_count(ac, sc, d_corpus, d_doc_offsets, D, n_bytes, p, 0, nullptr, d_dho, &n_hits, stream, offsets_checked))) return rc;
@@ -1325,21 +1245,20 @@ int32_t device_doc_counts(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, cons
         return AHA_E_NOMEM;
       }
       for (uint64_t d = 0; d <= nd; d++) rel[d] = off[d0 + d] - off[d0];
-      uint64_t *r = (uint64_t *)dc_reserve(sc, 2, (nd + 1) * 8);
+      uint64_t *r = (uint64_t *)dc_reserve(sc, kDcRel, (nd + 1) * 8);
       if (!r) return nomem();
       HIPCHK(ac, hipMemcpyAsync(r, rel.data(), (nd + 1) * 8, hipMemcpyHostToDevice, s));
       d_rel = r;
       text = d_corpus + off[d0];
       // (the kernels read aligned 16-byte pieces; a folded handle's match and count make their own folded -- and aligned -- copy)
       if (!ac->fold() && reinterpret_cast<uintptr_t>(text) % 16 != 0) {
-        uint8_t *t = (uint8_t *)dc_reserve(sc, 3, nb + 64);
+        void *t = dc_reserve(sc, kDcText, nb + 64);
         if (!t) return nomem();
-        HIPCHK(ac, hipMemcpyAsync(t, text, nb, hipMemcpyDeviceToDevice, s));
-        text = t;
+        if ((rc = stage_text(ac, &text, nb, t, false, s))) return rc;
       }
       HIPCHK(ac, hipStreamSynchronize(s));  // (rel is the host's until the copy has run)
     }
-    uint32_t *d_np = (uint32_t *)dc_reserve(sc, 5, nd * 4);
+    uint32_t *d_np = (uint32_t *)dc_reserve(sc, kDcPairsPerDoc, nd * 4);
     if (!d_np) return nomem();
     HIPCHK(ac, hipMemsetAsync(d_np, 0, nd * 4, s));
     try {
@@ -1351,9 +1270,9 @@ int32_t device_doc_counts(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, cons
     }
     const auto t_m0 = std::chrono::steady_clock::now();
     if (solo) {
-      unsigned long long *row = (unsigned long long *)dc_reserve(sc, 9, std::max<uint64_t>(K, 1) * 8);
-      uint32_t *tmp = (uint32_t *)dc_reserve(sc, 7, std::max<uint64_t>(K, 1) * 8);
-      DcItem *d_items = (DcItem *)dc_reserve(sc, 4, sizeof(DcItem));
+      unsigned long long *row = (unsigned long long *)dc_reserve(sc, kDcSoloRow, std::max<uint64_t>(K, 1) * 8);
+      uint32_t *tmp = (uint32_t *)dc_reserve(sc, kDcRangePairs, std::max<uint64_t>(K, 1) * 8);
+      DcItem *d_items = (DcItem *)dc_reserve(sc, kDcItems, sizeof(DcItem));
       if (!row || !tmp || !d_items) return nomem();
       uint64_t got = 0;
       if ((rc = device_count(ac, sc, text, d_rel, 1, nb, p, 0, (uint64_t *)row, nullptr, &got, stream, true))) return rc;
@@ -1363,7 +1282,7 @@ int32_t device_doc_counts(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, cons
       doccount_launch_compact64(d_items, row, (uint32_t)K, d_np, s);
       srcs[0] = tmp;
     } else {
-      aha_hit *d_hits = (aha_hit *)dc_reserve(sc, 1, rh * sizeof(aha_hit));
+      aha_hit *d_hits = (aha_hit *)dc_reserve(sc, kDcHits, rh * sizeof(aha_hit));
       if (!d_hits) return nomem();
       uint64_t got = 0;
       rc = device_match(ac, sc, text, d_rel, nd, nb, p, d_hits, rh, nullptr, &got, stream, true, nullptr, nullptr, false, true);
@@ -1386,10 +1305,10 @@ int32_t device_doc_counts(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, cons
       }
       const uint64_t rows_max = std::max<uint64_t>(1, ac->dc_row_bytes / (std::max<uint64_t>(K, 1) * 4));
       const uint64_t n_rows = std::min<uint64_t>(n_form[2], rows_max);
-      uint32_t *d_rtmp = range_pairs ? (uint32_t *)dc_reserve(sc, 7, range_pairs * 8) : nullptr;
-      uint32_t *d_rows = n_rows ? (uint32_t *)dc_reserve(sc, 6, n_rows * K * 4) : nullptr;
+      uint32_t *d_rtmp = range_pairs ? (uint32_t *)dc_reserve(sc, kDcRangePairs, range_pairs * 8) : nullptr;
+      uint32_t *d_rows = n_rows ? (uint32_t *)dc_reserve(sc, kDcRows, n_rows * K * 4) : nullptr;
       if ((range_pairs && !d_rtmp) || (n_rows && !d_rows)) return nomem();
-      if (n_rows && !sc->dc_rows_clear) HIPCHK(ac, hipMemsetAsync(d_rows, 0, sc->dcbuf[6].bytes, s));
+      if (n_rows && !sc->dc_rows_clear) HIPCHK(ac, hipMemsetAsync(d_rows, 0, sc->dcbuf[kDcRows].bytes, s));
       const size_t o_range = n_form[0], o_dense = o_range + n_form[1], o_slice = o_dense + n_form[2];
       try {
         items.resize(o_slice + n_slices);
@@ -1416,7 +1335,7 @@ int32_t device_doc_counts(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, cons
         }
         items[at[f]++] = DcItem{b, out, (uint32_t)h, (uint32_t)d};
       }
-      DcItem *d_items = (DcItem *)dc_reserve(sc, 4, std::max<size_t>(items.size(), 1) * sizeof(DcItem));
+      DcItem *d_items = (DcItem *)dc_reserve(sc, kDcItems, std::max<size_t>(items.size(), 1) * sizeof(DcItem));
       if (!d_items) return nomem();
       HIPCHK(ac, hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(DcItem), hipMemcpyHostToDevice, s));
       doccount_launch_sort(d_items, n_form[0], d_hits, d_np, s);
@@ -1449,7 +1368,7 @@ int32_t device_doc_counts(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, cons
     }
     const uint64_t room = cap > total ? cap - total : 0, n_write = std::min<uint64_t>(room, rel[nd]);
     if (n_write) {
-      uint64_t *d_po = (uint64_t *)dc_reserve(sc, 8, (nd + 1) * 8 + nd * sizeof(uint32_t *));
+      uint64_t *d_po = (uint64_t *)dc_reserve(sc, kDcGather, (nd + 1) * 8 + nd * sizeof(uint32_t *));
       if (!d_po) return nomem();
       const uint32_t **d_src = reinterpret_cast<const uint32_t **>(d_po + nd + 1);
       HIPCHK(ac, hipMemcpyAsync(d_po, rel.data(), (nd + 1) * 8, hipMemcpyHostToDevice, s));

@@ -27,6 +27,73 @@ struct Buf {
   void *p = nullptr;
   size_t bytes = 0;
 };
+// ---- the grow-only device buffers of a scratch set, by family; every slot has a name (a wrong index is silent corruption)
+// v2buf: one pass of the single-traversal engines (engine.cpp plan_v2 sizes them, launch_v2 binds them)
+enum V2Slot {
+  kEv,           // slab pipeline: the events as the traversal leaves them
+  kSortedEv,     // slab pipeline: the events in chunk order
+  kSortedCnt,    // slab pipeline: hits per sorted event
+  kSlabUsed,     // slab pipeline: events per slab
+  kEvCnt,        // events per chunk
+  kDocEvRank,    // per document: its first event's rank
+  kEvBase,       // events before every chunk
+  kBlkA,         // block sums of the scans
+  kBlkB,         // ... and their second array
+  kCursor,       // TWO blocks of 16 counter words and a third of odd words (Scratch::cursor_*); a new buffer resets the cursor
+  kEvAux,        // char offsets, slab pipeline: the events' lead counts
+  kSortedAux,    // ... in chunk order
+  kLeadCnt,      // char offsets: continuation bytes per chunk; the pair engine: its tiles' counts
+  kChunkDoc0,    // char offsets / pair engine: every chunk's first document
+  kDocLeadRank,  // char offsets: per document, the lead count before it
+  kLeadBase,     // char offsets: lead counts before every chunk
+  kEvRegions,    // region pipelines: the chunks' event regions, 8 bytes per event
+  kText,         // the aligned and / or folded copy of a caller's text (stage_text)
+  kChunkHits,    // region pipelines: hits per chunk
+  kHitBase,      // region pipelines: hits before every chunk
+  kDocHitRank,   // character-level engine: per document, its first hit's rank
+  kEvGroups,     // character-level engine: the wave-ordered events, 12 bytes each
+  kEngineA,      // the filter's candidate bitmap / the skip engine's marks / the pair engine's tile records
+  kEngineB,      // the filter's chunk records / the pair engine's candidates
+  kEngineC,      // the pair engine's deep walks
+  kKeyVisits,    // count calls: events per head key (device_count)
+  kV2Count
+};
+// hostbuf: device staging of the host-buffer entry points (capi.cpp)
+enum HostSlot {
+  kHostCorpus,   // the text (a cover call redacts it in place)
+  kHostDocs,     // the document offsets, relative to their range
+  kHostOffsets,  // what comes back per document: hit offsets, pair offsets, covered bytes
+  kHostOut,      // what comes back per call: hits, key counts, pairs, the mask
+  kHostCount
+};
+// cntbuf: count calls in document ranges (engine.cpp count_ranges)
+enum CountSlot {
+  kCntRel,   // the range's document offsets, relative to its first byte
+  kCntText,  // the aligned copy of an unaligned range
+  kCntDho,   // the range's hit offsets
+  kCntCount
+};
+// dcbuf: document counts (engine.cpp device_doc_counts)
+enum DocCountSlot {
+  kDcHitOff,      // the documents' hit offsets (the count call in front)
+  kDcHits,        // a range's hits
+  kDcRel,         // the range's document offsets, relative to its first byte
+  kDcText,        // the aligned copy of an unaligned range
+  kDcItems,       // the work items
+  kDcPairsPerDoc, // pairs per document
+  kDcRows,        // the dense form's rows; a new buffer is not known to be clear (Scratch::dc_rows_clear)
+  kDcRangePairs,  // the range form's pairs
+  kDcGather,      // pair offsets + sources of the gather
+  kDcSoloRow,     // one document's key counts (a document beyond the hit buffer's bound)
+  kDcCount
+};
+// covbuf: cover calls (engine.cpp device_cover)
+enum CoverSlot {
+  kCovMask,       // the mask where the caller gives none
+  kCovChunkDoc,   // the chunks' first documents
+  kCovTotal,      // the total
+  kCovCount
+};
 // Device scratch of ONE match call (grow-only, reused by later calls that lease the same set).
 struct Scratch {
   std::mutex mu;  // held by the call that leased the set
@@ -36,23 +103,35 @@ struct Scratch {
   uint64_t *h_totals = nullptr;  // pinned
   hipEvent_t ev[6] = {};
   bool ev_ready = false;
-  Buf v2buf[26];
-  Buf hostbuf[4];
-  Buf cntbuf[3];   // count calls in document ranges (engine.cpp count_ranges): relative offsets, an aligned text, offsets  // device staging of the host-buffer entry points (corpus, doc offsets, doc hit offsets, hits)
-  // document counts (engine.cpp device_doc_counts): 0 hit offsets, 1 hits, 2 relative offsets, 3 an aligned text, 4 work items,
-  // 5 pairs per document, 6 dense rows, 7 the range form's pairs, 8 pair offsets + sources of the gather, 9 one document's key counts
-  Buf dcbuf[10];
-  Buf covbuf[3];   // cover calls (engine.cpp device_cover): 0 the mask where the caller gives none, 1 the chunks' first documents, 2 the total
-  bool dc_rows_clear = false;  // every word of dcbuf[6] is zero (kdc_compact clears what kdc_add wrote; a call that failed may not have)
+  Buf v2buf[kV2Count];
+  Buf hostbuf[kHostCount];
+  Buf cntbuf[kCntCount];
+  Buf dcbuf[kDcCount];
+  Buf covbuf[kCovCount];
+  // every family above, for free_scratch and scratch_bytes (S: Scratch or const Scratch): a new family is one more line here
+  template <class S, class Fn>
+  static void each_buf(S &sc, Fn fn) {
+    for (auto &b : sc.v2buf) fn(b);
+    for (auto &b : sc.hostbuf) fn(b);
+    for (auto &b : sc.cntbuf) fn(b);
+    for (auto &b : sc.dcbuf) fn(b);
+    for (auto &b : sc.covbuf) fn(b);
+  }
+  bool dc_rows_clear = false;  // every word of dcbuf[kDcRows] is zero (kdc_compact clears what kdc_add wrote; a call that failed may not have)
   hipStream_t hs[3] = {};  // host-buffer entry: private non-blocking streams for upload, match, download
   unsigned long long *h_v2 = nullptr;  // pinned: cursor[2] + totals[3]
   unsigned long long *h_v2_dev = nullptr;  // the same words as the device addresses them
-  // v2buf[9] holds TWO blocks of 16 counter words (and a third of odd words): a call counts in one of them, and its last kernel
+  // v2buf[kCursor] holds TWO blocks of 16 counter words (and a third of odd words): a call counts in one of them, and its last kernel
   // clears the other for the call behind it -- no memset in front of a call (5 us of a 64 MiB call).  Dirty: the blocks are
   // not known to be clear (new buffer, a call that did not run to its end): the next call clears both itself.
   const void *cursor_buf = nullptr;
   bool cursor_dirty = true;
   uint32_t cursor_phase = 0;
+  void reset_cursor() {
+    cursor_buf = nullptr;
+    cursor_dirty = true;
+    cursor_phase = 0;
+  }
 };
 constexpr size_t kCursorBytes = 3 * 16 * 8;
 constexpr size_t kMaxScratch = 8;
@@ -179,8 +258,22 @@ class Lease {
   Scratch *wait_ = nullptr;
 };
 
+// a match entry point on a handle without a device (or where there is none): the error and its text
+inline int32_t no_device() {
+  tls_err = aha_strerror(AHA_E_NO_DEVICE);
+  return AHA_E_NO_DEVICE;
+}
 void free_scratch(Scratch *sc, bool all);
 uint64_t scratch_bytes(const Scratch *sc);
+// THE allocator of the grow-only buffers: b holds at least `bytes` afterwards, or nothing (the HIP error is returned, the
+// runtime's sticky one cleared).  What a new buffer gets beyond `bytes` is its family's rule:
+enum Grow {
+  kGrowEighth,   // bytes + bytes / 8 + 256 (v2buf, covbuf)
+  kGrowQuarter,  // bytes + bytes / 4 + 4096 (cntbuf, hostbuf)
+  kGrowOrExact   // an eighth, else exactly `bytes`; `bytes` is what it records (dcbuf: what is known to be there)
+};
+hipError_t reserve(Buf &b, size_t bytes, Grow grow);
+inline void *reserve_ptr(Buf &b, size_t bytes, Grow grow) { return reserve(b, bytes, grow) == hipSuccess ? b.p : nullptr; }  // null: no memory
 // adds the passes that were thrown away to the timing the last pass published (profiling on)
 void note_repeats(aha_ac *ac, uint32_t repeats);
 void publish_timing(aha_ac *ac, const aha_timing &t);

@@ -1,6 +1,6 @@
 """Call sequences on ONE handle, every call against the CPU oracle.
 
-A handle carries state from one call to the next: each leased scratch set keeps its buffers, and v2buf[9] holds two
+A handle carries state from one call to the next: each leased scratch set keeps its buffers, and v2buf[kCursor] holds two
 blocks of counter words -- a call counts in one of them and its last kernel clears the other for the call behind it
 (engine.cpp, match_v2); calls that do not publish leave the block dirty, hand-backs retry on the same set, and
 release_scratch frees the buffers.  The parity suite compiles fresh handles and makes a call or two on each, so none of
@@ -523,7 +523,7 @@ def test_release_resets_the_counter_block(monkeypatch):
     call()  # a publishing call: it clears the other half and leaves the block clean
     g.release_scratch()
     assert g.scratch_bytes() == 0
-    words = (3 * 16 * 8 + 3 * 16 * 8 // 8 + 256) // 8  # what v2_reserve(9, kCursorBytes) allocates: 688 bytes
+    words = (3 * 16 * 8 + 3 * 16 * 8 // 8 + 256) // 8  # what v2_reserve(kCursor, kCursorBytes) allocates: 688 bytes
     poison = np.zeros(words, dtype=np.uint64)
     poison[1] = poison[17] = 17
     bufs = [DeviceBuffer(0, words * 8) for _ in range(16)]
@@ -609,3 +609,203 @@ def test_separator_at_a_document_end_on_a_piece_boundary(variant, monkeypatch):
     assert rc == N.AHA_OK
     _check_np(out, n, want, n)
     _check_dho(dho, t.D, np.array(want_off, dtype=np.uint64))
+
+
+# ---- the scratch allocator's contract, family by family ---------------------------------------------------------------
+
+def _alloc_input():
+    """About 40 ASCII keys of 3 to 8 bytes in mixed case, a batch of 256 KiB in about 1000 documents, and its first half
+    (whole documents) as the smaller batch: whatever is cut into ranges of documents starts with the same ranges."""
+    rng = random.Random(77)
+    keys = set()
+    while len(keys) < 40:
+        keys.add("".join(rng.choice("abcdeFGH") for _ in range(rng.randint(3, 8))))
+    keys = sorted(keys)
+    words = keys + [k.swapcase() for k in keys[:10]] + ["zz", "q", "tuvwxyz", "0123", "mnop qr"]
+    docs, total = [], 0
+    while total < 256 << 10:
+        n = rng.randint(180, 345)
+        d = ""
+        while len(d) < n:
+            d += rng.choice(words) + rng.choice([" ", "", "-"])
+        docs.append(d[:n])
+        total += n
+    half, acc = 0, 0
+    while acc < total // 2:
+        acc += len(docs[half])
+        half += 1
+    return keys, Text(docs), Text(docs[:half])
+
+
+class _ModelAnswers:
+    """What every call kind returns for one batch, from ONE pass of tests/pymodel.py over its documents."""
+
+    def __init__(self, model, t, fold, n_keys):
+        from aha_amd.ac import HIT_DTYPE, KEY_COUNT_DTYPE
+
+        hits, pairs, self.dho, self.dpo = [], [], [0], [0]
+        covered = np.zeros(t.corpus.size, dtype=np.bool_)
+        self.doc_covered = np.zeros(t.D, dtype=np.uint64)
+        for d, doc in enumerate(t.docs):
+            h = model.match(doc.lower() if fold else doc, chars=False)
+            base = int(t.offs[d])
+            for s, e, _ in h:
+                covered[base + s:base + e] = True
+            self.doc_covered[d] = covered[base:base + len(doc)].sum()
+            hits += h
+            per_key = np.bincount([v for _, _, v in h], minlength=n_keys)
+            pairs += [(k, int(c)) for k, c in enumerate(per_key) if c]
+            self.dho.append(len(hits))
+            self.dpo.append(len(pairs))
+        self.hits = np.array(hits, dtype=HIT_DTYPE)
+        self.pairs = np.array(pairs, dtype=KEY_COUNT_DTYPE)
+        self.key_counts = np.bincount(self.hits["value"], minlength=n_keys).astype(np.uint64)
+        self.dho = np.array(self.dho, dtype=np.uint64)
+        self.dpo = np.array(self.dpo, dtype=np.uint64)
+        self.n_covered = int(covered.sum())
+        self.mask = np.packbits(np.concatenate([covered, np.zeros(-covered.size % 32, dtype=np.bool_)]),
+                                bitorder="little").view(np.uint32)
+        self.redacted = np.where(covered, np.uint8(0x2A), t.corpus)
+
+
+_ALLOC = {}
+
+
+def _alloc_case(fold):
+    from pymodel import ModelAC
+
+    if "input" not in _ALLOC:
+        _ALLOC["input"] = _alloc_input()
+    keys, big, small = _ALLOC["input"]
+    if fold not in _ALLOC:
+        model = ModelAC([k.lower() for k in keys] if fold else keys)
+        _ALLOC[fold] = tuple(_ModelAnswers(model, t, fold, len(keys)) for t in (big, small))
+    return keys, (big, small), _ALLOC[fold]
+
+
+@pytest.mark.parametrize("fold", [False, True], ids=["plain", "fold_ascii"])
+def test_scratch_only_grows_in_every_call_family(fold, monkeypatch):
+    """The allocator's contract (capi.cpp reserve), for every family of scratch buffers a call kind touches: the result is
+    the model's, a second identical call and a call on a smaller batch leave scratch_bytes() as it is (the buffers only
+    grow), release_scratch() brings it to 0, and the call gives the right answer again on fresh buffers."""
+    import torch
+
+    keys, texts, answers = _alloc_case(fold)
+    for v in ENGINE_VARS + ("AHA_COUNT_REGION_BYTES", "AHA_DOCCOUNT_HIT_BYTES"):
+        monkeypatch.delenv(v, raising=False)
+    g = AC.compile(keys, fold_ascii=fold)
+    monkeypatch.setenv("AHA_DOCCOUNT_HIT_BYTES", "4096")  # (read when the handle is compiled: ranges of ~340 hits)
+    g_dc = AC.compile(keys, fold_ascii=fold)
+    monkeypatch.delenv("AHA_DOCCOUNT_HIT_BYTES")
+    K = len(keys)
+
+    def i64(a):
+        return a.cpu().numpy().astype(np.uint64)
+
+    def unaligned(t):
+        holder = torch.full((t.corpus.size + 64,), 0xEE, dtype=torch.uint8, device="cuda")
+        view = holder[1:1 + t.corpus.size]
+        view.copy_(t.dev()[0])
+        assert view.data_ptr() % 16 == 1
+        return view
+
+    def dev_match(h, t, a, view=None):
+        out = torch.full((len(a.hits) + 37, 3), S32, dtype=torch.int32, device="cuda")
+        dho = _dho_dev(t.D)
+        torch.cuda.synchronize()
+        n = h.match_batch_device(view if view is not None else t.dev()[0], t.dev()[1], out, dho)
+        _check_dev(out, n, a.hits, n)
+        _check_dho(dho, t.D, a.dho)
+
+    def dev_count(h, t, a, region_bytes=None):
+        kc = torch.full((K,), -1, dtype=torch.int64, device="cuda")
+        dho = _dho_dev(t.D)
+        torch.cuda.synchronize()
+        if region_bytes:  # (read by every pass: the full-size regions of more than a few documents do not fit)
+            monkeypatch.setenv("AHA_COUNT_REGION_BYTES", str(region_bytes))
+        try:
+            n = h.count_batch_device(t.dev()[0], t.dev()[1], kc, dho)
+        finally:
+            monkeypatch.delenv("AHA_COUNT_REGION_BYTES", raising=False)
+        assert n == len(a.hits) and np.array_equal(i64(kc), a.key_counts)
+        _check_dho(dho, t.D, a.dho)
+
+    def dev_doc_counts(h, t, a):
+        out = torch.full((len(a.pairs) + 5, 2), S32, dtype=torch.int32, device="cuda")
+        dpo = _dho_dev(t.D)
+        torch.cuda.synchronize()
+        n, nh = h.doc_counts_batch_device(t.dev()[0], t.dev()[1], out, dpo)
+        assert (n, nh) == (len(a.pairs), len(a.hits))
+        assert out[:n].cpu().numpy().tobytes() == a.pairs.tobytes() and bool((out[n:] == S32).all())
+        _check_dho(dpo, t.D, a.dpo)
+
+    def dev_cover(h, t, a, with_mask):
+        mask = torch.full((a.mask.size,), -1, dtype=torch.int32, device="cuda") if with_mask else None
+        red = torch.zeros(t.corpus.size, dtype=torch.uint8, device="cuda")
+        cov = torch.full((t.D,), -1, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        nc, nh = h.cover_batch_device(t.dev()[0], t.dev()[1], mask=mask, redacted=red, doc_covered=cov)
+        assert (nc, nh) == (a.n_covered, len(a.hits))
+        assert np.array_equal(red.cpu().numpy(), a.redacted) and np.array_equal(i64(cov), a.doc_covered)
+        if with_mask:
+            assert np.array_equal(mask.cpu().numpy().view(np.uint32), a.mask)
+
+    def host_match_count(h, t, a):
+        hits, dho = h.match_batch(t.corpus, t.offs, cap=len(a.hits) + 37)
+        assert hits.tobytes() == a.hits.tobytes() and np.array_equal(dho, a.dho)
+        kc, dho = h.count_batch(t.corpus, t.offs)
+        assert np.array_equal(kc, a.key_counts) and np.array_equal(dho, a.dho)
+
+    def host_doc_counts(h, t, a):
+        pairs, dpo = h.doc_counts_batch(t.corpus, t.offs)
+        assert pairs.tobytes() == a.pairs.tobytes() and np.array_equal(dpo, a.dpo)
+
+    def host_cover(h, t, a):
+        mask, cov = h.cover_batch(t.corpus, t.offs)
+        assert np.array_equal(mask, a.mask) and np.array_equal(cov, a.doc_covered)
+        red, cov = h.redact_batch(t.corpus, t.offs)
+        assert np.array_equal(red, a.redacted) and np.array_equal(cov, a.doc_covered)
+
+    views = {}
+
+    def dev_match_unaligned(h, t, a):
+        if id(t) not in views:
+            views[id(t)] = unaligned(t)
+        dev_match(h, t, a, views[id(t)])
+
+    # the kinds named after document ranges must take them: aha_timing.repeats counts a call's ranges before its last
+    in_ranges = {"count in document ranges", "doc counts, small hit buffer"}
+    g.set_profiling(True)
+    g_dc.set_profiling(True)
+    kinds = [
+        ("device match", g, dev_match),
+        ("device match, unaligned view", g, dev_match_unaligned),
+        ("count", g, dev_count),
+        ("count in document ranges", g, lambda h, t, a: dev_count(h, t, a, region_bytes=300_000)),
+        ("doc counts", g, dev_doc_counts),
+        ("doc counts, small hit buffer", g_dc, dev_doc_counts),
+        ("cover, caller's mask", g, lambda h, t, a: dev_cover(h, t, a, True)),
+        ("cover, no mask", g, lambda h, t, a: dev_cover(h, t, a, False)),
+        ("host match and count", g, host_match_count),
+        ("host doc counts", g, host_doc_counts),
+        ("host cover", g, host_cover),
+    ]
+    (big, small), (a_big, a_small) = texts, answers
+    assert len(a_big.hits) > 2 * big.D and len(a_small.hits) > 0
+    for name, h, call in kinds:
+        try:
+            h.release_scratch()
+            call(h, big, a_big)
+            grown = h.scratch_bytes()
+            assert grown > 0
+            if name in in_ranges:
+                assert h.last_timing()["repeats"] >= 1, "the batch was not cut into document ranges"
+            call(h, big, a_big)
+            assert h.scratch_bytes() == grown, "a second identical call allocated"
+            call(h, small, a_small)
+            assert h.scratch_bytes() == grown, "a smaller batch allocated"
+            h.release_scratch()
+            assert h.scratch_bytes() == 0
+            call(h, big, a_big)
+        except AssertionError as e:
+            raise AssertionError(f"{name}: {e}") from e

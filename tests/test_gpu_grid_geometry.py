@@ -63,7 +63,7 @@ def grids(geos, engines):
     return pytest.mark.parametrize("geometry,engine", [(g, e) for g in geos for e in engines], indirect=True)
 
 
-# ---- the planner's arithmetic (engine.cpp match_v2) ---------------------------------------------------------------
+# ---- the planner's arithmetic (engine.cpp plan_v2) ----------------------------------------------------------------
 
 def v2_chunk(n, grid, lmax):
     """The chunk of the byte-level, character-level and skip-ahead traversals: the batch over grid * 1024 lanes, rounded
