@@ -151,6 +151,10 @@ SIGNATURES = {
                                   C.POINTER(_u64), C.POINTER(_u64)]),
     "aha_ac_cover_batch_device": (_i32, [_vp, _vp, _vp, _u64, _u64, C.POINTER(aha_match_params), _u32, _vp, _vp, C.c_uint8, _vp,
                                          C.POINTER(_u64), C.POINTER(_u64), _vp]),
+    "aha_ac_select_batch": (_i32, [_vp, _vp, _vp, _u64, C.POINTER(aha_match_params), _u32, _vp, _u64, _vp, C.POINTER(_u64),
+                                   C.POINTER(_u64)]),
+    "aha_ac_select_batch_device": (_i32, [_vp, _vp, _vp, _u64, _u64, C.POINTER(aha_match_params), _u32, _vp, _u64, _vp,
+                                          C.POINTER(_u64), C.POINTER(_u64), _vp]),
     "aha_ac_count_batch": (_i32, [_vp, _vp, _vp, _u64, C.POINTER(aha_match_params), _u32, _vp, _vp, C.POINTER(_u64)]),
     "aha_ac_count_batch_device": (_i32, [_vp, _vp, _vp, _u64, _u64, C.POINTER(aha_match_params), _u32, _vp, _vp,
                                          C.POINTER(_u64), _vp]),

@@ -101,6 +101,43 @@ def _params(chars, sep, longest=0):
     return p
 
 
+def char_offsets_of(text, hits):
+    """The byte offsets of a HIT_DTYPE array over the UTF-8 bytes `text` as character offsets: the character index of a
+    byte offset is the number of lead bytes (anything but 0b10xxxxxx) in front of it -- a running count."""
+    t = np.frombuffer(bytes(text), dtype=np.uint8)
+    lead = np.zeros(t.size + 1, dtype=np.int64)
+    np.cumsum((t & 0xC0) != 0x80, out=lead[1:])
+    out = np.array(hits, dtype=HIT_DTYPE)
+    out["start"] = lead[np.asarray(hits["start"], dtype=np.int64)]
+    out["end"] = lead[np.asarray(hits["end"], dtype=np.int64)]
+    return out
+
+
+def _replacement_of(repl, key, n_keys):
+    if hasattr(repl, "keys"):
+        return repl.get(key)  # a mapping: keys it does not name stay as they are
+    if len(repl) != n_keys:
+        raise ValueError("repl must have one entry per key (%d), or be a mapping from key index" % n_keys)
+    return repl[key]
+
+
+def substitute(text, hits, repl, n_keys):
+    """`text` (bytes) with every hit of `hits` (ascending, non-overlapping byte offsets: a selection) replaced by
+    repl[hit.value]; repl: a mapping from key index to replacement (a key it does not name, or that maps to None, is left
+    as it is) or a sequence with one entry per key.  Replacements are bytes or str (UTF-8).  -> bytes"""
+    text = bytes(text)
+    parts, at = [], 0
+    for s, e, v in np.asarray(hits).tolist():
+        r = _replacement_of(repl, v, n_keys)
+        if r is None:
+            continue
+        parts.append(text[at:s])
+        parts.append(_b(r))
+        at = e
+    parts.append(text[at:])
+    return b"".join(parts)
+
+
 class AC:
     """Aha::AC (= ACX(Int32), src/aha/ac.cr:8-11) on the MI355X."""
 
@@ -552,6 +589,112 @@ class AC:
         self._check(rc)
         return (out.download(np.zeros(cap, dtype=KEY_COUNT_DTYPE)), dpo.download(np.zeros(D + 1, dtype=np.uint64)),
                 int(nh.value))
+
+    # -- select: leftmost-longest, non-overlapping hits per document (aha_ac_select_batch*) ----------
+    def select_batch(self, corpus, doc_offsets, sep=None, cap=None):
+        """Per document the leftmost-longest, non-overlapping hits of match_batch(corpus, doc_offsets, sep), byte offsets:
+        -> (hits HIT_DTYPE, doc_sel_offsets uint64[D+1]); hits[doc_sel_offsets[d]:doc_sel_offsets[d+1]] is document d's
+        selection, ascending by start.  cap None: a sizing call first."""
+        if isinstance(corpus, (bytes, bytearray)):
+            corpus = np.frombuffer(bytes(corpus), dtype=np.uint8)
+        corpus = np.ascontiguousarray(corpus, dtype=np.uint8)
+        doc_offsets = np.ascontiguousarray(doc_offsets, dtype=np.uint64)
+        D = doc_offsets.size - 1
+        p = _params(False, sep)
+        dso = np.zeros(D + 1, dtype=np.uint64)
+        n = C.c_uint64(0)
+        L = N.lib()
+        if cap is None:
+            rc = L.aha_ac_select_batch(self._h, _ptr(corpus), _ptr(doc_offsets), D, C.byref(p), 0, None, 0, _ptr(dso),
+                                       C.byref(n), None)
+            if rc != N.AHA_E_CAPACITY:
+                self._check(rc)
+                return np.zeros(0, dtype=HIT_DTYPE), dso
+            cap = int(n.value)
+        out = np.zeros(max(int(cap), 1), dtype=HIT_DTYPE)
+        rc = L.aha_ac_select_batch(self._h, _ptr(corpus), _ptr(doc_offsets), D, C.byref(p), 0, _ptr(out), int(cap), _ptr(dso),
+                                   C.byref(n), None)
+        if rc == N.AHA_E_CAPACITY:
+            e = AhaError(rc, N.lib().aha_strerror(rc).decode())
+            e.n_required = int(n.value)
+            raise e
+        self._check(rc)
+        return out[: int(n.value)], dso
+
+    def select_array(self, seq, sep=None):
+        """The selection of one sequence as a HIT_DTYPE array: byte offsets for bytes, character offsets for str (the select
+        runs over the UTF-8 bytes; the offsets are mapped here)."""
+        b = _b(seq)
+        hits, _ = self.select_batch(np.frombuffer(b, dtype=np.uint8), np.array([0, len(b)], dtype=np.uint64), sep=sep)
+        return char_offsets_of(b, hits) if isinstance(seq, str) else hits
+
+    def select(self, seq, sep=None):
+        """The leftmost-longest, non-overlapping hits of match(seq, sep) as a list of Hit, ascending by start."""
+        return [Hit(s, e, v) for s, e, v in self.select_array(seq, sep).tolist()]
+
+    def replace(self, seq, repl, sep=None):
+        """seq with every selected hit replaced by repl[hit.value]: repl is a mapping from key index to replacement (keys it
+        does not name stay) or a sequence with one entry per key.  bytes in, bytes out; str in, str out.  The copy is built
+        on the host from select."""
+        b = _b(seq)
+        hits, _ = self.select_batch(np.frombuffer(b, dtype=np.uint8), np.array([0, len(b)], dtype=np.uint64), sep=sep)
+        out = substitute(b, hits, repl, self.n_keys)
+        return out.decode("utf-8") if isinstance(seq, str) else out
+
+    def select_batch_device(self, corpus, doc_offsets, out, doc_sel_offsets=None, sep=None, cap=None, stream=None):
+        """Device-resident select on torch CUDA tensors: uint8 corpus, int64/uint64 doc offsets, out int32 [cap, 3]
+        ({start, end, value} rows) or None (a sizing call), doc_sel_offsets int64/uint64 [D+1] or None.
+        -> (n_selected, n_hits); raises AhaError(AHA_E_CAPACITY) when out is too small (e.n_required = the hits needed);
+        nothing is written then."""
+        import torch
+
+        assert corpus.is_cuda and corpus.dtype == torch.uint8 and corpus.is_contiguous()
+        assert doc_offsets.is_cuda and doc_offsets.dtype in (torch.int64, torch.uint64)
+        if out is not None:
+            if not (out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.dim() == 2 and out.shape[1] == 3):
+                raise ValueError("out must be a contiguous int32 CUDA tensor of shape [cap, 3]")
+            cap = out.shape[0] if cap is None else min(int(cap), out.shape[0])
+        else:
+            cap = 0
+        if doc_sel_offsets is not None and not (doc_sel_offsets.is_cuda and doc_sel_offsets.dtype in (torch.int64, torch.uint64)
+                                                and doc_sel_offsets.is_contiguous()
+                                                and doc_sel_offsets.numel() >= doc_offsets.numel()):
+            raise ValueError("doc_sel_offsets must be a contiguous int64/uint64 CUDA tensor of at least D + 1 entries")
+        D = doc_offsets.numel() - 1
+        p = _params(False, sep)
+        n, nh = C.c_uint64(0), C.c_uint64(0)
+        s = stream if stream is not None else torch.cuda.current_stream(corpus.device).cuda_stream
+        rc = N.lib().aha_ac_select_batch_device(
+            self._h, corpus.data_ptr(), doc_offsets.data_ptr(), D, corpus.numel(), C.byref(p), 0,
+            out.data_ptr() if out is not None and cap else None, cap,
+            doc_sel_offsets.data_ptr() if doc_sel_offsets is not None else None, C.byref(n), C.byref(nh), C.c_void_p(s))
+        if rc == N.AHA_E_CAPACITY:
+            e = AhaError(rc, N.lib().aha_strerror(rc).decode())
+            e.n_required = int(n.value)
+            raise e
+        self._check(rc)
+        return int(n.value), int(nh.value)
+
+    def select_corpus(self, corpus, sep=None):
+        """The selection of a batch that already lives in HBM (DeviceCorpus), downloaded:
+        -> (hits HIT_DTYPE, doc_sel_offsets uint64[D+1], n_hits)."""
+        D = corpus.n_docs
+        p = _params(False, sep)
+        dev = corpus.device
+        dso = DeviceBuffer(dev, (D + 1) * 8)
+        n, nh = C.c_uint64(0), C.c_uint64(0)
+        L = N.lib()
+        rc = L.aha_ac_select_batch_device(self._h, corpus.ptr, corpus.doc_ptr, D, corpus.n_bytes, C.byref(p), 0, None, 0,
+                                          dso.ptr, C.byref(n), C.byref(nh), None)
+        if rc != N.AHA_E_CAPACITY:
+            self._check(rc)
+            return np.zeros(0, dtype=HIT_DTYPE), dso.download(np.zeros(D + 1, dtype=np.uint64)), int(nh.value)
+        cap = int(n.value)
+        out = DeviceBuffer(dev, cap * 12)
+        rc = L.aha_ac_select_batch_device(self._h, corpus.ptr, corpus.doc_ptr, D, corpus.n_bytes, C.byref(p), 0, out.ptr, cap,
+                                          dso.ptr, C.byref(n), C.byref(nh), None)
+        self._check(rc)
+        return (out.download(np.zeros(cap, dtype=HIT_DTYPE)), dso.download(np.zeros(D + 1, dtype=np.uint64)), int(nh.value))
 
     # -- cover: which bytes lie inside a hit, and a redacted copy (aha_ac_cover_batch*) ---------------
     def _cover_host(self, corpus, doc_offsets, sep, want_mask, want_redacted, fill):

@@ -1359,6 +1359,62 @@ int32_t aha_ac_cover_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *do
   return AHA_OK;
 }
 
+// ---- select calls (aha_ac_select_batch*) ---------------------------------------------------------------------------
+// the argument checks both entries share: before any device work, so they hold on a host-only handle
+static int32_t select_args(aha_ac *ac, const uint64_t *doc_offsets, const aha_match_params *params, uint32_t flags,
+                           uint64_t *n_selected) {
+  if (!ac || !n_selected || !doc_offsets || flags) return AHA_E_INVALID;
+  if (int32_t rc = no_longest_form(ac, params, "select calls have no match_longest form")) return rc;
+  if (params && params->struct_size >= offsetof(aha_match_params, char_offsets) + sizeof(params->char_offsets) && params->char_offsets) {
+    tls_err = "select calls give byte offsets only";
+    return AHA_E_INVALID;
+  }
+  if (ac->device < 0) return no_device();
+  return AHA_OK;
+}
+
+int32_t aha_ac_select_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                                   uint64_t n_bytes, const aha_match_params *params, uint32_t flags, aha_hit *d_out, uint64_t cap,
+                                   uint64_t *d_doc_sel_offsets, uint64_t *n_selected, uint64_t *n_hits, void *stream) {
+  int32_t rc = select_args(ac, d_doc_offsets, params, flags, n_selected);
+  if (rc) return rc;
+  if (cap && !d_out) return AHA_E_INVALID;
+  Lease lease(ac);
+  return device_select(ac, lease.get(), d_corpus, d_doc_offsets, n_docs, n_bytes, params, d_out, cap, d_doc_sel_offsets, n_selected,
+                       n_hits, stream, false);
+}
+
+// The host entry: the batch goes up in one piece into the staging buffers of the leased scratch set, over its private stream;
+// the selection and the offsets come back once the call has succeeded.
+int32_t aha_ac_select_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc_offsets, uint64_t n_docs,
+                            const aha_match_params *params, uint32_t flags, aha_hit *out, uint64_t cap, uint64_t *doc_sel_offsets,
+                            uint64_t *n_selected, uint64_t *n_hits) {
+  int32_t rc = select_args(ac, doc_offsets, params, flags, n_selected);
+  if (rc) return rc;
+  if (cap && !out) return AHA_E_INVALID;
+  if ((rc = check_host_batch(corpus, doc_offsets, n_docs))) return rc;
+  const uint64_t n_bytes = doc_offsets[n_docs];
+  DeviceGuard g(ac->device);
+  Lease lease(ac);
+  Scratch *sc = lease.get();
+  HostBatch B;
+  if ((rc = stage_host_batch(ac, sc, corpus, doc_offsets, n_docs, (n_docs + 1) * 8, cap * sizeof(aha_hit), B))) return rc;
+  uint64_t *d_dso = (uint64_t *)B.d_per_doc;
+  aha_hit *d_out = (aha_hit *)B.d_per_call;
+  hipStream_t s = B.s;
+  uint64_t ns = 0, nh = 0;
+  rc = device_select(ac, sc, B.d_corpus, B.d_doc, n_docs, n_bytes, params, d_out, cap, d_dso, &ns, &nh, s,
+                     true);  // the offsets were checked on the host above
+  if (rc == AHA_E_CAPACITY) *n_selected = ns;
+  if (rc != AHA_OK) return rc;
+  if (ns) HIPCHK(ac, hipMemcpyAsync(out, d_out, ns * sizeof(aha_hit), hipMemcpyDeviceToHost, s));
+  if (doc_sel_offsets) HIPCHK(ac, hipMemcpyAsync(doc_sel_offsets, d_dso, (n_docs + 1) * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  *n_selected = ns;
+  if (n_hits) *n_hits = nh;
+  return AHA_OK;
+}
+
 // ---- device buffers behind the C ABI (include/aha_hip.h) ---------------------------------------------------------
 namespace {
 std::mutex g_copy_mu;

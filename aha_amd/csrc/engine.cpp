@@ -82,6 +82,8 @@ static void doccount_setup(aha_ac *ac) {
   ac->dc_range_keys = (uint32_t)env("AHA_DOCCOUNT_RANGE_KEYS", kDcRangeKeys, 1, kDcRangeKeys);
   // the dense form costs O(K) per document: from K / 8 hits on
   ac->dc_dense_min = (uint32_t)env("AHA_DOCCOUNT_DENSE_MIN", std::max<uint64_t>(ac->dc_sort_max + 1ull, K / 8), 1, 0x7FFFFFFFull);
+  // select calls: the bound of a range's hit buffer, by default the document counts' (device_select)
+  ac->sel_hit_bytes = env("AHA_SELECT_HIT_BYTES", ac->dc_hit_bytes, 12, kV2MaxRegionBytes);
 }
 
 void v2_setup(aha_ac *ac) {
@@ -1398,6 +1400,209 @@ int32_t device_doc_counts(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, cons
     t_trav.n_hits = n_hits;
     t_trav.ms_write = (float)std::max(0.0, ms - ms_match);
     t_trav.repeats = ranges ? ranges - 1 : 0;
+    publish_timing(ac, t_trav);
+  }
+  if (total > cap) {
+    tls_err = "output buffer too small";
+    return AHA_E_CAPACITY;
+  }
+  return AHA_OK;
+}
+
+// ---- select calls (aha_ac_select_batch*) -----------------------------------------------------------------------------
+static void *sel_reserve(Scratch *sc, SelectSlot slot, size_t bytes) { return reserve_ptr(sc->selbuf[slot], bytes, kGrowEighth); }
+
+// One device-resident batch selected (aha_ac_select_batch_device): per document the leftmost-longest, non-overlapping hits.
+//   1. device_count without key counts: the hits per document and their total, no capacity (and the offsets' validation).
+//   2. Ranges of whole documents whose hits fit the bound of the hit buffer (one range, as a rule; a document beyond the bound
+//      is alone with the hitless documents around it): a match of the range with cap = its hits into the call's scratch --
+//      every engine, the handle's back-off state read and never written.
+//   3. The passes of scan_select.hip over the range: L, the masks, the walk, the rank -- the range's total comes back.
+//   4. Once the call's total is known to fit: the selection to its place, then the documents' offsets.
+// A failing call writes none of the caller's buffers, so nothing is emitted before the total of ALL ranges is known: with one
+// range its L and select mask are still in scratch then; with more, the ranges are worked through a second time (steps 2 and 3
+// again, then the emit) -- the price of the rare case, instead of a second buffer of the selection's size.
+int32_t device_select(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                      uint64_t n_bytes, const aha_match_params *params, aha_hit *d_out, uint64_t cap, uint64_t *d_doc_sel_offsets,
+                      uint64_t *n_selected, uint64_t *n_hits_out, void *stream, bool offsets_checked) {
+  if (!ac || !n_selected || !d_doc_offsets) return AHA_E_INVALID;
+  if (ac->device < 0) return no_device();
+  if (cap && !d_out) return AHA_E_INVALID;
+  DeviceGuard g(ac->device);
+  hipStream_t s = (hipStream_t)stream;
+  const uint64_t D = n_docs;
+  *n_selected = 0;
+  if (n_hits_out) *n_hits_out = 0;
+  auto nomem = [&]() {
+    tls_err = "hipMalloc failed for the scratch of a select call";
+    return AHA_E_HIP;
+  };
+  int32_t rc;
+  uint64_t *d_dho = (uint64_t *)sel_reserve(sc, kSelHitOff, (D + 1) * 8);
+  uint64_t *d_dso = (uint64_t *)sel_reserve(sc, kSelDocOff, (D + 1) * 8);
+  if (!d_dho || !d_dso) return nomem();
+  uint64_t n_hits = 0;
+  if ((rc = device_count(ac, sc, d_corpus, d_doc_offsets, D, n_bytes, params, 0, nullptr, d_dho, &n_hits, stream, offsets_checked)))
+    return rc;
+  std::vector<uint64_t> off, hd, rel, bounds;
+  try {
+    hd.resize(D + 1);
+    bounds.push_back(0);
+  } catch (...) {
+    return AHA_E_NOMEM;
+  }
+  HIPCHK(ac, hipMemcpyAsync(hd.data(), d_dho, (D + 1) * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  const auto t_all0 = std::chrono::steady_clock::now();
+  double ms_match = 0.0;
+  aha_timing t_trav;  // the timing of a pass that traversed (profiling)
+  memset(&t_trav, 0, sizeof(t_trav));
+  if (ac->profiling.load()) {
+    std::lock_guard<std::mutex> lk(ac->last_mu);
+    t_trav = ac->last;
+  }
+  // the ranges: whole documents while their hits fit the bound; documents without a hit cost nothing and never stand alone
+  try {
+    for (uint64_t d0 = 0; n_hits && d0 < D;) {
+      uint64_t d1 = d0, bytes = 0;
+      while (d1 < D && (bytes == 0 || bytes + (hd[d1 + 1] - hd[d1]) * sizeof(aha_hit) <= ac->sel_hit_bytes)) {
+        bytes += (hd[d1 + 1] - hd[d1]) * sizeof(aha_hit);
+        d1++;
+      }
+      bounds.push_back(d1);
+      d0 = d1;
+    }
+    if (bounds.size() > 2 && hd[bounds.back()] == hd[bounds[bounds.size() - 2]]) bounds.erase(bounds.end() - 2);  // (a hitless tail)
+    if (bounds.size() > 2) {
+      off.resize(D + 1);
+      HIPCHK(ac, hipMemcpyAsync(off.data(), d_doc_offsets, (D + 1) * 8, hipMemcpyDeviceToHost, s));
+      HIPCHK(ac, hipStreamSynchronize(s));
+    }
+  } catch (...) {
+    return AHA_E_NOMEM;
+  }
+  const size_t n_ranges = bounds.size() - 1;  // 0: no hit at all
+  const uint32_t blocks = 8u * std::max<uint32_t>(ac->v2_grid, 64u);
+  uint64_t total = 0;
+  bool first_match = true;
+  // what a worked range leaves in scratch for the emit
+  struct Range {
+    const uint64_t *d_rel;
+    uint64_t nd, nb;
+    uint64_t *L, *blk;
+    uint32_t *select;
+  } R{};
+  // steps 2 and 3 for the documents [d0, d1); *sel = the range's selected hits
+  auto work = [&](uint64_t d0, uint64_t d1, uint64_t *sel) -> int32_t {
+    const uint64_t nd = d1 - d0, rh = hd[d1] - hd[d0];
+    const uint8_t *text = d_corpus;
+    const uint64_t *d_rel = d_doc_offsets;
+    uint64_t nb = n_bytes;
+    if (d0 != 0 || d1 != D) {  // the range as a batch of its own: the caller's arrays where it is the whole batch
+      nb = off[d1] - off[d0];
+      try {
+        rel.resize(nd + 1);
+      } catch (...) {
+        return AHA_E_NOMEM;
+      }
+      for (uint64_t d = 0; d <= nd; d++) rel[d] = off[d0 + d] - off[d0];
+      uint64_t *r = (uint64_t *)sel_reserve(sc, kSelRel, (nd + 1) * 8);
+      if (!r) return nomem();
+      HIPCHK(ac, hipMemcpyAsync(r, rel.data(), (nd + 1) * 8, hipMemcpyHostToDevice, s));
+      d_rel = r;
+      text = d_corpus + off[d0];
+      // (the kernels read aligned 16-byte pieces; a folded handle's match makes its own folded -- and aligned -- copy)
+      if (!ac->fold() && reinterpret_cast<uintptr_t>(text) % 16 != 0) {
+        void *t = sel_reserve(sc, kSelText, nb + 64);
+        if (!t) return nomem();
+        if ((rc = stage_text(ac, &text, nb, t, false, s))) return rc;
+      }
+      HIPCHK(ac, hipStreamSynchronize(s));  // (rel is the host's until the copy has run)
+    }
+    const uint64_t n_words = (nb + 31) / 32, n_blk = select_rank_blocks(nb);
+    aha_hit *d_hits = (aha_hit *)sel_reserve(sc, kSelHits, rh * sizeof(aha_hit));
+    uint64_t *L = (uint64_t *)sel_reserve(sc, kSelLongest, nb * 8);
+    uint32_t *masks = (uint32_t *)sel_reserve(sc, kSelMasks, 3 * n_words * 4);
+    uint64_t *blk = (uint64_t *)sel_reserve(sc, kSelBlocks, (n_blk + 1) * 8);
+    if (!d_hits || !L || !masks || !blk) return nomem();
+    const auto t_m0 = std::chrono::steady_clock::now();
+    uint64_t got = 0;
+    rc = device_match(ac, sc, text, d_rel, nd, nb, params, d_hits, rh, nullptr, &got, stream, true, nullptr, nullptr, false, true);
+    if (rc) return rc;
+    if (got != rh) {
+      tls_err = "select: the match and the count of a range disagree";
+      return AHA_E_HIP;
+    }
+    ms_match += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_m0).count();
+    if (ac->profiling.load() && first_match) {
+      std::lock_guard<std::mutex> lk(ac->last_mu);
+      t_trav = ac->last;
+    }
+    first_match = false;
+    uint32_t *cover = masks, *doc_start = masks + n_words, *select = masks + 2 * n_words;
+    HIPCHK(ac, hipMemsetAsync(L, 0, nb * 8, s));
+    HIPCHK(ac, hipMemsetAsync(masks, 0, 3 * n_words * 4, s));
+    select_launch_longest(d_hits, rh, d_dho + d0, d_rel, nd, nb, L, blocks, s);
+    select_launch_marks(L, nb, d_rel, nd, cover, doc_start, blocks, s);
+    select_launch_walk(L, nb, cover, doc_start, select, blocks, s);
+    select_launch_rank(select, nb, blk, blocks, s);
+    HIPCHK(ac, hipGetLastError());
+    HIPCHK(ac, hipMemcpyAsync(sel, blk + n_blk, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(ac, hipStreamSynchronize(s));
+    R = Range{d_rel, nd, nb, L, blk, select};
+    return AHA_OK;
+  };
+  auto emit = [&](uint64_t base) -> int32_t {
+    select_launch_emit(R.select, R.nb, R.blk, R.L, R.d_rel, R.nd, d_out + base, blocks, s);
+    HIPCHK(ac, hipGetLastError());
+    return AHA_OK;
+  };
+  // the count pass: every range's total, the documents' offsets into scratch
+  for (size_t r = 0; r < n_ranges; r++) {
+    uint64_t sel = 0;
+    if ((rc = work(bounds[r], bounds[r + 1], &sel))) return rc;
+    select_launch_rank_docs(R.select, R.blk, R.d_rel, R.nd, total, d_dso + bounds[r], blocks, s);
+    HIPCHK(ac, hipGetLastError());
+    if (n_ranges > 1) HIPCHK(ac, hipStreamSynchronize(s));  // (the next range takes the scratch)
+    total += sel;
+  }
+  if (total <= cap) {
+    if (n_ranges == 1 && total) {
+      if ((rc = emit(0))) return rc;
+    } else if (n_ranges > 1) {  // the emit pass
+      uint64_t base = 0;
+      for (size_t r = 0; r < n_ranges; r++) {
+        uint64_t sel = 0;
+        if ((rc = work(bounds[r], bounds[r + 1], &sel))) return rc;
+        if (sel && (rc = emit(base))) return rc;
+        HIPCHK(ac, hipStreamSynchronize(s));
+        base += sel;
+      }
+      if (base != total) {
+        tls_err = "select: the two passes over the ranges disagree";
+        return AHA_E_HIP;
+      }
+    }
+    if (d_doc_sel_offsets) {
+      if (!n_ranges) {
+        HIPCHK(ac, hipMemsetAsync(d_doc_sel_offsets, 0, (D + 1) * 8, s));
+      } else {
+        HIPCHK(ac, hipMemcpyAsync(d_doc_sel_offsets, d_dso, D * 8, hipMemcpyDeviceToDevice, s));
+        HIPCHK(ac, hipMemcpyAsync(d_doc_sel_offsets + D, &total, 8, hipMemcpyHostToDevice, s));
+      }
+    }
+    HIPCHK(ac, hipStreamSynchronize(s));
+  }
+  *n_selected = total;
+  if (n_hits_out) *n_hits_out = n_hits;
+  if (ac->profiling.load()) {
+    // the engine that traversed, the call's hits; ms_write = everything after the match (the call from its first range on,
+    // less its matches); repeats = the ranges before the last
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_all0).count();
+    t_trav.struct_size = sizeof(t_trav);
+    t_trav.n_hits = n_hits;
+    t_trav.ms_write = (float)std::max(0.0, ms - ms_match);
+    t_trav.repeats = n_ranges ? (uint32_t)(n_ranges - 1) : 0;
     publish_timing(ac, t_trav);
   }
   if (total > cap) {

@@ -94,6 +94,18 @@ enum CoverSlot {
   kCovTotal,      // the total
   kCovCount
 };
+// selbuf: select calls (engine.cpp device_select)
+enum SelectSlot {
+  kSelHitOff,   // the documents' hit offsets (the count call in front)
+  kSelHits,     // a range's hits
+  kSelRel,      // the range's document offsets, relative to its first byte
+  kSelText,     // the aligned copy of an unaligned range
+  kSelLongest,  // L: per text byte of the range the longest hit that starts there, len << 32 | value
+  kSelMasks,    // the cover, document-start and select masks, one bit per text byte each
+  kSelBlocks,   // the selected hits before every 64 words of the select mask, the range's total behind them
+  kSelDocOff,   // the documents' offsets into the selection, until the call is known to succeed
+  kSelCount
+};
 // Device scratch of ONE match call (grow-only, reused by later calls that lease the same set).
 struct Scratch {
   std::mutex mu;  // held by the call that leased the set
@@ -108,6 +120,7 @@ struct Scratch {
   Buf cntbuf[kCntCount];
   Buf dcbuf[kDcCount];
   Buf covbuf[kCovCount];
+  Buf selbuf[kSelCount];
   // every family above, for free_scratch and scratch_bytes (S: Scratch or const Scratch): a new family is one more line here
   template <class S, class Fn>
   static void each_buf(S &sc, Fn fn) {
@@ -116,6 +129,7 @@ struct Scratch {
     for (auto &b : sc.cntbuf) fn(b);
     for (auto &b : sc.dcbuf) fn(b);
     for (auto &b : sc.covbuf) fn(b);
+    for (auto &b : sc.selbuf) fn(b);
   }
   bool dc_rows_clear = false;  // every word of dcbuf[kDcRows] is zero (kdc_compact clears what kdc_add wrote; a call that failed may not have)
   hipStream_t hs[3] = {};  // host-buffer entry: private non-blocking streams for upload, match, download
@@ -202,6 +216,7 @@ struct aha_ac {
   // document counts: read from the environment when the handle is compiled (engine.cpp doccount_setup)
   uint64_t dc_hit_bytes = 0, dc_row_bytes = 0;  // bounds of a range's hit buffer and of the dense rows in flight
   uint32_t dc_sort_max = 0, dc_dense_min = 0, dc_range_keys = 0;
+  uint64_t sel_hit_bytes = 0;  // select calls: the bound of a range's hit buffer (AHA_SELECT_HIT_BYTES)
   uint32_t seg2 = 0;  // slots below it: the root's and the depth-1 states' rows
   // match_longest only (cedar_replay.cpp): the states that carry one of Cedar's stale END flags, derived on the first
   // match_longest call (it replays every insert: as long again as the rest of compile); dev_longest = dev + the bitmap
@@ -268,7 +283,7 @@ uint64_t scratch_bytes(const Scratch *sc);
 // THE allocator of the grow-only buffers: b holds at least `bytes` afterwards, or nothing (the HIP error is returned, the
 // runtime's sticky one cleared).  What a new buffer gets beyond `bytes` is its family's rule:
 enum Grow {
-  kGrowEighth,   // bytes + bytes / 8 + 256 (v2buf, covbuf)
+  kGrowEighth,   // bytes + bytes / 8 + 256 (v2buf, covbuf, selbuf)
   kGrowQuarter,  // bytes + bytes / 4 + 4096 (cntbuf, hostbuf)
   kGrowOrExact   // an eighth, else exactly `bytes`; `bytes` is what it records (dcbuf: what is known to be there)
 };
@@ -369,4 +384,9 @@ int32_t device_doc_counts(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, cons
 int32_t device_cover(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
                      uint64_t n_bytes, const aha_match_params *params, uint32_t flags, uint32_t *d_mask, uint8_t *d_redacted,
                      uint8_t fill, uint64_t *d_doc_covered, uint64_t *n_covered, uint64_t *n_hits, void *stream, bool offsets_checked);
+// one device-resident batch selected (aha_ac_select_batch_device): a count call for the hits per document, the match into
+// scratch, the leftmost-longest non-overlapping hits of every document from it (scan_select.hip)
+int32_t device_select(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                      uint64_t n_bytes, const aha_match_params *params, aha_hit *d_out, uint64_t cap, uint64_t *d_doc_sel_offsets,
+                      uint64_t *n_selected, uint64_t *n_hits, void *stream, bool offsets_checked);
 }  // namespace ahai

@@ -287,6 +287,23 @@ void doccount_launch_compact64(const DcItem *doc, unsigned long long *row, uint3
 void doccount_launch_gather(const uint64_t *pair_off, const uint32_t *const *src, uint64_t n_docs, uint64_t n, void *out,
                             void *stream);
 
+// select path (scan_select.hip; engine.cpp device_select), over one range of whole documents: nd documents at rel[0 .. nd] of nb
+// bytes of text, their n_hits hits in `hits` (hit_off[d] - hit_off[0]: the first hit of document d).  L: nb words of 8 bytes,
+// clear; cover / doc_start / select: nb bits each, clear; blk: select_rank_blocks(nb) + 1 words of 8 bytes -- after
+// select_launch_rank the selected hits before every block of the select mask, the range's total in the last word.
+uint64_t select_rank_blocks(uint64_t n_bytes);
+void select_launch_longest(const void *hits, uint64_t n_hits, const uint64_t *hit_off, const uint64_t *rel, uint64_t nd, uint64_t nb,
+                           uint64_t *L, uint32_t max_blocks, void *stream);
+void select_launch_marks(const uint64_t *L, uint64_t nb, const uint64_t *rel, uint64_t nd, uint32_t *cover, uint32_t *doc_start,
+                         uint32_t max_blocks, void *stream);
+void select_launch_walk(const uint64_t *L, uint64_t nb, const uint32_t *cover, const uint32_t *doc_start, uint32_t *select,
+                        uint32_t max_blocks, void *stream);
+void select_launch_rank(const uint32_t *select, uint64_t nb, uint64_t *blk, uint32_t max_blocks, void *stream);
+void select_launch_rank_docs(const uint32_t *select, const uint64_t *blk, const uint64_t *rel, uint64_t nd, uint64_t base,
+                             uint64_t *out, uint32_t max_blocks, void *stream);
+void select_launch_emit(const uint32_t *select, uint64_t nb, const uint64_t *blk, const uint64_t *L, const uint64_t *rel, uint64_t nd,
+                        void *out, uint32_t max_blocks, void *stream);
+
 // exchange format of the multi-GPU all-gatherv (kernels.hip): {end, value} pairs <-> Hit triples
 void launch_hits_pack(const int32_t *hits, uint64_t n, int32_t *pairs, void *stream);
 void launch_hits_unpack(const DevAut &A, const int32_t *pairs, uint64_t n, int chars, int32_t *hits, void *stream);

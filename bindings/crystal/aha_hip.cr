@@ -202,6 +202,13 @@ lib LibAhaHip
   fun aha_ac_cover_batch_device(ac : Ac, d_corpus : UInt8*, d_doc_offsets : UInt64*, n_docs : UInt64, n_bytes : UInt64,
                                 params : MatchParams*, flags : UInt32, d_mask : UInt32*, d_redacted : UInt8*, fill : UInt8,
                                 d_doc_covered : UInt64*, n_covered : UInt64*, n_hits : UInt64*, stream : Void*) : Int32
+  # select: per document the leftmost-longest, non-overlapping hits of the match (byte offsets)
+  fun aha_ac_select_batch(ac : Ac, corpus : UInt8*, doc_offsets : UInt64*, n_docs : UInt64, params : MatchParams*,
+                          flags : UInt32, out : Hit*, cap : UInt64, doc_sel_offsets : UInt64*, n_selected : UInt64*,
+                          n_hits : UInt64*) : Int32
+  fun aha_ac_select_batch_device(ac : Ac, d_corpus : UInt8*, d_doc_offsets : UInt64*, n_docs : UInt64, n_bytes : UInt64,
+                                 params : MatchParams*, flags : UInt32, d_out : Hit*, cap : UInt64,
+                                 d_doc_sel_offsets : UInt64*, n_selected : UInt64*, n_hits : UInt64*, stream : Void*) : Int32
   # feeds: sequences that arrive in pieces across calls (offsets relative to the piece; FEED_CHARS: in characters)
   type Feed = Void*
   FEED_CHARS = 1_u32
@@ -444,6 +451,35 @@ module Aha
       Array.new(docs.size) do |d|
         Array.new((dpo[d + 1] - dpo[d]).to_i) { |i| p = pairs[dpo[d] + i]; {p.key, p.count} }
       end
+    end
+
+    # Per document the leftmost-longest, non-overlapping hits of match_batch(docs, sep: sep), ascending by start, as
+    # {start, end, value} in byte offsets (Aha::AC has no such method; CedarX#gsub walks the text the same way).
+    def select_batch(docs : Array(String) | Array(Bytes), sep : BitArray? = nil) : Array(Array({Int32, Int32, Int32}))
+      corpus = IO::Memory.new
+      offs = Array(UInt64).new(docs.size + 1)
+      offs << 0_u64
+      docs.each do |d|
+        corpus.write(d.is_a?(String) ? d.to_slice : d)
+        offs << corpus.pos.to_u64
+      end
+      params = AC.params(false, sep)
+      dso = Array(UInt64).new(docs.size + 1, 0_u64)
+      rc = LibAhaHip.aha_ac_select_batch(@handle, corpus.to_slice.to_unsafe, offs.to_unsafe, docs.size.to_u64,
+        pointerof(params), 0_u32, Pointer(LibAhaHip::Hit).null, 0_u64, dso.to_unsafe, out n, Pointer(UInt64).null)
+      hits = Pointer(LibAhaHip::Hit).malloc(n + 1)
+      if rc == E_CAPACITY # n is the required count; nothing was written
+        rc = LibAhaHip.aha_ac_select_batch(@handle, corpus.to_slice.to_unsafe, offs.to_unsafe, docs.size.to_u64,
+          pointerof(params), 0_u32, hits, n, dso.to_unsafe, out n2, Pointer(UInt64).null)
+      end
+      raise String.new(LibAhaHip.aha_last_error(@handle)) if rc != 0
+      Array.new(docs.size) do |d|
+        Array.new((dso[d + 1] - dso[d]).to_i) { |i| h = hits[dso[d] + i]; {h.start, h.end_, h.value} }
+      end
+    end
+
+    def select(seq : String | Bytes, sep : BitArray? = nil) : Array({Int32, Int32, Int32})
+      select_batch([seq.is_a?(String) ? seq.to_slice : seq], sep)[0]
     end
 
     private def run(seq : Bytes, chars : Bool, sep : BitArray?, longest : Int32 = 0, &block)

@@ -276,6 +276,33 @@ class AC {
     return pairs;
   }
 
+  // Per document the leftmost-longest, non-overlapping hits of match_batch (aha_ac_select_batch; byte offsets): document d's
+  // selection, ascending by start, is [(*doc_sel_offsets)[d], (*doc_sel_offsets)[d + 1]) of what is returned.  A sizing call first.
+  std::vector<Hit> select_batch(std::string_view corpus, const std::vector<uint64_t> &doc_offsets,
+                                std::vector<uint64_t> *doc_sel_offsets = nullptr, uint64_t *n_hits = nullptr) const {
+    if (doc_offsets.empty()) throw Error(AHA_E_INVALID, "doc_offsets holds D + 1 entries");
+    aha_match_params p{};
+    p.struct_size = sizeof(p);
+    const uint64_t D = doc_offsets.size() - 1;
+    const uint8_t *text = reinterpret_cast<const uint8_t *>(corpus.data());
+    std::vector<uint64_t> dso(D + 1);
+    std::vector<Hit> sel;
+    uint64_t n = 0, nh = 0;
+    int32_t rc = aha_ac_select_batch(h_, text, doc_offsets.data(), D, &p, 0, nullptr, 0, dso.data(), &n, &nh);
+    if (rc == AHA_E_CAPACITY) {
+      sel.resize(n);
+      rc = aha_ac_select_batch(h_, text, doc_offsets.data(), D, &p, 0, sel.data(), sel.size(), dso.data(), &n, &nh);
+    }
+    if (rc != AHA_OK) {
+      const char *m = aha_last_error(h_);
+      throw Error(rc, (m && *m) ? m : aha_strerror(rc));
+    }
+    if (doc_sel_offsets) *doc_sel_offsets = std::move(dso);
+    if (n_hits) *n_hits = nh;
+    return sel;
+  }
+  std::vector<Hit> select(std::string_view seq) const { return select_batch(seq, {0, seq.size()}); }
+
   // Which bytes of the batch lie inside a hit of match_batch, without the hit list (aha_ac_cover_batch): bit j of the batch is
   // word j >> 5, bit j & 31 of what is returned; doc_covered (optional): covered bytes per document.
   std::vector<uint32_t> cover_batch(std::string_view corpus, const std::vector<uint64_t> &doc_offsets,

@@ -550,6 +550,42 @@ int32_t aha_ac_cover_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uin
                                   uint8_t *d_redacted, uint8_t fill, uint64_t *d_doc_covered /* D or NULL */,
                                   uint64_t *n_covered, uint64_t *n_hits /* or NULL */, void *stream);
 
+/* ---- select: leftmost-longest, non-overlapping hits per document (pure additions to ABI 8) ------------------------------
+ * The same batch, validation and errors as aha_ac_match_batch / _device.  H_d = the hits that aha_ac_match_batch reports
+ * for document d with the same params (byte offsets; a separator filter is allowed) on the same handle (AHA_OPT_FOLD_ASCII
+ * included).  The selection S_d: p = 0; among the hits of H_d with start >= p take those with the smallest start, of these
+ * the one with the largest end (keys are distinct: it is unique); emit it, p = its end; repeat until no hit has start >= p.
+ * out[doc_sel_offsets[d] .. doc_sel_offsets[d+1]) = S_d, ascending by start, no two hits overlap, each an aha_hit
+ * {start, end, value} relative to the document exactly as the match writes it; documents in order; two calls give identical
+ * bytes.  A selected hit need not be the first hit at its end: keys ab, bcd, cd, d over "abcd" give (0,2,ab), (2,4,cd).
+ * *n_selected = all selected hits; *n_hits (optional) = the match call's hit count.  cap is in hits.
+ * AHA_E_CAPACITY: *n_selected is the required count and NONE of the caller's buffers is written (out == NULL with cap == 0
+ * is a sizing call).  Every failing call leaves the caller's buffers untouched.
+ * params->char_offsets != 0, params->longest != 0, any flag bit (flags is 0), n_selected == NULL, a NULL handle:
+ * AHA_E_INVALID; sep_size > 256: AHA_E_SEP_SIZE; a host-only handle: AHA_E_NO_DEVICE; all before any device work.  Bad
+ * offsets: AHA_E_INVALID / AHA_E_TOO_LONG (the device entry finds them on the device).  N = 0, D = 0 and empty documents are
+ * valid.  Like the count, cover and document-count calls it reads the handle's back-off state and never writes it.
+ * Pipeline (aha_amd/csrc/scan_select.hip): a count call without key counts (hits per document), the match
+ * with cap = hits into the call's scratch, then over the hit list: L[p] = the longest hit that starts at text byte p (a
+ * 64-bit atomicMax of len << 32 | value per hit), a cover mask (the union of the longest spans is the union of all hits) and
+ * a document-start mask, one walker per run (a maximal covered stretch inside one document: the greedy rule never jumps over
+ * an uncovered byte or a document start, so runs are independent; within a run the walk is sequential), the rank of the
+ * select mask (the documents' offsets, the total), and the emit once the total is known to fit.
+ * Device scratch: the count call's and the match's + 12 bytes per hit + 8 bytes per text byte + 3 N / 8 bytes of masks
+ * + N / 256 + 16 bytes per document.  Where the hits are beyond 48 GiB (AHA_SELECT_HIT_BYTES, read when the handle is
+ * compiled) the call works through ranges of whole documents (aha_timing.repeats = the ranges before the last; a document
+ * beyond the bound is a range of its own) -- twice, since nothing is written before the total is known.
+ * aha_ac_last_timing: engine = the engine of the match, n_hits = all hits, ms_write = everything after the match.
+ * Out of scope so far: char offsets, a substituted copy made on the device, feeds, groups. */
+int32_t aha_ac_select_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc_offsets, uint64_t n_docs,
+                            const aha_match_params *params, uint32_t flags /* 0 */, aha_hit *out, uint64_t cap,
+                            uint64_t *doc_sel_offsets /* D+1 or NULL */, uint64_t *n_selected, uint64_t *n_hits /* or NULL */);
+/* Device-resident form: d_ pointers are HBM on the handle's device; *n_selected, *n_hits are host memory; blocks until final. */
+int32_t aha_ac_select_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                                   uint64_t n_bytes, const aha_match_params *params, uint32_t flags, aha_hit *d_out, uint64_t cap,
+                                   uint64_t *d_doc_sel_offsets /* D+1 or NULL */, uint64_t *n_selected,
+                                   uint64_t *n_hits /* or NULL */, void *stream);
+
 /* Feed cover: the same pieces as aha_feed_match_batch*, and the cover of what a match call of them on a BYTE feed in the same
  * state would report (H_d: the hits of piece d, offsets relative to the piece, start possibly negative), without the hit list.
  * mask: the layout of aha_ac_cover_batch over the batch of pieces; bit j = 1 iff byte j lies in [max(start, 0), end) of a hit
