@@ -155,6 +155,12 @@ SIGNATURES = {
                                    C.POINTER(_u64)]),
     "aha_ac_select_batch_device": (_i32, [_vp, _vp, _vp, _u64, _u64, C.POINTER(aha_match_params), _u32, _vp, _u64, _vp,
                                           C.POINTER(_u64), C.POINTER(_u64), _vp]),
+    "aha_repl_create": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "aha_repl_free": (None, [_vp]),
+    "aha_ac_replace_batch": (_i32, [_vp, _vp, _vp, _vp, _u64, C.POINTER(aha_match_params), _u32, _vp, _u64, _vp, C.POINTER(_u64),
+                                    C.POINTER(_u64), C.POINTER(_u64)]),
+    "aha_ac_replace_batch_device": (_i32, [_vp, _vp, _vp, _vp, _u64, _u64, C.POINTER(aha_match_params), _u32, _vp, _u64, _vp,
+                                           C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), _vp]),
     "aha_ac_count_batch": (_i32, [_vp, _vp, _vp, _u64, C.POINTER(aha_match_params), _u32, _vp, _vp, C.POINTER(_u64)]),
     "aha_ac_count_batch_device": (_i32, [_vp, _vp, _vp, _u64, _u64, C.POINTER(aha_match_params), _u32, _vp, _vp,
                                          C.POINTER(_u64), _vp]),

@@ -138,6 +138,44 @@ def substitute(text, hits, repl, n_keys):
     return b"".join(parts)
 
 
+class ReplTable:
+    """A replacement table of one handle (aha_repl_create): validated and uploaded once, immutable, freed with the object.
+    Made by AC.replacements."""
+
+    def __init__(self, handle, n_keys):
+        self._h, self.n_keys = handle, n_keys
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                N.lib().aha_repl_free(h)
+            except Exception:  # interpreter shutdown
+                pass
+
+
+def _pack_replacements(repl, n_keys):
+    """repl as substitute takes it -> (blob uint8, offsets uint64[K+1], keep bits uint32[ceil(K/32)])"""
+    parts, keep = [], np.zeros((n_keys + 31) // 32, dtype=np.uint32)
+    offs = np.zeros(n_keys + 1, dtype=np.uint64)
+    if hasattr(repl, "keys"):
+        for k in repl.keys():
+            if not 0 <= int(k) < n_keys:
+                raise ValueError("repl names key %r; the handle has %d keys" % (k, n_keys))
+    at = 0
+    for k in range(n_keys):
+        r = _replacement_of(repl, k, n_keys)
+        if r is None:
+            keep[k >> 5] |= np.uint32(1 << (k & 31))
+        else:
+            r = _b(r)
+            parts.append(r)
+            at += len(r)
+        offs[k + 1] = at
+    blob = np.frombuffer(b"".join(parts), dtype=np.uint8) if at else np.zeros(0, np.uint8)
+    return blob, offs, keep
+
+
 class AC:
     """Aha::AC (= ACX(Int32), src/aha/ac.cr:8-11) on the MI355X."""
 
@@ -695,6 +733,109 @@ class AC:
                                           dso.ptr, C.byref(n), C.byref(nh), None)
         self._check(rc)
         return (out.download(np.zeros(cap, dtype=HIT_DTYPE)), dso.download(np.zeros(D + 1, dtype=np.uint64)), int(nh.value))
+
+    # -- replace: the substituted copy of a batch, built on the device (aha_ac_replace_batch*) ----------
+    def replacements(self, repl):
+        """repl -- a mapping from key index to bytes / str / None (keys it does not name are kept) or a sequence with one entry
+        per key (None: keep) -- as a ReplTable of this handle."""
+        n_keys = self.n_keys
+        blob, offs, keep = _pack_replacements(repl, n_keys)
+        h = C.c_void_p()
+        self._check(N.lib().aha_repl_create(self._h, _ptr(blob), _ptr(offs), _ptr(keep), C.byref(h)))
+        t = ReplTable(h, n_keys)
+        t._keep_alive = (blob, offs, keep)
+        return t
+
+    def _table(self, repl_or_table):
+        return repl_or_table if isinstance(repl_or_table, ReplTable) else self.replacements(repl_or_table)
+
+    @staticmethod
+    def _capacity_error(rc, n):
+        e = AhaError(rc, N.lib().aha_strerror(rc).decode())
+        e.n_required = int(n.value)
+        return e
+
+    def replace_batch(self, corpus, doc_offsets, repl_or_table, sep=None):
+        """Every document with its selected hits (select_batch) replaced as the table says, built on the device:
+        -> (uint8 array, doc_out_offsets uint64[D+1]); document d's result is out[doc_out_offsets[d]:doc_out_offsets[d+1]].
+        A sizing call first."""
+        if isinstance(corpus, (bytes, bytearray)):
+            corpus = np.frombuffer(bytes(corpus), dtype=np.uint8)
+        corpus = np.ascontiguousarray(corpus, dtype=np.uint8)
+        doc_offsets = np.ascontiguousarray(doc_offsets, dtype=np.uint64)
+        table = self._table(repl_or_table)
+        D = doc_offsets.size - 1
+        p = _params(False, sep)
+        doo = np.zeros(D + 1, dtype=np.uint64)
+        n = C.c_uint64(0)
+        L = N.lib()
+        rc = L.aha_ac_replace_batch(self._h, table._h, _ptr(corpus), _ptr(doc_offsets), D, C.byref(p), 0, None, 0, _ptr(doo),
+                                    C.byref(n), None, None)
+        if rc != N.AHA_E_CAPACITY:
+            self._check(rc)
+            return np.zeros(0, dtype=np.uint8), doo
+        cap = int(n.value)
+        out = np.zeros(cap, dtype=np.uint8)
+        rc = L.aha_ac_replace_batch(self._h, table._h, _ptr(corpus), _ptr(doc_offsets), D, C.byref(p), 0, _ptr(out), cap,
+                                    _ptr(doo), C.byref(n), None, None)
+        self._check(rc)
+        return out[: int(n.value)], doo
+
+    def replace_batch_device(self, corpus, doc_offsets, table, out, doc_out_offsets=None, sep=None, cap=None, stream=None):
+        """Device-resident replace on torch CUDA tensors: uint8 corpus, int64/uint64 doc offsets, out uint8 [cap] (any
+        alignment) or None (a sizing call), doc_out_offsets int64/uint64 [D+1] or None.
+        -> (n_out_bytes, n_selected, n_hits); raises AhaError(AHA_E_CAPACITY) when out is too small (e.n_required = the bytes
+        needed); nothing is written then."""
+        import torch
+
+        assert corpus.is_cuda and corpus.dtype == torch.uint8 and corpus.is_contiguous()
+        assert doc_offsets.is_cuda and doc_offsets.dtype in (torch.int64, torch.uint64)
+        if out is not None:
+            if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.dim() == 1):
+                raise ValueError("out must be a contiguous one-dimensional uint8 CUDA tensor")
+            cap = out.numel() if cap is None else min(int(cap), out.numel())
+        else:
+            cap = 0
+        if doc_out_offsets is not None and not (doc_out_offsets.is_cuda and doc_out_offsets.dtype in (torch.int64, torch.uint64)
+                                                and doc_out_offsets.is_contiguous()
+                                                and doc_out_offsets.numel() >= doc_offsets.numel()):
+            raise ValueError("doc_out_offsets must be a contiguous int64/uint64 CUDA tensor of at least D + 1 entries")
+        D = doc_offsets.numel() - 1
+        p = _params(False, sep)
+        n, ns, nh = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        s = stream if stream is not None else torch.cuda.current_stream(corpus.device).cuda_stream
+        rc = N.lib().aha_ac_replace_batch_device(
+            self._h, table._h, corpus.data_ptr(), doc_offsets.data_ptr(), D, corpus.numel(), C.byref(p), 0,
+            out.data_ptr() if out is not None and cap else None, cap,
+            doc_out_offsets.data_ptr() if doc_out_offsets is not None else None, C.byref(n), C.byref(ns), C.byref(nh),
+            C.c_void_p(s))
+        if rc == N.AHA_E_CAPACITY:
+            raise self._capacity_error(rc, n)
+        self._check(rc)
+        return int(n.value), int(ns.value), int(nh.value)
+
+    def replace_corpus(self, corpus, table, sep=None):
+        """The substituted copy of a batch that already lives in HBM (DeviceCorpus), downloaded:
+        -> (uint8 array, doc_out_offsets uint64[D+1], n_selected, n_hits)."""
+        table = self._table(table)
+        D = corpus.n_docs
+        p = _params(False, sep)
+        dev = corpus.device
+        doo = DeviceBuffer(dev, (D + 1) * 8)
+        n, ns, nh = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        L = N.lib()
+        rc = L.aha_ac_replace_batch_device(self._h, table._h, corpus.ptr, corpus.doc_ptr, D, corpus.n_bytes, C.byref(p), 0, None, 0,
+                                           doo.ptr, C.byref(n), C.byref(ns), C.byref(nh), None)
+        if rc != N.AHA_E_CAPACITY:
+            self._check(rc)
+            return (np.zeros(0, dtype=np.uint8), doo.download(np.zeros(D + 1, dtype=np.uint64)), int(ns.value), int(nh.value))
+        cap = int(n.value)
+        out = DeviceBuffer(dev, cap)
+        rc = L.aha_ac_replace_batch_device(self._h, table._h, corpus.ptr, corpus.doc_ptr, D, corpus.n_bytes, C.byref(p), 0, out.ptr,
+                                           cap, doo.ptr, C.byref(n), C.byref(ns), C.byref(nh), None)
+        self._check(rc)
+        return (out.download(np.zeros(cap, dtype=np.uint8)), doo.download(np.zeros(D + 1, dtype=np.uint64)), int(ns.value),
+                int(nh.value))
 
     # -- cover: which bytes lie inside a hit, and a redacted copy (aha_ac_cover_batch*) ---------------
     def _cover_host(self, corpus, doc_offsets, sep, want_mask, want_redacted, fill):

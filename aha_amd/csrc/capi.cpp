@@ -1453,6 +1453,136 @@ static int32_t buffer_copy(int device, void *dst, const void *src, uint64_t byte
 }
 }  // namespace
 
+// ---- replace calls (aha_repl_*, aha_ac_replace_batch*) ---------------------------------------------------------------
+// A table is validated and uploaded once.  On a host-only handle it is made all the same, with a host copy only, so that the
+// replace entries' argument checks hold there; they answer AHA_E_NO_DEVICE then.
+int32_t aha_repl_create(aha_ac *ac, const uint8_t *blob, const uint64_t *offsets, const uint32_t *keep_bits, aha_repl **out) {
+  if (out) *out = nullptr;
+  if (!ac || !offsets || !out) return AHA_E_INVALID;
+  const uint32_t K = ac->aut.n_keys;
+  if (offsets[0] != 0) return AHA_E_INVALID;
+  for (uint32_t k = 0; k < K; k++)
+    if (offsets[k + 1] < offsets[k] || offsets[k + 1] - offsets[k] > 0xFFFFFFFFull) return AHA_E_INVALID;
+  if (offsets[K] && !blob) return AHA_E_INVALID;
+  std::unique_ptr<aha_repl> t(new (std::nothrow) aha_repl());
+  if (!t) return AHA_E_NOMEM;
+  try {
+    t->blob.assign(blob, blob + offsets[K]);
+    t->ent.resize(K);
+  } catch (...) {
+    return AHA_E_NOMEM;
+  }
+  for (uint32_t k = 0; k < K; k++)
+    t->ent[k] = RepEntry{offsets[k], (uint32_t)(offsets[k + 1] - offsets[k]), keep_bits ? (keep_bits[k >> 5] >> (k & 31)) & 1u : 0u};
+  t->owner = ac->serial;
+  t->n_keys = K;
+  if (ac->device >= 0) {
+    DeviceGuard g(ac->device);
+    t->device = ac->device;
+    hipStream_t st = nullptr;
+    int32_t rc = copy_stream(ac->device, &st);
+    if (rc) return rc;
+    hipError_t e = hipMalloc(&t->d_blob, t->blob.size() + 16);
+    if (e == hipSuccess) e = hipMalloc((void **)&t->d_ent, std::max<size_t>(K, 1) * sizeof(RepEntry));
+    if (e == hipSuccess && !t->blob.empty()) e = hipMemcpyAsync(t->d_blob, t->blob.data(), t->blob.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && K) e = hipMemcpyAsync(t->d_ent, t->ent.data(), K * sizeof(RepEntry), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      tls_err = std::string("aha_repl_create: ") + hipGetErrorString(e);
+      aha_repl_free(t.release());
+      return AHA_E_HIP;
+    }
+  }
+  *out = t.release();
+  return AHA_OK;
+}
+
+void aha_repl_free(aha_repl *t) {
+  if (!t) return;
+  if (t->device >= 0) {
+    DeviceGuard g(t->device);
+    if (t->d_blob) (void)hipFree(t->d_blob);
+    if (t->d_ent) (void)hipFree(t->d_ent);
+  }
+  delete t;
+}
+
+// the argument checks both entries share: before any device work, so they hold on a host-only handle.  out / corpus: the two
+// address ranges that must not overlap (there is no in-place form)
+static int32_t replace_args(aha_ac *ac, const aha_repl *table, const uint8_t *corpus, uint64_t n_bytes, const uint64_t *doc_offsets,
+                            const aha_match_params *params, uint32_t flags, const uint8_t *out, uint64_t cap_bytes,
+                            uint64_t *n_out_bytes) {
+  if (!ac || !table || !n_out_bytes || !doc_offsets || flags) return AHA_E_INVALID;
+  if (table->owner != ac->serial) {
+    tls_err = "the replacement table was made for another handle";
+    return AHA_E_INVALID;
+  }
+  if (int32_t rc = no_longest_form(ac, params, "replace calls have no match_longest form")) return rc;
+  if (params && params->struct_size >= offsetof(aha_match_params, char_offsets) + sizeof(params->char_offsets) && params->char_offsets) {
+    tls_err = "replace calls take byte offsets only";
+    return AHA_E_INVALID;
+  }
+  if (cap_bytes && !out) return AHA_E_INVALID;
+  if (cap_bytes && n_bytes && corpus) {
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), c0 = reinterpret_cast<uintptr_t>(corpus);
+    if (o0 < c0 + n_bytes && c0 < o0 + cap_bytes) {
+      tls_err = "replace calls have no in-place form: out overlaps the corpus";
+      return AHA_E_INVALID;
+    }
+  }
+  if (ac->device < 0) return no_device();
+  return AHA_OK;
+}
+
+int32_t aha_ac_replace_batch_device(aha_ac *ac, const aha_repl *table, const uint8_t *d_corpus, const uint64_t *d_doc_offsets,
+                                    uint64_t n_docs, uint64_t n_bytes, const aha_match_params *params, uint32_t flags,
+                                    uint8_t *d_out, uint64_t cap_bytes, uint64_t *d_doc_out_offsets, uint64_t *n_out_bytes,
+                                    uint64_t *n_selected, uint64_t *n_hits, void *stream) {
+  int32_t rc = replace_args(ac, table, d_corpus, n_bytes, d_doc_offsets, params, flags, d_out, cap_bytes, n_out_bytes);
+  if (rc) return rc;
+  Lease lease(ac);
+  return device_replace(ac, lease.get(), table, d_corpus, d_doc_offsets, n_docs, n_bytes, params, d_out, cap_bytes,
+                        d_doc_out_offsets, n_out_bytes, n_selected, n_hits, stream, false);
+}
+
+// The host entry: the batch goes up in one piece into the staging buffers of the leased scratch set, over its private stream;
+// the result and the offsets come back once the call has succeeded.
+int32_t aha_ac_replace_batch(aha_ac *ac, const aha_repl *table, const uint8_t *corpus, const uint64_t *doc_offsets, uint64_t n_docs,
+                             const aha_match_params *params, uint32_t flags, uint8_t *out, uint64_t cap_bytes,
+                             uint64_t *doc_out_offsets, uint64_t *n_out_bytes, uint64_t *n_selected, uint64_t *n_hits) {
+  if (!doc_offsets) return AHA_E_INVALID;
+  int32_t rc = replace_args(ac, table, corpus, doc_offsets[n_docs], doc_offsets, params, flags, out, cap_bytes, n_out_bytes);
+  if (rc) return rc;
+  if ((rc = check_host_batch(corpus, doc_offsets, n_docs))) return rc;
+  const uint64_t n_bytes = doc_offsets[n_docs];
+  DeviceGuard g(ac->device);
+  Lease lease(ac);
+  Scratch *sc = lease.get();
+  HostBatch B;
+  if ((rc = stage_host_batch(ac, sc, corpus, doc_offsets, n_docs, (n_docs + 1) * 8, cap_bytes, B))) return rc;
+  uint64_t *d_doo = (uint64_t *)B.d_per_doc;
+  uint8_t *d_out = (uint8_t *)B.d_per_call;
+  hipStream_t s = B.s;
+  uint64_t nb = 0, ns = 0, nh = 0;
+  rc = device_replace(ac, sc, table, B.d_corpus, B.d_doc, n_docs, n_bytes, params, d_out, cap_bytes, d_doo, &nb, &ns, &nh, s,
+                      true);  // the offsets were checked on the host above
+  if (rc == AHA_E_CAPACITY) {  // (the required size and the counts, as the device entry gives them)
+    *n_out_bytes = nb;
+    if (n_selected) *n_selected = ns;
+    if (n_hits) *n_hits = nh;
+  }
+  if (rc != AHA_OK) return rc;
+  if (nb) HIPCHK(ac, hipMemcpyAsync(out, d_out, nb, hipMemcpyDeviceToHost, s));
+  if (doc_out_offsets) HIPCHK(ac, hipMemcpyAsync(doc_out_offsets, d_doo, (n_docs + 1) * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  *n_out_bytes = nb;
+  if (n_selected) *n_selected = ns;
+  if (n_hits) *n_hits = nh;
+  return AHA_OK;
+}
+
+
 struct aha_corpus {
   int device = -1;
   void *bytes = nullptr;

@@ -84,6 +84,8 @@ static void doccount_setup(aha_ac *ac) {
   ac->dc_dense_min = (uint32_t)env("AHA_DOCCOUNT_DENSE_MIN", std::max<uint64_t>(ac->dc_sort_max + 1ull, K / 8), 1, 0x7FFFFFFFull);
   // select calls: the bound of a range's hit buffer, by default the document counts' (device_select)
   ac->sel_hit_bytes = env("AHA_SELECT_HIT_BYTES", ac->dc_hit_bytes, 12, kV2MaxRegionBytes);
+  // replace calls: the cap of the scan's and the copy's grids (tests: 1, so that workgroups loop over tiles)
+  ac->rep_blocks = (uint32_t)env("AHA_REPLACE_BLOCKS", 0, 1, 1u << 20);
 }
 
 void v2_setup(aha_ac *ac) {
@@ -1425,6 +1427,16 @@ static void *sel_reserve(Scratch *sc, SelectSlot slot, size_t bytes) { return re
 int32_t device_select(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
                       uint64_t n_bytes, const aha_match_params *params, aha_hit *d_out, uint64_t cap, uint64_t *d_doc_sel_offsets,
                       uint64_t *n_selected, uint64_t *n_hits_out, void *stream, bool offsets_checked) {
+  return device_select_to(ac, sc, d_corpus, d_doc_offsets, n_docs, n_bytes, params, d_out, cap, d_doc_sel_offsets, n_selected,
+                          n_hits_out, stream, offsets_checked, nullptr);
+}
+
+// device_select with a say in where the selection goes (handle.hpp SelectSink).  sink == null: the public entries, as above.
+// With a sink every range's selection is emitted behind the ranges' before it as soon as the range has been worked -- one count
+// and one match per range whatever the number of ranges -- and d_out, cap and d_doc_sel_offsets are not used.
+int32_t device_select_to(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                         uint64_t n_bytes, const aha_match_params *params, aha_hit *d_out, uint64_t cap, uint64_t *d_doc_sel_offsets,
+                         uint64_t *n_selected, uint64_t *n_hits_out, void *stream, bool offsets_checked, const SelectSink *sink) {
   if (!ac || !n_selected || !d_doc_offsets) return AHA_E_INVALID;
   if (ac->device < 0) return no_device();
   if (cap && !d_out) return AHA_E_INVALID;
@@ -1563,10 +1575,22 @@ int32_t device_select(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const ui
     if ((rc = work(bounds[r], bounds[r + 1], &sel))) return rc;
     select_launch_rank_docs(R.select, R.blk, R.d_rel, R.nd, total, d_dso + bounds[r], blocks, s);
     HIPCHK(ac, hipGetLastError());
+    if (sink && sel) {  // the range's selection to its place in the sink's buffer at once
+      if ((rc = sink->place(total, total + sel, &d_out))) return rc;
+      if ((rc = emit(total))) return rc;
+    }
     if (n_ranges > 1) HIPCHK(ac, hipStreamSynchronize(s));  // (the next range takes the scratch)
     total += sel;
   }
-  if (total <= cap) {
+  if (sink) {  // the documents' offsets stay in scratch, all D + 1 of them
+    if (!n_ranges) {
+      HIPCHK(ac, hipMemsetAsync(d_dso, 0, (D + 1) * 8, s));
+    } else {
+      HIPCHK(ac, hipMemcpyAsync(d_dso + D, &total, 8, hipMemcpyHostToDevice, s));
+    }
+    HIPCHK(ac, hipStreamSynchronize(s));
+    cap = total;
+  } else if (total <= cap) {
     if (n_ranges == 1 && total) {
       if ((rc = emit(0))) return rc;
     } else if (n_ranges > 1) {  // the emit pass
@@ -1603,9 +1627,105 @@ int32_t device_select(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const ui
     t_trav.n_hits = n_hits;
     t_trav.ms_write = (float)std::max(0.0, ms - ms_match);
     t_trav.repeats = n_ranges ? (uint32_t)(n_ranges - 1) : 0;
-    publish_timing(ac, t_trav);
+    if (sink && sink->timing)
+      *sink->timing = t_trav;  // (the caller publishes)
+    else
+      publish_timing(ac, t_trav);
   }
   if (total > cap) {
+    tls_err = "output buffer too small";
+    return AHA_E_CAPACITY;
+  }
+  return AHA_OK;
+}
+
+// ---- replace calls (aha_ac_replace_batch*) ---------------------------------------------------------------------------
+static void *rep_reserve(Scratch *sc, ReplaceSlot slot, size_t bytes) { return reserve_ptr(sc->repbuf[slot], bytes, kGrowEighth); }
+
+// One device-resident batch substituted (aha_ac_replace_batch_device).
+//   1. device_select_to with a sink: the selection of ALL ranges into repbuf[kRepSel], the documents' offsets into it in
+//      selbuf[kSelDocOff] -- select's cost, one count and one match per range.
+//   2. Per selected hit its first byte in the corpus and its change of length; the exclusive scan of the changes; the
+//      documents' offsets into the result (scan_replace.hip).  The last of them is the total: it comes back to the host.
+//   3. Once the total is known to fit: the copy, then the documents' offsets to the caller.
+// A failing call writes none of the caller's buffers.
+int32_t device_replace(aha_ac *ac, Scratch *sc, const aha_repl *table, const uint8_t *d_corpus, const uint64_t *d_doc_offsets,
+                       uint64_t n_docs, uint64_t n_bytes, const aha_match_params *params, uint8_t *d_out, uint64_t cap_bytes,
+                       uint64_t *d_doc_out_offsets, uint64_t *n_out_bytes, uint64_t *n_selected, uint64_t *n_hits_out, void *stream,
+                       bool offsets_checked) {
+  if (!ac || !table || !n_out_bytes || !d_doc_offsets) return AHA_E_INVALID;
+  if (ac->device < 0 || !table->d_ent) return no_device();
+  if (cap_bytes && !d_out) return AHA_E_INVALID;
+  DeviceGuard g(ac->device);
+  hipStream_t s = (hipStream_t)stream;
+  const uint64_t D = n_docs;
+  *n_out_bytes = 0;
+  auto nomem = [&]() {
+    tls_err = "hipMalloc failed for the scratch of a replace call";
+    return AHA_E_HIP;
+  };
+  int32_t rc = AHA_OK;
+  aha_timing t_sel;  // what the select inside measured: the engine, the hits, the ranges (profiling)
+  memset(&t_sel, 0, sizeof(t_sel));
+  SelectSink sink;
+  sink.timing = &t_sel;
+  sink.place = [&](uint64_t kept, uint64_t upto, aha_hit **at) -> int32_t {
+    Buf &cur = sc->repbuf[kRepSel];
+    if (cur.bytes < upto * sizeof(aha_hit)) {
+      if (!kept) {
+        if (!rep_reserve(sc, kRepSel, upto * sizeof(aha_hit))) return nomem();
+      } else {  // a further range: the larger buffer, what is there already into it, then the two change places
+        Buf &spare = sc->repbuf[kRepSelSpare];
+        if (!rep_reserve(sc, kRepSelSpare, upto * sizeof(aha_hit))) return nomem();
+        hipError_t e = hipMemcpyAsync(spare.p, cur.p, kept * sizeof(aha_hit), hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+          (void)hipGetLastError();
+          tls_err = std::string("replace: moving the selection into a larger buffer: ") + hipGetErrorString(e);
+          return AHA_E_HIP;
+        }
+        std::swap(cur, spare);
+      }
+    }
+    *at = (aha_hit *)cur.p;
+    return AHA_OK;
+  };
+  uint64_t n = 0, n_hits = 0;
+  if ((rc = device_select_to(ac, sc, d_corpus, d_doc_offsets, D, n_bytes, params, nullptr, 0, nullptr, &n, &n_hits, stream,
+                             offsets_checked, &sink)))
+    return rc;
+  const auto t_sel1 = std::chrono::steady_clock::now();
+  const uint64_t *d_dso = (const uint64_t *)sc->selbuf[kSelDocOff].p;
+  const aha_hit *d_sel = (const aha_hit *)sc->repbuf[kRepSel].p;
+  const uint64_t n_blk = replace_scan_blocks(n);
+  uint64_t *A = (uint64_t *)rep_reserve(sc, kRepStart, std::max<uint64_t>(n, 1) * 8);
+  int64_t *shift = (int64_t *)rep_reserve(sc, kRepShift, (n + 1) * 8);
+  int64_t *sums = (int64_t *)rep_reserve(sc, kRepSums, (n_blk + 1) * 8);
+  uint64_t *d_doo = (uint64_t *)rep_reserve(sc, kRepDocOut, (D + 1) * 8);
+  if (!A || !shift || !sums || !d_doo) return nomem();
+  const uint32_t blocks = ac->rep_blocks ? ac->rep_blocks : 8u * std::max<uint32_t>(ac->v2_grid, 64u);
+  replace_launch_delta(d_sel, n, d_dso, d_doc_offsets, D, table->d_ent, table->n_keys, A, shift, blocks, s);
+  replace_launch_scan(shift, n, sums, blocks, s);
+  replace_launch_doc_offsets(d_doc_offsets, d_dso, shift, D, d_doo, blocks, s);
+  HIPCHK(ac, hipGetLastError());
+  uint64_t total = 0;
+  HIPCHK(ac, hipMemcpyAsync(&total, d_doo + D, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  if (total <= cap_bytes) {
+    replace_launch_copy(d_corpus, d_sel, A, shift, n, table->d_ent, table->n_keys, (const uint8_t *)table->d_blob, d_out, total,
+                        blocks, s);
+    HIPCHK(ac, hipGetLastError());
+    if (d_doc_out_offsets) HIPCHK(ac, hipMemcpyAsync(d_doc_out_offsets, d_doo, (D + 1) * 8, hipMemcpyDeviceToDevice, s));
+    HIPCHK(ac, hipStreamSynchronize(s));
+  }
+  *n_out_bytes = total;
+  if (n_selected) *n_selected = n;
+  if (n_hits_out) *n_hits_out = n_hits;
+  if (t_sel.struct_size) {  // (the select inside profiled) as select reports; ms_write = everything after the match
+    t_sel.ms_write += (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_sel1).count();
+    publish_timing(ac, t_sel);
+  }
+  if (total > cap_bytes) {
     tls_err = "output buffer too small";
     return AHA_E_CAPACITY;
   }

@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <atomic>
+#include <functional>
 #include <condition_variable>
 #include <memory>
 #include <mutex>
@@ -106,6 +107,16 @@ enum SelectSlot {
   kSelDocOff,   // the documents' offsets into the selection, until the call is known to succeed
   kSelCount
 };
+// repbuf: replace calls (engine.cpp device_replace)
+enum ReplaceSlot {
+  kRepSel,       // the selection of the whole batch, 12 bytes per selected hit
+  kRepSelSpare,  // ... while it grows over document ranges: the larger buffer, then the two change places
+  kRepStart,     // A: per selected hit its first byte in the corpus
+  kRepShift,     // per selected hit the change of length in front of it, the total change behind the last
+  kRepSums,      // the scan's block sums
+  kRepDocOut,    // the documents' offsets into the result, until the call is known to succeed
+  kRepCount
+};
 // Device scratch of ONE match call (grow-only, reused by later calls that lease the same set).
 struct Scratch {
   std::mutex mu;  // held by the call that leased the set
@@ -121,6 +132,7 @@ struct Scratch {
   Buf dcbuf[kDcCount];
   Buf covbuf[kCovCount];
   Buf selbuf[kSelCount];
+  Buf repbuf[kRepCount];
   // every family above, for free_scratch and scratch_bytes (S: Scratch or const Scratch): a new family is one more line here
   template <class S, class Fn>
   static void each_buf(S &sc, Fn fn) {
@@ -130,6 +142,7 @@ struct Scratch {
     for (auto &b : sc.dcbuf) fn(b);
     for (auto &b : sc.covbuf) fn(b);
     for (auto &b : sc.selbuf) fn(b);
+    for (auto &b : sc.repbuf) fn(b);
   }
   bool dc_rows_clear = false;  // every word of dcbuf[kDcRows] is zero (kdc_compact clears what kdc_add wrote; a call that failed may not have)
   hipStream_t hs[3] = {};  // host-buffer entry: private non-blocking streams for upload, match, download
@@ -160,6 +173,11 @@ struct aha_ac {
   // FOLDED keys (fold.hpp): everything derived from it (images, filter, stale ends, find_key) is what a plain handle compiled
   // from fold(keys) has; key_spelling holds the keys as the caller wrote them (same offsets) for aha_ac_key and aha_ac_save
   uint32_t opt_flags = 0;
+  static uint64_t next_serial() {
+    static std::atomic<uint64_t> n{0};
+    return ++n;
+  }
+  const uint64_t serial = next_serial();  // one per handle ever made in this process (a replacement table names its handle by it)
   std::vector<uint8_t> key_spelling;
   bool fold() const { return (opt_flags & AHA_OPT_FOLD_ASCII) != 0; }
   Image img;  // host copy of the device image (export / debugging)
@@ -217,6 +235,7 @@ struct aha_ac {
   uint64_t dc_hit_bytes = 0, dc_row_bytes = 0;  // bounds of a range's hit buffer and of the dense rows in flight
   uint32_t dc_sort_max = 0, dc_dense_min = 0, dc_range_keys = 0;
   uint64_t sel_hit_bytes = 0;  // select calls: the bound of a range's hit buffer (AHA_SELECT_HIT_BYTES)
+  uint32_t rep_blocks = 0;  // replace calls: the cap of the scan's and the copy's grids (AHA_REPLACE_BLOCKS; 0: the default)
   uint32_t seg2 = 0;  // slots below it: the root's and the depth-1 states' rows
   // match_longest only (cedar_replay.cpp): the states that carry one of Cedar's stale END flags, derived on the first
   // match_longest call (it replays every insert: as long again as the rest of compile); dev_longest = dev + the bitmap
@@ -227,6 +246,18 @@ struct aha_ac {
   std::vector<uint32_t> stale_states;
   int32_t stale_rc = AHA_OK;
   DevAut dev_longest{};
+};
+
+// A replacement table (aha_repl_create): immutable once made, so concurrent calls share it.  It belongs to the handle it was
+// made for by that handle's id, not by a pointer into it: either may be freed first.
+struct aha_repl {
+  uint64_t owner = 0;             // aha_ac::serial of its handle
+  int device = -1;                // -1: host copy only (a host-only handle)
+  uint32_t n_keys = 0;
+  std::vector<uint8_t> blob;
+  std::vector<aha::RepEntry> ent;  // [K]
+  void *d_blob = nullptr;
+  aha::RepEntry *d_ent = nullptr;
 };
 
 namespace ahai {
@@ -283,7 +314,7 @@ uint64_t scratch_bytes(const Scratch *sc);
 // THE allocator of the grow-only buffers: b holds at least `bytes` afterwards, or nothing (the HIP error is returned, the
 // runtime's sticky one cleared).  What a new buffer gets beyond `bytes` is its family's rule:
 enum Grow {
-  kGrowEighth,   // bytes + bytes / 8 + 256 (v2buf, covbuf, selbuf)
+  kGrowEighth,   // bytes + bytes / 8 + 256 (v2buf, covbuf, selbuf, repbuf)
   kGrowQuarter,  // bytes + bytes / 4 + 4096 (cntbuf, hostbuf)
   kGrowOrExact   // an eighth, else exactly `bytes`; `bytes` is what it records (dcbuf: what is known to be there)
 };
@@ -389,4 +420,23 @@ int32_t device_cover(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
 int32_t device_select(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
                       uint64_t n_bytes, const aha_match_params *params, aha_hit *d_out, uint64_t cap, uint64_t *d_doc_sel_offsets,
                       uint64_t *n_selected, uint64_t *n_hits, void *stream, bool offsets_checked);
+// What device_select_to does with the selection.  Without a sink (device_select, the public entries): the caller's buffer where
+// the total fits, the documents' offsets to the caller's array.  With one (device_replace): `place(kept, upto, &at)` is asked,
+// range by range, for a buffer that holds `upto` hits and still has the first `kept` ones (it returns the call's error, with
+// tls_err set, where it has none); every range is emitted as soon as it has been worked, so no range is matched twice; the
+// documents' offsets stay in selbuf[kSelDocOff], D + 1 of them.  The call's timing (profiling) is handed to `timing` and not
+// published: the caller publishes once, with its own share added.
+struct SelectSink {
+  std::function<int32_t(uint64_t kept, uint64_t upto, aha_hit **at)> place;
+  aha_timing *timing = nullptr;
+};
+int32_t device_select_to(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                         uint64_t n_bytes, const aha_match_params *params, aha_hit *d_out, uint64_t cap, uint64_t *d_doc_sel_offsets,
+                         uint64_t *n_selected, uint64_t *n_hits, void *stream, bool offsets_checked, const SelectSink *sink);
+// one device-resident batch substituted (aha_ac_replace_batch_device): device_select_to with the selection into scratch, then the
+// scan over the changes of length and the output-driven copy (scan_replace.hip)
+int32_t device_replace(aha_ac *ac, Scratch *sc, const aha_repl *table, const uint8_t *d_corpus, const uint64_t *d_doc_offsets,
+                       uint64_t n_docs, uint64_t n_bytes, const aha_match_params *params, uint8_t *d_out, uint64_t cap_bytes,
+                       uint64_t *d_doc_out_offsets, uint64_t *n_out_bytes, uint64_t *n_selected, uint64_t *n_hits, void *stream,
+                       bool offsets_checked);
 }  // namespace ahai

@@ -304,6 +304,28 @@ void select_launch_rank_docs(const uint32_t *select, const uint64_t *blk, const 
 void select_launch_emit(const uint32_t *select, uint64_t nb, const uint64_t *blk, const uint64_t *L, const uint64_t *rel, uint64_t nd,
                         void *out, uint32_t max_blocks, void *stream);
 
+// replace path (scan_replace.hip; engine.cpp device_replace), over the whole batch: its selection sel[0, n) (document by
+// document, dso[0 .. n_docs] the documents' offsets into it, dso[n_docs] = n) and the replacement table on the device.
+struct RepEntry {   // one key of a replacement table
+  uint64_t off;     // its replacement's first byte in the blob
+  uint32_t len;     // ... and its length
+  uint32_t keep;    // != 0: hits of this key stay as they are
+};
+constexpr uint32_t kRpScanBlock = 256;  // items of one block of the scan: an item per lane
+inline uint64_t replace_scan_blocks(uint64_t n) { return (n + kRpScanBlock - 1) / kRpScanBlock; }
+// start[j] = the hit's first byte in the corpus, shift[j] = its change of length (delta)
+void replace_launch_delta(const void *sel, uint64_t n, const uint64_t *dso, const uint64_t *doc_off, uint64_t n_docs,
+                          const RepEntry *ent, uint32_t n_keys, uint64_t *start, int64_t *shift, uint32_t max_blocks, void *stream);
+// shift[0, n) in place: the deltas -> their exclusive sums, shift[n] = their total; sums: replace_scan_blocks(n) + 1 words
+void replace_launch_scan(int64_t *shift, uint64_t n, int64_t *sums, uint32_t max_blocks, void *stream);
+// doc_out[d] = doc_off[d] + shift[dso[d]] for d in [0, n_docs]
+void replace_launch_doc_offsets(const uint64_t *doc_off, const uint64_t *dso, const int64_t *shift, uint64_t n_docs,
+                                uint64_t *doc_out, uint32_t max_blocks, void *stream);
+// out[0, total): the substituted copy
+void replace_launch_copy(const uint8_t *text, const void *sel, const uint64_t *start, const int64_t *shift, uint64_t n,
+                         const RepEntry *ent, uint32_t n_keys, const uint8_t *blob, uint8_t *out, uint64_t total,
+                         uint32_t max_blocks, void *stream);
+
 // exchange format of the multi-GPU all-gatherv (kernels.hip): {end, value} pairs <-> Hit triples
 void launch_hits_pack(const int32_t *hits, uint64_t n, int32_t *pairs, void *stream);
 void launch_hits_unpack(const DevAut &A, const int32_t *pairs, uint64_t n, int chars, int32_t *hits, void *stream);

@@ -209,6 +209,17 @@ lib LibAhaHip
   fun aha_ac_select_batch_device(ac : Ac, d_corpus : UInt8*, d_doc_offsets : UInt64*, n_docs : UInt64, n_bytes : UInt64,
                                  params : MatchParams*, flags : UInt32, d_out : Hit*, cap : UInt64,
                                  d_doc_sel_offsets : UInt64*, n_selected : UInt64*, n_hits : UInt64*, stream : Void*) : Int32
+  # replace: the substituted copy of a batch, built on the device from its selection; a table per handle
+  type Repl = Void*
+  fun aha_repl_create(ac : Ac, blob : UInt8*, offsets : UInt64*, keep_bits : UInt32*, out : Repl*) : Int32
+  fun aha_repl_free(table : Repl) : Void
+  fun aha_ac_replace_batch(ac : Ac, table : Repl, corpus : UInt8*, doc_offsets : UInt64*, n_docs : UInt64, params : MatchParams*,
+                           flags : UInt32, out : UInt8*, cap_bytes : UInt64, doc_out_offsets : UInt64*, n_out_bytes : UInt64*,
+                           n_selected : UInt64*, n_hits : UInt64*) : Int32
+  fun aha_ac_replace_batch_device(ac : Ac, table : Repl, d_corpus : UInt8*, d_doc_offsets : UInt64*, n_docs : UInt64,
+                                  n_bytes : UInt64, params : MatchParams*, flags : UInt32, d_out : UInt8*, cap_bytes : UInt64,
+                                  d_doc_out_offsets : UInt64*, n_out_bytes : UInt64*, n_selected : UInt64*, n_hits : UInt64*,
+                                  stream : Void*) : Int32
   # feeds: sequences that arrive in pieces across calls (offsets relative to the piece; FEED_CHARS: in characters)
   type Feed = Void*
   FEED_CHARS = 1_u32
@@ -480,6 +491,67 @@ module Aha
 
     def select(seq : String | Bytes, sep : BitArray? = nil) : Array({Int32, Int32, Int32})
       select_batch([seq.is_a?(String) ? seq.to_slice : seq], sep)[0]
+    end
+
+    # A replacement table of this handle (aha_repl_create): validated and uploaded once, used by any number of replace_batch
+    # calls.  It may outlive the handle.
+    class Replacements
+      getter handle : LibAhaHip::Repl
+
+      def initialize(@handle : LibAhaHip::Repl)
+      end
+
+      def finalize
+        LibAhaHip.aha_repl_free(@handle)
+      end
+    end
+
+    # repl[k] is key k's replacement (String or Bytes; empty: the hit is deleted), nil keeps the key's hits as they are.  One
+    # entry per key.
+    def replacements(repl : Array(String | Bytes | Nil)) : Replacements
+      blob = IO::Memory.new
+      roffs = Array(UInt64).new(repl.size + 1)
+      roffs << 0_u64
+      keep = Array(UInt32).new((repl.size + 31) // 32, 0_u32)
+      repl.each_with_index do |r, k|
+        if r.nil?
+          keep[k >> 5] |= 1_u32 << (k & 31)
+        else
+          blob.write(r.is_a?(String) ? r.to_slice : r)
+        end
+        roffs << blob.pos.to_u64
+      end
+      rc = LibAhaHip.aha_repl_create(@handle, blob.to_slice.to_unsafe, roffs.to_unsafe, keep.to_unsafe, out table)
+      raise String.new(LibAhaHip.aha_last_error(@handle)) if rc != 0
+      Replacements.new(table)
+    end
+
+    # Every document with the hits of select_batch replaced, built on the device.  Pass the table of `replacements` to use it
+    # for many batches; an array makes a table for this call alone.
+    def replace_batch(docs : Array(String) | Array(Bytes), repl : Replacements | Array(String | Bytes | Nil),
+                      sep : BitArray? = nil) : Array(Bytes)
+      table = repl.is_a?(Replacements) ? repl : replacements(repl)
+      corpus = IO::Memory.new
+      offs = Array(UInt64).new(docs.size + 1)
+      offs << 0_u64
+      docs.each do |d|
+        corpus.write(d.is_a?(String) ? d.to_slice : d)
+        offs << corpus.pos.to_u64
+      end
+      params = AC.params(false, sep)
+      doo = Array(UInt64).new(docs.size + 1, 0_u64)
+      n = 0_u64
+      rc = LibAhaHip.aha_ac_replace_batch(@handle, table.handle, corpus.to_slice.to_unsafe, offs.to_unsafe, docs.size.to_u64,
+        pointerof(params), 0_u32, Pointer(UInt8).null, 0_u64, doo.to_unsafe, pointerof(n), Pointer(UInt64).null,
+        Pointer(UInt64).null)
+      bytes = Bytes.empty
+      if rc == E_CAPACITY # n is the required size; nothing was written
+        bytes = Bytes.new(n)
+        rc = LibAhaHip.aha_ac_replace_batch(@handle, table.handle, corpus.to_slice.to_unsafe, offs.to_unsafe, docs.size.to_u64,
+          pointerof(params), 0_u32, bytes.to_unsafe, n, doo.to_unsafe, pointerof(n), Pointer(UInt64).null, Pointer(UInt64).null)
+      end
+      raise String.new(LibAhaHip.aha_last_error(@handle)) if rc != 0
+      Array.new(docs.size) { |d| bytes[doo[d], doo[d + 1] - doo[d]] }
     end
 
     private def run(seq : Bytes, chars : Bool, sep : BitArray?, longest : Int32 = 0, &block)

@@ -303,6 +303,82 @@ class AC {
   }
   std::vector<Hit> select(std::string_view seq) const { return select_batch(seq, {0, seq.size()}); }
 
+  // A replacement table of this handle (aha_repl_create): per key its replacement, or keep -- validated and uploaded once,
+  // immutable, freed with the object (before or after the handle).
+  class Replacements {
+   public:
+    Replacements() = default;
+    ~Replacements() { aha_repl_free(t_); }
+    Replacements(Replacements &&o) noexcept : t_(o.t_) { o.t_ = nullptr; }
+    Replacements &operator=(Replacements &&o) noexcept {
+      if (this != &o) {
+        aha_repl_free(t_);
+        t_ = o.t_;
+        o.t_ = nullptr;
+      }
+      return *this;
+    }
+    Replacements(const Replacements &) = delete;
+    Replacements &operator=(const Replacements &) = delete;
+    const aha_repl *handle() const { return t_; }
+
+   private:
+    friend class AC;
+    explicit Replacements(aha_repl *t) : t_(t) {}
+    aha_repl *t_ = nullptr;
+  };
+  // repl: one entry per key (an empty string deletes the key's hits); keep[k] = true: key k's hits stay as they are
+  Replacements replacements(const std::vector<std::string> &repl, const std::vector<bool> &keep = {}) const {
+    const uint32_t K = n_keys();
+    if (repl.size() != K || (!keep.empty() && keep.size() != K)) throw Error(AHA_E_INVALID, "one replacement per key");
+    std::string blob;
+    std::vector<uint64_t> offs(K + 1, 0);
+    std::vector<uint32_t> bits((K + 31) / 32 + 1, 0);
+    for (uint32_t k = 0; k < K; k++) {
+      const bool kept = !keep.empty() && keep[k];
+      if (kept)
+        bits[k >> 5] |= 1u << (k & 31);
+      else
+        blob += repl[k];
+      offs[k + 1] = blob.size();
+    }
+    aha_repl *t = nullptr;
+    int32_t rc = aha_repl_create(h_, reinterpret_cast<const uint8_t *>(blob.data()), offs.data(), bits.data(), &t);
+    if (rc != AHA_OK) {
+      const char *m = aha_last_error(h_);
+      throw Error(rc, (m && *m) ? m : aha_strerror(rc));
+    }
+    return Replacements(t);
+  }
+  // The batch with every selected hit (select_batch) replaced as the table says, built on the device (aha_ac_replace_batch):
+  // document d's result is [(*doc_out_offsets)[d], (*doc_out_offsets)[d + 1]) of what is returned.  A sizing call first.
+  std::string replace_batch(std::string_view corpus, const std::vector<uint64_t> &doc_offsets, const Replacements &table,
+                            std::vector<uint64_t> *doc_out_offsets = nullptr, uint64_t *n_selected = nullptr,
+                            uint64_t *n_hits = nullptr) const {
+    if (doc_offsets.empty()) throw Error(AHA_E_INVALID, "doc_offsets holds D + 1 entries");
+    aha_match_params p{};
+    p.struct_size = sizeof(p);
+    const uint64_t D = doc_offsets.size() - 1;
+    const uint8_t *text = reinterpret_cast<const uint8_t *>(corpus.data());
+    std::vector<uint64_t> doo(D + 1);
+    std::string out;
+    uint64_t n = 0, ns = 0, nh = 0;
+    int32_t rc = aha_ac_replace_batch(h_, table.handle(), text, doc_offsets.data(), D, &p, 0, nullptr, 0, doo.data(), &n, &ns, &nh);
+    if (rc == AHA_E_CAPACITY) {
+      out.resize(n);
+      rc = aha_ac_replace_batch(h_, table.handle(), text, doc_offsets.data(), D, &p, 0, reinterpret_cast<uint8_t *>(&out[0]),
+                                out.size(), doo.data(), &n, &ns, &nh);
+    }
+    if (rc != AHA_OK) {
+      const char *m = aha_last_error(h_);
+      throw Error(rc, (m && *m) ? m : aha_strerror(rc));
+    }
+    if (doc_out_offsets) *doc_out_offsets = std::move(doo);
+    if (n_selected) *n_selected = ns;
+    if (n_hits) *n_hits = nh;
+    return out;
+  }
+
   // Which bytes of the batch lie inside a hit of match_batch, without the hit list (aha_ac_cover_batch): bit j of the batch is
   // word j >> 5, bit j & 31 of what is returned; doc_covered (optional): covered bytes per document.
   std::vector<uint32_t> cover_batch(std::string_view corpus, const std::vector<uint64_t> &doc_offsets,

@@ -576,7 +576,7 @@ int32_t aha_ac_cover_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uin
  * compiled) the call works through ranges of whole documents (aha_timing.repeats = the ranges before the last; a document
  * beyond the bound is a range of its own) -- twice, since nothing is written before the total is known.
  * aha_ac_last_timing: engine = the engine of the match, n_hits = all hits, ms_write = everything after the match.
- * Out of scope so far: char offsets, a substituted copy made on the device, feeds, groups. */
+ * Out of scope so far: char offsets, feeds, groups (the substituted copy: the replace calls below). */
 int32_t aha_ac_select_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc_offsets, uint64_t n_docs,
                             const aha_match_params *params, uint32_t flags /* 0 */, aha_hit *out, uint64_t cap,
                             uint64_t *doc_sel_offsets /* D+1 or NULL */, uint64_t *n_selected, uint64_t *n_hits /* or NULL */);
@@ -585,6 +585,56 @@ int32_t aha_ac_select_batch_device(aha_ac *ac, const uint8_t *d_corpus, const ui
                                    uint64_t n_bytes, const aha_match_params *params, uint32_t flags, aha_hit *d_out, uint64_t cap,
                                    uint64_t *d_doc_sel_offsets /* D+1 or NULL */, uint64_t *n_selected,
                                    uint64_t *n_hits /* or NULL */, void *stream);
+
+/* ---- replace: the substituted copy of a batch, built on the device (pure additions to ABI 8) --------------------------------
+ * The same batch, params, validation and errors as aha_ac_select_batch / _device; S_d = the selection of document d as those
+ * calls report it (AHA_OPT_FOLD_ASCII included; a separator filter is allowed; offsets are bytes).
+ * A replacement table (aha_repl) gives for every key k of ONE handle either a byte string R_k -- blob[offsets[k] ..
+ * offsets[k+1]); it may be empty (deletion) and may hold NUL bytes -- or "keep" (bit k of keep_bits).  aha_repl_create
+ * validates and uploads once: a NULL handle / offsets / out, offsets[0] != 0, descending offsets, one replacement of 2^32 bytes
+ * or more: AHA_E_INVALID, *out stays NULL.  On a host-only handle the table is made with a host copy only.  A table is
+ * immutable (concurrent calls may share it) and may be freed before or after its handle; aha_repl_free(NULL) is a no-op.
+ * The result of document d: its text with every hit of S_d whose key is not kept replaced by R_value; kept hits stay as they
+ * are and still take part in the selection -- the table never changes S_d.  On a folded handle the bytes outside replaced hits
+ * are the caller's, not the folded copy's (the rule of redact).
+ * out = the documents' results one behind the other, doc_out_offsets[0 .. D] where each lies, *n_out_bytes the total;
+ * *n_selected, *n_hits (optional) as select reports them.  cap_bytes is in bytes.  AHA_E_CAPACITY: *n_out_bytes is the
+ * required size (*n_selected and *n_hits are set too, by both entries) and NONE of the caller's buffers is written -- out,
+ * doc_out_offsets, the bytes behind cap_bytes (out == NULL with cap_bytes == 0 is a sizing call; a total of 0 succeeds with
+ * cap_bytes == 0).  Every failing call leaves the caller's buffers untouched.  Two calls give identical bytes.
+ * params->char_offsets != 0, params->longest != 0, any flag bit, n_out_bytes == NULL, a NULL handle or table, a table made for
+ * another handle, out overlapping the corpus (the device entry: its address ranges, when cap_bytes > 0; there is no in-place
+ * form): AHA_E_INVALID; a host-only handle: AHA_E_NO_DEVICE; all before any device work.  Bad offsets as in select.  N = 0,
+ * D = 0, empty documents and documents without a hit are valid.  The handle's back-off state is read and never written.
+ * d_out and d_corpus may have any alignment: no load touches an aligned 16-byte piece without a byte of the corpus or of the
+ * blob, no store a byte outside [out, out + total).  Documents stay below 2 GiB; output offsets are 64-bit.
+ * Pipeline (aha_amd/csrc/scan_replace.hip): select into the call's scratch (one count and one match per
+ * document range, as select itself); per selected hit j its first corpus byte A[j] and its change of length delta[j]; a
+ * device-wide exclusive scan shift = scan(delta), signed 64-bit; the documents' output offsets doc_offsets[d] + shift[first
+ * selected hit of d]; the total comes to the host; once it fits, the copy, driven by the output: a wave owns 1024 output bytes,
+ * a lane 16; the segment of an output position q is the last j with A[j] + shift[j] <= q (deletions make ties); a tile inside
+ * one gap is two aligned 16-byte loads, a byte alignment and one aligned 16-byte store per lane, any other tile is walked
+ * segment by segment.
+ * Device scratch: select's + per selected hit 12 bytes of selection, 8 of A, 8 of shift, the scan's block sums (8 bytes per
+ * 256 selected hits) + 8 bytes per document; nothing per text byte beyond select's.  AHA_REPLACE_BLOCKS (read when the handle
+ * is compiled) caps the scan's and the copy's grids.
+ * aha_ac_last_timing: as select; ms_write = everything after the match.
+ * Out of scope so far: replacements indexed by character, feeds, groups, an in-place form, computed replacements. */
+typedef struct aha_repl aha_repl;
+int32_t aha_repl_create(aha_ac *ac, const uint8_t *blob, const uint64_t *offsets /* K+1, offsets[0] == 0, ascending */,
+                        const uint32_t *keep_bits /* ceil(K/32) words, bit k = keep key k; NULL: none kept */, aha_repl **out);
+void aha_repl_free(aha_repl *table);
+int32_t aha_ac_replace_batch(aha_ac *ac, const aha_repl *table, const uint8_t *corpus, const uint64_t *doc_offsets, uint64_t n_docs,
+                             const aha_match_params *params, uint32_t flags /* 0 */, uint8_t *out, uint64_t cap_bytes,
+                             uint64_t *doc_out_offsets /* D+1 or NULL */, uint64_t *n_out_bytes,
+                             uint64_t *n_selected /* or NULL */, uint64_t *n_hits /* or NULL */);
+/* Device-resident form: d_ pointers are HBM on the handle's device; *n_out_bytes, *n_selected, *n_hits are host memory; blocks
+ * until final. */
+int32_t aha_ac_replace_batch_device(aha_ac *ac, const aha_repl *table, const uint8_t *d_corpus, const uint64_t *d_doc_offsets,
+                                    uint64_t n_docs, uint64_t n_bytes, const aha_match_params *params, uint32_t flags /* 0 */,
+                                    uint8_t *d_out, uint64_t cap_bytes, uint64_t *d_doc_out_offsets /* D+1 or NULL */,
+                                    uint64_t *n_out_bytes, uint64_t *n_selected /* or NULL */, uint64_t *n_hits /* or NULL */,
+                                    void *stream);
 
 /* Feed cover: the same pieces as aha_feed_match_batch*, and the cover of what a match call of them on a BYTE feed in the same
  * state would report (H_d: the hits of piece d, offsets relative to the piece, start possibly negative), without the hit list.
