@@ -1303,6 +1303,98 @@ class Feed:
         """A Redactor over this feed: push(seq, piece) / finish(seq) give the redacted stream of every sequence."""
         return Redactor(self, fill)
 
+    # -- feed select: leftmost-longest, non-overlapping hits of sequences in pieces (aha_feed_select_batch*) ------------
+    def select_batch(self, corpus, piece_offsets, seq_ids, final=False, cap=None):
+        """The selected hits that this call settles (aha_feed_select_batch): for piece d, which takes its sequence from n0 to
+        n1 bytes, the hits of select(sequence so far) with a start in [F(n0), F(n1)), F(n) = max(0, n - (Lmax - 1)) -- up to
+        n1 with final=True, after which the named sequences start again from length 0.  -> (hits HIT_DTYPE, info) with
+        offsets relative to the piece (start may be negative, end may be <= 0) and info = {"piece_sel_offsets" uint64[D+1],
+        "piece_bases" uint64[D], "piece_hold" uint32[D]: the bytes at the end of the sequence whose fate is still open,
+        "n_hits"}.  Byte feeds only, and only for sequences fed through select calls alone since their last reset.
+        cap None: a sizing call first (a call that does not fit changes nothing)."""
+        if isinstance(corpus, (bytes, bytearray)):
+            corpus = np.frombuffer(bytes(corpus), dtype=np.uint8)
+        corpus = np.ascontiguousarray(corpus, dtype=np.uint8)
+        piece_offsets = np.ascontiguousarray(piece_offsets, dtype=np.uint64)
+        seq_ids = np.ascontiguousarray(seq_ids, dtype=np.uint32)
+        D = piece_offsets.size - 1
+        if seq_ids.size != D:
+            raise ValueError("one sequence id per piece")
+        flags = N.AHA_FEED_SELECT_FINAL if final else 0
+        pso = np.zeros(D + 1, dtype=np.uint64)
+        bases = np.zeros(max(D, 1), dtype=np.uint64)
+        hold = np.zeros(max(D, 1), dtype=np.uint32)
+        n, nh = C.c_uint64(0), C.c_uint64(0)
+        L = N.lib()
+        if cap is None:
+            rc = L.aha_feed_select_batch(self._h, _ptr(corpus), _ptr(piece_offsets), _ptr(seq_ids), D, flags, None, 0, _ptr(pso),
+                                         _ptr(bases), _ptr(hold), C.byref(n), C.byref(nh))
+            if rc != N.AHA_E_CAPACITY:
+                self._check(rc)
+                return np.zeros(0, dtype=HIT_DTYPE), {"piece_sel_offsets": pso, "piece_bases": bases[:D], "piece_hold": hold[:D],
+                                                      "n_hits": int(nh.value)}
+            cap = int(n.value)
+        out = np.zeros(max(int(cap), 1), dtype=HIT_DTYPE)
+        rc = L.aha_feed_select_batch(self._h, _ptr(corpus), _ptr(piece_offsets), _ptr(seq_ids), D, flags, _ptr(out), int(cap),
+                                     _ptr(pso), _ptr(bases), _ptr(hold), C.byref(n), C.byref(nh))
+        if rc == N.AHA_E_CAPACITY:
+            e = AhaError(rc, N.lib().aha_strerror(rc).decode())
+            e.n_required = int(n.value)
+            raise e
+        self._check(rc)
+        return out[: int(n.value)], {"piece_sel_offsets": pso, "piece_bases": bases[:D], "piece_hold": hold[:D],
+                                     "n_hits": int(nh.value)}
+
+    def select_batch_device(self, corpus, piece_offsets, seq_ids, out, piece_sel_offsets=None, piece_bases=None,
+                            piece_hold=None, final=False, cap=None, stream=None):
+        """Device-resident form on torch CUDA tensors: uint8 corpus, int64/uint64 piece offsets, int32/uint32 sequence ids,
+        out int32 [cap, 3] or None (a sizing call), piece_sel_offsets / piece_bases int64/uint64 [D+1] / [D] or None,
+        piece_hold int32/uint32 [D] or None.  -> (n_selected, n_hits); raises AhaError(AHA_E_CAPACITY) when out is too small
+        (e.n_required = the hits needed); nothing is written then and the feed is unchanged."""
+        import torch
+
+        assert corpus.is_cuda and corpus.dtype == torch.uint8 and corpus.is_contiguous()
+        assert piece_offsets.is_cuda and piece_offsets.dtype in (torch.int64, torch.uint64) and piece_offsets.is_contiguous()
+        assert seq_ids.is_cuda and seq_ids.dtype in (torch.int32, torch.uint32) and seq_ids.is_contiguous()
+        D = piece_offsets.numel() - 1
+        assert seq_ids.numel() >= D
+        if out is not None:
+            if not (out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.dim() == 2 and out.shape[1] == 3):
+                raise ValueError("out must be a contiguous int32 CUDA tensor of shape [cap, 3]")
+            cap = out.shape[0] if cap is None else min(int(cap), out.shape[0])
+        else:
+            cap = 0
+        for t, k in ((piece_sel_offsets, D + 1), (piece_bases, D)):
+            assert t is None or (t.is_cuda and t.dtype in (torch.int64, torch.uint64) and t.is_contiguous() and t.numel() >= k)
+        assert piece_hold is None or (piece_hold.is_cuda and piece_hold.dtype in (torch.int32, torch.uint32)
+                                      and piece_hold.is_contiguous() and piece_hold.numel() >= D)
+        n, nh = C.c_uint64(0), C.c_uint64(0)
+        s = stream if stream is not None else torch.cuda.current_stream(corpus.device).cuda_stream
+        rc = N.lib().aha_feed_select_batch_device(
+            self._h, corpus.data_ptr(), piece_offsets.data_ptr(), seq_ids.data_ptr(), D, corpus.numel(),
+            N.AHA_FEED_SELECT_FINAL if final else 0, out.data_ptr() if out is not None and cap else None, cap,
+            piece_sel_offsets.data_ptr() if piece_sel_offsets is not None else None,
+            piece_bases.data_ptr() if piece_bases is not None else None,
+            piece_hold.data_ptr() if piece_hold is not None else None, C.byref(n), C.byref(nh), C.c_void_p(s))
+        if rc == N.AHA_E_CAPACITY:
+            e = AhaError(rc, N.lib().aha_strerror(rc).decode())
+            e.n_required = int(n.value)
+            raise e
+        self._check(rc)
+        return int(n.value), int(nh.value)
+
+    def select(self, seq, piece, final=False):
+        """The next piece of one sequence: the selected hits it settles, as Hits with absolute offsets, ascending by start."""
+        b = _b(piece)
+        hits, info = self.select_batch(np.frombuffer(b, dtype=np.uint8), np.array([0, len(b)], dtype=np.uint64),
+                                       np.array([seq], dtype=np.uint32), final=final)
+        base = int(info["piece_bases"][0])
+        return [Hit(s + base, e + base, v) for s, e, v in hits.tolist()]
+
+    def replacer(self, repl):
+        """A Replacer over this feed: push(seq, piece) / finish(seq) give the substituted stream of every sequence."""
+        return Replacer(self, repl)
+
     def match(self, seq, piece):
         """The next piece of one sequence: its hits as Hits with absolute offsets."""
         b = _b(piece)
@@ -1338,6 +1430,46 @@ class Redactor:
         out = self._held.pop(seq, b"")
         self._feed.reset(seq)
         return out
+
+
+class Replacer:
+    """Substitution in sequences that arrive in pieces (Feed.replacer), host arithmetic on Feed.select_batch.  repl means what
+    it means for AC.replace: a mapping from key index to replacement (a key it does not name, or that maps to None, is kept)
+    or a sequence with one entry per key; "" deletes.  push(seq, piece) returns the substituted bytes that can no longer
+    change, finish(seq) the rest, and b"".join(pushes) + finish(seq) == matcher.replace(whole sequence, repl) as bytes.  Per
+    sequence at most W = Lmax - 1 source bytes are held on the host: those behind the cursor (piece_hold)."""
+
+    def __init__(self, feed, repl):
+        self._feed, self._repl = feed, repl
+        self._n_keys = feed._ac.n_keys
+        self._held = {}  # seq -> the source bytes behind the cursor
+
+    def _step(self, seq, piece, final):
+        b = _b(piece)
+        hits, info = self._feed.select_batch(np.frombuffer(b, dtype=np.uint8), np.array([0, len(b)], dtype=np.uint64),
+                                             np.array([seq], dtype=np.uint32), final=final)
+        # held || piece = the sequence from the old cursor on; the piece's first byte is at len(held) of it
+        held = self._held.get(seq, b"")
+        src = held + b
+        hold = int(info["piece_hold"][0])
+        done = len(src) - hold
+        if hits.size:
+            hits = hits.copy()
+            hits["start"] += len(held)
+            hits["end"] += len(held)
+        out = substitute(src[:done], hits, self._repl, self._n_keys)
+        if hold:
+            self._held[seq] = src[done:]
+        else:
+            self._held.pop(seq, None)
+        return out
+
+    def push(self, seq, piece):
+        return self._step(seq, piece, False)
+
+    def finish(self, seq):
+        """The bytes still open for seq, substituted; the sequence starts again from length 0."""
+        return self._step(seq, b"", True)
 
 
 # Aha::ACBig = ACX(Int64) (src/aha/ac.cr:9): node ids of 64 bits, the same Hit with an Int32 value (ac.cr:273) -- the

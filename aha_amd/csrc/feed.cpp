@@ -19,6 +19,10 @@
 //   kfd_cover_clear + kfd_cover_windows + kfd_scan   the mask corrected at the cuts, piece_back, piece_hit_offsets
 //   kfd_commit             the new contexts -- from the caller's text, so before an in-place redaction
 //   kv_total, kv_doc_covered, the mask's copy, kv_redact (scan_cover.hip)   each only where asked for; the redaction last
+// A select call (aha_feed_select_batch*) takes the first five steps of a match call with the hits into scratch, then
+//   scan_feedselect.hip    the pieces' extended positions, L from the sequences' tails and the hits, the masks, the walk up to the
+//                          frontier, the rank (one read-back: the total) -- above cap -> AHA_E_CAPACITY, nothing committed
+//   kfs_emit, kfd_commit + kfs_commit   the selection, the offsets; then the feed's state and, behind it, the select state
 // Calls on one feed are serialised by its mutex; its scratch is its own.  The two matches lease one of the handle's scratch
 // sets like any call, so different feeds and plain calls on the same handle run side by side.
 #include "feed.hpp"
@@ -35,18 +39,21 @@ struct aha_feed {
   std::mutex mu;
   FeedSeq *d_seqs = nullptr;
   uint8_t *d_ctx = nullptr;
+  // select calls: allocated by the feed's first one (8 W + 16 bytes per sequence)
+  FeedSelSeq *d_sel = nullptr;
+  unsigned long long *d_tail = nullptr;
   uint32_t stamp = 0;
   // grow-only scratch: 0 verdict + window size, 1 window bytes, 2 window offsets, 3 window hit offsets, 4 window hits,
   // 5 main hit offsets, 6 main hits, 7 piece hit offsets, 8 leads(ctx), 9 leads(P); 10 .. 15 the host entry's staging
   // (corpus, offsets, ids, hits, piece hit offsets, bases), 16 key counts (a count call's sums), 17 the host entry's key counts,
-  // 18 a cover call's mask, 19 / 20 the host entry's piece_back and piece_covered
-  Buf buf[21];
+  // 18 a cover call's mask, 19 / 20 the host entry's piece_back and piece_covered, 21 the host entry's piece_hold
+  Buf buf[22];
   uint64_t *h_pin = nullptr;  // pinned: read-backs
   hipStream_t hs = nullptr;   // the host entry's stream (and position / reset)
 };
 
 namespace {
-enum { kMisc, kWin, kWoff, kWdho, kWhits, kMdho, kMhits, kPho, kLeadCtx, kLeadP, kHCorpus, kHOff, kHIds, kHOut, kHPho, kHBases, kKc, kHKc, kMask, kHBack, kHCov };
+enum { kMisc, kWin, kWoff, kWdho, kWhits, kMdho, kMhits, kPho, kLeadCtx, kLeadP, kHCorpus, kHOff, kHIds, kHOut, kHPho, kHBases, kKc, kHKc, kMask, kHBack, kHCov, kHHold };
 
 void *reserve(aha_feed *f, int i, size_t bytes) {
   Buf &b = f->buf[i];
@@ -105,6 +112,10 @@ int32_t feed_windows(aha_feed *f, Scratch *sc, FeedArgs &F, hipStream_t s, bool 
   const uint32_t bad = (uint32_t)f->h_pin[0];
   if (bad & 1u) {
     tls_err = "feed: need piece_offsets[0] = 0, ascending, piece_offsets[n_pieces] = n_bytes, seq_ids below n_seqs and each once";
+    return AHA_E_INVALID;
+  }
+  if (bad & 4u) {
+    tls_err = "feed select: bytes of a named sequence went through a match, count or cover call; select works again after its reset";
     return AHA_E_INVALID;
   }
   if (bad & 2u) {
@@ -255,6 +266,134 @@ int32_t feed_cover(aha_feed *f, Scratch *sc, FeedArgs &F, hipStream_t s, uint32_
   return AHA_OK;
 }
 
+int32_t no_scratch() {
+  tls_err = "hipMalloc failed for the scratch of a feed select call";
+  return AHA_E_HIP;
+}
+
+// a whole select call on device-resident pieces.  Everything up to the total's read-back writes scratch only; the caller's
+// hits, offsets, bases and hold and the feed's state are written once the total is known to fit.
+int32_t feed_select(aha_feed *f, Scratch *sc, FeedArgs &F, uint32_t flags, aha_hit *d_out, uint64_t cap, uint64_t *d_pso,
+                    uint32_t *d_hold, hipStream_t s, uint64_t *n_selected, uint64_t *n_hits) {
+  aha_ac *ac = f->ac;
+  const uint64_t D = F.D, W = f->W;
+  if (!f->d_sel) {  // the feed's first select call: no sequence has select state yet
+    const size_t sel_bytes = (size_t)f->n_seqs * sizeof(FeedSelSeq), tail_bytes = std::max<size_t>((size_t)f->n_seqs * W * 8, 16);
+    void *a = nullptr, *b = nullptr;
+    if (hipMalloc(&a, sel_bytes) != hipSuccess || hipMalloc(&b, tail_bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      if (a) (void)hipFree(a);
+      return no_memory("select state");
+    }
+    hipError_t e = hipMemsetAsync(a, 0, sel_bytes, s);
+    if (e == hipSuccess) e = hipMemsetAsync(b, 0, tail_bytes, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+      (void)hipFree(a);
+      (void)hipFree(b);
+      HIPCHK(ac, e);
+    }
+    f->d_sel = (FeedSelSeq *)a;
+    f->d_tail = (unsigned long long *)b;
+  }
+  F.sel = f->d_sel;
+  uint64_t n_w = 0, nx = 0, ny = 0, nz = 0;
+  int32_t rc = feed_windows(f, sc, F, s, true, &n_w, &nx, &ny, &nz);
+  if (rc) return rc;
+  auto fs_reserve = [sc](FeedSelectSlot slot, size_t bytes) { return reserve_ptr(sc->fselbuf[slot], bytes, kGrowEighth); };
+  FeedSelArgs S{};
+  S.sseq = f->d_sel;
+  S.tail = f->d_tail;
+  S.final = (flags & AHA_FEED_SELECT_FINAL) ? 1u : 0u;
+  S.eoff = (uint64_t *)fs_reserve(kFsExtOff, (D + 1) * 8);
+  S.n0 = (uint64_t *)fs_reserve(kFsBases, std::max<uint64_t>(D, 1) * 8);
+  S.cend = (unsigned long long *)fs_reserve(kFsEnds, std::max<uint64_t>(D, 1) * 8);
+  S.pso = (uint64_t *)fs_reserve(kFsSelOff, (D + 1) * 8);
+  uint64_t *pho = (uint64_t *)fs_reserve(kFsHitOff, (D + 1) * 8);
+  if (!S.eoff || !S.n0 || !S.cend || !S.pso || !pho) return no_scratch();
+  S.hold = d_hold;
+  S.out = reinterpret_cast<int32_t *>(d_out);
+  // the pieces' extended positions (the ids are checked by now); their sum comes back with the main pass
+  feedsel_launch_layout(F, S, s);
+  HIPCHK(ac, hipGetLastError());
+  HIPCHK(ac, hipMemcpyAsync(f->h_pin + 2, S.eoff + D, 8, hipMemcpyDeviceToHost, s));
+  // the main pass, with the exact count where the hit buffer of the calls before is too small
+  aha_match_params p{};
+  p.struct_size = sizeof(p);
+  uint64_t n_m = 0;
+  if (!f->buf[kMhits].bytes && !reserve(f, kMhits, 1024 * sizeof(aha_hit))) return no_memory("hits");
+  for (int attempt = 0;; attempt++) {
+    const uint64_t cap_m = f->buf[kMhits].bytes / sizeof(aha_hit);
+    rc = device_match(ac, sc, F.text, F.off, D, F.n_bytes, &p, cap_m ? (aha_hit *)f->buf[kMhits].p : nullptr, cap_m,
+                      (uint64_t *)F.mdho, &n_m, s, true, nullptr, nullptr, false, true);
+    if (rc == AHA_E_CAPACITY && attempt == 0) {
+      if (!reserve(f, kMhits, std::max<uint64_t>(n_m, 1024) * sizeof(aha_hit))) return no_memory("hits");
+      continue;
+    }
+    if (rc) return rc;
+    break;
+  }
+  HIPCHK(ac, hipStreamSynchronize(s));
+  F.mhits = (const int32_t *)f->buf[kMhits].p;
+  const uint64_t n_true = (nx - ny) + (n_m - nz), NE = f->h_pin[2];
+  F.total = n_true;
+  int32_t *hits = (int32_t *)fs_reserve(kFsHits, std::max<uint64_t>(n_true, 1) * sizeof(aha_hit));
+  if (!hits) return no_scratch();
+  int32_t *caller_out = F.out;
+  uint64_t *caller_pho = F.pho;
+  F.out = hits;
+  F.pho = pho;
+  feed_launch_merge(F, s);
+  F.out = caller_out;
+  F.pho = caller_pho;
+  HIPCHK(ac, hipGetLastError());
+  S.hits = hits;
+  S.pho = pho;
+  S.n_hits = n_true;
+  S.NE = NE;
+  uint64_t total = 0;
+  const uint32_t blocks = 8u * std::max<uint32_t>(ac->v2_grid, 64u);
+  if (NE) {
+    const uint64_t n_words = (NE + 31) / 32, n_blk = select_rank_blocks(NE);
+    S.L = (unsigned long long *)fs_reserve(kFsLongest, NE * 8);
+    uint32_t *masks = (uint32_t *)fs_reserve(kFsMasks, 3 * n_words * 4);
+    S.blk = (unsigned long long *)fs_reserve(kFsBlocks, (n_blk + 1) * 8);
+    if (!S.L || !masks || !S.blk) return no_scratch();
+    S.cover = masks;
+    S.start = masks + n_words;
+    S.select = masks + 2 * n_words;
+    HIPCHK(ac, hipMemsetAsync(S.L, 0, NE * 8, s));
+    HIPCHK(ac, hipMemsetAsync(masks, 0, 3 * n_words * 4, s));
+    HIPCHK(ac, hipMemsetAsync(S.cend, 0, D * 8, s));
+    feedsel_launch_longest(F, S, blocks, s);
+    select_launch_marks((const uint64_t *)S.L, NE, S.eoff, D, S.cover, S.start, blocks, s);
+    feedsel_launch_walk(F, S, blocks, s);
+    select_launch_rank(S.select, NE, (uint64_t *)S.blk, blocks, s);
+    // (eoff[D] = NE: the last entry is the total)
+    select_launch_rank_docs(S.select, (const uint64_t *)S.blk, S.eoff, D + 1, 0, S.pso, blocks, s);
+    HIPCHK(ac, hipGetLastError());
+    HIPCHK(ac, hipMemcpyAsync(f->h_pin, S.blk + n_blk, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(ac, hipStreamSynchronize(s));
+    total = f->h_pin[0];
+  } else {
+    HIPCHK(ac, hipMemsetAsync(S.pso, 0, (D + 1) * 8, s));
+    if (D) HIPCHK(ac, hipMemsetAsync(S.cend, 0, D * 8, s));
+  }
+  *n_selected = total;
+  if (n_hits) *n_hits = n_true;
+  if (total > cap) {
+    tls_err = "output buffer too small";
+    return AHA_E_CAPACITY;
+  }
+  if (total) feedsel_launch_emit(F, S, blocks, s);
+  if (d_pso) HIPCHK(ac, hipMemcpyAsync(d_pso, S.pso, (D + 1) * 8, hipMemcpyDeviceToDevice, s));
+  feed_launch_commit(F, s);
+  feedsel_launch_commit(F, S, s);
+  HIPCHK(ac, hipGetLastError());
+  HIPCHK(ac, hipStreamSynchronize(s));
+  return AHA_OK;
+}
+
 // the part that writes: the caller's hits and offsets, then the feed's own state
 int32_t feed_finish(aha_feed *f, FeedArgs &F, hipStream_t s) {
   if (!F.pho) {
@@ -331,6 +470,8 @@ void aha_feed_free(aha_feed *f) {
       if (b.p) (void)hipFree(b.p);
     if (f->d_seqs) (void)hipFree(f->d_seqs);
     if (f->d_ctx) (void)hipFree(f->d_ctx);
+    if (f->d_sel) (void)hipFree(f->d_sel);
+    if (f->d_tail) (void)hipFree(f->d_tail);
     if (f->h_pin) (void)hipHostFree(f->h_pin);
     if (f->hs) (void)hipStreamDestroy(f->hs);
   }
@@ -348,6 +489,11 @@ int32_t aha_feed_reset(aha_feed *f, uint32_t seq) {
     HIPCHK(ac, hipMemsetAsync(f->d_seqs, 0, (size_t)f->n_seqs * sizeof(FeedSeq), f->hs));
   else
     HIPCHK(ac, hipMemsetAsync(f->d_seqs + seq, 0, 2 * sizeof(uint64_t), f->hs));
+  // the select state too: a sequence of length 0 has no open hits (its tail is never read) and its cursor is 0
+  if (f->d_sel && seq == UINT32_MAX)
+    HIPCHK(ac, hipMemsetAsync(f->d_sel, 0, (size_t)f->n_seqs * sizeof(FeedSelSeq), f->hs));
+  else if (f->d_sel)
+    HIPCHK(ac, hipMemsetAsync(f->d_sel + seq, 0, sizeof(FeedSelSeq), f->hs));
   HIPCHK(ac, hipStreamSynchronize(f->hs));
   return AHA_OK;
 }
@@ -604,5 +750,86 @@ int32_t aha_feed_cover_batch(aha_feed *f, const uint8_t *corpus, const uint64_t 
   HIPCHK(ac, hipStreamSynchronize(s));
   *n_covered = covered;
   if (n_hits) *n_hits = total;
+  return AHA_OK;
+}
+
+int32_t aha_feed_select_batch_device(aha_feed *f, const uint8_t *d_corpus, const uint64_t *d_piece_offsets,
+                                     const uint32_t *d_seq_ids, uint64_t n_pieces, uint64_t n_bytes, uint32_t flags,
+                                     aha_hit *d_out, uint64_t cap, uint64_t *d_piece_sel_offsets, uint64_t *d_piece_bases,
+                                     uint32_t *d_piece_hold, uint64_t *n_selected, uint64_t *n_hits, void *stream) {
+  if (!f || !n_selected || !d_piece_offsets || (n_pieces && !d_seq_ids) || (cap && !d_out) || (n_bytes && !d_corpus) ||
+      (flags & ~AHA_FEED_SELECT_FINAL))
+    return AHA_E_INVALID;
+  if (bad_feed(f)) return AHA_E_NO_DEVICE;
+  if (f->chars) {
+    tls_err = "feed select: a char feed (AHA_FEED_CHARS); select is in bytes";
+    return AHA_E_INVALID;
+  }
+  std::lock_guard<std::mutex> lk(f->mu);
+  DeviceGuard g(f->ac->device);
+  Lease lease(f->ac);
+  FeedArgs F{};
+  F.text = d_corpus;
+  F.off = d_piece_offsets;
+  F.ids = d_seq_ids;
+  F.D = n_pieces;
+  F.n_bytes = n_bytes;
+  F.bases = d_piece_bases;
+  *n_selected = 0;
+  if (n_hits) *n_hits = 0;
+  return feed_select(f, lease.get(), F, flags, d_out, cap, d_piece_sel_offsets, d_piece_hold, (hipStream_t)stream, n_selected, n_hits);
+}
+
+int32_t aha_feed_select_batch(aha_feed *f, const uint8_t *corpus, const uint64_t *piece_offsets, const uint32_t *seq_ids,
+                              uint64_t n_pieces, uint32_t flags, aha_hit *out, uint64_t cap, uint64_t *piece_sel_offsets,
+                              uint64_t *piece_bases, uint32_t *piece_hold, uint64_t *n_selected, uint64_t *n_hits) {
+  if (!f || !n_selected || !piece_offsets || (n_pieces && !seq_ids) || (cap && !out) || (flags & ~AHA_FEED_SELECT_FINAL))
+    return AHA_E_INVALID;
+  if (bad_feed(f)) return AHA_E_NO_DEVICE;
+  if (f->chars) {
+    tls_err = "feed select: a char feed (AHA_FEED_CHARS); select is in bytes";
+    return AHA_E_INVALID;
+  }
+  aha_ac *ac = f->ac;
+  int32_t rc = check_pieces_host(f, piece_offsets, seq_ids, n_pieces);
+  if (rc) return rc;
+  const uint64_t n_bytes = piece_offsets[n_pieces];
+  if (n_bytes && !corpus) return AHA_E_INVALID;
+  std::lock_guard<std::mutex> lk(f->mu);
+  DeviceGuard g(ac->device);
+  Lease lease(ac);
+  hipStream_t s = f->hs;
+  const uint64_t D = n_pieces;
+  uint8_t *d_corpus = (uint8_t *)reserve(f, kHCorpus, n_bytes + 64);
+  uint64_t *d_off = (uint64_t *)reserve(f, kHOff, (D + 1) * 8);
+  uint32_t *d_ids = (uint32_t *)reserve(f, kHIds, D * 4);
+  uint64_t *d_pso = (uint64_t *)reserve(f, kHPho, (D + 1) * 8);
+  uint64_t *d_bases = (uint64_t *)reserve(f, kHBases, D * 8);
+  uint32_t *d_hold = (uint32_t *)reserve(f, kHHold, D * 4);
+  // (the selection is at most the caller's cap, and at most one hit per extended position)
+  aha_hit *d_out = (aha_hit *)reserve(f, kHOut, std::min<uint64_t>(cap, n_bytes + D * f->W) * sizeof(aha_hit));
+  if (!d_corpus || !d_off || !d_ids || !d_pso || !d_bases || !d_hold || !d_out) return no_memory("staging buffers");
+  if (n_bytes) HIPCHK(ac, hipMemcpyAsync(d_corpus, corpus, n_bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(ac, hipMemcpyAsync(d_off, piece_offsets, (D + 1) * 8, hipMemcpyHostToDevice, s));
+  if (D) HIPCHK(ac, hipMemcpyAsync(d_ids, seq_ids, D * 4, hipMemcpyHostToDevice, s));
+  FeedArgs F{};
+  F.text = d_corpus;
+  F.off = d_off;
+  F.ids = d_ids;
+  F.D = D;
+  F.n_bytes = n_bytes;
+  F.bases = d_bases;
+  *n_selected = 0;
+  if (n_hits) *n_hits = 0;
+  uint64_t total = 0;
+  rc = feed_select(f, lease.get(), F, flags, d_out, cap, d_pso, d_hold, s, &total, n_hits);
+  if (rc == AHA_E_CAPACITY) *n_selected = total;
+  if (rc) return rc;
+  if (total) HIPCHK(ac, hipMemcpyAsync(out, d_out, total * sizeof(aha_hit), hipMemcpyDeviceToHost, s));
+  if (piece_sel_offsets) HIPCHK(ac, hipMemcpyAsync(piece_sel_offsets, d_pso, (D + 1) * 8, hipMemcpyDeviceToHost, s));
+  if (piece_bases && D) HIPCHK(ac, hipMemcpyAsync(piece_bases, d_bases, D * 8, hipMemcpyDeviceToHost, s));
+  if (piece_hold && D) HIPCHK(ac, hipMemcpyAsync(piece_hold, d_hold, D * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  *n_selected = total;
   return AHA_OK;
 }

@@ -11,6 +11,12 @@ struct FeedSeq {
   uint32_t bank;             // which of the two context banks holds its last min(W, bytes) bytes
 };
 
+// what a feed keeps per sequence for select calls (aha_feed_select_batch*), allocated by the feed's first one (16 bytes)
+struct FeedSelSeq {
+  unsigned long long seen;    // bytes that went through select calls since open / reset / a FINAL call
+  unsigned long long cursor;  // c: everything in front of it is final -- inside a reported hit or in no selected hit ever
+};
+
 // the arguments every feed kernel takes (by value)
 struct FeedArgs {
   const uint8_t *text;         // the caller's pieces
@@ -47,6 +53,29 @@ struct FeedArgs {
   // cover calls (aha_feed_cover_batch*): the head windows are X2 = ctx || P[0 .. min(2 W, |P|)) and P'2 = P[0 .. min(2 W, |P|))
   uint32_t *mask;              // bit j = byte j of the batch: the main pass's cover of the pieces, then corrected at the cuts
   uint32_t *back;              // [D] bytes in front of the piece inside a hit that ends in it, or null (cleared by the host)
+  // select calls (aha_feed_select_batch*): kfd_check refuses a sequence whose bytes did not all go through select calls
+  const FeedSelSeq *sel;       // [n_seqs], or null (every other call); verdict bit 2
+};
+
+// what the kernels of a select call take beside FeedArgs (scan_feedselect.hip).  The extended positions of piece d are
+// [eoff[d], eoff[d+1]): the last W'_d = min(W, n0[d]) bytes in front of the piece, then the piece.
+struct FeedSelArgs {
+  FeedSelSeq *sseq;            // [n_seqs]
+  unsigned long long *tail;    // [n_seqs][W]: entry j = the longest known hit (len << 32 | value) that starts at byte seen - W + j
+  uint32_t final;              // AHA_FEED_SELECT_FINAL
+  uint64_t *eoff;              // [D+1]
+  uint64_t *n0;                // [D] the sequence's length before the piece
+  uint64_t NE;                 // eoff[D]
+  const int32_t *hits;         // the call's true hits, piece by piece, relative to the piece (kfd_merge into scratch)
+  const uint64_t *pho;         // [D+1] where each piece's lie
+  uint64_t n_hits;
+  unsigned long long *L;       // [NE]
+  uint32_t *cover, *start, *select;  // NE bits each
+  unsigned long long *blk;     // the rank blocks of the select mask (scan_select.hip)
+  unsigned long long *cend;    // [D] the end of the piece's last selected hit as an extended position, 0: none
+  uint64_t *pso;               // [D+1] the pieces' offsets into the selection (scratch until the call is known to succeed)
+  uint32_t *hold;              // [D] the caller's piece_hold, or null
+  int32_t *out;                // the caller's hits
 };
 
 void feed_launch_check(const FeedArgs &F, void *stream);    // kfd_check, then kfd_scan of the window lengths
@@ -58,4 +87,10 @@ void feed_launch_count(const FeedArgs &F, void *stream);
 // cover calls: kfd_cover_clear (the first min(W, |P|) bits of every piece), kfd_cover_windows (the spans of the X2 hits that
 // end in the piece, F.back), kfd_scan of the hits per piece
 void feed_launch_cover(const FeedArgs &F, void *stream);
+// select calls (scan_feedselect.hip), in this order; masks, L and cend clear before feedsel_launch_longest
+void feedsel_launch_layout(const FeedArgs &F, const FeedSelArgs &S, void *stream);   // eoff, n0 (after the check)
+void feedsel_launch_longest(const FeedArgs &F, const FeedSelArgs &S, uint32_t max_blocks, void *stream);  // L: the tails, then the hits
+void feedsel_launch_walk(const FeedArgs &F, const FeedSelArgs &S, uint32_t max_blocks, void *stream);     // select, cend
+void feedsel_launch_emit(const FeedArgs &F, const FeedSelArgs &S, uint32_t max_blocks, void *stream);     // out
+void feedsel_launch_commit(const FeedArgs &F, const FeedSelArgs &S, void *stream);   // behind feed_launch_commit: tails, cursors, hold
 }  // namespace aha

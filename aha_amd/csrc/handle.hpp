@@ -117,6 +117,19 @@ enum ReplaceSlot {
   kRepDocOut,    // the documents' offsets into the result, until the call is known to succeed
   kRepCount
 };
+// fselbuf: feed select calls (feed.cpp feed_select; scan_feedselect.hip)
+enum FeedSelectSlot {
+  kFsHits,     // the call's true hits, piece by piece (kfd_merge into scratch)
+  kFsHitOff,   // where each piece's lie
+  kFsExtOff,   // the pieces' extended positions: offsets
+  kFsBases,    // the sequences' lengths before the pieces
+  kFsLongest,  // L: per extended position the longest hit that starts there, len << 32 | value
+  kFsMasks,    // the cover, piece-start and select masks, one bit per extended position each
+  kFsBlocks,   // the selected hits before every 64 words of the select mask, the total behind them
+  kFsEnds,     // per piece the end of its last selected hit
+  kFsSelOff,   // the pieces' offsets into the selection, until the call is known to succeed
+  kFsCount
+};
 // Device scratch of ONE match call (grow-only, reused by later calls that lease the same set).
 struct Scratch {
   std::mutex mu;  // held by the call that leased the set
@@ -133,6 +146,7 @@ struct Scratch {
   Buf covbuf[kCovCount];
   Buf selbuf[kSelCount];
   Buf repbuf[kRepCount];
+  Buf fselbuf[kFsCount];
   // every family above, for free_scratch and scratch_bytes (S: Scratch or const Scratch): a new family is one more line here
   template <class S, class Fn>
   static void each_buf(S &sc, Fn fn) {
@@ -143,6 +157,7 @@ struct Scratch {
     for (auto &b : sc.covbuf) fn(b);
     for (auto &b : sc.selbuf) fn(b);
     for (auto &b : sc.repbuf) fn(b);
+    for (auto &b : sc.fselbuf) fn(b);
   }
   bool dc_rows_clear = false;  // every word of dcbuf[kDcRows] is zero (kdc_compact clears what kdc_add wrote; a call that failed may not have)
   hipStream_t hs[3] = {};  // host-buffer entry: private non-blocking streams for upload, match, download
@@ -314,7 +329,7 @@ uint64_t scratch_bytes(const Scratch *sc);
 // THE allocator of the grow-only buffers: b holds at least `bytes` afterwards, or nothing (the HIP error is returned, the
 // runtime's sticky one cleared).  What a new buffer gets beyond `bytes` is its family's rule:
 enum Grow {
-  kGrowEighth,   // bytes + bytes / 8 + 256 (v2buf, covbuf, selbuf, repbuf)
+  kGrowEighth,   // bytes + bytes / 8 + 256 (v2buf, covbuf, selbuf, repbuf, fselbuf)
   kGrowQuarter,  // bytes + bytes / 4 + 4096 (cntbuf, hostbuf)
   kGrowOrExact   // an eighth, else exactly `bytes`; `bytes` is what it records (dcbuf: what is known to be there)
 };

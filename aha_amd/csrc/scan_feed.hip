@@ -65,6 +65,8 @@ __global__ void kfd_check(FeedArgs F) {
       bad |= 1u;
     else if (atomicExch(&F.seqs[id].stamp, F.stamp) == F.stamp)  // named twice in this call
       bad |= 1u;
+    else if (F.sel && F.sel[id].seen != F.seqs[id].bytes)  // a select call: bytes of the sequence went past its select state
+      bad |= 4u;
   }
   if (bad) atomicOr(F.verdict, bad);
 }

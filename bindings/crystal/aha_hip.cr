@@ -252,6 +252,15 @@ lib LibAhaHip
                                   d_redacted : UInt8*, fill : UInt8, d_piece_back : UInt32*, d_piece_covered : UInt64*,
                                   d_piece_hit_offsets : UInt64*, d_piece_bases : UInt64*, n_covered : UInt64*,
                                   n_hits : UInt64*, stream : Void*) : Int32
+  # feed select: the leftmost-longest, non-overlapping hits of the same pieces as far as they are settled (byte feeds)
+  FEED_SELECT_FINAL = 1_u32
+  fun aha_feed_select_batch(f : Feed, corpus : UInt8*, piece_offsets : UInt64*, seq_ids : UInt32*, n_pieces : UInt64,
+                            flags : UInt32, out : Hit*, cap : UInt64, piece_sel_offsets : UInt64*, piece_bases : UInt64*,
+                            piece_hold : UInt32*, n_selected : UInt64*, n_hits : UInt64*) : Int32
+  fun aha_feed_select_batch_device(f : Feed, d_corpus : UInt8*, d_piece_offsets : UInt64*, d_seq_ids : UInt32*,
+                                   n_pieces : UInt64, n_bytes : UInt64, flags : UInt32, d_out : Hit*, cap : UInt64,
+                                   d_piece_sel_offsets : UInt64*, d_piece_bases : UInt64*, d_piece_hold : UInt32*,
+                                   n_selected : UInt64*, n_hits : UInt64*, stream : Void*) : Int32
   fun aha_buffer_alloc(device : Int32, bytes : UInt64, d_ptr : Void**) : Int32
   fun aha_buffer_free(device : Int32, d_ptr : Void*) : Int32
   fun aha_buffer_upload(device : Int32, d_dst : Void*, src : Void*, bytes : UInt64) : Int32
@@ -720,6 +729,33 @@ module Aha
         raise String.new(LibAhaHip.aha_last_error(@ac.handle)) if rc != 0
         b = base.to_i32 # (raises OverflowError past 2^31)
         return Array(Hit).new(n.to_i32) { |i| Hit.new(buf[i].start + b, buf[i].end_ + b, buf[i].value) }
+      end
+    end
+
+    # The selected hits (leftmost-longest, non-overlapping, as AC#select of the whole sequence) that the next piece of one
+    # sequence settles, with absolute offsets: {hits, hold} -- hold: the bytes at the end of the sequence whose fate is still
+    # open.  final: the piece is the last of its sequence; everything settles and the sequence starts again from length 0.
+    # Byte feeds only, and only for sequences fed through select since their reset.  (Uncompiled, as the rest of this class;
+    # tests/test_feed_select_host.py checks that the lib block binds both entry points.)
+    def select(seq : Int, piece : Bytes | String, final : Bool = false) : {Array(Hit), UInt32}
+      bytes = piece.is_a?(String) ? piece.to_slice : piece
+      offs = [0_u64, bytes.size.to_u64]
+      ids = [seq.to_u32]
+      flags = final ? LibAhaHip::FEED_SELECT_FINAL : 0_u32
+      cap = 64_u64
+      loop do
+        buf = Slice(LibAhaHip::Hit).new(cap.to_i32)
+        base = 0_u64
+        hold = 0_u32
+        rc = LibAhaHip.aha_feed_select_batch(@handle, bytes.to_unsafe, offs.to_unsafe, ids.to_unsafe, 1_u64, flags,
+          buf.to_unsafe, cap, Pointer(UInt64).null, pointerof(base), pointerof(hold), out n, Pointer(UInt64).null)
+        if rc == -6 # AHA_E_CAPACITY: n is the exact count, the feed is unchanged
+          cap = n
+          next
+        end
+        raise String.new(LibAhaHip.aha_last_error(@ac.handle)) if rc != 0
+        b = base.to_i32 # (raises OverflowError past 2^31)
+        return {Array(Hit).new(n.to_i32) { |i| Hit.new(buf[i].start + b, buf[i].end_ + b, buf[i].value) }, hold}
       end
     end
 

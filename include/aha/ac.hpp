@@ -634,6 +634,55 @@ class Feed {
     if (back) *back = c.piece_back[0];
     return red;
   }
+  // What a select call of pieces gives beside the hits (aha_feed_select_batch).
+  struct Select {
+    std::vector<uint64_t> piece_sel_offsets;  // D + 1: where each piece's hits lie
+    std::vector<uint64_t> bases;              // D: the sequence's length before the piece
+    std::vector<uint32_t> piece_hold;         // D: bytes at the end of the sequence whose fate is still open
+    uint64_t n_hits = 0;                      // what match_batch of the same pieces would count
+  };
+  // The selected hits (leftmost-longest, non-overlapping, as AC::select of the whole sequence) that this call settles: for a
+  // piece that takes its sequence from n0 to n1 bytes those with a start in [F(n0), F(n1)), F(n) = max(0, n - (Lmax - 1));
+  // with final = true up to n1, and the named sequences start again from length 0.  Offsets are relative to the piece (start
+  // may be negative, end may be <= 0).  Byte feeds only, and only for sequences fed through select calls since their reset.
+  std::vector<Hit> select_batch(std::string_view corpus, const std::vector<uint64_t> &piece_offsets,
+                                const std::vector<uint32_t> &seq_ids, bool final = false, Select *info = nullptr) {
+    if (piece_offsets.empty()) throw Error(AHA_E_INVALID, "piece_offsets holds D + 1 entries");
+    const uint64_t D = piece_offsets.size() - 1;
+    if (seq_ids.size() != D) throw Error(AHA_E_INVALID, "one sequence id per piece");
+    if (corpus.size() < piece_offsets.back()) throw Error(AHA_E_INVALID, "the corpus is shorter than the last offset");
+    const uint32_t flags = final ? AHA_FEED_SELECT_FINAL : 0u;
+    Select c;
+    c.piece_sel_offsets.assign(D + 1, 0);
+    c.bases.assign(D, 0);
+    c.piece_hold.assign(D, 0);
+    std::vector<Hit> out(64);
+    uint64_t n = 0;
+    for (;;) {
+      const int32_t rc = aha_feed_select_batch(f_, reinterpret_cast<const uint8_t *>(corpus.data()), piece_offsets.data(),
+                                               seq_ids.data(), D, flags, out.data(), out.size(), c.piece_sel_offsets.data(),
+                                               D ? c.bases.data() : nullptr, D ? c.piece_hold.data() : nullptr, &n, &c.n_hits);
+      if (rc == AHA_E_CAPACITY) {  // (the feed is unchanged: the same call again)
+        out.resize(n);
+        continue;
+      }
+      check(rc);
+      break;
+    }
+    out.resize(n);
+    if (info) *info = std::move(c);
+    return out;
+  }
+  // the next piece of one sequence: the selected hits it settles, with absolute offsets (they must fit Int32)
+  std::vector<Hit> select(uint32_t seq, std::string_view piece, bool final = false) {
+    Select c;
+    auto hits = select_batch(piece, {0, piece.size()}, {seq}, final, &c);
+    for (auto &h : hits) {
+      h.start += (int32_t)c.bases[0];
+      h.end += (int32_t)c.bases[0];
+    }
+    return hits;
+  }
   void reset(uint32_t seq = UINT32_MAX) { check(aha_feed_reset(f_, seq)); }
   // {bytes, chars} fed to the sequence so far
   std::pair<uint64_t, uint64_t> position(uint32_t seq) const {

@@ -576,7 +576,8 @@ int32_t aha_ac_cover_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uin
  * compiled) the call works through ranges of whole documents (aha_timing.repeats = the ranges before the last; a document
  * beyond the bound is a range of its own) -- twice, since nothing is written before the total is known.
  * aha_ac_last_timing: engine = the engine of the match, n_hits = all hits, ms_write = everything after the match.
- * Out of scope so far: char offsets, feeds, groups (the substituted copy: the replace calls below). */
+ * Out of scope so far: char offsets, groups (the substituted copy: the replace calls below; sequences in pieces: the feed
+ * select calls below). */
 int32_t aha_ac_select_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc_offsets, uint64_t n_docs,
                             const aha_match_params *params, uint32_t flags /* 0 */, aha_hit *out, uint64_t cap,
                             uint64_t *doc_sel_offsets /* D+1 or NULL */, uint64_t *n_selected, uint64_t *n_hits /* or NULL */);
@@ -619,7 +620,8 @@ int32_t aha_ac_select_batch_device(aha_ac *ac, const uint8_t *d_corpus, const ui
  * 256 selected hits) + 8 bytes per document; nothing per text byte beyond select's.  AHA_REPLACE_BLOCKS (read when the handle
  * is compiled) caps the scan's and the copy's grids.
  * aha_ac_last_timing: as select; ms_write = everything after the match.
- * Out of scope so far: replacements indexed by character, feeds, groups, an in-place form, computed replacements. */
+ * Out of scope so far: replacements indexed by character, feeds built on the device (the selection of a stream: the feed select
+ * calls below), groups, an in-place form, computed replacements. */
 typedef struct aha_repl aha_repl;
 int32_t aha_repl_create(aha_ac *ac, const uint8_t *blob, const uint64_t *offsets /* K+1, offsets[0] == 0, ascending */,
                         const uint32_t *keep_bits /* ceil(K/32) words, bit k = keep key k; NULL: none kept */, aha_repl **out);
@@ -675,6 +677,63 @@ int32_t aha_feed_cover_batch_device(aha_feed *f, const uint8_t *d_corpus, const 
                                     uint32_t *d_mask, uint8_t *d_redacted, uint8_t fill, uint32_t *d_piece_back,
                                     uint64_t *d_piece_covered, uint64_t *d_piece_hit_offsets, uint64_t *d_piece_bases,
                                     uint64_t *n_covered, uint64_t *n_hits, void *stream);
+
+/* Feed select: the leftmost-longest, non-overlapping hits of sequences that arrive in pieces (pure additions to ABI 8).  The
+ * same pieces as aha_feed_match_batch*, on a BYTE feed.  T = one sequence, every piece since open, reset or a FINAL call,
+ * concatenated; S(T) = the selection aha_ac_select_batch reports for T as one document with default params on the same handle
+ * (AHA_OPT_FOLD_ASCII included); W = max(Lmax - 1, 0), F(n) = max(0, n - W).  A hit that starts at s ends at or before
+ * s + Lmax, so once a sequence is n bytes long every hit with a start below F(n) is known and so is the greedy choice there:
+ * the hits of S(T[0..n)) with a start below F(n) belong to S(T') for every extension T' of T, and no later text adds a selected
+ * hit in front of F(n).  A hit with a start at or behind F(n) may still lose to a longer key from the same start that only
+ * completes later (keys ab, abcde: "ab" reports nothing; "cde" then reports (0,5), as start -2).
+ * For piece d, which takes its sequence from n0 to n1 bytes, the call reports the hits of S(T[0..n1)) with a start in
+ * [F(n0), F(n1)), ascending by start: out[piece_sel_offsets[d] .. piece_sel_offsets[d+1]), each an aha_hit {start, end, value}
+ * with int32 offsets relative to the piece's first byte; start lies in [-W, |P| - W), end may be <= 0 (the hit lay wholly in
+ * earlier pieces and only now became final).  piece_bases[d] = n0: absolute = base + relative.  cap is in hits.
+ * AHA_FEED_SELECT_FINAL (bit 0 of flags): the pieces of this call are the last of their sequences -- everything settles, the
+ * starts in [F(n0), n1) are reported, and those sequences start again from length 0 as after aha_feed_reset.  A piece may be
+ * empty: "finish sequence q" is a FINAL call with one empty piece.  Any other flag bit: AHA_E_INVALID.
+ * The stream law: cut a sequence anywhere into pieces, empty ones included, feed them in order, the last call with FINAL, turn
+ * every reported hit to absolute offsets and concatenate -- the result is S(whole sequence), hit for hit, bit for bit.
+ * piece_hold[d] (uint32) = n1 - c, in [0, W], with c = max(end of the last selected hit reported so far for the sequence,
+ * F(n1)), absolute: the bytes at the end of the sequence whose fate is still open.  Everything in front of c is final -- inside a
+ * reported hit, or in no selected hit ever; 0 after FINAL.  *n_selected = all hits reported by the call; *n_hits (optional) = what
+ * aha_feed_match_batch of the same pieces would count.  Any output array may be NULL; N = 0, D = 0 and empty pieces are valid.
+ * Validation is that of the other feed entries (a sequence named twice, bad offsets, an id out of range: AHA_E_INVALID; a piece
+ * too long: AHA_E_TOO_LONG; the device entry finds these on the device).  n_selected == NULL, a NULL feed, a feed opened with
+ * AHA_FEED_CHARS (select is bytes only): AHA_E_INVALID.  AHA_E_CAPACITY: *n_selected is the required count, NONE of the
+ * caller's buffers is written and the feed is unchanged; the same call with a larger buffer gives what the first would have
+ * (out == NULL with cap == 0 is a sizing call).  Every failing call changes nothing.  Two feeds in the same state give
+ * identical bytes.  No separator filter, no match_longest, as for every feed call.
+ * Mixing: select keeps state per sequence that match, count and cover calls do not maintain (they stay exactly as they are).
+ * A select call is valid for a sequence only if every byte of it since open, reset or a FINAL call went through select calls;
+ * otherwise AHA_E_INVALID (found on the device, next to the duplicate check; aha_last_error says so) and nothing changes.  Such
+ * a sequence is usable for select again from its next aha_feed_reset, which clears the select state too.  Other sequences of
+ * the feed are not affected.
+ * Pipeline (feed.cpp, scan_feedselect.hip; DESIGN.md 4.10 "Feed select"): the context cannot give back a hit that ends inside
+ * it, so the open hits are carried: per sequence a tail of W 64-bit words len << 32 | value -- the longest known hit that
+ * starts at each of the last min(W, n) bytes --, the cursor c and the bytes seen by select.  A call runs the window batch and
+ * the main pass of a feed match with the true hits into scratch (the main pass is retried once with the exact count where the
+ * feed's hit buffer is too small; aha_ac_last_timing reports it; the handle's back-off state is read and never written), lays
+ * out the extended positions [F(n0), n1) of every piece, fills L from the tails and the hits (a 64-bit atomicMax per hit; what
+ * starts in front of c is ignored), builds the cover and piece-start masks, walks every run as select does but takes no start
+ * at or behind the piece's frontier (F(n1), or n1 under FINAL), ranks the select mask (the total comes to the host), and once
+ * the total fits emits and commits: the feed's ordinary commit, then the new tails, cursors and piece_hold.
+ * Device memory: 8 W + 16 bytes per sequence from the feed's first select call on (a feed that never selects keeps 2 W + 24);
+ * per call a feed match's with the hits in feed scratch, + 12 bytes per hit + 8 bytes and 3 bits per extended position (at most
+ * N + D W of them) + 40 bytes per piece in the handle's scratch set.  Nothing is proportional to W x hits. */
+#define AHA_FEED_SELECT_FINAL 1u /* the pieces named in this call are the last of their sequences */
+int32_t aha_feed_select_batch(aha_feed *f, const uint8_t *corpus, const uint64_t *piece_offsets, const uint32_t *seq_ids,
+                              uint64_t n_pieces, uint32_t flags, aha_hit *out, uint64_t cap,
+                              uint64_t *piece_sel_offsets /* D+1 or NULL */, uint64_t *piece_bases /* D or NULL */,
+                              uint32_t *piece_hold /* D or NULL */, uint64_t *n_selected, uint64_t *n_hits /* or NULL */);
+/* Device-resident form: d_ pointers are HBM on the handle's device, validated on the device before anything is indexed with
+ * them; *n_selected, *n_hits are host memory; blocks until final. */
+int32_t aha_feed_select_batch_device(aha_feed *f, const uint8_t *d_corpus, const uint64_t *d_piece_offsets,
+                                     const uint32_t *d_seq_ids, uint64_t n_pieces, uint64_t n_bytes, uint32_t flags,
+                                     aha_hit *d_out, uint64_t cap, uint64_t *d_piece_sel_offsets /* D+1 or NULL */,
+                                     uint64_t *d_piece_bases /* D or NULL */, uint32_t *d_piece_hold /* D or NULL */,
+                                     uint64_t *n_selected, uint64_t *n_hits /* or NULL */, void *stream);
 
 /* Frees the handle's device scratch (it grows with the largest batch seen and is otherwise kept for reuse). */
 int32_t aha_ac_release_scratch(aha_ac *ac);
