@@ -166,6 +166,9 @@ SIGNATURES = {
     "aha_ac_count_batch_device": (_i32, [_vp, _vp, _vp, _u64, _u64, C.POINTER(aha_match_params), _u32, _vp, _vp,
                                          C.POINTER(_u64), _vp]),
     "aha_feed_open": (_i32, [_vp, _u32, _u32, C.POINTER(_vp)]),
+    "aha_feed_open_params": (_i32, [_vp, _u32, _u32, C.POINTER(aha_match_params), C.POINTER(_vp)]),
+    "aha_feed_finish_batch": (_i32, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, C.POINTER(_u64)]),
+    "aha_feed_finish_batch_device": (_i32, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, C.POINTER(_u64), _vp]),
     "aha_feed_free": (None, [_vp]),
     "aha_feed_reset": (_i32, [_vp, _u32]),
     "aha_feed_position": (_i32, [_vp, _u32, C.POINTER(_u64), C.POINTER(_u64)]),

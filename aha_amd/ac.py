@@ -1029,12 +1029,18 @@ class AC:
         return buf
 
     # -- feeds: sequences that arrive in pieces (aha_feed_*) -----------------------------------------
-    def feed(self, n_seqs, chars=False):
-        """n_seqs open sequences matched piece by piece (aha_feed_open): see Feed.  chars: offsets and bases in characters."""
+    def feed(self, n_seqs, chars=False, sep=None):
+        """n_seqs open sequences matched piece by piece (aha_feed_open): see Feed.  chars: offsets and bases in characters.
+        sep: a BitArray -- the feed's match and count calls apply the separator filter of match(seq, sep) to the whole sequence
+        (aha_feed_open_params): a hit is reported one byte late, and Feed.finish ends a sequence."""
         h = C.c_void_p()
-        rc = N.lib().aha_feed_open(self._h, int(n_seqs), N.AHA_FEED_CHARS if chars else 0, C.byref(h))
+        if sep is None:
+            rc = N.lib().aha_feed_open(self._h, int(n_seqs), N.AHA_FEED_CHARS if chars else 0, C.byref(h))
+        else:
+            p = _params(False, sep)
+            rc = N.lib().aha_feed_open_params(self._h, int(n_seqs), N.AHA_FEED_CHARS if chars else 0, C.byref(p), C.byref(h))
         self._check(rc)
-        return Feed(self, h, int(n_seqs), chars)
+        return Feed(self, h, int(n_seqs), chars, sep)
 
     def set_profiling(self, enabled=True):
         self._check(N.lib().aha_ac_set_profiling(self._h, 1 if enabled else 0))
@@ -1059,10 +1065,13 @@ class Feed:
     part of sequence seq_ids[d] -- and yields exactly the hits one plain match over the whole sequence so far would report with
     an end inside the piece; a count call (count_batch, count) gives the same hits per key, a cover call (cover_batch,
     redact_batch, cover, redact, redactor) the bytes they cover.  Offsets are relative to the piece (start may be negative: the hit began in an earlier piece);
-    piece_bases[d] is the sequence's length before it, so base + offset is absolute."""
+    piece_bases[d] is the sequence's length before it, so base + offset is absolute.  A feed opened with sep (AC.feed(..,
+    sep=BitArray)) filters match and count calls as match(seq, sep) of the whole sequence does: a call reports the surviving
+    hits that end before the piece's last byte -- one that ended with the piece before has end == 0 -- and finish_batch /
+    finish report those that end with the sequence and start it again; cover and select calls are refused there."""
 
-    def __init__(self, ac, handle, n_seqs, chars):
-        self._ac, self._h, self.n_seqs, self.chars = ac, handle, n_seqs, chars
+    def __init__(self, ac, handle, n_seqs, chars, sep=None):
+        self._ac, self._h, self.n_seqs, self.chars, self.sep = ac, handle, n_seqs, chars, sep
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None
@@ -1141,6 +1150,57 @@ class Feed:
             raise e
         self._check(rc)
         return int(n.value)
+
+    # -- a feed with a separator filter: the named sequences end here (aha_feed_finish_batch*) ------------------------
+    def finish_batch(self, seq_ids, cap=None):
+        """The surviving hits that end with the named sequences, relative to each sequence's end (end == 0, start == -len):
+        -> (hits, seq_hit_offsets uint64[n+1], bases uint64[n] = the sequences' lengths).  The sequences start again at length
+        0.  Only on a feed opened with sep."""
+        seq_ids = np.ascontiguousarray(seq_ids, dtype=np.uint32)
+        D = seq_ids.size
+        sho = np.zeros(D + 1, dtype=np.uint64)
+        bases = np.zeros(max(D, 1), dtype=np.uint64)
+        if cap is None:
+            cap = max(16, 4 * D)
+        while True:
+            out = np.zeros(max(cap, 1), dtype=HIT_DTYPE)
+            n = C.c_uint64(0)
+            rc = N.lib().aha_feed_finish_batch(self._h, _ptr(seq_ids), D, _ptr(out), cap, _ptr(sho), _ptr(bases), C.byref(n))
+            if rc == N.AHA_E_CAPACITY:  # (the sequences have not restarted: the same call again)
+                cap = int(n.value)
+                continue
+            self._check(rc)
+            return out[: n.value], sho, bases[:D]
+
+    def finish_batch_device(self, seq_ids, out, seq_hit_offsets=None, bases=None, stream=None):
+        """Device-resident form on torch CUDA tensors (int32/uint32 sequence ids, int32 [cap, 3] out, int64/uint64 [n+1] / [n]
+        or None).  Returns the hit count; raises AhaError(AHA_E_CAPACITY) with .required when out is too small (the sequences
+        have then not restarted)."""
+        import torch
+
+        assert seq_ids.is_cuda and seq_ids.dtype in (torch.int32, torch.uint32) and seq_ids.is_contiguous()
+        assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous()
+        D = seq_ids.numel()
+        for t, n in ((seq_hit_offsets, D + 1), (bases, D)):
+            assert t is None or (t.is_cuda and t.dtype in (torch.int64, torch.uint64) and t.is_contiguous() and t.numel() >= n)
+        n = C.c_uint64(0)
+        s = stream if stream is not None else torch.cuda.current_stream(out.device).cuda_stream
+        rc = N.lib().aha_feed_finish_batch_device(
+            self._h, seq_ids.data_ptr() if D else None, D, out.data_ptr(), out.numel() // 3,
+            seq_hit_offsets.data_ptr() if seq_hit_offsets is not None else None,
+            bases.data_ptr() if bases is not None else None, C.byref(n), C.c_void_p(s))
+        if rc == N.AHA_E_CAPACITY:
+            e = AhaError(rc)
+            e.required = int(n.value)
+            raise e
+        self._check(rc)
+        return int(n.value)
+
+    def finish(self, seq):
+        """Sequence seq ends here: the surviving hits that end with it, as Hits with absolute offsets; it starts again."""
+        hits, _, bases = self.finish_batch(np.array([seq], dtype=np.uint32))
+        base = int(bases[0])
+        return [Hit(int(h["start"]) + base, int(h["end"]) + base, int(h["value"])) for h in hits]
 
     def count_batch(self, corpus, piece_offsets, seq_ids, per_key=True, accumulate_into=None):
         """Hits per key of match_batch on the same pieces, without the hit list (aha_feed_count_batch): -> (key_counts

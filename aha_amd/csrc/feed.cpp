@@ -23,6 +23,15 @@
 //   scan_feedselect.hip    the pieces' extended positions, L from the sequences' tails and the hits, the masks, the walk up to the
 //                          frontier, the rank (one read-back: the total) -- above cap -> AHA_E_CAPACITY, nothing committed
 //   kfs_emit, kfd_commit + kfs_commit   the selection, the offsets; then the feed's state and, behind it, the select state
+// A feed with a separator filter (aha_feed_open_params; scan_feedsep.hip, DESIGN.md 4.10 "Feed separator filter") keeps
+// W = Lmax + 1 bytes of context, so a hit that ended with the piece before and its left neighbour lie in the context.  Its match
+// and count calls take the first five steps of a match call unfiltered with the hits into scratch, then
+//   kfd_edge + kfd_scan + kfd_merge   the call's true hits piece by piece, the ones that end on the context's last byte included
+//   kfp_flag, the rank                one bit per true hit (end < |P|, both neighbours pass), the kept hits before every 2048 (one
+//                                     read-back: the total) -- above cap -> AHA_E_CAPACITY, nothing committed
+//   kfp_compact | kfp_count           the kept hits, or their values per key; the offsets from the same ranks; kfd_commit
+// and aha_feed_finish_batch* matches the named sequences' contexts as the window batch of a call of empty pieces, keeps the hits
+// that end on the last byte and pass on the left, and sets those sequences back to length 0 (kfp_restart).
 // Calls on one feed are serialised by its mutex; its scratch is its own.  The two matches lease one of the handle's scratch
 // sets like any call, so different feeds and plain calls on the same handle run side by side.
 #include "feed.hpp"
@@ -34,8 +43,10 @@ using namespace ahai;
 struct aha_feed {
   aha_ac *ac = nullptr;
   uint32_t n_seqs = 0;
-  uint32_t W = 0;
+  uint32_t W = 0;  // bytes of context per sequence: max(Lmax - 1, 0), or Lmax + 1 with a separator filter
   bool chars = false;
+  bool sep = false;         // opened with a separator filter: W = Lmax + 1, match and count calls report a hit one byte late
+  uint32_t blocked[8] = {};  // bit c: byte c does not pass (c < sep_size && !sep[c])
   std::mutex mu;
   FeedSeq *d_seqs = nullptr;
   uint8_t *d_ctx = nullptr;
@@ -195,7 +206,9 @@ int32_t feed_prepare(aha_feed *f, Scratch *sc, FeedArgs &F, uint64_t cap, hipStr
 
 // a whole count call on device-resident pieces: the windows, the main pass into the feed's vector, the window hits added,
 // then -- nothing the caller owns is written before -- the caller's key counts and offsets and the feed's state
+int32_t feed_sep_count(aha_feed *f, Scratch *sc, FeedArgs &F, hipStream_t s, uint64_t *total);
 int32_t feed_count(aha_feed *f, Scratch *sc, FeedArgs &F, hipStream_t s, uint64_t *total) {
+  if (f->sep) return feed_sep_count(f, sc, F, s, total);
   aha_ac *ac = f->ac;
   const bool per_key = F.key_counts != nullptr;
   uint64_t n_w = 0, nx = 0, ny = 0, nz = 0;
@@ -407,6 +420,188 @@ int32_t feed_finish(aha_feed *f, FeedArgs &F, hipStream_t s) {
   return AHA_OK;
 }
 
+int32_t no_sep_scratch() {
+  tls_err = "hipMalloc failed for the scratch of a call on a feed with a separator filter";
+  return AHA_E_HIP;
+}
+
+int32_t sep_refused(const char *what) {
+  tls_err = std::string("feed ") + what + ": the feed has a separator filter, which feed " + what +
+            " calls do not take yet (a follow-up); feed match and count calls do";
+  return AHA_E_INVALID;
+}
+
+uint32_t sep_blocks(const aha_ac *ac) { return 8u * std::max<uint32_t>(ac->v2_grid, 64u); }
+
+// the keep mask of P.n_true hits and its rank; *n_kept = the total (one read-back)
+int32_t feed_sep_rank(aha_feed *f, Scratch *sc, const FeedArgs &F, FeedSepArgs &P, bool finish, hipStream_t s, uint64_t *n_kept) {
+  aha_ac *ac = f->ac;
+  *n_kept = 0;
+  if (!P.n_true) return AHA_OK;
+  const uint64_t n_blk = select_rank_blocks(P.n_true);
+  P.keep = (unsigned long long *)reserve_ptr(sc->fsepbuf[kFpKeep], ((P.n_true + 63) / 64) * 8, kGrowEighth);
+  P.blk = (unsigned long long *)reserve_ptr(sc->fsepbuf[kFpBlocks], (n_blk + 1) * 8, kGrowEighth);
+  if (!P.keep || !P.blk) return no_sep_scratch();
+  if (finish)
+    feedsep_launch_flag_finish(F, P, sep_blocks(ac), s);
+  else
+    feedsep_launch_flag(F, P, sep_blocks(ac), s);
+  select_launch_rank(reinterpret_cast<const uint32_t *>(P.keep), P.n_true, reinterpret_cast<uint64_t *>(P.blk), sep_blocks(ac), s);
+  HIPCHK(ac, hipGetLastError());
+  HIPCHK(ac, hipMemcpyAsync(f->h_pin, P.blk + n_blk, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  *n_kept = f->h_pin[0];
+  return AHA_OK;
+}
+
+// the filtered offsets: the rank at every piece's first true hit (off: D + 1 entries, off[D] = P.n_true)
+int32_t feed_sep_offsets(aha_feed *f, const FeedSepArgs &P, const uint64_t *off, uint64_t D, uint64_t *d_out, hipStream_t s) {
+  if (!d_out) return AHA_OK;
+  if (P.n_true)
+    select_launch_rank_docs(reinterpret_cast<const uint32_t *>(P.keep), reinterpret_cast<const uint64_t *>(P.blk), off, D + 1, 0, d_out,
+                            sep_blocks(f->ac), s);
+  else
+    HIPCHK(f->ac, hipMemsetAsync(d_out, 0, (D + 1) * 8, s));
+  return AHA_OK;
+}
+
+// the part of a match or count call on a feed with a separator filter that writes scratch only: the windows and the main pass
+// unfiltered, the call's true hits piece by piece (the hits that ended with the pieces before included), the keep mask and its
+// rank.  *n_kept = the hits the call reports, also F.total.
+int32_t feed_sep_true(aha_feed *f, Scratch *sc, FeedArgs &F, hipStream_t s, FeedSepArgs &P, uint64_t *n_kept) {
+  aha_ac *ac = f->ac;
+  const uint64_t D = F.D;
+  uint64_t n_w = 0, nx = 0, ny = 0, nz = 0;
+  int32_t rc = feed_windows(f, sc, F, s, true, &n_w, &nx, &ny, &nz);
+  if (rc) return rc;
+  // the main pass, with the exact count where the hit buffer of the calls before is too small (the caller's cap says nothing
+  // about the unfiltered hits); like a count call it writes none of the handle's back-off state
+  aha_match_params p{};
+  p.struct_size = sizeof(p);
+  uint64_t n_m = 0;
+  if (!f->buf[kMhits].bytes && !reserve(f, kMhits, 1024 * sizeof(aha_hit))) return no_memory("hits");
+  for (int attempt = 0;; attempt++) {
+    const uint64_t cap_m = f->buf[kMhits].bytes / sizeof(aha_hit);
+    rc = device_match(ac, sc, F.text, F.off, D, F.n_bytes, &p, cap_m ? (aha_hit *)f->buf[kMhits].p : nullptr, cap_m,
+                      (uint64_t *)F.mdho, &n_m, s, true, nullptr, nullptr, false, true);
+    if (rc == AHA_E_CAPACITY && attempt == 0) {
+      if (!reserve(f, kMhits, std::max<uint64_t>(n_m, 1024) * sizeof(aha_hit))) return no_memory("hits");
+      continue;
+    }
+    if (rc) return rc;
+    break;
+  }
+  F.mhits = (const int32_t *)f->buf[kMhits].p;
+  F.edge = (uint64_t *)reserve_ptr(sc->fsepbuf[kFpEdge], std::max<uint64_t>(D, 1) * 8, kGrowEighth);
+  uint64_t *tho = (uint64_t *)reserve_ptr(sc->fsepbuf[kFpTrueOff], (D + 1) * 8, kGrowEighth);
+  if (!F.edge || !tho) return no_sep_scratch();
+  int32_t *caller_out = F.out;
+  uint64_t *caller_pho = F.pho;
+  F.pho = tho;
+  feed_launch_edge(F, s);
+  HIPCHK(ac, hipGetLastError());
+  HIPCHK(ac, hipMemcpyAsync(f->h_pin, tho + D, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  const uint64_t n_true = f->h_pin[0];
+  int32_t *hits = (int32_t *)reserve_ptr(sc->fsepbuf[kFpTrue], std::max<uint64_t>(n_true, 1) * sizeof(aha_hit), kGrowEighth);
+  if (!hits) return no_sep_scratch();
+  F.out = hits;
+  F.total = n_true;
+  feed_launch_merge_edge(F, s);
+  F.out = caller_out;
+  F.pho = caller_pho;
+  HIPCHK(ac, hipGetLastError());
+  memcpy(P.blocked, f->blocked, sizeof(P.blocked));
+  P.fold = ac->fold() ? 1u : 0u;
+  P.hits = hits;
+  P.tho = tho;
+  P.n_true = n_true;
+  if ((rc = feed_sep_rank(f, sc, F, P, false, s, n_kept))) return rc;
+  F.total = *n_kept;
+  return AHA_OK;
+}
+
+int32_t feed_sep_prepare(aha_feed *f, Scratch *sc, FeedArgs &F, uint64_t cap, hipStream_t s, FeedSepArgs &P, uint64_t *total) {
+  int32_t rc = feed_sep_true(f, sc, F, s, P, total);
+  if (rc) return rc;
+  if (*total > cap) {
+    tls_err = "output buffer too small";
+    return AHA_E_CAPACITY;
+  }
+  return AHA_OK;
+}
+
+// the part that writes: the kept hits and their offsets, then the feed's own state
+int32_t feed_sep_emit(aha_feed *f, FeedArgs &F, FeedSepArgs &P, hipStream_t s) {
+  P.out = F.out;
+  if (F.total) feedsep_launch_compact(P, false, sep_blocks(f->ac), s);
+  int32_t rc = feed_sep_offsets(f, P, P.tho, F.D, F.pho, s);
+  if (rc) return rc;
+  feed_launch_commit(F, s);
+  HIPCHK(f->ac, hipGetLastError());
+  HIPCHK(f->ac, hipStreamSynchronize(s));
+  return AHA_OK;
+}
+
+// a whole count call on a feed with a separator filter: the true hit list is built in scratch as for a match call (12 bytes per
+// unfiltered hit: what this count form costs beyond the plain one), the kept hits' values summed per key
+int32_t feed_sep_count(aha_feed *f, Scratch *sc, FeedArgs &F, hipStream_t s, uint64_t *total) {
+  aha_ac *ac = f->ac;
+  FeedSepArgs P{};
+  int32_t rc = feed_sep_true(f, sc, F, s, P, total);
+  if (rc) return rc;
+  F.K = ac->aut.n_keys;
+  if (F.key_counts && F.K) {
+    F.kc = (unsigned long long *)reserve(f, kKc, (size_t)F.K * 8);
+    if (!F.kc) return no_memory("key counts");
+    HIPCHK(ac, hipMemsetAsync(F.kc, 0, (size_t)F.K * 8, s));
+    if (*total) feedsep_launch_count(F, P, sep_blocks(ac), s);
+    feedsep_launch_count_finish(F, sep_blocks(ac), s);
+  }
+  if ((rc = feed_sep_offsets(f, P, P.tho, F.D, F.pho, s))) return rc;
+  feed_launch_commit(F, s);
+  HIPCHK(ac, hipGetLastError());
+  HIPCHK(ac, hipStreamSynchronize(s));
+  return AHA_OK;
+}
+
+// a whole finish call on device-resident ids: the named sequences' contexts matched as the window batch of a call of empty
+// pieces (which checks the ids on the device: kfd_check), the hits of its X block that end on the context's last byte and pass on
+// the left.  Everything up to the total's read-back writes scratch only.
+int32_t feed_finish_sep(aha_feed *f, Scratch *sc, const uint32_t *d_ids, uint64_t D, aha_hit *d_out, uint64_t cap, uint64_t *d_sho,
+                        uint64_t *d_bases, hipStream_t s, uint64_t *total) {
+  aha_ac *ac = f->ac;
+  uint64_t *zero = (uint64_t *)reserve_ptr(sc->fsepbuf[kFpZeroOff], (D + 1) * 8, kGrowEighth);
+  if (!zero) return no_sep_scratch();
+  HIPCHK(ac, hipMemsetAsync(zero, 0, (D + 1) * 8, s));
+  FeedArgs F{};
+  F.off = zero;
+  F.ids = d_ids;
+  F.D = D;
+  uint64_t n_w = 0, nx = 0, ny = 0, nz = 0;
+  int32_t rc = feed_windows(f, sc, F, s, true, &n_w, &nx, &ny, &nz);
+  if (rc) return rc;
+  FeedSepArgs P{};
+  memcpy(P.blocked, f->blocked, sizeof(P.blocked));
+  P.fold = ac->fold() ? 1u : 0u;
+  P.hits = F.whits;
+  P.tho = F.wdho;  // (its first D + 1 entries: the X block)
+  P.n_true = nx;
+  P.out = reinterpret_cast<int32_t *>(d_out);
+  P.bases = d_bases;
+  if ((rc = feed_sep_rank(f, sc, F, P, true, s, total))) return rc;
+  if (*total > cap) {
+    tls_err = "output buffer too small";
+    return AHA_E_CAPACITY;
+  }
+  if (*total) feedsep_launch_compact(P, true, sep_blocks(ac), s);
+  if ((rc = feed_sep_offsets(f, P, F.wdho, D, d_sho, s))) return rc;
+  feedsep_launch_restart(F, P, s);
+  HIPCHK(ac, hipGetLastError());
+  HIPCHK(ac, hipStreamSynchronize(s));
+  return AHA_OK;
+}
+
 bool bad_feed(const aha_feed *f) { return !f || !f->ac || f->ac->device < 0; }
 
 // the checks kfd_check makes, on the host (the host entries)
@@ -428,8 +623,28 @@ int32_t check_pieces_host(const aha_feed *f, const uint64_t *piece_offsets, cons
 }  // namespace
 
 int32_t aha_feed_open(aha_ac *ac, uint32_t n_seqs, uint32_t flags, aha_feed **out) {
+  return aha_feed_open_params(ac, n_seqs, flags, nullptr, out);
+}
+
+int32_t aha_feed_open_params(aha_ac *ac, uint32_t n_seqs, uint32_t flags, const aha_match_params *params, aha_feed **out) {
   if (!ac || !out || n_seqs == 0 || (flags & ~AHA_FEED_CHARS)) return AHA_E_INVALID;
   *out = nullptr;
+  const bool sep = params && params->sep_size > 0;
+  if (params) {
+    if (params->sep_size > 256) {
+      tls_err = "sep BitArray size > 256 is not supported";
+      return AHA_E_SEP_SIZE;
+    }
+    const bool has_longest = params->struct_size >= offsetof(aha_match_params, longest) + sizeof(int32_t);
+    if (params->char_offsets || (has_longest && params->longest)) {
+      tls_err = "aha_feed_open_params: only the separator filter; a feed counts in characters with AHA_FEED_CHARS and has no match_longest";
+      return AHA_E_INVALID;
+    }
+    if (sep && (flags & AHA_FEED_CHARS)) {
+      tls_err = "aha_feed_open_params: a separator filter on a char feed (AHA_FEED_CHARS) is not supported";
+      return AHA_E_INVALID;
+    }
+  }
   if (ac->device < 0) {
     tls_err = aha_strerror(AHA_E_NO_DEVICE);
     return AHA_E_NO_DEVICE;
@@ -441,6 +656,12 @@ int32_t aha_feed_open(aha_ac *ac, uint32_t n_seqs, uint32_t flags, aha_feed **ou
   f->n_seqs = n_seqs;
   f->W = ac->aut.max_key_len ? ac->aut.max_key_len - 1 : 0;
   f->chars = (flags & AHA_FEED_CHARS) != 0;
+  if (sep) {  // a hit that ends on the context's last byte and its left neighbour lie in the context: Lmax + 1 bytes
+    f->sep = true;
+    f->W = ac->aut.max_key_len + 1;
+    for (int c = 0; c < params->sep_size; c++)
+      if (!((params->sep_bits[c >> 3] >> (c & 7)) & 1)) f->blocked[c >> 5] |= 1u << (c & 31);
+  }
   const size_t ctx_bytes = std::max<size_t>(2ull * n_seqs * f->W, 16);
   int32_t rc = AHA_OK;
   if (hipMalloc((void **)&f->d_seqs, (size_t)n_seqs * sizeof(FeedSeq)) != hipSuccess ||
@@ -533,10 +754,11 @@ int32_t aha_feed_match_batch_device(aha_feed *f, const uint8_t *d_corpus, const 
   F.bases = d_piece_bases;
   uint64_t total = 0;
   *n_hits = 0;
-  int32_t rc = feed_prepare(f, lease.get(), F, cap, s, &total);
+  FeedSepArgs P{};
+  int32_t rc = f->sep ? feed_sep_prepare(f, lease.get(), F, cap, s, P, &total) : feed_prepare(f, lease.get(), F, cap, s, &total);
   if (rc == AHA_E_CAPACITY) *n_hits = total;
   if (rc) return rc;
-  if ((rc = feed_finish(f, F, s))) return rc;
+  if ((rc = f->sep ? feed_sep_emit(f, F, P, s) : feed_finish(f, F, s))) return rc;
   *n_hits = total;
   return AHA_OK;
 }
@@ -575,13 +797,14 @@ int32_t aha_feed_match_batch(aha_feed *f, const uint8_t *corpus, const uint64_t 
   F.bases = d_bases;
   uint64_t total = 0;
   *n_hits = 0;
-  rc = feed_prepare(f, lease.get(), F, cap, s, &total);
+  FeedSepArgs P{};
+  rc = f->sep ? feed_sep_prepare(f, lease.get(), F, cap, s, P, &total) : feed_prepare(f, lease.get(), F, cap, s, &total);
   if (rc == AHA_E_CAPACITY) *n_hits = total;
   if (rc) return rc;
   aha_hit *d_out = (aha_hit *)reserve(f, kHOut, total * sizeof(aha_hit));
   if (!d_out) return no_memory("hits");
   F.out = reinterpret_cast<int32_t *>(d_out);
-  if ((rc = feed_finish(f, F, s))) return rc;
+  if ((rc = f->sep ? feed_sep_emit(f, F, P, s) : feed_finish(f, F, s))) return rc;
   if (total) HIPCHK(ac, hipMemcpyAsync(out, d_out, total * sizeof(aha_hit), hipMemcpyDeviceToHost, s));
   if (piece_hit_offsets) HIPCHK(ac, hipMemcpyAsync(piece_hit_offsets, d_pho, (D + 1) * 8, hipMemcpyDeviceToHost, s));
   if (piece_bases && D) HIPCHK(ac, hipMemcpyAsync(piece_bases, d_bases, D * 8, hipMemcpyDeviceToHost, s));
@@ -590,6 +813,74 @@ int32_t aha_feed_match_batch(aha_feed *f, const uint8_t *corpus, const uint64_t 
   return AHA_OK;
 }
 
+
+int32_t aha_feed_finish_batch_device(aha_feed *f, const uint32_t *d_seq_ids, uint64_t n_named, aha_hit *d_out, uint64_t cap,
+                                     uint64_t *d_seq_hit_offsets, uint64_t *d_bases, uint64_t *n_hits, void *stream) {
+  if (!f || !n_hits || (n_named && !d_seq_ids) || (cap && !d_out)) return AHA_E_INVALID;
+  if (bad_feed(f)) return AHA_E_NO_DEVICE;
+  if (!f->sep) {
+    tls_err = "feed finish: the feed has no separator filter (aha_feed_open_params); its sequences end with aha_feed_reset";
+    return AHA_E_INVALID;
+  }
+  std::lock_guard<std::mutex> lk(f->mu);
+  DeviceGuard g(f->ac->device);
+  Lease lease(f->ac);
+  uint64_t total = 0;
+  *n_hits = 0;
+  int32_t rc = feed_finish_sep(f, lease.get(), d_seq_ids, n_named, d_out, cap, d_seq_hit_offsets, d_bases, (hipStream_t)stream, &total);
+  if (rc == AHA_E_CAPACITY) *n_hits = total;
+  if (rc) return rc;
+  *n_hits = total;
+  return AHA_OK;
+}
+
+int32_t aha_feed_finish_batch(aha_feed *f, const uint32_t *seq_ids, uint64_t n_named, aha_hit *out, uint64_t cap,
+                              uint64_t *seq_hit_offsets, uint64_t *bases, uint64_t *n_hits) {
+  if (!f || !n_hits || (n_named && !seq_ids) || (cap && !out)) return AHA_E_INVALID;
+  if (bad_feed(f)) return AHA_E_NO_DEVICE;
+  if (!f->sep) {
+    tls_err = "feed finish: the feed has no separator filter (aha_feed_open_params); its sequences end with aha_feed_reset";
+    return AHA_E_INVALID;
+  }
+  aha_ac *ac = f->ac;
+  {
+    std::vector<uint8_t> seen;
+    try {
+      seen.assign(f->n_seqs, 0);
+    } catch (...) {
+      return AHA_E_NOMEM;
+    }
+    for (uint64_t d = 0; d < n_named; d++)
+      if (seq_ids[d] >= f->n_seqs || seen[seq_ids[d]]++) {
+        tls_err = "feed finish: need seq_ids below n_seqs and each once";
+        return AHA_E_INVALID;
+      }
+  }
+  std::lock_guard<std::mutex> lk(f->mu);
+  DeviceGuard g(ac->device);
+  Lease lease(ac);
+  hipStream_t s = f->hs;
+  const uint64_t D = n_named;
+  // (a sequence ends at most Lmax hits: one per key length)
+  const uint64_t cap_d = std::min<uint64_t>(cap, D * std::max<uint64_t>(ac->aut.max_key_len, 1));
+  uint32_t *d_ids = (uint32_t *)reserve(f, kHIds, D * 4);
+  uint64_t *d_sho = (uint64_t *)reserve(f, kHPho, (D + 1) * 8);
+  uint64_t *d_bases = (uint64_t *)reserve(f, kHBases, D * 8);
+  aha_hit *d_out = (aha_hit *)reserve(f, kHOut, cap_d * sizeof(aha_hit));
+  if (!d_ids || !d_sho || !d_bases || !d_out) return no_memory("staging buffers");
+  if (D) HIPCHK(ac, hipMemcpyAsync(d_ids, seq_ids, D * 4, hipMemcpyHostToDevice, s));
+  uint64_t total = 0;
+  *n_hits = 0;
+  int32_t rc = feed_finish_sep(f, lease.get(), d_ids, D, d_out, cap_d, d_sho, d_bases, s, &total);
+  if (rc == AHA_E_CAPACITY) *n_hits = total;
+  if (rc) return rc;
+  if (total) HIPCHK(ac, hipMemcpyAsync(out, d_out, total * sizeof(aha_hit), hipMemcpyDeviceToHost, s));
+  if (seq_hit_offsets) HIPCHK(ac, hipMemcpyAsync(seq_hit_offsets, d_sho, (D + 1) * 8, hipMemcpyDeviceToHost, s));
+  if (bases && D) HIPCHK(ac, hipMemcpyAsync(bases, d_bases, D * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  *n_hits = total;
+  return AHA_OK;
+}
 
 int32_t aha_feed_count_batch_device(aha_feed *f, const uint8_t *d_corpus, const uint64_t *d_piece_offsets,
                                     const uint32_t *d_seq_ids, uint64_t n_pieces, uint64_t n_bytes, uint32_t flags,
@@ -676,6 +967,7 @@ int32_t aha_feed_cover_batch_device(aha_feed *f, const uint8_t *d_corpus, const 
                                     uint64_t *n_covered, uint64_t *n_hits, void *stream) {
   if (!f || !n_covered || !d_piece_offsets || (n_pieces && !d_seq_ids) || (n_bytes && !d_corpus) || flags) return AHA_E_INVALID;
   if (bad_feed(f)) return AHA_E_NO_DEVICE;
+  if (f->sep) return sep_refused("cover");
   std::lock_guard<std::mutex> lk(f->mu);
   DeviceGuard g(f->ac->device);
   Lease lease(f->ac);
@@ -706,6 +998,7 @@ int32_t aha_feed_cover_batch(aha_feed *f, const uint8_t *corpus, const uint64_t 
                              uint64_t *n_covered, uint64_t *n_hits) {
   if (!f || !n_covered || !piece_offsets || (n_pieces && !seq_ids) || flags) return AHA_E_INVALID;
   if (bad_feed(f)) return AHA_E_NO_DEVICE;
+  if (f->sep) return sep_refused("cover");
   aha_ac *ac = f->ac;
   int32_t rc = check_pieces_host(f, piece_offsets, seq_ids, n_pieces);
   if (rc) return rc;
@@ -765,6 +1058,7 @@ int32_t aha_feed_select_batch_device(aha_feed *f, const uint8_t *d_corpus, const
     tls_err = "feed select: a char feed (AHA_FEED_CHARS); select is in bytes";
     return AHA_E_INVALID;
   }
+  if (f->sep) return sep_refused("select");
   std::lock_guard<std::mutex> lk(f->mu);
   DeviceGuard g(f->ac->device);
   Lease lease(f->ac);
@@ -790,6 +1084,7 @@ int32_t aha_feed_select_batch(aha_feed *f, const uint8_t *corpus, const uint64_t
     tls_err = "feed select: a char feed (AHA_FEED_CHARS); select is in bytes";
     return AHA_E_INVALID;
   }
+  if (f->sep) return sep_refused("select");
   aha_ac *ac = f->ac;
   int32_t rc = check_pieces_host(f, piece_offsets, seq_ids, n_pieces);
   if (rc) return rc;

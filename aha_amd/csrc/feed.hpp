@@ -23,7 +23,7 @@ struct FeedArgs {
   const uint64_t *off;         // [D+1] piece offsets
   const uint32_t *ids;         // [D] sequence ids
   uint64_t D, n_bytes, n_seqs;
-  uint32_t W;                  // max(Lmax - 1, 0)
+  uint32_t W;                  // max(Lmax - 1, 0); Lmax + 1 on a feed with a separator filter
   uint32_t Wp;                 // bytes of the piece in the head windows X and P': W, or 2 W for a cover call
   uint32_t stamp;              // this call's stamp (never 0)
   uint64_t max_piece;          // a piece must be shorter than this
@@ -55,6 +55,24 @@ struct FeedArgs {
   uint32_t *back;              // [D] bytes in front of the piece inside a hit that ends in it, or null (cleared by the host)
   // select calls (aha_feed_select_batch*): kfd_check refuses a sequence whose bytes did not all go through select calls
   const FeedSelSeq *sel;       // [n_seqs], or null (every other call); verdict bit 2
+  // calls on a feed with a separator filter (aha_feed_open_params; scan_feedsep.hip): the call's true hits also hold the hits
+  // that end on the context's last byte -- the last edge[d] hits of ctx_d alone
+  uint64_t *edge;              // [D], or null (every call on a plain feed)
+};
+
+// what the kernels of a call on a feed with a separator filter take beside FeedArgs (scan_feedsep.hip).  The call's true hits
+// are those of the sequence with an end in [n0, n1], relative to the piece (end = 0: the hit ended with the piece before); a
+// finish call's are the hits of the named sequences' contexts alone (the X block of a window batch of empty pieces).
+struct FeedSepArgs {
+  const int32_t *hits;         // the true hits, piece by piece (kfd_merge into scratch; a finish call: the window hits)
+  const uint64_t *tho;         // [D+1] where each piece's lie
+  uint64_t n_true;
+  uint32_t blocked[8];         // bit c: byte c does not pass (c < sep_size && !sep[c])
+  uint32_t fold;               // the handle folds (AHA_OPT_FOLD_ASCII): the neighbours are folded before the test
+  unsigned long long *keep;    // one bit per true hit: it survives and its end lies in [n0, n1) (a finish call: end = n)
+  unsigned long long *blk;     // the rank blocks of the keep mask (scan_select.hip)
+  int32_t *out;                // the caller's hits
+  uint64_t *bases;             // a finish call: [D] the sequences' lengths, or null
 };
 
 // what the kernels of a select call take beside FeedArgs (scan_feedselect.hip).  The extended positions of piece d are
@@ -82,6 +100,10 @@ void feed_launch_check(const FeedArgs &F, void *stream);    // kfd_check, then k
 void feed_launch_windows(const FeedArgs &F, void *stream);  // kfd_windows (+ kfd_leads on char feeds)
 void feed_launch_merge(const FeedArgs &F, void *stream);    // kfd_scan of the hits per piece, kfd_merge
 void feed_launch_commit(const FeedArgs &F, void *stream);   // kfd_commit: bases, counters, the new contexts
+// a feed with a separator filter: kfd_edge (F.edge) and kfd_scan of the true hits per piece into F.pho; then, with F.total read
+// back from F.pho[D], kfd_merge of the true hits, the edge hits in front of every piece's
+void feed_launch_edge(const FeedArgs &F, void *stream);
+void feed_launch_merge_edge(const FeedArgs &F, void *stream);
 // count calls: kfd_count_windows (F.kc), kfd_scan of the hits per piece, kfd_count_finish (F.key_counts)
 void feed_launch_count(const FeedArgs &F, void *stream);
 // cover calls: kfd_cover_clear (the first min(W, |P|) bits of every piece), kfd_cover_windows (the spans of the X2 hits that
@@ -93,4 +115,12 @@ void feedsel_launch_longest(const FeedArgs &F, const FeedSelArgs &S, uint32_t ma
 void feedsel_launch_walk(const FeedArgs &F, const FeedSelArgs &S, uint32_t max_blocks, void *stream);     // select, cend
 void feedsel_launch_emit(const FeedArgs &F, const FeedSelArgs &S, uint32_t max_blocks, void *stream);     // out
 void feedsel_launch_commit(const FeedArgs &F, const FeedSelArgs &S, void *stream);   // behind feed_launch_commit: tails, cursors, hold
+// calls on a feed with a separator filter (scan_feedsep.hip), in this order; the rank between flag and compact is
+// select_launch_rank, the filtered offsets select_launch_rank_docs (scan_select.hip)
+void feedsep_launch_flag(const FeedArgs &F, const FeedSepArgs &P, uint32_t max_blocks, void *stream);         // keep
+void feedsep_launch_flag_finish(const FeedArgs &F, const FeedSepArgs &P, uint32_t max_blocks, void *stream);  // keep (a finish call)
+void feedsep_launch_compact(const FeedSepArgs &P, bool finish, uint32_t max_blocks, void *stream);            // out
+void feedsep_launch_count(const FeedArgs &F, const FeedSepArgs &P, uint32_t max_blocks, void *stream);  // F.kc (cleared by the host)
+void feedsep_launch_count_finish(const FeedArgs &F, uint32_t max_blocks, void *stream);                 // F.key_counts
+void feedsep_launch_restart(const FeedArgs &F, const FeedSepArgs &P, void *stream);  // a finish call: bases, the sequences at length 0
 }  // namespace aha

@@ -130,6 +130,16 @@ enum FeedSelectSlot {
   kFsSelOff,   // the pieces' offsets into the selection, until the call is known to succeed
   kFsCount
 };
+// fsepbuf: calls on a feed with a separator filter (feed.cpp feed_sep_true, feed_finish_sep; scan_feedsep.hip)
+enum FeedSepSlot {
+  kFpEdge,     // per piece the hits that end on its context's last byte
+  kFpTrueOff,  // where each piece's true hits lie
+  kFpTrue,     // the call's true hits, piece by piece (kfd_merge into scratch), 12 bytes each
+  kFpKeep,     // one bit per true hit: it survives the filter and is reported by this call
+  kFpBlocks,   // the kept hits before every 2048 true hits, the total behind them
+  kFpZeroOff,  // a finish call: the offsets of its empty pieces
+  kFpCount
+};
 // Device scratch of ONE match call (grow-only, reused by later calls that lease the same set).
 struct Scratch {
   std::mutex mu;  // held by the call that leased the set
@@ -147,6 +157,7 @@ struct Scratch {
   Buf selbuf[kSelCount];
   Buf repbuf[kRepCount];
   Buf fselbuf[kFsCount];
+  Buf fsepbuf[kFpCount];
   // every family above, for free_scratch and scratch_bytes (S: Scratch or const Scratch): a new family is one more line here
   template <class S, class Fn>
   static void each_buf(S &sc, Fn fn) {
@@ -158,6 +169,7 @@ struct Scratch {
     for (auto &b : sc.selbuf) fn(b);
     for (auto &b : sc.repbuf) fn(b);
     for (auto &b : sc.fselbuf) fn(b);
+    for (auto &b : sc.fsepbuf) fn(b);
   }
   bool dc_rows_clear = false;  // every word of dcbuf[kDcRows] is zero (kdc_compact clears what kdc_add wrote; a call that failed may not have)
   hipStream_t hs[3] = {};  // host-buffer entry: private non-blocking streams for upload, match, download
@@ -329,7 +341,7 @@ uint64_t scratch_bytes(const Scratch *sc);
 // THE allocator of the grow-only buffers: b holds at least `bytes` afterwards, or nothing (the HIP error is returned, the
 // runtime's sticky one cleared).  What a new buffer gets beyond `bytes` is its family's rule:
 enum Grow {
-  kGrowEighth,   // bytes + bytes / 8 + 256 (v2buf, covbuf, selbuf, repbuf, fselbuf)
+  kGrowEighth,   // bytes + bytes / 8 + 256 (v2buf, covbuf, selbuf, repbuf, fselbuf, fsepbuf)
   kGrowQuarter,  // bytes + bytes / 4 + 4096 (cntbuf, hostbuf)
   kGrowOrExact   // an eighth, else exactly `bytes`; `bytes` is what it records (dcbuf: what is known to be there)
 };

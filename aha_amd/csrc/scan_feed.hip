@@ -31,6 +31,11 @@
 // and, with P' widened to P[0 .. min(2 W, |P|)) as well, the hits per piece are x - y + m - z as for a count.
 //   kfd_cover_clear    bits [0, W') of every piece: pieces are not word-aligned and two may share a mask word
 //   kfd_cover_windows  the clipped spans with atomicOr; back with a wave reduction and one atomicMax per piece and wave
+// A feed with a separator filter (scan_feedsep.hip) keeps W = Lmax + 1 bytes of context -- both facts hold for any W >= Lmax - 1
+// -- and its calls also want the hits that ended with the piece before, which are hits of ctx alone:
+//   kfd_edge           per piece the hits of ctx alone that end on its last byte: a suffix of X's first y hits, by position
+//   kfd_scan<2>        the true hits per piece with them; kfd_merge<true> puts them in front of the piece's boundary hits
+// (instantiations of their own: a plain feed launches what it always launched)
 #include <hip/hip_runtime.h>
 
 #include "count_table.hpp"
@@ -84,6 +89,12 @@ __device__ __forceinline__ uint64_t kept_hits(const FeedArgs &F, uint64_t d) {
   const uint64_t z = F.wdho[2 * D + d + 1] - F.wdho[2 * D + d], m = F.mdho[d + 1] - F.mdho[d];
   return (x - y) + (m - z);
 }
+// ... of a call on a feed with a separator filter: the hits that end on the context's last byte too
+__device__ __forceinline__ uint64_t true_hits(const FeedArgs &F, uint64_t d) { return kept_hits(F, d) + F.edge[d]; }
+template <int kMode>
+__device__ __forceinline__ uint64_t scan_item(const FeedArgs &F, uint64_t i) {
+  return kMode == 0 ? win_len(F, i) : (kMode == 1 ? kept_hits(F, i) : true_hits(F, i));
+}
 
 // one block of kFdScanThreads: exclusive scan of n per-piece values into out[0..n], out[n] = the total.  Each thread takes a
 // contiguous run; the run sums are scanned in LDS.
@@ -92,11 +103,11 @@ __global__ void __launch_bounds__(kFdScanThreads) kfd_scan(FeedArgs F) {
   __shared__ uint64_t s[kFdScanThreads];
   if (*F.verdict) return;
   const uint64_t n = kMode == 0 ? 3 * F.D : F.D;
-  uint64_t *out = kMode == 0 ? F.woff : F.pho;
+  uint64_t *out = kMode == 0 ? F.woff : F.pho;  // (kMode 2: the true hits per piece of a call on a feed with a separator filter)
   const uint64_t per = (n + kFdScanThreads - 1) / kFdScanThreads;
   const uint64_t i0 = min(n, threadIdx.x * per), i1 = min(n, i0 + per);
   uint64_t mine = 0;
-  for (uint64_t i = i0; i < i1; i++) mine += kMode == 0 ? win_len(F, i) : kept_hits(F, i);
+  for (uint64_t i = i0; i < i1; i++) mine += scan_item<kMode>(F, i);
   s[threadIdx.x] = mine;
   __syncthreads();
   for (int k = 1; k < kFdScanThreads; k <<= 1) {
@@ -108,7 +119,7 @@ __global__ void __launch_bounds__(kFdScanThreads) kfd_scan(FeedArgs F) {
   uint64_t run = s[threadIdx.x] - mine;
   for (uint64_t i = i0; i < i1; i++) {
     out[i] = run;
-    run += kMode == 0 ? win_len(F, i) : kept_hits(F, i);
+    run += scan_item<kMode>(F, i);
   }
   if (threadIdx.x == kFdScanThreads - 1) {
     out[n] = s[threadIdx.x];
@@ -180,6 +191,33 @@ __global__ void __launch_bounds__(kFdThreads) kfd_leads(FeedArgs F) {
   }
 }
 
+// edge[d] = the hits of ctx_d alone that end on its last byte, where the piece has a byte to test them against (a feed with a
+// separator filter: they are reported now).  X_d's first y hits are those of ctx_d alone, in end order: the ones with
+// end = |ctx_d| are a suffix of them, found by position (such a feed is in bytes).
+__global__ void __launch_bounds__(kFdThreads) kfd_edge(FeedArgs F) {
+  const uint64_t D = F.D;
+  for (uint64_t d = blockIdx.x * (uint64_t)kFdThreads + threadIdx.x; d < D; d += (uint64_t)gridDim.x * kFdThreads) {
+    const int64_t lc = (int64_t)(F.woff[D + d + 1] - F.woff[D + d]);
+    const uint64_t y = F.wdho[D + d + 1] - F.wdho[D + d];
+    uint64_t e = 0;
+    if (lc > 0 && F.off[d + 1] > F.off[d]) {
+      const int32_t *h = F.whits + 3 * F.wdho[d];
+      uint64_t lo = 0, hi = y;  // the first of the y hits with end >= lc
+      while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if ((int64_t)h[3 * mid + 1] < lc)
+          lo = mid + 1;
+        else
+          hi = mid;
+      }
+      e = y - lo;
+    }
+    F.edge[d] = e;
+  }
+}
+
+// kEdge: a call on a feed with a separator filter -- the last edge[d] hits of ctx_d alone stand in front of the boundary hits
+template <bool kEdge>
 __global__ void __launch_bounds__(kFdThreads) kfd_merge(FeedArgs F) {
   const uint64_t D = F.D;
   const uint64_t i0 = (blockIdx.x * (uint64_t)kFdThreads + threadIdx.x) * 4;
@@ -200,11 +238,12 @@ __global__ void __launch_bounds__(kFdThreads) kfd_merge(FeedArgs F) {
     while (F.pho[d + 1] <= i) d++;
     const uint64_t j = i - F.pho[d];
     const uint64_t y = F.wdho[D + d + 1] - F.wdho[D + d];
-    const uint64_t xy = (F.wdho[d + 1] - F.wdho[d]) - y;
+    const uint64_t e = kEdge ? F.edge[d] : 0ull;
+    const uint64_t xy = (F.wdho[d + 1] - F.wdho[d]) - y + e;
     const int32_t *src;
     int32_t sh = 0;
     if (j < xy) {  // a boundary hit: X's offsets less the context
-      src = F.whits + 3 * (F.wdho[d] + y + j);
+      src = F.whits + 3 * (F.wdho[d] + y - e + j);
       sh = F.chars ? (int32_t)F.lead_ctx[d] : (int32_t)(F.woff[D + d + 1] - F.woff[D + d]);
     } else {  // a main hit: already relative to the piece
       const uint64_t z = F.wdho[2 * D + d + 1] - F.wdho[2 * D + d];
@@ -374,8 +413,21 @@ void feed_launch_merge(const FeedArgs &F, void *stream) {
   hipLaunchKernelGGL(kfd_scan<1>, dim3(1), dim3(kFdScanThreads), 0, s, F);
   if (F.total) {
     const uint64_t groups = (F.total + 3) / 4;
-    hipLaunchKernelGGL(kfd_merge, dim3((uint32_t)((groups + kFdThreads - 1) / kFdThreads)), dim3(kFdThreads), 0, s, F);
+    hipLaunchKernelGGL(kfd_merge<false>, dim3((uint32_t)((groups + kFdThreads - 1) / kFdThreads)), dim3(kFdThreads), 0, s, F);
   }
+}
+
+void feed_launch_edge(const FeedArgs &F, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(kfd_edge, dim3(grid_for(F.D, kFdThreads, 1024)), dim3(kFdThreads), 0, s, F);
+  hipLaunchKernelGGL(kfd_scan<2>, dim3(1), dim3(kFdScanThreads), 0, s, F);
+}
+
+void feed_launch_merge_edge(const FeedArgs &F, void *stream) {
+  if (!F.total) return;
+  const uint64_t groups = (F.total + 3) / 4;
+  hipLaunchKernelGGL(kfd_merge<true>, dim3((uint32_t)((groups + kFdThreads - 1) / kFdThreads)), dim3(kFdThreads), 0,
+                     (hipStream_t)stream, F);
 }
 
 void feed_launch_count(const FeedArgs &F, void *stream) {

@@ -224,6 +224,12 @@ lib LibAhaHip
   type Feed = Void*
   FEED_CHARS = 1_u32
   fun aha_feed_open(ac : Ac, n_seqs : UInt32, flags : UInt32, out : Feed*) : Int32
+  # a feed with a separator filter: match and count calls report a hit one byte late, finish ends a sequence
+  fun aha_feed_open_params(ac : Ac, n_seqs : UInt32, flags : UInt32, params : MatchParams*, out : Feed*) : Int32
+  fun aha_feed_finish_batch(f : Feed, seq_ids : UInt32*, n_named : UInt64, out : Hit*, cap : UInt64, seq_hit_offsets : UInt64*,
+                            bases : UInt64*, n_hits : UInt64*) : Int32
+  fun aha_feed_finish_batch_device(f : Feed, d_seq_ids : UInt32*, n_named : UInt64, d_out : Hit*, cap : UInt64,
+                                   d_seq_hit_offsets : UInt64*, d_bases : UInt64*, n_hits : UInt64*, stream : Void*) : Int32
   fun aha_feed_free(f : Feed) : Void
   fun aha_feed_reset(f : Feed, seq : UInt32) : Int32
   fun aha_feed_position(f : Feed, seq : UInt32, bytes : UInt64*, chars : UInt64*) : Int32
@@ -694,6 +700,42 @@ module Aha
       rc = LibAhaHip.aha_feed_open(ac.handle, n_seqs.to_u32, chars ? LibAhaHip::FEED_CHARS : 0_u32, out h)
       raise String.new(LibAhaHip.aha_strerror(rc)) if rc != 0
       @handle = h
+    end
+
+    # A feed whose #match and #count apply the separator filter of match(seq, sep) to the whole sequence
+    # (aha_feed_open_params): a hit is reported once the byte behind it is known, #finish ends a sequence.
+    def initialize(ac : AC, n_seqs : Int, sep : BitArray)
+      @ac = ac
+      raise "sep BitArray size > 256 is not supported" if sep.size > 256
+      params = LibAhaHip::MatchParams.new
+      params.struct_size = sizeof(LibAhaHip::MatchParams).to_u32
+      params.sep_size = sep.size
+      bits = StaticArray(UInt8, 32).new(0_u8)
+      sep.each_with_index { |b, i| bits[i >> 3] |= (1_u8 << (i & 7)) if b }
+      params.sep_bits = bits
+      rc = LibAhaHip.aha_feed_open_params(ac.handle, n_seqs.to_u32, 0_u32, pointerof(params), out h)
+      raise String.new(LibAhaHip.aha_last_error(ac.handle)) if rc != 0
+      @handle = h
+    end
+
+    # The sequence ends here (a feed with a separator filter): the surviving hits that end with it, with absolute offsets; it
+    # starts again at length 0.
+    def finish(seq : Int) : Array(Hit)
+      ids = [seq.to_u32]
+      cap = 16_u64
+      loop do
+        buf = Slice(LibAhaHip::Hit).new(cap.to_i32)
+        base = 0_u64
+        rc = LibAhaHip.aha_feed_finish_batch(@handle, ids.to_unsafe, 1_u64, buf.to_unsafe, cap, Pointer(UInt64).null,
+          pointerof(base), out n)
+        if rc == -6 # AHA_E_CAPACITY: n is the exact count, the sequence has not restarted
+          cap = n
+          next
+        end
+        raise String.new(LibAhaHip.aha_last_error(@ac.handle)) if rc != 0
+        b = base.to_i32 # (raises OverflowError past 2^31)
+        return Array(Hit).new(n.to_i32) { |i| Hit.new(buf[i].start + b, buf[i].end_ + b, buf[i].value) }
+      end
     end
 
     def finalize

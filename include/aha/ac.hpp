@@ -505,6 +505,20 @@ class Feed {
     const int32_t rc = aha_feed_open(ac_, n_seqs, chars ? AHA_FEED_CHARS : 0u, &f_);
     if (rc != AHA_OK) throw Error(rc, aha_strerror(rc));
   }
+  // a feed whose match and count calls apply the separator filter of match(seq, sep) to the whole sequence
+  // (aha_feed_open_params): a call reports the surviving hits that end before the piece's last byte -- one that ended with the
+  // piece before has end == 0 --, finish_batch / finish those that end with the sequence; cover and select calls throw
+  Feed(const AC &ac, uint32_t n_seqs, const BitArray &sep) : ac_(ac.handle()) {
+    aha_match_params p{};
+    p.struct_size = sizeof(p);
+    p.sep_size = sep.size();
+    std::memcpy(p.sep_bits, sep.bytes().data(), sep.bytes().size() < 32 ? sep.bytes().size() : 32);
+    const int32_t rc = aha_feed_open_params(ac_, n_seqs, 0u, &p, &f_);
+    if (rc != AHA_OK) {
+      const char *m = aha_last_error(ac_);
+      throw Error(rc, (m && *m) ? m : aha_strerror(rc));
+    }
+  }
   Feed(const Feed &) = delete;
   Feed &operator=(const Feed &) = delete;
   Feed(Feed &&o) noexcept : ac_(o.ac_), f_(o.f_) { o.f_ = nullptr; }
@@ -539,6 +553,40 @@ class Feed {
   std::vector<Hit> match(uint32_t seq, std::string_view piece) {
     std::vector<uint64_t> bases;
     auto hits = match_batch(piece, {0, piece.size()}, {seq}, nullptr, &bases);
+    for (auto &h : hits) {
+      h.start += (int32_t)bases[0];
+      h.end += (int32_t)bases[0];
+    }
+    return hits;
+  }
+  // a feed with a separator filter: the named sequences end here (aha_feed_finish_batch).  The surviving hits that end with
+  // them, relative to each sequence's end (end == 0, start == -len); seq_hit_offsets (n + 1) and bases (n: the sequences'
+  // lengths) when asked for.  The sequences start again at length 0.
+  std::vector<Hit> finish_batch(const std::vector<uint32_t> &seq_ids, std::vector<uint64_t> *seq_hit_offsets = nullptr,
+                                std::vector<uint64_t> *bases = nullptr) {
+    const uint64_t D = seq_ids.size();
+    if (seq_hit_offsets) seq_hit_offsets->assign(D + 1, 0);
+    if (bases) bases->assign(D, 0);
+    std::vector<Hit> out(4 * D + 16);
+    uint64_t n = 0;
+    for (;;) {
+      const int32_t rc = aha_feed_finish_batch(f_, seq_ids.data(), D, out.data(), out.size(),
+                                               seq_hit_offsets ? seq_hit_offsets->data() : nullptr,
+                                               bases ? bases->data() : nullptr, &n);
+      if (rc == AHA_E_CAPACITY) {  // (the sequences have not restarted: the same call again)
+        out.resize(n);
+        continue;
+      }
+      check(rc);
+      break;
+    }
+    out.resize(n);
+    return out;
+  }
+  // one sequence ends here: the surviving hits that end with it, with absolute offsets (they must fit Int32)
+  std::vector<Hit> finish(uint32_t seq) {
+    std::vector<uint64_t> bases;
+    auto hits = finish_batch({seq}, nullptr, &bases);
     for (auto &h : hits) {
       h.start += (int32_t)bases[0];
       h.end += (int32_t)bases[0];

@@ -423,7 +423,9 @@ int32_t aha_ac_count_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uin
  * limit; a piece must be shorter than 2^31 bytes minus Lmax (AHA_E_TOO_LONG).  Within one call a sequence appears at most
  * once (AHA_E_INVALID); pieces may come in any order and a call may name any subset of the sequences.  A call that fails
  * changes nothing, AHA_E_CAPACITY included: *n_hits is then the exact count and the same call with a larger buffer gives what
- * the first would have.  Counts: aha_feed_count_batch* below.  No separator filter, no match_longest (follow-ups).
+ * the first would have.  Counts: aha_feed_count_batch* below.  Separator filter: match and count calls take one fixed when the
+ * feed is opened (aha_feed_open_params, "feed separator filter" below); cover and select calls do not yet, and no feed call has
+ * match_longest (follow-ups).
  * Errors: aha_last_error(ac).  Calls
  * on one feed are serialised (a mutex in the feed); different feeds and plain calls on the handle run side by side.
  * Pipeline (aha_amd/csrc/feed.cpp, scan_feed.hip): with W = max(Lmax-1, 0) the feed keeps the last
@@ -475,6 +477,49 @@ int32_t aha_feed_count_batch_device(aha_feed *f, const uint8_t *d_corpus, const 
                                     const uint32_t *d_seq_ids, uint64_t n_pieces, uint64_t n_bytes, uint32_t flags,
                                     uint64_t *d_key_counts /* K or NULL */, uint64_t *d_piece_hit_offsets /* D+1 or NULL */,
                                     uint64_t *d_piece_bases /* D or NULL */, uint64_t *n_hits, void *stream);
+
+/* ---- feed separator filter: whole-word hits for sequences in pieces (pure additions to ABI 8) ---------------------------
+ * aha_feed_open_params opens a feed whose match and count calls apply the reference's separator filter, match(seq, sep :
+ * BitArray) src/aha/ac.cr:321-340, to the whole sequence: with pass(c) = c >= sep_size || sep_bits[c] -- applied to fold(c) on a
+ * handle with AHA_OPT_FOLD_ASCII -- a hit {start, end, value} of a sequence T survives when (end == |T| || pass(T[end])) and
+ * (start == 0 || pass(T[start-1])).  The survivors keep the order of the unfiltered list.  params == NULL or sep_size == 0:
+ * exactly aha_feed_open.  sep_size > 256: AHA_E_SEP_SIZE; char_offsets != 0, longest != 0, or AHA_FEED_CHARS together with a
+ * separator filter (the reference's char overload tests code points: out of scope): AHA_E_INVALID; these checks come before
+ * the device check, so a host-only handle answers AHA_E_NO_DEVICE only for valid arguments.
+ * The byte behind a hit that ends with a piece is not there yet, so such a feed reports a hit ONE BYTE LATE and a sequence has
+ * an explicit end.  Stream law: a match call that takes a sequence from n0 to n1 > n0 bytes reports the surviving hits of the
+ * sequence with absolute end in [n0, n1): a hit that ended exactly at the previous cut is reported now, tested against this
+ * piece's first byte; a hit that ends with this piece is not reported yet; a zero-length piece reports nothing.
+ * aha_feed_finish_batch names sequences that end here: it reports their surviving hits with end == n, the sequence's length
+ * (the right-hand test passes there), and starts each named sequence again at length 0.  The hits of all of a sequence's calls
+ * made absolute (base + relative), concatenated, with the finish call's appended, are aha_ac_match_batch of the whole sequence
+ * with the same sep, bit for bit and in the same order.  aha_feed_reset drops the hits that ended with the last byte (nothing
+ * is held anywhere: they are found again from the context).
+ * Offsets stay relative to the piece's first byte; a carried-over hit has end == 0 and start == -len, so on such a feed start
+ * goes down to -Lmax, not -(Lmax-1).  A finish call reports relative to the sequence's end: end == 0, start == -len, and
+ * bases[d] = n, the length of sequence seq_ids[d]; its hits are out[seq_hit_offsets[d] .. seq_hit_offsets[d+1]).
+ * aha_feed_count_batch* on such a feed gives key_counts, piece_hit_offsets, piece_bases and *n_hits of what the match call of
+ * the same pieces would report and moves the feed on exactly as that call would: match and count calls still mix freely.  It
+ * does build the call's unfiltered hit list in scratch (12 bytes per unfiltered hit of the pieces), unlike the plain feed
+ * count.  A failing call changes nothing; on AHA_E_CAPACITY *n_hits is the exact filtered count, the sequences of a finish call
+ * have NOT restarted, and the same call with a larger buffer gives what the first would have.
+ * aha_feed_finish_batch*: AHA_E_INVALID on a feed without a separator filter, for a sequence named twice or an id >= n_seqs
+ * (the device form checks both on the device).  aha_feed_cover_batch* and aha_feed_select_batch* on a feed with a separator
+ * filter: AHA_E_INVALID, the feed as it was (follow-ups).
+ * Pipeline (aha_amd/csrc/feed.cpp, scan_feedsep.hip; DESIGN.md 4.10 "Feed separator filter"): the feed keeps W = Lmax + 1 bytes
+ * of context per sequence (2 W + 24 bytes of device memory), so a hit that ended with the piece before is a hit of the context
+ * alone and its left neighbour lies in the context too.  A call runs the window batch and the main pass unfiltered, merges the
+ * call's true hits into scratch, flags each (12 B read, two neighbour bytes), ranks the flags, and writes the kept hits -- or
+ * adds their values per key -- once the filtered total is known to fit. */
+int32_t aha_feed_open_params(aha_ac *ac, uint32_t n_seqs, uint32_t flags, const aha_match_params *params, aha_feed **out);
+/* Host buffers (the ids are checked on the host).  Any output array may be NULL; n_named = 0 is valid. */
+int32_t aha_feed_finish_batch(aha_feed *f, const uint32_t *seq_ids, uint64_t n_named, aha_hit *out, uint64_t cap,
+                              uint64_t *seq_hit_offsets /* n_named+1 or NULL */, uint64_t *bases /* n_named or NULL */,
+                              uint64_t *n_hits);
+/* Device-resident form: d_ pointers are HBM on the handle's device; *n_hits is host memory; blocks until final. */
+int32_t aha_feed_finish_batch_device(aha_feed *f, const uint32_t *d_seq_ids, uint64_t n_named, aha_hit *d_out, uint64_t cap,
+                                     uint64_t *d_seq_hit_offsets /* n_named+1 or NULL */,
+                                     uint64_t *d_bases /* n_named or NULL */, uint64_t *n_hits, void *stream);
 
 /* ---- document counts: hits per key within each document, no hit list (pure additions to ABI 8) -----------------------
  * The same batch, params, validation and errors as aha_ac_match_batch / _device.  For document d,
@@ -657,7 +702,8 @@ int32_t aha_ac_replace_batch_device(aha_ac *ac, const aha_repl *table, const uin
  * capacity, so no AHA_E_CAPACITY.  A call that fails changes nothing -- neither the feed nor a caller buffer; in place, no
  * fill byte is written before the verdict is known.  Any output array may be NULL; N = 0, D = 0 and empty pieces are valid.
  * Two calls on feeds in the same state give identical bytes.  Like count and cover calls it reads the handle's back-off state
- * and never writes it.  No separator filter, no match_longest, as for every feed call.
+ * and never writes it.  No separator filter (a feed opened with one refuses the call: AHA_E_INVALID, the feed unchanged; a
+ * follow-up) and no match_longest.
  * Pipeline (feed.cpp, scan_feed.hip; DESIGN.md 4.10 "Feed cover"): with W = Lmax - 1 and W' = min(W, |P|), the head windows
  * are widened to X2 = ctx || P[0 .. min(2 W, |P|)) and P'2 = P[0 .. min(2 W, |P|)) (the window batch: at most 6 W bytes per
  * piece, matched quietly, in bytes); the pieces are covered alone as by aha_ac_cover_batch_device into a mask in feed scratch
@@ -704,7 +750,8 @@ int32_t aha_feed_cover_batch_device(aha_feed *f, const uint8_t *d_corpus, const 
  * AHA_FEED_CHARS (select is bytes only): AHA_E_INVALID.  AHA_E_CAPACITY: *n_selected is the required count, NONE of the
  * caller's buffers is written and the feed is unchanged; the same call with a larger buffer gives what the first would have
  * (out == NULL with cap == 0 is a sizing call).  Every failing call changes nothing.  Two feeds in the same state give
- * identical bytes.  No separator filter, no match_longest, as for every feed call.
+ * identical bytes.  No separator filter (a feed opened with one refuses the call: AHA_E_INVALID, the feed unchanged; a
+ * follow-up) and no match_longest.
  * Mixing: select keeps state per sequence that match, count and cover calls do not maintain (they stay exactly as they are).
  * A select call is valid for a sequence only if every byte of it since open, reset or a FINAL call went through select calls;
  * otherwise AHA_E_INVALID (found on the device, next to the duplicate check; aha_last_error says so) and nothing changes.  Such
