@@ -1068,7 +1068,7 @@ class Feed:
     piece_bases[d] is the sequence's length before it, so base + offset is absolute.  A feed opened with sep (AC.feed(..,
     sep=BitArray)) filters match and count calls as match(seq, sep) of the whole sequence does: a call reports the surviving
     hits that end before the piece's last byte -- one that ended with the piece before has end == 0 -- and finish_batch /
-    finish report those that end with the sequence and start it again; cover and select calls are refused there."""
+    finish report those that end with the sequence and start it again; cover, select and replace calls are refused there."""
 
     def __init__(self, ac, handle, n_seqs, chars, sep=None):
         self._ac, self._h, self.n_seqs, self.chars, self.sep = ac, handle, n_seqs, chars, sep
@@ -1450,6 +1450,88 @@ class Feed:
                                        np.array([seq], dtype=np.uint32), final=final)
         base = int(info["piece_bases"][0])
         return [Hit(s + base, e + base, v) for s, e, v in hits.tolist()]
+
+    # -- feed replace: the substituted stream of sequences in pieces, built on the device (aha_feed_replace_batch*) --------
+    def replace_batch(self, corpus, piece_offsets, seq_ids, repl_or_table, final=False):
+        """Every piece's share of the substituted stream (aha_feed_replace_batch): for piece d, which takes its sequence from
+        n0 to n1 bytes and moves its select cursor from c0 to c1, the bytes T[c0..c1) with every hit the call settles
+        (select_batch of the same pieces) replaced as the table says -- a ReplTable of the feed's handle, or what
+        AC.replacements takes.  With final=True everything settles and the named sequences start again from length 0.
+        -> (uint8 array, info) with info = {"piece_out_offsets" uint64[D+1], "piece_bases" uint64[D], "piece_hold" uint32[D],
+        "n_selected", "n_hits"}; piece d's bytes are out[piece_out_offsets[d]:piece_out_offsets[d+1]], and the pieces'
+        bytes of one sequence, concatenated, are AC.replace of the whole.  A sizing call first (it changes nothing)."""
+        if isinstance(corpus, (bytes, bytearray)):
+            corpus = np.frombuffer(bytes(corpus), dtype=np.uint8)
+        corpus = np.ascontiguousarray(corpus, dtype=np.uint8)
+        piece_offsets = np.ascontiguousarray(piece_offsets, dtype=np.uint64)
+        seq_ids = np.ascontiguousarray(seq_ids, dtype=np.uint32)
+        D = piece_offsets.size - 1
+        if seq_ids.size != D:
+            raise ValueError("one sequence id per piece")
+        table = self._ac._table(repl_or_table)
+        flags = N.AHA_FEED_REPLACE_FINAL if final else 0
+        poo = np.zeros(D + 1, dtype=np.uint64)
+        bases = np.zeros(max(D, 1), dtype=np.uint64)
+        hold = np.zeros(max(D, 1), dtype=np.uint32)
+        n, ns, nh = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        L = N.lib()
+        rc = L.aha_feed_replace_batch(self._h, table._h, _ptr(corpus), _ptr(piece_offsets), _ptr(seq_ids), D, flags, None, 0,
+                                      _ptr(poo), _ptr(bases), _ptr(hold), C.byref(n), C.byref(ns), C.byref(nh))
+        out = np.zeros(0, dtype=np.uint8)
+        if rc == N.AHA_E_CAPACITY:
+            cap = int(n.value)
+            out = np.zeros(cap, dtype=np.uint8)
+            rc = L.aha_feed_replace_batch(self._h, table._h, _ptr(corpus), _ptr(piece_offsets), _ptr(seq_ids), D, flags,
+                                          _ptr(out), cap, _ptr(poo), _ptr(bases), _ptr(hold), C.byref(n), C.byref(ns),
+                                          C.byref(nh))
+        self._check(rc)
+        return out[: int(n.value)], {"piece_out_offsets": poo, "piece_bases": bases[:D], "piece_hold": hold[:D],
+                                     "n_selected": int(ns.value), "n_hits": int(nh.value)}
+
+    def replace_batch_device(self, corpus, piece_offsets, seq_ids, table, out, piece_out_offsets=None, piece_bases=None,
+                             piece_hold=None, final=False, cap=None, stream=None):
+        """Device-resident form on torch CUDA tensors: uint8 corpus, int64/uint64 piece offsets, int32/uint32 sequence ids, a
+        ReplTable, out uint8 [cap] (any alignment) or None (a sizing call), piece_out_offsets / piece_bases int64/uint64
+        [D+1] / [D] or None, piece_hold int32/uint32 [D] or None.  -> (n_out_bytes, n_selected, n_hits); raises
+        AhaError(AHA_E_CAPACITY) when out is too small (e.n_required = the bytes needed); nothing is written then and the
+        feed is unchanged."""
+        import torch
+
+        assert corpus.is_cuda and corpus.dtype == torch.uint8 and corpus.is_contiguous()
+        assert piece_offsets.is_cuda and piece_offsets.dtype in (torch.int64, torch.uint64) and piece_offsets.is_contiguous()
+        assert seq_ids.is_cuda and seq_ids.dtype in (torch.int32, torch.uint32) and seq_ids.is_contiguous()
+        D = piece_offsets.numel() - 1
+        assert seq_ids.numel() >= D
+        if out is not None:
+            if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.dim() == 1):
+                raise ValueError("out must be a contiguous one-dimensional uint8 CUDA tensor")
+            cap = out.numel() if cap is None else min(int(cap), out.numel())
+        else:
+            cap = 0
+        for t, k in ((piece_out_offsets, D + 1), (piece_bases, D)):
+            assert t is None or (t.is_cuda and t.dtype in (torch.int64, torch.uint64) and t.is_contiguous() and t.numel() >= k)
+        assert piece_hold is None or (piece_hold.is_cuda and piece_hold.dtype in (torch.int32, torch.uint32)
+                                      and piece_hold.is_contiguous() and piece_hold.numel() >= D)
+        n, ns, nh = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        s = stream if stream is not None else torch.cuda.current_stream(corpus.device).cuda_stream
+        rc = N.lib().aha_feed_replace_batch_device(
+            self._h, table._h, corpus.data_ptr(), piece_offsets.data_ptr(), seq_ids.data_ptr(), D, corpus.numel(),
+            N.AHA_FEED_REPLACE_FINAL if final else 0, out.data_ptr() if out is not None and cap else None, cap,
+            piece_out_offsets.data_ptr() if piece_out_offsets is not None else None,
+            piece_bases.data_ptr() if piece_bases is not None else None,
+            piece_hold.data_ptr() if piece_hold is not None else None, C.byref(n), C.byref(ns), C.byref(nh), C.c_void_p(s))
+        if rc == N.AHA_E_CAPACITY:
+            raise AC._capacity_error(rc, n)
+        self._check(rc)
+        return int(n.value), int(ns.value), int(nh.value)
+
+    def replace(self, seq, piece, repl_or_table, final=False):
+        """The next piece of one sequence: the substituted bytes that can no longer change (bytes); with final=True the rest,
+        and the sequence starts again from length 0.  b"".join of a sequence's results == matcher.replace(whole, repl)."""
+        b = _b(piece)
+        out, _ = self.replace_batch(np.frombuffer(b, dtype=np.uint8), np.array([0, len(b)], dtype=np.uint64),
+                                    np.array([seq], dtype=np.uint32), repl_or_table, final=final)
+        return out.tobytes()
 
     def replacer(self, repl):
         """A Replacer over this feed: push(seq, piece) / finish(seq) give the substituted stream of every sequence."""

@@ -23,6 +23,13 @@
 //   scan_feedselect.hip    the pieces' extended positions, L from the sequences' tails and the hits, the masks, the walk up to the
 //                          frontier, the rank (one read-back: the total) -- above cap -> AHA_E_CAPACITY, nothing committed
 //   kfs_emit, kfd_commit + kfs_commit   the selection, the offsets; then the feed's state and, behind it, the select state
+// A replace call (aha_feed_replace_batch*) is a select call up to the rank (feed_select_settle), then
+//   kfs_emit               the settled selection into scratch instead of a caller buffer
+//   scan_feedreplace.hip   per piece the open bytes in front of it and the cursor it will leave; the staged text T[c0 .. c1) of
+//                          every piece, the open bytes from the sequence's context bank
+//   scan_replace.hip       its passes over the staged batch, unchanged (one read-back: the byte total) -- above cap_bytes ->
+//                          AHA_E_CAPACITY, nothing committed
+//   krp_copy, kfd_commit + kfs_commit   the result, the offsets; then the feed's state as a select call leaves it
 // A feed with a separator filter (aha_feed_open_params; scan_feedsep.hip, DESIGN.md 4.10 "Feed separator filter") keeps
 // W = Lmax + 1 bytes of context, so a hit that ended with the piece before and its left neighbour lie in the context.  Its match
 // and count calls take the first five steps of a match call unfiltered with the hits into scratch, then
@@ -50,7 +57,7 @@ struct aha_feed {
   std::mutex mu;
   FeedSeq *d_seqs = nullptr;
   uint8_t *d_ctx = nullptr;
-  // select calls: allocated by the feed's first one (8 W + 16 bytes per sequence)
+  // select and replace calls: allocated by the feed's first one (8 W + 16 bytes per sequence)
   FeedSelSeq *d_sel = nullptr;
   unsigned long long *d_tail = nullptr;
   uint32_t stamp = 0;
@@ -284,10 +291,13 @@ int32_t no_scratch() {
   return AHA_E_HIP;
 }
 
-// a whole select call on device-resident pieces.  Everything up to the total's read-back writes scratch only; the caller's
-// hits, offsets, bases and hold and the feed's state are written once the total is known to fit.
-int32_t feed_select(aha_feed *f, Scratch *sc, FeedArgs &F, uint32_t flags, aha_hit *d_out, uint64_t cap, uint64_t *d_pso,
-                    uint32_t *d_hold, hipStream_t s, uint64_t *n_selected, uint64_t *n_hits) {
+uint32_t select_blocks(const aha_ac *ac) { return 8u * std::max<uint32_t>(ac->v2_grid, 64u); }
+
+// the part of a select call that writes scratch only, shared with a replace call: the windows and the main pass with the true
+// hits into scratch, the extended positions, L, the masks, the walk and the rank.  -> S (everything but hold and out),
+// *n_selected = the selection's total (one read-back), *n_hits = the call's true hits.  Nothing of the feed's state changes.
+int32_t feed_select_settle(aha_feed *f, Scratch *sc, FeedArgs &F, uint32_t flags, FeedSelArgs &S, hipStream_t s, uint64_t *n_selected,
+                           uint64_t *n_hits) {
   aha_ac *ac = f->ac;
   const uint64_t D = F.D, W = f->W;
   if (!f->d_sel) {  // the feed's first select call: no sequence has select state yet
@@ -314,7 +324,7 @@ int32_t feed_select(aha_feed *f, Scratch *sc, FeedArgs &F, uint32_t flags, aha_h
   int32_t rc = feed_windows(f, sc, F, s, true, &n_w, &nx, &ny, &nz);
   if (rc) return rc;
   auto fs_reserve = [sc](FeedSelectSlot slot, size_t bytes) { return reserve_ptr(sc->fselbuf[slot], bytes, kGrowEighth); };
-  FeedSelArgs S{};
+  S = FeedSelArgs{};
   S.sseq = f->d_sel;
   S.tail = f->d_tail;
   S.final = (flags & AHA_FEED_SELECT_FINAL) ? 1u : 0u;
@@ -324,8 +334,6 @@ int32_t feed_select(aha_feed *f, Scratch *sc, FeedArgs &F, uint32_t flags, aha_h
   S.pso = (uint64_t *)fs_reserve(kFsSelOff, (D + 1) * 8);
   uint64_t *pho = (uint64_t *)fs_reserve(kFsHitOff, (D + 1) * 8);
   if (!S.eoff || !S.n0 || !S.cend || !S.pso || !pho) return no_scratch();
-  S.hold = d_hold;
-  S.out = reinterpret_cast<int32_t *>(d_out);
   // the pieces' extended positions (the ids are checked by now); their sum comes back with the main pass
   feedsel_launch_layout(F, S, s);
   HIPCHK(ac, hipGetLastError());
@@ -365,7 +373,7 @@ int32_t feed_select(aha_feed *f, Scratch *sc, FeedArgs &F, uint32_t flags, aha_h
   S.n_hits = n_true;
   S.NE = NE;
   uint64_t total = 0;
-  const uint32_t blocks = 8u * std::max<uint32_t>(ac->v2_grid, 64u);
+  const uint32_t blocks = select_blocks(ac);
   if (NE) {
     const uint64_t n_words = (NE + 31) / 32, n_blk = select_rank_blocks(NE);
     S.L = (unsigned long long *)fs_reserve(kFsLongest, NE * 8);
@@ -394,12 +402,87 @@ int32_t feed_select(aha_feed *f, Scratch *sc, FeedArgs &F, uint32_t flags, aha_h
   }
   *n_selected = total;
   if (n_hits) *n_hits = n_true;
+  return AHA_OK;
+}
+
+// a whole select call on device-resident pieces.  Everything up to the total's read-back writes scratch only; the caller's
+// hits, offsets, bases and hold and the feed's state are written once the total is known to fit.
+int32_t feed_select(aha_feed *f, Scratch *sc, FeedArgs &F, uint32_t flags, aha_hit *d_out, uint64_t cap, uint64_t *d_pso,
+                    uint32_t *d_hold, hipStream_t s, uint64_t *n_selected, uint64_t *n_hits) {
+  aha_ac *ac = f->ac;
+  const uint64_t D = F.D;
+  FeedSelArgs S{};
+  int32_t rc = feed_select_settle(f, sc, F, flags, S, s, n_selected, n_hits);
+  if (rc) return rc;
+  S.hold = d_hold;
+  S.out = reinterpret_cast<int32_t *>(d_out);
+  const uint64_t total = *n_selected;
   if (total > cap) {
     tls_err = "output buffer too small";
     return AHA_E_CAPACITY;
   }
-  if (total) feedsel_launch_emit(F, S, blocks, s);
+  if (total) feedsel_launch_emit(F, S, select_blocks(ac), s);
   if (d_pso) HIPCHK(ac, hipMemcpyAsync(d_pso, S.pso, (D + 1) * 8, hipMemcpyDeviceToDevice, s));
+  feed_launch_commit(F, s);
+  feedsel_launch_commit(F, S, s);
+  HIPCHK(ac, hipGetLastError());
+  HIPCHK(ac, hipStreamSynchronize(s));
+  return AHA_OK;
+}
+
+// a whole replace call on device-resident pieces: a select call's settle with the selection into scratch (kfs_emit), the staged
+// text T[c0 .. c1) of every piece (scan_feedreplace.hip), replace's passes over the staged batch (scan_replace.hip), one
+// read-back of the byte total.  Everything up to it writes scratch only; then the copy, the offsets and both commits.
+// out_slot >= 0: the result goes into that buffer of the feed, sized once the total is known (the host entry); else into d_out.
+int32_t feed_replace(aha_feed *f, Scratch *sc, const aha_repl *table, FeedArgs &F, uint32_t flags, uint8_t *d_out, int out_slot,
+                     uint64_t cap_bytes, uint64_t *d_poo, uint32_t *d_hold, hipStream_t s, uint64_t *n_out_bytes,
+                     uint64_t *n_selected, uint64_t *n_hits) {
+  aha_ac *ac = f->ac;
+  const uint64_t D = F.D;
+  FeedSelArgs S{};
+  uint64_t n = 0, n_true = 0;
+  int32_t rc = feed_select_settle(f, sc, F, flags, S, s, &n, &n_true);
+  if (rc) return rc;
+  auto fr_reserve = [sc](FeedReplaceSlot slot, size_t bytes) { return reserve_ptr(sc->frepbuf[slot], bytes, kGrowEighth); };
+  const uint64_t max_ext = F.n_bytes + D * f->W, n_blk = replace_scan_blocks(n);
+  int32_t *rows = (int32_t *)fr_reserve(kFrRows, std::max<uint64_t>(n, 1) * sizeof(aha_hit));
+  FeedRepArgs R{};
+  R.ext = (uint8_t *)fr_reserve(kFrExt, max_ext + 16);
+  R.ext_off = (uint64_t *)fr_reserve(kFrExtOff, (D + 1) * 8);
+  R.bias = (uint64_t *)fr_reserve(kFrBias, (D + 1) * 8);
+  R.hold0 = (uint32_t *)fr_reserve(kFrHold0, std::max<uint64_t>(D, 1) * 4);
+  uint64_t *A = (uint64_t *)fr_reserve(kFrStart, std::max<uint64_t>(n, 1) * 8);
+  int64_t *shift = (int64_t *)fr_reserve(kFrShift, (n + 1) * 8);
+  int64_t *sums = (int64_t *)fr_reserve(kFrSums, (n_blk + 1) * 8);
+  uint64_t *poo = (uint64_t *)fr_reserve(kFrOutOff, (D + 1) * 8);
+  if (!rows || !R.ext || !R.ext_off || !R.bias || !R.hold0 || !A || !shift || !sums || !poo) {
+    tls_err = "hipMalloc failed for the scratch of a feed replace call";
+    return AHA_E_HIP;
+  }
+  S.out = rows;
+  if (n) feedsel_launch_emit(F, S, select_blocks(ac), s);
+  const uint32_t blocks = ac->rep_blocks ? ac->rep_blocks : select_blocks(ac);
+  feedrep_launch_layout(F, S, R, s);
+  feedrep_launch_stage(F, R, max_ext, blocks, s);
+  // the staged batch is a replace problem: the rows are relative to the piece, so bias stands for the document offsets
+  replace_launch_delta(rows, n, S.pso, R.bias, D, table->d_ent, table->n_keys, A, shift, blocks, s);
+  replace_launch_scan(shift, n, sums, blocks, s);
+  replace_launch_doc_offsets(R.ext_off, S.pso, shift, D, poo, blocks, s);
+  HIPCHK(ac, hipGetLastError());
+  HIPCHK(ac, hipMemcpyAsync(f->h_pin, poo + D, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  const uint64_t total = f->h_pin[0];
+  *n_out_bytes = total;
+  if (n_selected) *n_selected = n;
+  if (n_hits) *n_hits = n_true;
+  if (total > cap_bytes) {
+    tls_err = "output buffer too small";
+    return AHA_E_CAPACITY;
+  }
+  if (out_slot >= 0 && !(d_out = (uint8_t *)reserve(f, out_slot, total))) return no_memory("result");
+  replace_launch_copy(R.ext, rows, A, shift, n, table->d_ent, table->n_keys, (const uint8_t *)table->d_blob, d_out, total, blocks, s);
+  if (d_poo) HIPCHK(ac, hipMemcpyAsync(d_poo, poo, (D + 1) * 8, hipMemcpyDeviceToDevice, s));
+  S.hold = d_hold;
   feed_launch_commit(F, s);
   feedsel_launch_commit(F, S, s);
   HIPCHK(ac, hipGetLastError());
@@ -1126,5 +1209,111 @@ int32_t aha_feed_select_batch(aha_feed *f, const uint8_t *corpus, const uint64_t
   if (piece_hold && D) HIPCHK(ac, hipMemcpyAsync(piece_hold, d_hold, D * 4, hipMemcpyDeviceToHost, s));
   HIPCHK(ac, hipStreamSynchronize(s));
   *n_selected = total;
+  return AHA_OK;
+}
+
+// the argument checks both replace entries share, before any device work
+static int32_t feed_replace_args(const aha_feed *f, const aha_repl *table, const uint64_t *piece_offsets, const uint32_t *seq_ids,
+                                 uint64_t n_pieces, uint32_t flags, const uint8_t *out, uint64_t cap_bytes,
+                                 const uint64_t *n_out_bytes) {
+  if (!f || !table || !n_out_bytes || !piece_offsets || (n_pieces && !seq_ids) || (cap_bytes && !out) ||
+      (flags & ~AHA_FEED_REPLACE_FINAL))
+    return AHA_E_INVALID;
+  if (bad_feed(f)) return AHA_E_NO_DEVICE;
+  if (table->owner != f->ac->serial) {
+    tls_err = "the replacement table was made for another handle";
+    return AHA_E_INVALID;
+  }
+  if (f->chars) {
+    tls_err = "feed replace: a char feed (AHA_FEED_CHARS); replace is in bytes";
+    return AHA_E_INVALID;
+  }
+  if (f->sep) return sep_refused("replace");
+  if (!table->d_ent) return no_device();
+  return AHA_OK;
+}
+
+int32_t aha_feed_replace_batch_device(aha_feed *f, const aha_repl *table, const uint8_t *d_corpus, const uint64_t *d_piece_offsets,
+                                      const uint32_t *d_seq_ids, uint64_t n_pieces, uint64_t n_bytes, uint32_t flags,
+                                      uint8_t *d_out, uint64_t cap_bytes, uint64_t *d_piece_out_offsets, uint64_t *d_piece_bases,
+                                      uint32_t *d_piece_hold, uint64_t *n_out_bytes, uint64_t *n_selected, uint64_t *n_hits,
+                                      void *stream) {
+  int32_t rc = feed_replace_args(f, table, d_piece_offsets, d_seq_ids, n_pieces, flags, d_out, cap_bytes, n_out_bytes);
+  if (rc) return rc;
+  if (n_bytes && !d_corpus) return AHA_E_INVALID;
+  if (cap_bytes && n_bytes) {
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), c0 = reinterpret_cast<uintptr_t>(d_corpus);
+    if (o0 < c0 + n_bytes && c0 < o0 + cap_bytes) {
+      tls_err = "feed replace calls have no in-place form: out overlaps the corpus";
+      return AHA_E_INVALID;
+    }
+  }
+  std::lock_guard<std::mutex> lk(f->mu);
+  DeviceGuard g(f->ac->device);
+  Lease lease(f->ac);
+  FeedArgs F{};
+  F.text = d_corpus;
+  F.off = d_piece_offsets;
+  F.ids = d_seq_ids;
+  F.D = n_pieces;
+  F.n_bytes = n_bytes;
+  F.bases = d_piece_bases;
+  *n_out_bytes = 0;
+  if (n_selected) *n_selected = 0;
+  if (n_hits) *n_hits = 0;
+  return feed_replace(f, lease.get(), table, F, flags, d_out, -1, cap_bytes, d_piece_out_offsets, d_piece_hold, (hipStream_t)stream,
+                      n_out_bytes, n_selected, n_hits);
+}
+
+// The host entry: the pieces go up into the feed's staging buffers; the result, sized once its total is known, and the offsets
+// come back once the call has succeeded.
+int32_t aha_feed_replace_batch(aha_feed *f, const aha_repl *table, const uint8_t *corpus, const uint64_t *piece_offsets,
+                               const uint32_t *seq_ids, uint64_t n_pieces, uint32_t flags, uint8_t *out, uint64_t cap_bytes,
+                               uint64_t *piece_out_offsets, uint64_t *piece_bases, uint32_t *piece_hold, uint64_t *n_out_bytes,
+                               uint64_t *n_selected, uint64_t *n_hits) {
+  int32_t rc = feed_replace_args(f, table, piece_offsets, seq_ids, n_pieces, flags, out, cap_bytes, n_out_bytes);
+  if (rc) return rc;
+  aha_ac *ac = f->ac;
+  if ((rc = check_pieces_host(f, piece_offsets, seq_ids, n_pieces))) return rc;
+  const uint64_t n_bytes = piece_offsets[n_pieces];
+  if (n_bytes && !corpus) return AHA_E_INVALID;
+  std::lock_guard<std::mutex> lk(f->mu);
+  DeviceGuard g(ac->device);
+  Lease lease(ac);
+  hipStream_t s = f->hs;
+  const uint64_t D = n_pieces;
+  uint8_t *d_corpus = (uint8_t *)reserve(f, kHCorpus, n_bytes + 64);
+  uint64_t *d_off = (uint64_t *)reserve(f, kHOff, (D + 1) * 8);
+  uint32_t *d_ids = (uint32_t *)reserve(f, kHIds, D * 4);
+  uint64_t *d_poo = (uint64_t *)reserve(f, kHPho, (D + 1) * 8);
+  uint64_t *d_bases = (uint64_t *)reserve(f, kHBases, D * 8);
+  uint32_t *d_hold = (uint32_t *)reserve(f, kHHold, D * 4);
+  if (!d_corpus || !d_off || !d_ids || !d_poo || !d_bases || !d_hold) return no_memory("staging buffers");
+  if (n_bytes) HIPCHK(ac, hipMemcpyAsync(d_corpus, corpus, n_bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(ac, hipMemcpyAsync(d_off, piece_offsets, (D + 1) * 8, hipMemcpyHostToDevice, s));
+  if (D) HIPCHK(ac, hipMemcpyAsync(d_ids, seq_ids, D * 4, hipMemcpyHostToDevice, s));
+  FeedArgs F{};
+  F.text = d_corpus;
+  F.off = d_off;
+  F.ids = d_ids;
+  F.D = D;
+  F.n_bytes = n_bytes;
+  F.bases = d_bases;
+  *n_out_bytes = 0;
+  if (n_selected) *n_selected = 0;
+  if (n_hits) *n_hits = 0;
+  uint64_t nb = 0, ns = 0, nh = 0;
+  rc = feed_replace(f, lease.get(), table, F, flags, nullptr, kHOut, cap_bytes, d_poo, d_hold, s, &nb, &ns, &nh);
+  if (rc == AHA_OK || rc == AHA_E_CAPACITY) {  // (the required size and the counts, as the device entry gives them)
+    *n_out_bytes = nb;
+    if (n_selected) *n_selected = ns;
+    if (n_hits) *n_hits = nh;
+  }
+  if (rc) return rc;
+  if (nb) HIPCHK(ac, hipMemcpyAsync(out, f->buf[kHOut].p, nb, hipMemcpyDeviceToHost, s));
+  if (piece_out_offsets) HIPCHK(ac, hipMemcpyAsync(piece_out_offsets, d_poo, (D + 1) * 8, hipMemcpyDeviceToHost, s));
+  if (piece_bases && D) HIPCHK(ac, hipMemcpyAsync(piece_bases, d_bases, D * 8, hipMemcpyDeviceToHost, s));
+  if (piece_hold && D) HIPCHK(ac, hipMemcpyAsync(piece_hold, d_hold, D * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
   return AHA_OK;
 }

@@ -1,4 +1,5 @@
-// feed.hpp -- what feed.cpp (the feed entry points of the C ABI) and scan_feed.hip (its kernels) share.  Library-internal.
+// feed.hpp -- what feed.cpp (the feed entry points of the C ABI) and its kernels (scan_feed.hip, scan_feedselect.hip,
+// scan_feedreplace.hip, scan_feedsep.hip) share.  Library-internal.
 #pragma once
 #include <cstdint>
 
@@ -11,9 +12,10 @@ struct FeedSeq {
   uint32_t bank;             // which of the two context banks holds its last min(W, bytes) bytes
 };
 
-// what a feed keeps per sequence for select calls (aha_feed_select_batch*), allocated by the feed's first one (16 bytes)
+// what a feed keeps per sequence for select and replace calls (aha_feed_select_batch*, aha_feed_replace_batch*), allocated by
+// the feed's first one (16 bytes)
 struct FeedSelSeq {
-  unsigned long long seen;    // bytes that went through select calls since open / reset / a FINAL call
+  unsigned long long seen;    // bytes that went through select or replace calls since open / reset / a FINAL call
   unsigned long long cursor;  // c: everything in front of it is final -- inside a reported hit or in no selected hit ever
 };
 
@@ -96,6 +98,30 @@ struct FeedSelArgs {
   int32_t *out;                // the caller's hits
 };
 
+// what the kernels of a replace call take beside FeedArgs and FeedSelArgs (scan_feedreplace.hip).  Piece d stages
+// T[c0 .. c1) of its sequence -- c0 the cursor the call finds, c1 the one it leaves -- at ext[ext_off[d], ext_off[d+1]): the
+// last hold0[d] = n0 - c0 bytes in front of the piece (from the sequence's context), then the piece up to c1.
+struct FeedRepArgs {
+  uint32_t *hold0;    // [D]
+  uint64_t *ext_off;  // [D+1] the exclusive scan of c1 - c0
+  uint64_t *bias;     // [D+1] ext_off[d] + hold0[d]: where the piece's own first byte lies, so a row's start (relative to the
+                      // piece, possibly negative) is a staged position by one addition (krp_delta's document offsets)
+  uint8_t *ext;       // the staged text, at most n_bytes + D W bytes
+};
+
+#ifdef __HIP__
+// The cursor a select or replace call leaves behind piece d (kfs_commit stores it, kfr_layout sizes the staged text by it):
+// everything in front of it is final.  cursor: the one the call finds; wb = min(W, n0); cend: the end of the last hit the call
+// settles as an extended position (0: none); under FINAL everything settles.
+__device__ inline uint64_t feedsel_cursor(uint64_t cursor, uint64_t n0, uint64_t wb, uint64_t cend, uint64_t n1, uint64_t W,
+                                      uint32_t final) {
+  if (final) return n1;
+  const uint64_t front = n1 > W ? n1 - W : 0, last = n0 - wb + cend;
+  const uint64_t c = cursor > last ? cursor : last;
+  return c > front ? c : front;
+}
+#endif
+
 void feed_launch_check(const FeedArgs &F, void *stream);    // kfd_check, then kfd_scan of the window lengths
 void feed_launch_windows(const FeedArgs &F, void *stream);  // kfd_windows (+ kfd_leads on char feeds)
 void feed_launch_merge(const FeedArgs &F, void *stream);    // kfd_scan of the hits per piece, kfd_merge
@@ -115,6 +141,10 @@ void feedsel_launch_longest(const FeedArgs &F, const FeedSelArgs &S, uint32_t ma
 void feedsel_launch_walk(const FeedArgs &F, const FeedSelArgs &S, uint32_t max_blocks, void *stream);     // select, cend
 void feedsel_launch_emit(const FeedArgs &F, const FeedSelArgs &S, uint32_t max_blocks, void *stream);     // out
 void feedsel_launch_commit(const FeedArgs &F, const FeedSelArgs &S, void *stream);   // behind feed_launch_commit: tails, cursors, hold
+// replace calls (scan_feedreplace.hip): behind the walk and kfs_emit into scratch, in front of both commits
+void feedrep_launch_layout(const FeedArgs &F, const FeedSelArgs &S, const FeedRepArgs &R, void *stream);  // hold0, ext_off, bias
+// ext; max_bytes: a bound of ext_off[D] known to the host (it sizes the grid)
+void feedrep_launch_stage(const FeedArgs &F, const FeedRepArgs &R, uint64_t max_bytes, uint32_t max_blocks, void *stream);
 // calls on a feed with a separator filter (scan_feedsep.hip), in this order; the rank between flag and compact is
 // select_launch_rank, the filtered offsets select_launch_rank_docs (scan_select.hip)
 void feedsep_launch_flag(const FeedArgs &F, const FeedSepArgs &P, uint32_t max_blocks, void *stream);         // keep

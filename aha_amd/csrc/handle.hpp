@@ -130,6 +130,19 @@ enum FeedSelectSlot {
   kFsSelOff,   // the pieces' offsets into the selection, until the call is known to succeed
   kFsCount
 };
+// frepbuf: feed replace calls (feed.cpp feed_replace; scan_feedreplace.hip, scan_replace.hip)
+enum FeedReplaceSlot {
+  kFrRows,    // the settled selection, piece by piece, relative to the piece (kfs_emit into scratch), 12 bytes each
+  kFrExt,     // ext: the staged text T[c0 .. c1) of every piece
+  kFrExtOff,  // where each piece's staged text lies
+  kFrBias,    // ... and where its own first byte lies in it: ext_off + hold0
+  kFrHold0,   // per piece the bytes between the cursor and the piece
+  kFrStart,   // A: per settled hit its first byte in ext
+  kFrShift,   // per settled hit the change of length in front of it, the total change behind the last
+  kFrSums,    // the scan's block sums
+  kFrOutOff,  // the pieces' offsets into the result, until the call is known to succeed
+  kFrCount
+};
 // fsepbuf: calls on a feed with a separator filter (feed.cpp feed_sep_true, feed_finish_sep; scan_feedsep.hip)
 enum FeedSepSlot {
   kFpEdge,     // per piece the hits that end on its context's last byte
@@ -157,6 +170,7 @@ struct Scratch {
   Buf selbuf[kSelCount];
   Buf repbuf[kRepCount];
   Buf fselbuf[kFsCount];
+  Buf frepbuf[kFrCount];
   Buf fsepbuf[kFpCount];
   // every family above, for free_scratch and scratch_bytes (S: Scratch or const Scratch): a new family is one more line here
   template <class S, class Fn>
@@ -169,6 +183,7 @@ struct Scratch {
     for (auto &b : sc.selbuf) fn(b);
     for (auto &b : sc.repbuf) fn(b);
     for (auto &b : sc.fselbuf) fn(b);
+    for (auto &b : sc.frepbuf) fn(b);
     for (auto &b : sc.fsepbuf) fn(b);
   }
   bool dc_rows_clear = false;  // every word of dcbuf[kDcRows] is zero (kdc_compact clears what kdc_add wrote; a call that failed may not have)
@@ -341,7 +356,7 @@ uint64_t scratch_bytes(const Scratch *sc);
 // THE allocator of the grow-only buffers: b holds at least `bytes` afterwards, or nothing (the HIP error is returned, the
 // runtime's sticky one cleared).  What a new buffer gets beyond `bytes` is its family's rule:
 enum Grow {
-  kGrowEighth,   // bytes + bytes / 8 + 256 (v2buf, covbuf, selbuf, repbuf, fselbuf, fsepbuf)
+  kGrowEighth,   // bytes + bytes / 8 + 256 (v2buf, covbuf, selbuf, repbuf, fselbuf, frepbuf, fsepbuf)
   kGrowQuarter,  // bytes + bytes / 4 + 4096 (cntbuf, hostbuf)
   kGrowOrExact   // an eighth, else exactly `bytes`; `bytes` is what it records (dcbuf: what is known to be there)
 };

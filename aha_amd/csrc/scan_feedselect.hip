@@ -175,8 +175,7 @@ __global__ void __launch_bounds__(kFsThreads) kfs_commit(FeedArgs F, FeedSelArgs
       for (uint64_t j = threadIdx.x; j < W; j += kFsThreads) S.tail[(uint64_t)id * W + j] = E + j >= W ? S.L[e0 + (E + j - W)] : 0ull;
     }
     if (threadIdx.x == 0) {
-      const uint64_t front = n1 > W ? n1 - W : 0;
-      const uint64_t c = max(max((uint64_t)S.sseq[id].cursor, n0 - wb + (uint64_t)S.cend[d]), front);
+      const uint64_t c = feedsel_cursor(S.sseq[id].cursor, n0, wb, S.cend[d], n1, W, S.final);
       FeedSelSeq ns;
       ns.seen = S.final ? 0 : n1;
       ns.cursor = S.final ? 0 : c;

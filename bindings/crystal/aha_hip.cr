@@ -267,6 +267,16 @@ lib LibAhaHip
                                    n_pieces : UInt64, n_bytes : UInt64, flags : UInt32, d_out : Hit*, cap : UInt64,
                                    d_piece_sel_offsets : UInt64*, d_piece_bases : UInt64*, d_piece_hold : UInt32*,
                                    n_selected : UInt64*, n_hits : UInt64*, stream : Void*) : Int32
+  # feed replace: the substituted stream of the same pieces, built on the device (byte feeds; a table of the feed's handle)
+  FEED_REPLACE_FINAL = FEED_SELECT_FINAL
+  fun aha_feed_replace_batch(f : Feed, table : Repl, corpus : UInt8*, piece_offsets : UInt64*, seq_ids : UInt32*,
+                             n_pieces : UInt64, flags : UInt32, out : UInt8*, cap_bytes : UInt64, piece_out_offsets : UInt64*,
+                             piece_bases : UInt64*, piece_hold : UInt32*, n_out_bytes : UInt64*, n_selected : UInt64*,
+                             n_hits : UInt64*) : Int32
+  fun aha_feed_replace_batch_device(f : Feed, table : Repl, d_corpus : UInt8*, d_piece_offsets : UInt64*, d_seq_ids : UInt32*,
+                                    n_pieces : UInt64, n_bytes : UInt64, flags : UInt32, d_out : UInt8*, cap_bytes : UInt64,
+                                    d_piece_out_offsets : UInt64*, d_piece_bases : UInt64*, d_piece_hold : UInt32*,
+                                    n_out_bytes : UInt64*, n_selected : UInt64*, n_hits : UInt64*, stream : Void*) : Int32
   fun aha_buffer_alloc(device : Int32, bytes : UInt64, d_ptr : Void**) : Int32
   fun aha_buffer_free(device : Int32, d_ptr : Void*) : Int32
   fun aha_buffer_upload(device : Int32, d_dst : Void*, src : Void*, bytes : UInt64) : Int32
@@ -799,6 +809,32 @@ module Aha
         b = base.to_i32 # (raises OverflowError past 2^31)
         return {Array(Hit).new(n.to_i32) { |i| Hit.new(buf[i].start + b, buf[i].end_ + b, buf[i].value) }, hold}
       end
+    end
+
+    # The next piece of one sequence substituted on the device: {bytes, hold} -- the substituted bytes that can no longer
+    # change (the sequence from the old select cursor to the new one, every hit settled in between replaced as the table
+    # says) and the bytes at the end of the sequence that no result holds yet.  final: the piece is the last of its
+    # sequence; the rest comes out and the sequence starts again from length 0.  The results of a sequence's pieces,
+    # concatenated, are AC#replace_batch of the whole.  (Uncompiled, as the rest of this class;
+    # tests/test_feed_replace_host.py checks that the lib block binds both entry points.)
+    def replace(seq : Int, piece : Bytes | String, table : AC::Replacements, final : Bool = false) : {Bytes, UInt32}
+      bytes = piece.is_a?(String) ? piece.to_slice : piece
+      offs = [0_u64, bytes.size.to_u64]
+      ids = [seq.to_u32]
+      flags = final ? LibAhaHip::FEED_REPLACE_FINAL : 0_u32
+      hold = 0_u32
+      # a sizing call: AHA_E_CAPACITY (-6) gives the exact size and changes nothing
+      rc = LibAhaHip.aha_feed_replace_batch(@handle, table.handle, bytes.to_unsafe, offs.to_unsafe, ids.to_unsafe, 1_u64, flags,
+        Pointer(UInt8).null, 0_u64, Pointer(UInt64).null, Pointer(UInt64).null, pointerof(hold), out n,
+        Pointer(UInt64).null, Pointer(UInt64).null)
+      buf = Bytes.new(n.to_i32)
+      if rc == -6
+        rc = LibAhaHip.aha_feed_replace_batch(@handle, table.handle, bytes.to_unsafe, offs.to_unsafe, ids.to_unsafe, 1_u64, flags,
+          buf.to_unsafe, n, Pointer(UInt64).null, Pointer(UInt64).null, pointerof(hold), out n2,
+          Pointer(UInt64).null, Pointer(UInt64).null)
+      end
+      raise String.new(LibAhaHip.aha_last_error(@ac.handle)) if rc != 0
+      {buf, hold}
     end
 
     # Hits per key of match on the same pieces, without the hit list: {key_counts (K entries), piece_hit_offsets,

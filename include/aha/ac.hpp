@@ -731,6 +731,51 @@ class Feed {
     }
     return hits;
   }
+  // What a replace call of pieces gives beside the bytes (aha_feed_replace_batch).
+  struct Replace {
+    std::vector<uint64_t> piece_out_offsets;  // D + 1: where each piece's result lies
+    std::vector<uint64_t> bases;              // D: the sequence's length before the piece
+    std::vector<uint32_t> piece_hold;         // D: bytes at the end of the sequence that no result holds yet
+    uint64_t n_selected = 0, n_hits = 0;      // as select_batch of the same pieces
+  };
+  // The substituted stream, built on the device: for a piece that moves its sequence's select cursor from c0 to c1 the bytes
+  // T[c0 .. c1) with every hit the call settles (select_batch of the same pieces) replaced as the table says -- a table of the
+  // feed's handle (AC::replacements).  With final = true everything settles and the named sequences start again from length
+  // 0.  The results of one sequence's pieces, concatenated, are AC::replace_batch of the whole.  A sizing call first (it
+  // changes nothing).  Byte feeds only, and only for sequences fed through select or replace calls since their reset.
+  std::string replace_batch(std::string_view corpus, const std::vector<uint64_t> &piece_offsets,
+                            const std::vector<uint32_t> &seq_ids, const AC::Replacements &table, bool final = false,
+                            Replace *info = nullptr) {
+    if (piece_offsets.empty()) throw Error(AHA_E_INVALID, "piece_offsets holds D + 1 entries");
+    const uint64_t D = piece_offsets.size() - 1;
+    if (seq_ids.size() != D) throw Error(AHA_E_INVALID, "one sequence id per piece");
+    if (corpus.size() < piece_offsets.back()) throw Error(AHA_E_INVALID, "the corpus is shorter than the last offset");
+    const uint32_t flags = final ? AHA_FEED_REPLACE_FINAL : 0u;
+    const uint8_t *text = reinterpret_cast<const uint8_t *>(corpus.data());
+    Replace c;
+    c.piece_out_offsets.assign(D + 1, 0);
+    c.bases.assign(D, 0);
+    c.piece_hold.assign(D, 0);
+    std::string out;
+    uint64_t n = 0;
+    int32_t rc = aha_feed_replace_batch(f_, table.handle(), text, piece_offsets.data(), seq_ids.data(), D, flags, nullptr, 0,
+                                        c.piece_out_offsets.data(), D ? c.bases.data() : nullptr,
+                                        D ? c.piece_hold.data() : nullptr, &n, &c.n_selected, &c.n_hits);
+    if (rc == AHA_E_CAPACITY) {  // (the feed is unchanged: the same call again, with room)
+      out.resize(n);
+      rc = aha_feed_replace_batch(f_, table.handle(), text, piece_offsets.data(), seq_ids.data(), D, flags,
+                                  reinterpret_cast<uint8_t *>(&out[0]), out.size(), c.piece_out_offsets.data(),
+                                  D ? c.bases.data() : nullptr, D ? c.piece_hold.data() : nullptr, &n, &c.n_selected, &c.n_hits);
+    }
+    check(rc);
+    out.resize(n);
+    if (info) *info = std::move(c);
+    return out;
+  }
+  // the next piece of one sequence: the substituted bytes that can no longer change; final: the rest
+  std::string replace(uint32_t seq, std::string_view piece, const AC::Replacements &table, bool final = false) {
+    return replace_batch(piece, {0, piece.size()}, {seq}, table, final);
+  }
   void reset(uint32_t seq = UINT32_MAX) { check(aha_feed_reset(f_, seq)); }
   // {bytes, chars} fed to the sequence so far
   std::pair<uint64_t, uint64_t> position(uint32_t seq) const {

@@ -665,8 +665,8 @@ int32_t aha_ac_select_batch_device(aha_ac *ac, const uint8_t *d_corpus, const ui
  * 256 selected hits) + 8 bytes per document; nothing per text byte beyond select's.  AHA_REPLACE_BLOCKS (read when the handle
  * is compiled) caps the scan's and the copy's grids.
  * aha_ac_last_timing: as select; ms_write = everything after the match.
- * Out of scope so far: replacements indexed by character, feeds built on the device (the selection of a stream: the feed select
- * calls below), groups, an in-place form, computed replacements. */
+ * Out of scope so far: replacements indexed by character, groups, an in-place form, computed replacements.  (The substituted
+ * stream of sequences in pieces: the feed replace calls below.) */
 typedef struct aha_repl aha_repl;
 int32_t aha_repl_create(aha_ac *ac, const uint8_t *blob, const uint64_t *offsets /* K+1, offsets[0] == 0, ascending */,
                         const uint32_t *keep_bits /* ceil(K/32) words, bit k = keep key k; NULL: none kept */, aha_repl **out);
@@ -781,6 +781,60 @@ int32_t aha_feed_select_batch_device(aha_feed *f, const uint8_t *d_corpus, const
                                      aha_hit *d_out, uint64_t cap, uint64_t *d_piece_sel_offsets /* D+1 or NULL */,
                                      uint64_t *d_piece_bases /* D or NULL */, uint32_t *d_piece_hold /* D or NULL */,
                                      uint64_t *n_selected, uint64_t *n_hits /* or NULL */, void *stream);
+
+/* Feed replace: the substituted stream of sequences that arrive in pieces, built on the device (pure additions to ABI 8).  The
+ * same pieces and flags as aha_feed_select_batch*, on a BYTE feed, and a replacement table of the feed's handle as for
+ * aha_ac_replace_batch*.  T, S(T), W and F(n) as for feed select; c = the sequence's select cursor.  A call takes a sequence
+ * from n0 to n1 bytes; it finds the cursor at c0 -- the bytes T[c0..n0) are still open, n0 - c0 is the previous piece_hold --
+ * and leaves it at c1 = max(c0, end of the last hit this call settles, F(n1)); c1 = n1 under FINAL.  "Settles" means what
+ * aha_feed_select_batch with the same flags would report for the piece; all such hits lie inside [c0, c1).
+ * The piece's result is T[c0..c1) with every hit this call settles replaced as the table says: kept keys stay as they are, an
+ * empty replacement deletes, and on a folded handle the bytes outside replaced hits are the caller's.  out = the pieces'
+ * results one behind the other, piece_out_offsets[0 .. D] where each lies (a piece may give 0 bytes), *n_out_bytes the total;
+ * piece_bases[d] = n0; piece_hold[d] = n1 - c1 (0 after FINAL, and those sequences start again from length 0); *n_selected,
+ * *n_hits (optional) as feed select reports them.  cap_bytes is in bytes.
+ * The stream law: cut a sequence anywhere into pieces, empty ones included, feed them through replace calls, the last with
+ * FINAL, and concatenate the results -- that is, byte for byte, aha_ac_replace_batch of the whole sequence as one document with
+ * the same table.  Example (keys ab -> "<AB>", abcde -> "", so W = 4): "xab" gives "" (hold 3: nothing lies in front of
+ * F(3) = 0), "cd" gives "x" (hold 4), "eab" gives "" (the longer key completed at (1, 6) and is deleted; hold 2), a FINAL call
+ * with an empty piece gives "<AB>".
+ * State: a replace call is a select call for the feed's state -- it maintains the bytes seen, the cursor and the tail exactly
+ * as a select call does and is valid under the same condition (every byte of the sequence since open, reset or FINAL went
+ * through select or replace calls; otherwise AHA_E_INVALID, found on the device, nothing changes, until the next reset).
+ * Select and replace calls may be mixed on one sequence: a replace call gives the substituted T[c0..c1) from wherever the
+ * cursor stands; the stream law is stated for sequences fed by replace calls only.
+ * AHA_E_CAPACITY: *n_out_bytes is the required size (*n_selected and *n_hits are set too), NONE of the caller's buffers is
+ * written and the feed is unchanged; the same call with a larger buffer gives what the first would have (out == NULL with
+ * cap_bytes == 0 is a sizing call; a total of 0 succeeds with cap_bytes == 0).  Every failing call changes nothing.
+ * A NULL feed, table or n_out_bytes, a table made for another handle, any flag bit but AHA_FEED_REPLACE_FINAL, a feed opened
+ * with AHA_FEED_CHARS, a feed opened with a separator filter (a follow-up), the device entry with out overlapping the corpus
+ * (its address ranges, when cap_bytes > 0): AHA_E_INVALID, all before any device work.  Piece and id validation is that of the
+ * other feed entries.  The handle's back-off state is read and never written; two feeds in the same state give identical bytes.
+ * d_out and d_corpus may have any alignment: no load touches an aligned 16-byte piece that holds no byte of its source buffer,
+ * no store a byte outside [out, out + total).
+ * Pipeline (feed.cpp feed_replace, scan_feedreplace.hip; DESIGN.md 4.10 "Feed replace"): a select call up to its total, the
+ * selection into the call's scratch; per piece hold0 = n0 - c0 and the staged length c1 - c0, scanned; the staged text ext --
+ * hold0 bytes from the sequence's context bank (the caller's bytes: the banks are filled from the caller's text), then the
+ * piece up to c1; a wave owns 1024 staged bytes, a lane 16, a tile inside one piece is two aligned 16-byte loads, a byte
+ * alignment and one aligned 16-byte store per lane --; then replace's own passes over (ext, its offsets, the selection), the
+ * byte total to the host, and once it fits the copy, the offsets and the two commits of a select call.
+ * Device scratch beyond a feed select call's: the staged text (at most N + D W bytes), per settled hit 12 bytes of selection, 8
+ * of A, 8 of shift, the scan's block sums, 28 bytes per piece.  AHA_REPLACE_BLOCKS caps the grids of the stage and of
+ * replace's passes. */
+#define AHA_FEED_REPLACE_FINAL AHA_FEED_SELECT_FINAL /* the same bit: the pieces are the last of their sequences */
+int32_t aha_feed_replace_batch(aha_feed *f, const aha_repl *table, const uint8_t *corpus, const uint64_t *piece_offsets,
+                               const uint32_t *seq_ids, uint64_t n_pieces, uint32_t flags, uint8_t *out, uint64_t cap_bytes,
+                               uint64_t *piece_out_offsets /* D+1 or NULL */, uint64_t *piece_bases /* D or NULL */,
+                               uint32_t *piece_hold /* D or NULL */, uint64_t *n_out_bytes, uint64_t *n_selected /* or NULL */,
+                               uint64_t *n_hits /* or NULL */);
+/* Device-resident form: d_ pointers are HBM on the handle's device, validated on the device before anything is indexed with
+ * them; *n_out_bytes, *n_selected, *n_hits are host memory; blocks until final. */
+int32_t aha_feed_replace_batch_device(aha_feed *f, const aha_repl *table, const uint8_t *d_corpus, const uint64_t *d_piece_offsets,
+                                      const uint32_t *d_seq_ids, uint64_t n_pieces, uint64_t n_bytes, uint32_t flags,
+                                      uint8_t *d_out, uint64_t cap_bytes, uint64_t *d_piece_out_offsets /* D+1 or NULL */,
+                                      uint64_t *d_piece_bases /* D or NULL */, uint32_t *d_piece_hold /* D or NULL */,
+                                      uint64_t *n_out_bytes, uint64_t *n_selected /* or NULL */, uint64_t *n_hits /* or NULL */,
+                                      void *stream);
 
 /* Frees the handle's device scratch (it grows with the largest batch seen and is otherwise kept for reuse). */
 int32_t aha_ac_release_scratch(aha_ac *ac);
