@@ -31,6 +31,7 @@ AHA_OPT_HOST_ONLY = 1
 AHA_OPT_FORCE_WIDE = 2
 AHA_OPT_FOLD_ASCII = 4
 AHA_COUNT_ACCUMULATE = 1
+AHA_GREP_INVERT = 1
 AHA_FEED_CHARS = 1
 AHA_FEED_SELECT_FINAL = 1
 AHA_FEED_REPLACE_FINAL = AHA_FEED_SELECT_FINAL
@@ -163,6 +164,12 @@ SIGNATURES = {
                                     C.POINTER(_u64), C.POINTER(_u64)]),
     "aha_ac_replace_batch_device": (_i32, [_vp, _vp, _vp, _vp, _u64, _u64, C.POINTER(aha_match_params), _u32, _vp, _u64, _vp,
                                            C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), _vp]),
+    "aha_ac_records_batch": (_i32, [_vp, _vp, _vp, _u64, C.c_uint8, _u32, _vp, _u64, _vp, C.POINTER(_u64)]),
+    "aha_ac_records_batch_device": (_i32, [_vp, _vp, _vp, _u64, _u64, C.c_uint8, _u32, _vp, _u64, _vp, C.POINTER(_u64), _vp]),
+    "aha_ac_grep_batch": (_i32, [_vp, _vp, _vp, _u64, C.POINTER(aha_match_params), _u32, _vp, _vp, _u64, _vp, _u64,
+                                 C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "aha_ac_grep_batch_device": (_i32, [_vp, _vp, _vp, _u64, _u64, C.POINTER(aha_match_params), _u32, _vp, _vp, _u64, _vp, _u64,
+                                        C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), _vp]),
     "aha_ac_count_batch": (_i32, [_vp, _vp, _vp, _u64, C.POINTER(aha_match_params), _u32, _vp, _vp, C.POINTER(_u64)]),
     "aha_ac_count_batch_device": (_i32, [_vp, _vp, _vp, _u64, _u64, C.POINTER(aha_match_params), _u32, _vp, _vp,
                                          C.POINTER(_u64), _vp]),

@@ -83,6 +83,19 @@ def _fill_byte(fill):
     return int(fill) & 0xFF
 
 
+def _delim_byte(delim):
+    """a record delimiter -- one byte as bytes, a one-byte str or an int -- as an int"""
+    if isinstance(delim, str):
+        delim = delim.encode("utf-8")
+    if isinstance(delim, (bytes, bytearray)):
+        if len(delim) != 1:
+            raise ValueError("the record delimiter is one byte")
+        return delim[0]
+    if not 0 <= int(delim) <= 255:
+        raise ValueError("the record delimiter is one byte")
+    return int(delim)
+
+
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
 
@@ -836,6 +849,167 @@ class AC:
         self._check(rc)
         return (out.download(np.zeros(cap, dtype=np.uint8)), doo.download(np.zeros(D + 1, dtype=np.uint64)), int(ns.value),
                 int(nh.value))
+
+    # -- records and grep: split a batch into records, keep those with a hit (aha_ac_records_batch*, aha_ac_grep_batch*) ----
+    def records(self, corpus, doc_offsets=None, delim=b"\n"):
+        """The batch split into records at the delimiter byte and at the documents' ends, on the device:
+        -> (rec_offsets uint64[R+1], doc_rec_offsets uint64[D+1]).  A record ends behind a delimiter or at a document's end
+        and is never empty; document d's records are rec_offsets[doc_rec_offsets[d]:doc_rec_offsets[d+1] + 1].  rec_offsets
+        is a doc_offsets for every batch call.  doc_offsets None: the corpus is one document.  A sizing call first."""
+        if isinstance(corpus, (bytes, bytearray)):
+            corpus = np.frombuffer(bytes(corpus), dtype=np.uint8)
+        corpus = np.ascontiguousarray(corpus, dtype=np.uint8)
+        if doc_offsets is None:
+            doc_offsets = [0, corpus.size]
+        doc_offsets = np.ascontiguousarray(doc_offsets, dtype=np.uint64)
+        D = doc_offsets.size - 1
+        dro = np.zeros(D + 1, dtype=np.uint64)
+        n = C.c_uint64(0)
+        L = N.lib()
+        d = _delim_byte(delim)
+        rc = L.aha_ac_records_batch(self._h, _ptr(corpus), _ptr(doc_offsets), D, d, 0, None, 0, None, C.byref(n))
+        if rc != N.AHA_E_CAPACITY:
+            self._check(rc)
+        cap = int(n.value)
+        rec = np.zeros(cap + 1, dtype=np.uint64)
+        self._check(L.aha_ac_records_batch(self._h, _ptr(corpus), _ptr(doc_offsets), D, d, 0, _ptr(rec), cap, _ptr(dro), C.byref(n)))
+        return rec[: int(n.value) + 1], dro
+
+    def records_device(self, corpus, doc_offsets, rec_offsets, doc_rec_offsets=None, delim=b"\n", cap=None, stream=None):
+        """Device-resident records on torch CUDA tensors: uint8 corpus (any alignment), int64/uint64 doc offsets, rec_offsets
+        int64/uint64 [cap + 1] or None (a sizing call), doc_rec_offsets int64/uint64 [D+1] or None.
+        -> n_records; raises AhaError(AHA_E_CAPACITY) when rec_offsets is too small (e.n_required = the records needed);
+        nothing is written then."""
+        import torch
+
+        assert corpus.is_cuda and corpus.dtype == torch.uint8 and corpus.is_contiguous()
+        assert doc_offsets.is_cuda and doc_offsets.dtype in (torch.int64, torch.uint64)
+        if rec_offsets is not None:
+            if not (rec_offsets.is_cuda and rec_offsets.dtype in (torch.int64, torch.uint64) and rec_offsets.is_contiguous()
+                    and rec_offsets.numel() >= 1):
+                raise ValueError("rec_offsets must be a contiguous int64/uint64 CUDA tensor of at least one entry")
+            cap = rec_offsets.numel() - 1 if cap is None else min(int(cap), rec_offsets.numel() - 1)
+        else:
+            cap = 0
+        if doc_rec_offsets is not None and not (doc_rec_offsets.is_cuda and doc_rec_offsets.dtype in (torch.int64, torch.uint64)
+                                                and doc_rec_offsets.is_contiguous()
+                                                and doc_rec_offsets.numel() >= doc_offsets.numel()):
+            raise ValueError("doc_rec_offsets must be a contiguous int64/uint64 CUDA tensor of at least D + 1 entries")
+        D = doc_offsets.numel() - 1
+        n = C.c_uint64(0)
+        s = stream if stream is not None else torch.cuda.current_stream(corpus.device).cuda_stream
+        rc = N.lib().aha_ac_records_batch_device(
+            self._h, corpus.data_ptr(), doc_offsets.data_ptr(), D, corpus.numel(), _delim_byte(delim), 0,
+            rec_offsets.data_ptr() if rec_offsets is not None else None, cap,
+            doc_rec_offsets.data_ptr() if doc_rec_offsets is not None else None, C.byref(n), C.c_void_p(s))
+        if rc == N.AHA_E_CAPACITY:
+            raise self._capacity_error(rc, n)
+        self._check(rc)
+        return int(n.value)
+
+    @staticmethod
+    def _grep_capacity_error(rc, n_docs, n_bytes):
+        e = AhaError(rc, N.lib().aha_strerror(rc).decode())
+        e.n_required = int(n_docs.value)
+        e.bytes_required = int(n_bytes.value)
+        return e
+
+    def grep_batch(self, corpus, doc_offsets, sep=None, invert=False, text=True):
+        """The documents with at least one hit of match_batch(corpus, doc_offsets, sep) -- invert: those without one --
+        compacted on the device: -> (kept_docs uint64[n_kept], uint8 array, doc_out_offsets uint64[n_kept+1]); kept document
+        i is document kept_docs[i] and its bytes are out[doc_out_offsets[i]:doc_out_offsets[i+1]].  text False: no bytes are
+        copied (an empty array comes back).  A sizing call first."""
+        if isinstance(corpus, (bytes, bytearray)):
+            corpus = np.frombuffer(bytes(corpus), dtype=np.uint8)
+        corpus = np.ascontiguousarray(corpus, dtype=np.uint8)
+        doc_offsets = np.ascontiguousarray(doc_offsets, dtype=np.uint64)
+        D = doc_offsets.size - 1
+        p = _params(False, sep)
+        flags = N.AHA_GREP_INVERT if invert else 0
+        nk, nb = C.c_uint64(0), C.c_uint64(0)
+        L = N.lib()
+        self._check(L.aha_ac_grep_batch(self._h, _ptr(corpus), _ptr(doc_offsets), D, C.byref(p), flags, None, None, 0, None, 0,
+                                        C.byref(nk), C.byref(nb), None))
+        cap_docs, cap_bytes = int(nk.value), int(nb.value) if text else 0
+        kept = np.zeros(max(cap_docs, 1), dtype=np.uint64)
+        doo = np.zeros(cap_docs + 1, dtype=np.uint64)
+        out = np.zeros(max(cap_bytes, 1), dtype=np.uint8)
+        self._check(L.aha_ac_grep_batch(self._h, _ptr(corpus), _ptr(doc_offsets), D, C.byref(p), flags, _ptr(kept), _ptr(doo),
+                                        cap_docs, _ptr(out) if text else None, cap_bytes, C.byref(nk), C.byref(nb), None))
+        return kept[: int(nk.value)], out[: int(nb.value) if text else 0], doo[: int(nk.value) + 1]
+
+    def grep_batch_device(self, corpus, doc_offsets, kept_docs=None, doc_out_offsets=None, out=None, sep=None, invert=False,
+                          cap_docs=None, cap_bytes=None, stream=None):
+        """Device-resident grep on torch CUDA tensors: uint8 corpus, int64/uint64 doc offsets, kept_docs int64/uint64
+        [cap_docs] or None, doc_out_offsets int64/uint64 [cap_docs + 1] or None, out uint8 [cap_bytes] (any alignment) or None
+        (no bytes are copied).  -> (n_kept, n_out_bytes, n_hits); raises AhaError(AHA_E_CAPACITY) when a buffer is too small
+        (e.n_required = the documents needed, e.bytes_required = the bytes needed); nothing is written then."""
+        import torch
+
+        assert corpus.is_cuda and corpus.dtype == torch.uint8 and corpus.is_contiguous()
+        assert doc_offsets.is_cuda and doc_offsets.dtype in (torch.int64, torch.uint64)
+        for name, t in (("kept_docs", kept_docs), ("doc_out_offsets", doc_out_offsets)):
+            if t is not None and not (t.is_cuda and t.dtype in (torch.int64, torch.uint64) and t.is_contiguous()):
+                raise ValueError(name + " must be a contiguous int64/uint64 CUDA tensor")
+        room = []
+        if kept_docs is not None:
+            room.append(kept_docs.numel())
+        if doc_out_offsets is not None:
+            if doc_out_offsets.numel() < 1:
+                raise ValueError("doc_out_offsets must have at least one entry")
+            room.append(doc_out_offsets.numel() - 1)
+        cap_docs = 0 if not room else min(room) if cap_docs is None else min([int(cap_docs)] + room)
+        if out is not None:
+            if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.dim() == 1):
+                raise ValueError("out must be a contiguous one-dimensional uint8 CUDA tensor")
+            cap_bytes = out.numel() if cap_bytes is None else min(int(cap_bytes), out.numel())
+        else:
+            cap_bytes = 0
+        D = doc_offsets.numel() - 1
+        p = _params(False, sep)
+        nk, nb, nh = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        s = stream if stream is not None else torch.cuda.current_stream(corpus.device).cuda_stream
+        rc = N.lib().aha_ac_grep_batch_device(
+            self._h, corpus.data_ptr(), doc_offsets.data_ptr(), D, corpus.numel(), C.byref(p), N.AHA_GREP_INVERT if invert else 0,
+            kept_docs.data_ptr() if kept_docs is not None else None,
+            doc_out_offsets.data_ptr() if doc_out_offsets is not None else None, cap_docs,
+            out.data_ptr() if out is not None else None, cap_bytes, C.byref(nk), C.byref(nb), C.byref(nh), C.c_void_p(s))
+        if rc == N.AHA_E_CAPACITY:
+            raise self._grep_capacity_error(rc, nk, nb)
+        self._check(rc)
+        return int(nk.value), int(nb.value), int(nh.value)
+
+    def grep_corpus(self, corpus, sep=None, invert=False, text=True):
+        """grep_batch of a batch that already lives in HBM (DeviceCorpus), downloaded:
+        -> (kept_docs uint64[n_kept], uint8 array, doc_out_offsets uint64[n_kept+1], n_hits)."""
+        D = corpus.n_docs
+        p = _params(False, sep)
+        flags = N.AHA_GREP_INVERT if invert else 0
+        dev = corpus.device
+        nk, nb, nh = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        L = N.lib()
+        self._check(L.aha_ac_grep_batch_device(self._h, corpus.ptr, corpus.doc_ptr, D, corpus.n_bytes, C.byref(p), flags, None, None,
+                                               0, None, 0, C.byref(nk), C.byref(nb), C.byref(nh), None))
+        cap_docs, cap_bytes = int(nk.value), int(nb.value) if text else 0
+        kept, doo = DeviceBuffer(dev, max(cap_docs, 1) * 8), DeviceBuffer(dev, (cap_docs + 1) * 8)
+        out = DeviceBuffer(dev, max(cap_bytes, 1)) if text else None
+        self._check(L.aha_ac_grep_batch_device(self._h, corpus.ptr, corpus.doc_ptr, D, corpus.n_bytes, C.byref(p), flags, kept.ptr,
+                                               doo.ptr, cap_docs, out.ptr if text else None, cap_bytes, C.byref(nk), C.byref(nb),
+                                               C.byref(nh), None))
+        got = out.download(np.zeros(max(cap_bytes, 1), dtype=np.uint8))[:cap_bytes] if text else np.zeros(0, dtype=np.uint8)
+        return (kept.download(np.zeros(max(cap_docs, 1), dtype=np.uint64))[:cap_docs], got,
+                doo.download(np.zeros(cap_docs + 1, dtype=np.uint64)), int(nh.value))
+
+    def grep(self, seq, delim="\n", invert=False, sep=None):
+        """The records of seq -- split at delim, each with its delimiter -- that have a hit of match(record, sep), as a
+        list; invert: those that have none.  bytes in, bytes out; str in, str out.  records plus grep_batch."""
+        b = _b(seq)
+        corpus = np.frombuffer(b, dtype=np.uint8)
+        rec, _ = self.records(corpus, None, delim)
+        _, out, doo = self.grep_batch(corpus, rec, sep=sep, invert=invert)
+        raw = out.tobytes()
+        parts = [raw[int(doo[i]):int(doo[i + 1])] for i in range(doo.size - 1)]
+        return [x.decode("utf-8") for x in parts] if isinstance(seq, str) else parts
 
     # -- cover: which bytes lie inside a hit, and a redacted copy (aha_ac_cover_batch*) ---------------
     def _cover_host(self, corpus, doc_offsets, sep, want_mask, want_redacted, fill):

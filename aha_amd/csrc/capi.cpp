@@ -1583,6 +1583,133 @@ int32_t aha_ac_replace_batch(aha_ac *ac, const aha_repl *table, const uint8_t *c
 }
 
 
+// ---- records and grep calls (aha_ac_records_batch*, aha_ac_grep_batch*) ------------------------------------------------
+// the argument checks both records entries share: before any device work, so they hold on a host-only handle
+static int32_t records_args(aha_ac *ac, const uint64_t *doc_offsets, uint32_t flags, const uint64_t *rec_offsets, uint64_t cap_records,
+                            uint64_t *n_records) {
+  if (!ac || !n_records || !doc_offsets || flags) return AHA_E_INVALID;
+  if (cap_records && !rec_offsets) return AHA_E_INVALID;
+  if (ac->device < 0) return no_device();
+  return AHA_OK;
+}
+
+int32_t aha_ac_records_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
+                                    uint8_t delim, uint32_t flags, uint64_t *d_rec_offsets, uint64_t cap_records,
+                                    uint64_t *d_doc_rec_offsets, uint64_t *n_records, void *stream) {
+  int32_t rc = records_args(ac, d_doc_offsets, flags, d_rec_offsets, cap_records, n_records);
+  if (rc) return rc;
+  Lease lease(ac);
+  return device_records(ac, lease.get(), d_corpus, d_doc_offsets, n_docs, n_bytes, delim, d_rec_offsets, cap_records,
+                        d_doc_rec_offsets, n_records, stream, false);
+}
+
+// The host entry: the batch goes up in one piece into the staging buffers of the leased scratch set, over its private stream;
+// the offsets come back once the call has succeeded.
+int32_t aha_ac_records_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc_offsets, uint64_t n_docs, uint8_t delim,
+                             uint32_t flags, uint64_t *rec_offsets, uint64_t cap_records, uint64_t *doc_rec_offsets,
+                             uint64_t *n_records) {
+  int32_t rc = records_args(ac, doc_offsets, flags, rec_offsets, cap_records, n_records);
+  if (rc) return rc;
+  if ((rc = check_host_batch(corpus, doc_offsets, n_docs))) return rc;
+  const uint64_t n_bytes = doc_offsets[n_docs];
+  DeviceGuard g(ac->device);
+  Lease lease(ac);
+  Scratch *sc = lease.get();
+  HostBatch B;
+  if ((rc = stage_host_batch(ac, sc, corpus, doc_offsets, n_docs, (n_docs + 1) * 8, rec_offsets ? (cap_records + 1) * 8 : 0, B)))
+    return rc;
+  uint64_t *d_dro = (uint64_t *)B.d_per_doc, *d_rec = (uint64_t *)B.d_per_call;
+  hipStream_t s = B.s;
+  uint64_t nr = 0;
+  rc = device_records(ac, sc, B.d_corpus, B.d_doc, n_docs, n_bytes, delim, d_rec, d_rec ? cap_records : 0, d_dro, &nr, s,
+                      true);  // the offsets were checked on the host above
+  if (rc == AHA_E_CAPACITY) *n_records = nr;
+  if (rc != AHA_OK) return rc;
+  if (rec_offsets) HIPCHK(ac, hipMemcpyAsync(rec_offsets, d_rec, (nr + 1) * 8, hipMemcpyDeviceToHost, s));
+  if (doc_rec_offsets) HIPCHK(ac, hipMemcpyAsync(doc_rec_offsets, d_dro, (n_docs + 1) * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  *n_records = nr;
+  return AHA_OK;
+}
+
+// the argument checks both grep entries share: before any device work, so they hold on a host-only handle.  out / corpus: the
+// two address ranges that must not overlap (there is no in-place form)
+static int32_t grep_args(aha_ac *ac, const uint8_t *corpus, uint64_t n_bytes, const uint64_t *doc_offsets, const aha_match_params *params,
+                         uint32_t flags, const uint64_t *kept_docs, const uint64_t *doc_out_offsets, uint64_t cap_docs,
+                         const uint8_t *out, uint64_t cap_bytes, uint64_t *n_kept) {
+  if (!ac || !n_kept || !doc_offsets || (flags & ~AHA_GREP_INVERT)) return AHA_E_INVALID;
+  if (int32_t rc = no_longest_form(ac, params, "grep calls have no match_longest form")) return rc;
+  if (params && params->struct_size >= offsetof(aha_match_params, char_offsets) + sizeof(params->char_offsets) && params->char_offsets) {
+    tls_err = "grep calls take byte offsets only";
+    return AHA_E_INVALID;
+  }
+  if ((cap_docs && !kept_docs && !doc_out_offsets) || (cap_bytes && !out)) return AHA_E_INVALID;
+  if (cap_bytes && n_bytes && corpus) {
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), c0 = reinterpret_cast<uintptr_t>(corpus);
+    if (o0 < c0 + n_bytes && c0 < o0 + cap_bytes) {
+      tls_err = "grep calls have no in-place form: out overlaps the corpus";
+      return AHA_E_INVALID;
+    }
+  }
+  if (ac->device < 0) return no_device();
+  return AHA_OK;
+}
+
+int32_t aha_ac_grep_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
+                                 const aha_match_params *params, uint32_t flags, uint64_t *d_kept_docs, uint64_t *d_doc_out_offsets,
+                                 uint64_t cap_docs, uint8_t *d_out, uint64_t cap_bytes, uint64_t *n_kept, uint64_t *n_out_bytes,
+                                 uint64_t *n_hits, void *stream) {
+  int32_t rc = grep_args(ac, d_corpus, n_bytes, d_doc_offsets, params, flags, d_kept_docs, d_doc_out_offsets, cap_docs, d_out, cap_bytes,
+                         n_kept);
+  if (rc) return rc;
+  Lease lease(ac);
+  return device_grep(ac, lease.get(), d_corpus, d_doc_offsets, n_docs, n_bytes, params, flags, d_kept_docs, d_doc_out_offsets, cap_docs,
+                     d_out, cap_bytes, n_kept, n_out_bytes, n_hits, stream, false);
+}
+
+// The host entry: the batch goes up in one piece into the staging buffers of the leased scratch set, over its private stream;
+// the kept documents, their offsets and their bytes come back once the call has succeeded.
+int32_t aha_ac_grep_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc_offsets, uint64_t n_docs, const aha_match_params *params,
+                          uint32_t flags, uint64_t *kept_docs, uint64_t *doc_out_offsets, uint64_t cap_docs, uint8_t *out,
+                          uint64_t cap_bytes, uint64_t *n_kept, uint64_t *n_out_bytes, uint64_t *n_hits) {
+  if (!doc_offsets) return AHA_E_INVALID;
+  int32_t rc = grep_args(ac, corpus, doc_offsets[n_docs], doc_offsets, params, flags, kept_docs, doc_out_offsets, cap_docs, out, cap_bytes,
+                         n_kept);
+  if (rc) return rc;
+  if ((rc = check_host_batch(corpus, doc_offsets, n_docs))) return rc;
+  const uint64_t n_bytes = doc_offsets[n_docs];
+  DeviceGuard g(ac->device);
+  Lease lease(ac);
+  Scratch *sc = lease.get();
+  HostBatch B;
+  // per document: the kept documents' indices, cap_docs of them, then their offsets, cap_docs + 1
+  const bool per_doc = kept_docs || doc_out_offsets;
+  if ((rc = stage_host_batch(ac, sc, corpus, doc_offsets, n_docs, per_doc ? (2 * cap_docs + 1) * 8 : 0, out ? std::max<uint64_t>(cap_bytes, 1) : 0,
+                             B)))
+    return rc;
+  uint64_t *d_kept = kept_docs ? (uint64_t *)B.d_per_doc : nullptr;
+  uint64_t *d_doo = doc_out_offsets ? (uint64_t *)B.d_per_doc + cap_docs : nullptr;
+  uint8_t *d_out = (uint8_t *)B.d_per_call;
+  hipStream_t s = B.s;
+  uint64_t nk = 0, nb = 0, nh = 0;
+  rc = device_grep(ac, sc, B.d_corpus, B.d_doc, n_docs, n_bytes, params, flags, d_kept, d_doo, cap_docs, d_out, d_out ? cap_bytes : 0, &nk,
+                   &nb, &nh, s, true);  // the offsets were checked on the host above
+  if (rc == AHA_E_CAPACITY) {  // (both required numbers and the count, as the device entry gives them)
+    *n_kept = nk;
+    if (n_out_bytes) *n_out_bytes = nb;
+    if (n_hits) *n_hits = nh;
+  }
+  if (rc != AHA_OK) return rc;
+  if (kept_docs && nk) HIPCHK(ac, hipMemcpyAsync(kept_docs, d_kept, nk * 8, hipMemcpyDeviceToHost, s));
+  if (doc_out_offsets) HIPCHK(ac, hipMemcpyAsync(doc_out_offsets, d_doo, (nk + 1) * 8, hipMemcpyDeviceToHost, s));
+  if (out && nb) HIPCHK(ac, hipMemcpyAsync(out, d_out, nb, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  *n_kept = nk;
+  if (n_out_bytes) *n_out_bytes = nb;
+  if (n_hits) *n_hits = nh;
+  return AHA_OK;
+}
+
 struct aha_corpus {
   int device = -1;
   void *bytes = nullptr;

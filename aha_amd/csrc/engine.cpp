@@ -86,6 +86,8 @@ static void doccount_setup(aha_ac *ac) {
   ac->sel_hit_bytes = env("AHA_SELECT_HIT_BYTES", ac->dc_hit_bytes, 12, kV2MaxRegionBytes);
   // replace calls: the cap of the scan's and the copy's grids (tests: 1, so that workgroups loop over tiles)
   ac->rep_blocks = (uint32_t)env("AHA_REPLACE_BLOCKS", 0, 1, 1u << 20);
+  // records and grep calls: the cap of their grids, the reused rank, scan and copy launches included
+  ac->grep_blocks = (uint32_t)env("AHA_GREP_BLOCKS", 0, 1, 1u << 20);
 }
 
 void v2_setup(aha_ac *ac) {
@@ -1726,6 +1728,153 @@ int32_t device_replace(aha_ac *ac, Scratch *sc, const aha_repl *table, const uin
     publish_timing(ac, t_sel);
   }
   if (total > cap_bytes) {
+    tls_err = "output buffer too small";
+    return AHA_E_CAPACITY;
+  }
+  return AHA_OK;
+}
+
+// ---- records and grep calls (aha_ac_records_batch*, aha_ac_grep_batch*) ------------------------------------------------
+static void *grp_reserve(Scratch *sc, GrepSlot slot, size_t bytes) { return reserve_ptr(sc->grpbuf[slot], bytes, kGrowEighth); }
+static uint32_t grep_grid(const aha_ac *ac) { return ac->grep_blocks ? ac->grep_blocks : 8u * std::max<uint32_t>(ac->v2_grid, 64u); }
+
+// One device-resident batch split into records (aha_ac_records_batch_device).  The handle's keys play no part: its device,
+// scratch and stream do.
+//   1. The record-end mask in one pass over the text, the documents' ends OR-ed in behind it (scan_grep.hip).
+//   2. Its rank by select's ranker; the total comes back to the host, where the capacity verdict is given.
+//   3. Once it fits: every set bit as a record's end, and the documents' offsets into the records -- the rank of their first
+//      byte (select's per-position rank).
+// A failing call writes none of the caller's buffers.  Scratch: N / 8 bytes of mask, 8 bytes per 2048 text bytes.
+int32_t device_records(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                       uint64_t n_bytes, uint8_t delim, uint64_t *d_rec_offsets, uint64_t cap_records, uint64_t *d_doc_rec_offsets,
+                       uint64_t *n_records, void *stream, bool offsets_checked) {
+  if (!ac || !n_records || !d_doc_offsets) return AHA_E_INVALID;
+  if (cap_records && !d_rec_offsets) return AHA_E_INVALID;
+  if (ac->device < 0) return no_device();
+  DeviceGuard g(ac->device);
+  hipStream_t s = (hipStream_t)stream;
+  *n_records = 0;
+  int32_t rc;
+  if (!offsets_checked && (rc = check_docs_now(ac, sc, d_doc_offsets, n_docs, n_bytes, s))) return rc;
+  if (n_bytes && !d_corpus) return AHA_E_INVALID;
+  const uint32_t blocks = grep_grid(ac);
+  const uint64_t n_words = (n_bytes + 31) / 32, n_blk = select_rank_blocks(n_bytes);
+  uint32_t *mask = nullptr;
+  uint64_t *blk = nullptr;
+  uint64_t total = 0;
+  if (n_bytes) {
+    mask = (uint32_t *)grp_reserve(sc, kGrpEnds, n_words * 4);
+    blk = (uint64_t *)grp_reserve(sc, kGrpEndBlocks, (n_blk + 1) * 8);
+    if (!mask || !blk) {
+      tls_err = "hipMalloc failed for the scratch of a records call";
+      return AHA_E_HIP;
+    }
+    grep_launch_ends(d_corpus, n_bytes, delim, d_doc_offsets, n_docs, mask, blocks, s);
+    select_launch_rank(mask, n_bytes, blk, blocks, s);
+    HIPCHK(ac, hipGetLastError());
+    HIPCHK(ac, hipMemcpyAsync(&total, blk + n_blk, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(ac, hipStreamSynchronize(s));
+  }
+  *n_records = total;
+  if (total > cap_records) {
+    tls_err = "output buffer too small";
+    return AHA_E_CAPACITY;
+  }
+  if (n_bytes) {
+    if (d_rec_offsets) grep_launch_emit_ends(mask, n_bytes, blk, d_rec_offsets, blocks, s);
+    if (d_doc_rec_offsets) select_launch_rank_docs(mask, blk, d_doc_offsets, n_docs + 1, 0, d_doc_rec_offsets, blocks, s);
+    HIPCHK(ac, hipGetLastError());
+  } else {
+    if (d_rec_offsets) HIPCHK(ac, hipMemsetAsync(d_rec_offsets, 0, 8, s));
+    if (d_doc_rec_offsets) HIPCHK(ac, hipMemsetAsync(d_doc_rec_offsets, 0, (n_docs + 1) * 8, s));
+  }
+  HIPCHK(ac, hipStreamSynchronize(s));
+  return AHA_OK;
+}
+
+// One device-resident batch filtered (aha_ac_grep_batch_device).
+//   1. device_count without key counts: the documents' hit offsets into scratch, the total, the offsets validated.
+//   2. The keep, S and T masks over documents (scan_grep.hip kgr_flag) and their ranks by select's ranker: the kept documents
+//      and the dropped runs come back to the host as two counts.
+//   3. Per dropped run its first byte and its change of length (minus its bytes); replace's scan gives shift; the total comes
+//      back to the host, where the verdict is given.  Nothing has been written to the caller so far.
+//   4. The kept documents' indices and offsets, and replace's copy fed with the runs as deleted hits.
+// A failing call writes none of the caller's buffers.
+int32_t device_grep(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
+                    const aha_match_params *params, uint32_t flags, uint64_t *d_kept_docs, uint64_t *d_doc_out_offsets,
+                    uint64_t cap_docs, uint8_t *d_out, uint64_t cap_bytes, uint64_t *n_kept, uint64_t *n_out_bytes,
+                    uint64_t *n_hits_out, void *stream, bool offsets_checked) {
+  if (!ac || !n_kept || !d_doc_offsets || (flags & ~AHA_GREP_INVERT)) return AHA_E_INVALID;
+  if ((cap_docs && !d_kept_docs && !d_doc_out_offsets) || (cap_bytes && !d_out)) return AHA_E_INVALID;
+  if (ac->device < 0) return no_device();
+  DeviceGuard g(ac->device);
+  hipStream_t s = (hipStream_t)stream;
+  const uint64_t D = n_docs;
+  *n_kept = 0;
+  if (n_out_bytes) *n_out_bytes = 0;
+  if (n_hits_out) *n_hits_out = 0;
+  auto nomem = [&]() {
+    tls_err = "hipMalloc failed for the scratch of a grep call";
+    return AHA_E_HIP;
+  };
+  uint64_t *d_dho = (uint64_t *)grp_reserve(sc, kGrpHitOff, (D + 1) * 8);
+  if (!d_dho) return nomem();
+  int32_t rc;
+  uint64_t n_hits = 0;
+  if ((rc = device_count(ac, sc, d_corpus, d_doc_offsets, D, n_bytes, params, 0, nullptr, d_dho, &n_hits, stream, offsets_checked)))
+    return rc;
+  const bool prof = ac->profiling.load();
+  const auto t0 = std::chrono::steady_clock::now();
+  const uint32_t blocks = grep_grid(ac);
+  const uint64_t n_words = (D + 31) / 32, n_blk = select_rank_blocks(D);
+  uint32_t *masks = (uint32_t *)grp_reserve(sc, kGrpDocMasks, std::max<uint64_t>(n_words, 1) * 3 * 4);
+  uint64_t *blks = (uint64_t *)grp_reserve(sc, kGrpDocBlocks, (n_blk + 1) * 3 * 8);
+  RepEntry *ent = (RepEntry *)grp_reserve(sc, kGrpTable, sizeof(RepEntry));
+  if (!masks || !blks || !ent) return nomem();
+  uint32_t *keep = masks, *S = masks + n_words, *T = masks + 2 * n_words;
+  uint64_t *blk_k = blks, *blk_s = blks + (n_blk + 1), *blk_t = blks + 2 * (n_blk + 1);
+  grep_launch_flag(d_dho, D, (flags & AHA_GREP_INVERT) != 0, keep, S, T, blocks, s);
+  select_launch_rank(keep, D, blk_k, blocks, s);
+  select_launch_rank(S, D, blk_s, blocks, s);
+  select_launch_rank(T, D, blk_t, blocks, s);
+  HIPCHK(ac, hipGetLastError());
+  uint64_t kept = 0, n_runs = 0;
+  HIPCHK(ac, hipMemcpyAsync(&kept, blk_k + n_blk, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipMemcpyAsync(&n_runs, blk_s + n_blk, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  const uint64_t n_sum = replace_scan_blocks(n_runs);
+  aha_hit *sel = (aha_hit *)grp_reserve(sc, kGrpSel, std::max<uint64_t>(n_runs, 1) * sizeof(aha_hit));
+  uint64_t *A = (uint64_t *)grp_reserve(sc, kGrpStart, std::max<uint64_t>(n_runs, 1) * 8);
+  int64_t *shift = (int64_t *)grp_reserve(sc, kGrpShift, (n_runs + 1) * 8);
+  int64_t *sums = (int64_t *)grp_reserve(sc, kGrpSums, (n_sum + 1) * 8);
+  if (!sel || !A || !shift || !sums) return nomem();
+  grep_launch_runs(S, T, D, blk_s, blk_t, d_doc_offsets, n_runs, A, shift, sel, ent, blocks, s);
+  replace_launch_scan(shift, n_runs, sums, blocks, s);
+  HIPCHK(ac, hipGetLastError());
+  int64_t change = 0;
+  HIPCHK(ac, hipMemcpyAsync(&change, shift + n_runs, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  const uint64_t total = (uint64_t)((int64_t)n_bytes + change);
+  const bool per_doc = d_kept_docs || d_doc_out_offsets;
+  const bool fits = !(per_doc && kept > cap_docs) && !(d_out && total > cap_bytes);
+  if (fits) {
+    if (per_doc)
+      grep_launch_emit_docs(keep, S, D, blk_k, blk_s, d_doc_offsets, shift, n_runs, d_kept_docs, d_doc_out_offsets, blocks, s);
+    if (d_out)
+      replace_launch_copy(d_corpus, sel, A, shift, n_runs, ent, 1, (const uint8_t *)ent, d_out, total, blocks, s);
+    HIPCHK(ac, hipGetLastError());
+    HIPCHK(ac, hipStreamSynchronize(s));
+  }
+  *n_kept = kept;
+  if (n_out_bytes) *n_out_bytes = total;
+  if (n_hits_out) *n_hits_out = n_hits;
+  if (prof) {  // ms_write: everything after the count
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    std::lock_guard<std::mutex> lk(ac->last_mu);
+    ac->last.ms_write += (float)ms;
+    ac->last.n_hits = n_hits;
+  }
+  if (!fits) {
     tls_err = "output buffer too small";
     return AHA_E_CAPACITY;
   }

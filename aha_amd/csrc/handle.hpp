@@ -153,6 +153,20 @@ enum FeedSepSlot {
   kFpZeroOff,  // a finish call: the offsets of its empty pieces
   kFpCount
 };
+// grpbuf: records and grep calls (engine.cpp device_records, device_grep; scan_grep.hip)
+enum GrepSlot {
+  kGrpEnds,       // records: the record-end mask, one bit per text byte
+  kGrpEndBlocks,  // records: the set bits before every 64 words of it, the total behind them
+  kGrpHitOff,     // grep: the documents' hit offsets (the count call in front)
+  kGrpDocMasks,   // grep: the keep, S and T masks, one bit per document each
+  kGrpDocBlocks,  // grep: their three block ranks, each with its total behind it
+  kGrpSel,        // grep: one synthesized selection row per dropped run, 12 bytes each
+  kGrpStart,      // grep: A, per dropped run its first byte in the corpus
+  kGrpShift,      // grep: per dropped run the change of length in front of it, the total change behind the last
+  kGrpSums,       // grep: the scan's block sums
+  kGrpTable,      // grep: the one-entry replacement table (the empty replacement)
+  kGrpCount
+};
 // Device scratch of ONE match call (grow-only, reused by later calls that lease the same set).
 struct Scratch {
   std::mutex mu;  // held by the call that leased the set
@@ -172,6 +186,7 @@ struct Scratch {
   Buf fselbuf[kFsCount];
   Buf frepbuf[kFrCount];
   Buf fsepbuf[kFpCount];
+  Buf grpbuf[kGrpCount];
   // every family above, for free_scratch and scratch_bytes (S: Scratch or const Scratch): a new family is one more line here
   template <class S, class Fn>
   static void each_buf(S &sc, Fn fn) {
@@ -185,6 +200,7 @@ struct Scratch {
     for (auto &b : sc.fselbuf) fn(b);
     for (auto &b : sc.frepbuf) fn(b);
     for (auto &b : sc.fsepbuf) fn(b);
+    for (auto &b : sc.grpbuf) fn(b);
   }
   bool dc_rows_clear = false;  // every word of dcbuf[kDcRows] is zero (kdc_compact clears what kdc_add wrote; a call that failed may not have)
   hipStream_t hs[3] = {};  // host-buffer entry: private non-blocking streams for upload, match, download
@@ -278,6 +294,7 @@ struct aha_ac {
   uint32_t dc_sort_max = 0, dc_dense_min = 0, dc_range_keys = 0;
   uint64_t sel_hit_bytes = 0;  // select calls: the bound of a range's hit buffer (AHA_SELECT_HIT_BYTES)
   uint32_t rep_blocks = 0;  // replace calls: the cap of the scan's and the copy's grids (AHA_REPLACE_BLOCKS; 0: the default)
+  uint32_t grep_blocks = 0;  // records and grep calls: the cap of their grids (AHA_GREP_BLOCKS; 0: the default)
   uint32_t seg2 = 0;  // slots below it: the root's and the depth-1 states' rows
   // match_longest only (cedar_replay.cpp): the states that carry one of Cedar's stale END flags, derived on the first
   // match_longest call (it replays every insert: as long again as the rest of compile); dev_longest = dev + the bitmap
@@ -356,7 +373,7 @@ uint64_t scratch_bytes(const Scratch *sc);
 // THE allocator of the grow-only buffers: b holds at least `bytes` afterwards, or nothing (the HIP error is returned, the
 // runtime's sticky one cleared).  What a new buffer gets beyond `bytes` is its family's rule:
 enum Grow {
-  kGrowEighth,   // bytes + bytes / 8 + 256 (v2buf, covbuf, selbuf, repbuf, fselbuf, frepbuf, fsepbuf)
+  kGrowEighth,   // bytes + bytes / 8 + 256 (v2buf, covbuf, selbuf, repbuf, fselbuf, frepbuf, fsepbuf, grpbuf)
   kGrowQuarter,  // bytes + bytes / 4 + 4096 (cntbuf, hostbuf)
   kGrowOrExact   // an eighth, else exactly `bytes`; `bytes` is what it records (dcbuf: what is known to be there)
 };
@@ -481,4 +498,15 @@ int32_t device_replace(aha_ac *ac, Scratch *sc, const aha_repl *table, const uin
                        uint64_t n_docs, uint64_t n_bytes, const aha_match_params *params, uint8_t *d_out, uint64_t cap_bytes,
                        uint64_t *d_doc_out_offsets, uint64_t *n_out_bytes, uint64_t *n_selected, uint64_t *n_hits, void *stream,
                        bool offsets_checked);
+// one device-resident batch split into records (aha_ac_records_batch_device): the record-end mask in one pass over the text,
+// its rank, the offsets once the count is known to fit (scan_grep.hip)
+int32_t device_records(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                       uint64_t n_bytes, uint8_t delim, uint64_t *d_rec_offsets, uint64_t cap_records, uint64_t *d_doc_rec_offsets,
+                       uint64_t *n_records, void *stream, bool offsets_checked);
+// one device-resident batch filtered (aha_ac_grep_batch_device): device_count for the hits per document, the kept documents and
+// the dropped runs from them (scan_grep.hip), replace's scan and copy over the runs (scan_replace.hip)
+int32_t device_grep(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
+                    const aha_match_params *params, uint32_t flags, uint64_t *d_kept_docs, uint64_t *d_doc_out_offsets,
+                    uint64_t cap_docs, uint8_t *d_out, uint64_t cap_bytes, uint64_t *n_kept, uint64_t *n_out_bytes, uint64_t *n_hits,
+                    void *stream, bool offsets_checked);
 }  // namespace ahai

@@ -326,6 +326,26 @@ void replace_launch_copy(const uint8_t *text, const void *sel, const uint64_t *s
                          const RepEntry *ent, uint32_t n_keys, const uint8_t *blob, uint8_t *out, uint64_t total,
                          uint32_t max_blocks, void *stream);
 
+// records and grep paths (scan_grep.hip; engine.cpp device_records, device_grep).  Masks are ranked by select_launch_rank.
+// mask[0, ceil(n_bytes / 32)): bit p = (corpus[p] == delim) or p + 1 is a document's end; the corpus may have any alignment
+void grep_launch_ends(const uint8_t *corpus, uint64_t n_bytes, uint8_t delim, const uint64_t *doc_off, uint64_t n_docs, uint32_t *mask,
+                      uint32_t max_blocks, void *stream);
+// rec_off[0] = 0, rec_off[r + 1] = p + 1 for the r-th set bit p of the ranked mask
+void grep_launch_emit_ends(const uint32_t *mask, uint64_t n_bytes, const uint64_t *blk, uint64_t *rec_off, uint32_t max_blocks,
+                           void *stream);
+// keep / S / T: ceil(n_docs / 32) words each, from the documents' hit offsets dho[0 .. n_docs]
+void grep_launch_flag(const uint64_t *dho, uint64_t n_docs, bool invert, uint32_t *keep, uint32_t *S, uint32_t *T, uint32_t max_blocks,
+                      void *stream);
+// the dropped runs as replace's copy takes them: start[j], shift[j] = delta[j] (n_runs + 1 words: the scan's), sel[j] (12 bytes
+// each), ent[0] = the empty replacement
+void grep_launch_runs(const uint32_t *S, const uint32_t *T, uint64_t n_docs, const uint64_t *blk_s, const uint64_t *blk_t,
+                      const uint64_t *doc_off, uint64_t n_runs, uint64_t *start, int64_t *shift, void *sel, RepEntry *ent,
+                      uint32_t max_blocks, void *stream);
+// kept_docs[r], doc_out[r] for the kept documents in order (either may be null), doc_out[n_kept] = the total
+void grep_launch_emit_docs(const uint32_t *keep, const uint32_t *S, uint64_t n_docs, const uint64_t *blk_k, const uint64_t *blk_s,
+                           const uint64_t *doc_off, const int64_t *shift, uint64_t n_runs, uint64_t *kept_docs, uint64_t *doc_out,
+                           uint32_t max_blocks, void *stream);
+
 // exchange format of the multi-GPU all-gatherv (kernels.hip): {end, value} pairs <-> Hit triples
 void launch_hits_pack(const int32_t *hits, uint64_t n, int32_t *pairs, void *stream);
 void launch_hits_unpack(const DevAut &A, const int32_t *pairs, uint64_t n, int chars, int32_t *hits, void *stream);

@@ -220,6 +220,20 @@ lib LibAhaHip
                                   n_bytes : UInt64, params : MatchParams*, flags : UInt32, d_out : UInt8*, cap_bytes : UInt64,
                                   d_doc_out_offsets : UInt64*, n_out_bytes : UInt64*, n_selected : UInt64*, n_hits : UInt64*,
                                   stream : Void*) : Int32
+  # records: a batch split at a delimiter byte and at the documents' ends; grep: the documents with a hit (GREP_INVERT: without)
+  GREP_INVERT = 1_u32
+  fun aha_ac_records_batch(ac : Ac, corpus : UInt8*, doc_offsets : UInt64*, n_docs : UInt64, delim : UInt8, flags : UInt32,
+                           rec_offsets : UInt64*, cap_records : UInt64, doc_rec_offsets : UInt64*, n_records : UInt64*) : Int32
+  fun aha_ac_records_batch_device(ac : Ac, d_corpus : UInt8*, d_doc_offsets : UInt64*, n_docs : UInt64, n_bytes : UInt64,
+                                  delim : UInt8, flags : UInt32, d_rec_offsets : UInt64*, cap_records : UInt64,
+                                  d_doc_rec_offsets : UInt64*, n_records : UInt64*, stream : Void*) : Int32
+  fun aha_ac_grep_batch(ac : Ac, corpus : UInt8*, doc_offsets : UInt64*, n_docs : UInt64, params : MatchParams*, flags : UInt32,
+                        kept_docs : UInt64*, doc_out_offsets : UInt64*, cap_docs : UInt64, out : UInt8*, cap_bytes : UInt64,
+                        n_kept : UInt64*, n_out_bytes : UInt64*, n_hits : UInt64*) : Int32
+  fun aha_ac_grep_batch_device(ac : Ac, d_corpus : UInt8*, d_doc_offsets : UInt64*, n_docs : UInt64, n_bytes : UInt64,
+                               params : MatchParams*, flags : UInt32, d_kept_docs : UInt64*, d_doc_out_offsets : UInt64*,
+                               cap_docs : UInt64, d_out : UInt8*, cap_bytes : UInt64, n_kept : UInt64*, n_out_bytes : UInt64*,
+                               n_hits : UInt64*, stream : Void*) : Int32
   # feeds: sequences that arrive in pieces across calls (offsets relative to the piece; FEED_CHARS: in characters)
   type Feed = Void*
   FEED_CHARS = 1_u32
@@ -577,6 +591,47 @@ module Aha
       end
       raise String.new(LibAhaHip.aha_last_error(@handle)) if rc != 0
       Array.new(docs.size) { |d| bytes[doo[d], doo[d + 1] - doo[d]] }
+    end
+
+    # The offsets of the records of one sequence: split at the delimiter byte, every record with its delimiter, none empty
+    # (aha_ac_records_batch).  R + 1 offsets, 0 first: a doc_offsets for the batch entry points.
+    def records(seq : String | Bytes, delim : UInt8 = 10_u8) : Array(UInt64)
+      bytes = seq.is_a?(String) ? seq.to_slice : seq
+      offs = [0_u64, bytes.size.to_u64]
+      n = 0_u64
+      rc = LibAhaHip.aha_ac_records_batch(@handle, bytes.to_unsafe, offs.to_unsafe, 1_u64, delim, 0_u32, Pointer(UInt64).null,
+        0_u64, Pointer(UInt64).null, pointerof(n))
+      rec = Array(UInt64).new(n + 1, 0_u64)
+      if rc == E_CAPACITY || rc == 0 # n is the required count; nothing was written
+        rc = LibAhaHip.aha_ac_records_batch(@handle, bytes.to_unsafe, offs.to_unsafe, 1_u64, delim, 0_u32, rec.to_unsafe, n,
+          Pointer(UInt64).null, pointerof(n))
+      end
+      raise String.new(LibAhaHip.aha_last_error(@handle)) if rc != 0
+      rec
+    end
+
+    # The records of seq that have a hit of match(record, sep: sep), each with its delimiter; invert: those that have none
+    # (aha_ac_records_batch, then aha_ac_grep_batch over the records; Aha::AC has no such method).
+    def grep(seq : String | Bytes, delim : UInt8 = 10_u8, invert : Bool = false, sep : BitArray? = nil) : Array(Bytes)
+      bytes = seq.is_a?(String) ? seq.to_slice : seq
+      rec = records(bytes, delim)
+      n_rec = (rec.size - 1).to_u64
+      params = AC.params(false, sep)
+      flags = invert ? LibAhaHip::GREP_INVERT : 0_u32
+      nk = 0_u64
+      nb = 0_u64
+      # a sizing call: no buffer, no capacity -- it succeeds and gives both counts
+      rc = LibAhaHip.aha_ac_grep_batch(@handle, bytes.to_unsafe, rec.to_unsafe, n_rec, pointerof(params), flags,
+        Pointer(UInt64).null, Pointer(UInt64).null, 0_u64, Pointer(UInt8).null, 0_u64, pointerof(nk), pointerof(nb),
+        Pointer(UInt64).null)
+      raise String.new(LibAhaHip.aha_last_error(@handle)) if rc != 0
+      doo = Array(UInt64).new(nk + 1, 0_u64)
+      out_bytes = Bytes.new(nb)
+      rc = LibAhaHip.aha_ac_grep_batch(@handle, bytes.to_unsafe, rec.to_unsafe, n_rec, pointerof(params), flags,
+        Pointer(UInt64).null, doo.to_unsafe, nk, nb > 0 ? out_bytes.to_unsafe : Pointer(UInt8).null, nb, pointerof(nk),
+        pointerof(nb), Pointer(UInt64).null)
+      raise String.new(LibAhaHip.aha_last_error(@handle)) if rc != 0
+      Array.new(nk.to_i32) { |i| out_bytes[doo[i], doo[i + 1] - doo[i]] }
     end
 
     private def run(seq : Bytes, chars : Bool, sep : BitArray?, longest : Int32 = 0, &block)

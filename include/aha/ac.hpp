@@ -379,6 +379,67 @@ class AC {
     return out;
   }
 
+  // The batch split into records at `delim` and at the documents' ends, on the device (aha_ac_records_batch): what is returned
+  // holds R + 1 offsets, 0 first; a record ends behind a delimiter or at a document's end and is never empty; it is a
+  // doc_offsets for every batch call.  doc_rec_offsets (optional): D + 1 offsets into the records.  A sizing call first.
+  std::vector<uint64_t> records_batch(std::string_view corpus, const std::vector<uint64_t> &doc_offsets, char delim = '\n',
+                                      std::vector<uint64_t> *doc_rec_offsets = nullptr) const {
+    if (doc_offsets.empty()) throw Error(AHA_E_INVALID, "doc_offsets holds D + 1 entries");
+    const uint64_t D = doc_offsets.size() - 1;
+    const uint8_t *text = reinterpret_cast<const uint8_t *>(corpus.data());
+    const uint8_t dl = static_cast<uint8_t>(delim);
+    std::vector<uint64_t> dro(D + 1);
+    uint64_t n = 0;
+    int32_t rc = aha_ac_records_batch(h_, text, doc_offsets.data(), D, dl, 0, nullptr, 0, nullptr, &n);
+    std::vector<uint64_t> rec(n + 1, 0);
+    if (rc == AHA_E_CAPACITY || rc == AHA_OK) rc = aha_ac_records_batch(h_, text, doc_offsets.data(), D, dl, 0, rec.data(), n, dro.data(), &n);
+    if (rc != AHA_OK) {
+      const char *m = aha_last_error(h_);
+      throw Error(rc, (m && *m) ? m : aha_strerror(rc));
+    }
+    if (doc_rec_offsets) *doc_rec_offsets = std::move(dro);
+    return rec;
+  }
+  std::vector<uint64_t> records(std::string_view seq, char delim = '\n') const { return records_batch(seq, {0, seq.size()}, delim); }
+  // The documents with at least one hit of match_batch -- invert: those without one -- compacted on the device
+  // (aha_ac_grep_batch): their bytes one behind the other; kept_docs (optional): their indices, ascending; doc_out_offsets
+  // (optional): n_kept + 1 offsets into what is returned.  A sizing call first.
+  std::string grep_batch(std::string_view corpus, const std::vector<uint64_t> &doc_offsets, bool invert = false,
+                         std::vector<uint64_t> *kept_docs = nullptr, std::vector<uint64_t> *doc_out_offsets = nullptr,
+                         uint64_t *n_hits = nullptr) const {
+    if (doc_offsets.empty()) throw Error(AHA_E_INVALID, "doc_offsets holds D + 1 entries");
+    aha_match_params p{};
+    p.struct_size = sizeof(p);
+    const uint64_t D = doc_offsets.size() - 1;
+    const uint8_t *text = reinterpret_cast<const uint8_t *>(corpus.data());
+    const uint32_t flags = invert ? AHA_GREP_INVERT : 0u;
+    uint64_t nk = 0, nb = 0, nh = 0;
+    int32_t rc = aha_ac_grep_batch(h_, text, doc_offsets.data(), D, &p, flags, nullptr, nullptr, 0, nullptr, 0, &nk, &nb, &nh);
+    std::vector<uint64_t> kept(nk + 1), doo(nk + 1);
+    std::string out(nb, '\0');
+    if (rc == AHA_OK)
+      rc = aha_ac_grep_batch(h_, text, doc_offsets.data(), D, &p, flags, kept.data(), doo.data(), nk,
+                             nb ? reinterpret_cast<uint8_t *>(&out[0]) : nullptr, nb, &nk, &nb, &nh);
+    if (rc != AHA_OK) {
+      const char *m = aha_last_error(h_);
+      throw Error(rc, (m && *m) ? m : aha_strerror(rc));
+    }
+    kept.resize(nk);
+    if (kept_docs) *kept_docs = std::move(kept);
+    if (doc_out_offsets) *doc_out_offsets = std::move(doo);
+    if (n_hits) *n_hits = nh;
+    return out;
+  }
+  // The records of seq (split at delim, each with its delimiter) that have a hit; invert: those that have none.
+  std::vector<std::string> grep(std::string_view seq, char delim = '\n', bool invert = false) const {
+    const std::vector<uint64_t> rec = records(seq, delim);
+    std::vector<uint64_t> doo;
+    const std::string out = grep_batch(seq, rec, invert, nullptr, &doo);
+    std::vector<std::string> lines;
+    for (size_t i = 0; i + 1 < doo.size(); i++) lines.push_back(out.substr(doo[i], doo[i + 1] - doo[i]));
+    return lines;
+  }
+
   // Which bytes of the batch lie inside a hit of match_batch, without the hit list (aha_ac_cover_batch): bit j of the batch is
   // word j >> 5, bit j & 31 of what is returned; doc_covered (optional): covered bytes per document.
   std::vector<uint32_t> cover_batch(std::string_view corpus, const std::vector<uint64_t> &doc_offsets,

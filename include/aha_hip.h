@@ -683,6 +683,82 @@ int32_t aha_ac_replace_batch_device(aha_ac *ac, const aha_repl *table, const uin
                                     uint64_t *n_out_bytes, uint64_t *n_selected /* or NULL */, uint64_t *n_hits /* or NULL */,
                                     void *stream);
 
+/* ---- records and grep: split a batch into records, keep those with a hit (pure additions to ABI 8) -----------------------
+ * RECORDS.  The same batch as aha_ac_match_batch / _device and a delimiter byte.  E = {doc_offsets[d] : 1 <= d <= D} united
+ * with {p + 1 : corpus[p] == delim}, without 0.  rec_offsets[0 .. R] = 0 followed by the elements of E, ascending, without
+ * repeats; *n_records = R.  So every record is non-empty; it ends behind a delimiter (the delimiter belongs to its record)
+ * or at a document's end; a document boundary behind a delimiter is counted once; empty documents have no record.
+ * doc_rec_offsets[d] (optional, D + 1 entries) = the elements of E that are <= doc_offsets[d]: document d's records are
+ * rec_offsets[doc_rec_offsets[d] .. doc_rec_offsets[d+1]].  rec_offsets is a valid doc_offsets for every batch call of this
+ * header: it starts at 0, ascends and ends at N -- records are documents from then on (select per line, grep below).
+ * cap_records is in records: the buffer holds cap_records + 1 entries.  AHA_E_CAPACITY: *n_records is the required count and
+ * NONE of the caller's buffers is written (rec_offsets == NULL with cap_records == 0 is a sizing call).  N = 0: R = 0,
+ * rec_offsets[0] = 0 is written where a buffer is given, doc_rec_offsets is all zero.  A record of 2 GiB or more is not this
+ * call's business: the match that follows answers AHA_E_TOO_LONG.
+ * A NULL handle / doc_offsets / n_records, rec_offsets == NULL with cap_records != 0, any flag bit (flags is 0):
+ * AHA_E_INVALID; a host-only handle: AHA_E_NO_DEVICE; all before any device work.  Bad offsets as in the match (the device
+ * entry finds them on the device).  The handle's key set plays no part: the call uses its device, scratch and stream.
+ * d_corpus may have any alignment; no load touches a byte outside [corpus, corpus + N).
+ * Pipeline (aha_amd/csrc/scan_grep.hip): one pass over the text with aligned 16-byte loads writes a record-end
+ * mask, one bit per byte; one lane per document ORs the documents' ends in; the mask is ranked as select's (set bits per 64
+ * words, their scan, the rank of every document's first byte); the total comes to the host; once it fits, every set bit p
+ * writes rec_offsets[rank + 1] = p + 1.  Device scratch: N / 8 bytes of mask + 8 bytes per 2048 text bytes.
+ *
+ * GREP.  The same batch, params, validation and errors as aha_ac_count_batch / _device.  h_d = the hits aha_ac_match_batch
+ * reports for document d with the same params on the same handle (a separator filter -- whole-word grep -- and
+ * AHA_OPT_FOLD_ASCII included).  Document d is KEPT when (h_d >= 1) != invert (flags & AHA_GREP_INVERT).
+ * kept_docs[0 .. n_kept) (optional) = the kept documents' indices, ascending; doc_out_offsets[0 .. n_kept] (optional) = where
+ * each lies in out; out (optional) = the kept documents' bytes one behind the other -- the caller's own bytes, on a folded
+ * handle the original spelling (the rule of redact and replace); *n_kept, *n_out_bytes (optional), *n_hits (optional; all
+ * hits of the batch).  Kept empty documents appear in kept_docs with equal neighbouring offsets (under AHA_GREP_INVERT).
+ * cap_docs bounds both per-document buffers (doc_out_offsets holds cap_docs + 1), cap_bytes bounds out.  AHA_E_CAPACITY
+ * when n_kept > cap_docs and either per-document buffer was given, or when n_out_bytes > cap_bytes and out was given: BOTH
+ * required numbers are reported and NONE of the caller's buffers is written.  Every failing call leaves them untouched.
+ * All three buffers NULL with capacities 0 is a sizing call that succeeds; out == NULL with cap_bytes == 0 never launches
+ * the copy (the "which documents" and "how many" forms).  Two calls give identical bytes.
+ * params->char_offsets != 0, params->longest != 0, an unknown flag, n_kept == NULL, a NULL handle, a NULL buffer with a
+ * non-zero capacity, out overlapping the corpus (there is no in-place form): AHA_E_INVALID; a host-only handle:
+ * AHA_E_NO_DEVICE; all before any device work.  N = 0, D = 0 and empty documents are valid.  The handle's back-off state is
+ * read and never written, as in the count call.
+ * Example: keys "ab", "b\n" over the one document "xab\nq\n\nb" with delimiter '\n'.  Records gives rec_offsets
+ * 0, 4, 6, 7, 8: the records "xab\n", "q\n", "\n", "b".  Grep over rec_offsets keeps record 0 only: kept_docs = {0},
+ * doc_out_offsets = {0, 4}, out = "xab\n".  The key "b\n" anchors at a record's end: it hits in "xab\n" and does not hit in the
+ * last record, which has no delimiter.  With AHA_GREP_INVERT: kept_docs = {1, 2, 3}, out = "q\n\nb".
+ * Pipeline (scan_grep.hip): the count call without key counts (hit offsets per document into scratch); one lane
+ * per document writes three masks over documents -- keep, S (a dropped document whose predecessor is kept or which is the
+ * first) and T (a dropped document whose successor is kept or which is the last); the three are ranked as above; the j-th bit
+ * of S and the j-th bit of T delimit the j-th maximal run of dropped documents, so A[j] = doc_offsets[a_j] and delta[j] =
+ * -(doc_offsets[b_j + 1] - A[j]) without a walk along the run; replace's scan gives shift, n_out_bytes = N + shift[n_runs];
+ * both totals come to the host; once they fit, kept document d of rank r writes kept_docs[r] = d and doc_out_offsets[r] =
+ * doc_offsets[d] + shift[runs in front of d], and replace's copy (above) runs over the dropped runs as deleted hits.
+ * Device scratch beside the count call's: 8 bytes per document of hit offsets, 3 bits per document of masks and their block
+ * ranks, 28 bytes per dropped run and the scan's block sums.  AHA_GREP_BLOCKS (read when the handle is compiled) caps the grids
+ * of these calls' kernels, the reused rank, scan and copy launches included.
+ * aha_ac_last_timing (grep): engine = the engine that traversed, n_hits = all hits, ms_write = everything after the count.
+ * The host entries stage the batch on the device; a host sizing call followed by the real call runs the device work twice.
+ * Out of scope so far: char offsets, match_longest, feeds, groups, multi-byte delimiters, a minimum hit count, an in-place
+ * form. */
+#define AHA_GREP_INVERT 1u /* keep the documents WITHOUT a hit */
+int32_t aha_ac_records_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc_offsets, uint64_t n_docs, uint8_t delim,
+                             uint32_t flags /* 0 */, uint64_t *rec_offsets /* cap_records + 1 */, uint64_t cap_records,
+                             uint64_t *doc_rec_offsets /* D+1 or NULL */, uint64_t *n_records);
+/* Device-resident form: d_ pointers are HBM on the handle's device; *n_records is host memory; blocks until final. */
+int32_t aha_ac_records_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                                    uint64_t n_bytes, uint8_t delim, uint32_t flags /* 0 */,
+                                    uint64_t *d_rec_offsets /* cap_records + 1 */, uint64_t cap_records,
+                                    uint64_t *d_doc_rec_offsets /* D+1 or NULL */, uint64_t *n_records, void *stream);
+int32_t aha_ac_grep_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc_offsets, uint64_t n_docs,
+                          const aha_match_params *params, uint32_t flags /* AHA_GREP_INVERT */, uint64_t *kept_docs /* or NULL */,
+                          uint64_t *doc_out_offsets /* cap_docs + 1 or NULL */, uint64_t cap_docs, uint8_t *out /* or NULL */,
+                          uint64_t cap_bytes, uint64_t *n_kept, uint64_t *n_out_bytes /* or NULL */, uint64_t *n_hits /* or NULL */);
+/* Device-resident form: d_ pointers are HBM on the handle's device; *n_kept, *n_out_bytes, *n_hits are host memory; blocks
+ * until final. */
+int32_t aha_ac_grep_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                                 uint64_t n_bytes, const aha_match_params *params, uint32_t flags /* AHA_GREP_INVERT */,
+                                 uint64_t *d_kept_docs /* or NULL */, uint64_t *d_doc_out_offsets /* cap_docs + 1 or NULL */,
+                                 uint64_t cap_docs, uint8_t *d_out /* or NULL */, uint64_t cap_bytes, uint64_t *n_kept,
+                                 uint64_t *n_out_bytes /* or NULL */, uint64_t *n_hits /* or NULL */, void *stream);
+
 /* Feed cover: the same pieces as aha_feed_match_batch*, and the cover of what a match call of them on a BYTE feed in the same
  * state would report (H_d: the hits of piece d, offsets relative to the piece, start possibly negative), without the hit list.
  * mask: the layout of aha_ac_cover_batch over the batch of pieces; bit j = 1 iff byte j lies in [max(start, 0), end) of a hit
