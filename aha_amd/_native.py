@@ -35,6 +35,7 @@ AHA_GREP_INVERT = 1
 AHA_FEED_CHARS = 1
 AHA_FEED_SELECT_FINAL = 1
 AHA_FEED_REPLACE_FINAL = AHA_FEED_SELECT_FINAL
+AHA_FEED_GREP_FINAL = 2
 AHA_IMG_SLOTS, AHA_IMG_END_KEY, AHA_IMG_KEY_LN, AHA_IMG_KEY_CNT, AHA_IMG_KEY_KC = 0, 1, 2, 3, 4
 AHA_IMG_STALE_ENDS = 5
 AHA_IMG_UNIT_SLOTS, AHA_IMG_UNIT_ROOT, AHA_IMG_UNIT_END_KEY, AHA_IMG_UNIT_TABLES = 6, 7, 8, 9
@@ -196,6 +197,11 @@ SIGNATURES = {
                                     C.POINTER(_u64), C.POINTER(_u64)]),
     "aha_feed_replace_batch_device": (_i32, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _u32, _vp, _u64, _vp, _vp, _vp, C.POINTER(_u64),
                                            C.POINTER(_u64), C.POINTER(_u64), _vp]),
+    "aha_feed_grep_batch": (_i32, [_vp, _vp, _vp, _vp, _u64, C.c_uint8, _u32, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp,
+                                 _vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "aha_feed_grep_batch_device": (_i32, [_vp, _vp, _vp, _vp, _u64, _u64, C.c_uint8, _u32, _vp, _vp, _u64, _vp, _u64, _vp, _vp,
+                                        _vp, _vp, _vp, _vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64),
+                                        C.POINTER(_u64), _vp]),
 }
 
 _lib = None

@@ -1242,7 +1242,8 @@ class Feed:
     piece_bases[d] is the sequence's length before it, so base + offset is absolute.  A feed opened with sep (AC.feed(..,
     sep=BitArray)) filters match and count calls as match(seq, sep) of the whole sequence does: a call reports the surviving
     hits that end before the piece's last byte -- one that ended with the piece before has end == 0 -- and finish_batch /
-    finish report those that end with the sequence and start it again; cover, select and replace calls are refused there."""
+    finish report those that end with the sequence and start it again; cover, select, replace and grep calls are refused
+    there.  A grep call (grep_batch, grepper) gives the lines that close in the call and have a hit."""
 
     def __init__(self, ac, handle, n_seqs, chars, sep=None):
         self._ac, self._h, self.n_seqs, self.chars, self.sep = ac, handle, n_seqs, chars, sep
@@ -1711,6 +1712,108 @@ class Feed:
         """A Replacer over this feed: push(seq, piece) / finish(seq) give the substituted stream of every sequence."""
         return Replacer(self, repl)
 
+    # -- feed grep: the lines of sequences in pieces that have a hit (aha_feed_grep_batch*) ------------------------------------
+    def grep_batch(self, corpus, piece_offsets, seq_ids, delim=b"\n", invert=False, final=False, text=True):
+        """The fragments of this call's pieces that close in it and are kept (aha_feed_grep_batch).  The pieces are split
+        as AC.records(corpus, piece_offsets, delim) splits them; a fragment closes when it ends with the delimiter, or under
+        final=True; it is kept when (its record, matched as its own document, has a hit) != invert -- a piece's first
+        fragment may continue a record that earlier pieces left open.  -> (kept_recs uint64[n_kept], uint8 array,
+        rec_out_offsets uint64[n_kept+1], info) with info = {"piece_rec_offsets", "piece_kept_offsets" uint64[D+1],
+        "piece_hold" uint32[D]: the bytes at the end of the piece that belong to the record left open -- the caller keeps them,
+        "piece_head" uint64[D]: the held bytes to emit in front of the piece's first kept fragment, "piece_bases",
+        "piece_rec_bases" uint64[D], "n_recs", "n_hits"}.  With final=True the named sequences start again from length 0.
+        Byte feeds only, one delimiter per feed, and only for sequences fed through grep calls alone since their last reset.
+        text False: no bytes are copied.  A sizing call first (a call that does not fit changes nothing)."""
+        if isinstance(corpus, (bytes, bytearray)):
+            corpus = np.frombuffer(bytes(corpus), dtype=np.uint8)
+        corpus = np.ascontiguousarray(corpus, dtype=np.uint8)
+        piece_offsets = np.ascontiguousarray(piece_offsets, dtype=np.uint64)
+        seq_ids = np.ascontiguousarray(seq_ids, dtype=np.uint32)
+        D = piece_offsets.size - 1
+        if seq_ids.size != D:
+            raise ValueError("one sequence id per piece")
+        d = _delim_byte(delim)
+        flags = (N.AHA_GREP_INVERT if invert else 0) | (N.AHA_FEED_GREP_FINAL if final else 0)
+        pro, pko = np.zeros(D + 1, dtype=np.uint64), np.zeros(D + 1, dtype=np.uint64)
+        hold = np.zeros(max(D, 1), dtype=np.uint32)
+        head, bases, rbases = (np.zeros(max(D, 1), dtype=np.uint64) for _ in range(3))
+        nr, nk, nb, nh = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        L = N.lib()
+
+        def call(kept, roo, cap_recs, out, cap_bytes):
+            return L.aha_feed_grep_batch(self._h, _ptr(corpus), _ptr(piece_offsets), _ptr(seq_ids), D, d, flags, _ptr(kept),
+                                         _ptr(roo), cap_recs, _ptr(out) if text else None, cap_bytes, _ptr(pro), _ptr(pko),
+                                         _ptr(hold), _ptr(head), _ptr(bases), _ptr(rbases), C.byref(nr), C.byref(nk),
+                                         C.byref(nb), C.byref(nh))
+
+        # (a buffer with no room: the call succeeds only where nothing is kept)
+        kept, roo, out = np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.uint8)
+        rc = call(kept, roo, 0, out, 0)
+        if rc == N.AHA_E_CAPACITY:
+            cap_recs, cap_bytes = int(nk.value), int(nb.value) if text else 0
+            kept, roo = np.zeros(max(cap_recs, 1), dtype=np.uint64), np.zeros(cap_recs + 1, dtype=np.uint64)
+            out = np.zeros(max(cap_bytes, 1), dtype=np.uint8)
+            rc = call(kept, roo, cap_recs, out, cap_bytes)
+        self._check(rc)
+        n = int(nk.value)
+        info = {"piece_rec_offsets": pro, "piece_kept_offsets": pko, "piece_hold": hold[:D], "piece_head": head[:D],
+                "piece_bases": bases[:D], "piece_rec_bases": rbases[:D], "n_recs": int(nr.value), "n_hits": int(nh.value)}
+        return kept[:n], out[: int(nb.value) if text else 0], roo[: n + 1], info
+
+    def grep_batch_device(self, corpus, piece_offsets, seq_ids, kept_recs=None, rec_out_offsets=None, out=None, delim=b"\n",
+                          invert=False, final=False, piece_rec_offsets=None, piece_kept_offsets=None, piece_hold=None,
+                          piece_head=None, piece_bases=None, piece_rec_bases=None, cap_recs=None, cap_bytes=None, stream=None):
+        """Device-resident form on torch CUDA tensors: uint8 corpus (any alignment), int64/uint64 piece offsets, int32/uint32
+        sequence ids, kept_recs int64/uint64 [cap_recs] or None, rec_out_offsets int64/uint64 [cap_recs + 1] or None, out
+        uint8 [cap_bytes] or None (no bytes are copied), the per-piece outputs int64/uint64 [D+1] / [D] (piece_hold
+        int32/uint32 [D]) or None.  -> (n_recs, n_kept, n_out_bytes, n_hits); raises AhaError(AHA_E_CAPACITY) when a buffer is
+        too small (e.n_required = the fragments needed, e.bytes_required = the bytes needed); nothing is written then and the
+        feed is unchanged."""
+        import torch
+
+        assert corpus.is_cuda and corpus.dtype == torch.uint8 and corpus.is_contiguous()
+        assert piece_offsets.is_cuda and piece_offsets.dtype in (torch.int64, torch.uint64) and piece_offsets.is_contiguous()
+        assert seq_ids.is_cuda and seq_ids.dtype in (torch.int32, torch.uint32) and seq_ids.is_contiguous()
+        D = piece_offsets.numel() - 1
+        assert seq_ids.numel() >= D
+        for name, t in (("kept_recs", kept_recs), ("rec_out_offsets", rec_out_offsets)):
+            if t is not None and not (t.is_cuda and t.dtype in (torch.int64, torch.uint64) and t.is_contiguous()):
+                raise ValueError(name + " must be a contiguous int64/uint64 CUDA tensor")
+        room = []
+        if kept_recs is not None:
+            room.append(kept_recs.numel())
+        if rec_out_offsets is not None:
+            if rec_out_offsets.numel() < 1:
+                raise ValueError("rec_out_offsets must have at least one entry")
+            room.append(rec_out_offsets.numel() - 1)
+        cap_recs = 0 if not room else min(room) if cap_recs is None else min([int(cap_recs)] + room)
+        if out is not None:
+            if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.dim() == 1):
+                raise ValueError("out must be a contiguous one-dimensional uint8 CUDA tensor")
+            cap_bytes = out.numel() if cap_bytes is None else min(int(cap_bytes), out.numel())
+        else:
+            cap_bytes = 0
+        for t, k in ((piece_rec_offsets, D + 1), (piece_kept_offsets, D + 1), (piece_head, D), (piece_bases, D), (piece_rec_bases, D)):
+            assert t is None or (t.is_cuda and t.dtype in (torch.int64, torch.uint64) and t.is_contiguous() and t.numel() >= k)
+        assert piece_hold is None or (piece_hold.is_cuda and piece_hold.dtype in (torch.int32, torch.uint32)
+                                      and piece_hold.is_contiguous() and piece_hold.numel() >= D)
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        nr, nk, nb, nh = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        s = stream if stream is not None else torch.cuda.current_stream(corpus.device).cuda_stream
+        rc = N.lib().aha_feed_grep_batch_device(
+            self._h, corpus.data_ptr(), piece_offsets.data_ptr(), seq_ids.data_ptr(), D, corpus.numel(), _delim_byte(delim),
+            (N.AHA_GREP_INVERT if invert else 0) | (N.AHA_FEED_GREP_FINAL if final else 0), ptr(kept_recs), ptr(rec_out_offsets),
+            cap_recs, ptr(out), cap_bytes, ptr(piece_rec_offsets), ptr(piece_kept_offsets), ptr(piece_hold), ptr(piece_head),
+            ptr(piece_bases), ptr(piece_rec_bases), C.byref(nr), C.byref(nk), C.byref(nb), C.byref(nh), C.c_void_p(s))
+        if rc == N.AHA_E_CAPACITY:
+            raise AC._grep_capacity_error(rc, nk, nb)
+        self._check(rc)
+        return int(nr.value), int(nk.value), int(nb.value), int(nh.value)
+
+    def grepper(self, delim=b"\n", invert=False):
+        """A Grepper over this feed: push(seq, piece) / finish(seq) give the kept lines of every sequence."""
+        return Grepper(self, delim, invert)
+
     def match(self, seq, piece):
         """The next piece of one sequence: its hits as Hits with absolute offsets."""
         b = _b(piece)
@@ -1785,6 +1888,51 @@ class Replacer:
 
     def finish(self, seq):
         """The bytes still open for seq, substituted; the sequence starts again from length 0."""
+        return self._step(seq, b"", True)
+
+
+class Grepper:
+    """Grep over sequences that arrive in pieces whose ends fall in the middle of lines (Feed.grepper), host arithmetic on
+    Feed.grep_batch.  push(seq, piece) returns the kept lines that closed with this piece -- each with its delimiter, as
+    bytes --, finish(seq) the trailing line without one if it is kept, and pushes + finish(seq), concatenated, are
+    matcher.grep(whole sequence, delim, invert) as bytes.  The bytes of the line that is still open are held on the host
+    (piece_hold): a line has no length limit, the feed's state per sequence has."""
+
+    def __init__(self, feed, delim=b"\n", invert=False):
+        self._feed, self._delim, self._invert = feed, _delim_byte(delim), bool(invert)
+        self._held = {}  # seq -> the bytes of the open line
+
+    def _step(self, seq, piece, final):
+        b = _b(piece)
+        _, out, roo, info = self._feed.grep_batch(np.frombuffer(b, dtype=np.uint8), np.array([0, len(b)], dtype=np.uint64),
+                                                  np.array([seq], dtype=np.uint32), delim=self._delim, invert=self._invert,
+                                                  final=final)
+        raw = out.tobytes()
+        lines = [raw[int(roo[i]):int(roo[i + 1])] for i in range(roo.size - 1)]
+        held = self._held.get(seq, b"")
+        head, hold = int(info["piece_head"][0]), int(info["piece_hold"][0])
+        if head:  # the open line closed and is kept: it stands in front of the piece's first kept fragment
+            if lines:
+                lines[0] = held[len(held) - head:] + lines[0]
+            else:  # (an empty piece under final: the line closes without a fragment)
+                lines = [held[len(held) - head:]]
+        if final:
+            held = b""
+        elif hold == len(b):
+            held = held + b
+        else:
+            held = b[len(b) - hold:]
+        if held:
+            self._held[seq] = held
+        else:
+            self._held.pop(seq, None)
+        return lines
+
+    def push(self, seq, piece):
+        return self._step(seq, piece, False)
+
+    def finish(self, seq):
+        """The open line of seq if it is kept; the sequence starts again from length 0."""
         return self._step(seq, b"", True)
 
 

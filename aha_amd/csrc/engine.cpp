@@ -1736,7 +1736,50 @@ int32_t device_replace(aha_ac *ac, Scratch *sc, const aha_repl *table, const uin
 
 // ---- records and grep calls (aha_ac_records_batch*, aha_ac_grep_batch*) ------------------------------------------------
 static void *grp_reserve(Scratch *sc, GrepSlot slot, size_t bytes) { return reserve_ptr(sc->grpbuf[slot], bytes, kGrowEighth); }
-static uint32_t grep_grid(const aha_ac *ac) { return ac->grep_blocks ? ac->grep_blocks : 8u * std::max<uint32_t>(ac->v2_grid, 64u); }
+uint32_t grep_grid(const aha_ac *ac) { return ac->grep_blocks ? ac->grep_blocks : 8u * std::max<uint32_t>(ac->v2_grid, 64u); }
+
+// The first half of a records call: the record-end mask and its rank into grpbuf, the total read back.
+int32_t device_records_settle(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                              uint64_t n_bytes, uint8_t delim, uint64_t *n_records, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  *n_records = 0;
+  if (!n_bytes) return AHA_OK;
+  const uint32_t blocks = grep_grid(ac);
+  const uint64_t n_words = (n_bytes + 31) / 32, n_blk = select_rank_blocks(n_bytes);
+  uint32_t *mask = (uint32_t *)grp_reserve(sc, kGrpEnds, n_words * 4);
+  uint64_t *blk = (uint64_t *)grp_reserve(sc, kGrpEndBlocks, (n_blk + 1) * 8);
+  if (!mask || !blk) {
+    tls_err = "hipMalloc failed for the scratch of a records call";
+    return AHA_E_HIP;
+  }
+  uint64_t total = 0;
+  grep_launch_ends(d_corpus, n_bytes, delim, d_doc_offsets, n_docs, mask, blocks, s);
+  select_launch_rank(mask, n_bytes, blk, blocks, s);
+  HIPCHK(ac, hipGetLastError());
+  HIPCHK(ac, hipMemcpyAsync(&total, blk + n_blk, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  *n_records = total;
+  return AHA_OK;
+}
+
+// The second half, once the total is known to fit: every set bit as a record's end, the documents' offsets into the records.
+int32_t device_records_emit(aha_ac *ac, Scratch *sc, const uint64_t *d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
+                            uint64_t *d_rec_offsets, uint64_t *d_doc_rec_offsets, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (n_bytes) {
+    const uint32_t blocks = grep_grid(ac);
+    const uint32_t *mask = (const uint32_t *)sc->grpbuf[kGrpEnds].p;
+    const uint64_t *blk = (const uint64_t *)sc->grpbuf[kGrpEndBlocks].p;
+    if (d_rec_offsets) grep_launch_emit_ends(mask, n_bytes, blk, d_rec_offsets, blocks, s);
+    if (d_doc_rec_offsets) select_launch_rank_docs(mask, blk, d_doc_offsets, n_docs + 1, 0, d_doc_rec_offsets, blocks, s);
+    HIPCHK(ac, hipGetLastError());
+  } else {
+    if (d_rec_offsets) HIPCHK(ac, hipMemsetAsync(d_rec_offsets, 0, 8, s));
+    if (d_doc_rec_offsets) HIPCHK(ac, hipMemsetAsync(d_doc_rec_offsets, 0, (n_docs + 1) * 8, s));
+  }
+  HIPCHK(ac, hipStreamSynchronize(s));
+  return AHA_OK;
+}
 
 // One device-resident batch split into records (aha_ac_records_batch_device).  The handle's keys play no part: its device,
 // scratch and stream do.
@@ -1757,39 +1800,14 @@ int32_t device_records(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const u
   int32_t rc;
   if (!offsets_checked && (rc = check_docs_now(ac, sc, d_doc_offsets, n_docs, n_bytes, s))) return rc;
   if (n_bytes && !d_corpus) return AHA_E_INVALID;
-  const uint32_t blocks = grep_grid(ac);
-  const uint64_t n_words = (n_bytes + 31) / 32, n_blk = select_rank_blocks(n_bytes);
-  uint32_t *mask = nullptr;
-  uint64_t *blk = nullptr;
   uint64_t total = 0;
-  if (n_bytes) {
-    mask = (uint32_t *)grp_reserve(sc, kGrpEnds, n_words * 4);
-    blk = (uint64_t *)grp_reserve(sc, kGrpEndBlocks, (n_blk + 1) * 8);
-    if (!mask || !blk) {
-      tls_err = "hipMalloc failed for the scratch of a records call";
-      return AHA_E_HIP;
-    }
-    grep_launch_ends(d_corpus, n_bytes, delim, d_doc_offsets, n_docs, mask, blocks, s);
-    select_launch_rank(mask, n_bytes, blk, blocks, s);
-    HIPCHK(ac, hipGetLastError());
-    HIPCHK(ac, hipMemcpyAsync(&total, blk + n_blk, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(ac, hipStreamSynchronize(s));
-  }
+  if ((rc = device_records_settle(ac, sc, d_corpus, d_doc_offsets, n_docs, n_bytes, delim, &total, stream))) return rc;
   *n_records = total;
   if (total > cap_records) {
     tls_err = "output buffer too small";
     return AHA_E_CAPACITY;
   }
-  if (n_bytes) {
-    if (d_rec_offsets) grep_launch_emit_ends(mask, n_bytes, blk, d_rec_offsets, blocks, s);
-    if (d_doc_rec_offsets) select_launch_rank_docs(mask, blk, d_doc_offsets, n_docs + 1, 0, d_doc_rec_offsets, blocks, s);
-    HIPCHK(ac, hipGetLastError());
-  } else {
-    if (d_rec_offsets) HIPCHK(ac, hipMemsetAsync(d_rec_offsets, 0, 8, s));
-    if (d_doc_rec_offsets) HIPCHK(ac, hipMemsetAsync(d_doc_rec_offsets, 0, (n_docs + 1) * 8, s));
-  }
-  HIPCHK(ac, hipStreamSynchronize(s));
-  return AHA_OK;
+  return device_records_emit(ac, sc, d_doc_offsets, n_docs, n_bytes, d_rec_offsets, d_doc_rec_offsets, stream);
 }
 
 // One device-resident batch filtered (aha_ac_grep_batch_device).

@@ -39,6 +39,17 @@
 //   kfp_compact | kfp_count           the kept hits, or their values per key; the offsets from the same ranks; kfd_commit
 // and aha_feed_finish_batch* matches the named sequences' contexts as the window batch of a call of empty pieces, keeps the hits
 // that end on the last byte and pass on the left, and sets those sequences back to length 0 (kfp_restart).
+// A grep call (aha_feed_grep_batch*; DESIGN.md 4.10 "Feed grep") lays out windows of its own, per record and not per sequence:
+//   kfd_check              offsets, ids, duplicates, and that the named sequences went through grep calls alone (one read-back)
+//   device_records         the pieces split into fragments, in two halves: the total sizes the fragments' offsets (one read-back)
+//   kfg_layout, kfg_windows   the window batch [X_d | Y_d | Z_d] of the pieces whose first fragment continues an open record
+//                          (one read-back: its size)
+//   device_count x 2       the window batch, then the fragments as documents from the root (a plain grep's engine and count path)
+//   kfg_has, kfg_first, kfg_flag   keep, S and T over the fragments; an open tail counts as dropped
+//   scan_grep.hip, scan_replace.hip   grep's steps over these masks, unchanged (two read-backs: the kept fragments and the runs,
+//                          then the byte total) -- above either capacity -> AHA_E_CAPACITY, nothing committed
+//   kgr_emit_docs, krp_copy, kfd_commit + kfg_commit   the kept fragments, their bytes, the offsets; then the feed's state and,
+//                          behind it, the grep state
 // Calls on one feed are serialised by its mutex; its scratch is its own.  The two matches lease one of the handle's scratch
 // sets like any call, so different feeds and plain calls on the same handle run side by side.
 #include "feed.hpp"
@@ -60,18 +71,23 @@ struct aha_feed {
   // select and replace calls: allocated by the feed's first one (8 W + 16 bytes per sequence)
   FeedSelSeq *d_sel = nullptr;
   unsigned long long *d_tail = nullptr;
+  // grep calls: allocated by the feed's first one (32 bytes per sequence); the delimiter its first successful one fixed
+  FeedGrepSeq *d_grep = nullptr;
+  int grep_delim = -1;
   uint32_t stamp = 0;
   // grow-only scratch: 0 verdict + window size, 1 window bytes, 2 window offsets, 3 window hit offsets, 4 window hits,
   // 5 main hit offsets, 6 main hits, 7 piece hit offsets, 8 leads(ctx), 9 leads(P); 10 .. 15 the host entry's staging
   // (corpus, offsets, ids, hits, piece hit offsets, bases), 16 key counts (a count call's sums), 17 the host entry's key counts,
-  // 18 a cover call's mask, 19 / 20 the host entry's piece_back and piece_covered, 21 the host entry's piece_hold
-  Buf buf[22];
+  // 18 a cover call's mask, 19 / 20 the host entry's piece_back and piece_covered, 21 the host entry's piece_hold,
+  // 22 .. 27 the host entry's kept_recs, rec_out_offsets, piece_rec_offsets, piece_kept_offsets, piece_head, piece_rec_bases
+  Buf buf[28];
   uint64_t *h_pin = nullptr;  // pinned: read-backs
   hipStream_t hs = nullptr;   // the host entry's stream (and position / reset)
 };
 
 namespace {
-enum { kMisc, kWin, kWoff, kWdho, kWhits, kMdho, kMhits, kPho, kLeadCtx, kLeadP, kHCorpus, kHOff, kHIds, kHOut, kHPho, kHBases, kKc, kHKc, kMask, kHBack, kHCov, kHHold };
+enum { kMisc, kWin, kWoff, kWdho, kWhits, kMdho, kMhits, kPho, kLeadCtx, kLeadP, kHCorpus, kHOff, kHIds, kHOut, kHPho, kHBases, kKc, kHKc, kMask, kHBack, kHCov, kHHold, kHKept, kHRecOut,
+       kHPieceRec, kHPieceKept, kHHead, kHRecBases };
 
 void *reserve(aha_feed *f, int i, size_t bytes) {
   Buf &b = f->buf[i];
@@ -490,6 +506,185 @@ int32_t feed_replace(aha_feed *f, Scratch *sc, const aha_repl *table, FeedArgs &
   return AHA_OK;
 }
 
+// the caller's buffers of a grep call, on the device.  The host entry gives slots of the feed's staging buffers for the three
+// whose size only the call knows (>= 0: wanted; they are reserved once the totals are known)
+struct GrepOut {
+  uint64_t *kept = nullptr, *rec_out = nullptr;
+  uint8_t *out = nullptr;
+  int kept_slot = -1, rec_out_slot = -1, out_slot = -1;
+  uint64_t cap_recs = 0, cap_bytes = 0;
+  uint64_t *piece_rec = nullptr, *piece_kept = nullptr, *head = nullptr, *rec_bases = nullptr;
+  uint32_t *hold = nullptr;
+};
+
+// a whole grep call on device-resident pieces.  Everything up to the second total's read-back writes scratch only; the caller's
+// buffers and the feed's state are written once both totals are known to fit.
+int32_t feed_grep(aha_feed *f, Scratch *sc, FeedArgs &F, uint8_t delim, uint32_t flags, GrepOut &O, hipStream_t s, uint64_t *n_recs,
+                  uint64_t *n_kept, uint64_t *n_out_bytes, uint64_t *n_hits) {
+  aha_ac *ac = f->ac;
+  const uint64_t D = F.D;
+  if (f->grep_delim >= 0 && f->grep_delim != (int)delim) {
+    tls_err = "feed grep: the delimiter is fixed by the feed's first grep call";
+    return AHA_E_INVALID;
+  }
+  if (!f->d_grep) {  // the feed's first grep call: no sequence has grep state yet
+    const size_t bytes = (size_t)f->n_seqs * sizeof(FeedGrepSeq);
+    void *a = nullptr;
+    if (hipMalloc(&a, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      return no_memory("grep state");
+    }
+    hipError_t e = hipMemsetAsync(a, 0, bytes, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+      (void)hipFree(a);
+      HIPCHK(ac, e);
+    }
+    f->d_grep = (FeedGrepSeq *)a;
+  }
+  if (++f->stamp == 0) f->stamp = 1;
+  F.stamp = f->stamp;
+  F.seqs = f->d_seqs;
+  F.ctx = f->d_ctx;
+  F.n_seqs = f->n_seqs;
+  F.W = F.Wp = f->W;
+  F.chars = 0;
+  F.max_piece = (1ull << 31) - std::max<uint64_t>(ac->aut.max_key_len, 1);
+  F.grep = f->d_grep;
+  uint64_t *misc = (uint64_t *)reserve(f, kMisc, 24);
+  if (!misc) return no_memory("offsets");
+  F.verdict = (uint32_t *)misc;
+  F.win_total = misc + 1;
+  HIPCHK(ac, hipMemsetAsync(F.verdict, 0, 4, s));
+  feed_launch_check_only(F, s);
+  HIPCHK(ac, hipGetLastError());
+  HIPCHK(ac, hipMemcpyAsync(f->h_pin, misc, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  const uint32_t bad = (uint32_t)f->h_pin[0];
+  if (bad & 1u) {
+    tls_err = "feed: need piece_offsets[0] = 0, ascending, piece_offsets[n_pieces] = n_bytes, seq_ids below n_seqs and each once";
+    return AHA_E_INVALID;
+  }
+  if (bad & 8u) {
+    tls_err = "feed grep: bytes of a named sequence went through another kind of call; grep works again after its reset";
+    return AHA_E_INVALID;
+  }
+  if (bad & 2u) {
+    tls_err = "feed: a piece must be shorter than 2^31 bytes minus the longest key";
+    return AHA_E_TOO_LONG;
+  }
+  auto fg_reserve = [sc](FeedGrepSlot slot, size_t bytes) { return reserve_ptr(sc->fgrpbuf[slot], bytes, kGrowEighth); };
+  auto nomem = [&]() {
+    tls_err = "hipMalloc failed for the scratch of a feed grep call";
+    return AHA_E_HIP;
+  };
+  // the fragments: a records call over the pieces, its offsets sized from its total
+  int32_t rc;
+  uint64_t R = 0;
+  if ((rc = device_records_settle(ac, sc, F.text, F.off, D, F.n_bytes, delim, &R, s))) return rc;
+  uint64_t *frag = (uint64_t *)fg_reserve(kFgFragOff, (R + 1) * 8);
+  uint64_t *pro = (uint64_t *)fg_reserve(kFgPieceFrag, (D + 1) * 8);
+  if (!frag || !pro) return nomem();
+  if ((rc = device_records_emit(ac, sc, F.off, D, F.n_bytes, frag, pro, s))) return rc;
+  F.woff = (uint64_t *)fg_reserve(kFgWinOff, (3 * D + 1) * 8);
+  uint64_t *wdho = (uint64_t *)fg_reserve(kFgWinHitOff, (3 * D + 1) * 8);
+  uint64_t *fdho = (uint64_t *)fg_reserve(kFgFragHitOff, (R + 1) * 8);
+  const uint32_t blocks = grep_grid(ac);
+  const uint64_t n_words = (R + 31) / 32, n_blk = select_rank_blocks(R);
+  uint8_t *flag = (uint8_t *)fg_reserve(kFgFlags, std::max<uint64_t>(R, 1));
+  uint32_t *masks = (uint32_t *)fg_reserve(kFgMasks, std::max<uint64_t>(n_words, 1) * 3 * 4);
+  uint64_t *blks = (uint64_t *)fg_reserve(kFgBlocks, (n_blk + 1) * 3 * 8);
+  RepEntry *ent = (RepEntry *)fg_reserve(kFgTable, sizeof(RepEntry));
+  if (!F.woff || !wdho || !fdho || !flag || !masks || !blks || !ent) return nomem();
+  F.wdho = wdho;
+  FeedGrepArgs G{};
+  G.gseq = f->d_grep;
+  G.delim = delim;
+  G.invert = (flags & AHA_GREP_INVERT) ? 1u : 0u;
+  G.final = (flags & AHA_FEED_GREP_FINAL) ? 1u : 0u;
+  G.R = R;
+  G.frag = frag;
+  G.pro = pro;
+  G.fdho = fdho;
+  G.flag = flag;
+  G.keep = masks;
+  G.S = masks + n_words;
+  G.T = masks + 2 * n_words;
+  // the windows of the pieces whose first fragment continues an open record
+  feedgrep_launch_layout(F, G, s);
+  HIPCHK(ac, hipGetLastError());
+  HIPCHK(ac, hipMemcpyAsync(f->h_pin, F.win_total, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  const uint64_t n_win = f->h_pin[0];
+  F.win = (uint8_t *)fg_reserve(kFgWin, n_win + 64);
+  if (!F.win) return nomem();
+  if (n_win) {
+    feedgrep_launch_windows(F, G, s);
+    HIPCHK(ac, hipGetLastError());
+  }
+  // both counts without key counts: a count call never writes the handle's back-off state.  The fragments' pass last: it is
+  // the engine and count path a plain grep of them takes, and its timing is the call's
+  aha_match_params p{};
+  p.struct_size = sizeof(p);
+  uint64_t n_w = 0, n_m = 0;
+  if ((rc = device_count(ac, sc, F.win, F.woff, 3 * D, n_win, &p, 0, nullptr, wdho, &n_w, s, true))) return rc;
+  if ((rc = device_count(ac, sc, F.text, frag, R, F.n_bytes, &p, 0, nullptr, fdho, &n_m, s, true))) return rc;
+  // grep's steps over the fragments (engine.cpp device_grep)
+  uint64_t *blk_k = blks, *blk_s = blks + (n_blk + 1), *blk_t = blks + 2 * (n_blk + 1);
+  feedgrep_launch_flag(F, G, blocks, s);
+  select_launch_rank(G.keep, R, blk_k, blocks, s);
+  select_launch_rank(G.S, R, blk_s, blocks, s);
+  select_launch_rank(G.T, R, blk_t, blocks, s);
+  HIPCHK(ac, hipGetLastError());
+  HIPCHK(ac, hipMemcpyAsync(f->h_pin, blk_k + n_blk, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipMemcpyAsync(f->h_pin + 1, blk_s + n_blk, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  const uint64_t kept = f->h_pin[0], n_runs = f->h_pin[1];
+  const uint64_t n_sum = replace_scan_blocks(n_runs);
+  aha_hit *sel = (aha_hit *)fg_reserve(kFgSel, std::max<uint64_t>(n_runs, 1) * sizeof(aha_hit));
+  uint64_t *A = (uint64_t *)fg_reserve(kFgStart, std::max<uint64_t>(n_runs, 1) * 8);
+  int64_t *shift = (int64_t *)fg_reserve(kFgShift, (n_runs + 1) * 8);
+  int64_t *sums = (int64_t *)fg_reserve(kFgSums, (n_sum + 1) * 8);
+  if (!sel || !A || !shift || !sums) return nomem();
+  grep_launch_runs(G.S, G.T, R, blk_s, blk_t, frag, n_runs, A, shift, sel, ent, blocks, s);
+  replace_launch_scan(shift, n_runs, sums, blocks, s);
+  HIPCHK(ac, hipGetLastError());
+  HIPCHK(ac, hipMemcpyAsync(f->h_pin, shift + n_runs, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  const uint64_t total = (uint64_t)((int64_t)F.n_bytes + (int64_t)f->h_pin[0]);
+  if (n_recs) *n_recs = R;
+  *n_kept = kept;
+  if (n_out_bytes) *n_out_bytes = total;
+  if (n_hits) *n_hits = n_m;
+  const bool per_rec = O.kept || O.rec_out || O.kept_slot >= 0 || O.rec_out_slot >= 0, want_out = O.out || O.out_slot >= 0;
+  if ((per_rec && kept > O.cap_recs) || (want_out && total > O.cap_bytes)) {
+    tls_err = "output buffer too small";
+    return AHA_E_CAPACITY;
+  }
+  // the part that writes: the caller's buffers, then the feed's own state and, behind it, the grep state
+  if (O.kept_slot >= 0 && !(O.kept = (uint64_t *)reserve(f, O.kept_slot, kept * 8))) return no_memory("result");
+  if (O.rec_out_slot >= 0 && !(O.rec_out = (uint64_t *)reserve(f, O.rec_out_slot, (kept + 1) * 8))) return no_memory("result");
+  if (O.out_slot >= 0 && !(O.out = (uint8_t *)reserve(f, O.out_slot, total))) return no_memory("result");
+  if (per_rec) grep_launch_emit_docs(G.keep, G.S, R, blk_k, blk_s, frag, shift, n_runs, O.kept, O.rec_out, blocks, s);
+  if (want_out) replace_launch_copy(F.text, sel, A, shift, n_runs, ent, 1, (const uint8_t *)ent, O.out, total, blocks, s);
+  if (O.piece_kept) {
+    if (R)
+      select_launch_rank_docs(G.keep, blk_k, pro, D + 1, 0, O.piece_kept, blocks, s);
+    else
+      HIPCHK(ac, hipMemsetAsync(O.piece_kept, 0, (D + 1) * 8, s));
+  }
+  if (O.piece_rec) HIPCHK(ac, hipMemcpyAsync(O.piece_rec, pro, (D + 1) * 8, hipMemcpyDeviceToDevice, s));
+  G.hold = O.hold;
+  G.head = O.head;
+  G.rec_bases = O.rec_bases;
+  feed_launch_commit(F, s);
+  feedgrep_launch_commit(F, G, blocks, s);
+  HIPCHK(ac, hipGetLastError());
+  HIPCHK(ac, hipStreamSynchronize(s));
+  f->grep_delim = delim;
+  return AHA_OK;
+}
+
 // the part that writes: the caller's hits and offsets, then the feed's own state
 int32_t feed_finish(aha_feed *f, FeedArgs &F, hipStream_t s) {
   if (!F.pho) {
@@ -776,6 +971,7 @@ void aha_feed_free(aha_feed *f) {
     if (f->d_ctx) (void)hipFree(f->d_ctx);
     if (f->d_sel) (void)hipFree(f->d_sel);
     if (f->d_tail) (void)hipFree(f->d_tail);
+    if (f->d_grep) (void)hipFree(f->d_grep);
     if (f->h_pin) (void)hipHostFree(f->h_pin);
     if (f->hs) (void)hipStreamDestroy(f->hs);
   }
@@ -798,6 +994,11 @@ int32_t aha_feed_reset(aha_feed *f, uint32_t seq) {
     HIPCHK(ac, hipMemsetAsync(f->d_sel, 0, (size_t)f->n_seqs * sizeof(FeedSelSeq), f->hs));
   else if (f->d_sel)
     HIPCHK(ac, hipMemsetAsync(f->d_sel + seq, 0, sizeof(FeedSelSeq), f->hs));
+  // ... and the grep state: no record is open, none is closed
+  if (f->d_grep && seq == UINT32_MAX)
+    HIPCHK(ac, hipMemsetAsync(f->d_grep, 0, (size_t)f->n_seqs * sizeof(FeedGrepSeq), f->hs));
+  else if (f->d_grep)
+    HIPCHK(ac, hipMemsetAsync(f->d_grep + seq, 0, sizeof(FeedGrepSeq), f->hs));
   HIPCHK(ac, hipStreamSynchronize(f->hs));
   return AHA_OK;
 }
@@ -1314,6 +1515,148 @@ int32_t aha_feed_replace_batch(aha_feed *f, const aha_repl *table, const uint8_t
   if (piece_out_offsets) HIPCHK(ac, hipMemcpyAsync(piece_out_offsets, d_poo, (D + 1) * 8, hipMemcpyDeviceToHost, s));
   if (piece_bases && D) HIPCHK(ac, hipMemcpyAsync(piece_bases, d_bases, D * 8, hipMemcpyDeviceToHost, s));
   if (piece_hold && D) HIPCHK(ac, hipMemcpyAsync(piece_hold, d_hold, D * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  return AHA_OK;
+}
+
+// the argument checks both grep entries share, before any device work
+static int32_t feed_grep_args(const aha_feed *f, const uint64_t *piece_offsets, const uint32_t *seq_ids, uint64_t n_pieces, uint32_t flags,
+                              const uint64_t *kept_recs, const uint64_t *rec_out_offsets, uint64_t cap_recs, const uint8_t *out,
+                              uint64_t cap_bytes, const uint64_t *n_kept) {
+  if (!f || !n_kept || !piece_offsets || (n_pieces && !seq_ids) || (flags & ~(AHA_GREP_INVERT | AHA_FEED_GREP_FINAL)))
+    return AHA_E_INVALID;
+  if ((cap_recs && !kept_recs && !rec_out_offsets) || (cap_bytes && !out)) return AHA_E_INVALID;
+  if (bad_feed(f)) return AHA_E_NO_DEVICE;
+  if (f->chars) {
+    tls_err = "feed grep: a char feed (AHA_FEED_CHARS); grep is in bytes";
+    return AHA_E_INVALID;
+  }
+  if (f->sep) return sep_refused("grep");
+  return AHA_OK;
+}
+
+static int32_t feed_grep_overlap(const uint8_t *corpus, uint64_t n_bytes, const uint8_t *out, uint64_t cap_bytes) {
+  if (cap_bytes && n_bytes && corpus) {
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), c0 = reinterpret_cast<uintptr_t>(corpus);
+    if (o0 < c0 + n_bytes && c0 < o0 + cap_bytes) {
+      tls_err = "feed grep calls have no in-place form: out overlaps the corpus";
+      return AHA_E_INVALID;
+    }
+  }
+  return AHA_OK;
+}
+
+int32_t aha_feed_grep_batch_device(aha_feed *f, const uint8_t *d_corpus, const uint64_t *d_piece_offsets, const uint32_t *d_seq_ids,
+                                   uint64_t n_pieces, uint64_t n_bytes, uint8_t delim, uint32_t flags, uint64_t *d_kept_recs,
+                                   uint64_t *d_rec_out_offsets, uint64_t cap_recs, uint8_t *d_out, uint64_t cap_bytes,
+                                   uint64_t *d_piece_rec_offsets, uint64_t *d_piece_kept_offsets, uint32_t *d_piece_hold,
+                                   uint64_t *d_piece_head, uint64_t *d_piece_bases, uint64_t *d_piece_rec_bases, uint64_t *n_recs,
+                                   uint64_t *n_kept, uint64_t *n_out_bytes, uint64_t *n_hits, void *stream) {
+  int32_t rc = feed_grep_args(f, d_piece_offsets, d_seq_ids, n_pieces, flags, d_kept_recs, d_rec_out_offsets, cap_recs, d_out, cap_bytes,
+                              n_kept);
+  if (rc) return rc;
+  if (n_bytes && !d_corpus) return AHA_E_INVALID;
+  if ((rc = feed_grep_overlap(d_corpus, n_bytes, d_out, cap_bytes))) return rc;
+  std::lock_guard<std::mutex> lk(f->mu);
+  DeviceGuard g(f->ac->device);
+  Lease lease(f->ac);
+  FeedArgs F{};
+  F.text = d_corpus;
+  F.off = d_piece_offsets;
+  F.ids = d_seq_ids;
+  F.D = n_pieces;
+  F.n_bytes = n_bytes;
+  F.bases = d_piece_bases;
+  GrepOut O;
+  O.kept = d_kept_recs;
+  O.rec_out = d_rec_out_offsets;
+  O.out = d_out;
+  O.cap_recs = cap_recs;
+  O.cap_bytes = cap_bytes;
+  O.piece_rec = d_piece_rec_offsets;
+  O.piece_kept = d_piece_kept_offsets;
+  O.hold = d_piece_hold;
+  O.head = d_piece_head;
+  O.rec_bases = d_piece_rec_bases;
+  if (n_recs) *n_recs = 0;
+  *n_kept = 0;
+  if (n_out_bytes) *n_out_bytes = 0;
+  if (n_hits) *n_hits = 0;
+  return feed_grep(f, lease.get(), F, delim, flags, O, (hipStream_t)stream, n_recs, n_kept, n_out_bytes, n_hits);
+}
+
+// The host entry: the pieces go up into the feed's staging buffers; the kept fragments, their offsets and their bytes, sized
+// once the totals are known, and the per-piece arrays come back once the call has succeeded.
+int32_t aha_feed_grep_batch(aha_feed *f, const uint8_t *corpus, const uint64_t *piece_offsets, const uint32_t *seq_ids,
+                            uint64_t n_pieces, uint8_t delim, uint32_t flags, uint64_t *kept_recs, uint64_t *rec_out_offsets,
+                            uint64_t cap_recs, uint8_t *out, uint64_t cap_bytes, uint64_t *piece_rec_offsets,
+                            uint64_t *piece_kept_offsets, uint32_t *piece_hold, uint64_t *piece_head, uint64_t *piece_bases,
+                            uint64_t *piece_rec_bases, uint64_t *n_recs, uint64_t *n_kept, uint64_t *n_out_bytes, uint64_t *n_hits) {
+  int32_t rc = feed_grep_args(f, piece_offsets, seq_ids, n_pieces, flags, kept_recs, rec_out_offsets, cap_recs, out, cap_bytes, n_kept);
+  if (rc) return rc;
+  aha_ac *ac = f->ac;
+  if ((rc = check_pieces_host(f, piece_offsets, seq_ids, n_pieces))) return rc;
+  const uint64_t n_bytes = piece_offsets[n_pieces];
+  if (n_bytes && !corpus) return AHA_E_INVALID;
+  if ((rc = feed_grep_overlap(corpus, n_bytes, out, cap_bytes))) return rc;
+  std::lock_guard<std::mutex> lk(f->mu);
+  DeviceGuard g(ac->device);
+  Lease lease(ac);
+  hipStream_t s = f->hs;
+  const uint64_t D = n_pieces;
+  uint8_t *d_corpus = (uint8_t *)reserve(f, kHCorpus, n_bytes + 64);
+  uint64_t *d_off = (uint64_t *)reserve(f, kHOff, (D + 1) * 8);
+  uint32_t *d_ids = (uint32_t *)reserve(f, kHIds, D * 4);
+  uint64_t *d_bases = (uint64_t *)reserve(f, kHBases, D * 8);
+  uint32_t *d_hold = (uint32_t *)reserve(f, kHHold, D * 4);
+  uint64_t *d_pro = (uint64_t *)reserve(f, kHPieceRec, (D + 1) * 8);
+  uint64_t *d_pko = (uint64_t *)reserve(f, kHPieceKept, (D + 1) * 8);
+  uint64_t *d_head = (uint64_t *)reserve(f, kHHead, D * 8);
+  uint64_t *d_rb = (uint64_t *)reserve(f, kHRecBases, D * 8);
+  if (!d_corpus || !d_off || !d_ids || !d_bases || !d_hold || !d_pro || !d_pko || !d_head || !d_rb) return no_memory("staging buffers");
+  if (n_bytes) HIPCHK(ac, hipMemcpyAsync(d_corpus, corpus, n_bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(ac, hipMemcpyAsync(d_off, piece_offsets, (D + 1) * 8, hipMemcpyHostToDevice, s));
+  if (D) HIPCHK(ac, hipMemcpyAsync(d_ids, seq_ids, D * 4, hipMemcpyHostToDevice, s));
+  FeedArgs F{};
+  F.text = d_corpus;
+  F.off = d_off;
+  F.ids = d_ids;
+  F.D = D;
+  F.n_bytes = n_bytes;
+  F.bases = d_bases;
+  GrepOut O;
+  if (kept_recs) O.kept_slot = kHKept;
+  if (rec_out_offsets) O.rec_out_slot = kHRecOut;
+  if (out) O.out_slot = kHOut;
+  O.cap_recs = cap_recs;
+  O.cap_bytes = cap_bytes;
+  O.piece_rec = d_pro;
+  O.piece_kept = d_pko;
+  O.hold = d_hold;
+  O.head = d_head;
+  O.rec_bases = d_rb;
+  if (n_recs) *n_recs = 0;
+  *n_kept = 0;
+  if (n_out_bytes) *n_out_bytes = 0;
+  if (n_hits) *n_hits = 0;
+  uint64_t nr = 0, nk = 0, nb = 0, nh = 0;
+  rc = feed_grep(f, lease.get(), F, delim, flags, O, s, &nr, &nk, &nb, &nh);
+  if (rc == AHA_OK || rc == AHA_E_CAPACITY) {  // (both required numbers and the counts, as the device entry gives them)
+    if (n_recs) *n_recs = nr;
+    *n_kept = nk;
+    if (n_out_bytes) *n_out_bytes = nb;
+    if (n_hits) *n_hits = nh;
+  }
+  if (rc) return rc;
+  if (kept_recs && nk) HIPCHK(ac, hipMemcpyAsync(kept_recs, O.kept, nk * 8, hipMemcpyDeviceToHost, s));
+  if (rec_out_offsets) HIPCHK(ac, hipMemcpyAsync(rec_out_offsets, O.rec_out, (nk + 1) * 8, hipMemcpyDeviceToHost, s));
+  if (out && nb) HIPCHK(ac, hipMemcpyAsync(out, O.out, nb, hipMemcpyDeviceToHost, s));
+  if (piece_rec_offsets) HIPCHK(ac, hipMemcpyAsync(piece_rec_offsets, d_pro, (D + 1) * 8, hipMemcpyDeviceToHost, s));
+  if (piece_kept_offsets) HIPCHK(ac, hipMemcpyAsync(piece_kept_offsets, d_pko, (D + 1) * 8, hipMemcpyDeviceToHost, s));
+  if (piece_hold && D) HIPCHK(ac, hipMemcpyAsync(piece_hold, d_hold, D * 4, hipMemcpyDeviceToHost, s));
+  if (piece_head && D) HIPCHK(ac, hipMemcpyAsync(piece_head, d_head, D * 8, hipMemcpyDeviceToHost, s));
+  if (piece_bases && D) HIPCHK(ac, hipMemcpyAsync(piece_bases, d_bases, D * 8, hipMemcpyDeviceToHost, s));
+  if (piece_rec_bases && D) HIPCHK(ac, hipMemcpyAsync(piece_rec_bases, d_rb, D * 8, hipMemcpyDeviceToHost, s));
   HIPCHK(ac, hipStreamSynchronize(s));
   return AHA_OK;
 }

@@ -1,5 +1,5 @@
 // feed.hpp -- what feed.cpp (the feed entry points of the C ABI) and its kernels (scan_feed.hip, scan_feedselect.hip,
-// scan_feedreplace.hip, scan_feedsep.hip) share.  Library-internal.
+// scan_feedreplace.hip, scan_feedsep.hip, scan_feedgrep.hip) share.  Library-internal.
 #pragma once
 #include <cstdint>
 
@@ -19,6 +19,16 @@ struct FeedSelSeq {
   unsigned long long cursor;  // c: everything in front of it is final -- inside a reported hit or in no selected hit ever
 };
 
+// what a feed keeps per sequence for grep calls (aha_feed_grep_batch*), allocated by the feed's first one (32 bytes).  The
+// record that is open -- its delimiter has not arrived -- is the last open_len bytes of the sequence; the caller holds them.
+struct FeedGrepSeq {
+  unsigned long long seen;      // bytes that went through grep calls since open / reset / a FINAL call
+  unsigned long long open_len;  // bytes of the open record
+  unsigned long long recs;      // records closed so far
+  uint32_t open_hit;            // the open record, matched as its own document, has a hit already
+  uint32_t pad;
+};
+
 // the arguments every feed kernel takes (by value)
 struct FeedArgs {
   const uint8_t *text;         // the caller's pieces
@@ -32,7 +42,7 @@ struct FeedArgs {
   int32_t chars;
   FeedSeq *seqs;               // [n_seqs]
   uint8_t *ctx;                // [2][n_seqs][W]
-  uint32_t *verdict;           // [1]: bit 0 invalid offsets or ids, bit 1 a piece too long
+  uint32_t *verdict;           // [1]: bit 0 invalid offsets or ids, bit 1 a piece too long, bit 2 / 3 the select / grep state is behind
   uint64_t *win_total;         // [1]: bytes of the window batch
   uint8_t *win;                // the window batch [X_0..X_{D-1} | ctx_0.. | P'_0..]
   uint64_t *woff;              // [3D+1] its document offsets
@@ -60,6 +70,24 @@ struct FeedArgs {
   // calls on a feed with a separator filter (aha_feed_open_params; scan_feedsep.hip): the call's true hits also hold the hits
   // that end on the context's last byte -- the last edge[d] hits of ctx_d alone
   uint64_t *edge;              // [D], or null (every call on a plain feed)
+  // grep calls (aha_feed_grep_batch*): kfd_check refuses a sequence whose bytes did not all go through grep calls
+  const FeedGrepSeq *grep;     // [n_seqs], or null (every other call); verdict bit 3
+};
+
+// what the kernels of a grep call take beside FeedArgs (scan_feedgrep.hip).  The pieces are split into R fragments as a records
+// call splits documents; the window batch is [X_0.. | Y_0.. | Z_0..] at F.win / F.woff with the hit offsets F.wdho.
+struct FeedGrepArgs {
+  FeedGrepSeq *gseq;           // [n_seqs]
+  uint32_t delim, invert, final;
+  uint64_t R;
+  const uint64_t *frag;        // [R+1] the fragments' offsets into the pieces' bytes
+  const uint64_t *pro;         // [D+1] the pieces' offsets into the fragments (piece_rec_offsets)
+  const uint64_t *fdho;        // [R+1] the fragments' hit offsets, each matched from the root
+  uint8_t *flag;               // [R] bit 0 keep, bit 1 has, bit 2 closed
+  uint32_t *keep, *S, *T;      // ceil(R / 32) words each (scan_grep.hip kgr_flag's masks)
+  uint32_t *hold;              // [D] the caller's piece_hold, or null
+  uint64_t *head;              // [D] the caller's piece_head, or null
+  uint64_t *rec_bases;         // [D] the caller's piece_rec_bases, or null
 };
 
 // what the kernels of a call on a feed with a separator filter take beside FeedArgs (scan_feedsep.hip).  The call's true hits
@@ -123,6 +151,7 @@ __device__ inline uint64_t feedsel_cursor(uint64_t cursor, uint64_t n0, uint64_t
 #endif
 
 void feed_launch_check(const FeedArgs &F, void *stream);    // kfd_check, then kfd_scan of the window lengths
+void feed_launch_check_only(const FeedArgs &F, void *stream);  // kfd_check alone (a grep call lays out windows of its own)
 void feed_launch_windows(const FeedArgs &F, void *stream);  // kfd_windows (+ kfd_leads on char feeds)
 void feed_launch_merge(const FeedArgs &F, void *stream);    // kfd_scan of the hits per piece, kfd_merge
 void feed_launch_commit(const FeedArgs &F, void *stream);   // kfd_commit: bases, counters, the new contexts
@@ -152,5 +181,11 @@ void feedsep_launch_flag_finish(const FeedArgs &F, const FeedSepArgs &P, uint32_
 void feedsep_launch_compact(const FeedSepArgs &P, bool finish, uint32_t max_blocks, void *stream);            // out
 void feedsep_launch_count(const FeedArgs &F, const FeedSepArgs &P, uint32_t max_blocks, void *stream);  // F.kc (cleared by the host)
 void feedsep_launch_count_finish(const FeedArgs &F, uint32_t max_blocks, void *stream);                 // F.key_counts
+// grep calls (scan_feedgrep.hip), in this order; the ranks between flag and commit are select_launch_rank, the runs, the kept
+// fragments and the copy scan_grep.hip's and scan_replace.hip's
+void feedgrep_launch_layout(const FeedArgs &F, const FeedGrepArgs &G, void *stream);  // F.woff, F.win_total (after the check and the fragments)
+void feedgrep_launch_windows(const FeedArgs &F, const FeedGrepArgs &G, void *stream);  // F.win
+void feedgrep_launch_flag(const FeedArgs &F, const FeedGrepArgs &G, uint32_t max_blocks, void *stream);  // flag, then keep, S, T
+void feedgrep_launch_commit(const FeedArgs &F, const FeedGrepArgs &G, uint32_t max_blocks, void *stream);  // behind feed_launch_commit
 void feedsep_launch_restart(const FeedArgs &F, const FeedSepArgs &P, void *stream);  // a finish call: bases, the sequences at length 0
 }  // namespace aha

@@ -167,6 +167,25 @@ enum GrepSlot {
   kGrpTable,      // grep: the one-entry replacement table (the empty replacement)
   kGrpCount
 };
+// fgrpbuf: feed grep calls (feed.cpp feed_grep; scan_feedgrep.hip).  The fragments come from device_records, whose mask
+// (grpbuf) is dead once they are emitted; nothing here shares a buffer with grpbuf or with another slot of this family
+enum FeedGrepSlot {
+  kFgFragOff,     // the fragments' offsets into the pieces' bytes
+  kFgPieceFrag,   // the pieces' offsets into the fragments (piece_rec_offsets)
+  kFgWinOff,      // the window batch [X | Y | Z]: its document offsets
+  kFgWin,         // ... its bytes
+  kFgWinHitOff,   // ... its per-document hit offsets
+  kFgFragHitOff,  // the fragments' hit offsets, each matched from the root
+  kFgFlags,       // per fragment: keep, has, closed
+  kFgMasks,       // the keep, S and T masks, one bit per fragment each
+  kFgBlocks,      // their three block ranks, each with its total behind it
+  kFgSel,         // one synthesized selection row per dropped run, 12 bytes each
+  kFgStart,       // A, per dropped run its first byte in the pieces' bytes
+  kFgShift,       // per dropped run the change of length in front of it, the total change behind the last
+  kFgSums,        // the scan's block sums
+  kFgTable,       // the one-entry replacement table (the empty replacement)
+  kFgCount
+};
 // Device scratch of ONE match call (grow-only, reused by later calls that lease the same set).
 struct Scratch {
   std::mutex mu;  // held by the call that leased the set
@@ -187,6 +206,7 @@ struct Scratch {
   Buf frepbuf[kFrCount];
   Buf fsepbuf[kFpCount];
   Buf grpbuf[kGrpCount];
+  Buf fgrpbuf[kFgCount];
   // every family above, for free_scratch and scratch_bytes (S: Scratch or const Scratch): a new family is one more line here
   template <class S, class Fn>
   static void each_buf(S &sc, Fn fn) {
@@ -201,6 +221,7 @@ struct Scratch {
     for (auto &b : sc.frepbuf) fn(b);
     for (auto &b : sc.fsepbuf) fn(b);
     for (auto &b : sc.grpbuf) fn(b);
+    for (auto &b : sc.fgrpbuf) fn(b);
   }
   bool dc_rows_clear = false;  // every word of dcbuf[kDcRows] is zero (kdc_compact clears what kdc_add wrote; a call that failed may not have)
   hipStream_t hs[3] = {};  // host-buffer entry: private non-blocking streams for upload, match, download
@@ -373,7 +394,7 @@ uint64_t scratch_bytes(const Scratch *sc);
 // THE allocator of the grow-only buffers: b holds at least `bytes` afterwards, or nothing (the HIP error is returned, the
 // runtime's sticky one cleared).  What a new buffer gets beyond `bytes` is its family's rule:
 enum Grow {
-  kGrowEighth,   // bytes + bytes / 8 + 256 (v2buf, covbuf, selbuf, repbuf, fselbuf, frepbuf, fsepbuf, grpbuf)
+  kGrowEighth,   // bytes + bytes / 8 + 256 (v2buf, covbuf, selbuf, repbuf, fselbuf, frepbuf, fsepbuf, grpbuf, fgrpbuf)
   kGrowQuarter,  // bytes + bytes / 4 + 4096 (cntbuf, hostbuf)
   kGrowOrExact   // an eighth, else exactly `bytes`; `bytes` is what it records (dcbuf: what is known to be there)
 };
@@ -503,6 +524,13 @@ int32_t device_replace(aha_ac *ac, Scratch *sc, const aha_repl *table, const uin
 int32_t device_records(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
                        uint64_t n_bytes, uint8_t delim, uint64_t *d_rec_offsets, uint64_t cap_records, uint64_t *d_doc_rec_offsets,
                        uint64_t *n_records, void *stream, bool offsets_checked);
+// its two halves, split at the total (a feed grep call sizes the fragments' offsets from it): the mask and its rank into
+// grpbuf, *n_records read back; then, with grpbuf untouched in between, the offsets (either may be null).  No argument checks.
+int32_t device_records_settle(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                              uint64_t n_bytes, uint8_t delim, uint64_t *n_records, void *stream);
+int32_t device_records_emit(aha_ac *ac, Scratch *sc, const uint64_t *d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
+                            uint64_t *d_rec_offsets, uint64_t *d_doc_rec_offsets, void *stream);
+uint32_t grep_grid(const aha_ac *ac);  // the cap of the records and grep grids (AHA_GREP_BLOCKS)
 // one device-resident batch filtered (aha_ac_grep_batch_device): device_count for the hits per document, the kept documents and
 // the dropped runs from them (scan_grep.hip), replace's scan and copy over the runs (scan_replace.hip)
 int32_t device_grep(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,

@@ -72,6 +72,8 @@ __global__ void kfd_check(FeedArgs F) {
       bad |= 1u;
     else if (F.sel && F.sel[id].seen != F.seqs[id].bytes)  // a select call: bytes of the sequence went past its select state
       bad |= 4u;
+    else if (F.grep && F.grep[id].seen != F.seqs[id].bytes)  // a grep call: bytes of the sequence went past its grep state
+      bad |= 8u;
   }
   if (bad) atomicOr(F.verdict, bad);
 }
@@ -400,6 +402,10 @@ void feed_launch_check(const FeedArgs &F, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(kfd_check, dim3(grid_for(F.D + 1, kFdThreads, 1024)), dim3(kFdThreads), 0, s, F);
   hipLaunchKernelGGL(kfd_scan<0>, dim3(1), dim3(kFdScanThreads), 0, s, F);
+}
+
+void feed_launch_check_only(const FeedArgs &F, void *stream) {
+  hipLaunchKernelGGL(kfd_check, dim3(grid_for(F.D + 1, kFdThreads, 1024)), dim3(kFdThreads), 0, (hipStream_t)stream, F);
 }
 
 void feed_launch_windows(const FeedArgs &F, void *stream) {

@@ -291,6 +291,20 @@ lib LibAhaHip
                                     n_pieces : UInt64, n_bytes : UInt64, flags : UInt32, d_out : UInt8*, cap_bytes : UInt64,
                                     d_piece_out_offsets : UInt64*, d_piece_bases : UInt64*, d_piece_hold : UInt32*,
                                     n_out_bytes : UInt64*, n_selected : UInt64*, n_hits : UInt64*, stream : Void*) : Int32
+  # feed grep: the lines of the same pieces that close in the call and have a hit (byte feeds; the caller holds the open line)
+  FEED_GREP_FINAL = 2_u32 # (beside GREP_INVERT in the same flags word)
+  fun aha_feed_grep_batch(f : Feed, corpus : UInt8*, piece_offsets : UInt64*, seq_ids : UInt32*, n_pieces : UInt64,
+                          delim : UInt8, flags : UInt32, kept_recs : UInt64*, rec_out_offsets : UInt64*, cap_recs : UInt64,
+                          out : UInt8*, cap_bytes : UInt64, piece_rec_offsets : UInt64*, piece_kept_offsets : UInt64*,
+                          piece_hold : UInt32*, piece_head : UInt64*, piece_bases : UInt64*, piece_rec_bases : UInt64*,
+                          n_recs : UInt64*, n_kept : UInt64*, n_out_bytes : UInt64*, n_hits : UInt64*) : Int32
+  fun aha_feed_grep_batch_device(f : Feed, d_corpus : UInt8*, d_piece_offsets : UInt64*, d_seq_ids : UInt32*,
+                                 n_pieces : UInt64, n_bytes : UInt64, delim : UInt8, flags : UInt32, d_kept_recs : UInt64*,
+                                 d_rec_out_offsets : UInt64*, cap_recs : UInt64, d_out : UInt8*, cap_bytes : UInt64,
+                                 d_piece_rec_offsets : UInt64*, d_piece_kept_offsets : UInt64*, d_piece_hold : UInt32*,
+                                 d_piece_head : UInt64*, d_piece_bases : UInt64*, d_piece_rec_bases : UInt64*,
+                                 n_recs : UInt64*, n_kept : UInt64*, n_out_bytes : UInt64*, n_hits : UInt64*,
+                                 stream : Void*) : Int32
   fun aha_buffer_alloc(device : Int32, bytes : UInt64, d_ptr : Void**) : Int32
   fun aha_buffer_free(device : Int32, d_ptr : Void*) : Int32
   fun aha_buffer_upload(device : Int32, d_dst : Void*, src : Void*, bytes : UInt64) : Int32
@@ -890,6 +904,39 @@ module Aha
       end
       raise String.new(LibAhaHip.aha_last_error(@ac.handle)) if rc != 0
       {buf, hold}
+    end
+
+    # The next piece of one sequence grepped on the device: {lines, head, hold} -- the piece's fragments that close with it and
+    # are kept (each with its delimiter), the held bytes to emit in front of the first of them (the line that was open), and
+    # the bytes at the end of the piece that belong to the line left open: the caller keeps those (held += piece when
+    # hold == piece.size, else held = the piece's last hold bytes).  final: the piece is the last of its sequence; the open
+    # line closes and the sequence starts again from length 0.  (Uncompiled, as the rest of this class;
+    # tests/test_feed_grep_host.py checks that the lib block binds both entry points.)
+    def grep(seq : Int, piece : Bytes | String, delim : UInt8 = 10_u8, invert : Bool = false,
+             final : Bool = false) : {Array(Bytes), UInt64, UInt32}
+      bytes = piece.is_a?(String) ? piece.to_slice : piece
+      offs = [0_u64, bytes.size.to_u64]
+      ids = [seq.to_u32]
+      flags = (invert ? LibAhaHip::GREP_INVERT : 0_u32) | (final ? LibAhaHip::FEED_GREP_FINAL : 0_u32)
+      hold = 0_u32
+      head = 0_u64
+      # a call with no room: AHA_E_CAPACITY (-6) gives both sizes and changes nothing
+      none = Bytes.new(1)
+      roo = Array(UInt64).new(1, 0_u64)
+      rc = LibAhaHip.aha_feed_grep_batch(@handle, bytes.to_unsafe, offs.to_unsafe, ids.to_unsafe, 1_u64, delim, flags,
+        Pointer(UInt64).null, roo.to_unsafe, 0_u64, none.to_unsafe, 0_u64, Pointer(UInt64).null, Pointer(UInt64).null,
+        pointerof(hold), pointerof(head), Pointer(UInt64).null, Pointer(UInt64).null, Pointer(UInt64).null, out nk, out nb,
+        Pointer(UInt64).null)
+      buf = Bytes.new(nb.to_i32)
+      if rc == -6
+        roo = Array(UInt64).new(nk.to_i32 + 1, 0_u64)
+        rc = LibAhaHip.aha_feed_grep_batch(@handle, bytes.to_unsafe, offs.to_unsafe, ids.to_unsafe, 1_u64, delim, flags,
+          Pointer(UInt64).null, roo.to_unsafe, nk, buf.to_unsafe, nb, Pointer(UInt64).null, Pointer(UInt64).null,
+          pointerof(hold), pointerof(head), Pointer(UInt64).null, Pointer(UInt64).null, Pointer(UInt64).null, out nk2, out nb2,
+          Pointer(UInt64).null)
+      end
+      raise String.new(LibAhaHip.aha_last_error(@ac.handle)) if rc != 0
+      {Array(Bytes).new(roo.size - 1) { |i| buf[roo[i].to_i32, (roo[i + 1] - roo[i]).to_i32] }, head, hold}
     end
 
     # Hits per key of match on the same pieces, without the hit list: {key_counts (K entries), piece_hit_offsets,

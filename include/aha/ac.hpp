@@ -12,8 +12,10 @@
 // Header-only; link with -laha_hip.  No CPU fallback: matching needs a GPU.
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <map>
 #include <stdexcept>
 #include <string>
 #include <string_view>
@@ -582,7 +584,7 @@ class Feed {
   }
   Feed(const Feed &) = delete;
   Feed &operator=(const Feed &) = delete;
-  Feed(Feed &&o) noexcept : ac_(o.ac_), f_(o.f_) { o.f_ = nullptr; }
+  Feed(Feed &&o) noexcept : ac_(o.ac_), f_(o.f_), grep_held_(std::move(o.grep_held_)) { o.f_ = nullptr; }
   ~Feed() { aha_feed_free(f_); }
 
   // host buffers: the hits of the call; piece_hit_offsets (D+1) and bases (D) when asked for
@@ -837,7 +839,97 @@ class Feed {
   std::string replace(uint32_t seq, std::string_view piece, const AC::Replacements &table, bool final = false) {
     return replace_batch(piece, {0, piece.size()}, {seq}, table, final);
   }
-  void reset(uint32_t seq = UINT32_MAX) { check(aha_feed_reset(f_, seq)); }
+  // What a grep call of pieces gives beside the kept bytes (aha_feed_grep_batch).
+  struct Grep {
+    std::vector<uint64_t> kept_recs;           // n_kept: the kept closed fragments, numbered as records of the pieces
+    std::vector<uint64_t> rec_out_offsets;     // n_kept + 1: where each lies in the result
+    std::vector<uint64_t> piece_rec_offsets;   // D + 1: where each piece's fragments lie
+    std::vector<uint64_t> piece_kept_offsets;  // D + 1: kept fragments per piece, scanned
+    std::vector<uint32_t> piece_hold;          // D: bytes at the end of the piece that belong to the record left open
+    std::vector<uint64_t> piece_head;          // D: held bytes to emit in front of the piece's first kept fragment
+    std::vector<uint64_t> bases;               // D: the sequence's length before the piece
+    std::vector<uint64_t> piece_rec_bases;     // D: the sequence's records closed before the call
+    uint64_t n_recs = 0, n_hits = 0;
+  };
+  // The lines of sequences in pieces, kept when they have a hit: the pieces are split at `delim` as AC::records splits
+  // documents; a fragment closes when it ends with the delimiter (or with final = true) and is kept when (its record, matched
+  // as its own document, has a hit) != invert -- a piece's first fragment may continue a record earlier pieces left open.
+  // -> the kept fragments' bytes of this call's pieces, one behind the other.  The caller keeps the bytes of the open record
+  // (piece_hold) and emits them in front of the piece's first kept fragment when piece_head says so.  With final = true the
+  // named sequences start again from length 0.  Byte feeds only, one delimiter per feed, and only for sequences fed through
+  // grep calls since their reset.  A call with no room first (it changes nothing).
+  std::string grep_batch(std::string_view corpus, const std::vector<uint64_t> &piece_offsets, const std::vector<uint32_t> &seq_ids,
+                         char delim = '\n', bool invert = false, bool final = false, Grep *info = nullptr) {
+    if (piece_offsets.empty()) throw Error(AHA_E_INVALID, "piece_offsets holds D + 1 entries");
+    const uint64_t D = piece_offsets.size() - 1;
+    if (seq_ids.size() != D) throw Error(AHA_E_INVALID, "one sequence id per piece");
+    if (corpus.size() < piece_offsets.back()) throw Error(AHA_E_INVALID, "the corpus is shorter than the last offset");
+    const uint32_t flags = (invert ? AHA_GREP_INVERT : 0u) | (final ? AHA_FEED_GREP_FINAL : 0u);
+    const uint8_t *text = reinterpret_cast<const uint8_t *>(corpus.data());
+    Grep c;
+    c.piece_rec_offsets.assign(D + 1, 0);
+    c.piece_kept_offsets.assign(D + 1, 0);
+    c.piece_hold.assign(D, 0);
+    c.piece_head.assign(D, 0);
+    c.bases.assign(D, 0);
+    c.piece_rec_bases.assign(D, 0);
+    c.kept_recs.assign(1, 0);
+    c.rec_out_offsets.assign(1, 0);
+    std::string out(1, '\0');
+    uint64_t nk = 0, nb = 0;
+    auto call = [&](uint64_t cap_recs, uint64_t cap_bytes) {
+      return aha_feed_grep_batch(f_, text, piece_offsets.data(), seq_ids.data(), D, (uint8_t)delim, flags, c.kept_recs.data(),
+                                 c.rec_out_offsets.data(), cap_recs, reinterpret_cast<uint8_t *>(&out[0]), cap_bytes,
+                                 c.piece_rec_offsets.data(), c.piece_kept_offsets.data(), D ? c.piece_hold.data() : nullptr,
+                                 D ? c.piece_head.data() : nullptr, D ? c.bases.data() : nullptr,
+                                 D ? c.piece_rec_bases.data() : nullptr, &c.n_recs, &nk, &nb, &c.n_hits);
+    };
+    int32_t rc = call(0, 0);
+    if (rc == AHA_E_CAPACITY) {  // (the feed is unchanged: the same call again, with room)
+      c.kept_recs.assign(std::max<uint64_t>(nk, 1), 0);
+      c.rec_out_offsets.assign(nk + 1, 0);
+      out.assign(std::max<uint64_t>(nb, 1), '\0');
+      rc = call(nk, nb);
+    }
+    check(rc);
+    c.kept_recs.resize(nk);
+    c.rec_out_offsets.resize(nk + 1);
+    out.resize(nb);
+    if (info) *info = std::move(c);
+    return out;
+  }
+  // the next piece of one sequence: the kept lines that close with it, the held bytes of the open line in front of the first
+  // where it is kept; the open line's bytes stay in this object.  final: the open line closes.  One delimiter and one invert
+  // per sequence; the lines of a sequence's pieces, in order, are AC::grep of the whole.
+  std::vector<std::string> grep(uint32_t seq, std::string_view piece, char delim = '\n', bool invert = false, bool final = false) {
+    Grep c;
+    const std::string raw = grep_batch(piece, {0, piece.size()}, {seq}, delim, invert, final, &c);
+    std::vector<std::string> lines;
+    for (size_t i = 0; i + 1 < c.rec_out_offsets.size(); i++)
+      lines.emplace_back(raw.substr(c.rec_out_offsets[i], c.rec_out_offsets[i + 1] - c.rec_out_offsets[i]));
+    std::string &held = grep_held_[seq];
+    if (c.piece_head[0]) {
+      const std::string open = held.substr(held.size() - c.piece_head[0]);
+      if (lines.empty())
+        lines.push_back(open);  // (an empty piece under final: the line closes without a fragment)
+      else
+        lines[0] = open + lines[0];
+    }
+    if (final)
+      held.clear();
+    else if (c.piece_hold[0] == piece.size())
+      held.append(piece);
+    else
+      held.assign(piece.substr(piece.size() - c.piece_hold[0]));
+    return lines;
+  }
+  void reset(uint32_t seq = UINT32_MAX) {
+    check(aha_feed_reset(f_, seq));
+    if (seq == UINT32_MAX)
+      grep_held_.clear();
+    else
+      grep_held_.erase(seq);
+  }
   // {bytes, chars} fed to the sequence so far
   std::pair<uint64_t, uint64_t> position(uint32_t seq) const {
     uint64_t b = 0, c = 0;
@@ -854,6 +946,7 @@ class Feed {
   }
   aha_ac *ac_;
   aha_feed *f_ = nullptr;
+  std::map<uint32_t, std::string> grep_held_;  // grep(): the bytes of every sequence's open line
 };
 
 // Several GPUs of one node behind one object (aha_group_*): contiguous byte-balanced document ranges, one per device entry,

@@ -736,8 +736,8 @@ int32_t aha_ac_replace_batch_device(aha_ac *ac, const aha_repl *table, const uin
  * of these calls' kernels, the reused rank, scan and copy launches included.
  * aha_ac_last_timing (grep): engine = the engine that traversed, n_hits = all hits, ms_write = everything after the count.
  * The host entries stage the batch on the device; a host sizing call followed by the real call runs the device work twice.
- * Out of scope so far: char offsets, match_longest, feeds, groups, multi-byte delimiters, a minimum hit count, an in-place
- * form. */
+ * Out of scope so far: char offsets, match_longest, groups, multi-byte delimiters, a minimum hit count, an in-place form
+ * (feeds: aha_feed_grep_batch* below). */
 #define AHA_GREP_INVERT 1u /* keep the documents WITHOUT a hit */
 int32_t aha_ac_records_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc_offsets, uint64_t n_docs, uint8_t delim,
                              uint32_t flags /* 0 */, uint64_t *rec_offsets /* cap_records + 1 */, uint64_t cap_records,
@@ -911,6 +911,94 @@ int32_t aha_feed_replace_batch_device(aha_feed *f, const aha_repl *table, const 
                                       uint64_t *d_piece_bases /* D or NULL */, uint32_t *d_piece_hold /* D or NULL */,
                                       uint64_t *n_out_bytes, uint64_t *n_selected /* or NULL */, uint64_t *n_hits /* or NULL */,
                                       void *stream);
+
+/* Feed grep: records and grep (aha_ac_records_batch*, aha_ac_grep_batch* above) for sequences that arrive in pieces whose ends
+ * fall in the middle of lines.  The same pieces as aha_feed_match_batch*, on a BYTE feed, and a delimiter byte.
+ * The whole-sequence definition.  T = a sequence: all its pieces since open, reset or a FINAL call, concatenated.  Its records
+ * are aha_ac_records_batch of the one document T with `delim`; a record is KEPT when (aha_ac_match_batch of the record AS ITS
+ * OWN DOCUMENT has >= 1 hit) != invert -- aha_ac_grep_batch over those record offsets, on a plain or a folded handle.  A record
+ * CLOSES in the call that delivers its delimiter byte; the trailing record without a delimiter closes in the sequence's FINAL
+ * call.  Concatenated over a sequence's calls (the last with AHA_FEED_GREP_FINAL), what the feed reports as kept -- the held
+ * bytes it tells the caller to emit included -- is aha_ac_grep_batch's `out` for the whole sequence, byte for byte, in order.
+ * The open line has no length limit and the feed's state per sequence is bounded, so -- as with piece_hold of
+ * aha_feed_select_batch -- the CALLER keeps the bytes of the record that is still open; the call says how many to keep and when
+ * to emit or drop them.
+ * The pieces are split into FRAGMENTS exactly as aha_ac_records_batch(corpus, piece_offsets, delim) splits them: R fragments,
+ * piece_rec_offsets[0 .. D] = that call's doc_rec_offsets.  Only a piece's last fragment can be open (it has no delimiter and
+ * the call is not FINAL); only a piece's first fragment can continue a record from earlier pieces.  Outputs, optional unless
+ * noted:
+ *   kept_recs[0 .. n_kept)        the kept CLOSED fragments' indices in that numbering, ascending; an open fragment is never listed
+ *   rec_out_offsets[0 .. n_kept], out   the kept fragments' bytes that lie in this call's pieces, one behind the other -- the
+ *                                 caller's own bytes, on a folded handle too.  cap_recs bounds kept_recs and rec_out_offsets
+ *                                 (which holds cap_recs + 1 entries), cap_bytes bounds out
+ *   piece_kept_offsets[0 .. D]    kept fragments per piece, scanned
+ *   piece_hold[d] (uint32)        the bytes at the end of piece d that belong to the record left open: 0 under FINAL; outside
+ *                                 FINAL it equals |P_d| exactly when nothing closed in the piece
+ *   piece_head[d] (uint64)        the bytes IN FRONT of the piece that belong to a record which closes in this piece and is
+ *                                 kept -- the length of the record that was open before the call: the caller emits that many
+ *                                 held bytes in front of the piece's first kept fragment.  0 when no record was open, when it
+ *                                 stays open, or when it closes and is dropped.  One case is irregular: an EMPTY piece under
+ *                                 FINAL with a record open closes that record without any fragment -- it appears only as
+ *                                 piece_head[d], not in kept_recs, *n_kept or piece_kept_offsets
+ *   piece_bases[d]                the sequence's length before the piece
+ *   piece_rec_bases[d]            the records of the sequence closed before the call: fragment j of piece d is line
+ *                                 piece_rec_bases[d] + (j - piece_rec_offsets[d]) of its sequence
+ *   *n_recs = R; *n_kept (required); *n_out_bytes; *n_hits = the hits of the fragments, each matched as its own document.
+ * The caller's holding rule, per sequence: emit piece_head held bytes (else drop them when hold < |P| or under FINAL), then the
+ * piece's kept bytes; then, under FINAL, hold nothing; else if hold == |P|: held += piece; else held = the piece's last hold bytes.
+ * A call takes the sequence from n0 to n1 as a match call does.  Under FINAL the named sequences start again at length 0, as
+ * after aha_feed_reset.
+ * THE TRAP.  The hits of a record are those of the record matched as its own document: the automaton reports by state (only
+ * where the longest suffix that is a trie path ends a key), so they are neither the hits of the sequence that lie inside the
+ * record nor the hits of a fragment from the root.  Keys "abc", "b", pieces "a" | "b\n": the record "ab\n" has no hit (the
+ * state at b is "ab"); the fragment "b\n" from the root has one.  Keys "x\nabc", "b", sequence "x\nab\n": the record "ab\n" has
+ * a hit; a feed match of the sequence reports none there (its state at b is "x\nab").  A key "\nb" never hits in a record; a
+ * key "b\n" hits only at a record's end.  The call applies the feed's two facts to the record as the sequence (DESIGN.md 4.10
+ * "Feed grep"): for a piece whose first fragment continues an open record of open_len bytes that already has a hit or not
+ * (open_hit), with W = max(Lmax - 1, 0), c = min(W, open_len), e0 = the first fragment's length, g = min(W, e0),
+ * X = ctx[-c:] || P[0 .. g), Y = ctx[-c:], Z = P[0 .. g):
+ *   has(record) = open_hit  ||  hits(X) - hits(Y) > 0  ||  hits(fragment from the root) - hits(Z) > 0
+ * Every other fragment begins a record, so its own count from the root is exact.
+ * Validity: a grep call is valid on a sequence only if all its bytes since open, reset or FINAL went through grep calls
+ * (otherwise AHA_E_INVALID, found on the device, nothing changes, until its reset).  `delim` is fixed by the feed's first
+ * successful grep call; another value later is AHA_E_INVALID.  A NULL feed or n_kept, a feed opened with AHA_FEED_CHARS or with a
+ * separator filter (a follow-up), an unknown flag, a NULL buffer with a non-zero capacity (cap_recs with neither kept_recs nor
+ * rec_out_offsets; cap_bytes without out), out overlapping the corpus: AHA_E_INVALID, all before any device work.  Piece and id
+ * validation is that of the other feed entries.
+ * AHA_E_CAPACITY when n_kept > cap_recs and kept_recs or rec_out_offsets was given, or when n_out_bytes > cap_bytes and out was
+ * given: BOTH required numbers are reported.  No failing call writes a caller buffer or moves any sequence, AHA_E_CAPACITY
+ * included: the same call with larger buffers gives what the first would have.  A call whose buffers are all NULL succeeds and
+ * moves the sequences: size with a non-NULL buffer of capacity 0.  out == NULL never launches the copy.  Two identical call
+ * sequences give identical bytes.  aha_feed_reset clears the grep state.  The handle's back-off state is read, never written.
+ * Pipeline (feed.cpp feed_grep, scan_feedgrep.hip): kfd_check; the records call over the pieces in two halves (the total sizes
+ * the fragment offsets); the window batch [X | Y | Z], at most 4 W bytes per piece; the count call without key counts over the
+ * windows, then over the fragments as documents (aha_ac_last_timing reports this pass); keep, S and T over the fragments (an
+ * open tail counts as dropped); grep's rank, runs, scan, emit and copy as they are; kfd_commit and kfg_commit.  Device scratch:
+ * a records call's and a count call's, 17 bytes and 3 bits per fragment, 28 bytes per dropped run, 56 bytes and 4 W per piece;
+ * 32 bytes of state per sequence.  AHA_GREP_BLOCKS caps the grids.
+ * Out of scope so far: separator-filter feeds, char feeds, match_longest, a device-side hold buffer, a minimum hit count,
+ * context lines. */
+#define AHA_FEED_GREP_FINAL 2u /* the pieces named in this call are the last of their sequences (beside AHA_GREP_INVERT, bit 0) */
+int32_t aha_feed_grep_batch(aha_feed *f, const uint8_t *corpus, const uint64_t *piece_offsets, const uint32_t *seq_ids,
+                            uint64_t n_pieces, uint8_t delim, uint32_t flags /* AHA_GREP_INVERT | AHA_FEED_GREP_FINAL */,
+                            uint64_t *kept_recs /* or NULL */, uint64_t *rec_out_offsets /* cap_recs + 1 or NULL */,
+                            uint64_t cap_recs, uint8_t *out /* or NULL */, uint64_t cap_bytes,
+                            uint64_t *piece_rec_offsets /* D+1 or NULL */, uint64_t *piece_kept_offsets /* D+1 or NULL */,
+                            uint32_t *piece_hold /* D or NULL */, uint64_t *piece_head /* D or NULL */,
+                            uint64_t *piece_bases /* D or NULL */, uint64_t *piece_rec_bases /* D or NULL */,
+                            uint64_t *n_recs /* or NULL */, uint64_t *n_kept, uint64_t *n_out_bytes /* or NULL */,
+                            uint64_t *n_hits /* or NULL */);
+/* Device-resident form: d_ pointers are HBM on the handle's device, validated on the device before anything is indexed with
+ * them; the n_ pointers are host memory; blocks until final. */
+int32_t aha_feed_grep_batch_device(aha_feed *f, const uint8_t *d_corpus, const uint64_t *d_piece_offsets, const uint32_t *d_seq_ids,
+                                   uint64_t n_pieces, uint64_t n_bytes, uint8_t delim,
+                                   uint32_t flags /* AHA_GREP_INVERT | AHA_FEED_GREP_FINAL */, uint64_t *d_kept_recs /* or NULL */,
+                                   uint64_t *d_rec_out_offsets /* cap_recs + 1 or NULL */, uint64_t cap_recs,
+                                   uint8_t *d_out /* or NULL */, uint64_t cap_bytes, uint64_t *d_piece_rec_offsets /* D+1 or NULL */,
+                                   uint64_t *d_piece_kept_offsets /* D+1 or NULL */, uint32_t *d_piece_hold /* D or NULL */,
+                                   uint64_t *d_piece_head /* D or NULL */, uint64_t *d_piece_bases /* D or NULL */,
+                                   uint64_t *d_piece_rec_bases /* D or NULL */, uint64_t *n_recs /* or NULL */, uint64_t *n_kept,
+                                   uint64_t *n_out_bytes /* or NULL */, uint64_t *n_hits /* or NULL */, void *stream);
 
 /* Frees the handle's device scratch (it grows with the largest batch seen and is otherwise kept for reuse). */
 int32_t aha_ac_release_scratch(aha_ac *ac);
