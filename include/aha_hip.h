@@ -394,7 +394,10 @@ int32_t aha_ac_load(const void *buf, uint64_t n_bytes, const aha_options *opts, 
  * char_offsets changes no count (the call takes the byte-offset route); a separator filter counts the filtered hits;
  * longest != 0 is AHA_E_INVALID.  AHA_COUNT_ACCUMULATE adds into key_counts instead of overwriting it: running totals over
  * a corpus streamed through in batches.  Errors, device validation of d_doc_offsets, threading (a call leases a scratch
- * set) and the host entry's range-by-range uploads are those of the match entries.  A count call changes nothing a later
+ * set) and the host entry's range-by-range uploads are those of the match entries.  A device call refused for its offsets
+ * (AHA_E_INVALID / AHA_E_TOO_LONG) writes no doc_hit_offsets but may already have cleared d_key_counts (without
+ * AHA_COUNT_ACCUMULATE): the verdict comes from the device, behind the clear -- unlike aha_feed_count_batch*, which leaves
+ * key_counts as it was.  A count call changes nothing a later
  * match call of the handle depends on.  Pipeline: the match's engine with full-size event regions (document ranges where
  * they do not fit: device scratch above); one add per EVENT (END position) into an LDS table per workgroup instead of the
  * expansion, then the keys' output chains (aha_amd/csrc/scan_count.hip).  A separator filter -- a test per hit -- and

@@ -16,24 +16,17 @@ import time
 import numpy as np
 import pytest
 
+import grepsim
 import pyoracle as orc
+import replacesim
+import selectsim
 from aha_amd import AC, AhaError, BitArray, DeviceBuffer
 from aha_amd import _native as N
 from aha_amd.ac import _params
+from walksim import (ENGINE_VARS, PAD, S32, S64, VARIANTS, Text, ascii_keys, cjk_keys, compile_under, de_bruijn_walk)
+from walksim import check_dev as _check_dev, check_dho as _check_dho, check_np as _check_np, dho_dev as _dho_dev, hits_np as _hits_np
 
 pytestmark = pytest.mark.gpu
-
-# the engine variants of test_gpu_parity.py's fixture (the opt-in skip and pair engines left out); read at compile time
-ENGINE_VARS = ("AHA_ENGINE", "AHA_UNIT_HEADER_BESIDE", "AHA_UNIT_BASE_BITS", "AHA_UNIT_POST", "AHA_LDS_SLOTS")
-VARIANTS = {
-    "auto": {},
-    "v2": {"AHA_ENGINE": "v2"},
-    "v1": {"AHA_ENGINE": "v1"},
-    "u": {"AHA_ENGINE": "unit", "AHA_UNIT_HEADER_BESIDE": "0"},
-    "ur": {"AHA_ENGINE": "unit", "AHA_UNIT_POST": "regroup"},
-    "uh": {"AHA_ENGINE": "unit", "AHA_UNIT_HEADER_BESIDE": "1"},
-    "f": {"AHA_ENGINE": "filter"},
-}
 
 HOST, DEV_DHO, DEV_NODHO, STREAM, KEEP, CHARS, SEP, LONG1, LONG2, SINGLE, CAP, BADOFF, EMPTY, UNALIGNED, RELEASE, PROFILE = range(16)
 KIND_NAMES = ["host", "dev_dho", "dev_nodho", "stream", "keep", "chars", "sep", "longest1", "longest2", "single", "capacity",
@@ -43,49 +36,10 @@ ZERO_HIT_KINDS = {EMPTY}          # their count is 0 whatever the text
 NO_DOC_KINDS = {SINGLE}           # one sequence, no document offsets
 TIMED = {HOST, DEV_DHO, DEV_NODHO, STREAM, KEEP, CHARS, SEP, SINGLE, UNALIGNED, PROFILE}  # match_longest and empty batches publish no timing
 
-S32 = -7                          # sentinel of the int32 hit rows
-S64 = 0xFFFFFFFFFFFFFFFB          # sentinel of the uint64 per-document offsets
-PAD = 64                          # rows / entries behind what a call may write
 SEP_BITS = [32]                   # a space separates
 
 
-def de_bruijn_walk(k):
-    """Kinds 0 .. k-1 in an order in which every ordered pair (a, b) stands next to each other once: k^2 + 1 steps."""
-    a = [0] * (2 * k)
-    seq = []
-
-    def db(t, p):
-        if t > 2:
-            if 2 % p == 0:
-                seq.extend(a[1:p + 1])
-        else:
-            a[t] = a[t - p]
-            db(t + 1, p)
-            for j in range(a[t - p] + 1, k):
-                a[t] = j
-                db(t + 1, t)
-
-    db(1, 1)
-    return seq + seq[:1]
-
-
 # ---- key sets and their texts ------------------------------------------------
-
-class Text:
-    def __init__(self, docs):
-        self.docs = [d.encode() if isinstance(d, str) else d for d in docs]
-        self.corpus = np.frombuffer(b"".join(self.docs), dtype=np.uint8).copy()
-        self.offs = np.cumsum([0] + [len(d) for d in self.docs]).astype(np.uint64)
-        self.D = len(self.docs)
-        self._dev = None
-
-    def dev(self):
-        import torch
-
-        if self._dev is None:
-            self._dev = (torch.from_numpy(self.corpus).cuda(), torch.from_numpy(self.offs.astype(np.int64)).cuda())
-        return self._dev
-
 
 def _docs(rng, tokens, sep, shape, density, fill):
     out = []
@@ -110,12 +64,7 @@ def _ascii_set():
     """(a) a keyword list of ASCII keys of 3 to 64 bytes (the prefix-filter engine's) over text with a few non-ASCII
     characters; keys nested six deep on one walk and a document dense with them: kf_walk hands the batch back."""
     rng = random.Random(31)
-    keys = set()
-    while len(keys) < 150:
-        keys.add("".join(rng.choice("abcdefghijkl") for _ in range(rng.randint(3, 8))))
-    keys = sorted(keys) + ["".join(rng.choice("abcdefghijklmnopqrstuvwxyz") for _ in range(n)) for n in (20, 33, 64)]
-    nested = ["qrstuvwxy"[:n] for n in range(4, 10)]
-    keys = list(dict.fromkeys(keys + nested))
+    keys, nested = ascii_keys(rng)
     fill = ["zz", "é", "ü9", "0", "mn"]
     dense = Text(["qrstuvwxy " * 3000, "ab qrstuvwxy", "é" * 40 + "qrstuvwxy" * 700])
     return keys, _pool(rng, keys + nested * 4, " ", fill, [dense])
@@ -124,13 +73,7 @@ def _ascii_set():
 def _cjk_set():
     """(b) CJK / mixed UTF-8 keys of 1 to 4 characters: the character-level image (engine 4) under `auto`."""
     rng = random.Random(32)
-    cps = [chr(c) for c in list(range(0x4E00, 0x4E30)) + list(range(97, 105)) + list(range(0x430, 0x438))]
-    keys, seen = [], set()
-    while len(keys) < 150:
-        k = "".join(rng.choice(cps) for _ in range(rng.randint(1, 4)))
-        if k not in seen:
-            seen.add(k)
-            keys.append(k)
+    keys, cps = cjk_keys(rng)
     fill = ["ä", "ß", "\U0001F600", "x", "é"]
     return keys, _pool(rng, cps + keys + [" "] * 20, "", fill)
 
@@ -241,40 +184,6 @@ def plan_walk(name):
 
 
 # ---- one call of each kind ---------------------------------------------------
-
-def _hits_np(cap):
-    out = np.empty(cap + PAD, dtype=orc.HIT_DTYPE)
-    out["start"] = out["end"] = out["value"] = S32
-    return out
-
-
-def _check_np(out, n, want, limit):
-    """hits [0, n) are the oracle's, rows [limit, end) untouched."""
-    assert n == len(want)
-    assert out[:n].tobytes() == want.tobytes()
-    tail = out[limit:]
-    assert (tail["start"] == S32).all() and (tail["end"] == S32).all() and (tail["value"] == S32).all()
-
-
-def _check_dev(big, n, want, limit):
-    import torch
-
-    assert n == len(want)
-    assert big[:n].cpu().numpy().tobytes() == want.tobytes()
-    assert bool((big[limit:] == S32).all())
-
-
-def _dho_dev(D):
-    import torch
-
-    return torch.full((D + 1 + PAD,), S64 - (1 << 64), dtype=torch.int64, device="cuda")
-
-
-def _check_dho(dho, D, want):
-    got = dho.cpu().numpy().astype(np.uint64) if not isinstance(dho, np.ndarray) else dho
-    assert np.array_equal(got[:D + 1], want)
-    assert (got[D + 1:] == np.uint64(S64)).all()
-
 
 def _host_batch(g, t, cap, chars=False, sep=None, longest=0, keep=None):
     """aha_ac_match_batch / _keep on the caller's own buffers (prefilled with sentinels)."""
@@ -447,14 +356,6 @@ def run_kind(g, name, kind, ti, st, state):
         _check_dho(dho, 5, np.zeros(6, dtype=np.uint64))
         return 0, 5
     raise AssertionError(kind)
-
-
-def compile_under(monkeypatch, variant, keys):
-    for v in ENGINE_VARS:
-        monkeypatch.delenv(v, raising=False)
-    for k, v in VARIANTS[variant].items():
-        monkeypatch.setenv(k, v)
-    return AC.compile(keys)
 
 
 def multi_range_call(g, name):
@@ -640,10 +541,11 @@ def _alloc_input():
 class _ModelAnswers:
     """What every call kind returns for one batch, from ONE pass of tests/pymodel.py over its documents."""
 
-    def __init__(self, model, t, fold, n_keys):
+    def __init__(self, model, t, fold, n_keys, repl):
         from aha_amd.ac import HIT_DTYPE, KEY_COUNT_DTYPE
 
         hits, pairs, self.dho, self.dpo = [], [], [0], [0]
+        sep_hits, self.sep_pho = [], [0]
         covered = np.zeros(t.corpus.size, dtype=np.bool_)
         self.doc_covered = np.zeros(t.D, dtype=np.uint64)
         for d, doc in enumerate(t.docs):
@@ -657,6 +559,9 @@ class _ModelAnswers:
             pairs += [(k, int(c)) for k, c in enumerate(per_key) if c]
             self.dho.append(len(hits))
             self.dpo.append(len(pairs))
+            # a first piece on a feed with a separator filter: the surviving hits that end before the piece's last byte
+            sep_hits += [x for x in model.match(doc.lower() if fold else doc, sep=(256, ALLOC_SEP), chars=False) if x[1] < len(doc)]
+            self.sep_pho.append(len(sep_hits))
         self.hits = np.array(hits, dtype=HIT_DTYPE)
         self.pairs = np.array(pairs, dtype=KEY_COUNT_DTYPE)
         self.key_counts = np.bincount(self.hits["value"], minlength=n_keys).astype(np.uint64)
@@ -666,9 +571,27 @@ class _ModelAnswers:
         self.mask = np.packbits(np.concatenate([covered, np.zeros(-covered.size % 32, dtype=np.bool_)]),
                                 bitorder="little").view(np.uint32)
         self.redacted = np.where(covered, np.uint8(0x2A), t.corpus)
+        # select, replace, records and grep over the same hit list
+        self.sel, self.dso = selectsim.select(self.hits, self.dho)
+        self.rep, self.doo = replacesim.replace(t.corpus, t.offs, self.sel, self.dso, repl)
+        self.rec, self.dro = grepsim.records(t.corpus, t.offs, b"\n")
+        self.kept, self.kept_out, self.kept_doo = grepsim.grep(np.diff(self.dho.astype(np.int64)), t.offs, t.corpus, False)
+        self.sep_hits = np.array(sep_hits, dtype=HIT_DTYPE)
+        self.sep_pho = np.array(self.sep_pho, dtype=np.uint64)
 
 
 _ALLOC = {}
+ALLOC_SEP = [32, 45]              # a space and a hyphen separate (what _alloc_input joins its words with)
+
+
+def _alloc_repl(keys):
+    """grow, shrink, delete, same length, keep -- by the key's index"""
+    repl = {}
+    for i, k in enumerate(keys):
+        r = [k + "++", "_", "", "#" * len(k), None][i % 5]
+        if r is not None:
+            repl[i] = r.encode()
+    return repl
 
 
 def _alloc_case(fold):
@@ -679,7 +602,7 @@ def _alloc_case(fold):
     keys, big, small = _ALLOC["input"]
     if fold not in _ALLOC:
         model = ModelAC([k.lower() for k in keys] if fold else keys)
-        _ALLOC[fold] = tuple(_ModelAnswers(model, t, fold, len(keys)) for t in (big, small))
+        _ALLOC[fold] = tuple(_ModelAnswers(model, t, fold, len(keys), _alloc_repl(keys)) for t in (big, small))
     return keys, (big, small), _ALLOC[fold]
 
 
@@ -687,17 +610,67 @@ def _alloc_case(fold):
 def test_scratch_only_grows_in_every_call_family(fold, monkeypatch):
     """The allocator's contract (capi.cpp reserve), for every family of scratch buffers a call kind touches: the result is
     the model's, a second identical call and a call on a smaller batch leave scratch_bytes() as it is (the buffers only
-    grow), release_scratch() brings it to 0, and the call gives the right answer again on fresh buffers."""
+    grow), release_scratch() brings it to 0, and the call gives the right answer again on fresh buffers.
+
+    Feed match, select and replace calls keep the rule for an identical call, not for the smaller batch: a feed matches its window batch into a hit buffer
+    of its own that only grows (feed.cpp feed_windows), so the smaller batch's windows run with the larger batch's capacity;
+    with a capacity above a hit per 4 bytes of text the match plans full-size event regions (engine.cpp plan_v2, `dense`), which
+    the larger batch at the same capacity did not need.  Nothing is freed and nothing grows twice: what is asserted there is
+    that scratch_bytes() does not shrink on the smaller batch and that the smaller and the larger batch again leave it where
+    it then stands."""
     import torch
 
     keys, texts, answers = _alloc_case(fold)
-    for v in ENGINE_VARS + ("AHA_COUNT_REGION_BYTES", "AHA_DOCCOUNT_HIT_BYTES"):
+    for v in ENGINE_VARS + ("AHA_COUNT_REGION_BYTES", "AHA_DOCCOUNT_HIT_BYTES", "AHA_SELECT_HIT_BYTES"):
         monkeypatch.delenv(v, raising=False)
     g = AC.compile(keys, fold_ascii=fold)
     monkeypatch.setenv("AHA_DOCCOUNT_HIT_BYTES", "4096")  # (read when the handle is compiled: ranges of ~340 hits)
     g_dc = AC.compile(keys, fold_ascii=fold)
     monkeypatch.delenv("AHA_DOCCOUNT_HIT_BYTES")
+    monkeypatch.setenv("AHA_SELECT_HIT_BYTES", "4096")  # (the same for select and replace calls)
+    g_sel = AC.compile(keys, fold_ascii=fold)
+    monkeypatch.delenv("AHA_SELECT_HIT_BYTES")
     K = len(keys)
+    repl = _alloc_repl(keys)
+    tables, feeds = {}, {}
+
+    def table_of(h):
+        if id(h) not in tables:
+            tables[id(h)] = h.replacements(repl)
+        return tables[id(h)]
+
+    def feed_of(h, sep=False):
+        """a feed of the handle with a sequence per document of the larger batch, every sequence at length 0: document d is
+        the first piece of sequence d, so the call is the same call every time.  What a Feed owns (its sequences' contexts,
+        tails, cursors and open records: feed.cpp) is not the handle's scratch; what a feed call builds its answer in --
+        fselbuf, frepbuf, fsepbuf, fgrpbuf and the families' own buffers -- is, and falls under the contract."""
+        if (id(h), sep) not in feeds:
+            b = None
+            if sep:
+                b = BitArray(256)
+                for x in ALLOC_SEP:
+                    b[x] = True
+            feeds[(id(h), sep)] = h.feed(texts[0].D, sep=b)
+        f = feeds[(id(h), sep)]
+        f.reset()
+        return f
+
+    def ids_of(t):
+        return torch.arange(t.D, dtype=torch.int32, device="cuda")
+
+    def rows(n, width):
+        return torch.full((n + PAD, width), S32, dtype=torch.int32, device="cuda")
+
+    def raw(n):
+        return torch.full((n + PAD,), 0x5A, dtype=torch.uint8, device="cuda")
+
+    def check_raw(buf, n, want):
+        got = buf.cpu().numpy()
+        assert n == want.size and got[:n].tobytes() == want.tobytes() and (got[n:] == 0x5A).all()
+
+    def zeros_then_sentinels(buf, D):
+        got = buf.cpu().numpy()
+        assert not got[:D].any() and (got[D:] == S64 - (1 << 64)).all()
 
     def i64(a):
         return a.cpu().numpy().astype(np.uint64)
@@ -750,6 +723,99 @@ def test_scratch_only_grows_in_every_call_family(fold, monkeypatch):
         if with_mask:
             assert np.array_equal(mask.cpu().numpy().view(np.uint32), a.mask)
 
+    def dev_select(h, t, a):
+        out, dso = rows(len(a.sel), 3), _dho_dev(t.D)
+        torch.cuda.synchronize()
+        n, nh = h.select_batch_device(t.dev()[0], t.dev()[1], out, dso, cap=len(a.sel))
+        assert nh == len(a.hits)
+        _check_dev(out, n, a.sel, n)
+        _check_dho(dso, t.D, a.dso)
+
+    def dev_replace(h, t, a):
+        out, doo = raw(a.rep.size), _dho_dev(t.D)
+        torch.cuda.synchronize()
+        n, ns, nh = h.replace_batch_device(t.dev()[0], t.dev()[1], table_of(h), out, doo, cap=a.rep.size)
+        assert (ns, nh) == (len(a.sel), len(a.hits))
+        check_raw(out, n, a.rep)
+        _check_dho(doo, t.D, a.doo)
+
+    def dev_records(h, t, a):
+        R = a.rec.size - 1
+        rec, dro = _dho_dev(R), _dho_dev(t.D)
+        torch.cuda.synchronize()
+        assert h.records_device(t.dev()[0], t.dev()[1], rec, dro, cap=R) == R
+        _check_dho(rec, R, a.rec)
+        _check_dho(dro, t.D, a.dro)
+
+    def dev_grep(h, t, a):
+        nk = a.kept.size
+        kept, doo, out = _dho_dev(nk - 1), _dho_dev(nk), raw(a.kept_out.size)
+        torch.cuda.synchronize()
+        got = h.grep_batch_device(t.dev()[0], t.dev()[1], kept, doo, out, cap_docs=nk, cap_bytes=a.kept_out.size)
+        assert got == (nk, a.kept_out.size, len(a.hits))
+        _check_dho(kept, nk - 1, a.kept)
+        _check_dho(doo, nk, a.kept_doo)
+        check_raw(out, got[1], a.kept_out)
+
+    def host_select(h, t, a):
+        sel, dso = h.select_batch(t.corpus, t.offs)
+        assert sel.tobytes() == a.sel.tobytes() and np.array_equal(dso, a.dso)
+
+    def host_replace(h, t, a):
+        out, doo = h.replace_batch(t.corpus, t.offs, table_of(h))
+        assert out.tobytes() == a.rep.tobytes() and np.array_equal(doo, a.doo)
+
+    def host_records(h, t, a):
+        rec, dro = h.records(t.corpus, t.offs)
+        assert np.array_equal(rec, a.rec) and np.array_equal(dro, a.dro)
+
+    def host_grep(h, t, a):
+        kept, out, doo = h.grep_batch(t.corpus, t.offs)
+        assert np.array_equal(kept, a.kept) and out.tobytes() == a.kept_out.tobytes() and np.array_equal(doo, a.kept_doo)
+
+    def feed_match(h, t, a, sep=False):
+        f = feed_of(h, sep)
+        want, want_pho = (a.sep_hits, a.sep_pho) if sep else (a.hits, a.dho)
+        out, pho, bases = rows(len(want), 3), _dho_dev(t.D), _dho_dev(t.D - 1)
+        torch.cuda.synchronize()
+        n = f.match_batch_device(t.dev()[0], t.dev()[1], ids_of(t), out[:len(want)], pho, bases)
+        _check_dev(out, n, want, n)
+        _check_dho(pho, t.D, want_pho)
+        zeros_then_sentinels(bases, t.D)
+
+    def feed_select(h, t, a):
+        f = feed_of(h)
+        out, pso, bases = rows(len(a.sel), 3), _dho_dev(t.D), _dho_dev(t.D - 1)
+        torch.cuda.synchronize()
+        n, nh = f.select_batch_device(t.dev()[0], t.dev()[1], ids_of(t), out, pso, bases, final=True, cap=len(a.sel))
+        _check_dev(out, n, a.sel, n)
+        _check_dho(pso, t.D, a.dso)
+        zeros_then_sentinels(bases, t.D)
+
+    def feed_replace(h, t, a):
+        f = feed_of(h)
+        out, poo, bases = raw(a.rep.size), _dho_dev(t.D), _dho_dev(t.D - 1)
+        torch.cuda.synchronize()
+        n, ns, nh = f.replace_batch_device(t.dev()[0], t.dev()[1], ids_of(t), table_of(h), out, poo, bases, final=True,
+                                           cap=a.rep.size)
+        assert ns == len(a.sel)
+        check_raw(out, n, a.rep)
+        _check_dho(poo, t.D, a.doo)
+        zeros_then_sentinels(bases, t.D)
+
+    def feed_grep(h, t, a):
+        # (no document of this batch holds a line feed or is empty: under FINAL every piece is one record that closes)
+        f = feed_of(h)
+        nk = a.kept.size
+        kept, roo, out = _dho_dev(nk - 1), _dho_dev(nk), raw(a.kept_out.size)
+        torch.cuda.synchronize()
+        got = f.grep_batch_device(t.dev()[0], t.dev()[1], ids_of(t), kept, roo, out, final=True, cap_recs=nk,
+                                  cap_bytes=a.kept_out.size)
+        assert got[:3] == (t.D, nk, a.kept_out.size), got
+        _check_dho(kept, nk - 1, a.kept)
+        _check_dho(roo, nk, a.kept_doo)
+        check_raw(out, got[2], a.kept_out)
+
     def host_match_count(h, t, a):
         hits, dho = h.match_batch(t.corpus, t.offs, cap=len(a.hits) + 37)
         assert hits.tobytes() == a.hits.tobytes() and np.array_equal(dho, a.dho)
@@ -774,9 +840,11 @@ def test_scratch_only_grows_in_every_call_family(fold, monkeypatch):
         dev_match(h, t, a, views[id(t)])
 
     # the kinds named after document ranges must take them: aha_timing.repeats counts a call's ranges before its last
-    in_ranges = {"count in document ranges", "doc counts, small hit buffer"}
+    in_ranges = {"count in document ranges", "doc counts, small hit buffer", "select in document ranges",
+                 "replace in document ranges"}
     g.set_profiling(True)
     g_dc.set_profiling(True)
+    g_sel.set_profiling(True)
     kinds = [
         ("device match", g, dev_match),
         ("device match, unaligned view", g, dev_match_unaligned),
@@ -789,7 +857,25 @@ def test_scratch_only_grows_in_every_call_family(fold, monkeypatch):
         ("host match and count", g, host_match_count),
         ("host doc counts", g, host_doc_counts),
         ("host cover", g, host_cover),
+        ("select", g, dev_select),
+        ("select in document ranges", g_sel, dev_select),
+        ("replace", g, dev_replace),
+        ("replace in document ranges", g_sel, dev_replace),
+        ("records", g, dev_records),
+        ("grep", g, dev_grep),
+        ("host select", g, host_select),
+        ("host replace", g, host_replace),
+        ("host records", g, host_records),
+        ("host grep", g, host_grep),
+        ("feed match", g, feed_match),
+        ("feed select", g, feed_select),
+        ("feed replace", g, feed_replace),
+        ("feed grep", g, feed_grep),
+        ("feed match, separator filter", g, lambda h, t, a: feed_match(h, t, a, sep=True)),
     ]
+    # the feed kinds whose window batch is matched into the feed's own grow-only hit buffer (feed_windows with hits); a feed
+    # grep counts its windows and keeps the strict rule
+    windows_with_hits = {"feed match", "feed select", "feed replace", "feed match, separator filter"}
     (big, small), (a_big, a_small) = texts, answers
     assert len(a_big.hits) > 2 * big.D and len(a_small.hits) > 0
     for name, h, call in kinds:
@@ -803,7 +889,14 @@ def test_scratch_only_grows_in_every_call_family(fold, monkeypatch):
             call(h, big, a_big)
             assert h.scratch_bytes() == grown, "a second identical call allocated"
             call(h, small, a_small)
-            assert h.scratch_bytes() == grown, "a smaller batch allocated"
+            if name in windows_with_hits:
+                settled = h.scratch_bytes()
+                assert settled >= grown
+                call(h, small, a_small)
+                call(h, big, a_big)
+                assert h.scratch_bytes() == settled, "the buffers did not settle"
+            else:
+                assert h.scratch_bytes() == grown, "a smaller batch allocated"
             h.release_scratch()
             assert h.scratch_bytes() == 0
             call(h, big, a_big)
