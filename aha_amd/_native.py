@@ -171,6 +171,11 @@ SIGNATURES = {
                                  C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
     "aha_ac_grep_batch_device": (_i32, [_vp, _vp, _vp, _u64, _u64, C.POINTER(aha_match_params), _u32, _vp, _vp, _u64, _vp, _u64,
                                         C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), _vp]),
+    "aha_classes_create": (_i32, [_vp, _vp, _vp, _u32, C.POINTER(_vp)]),
+    "aha_classes_free": (None, [_vp]),
+    "aha_ac_class_counts_batch": (_i32, [_vp, _vp, _vp, _vp, _u64, C.POINTER(aha_match_params), _u32, _vp, C.POINTER(_u64)]),
+    "aha_ac_class_counts_batch_device": (_i32, [_vp, _vp, _vp, _vp, _u64, _u64, C.POINTER(aha_match_params), _u32, _vp,
+                                                C.POINTER(_u64), _vp]),
     "aha_ac_count_batch": (_i32, [_vp, _vp, _vp, _u64, C.POINTER(aha_match_params), _u32, _vp, _vp, C.POINTER(_u64)]),
     "aha_ac_count_batch_device": (_i32, [_vp, _vp, _vp, _u64, _u64, C.POINTER(aha_match_params), _u32, _vp, _vp,
                                          C.POINTER(_u64), _vp]),

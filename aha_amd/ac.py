@@ -167,6 +167,23 @@ class ReplTable:
                 pass
 
 
+class Classes:
+    """A class table of one handle (aha_classes_create): per key its classes, validated and uploaded once, immutable, freed
+    with the object.  Made by AC.classes.  n_classes = C; names: the class names in column order where the spec gave
+    names, else None."""
+
+    def __init__(self, handle, n_keys, n_classes, names=None):
+        self._h, self.n_keys, self.n_classes, self.names = handle, n_keys, n_classes, names
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                N.lib().aha_classes_free(h)
+            except Exception:  # interpreter shutdown
+                pass
+
+
 def _pack_replacements(repl, n_keys):
     """repl as substitute takes it -> (blob uint8, offsets uint64[K+1], keep bits uint32[ceil(K/32)])"""
     parts, keep = [], np.zeros((n_keys + 31) // 32, dtype=np.uint32)
@@ -849,6 +866,99 @@ class AC:
         self._check(rc)
         return (out.download(np.zeros(cap, dtype=np.uint8)), doo.download(np.zeros(D + 1, dtype=np.uint64)), int(ns.value),
                 int(nh.value))
+
+    # -- class counts: hits per key class within each document, dense (aha_ac_class_counts_batch*) ----------
+    def classes(self, spec, n_classes=None):
+        """A Classes table of this handle from spec:
+        a sequence of K items, one per key -- None (no class), an int, or a sequence of ints;
+        or a mapping {class: iterable of keys} where a class is an int id or a name (names become the columns in the mapping's
+        order, kept as Classes.names) and a key is its index or its spelling (bytes / str).
+        n_classes: C where it is more than the largest id + 1."""
+        K = self.n_keys
+        per_key = [set() for _ in range(K)]
+        names = None
+        if hasattr(spec, "keys"):
+            labels = list(spec.keys())
+            by_name = not all(isinstance(c, (int, np.integer)) and not isinstance(c, bool) for c in labels)
+            if by_name:
+                names = labels
+            for col, label in enumerate(labels):
+                c = col if by_name else int(label)
+                for key in spec[label]:
+                    k = int(key) if isinstance(key, (int, np.integer)) else self[key]
+                    if not 0 <= k < K:
+                        raise ValueError("the class table names key %r; the handle has %d keys" % (key, K))
+                    per_key[k].add(c)
+        else:
+            if len(spec) != K:
+                raise ValueError("the class table must have one entry per key (%d), or be a mapping from class to keys" % K)
+            for k, item in enumerate(spec):
+                if item is None:
+                    continue
+                per_key[k].update([int(item)] if isinstance(item, (int, np.integer)) else [int(c) for c in item])
+        top = max((max(cs) for cs in per_key if cs), default=-1)
+        low = min((min(cs) for cs in per_key if cs), default=0)
+        if low < 0:
+            raise ValueError("class ids are not negative")
+        C_ = max(top + 1, len(names) if names else 0, 1) if n_classes is None else int(n_classes)
+        offs = np.zeros(K + 1, dtype=np.uint64)
+        offs[1:] = np.cumsum([len(cs) for cs in per_key])
+        ids = np.array([c for cs in per_key for c in sorted(cs)], dtype=np.uint32)
+        h = C.c_void_p()
+        self._check(N.lib().aha_classes_create(self._h, _ptr(ids), _ptr(offs), C_, C.byref(h)))
+        return Classes(h, K, C_, names)
+
+    def _classes(self, classes):
+        return classes if isinstance(classes, Classes) else self.classes(classes)
+
+    def class_counts_batch(self, corpus, doc_offsets, classes, sep=None):
+        """Per document the hits of match_batch(corpus, doc_offsets, sep) counted by key class: -> uint32 array of shape
+        (D, C); entry [d, c] = the hits of document d whose key is in class c (a key in several classes counts in each)."""
+        if isinstance(corpus, (bytes, bytearray)):
+            corpus = np.frombuffer(bytes(corpus), dtype=np.uint8)
+        corpus = np.ascontiguousarray(corpus, dtype=np.uint8)
+        doc_offsets = np.ascontiguousarray(doc_offsets, dtype=np.uint64)
+        table = self._classes(classes)
+        D = doc_offsets.size - 1
+        p = _params(False, sep)
+        out = np.zeros((D, table.n_classes), dtype=np.uint32)
+        self._check(N.lib().aha_ac_class_counts_batch(self._h, table._h, _ptr(corpus), _ptr(doc_offsets), D, C.byref(p), 0,
+                                                      _ptr(out), None))
+        return out
+
+    def class_counts(self, seq, classes, sep=None):
+        """The hits of match(seq, sep) counted by key class: -> uint32[C]."""
+        b = _b(seq)
+        return self.class_counts_batch(np.frombuffer(b, dtype=np.uint8), np.array([0, len(b)], dtype=np.uint64), classes, sep=sep)[0]
+
+    def class_counts_batch_device(self, corpus, doc_offsets, classes, out, sep=None, stream=None):
+        """Device-resident class counts on torch CUDA tensors: uint8 corpus, int64/uint64 doc offsets, out a contiguous int32
+        tensor of shape (D, C), every entry of which is written (as uint32).  -> n_hits."""
+        import torch
+
+        assert corpus.is_cuda and corpus.dtype == torch.uint8 and corpus.is_contiguous()
+        assert doc_offsets.is_cuda and doc_offsets.dtype in (torch.int64, torch.uint64)
+        D = doc_offsets.numel() - 1
+        if not (out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (D, classes.n_classes)):
+            raise ValueError("out must be a contiguous int32 CUDA tensor of shape (D, C) = (%d, %d)" % (D, classes.n_classes))
+        p = _params(False, sep)
+        nh = C.c_uint64(0)
+        s = stream if stream is not None else torch.cuda.current_stream(corpus.device).cuda_stream
+        self._check(N.lib().aha_ac_class_counts_batch_device(
+            self._h, classes._h, corpus.data_ptr(), doc_offsets.data_ptr(), D, corpus.numel(), C.byref(p), 0,
+            out.data_ptr() if D else None, C.byref(nh), C.c_void_p(s)))
+        return int(nh.value)
+
+    def class_counts_corpus(self, corpus, classes, sep=None):
+        """The class counts of a batch that already lives in HBM (DeviceCorpus), downloaded: -> (uint32 (D, C), n_hits)."""
+        table = self._classes(classes)
+        D, C_ = corpus.n_docs, table.n_classes
+        p = _params(False, sep)
+        out = DeviceBuffer(corpus.device, max(D * C_ * 4, 4))
+        nh = C.c_uint64(0)
+        self._check(N.lib().aha_ac_class_counts_batch_device(self._h, table._h, corpus.ptr, corpus.doc_ptr, D, corpus.n_bytes,
+                                                             C.byref(p), 0, out.ptr, C.byref(nh), None))
+        return out.download(np.zeros((D, C_), dtype=np.uint32)), int(nh.value)
 
     # -- records and grep: split a batch into records, keep those with a hit (aha_ac_records_batch*, aha_ac_grep_batch*) ----
     def records(self, corpus, doc_offsets=None, delim=b"\n"):

@@ -1582,6 +1582,117 @@ int32_t aha_ac_replace_batch(aha_ac *ac, const aha_repl *table, const uint8_t *c
   return AHA_OK;
 }
 
+// ---- class counts (aha_classes_*, aha_ac_class_counts_batch*) --------------------------------------------------------
+// A table is validated and uploaded once.  On a host-only handle it is made all the same, with a host copy only, so that the
+// entries' argument checks hold there; they answer AHA_E_NO_DEVICE then.
+int32_t aha_classes_create(aha_ac *ac, const uint32_t *class_ids, const uint64_t *offsets, uint32_t n_classes, aha_classes **out) {
+  if (out) *out = nullptr;
+  if (!ac || !offsets || !out) return AHA_E_INVALID;
+  if (n_classes == 0 || n_classes > 65536u) return AHA_E_INVALID;
+  const uint32_t K = ac->aut.n_keys;
+  if (offsets[0] != 0) return AHA_E_INVALID;
+  for (uint32_t k = 0; k < K; k++)
+    if (offsets[k + 1] < offsets[k]) return AHA_E_INVALID;
+  if (offsets[K] && !class_ids) return AHA_E_INVALID;
+  for (uint32_t k = 0; k < K; k++)
+    for (uint64_t j = offsets[k]; j < offsets[k + 1]; j++) {
+      if (class_ids[j] >= n_classes) return AHA_E_INVALID;
+      if (j > offsets[k] && class_ids[j] <= class_ids[j - 1]) return AHA_E_INVALID;  // (a class at most once per key)
+    }
+  std::unique_ptr<aha_classes> t(new (std::nothrow) aha_classes());
+  if (!t) return AHA_E_NOMEM;
+  try {
+    t->off.assign(offsets, offsets + K + 1);
+    if (offsets[K]) t->ids.assign(class_ids, class_ids + offsets[K]);
+  } catch (...) {
+    return AHA_E_NOMEM;
+  }
+  t->owner = ac->serial;
+  t->n_keys = K;
+  t->n_classes = n_classes;
+  if (ac->device >= 0) {
+    DeviceGuard g(ac->device);
+    t->device = ac->device;
+    hipStream_t st = nullptr;
+    int32_t rc = copy_stream(ac->device, &st);
+    if (rc) return rc;
+    hipError_t e = hipMalloc((void **)&t->d_off, t->off.size() * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&t->d_ids, std::max<size_t>(t->ids.size(), 1) * 4);
+    if (e == hipSuccess) e = hipMemcpyAsync(t->d_off, t->off.data(), t->off.size() * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && !t->ids.empty()) e = hipMemcpyAsync(t->d_ids, t->ids.data(), t->ids.size() * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      tls_err = std::string("aha_classes_create: ") + hipGetErrorString(e);
+      aha_classes_free(t.release());
+      return AHA_E_HIP;
+    }
+  }
+  *out = t.release();
+  return AHA_OK;
+}
+
+void aha_classes_free(aha_classes *t) {
+  if (!t) return;
+  if (t->device >= 0) {
+    DeviceGuard g(t->device);
+    if (t->d_off) (void)hipFree(t->d_off);
+    if (t->d_ids) (void)hipFree(t->d_ids);
+  }
+  delete t;
+}
+
+// the argument checks both entries share: before any device work, so they hold on a host-only handle
+static int32_t class_counts_args(aha_ac *ac, const aha_classes *table, const uint64_t *doc_offsets, uint64_t n_docs,
+                                 const aha_match_params *params, uint32_t flags, const uint32_t *out) {
+  if (!ac || !table || !doc_offsets || flags) return AHA_E_INVALID;
+  if (table->owner != ac->serial) {
+    tls_err = "the class table was made for another handle";
+    return AHA_E_INVALID;
+  }
+  if (int32_t rc = no_longest_form(ac, params, "class counts have no match_longest form")) return rc;
+  if (params && params->struct_size >= offsetof(aha_match_params, char_offsets) + sizeof(params->char_offsets) && params->char_offsets) {
+    tls_err = "class counts take byte offsets only";
+    return AHA_E_INVALID;
+  }
+  if (n_docs && !out) return AHA_E_INVALID;
+  if (ac->device < 0) return no_device();
+  return AHA_OK;
+}
+
+int32_t aha_ac_class_counts_batch_device(aha_ac *ac, const aha_classes *table, const uint8_t *d_corpus, const uint64_t *d_doc_offsets,
+                                         uint64_t n_docs, uint64_t n_bytes, const aha_match_params *params, uint32_t flags,
+                                         uint32_t *d_out, uint64_t *n_hits, void *stream) {
+  int32_t rc = class_counts_args(ac, table, d_doc_offsets, n_docs, params, flags, d_out);
+  if (rc) return rc;
+  Lease lease(ac);
+  return device_class_counts(ac, lease.get(), table, d_corpus, d_doc_offsets, n_docs, n_bytes, params, d_out, n_hits, stream, false);
+}
+
+// The host entry: the batch goes up in one piece into the staging buffers of the leased scratch set, over its private stream;
+// the table comes back once the call has succeeded.
+int32_t aha_ac_class_counts_batch(aha_ac *ac, const aha_classes *table, const uint8_t *corpus, const uint64_t *doc_offsets,
+                                  uint64_t n_docs, const aha_match_params *params, uint32_t flags, uint32_t *out, uint64_t *n_hits) {
+  int32_t rc = class_counts_args(ac, table, doc_offsets, n_docs, params, flags, out);
+  if (rc) return rc;
+  if ((rc = check_host_batch(corpus, doc_offsets, n_docs))) return rc;
+  const uint64_t n_bytes = doc_offsets[n_docs], n_out = n_docs * table->n_classes;
+  DeviceGuard g(ac->device);
+  Lease lease(ac);
+  Scratch *sc = lease.get();
+  HostBatch B;
+  if ((rc = stage_host_batch(ac, sc, corpus, doc_offsets, n_docs, 0, n_out * 4, B))) return rc;
+  uint32_t *d_out = (uint32_t *)B.d_per_call;
+  hipStream_t s = B.s;
+  uint64_t nh = 0;
+  rc = device_class_counts(ac, sc, table, B.d_corpus, B.d_doc, n_docs, n_bytes, params, d_out, &nh, s,
+                           true);  // the offsets were checked on the host above
+  if (rc != AHA_OK) return rc;
+  if (n_out) HIPCHK(ac, hipMemcpyAsync(out, d_out, n_out * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  if (n_hits) *n_hits = nh;
+  return AHA_OK;
+}
 
 // ---- records and grep calls (aha_ac_records_batch*, aha_ac_grep_batch*) ------------------------------------------------
 // the argument checks both records entries share: before any device work, so they hold on a host-only handle

@@ -3,6 +3,7 @@
 // passes of a device-resident batch (device_match: the prefix filter's back-off, the repeat with larger regions, the hand-over
 // to the two-pass engine).  The C ABI around it is capi.cpp; what they share is handle.hpp.
 #include "handle.hpp"
+#include "class_overflow.hpp"
 
 #include <chrono>
 
@@ -88,6 +89,10 @@ static void doccount_setup(aha_ac *ac) {
   ac->rep_blocks = (uint32_t)env("AHA_REPLACE_BLOCKS", 0, 1, 1u << 20);
   // records and grep calls: the cap of their grids, the reused rank, scan and copy launches included
   ac->grep_blocks = (uint32_t)env("AHA_GREP_BLOCKS", 0, 1, 1u << 20);
+  // class-counts calls: the bound of a range's hit buffer, by default the document counts', and the cap of their kernels' grids
+  // (tests: a few hits, so that a batch takes several ranges or a document goes through its key counts; 1 block)
+  ac->cls_hit_bytes = env("AHA_CLASS_HIT_BYTES", ac->dc_hit_bytes, 12, kV2MaxRegionBytes);
+  ac->cls_blocks = (uint32_t)env("AHA_CLASS_BLOCKS", 0, 1, 1u << 20);
 }
 
 void v2_setup(aha_ac *ac) {
@@ -1895,6 +1900,166 @@ int32_t device_grep(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint
   if (!fits) {
     tls_err = "output buffer too small";
     return AHA_E_CAPACITY;
+  }
+  return AHA_OK;
+}
+
+// ---- class counts (aha_ac_class_counts_batch*) -----------------------------------------------------------------------
+uint32_t class_grid(const aha_ac *ac) { return ac->cls_blocks ? ac->cls_blocks : 8u * std::max<uint32_t>(ac->v2_grid, 64u); }
+static void *cls_reserve(Scratch *sc, ClassSlot slot, size_t bytes) { return reserve_ptr(sc->clsbuf[slot], bytes, kGrowEighth); }
+
+// One device-resident batch as hits per (document, key class) (aha_ac_class_counts_batch_device): d_out[D][C], every entry written.
+//   1. device_count without key counts: the hits per document and their total (and the offsets' validation).  A call with 2^32
+//      hits or more is checked for a document that could overflow a uint32 (class_overflow.hpp) before d_out is touched.
+//   2. d_out is cleared on the call's stream.
+//   3. Ranges of whole documents whose hits fit the bound of the hit buffer (one range, as a rule): a match of the range with
+//      cap = its hits into the call's scratch -- every engine, the handle's back-off state read and never written --, then
+//      kcc_add over the hit list (scan_classcount.hip).  A single document beyond the bound is never matched: a count call over
+//      it alone gives its key counts, which kcc_fold_keys adds into its row through the table.
+int32_t device_class_counts(aha_ac *ac, Scratch *sc, const aha_classes *table, const uint8_t *d_corpus, const uint64_t *d_doc_offsets,
+                            uint64_t n_docs, uint64_t n_bytes, const aha_match_params *params, uint32_t *d_out, uint64_t *n_hits_out,
+                            void *stream, bool offsets_checked) {
+  if (!ac || !table || !d_doc_offsets) return AHA_E_INVALID;
+  if (ac->device < 0 || !table->d_off) return no_device();
+  if (n_docs && !d_out) return AHA_E_INVALID;
+  DeviceGuard g(ac->device);
+  hipStream_t s = (hipStream_t)stream;
+  const uint64_t D = n_docs, C = table->n_classes;
+  const uint32_t K = ac->aut.n_keys;
+  if (n_hits_out) *n_hits_out = 0;
+  auto nomem = [&]() {
+    tls_err = "hipMalloc failed for the scratch of a class-counts call";
+    return AHA_E_HIP;
+  };
+  int32_t rc;
+  uint64_t *d_dho = (uint64_t *)cls_reserve(sc, kClsHitOff, (D + 1) * 8);
+  if (!d_dho) return nomem();
+  uint64_t n_hits = 0;
+  if ((rc = device_count(ac, sc, d_corpus, d_doc_offsets, D, n_bytes, params, 0, nullptr, d_dho, &n_hits, stream, offsets_checked)))
+    return rc;
+  const auto t_all0 = std::chrono::steady_clock::now();
+  double ms_match = 0.0;
+  aha_timing t_trav;  // the timing of a pass that traversed (profiling)
+  memset(&t_trav, 0, sizeof(t_trav));
+  if (ac->profiling.load()) {
+    std::lock_guard<std::mutex> lk(ac->last_mu);
+    t_trav = ac->last;
+  }
+  // the ranges {d0, d1, solo}: one where all hits fit the bound (the hit offsets stay on the device then)
+  struct Range {
+    uint64_t d0, d1;
+    bool solo;
+  };
+  std::vector<Range> ranges;
+  std::vector<uint64_t> off, hd, rel;
+  const uint64_t bound = ac->cls_hit_bytes;
+  try {
+    if (n_hits && n_hits <= bound / sizeof(aha_hit) && n_hits < (1ull << 32)) {  // (2^32 hits: the documents are looked at)
+      ranges.push_back(Range{0, D, false});
+    } else if (n_hits) {
+      hd.resize(D + 1);
+      off.resize(D + 1);
+      HIPCHK(ac, hipMemcpyAsync(hd.data(), d_dho, (D + 1) * 8, hipMemcpyDeviceToHost, s));
+      HIPCHK(ac, hipMemcpyAsync(off.data(), d_doc_offsets, (D + 1) * 8, hipMemcpyDeviceToHost, s));
+      HIPCHK(ac, hipStreamSynchronize(s));
+      uint64_t bad = 0;
+      if (class_counts_overflow(hd.data(), D, &bad)) {
+        tls_err = "class counts: document " + std::to_string(bad) + " has 2^32 hits or more";
+        return AHA_E_TOO_LONG;
+      }
+      // a range starts at a document with hits; the hitless documents behind its last one come with it
+      for (uint64_t d0 = 0; d0 < D;) {
+        if (hd[d0 + 1] == hd[d0]) {
+          d0++;
+          continue;
+        }
+        uint64_t d1 = d0 + 1, bytes = (hd[d0 + 1] - hd[d0]) * sizeof(aha_hit);
+        const bool solo = bytes > bound;
+        while (!solo && d1 < D && bytes + (hd[d1 + 1] - hd[d1]) * sizeof(aha_hit) <= bound) {
+          bytes += (hd[d1 + 1] - hd[d1]) * sizeof(aha_hit);
+          d1++;
+        }
+        ranges.push_back(Range{d0, d1, solo});
+        d0 = d1;
+      }
+    }
+  } catch (...) {
+    return AHA_E_NOMEM;
+  }
+  if (D) HIPCHK(ac, hipMemsetAsync(d_out, 0, D * C * 4, s));
+  const uint32_t blocks = class_grid(ac);
+  bool first_match = true;
+  for (size_t r = 0; r < ranges.size(); r++) {
+    const uint64_t d0 = ranges[r].d0, d1 = ranges[r].d1, nd = d1 - d0;
+    // the range as a batch of its own: the caller's arrays where it is the whole batch
+    const uint8_t *text = d_corpus;
+    const uint64_t *d_rel = d_doc_offsets;
+    uint64_t nb = n_bytes, rh = n_hits;
+    if (d0 != 0 || d1 != D) {
+      nb = off[d1] - off[d0];
+      rh = hd[d1] - hd[d0];
+      try {
+        rel.resize(nd + 1);
+      } catch (...) {
+        return AHA_E_NOMEM;
+      }
+      for (uint64_t d = 0; d <= nd; d++) rel[d] = off[d0 + d] - off[d0];
+      uint64_t *rr = (uint64_t *)cls_reserve(sc, kClsRel, (nd + 1) * 8);
+      if (!rr) return nomem();
+      HIPCHK(ac, hipMemcpyAsync(rr, rel.data(), (nd + 1) * 8, hipMemcpyHostToDevice, s));
+      d_rel = rr;
+      text = d_corpus + off[d0];
+      // (the kernels read aligned 16-byte pieces; a folded handle's match and count make their own folded -- and aligned -- copy)
+      if (!ac->fold() && reinterpret_cast<uintptr_t>(text) % 16 != 0) {
+        void *t = cls_reserve(sc, kClsText, nb + 64);
+        if (!t) return nomem();
+        if ((rc = stage_text(ac, &text, nb, t, false, s))) return rc;
+      }
+      HIPCHK(ac, hipStreamSynchronize(s));  // (rel is the host's until the copy has run)
+    }
+    const auto t_m0 = std::chrono::steady_clock::now();
+    uint64_t got = 0;
+    if (ranges[r].solo) {
+      uint64_t *row = (uint64_t *)cls_reserve(sc, kClsSoloRow, std::max<uint64_t>(K, 1) * 8);
+      if (!row) return nomem();
+      if ((rc = device_count(ac, sc, text, d_rel, nd, nb, params, 0, row, nullptr, &got, stream, true))) return rc;
+      ms_match += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_m0).count();
+      if (got != rh) {
+        tls_err = "class counts: the two counts of a document disagree";
+        return AHA_E_HIP;
+      }
+      classcount_launch_fold_keys(row, K, table->d_off, table->d_ids, d_out + d0 * C, blocks, s);
+    } else {
+      aha_hit *d_hits = (aha_hit *)cls_reserve(sc, kClsHits, rh * sizeof(aha_hit));
+      if (!d_hits) return nomem();
+      rc = device_match(ac, sc, text, d_rel, nd, nb, params, d_hits, rh, nullptr, &got, stream, true, nullptr, nullptr, false, true);
+      if (rc) return rc;
+      if (got != rh) {
+        tls_err = "class counts: the match and the count of a range disagree";
+        return AHA_E_HIP;
+      }
+      ms_match += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_m0).count();
+      if (ac->profiling.load() && first_match) {
+        std::lock_guard<std::mutex> lk(ac->last_mu);
+        t_trav = ac->last;
+      }
+      first_match = false;
+      classcount_launch_add(d_hits, rh, d_dho + d0, nd, table->d_off, table->d_ids, K, (uint32_t)C, d_out + d0 * C, blocks, s);
+    }
+    HIPCHK(ac, hipGetLastError());
+    if (r + 1 < ranges.size()) HIPCHK(ac, hipStreamSynchronize(s));  // (the next range takes the scratch)
+  }
+  HIPCHK(ac, hipStreamSynchronize(s));
+  if (n_hits_out) *n_hits_out = n_hits;
+  if (ac->profiling.load()) {
+    // the engine that traversed, the call's hits; ms_write = everything after the match (the call from its first range on, less
+    // its matches); repeats = the ranges before the last
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_all0).count();
+    t_trav.struct_size = sizeof(t_trav);
+    t_trav.n_hits = n_hits;
+    t_trav.ms_write = (float)std::max(0.0, ms - ms_match);
+    t_trav.repeats = ranges.empty() ? 0 : (uint32_t)(ranges.size() - 1);
+    publish_timing(ac, t_trav);
   }
   return AHA_OK;
 }

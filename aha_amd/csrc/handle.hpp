@@ -186,6 +186,15 @@ enum FeedGrepSlot {
   kFgTable,       // the one-entry replacement table (the empty replacement)
   kFgCount
 };
+// clsbuf: class-counts calls (engine.cpp device_class_counts; scan_classcount.hip)
+enum ClassSlot {
+  kClsHitOff,   // the documents' hit offsets (the count call in front)
+  kClsHits,     // the hits of the range in flight, 12 bytes each
+  kClsRel,      // the range's document offsets, relative to its first byte
+  kClsText,     // the aligned copy of an unaligned range
+  kClsSoloRow,  // one document's key counts (a document beyond the hit buffer's bound)
+  kClsCount
+};
 // Device scratch of ONE match call (grow-only, reused by later calls that lease the same set).
 struct Scratch {
   std::mutex mu;  // held by the call that leased the set
@@ -207,6 +216,7 @@ struct Scratch {
   Buf fsepbuf[kFpCount];
   Buf grpbuf[kGrpCount];
   Buf fgrpbuf[kFgCount];
+  Buf clsbuf[kClsCount];
   // every family above, for free_scratch and scratch_bytes (S: Scratch or const Scratch): a new family is one more line here
   template <class S, class Fn>
   static void each_buf(S &sc, Fn fn) {
@@ -222,6 +232,7 @@ struct Scratch {
     for (auto &b : sc.fsepbuf) fn(b);
     for (auto &b : sc.grpbuf) fn(b);
     for (auto &b : sc.fgrpbuf) fn(b);
+    for (auto &b : sc.clsbuf) fn(b);
   }
   bool dc_rows_clear = false;  // every word of dcbuf[kDcRows] is zero (kdc_compact clears what kdc_add wrote; a call that failed may not have)
   hipStream_t hs[3] = {};  // host-buffer entry: private non-blocking streams for upload, match, download
@@ -316,6 +327,8 @@ struct aha_ac {
   uint64_t sel_hit_bytes = 0;  // select calls: the bound of a range's hit buffer (AHA_SELECT_HIT_BYTES)
   uint32_t rep_blocks = 0;  // replace calls: the cap of the scan's and the copy's grids (AHA_REPLACE_BLOCKS; 0: the default)
   uint32_t grep_blocks = 0;  // records and grep calls: the cap of their grids (AHA_GREP_BLOCKS; 0: the default)
+  uint64_t cls_hit_bytes = 0;  // class-counts calls: the bound of a range's hit buffer (AHA_CLASS_HIT_BYTES)
+  uint32_t cls_blocks = 0;  // ... and the cap of their kernels' grids (AHA_CLASS_BLOCKS; 0: the default)
   uint32_t seg2 = 0;  // slots below it: the root's and the depth-1 states' rows
   // match_longest only (cedar_replay.cpp): the states that carry one of Cedar's stale END flags, derived on the first
   // match_longest call (it replays every insert: as long again as the rest of compile); dev_longest = dev + the bitmap
@@ -338,6 +351,18 @@ struct aha_repl {
   std::vector<aha::RepEntry> ent;  // [K]
   void *d_blob = nullptr;
   aha::RepEntry *d_ent = nullptr;
+};
+
+// A class table (aha_classes_create): key k's classes are ids[off[k] .. off[k+1]), strictly ascending and below n_classes.
+// Immutable once made and tied to its handle by that handle's id, as a replacement table is.
+struct aha_classes {
+  uint64_t owner = 0;  // aha_ac::serial of its handle
+  int device = -1;     // -1: host copy only (a host-only handle)
+  uint32_t n_keys = 0, n_classes = 0;
+  std::vector<uint64_t> off;  // [K + 1]
+  std::vector<uint32_t> ids;  // [off[K]]
+  uint64_t *d_off = nullptr;
+  uint32_t *d_ids = nullptr;
 };
 
 namespace ahai {
@@ -394,7 +419,7 @@ uint64_t scratch_bytes(const Scratch *sc);
 // THE allocator of the grow-only buffers: b holds at least `bytes` afterwards, or nothing (the HIP error is returned, the
 // runtime's sticky one cleared).  What a new buffer gets beyond `bytes` is its family's rule:
 enum Grow {
-  kGrowEighth,   // bytes + bytes / 8 + 256 (v2buf, covbuf, selbuf, repbuf, fselbuf, frepbuf, fsepbuf, grpbuf, fgrpbuf)
+  kGrowEighth,   // bytes + bytes / 8 + 256 (v2buf, covbuf, selbuf, repbuf, fselbuf, frepbuf, fsepbuf, grpbuf, fgrpbuf, clsbuf)
   kGrowQuarter,  // bytes + bytes / 4 + 4096 (cntbuf, hostbuf)
   kGrowOrExact   // an eighth, else exactly `bytes`; `bytes` is what it records (dcbuf: what is known to be there)
 };
@@ -537,4 +562,11 @@ int32_t device_grep(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint
                     const aha_match_params *params, uint32_t flags, uint64_t *d_kept_docs, uint64_t *d_doc_out_offsets,
                     uint64_t cap_docs, uint8_t *d_out, uint64_t cap_bytes, uint64_t *n_kept, uint64_t *n_out_bytes, uint64_t *n_hits,
                     void *stream, bool offsets_checked);
+// one device-resident batch as a dense table of hits per (document, key class) (aha_ac_class_counts_batch_device):
+// device_count for the hits per document, the match of every range of whole documents into scratch, one add per (hit, class)
+// into d_out[n_docs][table->n_classes] (scan_classcount.hip)
+int32_t device_class_counts(aha_ac *ac, Scratch *sc, const aha_classes *table, const uint8_t *d_corpus, const uint64_t *d_doc_offsets,
+                            uint64_t n_docs, uint64_t n_bytes, const aha_match_params *params, uint32_t *d_out, uint64_t *n_hits,
+                            void *stream, bool offsets_checked);
+uint32_t class_grid(const aha_ac *ac);  // the cap of the class-counts grids (AHA_CLASS_BLOCKS)
 }  // namespace ahai

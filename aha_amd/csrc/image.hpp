@@ -346,6 +346,19 @@ void grep_launch_emit_docs(const uint32_t *keep, const uint32_t *S, uint64_t n_d
                            const uint64_t *doc_off, const int64_t *shift, uint64_t n_runs, uint64_t *kept_docs, uint64_t *doc_out,
                            uint32_t max_blocks, void *stream);
 
+// class-counts path (scan_classcount.hip; engine.cpp device_class_counts), over one range of whole documents: its n_hits hits in
+// `hits` (hit_off[d] - hit_off[0]: the first hit of document d of its nd), key k's classes cls_ids[cls_off[k] .. cls_off[k+1]),
+// out: the row of the range's first document (n_classes words per document, cleared before the call's first range).
+// Starting values, not tuned ones:
+constexpr uint32_t kCcSlice = 2048;  // consecutive hits one workgroup takes at a time
+constexpr uint32_t kCcTable = 8192;  // words of its LDS table (32 KiB): (documents of a slice) x n_classes beyond it adds to HBM directly
+void classcount_launch_add(const void *hits, uint64_t n_hits, const uint64_t *hit_off, uint64_t nd, const uint64_t *cls_off,
+                           const uint32_t *cls_ids, uint32_t n_keys, uint32_t n_classes, uint32_t *out, uint32_t max_blocks,
+                           void *stream);
+// one document's hits per key (a count call over it alone) added into its row
+void classcount_launch_fold_keys(const uint64_t *key_counts, uint32_t n_keys, const uint64_t *cls_off, const uint32_t *cls_ids,
+                                 uint32_t *row, uint32_t max_blocks, void *stream);
+
 // exchange format of the multi-GPU all-gatherv (kernels.hip): {end, value} pairs <-> Hit triples
 void launch_hits_pack(const int32_t *hits, uint64_t n, int32_t *pairs, void *stream);
 void launch_hits_unpack(const DevAut &A, const int32_t *pairs, uint64_t n, int chars, int32_t *hits, void *stream);

@@ -234,6 +234,14 @@ lib LibAhaHip
                                params : MatchParams*, flags : UInt32, d_kept_docs : UInt64*, d_doc_out_offsets : UInt64*,
                                cap_docs : UInt64, d_out : UInt8*, cap_bytes : UInt64, n_kept : UInt64*, n_out_bytes : UInt64*,
                                n_hits : UInt64*, stream : Void*) : Int32
+  type Classes = Void*
+  fun aha_classes_create(ac : Ac, class_ids : UInt32*, offsets : UInt64*, n_classes : UInt32, out : Classes*) : Int32
+  fun aha_classes_free(table : Classes) : Void
+  fun aha_ac_class_counts_batch(ac : Ac, table : Classes, corpus : UInt8*, doc_offsets : UInt64*, n_docs : UInt64,
+                                params : MatchParams*, flags : UInt32, out : UInt32*, n_hits : UInt64*) : Int32
+  fun aha_ac_class_counts_batch_device(ac : Ac, table : Classes, d_corpus : UInt8*, d_doc_offsets : UInt64*, n_docs : UInt64,
+                                       n_bytes : UInt64, params : MatchParams*, flags : UInt32, d_out : UInt32*, n_hits : UInt64*,
+                                       stream : Void*) : Int32
   # feeds: sequences that arrive in pieces across calls (offsets relative to the piece; FEED_CHARS: in characters)
   type Feed = Void*
   FEED_CHARS = 1_u32

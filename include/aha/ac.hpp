@@ -442,6 +442,80 @@ class AC {
     return lines;
   }
 
+  // A class table of this handle (aha_classes_create): per key its classes -- none, one or several of n_classes --, validated
+  // and uploaded once, immutable, freed with the object (before or after the handle).
+  class Classes {
+   public:
+    Classes() = default;
+    ~Classes() { aha_classes_free(t_); }
+    Classes(Classes &&o) noexcept : t_(o.t_), n_(o.n_) { o.t_ = nullptr; }
+    Classes &operator=(Classes &&o) noexcept {
+      if (this != &o) {
+        aha_classes_free(t_);
+        t_ = o.t_;
+        n_ = o.n_;
+        o.t_ = nullptr;
+      }
+      return *this;
+    }
+    Classes(const Classes &) = delete;
+    Classes &operator=(const Classes &) = delete;
+    const aha_classes *handle() const { return t_; }
+    uint32_t n_classes() const { return n_; }
+
+   private:
+    friend class AC;
+    Classes(aha_classes *t, uint32_t n) : t_(t), n_(n) {}
+    aha_classes *t_ = nullptr;
+    uint32_t n_ = 0;
+  };
+  // per_key: one entry per key, the key's class ids in ascending order (empty: the key counts nowhere)
+  Classes classes(const std::vector<std::vector<uint32_t>> &per_key, uint32_t n_classes) const {
+    const uint32_t K = n_keys();
+    if (per_key.size() != K) throw Error(AHA_E_INVALID, "one class list per key");
+    std::vector<uint32_t> ids;
+    std::vector<uint64_t> offs(K + 1, 0);
+    for (uint32_t k = 0; k < K; k++) {
+      ids.insert(ids.end(), per_key[k].begin(), per_key[k].end());
+      offs[k + 1] = ids.size();
+    }
+    aha_classes *t = nullptr;
+    int32_t rc = aha_classes_create(h_, ids.data(), offs.data(), n_classes, &t);
+    if (rc != AHA_OK) {
+      const char *m = aha_last_error(h_);
+      throw Error(rc, (m && *m) ? m : aha_strerror(rc));
+    }
+    return Classes(t, n_classes);
+  }
+  // The hits of match_batch counted per document and key class, on the device (aha_ac_class_counts_batch): D x C entries,
+  // row-major; entry d * C + c = the hits of document d whose key is in class c (a key in several classes counts in each).
+  // No hit list, no pairs, no capacity: the size is known before the call.  (A batch that already lives in HBM goes through the
+  // C ABI's aha_ac_class_counts_batch_device, which writes the table in place on the caller's stream.)
+  //   auto m = aha::AC::compile({"he", "she", "hers"});
+  //   auto t = m.classes({{0}, {0, 1}, {}}, 2);                        // he: class 0; she: classes 0 and 1; hers: none
+  //   m.class_counts_batch("ushershe", {0, 6, 8}, t)                   // "ushers": she, he, hers; "he": he
+  //     == std::vector<uint32_t>{2, 1, 1, 0};
+  std::vector<uint32_t> class_counts_batch(std::string_view corpus, const std::vector<uint64_t> &doc_offsets, const Classes &table,
+                                           uint64_t *n_hits = nullptr) const {
+    if (doc_offsets.empty()) throw Error(AHA_E_INVALID, "doc_offsets holds D + 1 entries");
+    aha_match_params p{};
+    p.struct_size = sizeof(p);
+    const uint64_t D = doc_offsets.size() - 1;
+    std::vector<uint32_t> out(D * table.n_classes());
+    uint64_t nh = 0;
+    int32_t rc = aha_ac_class_counts_batch(h_, table.handle(), reinterpret_cast<const uint8_t *>(corpus.data()), doc_offsets.data(), D,
+                                           &p, 0, out.data(), &nh);
+    if (rc != AHA_OK) {
+      const char *m = aha_last_error(h_);
+      throw Error(rc, (m && *m) ? m : aha_strerror(rc));
+    }
+    if (n_hits) *n_hits = nh;
+    return out;
+  }
+  std::vector<uint32_t> class_counts(std::string_view seq, const Classes &table) const {
+    return class_counts_batch(seq, {0, seq.size()}, table);
+  }
+
   // Which bytes of the batch lie inside a hit of match_batch, without the hit list (aha_ac_cover_batch): bit j of the batch is
   // word j >> 5, bit j & 31 of what is returned; doc_covered (optional): covered bytes per document.
   std::vector<uint32_t> cover_batch(std::string_view corpus, const std::vector<uint64_t> &doc_offsets,

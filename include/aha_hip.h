@@ -762,6 +762,57 @@ int32_t aha_ac_grep_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uint
                                  uint64_t cap_docs, uint8_t *d_out /* or NULL */, uint64_t cap_bytes, uint64_t *n_kept,
                                  uint64_t *n_out_bytes /* or NULL */, uint64_t *n_hits /* or NULL */, void *stream);
 
+/* Class counts: hits per key CLASS within each document, as a dense table.  The K keys of a handle belong to a few lexicons
+ * (blocklist categories, PII types, topic word lists) and the caller wants one row of C numbers per document -- the feature
+ * matrix of a curation pipeline -- without the hit list, without {key, count} pairs and without a capacity to negotiate: the
+ * size of the result, D x C, is known before the call.
+ * A class table (aha_classes) names for every key k of ONE handle its classes class_ids[offsets[k] .. offsets[k+1]): none,
+ * one or several ("apple" may be a fruit and a company).  aha_classes_create validates and uploads it once; it is immutable
+ * (concurrent calls may share it), tied to its handle by that handle's serial number, and may be freed before or after its
+ * handle; aha_classes_free(NULL) is a no-op.  AHA_E_INVALID with *out left NULL: a NULL handle / offsets / out, offsets[0]
+ * != 0 or descending offsets, n_classes == 0 or n_classes > 65536, a class id >= n_classes, one key's ids not strictly
+ * ascending (no class twice for a key), class_ids == NULL with offsets[K] != 0.  On a host-only handle the table is made
+ * with a host copy only.
+ * The calls take the same batch, params, validation and errors as aha_ac_match_batch / _device.  out holds D x C uint32
+ * entries, row-major, C = the table's n_classes:
+ *   out[d*C + c] = the number of pairs (h, c) where h is a hit aha_ac_match_batch reports for document d with the same params
+ *   on the same handle (a separator filter and AHA_OPT_FOLD_ASCII included) and c is among the classes of h.value.
+ * EVERY entry of out[0 .. D*C) is written -- the rows of empty documents, of documents without a hit, and every row when no
+ * key has a class are zero -- and nothing outside it.  *n_hits (optional) = all hits of the batch.  Two calls give identical
+ * bytes.  The handle's back-off state is read and never written, as in the select call.
+ * params->char_offsets != 0, params->longest != 0, any flag bit (flags is 0), a NULL handle / doc_offsets / table, a table made
+ * for another handle, out == NULL with D > 0: AHA_E_INVALID, before any device work and with every buffer untouched; a
+ * host-only handle: AHA_E_NO_DEVICE.  D = 0 and N = 0 succeed.
+ * Counts are uint32.  A class count of a document is at most that document's hit count (a key names a class at most once), so
+ * a call whose total hit count is below 2^32 cannot overflow; otherwise the documents' hit counts are looked at and a document
+ * with 2^32 hits or more fails the call with AHA_E_TOO_LONG before out is written (aha_amd/csrc/class_overflow.hpp).
+ * Example: keys "he", "she", "hers" with classes {0}, {0, 1}, {} and C = 2 over the documents "ushers" and "he": the hits
+ * are she, he, hers and he, so out = {2, 1, 1, 0}.
+ * Pipeline (aha_amd/csrc/scan_classcount.hip): the count call without key counts (hit offsets per document);
+ * out is cleared; per range of whole documents whose hit list stays below AHA_CLASS_HIT_BYTES (read when the handle is
+ * compiled; one range as a rule) the match into scratch and kcc_add -- a workgroup takes slices of 2048 consecutive hits, sums
+ * a slice in an LDS table of 8192 words where (documents of the slice) x C fits it and flushes the non-zero slots with one
+ * global add each, and adds to HBM directly otherwise.  A single document beyond the bound is never matched: a count call
+ * over it alone gives its key counts, which go into its row through the table.  Integer adds only: no order shows.
+ * Device scratch beside the count call's and the match's: 12 bytes per hit of the range in flight, 8 bytes per document of hit
+ * offsets, K x 8 bytes for an oversized document; nothing per text byte or per class.  AHA_CLASS_BLOCKS (read when the handle
+ * is compiled) caps the grids of these calls' kernels.
+ * aha_ac_last_timing: engine = the engine that traversed, n_hits = all hits, ms_write = everything after the match, repeats =
+ * the ranges before the last.  The host entry stages the batch on the device and downloads out.
+ * Out of scope so far: feeds, groups, weights, accumulating into an existing table, char offsets, match_longest, conditions
+ * on the row (grep by class, minimum counts). */
+typedef struct aha_classes aha_classes;
+int32_t aha_classes_create(aha_ac *ac, const uint32_t *class_ids /* offsets[K] */,
+                           const uint64_t *offsets /* K+1, offsets[0] == 0, ascending */, uint32_t n_classes, aha_classes **out);
+void aha_classes_free(aha_classes *table);
+int32_t aha_ac_class_counts_batch(aha_ac *ac, const aha_classes *table, const uint8_t *corpus, const uint64_t *doc_offsets,
+                                  uint64_t n_docs, const aha_match_params *params, uint32_t flags /* 0 */,
+                                  uint32_t *out /* D x n_classes */, uint64_t *n_hits /* or NULL */);
+/* Device-resident form: d_ pointers are HBM on the handle's device; *n_hits is host memory; blocks until final. */
+int32_t aha_ac_class_counts_batch_device(aha_ac *ac, const aha_classes *table, const uint8_t *d_corpus, const uint64_t *d_doc_offsets,
+                                         uint64_t n_docs, uint64_t n_bytes, const aha_match_params *params, uint32_t flags /* 0 */,
+                                         uint32_t *d_out /* D x n_classes */, uint64_t *n_hits /* or NULL */, void *stream);
+
 /* Feed cover: the same pieces as aha_feed_match_batch*, and the cover of what a match call of them on a BYTE feed in the same
  * state would report (H_d: the hits of piece d, offsets relative to the piece, start possibly negative), without the hit list.
  * mask: the layout of aha_ac_cover_batch over the batch of pieces; bit j = 1 iff byte j lies in [max(start, 0), end) of a hit
