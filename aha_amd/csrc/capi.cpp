@@ -10,6 +10,9 @@ using namespace ahai;
 namespace ahai {
 // last error text of the calling thread (aha_last_error): calls on one handle may run concurrently
 thread_local std::string tls_err;
+}  // namespace ahai
+void aha_internal_set_error(const char *text) { ahai::tls_err = text; }
+namespace ahai {
 
 hipError_t reserve(Buf &b, size_t bytes, Grow grow) {
   if (b.bytes >= bytes) return hipSuccess;
@@ -306,12 +309,12 @@ int32_t aha_ac_compile(const uint8_t *key_bytes, const uint64_t *key_offsets, ui
   uint32_t flags = opts ? opts->flags : 0;
   int device = opts ? opts->device : -1;
   aha_ac *ac = new aha_ac();
-  ac->opt_flags = flags & (AHA_OPT_HOST_ONLY | AHA_OPT_FORCE_WIDE | AHA_OPT_FOLD_ASCII);
+  ac->opt_flags = flags & (AHA_OPT_HOST_ONLY | AHA_OPT_FORCE_WIDE | AHA_OPT_FOLD_ASCII | AHA_OPT_FOLD_SIMPLE);
   BuildError be;
   static const uint8_t dummy = 0;
   // AHA_OPT_FOLD_ASCII: the automaton -- and with it both images, the filter, the stale ends and the duplicate check (two keys
   // equal after folding: AHA_E_DUP_KEY at the second) -- is built from a folded copy of the keys; the handle keeps the
-  // caller's spelling beside it
+  // caller's spelling beside it.  AHA_OPT_FOLD_SIMPLE: the same with fold2 of every key on its own (fold.hpp)
   // (only the keys' own bytes [offs[0], offs[K]) are copied, with the offsets rebased as build_automaton rebases them)
   std::vector<uint8_t> folded;
   std::vector<uint64_t> rebased;
@@ -326,8 +329,14 @@ int32_t aha_ac_compile(const uint8_t *key_bytes, const uint64_t *key_offsets, ui
       delete ac;
       return AHA_E_NOMEM;
     }
-    fold_bytes(folded.data(), folded.size());
     for (auto &o : rebased) o -= key_offsets[0];
+    if (ac->fold_mode() == 2) {
+      // (offsets that do not ascend are build_automaton's to refuse: such a key is left as it is)
+      for (uint32_t k = 0; k < n_keys; k++)
+        if (rebased[k] <= rebased[k + 1] && rebased[k + 1] <= folded.size()) fold2_bytes(folded.data() + rebased[k], rebased[k + 1] - rebased[k]);
+    } else {
+      fold_bytes(folded.data(), folded.size());
+    }
     build_from = folded.data();
     build_offs = rebased.data();
   }
@@ -698,7 +707,10 @@ int32_t aha_ac_id(const aha_ac *ac, const uint8_t *key, int32_t len) {
   if (ac->fold() && len > 0) {
     try {
       std::vector<uint8_t> q(key, key + len);
-      fold_bytes(q.data(), q.size());
+      if (ac->fold_mode() == 2)
+        fold2_bytes(q.data(), q.size());
+      else
+        fold_bytes(q.data(), q.size());
       k = ac->aut.find_key(q.data(), len);
     } catch (...) {
       return AHA_E_NOMEM;

@@ -257,10 +257,17 @@ static void *cover_reserve(Scratch *sc, CoverSlot slot, size_t bytes) { return r
 
 // The kernels read a text in aligned 16-byte pieces, and a folded handle (AHA_OPT_FOLD_ASCII) matches the folded text: *text
 // becomes its copy in `dst` (n_bytes + 64 bytes of scratch), a plain device-to-device copy (~0.7 ms per GiB: about a fifth of
-// a match) or, with `fold`, the one streaming pass that does both jobs (scan_fold.hip).  The caller's text is only read.
-static int32_t stage_text(aha_ac *ac, const uint8_t **text, uint64_t n_bytes, void *dst, bool fold, hipStream_t s) {
+// a match) or, with `fold` (the handle's fold mode: 1 ASCII, 2 simple), the one streaming pass that does both jobs
+// (scan_fold.hip).  The simple fold is that of every document on its own: doc_off (device) are the n_docs + 1 offsets of
+// exactly these n_bytes, a batch or a range of whole documents.  The caller's text is only read.
+static int32_t stage_text(aha_ac *ac, const uint8_t **text, uint64_t n_bytes, void *dst, int fold, const uint64_t *doc_off,
+                          uint64_t n_docs, hipStream_t s) {
   if (fold) {
-    fold_launch_copy(*text, (uint8_t *)dst, n_bytes, 8u * std::max<uint32_t>(ac->v2_grid, 64u), s);
+    const uint32_t max_blocks = 8u * std::max<uint32_t>(ac->v2_grid, 64u);
+    if (fold == 2)
+      fold2_launch_copy(*text, (uint8_t *)dst, n_bytes, doc_off, n_docs, max_blocks, s);
+    else
+      fold_launch_copy(*text, (uint8_t *)dst, n_bytes, max_blocks, s);
     HIPCHK(ac, hipGetLastError());
   } else {
     HIPCHK(ac, hipMemcpyAsync(dst, *text, n_bytes, hipMemcpyDeviceToDevice, s));
@@ -269,26 +276,30 @@ static int32_t stage_text(aha_ac *ac, const uint8_t **text, uint64_t n_bytes, vo
   return AHA_OK;
 }
 // ... of a whole batch, in v2buf[kText]
-static int32_t stage_batch(aha_ac *ac, Scratch *sc, const uint8_t **text, uint64_t n_bytes, bool fold, hipStream_t s) {
+static int32_t stage_batch(aha_ac *ac, Scratch *sc, const uint8_t **text, uint64_t n_bytes, int fold, const uint64_t *doc_off,
+                           uint64_t n_docs, hipStream_t s) {
   if (int32_t rc = v2_reserve(sc, kText, n_bytes + 64)) return rc;
-  return stage_text(ac, text, n_bytes, sc->v2buf[kText].p, fold, s);
+  return stage_text(ac, text, n_bytes, sc->v2buf[kText].p, fold, doc_off, n_docs, s);
 }
-// M.fold: M.text is still the caller's.  Only the prefix-filter engine takes it like that (it folds in its own loads); every
+// M.fold (the fold mode): M.text is still the caller's.  Only the prefix-filter engine takes it like that, and only the ASCII
+// fold (it folds in its own loads; with the simple fold it reads the staged copy like everyone else: match_v2); every
 // other path -- the byte-level and character-level engines, the opt-in ones, the two-pass engine, match_longest, a pass
 // behind a hand-back of the filter -- calls this first: the copy is made at that moment, once per call.
 static int32_t stage_folded(aha_ac *ac, Scratch *sc, MatchArgs &M, hipStream_t s) {
   if (!M.fold) return AHA_OK;
-  const int32_t rc = stage_batch(ac, sc, &M.text, M.n_bytes, true, s);
+  const int32_t rc = stage_batch(ac, sc, &M.text, M.n_bytes, M.fold, M.doc_off, M.n_docs, s);
   if (rc == AHA_OK) M.fold = 0;
   return rc;
 }
 // The text of a device-resident batch as the engines take it (device_match, device_count): an unaligned view (a slice of a
 // larger buffer) is copied once into scratch, folded on the way on a folded handle; an aligned text stays the caller's, and on
 // a folded handle M.fold says so: the prefix-filter engine reads it where it lies, the others stage it (stage_folded).
+// (M.doc_off and M.n_docs are the batch's by now: the simple fold goes document by document)
 static int32_t take_text(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, uint64_t n_bytes, MatchArgs &M, hipStream_t s) {
   M.text = d_corpus;
-  if (reinterpret_cast<uintptr_t>(d_corpus) % 16 != 0) return stage_batch(ac, sc, &M.text, n_bytes, ac->fold(), s);
-  if (ac->fold()) M.fold = 1;
+  if (reinterpret_cast<uintptr_t>(d_corpus) % 16 != 0)
+    return stage_batch(ac, sc, &M.text, n_bytes, ac->fold_mode(), M.doc_off, M.n_docs, s);
+  M.fold = ac->fold_mode();
   return AHA_OK;
 }
 // The two-pass engine's chunk: `chunk0`, doubled until the warm-up (a multiple of Lmax - 1 bytes) is a small fraction of it --
@@ -472,8 +483,8 @@ static int32_t launch_v2(aha_ac *ac, Scratch *sc, MatchArgs &M1, const V2Plan &P
     if (!P.sizes[i]) continue;
     if ((rc = v2_reserve(sc, (V2Slot)i, P.sizes[i]))) return ((i == kEvRegions || i == kEvGroups) && P.mode != kSlabs) ? kNoRegions : rc;
   }
-  if (M1.fold && !filt && (rc = stage_folded(ac, sc, M1, s))) return rc;
-  const bool fold_loads = filt && M1.fold;  // (the filter engine on the caller's own text)
+  if (M1.fold && (!filt || M1.fold == 2) && (rc = stage_folded(ac, sc, M1, s))) return rc;
+  const bool fold_loads = filt && M1.fold;  // (the filter engine on the caller's own text: the ASCII fold only)
   auto at = [sc](V2Slot slot) { return sc->v2buf[slot].p; };
   M.text = M1.text;
   M.ev = (uint4 *)at(kEv);
@@ -991,7 +1002,7 @@ static int32_t count_ranges(aha_ac *ac, Scratch *sc, const MatchArgs &M0, hipStr
     if (nb && reinterpret_cast<uintptr_t>(Mr.text) % 16 != 0) {
       void *t = count_reserve(sc, kCntText, nb + 64);
       if (!t) return nomem();
-      if ((rc = stage_text(ac, &Mr.text, nb, t, M0.fold != 0, s))) return rc;
+      if ((rc = stage_text(ac, &Mr.text, nb, t, M0.fold, d_rel, nd, s))) return rc;
       Mr.fold = 0;
     }
     uint64_t nh = 0;
@@ -1064,10 +1075,10 @@ int32_t device_count(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
     return AHA_OK;
   }
   if (!d_corpus) return AHA_E_INVALID;
-  if ((rc = take_text(ac, sc, d_corpus, n_bytes, M, s))) return rc;
   M.doc_off = d_doc_offsets;
   M.n_docs = n_docs;
   M.n_bytes = n_bytes;
+  if ((rc = take_text(ac, sc, d_corpus, n_bytes, M, s))) return rc;
   M.out = nullptr;
   M.cap = 0;
   M.doc_hit_off = d_doc_hit_offsets;
@@ -1265,7 +1276,7 @@ int32_t device_doc_counts(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, cons
       if (!ac->fold() && reinterpret_cast<uintptr_t>(text) % 16 != 0) {
         void *t = dc_reserve(sc, kDcText, nb + 64);
         if (!t) return nomem();
-        if ((rc = stage_text(ac, &text, nb, t, false, s))) return rc;
+        if ((rc = stage_text(ac, &text, nb, t, 0, nullptr, 0, s))) return rc;
       }
       HIPCHK(ac, hipStreamSynchronize(s));  // (rel is the host's until the copy has run)
     }
@@ -1534,7 +1545,7 @@ int32_t device_select_to(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const
       if (!ac->fold() && reinterpret_cast<uintptr_t>(text) % 16 != 0) {
         void *t = sel_reserve(sc, kSelText, nb + 64);
         if (!t) return nomem();
-        if ((rc = stage_text(ac, &text, nb, t, false, s))) return rc;
+        if ((rc = stage_text(ac, &text, nb, t, 0, nullptr, 0, s))) return rc;
       }
       HIPCHK(ac, hipStreamSynchronize(s));  // (rel is the host's until the copy has run)
     }
@@ -2013,7 +2024,7 @@ int32_t device_class_counts(aha_ac *ac, Scratch *sc, const aha_classes *table, c
       if (!ac->fold() && reinterpret_cast<uintptr_t>(text) % 16 != 0) {
         void *t = cls_reserve(sc, kClsText, nb + 64);
         if (!t) return nomem();
-        if ((rc = stage_text(ac, &text, nb, t, false, s))) return rc;
+        if ((rc = stage_text(ac, &text, nb, t, 0, nullptr, 0, s))) return rc;
       }
       HIPCHK(ac, hipStreamSynchronize(s));  // (rel is the host's until the copy has run)
     }

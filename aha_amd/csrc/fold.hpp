@@ -1,10 +1,19 @@
-// fold.hpp -- the ASCII case fold of AHA_OPT_FOLD_ASCII (include/aha_hip.h), host and device.  The ONLY place the rule is
-// written down: fold(b) = b + 32 for 0x41 <= b <= 0x5A ('A' .. 'Z'), b otherwise.  Bytes >= 0x80, '@', '[', '`' and '{' stay,
+// fold.hpp -- the case folds of AHA_OPT_FOLD_ASCII and AHA_OPT_FOLD_SIMPLE (include/aha_hip.h), host and device.  The ONLY place
+// the rules are written down.
+// ASCII: fold(b) = b + 32 for 0x41 <= b <= 0x5A ('A' .. 'Z'), b otherwise.  Bytes >= 0x80, '@', '[', '`' and '{' stay,
 // lengths and UTF-8 lead bytes never change.  Compile folds a copy of the keys with it (capi.cpp), the prefix-filter engine
 // folds its text loads (scan_filter.hip), every other engine reads a copy folded on the way (scan_fold.hip).
+// SIMPLE: fold2 of one buffer, byte for byte as long as its input.  At every j with buf[j] in 0xC2 .. 0xDF, j + 1 < n and
+// buf[j + 1] in 0x80 .. 0xBF the pair is the UTF-8 of a code point cp in U+0080 .. U+07FF and becomes the UTF-8 of F(cp)
+// (fold_table.hpp: two bytes again, a lead byte stays a lead byte); such pairs cannot overlap; every other byte gets the ASCII
+// fold.  A rule on bytes, not on well-formed text: a stray continuation byte, a lead byte at the end, 0xC0, 0xC1 and the
+// bytes of three- and four-byte sequences stay.  Keys are folded one by one, a batch document by document (fold2_bytes here,
+// scan_fold.hip there): a lead byte never pairs with a byte of the next key or document.
 #pragma once
 #include <cstddef>
 #include <cstdint>
+
+#include "fold_table.hpp"
 
 #ifndef AHA_HD
 #if defined(__HIPCC__)
@@ -37,6 +46,35 @@ AHA_HD inline void fold128(uint32_t &a, uint32_t &b, uint32_t &c, uint32_t &d) {
 
 inline void fold_bytes(uint8_t *p, size_t n) {
   for (size_t i = 0; i < n; i++) p[i] = fold8(p[i]);
+}
+
+// ---- the simple fold: the pieces both sides share (the table itself comes as an argument: the device reads its copy in LDS)
+AHA_HD inline bool fold2_lead(uint32_t b) { return b - 0xC2u < 30u; }           // 0xC2 .. 0xDF
+AHA_HD inline bool fold2_cont(uint32_t b) { return (b & 0xC0u) == 0x80u; }      // 0x80 .. 0xBF
+// F(cp) of the pair (lead, cont); both hold, so 0x80 <= cp <= 0x7FF
+AHA_HD inline uint32_t fold2_pair(const uint16_t *table, uint32_t lead, uint32_t cont) {
+  return table[(((lead & 0x1Fu) << 6) | (cont & 0x3Fu)) - 0x80u];
+}
+// One byte of fold2 from the byte and its two neighbours (0 -- neither a lead nor a continuation byte -- where there is none):
+// the lead byte and the continuation byte of a pair come from the same table entry, whoever asks for them.
+AHA_HD inline uint8_t fold2_byte(const uint16_t *table, uint32_t prev, uint32_t cur, uint32_t next) {
+  if (fold2_lead(cur) && fold2_cont(next)) return (uint8_t)(0xC0u | (fold2_pair(table, cur, next) >> 6));
+  if (fold2_cont(cur) && fold2_lead(prev)) return (uint8_t)(0x80u | (fold2_pair(table, prev, cur) & 0x3Fu));
+  return fold8((uint8_t)cur);
+}
+
+// fold2 of one buffer in place (one key, one document): the host's statement of the rule
+inline void fold2_bytes(uint8_t *p, size_t n) {
+  for (size_t i = 0; i < n; i++) {
+    if (fold2_lead(p[i]) && i + 1 < n && fold2_cont(p[i + 1])) {
+      const uint32_t f = fold2_pair(kFold2Table, p[i], p[i + 1]);
+      p[i] = (uint8_t)(0xC0u | (f >> 6));
+      p[i + 1] = (uint8_t)(0x80u | (f & 0x3Fu));
+      i++;
+    } else {
+      p[i] = fold8(p[i]);
+    }
+  }
 }
 
 }  // namespace aha

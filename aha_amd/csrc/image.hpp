@@ -79,7 +79,8 @@ struct MatchArgs {
   int32_t cover_clear;               // host side: the pass clears the mask itself, once it knows the offsets are good
   // host side, a handle compiled with AHA_OPT_FOLD_ASCII: `text` is still the caller's (16-byte aligned) and not folded yet.  The
   // prefix-filter engine reads it as it is and folds in its loads; every other path takes the folded copy first (engine.cpp
-  // stage_folded), which clears this
+  // stage_folded), which clears this.  The value is the handle's fold mode (handle.hpp): 1 ASCII, 2 simple -- with 2 the
+  // prefix-filter engine takes the folded copy too (its loads fold ASCII only)
   int32_t fold;
 };
 
@@ -233,6 +234,10 @@ void filter_launch_walk_fold(const DevAut &A, const V2Args &M, const void *bitma
                              const unsigned long long *non_ascii, uint32_t cus, void *stream);
 // scan_fold.hip: dst[j] = fold(src[j]) for j < n_bytes; src any byte address, dst 16-byte aligned; src is only read
 void fold_launch_copy(const uint8_t *src, uint8_t *dst, uint64_t n_bytes, uint32_t max_blocks, void *stream);
+// ... with AHA_OPT_FOLD_SIMPLE: dst = fold2 (fold.hpp) of every document of src on its own.  doc_offsets (device, n_docs + 1
+// entries; the first is subtracted from the others) are those of exactly these n_bytes: a batch or a range of whole documents
+void fold2_launch_copy(const uint8_t *src, uint8_t *dst, uint64_t n_bytes, const uint64_t *doc_offsets, uint64_t n_docs,
+                       uint32_t max_blocks, void *stream);
 
 size_t v2_lds_bytes(uint32_t lds_slots, bool compact);
 int v2_prepare(bool compact, size_t lds_bytes);  // raises the dynamic-LDS limit; hipError_t as int

@@ -43,6 +43,9 @@ struct aha_internal_host_copy {
   }
 };
 
+// the calling thread's aha_last_error text, for group.cpp's own refusals
+void aha_internal_set_error(const char *text);
+
 // aha_ac_match_batch_keep that also copies the ranges' hits to host memory while they fit (hc may be null)
 extern "C" int32_t aha_internal_match_batch_keep_copy(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc_offsets,
                                                       uint64_t n_docs, const aha_match_params *params, aha_hit *d_hits,

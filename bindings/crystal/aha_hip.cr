@@ -39,6 +39,7 @@ lib LibAhaHip
   end
 
   OPT_FOLD_ASCII = 4_u32 # compile-time flag: 'A'..'Z' of keys and text match as 'a'..'z' (include/aha_hip.h)
+  OPT_FOLD_SIMPLE = 8_u32 # ... and the two-byte UTF-8 characters by their simple case fold, document by document; no feeds, no groups yet
 
   struct Options
     struct_size : UInt32

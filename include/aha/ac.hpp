@@ -82,8 +82,10 @@ class AC {
   ~AC() { aha_ac_free(h_); }
 
   // Aha::AC.compile(keys).  fold_ascii: an ASCII case-insensitive handle (AHA_OPT_FOLD_ASCII, aha_hip.h): every call gives what a
-  // plain handle compiled from the lower-cased keys gives over the lower-cased text; key(id) keeps the spelling given here
-  static AC compile(const std::vector<std::string> &keys, int device = -1, bool fold_ascii = false) {
+  // plain handle compiled from the lower-cased keys gives over the lower-cased text; key(id) keeps the spelling given here.
+  // fold_simple: that plus the simple case fold of the two-byte UTF-8 characters (AHA_OPT_FOLD_SIMPLE: Latin-1, Latin
+  // Extended-A/B, Greek, Cyrillic, Armenian), every document folded on its own; such a handle has no feeds and no groups yet
+  static AC compile(const std::vector<std::string> &keys, int device = -1, bool fold_ascii = false, bool fold_simple = false) {
     std::vector<uint8_t> blob;
     std::vector<uint64_t> offs(keys.size() + 1, 0);
     for (size_t i = 0; i < keys.size(); i++) {
@@ -93,7 +95,7 @@ class AC {
     aha_options o{};
     o.struct_size = sizeof(o);
     o.device = device;
-    o.flags = fold_ascii ? AHA_OPT_FOLD_ASCII : 0u;
+    o.flags = (fold_ascii ? AHA_OPT_FOLD_ASCII : 0u) | (fold_simple ? AHA_OPT_FOLD_SIMPLE : 0u);
     aha_ac *h = nullptr;
     uint32_t bad = 0;
     int32_t rc = aha_ac_compile(blob.data(), offs.data(), (uint32_t)keys.size(), &o, &h, &bad);
@@ -583,18 +585,19 @@ class AC {
     aha_ac_save(h_, v.data(), (uint64_t)n);
     return v;
   }
-  // (the container stores the keys as spelled and no options: say fold_ascii again)
-  static AC from_bytes(const std::vector<uint8_t> &data, int device = -1, bool fold_ascii = false) {
+  // (the container stores the keys as spelled and no options: say fold_ascii / fold_simple again)
+  static AC from_bytes(const std::vector<uint8_t> &data, int device = -1, bool fold_ascii = false, bool fold_simple = false) {
     aha_options o{};
     o.struct_size = sizeof(o);
     o.device = device;
-    o.flags = fold_ascii ? AHA_OPT_FOLD_ASCII : 0u;
+    o.flags = (fold_ascii ? AHA_OPT_FOLD_ASCII : 0u) | (fold_simple ? AHA_OPT_FOLD_SIMPLE : 0u);
     aha_ac *h = nullptr;
     int32_t rc = aha_ac_load(data.data(), data.size(), &o, &h);
     if (rc != AHA_OK) throw Error(rc, aha_strerror(rc));
     return AC(h);
   }
   bool fold_ascii() const { return (aha_ac_flags(h_) & AHA_OPT_FOLD_ASCII) != 0; }
+  bool fold_simple() const { return (aha_ac_flags(h_) & AHA_OPT_FOLD_SIMPLE) != 0; }
   aha_ac *handle() const { return h_; }
 
  private:

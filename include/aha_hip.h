@@ -110,6 +110,30 @@ typedef struct {
  * Cost: the prefix-filter engine folds inside its own text loads (no copy, no extra scratch); every other engine reads a
  * folded copy made by one streaming pass into scratch (N bytes; aha_amd/csrc/scan_fold.hip). */
 #define AHA_OPT_FOLD_ASCII 4u
+/* Simple case folding for the characters UTF-8 writes in two bytes (a pure addition to ABI 8; implies AHA_OPT_FOLD_ASCII:
+ * 4u | 8u means what 8u means, and aha_ac_flags reports the bits as they were passed).  fold2(buf) is a byte-to-byte map of
+ * one buffer, as long as its input: at every j with buf[j] in 0xC2 .. 0xDF, j + 1 < len and buf[j + 1] in 0x80 .. 0xBF the
+ * pair -- the UTF-8 of a code point cp in U+0080 .. U+07FF -- becomes the UTF-8 of F(cp); such pairs cannot overlap; every
+ * other byte gets the ASCII fold above.  A rule on bytes, not on well-formed text: stray continuation bytes, a lead byte at
+ * the end, three- and four-byte sequences, 0xC0 and 0xC1 pass through unchanged.  F (aha_amd/csrc/fold_table.hpp, written by
+ * tools/gen_fold_table.py from Unicode 13.0.0): with one(s) = "s is one code point in U+0080 .. U+07FF", u = upper(c) if
+ * one(upper(c)) else c, F(c) = lower(u) if one(lower(u)) else c.  F is idempotent, gives one representative per case class
+ * and equals full case folding wherever that is one code point; it moves 450 code points (Latin-1 Supplement, Latin
+ * Extended-A/B, Greek, Cyrillic, Armenian), 108 of them to another lead byte; U+00DF, U+0130, U+0131 and U+017F stay (their
+ * partners are not single two-byte characters).  Lengths never change and a lead byte stays a lead byte, so byte offsets,
+ * char offsets, masks, selections and substituted copies are those of the original text.
+ * THE RULE is AHA_OPT_FOLD_ASCII's with its three exceptions unchanged: every call gives, bit for bit, what the same call gives
+ * on an ordinary handle compiled from fold2(key) of each key and run over the batch in which EACH DOCUMENT is folded on its
+ * own, fold2(corpus[off[d] .. off[d + 1])) -- a lead byte that ends document d never pairs with a continuation byte that
+ * opens d + 1.  Covered: match, match_longest in both modes, a separator filter (it tests the folded neighbour bytes), char
+ * offsets, count, document counts, class counts, cover, redact, select, replace, records, grep, the pack / unpack exchange,
+ * replicate and export.  Two keys equal after fold2 are AHA_E_DUP_KEY at the second; aha_ac_id folds its argument with
+ * fold2; aha_ac_load takes the flag in `opts` again.
+ * NOT supported yet, AHA_E_INVALID before any device work: aha_feed_open / aha_feed_open_params on such a handle (a character
+ * may be cut between two calls) and aha_group_compile with the flag (the shards cut the batch).
+ * Cost: every engine, the prefix filter included, reads a folded copy made by one streaming pass into scratch (N bytes) and a
+ * fix-up of one lane per document boundary (scan_fold.hip). */
+#define AHA_OPT_FOLD_SIMPLE 8u
 
 /* Per-call options mirroring the reference's overloads:
  *   char_offsets = 0: match(seq : Bytes)        src/aha/ac.cr:280-286  (byte offsets)
