@@ -1,5 +1,5 @@
-// fold.hpp -- the case folds of AHA_OPT_FOLD_ASCII and AHA_OPT_FOLD_SIMPLE (include/aha_hip.h), host and device.  The ONLY place
-// the rules are written down.
+// fold.hpp -- the case folds of AHA_OPT_FOLD_ASCII, AHA_OPT_FOLD_SIMPLE and AHA_OPT_FOLD_BMP (include/aha_hip.h), host and
+// device.  The ONLY place the rules are written down.
 // ASCII: fold(b) = b + 32 for 0x41 <= b <= 0x5A ('A' .. 'Z'), b otherwise.  Bytes >= 0x80, '@', '[', '`' and '{' stay,
 // lengths and UTF-8 lead bytes never change.  Compile folds a copy of the keys with it (capi.cpp), the prefix-filter engine
 // folds its text loads (scan_filter.hip), every other engine reads a copy folded on the way (scan_fold.hip).
@@ -9,10 +9,18 @@
 // fold.  A rule on bytes, not on well-formed text: a stray continuation byte, a lead byte at the end, 0xC0, 0xC1 and the
 // bytes of three- and four-byte sequences stay.  Keys are folded one by one, a batch document by document (fold2_bytes here,
 // scan_fold.hip there): a lead byte never pairs with a byte of the next key or document.
+// BMP: fold3 of one buffer, as long as its input again.  At every j with buf[j] in 0xE0 .. 0xEF, j + 2 < n and buf[j + 1],
+// buf[j + 2] both in 0x80 .. 0xBF the triple becomes the UTF-8 of F3(cp) (fold3_table.hpp: three bytes again), where an overlong
+// form (cp < 0x800) and a surrogate are their own F3; else the pair rule of fold2; else the ASCII fold.  A lead byte is never a
+// continuation byte, so triples and pairs cannot overlap and every output byte is a function of the byte and its two
+// neighbours on each side (fold3_byte).  A truncated triple, four-byte sequences and 0xF5 .. 0xFF stay.  33 code points whose
+// only case partner is written in another number of bytes (the Kelvin, ohm and Angstrom signs, U+1E9E, U+1C80 .. U+1C87,
+// U+2C62 and others: include/aha_hip.h has the list) stay.
 #pragma once
 #include <cstddef>
 #include <cstdint>
 
+#include "fold3_table.hpp"
 #include "fold_table.hpp"
 
 #ifndef AHA_HD
@@ -67,6 +75,65 @@ AHA_HD inline uint8_t fold2_byte(const uint16_t *table, uint32_t prev, uint32_t 
 inline void fold2_bytes(uint8_t *p, size_t n) {
   for (size_t i = 0; i < n; i++) {
     if (fold2_lead(p[i]) && i + 1 < n && fold2_cont(p[i + 1])) {
+      const uint32_t f = fold2_pair(kFold2Table, p[i], p[i + 1]);
+      p[i] = (uint8_t)(0xC0u | (f >> 6));
+      p[i + 1] = (uint8_t)(0x80u | (f & 0x3Fu));
+      i++;
+    } else {
+      p[i] = fold8(p[i]);
+    }
+  }
+}
+
+// ---- the fold of the three-byte characters (AHA_OPT_FOLD_BMP): the two-byte table, and F3 in two levels (fold3_table.hpp)
+struct Fold3Tables {
+  const uint16_t *pair;   // kFold2Table or its copy in LDS
+  const uint8_t *index;   // kFold3Index
+  const uint16_t *live;   // kFold3Live
+};
+AHA_HD inline bool fold3_lead(uint32_t b) { return (b & 0xF0u) == 0xE0u; }      // 0xE0 .. 0xEF
+// F3(cp) of the triple (lead, c1, c2), all three hold; an overlong form (cp < 0x800) is its own fold, and so is a surrogate
+// (its block is not live): encoded again they are the bytes they were
+// (both look-ups are made whatever they find, at an entry that exists, and chosen afterwards: on the device the lanes of a
+// wave then stay together)
+AHA_HD inline uint32_t fold3_triple(const Fold3Tables &T, uint32_t lead, uint32_t c1, uint32_t c2) {
+  const uint32_t cp = ((lead & 0xFu) << 12) | ((c1 & 0x3Fu) << 6) | (c2 & 0x3Fu);
+  const uint32_t block = cp >> 6;
+  const uint32_t k = block < 0x20u ? 0u : T.index[block < 0x20u ? 0u : block - 0x20u];
+  const uint32_t f = T.live[(k ? k - 1u : 0u) * 64u + (cp & 63u)];
+  return k ? f : cp;
+}
+// One byte of fold3 from the byte and its two neighbours on each side (0 where there is none): the three bytes of a triple
+// come from the same table entry, whoever asks for them.
+// Which byte of which triple or pair `cur` is comes first, as flags; then one look-up for the triple, or one for the pair.
+AHA_HD inline uint8_t fold3_byte(const Fold3Tables &T, uint32_t prev2, uint32_t prev, uint32_t cur, uint32_t next, uint32_t next2) {
+  const bool cc = fold2_cont(cur), nc = fold2_cont(next);
+  const bool first = fold3_lead(cur) & nc & fold2_cont(next2);
+  const bool second = cc & fold3_lead(prev) & nc;
+  const bool third = cc & fold2_cont(prev) & fold3_lead(prev2);
+  if (first | second | third) {
+    const uint32_t f = fold3_triple(T, first ? cur : second ? prev : prev2, first ? next : second ? cur : prev, first ? next2 : second ? next : cur);
+    return (uint8_t)(first ? 0xE0u | (f >> 12) : second ? 0x80u | ((f >> 6) & 0x3Fu) : 0x80u | (f & 0x3Fu));
+  }
+  const bool opens = fold2_lead(cur) & nc, closes = cc & fold2_lead(prev);
+  if (opens | closes) {
+    const uint32_t f = fold2_pair(T.pair, opens ? cur : prev, opens ? next : cur);
+    return (uint8_t)(opens ? 0xC0u | (f >> 6) : 0x80u | (f & 0x3Fu));
+  }
+  return fold8((uint8_t)cur);
+}
+
+// fold3 of one buffer in place (one key, one document): the host's statement of the rule
+inline void fold3_bytes(uint8_t *p, size_t n) {
+  const Fold3Tables T = {kFold2Table, kFold3Index, kFold3Live};
+  for (size_t i = 0; i < n; i++) {
+    if (fold3_lead(p[i]) && i + 2 < n && fold2_cont(p[i + 1]) && fold2_cont(p[i + 2])) {
+      const uint32_t f = fold3_triple(T, p[i], p[i + 1], p[i + 2]);
+      p[i] = (uint8_t)(0xE0u | (f >> 12));
+      p[i + 1] = (uint8_t)(0x80u | ((f >> 6) & 0x3Fu));
+      p[i + 2] = (uint8_t)(0x80u | (f & 0x3Fu));
+      i += 2;
+    } else if (fold2_lead(p[i]) && i + 1 < n && fold2_cont(p[i + 1])) {
       const uint32_t f = fold2_pair(kFold2Table, p[i], p[i + 1]);
       p[i] = (uint8_t)(0xC0u | (f >> 6));
       p[i + 1] = (uint8_t)(0x80u | (f & 0x3Fu));

@@ -269,9 +269,12 @@ struct aha_ac {
   }
   const uint64_t serial = next_serial();  // one per handle ever made in this process (a replacement table names its handle by it)
   std::vector<uint8_t> key_spelling;
-  bool fold() const { return (opt_flags & (AHA_OPT_FOLD_ASCII | AHA_OPT_FOLD_SIMPLE)) != 0; }  // any fold
-  // which one: 0 none, 1 ASCII (fold8), 2 simple (fold2: AHA_OPT_FOLD_SIMPLE implies the ASCII fold)
-  int fold_mode() const { return (opt_flags & AHA_OPT_FOLD_SIMPLE) ? 2 : (opt_flags & AHA_OPT_FOLD_ASCII) ? 1 : 0; }
+  bool fold() const { return (opt_flags & (AHA_OPT_FOLD_ASCII | AHA_OPT_FOLD_SIMPLE | AHA_OPT_FOLD_BMP)) != 0; }  // any fold
+  // which one: 0 none, 1 ASCII (fold8), 2 simple (fold2: AHA_OPT_FOLD_SIMPLE implies the ASCII fold), 3 BMP (fold3:
+  // AHA_OPT_FOLD_BMP implies both)
+  int fold_mode() const {
+    return (opt_flags & AHA_OPT_FOLD_BMP) ? 3 : (opt_flags & AHA_OPT_FOLD_SIMPLE) ? 2 : (opt_flags & AHA_OPT_FOLD_ASCII) ? 1 : 0;
+  }
   Image img;  // host copy of the device image (export / debugging)
   uint32_t n_slots = 0;
   uint32_t slot_bytes = 0;

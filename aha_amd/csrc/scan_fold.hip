@@ -4,10 +4,12 @@
 // at once the "aligned copy of an unaligned corpus" the engines need anyway (engine.cpp).  The caller's text is only read.
 // A handle compiled with AHA_OPT_FOLD_SIMPLE gets the same pass with the two-byte characters folded through the table
 // (k_fold2_copy: the buffer as ONE run of bytes) and a second, tiny one that takes back what the first did across a document
-// boundary (k_fold2_fix): together fold2 of every document on its own (fold.hpp).
+// boundary (k_fold2_fix): together fold2 of every document on its own (fold.hpp).  AHA_OPT_FOLD_BMP: the same two steps with
+// the three-byte characters folded too (k_fold3_copy, k_fold3_fix): fold3 of every document on its own.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdlib>
 
 #include "fold.hpp"
 #include "image.hpp"
@@ -111,6 +113,124 @@ __global__ __launch_bounds__(256) void k_fold2_fix(const uint8_t *__restrict__ s
   }
 }
 
+// ---- the fold of the three-byte characters (AHA_OPT_FOLD_BMP) -------------------------------------------------------------
+__device__ const uint8_t d_fold3_index[AHA_FOLD3_INDEX_ENTRIES] = {AHA_FOLD3_INDEX};
+__device__ const uint16_t d_fold3_live[AHA_FOLD3_LIVE_ENTRIES] = {AHA_FOLD3_LIVE};
+
+// bit 7 of every byte of w that is >= 0x80 and whose low seven bits t lie in lo .. hi (fold32's sums: no carry between bytes)
+__device__ __forceinline__ uint32_t kc_in(uint32_t t, uint32_t lo, uint32_t hi) {
+  return (t + (0x80u - lo) * 0x01010101u) & ~(t + (0x7Fu - hi) * 0x01010101u);
+}
+// ... that is a lead byte whose character may move: 0xC2 .. 0xDF (the two-byte table), 0xE1, 0xE2, 0xEA, 0xEF (the only lead
+// bytes of the code points F3 moves: fold3_table.hpp)
+__device__ __forceinline__ uint32_t kc_live32(uint32_t w) {
+  const uint32_t t = w & 0x7f7f7f7fu;
+  return (kc_in(t, 0x42, 0x5F) | kc_in(t, 0x61, 0x62) | kc_in(t, 0x6A, 0x6A) | kc_in(t, 0x6F, 0x6F)) & w & 0x80808080u;
+}
+
+// fold3 of piece i (fold.hpp) in two steps, so that the neighbour loads of the four pieces a lane has in flight are in flight
+// together.  kc_fold3_halo: up to two bytes before the piece and two after it decide what its own bytes become; they belong to
+// other lanes (the next piece, another wave's 1 KiB, a piece a grid stride away) and are loaded from src only where they
+// decide something and only inside [0, n): the two before when byte 0 is a continuation byte (the second or third byte of a
+// character that began there; j0 > 0 is j0 >= 16, so j0 - 2 is inside), the one after when byte 15 is a lead byte or bytes 14,
+// 15 open a triple, the second one after when byte 15 is the lead of a triple.  -> prev2 | prev << 8 | next << 16 | next2 << 24,
+// 0 (neither a lead nor a continuation byte) where nothing was loaded; a piece of ASCII loads nothing.
+__device__ __forceinline__ uint32_t kc_fold3_halo(const uint8_t *__restrict__ src, uint64_t i, uint64_t n, const kc_v4u &v) {
+  if (!((v[0] | v[1] | v[2] | v[3]) & 0x80808080u)) return 0;
+  const uint64_t j0 = i * 16;
+  uint32_t h = 0;
+  if (fold2_cont(kc_byte(v, 0)) && j0 > 0) h = (uint32_t)src[j0 - 2] | ((uint32_t)src[j0 - 1] << 8);
+  const uint32_t b14 = kc_byte(v, 14), b15 = kc_byte(v, 15);
+  if ((fold2_lead(b15) || fold3_lead(b15) || (fold3_lead(b14) && fold2_cont(b15))) && j0 + 16 < n) h |= (uint32_t)src[j0 + 16] << 16;
+  if (fold3_lead(b15) && j0 + 17 < n) h |= (uint32_t)src[j0 + 17] << 24;
+  return h;
+}
+// kc_fold3_apply: a piece of ASCII takes fold32 and nothing else.  kLive (opt-in, see fold3_live_test): so does a piece in
+// which no character can move -- no live lead byte in it, none in the two bytes before it where its first character began
+// there: Chinese text, whose lead bytes are 0xE3 .. 0xE9, then never reaches the tables.  Otherwise byte by byte from the
+// byte and its neighbours (fold3_byte); the lanes that own the bytes of one triple each compute their byte from the same
+// table entry.  Every lane writes its own 16 bytes and no others.
+template <bool kLive>
+__device__ __forceinline__ kc_v4u kc_fold3_apply(const Fold3Tables &T, const kc_v4u &v, uint32_t halo) {
+  if (!((v[0] | v[1] | v[2] | v[3]) & 0x80808080u)) return kc_fold16(v);
+  if (kLive && !(kc_live32(v[0]) | kc_live32(v[1]) | kc_live32(v[2]) | kc_live32(v[3]) | kc_live32(halo & 0xFFFFu))) return kc_fold16(v);
+  uint32_t c[20];  // (bytes -2 .. 17 of the piece)
+  c[0] = halo & 0xFFu;
+  c[1] = (halo >> 8) & 0xFFu;
+  c[18] = (halo >> 16) & 0xFFu;
+  c[19] = halo >> 24;
+#pragma unroll
+  for (int k = 0; k < 16; k++) c[k + 2] = kc_byte(v, k);
+  kc_v4u o = {0, 0, 0, 0};
+#pragma unroll
+  for (int k = 0; k < 16; k++) o[k >> 2] |= (uint32_t)fold3_byte(T, c[k], c[k + 1], c[k + 2], c[k + 3], c[k + 4]) << ((k & 3) * 8);
+  return o;
+}
+
+// k_fold2_copy's loop with both tables -- 3840 + 992 + 3712 bytes -- staged in LDS once per workgroup.
+template <bool kLive>
+__global__ __launch_bounds__(256) void k_fold3_copy(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, uint64_t n) {
+  __shared__ uint16_t tab[AHA_FOLD2_ENTRIES];
+  __shared__ uint16_t live[AHA_FOLD3_LIVE_ENTRIES];
+  __shared__ uint8_t index[AHA_FOLD3_INDEX_ENTRIES];
+  for (uint32_t t = threadIdx.x; t < AHA_FOLD2_ENTRIES; t += 256) tab[t] = d_fold2_table[t];
+  for (uint32_t t = threadIdx.x; t < AHA_FOLD3_LIVE_ENTRIES; t += 256) live[t] = d_fold3_live[t];
+  for (uint32_t t = threadIdx.x; t < AHA_FOLD3_INDEX_ENTRIES; t += 256) index[t] = d_fold3_index[t];
+  __syncthreads();
+  const Fold3Tables T = {tab, index, live};
+  const uint64_t pieces = n / 16, stride = (uint64_t)gridDim.x * 256;
+  kc_v4u *out = reinterpret_cast<kc_v4u *>(dst);
+  uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  for (; i + 3 * stride < pieces; i += 4 * stride) {
+    const kc_v4u a = kc_load16(src + i * 16), b = kc_load16(src + (i + stride) * 16);
+    const kc_v4u c = kc_load16(src + (i + 2 * stride) * 16), d = kc_load16(src + (i + 3 * stride) * 16);
+    const uint32_t ha = kc_fold3_halo(src, i, n, a), hb = kc_fold3_halo(src, i + stride, n, b);
+    const uint32_t hc = kc_fold3_halo(src, i + 2 * stride, n, c), hd = kc_fold3_halo(src, i + 3 * stride, n, d);
+    out[i] = kc_fold3_apply<kLive>(T, a, ha);
+    out[i + stride] = kc_fold3_apply<kLive>(T, b, hb);
+    out[i + 2 * stride] = kc_fold3_apply<kLive>(T, c, hc);
+    out[i + 3 * stride] = kc_fold3_apply<kLive>(T, d, hd);
+  }
+  for (; i < pieces; i += stride) {
+    const kc_v4u a = kc_load16(src + i * 16);
+    out[i] = kc_fold3_apply<kLive>(T, a, kc_fold3_halo(src, i, n, a));
+  }
+  const uint64_t tail = pieces * 16 + threadIdx.x;
+  if (blockIdx.x == 0 && threadIdx.x < 16 && tail < n)
+    dst[tail] = fold3_byte(T, tail > 1 ? src[tail - 2] : 0u, tail > 0 ? src[tail - 1] : 0u, src[tail], tail + 1 < n ? src[tail + 1] : 0u,
+                           tail + 2 < n ? src[tail + 2] : 0u);
+}
+
+// A lane per interior document boundary b, as in k_fold2_fix.  k_fold3_copy folded across b where a pair lies at (b - 1, b) or a
+// triple is cut 1|2 (b - 1, b, b + 1) or 2|1 (b - 2, b - 1, b); the fragments -- a lead byte alone or with one continuation
+// byte, continuation bytes without their lead -- have no fold of their own, so the original bytes are what fold3 of either
+// document has there.  A triple cut twice (a one-byte or empty document inside it) is put back by two lanes, both with the
+// same source bytes.  (b is taken as it comes, see k_fold2_fix; every index is checked against [0, n) here.)
+__global__ __launch_bounds__(256) void k_fold3_fix(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, uint64_t n,
+                                                   const uint64_t *__restrict__ off, uint64_t D) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  for (uint64_t d = 1 + (uint64_t)blockIdx.x * 256 + threadIdx.x; d < D; d += stride) {
+    const uint64_t b = off[d] - off[0];
+    if (b == 0 || b >= n) continue;
+    const uint8_t before = src[b - 1], at = src[b];
+    if (!fold2_cont(at)) continue;
+    if (fold2_lead(before)) {
+      dst[b - 1] = before;
+      dst[b] = at;
+    } else if (fold3_lead(before)) {
+      if (b + 1 < n && fold2_cont(src[b + 1])) {
+        dst[b - 1] = before;
+        dst[b] = at;
+        dst[b + 1] = src[b + 1];
+      }
+    } else if (fold2_cont(before) && b >= 2 && fold3_lead(src[b - 2])) {
+      dst[b - 2] = src[b - 2];
+      dst[b - 1] = before;
+      dst[b] = at;
+    }
+  }
+}
+
 }  // namespace
 
 // (the grid of both staged copies: a workgroup per 1024 pieces, max_blocks at the most -- beyond that lanes stride)
@@ -127,6 +247,27 @@ void fold2_launch_copy(const uint8_t *src, uint8_t *dst, uint64_t n_bytes, const
   const uint64_t want = (n_docs - 1 + 255) / 256;
   const uint32_t grid = (uint32_t)std::min<uint64_t>(want, std::max<uint32_t>(max_blocks, 1u));
   hipLaunchKernelGGL(k_fold2_fix, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, dst, n_bytes, doc_offsets, n_docs);
+}
+
+// AHA_FOLD3_LIVE_TEST=1 launches the instantiation with the live-lead test; it measured slower on every text, Chinese
+// included, so the default is the one without (read at every launch, so that one process can time both
+// kernels call by call)
+static bool fold3_live_test() {
+  const char *e = getenv("AHA_FOLD3_LIVE_TEST");
+  return e && e[0] == '1' && !e[1];
+}
+
+void fold3_launch_copy(const uint8_t *src, uint8_t *dst, uint64_t n_bytes, const uint64_t *doc_offsets, uint64_t n_docs,
+                       uint32_t max_blocks, void *stream) {
+  if (!n_bytes) return;
+  if (fold3_live_test())
+    hipLaunchKernelGGL(k_fold3_copy<true>, dim3(fold_grid(n_bytes, max_blocks)), dim3(256), 0, (hipStream_t)stream, src, dst, n_bytes);
+  else
+    hipLaunchKernelGGL(k_fold3_copy<false>, dim3(fold_grid(n_bytes, max_blocks)), dim3(256), 0, (hipStream_t)stream, src, dst, n_bytes);
+  if (!doc_offsets || n_docs < 2) return;
+  const uint64_t want = (n_docs - 1 + 255) / 256;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(want, std::max<uint32_t>(max_blocks, 1u));
+  hipLaunchKernelGGL(k_fold3_fix, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, dst, n_bytes, doc_offsets, n_docs);
 }
 
 void fold_launch_copy(const uint8_t *src, uint8_t *dst, uint64_t n_bytes, uint32_t max_blocks, void *stream) {

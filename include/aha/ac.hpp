@@ -84,8 +84,11 @@ class AC {
   // Aha::AC.compile(keys).  fold_ascii: an ASCII case-insensitive handle (AHA_OPT_FOLD_ASCII, aha_hip.h): every call gives what a
   // plain handle compiled from the lower-cased keys gives over the lower-cased text; key(id) keeps the spelling given here.
   // fold_simple: that plus the simple case fold of the two-byte UTF-8 characters (AHA_OPT_FOLD_SIMPLE: Latin-1, Latin
-  // Extended-A/B, Greek, Cyrillic, Armenian), every document folded on its own; such a handle has no feeds and no groups yet
-  static AC compile(const std::vector<std::string> &keys, int device = -1, bool fold_ascii = false, bool fold_simple = false) {
+  // Extended-A/B, Greek, Cyrillic, Armenian), every document folded on its own; such a handle has no feeds and no groups yet.
+  // fold_bmp: that plus the three-byte characters (AHA_OPT_FOLD_BMP: full-width Latin, Vietnamese, polytonic Greek, Georgian,
+  // Cherokee, Glagolitic, Coptic ..), with the same limits
+  static AC compile(const std::vector<std::string> &keys, int device = -1, bool fold_ascii = false, bool fold_simple = false,
+                    bool fold_bmp = false) {
     std::vector<uint8_t> blob;
     std::vector<uint64_t> offs(keys.size() + 1, 0);
     for (size_t i = 0; i < keys.size(); i++) {
@@ -95,7 +98,7 @@ class AC {
     aha_options o{};
     o.struct_size = sizeof(o);
     o.device = device;
-    o.flags = (fold_ascii ? AHA_OPT_FOLD_ASCII : 0u) | (fold_simple ? AHA_OPT_FOLD_SIMPLE : 0u);
+    o.flags = (fold_ascii ? AHA_OPT_FOLD_ASCII : 0u) | (fold_simple ? AHA_OPT_FOLD_SIMPLE : 0u) | (fold_bmp ? AHA_OPT_FOLD_BMP : 0u);
     aha_ac *h = nullptr;
     uint32_t bad = 0;
     int32_t rc = aha_ac_compile(blob.data(), offs.data(), (uint32_t)keys.size(), &o, &h, &bad);
@@ -585,12 +588,13 @@ class AC {
     aha_ac_save(h_, v.data(), (uint64_t)n);
     return v;
   }
-  // (the container stores the keys as spelled and no options: say fold_ascii / fold_simple again)
-  static AC from_bytes(const std::vector<uint8_t> &data, int device = -1, bool fold_ascii = false, bool fold_simple = false) {
+  // (the container stores the keys as spelled and no options: say fold_ascii / fold_simple / fold_bmp again)
+  static AC from_bytes(const std::vector<uint8_t> &data, int device = -1, bool fold_ascii = false, bool fold_simple = false,
+                       bool fold_bmp = false) {
     aha_options o{};
     o.struct_size = sizeof(o);
     o.device = device;
-    o.flags = (fold_ascii ? AHA_OPT_FOLD_ASCII : 0u) | (fold_simple ? AHA_OPT_FOLD_SIMPLE : 0u);
+    o.flags = (fold_ascii ? AHA_OPT_FOLD_ASCII : 0u) | (fold_simple ? AHA_OPT_FOLD_SIMPLE : 0u) | (fold_bmp ? AHA_OPT_FOLD_BMP : 0u);
     aha_ac *h = nullptr;
     int32_t rc = aha_ac_load(data.data(), data.size(), &o, &h);
     if (rc != AHA_OK) throw Error(rc, aha_strerror(rc));
@@ -598,6 +602,7 @@ class AC {
   }
   bool fold_ascii() const { return (aha_ac_flags(h_) & AHA_OPT_FOLD_ASCII) != 0; }
   bool fold_simple() const { return (aha_ac_flags(h_) & AHA_OPT_FOLD_SIMPLE) != 0; }
+  bool fold_bmp() const { return (aha_ac_flags(h_) & AHA_OPT_FOLD_BMP) != 0; }
   aha_ac *handle() const { return h_; }
 
  private:

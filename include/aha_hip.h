@@ -134,6 +134,32 @@ typedef struct {
  * Cost: every engine, the prefix filter included, reads a folded copy made by one streaming pass into scratch (N bytes) and a
  * fix-up of one lane per document boundary (scan_fold.hip). */
 #define AHA_OPT_FOLD_SIMPLE 8u
+/* ... and for the characters UTF-8 writes in three bytes (a pure addition to ABI 8 again; implies AHA_OPT_FOLD_SIMPLE and
+ * AHA_OPT_FOLD_ASCII: 16u alone means what 4u | 8u | 16u means, and aha_ac_flags reports the bits as they were passed).
+ * fold3(buf) is a byte-to-byte map of one buffer, as long as its input.  At every j the first of these that applies: buf[j] in
+ * 0xE0 .. 0xEF, j + 2 < len and buf[j + 1], buf[j + 2] both in 0x80 .. 0xBF -- the triple becomes the UTF-8 of F3(cp), cp =
+ * (b0 & 0xF) << 12 | (b1 & 0x3F) << 6 | (b2 & 0x3F), where 0x800 <= cp <= 0xFFFF and cp is no surrogate; overlong forms and
+ * 0xD800 .. 0xDFFF pass through byte for byte --; the pair rule of fold2 above, with the same table; the ASCII fold.  Triples
+ * cannot overlap each other or a pair.  A rule on bytes: stray continuation bytes, a truncated triple at the end, four-byte
+ * sequences, 0xC0, 0xC1 and 0xF5 .. 0xFF pass through.  F3 (aha_amd/csrc/fold3_table.hpp, written by tools/gen_fold3_table.py
+ * from Unicode 13.0.0) is F's construction with one3(s) = "s is one code point in U+0800 .. U+FFFF, no surrogate": u = upper(c) if
+ * one3(upper(c)) else c, F3(c) = lower(u) if one3(lower(u)) else c.  F3 is idempotent and gives one representative per case
+ * class inside the block; it moves 679 code points in 29 blocks of 64 (Georgian with Mtavruli, Cherokee, Latin Extended Additional with every Vietnamese letter, polytonic Greek, the Roman numerals, the circled letters,
+ * Glagolitic, Latin Extended-C/D, Coptic, Cyrillic Extended-B, the full-width Latin letters), 124 of them to another lead byte
+ * (U+10A0 Georgian E1 82 A0 -> U+2D00 E2 B4 80, U+13A0 Cherokee E1 8E A0 -> U+AB70 EA AD B0); the lead bytes of moved
+ * characters are 0xE1, 0xE2, 0xEA and 0xEF only.  Cherokee lands on its lower-case letters (Unicode's case folding on the
+ * upper-case ones: either names the class).  33 code points have their only partner outside the block -- the Kelvin sign
+ * U+212A (k), the ohm sign U+2126, the Angstrom sign U+212B, U+1E9E (U+00DF), U+1FBE, U+1C80 .. U+1C87, U+2C62, U+2C64 .. U+2C66,
+ * U+2C6D .. U+2C70, U+2C7E, U+2C7F, U+A78D, U+A7AA .. U+A7AE, U+A7B0 .. U+A7B2, U+A7C5 --: folding them would change a length,
+ * so they stay.  Lengths never change and a lead byte stays a lead byte: all offsets are those of the original text.
+ * THE RULE, what is covered and the three exceptions are AHA_OPT_FOLD_SIMPLE's with fold3 for fold2: keys are folded one by one
+ * (two keys equal after fold3 are AHA_E_DUP_KEY at the second, aha_ac_id folds its argument), a batch document by document --
+ * a character cut by a document boundary is not folded --, aha_ac_load takes the flag in `opts` again.
+ * NOT supported yet, AHA_E_INVALID before any device work: aha_feed_open / aha_feed_open_params on such a handle and
+ * aha_group_compile with the flag.
+ * Cost: AHA_OPT_FOLD_SIMPLE's -- one streaming pass into scratch (N bytes) and a fix-up of one lane per document boundary; ASCII
+ * text costs what it costs there, text of three-byte characters about twice that pass (scan_fold.hip). */
+#define AHA_OPT_FOLD_BMP 16u
 
 /* Per-call options mirroring the reference's overloads:
  *   char_offsets = 0: match(seq : Bytes)        src/aha/ac.cr:280-286  (byte offsets)
