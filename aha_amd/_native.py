@@ -32,6 +32,7 @@ AHA_OPT_FORCE_WIDE = 2
 AHA_OPT_FOLD_ASCII = 4
 AHA_OPT_FOLD_SIMPLE = 8
 AHA_OPT_FOLD_BMP = 16
+AHA_OPT_FOLD_KANA = 32
 AHA_COUNT_ACCUMULATE = 1
 AHA_GREP_INVERT = 1
 AHA_FEED_CHARS = 1

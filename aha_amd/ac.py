@@ -222,8 +222,11 @@ class AC:
 
     # -- Aha::AC.compile(keys) src/aha/ac.cr:62-69 ---------------------------
     @classmethod
-    def compile(cls, keys, device=-1, host_only=False, force_wide=False, fold_ascii=False, fold_simple=False, fold_bmp=False):
-        """fold_bmp: fold_simple plus the three-byte UTF-8 characters (AHA_OPT_FOLD_BMP: full-width Latin, Vietnamese, polytonic
+    def compile(cls, keys, device=-1, host_only=False, force_wide=False, fold_ascii=False, fold_simple=False, fold_bmp=False,
+                fold_kana=False):
+        """fold_kana: fold_bmp plus hiragana and half-width katakana matched as katakana (AHA_OPT_FOLD_KANA: length-preserving, so
+        a half-width letter and its voiced mark stay two characters; small and large kana stay apart; the same limits).
+        fold_bmp: fold_simple plus the three-byte UTF-8 characters (AHA_OPT_FOLD_BMP: full-width Latin, Vietnamese, polytonic
         Greek, Georgian, Cherokee, Glagolitic, Coptic ..; the same limits).
         fold_simple: fold_ascii plus the simple case fold of the two-byte UTF-8 characters (AHA_OPT_FOLD_SIMPLE: Latin-1,
         Latin Extended-A/B, Greek, Cyrillic, Armenian; every document folded on its own; no feeds and no groups yet).
@@ -231,11 +234,11 @@ class AC:
         handle compiled from the lower-cased keys gives over the lower-cased text ('A'..'Z' only; offsets are the original
         text's); `redact` keeps the original bytes outside the hits, `m[id]` the keys as spelled here."""
         blob, offs = _pack_keys(keys)
-        return cls.compile_packed(blob, offs, device, host_only, force_wide, fold_ascii, fold_simple, fold_bmp)
+        return cls.compile_packed(blob, offs, device, host_only, force_wide, fold_ascii, fold_simple, fold_bmp, fold_kana)
 
     @classmethod
     def compile_packed(cls, blob, offs, device=-1, host_only=False, force_wide=False, fold_ascii=False, fold_simple=False,
-                       fold_bmp=False):
+                       fold_bmp=False, fold_kana=False):
         blob = np.ascontiguousarray(blob, dtype=np.uint8)
         offs = np.ascontiguousarray(offs, dtype=np.uint64)
         opts = N.aha_options()
@@ -243,7 +246,7 @@ class AC:
         opts.device = device
         opts.flags = ((N.AHA_OPT_HOST_ONLY if host_only else 0) | (N.AHA_OPT_FORCE_WIDE if force_wide else 0) |
                       (N.AHA_OPT_FOLD_ASCII if fold_ascii else 0) | (N.AHA_OPT_FOLD_SIMPLE if fold_simple else 0) |
-                      (N.AHA_OPT_FOLD_BMP if fold_bmp else 0))
+                      (N.AHA_OPT_FOLD_BMP if fold_bmp else 0) | (N.AHA_OPT_FOLD_KANA if fold_kana else 0))
         h = C.c_void_p()
         ek = C.c_uint32(0)
         rc = N.lib().aha_ac_compile(_ptr(blob), _ptr(offs), len(offs) - 1, C.byref(opts), C.byref(h),
@@ -276,8 +279,9 @@ class AC:
                 f.write(data)
 
     @classmethod
-    def from_bytes(cls, data, device=-1, host_only=False, force_wide=False, fold_ascii=False, fold_simple=False, fold_bmp=False):
-        """The container stores the keys as they were spelled and no options: say fold_ascii / fold_simple / fold_bmp again, like
+    def from_bytes(cls, data, device=-1, host_only=False, force_wide=False, fold_ascii=False, fold_simple=False, fold_bmp=False,
+                   fold_kana=False):
+        """The container stores the keys as they were spelled and no options: say fold_ascii / fold_simple / fold_bmp / fold_kana again, like
         force_wide."""
         buf = np.frombuffer(bytes(data), dtype=np.uint8)
         opts = N.aha_options()
@@ -285,7 +289,7 @@ class AC:
         opts.device = device
         opts.flags = ((N.AHA_OPT_HOST_ONLY if host_only else 0) | (N.AHA_OPT_FORCE_WIDE if force_wide else 0) |
                       (N.AHA_OPT_FOLD_ASCII if fold_ascii else 0) | (N.AHA_OPT_FOLD_SIMPLE if fold_simple else 0) |
-                      (N.AHA_OPT_FOLD_BMP if fold_bmp else 0))
+                      (N.AHA_OPT_FOLD_BMP if fold_bmp else 0) | (N.AHA_OPT_FOLD_KANA if fold_kana else 0))
         h = C.c_void_p()
         rc = N.lib().aha_ac_load(_ptr(buf), buf.size, C.byref(opts), C.byref(h))
         if rc != N.AHA_OK:
@@ -325,6 +329,11 @@ class AC:
     def fold_bmp(self):
         """True for a handle compiled (or loaded) with fold_bmp=True."""
         return bool(N.lib().aha_ac_flags(self._h) & N.AHA_OPT_FOLD_BMP)
+
+    @property
+    def fold_kana(self):
+        """True for a handle compiled (or loaded) with fold_kana=True."""
+        return bool(N.lib().aha_ac_flags(self._h) & N.AHA_OPT_FOLD_KANA)
 
     # -- delegate :[] src/aha/ac.cr:41-43 ------------------------------------
     def __getitem__(self, x):
@@ -1335,7 +1344,7 @@ class AC:
         """n_seqs open sequences matched piece by piece (aha_feed_open): see Feed.  chars: offsets and bases in characters.
         sep: a BitArray -- the feed's match and count calls apply the separator filter of match(seq, sep) to the whole sequence
         (aha_feed_open_params): a hit is reported one byte late, and Feed.finish ends a sequence.  A handle compiled with
-        fold_simple or fold_bmp has no feeds yet: the library's AHA_E_INVALID is raised."""
+        fold_simple, fold_bmp or fold_kana has no feeds yet: the library's AHA_E_INVALID is raised."""
         h = C.c_void_p()
         if sep is None:
             rc = N.lib().aha_feed_open(self._h, int(n_seqs), N.AHA_FEED_CHARS if chars else 0, C.byref(h))

@@ -309,13 +309,14 @@ int32_t aha_ac_compile(const uint8_t *key_bytes, const uint64_t *key_offsets, ui
   uint32_t flags = opts ? opts->flags : 0;
   int device = opts ? opts->device : -1;
   aha_ac *ac = new aha_ac();
-  ac->opt_flags = flags & (AHA_OPT_HOST_ONLY | AHA_OPT_FORCE_WIDE | AHA_OPT_FOLD_ASCII | AHA_OPT_FOLD_SIMPLE | AHA_OPT_FOLD_BMP);
+  ac->opt_flags = flags & (AHA_OPT_HOST_ONLY | AHA_OPT_FORCE_WIDE | AHA_OPT_FOLD_ASCII | AHA_OPT_FOLD_SIMPLE | AHA_OPT_FOLD_BMP |
+                             AHA_OPT_FOLD_KANA);
   BuildError be;
   static const uint8_t dummy = 0;
   // AHA_OPT_FOLD_ASCII: the automaton -- and with it both images, the filter, the stale ends and the duplicate check (two keys
   // equal after folding: AHA_E_DUP_KEY at the second) -- is built from a folded copy of the keys; the handle keeps the
   // caller's spelling beside it.  AHA_OPT_FOLD_SIMPLE: the same with fold2 of every key on its own (fold.hpp),
-  // AHA_OPT_FOLD_BMP: with fold3 of it
+  // AHA_OPT_FOLD_BMP: with fold3 of it, AHA_OPT_FOLD_KANA: with foldk of it
   // (only the keys' own bytes [offs[0], offs[K]) are copied, with the offsets rebased as build_automaton rebases them)
   std::vector<uint8_t> folded;
   std::vector<uint64_t> rebased;
@@ -335,7 +336,7 @@ int32_t aha_ac_compile(const uint8_t *key_bytes, const uint64_t *key_offsets, ui
       // (offsets that do not ascend are build_automaton's to refuse: such a key is left as it is)
       for (uint32_t k = 0; k < n_keys; k++)
         if (rebased[k] <= rebased[k + 1] && rebased[k + 1] <= folded.size())
-          (mode == 3 ? fold3_bytes : fold2_bytes)(folded.data() + rebased[k], rebased[k + 1] - rebased[k]);
+          (mode == 4 ? foldk_bytes : mode == 3 ? fold3_bytes : fold2_bytes)(folded.data() + rebased[k], rebased[k + 1] - rebased[k]);
     } else {
       fold_bytes(folded.data(), folded.size());
     }
@@ -709,7 +710,9 @@ int32_t aha_ac_id(const aha_ac *ac, const uint8_t *key, int32_t len) {
   if (ac->fold() && len > 0) {
     try {
       std::vector<uint8_t> q(key, key + len);
-      if (ac->fold_mode() == 3)
+      if (ac->fold_mode() == 4)
+        foldk_bytes(q.data(), q.size());
+      else if (ac->fold_mode() == 3)
         fold3_bytes(q.data(), q.size());
       else if (ac->fold_mode() == 2)
         fold2_bytes(q.data(), q.size());

@@ -257,14 +257,16 @@ static void *cover_reserve(Scratch *sc, CoverSlot slot, size_t bytes) { return r
 
 // The kernels read a text in aligned 16-byte pieces, and a folded handle (AHA_OPT_FOLD_ASCII) matches the folded text: *text
 // becomes its copy in `dst` (n_bytes + 64 bytes of scratch), a plain device-to-device copy (~0.7 ms per GiB: about a fifth of
-// a match) or, with `fold` (the handle's fold mode: 1 ASCII, 2 simple, 3 BMP), the one streaming pass that does both jobs
-// (scan_fold.hip).  The simple and the BMP fold are those of every document on its own: doc_off (device) are the n_docs + 1 offsets of
+// a match) or, with `fold` (the handle's fold mode: 1 ASCII, 2 simple, 3 BMP, 4 kana), the one streaming pass that does both jobs
+// (scan_fold.hip).  The simple, the BMP and the kana fold are those of every document on its own: doc_off (device) are the n_docs + 1 offsets of
 // exactly these n_bytes, a batch or a range of whole documents.  The caller's text is only read.
 static int32_t stage_text(aha_ac *ac, const uint8_t **text, uint64_t n_bytes, void *dst, int fold, const uint64_t *doc_off,
                           uint64_t n_docs, hipStream_t s) {
   if (fold) {
     const uint32_t max_blocks = 8u * std::max<uint32_t>(ac->v2_grid, 64u);
-    if (fold == 3)
+    if (fold == 4)
+      foldk_launch_copy(*text, (uint8_t *)dst, n_bytes, doc_off, n_docs, max_blocks, s);
+    else if (fold == 3)
       fold3_launch_copy(*text, (uint8_t *)dst, n_bytes, doc_off, n_docs, max_blocks, s);
     else if (fold == 2)
       fold2_launch_copy(*text, (uint8_t *)dst, n_bytes, doc_off, n_docs, max_blocks, s);
@@ -284,7 +286,7 @@ static int32_t stage_batch(aha_ac *ac, Scratch *sc, const uint8_t **text, uint64
   return stage_text(ac, text, n_bytes, sc->v2buf[kText].p, fold, doc_off, n_docs, s);
 }
 // M.fold (the fold mode): M.text is still the caller's.  Only the prefix-filter engine takes it like that, and only the ASCII
-// fold (it folds in its own loads; with the simple and the BMP fold it reads the staged copy like everyone else: match_v2); every
+// fold (it folds in its own loads; with the simple, the BMP and the kana fold -- M.fold >= 2 -- it reads the staged copy like everyone else: match_v2); every
 // other path -- the byte-level and character-level engines, the opt-in ones, the two-pass engine, match_longest, a pass
 // behind a hand-back of the filter -- calls this first: the copy is made at that moment, once per call.
 static int32_t stage_folded(aha_ac *ac, Scratch *sc, MatchArgs &M, hipStream_t s) {

@@ -923,6 +923,12 @@ int32_t aha_feed_open_params(aha_ac *ac, uint32_t n_seqs, uint32_t flags, const 
       return AHA_E_INVALID;
     }
   }
+  if (ac->fold_mode() == 4) {  // (before any device work, host-only handles included)
+    tls_err = "aha_feed_open: no feed on a handle compiled with AHA_OPT_FOLD_KANA yet: a two- or three-byte character may be cut "
+              "between two calls, and the context a feed keeps would have to carry part of it (a follow-up; fold the pieces' "
+              "sequences whole, or use AHA_OPT_FOLD_ASCII)";
+    return AHA_E_INVALID;
+  }
   if (ac->fold_mode() == 3) {  // (before any device work, host-only handles included)
     tls_err = "aha_feed_open: no feed on a handle compiled with AHA_OPT_FOLD_BMP yet: a two- or three-byte character may be cut "
               "between two calls, and the context a feed keeps would have to carry part of it (a follow-up; fold the pieces' "

@@ -1,5 +1,5 @@
-// fold.hpp -- the case folds of AHA_OPT_FOLD_ASCII, AHA_OPT_FOLD_SIMPLE and AHA_OPT_FOLD_BMP (include/aha_hip.h), host and
-// device.  The ONLY place the rules are written down.
+// fold.hpp -- the case folds of AHA_OPT_FOLD_ASCII, AHA_OPT_FOLD_SIMPLE and AHA_OPT_FOLD_BMP and the kana fold of
+// AHA_OPT_FOLD_KANA (include/aha_hip.h), host and device.  The ONLY place the rules are written down.
 // ASCII: fold(b) = b + 32 for 0x41 <= b <= 0x5A ('A' .. 'Z'), b otherwise.  Bytes >= 0x80, '@', '[', '`' and '{' stay,
 // lengths and UTF-8 lead bytes never change.  Compile folds a copy of the keys with it (capi.cpp), the prefix-filter engine
 // folds its text loads (scan_filter.hip), every other engine reads a copy folded on the way (scan_fold.hip).
@@ -16,12 +16,16 @@
 // neighbours on each side (fold3_byte).  A truncated triple, four-byte sequences and 0xF5 .. 0xFF stay.  33 code points whose
 // only case partner is written in another number of bytes (the Kelvin, ohm and Angstrom signs, U+1E9E, U+1C80 .. U+1C87,
 // U+2C62 and others: include/aha_hip.h has the list) stay.
+// KANA (AHA_OPT_FOLD_KANA): foldk is fold3 with FK for F3 (foldk_table.hpp): FK(cp) = K(cp) where K moves cp -- hiragana U+3041 ..
+// U+3096, U+309D, U+309E and the half-width katakana U+FF66 .. U+FF9D, each to its katakana letter --, else F3(cp).  The byte
+// logic is fold3's; only the tables differ (Fold3Tables); the device pass is scan_foldk.hip.
 #pragma once
 #include <cstddef>
 #include <cstdint>
 
 #include "fold3_table.hpp"
 #include "fold_table.hpp"
+#include "foldk_table.hpp"
 
 #ifndef AHA_HD
 #if defined(__HIPCC__)
@@ -88,8 +92,8 @@ inline void fold2_bytes(uint8_t *p, size_t n) {
 // ---- the fold of the three-byte characters (AHA_OPT_FOLD_BMP): the two-byte table, and F3 in two levels (fold3_table.hpp)
 struct Fold3Tables {
   const uint16_t *pair;   // kFold2Table or its copy in LDS
-  const uint8_t *index;   // kFold3Index
-  const uint16_t *live;   // kFold3Live
+  const uint8_t *index;   // kFold3Index -- or kFoldKIndex: the same form, FK for F3
+  const uint16_t *live;   // kFold3Live / kFoldKLive
 };
 AHA_HD inline bool fold3_lead(uint32_t b) { return (b & 0xF0u) == 0xE0u; }      // 0xE0 .. 0xEF
 // F3(cp) of the triple (lead, c1, c2), all three hold; an overlong form (cp < 0x800) is its own fold, and so is a surrogate
@@ -123,9 +127,8 @@ AHA_HD inline uint8_t fold3_byte(const Fold3Tables &T, uint32_t prev2, uint32_t 
   return fold8((uint8_t)cur);
 }
 
-// fold3 of one buffer in place (one key, one document): the host's statement of the rule
-inline void fold3_bytes(uint8_t *p, size_t n) {
-  const Fold3Tables T = {kFold2Table, kFold3Index, kFold3Live};
+// fold3 of one buffer in place (one key, one document) with the tables T: the host's statement of the rule
+inline void fold3_bytes_with(const Fold3Tables &T, uint8_t *p, size_t n) {
   for (size_t i = 0; i < n; i++) {
     if (fold3_lead(p[i]) && i + 2 < n && fold2_cont(p[i + 1]) && fold2_cont(p[i + 2])) {
       const uint32_t f = fold3_triple(T, p[i], p[i + 1], p[i + 2]);
@@ -134,7 +137,7 @@ inline void fold3_bytes(uint8_t *p, size_t n) {
       p[i + 2] = (uint8_t)(0x80u | (f & 0x3Fu));
       i += 2;
     } else if (fold2_lead(p[i]) && i + 1 < n && fold2_cont(p[i + 1])) {
-      const uint32_t f = fold2_pair(kFold2Table, p[i], p[i + 1]);
+      const uint32_t f = fold2_pair(T.pair, p[i], p[i + 1]);
       p[i] = (uint8_t)(0xC0u | (f >> 6));
       p[i + 1] = (uint8_t)(0x80u | (f & 0x3Fu));
       i++;
@@ -142,6 +145,13 @@ inline void fold3_bytes(uint8_t *p, size_t n) {
       p[i] = fold8(p[i]);
     }
   }
+}
+inline void fold3_bytes(uint8_t *p, size_t n) { fold3_bytes_with(Fold3Tables{kFold2Table, kFold3Index, kFold3Live}, p, n); }
+// foldk of one buffer in place (AHA_OPT_FOLD_KANA): the same rule over FK's tables
+inline void foldk_bytes(uint8_t *p, size_t n) { fold3_bytes_with(Fold3Tables{kFold2Table, kFoldKIndex, kFoldKLive}, p, n); }
+// ... and one byte of it from the byte and its neighbours
+inline uint8_t foldk_byte(uint32_t prev2, uint32_t prev, uint32_t cur, uint32_t next, uint32_t next2) {
+  return fold3_byte(Fold3Tables{kFold2Table, kFoldKIndex, kFoldKLive}, prev2, prev, cur, next, next2);
 }
 
 }  // namespace aha

@@ -258,6 +258,11 @@ int32_t aha_group_compile(const uint8_t *key_bytes, const uint64_t *key_offsets,
                           int32_t n_devices, uint32_t flags, aha_group **out, uint32_t *err_key) {
   if (!out || !devices || n_devices <= 0 || n_devices > 64) return AHA_E_INVALID;
   *out = nullptr;
+  if (flags & AHA_OPT_FOLD_KANA) {  // (before anything is compiled or any device is touched)
+    aha_internal_set_error("aha_group_compile: no group with AHA_OPT_FOLD_KANA yet: the shards cut the batch, and the fold of the two- "
+              "and three-byte characters goes document by document (a follow-up; AHA_OPT_FOLD_ASCII is supported)");
+    return AHA_E_INVALID;
+  }
   if (flags & AHA_OPT_FOLD_BMP) {  // (before anything is compiled or any device is touched)
     aha_internal_set_error("aha_group_compile: no group with AHA_OPT_FOLD_BMP yet: the shards cut the batch, and the fold of the two- "
               "and three-byte characters goes document by document (a follow-up; AHA_OPT_FOLD_ASCII is supported)");

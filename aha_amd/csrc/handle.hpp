@@ -269,11 +269,12 @@ struct aha_ac {
   }
   const uint64_t serial = next_serial();  // one per handle ever made in this process (a replacement table names its handle by it)
   std::vector<uint8_t> key_spelling;
-  bool fold() const { return (opt_flags & (AHA_OPT_FOLD_ASCII | AHA_OPT_FOLD_SIMPLE | AHA_OPT_FOLD_BMP)) != 0; }  // any fold
+  bool fold() const { return (opt_flags & (AHA_OPT_FOLD_ASCII | AHA_OPT_FOLD_SIMPLE | AHA_OPT_FOLD_BMP | AHA_OPT_FOLD_KANA)) != 0; }  // any fold
   // which one: 0 none, 1 ASCII (fold8), 2 simple (fold2: AHA_OPT_FOLD_SIMPLE implies the ASCII fold), 3 BMP (fold3:
-  // AHA_OPT_FOLD_BMP implies both)
+  // AHA_OPT_FOLD_BMP implies both), 4 kana (foldk: AHA_OPT_FOLD_KANA implies all three).  >= 2: every engine reads a staged
+  // copy, >= 3: three-byte characters take part; == 4: FK's tables and the kernel of their own
   int fold_mode() const {
-    return (opt_flags & AHA_OPT_FOLD_BMP) ? 3 : (opt_flags & AHA_OPT_FOLD_SIMPLE) ? 2 : (opt_flags & AHA_OPT_FOLD_ASCII) ? 1 : 0;
+    return (opt_flags & AHA_OPT_FOLD_KANA) ? 4 : (opt_flags & AHA_OPT_FOLD_BMP) ? 3 : (opt_flags & AHA_OPT_FOLD_SIMPLE) ? 2 : (opt_flags & AHA_OPT_FOLD_ASCII) ? 1 : 0;
   }
   Image img;  // host copy of the device image (export / debugging)
   uint32_t n_slots = 0;

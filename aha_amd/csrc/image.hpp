@@ -79,7 +79,7 @@ struct MatchArgs {
   int32_t cover_clear;               // host side: the pass clears the mask itself, once it knows the offsets are good
   // host side, a handle compiled with AHA_OPT_FOLD_ASCII: `text` is still the caller's (16-byte aligned) and not folded yet.  The
   // prefix-filter engine reads it as it is and folds in its loads; every other path takes the folded copy first (engine.cpp
-  // stage_folded), which clears this.  The value is the handle's fold mode (handle.hpp): 1 ASCII, 2 simple, 3 BMP -- with 2 and 3 the
+  // stage_folded), which clears this.  The value is the handle's fold mode (handle.hpp): 1 ASCII, 2 simple, 3 BMP, 4 kana -- from 2 on the
   // prefix-filter engine takes the folded copy too (its loads fold ASCII only)
   int32_t fold;
 };
@@ -240,6 +240,14 @@ void fold2_launch_copy(const uint8_t *src, uint8_t *dst, uint64_t n_bytes, const
                        uint32_t max_blocks, void *stream);
 // ... with AHA_OPT_FOLD_BMP: dst = fold3 of every document of src on its own, the same arguments
 void fold3_launch_copy(const uint8_t *src, uint8_t *dst, uint64_t n_bytes, const uint64_t *doc_offsets, uint64_t n_docs,
+                       uint32_t max_blocks, void *stream);
+// (the second step of it alone, and the grid of the staged copies: a workgroup per 1024 pieces, max_blocks at the most)
+void fold3_launch_fix(const uint8_t *src, uint8_t *dst, uint64_t n_bytes, const uint64_t *doc_offsets, uint64_t n_docs,
+                      uint32_t max_blocks, void *stream);
+uint32_t fold_grid(uint64_t n_bytes, uint32_t max_blocks);
+// ... with AHA_OPT_FOLD_KANA: dst = foldk of every document of src on its own, the same arguments (a kernel of its own,
+// scan_foldk.hip)
+void foldk_launch_copy(const uint8_t *src, uint8_t *dst, uint64_t n_bytes, const uint64_t *doc_offsets, uint64_t n_docs,
                        uint32_t max_blocks, void *stream);
 
 size_t v2_lds_bytes(uint32_t lds_slots, bool compact);

@@ -41,6 +41,7 @@ lib LibAhaHip
   OPT_FOLD_ASCII = 4_u32 # compile-time flag: 'A'..'Z' of keys and text match as 'a'..'z' (include/aha_hip.h)
   OPT_FOLD_SIMPLE = 8_u32 # ... and the two-byte UTF-8 characters by their simple case fold, document by document; no feeds, no groups yet
   OPT_FOLD_BMP = 16_u32 # ... and the three-byte ones (full-width Latin, Vietnamese, polytonic Greek, Georgian, Cherokee ..); implies both; no feeds, no groups yet
+  OPT_FOLD_KANA = 32_u32 # ... and hiragana and half-width katakana as katakana (length-preserving; no voiced half-width sequences); implies all three; no feeds, no groups yet
 
   struct Options
     struct_size : UInt32

@@ -86,9 +86,10 @@ class AC {
   // fold_simple: that plus the simple case fold of the two-byte UTF-8 characters (AHA_OPT_FOLD_SIMPLE: Latin-1, Latin
   // Extended-A/B, Greek, Cyrillic, Armenian), every document folded on its own; such a handle has no feeds and no groups yet.
   // fold_bmp: that plus the three-byte characters (AHA_OPT_FOLD_BMP: full-width Latin, Vietnamese, polytonic Greek, Georgian,
-  // Cherokee, Glagolitic, Coptic ..), with the same limits
+  // Cherokee, Glagolitic, Coptic ..), with the same limits.  fold_kana: that plus hiragana and half-width katakana matched as
+  // katakana (AHA_OPT_FOLD_KANA: length-preserving, so a half-width letter and its voiced mark stay two characters)
   static AC compile(const std::vector<std::string> &keys, int device = -1, bool fold_ascii = false, bool fold_simple = false,
-                    bool fold_bmp = false) {
+                    bool fold_bmp = false, bool fold_kana = false) {
     std::vector<uint8_t> blob;
     std::vector<uint64_t> offs(keys.size() + 1, 0);
     for (size_t i = 0; i < keys.size(); i++) {
@@ -98,7 +99,8 @@ class AC {
     aha_options o{};
     o.struct_size = sizeof(o);
     o.device = device;
-    o.flags = (fold_ascii ? AHA_OPT_FOLD_ASCII : 0u) | (fold_simple ? AHA_OPT_FOLD_SIMPLE : 0u) | (fold_bmp ? AHA_OPT_FOLD_BMP : 0u);
+    o.flags = (fold_ascii ? AHA_OPT_FOLD_ASCII : 0u) | (fold_simple ? AHA_OPT_FOLD_SIMPLE : 0u) | (fold_bmp ? AHA_OPT_FOLD_BMP : 0u) |
+              (fold_kana ? AHA_OPT_FOLD_KANA : 0u);
     aha_ac *h = nullptr;
     uint32_t bad = 0;
     int32_t rc = aha_ac_compile(blob.data(), offs.data(), (uint32_t)keys.size(), &o, &h, &bad);
@@ -588,13 +590,14 @@ class AC {
     aha_ac_save(h_, v.data(), (uint64_t)n);
     return v;
   }
-  // (the container stores the keys as spelled and no options: say fold_ascii / fold_simple / fold_bmp again)
+  // (the container stores the keys as spelled and no options: say fold_ascii / fold_simple / fold_bmp / fold_kana again)
   static AC from_bytes(const std::vector<uint8_t> &data, int device = -1, bool fold_ascii = false, bool fold_simple = false,
-                       bool fold_bmp = false) {
+                       bool fold_bmp = false, bool fold_kana = false) {
     aha_options o{};
     o.struct_size = sizeof(o);
     o.device = device;
-    o.flags = (fold_ascii ? AHA_OPT_FOLD_ASCII : 0u) | (fold_simple ? AHA_OPT_FOLD_SIMPLE : 0u) | (fold_bmp ? AHA_OPT_FOLD_BMP : 0u);
+    o.flags = (fold_ascii ? AHA_OPT_FOLD_ASCII : 0u) | (fold_simple ? AHA_OPT_FOLD_SIMPLE : 0u) | (fold_bmp ? AHA_OPT_FOLD_BMP : 0u) |
+              (fold_kana ? AHA_OPT_FOLD_KANA : 0u);
     aha_ac *h = nullptr;
     int32_t rc = aha_ac_load(data.data(), data.size(), &o, &h);
     if (rc != AHA_OK) throw Error(rc, aha_strerror(rc));
@@ -603,6 +606,7 @@ class AC {
   bool fold_ascii() const { return (aha_ac_flags(h_) & AHA_OPT_FOLD_ASCII) != 0; }
   bool fold_simple() const { return (aha_ac_flags(h_) & AHA_OPT_FOLD_SIMPLE) != 0; }
   bool fold_bmp() const { return (aha_ac_flags(h_) & AHA_OPT_FOLD_BMP) != 0; }
+  bool fold_kana() const { return (aha_ac_flags(h_) & AHA_OPT_FOLD_KANA) != 0; }
   aha_ac *handle() const { return h_; }
 
  private:

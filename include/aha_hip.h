@@ -130,7 +130,8 @@ typedef struct {
  * replicate and export.  Two keys equal after fold2 are AHA_E_DUP_KEY at the second; aha_ac_id folds its argument with
  * fold2; aha_ac_load takes the flag in `opts` again.
  * NOT supported yet, AHA_E_INVALID before any device work: aha_feed_open / aha_feed_open_params on such a handle (a character
- * may be cut between two calls) and aha_group_compile with the flag (the shards cut the batch).
+ * may be cut between two calls) and aha_group_compile with the flag (the shards cut the batch).  The same holds with
+ * AHA_OPT_FOLD_KANA below.
  * Cost: every engine, the prefix filter included, reads a folded copy made by one streaming pass into scratch (N bytes) and a
  * fix-up of one lane per document boundary (scan_fold.hip). */
 #define AHA_OPT_FOLD_SIMPLE 8u
@@ -156,10 +157,36 @@ typedef struct {
  * (two keys equal after fold3 are AHA_E_DUP_KEY at the second, aha_ac_id folds its argument), a batch document by document --
  * a character cut by a document boundary is not folded --, aha_ac_load takes the flag in `opts` again.
  * NOT supported yet, AHA_E_INVALID before any device work: aha_feed_open / aha_feed_open_params on such a handle and
- * aha_group_compile with the flag.
+ * aha_group_compile with the flag.  The same holds with AHA_OPT_FOLD_KANA below.
  * Cost: AHA_OPT_FOLD_SIMPLE's -- one streaming pass into scratch (N bytes) and a fix-up of one lane per document boundary; ASCII
  * text costs what it costs there, text of three-byte characters about twice that pass (scan_fold.hip). */
 #define AHA_OPT_FOLD_BMP 16u
+/* ... and for the three scripts Japanese text spells its kana in (a pure addition to ABI 8 again; implies AHA_OPT_FOLD_BMP and
+ * through it AHA_OPT_FOLD_SIMPLE and AHA_OPT_FOLD_ASCII: 32u alone means what 4u | 8u | 16u | 32u means, and aha_ac_flags reports
+ * the bits as they were passed): a key list in katakana hits text spelled in hiragana or in half-width katakana.
+ * foldk(buf) is fold3(buf) with FK in place of F3 for the triples; pairs, ASCII and everything that passes through are
+ * unchanged.  FK(cp) = K(cp) where K moves cp, else F3(cp).  K maps these 144 code points and nothing else:
+ *   hiragana U+3041 .. U+3096            -> cp + 0x60, the katakana letters U+30A1 .. U+30F6
+ *   the iteration marks U+309D, U+309E   -> U+30FD, U+30FE
+ *   half-width katakana U+FF66 .. U+FF9D -> the one code point NFKC gives (U+FF71 -> U+30A2, the long-vowel mark U+FF70 -> U+30FC)
+ * FK is committed as data (aha_amd/csrc/foldk_table.hpp, written by tools/gen_foldk_table.py from Unicode 13.0.0, in
+ * fold3_table.hpp's two levels: F3's 29 live blocks and those of U+3040, U+3080, U+FF40 and U+FF80).  Every image is a
+ * three-byte KATAKANA character, no image is a source of K, no source or image has a case mapping: FK is idempotent, K and F3
+ * never meet.  The half-width kana change their lead byte (EF -> E3), hiragana their second or third byte; lengths never change
+ * and a lead byte stays a lead byte, so all offsets, masks, selections and substituted copies are those of the original text.
+ * Limits: the representative is katakana.  A half-width letter followed by a voiced or semi-voiced mark (U+FF76 U+FF9E, six
+ * bytes) does NOT become the voiced letter (U+30AC, three bytes): that would change a length; it folds to U+30AB followed by
+ * the unchanged U+FF9E.  U+FF9E and U+FF9F stay.  Small and large kana stay apart.  U+30F7 .. U+30FA, U+309F, U+30FF and the
+ * combining marks U+3099, U+309A stay.  No normalisation takes place.
+ * THE RULE, what is covered and the three exceptions are AHA_OPT_FOLD_BMP's with foldk for fold3: keys are folded one by one
+ * (two keys equal after foldk -- U+3042 and U+30A2, U+FF71 and U+30A2 -- are AHA_E_DUP_KEY at the second, aha_ac_id folds its
+ * argument), a batch document by document -- a character cut by a document boundary is not folded --, aha_ac_load takes the
+ * flag in `opts` again and aha_ac_replicate copies it.  Every batch call family is covered.
+ * NOT supported yet, AHA_E_INVALID before any device work: aha_feed_open / aha_feed_open_params on such a handle and
+ * aha_group_compile with the flag.
+ * Cost: AHA_OPT_FOLD_BMP's, by a kernel of its own (scan_foldk.hip k_foldk_copy; AHA_FOLDK_HALO=mem|lane chooses how a lane
+ * gets the bytes around its piece). */
+#define AHA_OPT_FOLD_KANA 32u
 
 /* Per-call options mirroring the reference's overloads:
  *   char_offsets = 0: match(seq : Bytes)        src/aha/ac.cr:280-286  (byte offsets)
