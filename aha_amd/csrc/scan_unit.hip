@@ -112,7 +112,7 @@ __global__ __launch_bounds__(kV2Threads) void ku_traverse(UnitDev U, V2Args M) {
     const int64_t e = live ? min(a + S, N) : a;
     uint64_t dn = 0;
     int64_t nb = INT64_MAX, doc_start = a, pos = e;
-    // Events leave through a buffer of 64 records per wave in LDS and go out 512 bytes at a time into the wave's part
+    // Events leave through a buffer of 64 records per wave in LDS and go out up to 768 bytes at a time into the wave's part
     // of the event space (the regions of its 64 chunks, taken together), tagged with the lane: a store per lane and event
     // into the lane's own region put a scattered 8-byte store -- and its acknowledgement, which the next probe waits for
     // through the shared vmcnt -- into almost every trip (-0.28 ms per GiB on cfg 3, profiles/r03_unit_lab.txt).
@@ -341,36 +341,31 @@ __global__ __launch_bounds__(kV2Threads) void ku_traverse(UnitDev U, V2Args M) {
           const uint64_t evm = wballot(evc != 0u);
           if (evm) {
             // (a lane may send more than its region holds -- the call is repeated with larger regions then, see below --
-            // but a wave never writes beyond its part: blocks past it are dropped)
+            // but a wave never writes beyond its part: records past it are dropped)
             const bool ev = evc != 0u;
+            // The buffer is emptied BEFORE an insert it cannot take (the wfill records it holds go out: up to 64, like the
+            // rest after the last round), so an insert never wraps: one masked block and a 24-bit multiply-add for the
+            // address, instead of a compare on the place, a second block behind the flush and a 64-bit one (-1.7 % on
+            // cfg 3, profiles/trip_trim.txt).  The records leave in the same order.
+            const uint32_t kp = __popcll(evm);
+            if (wfill + kp > 64u) {
+              const uint32_t *q = reinterpret_cast<const uint32_t *>(smem + (wbo + __umul24((uint32_t)lane, 12u)));
+              const v3u r = {q[0], q[1], q[2]};
+              if ((uint32_t)lane < wfill && wout + (uint32_t)lane < wcap) *reinterpret_cast<v3u *>(wreg + (size_t)(wout + lane) * 3) = r;
+              wout += wfill;
+              wfill = 0;
+            }
             const uint32_t my = wfill + __builtin_amdgcn_mbcnt_hi((uint32_t)(evm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)evm, 0u));
             // {END state | lane | hits it stands for, end offset in the document, hits of the chunk before it}
             const uint32_t rx = u_rec_x(u_child(E, BB), (uint32_t)lane, evc, BB), rz = u_rec_z(hits, evc, BB);
             const uint32_t ry = CHARS ? ((lc << 1) | lc_exact) : (uint32_t)(docrel + (int32_t)rel);
-            if (ev && my < 64u) {
+            if (ev) {  // (my < 64)
               uint32_t *d = reinterpret_cast<uint32_t *>(smem + (wbo + __umul24(my, 12u)));
               d[0] = rx;
               d[1] = ry;
               d[2] = rz;
             }
-            const uint32_t kp = __popcll(evm);
-            if (wfill + kp >= 64u) {
-              const uint32_t *q = reinterpret_cast<const uint32_t *>(smem + (wbo + __umul24((uint32_t)lane, 12u)));
-              const v3u r = {q[0], q[1], q[2]};
-#ifndef AHA_KU_LAB_NOFLUSH  // (lab, timing only: what the flush's store costs the trips behind it)
-              if (wout + 64u <= wcap) *reinterpret_cast<v3u *>(wreg + (size_t)(wout + lane) * 3) = r;
-#else
-              if (wout + 64u == 0xFFFFFFF0u) *reinterpret_cast<v3u *>(wreg + (size_t)(wout + lane) * 3) = r;
-#endif
-              wout += 64u;
-              if (ev && my >= 64u) {
-                uint32_t *d = reinterpret_cast<uint32_t *>(smem + (wbo + __umul24(my - 64u, 12u)));
-                d[0] = rx;
-                d[1] = ry;
-                d[2] = rz;
-              }
-            }
-            wfill = (wfill + kp) & 63u;
+            wfill += kp;
             seq += ev ? 1u : 0u;
             hits += evc;
           }

@@ -1,32 +1,83 @@
 """Audit of the hand-issued loads of ku_traverse (scan_unit.hip), ks_traverse (scan_skip.hip) and k2d_expand_dense (scan_v2.hip): an asm load is invisible to hipcc's wait insertion, and its
 destination registers count as written at the end of the asm statement -- so nothing may read, copy or overwrite them between
 the load and the hand-written s_waitcnt that names them (cdna_hip_programming.md 5.7, item 1).  Compiles the two files to
-ISA and checks every `global_load_dword*` that sits inside an ASMSTART/ASMEND pair.  Exit code 1 on a violation."""
+ISA and checks every `global_load_dword*` that sits anywhere inside an ASMSTART/ASMEND pair; a statement that masks its load
+(ku_traverse: only the probing lanes ask) must restore exec before it ends.  Exit code 1 on a violation."""
 import os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def exec_kept(lines, start, end):
+    """The asm statement lines[start..end] (#ASMSTART .. #ASMEND) may mask its loads: every write of exec in it must sit between
+    a save of exec into an SGPR pair (s_mov_b64 s[..], exec or s_*_saveexec_b64 s[..], ..) and, as the statement's last write of
+    exec, `s_mov_b64 exec, <that pair>` -- with the pair left alone in between."""
+    saved, bad, dirty = None, [], False
+    for j in range(start + 1, end):
+        body = lines[j].split(";")[0].strip()
+        if not body:
+            continue
+        ops = body.replace(",", " ").split()
+        op, dst = ops[0], ops[1] if len(ops) > 1 else ""
+        if op == "s_mov_b64" and dst == "exec":
+            if saved is None:
+                bad.append((j + 1, f"{body}   <- exec written in an asm statement that has not saved it"))
+            dirty = saved is None or ops[2] != saved
+        elif re.match(r"s_\w+_saveexec_b64$", op) or (op == "s_mov_b64" and ops[2:3] == ["exec"]):
+            if saved is None and not dirty:
+                saved = dst
+            elif dst == saved:
+                bad.append((j + 1, f"{body}   <- overwrites the saved exec"))
+            dirty = dirty or op != "s_mov_b64"
+        elif dst.startswith("exec") or (op.startswith("v_cmpx") and not op.endswith("_e64")):
+            dirty = True
+            if saved is None:
+                bad.append((j + 1, f"{body}   <- exec written in an asm statement that has not saved it"))
+        elif saved is not None and op.startswith("s_") and dst == saved:
+            bad.append((j + 1, f"{body}   <- overwrites the saved exec"))
+    if dirty:
+        bad.append((end + 1, "exec is not restored at the end of this asm statement"))
+    return bad
+
+
 def audit(isa):
-    """Text order from every hand-issued load to the first hand-written wait behind it -- without the blocks that are laid
-    out in between but cannot run there: a block behind an unconditional s_branch whose label no branch of the stretch
-    itself names (hipcc places blocks of other paths of the loop wherever it likes)."""
+    """Text order from every hand-issued load -- anywhere inside an asm statement -- to the first hand-written wait behind it,
+    without the blocks that are laid out in between but cannot run there: a block behind an unconditional s_branch whose label
+    no branch of the stretch itself names (hipcc places blocks of other paths of the loop wherever it likes).  A statement
+    that holds a load may mask it, and must then leave exec as it found it (exec_kept)."""
     lines = isa.splitlines()
     bad, seen = [], 0
     br = re.compile(r"(s_branch|s_cbranch_\w+)\s+(\.LBB\d+_\d+)")
-    for i in range(len(lines) - 1):
-        if not ("#ASMSTART" in lines[i] and "global_load_dword" in lines[i + 1]):
-            continue
-        m = re.search(r"global_load_dword(?:x\d)?\s+v(?:\[(\d+):(\d+)\]|(\d+))", lines[i + 1])
+    loads, start = [], None  # (line of the load, line of its statement's #ASMEND)
+    for i, t in enumerate(lines):
+        if "#ASMSTART" in t:
+            start = i
+        elif "#ASMEND" in t and start is not None:
+            here = [(p, i) for p in range(start + 1, i) if re.match(r"\s*global_load_dword", lines[p])]
+            if here:
+                bad += exec_kept(lines, start, i)
+            loads += here
+            start = None
+
+    def uses(body, pat, regs):
+        return any(mm.group(1) or any(f"v{r}" in regs for r in range(int(mm.group(2)), int(mm.group(3)) + 1))
+                   for mm in pat.finditer(body))
+
+    for p, stop in loads:
+        m = re.search(r"global_load_dword(?:x\d)?\s+v(?:\[(\d+):(\d+)\]|(\d+))", lines[p])
         lo_, hi_ = (int(m.group(1)), int(m.group(2))) if m.group(1) else (int(m.group(3)), int(m.group(3)))
         regs = {f"v{r}" for r in range(lo_, hi_ + 1)}
         pat = re.compile(r"\b(" + "|".join(regs) + r")\b|v\[(\d+):(\d+)\]")
         seen += 1
-        if "s_waitcnt vmcnt(0)" in lines[i + 2]:  # the load and its wait in ONE asm statement
+        if any("s_waitcnt vmcnt(0)" in t for t in lines[p + 1:stop]):  # the load and its wait in ONE asm statement
             continue
+        for j in range(p + 1, stop):  # the rest of its own statement (the other loads of the group have registers of their own)
+            body = lines[j].split(";")[0].strip()
+            if body and "global_load_dword" not in body and uses(body, pat, regs):
+                bad.append((j + 1, f"{body}   <- register of the load at line {p + 1}, before its wait"))
         # the stretch: up to the first hand-written wait
         end, in_asm = None, False
-        for j in range(i + 3, len(lines)):
+        for j in range(stop + 1, len(lines)):
             t = lines[j]
             if "#ASMSTART" in t:
                 in_asm = True
@@ -38,11 +89,11 @@ def audit(isa):
             if t.strip().startswith(("s_endpgm", "s_setpc")):
                 break
         if end is None:
-            bad.append((i + 2, "no hand-written wait behind this load"))
+            bad.append((p + 1, "no hand-written wait behind this load"))
             continue
-        targets = {mb.group(2) for t in lines[i + 3:end] for mb in [br.search(t.split(";")[0])] if mb}
+        targets = {mb.group(2) for t in lines[stop + 1:end] for mb in [br.search(t.split(";")[0])] if mb}
         live, in_asm = True, False
-        for j in range(i + 3, end):
+        for j in range(stop + 1, end):
             t = lines[j]
             body = t.split(";")[0].strip()
             if "#ASMSTART" in t:
@@ -54,10 +105,8 @@ def audit(isa):
                 live = ml.group(1) in targets
             if not live or not body:
                 continue
-            if not (in_asm and "global_load_dword" in body):  # (the other loads of the group have registers of their own)
-                for mm in pat.finditer(body):
-                    if mm.group(1) or any(f"v{r}" in regs for r in range(int(mm.group(2)), int(mm.group(3)) + 1)):
-                        bad.append((j + 1, f"{t.strip()}   <- register of the load at line {i + 2}, before its wait"))
+            if not (in_asm and "global_load_dword" in body) and uses(body, pat, regs):  # (the other loads of the group have registers of their own)
+                bad.append((j + 1, f"{t.strip()}   <- register of the load at line {p + 1}, before its wait"))
             if body.startswith("s_branch"):
                 live = False
     return seen, sorted(set(bad))

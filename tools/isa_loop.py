@@ -10,7 +10,9 @@ for i,l in enumerate(src):
 end=next(i for i in range(start,len(src)) if '.end_amdhsa_kernel' in src[i] or src[i].strip().startswith('s_endpgm'))
 fn=src[start:end]
 # find first asm load
-li=next(i for i,l in enumerate(fn) if 'global_load_dwordx2' in l and '#ASMSTART' in fn[i-1])
+def in_asm(i):  # the nearest marker above is an ASMSTART (the load may sit behind a mask set inside the statement)
+    return next((('#ASMSTART' in fn[j]) for j in range(i-1,-1,-1) if '#ASMSTART' in fn[j] or '#ASMEND' in fn[j]),False)
+li=next(i for i,l in enumerate(fn) if 'global_load_dwordx2' in l and in_asm(i))
 # loop header: nearest preceding label with "Inner Loop Header"
 hs=max(i for i in range(li) if re.match(r'\.LBB\d+_\d+:',fn[i]) and 'Inner Loop Header' in ''.join(fn[i:i+5]))
 lab=fn[hs].split(':')[0]
