@@ -4,6 +4,7 @@
 // to the two-pass engine).  The C ABI around it is capi.cpp; what they share is handle.hpp.
 #include "handle.hpp"
 #include "class_overflow.hpp"
+#include "doc_ranges.hpp"
 
 #include <chrono>
 
@@ -1170,6 +1171,127 @@ int32_t device_cover(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
   return AHA_OK;
 }
 
+// ---- calls that work on a hit list per range of documents: doc counts, select and replace, class counts -----------------
+// Each counts first (device_count with the documents' hit offsets), cuts the batch into ranges of whole documents whose hits fit
+// the family's bound (doc_ranges.hpp: the rule) and matches range after range into the family's scratch.
+
+// The profiling book of such a call: the timing of the pass that traversed, the time of the matches, the ranges.
+struct RangeBook {
+  aha_ac *ac;
+  bool after_match;  // t_trav is taken again after the first match (select, class counts); else the caller says when (doc counts)
+  std::chrono::steady_clock::time_point t0{};
+  double ms_match = 0.0;
+  bool first = true;
+  aha_timing t_trav{};  // the timing of a pass that traversed (profiling)
+  void take() {
+    if (!ac->profiling.load()) return;
+    std::lock_guard<std::mutex> lk(ac->last_mu);
+    t_trav = ac->last;
+  }
+  void begin() {
+    t0 = std::chrono::steady_clock::now();
+    take();
+  }
+  void matched(std::chrono::steady_clock::time_point t_m0) {
+    ms_match += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_m0).count();
+  }
+  void first_done() {
+    if (first) take();
+    first = false;
+  }
+  // the engine that traversed, the call's hits; ms_write = the call from its first range on, less its matches; repeats = the
+  // ranges before the last.  `to` == null: published; else handed over (SelectSink::timing: the caller publishes)
+  void finish(uint64_t n_hits, size_t n_ranges, aha_timing *to) {
+    if (!ac->profiling.load()) return;
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    t_trav.struct_size = sizeof(t_trav);
+    t_trav.n_hits = n_hits;
+    t_trav.ms_write = (float)std::max(0.0, ms - ms_match);
+    t_trav.repeats = n_ranges ? (uint32_t)(n_ranges - 1) : 0;
+    if (to)
+      *to = t_trav;
+    else
+      publish_timing(ac, t_trav);
+  }
+};
+
+struct RangeBatch {  // a range as a batch of its own
+  const uint8_t *text;
+  const uint64_t *d_rel;
+  uint64_t nd, nb;
+};
+
+// What the ranges of one call share: the caller's batch, the family's slots and their growth, its name in the messages.
+struct RangeCall {
+  aha_ac *ac;
+  Scratch *sc;
+  const uint8_t *d_corpus;
+  const uint64_t *d_doc_offsets;
+  uint64_t D, n_bytes;
+  const aha_match_params *params;
+  void *stream;
+  Buf &rel_slot, &text_slot, &hits_slot;
+  Grow grow;
+  const char *family, *nomem_text;
+  RangeBook book;
+  std::vector<uint64_t> off, rel;  // the documents' offsets on the host (taken when the first range needs them); a range's own
+
+  int32_t nomem() const {
+    tls_err = nomem_text;
+    return AHA_E_HIP;
+  }
+
+  // The documents [d0, d1) as a batch: the caller's arrays where that is the whole batch; else the text from the range's first
+  // byte, the offsets relative to it in rel_slot.
+  int32_t batch(uint64_t d0, uint64_t d1, RangeBatch &B) {
+    hipStream_t s = (hipStream_t)stream;
+    B = RangeBatch{d_corpus, d_doc_offsets, d1 - d0, n_bytes};
+    if (d0 == 0 && d1 == D) return AHA_OK;
+    try {
+      if (off.empty()) {
+        off.resize(D + 1);
+        HIPCHK(ac, hipMemcpyAsync(off.data(), d_doc_offsets, (D + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(ac, hipStreamSynchronize(s));
+      }
+      rel.resize(B.nd + 1);
+    } catch (...) {
+      return AHA_E_NOMEM;
+    }
+    B.nb = off[d1] - off[d0];
+    for (uint64_t d = 0; d <= B.nd; d++) rel[d] = off[d0 + d] - off[d0];
+    uint64_t *r = (uint64_t *)reserve_ptr(rel_slot, (B.nd + 1) * 8, grow);
+    if (!r) return nomem();
+    HIPCHK(ac, hipMemcpyAsync(r, rel.data(), (B.nd + 1) * 8, hipMemcpyHostToDevice, s));
+    B.d_rel = r;
+    B.text = d_corpus + off[d0];
+    // (the kernels read aligned 16-byte pieces; a folded handle's match and count make their own folded -- and aligned -- copy)
+    if (!ac->fold() && reinterpret_cast<uintptr_t>(B.text) % 16 != 0) {
+      void *t = reserve_ptr(text_slot, B.nb + 64, grow);
+      if (!t) return nomem();
+      if (int32_t rc = stage_text(ac, &B.text, B.nb, t, 0, nullptr, 0, s)) return rc;
+    }
+    HIPCHK(ac, hipStreamSynchronize(s));  // (rel is the host's until the copy has run)
+    return AHA_OK;
+  }
+
+  // The range's rh hits (the count's figure) into hits_slot: every engine, the handle's back-off state read and never written.
+  int32_t match(const RangeBatch &B, uint64_t rh, aha_hit **d_hits) {
+    if (!(*d_hits = (aha_hit *)reserve_ptr(hits_slot, rh * sizeof(aha_hit), grow))) return nomem();
+    const auto t_m0 = std::chrono::steady_clock::now();
+    uint64_t got = 0;
+    if (int32_t rc = device_match(ac, sc, B.text, B.d_rel, B.nd, B.nb, params, *d_hits, rh, nullptr, &got, stream, true, nullptr,
+                                  nullptr, false, true))
+      return rc;
+    if (got != rh) {
+      tls_err = std::string(family) + ": the match and the count of a range disagree";
+      return AHA_E_HIP;
+    }
+    book.matched(t_m0);
+    if (book.after_match) book.first_done();
+    return AHA_OK;
+  }
+};
+
 // ---- document counts (aha_ac_doc_counts_batch*) ----------------------------------------------------------------------
 static void *dc_reserve(Scratch *sc, DocCountSlot slot, size_t bytes) {
   if (slot == kDcRows && sc->dcbuf[slot].bytes < bytes) sc->dc_rows_clear = false;  // (new rows: nothing is known about their words)
@@ -1178,8 +1300,7 @@ static void *dc_reserve(Scratch *sc, DocCountSlot slot, size_t bytes) {
 
 // One device-resident batch as {key, count} pairs per document (aha_ac_doc_counts_batch_device).
 //   1. device_count without key counts: the hits per document and their total, no capacity (and the offsets' validation).
-//   2. Ranges of whole documents whose hits fit the bound of the hit buffer (one range, as a rule): a match of the range with
-//      cap = its hits into the call's scratch -- every engine, the handle's back-off state read and never written.
+//   2. The ranges of doc_ranges.hpp (one, as a rule), each matched into the call's scratch (RangeCall, above).
 //   3. Per document one of the three forms of scan_doccount.hip, chosen from its hit count; the pairs per document come back,
 //      the host adds them up (the offsets, the capacity check), kdc_gather writes the pairs below the capacity.
 // A single document whose hits are beyond the bound is never matched: a count call over it alone gives its key counts -- the
@@ -1201,20 +1322,20 @@ int32_t device_doc_counts(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, cons
   if (params) memcpy(&pb, params, std::min<size_t>(params->struct_size, sizeof(pb)));
   pb.char_offsets = 0;
   const aha_match_params *p = params ? &pb : nullptr;
-  auto nomem = [&]() {
-    tls_err = "hipMalloc failed for the scratch of a document-count call";
-    return AHA_E_HIP;
-  };
+  RangeCall call{ac, sc, d_corpus, d_doc_offsets, D, n_bytes, p, stream, sc->dcbuf[kDcRel], sc->dcbuf[kDcText], sc->dcbuf[kDcHits],
+                 kGrowOrExact, "document counts", "hipMalloc failed for the scratch of a document-count call", RangeBook{ac, false}};
+  auto nomem = [&]() { return call.nomem(); };
   int32_t rc;
   uint64_t *d_dho = (uint64_t *)dc_reserve(sc, kDcHitOff, (D + 1) * 8);
   if (!d_dho) return nomem();
   uint64_t n_hits = 0;
   if ((rc = device_count(ac, sc, d_corpus, d_doc_offsets, D, n_bytes, p, 0, nullptr, d_dho, &n_hits, stream, offsets_checked))) return rc;
   if (n_hits_out) *n_hits_out = n_hits;
-  std::vector<uint64_t> off, hd, dpo, rel;
+  std::vector<uint64_t> hd, dpo, po;
   std::vector<uint32_t> np;
   std::vector<DcItem> items;
   std::vector<const uint32_t *> srcs;
+  std::vector<DocRange> ranges;
   try {
     hd.resize(D + 1);
     dpo.assign(D + 1, 0);
@@ -1223,67 +1344,20 @@ int32_t device_doc_counts(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, cons
   }
   HIPCHK(ac, hipMemcpyAsync(hd.data(), d_dho, (D + 1) * 8, hipMemcpyDeviceToHost, s));
   HIPCHK(ac, hipStreamSynchronize(s));
-  const auto t_all0 = std::chrono::steady_clock::now();
-  double ms_match = 0.0;
-  aha_timing t_trav;  // the timing of a pass that traversed (profiling)
-  memset(&t_trav, 0, sizeof(t_trav));
-  if (ac->profiling.load()) {
-    std::lock_guard<std::mutex> lk(ac->last_mu);
-    t_trav = ac->last;
-  }
+  call.book.begin();
   const uint32_t sort_max = ac->dc_sort_max, dense_min = ac->dc_dense_min;
   // what a document holds in scratch while its range is worked on: its hits, and in the range form its pairs beside them
   auto form = [&](uint64_t h) { return h <= sort_max ? 0 : (h < dense_min ? 1 : 2); };
   auto doc_bytes = [&](uint64_t h) { return h * sizeof(aha_hit) + (form(h) == 1 ? std::min<uint64_t>(h, K) * 8 : 0); };
-  uint64_t total = 0;
-  uint32_t ranges = 0;
-  for (uint64_t d0 = 0; d0 < D;) {
-    uint64_t d1 = d0, bytes = 0;
-    while (d1 < D && (d1 == d0 || bytes + doc_bytes(hd[d1 + 1] - hd[d1]) <= ac->dc_hit_bytes)) {
-      bytes += doc_bytes(hd[d1 + 1] - hd[d1]);
-      d1++;
-    }
-    const uint64_t nd = d1 - d0, rh = hd[d1] - hd[d0];
-    const bool solo = nd == 1 && bytes > ac->dc_hit_bytes;
-    if (rh == 0) {  // (no hit: the documents' offsets stand as they are)
-      for (uint64_t d = d0; d < d1; d++) dpo[d + 1] = total;
-      d0 = d1;
-      continue;
-    }
-    if (off.empty() && (d0 != 0 || d1 != D)) {
-      try {
-        off.resize(D + 1);
-      } catch (...) {
-        return AHA_E_NOMEM;
-      }
-      HIPCHK(ac, hipMemcpyAsync(off.data(), d_doc_offsets, (D + 1) * 8, hipMemcpyDeviceToHost, s));
-      HIPCHK(ac, hipStreamSynchronize(s));
-    }
-    // the range as a batch of its own: the caller's arrays where it is the whole batch
-    const uint8_t *text = d_corpus;
-    const uint64_t *d_rel = d_doc_offsets;
-    uint64_t nb = n_bytes;
-    if (d0 != 0 || d1 != D) {
-      nb = off[d1] - off[d0];
-      try {
-        rel.resize(nd + 1);
-      } catch (...) {
-        return AHA_E_NOMEM;
-      }
-      for (uint64_t d = 0; d <= nd; d++) rel[d] = off[d0 + d] - off[d0];
-      uint64_t *r = (uint64_t *)dc_reserve(sc, kDcRel, (nd + 1) * 8);
-      if (!r) return nomem();
-      HIPCHK(ac, hipMemcpyAsync(r, rel.data(), (nd + 1) * 8, hipMemcpyHostToDevice, s));
-      d_rel = r;
-      text = d_corpus + off[d0];
-      // (the kernels read aligned 16-byte pieces; a folded handle's match and count make their own folded -- and aligned -- copy)
-      if (!ac->fold() && reinterpret_cast<uintptr_t>(text) % 16 != 0) {
-        void *t = dc_reserve(sc, kDcText, nb + 64);
-        if (!t) return nomem();
-        if ((rc = stage_text(ac, &text, nb, t, 0, nullptr, 0, s))) return rc;
-      }
-      HIPCHK(ac, hipStreamSynchronize(s));  // (rel is the host's until the copy has run)
-    }
+  // (where the batch is cut, a range starts at a document with hits, not at the hitless ones before it: fewer bytes are matched,
+  // the same pairs come out; the pair offsets of the documents in no range are the host's to write)
+  if (!doc_ranges(hd.data(), D, ac->dc_hit_bytes, doc_bytes, ranges)) return AHA_E_NOMEM;
+  uint64_t total = 0, done = 0;  // (done: the documents whose pair offsets stand)
+  for (const DocRange &g : ranges) {
+    const uint64_t d0 = g.d0, d1 = g.d1, nd = d1 - d0, rh = hd[d1] - hd[d0];
+    for (uint64_t d = done; d < d0; d++) dpo[d + 1] = total;
+    RangeBatch B;
+    if ((rc = call.batch(d0, d1, B))) return rc;
     uint32_t *d_np = (uint32_t *)dc_reserve(sc, kDcPairsPerDoc, nd * 4);
     if (!d_np) return nomem();
     HIPCHK(ac, hipMemsetAsync(d_np, 0, nd * 4, s));
@@ -1294,30 +1368,22 @@ int32_t device_doc_counts(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, cons
     } catch (...) {
       return AHA_E_NOMEM;
     }
-    const auto t_m0 = std::chrono::steady_clock::now();
-    if (solo) {
+    if (g.solo) {
+      const auto t_m0 = std::chrono::steady_clock::now();
       unsigned long long *row = (unsigned long long *)dc_reserve(sc, kDcSoloRow, std::max<uint64_t>(K, 1) * 8);
       uint32_t *tmp = (uint32_t *)dc_reserve(sc, kDcRangePairs, std::max<uint64_t>(K, 1) * 8);
       DcItem *d_items = (DcItem *)dc_reserve(sc, kDcItems, sizeof(DcItem));
       if (!row || !tmp || !d_items) return nomem();
       uint64_t got = 0;
-      if ((rc = device_count(ac, sc, text, d_rel, 1, nb, p, 0, (uint64_t *)row, nullptr, &got, stream, true))) return rc;
-      ms_match += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_m0).count();
+      if ((rc = device_count(ac, sc, B.text, B.d_rel, 1, B.nb, p, 0, (uint64_t *)row, nullptr, &got, stream, true))) return rc;
+      call.book.matched(t_m0);
       items.assign(1, DcItem{0, tmp, 0, 0});
       HIPCHK(ac, hipMemcpyAsync(d_items, items.data(), sizeof(DcItem), hipMemcpyHostToDevice, s));
       doccount_launch_compact64(d_items, row, (uint32_t)K, d_np, s);
       srcs[0] = tmp;
     } else {
-      aha_hit *d_hits = (aha_hit *)dc_reserve(sc, kDcHits, rh * sizeof(aha_hit));
-      if (!d_hits) return nomem();
-      uint64_t got = 0;
-      rc = device_match(ac, sc, text, d_rel, nd, nb, p, d_hits, rh, nullptr, &got, stream, true, nullptr, nullptr, false, true);
-      if (rc) return rc;
-      if (got != rh) {
-        tls_err = "document counts: the match and the count of a range disagree";
-        return AHA_E_HIP;
-      }
-      ms_match += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_m0).count();
+      aha_hit *d_hits = nullptr;
+      if ((rc = call.match(B, rh, &d_hits))) return rc;
       // the work items: [sort | range | dense documents (a row each, in groups) | slices of the dense documents' hits]
       uint32_t n_form[3] = {0, 0, 0};
       uint64_t range_pairs = 0, n_slices = 0;
@@ -1383,49 +1449,37 @@ int32_t device_doc_counts(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, cons
     sc->dc_rows_clear = true;
     // the range's pair offsets; the pairs below the capacity to their place
     try {
-      rel.resize(nd + 1);
+      po.resize(nd + 1);
     } catch (...) {
       return AHA_E_NOMEM;
     }
-    rel[0] = 0;
+    po[0] = 0;
     for (uint64_t d = 0; d < nd; d++) {
-      rel[d + 1] = rel[d] + np[d];
-      dpo[d0 + d + 1] = total + rel[d + 1];
+      po[d + 1] = po[d] + np[d];
+      dpo[d0 + d + 1] = total + po[d + 1];
     }
-    const uint64_t room = cap > total ? cap - total : 0, n_write = std::min<uint64_t>(room, rel[nd]);
+    const uint64_t room = cap > total ? cap - total : 0, n_write = std::min<uint64_t>(room, po[nd]);
     if (n_write) {
       uint64_t *d_po = (uint64_t *)dc_reserve(sc, kDcGather, (nd + 1) * 8 + nd * sizeof(uint32_t *));
       if (!d_po) return nomem();
       const uint32_t **d_src = reinterpret_cast<const uint32_t **>(d_po + nd + 1);
-      HIPCHK(ac, hipMemcpyAsync(d_po, rel.data(), (nd + 1) * 8, hipMemcpyHostToDevice, s));
+      HIPCHK(ac, hipMemcpyAsync(d_po, po.data(), (nd + 1) * 8, hipMemcpyHostToDevice, s));
       HIPCHK(ac, hipMemcpyAsync(d_src, srcs.data(), nd * sizeof(uint32_t *), hipMemcpyHostToDevice, s));
       doccount_launch_gather(d_po, d_src, nd, n_write, d_out + total, s);
       HIPCHK(ac, hipGetLastError());
       HIPCHK(ac, hipStreamSynchronize(s));
     }
-    total += rel[nd];
-    if (ac->profiling.load() && !ranges) {
-      std::lock_guard<std::mutex> lk(ac->last_mu);
-      t_trav = ac->last;
-    }
-    ranges++;
-    d0 = d1;
+    total += po[nd];
+    call.book.first_done();  // (after the first range, matched or solo)
+    done = d1;
   }
+  for (uint64_t d = done; d < D; d++) dpo[d + 1] = total;
   if (d_doc_pair_offsets) {
     HIPCHK(ac, hipMemcpyAsync(d_doc_pair_offsets, dpo.data(), (D + 1) * 8, hipMemcpyHostToDevice, s));
     HIPCHK(ac, hipStreamSynchronize(s));
   }
   *n_pairs = total;
-  if (ac->profiling.load()) {
-    // the engine that traversed, the call's hits; ms_write = the passes of this file (the call from its first range on, less
-    // its matches); repeats = the ranges before the last
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_all0).count();
-    t_trav.struct_size = sizeof(t_trav);
-    t_trav.n_hits = n_hits;
-    t_trav.ms_write = (float)std::max(0.0, ms - ms_match);
-    t_trav.repeats = ranges ? ranges - 1 : 0;
-    publish_timing(ac, t_trav);
-  }
+  call.book.finish(n_hits, ranges.size(), nullptr);
   if (total > cap) {
     tls_err = "output buffer too small";
     return AHA_E_CAPACITY;
@@ -1438,9 +1492,8 @@ static void *sel_reserve(Scratch *sc, SelectSlot slot, size_t bytes) { return re
 
 // One device-resident batch selected (aha_ac_select_batch_device): per document the leftmost-longest, non-overlapping hits.
 //   1. device_count without key counts: the hits per document and their total, no capacity (and the offsets' validation).
-//   2. Ranges of whole documents whose hits fit the bound of the hit buffer (one range, as a rule; a document beyond the bound
-//      is alone with the hitless documents around it): a match of the range with cap = its hits into the call's scratch --
-//      every engine, the handle's back-off state read and never written.
+//   2. The ranges of doc_ranges.hpp (one, as a rule), tiled so that every document is in one, each matched into the call's
+//      scratch (RangeCall, above).
 //   3. The passes of scan_select.hip over the range: L, the masks, the walk, the rank -- the range's total comes back.
 //   4. Once the call's total is known to fit: the selection to its place, then the documents' offsets.
 // A failing call writes none of the caller's buffers, so nothing is emitted before the total of ALL ranges is known: with one
@@ -1467,10 +1520,9 @@ int32_t device_select_to(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const
   const uint64_t D = n_docs;
   *n_selected = 0;
   if (n_hits_out) *n_hits_out = 0;
-  auto nomem = [&]() {
-    tls_err = "hipMalloc failed for the scratch of a select call";
-    return AHA_E_HIP;
-  };
+  RangeCall call{ac, sc, d_corpus, d_doc_offsets, D, n_bytes, params, stream, sc->selbuf[kSelRel], sc->selbuf[kSelText],
+                 sc->selbuf[kSelHits], kGrowEighth, "select", "hipMalloc failed for the scratch of a select call", RangeBook{ac, true}};
+  auto nomem = [&]() { return call.nomem(); };
   int32_t rc;
   uint64_t *d_dho = (uint64_t *)sel_reserve(sc, kSelHitOff, (D + 1) * 8);
   uint64_t *d_dso = (uint64_t *)sel_reserve(sc, kSelDocOff, (D + 1) * 8);
@@ -1478,7 +1530,8 @@ int32_t device_select_to(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const
   uint64_t n_hits = 0;
   if ((rc = device_count(ac, sc, d_corpus, d_doc_offsets, D, n_bytes, params, 0, nullptr, d_dho, &n_hits, stream, offsets_checked)))
     return rc;
-  std::vector<uint64_t> off, hd, rel, bounds;
+  std::vector<uint64_t> hd, bounds;
+  std::vector<DocRange> ranges;
   try {
     hd.resize(D + 1);
     bounds.push_back(0);
@@ -1487,38 +1540,19 @@ int32_t device_select_to(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const
   }
   HIPCHK(ac, hipMemcpyAsync(hd.data(), d_dho, (D + 1) * 8, hipMemcpyDeviceToHost, s));
   HIPCHK(ac, hipStreamSynchronize(s));
-  const auto t_all0 = std::chrono::steady_clock::now();
-  double ms_match = 0.0;
-  aha_timing t_trav;  // the timing of a pass that traversed (profiling)
-  memset(&t_trav, 0, sizeof(t_trav));
-  if (ac->profiling.load()) {
-    std::lock_guard<std::mutex> lk(ac->last_mu);
-    t_trav = ac->last;
-  }
-  // the ranges: whole documents while their hits fit the bound; documents without a hit cost nothing and never stand alone
+  call.book.begin();
+  // the ranges, tiled: each from the end of the one before it (the first from 0), the last to D -- the walk takes every document,
+  // hitless ones cost nothing, and a document beyond the bound is matched like any other (no solo form)
+  if (!doc_ranges(hd.data(), D, ac->sel_hit_bytes, [](uint64_t h) { return h * sizeof(aha_hit); }, ranges)) return AHA_E_NOMEM;
   try {
-    for (uint64_t d0 = 0; n_hits && d0 < D;) {
-      uint64_t d1 = d0, bytes = 0;
-      while (d1 < D && (bytes == 0 || bytes + (hd[d1 + 1] - hd[d1]) * sizeof(aha_hit) <= ac->sel_hit_bytes)) {
-        bytes += (hd[d1 + 1] - hd[d1]) * sizeof(aha_hit);
-        d1++;
-      }
-      bounds.push_back(d1);
-      d0 = d1;
-    }
-    if (bounds.size() > 2 && hd[bounds.back()] == hd[bounds[bounds.size() - 2]]) bounds.erase(bounds.end() - 2);  // (a hitless tail)
-    if (bounds.size() > 2) {
-      off.resize(D + 1);
-      HIPCHK(ac, hipMemcpyAsync(off.data(), d_doc_offsets, (D + 1) * 8, hipMemcpyDeviceToHost, s));
-      HIPCHK(ac, hipStreamSynchronize(s));
-    }
+    for (const DocRange &g : ranges) bounds.push_back(g.d1);
   } catch (...) {
     return AHA_E_NOMEM;
   }
-  const size_t n_ranges = bounds.size() - 1;  // 0: no hit at all
+  const size_t n_ranges = ranges.size();  // 0: no hit at all
+  if (n_ranges) bounds.back() = D;
   const uint32_t blocks = 8u * std::max<uint32_t>(ac->v2_grid, 64u);
   uint64_t total = 0;
-  bool first_match = true;
   // what a worked range leaves in scratch for the emit
   struct Range {
     const uint64_t *d_rel;
@@ -1528,51 +1562,17 @@ int32_t device_select_to(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const
   } R{};
   // steps 2 and 3 for the documents [d0, d1); *sel = the range's selected hits
   auto work = [&](uint64_t d0, uint64_t d1, uint64_t *sel) -> int32_t {
-    const uint64_t nd = d1 - d0, rh = hd[d1] - hd[d0];
-    const uint8_t *text = d_corpus;
-    const uint64_t *d_rel = d_doc_offsets;
-    uint64_t nb = n_bytes;
-    if (d0 != 0 || d1 != D) {  // the range as a batch of its own: the caller's arrays where it is the whole batch
-      nb = off[d1] - off[d0];
-      try {
-        rel.resize(nd + 1);
-      } catch (...) {
-        return AHA_E_NOMEM;
-      }
-      for (uint64_t d = 0; d <= nd; d++) rel[d] = off[d0 + d] - off[d0];
-      uint64_t *r = (uint64_t *)sel_reserve(sc, kSelRel, (nd + 1) * 8);
-      if (!r) return nomem();
-      HIPCHK(ac, hipMemcpyAsync(r, rel.data(), (nd + 1) * 8, hipMemcpyHostToDevice, s));
-      d_rel = r;
-      text = d_corpus + off[d0];
-      // (the kernels read aligned 16-byte pieces; a folded handle's match makes its own folded -- and aligned -- copy)
-      if (!ac->fold() && reinterpret_cast<uintptr_t>(text) % 16 != 0) {
-        void *t = sel_reserve(sc, kSelText, nb + 64);
-        if (!t) return nomem();
-        if ((rc = stage_text(ac, &text, nb, t, 0, nullptr, 0, s))) return rc;
-      }
-      HIPCHK(ac, hipStreamSynchronize(s));  // (rel is the host's until the copy has run)
-    }
-    const uint64_t n_words = (nb + 31) / 32, n_blk = select_rank_blocks(nb);
-    aha_hit *d_hits = (aha_hit *)sel_reserve(sc, kSelHits, rh * sizeof(aha_hit));
+    const uint64_t rh = hd[d1] - hd[d0];
+    RangeBatch B;
+    if ((rc = call.batch(d0, d1, B))) return rc;
+    const uint64_t *d_rel = B.d_rel;
+    const uint64_t nd = B.nd, nb = B.nb, n_words = (nb + 31) / 32, n_blk = select_rank_blocks(nb);
     uint64_t *L = (uint64_t *)sel_reserve(sc, kSelLongest, nb * 8);
     uint32_t *masks = (uint32_t *)sel_reserve(sc, kSelMasks, 3 * n_words * 4);
     uint64_t *blk = (uint64_t *)sel_reserve(sc, kSelBlocks, (n_blk + 1) * 8);
-    if (!d_hits || !L || !masks || !blk) return nomem();
-    const auto t_m0 = std::chrono::steady_clock::now();
-    uint64_t got = 0;
-    rc = device_match(ac, sc, text, d_rel, nd, nb, params, d_hits, rh, nullptr, &got, stream, true, nullptr, nullptr, false, true);
-    if (rc) return rc;
-    if (got != rh) {
-      tls_err = "select: the match and the count of a range disagree";
-      return AHA_E_HIP;
-    }
-    ms_match += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_m0).count();
-    if (ac->profiling.load() && first_match) {
-      std::lock_guard<std::mutex> lk(ac->last_mu);
-      t_trav = ac->last;
-    }
-    first_match = false;
+    if (!L || !masks || !blk) return nomem();
+    aha_hit *d_hits = nullptr;
+    if ((rc = call.match(B, rh, &d_hits))) return rc;
     uint32_t *cover = masks, *doc_start = masks + n_words, *select = masks + 2 * n_words;
     HIPCHK(ac, hipMemsetAsync(L, 0, nb * 8, s));
     HIPCHK(ac, hipMemsetAsync(masks, 0, 3 * n_words * 4, s));
@@ -1641,19 +1641,7 @@ int32_t device_select_to(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const
   }
   *n_selected = total;
   if (n_hits_out) *n_hits_out = n_hits;
-  if (ac->profiling.load()) {
-    // the engine that traversed, the call's hits; ms_write = everything after the match (the call from its first range on,
-    // less its matches); repeats = the ranges before the last
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_all0).count();
-    t_trav.struct_size = sizeof(t_trav);
-    t_trav.n_hits = n_hits;
-    t_trav.ms_write = (float)std::max(0.0, ms - ms_match);
-    t_trav.repeats = n_ranges ? (uint32_t)(n_ranges - 1) : 0;
-    if (sink && sink->timing)
-      *sink->timing = t_trav;  // (the caller publishes)
-    else
-      publish_timing(ac, t_trav);
-  }
+  call.book.finish(n_hits, n_ranges, sink ? sink->timing : nullptr);
   if (total > cap) {
     tls_err = "output buffer too small";
     return AHA_E_CAPACITY;
@@ -1927,10 +1915,9 @@ static void *cls_reserve(Scratch *sc, ClassSlot slot, size_t bytes) { return res
 //   1. device_count without key counts: the hits per document and their total (and the offsets' validation).  A call with 2^32
 //      hits or more is checked for a document that could overflow a uint32 (class_overflow.hpp) before d_out is touched.
 //   2. d_out is cleared on the call's stream.
-//   3. Ranges of whole documents whose hits fit the bound of the hit buffer (one range, as a rule): a match of the range with
-//      cap = its hits into the call's scratch -- every engine, the handle's back-off state read and never written --, then
-//      kcc_add over the hit list (scan_classcount.hip).  A single document beyond the bound is never matched: a count call over
-//      it alone gives its key counts, which kcc_fold_keys adds into its row through the table.
+//   3. The ranges of doc_ranges.hpp (one, as a rule), each matched into the call's scratch (RangeCall, above), then kcc_add over
+//      the hit list (scan_classcount.hip).  A single document beyond the bound is never matched: a count call over it alone
+//      gives its key counts, which kcc_fold_keys adds into its row through the table.
 int32_t device_class_counts(aha_ac *ac, Scratch *sc, const aha_classes *table, const uint8_t *d_corpus, const uint64_t *d_doc_offsets,
                             uint64_t n_docs, uint64_t n_bytes, const aha_match_params *params, uint32_t *d_out, uint64_t *n_hits_out,
                             void *stream, bool offsets_checked) {
@@ -1942,123 +1929,62 @@ int32_t device_class_counts(aha_ac *ac, Scratch *sc, const aha_classes *table, c
   const uint64_t D = n_docs, C = table->n_classes;
   const uint32_t K = ac->aut.n_keys;
   if (n_hits_out) *n_hits_out = 0;
-  auto nomem = [&]() {
-    tls_err = "hipMalloc failed for the scratch of a class-counts call";
-    return AHA_E_HIP;
-  };
+  RangeCall call{ac, sc, d_corpus, d_doc_offsets, D, n_bytes, params, stream, sc->clsbuf[kClsRel], sc->clsbuf[kClsText],
+                 sc->clsbuf[kClsHits], kGrowEighth, "class counts", "hipMalloc failed for the scratch of a class-counts call",
+                 RangeBook{ac, true}};
+  auto nomem = [&]() { return call.nomem(); };
   int32_t rc;
   uint64_t *d_dho = (uint64_t *)cls_reserve(sc, kClsHitOff, (D + 1) * 8);
   if (!d_dho) return nomem();
   uint64_t n_hits = 0;
   if ((rc = device_count(ac, sc, d_corpus, d_doc_offsets, D, n_bytes, params, 0, nullptr, d_dho, &n_hits, stream, offsets_checked)))
     return rc;
-  const auto t_all0 = std::chrono::steady_clock::now();
-  double ms_match = 0.0;
-  aha_timing t_trav;  // the timing of a pass that traversed (profiling)
-  memset(&t_trav, 0, sizeof(t_trav));
-  if (ac->profiling.load()) {
-    std::lock_guard<std::mutex> lk(ac->last_mu);
-    t_trav = ac->last;
-  }
-  // the ranges {d0, d1, solo}: one where all hits fit the bound (the hit offsets stay on the device then)
-  struct Range {
-    uint64_t d0, d1;
-    bool solo;
-  };
-  std::vector<Range> ranges;
-  std::vector<uint64_t> off, hd, rel;
+  call.book.begin();
+  // the ranges: the whole batch where all hits are known to fit the bound (the hit offsets stay on the device then)
+  std::vector<DocRange> ranges;
+  std::vector<uint64_t> hd;
   const uint64_t bound = ac->cls_hit_bytes;
   try {
     if (n_hits && n_hits <= bound / sizeof(aha_hit) && n_hits < (1ull << 32)) {  // (2^32 hits: the documents are looked at)
-      ranges.push_back(Range{0, D, false});
+      ranges.push_back(DocRange{0, D, false});
     } else if (n_hits) {
       hd.resize(D + 1);
-      off.resize(D + 1);
+      call.off.resize(D + 1);
       HIPCHK(ac, hipMemcpyAsync(hd.data(), d_dho, (D + 1) * 8, hipMemcpyDeviceToHost, s));
-      HIPCHK(ac, hipMemcpyAsync(off.data(), d_doc_offsets, (D + 1) * 8, hipMemcpyDeviceToHost, s));
+      HIPCHK(ac, hipMemcpyAsync(call.off.data(), d_doc_offsets, (D + 1) * 8, hipMemcpyDeviceToHost, s));
       HIPCHK(ac, hipStreamSynchronize(s));
       uint64_t bad = 0;
       if (class_counts_overflow(hd.data(), D, &bad)) {
         tls_err = "class counts: document " + std::to_string(bad) + " has 2^32 hits or more";
         return AHA_E_TOO_LONG;
       }
-      // a range starts at a document with hits; the hitless documents behind its last one come with it
-      for (uint64_t d0 = 0; d0 < D;) {
-        if (hd[d0 + 1] == hd[d0]) {
-          d0++;
-          continue;
-        }
-        uint64_t d1 = d0 + 1, bytes = (hd[d0 + 1] - hd[d0]) * sizeof(aha_hit);
-        const bool solo = bytes > bound;
-        while (!solo && d1 < D && bytes + (hd[d1 + 1] - hd[d1]) * sizeof(aha_hit) <= bound) {
-          bytes += (hd[d1 + 1] - hd[d1]) * sizeof(aha_hit);
-          d1++;
-        }
-        ranges.push_back(Range{d0, d1, solo});
-        d0 = d1;
-      }
+      if (!doc_ranges(hd.data(), D, bound, [](uint64_t h) { return h * sizeof(aha_hit); }, ranges)) return AHA_E_NOMEM;
     }
   } catch (...) {
     return AHA_E_NOMEM;
   }
   if (D) HIPCHK(ac, hipMemsetAsync(d_out, 0, D * C * 4, s));
   const uint32_t blocks = class_grid(ac);
-  bool first_match = true;
   for (size_t r = 0; r < ranges.size(); r++) {
-    const uint64_t d0 = ranges[r].d0, d1 = ranges[r].d1, nd = d1 - d0;
-    // the range as a batch of its own: the caller's arrays where it is the whole batch
-    const uint8_t *text = d_corpus;
-    const uint64_t *d_rel = d_doc_offsets;
-    uint64_t nb = n_bytes, rh = n_hits;
-    if (d0 != 0 || d1 != D) {
-      nb = off[d1] - off[d0];
-      rh = hd[d1] - hd[d0];
-      try {
-        rel.resize(nd + 1);
-      } catch (...) {
-        return AHA_E_NOMEM;
-      }
-      for (uint64_t d = 0; d <= nd; d++) rel[d] = off[d0 + d] - off[d0];
-      uint64_t *rr = (uint64_t *)cls_reserve(sc, kClsRel, (nd + 1) * 8);
-      if (!rr) return nomem();
-      HIPCHK(ac, hipMemcpyAsync(rr, rel.data(), (nd + 1) * 8, hipMemcpyHostToDevice, s));
-      d_rel = rr;
-      text = d_corpus + off[d0];
-      // (the kernels read aligned 16-byte pieces; a folded handle's match and count make their own folded -- and aligned -- copy)
-      if (!ac->fold() && reinterpret_cast<uintptr_t>(text) % 16 != 0) {
-        void *t = cls_reserve(sc, kClsText, nb + 64);
-        if (!t) return nomem();
-        if ((rc = stage_text(ac, &text, nb, t, 0, nullptr, 0, s))) return rc;
-      }
-      HIPCHK(ac, hipStreamSynchronize(s));  // (rel is the host's until the copy has run)
-    }
-    const auto t_m0 = std::chrono::steady_clock::now();
-    uint64_t got = 0;
+    const uint64_t d0 = ranges[r].d0, d1 = ranges[r].d1, rh = hd.empty() ? n_hits : hd[d1] - hd[d0];
+    RangeBatch B;
+    if ((rc = call.batch(d0, d1, B))) return rc;
+    const uint64_t nd = B.nd;
     if (ranges[r].solo) {
+      const auto t_m0 = std::chrono::steady_clock::now();
+      uint64_t got = 0;
       uint64_t *row = (uint64_t *)cls_reserve(sc, kClsSoloRow, std::max<uint64_t>(K, 1) * 8);
       if (!row) return nomem();
-      if ((rc = device_count(ac, sc, text, d_rel, nd, nb, params, 0, row, nullptr, &got, stream, true))) return rc;
-      ms_match += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_m0).count();
+      if ((rc = device_count(ac, sc, B.text, B.d_rel, nd, B.nb, params, 0, row, nullptr, &got, stream, true))) return rc;
+      call.book.matched(t_m0);
       if (got != rh) {
         tls_err = "class counts: the two counts of a document disagree";
         return AHA_E_HIP;
       }
       classcount_launch_fold_keys(row, K, table->d_off, table->d_ids, d_out + d0 * C, blocks, s);
     } else {
-      aha_hit *d_hits = (aha_hit *)cls_reserve(sc, kClsHits, rh * sizeof(aha_hit));
-      if (!d_hits) return nomem();
-      rc = device_match(ac, sc, text, d_rel, nd, nb, params, d_hits, rh, nullptr, &got, stream, true, nullptr, nullptr, false, true);
-      if (rc) return rc;
-      if (got != rh) {
-        tls_err = "class counts: the match and the count of a range disagree";
-        return AHA_E_HIP;
-      }
-      ms_match += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_m0).count();
-      if (ac->profiling.load() && first_match) {
-        std::lock_guard<std::mutex> lk(ac->last_mu);
-        t_trav = ac->last;
-      }
-      first_match = false;
+      aha_hit *d_hits = nullptr;
+      if ((rc = call.match(B, rh, &d_hits))) return rc;
       classcount_launch_add(d_hits, rh, d_dho + d0, nd, table->d_off, table->d_ids, K, (uint32_t)C, d_out + d0 * C, blocks, s);
     }
     HIPCHK(ac, hipGetLastError());
@@ -2066,16 +1992,7 @@ int32_t device_class_counts(aha_ac *ac, Scratch *sc, const aha_classes *table, c
   }
   HIPCHK(ac, hipStreamSynchronize(s));
   if (n_hits_out) *n_hits_out = n_hits;
-  if (ac->profiling.load()) {
-    // the engine that traversed, the call's hits; ms_write = everything after the match (the call from its first range on, less
-    // its matches); repeats = the ranges before the last
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_all0).count();
-    t_trav.struct_size = sizeof(t_trav);
-    t_trav.n_hits = n_hits;
-    t_trav.ms_write = (float)std::max(0.0, ms - ms_match);
-    t_trav.repeats = ranges.empty() ? 0 : (uint32_t)(ranges.size() - 1);
-    publish_timing(ac, t_trav);
-  }
+  call.book.finish(n_hits, ranges.size(), nullptr);
   return AHA_OK;
 }
 

@@ -469,3 +469,15 @@ def test_prefix_filter_is_built_for_keyword_lists_only():
     many = AC.compile(sorted({bytes(rng.choice(b"abcdefghijklmnopqrstuvwxyz") for _ in range(rng.randint(4, 12)))
                               for _ in range(5000)}), host_only=True).info
     assert many["filter_prefix_bytes"] == 4 and many["filter_words"] == 1 << 14               # ~10 000 bits set: 2^14 words
+
+
+def test_document_ranges_follow_the_three_loops_they_replaced(tmp_path):
+    """aha_amd/csrc/doc_ranges.hpp, the partition of doc counts, select and class counts, against the loops it replaced and the
+    properties the callers rely on (tests/cpp/spec_doc_ranges.cpp): a stand-alone host program, made-up hit offsets."""
+    import subprocess
+
+    exe = str(tmp_path / "spec_doc_ranges")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", os.path.join(ROOT, "tests", "cpp", "spec_doc_ranges.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "FAIL" not in r.stdout, r.stdout + r.stderr
+    assert r.stdout.count("ok  ") >= 16
