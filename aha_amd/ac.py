@@ -1340,19 +1340,23 @@ class AC:
         return buf
 
     # -- feeds: sequences that arrive in pieces (aha_feed_*) -----------------------------------------
-    def feed(self, n_seqs, chars=False, sep=None):
+    def feed(self, n_seqs, chars=False, sep=None, longest=0):
         """n_seqs open sequences matched piece by piece (aha_feed_open): see Feed.  chars: offsets and bases in characters.
         sep: a BitArray -- the feed's match and count calls apply the separator filter of match(seq, sep) to the whole sequence
-        (aha_feed_open_params): a hit is reported one byte late, and Feed.finish ends a sequence.  A handle compiled with
-        fold_simple, fold_bmp or fold_kana has no feeds yet: the library's AHA_E_INVALID is raised."""
+        (aha_feed_open_params): a hit is reported one byte late, and Feed.finish ends a sequence.
+        longest: 1 or 2 -- a longest feed: its match calls report what match_longest(seq, intersectable = False | True) of the
+        whole sequence yields, each hit in the call that holds the byte at which it is yielded, and Feed.finish reports the hit
+        that is still pending and ends the sequence.  Refused (AHA_E_INVALID): longest with sep or chars, and count, cover,
+        select, replace and grep calls on such a feed.  A handle compiled with fold_simple, fold_bmp or fold_kana has no feeds
+        yet: the library's AHA_E_INVALID is raised."""
         h = C.c_void_p()
-        if sep is None:
+        if sep is None and not longest:
             rc = N.lib().aha_feed_open(self._h, int(n_seqs), N.AHA_FEED_CHARS if chars else 0, C.byref(h))
         else:
-            p = _params(False, sep)
+            p = _params(False, sep, longest)
             rc = N.lib().aha_feed_open_params(self._h, int(n_seqs), N.AHA_FEED_CHARS if chars else 0, C.byref(p), C.byref(h))
         self._check(rc)
-        return Feed(self, h, int(n_seqs), chars, sep)
+        return Feed(self, h, int(n_seqs), chars, sep, int(longest))
 
     def set_profiling(self, enabled=True):
         self._check(N.lib().aha_ac_set_profiling(self._h, 1 if enabled else 0))
@@ -1381,10 +1385,14 @@ class Feed:
     sep=BitArray)) filters match and count calls as match(seq, sep) of the whole sequence does: a call reports the surviving
     hits that end before the piece's last byte -- one that ended with the piece before has end == 0 -- and finish_batch /
     finish report those that end with the sequence and start it again; cover, select, replace and grep calls are refused
-    there.  A grep call (grep_batch, grepper) gives the lines that close in the call and have a hit."""
+    there.  A grep call (grep_batch, grepper) gives the lines that close in the call and have a hit.
+    A longest feed (AC.feed(.., longest=1 | 2); Feed.longest) is match_longest in pieces: a call that takes a sequence from n0
+    to n1 bytes reports the hits of match_longest(whole sequence) that are yielded at a byte in [n0, n1) -- a hit may lie
+    wholly in earlier pieces (start >= -Lmax, end >= -(Lmax - 1)) -- and finish_batch / finish report the one hit still
+    pending and start the sequence again; count, cover, select, replace and grep calls are refused there."""
 
-    def __init__(self, ac, handle, n_seqs, chars, sep=None):
-        self._ac, self._h, self.n_seqs, self.chars, self.sep = ac, handle, n_seqs, chars, sep
+    def __init__(self, ac, handle, n_seqs, chars, sep=None, longest=0):
+        self._ac, self._h, self.n_seqs, self.chars, self.sep, self.longest = ac, handle, n_seqs, chars, sep, longest
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None
@@ -1464,11 +1472,12 @@ class Feed:
         self._check(rc)
         return int(n.value)
 
-    # -- a feed with a separator filter: the named sequences end here (aha_feed_finish_batch*) ------------------------
+    # -- a feed with a separator filter or a longest feed: the named sequences end here (aha_feed_finish_batch*) ------
     def finish_batch(self, seq_ids, cap=None):
         """The surviving hits that end with the named sequences, relative to each sequence's end (end == 0, start == -len):
         -> (hits, seq_hit_offsets uint64[n+1], bases uint64[n] = the sequences' lengths).  The sequences start again at length
-        0.  Only on a feed opened with sep."""
+        0.  On a longest feed: the one hit of each sequence that is still pending (end <= 0).  Only on a feed opened with sep
+        or longest."""
         seq_ids = np.ascontiguousarray(seq_ids, dtype=np.uint32)
         D = seq_ids.size
         sho = np.zeros(D + 1, dtype=np.uint64)

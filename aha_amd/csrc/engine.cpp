@@ -1042,6 +1042,77 @@ static int32_t count_ranges(aha_ac *ac, Scratch *sc, const MatchArgs &M0, hipStr
   return AHA_OK;
 }
 
+// The pieces of a call on a longest feed as the documents of a two-pass match_longest batch (scan_feedlongest.hip): the steps of
+// device_match's match_longest branch with the feed's walks in place of the batch kernels.  Mode 2 (intersectable) takes a thread
+// per chunk where the pieces are at least a chunk long on average -- below that most chunks hold a cut, a thread per piece has as
+// many threads and none of them walks a warm-up (DESIGN.md 4.10 "Feed match_longest") -- and a thread per piece otherwise, as
+// mode 1 always does and as a call whose chunks gave up on a NUL every few bytes does.
+int32_t device_feed_longest_count(aha_ac *ac, Scratch *sc, const FeedArgs &F, FeedLongArgs &L, int longest, FeedLongPlan &P,
+                                  uint64_t *n_hits, void *stream) {
+  DeviceGuard g(ac->device);
+  hipStream_t s = (hipStream_t)stream;
+  MatchArgs &M = P.M;
+  M = MatchArgs{};
+  int32_t rc;
+  *n_hits = 0;
+  M.doc_off = F.off;
+  M.n_docs = F.D;
+  M.n_bytes = F.n_bytes;
+  if ((rc = take_text(ac, sc, F.text, F.n_bytes, M, s))) return rc;
+  if ((rc = stage_folded(ac, sc, M, s))) return rc;
+  if ((rc = ensure_scratch(ac, sc, 1, 1, F.D))) return rc;
+  L.end = (FeedLongSeq *)reserve_ptr(sc->flngbuf[kFlEnd], std::max<uint64_t>(F.D, 1) * sizeof(FeedLongSeq), kGrowEighth);
+  if (!L.end) {
+    tls_err = "hipMalloc failed for the scratch of a call on a longest feed";
+    return AHA_E_HIP;
+  }
+  P.intersectable = longest == 2;
+  two_pass_chunks(ac, M, 1024, 16);  // the warm-up is 2 * Lmax
+  P.chunks = P.intersectable && F.n_bytes / F.D >= M.chunk;
+  if (const char *walk = getenv("AHA_FEED_LONGEST_WALK")) {  // (tools/feed_longest_bench.py: both walks at every piece length)
+    if (P.intersectable && !strcmp(walk, "chunks")) P.chunks = true;
+    if (!strcmp(walk, "pieces")) P.chunks = false;
+  }
+  if (P.chunks) {
+    // the chunked form is exact only for text without NUL bytes (kernels.hip, k_has_nul): look first
+    HIPCHK(ac, hipMemsetAsync(sc->d_totals, 0, 2 * sizeof(uint64_t), s));
+    launch_has_nul(M.text, F.n_bytes, sc->d_totals + 1, s);
+    HIPCHK(ac, hipMemcpyAsync(sc->h_totals, sc->d_totals, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(ac, hipStreamSynchronize(s));
+    M.has_nul = sc->h_totals[1] ? 1 : 0;
+  }
+  uint64_t n_blocks;
+  if ((rc = bind_two_pass(ac, sc, M, P.chunks ? M.n_chunks : F.D + 1, &n_blocks))) return rc;
+  if ((rc = ensure_stale(ac))) return rc;
+  feedlong_launch_walk(ac->dev_longest, M, F, L, P.chunks, P.intersectable, false, s);
+  if (P.chunks && M.has_nul) {  // a chunk whose warm-up would not end (a NUL every few bytes) gave up: piece by piece
+    HIPCHK(ac, hipMemcpyAsync(sc->h_totals, sc->d_totals, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(ac, hipStreamSynchronize(s));
+    if (sc->h_totals[1] == 2) {
+      P.chunks = false;
+      if ((rc = bind_two_pass(ac, sc, M, F.D + 1, &n_blocks))) return rc;
+      feedlong_launch_walk(ac->dev_longest, M, F, L, false, true, false, s);
+    }
+  }
+  launch_scan_blocks(M, n_blocks, s);
+  HIPCHK(ac, hipGetLastError());
+  HIPCHK(ac, hipMemcpyAsync(sc->h_totals, sc->d_totals, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  *n_hits = sc->h_totals[0];
+  return AHA_OK;
+}
+
+int32_t device_feed_longest_write(aha_ac *ac, const FeedArgs &F, const FeedLongArgs &L, FeedLongPlan &P, aha_hit *d_out, uint64_t cap,
+                                  uint64_t *d_pho, void *stream) {
+  DeviceGuard g(ac->device);
+  P.M.out = d_out;
+  P.M.cap = cap;
+  P.M.doc_hit_off = d_pho;
+  feedlong_launch_walk(ac->dev_longest, P.M, F, L, P.chunks, P.intersectable, true, stream);
+  HIPCHK(ac, hipGetLastError());
+  return AHA_OK;
+}
+
 // One device-resident batch counted (aha_ac_count_batch_device): the match's engine and pipeline with the count passes in
 // place of the expansion (match_v2, `counting`); document ranges where its full-size regions do not fit (count_ranges); the
 // two-pass engine's counting form where a match of the batch takes that engine, and for a separator filter (a test per hit).

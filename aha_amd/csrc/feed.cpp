@@ -50,6 +50,14 @@
 //                          then the byte total) -- above either capacity -> AHA_E_CAPACITY, nothing committed
 //   kgr_emit_docs, krp_copy, kfd_commit + kfg_commit   the kept fragments, their bytes, the offsets; then the feed's state and,
 //                          behind it, the grep state
+// A longest feed (aha_feed_open_params with longest = 1 | 2; scan_feedlongest.hip, DESIGN.md 4.10 "Feed match_longest") keeps no
+// context: it carries match_longest_'s whole state per sequence (FeedLongSeq, 16 bytes).  Its match calls are
+//   kfd_check              offsets, ids, duplicates (one read-back)
+//   device_feed_longest_count   the text as the kernels take it (folded on a folded handle), the NUL look and the chunks in
+//                          mode 2, pass 1 from the carried states -- it leaves the states at the pieces' ends in scratch -- and the
+//                          block scan (one read-back: the total) -- above cap -> AHA_E_CAPACITY, nothing committed
+//   device_feed_longest_write, kfl_commit   pass 2: the hits and piece_hit_offsets; then bases, lengths and the carried states
+// and aha_feed_finish_batch* reports the named sequences' pending hits (kfl_finish: counted, then written) and restarts them.
 // Calls on one feed are serialised by its mutex; its scratch is its own.  The two matches lease one of the handle's scratch
 // sets like any call, so different feeds and plain calls on the same handle run side by side.
 #include "feed.hpp"
@@ -65,6 +73,8 @@ struct aha_feed {
   bool chars = false;
   bool sep = false;         // opened with a separator filter: W = Lmax + 1, match and count calls report a hit one byte late
   uint32_t blocked[8] = {};  // bit c: byte c does not pass (c < sep_size && !sep[c])
+  int longest = 0;          // opened with longest = 1 | 2: match_longest, intersectable = false | true; no context is kept
+  FeedLongSeq *d_long = nullptr;  // ... its carried states, allocated at open (16 bytes per sequence)
   std::mutex mu;
   FeedSeq *d_seqs = nullptr;
   uint8_t *d_ctx = nullptr;
@@ -880,6 +890,109 @@ int32_t feed_finish_sep(aha_feed *f, Scratch *sc, const uint32_t *d_ids, uint64_
   return AHA_OK;
 }
 
+int32_t longest_refused(const char *what) {
+  tls_err = std::string("feed ") + what + ": the feed was opened for match_longest, which feed " + what +
+            " calls do not take yet (a follow-up); feed match and finish calls do";
+  return AHA_E_INVALID;
+}
+
+// kfd_check alone and its verdict: the first step of a call on a longest feed (F.off, F.ids, F.D, F.n_bytes are the call's)
+int32_t feed_long_check(aha_feed *f, FeedArgs &F, hipStream_t s) {
+  aha_ac *ac = f->ac;
+  if (++f->stamp == 0) f->stamp = 1;
+  F.stamp = f->stamp;
+  F.seqs = f->d_seqs;
+  F.n_seqs = f->n_seqs;
+  F.max_piece = (1ull << 31) - std::max<uint64_t>(ac->aut.max_key_len, 1);
+  uint64_t *misc = (uint64_t *)reserve(f, kMisc, 24);
+  if (!misc) return no_memory("offsets");
+  F.verdict = (uint32_t *)misc;
+  HIPCHK(ac, hipMemsetAsync(F.verdict, 0, 4, s));
+  feed_launch_check_only(F, s);
+  HIPCHK(ac, hipGetLastError());
+  HIPCHK(ac, hipMemcpyAsync(f->h_pin, misc, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  const uint32_t bad = (uint32_t)f->h_pin[0];
+  if (bad & 1u) {
+    tls_err = "feed: need piece_offsets[0] = 0, ascending, piece_offsets[n_pieces] = n_bytes, seq_ids below n_seqs and each once";
+    return AHA_E_INVALID;
+  }
+  if (bad & 2u) {
+    tls_err = "feed: a piece must be shorter than 2^31 bytes minus the longest key";
+    return AHA_E_TOO_LONG;
+  }
+  return AHA_OK;
+}
+
+// the part of a match call on a longest feed that writes scratch only: the check and pass 1.  *total = the call's hits;
+// AHA_E_CAPACITY when they are more than cap.
+int32_t feed_long_prepare(aha_feed *f, Scratch *sc, FeedArgs &F, uint64_t cap, hipStream_t s, FeedLongArgs &L, FeedLongPlan &P,
+                          uint64_t *total) {
+  int32_t rc = feed_long_check(f, F, s);
+  if (rc) return rc;
+  L = FeedLongArgs{};
+  L.lseq = f->d_long;
+  *total = 0;
+  if (F.n_bytes && (rc = device_feed_longest_count(f->ac, sc, F, L, f->longest, P, total, s))) return rc;
+  F.total = *total;
+  if (*total > cap) {
+    tls_err = "output buffer too small";
+    return AHA_E_CAPACITY;
+  }
+  return AHA_OK;
+}
+
+// the part that writes: the caller's hits and offsets, then the feed's own state
+int32_t feed_long_emit(aha_feed *f, FeedArgs &F, const FeedLongArgs &L, FeedLongPlan &P, uint64_t cap, hipStream_t s) {
+  aha_ac *ac = f->ac;
+  if (!F.pho && !(F.pho = (uint64_t *)reserve(f, kPho, (F.D + 1) * 8))) return no_memory("piece hit offsets");
+  if (F.n_bytes) {
+    int32_t rc = device_feed_longest_write(ac, F, L, P, reinterpret_cast<aha_hit *>(F.out), cap, F.pho, s);
+    if (rc) return rc;
+  } else {
+    HIPCHK(ac, hipMemsetAsync(F.pho, 0, (F.D + 1) * 8, s));
+  }
+  feedlong_launch_commit(F, L, s);
+  HIPCHK(ac, hipGetLastError());
+  HIPCHK(ac, hipStreamSynchronize(s));
+  return AHA_OK;
+}
+
+// a whole finish call on a longest feed, device-resident ids: the ids checked as the ids of a call of empty pieces, the named
+// sequences' pending hits counted (one read-back), then -- once they fit -- written, with the bases, and the sequences restarted
+int32_t feed_finish_long(aha_feed *f, Scratch *sc, const uint32_t *d_ids, uint64_t D, aha_hit *d_out, uint64_t cap, uint64_t *d_sho,
+                         uint64_t *d_bases, hipStream_t s, uint64_t *total) {
+  aha_ac *ac = f->ac;
+  uint64_t *zero = (uint64_t *)reserve_ptr(sc->fsepbuf[kFpZeroOff], (D + 1) * 8, kGrowEighth);
+  if (!zero) return no_memory("offsets");
+  HIPCHK(ac, hipMemsetAsync(zero, 0, (D + 1) * 8, s));
+  FeedArgs F{};
+  F.off = zero;
+  F.ids = d_ids;
+  F.D = D;
+  int32_t rc = feed_long_check(f, F, s);
+  if (rc) return rc;
+  if (!(F.pho = (uint64_t *)reserve(f, kPho, (D + 1) * 8))) return no_memory("piece hit offsets");
+  FeedLongArgs L{};
+  L.lseq = f->d_long;
+  L.sho = d_sho;
+  F.out = reinterpret_cast<int32_t *>(d_out);
+  F.bases = d_bases;
+  feedlong_launch_finish(F, L, ac->dev.key_ln, false, s);
+  HIPCHK(ac, hipGetLastError());
+  HIPCHK(ac, hipMemcpyAsync(f->h_pin, F.pho + D, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  *total = f->h_pin[0];
+  if (*total > cap) {
+    tls_err = "output buffer too small";
+    return AHA_E_CAPACITY;
+  }
+  feedlong_launch_finish(F, L, ac->dev.key_ln, true, s);
+  HIPCHK(ac, hipGetLastError());
+  HIPCHK(ac, hipStreamSynchronize(s));
+  return AHA_OK;
+}
+
 bool bad_feed(const aha_feed *f) { return !f || !f->ac || f->ac->device < 0; }
 
 // the checks kfd_check makes, on the host (the host entries)
@@ -908,14 +1021,32 @@ int32_t aha_feed_open_params(aha_ac *ac, uint32_t n_seqs, uint32_t flags, const 
   if (!ac || !out || n_seqs == 0 || (flags & ~AHA_FEED_CHARS)) return AHA_E_INVALID;
   *out = nullptr;
   const bool sep = params && params->sep_size > 0;
+  int longest = 0;
   if (params) {
     if (params->sep_size > 256) {
       tls_err = "sep BitArray size > 256 is not supported";
       return AHA_E_SEP_SIZE;
     }
     const bool has_longest = params->struct_size >= offsetof(aha_match_params, longest) + sizeof(int32_t);
-    if (params->char_offsets || (has_longest && params->longest)) {
-      tls_err = "aha_feed_open_params: only the separator filter; a feed counts in characters with AHA_FEED_CHARS and has no match_longest";
+    longest = has_longest ? params->longest : 0;
+    if (longest < 0 || longest > 2) {
+      tls_err = "aha_feed_open_params: longest is 0 (match), 1 (match_longest, intersectable = false) or 2 (intersectable = true)";
+      return AHA_E_INVALID;
+    }
+    if (longest && sep) {
+      tls_err = "aha_feed_open_params: match_longest has no separator overload (longest != 0 with sep_size > 0)";
+      return AHA_E_INVALID;
+    }
+    if (longest && params->char_offsets) {
+      tls_err = "aha_feed_open_params: a longest feed reports byte offsets (longest != 0 with char_offsets != 0)";
+      return AHA_E_INVALID;
+    }
+    if (longest && (flags & AHA_FEED_CHARS)) {
+      tls_err = "aha_feed_open_params: a longest feed on a char feed (AHA_FEED_CHARS) is not supported yet (a follow-up)";
+      return AHA_E_INVALID;
+    }
+    if (params->char_offsets) {
+      tls_err = "aha_feed_open_params: the separator filter and longest only; a feed counts in characters with AHA_FEED_CHARS";
       return AHA_E_INVALID;
     }
     if (sep && (flags & AHA_FEED_CHARS)) {
@@ -958,15 +1089,18 @@ int32_t aha_feed_open_params(aha_ac *ac, uint32_t n_seqs, uint32_t flags, const 
     for (int c = 0; c < params->sep_size; c++)
       if (!((params->sep_bits[c >> 3] >> (c & 7)) & 1)) f->blocked[c >> 5] |= 1u << (c & 31);
   }
-  const size_t ctx_bytes = std::max<size_t>(2ull * n_seqs * f->W, 16);
+  f->longest = longest;
+  // (a longest feed carries its state in d_long and never reads a context)
+  const size_t ctx_bytes = longest ? 16 : std::max<size_t>(2ull * n_seqs * f->W, 16);
+  const size_t long_bytes = (size_t)n_seqs * sizeof(FeedLongSeq);
   int32_t rc = AHA_OK;
   if (hipMalloc((void **)&f->d_seqs, (size_t)n_seqs * sizeof(FeedSeq)) != hipSuccess ||
-      hipMalloc((void **)&f->d_ctx, ctx_bytes) != hipSuccess || hipHostMalloc((void **)&f->h_pin, 32) != hipSuccess ||
+      hipMalloc((void **)&f->d_ctx, ctx_bytes) != hipSuccess || (longest && hipMalloc((void **)&f->d_long, long_bytes) != hipSuccess) || hipHostMalloc((void **)&f->h_pin, 32) != hipSuccess ||
       hipStreamCreateWithFlags(&f->hs, hipStreamNonBlocking) != hipSuccess) {
     tls_err = "aha_feed_open: device allocation failed";
     rc = AHA_E_HIP;
   } else if (hipMemsetAsync(f->d_seqs, 0, (size_t)n_seqs * sizeof(FeedSeq), f->hs) != hipSuccess ||
-             hipStreamSynchronize(f->hs) != hipSuccess) {
+             (longest && hipMemsetAsync(f->d_long, 0, long_bytes, f->hs) != hipSuccess) || hipStreamSynchronize(f->hs) != hipSuccess) {
     tls_err = "aha_feed_open: clearing the sequences failed";
     rc = AHA_E_HIP;
   }
@@ -990,6 +1124,7 @@ void aha_feed_free(aha_feed *f) {
     if (f->d_sel) (void)hipFree(f->d_sel);
     if (f->d_tail) (void)hipFree(f->d_tail);
     if (f->d_grep) (void)hipFree(f->d_grep);
+    if (f->d_long) (void)hipFree(f->d_long);
     if (f->h_pin) (void)hipHostFree(f->h_pin);
     if (f->hs) (void)hipStreamDestroy(f->hs);
   }
@@ -1017,6 +1152,11 @@ int32_t aha_feed_reset(aha_feed *f, uint32_t seq) {
     HIPCHK(ac, hipMemsetAsync(f->d_grep, 0, (size_t)f->n_seqs * sizeof(FeedGrepSeq), f->hs));
   else if (f->d_grep)
     HIPCHK(ac, hipMemsetAsync(f->d_grep + seq, 0, sizeof(FeedGrepSeq), f->hs));
+  // ... and a longest feed's carried state: the root, nothing pending
+  if (f->d_long && seq == UINT32_MAX)
+    HIPCHK(ac, hipMemsetAsync(f->d_long, 0, (size_t)f->n_seqs * sizeof(FeedLongSeq), f->hs));
+  else if (f->d_long)
+    HIPCHK(ac, hipMemsetAsync(f->d_long + seq, 0, sizeof(FeedLongSeq), f->hs));
   HIPCHK(ac, hipStreamSynchronize(f->hs));
   return AHA_OK;
 }
@@ -1056,6 +1196,16 @@ int32_t aha_feed_match_batch_device(aha_feed *f, const uint8_t *d_corpus, const 
   F.bases = d_piece_bases;
   uint64_t total = 0;
   *n_hits = 0;
+  if (f->longest) {
+    FeedLongArgs L{};
+    FeedLongPlan plan;
+    int32_t rc = feed_long_prepare(f, lease.get(), F, cap, s, L, plan, &total);
+    if (rc == AHA_E_CAPACITY) *n_hits = total;
+    if (rc) return rc;
+    if ((rc = feed_long_emit(f, F, L, plan, cap, s))) return rc;
+    *n_hits = total;
+    return AHA_OK;
+  }
   FeedSepArgs P{};
   int32_t rc = f->sep ? feed_sep_prepare(f, lease.get(), F, cap, s, P, &total) : feed_prepare(f, lease.get(), F, cap, s, &total);
   if (rc == AHA_E_CAPACITY) *n_hits = total;
@@ -1100,13 +1250,22 @@ int32_t aha_feed_match_batch(aha_feed *f, const uint8_t *corpus, const uint64_t 
   uint64_t total = 0;
   *n_hits = 0;
   FeedSepArgs P{};
-  rc = f->sep ? feed_sep_prepare(f, lease.get(), F, cap, s, P, &total) : feed_prepare(f, lease.get(), F, cap, s, &total);
+  FeedLongArgs L{};
+  FeedLongPlan plan;
+  if (f->longest)
+    rc = feed_long_prepare(f, lease.get(), F, cap, s, L, plan, &total);
+  else
+    rc = f->sep ? feed_sep_prepare(f, lease.get(), F, cap, s, P, &total) : feed_prepare(f, lease.get(), F, cap, s, &total);
   if (rc == AHA_E_CAPACITY) *n_hits = total;
   if (rc) return rc;
   aha_hit *d_out = (aha_hit *)reserve(f, kHOut, total * sizeof(aha_hit));
   if (!d_out) return no_memory("hits");
   F.out = reinterpret_cast<int32_t *>(d_out);
-  if ((rc = f->sep ? feed_sep_emit(f, F, P, s) : feed_finish(f, F, s))) return rc;
+  if (f->longest)
+    rc = feed_long_emit(f, F, L, plan, total, s);
+  else
+    rc = f->sep ? feed_sep_emit(f, F, P, s) : feed_finish(f, F, s);
+  if (rc) return rc;
   if (total) HIPCHK(ac, hipMemcpyAsync(out, d_out, total * sizeof(aha_hit), hipMemcpyDeviceToHost, s));
   if (piece_hit_offsets) HIPCHK(ac, hipMemcpyAsync(piece_hit_offsets, d_pho, (D + 1) * 8, hipMemcpyDeviceToHost, s));
   if (piece_bases && D) HIPCHK(ac, hipMemcpyAsync(piece_bases, d_bases, D * 8, hipMemcpyDeviceToHost, s));
@@ -1120,8 +1279,9 @@ int32_t aha_feed_finish_batch_device(aha_feed *f, const uint32_t *d_seq_ids, uin
                                      uint64_t *d_seq_hit_offsets, uint64_t *d_bases, uint64_t *n_hits, void *stream) {
   if (!f || !n_hits || (n_named && !d_seq_ids) || (cap && !d_out)) return AHA_E_INVALID;
   if (bad_feed(f)) return AHA_E_NO_DEVICE;
-  if (!f->sep) {
-    tls_err = "feed finish: the feed has no separator filter (aha_feed_open_params); its sequences end with aha_feed_reset";
+  if (!f->sep && !f->longest) {
+    tls_err = "feed finish: the feed has neither a separator filter nor match_longest (aha_feed_open_params); its sequences end with "
+              "aha_feed_reset";
     return AHA_E_INVALID;
   }
   std::lock_guard<std::mutex> lk(f->mu);
@@ -1129,7 +1289,8 @@ int32_t aha_feed_finish_batch_device(aha_feed *f, const uint32_t *d_seq_ids, uin
   Lease lease(f->ac);
   uint64_t total = 0;
   *n_hits = 0;
-  int32_t rc = feed_finish_sep(f, lease.get(), d_seq_ids, n_named, d_out, cap, d_seq_hit_offsets, d_bases, (hipStream_t)stream, &total);
+  int32_t rc = f->longest ? feed_finish_long(f, lease.get(), d_seq_ids, n_named, d_out, cap, d_seq_hit_offsets, d_bases, (hipStream_t)stream, &total)
+                          : feed_finish_sep(f, lease.get(), d_seq_ids, n_named, d_out, cap, d_seq_hit_offsets, d_bases, (hipStream_t)stream, &total);
   if (rc == AHA_E_CAPACITY) *n_hits = total;
   if (rc) return rc;
   *n_hits = total;
@@ -1140,8 +1301,9 @@ int32_t aha_feed_finish_batch(aha_feed *f, const uint32_t *seq_ids, uint64_t n_n
                               uint64_t *seq_hit_offsets, uint64_t *bases, uint64_t *n_hits) {
   if (!f || !n_hits || (n_named && !seq_ids) || (cap && !out)) return AHA_E_INVALID;
   if (bad_feed(f)) return AHA_E_NO_DEVICE;
-  if (!f->sep) {
-    tls_err = "feed finish: the feed has no separator filter (aha_feed_open_params); its sequences end with aha_feed_reset";
+  if (!f->sep && !f->longest) {
+    tls_err = "feed finish: the feed has neither a separator filter nor match_longest (aha_feed_open_params); its sequences end with "
+              "aha_feed_reset";
     return AHA_E_INVALID;
   }
   aha_ac *ac = f->ac;
@@ -1173,7 +1335,8 @@ int32_t aha_feed_finish_batch(aha_feed *f, const uint32_t *seq_ids, uint64_t n_n
   if (D) HIPCHK(ac, hipMemcpyAsync(d_ids, seq_ids, D * 4, hipMemcpyHostToDevice, s));
   uint64_t total = 0;
   *n_hits = 0;
-  int32_t rc = feed_finish_sep(f, lease.get(), d_ids, D, d_out, cap_d, d_sho, d_bases, s, &total);
+  int32_t rc = f->longest ? feed_finish_long(f, lease.get(), d_ids, D, d_out, cap_d, d_sho, d_bases, s, &total)
+                          : feed_finish_sep(f, lease.get(), d_ids, D, d_out, cap_d, d_sho, d_bases, s, &total);
   if (rc == AHA_E_CAPACITY) *n_hits = total;
   if (rc) return rc;
   if (total) HIPCHK(ac, hipMemcpyAsync(out, d_out, total * sizeof(aha_hit), hipMemcpyDeviceToHost, s));
@@ -1191,6 +1354,7 @@ int32_t aha_feed_count_batch_device(aha_feed *f, const uint8_t *d_corpus, const 
   if (!f || !n_hits || !d_piece_offsets || (n_pieces && !d_seq_ids) || (n_bytes && !d_corpus) || (flags & ~AHA_COUNT_ACCUMULATE))
     return AHA_E_INVALID;
   if (bad_feed(f)) return AHA_E_NO_DEVICE;
+  if (f->longest) return longest_refused("count");
   std::lock_guard<std::mutex> lk(f->mu);
   DeviceGuard g(f->ac->device);
   Lease lease(f->ac);
@@ -1217,6 +1381,7 @@ int32_t aha_feed_count_batch(aha_feed *f, const uint8_t *corpus, const uint64_t 
                              uint64_t *piece_bases, uint64_t *n_hits) {
   if (!f || !n_hits || !piece_offsets || (n_pieces && !seq_ids) || (flags & ~AHA_COUNT_ACCUMULATE)) return AHA_E_INVALID;
   if (bad_feed(f)) return AHA_E_NO_DEVICE;
+  if (f->longest) return longest_refused("count");
   aha_ac *ac = f->ac;
   int32_t rc = check_pieces_host(f, piece_offsets, seq_ids, n_pieces);
   if (rc) return rc;
@@ -1270,6 +1435,7 @@ int32_t aha_feed_cover_batch_device(aha_feed *f, const uint8_t *d_corpus, const 
   if (!f || !n_covered || !d_piece_offsets || (n_pieces && !d_seq_ids) || (n_bytes && !d_corpus) || flags) return AHA_E_INVALID;
   if (bad_feed(f)) return AHA_E_NO_DEVICE;
   if (f->sep) return sep_refused("cover");
+  if (f->longest) return longest_refused("cover");
   std::lock_guard<std::mutex> lk(f->mu);
   DeviceGuard g(f->ac->device);
   Lease lease(f->ac);
@@ -1301,6 +1467,7 @@ int32_t aha_feed_cover_batch(aha_feed *f, const uint8_t *corpus, const uint64_t 
   if (!f || !n_covered || !piece_offsets || (n_pieces && !seq_ids) || flags) return AHA_E_INVALID;
   if (bad_feed(f)) return AHA_E_NO_DEVICE;
   if (f->sep) return sep_refused("cover");
+  if (f->longest) return longest_refused("cover");
   aha_ac *ac = f->ac;
   int32_t rc = check_pieces_host(f, piece_offsets, seq_ids, n_pieces);
   if (rc) return rc;
@@ -1361,6 +1528,7 @@ int32_t aha_feed_select_batch_device(aha_feed *f, const uint8_t *d_corpus, const
     return AHA_E_INVALID;
   }
   if (f->sep) return sep_refused("select");
+  if (f->longest) return longest_refused("select");
   std::lock_guard<std::mutex> lk(f->mu);
   DeviceGuard g(f->ac->device);
   Lease lease(f->ac);
@@ -1387,6 +1555,7 @@ int32_t aha_feed_select_batch(aha_feed *f, const uint8_t *corpus, const uint64_t
     return AHA_E_INVALID;
   }
   if (f->sep) return sep_refused("select");
+  if (f->longest) return longest_refused("select");
   aha_ac *ac = f->ac;
   int32_t rc = check_pieces_host(f, piece_offsets, seq_ids, n_pieces);
   if (rc) return rc;
@@ -1448,6 +1617,7 @@ static int32_t feed_replace_args(const aha_feed *f, const aha_repl *table, const
     return AHA_E_INVALID;
   }
   if (f->sep) return sep_refused("replace");
+  if (f->longest) return longest_refused("replace");
   if (!table->d_ent) return no_device();
   return AHA_OK;
 }
@@ -1550,6 +1720,7 @@ static int32_t feed_grep_args(const aha_feed *f, const uint64_t *piece_offsets, 
     return AHA_E_INVALID;
   }
   if (f->sep) return sep_refused("grep");
+  if (f->longest) return longest_refused("grep");
   return AHA_OK;
 }
 

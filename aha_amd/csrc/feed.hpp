@@ -1,9 +1,11 @@
 // feed.hpp -- what feed.cpp (the feed entry points of the C ABI) and its kernels (scan_feed.hip, scan_feedselect.hip,
-// scan_feedreplace.hip, scan_feedsep.hip, scan_feedgrep.hip) share.  Library-internal.
+// scan_feedreplace.hip, scan_feedsep.hip, scan_feedgrep.hip, scan_feedlongest.hip) share.  Library-internal.
 #pragma once
 #include <cstdint>
 
 namespace aha {
+struct DevAut;
+struct MatchArgs;
 // one open sequence of a feed, on the device (24 bytes)
 struct FeedSeq {
   unsigned long long bytes;  // bytes consumed since open / reset
@@ -27,6 +29,15 @@ struct FeedGrepSeq {
   unsigned long long recs;      // records closed so far
   uint32_t open_hit;            // the open record, matched as its own document, has a hit already
   uint32_t pad;
+};
+
+// what a longest feed (aha_feed_open_params with longest = 1 | 2; scan_feedlongest.hip) carries per sequence across calls: the
+// whole state of match_longest_'s loop at the sequence's current end (16 bytes).  All zero: a sequence of length 0.
+struct FeedLongSeq {
+  uint32_t state;  // 0: the root; else B + 1, B the state in the numbering of the handle's match_longest image (kValueNode included)
+  uint32_t back;   // the pending end lies `back` bytes in front of the sequence's current end (1: its last byte); 0: none
+  uint32_t key;    // its key (kNoKey: it yields nothing)
+  uint32_t prev;   // the sequence's last byte | the one before << 8, as the kernels saw them (folded on a folded handle)
 };
 
 // the arguments every feed kernel takes (by value)
@@ -137,6 +148,14 @@ struct FeedRepArgs {
   uint8_t *ext;       // the staged text, at most n_bytes + D W bytes
 };
 
+// what the kernels of a call on a longest feed take beside FeedArgs (scan_feedlongest.hip); the two-pass scratch (counts, block
+// sums, totals) is the batch match_longest's (MatchArgs)
+struct FeedLongArgs {
+  FeedLongSeq *lseq;      // [n_seqs] the carried states
+  FeedLongSeq *end;       // [D] scratch: the state at every non-empty piece's end (pass 1 writes it, kfl_commit moves it)
+  uint64_t *sho;          // a finish call: [D + 1] the named sequences' hit offsets, or null
+};
+
 #ifdef __HIP__
 // The cursor a select or replace call leaves behind piece d (kfs_commit stores it, kfr_layout sizes the staged text by it):
 // everything in front of it is final.  cursor: the one the call finds; wb = min(W, n0); cend: the end of the last hit the call
@@ -188,4 +207,13 @@ void feedgrep_launch_windows(const FeedArgs &F, const FeedGrepArgs &G, void *str
 void feedgrep_launch_flag(const FeedArgs &F, const FeedGrepArgs &G, uint32_t max_blocks, void *stream);  // flag, then keep, S, T
 void feedgrep_launch_commit(const FeedArgs &F, const FeedGrepArgs &G, uint32_t max_blocks, void *stream);  // behind feed_launch_commit
 void feedsep_launch_restart(const FeedArgs &F, const FeedSepArgs &P, void *stream);  // a finish call: bases, the sequences at length 0
+// calls on a longest feed (scan_feedlongest.hip): kfl_commit behind pass 2 -- bases, lengths, the carried states; a finish call
+// is kfl_finish twice: the pending hits counted (F.pho: the exclusive scan, F.pho[D] the total; one workgroup strides the ids),
+// then written, with the bases, and the sequences restarted
+// the walk: kfl_pieces (a thread per piece: exact for both modes) or kfl_chunks (intersectable only: a thread per chunk of
+// M.chunk bytes); write = false counts (M.counts, M.blk_hits) and leaves L.end, true writes M.out and M.doc_hit_off
+void feedlong_launch_walk(const DevAut &A, const MatchArgs &M, const FeedArgs &F, const FeedLongArgs &L, bool chunks, bool intersectable,
+                          bool write, void *stream);
+void feedlong_launch_commit(const FeedArgs &F, const FeedLongArgs &L, void *stream);
+void feedlong_launch_finish(const FeedArgs &F, const FeedLongArgs &L, const void *key_ln, bool write, void *stream);
 }  // namespace aha

@@ -19,6 +19,7 @@
 #include "automaton.hpp"
 #include "cedar_replay.hpp"
 #include "image.hpp"
+#include "feed.hpp"
 #include "unit.hpp"
 #include "internal.hpp"
 
@@ -186,6 +187,11 @@ enum FeedGrepSlot {
   kFgTable,       // the one-entry replacement table (the empty replacement)
   kFgCount
 };
+// flngbuf: calls on a longest feed (engine.cpp device_feed_longest_count; scan_feedlongest.hip)
+enum FeedLongSlot {
+  kFlEnd,  // the state at every piece's end, 16 bytes each (pass 1 writes it, kfl_commit moves it into the feed)
+  kFlCount
+};
 // clsbuf: class-counts calls (engine.cpp device_class_counts; scan_classcount.hip)
 enum ClassSlot {
   kClsHitOff,   // the documents' hit offsets (the count call in front)
@@ -217,6 +223,7 @@ struct Scratch {
   Buf grpbuf[kGrpCount];
   Buf fgrpbuf[kFgCount];
   Buf clsbuf[kClsCount];
+  Buf flngbuf[kFlCount];
   // every family above, for free_scratch and scratch_bytes (S: Scratch or const Scratch): a new family is one more line here
   template <class S, class Fn>
   static void each_buf(S &sc, Fn fn) {
@@ -233,6 +240,7 @@ struct Scratch {
     for (auto &b : sc.grpbuf) fn(b);
     for (auto &b : sc.fgrpbuf) fn(b);
     for (auto &b : sc.clsbuf) fn(b);
+    for (auto &b : sc.flngbuf) fn(b);
   }
   bool dc_rows_clear = false;  // every word of dcbuf[kDcRows] is zero (kdc_compact clears what kdc_add wrote; a call that failed may not have)
   hipStream_t hs[3] = {};  // host-buffer entry: private non-blocking streams for upload, match, download
@@ -425,7 +433,7 @@ uint64_t scratch_bytes(const Scratch *sc);
 // THE allocator of the grow-only buffers: b holds at least `bytes` afterwards, or nothing (the HIP error is returned, the
 // runtime's sticky one cleared).  What a new buffer gets beyond `bytes` is its family's rule:
 enum Grow {
-  kGrowEighth,   // bytes + bytes / 8 + 256 (v2buf, covbuf, selbuf, repbuf, fselbuf, frepbuf, fsepbuf, grpbuf, fgrpbuf, clsbuf)
+  kGrowEighth,   // bytes + bytes / 8 + 256 (v2buf, covbuf, selbuf, repbuf, fselbuf, frepbuf, fsepbuf, grpbuf, fgrpbuf, clsbuf, flngbuf)
   kGrowQuarter,  // bytes + bytes / 4 + 4096 (cntbuf, hostbuf)
   kGrowOrExact   // an eighth, else exactly `bytes`; `bytes` is what it records (dcbuf: what is known to be there)
 };
@@ -574,5 +582,17 @@ int32_t device_grep(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint
 int32_t device_class_counts(aha_ac *ac, Scratch *sc, const aha_classes *table, const uint8_t *d_corpus, const uint64_t *d_doc_offsets,
                             uint64_t n_docs, uint64_t n_bytes, const aha_match_params *params, uint32_t *d_out, uint64_t *n_hits,
                             void *stream, bool offsets_checked);
+// the pieces of a call on a longest feed (feed.cpp feed_long_prepare; scan_feedlongest.hip), walked as the documents of a
+// two-pass match_longest batch that start from the feed's carried states.  _count: the text as the kernels take it (folded on a
+// folded handle), the NUL look and the chunks in mode 2, pass 1 and the block scan; *n_hits = the call's hits (one read-back),
+// P = what pass 2 needs.  _write: pass 2 into d_out (cap >= *n_hits) and d_pho [D + 1]; nothing is synchronised.  F.n_bytes > 0.
+struct FeedLongPlan {
+  MatchArgs M;
+  bool chunks = false, intersectable = false;
+};
+int32_t device_feed_longest_count(aha_ac *ac, Scratch *sc, const FeedArgs &F, FeedLongArgs &L, int longest, FeedLongPlan &P,
+                                  uint64_t *n_hits, void *stream);
+int32_t device_feed_longest_write(aha_ac *ac, const FeedArgs &F, const FeedLongArgs &L, FeedLongPlan &P, aha_hit *d_out, uint64_t cap,
+                                  uint64_t *d_pho, void *stream);
 uint32_t class_grid(const aha_ac *ac);  // the cap of the class-counts grids (AHA_CLASS_BLOCKS)
 }  // namespace ahai

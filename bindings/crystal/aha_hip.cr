@@ -808,8 +808,26 @@ module Aha
       @handle = h
     end
 
-    # The sequence ends here (a feed with a separator filter): the surviving hits that end with it, with absolute offsets; it
-    # starts again at length 0.
+    # A longest feed (aha_feed_open_params with longest = 1 | 2), the mirror of AC#match_longest(seq, intersectable) for a
+    # sequence in pieces: #match gives the hits of match_longest(whole sequence) that are yielded at a byte of the piece -- a
+    # hit may lie wholly in earlier pieces --, #finish the one hit still pending; #count, #select and the other call families
+    # raise on such a feed.  Feed.match_longest(ac, n_seqs, intersectable)
+    def initialize(ac : AC, n_seqs : Int, *, longest : Int32)
+      @ac = ac
+      params = LibAhaHip::MatchParams.new
+      params.struct_size = sizeof(LibAhaHip::MatchParams).to_u32
+      params.longest = longest
+      rc = LibAhaHip.aha_feed_open_params(ac.handle, n_seqs.to_u32, 0_u32, pointerof(params), out h)
+      raise String.new(LibAhaHip.aha_last_error(ac.handle)) if rc != 0
+      @handle = h
+    end
+
+    def self.match_longest(ac : AC, n_seqs : Int, intersectable : Bool = false) : Feed
+      new(ac, n_seqs, longest: intersectable ? 2 : 1)
+    end
+
+    # The sequence ends here (a feed with a separator filter: the surviving hits that end with it; a longest feed: the hit
+    # still pending), with absolute offsets; it starts again at length 0.
     def finish(seq : Int) : Array(Hit)
       ids = [seq.to_u32]
       cap = 16_u64

@@ -668,6 +668,16 @@ class Feed {
       throw Error(rc, (m && *m) ? m : aha_strerror(rc));
     }
   }
+  // a longest feed (aha_feed_open_params with longest = 1 | 2), the mirror of AC#match_longest(seq, intersectable) for a sequence
+  // in pieces: a call that takes a sequence from n0 to n1 bytes gives the hits of match_longest(whole sequence) that are yielded
+  // at a byte in [n0, n1) -- a hit may lie wholly in earlier pieces --, finish_batch / finish the one hit still pending, and the
+  // sequence starts again.  Byte offsets; count, cover, select, replace and grep calls throw
+  static Feed match_longest(const AC &ac, uint32_t n_seqs, bool intersectable = false) {
+    aha_match_params p{};
+    p.struct_size = sizeof(p);
+    p.longest = intersectable ? 2 : 1;
+    return Feed(ac, n_seqs, p);
+  }
   Feed(const Feed &) = delete;
   Feed &operator=(const Feed &) = delete;
   Feed(Feed &&o) noexcept : ac_(o.ac_), f_(o.f_), grep_held_(std::move(o.grep_held_)) { o.f_ = nullptr; }
@@ -710,7 +720,8 @@ class Feed {
   }
   // a feed with a separator filter: the named sequences end here (aha_feed_finish_batch).  The surviving hits that end with
   // them, relative to each sequence's end (end == 0, start == -len); seq_hit_offsets (n + 1) and bases (n: the sequences'
-  // lengths) when asked for.  The sequences start again at length 0.
+  // lengths) when asked for.  The sequences start again at length 0.  A longest feed: the one hit of each sequence that is
+  // still pending (end <= 0).
   std::vector<Hit> finish_batch(const std::vector<uint32_t> &seq_ids, std::vector<uint64_t> *seq_hit_offsets = nullptr,
                                 std::vector<uint64_t> *bases = nullptr) {
     const uint64_t D = seq_ids.size();
@@ -1025,6 +1036,13 @@ class Feed {
   aha_feed *handle() const { return f_; }
 
  private:
+  Feed(const AC &ac, uint32_t n_seqs, const aha_match_params &p) : ac_(ac.handle()) {
+    const int32_t rc = aha_feed_open_params(ac_, n_seqs, 0u, &p, &f_);
+    if (rc != AHA_OK) {
+      const char *m = aha_last_error(ac_);
+      throw Error(rc, (m && *m) ? m : aha_strerror(rc));
+    }
+  }
   void check(int32_t rc) const {
     if (rc == AHA_OK) return;
     const char *m = aha_last_error(ac_);

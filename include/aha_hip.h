@@ -504,8 +504,9 @@ int32_t aha_ac_count_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uin
  * once (AHA_E_INVALID); pieces may come in any order and a call may name any subset of the sequences.  A call that fails
  * changes nothing, AHA_E_CAPACITY included: *n_hits is then the exact count and the same call with a larger buffer gives what
  * the first would have.  Counts: aha_feed_count_batch* below.  Separator filter: match and count calls take one fixed when the
- * feed is opened (aha_feed_open_params, "feed separator filter" below); cover and select calls do not yet, and no feed call has
- * match_longest (follow-ups).
+ * feed is opened (aha_feed_open_params, "feed separator filter" below); cover and select calls do not yet (follow-ups).
+ * match_longest: a longest feed, opened with aha_feed_open_params ("feed match_longest" below); its match and finish calls
+ * report match_longest's hits, the other call families do not take such a feed yet (follow-ups).
  * Errors: aha_last_error(ac).  Calls
  * on one feed are serialised (a mutex in the feed); different feeds and plain calls on the handle run side by side.
  * Pipeline (aha_amd/csrc/feed.cpp, scan_feed.hip): with W = max(Lmax-1, 0) the feed keeps the last
@@ -563,7 +564,8 @@ int32_t aha_feed_count_batch_device(aha_feed *f, const uint8_t *d_corpus, const 
  * BitArray) src/aha/ac.cr:321-340, to the whole sequence: with pass(c) = c >= sep_size || sep_bits[c] -- applied to fold(c) on a
  * handle with AHA_OPT_FOLD_ASCII -- a hit {start, end, value} of a sequence T survives when (end == |T| || pass(T[end])) and
  * (start == 0 || pass(T[start-1])).  The survivors keep the order of the unfiltered list.  params == NULL or sep_size == 0:
- * exactly aha_feed_open.  sep_size > 256: AHA_E_SEP_SIZE; char_offsets != 0, longest != 0, or AHA_FEED_CHARS together with a
+ * exactly aha_feed_open (longest != 0 without a separator filter: a longest feed, below).  sep_size > 256: AHA_E_SEP_SIZE;
+ * char_offsets != 0, longest != 0 with a separator filter (the reference has no such overload), or AHA_FEED_CHARS together with a
  * separator filter (the reference's char overload tests code points: out of scope): AHA_E_INVALID; these checks come before
  * the device check, so a host-only handle answers AHA_E_NO_DEVICE only for valid arguments.
  * The byte behind a hit that ends with a piece is not there yet, so such a feed reports a hit ONE BYTE LATE and a sequence has
@@ -583,14 +585,50 @@ int32_t aha_feed_count_batch_device(aha_feed *f, const uint8_t *d_corpus, const 
  * does build the call's unfiltered hit list in scratch (12 bytes per unfiltered hit of the pieces), unlike the plain feed
  * count.  A failing call changes nothing; on AHA_E_CAPACITY *n_hits is the exact filtered count, the sequences of a finish call
  * have NOT restarted, and the same call with a larger buffer gives what the first would have.
- * aha_feed_finish_batch*: AHA_E_INVALID on a feed without a separator filter, for a sequence named twice or an id >= n_seqs
+ * aha_feed_finish_batch*: AHA_E_INVALID on a plain feed (neither a separator filter nor longest), for a sequence named twice or an id >= n_seqs
  * (the device form checks both on the device).  aha_feed_cover_batch* and aha_feed_select_batch* on a feed with a separator
  * filter: AHA_E_INVALID, the feed as it was (follow-ups).
  * Pipeline (aha_amd/csrc/feed.cpp, scan_feedsep.hip; DESIGN.md 4.10 "Feed separator filter"): the feed keeps W = Lmax + 1 bytes
  * of context per sequence (2 W + 24 bytes of device memory), so a hit that ended with the piece before is a hit of the context
  * alone and its left neighbour lies in the context too.  A call runs the window batch and the main pass unfiltered, merges the
  * call's true hits into scratch, flags each (12 B read, two neighbour bytes), ranks the flags, and writes the kept hits -- or
- * adds their values per key -- once the filtered total is known to fit. */
+ * adds their values per key -- once the filtered total is known to fit.
+ *
+ * ---- feed match_longest: longest hits for sequences in pieces (no new symbol: ABI 8 as it is) ------------------------------
+ * aha_feed_open_params(ac, n_seqs, 0, params, &feed) with params->longest = 1 (intersectable = false) or 2 (true) and
+ * sep_size == 0 opens a LONGEST FEED: the reference's match_longest(seq, intersectable), src/aha/ac.cr:118-143, for sequences
+ * that arrive in pieces.  Let Y(T) be what aha_ac_match_batch with the same longest reports for the one-document batch T, in
+ * order.  Every hit of Y(T) has a yield position: the index j >= end of the first byte that finds no goto while the hit is the
+ * pending end (ac.cr:131-133); if the sequence ends first it has none.
+ * Stream law: a match call that takes a sequence from n0 to n1 bytes reports the hits whose yield position lies in [n0, n1); a
+ * zero-length piece reports nothing and changes nothing.  aha_feed_finish_batch* on a named sequence reports the one hit that is
+ * still pending, if there is one, and starts the sequence again at length 0.  A sequence's match calls, made absolute (base +
+ * relative) and concatenated, with the finish call's hit appended, are Y(T) bit for bit and in order; the hits of the calls up
+ * to length n plus a finish at n are Y(T[0..n)) for every n.
+ * Offsets are relative to the piece's first byte, piece_bases[d] = n0.  A hit may lie wholly in earlier pieces: a pending end is
+ * followed by direct gotos only, so start >= -Lmax and end >= -(Lmax - 1), and both bounds are reached.  A finish call reports
+ * relative to the sequence's end as on a feed with a separator filter: end <= 0, bases[d] = n, at most one hit per named
+ * sequence.
+ * As on the other feeds: a sequence appears at most once per call, pieces may come in any order, a call may name any subset of
+ * the sequences, a piece is shorter than 2^31 bytes minus Lmax; a failing call changes nothing, AHA_E_CAPACITY included (*n_hits
+ * is then the exact count, the same call with a larger buffer gives what the first would have, the sequences of a finish call
+ * have NOT restarted); aha_feed_reset drops the carried state, the pending end with it; calls on one feed are serialised.  On a
+ * handle with AHA_OPT_FOLD_ASCII everything the kernels see is the folded text, the two bytes the state carries included.
+ * Cedar's stale END flags and NUL bytes (the value node of a key that has children) behave as in the batch call: that is the
+ * point of Y(T).
+ * Refused, AHA_E_INVALID before any device work, nothing changed, each with its own aha_last_error text: longest outside 0..2;
+ * longest != 0 with sep_size > 0, with char_offsets != 0, or with AHA_FEED_CHARS (a follow-up); aha_feed_count_batch*,
+ * _cover_, _select_, _replace_ and _grep_ on a longest feed (follow-ups).  The argument checks come before the device check: a
+ * host-only handle answers AHA_E_NO_DEVICE for longest = 1 | 2 with valid arguments.  Handles folded beyond ASCII stay refused.
+ * Pipeline (aha_amd/csrc/feed.cpp, scan_feedlongest.hip; DESIGN.md 4.10 "Feed match_longest"): match_longest's state at a cut
+ * depends on the whole sequence (intersectable = false resets it at every yield), so the feed carries it: 16 bytes per sequence
+ * -- the automaton state, the pending end as a distance back from the sequence's end, its key, the last two bytes (all that the
+ * shadow fail links ever read in front of the current byte) -- and no context.  A call checks offsets and ids, walks the pieces
+ * as the documents of a two-pass batch (count, block scan, write: the batch match_longest's scratch) that start from the carried
+ * state and do not flush at their end, one thread per piece, or for longest = 2 and pieces of a chunk or more on average one
+ * thread per chunk with the batch kernel's warm-up, and commits the new states once the total is known to fit.
+ * aha_ac_last_timing reports what a batch match_longest reports.  Device memory: 40 bytes per sequence; per call 16 bytes per
+ * piece beside the batch match_longest's scratch. */
 int32_t aha_feed_open_params(aha_ac *ac, uint32_t n_seqs, uint32_t flags, const aha_match_params *params, aha_feed **out);
 /* Host buffers (the ids are checked on the host).  Any output array may be NULL; n_named = 0 is valid. */
 int32_t aha_feed_finish_batch(aha_feed *f, const uint32_t *seq_ids, uint64_t n_named, aha_hit *out, uint64_t cap,
@@ -910,7 +948,7 @@ int32_t aha_ac_class_counts_batch_device(aha_ac *ac, const aha_classes *table, c
  * fill byte is written before the verdict is known.  Any output array may be NULL; N = 0, D = 0 and empty pieces are valid.
  * Two calls on feeds in the same state give identical bytes.  Like count and cover calls it reads the handle's back-off state
  * and never writes it.  No separator filter (a feed opened with one refuses the call: AHA_E_INVALID, the feed unchanged; a
- * follow-up) and no match_longest.
+ * follow-up); a longest feed refuses the call too (AHA_E_INVALID, the feed unchanged; a follow-up).
  * Pipeline (feed.cpp, scan_feed.hip; DESIGN.md 4.10 "Feed cover"): with W = Lmax - 1 and W' = min(W, |P|), the head windows
  * are widened to X2 = ctx || P[0 .. min(2 W, |P|)) and P'2 = P[0 .. min(2 W, |P|)) (the window batch: at most 6 W bytes per
  * piece, matched quietly, in bytes); the pieces are covered alone as by aha_ac_cover_batch_device into a mask in feed scratch
@@ -958,7 +996,7 @@ int32_t aha_feed_cover_batch_device(aha_feed *f, const uint8_t *d_corpus, const 
  * caller's buffers is written and the feed is unchanged; the same call with a larger buffer gives what the first would have
  * (out == NULL with cap == 0 is a sizing call).  Every failing call changes nothing.  Two feeds in the same state give
  * identical bytes.  No separator filter (a feed opened with one refuses the call: AHA_E_INVALID, the feed unchanged; a
- * follow-up) and no match_longest.
+ * follow-up); a longest feed refuses the call too (AHA_E_INVALID, the feed unchanged; a follow-up).
  * Mixing: select keeps state per sequence that match, count and cover calls do not maintain (they stay exactly as they are).
  * A select call is valid for a sequence only if every byte of it since open, reset or a FINAL call went through select calls;
  * otherwise AHA_E_INVALID (found on the device, next to the duplicate check; aha_last_error says so) and nothing changes.  Such
