@@ -13,7 +13,7 @@
 //
 // LDS: the root's transitions (4 bytes per symbol) + the decode tables (11 KiB) + a wave-private input window (three
 // 16-byte pieces + the last 4 bytes before them per lane, rows of 13 dwords: odd stride, no bank conflicts).
-// Everything else is probed in HBM/L2, 8 bytes per probe.
+// Everything else is probed in HBM/L2, 8 bytes per probe.  (Behind the rows: a 64-record event buffer and a progress word per wave.)
 #include <hip/hip_runtime.h>
 
 #include "automaton.hpp"
@@ -62,8 +62,11 @@ __device__ __forceinline__ bool wall(bool p) { return __builtin_amdgcn_ballot_w6
 __host__ __device__ inline size_t u_lds_rows(uint32_t n_syms) {  // decode tables, root table, input rows
   return (size_t)(kUTabWords + ((n_syms + 3u) & ~3u)) * 4 + (size_t)(kV2Threads / 64) * kUWave + 16;
 }
+__host__ __device__ inline size_t u_lds_prog(uint32_t n_syms) {  // + the waves' event buffers (every term a multiple of 16)
+  return u_lds_rows(n_syms) + (size_t)(kV2Threads / 64) * 64 * 12;
+}
 __host__ __device__ inline size_t u_lds(uint32_t n_syms) {
-  return u_lds_rows(n_syms) + (size_t)(kV2Threads / 64) * 64 * 12;  // + the waves' event buffers
+  return u_lds_prog(n_syms) + (size_t)(kV2Threads / 64) * 4;  // + the waves' progress words (ku_traverse: issue priority)
 }
 
 // CHARS (String overload, matcher.cr:34-39): an event's second word is the number of characters -- bytes outside
@@ -84,6 +87,15 @@ __global__ __launch_bounds__(kV2Threads) void ku_traverse(UnitDev U, V2Args M) {
   const uint32_t n_root = (U.n_syms + 3u) & ~3u;
   for (uint32_t i = threadIdx.x; i < kUTabWords; i += kV2Threads) tabw[i] = U.tables[i];
   for (uint32_t i = threadIdx.x; i < n_root; i += kV2Threads) rlw[i] = i < U.n_syms ? U.root[i] : 0u;
+  // Rounds done, by SIMD and by the wave's rank on it (wave w of the workgroup is the (w >> 2)-th wave of SIMD w & 3: what the
+  // per-wave clocks show; on another placement the words below would cost speed, never a result): the
+  // issue arbiter serves the oldest wave of a SIMD first, so with equal priorities the four finish one after the other --
+  // at 0.76, 0.81, 0.88 and 1.0 of the kernel on cfg 3 -- and a SIMD runs short of waves for the last quarter (14 % of the
+  // wave slots stand empty, profiles/wave_groups.txt).  Every round a wave notes its progress here and takes the priority
+  // "number of waves of my SIMD that are ahead of me": they finish within 1 % of each other, the kernel 8.5 % sooner.
+  // Nobody waits for these words; a stale one costs a round at the wrong priority.
+  uint32_t *prog = reinterpret_cast<uint32_t *>(smem + u_lds_prog(U.n_syms));
+  if (threadIdx.x < kV2Threads / 64) prog[threadIdx.x] = 0u;
   __syncthreads();
   const uint32_t *rl = rlw;
   const uint4 *t0a = reinterpret_cast<const uint4 *>(tabw + kUT0a);
@@ -102,6 +114,10 @@ __global__ __launch_bounds__(kV2Threads) void ku_traverse(UnitDev U, V2Args M) {
   const int rounds = (int)(M.S / kUPiece);
   const int warm = U.max_len > 1 ? (int)U.max_len - 1 : 0;
   const int R = (warm + kUPiece - 1) / kUPiece;  // warm-up rounds before the chunk
+  const uint32_t wave_u = (uint32_t)__builtin_amdgcn_readfirstlane(wave);
+  uint32_t *my_prog = prog + (wave_u & 3u) * 4u + (wave_u >> 2);
+  const uint4 *simd_prog = reinterpret_cast<const uint4 *>(prog + (wave_u & 3u) * 4u);
+  uint32_t n_rounds = 0;  // rounds this wave has done, over all its tiles
 
   const uint64_t n_tiles = (M.n_chunks + kV2Threads - 1) / kV2Threads;
   for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
@@ -146,6 +162,21 @@ __global__ __launch_bounds__(kV2Threads) void ku_traverse(UnitDev U, V2Args M) {
     // bytes of the chunk continues in the next one.
     // (the first piece loaded starts a 64-byte line, so that the line queue below is filled: R is rounded up to whole lines)
     for (int r = -((R + 3) / 4) * 4 - 2; r <= rounds; r++) {
+      {  // the wave's issue priority for this round: the waves of its SIMD that have done more rounds (s_setprio takes an immediate)
+        n_rounds++;
+        if (lane == 0) *my_prog = n_rounds;
+        const uint4 pm = *simd_prog;
+        const uint32_t ahead = ((uint32_t)__builtin_amdgcn_readfirstlane(pm.x) > n_rounds) + ((uint32_t)__builtin_amdgcn_readfirstlane(pm.y) > n_rounds) +
+                               ((uint32_t)__builtin_amdgcn_readfirstlane(pm.z) > n_rounds) + ((uint32_t)__builtin_amdgcn_readfirstlane(pm.w) > n_rounds);
+        if (ahead == 0u)
+          __builtin_amdgcn_s_setprio(0);
+        else if (ahead == 1u)
+          __builtin_amdgcn_s_setprio(1);
+        else if (ahead == 2u)
+          __builtin_amdgcn_s_setprio(2);
+        else
+          __builtin_amdgcn_s_setprio(3);
+      }
       const int64_t pb = a + (int64_t)r * kUPiece;
       const int64_t pl = pb + 2 * kUPiece;  // the piece loaded in this round
       const int64_t pend = min(pb + kUWin, e);
