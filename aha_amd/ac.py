@@ -100,6 +100,11 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
 
 
+def _dptr(t):
+    """a torch tensor's device address, or None"""
+    return t.data_ptr() if t is not None else None
+
+
 def _params(chars, sep, longest=0):
     p = N.aha_match_params()
     p.struct_size = C.sizeof(N.aha_match_params)
@@ -1419,8 +1424,10 @@ class Feed:
         self._check(N.lib().aha_feed_position(self._h, int(seq), C.byref(b), C.byref(c)))
         return int(b.value), int(c.value)
 
-    def match_batch(self, corpus, piece_offsets, seq_ids, cap=None):
-        """Host buffers: -> (hits, piece_hit_offsets uint64[D+1], piece_bases uint64[D])."""
+    # -- what the batch methods share: the pieces of a host or a device call, optional device outputs, the capacity error ------
+    @staticmethod
+    def _pieces_host(corpus, piece_offsets, seq_ids):
+        """-> (corpus uint8, piece_offsets uint64, seq_ids uint32, D): contiguous arrays; corpus may come as bytes."""
         if isinstance(corpus, (bytes, bytearray)):
             corpus = np.frombuffer(bytes(corpus), dtype=np.uint8)
         corpus = np.ascontiguousarray(corpus, dtype=np.uint8)
@@ -1429,6 +1436,46 @@ class Feed:
         D = piece_offsets.size - 1
         if seq_ids.size != D:
             raise ValueError("one sequence id per piece")
+        return corpus, piece_offsets, seq_ids, D
+
+    @staticmethod
+    def _pieces_device(corpus, piece_offsets, seq_ids, stream):
+        """-> (D, n_bytes, the stream's handle): stream None is torch's current stream on the corpus' device."""
+        import torch
+
+        assert corpus.is_cuda and corpus.dtype == torch.uint8 and corpus.is_contiguous()
+        assert piece_offsets.is_cuda and piece_offsets.dtype in (torch.int64, torch.uint64) and piece_offsets.is_contiguous()
+        assert seq_ids.is_cuda and seq_ids.dtype in (torch.int32, torch.uint32) and seq_ids.is_contiguous()
+        D = piece_offsets.numel() - 1
+        assert seq_ids.numel() >= D
+        return D, corpus.numel(), stream if stream is not None else torch.cuda.current_stream(corpus.device).cuda_stream
+
+    @staticmethod
+    def _opt64(*pairs):
+        """(tensor, n) pairs: each tensor None or a contiguous int64/uint64 CUDA tensor of at least n entries."""
+        import torch
+
+        for t, n in pairs:
+            assert t is None or (t.is_cuda and t.dtype in (torch.int64, torch.uint64) and t.is_contiguous() and t.numel() >= n)
+
+    @staticmethod
+    def _opt32(*pairs):
+        """... or a contiguous int32/uint32 one."""
+        import torch
+
+        for t, n in pairs:
+            assert t is None or (t.is_cuda and t.dtype in (torch.int32, torch.uint32) and t.is_contiguous() and t.numel() >= n)
+
+    @staticmethod
+    def _capacity(rc, n, attr):
+        """The AhaError of a call that did not fit; what is needed goes into .required or .n_required, as each method documents."""
+        e = AhaError(rc)
+        setattr(e, attr, int(n.value))
+        return e
+
+    def match_batch(self, corpus, piece_offsets, seq_ids, cap=None):
+        """Host buffers: -> (hits, piece_hit_offsets uint64[D+1], piece_bases uint64[D])."""
+        corpus, piece_offsets, seq_ids, D = self._pieces_host(corpus, piece_offsets, seq_ids)
         pho = np.zeros(D + 1, dtype=np.uint64)
         bases = np.zeros(max(D, 1), dtype=np.uint64)
         if cap is None:
@@ -1450,25 +1497,15 @@ class Feed:
         .required when out is too small (the feed is then unchanged)."""
         import torch
 
-        assert corpus.is_cuda and corpus.dtype == torch.uint8 and corpus.is_contiguous()
-        assert piece_offsets.is_cuda and piece_offsets.dtype in (torch.int64, torch.uint64) and piece_offsets.is_contiguous()
-        assert seq_ids.is_cuda and seq_ids.dtype in (torch.int32, torch.uint32) and seq_ids.is_contiguous()
+        D, n_bytes, s = self._pieces_device(corpus, piece_offsets, seq_ids, stream)
         assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous()
-        D = piece_offsets.numel() - 1
-        assert seq_ids.numel() >= D
-        for t, n in ((piece_hit_offsets, D + 1), (piece_bases, D)):
-            assert t is None or (t.is_cuda and t.dtype in (torch.int64, torch.uint64) and t.is_contiguous() and t.numel() >= n)
-        cap = out.numel() // 3
+        self._opt64((piece_hit_offsets, D + 1), (piece_bases, D))
         n = C.c_uint64(0)
-        s = stream if stream is not None else torch.cuda.current_stream(corpus.device).cuda_stream
         rc = N.lib().aha_feed_match_batch_device(
-            self._h, corpus.data_ptr(), piece_offsets.data_ptr(), seq_ids.data_ptr(), D, corpus.numel(), out.data_ptr(), cap,
-            piece_hit_offsets.data_ptr() if piece_hit_offsets is not None else None,
-            piece_bases.data_ptr() if piece_bases is not None else None, C.byref(n), C.c_void_p(s))
+            self._h, corpus.data_ptr(), piece_offsets.data_ptr(), seq_ids.data_ptr(), D, n_bytes, out.data_ptr(), out.numel() // 3,
+            _dptr(piece_hit_offsets), _dptr(piece_bases), C.byref(n), C.c_void_p(s))
         if rc == N.AHA_E_CAPACITY:
-            e = AhaError(rc)
-            e.required = int(n.value)
-            raise e
+            raise self._capacity(rc, n, "required")
         self._check(rc)
         return int(n.value)
 
@@ -1503,18 +1540,13 @@ class Feed:
         assert seq_ids.is_cuda and seq_ids.dtype in (torch.int32, torch.uint32) and seq_ids.is_contiguous()
         assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous()
         D = seq_ids.numel()
-        for t, n in ((seq_hit_offsets, D + 1), (bases, D)):
-            assert t is None or (t.is_cuda and t.dtype in (torch.int64, torch.uint64) and t.is_contiguous() and t.numel() >= n)
+        self._opt64((seq_hit_offsets, D + 1), (bases, D))
         n = C.c_uint64(0)
         s = stream if stream is not None else torch.cuda.current_stream(out.device).cuda_stream
-        rc = N.lib().aha_feed_finish_batch_device(
-            self._h, seq_ids.data_ptr() if D else None, D, out.data_ptr(), out.numel() // 3,
-            seq_hit_offsets.data_ptr() if seq_hit_offsets is not None else None,
-            bases.data_ptr() if bases is not None else None, C.byref(n), C.c_void_p(s))
+        rc = N.lib().aha_feed_finish_batch_device(self._h, seq_ids.data_ptr() if D else None, D, out.data_ptr(), out.numel() // 3,
+                                                  _dptr(seq_hit_offsets), _dptr(bases), C.byref(n), C.c_void_p(s))
         if rc == N.AHA_E_CAPACITY:
-            e = AhaError(rc)
-            e.required = int(n.value)
-            raise e
+            raise self._capacity(rc, n, "required")
         self._check(rc)
         return int(n.value)
 
@@ -1529,14 +1561,7 @@ class Feed:
         uint64[K] or None, piece_hit_offsets uint64[D+1], piece_bases uint64[D]).  The sequences move on as a match call would
         move them.  accumulate_into: a uint64[K] array the counts are added to (AHA_COUNT_ACCUMULATE); it is also what is
         returned, and a call that fails leaves it as it was."""
-        if isinstance(corpus, (bytes, bytearray)):
-            corpus = np.frombuffer(bytes(corpus), dtype=np.uint8)
-        corpus = np.ascontiguousarray(corpus, dtype=np.uint8)
-        piece_offsets = np.ascontiguousarray(piece_offsets, dtype=np.uint64)
-        seq_ids = np.ascontiguousarray(seq_ids, dtype=np.uint32)
-        D = piece_offsets.size - 1
-        if seq_ids.size != D:
-            raise ValueError("one sequence id per piece")
+        corpus, piece_offsets, seq_ids, D = self._pieces_host(corpus, piece_offsets, seq_ids)
         K = self._ac.n_keys
         flags = 0
         kc = None
@@ -1563,24 +1588,17 @@ class Feed:
         key_counts."""
         import torch
 
-        assert corpus.is_cuda and corpus.dtype == torch.uint8 and corpus.is_contiguous()
-        assert piece_offsets.is_cuda and piece_offsets.dtype in (torch.int64, torch.uint64) and piece_offsets.is_contiguous()
-        assert seq_ids.is_cuda and seq_ids.dtype in (torch.int32, torch.uint32) and seq_ids.is_contiguous()
+        D, n_bytes, s = self._pieces_device(corpus, piece_offsets, seq_ids, stream)
         K = self._ac.n_keys
         if key_counts is not None and not (key_counts.is_cuda and key_counts.dtype in (torch.int64, torch.uint64)
                                            and key_counts.is_contiguous() and key_counts.numel() >= K):
             raise ValueError(f"key_counts must be a contiguous int64/uint64 CUDA tensor of at least {K} entries")
-        D = piece_offsets.numel() - 1
-        assert seq_ids.numel() >= D
-        for t, n in ((piece_hit_offsets, D + 1), (piece_bases, D)):
-            assert t is None or (t.is_cuda and t.dtype in (torch.int64, torch.uint64) and t.is_contiguous() and t.numel() >= n)
+        self._opt64((piece_hit_offsets, D + 1), (piece_bases, D))
         n = C.c_uint64(0)
-        s = stream if stream is not None else torch.cuda.current_stream(corpus.device).cuda_stream
         rc = N.lib().aha_feed_count_batch_device(
-            self._h, corpus.data_ptr(), piece_offsets.data_ptr(), seq_ids.data_ptr(), D, corpus.numel(),
-            N.AHA_COUNT_ACCUMULATE if accumulate else 0, key_counts.data_ptr() if key_counts is not None else None,
-            piece_hit_offsets.data_ptr() if piece_hit_offsets is not None else None,
-            piece_bases.data_ptr() if piece_bases is not None else None, C.byref(n), C.c_void_p(s))
+            self._h, corpus.data_ptr(), piece_offsets.data_ptr(), seq_ids.data_ptr(), D, n_bytes,
+            N.AHA_COUNT_ACCUMULATE if accumulate else 0, _dptr(key_counts), _dptr(piece_hit_offsets), _dptr(piece_bases),
+            C.byref(n), C.c_void_p(s))
         self._check(rc)
         return int(n.value)
 
@@ -1593,14 +1611,7 @@ class Feed:
 
     # -- feed cover: the mask and the redacted copy of pieces, straddling hits included (aha_feed_cover_batch*) ---------
     def _cover_host(self, corpus, piece_offsets, seq_ids, want_mask, want_redacted, fill):
-        if isinstance(corpus, (bytes, bytearray)):
-            corpus = np.frombuffer(bytes(corpus), dtype=np.uint8)
-        corpus = np.ascontiguousarray(corpus, dtype=np.uint8)
-        piece_offsets = np.ascontiguousarray(piece_offsets, dtype=np.uint64)
-        seq_ids = np.ascontiguousarray(seq_ids, dtype=np.uint32)
-        D = piece_offsets.size - 1
-        if seq_ids.size != D:
-            raise ValueError("one sequence id per piece")
+        corpus, piece_offsets, seq_ids, D = self._pieces_host(corpus, piece_offsets, seq_ids)
         n_bytes = int(piece_offsets[-1])
         mask = np.zeros((n_bytes + 31) // 32, dtype=np.uint32) if want_mask else None
         red = np.zeros(n_bytes, dtype=np.uint8) if want_redacted else None
@@ -1639,11 +1650,7 @@ class Feed:
         -> (n_covered, n_hits)."""
         import torch
 
-        assert corpus.is_cuda and corpus.dtype == torch.uint8 and corpus.is_contiguous()
-        assert piece_offsets.is_cuda and piece_offsets.dtype in (torch.int64, torch.uint64) and piece_offsets.is_contiguous()
-        assert seq_ids.is_cuda and seq_ids.dtype in (torch.int32, torch.uint32) and seq_ids.is_contiguous()
-        n_bytes, D = corpus.numel(), piece_offsets.numel() - 1
-        assert seq_ids.numel() >= D
+        D, n_bytes, s = self._pieces_device(corpus, piece_offsets, seq_ids, stream)
         if mask is not None and not (mask.is_cuda and mask.dtype in (torch.int32, torch.uint32) and mask.is_contiguous()
                                      and mask.numel() >= (n_bytes + 31) // 32):
             raise ValueError("mask must be a contiguous int32/uint32 CUDA tensor of at least ceil(N / 32) entries")
@@ -1653,14 +1660,11 @@ class Feed:
         if piece_back is not None and not (piece_back.is_cuda and piece_back.dtype in (torch.int32, torch.uint32)
                                            and piece_back.is_contiguous() and piece_back.numel() >= D):
             raise ValueError("piece_back must be a contiguous int32/uint32 CUDA tensor of at least D entries")
-        for t, n in ((piece_covered, D), (piece_hit_offsets, D + 1), (piece_bases, D)):
-            assert t is None or (t.is_cuda and t.dtype in (torch.int64, torch.uint64) and t.is_contiguous() and t.numel() >= n)
-        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        self._opt64((piece_covered, D), (piece_hit_offsets, D + 1), (piece_bases, D))
         nc, nh = C.c_uint64(0), C.c_uint64(0)
-        s = stream if stream is not None else torch.cuda.current_stream(corpus.device).cuda_stream
         rc = N.lib().aha_feed_cover_batch_device(
-            self._h, corpus.data_ptr(), piece_offsets.data_ptr(), seq_ids.data_ptr(), D, n_bytes, 0, ptr(mask), ptr(redacted),
-            _fill_byte(fill), ptr(piece_back), ptr(piece_covered), ptr(piece_hit_offsets), ptr(piece_bases), C.byref(nc),
+            self._h, corpus.data_ptr(), piece_offsets.data_ptr(), seq_ids.data_ptr(), D, n_bytes, 0, _dptr(mask), _dptr(redacted),
+            _fill_byte(fill), _dptr(piece_back), _dptr(piece_covered), _dptr(piece_hit_offsets), _dptr(piece_bases), C.byref(nc),
             C.byref(nh), C.c_void_p(s))
         self._check(rc)
         return int(nc.value), int(nh.value)
@@ -1694,14 +1698,7 @@ class Feed:
         "piece_bases" uint64[D], "piece_hold" uint32[D]: the bytes at the end of the sequence whose fate is still open,
         "n_hits"}.  Byte feeds only, and only for sequences fed through select calls alone since their last reset.
         cap None: a sizing call first (a call that does not fit changes nothing)."""
-        if isinstance(corpus, (bytes, bytearray)):
-            corpus = np.frombuffer(bytes(corpus), dtype=np.uint8)
-        corpus = np.ascontiguousarray(corpus, dtype=np.uint8)
-        piece_offsets = np.ascontiguousarray(piece_offsets, dtype=np.uint64)
-        seq_ids = np.ascontiguousarray(seq_ids, dtype=np.uint32)
-        D = piece_offsets.size - 1
-        if seq_ids.size != D:
-            raise ValueError("one sequence id per piece")
+        corpus, piece_offsets, seq_ids, D = self._pieces_host(corpus, piece_offsets, seq_ids)
         flags = N.AHA_FEED_SELECT_FINAL if final else 0
         pso = np.zeros(D + 1, dtype=np.uint64)
         bases = np.zeros(max(D, 1), dtype=np.uint64)
@@ -1720,9 +1717,7 @@ class Feed:
         rc = L.aha_feed_select_batch(self._h, _ptr(corpus), _ptr(piece_offsets), _ptr(seq_ids), D, flags, _ptr(out), int(cap),
                                      _ptr(pso), _ptr(bases), _ptr(hold), C.byref(n), C.byref(nh))
         if rc == N.AHA_E_CAPACITY:
-            e = AhaError(rc, N.lib().aha_strerror(rc).decode())
-            e.n_required = int(n.value)
-            raise e
+            raise self._capacity(rc, n, "n_required")
         self._check(rc)
         return out[: int(n.value)], {"piece_sel_offsets": pso, "piece_bases": bases[:D], "piece_hold": hold[:D],
                                      "n_hits": int(nh.value)}
@@ -1735,33 +1730,22 @@ class Feed:
         (e.n_required = the hits needed); nothing is written then and the feed is unchanged."""
         import torch
 
-        assert corpus.is_cuda and corpus.dtype == torch.uint8 and corpus.is_contiguous()
-        assert piece_offsets.is_cuda and piece_offsets.dtype in (torch.int64, torch.uint64) and piece_offsets.is_contiguous()
-        assert seq_ids.is_cuda and seq_ids.dtype in (torch.int32, torch.uint32) and seq_ids.is_contiguous()
-        D = piece_offsets.numel() - 1
-        assert seq_ids.numel() >= D
+        D, n_bytes, s = self._pieces_device(corpus, piece_offsets, seq_ids, stream)
         if out is not None:
             if not (out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.dim() == 2 and out.shape[1] == 3):
                 raise ValueError("out must be a contiguous int32 CUDA tensor of shape [cap, 3]")
             cap = out.shape[0] if cap is None else min(int(cap), out.shape[0])
         else:
             cap = 0
-        for t, k in ((piece_sel_offsets, D + 1), (piece_bases, D)):
-            assert t is None or (t.is_cuda and t.dtype in (torch.int64, torch.uint64) and t.is_contiguous() and t.numel() >= k)
-        assert piece_hold is None or (piece_hold.is_cuda and piece_hold.dtype in (torch.int32, torch.uint32)
-                                      and piece_hold.is_contiguous() and piece_hold.numel() >= D)
+        self._opt64((piece_sel_offsets, D + 1), (piece_bases, D))
+        self._opt32((piece_hold, D))
         n, nh = C.c_uint64(0), C.c_uint64(0)
-        s = stream if stream is not None else torch.cuda.current_stream(corpus.device).cuda_stream
         rc = N.lib().aha_feed_select_batch_device(
-            self._h, corpus.data_ptr(), piece_offsets.data_ptr(), seq_ids.data_ptr(), D, corpus.numel(),
-            N.AHA_FEED_SELECT_FINAL if final else 0, out.data_ptr() if out is not None and cap else None, cap,
-            piece_sel_offsets.data_ptr() if piece_sel_offsets is not None else None,
-            piece_bases.data_ptr() if piece_bases is not None else None,
-            piece_hold.data_ptr() if piece_hold is not None else None, C.byref(n), C.byref(nh), C.c_void_p(s))
+            self._h, corpus.data_ptr(), piece_offsets.data_ptr(), seq_ids.data_ptr(), D, n_bytes,
+            N.AHA_FEED_SELECT_FINAL if final else 0, _dptr(out) if cap else None, cap, _dptr(piece_sel_offsets), _dptr(piece_bases),
+            _dptr(piece_hold), C.byref(n), C.byref(nh), C.c_void_p(s))
         if rc == N.AHA_E_CAPACITY:
-            e = AhaError(rc, N.lib().aha_strerror(rc).decode())
-            e.n_required = int(n.value)
-            raise e
+            raise self._capacity(rc, n, "n_required")
         self._check(rc)
         return int(n.value), int(nh.value)
 
@@ -1782,14 +1766,7 @@ class Feed:
         -> (uint8 array, info) with info = {"piece_out_offsets" uint64[D+1], "piece_bases" uint64[D], "piece_hold" uint32[D],
         "n_selected", "n_hits"}; piece d's bytes are out[piece_out_offsets[d]:piece_out_offsets[d+1]], and the pieces'
         bytes of one sequence, concatenated, are AC.replace of the whole.  A sizing call first (it changes nothing)."""
-        if isinstance(corpus, (bytes, bytearray)):
-            corpus = np.frombuffer(bytes(corpus), dtype=np.uint8)
-        corpus = np.ascontiguousarray(corpus, dtype=np.uint8)
-        piece_offsets = np.ascontiguousarray(piece_offsets, dtype=np.uint64)
-        seq_ids = np.ascontiguousarray(seq_ids, dtype=np.uint32)
-        D = piece_offsets.size - 1
-        if seq_ids.size != D:
-            raise ValueError("one sequence id per piece")
+        corpus, piece_offsets, seq_ids, D = self._pieces_host(corpus, piece_offsets, seq_ids)
         table = self._ac._table(repl_or_table)
         flags = N.AHA_FEED_REPLACE_FINAL if final else 0
         poo = np.zeros(D + 1, dtype=np.uint64)
@@ -1819,31 +1796,22 @@ class Feed:
         feed is unchanged."""
         import torch
 
-        assert corpus.is_cuda and corpus.dtype == torch.uint8 and corpus.is_contiguous()
-        assert piece_offsets.is_cuda and piece_offsets.dtype in (torch.int64, torch.uint64) and piece_offsets.is_contiguous()
-        assert seq_ids.is_cuda and seq_ids.dtype in (torch.int32, torch.uint32) and seq_ids.is_contiguous()
-        D = piece_offsets.numel() - 1
-        assert seq_ids.numel() >= D
+        D, n_bytes, s = self._pieces_device(corpus, piece_offsets, seq_ids, stream)
         if out is not None:
             if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.dim() == 1):
                 raise ValueError("out must be a contiguous one-dimensional uint8 CUDA tensor")
             cap = out.numel() if cap is None else min(int(cap), out.numel())
         else:
             cap = 0
-        for t, k in ((piece_out_offsets, D + 1), (piece_bases, D)):
-            assert t is None or (t.is_cuda and t.dtype in (torch.int64, torch.uint64) and t.is_contiguous() and t.numel() >= k)
-        assert piece_hold is None or (piece_hold.is_cuda and piece_hold.dtype in (torch.int32, torch.uint32)
-                                      and piece_hold.is_contiguous() and piece_hold.numel() >= D)
+        self._opt64((piece_out_offsets, D + 1), (piece_bases, D))
+        self._opt32((piece_hold, D))
         n, ns, nh = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        s = stream if stream is not None else torch.cuda.current_stream(corpus.device).cuda_stream
         rc = N.lib().aha_feed_replace_batch_device(
-            self._h, table._h, corpus.data_ptr(), piece_offsets.data_ptr(), seq_ids.data_ptr(), D, corpus.numel(),
-            N.AHA_FEED_REPLACE_FINAL if final else 0, out.data_ptr() if out is not None and cap else None, cap,
-            piece_out_offsets.data_ptr() if piece_out_offsets is not None else None,
-            piece_bases.data_ptr() if piece_bases is not None else None,
-            piece_hold.data_ptr() if piece_hold is not None else None, C.byref(n), C.byref(ns), C.byref(nh), C.c_void_p(s))
+            self._h, table._h, corpus.data_ptr(), piece_offsets.data_ptr(), seq_ids.data_ptr(), D, n_bytes,
+            N.AHA_FEED_REPLACE_FINAL if final else 0, _dptr(out) if cap else None, cap, _dptr(piece_out_offsets),
+            _dptr(piece_bases), _dptr(piece_hold), C.byref(n), C.byref(ns), C.byref(nh), C.c_void_p(s))
         if rc == N.AHA_E_CAPACITY:
-            raise AC._capacity_error(rc, n)
+            raise self._capacity(rc, n, "n_required")
         self._check(rc)
         return int(n.value), int(ns.value), int(nh.value)
 
@@ -1871,14 +1839,7 @@ class Feed:
         "piece_rec_bases" uint64[D], "n_recs", "n_hits"}.  With final=True the named sequences start again from length 0.
         Byte feeds only, one delimiter per feed, and only for sequences fed through grep calls alone since their last reset.
         text False: no bytes are copied.  A sizing call first (a call that does not fit changes nothing)."""
-        if isinstance(corpus, (bytes, bytearray)):
-            corpus = np.frombuffer(bytes(corpus), dtype=np.uint8)
-        corpus = np.ascontiguousarray(corpus, dtype=np.uint8)
-        piece_offsets = np.ascontiguousarray(piece_offsets, dtype=np.uint64)
-        seq_ids = np.ascontiguousarray(seq_ids, dtype=np.uint32)
-        D = piece_offsets.size - 1
-        if seq_ids.size != D:
-            raise ValueError("one sequence id per piece")
+        corpus, piece_offsets, seq_ids, D = self._pieces_host(corpus, piece_offsets, seq_ids)
         d = _delim_byte(delim)
         flags = (N.AHA_GREP_INVERT if invert else 0) | (N.AHA_FEED_GREP_FINAL if final else 0)
         pro, pko = np.zeros(D + 1, dtype=np.uint64), np.zeros(D + 1, dtype=np.uint64)
@@ -1918,11 +1879,7 @@ class Feed:
         feed is unchanged."""
         import torch
 
-        assert corpus.is_cuda and corpus.dtype == torch.uint8 and corpus.is_contiguous()
-        assert piece_offsets.is_cuda and piece_offsets.dtype in (torch.int64, torch.uint64) and piece_offsets.is_contiguous()
-        assert seq_ids.is_cuda and seq_ids.dtype in (torch.int32, torch.uint32) and seq_ids.is_contiguous()
-        D = piece_offsets.numel() - 1
-        assert seq_ids.numel() >= D
+        D, n_bytes, s = self._pieces_device(corpus, piece_offsets, seq_ids, stream)
         for name, t in (("kept_recs", kept_recs), ("rec_out_offsets", rec_out_offsets)):
             if t is not None and not (t.is_cuda and t.dtype in (torch.int64, torch.uint64) and t.is_contiguous()):
                 raise ValueError(name + " must be a contiguous int64/uint64 CUDA tensor")
@@ -1940,18 +1897,16 @@ class Feed:
             cap_bytes = out.numel() if cap_bytes is None else min(int(cap_bytes), out.numel())
         else:
             cap_bytes = 0
-        for t, k in ((piece_rec_offsets, D + 1), (piece_kept_offsets, D + 1), (piece_head, D), (piece_bases, D), (piece_rec_bases, D)):
-            assert t is None or (t.is_cuda and t.dtype in (torch.int64, torch.uint64) and t.is_contiguous() and t.numel() >= k)
-        assert piece_hold is None or (piece_hold.is_cuda and piece_hold.dtype in (torch.int32, torch.uint32)
-                                      and piece_hold.is_contiguous() and piece_hold.numel() >= D)
-        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        self._opt64((piece_rec_offsets, D + 1), (piece_kept_offsets, D + 1), (piece_head, D), (piece_bases, D),
+                    (piece_rec_bases, D))
+        self._opt32((piece_hold, D))
         nr, nk, nb, nh = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        s = stream if stream is not None else torch.cuda.current_stream(corpus.device).cuda_stream
         rc = N.lib().aha_feed_grep_batch_device(
-            self._h, corpus.data_ptr(), piece_offsets.data_ptr(), seq_ids.data_ptr(), D, corpus.numel(), _delim_byte(delim),
-            (N.AHA_GREP_INVERT if invert else 0) | (N.AHA_FEED_GREP_FINAL if final else 0), ptr(kept_recs), ptr(rec_out_offsets),
-            cap_recs, ptr(out), cap_bytes, ptr(piece_rec_offsets), ptr(piece_kept_offsets), ptr(piece_hold), ptr(piece_head),
-            ptr(piece_bases), ptr(piece_rec_bases), C.byref(nr), C.byref(nk), C.byref(nb), C.byref(nh), C.c_void_p(s))
+            self._h, corpus.data_ptr(), piece_offsets.data_ptr(), seq_ids.data_ptr(), D, n_bytes, _delim_byte(delim),
+            (N.AHA_GREP_INVERT if invert else 0) | (N.AHA_FEED_GREP_FINAL if final else 0), _dptr(kept_recs),
+            _dptr(rec_out_offsets), cap_recs, _dptr(out), cap_bytes, _dptr(piece_rec_offsets), _dptr(piece_kept_offsets),
+            _dptr(piece_hold), _dptr(piece_head), _dptr(piece_bases), _dptr(piece_rec_bases), C.byref(nr), C.byref(nk),
+            C.byref(nb), C.byref(nh), C.c_void_p(s))
         if rc == N.AHA_E_CAPACITY:
             raise AC._grep_capacity_error(rc, nk, nb)
         self._check(rc)

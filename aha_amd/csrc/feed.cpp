@@ -60,11 +60,53 @@
 // and aha_feed_finish_batch* reports the named sequences' pending hits (kfl_finish: counted, then written) and restarts them.
 // Calls on one feed are serialised by its mutex; its scratch is its own.  The two matches lease one of the handle's scratch
 // sets like any call, so different feeds and plain calls on the same handle run side by side.
+// Every public batch entry has one shape: its family's argument checks (feed_*_args: the refusals both entries share), one call
+// scope (FeedCall: the mutex, the device, the lease), for a host entry the staging of the pieces (stage_pieces: the host checks,
+// then the scope, then the upload), the family function on device-resident pieces (feed_match .. feed_grep), and for a host entry
+// the read-backs (fetch).  What a family adds to the arguments of a call (feed_args) it sets itself.
 #include "feed.hpp"
+
+#include <initializer_list>
+#include <optional>
 
 #include "handle.hpp"
 
 using namespace ahai;
+
+namespace {
+// the feed's grow-only scratch; every slot has a name.  kH*: the host entries' staging of what the caller gives and takes
+enum FeedSlot {
+  kMisc,        // the verdict, the window batch's size, a cover call's total
+  kWin,         // the window batch's bytes
+  kWoff,        // ... its document offsets
+  kWdho,        // ... its per-document hit offsets
+  kWhits,       // ... its hits
+  kMdho,        // the main pass's per-document hit offsets
+  kMhits,       // ... its hits
+  kPho,         // piece hit offsets, where the caller takes none
+  kLeadCtx,     // leads(ctx) (char feeds)
+  kLeadP,       // leads(P) (char feeds)
+  kHCorpus,     // the pieces
+  kHOff,        // piece_offsets
+  kHIds,        // seq_ids
+  kHOut,        // the result: hits, or a replace or grep call's bytes
+  kHPho,        // piece_hit_offsets and what stands in its place: sel, out and seq_hit offsets
+  kHBases,      // piece_bases
+  kKc,          // a count call's per-key sums
+  kHKc,         // key_counts
+  kMask,        // a cover call's mask
+  kHBack,       // piece_back
+  kHCov,        // piece_covered
+  kHHold,       // piece_hold
+  kHKept,       // kept_recs
+  kHRecOut,     // rec_out_offsets
+  kHPieceRec,   // piece_rec_offsets
+  kHPieceKept,  // piece_kept_offsets
+  kHHead,       // piece_head
+  kHRecBases,   // piece_rec_bases
+  kFeedSlots
+};
+}  // namespace
 
 struct aha_feed {
   aha_ac *ac = nullptr;
@@ -85,20 +127,12 @@ struct aha_feed {
   FeedGrepSeq *d_grep = nullptr;
   int grep_delim = -1;
   uint32_t stamp = 0;
-  // grow-only scratch: 0 verdict + window size, 1 window bytes, 2 window offsets, 3 window hit offsets, 4 window hits,
-  // 5 main hit offsets, 6 main hits, 7 piece hit offsets, 8 leads(ctx), 9 leads(P); 10 .. 15 the host entry's staging
-  // (corpus, offsets, ids, hits, piece hit offsets, bases), 16 key counts (a count call's sums), 17 the host entry's key counts,
-  // 18 a cover call's mask, 19 / 20 the host entry's piece_back and piece_covered, 21 the host entry's piece_hold,
-  // 22 .. 27 the host entry's kept_recs, rec_out_offsets, piece_rec_offsets, piece_kept_offsets, piece_head, piece_rec_bases
-  Buf buf[28];
+  Buf buf[kFeedSlots];        // grow-only scratch (FeedSlot)
   uint64_t *h_pin = nullptr;  // pinned: read-backs
   hipStream_t hs = nullptr;   // the host entry's stream (and position / reset)
 };
 
 namespace {
-enum { kMisc, kWin, kWoff, kWdho, kWhits, kMdho, kMhits, kPho, kLeadCtx, kLeadP, kHCorpus, kHOff, kHIds, kHOut, kHPho, kHBases, kKc, kHKc, kMask, kHBack, kHCov, kHHold, kHKept, kHRecOut,
-       kHPieceRec, kHPieceKept, kHHead, kHRecBases };
-
 void *reserve(aha_feed *f, int i, size_t bytes) {
   Buf &b = f->buf[i];
   bytes = std::max<size_t>(bytes, 16);
@@ -696,7 +730,7 @@ int32_t feed_grep(aha_feed *f, Scratch *sc, FeedArgs &F, uint8_t delim, uint32_t
 }
 
 // the part that writes: the caller's hits and offsets, then the feed's own state
-int32_t feed_finish(aha_feed *f, FeedArgs &F, hipStream_t s) {
+int32_t feed_emit(aha_feed *f, FeedArgs &F, hipStream_t s) {
   if (!F.pho) {
     F.pho = (uint64_t *)reserve(f, kPho, (F.D + 1) * 8);
     if (!F.pho) return no_memory("piece hit offsets");
@@ -993,22 +1027,268 @@ int32_t feed_finish_long(aha_feed *f, Scratch *sc, const uint32_t *d_ids, uint64
   return AHA_OK;
 }
 
+// a whole match call on device-resident pieces, whatever the feed was opened for: the part that writes scratch only (*total =
+// the call's hits; above cap -> AHA_E_CAPACITY, nothing committed), then the part that writes.  out_slot >= 0: the hits go into
+// that buffer of the feed, sized once the total is known (the host entry); else into d_out.
+int32_t feed_match(aha_feed *f, Scratch *sc, FeedArgs &F, aha_hit *d_out, int out_slot, uint64_t cap, hipStream_t s, uint64_t *total) {
+  FeedSepArgs P{};
+  FeedLongArgs L{};
+  FeedLongPlan plan;
+  int32_t rc = f->longest ? feed_long_prepare(f, sc, F, cap, s, L, plan, total)
+               : f->sep   ? feed_sep_prepare(f, sc, F, cap, s, P, total)
+                          : feed_prepare(f, sc, F, cap, s, total);
+  if (rc) return rc;
+  if (out_slot >= 0 && !(d_out = (aha_hit *)reserve(f, out_slot, *total * sizeof(aha_hit)))) return no_memory("hits");
+  F.out = reinterpret_cast<int32_t *>(d_out);
+  if (f->longest) return feed_long_emit(f, F, L, plan, out_slot >= 0 ? *total : cap, s);
+  return f->sep ? feed_sep_emit(f, F, P, s) : feed_emit(f, F, s);
+}
+
+// a whole finish call on device-resident ids
+int32_t feed_finish(aha_feed *f, Scratch *sc, const uint32_t *d_ids, uint64_t D, aha_hit *d_out, uint64_t cap, uint64_t *d_sho,
+                    uint64_t *d_bases, hipStream_t s, uint64_t *total) {
+  return f->longest ? feed_finish_long(f, sc, d_ids, D, d_out, cap, d_sho, d_bases, s, total)
+                    : feed_finish_sep(f, sc, d_ids, D, d_out, cap, d_sho, d_bases, s, total);
+}
+
+// ---- what the public entries share ------------------------------------------------------------------------------------
 bool bad_feed(const aha_feed *f) { return !f || !f->ac || f->ac->device < 0; }
+
+// one call's scope: the feed's mutex, its device, one of the handle's scratch sets -- taken in this order
+struct FeedCall {
+  std::lock_guard<std::mutex> lk;
+  DeviceGuard g;
+  Lease lease;
+  explicit FeedCall(aha_feed *f) : lk(f->mu), g(f->ac->device), lease(f->ac) {}
+  Scratch *sc() { return lease.get(); }
+};
+
+// the arguments of a call as every family takes them; what is its own (key_counts, accumulate, back, out) the family sets
+FeedArgs feed_args(const uint8_t *text, const uint64_t *off, const uint32_t *ids, uint64_t D, uint64_t n_bytes, uint64_t *pho,
+                   uint64_t *bases) {
+  FeedArgs F{};
+  F.text = text;
+  F.off = off;
+  F.ids = ids;
+  F.D = D;
+  F.n_bytes = n_bytes;
+  F.pho = pho;
+  F.bases = bases;
+  return F;
+}
+
+// the ids a call names: each below n_seqs and only once (what kfd_check asks of them)
+struct SeenIds {
+  std::vector<uint8_t> seen;
+  bool init(uint32_t n_seqs) {
+    try {
+      seen.assign(n_seqs, 0);
+    } catch (...) {
+      return false;
+    }
+    return true;
+  }
+  bool take(uint32_t id) { return id < seen.size() && !seen[id]++; }
+};
 
 // the checks kfd_check makes, on the host (the host entries)
 int32_t check_pieces_host(const aha_feed *f, const uint64_t *piece_offsets, const uint32_t *seq_ids, uint64_t n_pieces) {
   if (piece_offsets[0] != 0) return AHA_E_INVALID;
   const uint64_t max_piece = (1ull << 31) - std::max<uint64_t>(f->ac->aut.max_key_len, 1);
-  std::vector<uint8_t> seen;
-  try {
-    seen.assign(f->n_seqs, 0);
-  } catch (...) {
-    return AHA_E_NOMEM;
-  }
+  SeenIds seen;
+  if (!seen.init(f->n_seqs)) return AHA_E_NOMEM;
   for (uint64_t d = 0; d < n_pieces; d++) {
-    if (piece_offsets[d + 1] < piece_offsets[d] || seq_ids[d] >= f->n_seqs || seen[seq_ids[d]]++) return AHA_E_INVALID;
+    if (piece_offsets[d + 1] < piece_offsets[d] || !seen.take(seq_ids[d])) return AHA_E_INVALID;
     if (piece_offsets[d + 1] - piece_offsets[d] >= max_piece) return AHA_E_TOO_LONG;
   }
+  return AHA_OK;
+}
+
+// ... and of a finish call's ids
+int32_t check_ids_host(const aha_feed *f, const uint32_t *seq_ids, uint64_t n_named) {
+  SeenIds seen;
+  if (!seen.init(f->n_seqs)) return AHA_E_NOMEM;
+  for (uint64_t d = 0; d < n_named; d++)
+    if (!seen.take(seq_ids[d])) {
+      tls_err = "feed finish: need seq_ids below n_seqs and each once";
+      return AHA_E_INVALID;
+    }
+  return AHA_OK;
+}
+
+int32_t overlap_refused(const char *what, const uint8_t *corpus, uint64_t n_bytes, const uint8_t *out, uint64_t cap_bytes) {
+  if (cap_bytes && n_bytes && corpus) {
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), c0 = reinterpret_cast<uintptr_t>(corpus);
+    if (o0 < c0 + n_bytes && c0 < o0 + cap_bytes) {
+      tls_err = std::string("feed ") + what + " calls have no in-place form: out overlaps the corpus";
+      return AHA_E_INVALID;
+    }
+  }
+  return AHA_OK;
+}
+
+// what a host entry stages beside the pieces (stage_pieces): the per-piece arrays of its family, and for grep the caller's
+// result buffer, which must not overlap the corpus
+enum { kWantHold = 1, kWantBack = 2, kWantCov = 4, kWantGrep = 8 };
+struct StageAsk {
+  unsigned want = 0;
+  const uint8_t *out = nullptr;
+  uint64_t cap_bytes = 0;
+};
+// the staged pieces of a host call, on the device.  pho stands for the family's (D + 1)-entry offsets
+struct Staged {
+  uint64_t n_bytes;
+  uint8_t *corpus;
+  uint64_t *off;
+  uint32_t *ids;
+  uint64_t *pho, *bases;
+  uint32_t *hold, *back;                                // kWantHold, kWantBack
+  uint64_t *cov;                                        // kWantCov
+  uint64_t *piece_rec, *piece_kept, *head, *rec_bases;  // kWantGrep
+};
+
+// the host entries' prologue: the pieces checked as kfd_check checks them -- before the lock is taken -- then the call's scope,
+// the staging buffers and the upload over the feed's stream
+int32_t stage_pieces(aha_feed *f, std::optional<FeedCall> &call, const uint8_t *corpus, const uint64_t *piece_offsets,
+                     const uint32_t *seq_ids, uint64_t n_pieces, const StageAsk &ask, Staged &B) {
+  int32_t rc = check_pieces_host(f, piece_offsets, seq_ids, n_pieces);
+  if (rc) return rc;
+  const uint64_t n_bytes = piece_offsets[n_pieces], D = n_pieces;
+  if (n_bytes && !corpus) return AHA_E_INVALID;
+  if ((rc = overlap_refused("grep", corpus, n_bytes, ask.out, ask.cap_bytes))) return rc;
+  call.emplace(f);
+  hipStream_t s = f->hs;
+  B = Staged{};
+  B.n_bytes = n_bytes;
+  uint8_t *d_corpus = B.corpus = (uint8_t *)reserve(f, kHCorpus, n_bytes + 64);
+  uint64_t *d_off = B.off = (uint64_t *)reserve(f, kHOff, (D + 1) * 8);
+  uint32_t *d_ids = B.ids = (uint32_t *)reserve(f, kHIds, D * 4);
+  B.pho = (uint64_t *)reserve(f, kHPho, (D + 1) * 8);
+  B.bases = (uint64_t *)reserve(f, kHBases, D * 8);
+  bool ok = d_corpus && d_off && d_ids && B.pho && B.bases;
+  if (ask.want & kWantHold) ok &= (B.hold = (uint32_t *)reserve(f, kHHold, D * 4)) != nullptr;
+  if (ask.want & kWantBack) ok &= (B.back = (uint32_t *)reserve(f, kHBack, D * 4)) != nullptr;
+  if (ask.want & kWantCov) ok &= (B.cov = (uint64_t *)reserve(f, kHCov, D * 8)) != nullptr;
+  if (ask.want & kWantGrep) {
+    ok &= (B.piece_rec = (uint64_t *)reserve(f, kHPieceRec, (D + 1) * 8)) != nullptr;
+    ok &= (B.piece_kept = (uint64_t *)reserve(f, kHPieceKept, (D + 1) * 8)) != nullptr;
+    ok &= (B.head = (uint64_t *)reserve(f, kHHead, D * 8)) != nullptr;
+    ok &= (B.rec_bases = (uint64_t *)reserve(f, kHRecBases, D * 8)) != nullptr;
+  }
+  if (!ok) return no_memory("staging buffers");
+  // (the names HIPCHK quotes in aha_last_error, as the entries had them)
+  if (n_bytes) HIPCHK(f->ac, hipMemcpyAsync(d_corpus, corpus, n_bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(f->ac, hipMemcpyAsync(d_off, piece_offsets, (D + 1) * 8, hipMemcpyHostToDevice, s));
+  if (D) HIPCHK(f->ac, hipMemcpyAsync(d_ids, seq_ids, D * 4, hipMemcpyHostToDevice, s));
+  return AHA_OK;
+}
+
+// the host entries' epilogue: what the caller asked for comes back over the feed's stream, then the stream is awaited.  A null
+// array and an empty one are skipped: a per-piece array where D == 0 (the (D + 1)-entry offsets are never empty)
+struct Back {
+  void *dst;
+  const void *src;
+  size_t bytes;
+};
+int32_t fetch(aha_feed *f, std::initializer_list<Back> back) {
+  hipStream_t s = f->hs;
+  for (const Back &b : back)
+    if (b.dst && b.bytes) HIPCHK(f->ac, hipMemcpyAsync(b.dst, b.src, b.bytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(f->ac, hipStreamSynchronize(s));
+  return AHA_OK;
+}
+
+// the argument checks both entries of a family share, before any device work.  no_corpus: a device entry's n_bytes && !d_corpus
+// (a host entry knows n_bytes only from the offsets it has yet to check: stage_pieces)
+int32_t feed_match_args(const aha_feed *f, const uint64_t *piece_offsets, const uint32_t *seq_ids, uint64_t n_pieces, const aha_hit *out,
+                        uint64_t cap, const uint64_t *n_hits, bool no_corpus) {
+  if (!f || !n_hits || !piece_offsets || (n_pieces && !seq_ids) || (cap && !out) || no_corpus) return AHA_E_INVALID;
+  if (bad_feed(f)) return AHA_E_NO_DEVICE;
+  return AHA_OK;
+}
+
+int32_t feed_finish_args(const aha_feed *f, const uint32_t *seq_ids, uint64_t n_named, const aha_hit *out, uint64_t cap,
+                         const uint64_t *n_hits) {
+  if (!f || !n_hits || (n_named && !seq_ids) || (cap && !out)) return AHA_E_INVALID;
+  if (bad_feed(f)) return AHA_E_NO_DEVICE;
+  if (!f->sep && !f->longest) {
+    tls_err = "feed finish: the feed has neither a separator filter nor match_longest (aha_feed_open_params); its sequences end with "
+              "aha_feed_reset";
+    return AHA_E_INVALID;
+  }
+  return AHA_OK;
+}
+
+int32_t feed_count_args(const aha_feed *f, const uint64_t *piece_offsets, const uint32_t *seq_ids, uint64_t n_pieces, uint32_t flags,
+                        const uint64_t *n_hits, bool no_corpus) {
+  if (!f || !n_hits || !piece_offsets || (n_pieces && !seq_ids) || no_corpus || (flags & ~AHA_COUNT_ACCUMULATE)) return AHA_E_INVALID;
+  if (bad_feed(f)) return AHA_E_NO_DEVICE;
+  if (f->longest) return longest_refused("count");
+  return AHA_OK;
+}
+
+int32_t feed_cover_args(const aha_feed *f, const uint64_t *piece_offsets, const uint32_t *seq_ids, uint64_t n_pieces, uint32_t flags,
+                        const uint64_t *n_covered, bool no_corpus) {
+  if (!f || !n_covered || !piece_offsets || (n_pieces && !seq_ids) || no_corpus || flags) return AHA_E_INVALID;
+  if (bad_feed(f)) return AHA_E_NO_DEVICE;
+  if (f->sep) return sep_refused("cover");
+  if (f->longest) return longest_refused("cover");
+  return AHA_OK;
+}
+
+// a family that works in bytes (select, replace, grep) on a char feed, a feed with a separator filter or a longest feed
+int32_t bytes_only_refused(const aha_feed *f, const char *what) {
+  if (f->chars) {
+    tls_err = std::string("feed ") + what + ": a char feed (AHA_FEED_CHARS); " + what + " is in bytes";
+    return AHA_E_INVALID;
+  }
+  if (f->sep) return sep_refused(what);
+  if (f->longest) return longest_refused(what);
+  return AHA_OK;
+}
+
+int32_t feed_select_args(const aha_feed *f, const uint64_t *piece_offsets, const uint32_t *seq_ids, uint64_t n_pieces, uint32_t flags,
+                         const aha_hit *out, uint64_t cap, const uint64_t *n_selected, bool no_corpus) {
+  if (!f || !n_selected || !piece_offsets || (n_pieces && !seq_ids) || (cap && !out) || no_corpus || (flags & ~AHA_FEED_SELECT_FINAL))
+    return AHA_E_INVALID;
+  if (bad_feed(f)) return AHA_E_NO_DEVICE;
+  return bytes_only_refused(f, "select");
+}
+
+int32_t feed_replace_args(const aha_feed *f, const aha_repl *table, const uint64_t *piece_offsets, const uint32_t *seq_ids,
+                          uint64_t n_pieces, uint32_t flags, const uint8_t *out, uint64_t cap_bytes, const uint64_t *n_out_bytes) {
+  if (!f || !table || !n_out_bytes || !piece_offsets || (n_pieces && !seq_ids) || (cap_bytes && !out) ||
+      (flags & ~AHA_FEED_REPLACE_FINAL))
+    return AHA_E_INVALID;
+  if (bad_feed(f)) return AHA_E_NO_DEVICE;
+  if (table->owner != f->ac->serial) {
+    tls_err = "the replacement table was made for another handle";
+    return AHA_E_INVALID;
+  }
+  int32_t rc = bytes_only_refused(f, "replace");
+  if (rc) return rc;
+  if (!table->d_ent) return no_device();
+  return AHA_OK;
+}
+
+int32_t feed_grep_args(const aha_feed *f, const uint64_t *piece_offsets, const uint32_t *seq_ids, uint64_t n_pieces, uint32_t flags,
+                       const uint64_t *kept_recs, const uint64_t *rec_out_offsets, uint64_t cap_recs, const uint8_t *out,
+                       uint64_t cap_bytes, const uint64_t *n_kept) {
+  if (!f || !n_kept || !piece_offsets || (n_pieces && !seq_ids) || (flags & ~(AHA_GREP_INVERT | AHA_FEED_GREP_FINAL)))
+    return AHA_E_INVALID;
+  if ((cap_recs && !kept_recs && !rec_out_offsets) || (cap_bytes && !out)) return AHA_E_INVALID;
+  if (bad_feed(f)) return AHA_E_NO_DEVICE;
+  return bytes_only_refused(f, "grep");
+}
+
+// all records of a per-sequence array cleared (seq == UINT32_MAX), or the first `bytes` bytes of one; an array not allocated yet
+// has nothing to clear
+int32_t clear_seqs(aha_feed *f, void *base, size_t stride, size_t bytes, uint32_t seq) {
+  if (!base) return AHA_OK;
+  if (seq == UINT32_MAX)
+    HIPCHK(f->ac, hipMemsetAsync(base, 0, (size_t)f->n_seqs * stride, f->hs));
+  else
+    HIPCHK(f->ac, hipMemsetAsync((uint8_t *)base + (size_t)seq * stride, 0, bytes, f->hs));
   return AHA_OK;
 }
 }  // namespace
@@ -1054,22 +1334,13 @@ int32_t aha_feed_open_params(aha_ac *ac, uint32_t n_seqs, uint32_t flags, const 
       return AHA_E_INVALID;
     }
   }
-  if (ac->fold_mode() == 4) {  // (before any device work, host-only handles included)
-    tls_err = "aha_feed_open: no feed on a handle compiled with AHA_OPT_FOLD_KANA yet: a two- or three-byte character may be cut "
-              "between two calls, and the context a feed keeps would have to carry part of it (a follow-up; fold the pieces' "
-              "sequences whole, or use AHA_OPT_FOLD_ASCII)";
-    return AHA_E_INVALID;
-  }
-  if (ac->fold_mode() == 3) {  // (before any device work, host-only handles included)
-    tls_err = "aha_feed_open: no feed on a handle compiled with AHA_OPT_FOLD_BMP yet: a two- or three-byte character may be cut "
-              "between two calls, and the context a feed keeps would have to carry part of it (a follow-up; fold the pieces' "
-              "sequences whole, or use AHA_OPT_FOLD_ASCII)";
-    return AHA_E_INVALID;
-  }
-  if (ac->fold_mode() == 2) {  // (before any device work, host-only handles included)
-    tls_err = "aha_feed_open: no feed on a handle compiled with AHA_OPT_FOLD_SIMPLE yet: a two-byte character may be cut between "
-              "two calls, and the context a feed keeps would have to carry half of it (a follow-up; fold the pieces' "
-              "sequences whole, or use AHA_OPT_FOLD_ASCII)";
+  if (const int mode = ac->fold_mode(); mode >= 2 && mode <= 4) {  // (before any device work, host-only handles included)
+    const char *option = mode == 2 ? "SIMPLE" : mode == 3 ? "BMP" : "KANA";
+    tls_err = std::string("aha_feed_open: no feed on a handle compiled with AHA_OPT_FOLD_") + option + " yet: a " +
+              (mode == 2 ? "two-byte" : "two- or three-byte") +
+              " character may be cut between two calls, and the context a feed keeps would have to carry " +
+              (mode == 2 ? "half" : "part") +
+              " of it (a follow-up; fold the pieces' sequences whole, or use AHA_OPT_FOLD_ASCII)";
     return AHA_E_INVALID;
   }
   if (ac->device < 0) {
@@ -1137,26 +1408,15 @@ int32_t aha_feed_reset(aha_feed *f, uint32_t seq) {
   std::lock_guard<std::mutex> lk(f->mu);
   aha_ac *ac = f->ac;
   DeviceGuard g(ac->device);
+  int32_t rc;
   // a sequence of length 0 has an empty context: only the counters are cleared (a stamp of 0 is never a call's)
-  if (seq == UINT32_MAX)
-    HIPCHK(ac, hipMemsetAsync(f->d_seqs, 0, (size_t)f->n_seqs * sizeof(FeedSeq), f->hs));
-  else
-    HIPCHK(ac, hipMemsetAsync(f->d_seqs + seq, 0, 2 * sizeof(uint64_t), f->hs));
+  if ((rc = clear_seqs(f, f->d_seqs, sizeof(FeedSeq), 2 * sizeof(uint64_t), seq))) return rc;
   // the select state too: a sequence of length 0 has no open hits (its tail is never read) and its cursor is 0
-  if (f->d_sel && seq == UINT32_MAX)
-    HIPCHK(ac, hipMemsetAsync(f->d_sel, 0, (size_t)f->n_seqs * sizeof(FeedSelSeq), f->hs));
-  else if (f->d_sel)
-    HIPCHK(ac, hipMemsetAsync(f->d_sel + seq, 0, sizeof(FeedSelSeq), f->hs));
+  if ((rc = clear_seqs(f, f->d_sel, sizeof(FeedSelSeq), sizeof(FeedSelSeq), seq))) return rc;
   // ... and the grep state: no record is open, none is closed
-  if (f->d_grep && seq == UINT32_MAX)
-    HIPCHK(ac, hipMemsetAsync(f->d_grep, 0, (size_t)f->n_seqs * sizeof(FeedGrepSeq), f->hs));
-  else if (f->d_grep)
-    HIPCHK(ac, hipMemsetAsync(f->d_grep + seq, 0, sizeof(FeedGrepSeq), f->hs));
+  if ((rc = clear_seqs(f, f->d_grep, sizeof(FeedGrepSeq), sizeof(FeedGrepSeq), seq))) return rc;
   // ... and a longest feed's carried state: the root, nothing pending
-  if (f->d_long && seq == UINT32_MAX)
-    HIPCHK(ac, hipMemsetAsync(f->d_long, 0, (size_t)f->n_seqs * sizeof(FeedLongSeq), f->hs));
-  else if (f->d_long)
-    HIPCHK(ac, hipMemsetAsync(f->d_long + seq, 0, sizeof(FeedLongSeq), f->hs));
+  if ((rc = clear_seqs(f, f->d_long, sizeof(FeedLongSeq), sizeof(FeedLongSeq), seq))) return rc;
   HIPCHK(ac, hipStreamSynchronize(f->hs));
   return AHA_OK;
 }
@@ -1178,151 +1438,57 @@ int32_t aha_feed_match_batch_device(aha_feed *f, const uint8_t *d_corpus, const 
                                     const uint32_t *d_seq_ids, uint64_t n_pieces, uint64_t n_bytes, aha_hit *d_out,
                                     uint64_t cap, uint64_t *d_piece_hit_offsets, uint64_t *d_piece_bases, uint64_t *n_hits,
                                     void *stream) {
-  if (!f || !n_hits || !d_piece_offsets || (n_pieces && !d_seq_ids) || (cap && !d_out) || (n_bytes && !d_corpus))
-    return AHA_E_INVALID;
-  if (bad_feed(f)) return AHA_E_NO_DEVICE;
-  std::lock_guard<std::mutex> lk(f->mu);
-  DeviceGuard g(f->ac->device);
-  Lease lease(f->ac);
-  hipStream_t s = (hipStream_t)stream;
-  FeedArgs F{};
-  F.text = d_corpus;
-  F.off = d_piece_offsets;
-  F.ids = d_seq_ids;
-  F.D = n_pieces;
-  F.n_bytes = n_bytes;
-  F.out = reinterpret_cast<int32_t *>(d_out);
-  F.pho = d_piece_hit_offsets;
-  F.bases = d_piece_bases;
+  int32_t rc = feed_match_args(f, d_piece_offsets, d_seq_ids, n_pieces, d_out, cap, n_hits, n_bytes && !d_corpus);
+  if (rc) return rc;
+  FeedCall call(f);
+  FeedArgs F = feed_args(d_corpus, d_piece_offsets, d_seq_ids, n_pieces, n_bytes, d_piece_hit_offsets, d_piece_bases);
   uint64_t total = 0;
   *n_hits = 0;
-  if (f->longest) {
-    FeedLongArgs L{};
-    FeedLongPlan plan;
-    int32_t rc = feed_long_prepare(f, lease.get(), F, cap, s, L, plan, &total);
-    if (rc == AHA_E_CAPACITY) *n_hits = total;
-    if (rc) return rc;
-    if ((rc = feed_long_emit(f, F, L, plan, cap, s))) return rc;
-    *n_hits = total;
-    return AHA_OK;
-  }
-  FeedSepArgs P{};
-  int32_t rc = f->sep ? feed_sep_prepare(f, lease.get(), F, cap, s, P, &total) : feed_prepare(f, lease.get(), F, cap, s, &total);
-  if (rc == AHA_E_CAPACITY) *n_hits = total;
-  if (rc) return rc;
-  if ((rc = f->sep ? feed_sep_emit(f, F, P, s) : feed_finish(f, F, s))) return rc;
-  *n_hits = total;
-  return AHA_OK;
+  rc = feed_match(f, call.sc(), F, d_out, -1, cap, (hipStream_t)stream, &total);
+  if (rc == AHA_OK || rc == AHA_E_CAPACITY) *n_hits = total;
+  return rc;
 }
 
 int32_t aha_feed_match_batch(aha_feed *f, const uint8_t *corpus, const uint64_t *piece_offsets, const uint32_t *seq_ids,
                              uint64_t n_pieces, aha_hit *out, uint64_t cap, uint64_t *piece_hit_offsets,
                              uint64_t *piece_bases, uint64_t *n_hits) {
-  if (!f || !n_hits || !piece_offsets || (n_pieces && !seq_ids) || (cap && !out)) return AHA_E_INVALID;
-  if (bad_feed(f)) return AHA_E_NO_DEVICE;
-  aha_ac *ac = f->ac;
-  int32_t rc = check_pieces_host(f, piece_offsets, seq_ids, n_pieces);
+  int32_t rc = feed_match_args(f, piece_offsets, seq_ids, n_pieces, out, cap, n_hits, false);
   if (rc) return rc;
-  const uint64_t n_bytes = piece_offsets[n_pieces];
-  if (n_bytes && !corpus) return AHA_E_INVALID;
-  std::lock_guard<std::mutex> lk(f->mu);
-  DeviceGuard g(ac->device);
-  Lease lease(ac);
-  hipStream_t s = f->hs;
+  std::optional<FeedCall> call;
+  Staged B;
+  if ((rc = stage_pieces(f, call, corpus, piece_offsets, seq_ids, n_pieces, {}, B))) return rc;
   const uint64_t D = n_pieces;
-  uint8_t *d_corpus = (uint8_t *)reserve(f, kHCorpus, n_bytes + 64);
-  uint64_t *d_off = (uint64_t *)reserve(f, kHOff, (D + 1) * 8);
-  uint32_t *d_ids = (uint32_t *)reserve(f, kHIds, D * 4);
-  uint64_t *d_pho = (uint64_t *)reserve(f, kHPho, (D + 1) * 8);
-  uint64_t *d_bases = (uint64_t *)reserve(f, kHBases, D * 8);
-  if (!d_corpus || !d_off || !d_ids || !d_pho || !d_bases) return no_memory("staging buffers");
-  if (n_bytes) HIPCHK(ac, hipMemcpyAsync(d_corpus, corpus, n_bytes, hipMemcpyHostToDevice, s));
-  HIPCHK(ac, hipMemcpyAsync(d_off, piece_offsets, (D + 1) * 8, hipMemcpyHostToDevice, s));
-  if (D) HIPCHK(ac, hipMemcpyAsync(d_ids, seq_ids, D * 4, hipMemcpyHostToDevice, s));
-  FeedArgs F{};
-  F.text = d_corpus;
-  F.off = d_off;
-  F.ids = d_ids;
-  F.D = D;
-  F.n_bytes = n_bytes;
-  F.pho = d_pho;
-  F.bases = d_bases;
+  FeedArgs F = feed_args(B.corpus, B.off, B.ids, D, B.n_bytes, B.pho, B.bases);
   uint64_t total = 0;
   *n_hits = 0;
-  FeedSepArgs P{};
-  FeedLongArgs L{};
-  FeedLongPlan plan;
-  if (f->longest)
-    rc = feed_long_prepare(f, lease.get(), F, cap, s, L, plan, &total);
-  else
-    rc = f->sep ? feed_sep_prepare(f, lease.get(), F, cap, s, P, &total) : feed_prepare(f, lease.get(), F, cap, s, &total);
+  rc = feed_match(f, call->sc(), F, nullptr, kHOut, cap, f->hs, &total);
   if (rc == AHA_E_CAPACITY) *n_hits = total;
   if (rc) return rc;
-  aha_hit *d_out = (aha_hit *)reserve(f, kHOut, total * sizeof(aha_hit));
-  if (!d_out) return no_memory("hits");
-  F.out = reinterpret_cast<int32_t *>(d_out);
-  if (f->longest)
-    rc = feed_long_emit(f, F, L, plan, total, s);
-  else
-    rc = f->sep ? feed_sep_emit(f, F, P, s) : feed_finish(f, F, s);
-  if (rc) return rc;
-  if (total) HIPCHK(ac, hipMemcpyAsync(out, d_out, total * sizeof(aha_hit), hipMemcpyDeviceToHost, s));
-  if (piece_hit_offsets) HIPCHK(ac, hipMemcpyAsync(piece_hit_offsets, d_pho, (D + 1) * 8, hipMemcpyDeviceToHost, s));
-  if (piece_bases && D) HIPCHK(ac, hipMemcpyAsync(piece_bases, d_bases, D * 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(ac, hipStreamSynchronize(s));
+  if ((rc = fetch(f, {{out, F.out, total * sizeof(aha_hit)}, {piece_hit_offsets, B.pho, (D + 1) * 8}, {piece_bases, B.bases, D * 8}})))
+    return rc;
   *n_hits = total;
   return AHA_OK;
 }
 
-
 int32_t aha_feed_finish_batch_device(aha_feed *f, const uint32_t *d_seq_ids, uint64_t n_named, aha_hit *d_out, uint64_t cap,
                                      uint64_t *d_seq_hit_offsets, uint64_t *d_bases, uint64_t *n_hits, void *stream) {
-  if (!f || !n_hits || (n_named && !d_seq_ids) || (cap && !d_out)) return AHA_E_INVALID;
-  if (bad_feed(f)) return AHA_E_NO_DEVICE;
-  if (!f->sep && !f->longest) {
-    tls_err = "feed finish: the feed has neither a separator filter nor match_longest (aha_feed_open_params); its sequences end with "
-              "aha_feed_reset";
-    return AHA_E_INVALID;
-  }
-  std::lock_guard<std::mutex> lk(f->mu);
-  DeviceGuard g(f->ac->device);
-  Lease lease(f->ac);
+  int32_t rc = feed_finish_args(f, d_seq_ids, n_named, d_out, cap, n_hits);
+  if (rc) return rc;
+  FeedCall call(f);
   uint64_t total = 0;
   *n_hits = 0;
-  int32_t rc = f->longest ? feed_finish_long(f, lease.get(), d_seq_ids, n_named, d_out, cap, d_seq_hit_offsets, d_bases, (hipStream_t)stream, &total)
-                          : feed_finish_sep(f, lease.get(), d_seq_ids, n_named, d_out, cap, d_seq_hit_offsets, d_bases, (hipStream_t)stream, &total);
-  if (rc == AHA_E_CAPACITY) *n_hits = total;
-  if (rc) return rc;
-  *n_hits = total;
-  return AHA_OK;
+  rc = feed_finish(f, call.sc(), d_seq_ids, n_named, d_out, cap, d_seq_hit_offsets, d_bases, (hipStream_t)stream, &total);
+  if (rc == AHA_OK || rc == AHA_E_CAPACITY) *n_hits = total;
+  return rc;
 }
 
 int32_t aha_feed_finish_batch(aha_feed *f, const uint32_t *seq_ids, uint64_t n_named, aha_hit *out, uint64_t cap,
                               uint64_t *seq_hit_offsets, uint64_t *bases, uint64_t *n_hits) {
-  if (!f || !n_hits || (n_named && !seq_ids) || (cap && !out)) return AHA_E_INVALID;
-  if (bad_feed(f)) return AHA_E_NO_DEVICE;
-  if (!f->sep && !f->longest) {
-    tls_err = "feed finish: the feed has neither a separator filter nor match_longest (aha_feed_open_params); its sequences end with "
-              "aha_feed_reset";
-    return AHA_E_INVALID;
-  }
+  int32_t rc = feed_finish_args(f, seq_ids, n_named, out, cap, n_hits);
+  if (rc) return rc;
+  if ((rc = check_ids_host(f, seq_ids, n_named))) return rc;
+  FeedCall call(f);
   aha_ac *ac = f->ac;
-  {
-    std::vector<uint8_t> seen;
-    try {
-      seen.assign(f->n_seqs, 0);
-    } catch (...) {
-      return AHA_E_NOMEM;
-    }
-    for (uint64_t d = 0; d < n_named; d++)
-      if (seq_ids[d] >= f->n_seqs || seen[seq_ids[d]]++) {
-        tls_err = "feed finish: need seq_ids below n_seqs and each once";
-        return AHA_E_INVALID;
-      }
-  }
-  std::lock_guard<std::mutex> lk(f->mu);
-  DeviceGuard g(ac->device);
-  Lease lease(ac);
   hipStream_t s = f->hs;
   const uint64_t D = n_named;
   // (a sequence ends at most Lmax hits: one per key length)
@@ -1335,14 +1501,10 @@ int32_t aha_feed_finish_batch(aha_feed *f, const uint32_t *seq_ids, uint64_t n_n
   if (D) HIPCHK(ac, hipMemcpyAsync(d_ids, seq_ids, D * 4, hipMemcpyHostToDevice, s));
   uint64_t total = 0;
   *n_hits = 0;
-  int32_t rc = f->longest ? feed_finish_long(f, lease.get(), d_ids, D, d_out, cap_d, d_sho, d_bases, s, &total)
-                          : feed_finish_sep(f, lease.get(), d_ids, D, d_out, cap_d, d_sho, d_bases, s, &total);
+  rc = feed_finish(f, call.sc(), d_ids, D, d_out, cap_d, d_sho, d_bases, s, &total);
   if (rc == AHA_E_CAPACITY) *n_hits = total;
   if (rc) return rc;
-  if (total) HIPCHK(ac, hipMemcpyAsync(out, d_out, total * sizeof(aha_hit), hipMemcpyDeviceToHost, s));
-  if (seq_hit_offsets) HIPCHK(ac, hipMemcpyAsync(seq_hit_offsets, d_sho, (D + 1) * 8, hipMemcpyDeviceToHost, s));
-  if (bases && D) HIPCHK(ac, hipMemcpyAsync(bases, d_bases, D * 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(ac, hipStreamSynchronize(s));
+  if ((rc = fetch(f, {{out, d_out, total * sizeof(aha_hit)}, {seq_hit_offsets, d_sho, (D + 1) * 8}, {bases, d_bases, D * 8}}))) return rc;
   *n_hits = total;
   return AHA_OK;
 }
@@ -1351,27 +1513,15 @@ int32_t aha_feed_count_batch_device(aha_feed *f, const uint8_t *d_corpus, const 
                                     const uint32_t *d_seq_ids, uint64_t n_pieces, uint64_t n_bytes, uint32_t flags,
                                     uint64_t *d_key_counts, uint64_t *d_piece_hit_offsets, uint64_t *d_piece_bases,
                                     uint64_t *n_hits, void *stream) {
-  if (!f || !n_hits || !d_piece_offsets || (n_pieces && !d_seq_ids) || (n_bytes && !d_corpus) || (flags & ~AHA_COUNT_ACCUMULATE))
-    return AHA_E_INVALID;
-  if (bad_feed(f)) return AHA_E_NO_DEVICE;
-  if (f->longest) return longest_refused("count");
-  std::lock_guard<std::mutex> lk(f->mu);
-  DeviceGuard g(f->ac->device);
-  Lease lease(f->ac);
-  FeedArgs F{};
-  F.text = d_corpus;
-  F.off = d_piece_offsets;
-  F.ids = d_seq_ids;
-  F.D = n_pieces;
-  F.n_bytes = n_bytes;
-  F.pho = d_piece_hit_offsets;
-  F.bases = d_piece_bases;
+  int32_t rc = feed_count_args(f, d_piece_offsets, d_seq_ids, n_pieces, flags, n_hits, n_bytes && !d_corpus);
+  if (rc) return rc;
+  FeedCall call(f);
+  FeedArgs F = feed_args(d_corpus, d_piece_offsets, d_seq_ids, n_pieces, n_bytes, d_piece_hit_offsets, d_piece_bases);
   F.key_counts = d_key_counts;
   F.accumulate = (flags & AHA_COUNT_ACCUMULATE) ? 1u : 0u;
   uint64_t total = 0;
   *n_hits = 0;
-  int32_t rc = feed_count(f, lease.get(), F, (hipStream_t)stream, &total);
-  if (rc) return rc;
+  if ((rc = feed_count(f, call.sc(), F, (hipStream_t)stream, &total))) return rc;
   *n_hits = total;
   return AHA_OK;
 }
@@ -1379,50 +1529,27 @@ int32_t aha_feed_count_batch_device(aha_feed *f, const uint8_t *d_corpus, const 
 int32_t aha_feed_count_batch(aha_feed *f, const uint8_t *corpus, const uint64_t *piece_offsets, const uint32_t *seq_ids,
                              uint64_t n_pieces, uint32_t flags, uint64_t *key_counts, uint64_t *piece_hit_offsets,
                              uint64_t *piece_bases, uint64_t *n_hits) {
-  if (!f || !n_hits || !piece_offsets || (n_pieces && !seq_ids) || (flags & ~AHA_COUNT_ACCUMULATE)) return AHA_E_INVALID;
-  if (bad_feed(f)) return AHA_E_NO_DEVICE;
-  if (f->longest) return longest_refused("count");
-  aha_ac *ac = f->ac;
-  int32_t rc = check_pieces_host(f, piece_offsets, seq_ids, n_pieces);
+  int32_t rc = feed_count_args(f, piece_offsets, seq_ids, n_pieces, flags, n_hits, false);
   if (rc) return rc;
-  const uint64_t n_bytes = piece_offsets[n_pieces];
-  if (n_bytes && !corpus) return AHA_E_INVALID;
-  std::lock_guard<std::mutex> lk(f->mu);
-  DeviceGuard g(ac->device);
-  Lease lease(ac);
+  std::optional<FeedCall> call;
+  Staged B;
+  if ((rc = stage_pieces(f, call, corpus, piece_offsets, seq_ids, n_pieces, {}, B))) return rc;
+  aha_ac *ac = f->ac;
   hipStream_t s = f->hs;
   const uint64_t D = n_pieces;
   const size_t kc_bytes = (size_t)ac->aut.n_keys * 8;
-  uint8_t *d_corpus = (uint8_t *)reserve(f, kHCorpus, n_bytes + 64);
-  uint64_t *d_off = (uint64_t *)reserve(f, kHOff, (D + 1) * 8);
-  uint32_t *d_ids = (uint32_t *)reserve(f, kHIds, D * 4);
-  uint64_t *d_pho = (uint64_t *)reserve(f, kHPho, (D + 1) * 8);
-  uint64_t *d_bases = (uint64_t *)reserve(f, kHBases, D * 8);
   uint64_t *d_kc = key_counts ? (uint64_t *)reserve(f, kHKc, kc_bytes) : nullptr;
-  if (!d_corpus || !d_off || !d_ids || !d_pho || !d_bases || (key_counts && !d_kc)) return no_memory("staging buffers");
-  if (n_bytes) HIPCHK(ac, hipMemcpyAsync(d_corpus, corpus, n_bytes, hipMemcpyHostToDevice, s));
-  HIPCHK(ac, hipMemcpyAsync(d_off, piece_offsets, (D + 1) * 8, hipMemcpyHostToDevice, s));
-  if (D) HIPCHK(ac, hipMemcpyAsync(d_ids, seq_ids, D * 4, hipMemcpyHostToDevice, s));
+  if (key_counts && !d_kc) return no_memory("staging buffers");
   // running totals: the caller's vector goes up first and comes back only from a call that succeeded
   if (d_kc && (flags & AHA_COUNT_ACCUMULATE) && kc_bytes)
     HIPCHK(ac, hipMemcpyAsync(d_kc, key_counts, kc_bytes, hipMemcpyHostToDevice, s));
-  FeedArgs F{};
-  F.text = d_corpus;
-  F.off = d_off;
-  F.ids = d_ids;
-  F.D = D;
-  F.n_bytes = n_bytes;
-  F.pho = d_pho;
-  F.bases = d_bases;
+  FeedArgs F = feed_args(B.corpus, B.off, B.ids, D, B.n_bytes, B.pho, B.bases);
   F.key_counts = d_kc;
   F.accumulate = (flags & AHA_COUNT_ACCUMULATE) ? 1u : 0u;
   uint64_t total = 0;
   *n_hits = 0;
-  if ((rc = feed_count(f, lease.get(), F, s, &total))) return rc;
-  if (d_kc && kc_bytes) HIPCHK(ac, hipMemcpyAsync(key_counts, d_kc, kc_bytes, hipMemcpyDeviceToHost, s));
-  if (piece_hit_offsets) HIPCHK(ac, hipMemcpyAsync(piece_hit_offsets, d_pho, (D + 1) * 8, hipMemcpyDeviceToHost, s));
-  if (piece_bases && D) HIPCHK(ac, hipMemcpyAsync(piece_bases, d_bases, D * 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(ac, hipStreamSynchronize(s));
+  if ((rc = feed_count(f, call->sc(), F, s, &total))) return rc;
+  if ((rc = fetch(f, {{key_counts, d_kc, kc_bytes}, {piece_hit_offsets, B.pho, (D + 1) * 8}, {piece_bases, B.bases, D * 8}}))) return rc;
   *n_hits = total;
   return AHA_OK;
 }
@@ -1432,27 +1559,15 @@ int32_t aha_feed_cover_batch_device(aha_feed *f, const uint8_t *d_corpus, const 
                                     uint32_t *d_mask, uint8_t *d_redacted, uint8_t fill, uint32_t *d_piece_back,
                                     uint64_t *d_piece_covered, uint64_t *d_piece_hit_offsets, uint64_t *d_piece_bases,
                                     uint64_t *n_covered, uint64_t *n_hits, void *stream) {
-  if (!f || !n_covered || !d_piece_offsets || (n_pieces && !d_seq_ids) || (n_bytes && !d_corpus) || flags) return AHA_E_INVALID;
-  if (bad_feed(f)) return AHA_E_NO_DEVICE;
-  if (f->sep) return sep_refused("cover");
-  if (f->longest) return longest_refused("cover");
-  std::lock_guard<std::mutex> lk(f->mu);
-  DeviceGuard g(f->ac->device);
-  Lease lease(f->ac);
-  FeedArgs F{};
-  F.text = d_corpus;
-  F.off = d_piece_offsets;
-  F.ids = d_seq_ids;
-  F.D = n_pieces;
-  F.n_bytes = n_bytes;
-  F.pho = d_piece_hit_offsets;
-  F.bases = d_piece_bases;
+  int32_t rc = feed_cover_args(f, d_piece_offsets, d_seq_ids, n_pieces, flags, n_covered, n_bytes && !d_corpus);
+  if (rc) return rc;
+  FeedCall call(f);
+  FeedArgs F = feed_args(d_corpus, d_piece_offsets, d_seq_ids, n_pieces, n_bytes, d_piece_hit_offsets, d_piece_bases);
   F.back = d_piece_back;
   uint64_t total = 0, covered = 0;
   *n_covered = 0;
   if (n_hits) *n_hits = 0;
-  int32_t rc = feed_cover(f, lease.get(), F, (hipStream_t)stream, d_mask, d_redacted, fill, d_piece_covered, &total, &covered);
-  if (rc) return rc;
+  if ((rc = feed_cover(f, call.sc(), F, (hipStream_t)stream, d_mask, d_redacted, fill, d_piece_covered, &total, &covered))) return rc;
   *n_covered = covered;
   if (n_hits) *n_hits = total;
   return AHA_OK;
@@ -1464,52 +1579,22 @@ int32_t aha_feed_cover_batch(aha_feed *f, const uint8_t *corpus, const uint64_t 
                              uint64_t n_pieces, uint32_t flags, uint32_t *mask, uint8_t *redacted, uint8_t fill,
                              uint32_t *piece_back, uint64_t *piece_covered, uint64_t *piece_hit_offsets, uint64_t *piece_bases,
                              uint64_t *n_covered, uint64_t *n_hits) {
-  if (!f || !n_covered || !piece_offsets || (n_pieces && !seq_ids) || flags) return AHA_E_INVALID;
-  if (bad_feed(f)) return AHA_E_NO_DEVICE;
-  if (f->sep) return sep_refused("cover");
-  if (f->longest) return longest_refused("cover");
-  aha_ac *ac = f->ac;
-  int32_t rc = check_pieces_host(f, piece_offsets, seq_ids, n_pieces);
+  int32_t rc = feed_cover_args(f, piece_offsets, seq_ids, n_pieces, flags, n_covered, false);
   if (rc) return rc;
-  const uint64_t n_bytes = piece_offsets[n_pieces], n_words = (n_bytes + 31) / 32;
-  if (n_bytes && !corpus) return AHA_E_INVALID;
-  std::lock_guard<std::mutex> lk(f->mu);
-  DeviceGuard g(ac->device);
-  Lease lease(ac);
-  hipStream_t s = f->hs;
-  const uint64_t D = n_pieces;
-  uint8_t *d_corpus = (uint8_t *)reserve(f, kHCorpus, n_bytes + 64);
-  uint64_t *d_off = (uint64_t *)reserve(f, kHOff, (D + 1) * 8);
-  uint32_t *d_ids = (uint32_t *)reserve(f, kHIds, D * 4);
-  uint64_t *d_pho = (uint64_t *)reserve(f, kHPho, (D + 1) * 8);
-  uint64_t *d_bases = (uint64_t *)reserve(f, kHBases, D * 8);
-  uint32_t *d_back = piece_back ? (uint32_t *)reserve(f, kHBack, D * 4) : nullptr;
-  uint64_t *d_cov = piece_covered ? (uint64_t *)reserve(f, kHCov, D * 8) : nullptr;
-  if (!d_corpus || !d_off || !d_ids || !d_pho || !d_bases || (piece_back && !d_back) || (piece_covered && !d_cov))
-    return no_memory("staging buffers");
-  if (n_bytes) HIPCHK(ac, hipMemcpyAsync(d_corpus, corpus, n_bytes, hipMemcpyHostToDevice, s));
-  HIPCHK(ac, hipMemcpyAsync(d_off, piece_offsets, (D + 1) * 8, hipMemcpyHostToDevice, s));
-  if (D) HIPCHK(ac, hipMemcpyAsync(d_ids, seq_ids, D * 4, hipMemcpyHostToDevice, s));
-  FeedArgs F{};
-  F.text = d_corpus;
-  F.off = d_off;
-  F.ids = d_ids;
-  F.D = D;
-  F.n_bytes = n_bytes;
-  F.pho = d_pho;
-  F.bases = d_bases;
-  F.back = d_back;
+  std::optional<FeedCall> call;
+  Staged B;
+  const unsigned want = (piece_back ? kWantBack : 0) | (piece_covered ? kWantCov : 0);
+  if ((rc = stage_pieces(f, call, corpus, piece_offsets, seq_ids, n_pieces, {want}, B))) return rc;
+  const uint64_t D = n_pieces, n_bytes = B.n_bytes, n_words = (n_bytes + 31) / 32;
+  FeedArgs F = feed_args(B.corpus, B.off, B.ids, D, n_bytes, B.pho, B.bases);
+  F.back = B.back;
   uint64_t total = 0, covered = 0;
   *n_covered = 0;
   if (n_hits) *n_hits = 0;
-  if ((rc = feed_cover(f, lease.get(), F, s, nullptr, redacted ? d_corpus : nullptr, fill, d_cov, &total, &covered))) return rc;
-  if (mask && n_words) HIPCHK(ac, hipMemcpyAsync(mask, F.mask, n_words * 4, hipMemcpyDeviceToHost, s));
-  if (redacted && n_bytes) HIPCHK(ac, hipMemcpyAsync(redacted, d_corpus, n_bytes, hipMemcpyDeviceToHost, s));
-  if (piece_back && D) HIPCHK(ac, hipMemcpyAsync(piece_back, d_back, D * 4, hipMemcpyDeviceToHost, s));
-  if (piece_covered && D) HIPCHK(ac, hipMemcpyAsync(piece_covered, d_cov, D * 8, hipMemcpyDeviceToHost, s));
-  if (piece_hit_offsets) HIPCHK(ac, hipMemcpyAsync(piece_hit_offsets, d_pho, (D + 1) * 8, hipMemcpyDeviceToHost, s));
-  if (piece_bases && D) HIPCHK(ac, hipMemcpyAsync(piece_bases, d_bases, D * 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(ac, hipStreamSynchronize(s));
+  if ((rc = feed_cover(f, call->sc(), F, f->hs, nullptr, redacted ? B.corpus : nullptr, fill, B.cov, &total, &covered))) return rc;
+  if ((rc = fetch(f, {{mask, F.mask, n_words * 4}, {redacted, B.corpus, n_bytes}, {piece_back, B.back, D * 4},
+                      {piece_covered, B.cov, D * 8}, {piece_hit_offsets, B.pho, (D + 1) * 8}, {piece_bases, B.bases, D * 8}})))
+    return rc;
   *n_covered = covered;
   if (n_hits) *n_hits = total;
   return AHA_OK;
@@ -1519,106 +1604,38 @@ int32_t aha_feed_select_batch_device(aha_feed *f, const uint8_t *d_corpus, const
                                      const uint32_t *d_seq_ids, uint64_t n_pieces, uint64_t n_bytes, uint32_t flags,
                                      aha_hit *d_out, uint64_t cap, uint64_t *d_piece_sel_offsets, uint64_t *d_piece_bases,
                                      uint32_t *d_piece_hold, uint64_t *n_selected, uint64_t *n_hits, void *stream) {
-  if (!f || !n_selected || !d_piece_offsets || (n_pieces && !d_seq_ids) || (cap && !d_out) || (n_bytes && !d_corpus) ||
-      (flags & ~AHA_FEED_SELECT_FINAL))
-    return AHA_E_INVALID;
-  if (bad_feed(f)) return AHA_E_NO_DEVICE;
-  if (f->chars) {
-    tls_err = "feed select: a char feed (AHA_FEED_CHARS); select is in bytes";
-    return AHA_E_INVALID;
-  }
-  if (f->sep) return sep_refused("select");
-  if (f->longest) return longest_refused("select");
-  std::lock_guard<std::mutex> lk(f->mu);
-  DeviceGuard g(f->ac->device);
-  Lease lease(f->ac);
-  FeedArgs F{};
-  F.text = d_corpus;
-  F.off = d_piece_offsets;
-  F.ids = d_seq_ids;
-  F.D = n_pieces;
-  F.n_bytes = n_bytes;
-  F.bases = d_piece_bases;
+  int32_t rc = feed_select_args(f, d_piece_offsets, d_seq_ids, n_pieces, flags, d_out, cap, n_selected, n_bytes && !d_corpus);
+  if (rc) return rc;
+  FeedCall call(f);
+  FeedArgs F = feed_args(d_corpus, d_piece_offsets, d_seq_ids, n_pieces, n_bytes, nullptr, d_piece_bases);
   *n_selected = 0;
   if (n_hits) *n_hits = 0;
-  return feed_select(f, lease.get(), F, flags, d_out, cap, d_piece_sel_offsets, d_piece_hold, (hipStream_t)stream, n_selected, n_hits);
+  return feed_select(f, call.sc(), F, flags, d_out, cap, d_piece_sel_offsets, d_piece_hold, (hipStream_t)stream, n_selected, n_hits);
 }
 
 int32_t aha_feed_select_batch(aha_feed *f, const uint8_t *corpus, const uint64_t *piece_offsets, const uint32_t *seq_ids,
                               uint64_t n_pieces, uint32_t flags, aha_hit *out, uint64_t cap, uint64_t *piece_sel_offsets,
                               uint64_t *piece_bases, uint32_t *piece_hold, uint64_t *n_selected, uint64_t *n_hits) {
-  if (!f || !n_selected || !piece_offsets || (n_pieces && !seq_ids) || (cap && !out) || (flags & ~AHA_FEED_SELECT_FINAL))
-    return AHA_E_INVALID;
-  if (bad_feed(f)) return AHA_E_NO_DEVICE;
-  if (f->chars) {
-    tls_err = "feed select: a char feed (AHA_FEED_CHARS); select is in bytes";
-    return AHA_E_INVALID;
-  }
-  if (f->sep) return sep_refused("select");
-  if (f->longest) return longest_refused("select");
-  aha_ac *ac = f->ac;
-  int32_t rc = check_pieces_host(f, piece_offsets, seq_ids, n_pieces);
+  int32_t rc = feed_select_args(f, piece_offsets, seq_ids, n_pieces, flags, out, cap, n_selected, false);
   if (rc) return rc;
-  const uint64_t n_bytes = piece_offsets[n_pieces];
-  if (n_bytes && !corpus) return AHA_E_INVALID;
-  std::lock_guard<std::mutex> lk(f->mu);
-  DeviceGuard g(ac->device);
-  Lease lease(ac);
-  hipStream_t s = f->hs;
+  std::optional<FeedCall> call;
+  Staged B;
+  if ((rc = stage_pieces(f, call, corpus, piece_offsets, seq_ids, n_pieces, {kWantHold}, B))) return rc;
   const uint64_t D = n_pieces;
-  uint8_t *d_corpus = (uint8_t *)reserve(f, kHCorpus, n_bytes + 64);
-  uint64_t *d_off = (uint64_t *)reserve(f, kHOff, (D + 1) * 8);
-  uint32_t *d_ids = (uint32_t *)reserve(f, kHIds, D * 4);
-  uint64_t *d_pso = (uint64_t *)reserve(f, kHPho, (D + 1) * 8);
-  uint64_t *d_bases = (uint64_t *)reserve(f, kHBases, D * 8);
-  uint32_t *d_hold = (uint32_t *)reserve(f, kHHold, D * 4);
   // (the selection is at most the caller's cap, and at most one hit per extended position)
-  aha_hit *d_out = (aha_hit *)reserve(f, kHOut, std::min<uint64_t>(cap, n_bytes + D * f->W) * sizeof(aha_hit));
-  if (!d_corpus || !d_off || !d_ids || !d_pso || !d_bases || !d_hold || !d_out) return no_memory("staging buffers");
-  if (n_bytes) HIPCHK(ac, hipMemcpyAsync(d_corpus, corpus, n_bytes, hipMemcpyHostToDevice, s));
-  HIPCHK(ac, hipMemcpyAsync(d_off, piece_offsets, (D + 1) * 8, hipMemcpyHostToDevice, s));
-  if (D) HIPCHK(ac, hipMemcpyAsync(d_ids, seq_ids, D * 4, hipMemcpyHostToDevice, s));
-  FeedArgs F{};
-  F.text = d_corpus;
-  F.off = d_off;
-  F.ids = d_ids;
-  F.D = D;
-  F.n_bytes = n_bytes;
-  F.bases = d_bases;
+  aha_hit *d_out = (aha_hit *)reserve(f, kHOut, std::min<uint64_t>(cap, B.n_bytes + D * f->W) * sizeof(aha_hit));
+  if (!d_out) return no_memory("staging buffers");
+  FeedArgs F = feed_args(B.corpus, B.off, B.ids, D, B.n_bytes, nullptr, B.bases);
   *n_selected = 0;
   if (n_hits) *n_hits = 0;
   uint64_t total = 0;
-  rc = feed_select(f, lease.get(), F, flags, d_out, cap, d_pso, d_hold, s, &total, n_hits);
+  rc = feed_select(f, call->sc(), F, flags, d_out, cap, B.pho, B.hold, f->hs, &total, n_hits);
   if (rc == AHA_E_CAPACITY) *n_selected = total;
   if (rc) return rc;
-  if (total) HIPCHK(ac, hipMemcpyAsync(out, d_out, total * sizeof(aha_hit), hipMemcpyDeviceToHost, s));
-  if (piece_sel_offsets) HIPCHK(ac, hipMemcpyAsync(piece_sel_offsets, d_pso, (D + 1) * 8, hipMemcpyDeviceToHost, s));
-  if (piece_bases && D) HIPCHK(ac, hipMemcpyAsync(piece_bases, d_bases, D * 8, hipMemcpyDeviceToHost, s));
-  if (piece_hold && D) HIPCHK(ac, hipMemcpyAsync(piece_hold, d_hold, D * 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(ac, hipStreamSynchronize(s));
+  if ((rc = fetch(f, {{out, d_out, total * sizeof(aha_hit)}, {piece_sel_offsets, B.pho, (D + 1) * 8}, {piece_bases, B.bases, D * 8},
+                      {piece_hold, B.hold, D * 4}})))
+    return rc;
   *n_selected = total;
-  return AHA_OK;
-}
-
-// the argument checks both replace entries share, before any device work
-static int32_t feed_replace_args(const aha_feed *f, const aha_repl *table, const uint64_t *piece_offsets, const uint32_t *seq_ids,
-                                 uint64_t n_pieces, uint32_t flags, const uint8_t *out, uint64_t cap_bytes,
-                                 const uint64_t *n_out_bytes) {
-  if (!f || !table || !n_out_bytes || !piece_offsets || (n_pieces && !seq_ids) || (cap_bytes && !out) ||
-      (flags & ~AHA_FEED_REPLACE_FINAL))
-    return AHA_E_INVALID;
-  if (bad_feed(f)) return AHA_E_NO_DEVICE;
-  if (table->owner != f->ac->serial) {
-    tls_err = "the replacement table was made for another handle";
-    return AHA_E_INVALID;
-  }
-  if (f->chars) {
-    tls_err = "feed replace: a char feed (AHA_FEED_CHARS); replace is in bytes";
-    return AHA_E_INVALID;
-  }
-  if (f->sep) return sep_refused("replace");
-  if (f->longest) return longest_refused("replace");
-  if (!table->d_ent) return no_device();
   return AHA_OK;
 }
 
@@ -1630,27 +1647,13 @@ int32_t aha_feed_replace_batch_device(aha_feed *f, const aha_repl *table, const 
   int32_t rc = feed_replace_args(f, table, d_piece_offsets, d_seq_ids, n_pieces, flags, d_out, cap_bytes, n_out_bytes);
   if (rc) return rc;
   if (n_bytes && !d_corpus) return AHA_E_INVALID;
-  if (cap_bytes && n_bytes) {
-    const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), c0 = reinterpret_cast<uintptr_t>(d_corpus);
-    if (o0 < c0 + n_bytes && c0 < o0 + cap_bytes) {
-      tls_err = "feed replace calls have no in-place form: out overlaps the corpus";
-      return AHA_E_INVALID;
-    }
-  }
-  std::lock_guard<std::mutex> lk(f->mu);
-  DeviceGuard g(f->ac->device);
-  Lease lease(f->ac);
-  FeedArgs F{};
-  F.text = d_corpus;
-  F.off = d_piece_offsets;
-  F.ids = d_seq_ids;
-  F.D = n_pieces;
-  F.n_bytes = n_bytes;
-  F.bases = d_piece_bases;
+  if ((rc = overlap_refused("replace", d_corpus, n_bytes, d_out, cap_bytes))) return rc;
+  FeedCall call(f);
+  FeedArgs F = feed_args(d_corpus, d_piece_offsets, d_seq_ids, n_pieces, n_bytes, nullptr, d_piece_bases);
   *n_out_bytes = 0;
   if (n_selected) *n_selected = 0;
   if (n_hits) *n_hits = 0;
-  return feed_replace(f, lease.get(), table, F, flags, d_out, -1, cap_bytes, d_piece_out_offsets, d_piece_hold, (hipStream_t)stream,
+  return feed_replace(f, call.sc(), table, F, flags, d_out, -1, cap_bytes, d_piece_out_offsets, d_piece_hold, (hipStream_t)stream,
                       n_out_bytes, n_selected, n_hits);
 }
 
@@ -1662,77 +1665,24 @@ int32_t aha_feed_replace_batch(aha_feed *f, const aha_repl *table, const uint8_t
                                uint64_t *n_selected, uint64_t *n_hits) {
   int32_t rc = feed_replace_args(f, table, piece_offsets, seq_ids, n_pieces, flags, out, cap_bytes, n_out_bytes);
   if (rc) return rc;
-  aha_ac *ac = f->ac;
-  if ((rc = check_pieces_host(f, piece_offsets, seq_ids, n_pieces))) return rc;
-  const uint64_t n_bytes = piece_offsets[n_pieces];
-  if (n_bytes && !corpus) return AHA_E_INVALID;
-  std::lock_guard<std::mutex> lk(f->mu);
-  DeviceGuard g(ac->device);
-  Lease lease(ac);
-  hipStream_t s = f->hs;
+  std::optional<FeedCall> call;
+  Staged B;
+  if ((rc = stage_pieces(f, call, corpus, piece_offsets, seq_ids, n_pieces, {kWantHold}, B))) return rc;
   const uint64_t D = n_pieces;
-  uint8_t *d_corpus = (uint8_t *)reserve(f, kHCorpus, n_bytes + 64);
-  uint64_t *d_off = (uint64_t *)reserve(f, kHOff, (D + 1) * 8);
-  uint32_t *d_ids = (uint32_t *)reserve(f, kHIds, D * 4);
-  uint64_t *d_poo = (uint64_t *)reserve(f, kHPho, (D + 1) * 8);
-  uint64_t *d_bases = (uint64_t *)reserve(f, kHBases, D * 8);
-  uint32_t *d_hold = (uint32_t *)reserve(f, kHHold, D * 4);
-  if (!d_corpus || !d_off || !d_ids || !d_poo || !d_bases || !d_hold) return no_memory("staging buffers");
-  if (n_bytes) HIPCHK(ac, hipMemcpyAsync(d_corpus, corpus, n_bytes, hipMemcpyHostToDevice, s));
-  HIPCHK(ac, hipMemcpyAsync(d_off, piece_offsets, (D + 1) * 8, hipMemcpyHostToDevice, s));
-  if (D) HIPCHK(ac, hipMemcpyAsync(d_ids, seq_ids, D * 4, hipMemcpyHostToDevice, s));
-  FeedArgs F{};
-  F.text = d_corpus;
-  F.off = d_off;
-  F.ids = d_ids;
-  F.D = D;
-  F.n_bytes = n_bytes;
-  F.bases = d_bases;
+  FeedArgs F = feed_args(B.corpus, B.off, B.ids, D, B.n_bytes, nullptr, B.bases);
   *n_out_bytes = 0;
   if (n_selected) *n_selected = 0;
   if (n_hits) *n_hits = 0;
   uint64_t nb = 0, ns = 0, nh = 0;
-  rc = feed_replace(f, lease.get(), table, F, flags, nullptr, kHOut, cap_bytes, d_poo, d_hold, s, &nb, &ns, &nh);
+  rc = feed_replace(f, call->sc(), table, F, flags, nullptr, kHOut, cap_bytes, B.pho, B.hold, f->hs, &nb, &ns, &nh);
   if (rc == AHA_OK || rc == AHA_E_CAPACITY) {  // (the required size and the counts, as the device entry gives them)
     *n_out_bytes = nb;
     if (n_selected) *n_selected = ns;
     if (n_hits) *n_hits = nh;
   }
   if (rc) return rc;
-  if (nb) HIPCHK(ac, hipMemcpyAsync(out, f->buf[kHOut].p, nb, hipMemcpyDeviceToHost, s));
-  if (piece_out_offsets) HIPCHK(ac, hipMemcpyAsync(piece_out_offsets, d_poo, (D + 1) * 8, hipMemcpyDeviceToHost, s));
-  if (piece_bases && D) HIPCHK(ac, hipMemcpyAsync(piece_bases, d_bases, D * 8, hipMemcpyDeviceToHost, s));
-  if (piece_hold && D) HIPCHK(ac, hipMemcpyAsync(piece_hold, d_hold, D * 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(ac, hipStreamSynchronize(s));
-  return AHA_OK;
-}
-
-// the argument checks both grep entries share, before any device work
-static int32_t feed_grep_args(const aha_feed *f, const uint64_t *piece_offsets, const uint32_t *seq_ids, uint64_t n_pieces, uint32_t flags,
-                              const uint64_t *kept_recs, const uint64_t *rec_out_offsets, uint64_t cap_recs, const uint8_t *out,
-                              uint64_t cap_bytes, const uint64_t *n_kept) {
-  if (!f || !n_kept || !piece_offsets || (n_pieces && !seq_ids) || (flags & ~(AHA_GREP_INVERT | AHA_FEED_GREP_FINAL)))
-    return AHA_E_INVALID;
-  if ((cap_recs && !kept_recs && !rec_out_offsets) || (cap_bytes && !out)) return AHA_E_INVALID;
-  if (bad_feed(f)) return AHA_E_NO_DEVICE;
-  if (f->chars) {
-    tls_err = "feed grep: a char feed (AHA_FEED_CHARS); grep is in bytes";
-    return AHA_E_INVALID;
-  }
-  if (f->sep) return sep_refused("grep");
-  if (f->longest) return longest_refused("grep");
-  return AHA_OK;
-}
-
-static int32_t feed_grep_overlap(const uint8_t *corpus, uint64_t n_bytes, const uint8_t *out, uint64_t cap_bytes) {
-  if (cap_bytes && n_bytes && corpus) {
-    const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), c0 = reinterpret_cast<uintptr_t>(corpus);
-    if (o0 < c0 + n_bytes && c0 < o0 + cap_bytes) {
-      tls_err = "feed grep calls have no in-place form: out overlaps the corpus";
-      return AHA_E_INVALID;
-    }
-  }
-  return AHA_OK;
+  return fetch(f, {{out, f->buf[kHOut].p, nb}, {piece_out_offsets, B.pho, (D + 1) * 8}, {piece_bases, B.bases, D * 8},
+                   {piece_hold, B.hold, D * 4}});
 }
 
 int32_t aha_feed_grep_batch_device(aha_feed *f, const uint8_t *d_corpus, const uint64_t *d_piece_offsets, const uint32_t *d_seq_ids,
@@ -1745,17 +1695,9 @@ int32_t aha_feed_grep_batch_device(aha_feed *f, const uint8_t *d_corpus, const u
                               n_kept);
   if (rc) return rc;
   if (n_bytes && !d_corpus) return AHA_E_INVALID;
-  if ((rc = feed_grep_overlap(d_corpus, n_bytes, d_out, cap_bytes))) return rc;
-  std::lock_guard<std::mutex> lk(f->mu);
-  DeviceGuard g(f->ac->device);
-  Lease lease(f->ac);
-  FeedArgs F{};
-  F.text = d_corpus;
-  F.off = d_piece_offsets;
-  F.ids = d_seq_ids;
-  F.D = n_pieces;
-  F.n_bytes = n_bytes;
-  F.bases = d_piece_bases;
+  if ((rc = overlap_refused("grep", d_corpus, n_bytes, d_out, cap_bytes))) return rc;
+  FeedCall call(f);
+  FeedArgs F = feed_args(d_corpus, d_piece_offsets, d_seq_ids, n_pieces, n_bytes, nullptr, d_piece_bases);
   GrepOut O;
   O.kept = d_kept_recs;
   O.rec_out = d_rec_out_offsets;
@@ -1771,7 +1713,7 @@ int32_t aha_feed_grep_batch_device(aha_feed *f, const uint8_t *d_corpus, const u
   *n_kept = 0;
   if (n_out_bytes) *n_out_bytes = 0;
   if (n_hits) *n_hits = 0;
-  return feed_grep(f, lease.get(), F, delim, flags, O, (hipStream_t)stream, n_recs, n_kept, n_out_bytes, n_hits);
+  return feed_grep(f, call.sc(), F, delim, flags, O, (hipStream_t)stream, n_recs, n_kept, n_out_bytes, n_hits);
 }
 
 // The host entry: the pieces go up into the feed's staging buffers; the kept fragments, their offsets and their bytes, sized
@@ -1783,53 +1725,28 @@ int32_t aha_feed_grep_batch(aha_feed *f, const uint8_t *corpus, const uint64_t *
                             uint64_t *piece_rec_bases, uint64_t *n_recs, uint64_t *n_kept, uint64_t *n_out_bytes, uint64_t *n_hits) {
   int32_t rc = feed_grep_args(f, piece_offsets, seq_ids, n_pieces, flags, kept_recs, rec_out_offsets, cap_recs, out, cap_bytes, n_kept);
   if (rc) return rc;
-  aha_ac *ac = f->ac;
-  if ((rc = check_pieces_host(f, piece_offsets, seq_ids, n_pieces))) return rc;
-  const uint64_t n_bytes = piece_offsets[n_pieces];
-  if (n_bytes && !corpus) return AHA_E_INVALID;
-  if ((rc = feed_grep_overlap(corpus, n_bytes, out, cap_bytes))) return rc;
-  std::lock_guard<std::mutex> lk(f->mu);
-  DeviceGuard g(ac->device);
-  Lease lease(ac);
-  hipStream_t s = f->hs;
+  std::optional<FeedCall> call;
+  Staged B;
+  if ((rc = stage_pieces(f, call, corpus, piece_offsets, seq_ids, n_pieces, {kWantHold | kWantGrep, out, cap_bytes}, B))) return rc;
   const uint64_t D = n_pieces;
-  uint8_t *d_corpus = (uint8_t *)reserve(f, kHCorpus, n_bytes + 64);
-  uint64_t *d_off = (uint64_t *)reserve(f, kHOff, (D + 1) * 8);
-  uint32_t *d_ids = (uint32_t *)reserve(f, kHIds, D * 4);
-  uint64_t *d_bases = (uint64_t *)reserve(f, kHBases, D * 8);
-  uint32_t *d_hold = (uint32_t *)reserve(f, kHHold, D * 4);
-  uint64_t *d_pro = (uint64_t *)reserve(f, kHPieceRec, (D + 1) * 8);
-  uint64_t *d_pko = (uint64_t *)reserve(f, kHPieceKept, (D + 1) * 8);
-  uint64_t *d_head = (uint64_t *)reserve(f, kHHead, D * 8);
-  uint64_t *d_rb = (uint64_t *)reserve(f, kHRecBases, D * 8);
-  if (!d_corpus || !d_off || !d_ids || !d_bases || !d_hold || !d_pro || !d_pko || !d_head || !d_rb) return no_memory("staging buffers");
-  if (n_bytes) HIPCHK(ac, hipMemcpyAsync(d_corpus, corpus, n_bytes, hipMemcpyHostToDevice, s));
-  HIPCHK(ac, hipMemcpyAsync(d_off, piece_offsets, (D + 1) * 8, hipMemcpyHostToDevice, s));
-  if (D) HIPCHK(ac, hipMemcpyAsync(d_ids, seq_ids, D * 4, hipMemcpyHostToDevice, s));
-  FeedArgs F{};
-  F.text = d_corpus;
-  F.off = d_off;
-  F.ids = d_ids;
-  F.D = D;
-  F.n_bytes = n_bytes;
-  F.bases = d_bases;
+  FeedArgs F = feed_args(B.corpus, B.off, B.ids, D, B.n_bytes, nullptr, B.bases);
   GrepOut O;
   if (kept_recs) O.kept_slot = kHKept;
   if (rec_out_offsets) O.rec_out_slot = kHRecOut;
   if (out) O.out_slot = kHOut;
   O.cap_recs = cap_recs;
   O.cap_bytes = cap_bytes;
-  O.piece_rec = d_pro;
-  O.piece_kept = d_pko;
-  O.hold = d_hold;
-  O.head = d_head;
-  O.rec_bases = d_rb;
+  O.piece_rec = B.piece_rec;
+  O.piece_kept = B.piece_kept;
+  O.hold = B.hold;
+  O.head = B.head;
+  O.rec_bases = B.rec_bases;
   if (n_recs) *n_recs = 0;
   *n_kept = 0;
   if (n_out_bytes) *n_out_bytes = 0;
   if (n_hits) *n_hits = 0;
   uint64_t nr = 0, nk = 0, nb = 0, nh = 0;
-  rc = feed_grep(f, lease.get(), F, delim, flags, O, s, &nr, &nk, &nb, &nh);
+  rc = feed_grep(f, call->sc(), F, delim, flags, O, f->hs, &nr, &nk, &nb, &nh);
   if (rc == AHA_OK || rc == AHA_E_CAPACITY) {  // (both required numbers and the counts, as the device entry gives them)
     if (n_recs) *n_recs = nr;
     *n_kept = nk;
@@ -1837,15 +1754,9 @@ int32_t aha_feed_grep_batch(aha_feed *f, const uint8_t *corpus, const uint64_t *
     if (n_hits) *n_hits = nh;
   }
   if (rc) return rc;
-  if (kept_recs && nk) HIPCHK(ac, hipMemcpyAsync(kept_recs, O.kept, nk * 8, hipMemcpyDeviceToHost, s));
-  if (rec_out_offsets) HIPCHK(ac, hipMemcpyAsync(rec_out_offsets, O.rec_out, (nk + 1) * 8, hipMemcpyDeviceToHost, s));
-  if (out && nb) HIPCHK(ac, hipMemcpyAsync(out, O.out, nb, hipMemcpyDeviceToHost, s));
-  if (piece_rec_offsets) HIPCHK(ac, hipMemcpyAsync(piece_rec_offsets, d_pro, (D + 1) * 8, hipMemcpyDeviceToHost, s));
-  if (piece_kept_offsets) HIPCHK(ac, hipMemcpyAsync(piece_kept_offsets, d_pko, (D + 1) * 8, hipMemcpyDeviceToHost, s));
-  if (piece_hold && D) HIPCHK(ac, hipMemcpyAsync(piece_hold, d_hold, D * 4, hipMemcpyDeviceToHost, s));
-  if (piece_head && D) HIPCHK(ac, hipMemcpyAsync(piece_head, d_head, D * 8, hipMemcpyDeviceToHost, s));
-  if (piece_bases && D) HIPCHK(ac, hipMemcpyAsync(piece_bases, d_bases, D * 8, hipMemcpyDeviceToHost, s));
-  if (piece_rec_bases && D) HIPCHK(ac, hipMemcpyAsync(piece_rec_bases, d_rb, D * 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(ac, hipStreamSynchronize(s));
-  return AHA_OK;
+  return fetch(f, {{kept_recs, O.kept, nk * 8}, {rec_out_offsets, O.rec_out, (nk + 1) * 8}, {out, O.out, nb},
+                   {piece_rec_offsets, B.piece_rec, (D + 1) * 8}, {piece_kept_offsets, B.piece_kept, (D + 1) * 8},
+                   {piece_hold, B.hold, D * 4}, {piece_head, B.head, D * 8}, {piece_bases, B.bases, D * 8},
+                   {piece_rec_bases, B.rec_bases, D * 8}});
 }
+
