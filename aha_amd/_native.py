@@ -36,6 +36,7 @@ AHA_OPT_FOLD_KANA = 32
 AHA_COUNT_ACCUMULATE = 1
 AHA_GREP_INVERT = 1
 AHA_FEED_CHARS = 1
+AHA_FEED_FOLD = 4
 AHA_FEED_SELECT_FINAL = 1
 AHA_FEED_REPLACE_FINAL = AHA_FEED_SELECT_FINAL
 AHA_FEED_GREP_FINAL = 2

@@ -1345,21 +1345,27 @@ class AC:
         return buf
 
     # -- feeds: sequences that arrive in pieces (aha_feed_*) -----------------------------------------
-    def feed(self, n_seqs, chars=False, sep=None, longest=0):
+    def feed(self, n_seqs, chars=False, sep=None, longest=0, fold=False):
         """n_seqs open sequences matched piece by piece (aha_feed_open): see Feed.  chars: offsets and bases in characters.
         sep: a BitArray -- the feed's match and count calls apply the separator filter of match(seq, sep) to the whole sequence
         (aha_feed_open_params): a hit is reported one byte late, and Feed.finish ends a sequence.
         longest: 1 or 2 -- a longest feed: its match calls report what match_longest(seq, intersectable = False | True) of the
         whole sequence yields, each hit in the call that holds the byte at which it is yielded, and Feed.finish reports the hit
         that is still pending and ends the sequence.  Refused (AHA_E_INVALID): longest with sep or chars, and count, cover,
-        select, replace and grep calls on such a feed.  A handle compiled with fold_simple, fold_bmp or fold_kana has no feeds
-        yet: the library's AHA_E_INVALID is raised."""
+        select, replace and grep calls on such a feed.
+        fold: on a handle compiled with fold_simple, fold_bmp or fold_kana a FOLDED feed (AHA_FEED_FOLD; without it such a handle
+        has no feeds: the library's AHA_E_INVALID is raised): every call answers as if the sequence ended with its piece -- a
+        character cut between two calls is folded whole, one still open at a call's end is matched unfolded, so for keys that
+        are whole characters the hits are those of the whole sequence folded as one document.  match, count and cover calls
+        (redactor included: the original bytes outside hits); select, replace and grep calls, sep and longest are refused.  On any
+        other handle fold changes nothing."""
         h = C.c_void_p()
+        flags = (N.AHA_FEED_CHARS if chars else 0) | (N.AHA_FEED_FOLD if fold else 0)
         if sep is None and not longest:
-            rc = N.lib().aha_feed_open(self._h, int(n_seqs), N.AHA_FEED_CHARS if chars else 0, C.byref(h))
+            rc = N.lib().aha_feed_open(self._h, int(n_seqs), flags, C.byref(h))
         else:
             p = _params(False, sep, longest)
-            rc = N.lib().aha_feed_open_params(self._h, int(n_seqs), N.AHA_FEED_CHARS if chars else 0, C.byref(p), C.byref(h))
+            rc = N.lib().aha_feed_open_params(self._h, int(n_seqs), flags, C.byref(p), C.byref(h))
         self._check(rc)
         return Feed(self, h, int(n_seqs), chars, sep, int(longest))
 

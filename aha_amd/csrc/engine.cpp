@@ -300,11 +300,15 @@ static int32_t stage_folded(aha_ac *ac, Scratch *sc, MatchArgs &M, hipStream_t s
 // larger buffer) is copied once into scratch, folded on the way on a folded handle; an aligned text stays the caller's, and on
 // a folded handle M.fold says so: the prefix-filter engine reads it where it lies, the others stage it (stage_folded).
 // (M.doc_off and M.n_docs are the batch's by now: the simple fold goes document by document)
-static int32_t take_text(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, uint64_t n_bytes, MatchArgs &M, hipStream_t s) {
+// as_is: the text is already as the engines take it -- a folded feed's pieces and windows (feed.cpp), folded by the feed with
+// its sequences' contexts in view: M.fold stays 0 and only an unaligned view is copied.  Folding folded text again would change
+// no byte (F, F3 and FK are idempotent and fragments pass through): the switch saves a staged pass, it corrects nothing.
+static int32_t take_text(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, uint64_t n_bytes, MatchArgs &M, hipStream_t s,
+                         bool as_is = false) {
   M.text = d_corpus;
-  if (reinterpret_cast<uintptr_t>(d_corpus) % 16 != 0)
-    return stage_batch(ac, sc, &M.text, n_bytes, ac->fold_mode(), M.doc_off, M.n_docs, s);
-  M.fold = ac->fold_mode();
+  const int fold = as_is ? 0 : ac->fold_mode();
+  if (reinterpret_cast<uintptr_t>(d_corpus) % 16 != 0) return stage_batch(ac, sc, &M.text, n_bytes, fold, M.doc_off, M.n_docs, s);
+  M.fold = fold;
   return AHA_OK;
 }
 // The two-pass engine's chunk: `chunk0`, doubled until the warm-up (a multiple of Lmax - 1 bytes) is a small fraction of it --
@@ -744,7 +748,8 @@ static int32_t check_docs_now(aha_ac *ac, Scratch *sc, const uint64_t *d_doc_off
 
 int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
                      uint64_t n_bytes, const aha_match_params *params, aha_hit *d_out, uint64_t cap, uint64_t *d_doc_hit_offsets,
-                     uint64_t *n_hits, void *stream, bool offsets_checked, const PackOut *pk, bool *packed, bool quiet, bool neutral) {
+                     uint64_t *n_hits, void *stream, bool offsets_checked, const PackOut *pk, bool *packed, bool quiet, bool neutral,
+                     bool as_is) {
   if (!ac || !n_hits || !d_doc_offsets) return AHA_E_INVALID;
   if (ac->device < 0) return no_device();
   if (cap && !d_out) return AHA_E_INVALID;
@@ -782,7 +787,7 @@ int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
   M.out = d_out;
   M.cap = cap;
   M.doc_hit_off = d_doc_hit_offsets;
-  if ((rc = take_text(ac, sc, d_corpus, n_bytes, M, s))) return rc;
+  if ((rc = take_text(ac, sc, d_corpus, n_bytes, M, s, as_is))) return rc;
   if (longest) {
     if ((rc = stage_folded(ac, sc, M, s))) return rc;
     d_corpus = M.text;
@@ -1120,7 +1125,8 @@ int32_t device_feed_longest_write(aha_ac *ac, const FeedArgs &F, const FeedLongA
 // engine's give-ups) is read, never written: the next match call behaves as if this call had not happened.
 int32_t device_count(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
                      uint64_t n_bytes, const aha_match_params *params, uint32_t flags, uint64_t *d_key_counts,
-                     uint64_t *d_doc_hit_offsets, uint64_t *n_hits, void *stream, bool offsets_checked, uint32_t *cover_mask) {
+                     uint64_t *d_doc_hit_offsets, uint64_t *n_hits, void *stream, bool offsets_checked, uint32_t *cover_mask,
+                     bool as_is) {
   if (!ac || !n_hits || !d_doc_offsets) return AHA_E_INVALID;
   if (ac->device < 0) return no_device();
   if (flags & ~AHA_COUNT_ACCUMULATE) return AHA_E_INVALID;
@@ -1154,7 +1160,7 @@ int32_t device_count(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
   M.doc_off = d_doc_offsets;
   M.n_docs = n_docs;
   M.n_bytes = n_bytes;
-  if ((rc = take_text(ac, sc, d_corpus, n_bytes, M, s))) return rc;
+  if ((rc = take_text(ac, sc, d_corpus, n_bytes, M, s, as_is))) return rc;
   M.out = nullptr;
   M.cap = 0;
   M.doc_hit_off = d_doc_hit_offsets;

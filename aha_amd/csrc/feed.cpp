@@ -58,6 +58,13 @@
 //                          block scan (one read-back: the total) -- above cap -> AHA_E_CAPACITY, nothing committed
 //   device_feed_longest_write, kfl_commit   pass 2: the hits and piece_hit_offsets; then bases, lengths and the carried states
 // and aha_feed_finish_batch* reports the named sequences' pending hits (kfl_finish: counted, then written) and restarts them.
+// A folded feed (AHA_FEED_FOLD on a handle folded beyond ASCII; scan_feedfold.hip, DESIGN.md 4.13 "Feeds on handles folded beyond
+// ASCII") keeps W = Lmax + 1 ORIGINAL bytes of context and answers every call as if the sequence ended with its piece.  Its
+// match, count and cover calls are the plain feed's with the first three steps folded (feed_windows):
+//   the staged copy + kff_heads   the pieces folded once into the feed's scratch, every piece on its own, then the first two bytes
+//                          of each from ctx || P
+//   kff_windows            the window batch cut from fold(ctx || P), in kfd_windows' place
+//   device_match / device_count, as_is   both matches read text that is folded already; everything behind them is unchanged
 // Calls on one feed are serialised by its mutex; its scratch is its own.  The two matches lease one of the handle's scratch
 // sets like any call, so different feeds and plain calls on the same handle run side by side.
 // Every public batch entry has one shape: its family's argument checks (feed_*_args: the refusals both entries share), one call
@@ -104,6 +111,7 @@ enum FeedSlot {
   kHPieceKept,  // piece_kept_offsets
   kHHead,       // piece_head
   kHRecBases,   // piece_rec_bases
+  kFold,        // a folded feed: the pieces as the engines take them (FeedArgs::ftext)
   kFeedSlots
 };
 }  // namespace
@@ -111,11 +119,13 @@ enum FeedSlot {
 struct aha_feed {
   aha_ac *ac = nullptr;
   uint32_t n_seqs = 0;
-  uint32_t W = 0;  // bytes of context per sequence: max(Lmax - 1, 0), or Lmax + 1 with a separator filter
+  uint32_t W = 0;  // bytes of context per sequence: max(Lmax - 1, 0), or Lmax + 1 with a separator filter or on a folded feed
   bool chars = false;
   bool sep = false;         // opened with a separator filter: W = Lmax + 1, match and count calls report a hit one byte late
   uint32_t blocked[8] = {};  // bit c: byte c does not pass (c < sep_size && !sep[c])
   int longest = 0;          // opened with longest = 1 | 2: match_longest, intersectable = false | true; no context is kept
+  int fold = 0;             // opened with AHA_FEED_FOLD on a handle folded beyond ASCII: its fold mode (2, 3, 4), W = Lmax + 1, and
+                            // every call answers as if the sequence ended with its piece (scan_feedfold.hip); else 0
   FeedLongSeq *d_long = nullptr;  // ... its carried states, allocated at open (16 bytes per sequence)
   std::mutex mu;
   FeedSeq *d_seqs = nullptr;
@@ -204,7 +214,25 @@ int32_t feed_windows(aha_feed *f, Scratch *sc, FeedArgs &F, hipStream_t s, bool 
   F.win = (uint8_t *)reserve(f, kWin, n_win + 64);
   if (!F.win) return no_memory("windows");
   if (F.chars && D) HIPCHK(ac, hipMemsetAsync(F.lead_p, 0, D * 8, s));
-  feed_launch_windows(F, s);
+  if (f->fold) {
+    // a folded feed: the pieces folded once into the feed's scratch -- every piece on its own (consecutive pieces belong to
+    // different sequences, so the copies' fix-up at the boundaries is always wanted), then the first two bytes of each with the
+    // sequence's context in view -- and the windows cut from the fold of ctx || P; both matches read them as they are
+    F.ftext = (uint8_t *)reserve(f, kFold, F.n_bytes + 64);
+    if (!F.ftext) return no_memory("folded pieces");
+    const uint32_t max_blocks = 8u * std::max<uint32_t>(ac->v2_grid, 64u);
+    if (f->fold == 4)
+      foldk_launch_copy(F.text, F.ftext, F.n_bytes, F.off, D, max_blocks, s);
+    else if (f->fold == 3)
+      fold3_launch_copy(F.text, F.ftext, F.n_bytes, F.off, D, max_blocks, s);
+    else
+      fold2_launch_copy(F.text, F.ftext, F.n_bytes, F.off, D, max_blocks, s);
+    feedfold_launch_heads(F, f->fold, s);
+    feedfold_launch_windows(F, f->fold, s);
+    feed_launch_leads(F, s);
+  } else {
+    feed_launch_windows(F, s);
+  }
   HIPCHK(ac, hipGetLastError());
 
   aha_match_params p{};
@@ -217,7 +245,7 @@ int32_t feed_windows(aha_feed *f, Scratch *sc, FeedArgs &F, hipStream_t s, bool 
     for (int attempt = 0;; attempt++) {
       const uint64_t cap_w = f->buf[kWhits].bytes / sizeof(aha_hit);
       int32_t rc = device_match(ac, sc, F.win, F.woff, 3 * D, n_win, &p, cap_w ? (aha_hit *)f->buf[kWhits].p : nullptr, cap_w,
-                                wdho, n_w, s, true, nullptr, &packed, true);
+                                wdho, n_w, s, true, nullptr, &packed, true, false, f->fold != 0);
       if (rc == AHA_E_CAPACITY && attempt == 0) {
         if (!reserve(f, kWhits, std::max<uint64_t>(*n_w, 1024) * sizeof(aha_hit))) return no_memory("window hits");
         continue;
@@ -227,7 +255,7 @@ int32_t feed_windows(aha_feed *f, Scratch *sc, FeedArgs &F, hipStream_t s, bool 
     }
   } else {
     // (a count call never writes the handle's back-off state, so it needs no quiet form)
-    int32_t rc = device_count(ac, sc, F.win, F.woff, 3 * D, n_win, &p, 0, nullptr, wdho, n_w, s, true);
+    int32_t rc = device_count(ac, sc, F.win, F.woff, 3 * D, n_win, &p, 0, nullptr, wdho, n_w, s, true, nullptr, f->fold != 0);
     if (rc) return rc;
   }
   F.whits = (const int32_t *)f->buf[kWhits].p;
@@ -242,6 +270,10 @@ int32_t feed_windows(aha_feed *f, Scratch *sc, FeedArgs &F, hipStream_t s, bool 
   }
   return AHA_OK;
 }
+
+// the text of a call's main pass: the caller's pieces, or on a folded feed their folded copy (feed_windows made it), which the
+// engines then take as it is -- one staged pass per call, not two
+const uint8_t *main_text(const aha_feed *f, const FeedArgs &F) { return f->fold ? F.ftext : F.text; }
 
 // the part of a match call before anything is written for the caller: the windows, then the main pass.  *total = the call's
 // hits; AHA_E_CAPACITY when they are more than cap.
@@ -259,7 +291,8 @@ int32_t feed_prepare(aha_feed *f, Scratch *sc, FeedArgs &F, uint64_t cap, hipStr
   aha_hit *mh = cap_m ? (aha_hit *)reserve(f, kMhits, cap_m * sizeof(aha_hit)) : nullptr;
   if (cap_m && !mh) return no_memory("hits");
   uint64_t n_m = 0;
-  rc = device_match(ac, sc, F.text, F.off, F.D, F.n_bytes, &p, mh, cap_m, (uint64_t *)F.mdho, &n_m, s, true, nullptr, &packed);
+  rc = device_match(ac, sc, main_text(f, F), F.off, F.D, F.n_bytes, &p, mh, cap_m, (uint64_t *)F.mdho, &n_m, s, true, nullptr, &packed,
+                    false, false, f->fold != 0);
   if (rc && rc != AHA_E_CAPACITY) return rc;
   F.mhits = (const int32_t *)mh;
   *total = (nx - ny) + (n_m - nz);
@@ -290,7 +323,8 @@ int32_t feed_count(aha_feed *f, Scratch *sc, FeedArgs &F, hipStream_t s, uint64_
   aha_match_params p{};
   p.struct_size = sizeof(p);
   uint64_t n_m = 0;
-  rc = device_count(ac, sc, F.text, F.off, F.D, F.n_bytes, &p, 0, (uint64_t *)F.kc, (uint64_t *)F.mdho, &n_m, s, true);
+  rc = device_count(ac, sc, main_text(f, F), F.off, F.D, F.n_bytes, &p, 0, (uint64_t *)F.kc, (uint64_t *)F.mdho, &n_m, s, true, nullptr,
+                    f->fold != 0);
   if (rc) return rc;
   *total = (nx - ny) + (n_m - nz);
   F.total = *total;
@@ -319,7 +353,8 @@ int32_t feed_cover(aha_feed *f, Scratch *sc, FeedArgs &F, hipStream_t s, uint32_
   aha_match_params p{};
   p.struct_size = sizeof(p);
   uint64_t n_m = 0;
-  rc = device_count(ac, sc, F.text, F.off, F.D, F.n_bytes, &p, 0, nullptr, (uint64_t *)F.mdho, &n_m, s, true, F.mask);
+  rc = device_count(ac, sc, main_text(f, F), F.off, F.D, F.n_bytes, &p, 0, nullptr, (uint64_t *)F.mdho, &n_m, s, true, F.mask,
+                    f->fold != 0);
   if (rc) return rc;
   *total = (nx - ny) + (n_m - nz);
   F.total = *total;
@@ -1244,6 +1279,12 @@ int32_t bytes_only_refused(const aha_feed *f, const char *what) {
   }
   if (f->sep) return sep_refused(what);
   if (f->longest) return longest_refused(what);
+  if (f->fold) {
+    tls_err = std::string("feed ") + what + ": the feed was opened with AHA_FEED_FOLD on a handle folded beyond ASCII, which feed " + what +
+              " calls do not take yet (a follow-up: what they keep between calls is derived from hits, and a hit that ends in a "
+              "character still open is decided on its unfolded byte); feed match, count and cover calls do";
+    return AHA_E_INVALID;
+  }
   return AHA_OK;
 }
 
@@ -1298,7 +1339,7 @@ int32_t aha_feed_open(aha_ac *ac, uint32_t n_seqs, uint32_t flags, aha_feed **ou
 }
 
 int32_t aha_feed_open_params(aha_ac *ac, uint32_t n_seqs, uint32_t flags, const aha_match_params *params, aha_feed **out) {
-  if (!ac || !out || n_seqs == 0 || (flags & ~AHA_FEED_CHARS)) return AHA_E_INVALID;
+  if (!ac || !out || n_seqs == 0 || (flags & ~(AHA_FEED_CHARS | AHA_FEED_FOLD))) return AHA_E_INVALID;
   *out = nullptr;
   const bool sep = params && params->sep_size > 0;
   int longest = 0;
@@ -1334,13 +1375,21 @@ int32_t aha_feed_open_params(aha_ac *ac, uint32_t n_seqs, uint32_t flags, const 
       return AHA_E_INVALID;
     }
   }
-  if (const int mode = ac->fold_mode(); mode >= 2 && mode <= 4) {  // (before any device work, host-only handles included)
+  // AHA_FEED_FOLD on a handle folded beyond ASCII: a folded feed.  On any other handle the flag changes nothing.
+  const int fold = (flags & AHA_FEED_FOLD) && ac->fold_mode() >= 2 ? ac->fold_mode() : 0;
+  if (fold && (sep || longest)) {  // (before any device work, host-only handles included)
+    tls_err = std::string("aha_feed_open_params: AHA_FEED_FOLD on a handle folded beyond ASCII takes neither ") +
+              (sep ? "a separator filter" : "longest != 0") + " yet (a follow-up)";
+    return AHA_E_INVALID;
+  }
+  if (const int mode = ac->fold_mode(); !fold && mode >= 2 && mode <= 4) {  // (before any device work, host-only handles included)
     const char *option = mode == 2 ? "SIMPLE" : mode == 3 ? "BMP" : "KANA";
     tls_err = std::string("aha_feed_open: no feed on a handle compiled with AHA_OPT_FOLD_") + option + " yet: a " +
               (mode == 2 ? "two-byte" : "two- or three-byte") +
               " character may be cut between two calls, and the context a feed keeps would have to carry " +
               (mode == 2 ? "half" : "part") +
-              " of it (a follow-up; fold the pieces' sequences whole, or use AHA_OPT_FOLD_ASCII)";
+              " of it (a follow-up; fold the pieces' sequences whole, or use AHA_OPT_FOLD_ASCII); AHA_FEED_FOLD opens a feed that does, "
+              "with Lmax + 1 bytes of context and a character still open at a call's end matched unfolded";
     return AHA_E_INVALID;
   }
   if (ac->device < 0) {
@@ -1359,6 +1408,11 @@ int32_t aha_feed_open_params(aha_ac *ac, uint32_t n_seqs, uint32_t flags, const 
     f->W = ac->aut.max_key_len + 1;
     for (int c = 0; c < params->sep_size; c++)
       if (!((params->sep_bits[c >> 3] >> (c & 7)) & 1)) f->blocked[c >> 5] |= 1u << (c & 31);
+  }
+  if (fold) {  // the first two bytes of a window may be folded differently from the sequence's: a hit that touches them must end
+               // inside the context, so Lmax + 1 bytes -- what a feed with a separator filter keeps (scan_feedfold.hip)
+    f->fold = fold;
+    f->W = ac->aut.max_key_len + 1;
   }
   f->longest = longest;
   // (a longest feed carries its state in d_long and never reads a context)

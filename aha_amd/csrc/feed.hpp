@@ -1,5 +1,5 @@
 // feed.hpp -- what feed.cpp (the feed entry points of the C ABI) and its kernels (scan_feed.hip, scan_feedselect.hip,
-// scan_feedreplace.hip, scan_feedsep.hip, scan_feedgrep.hip, scan_feedlongest.hip) share.  Library-internal.
+// scan_feedreplace.hip, scan_feedsep.hip, scan_feedgrep.hip, scan_feedlongest.hip, scan_feedfold.hip) share.  Library-internal.
 #pragma once
 #include <cstdint>
 
@@ -46,7 +46,7 @@ struct FeedArgs {
   const uint64_t *off;         // [D+1] piece offsets
   const uint32_t *ids;         // [D] sequence ids
   uint64_t D, n_bytes, n_seqs;
-  uint32_t W;                  // max(Lmax - 1, 0); Lmax + 1 on a feed with a separator filter
+  uint32_t W;                  // max(Lmax - 1, 0); Lmax + 1 on a feed with a separator filter and on a folded feed (AHA_FEED_FOLD)
   uint32_t Wp;                 // bytes of the piece in the head windows X and P': W, or 2 W for a cover call
   uint32_t stamp;              // this call's stamp (never 0)
   uint64_t max_piece;          // a piece must be shorter than this
@@ -83,6 +83,10 @@ struct FeedArgs {
   uint64_t *edge;              // [D], or null (every call on a plain feed)
   // grep calls (aha_feed_grep_batch*): kfd_check refuses a sequence whose bytes did not all go through grep calls
   const FeedGrepSeq *grep;     // [n_seqs], or null (every other call); verdict bit 3
+  // calls on a folded feed (AHA_FEED_FOLD on a handle folded beyond ASCII; scan_feedfold.hip): the pieces as the engines take
+  // them, every piece folded as the end of its sequence.  `text` stays the caller's: the new contexts, leads(P) and a cover
+  // call's redaction read it
+  uint8_t *ftext;              // [n_bytes] in the feed's scratch, or null (every call on another feed)
 };
 
 // what the kernels of a grep call take beside FeedArgs (scan_feedgrep.hip).  The pieces are split into R fragments as a records
@@ -172,6 +176,11 @@ __device__ inline uint64_t feedsel_cursor(uint64_t cursor, uint64_t n0, uint64_t
 void feed_launch_check(const FeedArgs &F, void *stream);    // kfd_check, then kfd_scan of the window lengths
 void feed_launch_check_only(const FeedArgs &F, void *stream);  // kfd_check alone (a grep call lays out windows of its own)
 void feed_launch_windows(const FeedArgs &F, void *stream);  // kfd_windows (+ kfd_leads on char feeds)
+void feed_launch_leads(const FeedArgs &F, void *stream);    // kfd_leads alone, on char feeds (a folded feed cuts its own windows)
+// a folded feed (scan_feedfold.hip; mode: the handle's fold, 2 simple, 3 BMP, 4 kana): kff_heads -- the first two bytes of every
+// piece of F.ftext, behind the staged copy's fix-up -- and kff_windows in kfd_windows' place
+void feedfold_launch_heads(const FeedArgs &F, int mode, void *stream);
+void feedfold_launch_windows(const FeedArgs &F, int mode, void *stream);
 void feed_launch_merge(const FeedArgs &F, void *stream);    // kfd_scan of the hits per piece, kfd_merge
 void feed_launch_commit(const FeedArgs &F, void *stream);   // kfd_commit: bases, counters, the new contexts
 // a feed with a separator filter: kfd_edge (F.edge) and kfd_scan of the true hits per piece into F.pho; then, with F.total read

@@ -516,14 +516,17 @@ struct PackOut {
 // neutral: every engine, but the back-off state is only read (the match inside a document-count call).
 // quiet: neither the prefix-filter nor the pair engine, so the handle's back-off state is neither read nor written (a feed's
 // window batch, feed.cpp: an internal batch must not change which engine the caller's next call takes)
+// as_is: the text is already as the engines take it -- folded by a folded feed (feed.cpp, scan_feedfold.hip) -- so a folded
+// handle's staged pass is left out; only an unaligned view is still copied.  No other caller passes it.
 int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
                      uint64_t n_bytes, const aha_match_params *params, aha_hit *d_out, uint64_t cap, uint64_t *d_doc_hit_offsets,
                      uint64_t *n_hits, void *stream, bool offsets_checked, const PackOut *pk, bool *packed, bool quiet = false,
-                     bool neutral = false);
+                     bool neutral = false, bool as_is = false);
 // one device-resident batch counted (aha_ac_count_batch_device): the match's engine, the count passes instead of the expansion
 int32_t device_count(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
                      uint64_t n_bytes, const aha_match_params *params, uint32_t flags, uint64_t *d_key_counts,
-                     uint64_t *d_doc_hit_offsets, uint64_t *n_hits, void *stream, bool offsets_checked, uint32_t *cover_mask = nullptr);
+                     uint64_t *d_doc_hit_offsets, uint64_t *n_hits, void *stream, bool offsets_checked, uint32_t *cover_mask = nullptr,
+                     bool as_is = false);
 // one device-resident batch as {key, count} pairs per document (aha_ac_doc_counts_batch_device): a count call for the hits per
 // document, the match into scratch, the per-document reduction (scan_doccount.hip)
 int32_t device_doc_counts(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,

@@ -411,7 +411,12 @@ void feed_launch_check_only(const FeedArgs &F, void *stream) {
 void feed_launch_windows(const FeedArgs &F, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(kfd_windows, dim3(grid_for(F.D, 1, 4096)), dim3(kFdThreads), 0, s, F);
-  if (F.chars && F.n_bytes) hipLaunchKernelGGL(kfd_leads, dim3(grid_for(F.n_bytes, kFdSpan, 4096)), dim3(kFdThreads), 0, s, F);
+  feed_launch_leads(F, stream);
+}
+
+void feed_launch_leads(const FeedArgs &F, void *stream) {
+  if (F.chars && F.n_bytes)
+    hipLaunchKernelGGL(kfd_leads, dim3(grid_for(F.n_bytes, kFdSpan, 4096)), dim3(kFdThreads), 0, (hipStream_t)stream, F);
 }
 
 void feed_launch_merge(const FeedArgs &F, void *stream) {

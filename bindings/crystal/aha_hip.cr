@@ -248,6 +248,9 @@ lib LibAhaHip
   # feeds: sequences that arrive in pieces across calls (offsets relative to the piece; FEED_CHARS: in characters)
   type Feed = Void*
   FEED_CHARS = 1_u32
+  # on a handle folded beyond ASCII (FOLD_SIMPLE, _BMP, _KANA): a folded feed -- every call answers as if the sequence ended with
+  # its piece, Lmax + 1 bytes of context; match, count and cover calls (aha_hip.h AHA_FEED_FOLD)
+  FEED_FOLD  = 4_u32
   fun aha_feed_open(ac : Ac, n_seqs : UInt32, flags : UInt32, out : Feed*) : Int32
   # a feed with a separator filter: match and count calls report a hit one byte late, finish ends a sequence
   fun aha_feed_open_params(ac : Ac, n_seqs : UInt32, flags : UInt32, params : MatchParams*, out : Feed*) : Int32
@@ -785,9 +788,10 @@ module Aha
   # hand when it was written; tests/test_feed_host.py checks that the lib block binds every entry point.)  Hit holds Int32
   # offsets: past 2^31 bytes of a sequence use aha_feed_match_batch, whose offsets are relative to the piece.
   class Feed
-    def initialize(ac : AC, n_seqs : Int, chars : Bool = false)
+    def initialize(ac : AC, n_seqs : Int, chars : Bool = false, fold : Bool = false)
       @ac = ac
-      rc = LibAhaHip.aha_feed_open(ac.handle, n_seqs.to_u32, chars ? LibAhaHip::FEED_CHARS : 0_u32, out h)
+      flags = (chars ? LibAhaHip::FEED_CHARS : 0_u32) | (fold ? LibAhaHip::FEED_FOLD : 0_u32)
+      rc = LibAhaHip.aha_feed_open(ac.handle, n_seqs.to_u32, flags, out h)
       raise String.new(LibAhaHip.aha_strerror(rc)) if rc != 0
       @handle = h
     end

@@ -650,9 +650,17 @@ using ACBig = AC;
 // feed before its AC.
 class Feed {
  public:
-  Feed(const AC &ac, uint32_t n_seqs, bool chars = false) : ac_(ac.handle()) {
-    const int32_t rc = aha_feed_open(ac_, n_seqs, chars ? AHA_FEED_CHARS : 0u, &f_);
-    if (rc != AHA_OK) throw Error(rc, aha_strerror(rc));
+  // fold: on an AC compiled with a fold beyond ASCII (simple, BMP, kana) a FOLDED feed (kFeedFold = AHA_FEED_FOLD) -- every call
+  // answers as if the sequence ended with its piece: a character cut between two calls is folded whole, one still open at a call's
+  // end is matched unfolded; match, count and cover calls (select, replace and grep calls throw).  Without it such an AC has no
+  // feeds; on any other AC it changes nothing
+  static constexpr uint32_t kFeedFold = AHA_FEED_FOLD;
+  Feed(const AC &ac, uint32_t n_seqs, bool chars = false, bool fold = false) : ac_(ac.handle()) {
+    const int32_t rc = aha_feed_open(ac_, n_seqs, (chars ? AHA_FEED_CHARS : 0u) | (fold ? kFeedFold : 0u), &f_);
+    if (rc != AHA_OK) {
+      const char *m = aha_last_error(ac_);
+      throw Error(rc, (m && *m) ? m : aha_strerror(rc));
+    }
   }
   // a feed whose match and count calls apply the separator filter of match(seq, sep) to the whole sequence
   // (aha_feed_open_params): a call reports the surviving hits that end before the piece's last byte -- one that ended with the

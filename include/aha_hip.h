@@ -517,7 +517,26 @@ int32_t aha_ac_count_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uin
  * handle's scratch set for the two matches; the host entry stages the corpus and the hits on the device as well. */
 typedef struct aha_feed aha_feed;
 #define AHA_FEED_CHARS 1u /* offsets and bases in characters (the lead-byte rule) instead of bytes */
-/* AHA_E_NO_DEVICE on a host-only handle; AHA_E_INVALID for NULL arguments, n_seqs = 0 or unknown flags. */
+/* A FOLDED FEED: AHA_FEED_FOLD on a handle compiled with AHA_OPT_FOLD_SIMPLE, _BMP or _KANA (without the flag such a handle has
+ * no feeds: AHA_E_INVALID; on any other handle the flag changes nothing).  Let fold be the handle's fold of ONE document -- a
+ * truncated character at its end passes through.  A call that takes a sequence S from n0 to n1 bytes reports exactly the hits
+ * with n0 < end <= n1 of fold(S[0 .. n1)) matched as one document by a plain handle of the folded keys: every call answers as if
+ * the sequence ended with its piece.  A character cut between two calls is folded whole and hits that run through it are found;
+ * a character still open at the end of a call is not folded yet, and only a hit that ENDS on one of its bytes is decided on the
+ * unfolded byte (the feed's form of "a character cut by a document boundary is not folded").  Such a hit needs a key that ends
+ * in a truncated UTF-8 sequence: for keys that are whole characters the feed is bit-exact with the batch call on the whole
+ * sequence as one document.  Offsets, bases, piece_hit_offsets, char offsets (AHA_FEED_CHARS), counts and cover masks follow
+ * from that hit list as on a plain feed.  Opt-in because the feed keeps W = Lmax + 1 bytes of context (ORIGINAL bytes) and has
+ * the open-character rule.  Calls: aha_feed_match_batch*, aha_feed_count_batch* and aha_feed_cover_batch* (the redacted copy
+ * keeps the caller's bytes outside hits); aha_feed_select_batch*, _replace_ and _grep_ answer AHA_E_INVALID and leave the feed
+ * as it was (follow-ups), aha_feed_finish_batch* as on every plain feed.  With a separator filter or longest != 0:
+ * AHA_E_INVALID before any device work (follow-ups).  Pipeline (aha_amd/csrc/scan_feedfold.hip; DESIGN.md 4.13 "Feeds on
+ * handles folded beyond ASCII"): per call the pieces are folded once into feed scratch (n_bytes + 64 bytes), the first two bytes
+ * of each with the sequence's context in view, the windows are cut from the fold of context || piece, and both matches read
+ * text that is already folded. */
+#define AHA_FEED_FOLD 4u /* (2u is refused: the value is not taken) */
+/* AHA_E_NO_DEVICE on a host-only handle; AHA_E_INVALID for NULL arguments, n_seqs = 0, unknown flags, or a handle folded
+ * beyond ASCII without AHA_FEED_FOLD. */
 int32_t aha_feed_open(aha_ac *ac, uint32_t n_seqs, uint32_t flags, aha_feed **out);
 /* Frees the feed (waits for a call in flight); before aha_ac_free of its handle. */
 void aha_feed_free(aha_feed *f);
@@ -619,7 +638,8 @@ int32_t aha_feed_count_batch_device(aha_feed *f, const uint8_t *d_corpus, const 
  * Refused, AHA_E_INVALID before any device work, nothing changed, each with its own aha_last_error text: longest outside 0..2;
  * longest != 0 with sep_size > 0, with char_offsets != 0, or with AHA_FEED_CHARS (a follow-up); aha_feed_count_batch*,
  * _cover_, _select_, _replace_ and _grep_ on a longest feed (follow-ups).  The argument checks come before the device check: a
- * host-only handle answers AHA_E_NO_DEVICE for longest = 1 | 2 with valid arguments.  Handles folded beyond ASCII stay refused.
+ * host-only handle answers AHA_E_NO_DEVICE for longest = 1 | 2 with valid arguments.  Handles folded beyond ASCII stay refused,
+ * with AHA_FEED_FOLD too.
  * Pipeline (aha_amd/csrc/feed.cpp, scan_feedlongest.hip; DESIGN.md 4.10 "Feed match_longest"): match_longest's state at a cut
  * depends on the whole sequence (intersectable = false resets it at every yield), so the feed carries it: 16 bytes per sequence
  * -- the automaton state, the pending end as a distance back from the sequence's end, its key, the last two bytes (all that the
