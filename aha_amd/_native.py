@@ -35,6 +35,10 @@ AHA_OPT_FOLD_BMP = 16
 AHA_OPT_FOLD_KANA = 32
 AHA_COUNT_ACCUMULATE = 1
 AHA_GREP_INVERT = 1
+AHA_GREP_RULE = 4
+AHA_RULE_GE = 0
+AHA_RULE_LT = 1
+AHA_RULE_MAX_TERMS = 64
 AHA_FEED_CHARS = 1
 AHA_FEED_FOLD = 4
 AHA_FEED_SELECT_FINAL = 1
@@ -54,6 +58,17 @@ class aha_options(C.Structure):
 class aha_match_params(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("char_offsets", C.c_int32), ("sep_size", C.c_int32),
                 ("sep_bits", C.c_uint8 * 32), ("longest", C.c_int32)]
+
+
+class aha_rule_term(C.Structure):
+    _fields_ = [("class_id", C.c_uint32), ("op", C.c_uint16), ("group", C.c_uint16), ("num", C.c_uint32),
+                ("den_bytes", C.c_uint32)]
+
+
+class aha_grep_params(C.Structure):
+    """AHA_GREP_RULE: what `params` of a grep call points to; match.struct_size = sizeof(aha_grep_params)"""
+    _fields_ = [("match", aha_match_params), ("classes", C.c_void_p), ("terms", C.POINTER(aha_rule_term)),
+                ("n_terms", C.c_uint32), ("reserved", C.c_uint32), ("rows", C.c_void_p)]
 
 
 class aha_ac_info_t(C.Structure):

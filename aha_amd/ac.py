@@ -189,6 +189,28 @@ class Classes:
                 pass
 
 
+class Rule:
+    """A rule over class counts for the grep calls (AHA_GREP_RULE), validated on the host and immutable.  Made by AC.rule.
+    classes: the Classes it names; terms: a tuple of (class_id, op, group, num, den_bytes) with op 0 for >= and 1 for <; a
+    document passes when some group has all its terms true."""
+
+    __slots__ = ("classes", "terms", "_arr")
+
+    def __init__(self, classes, terms):
+        object.__setattr__(self, "classes", classes)
+        object.__setattr__(self, "terms", tuple(terms))
+        arr = (N.aha_rule_term * len(self.terms))()
+        for i, (c, op, g, num, den) in enumerate(self.terms):
+            arr[i] = N.aha_rule_term(c, op, g, num, den)
+        object.__setattr__(self, "_arr", arr)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a Rule is immutable")
+
+    def __repr__(self):
+        return "Rule(%r)" % (self.terms,)
+
+
 def _pack_replacements(repl, n_keys):
     """repl as substitute takes it -> (blob uint8, offsets uint64[K+1], keep bits uint32[ceil(K/32)])"""
     parts, keep = [], np.zeros((n_keys + 31) // 32, dtype=np.uint32)
@@ -992,6 +1014,79 @@ class AC:
                                                              C.byref(p), 0, out.ptr, C.byref(nh), None))
         return out.download(np.zeros((D, C_), dtype=np.uint32)), int(nh.value)
 
+    # -- rule grep: keep documents by conditions on their class counts (aha_ac_grep_batch* with AHA_GREP_RULE) ----
+    def rule(self, spec, classes):
+        """A Rule over the class counts of `classes` (a Classes of this handle, or what AC.classes takes) from spec: a list
+        of groups, a group a list of terms (class, ">=" | "<", num) or (class, op, num, per_bytes); a class is its index, or
+        its name where the Classes has names.  (c, ">=", 3) is "at least 3 hits of class c"; (c, ">=", 3, 1000) is "at
+        least 3 hits of class c per 1000 bytes of the document".  A document passes when some group has all its terms
+        true.  1 to 64 terms in all; ValueError otherwise."""
+        table = self._classes(classes)
+        ops = {">=": N.AHA_RULE_GE, "<": N.AHA_RULE_LT}
+        terms = []
+        groups = list(spec)
+        for g, group in enumerate(groups):
+            if isinstance(group, tuple) or not hasattr(group, "__iter__") or isinstance(group, (str, bytes)):
+                raise ValueError("a rule is a list of groups, a group a list of terms")
+            group = list(group)
+            if not group:
+                raise ValueError("group %d of the rule has no term" % g)
+            for term in group:
+                if len(term) not in (3, 4):
+                    raise ValueError("a term is (class, op, num) or (class, op, num, per_bytes): %r" % (term,))
+                c, op, num = term[0], term[1], term[2]
+                den = term[3] if len(term) == 4 else 0
+                if op not in ops:
+                    raise ValueError("a term's op is '>=' or '<': %r" % (op,))
+                if isinstance(c, (int, np.integer)) and not isinstance(c, bool):
+                    c = int(c)
+                elif table.names is not None and c in table.names:
+                    c = table.names.index(c)
+                else:
+                    raise ValueError("the rule names class %r; the table has %s" % (c, table.names or "no names"))
+                if not 0 <= c < table.n_classes:
+                    raise ValueError("the rule names class %d; the table has %d classes" % (c, table.n_classes))
+                num, den = int(num), int(den)
+                if not (0 <= num < 1 << 32 and 0 <= den < 1 << 32):
+                    raise ValueError("num and per_bytes are 32-bit and not negative: %r" % (term,))
+                terms.append((c, ops[op], g, num, den))
+        if not 1 <= len(terms) <= N.AHA_RULE_MAX_TERMS:
+            raise ValueError("a rule has 1 to %d terms, this one %d" % (N.AHA_RULE_MAX_TERMS, len(terms)))
+        return Rule(table, terms)
+
+    def _grep_params(self, sep, invert, classes, rule, rows_ptr):
+        """-> (params pointer, flags, what must stay alive over the call, the Classes or None) of a grep call"""
+        flags = N.AHA_GREP_INVERT if invert else 0
+        if rule is None:
+            if classes is not None or rows_ptr is not None:
+                raise ValueError("classes and rows belong to a rule: give rule=")
+            p = _params(False, sep)
+            return C.pointer(p), flags, p, None
+        if not isinstance(rule, Rule):
+            if classes is None:
+                raise ValueError("a rule given as a spec needs classes=")
+            rule = self.rule(rule, classes)
+        elif classes is not None and classes is not rule.classes:
+            raise ValueError("the rule was made for another Classes")
+        gp = N.aha_grep_params()
+        gp.match = _params(False, sep)
+        gp.match.struct_size = C.sizeof(N.aha_grep_params)
+        gp.classes = rule.classes._h
+        gp.terms = C.cast(rule._arr, C.POINTER(N.aha_rule_term))
+        gp.n_terms = len(rule.terms)
+        gp.reserved = 0
+        gp.rows = rows_ptr
+        return C.cast(C.pointer(gp), C.POINTER(N.aha_match_params)), flags | N.AHA_GREP_RULE, (gp, rule), rule.classes
+
+    @staticmethod
+    def _host_rows(rows, D, table):
+        if rows is None:
+            return None
+        if not (isinstance(rows, np.ndarray) and rows.dtype == np.uint32 and rows.flags.c_contiguous and rows.flags.writeable
+                and rows.shape == (D, table.n_classes)):
+            raise ValueError("rows must be a contiguous uint32 array of shape (D, C) = (%d, %d)" % (D, table.n_classes))
+        return rows
+
     # -- records and grep: split a batch into records, keep those with a hit (aha_ac_records_batch*, aha_ac_grep_batch*) ----
     def records(self, corpus, doc_offsets=None, delim=b"\n"):
         """The batch split into records at the delimiter byte and at the documents' ends, on the device:
@@ -1056,36 +1151,46 @@ class AC:
         e.bytes_required = int(n_bytes.value)
         return e
 
-    def grep_batch(self, corpus, doc_offsets, sep=None, invert=False, text=True):
+    def grep_batch(self, corpus, doc_offsets, sep=None, invert=False, text=True, classes=None, rule=None, rows=None):
         """The documents with at least one hit of match_batch(corpus, doc_offsets, sep) -- invert: those without one --
         compacted on the device: -> (kept_docs uint64[n_kept], uint8 array, doc_out_offsets uint64[n_kept+1]); kept document
         i is document kept_docs[i] and its bytes are out[doc_out_offsets[i]:doc_out_offsets[i+1]].  text False: no bytes are
-        copied (an empty array comes back).  A sizing call first."""
+        copied (an empty array comes back).  A sizing call first.
+        rule (a Rule of AC.rule, or its spec with classes=): the documents whose class counts pass the rule instead -- invert:
+        those that do not; rows (a uint32 array of shape (D, C)) then receives class_counts_batch of the batch."""
         if isinstance(corpus, (bytes, bytearray)):
             corpus = np.frombuffer(bytes(corpus), dtype=np.uint8)
         corpus = np.ascontiguousarray(corpus, dtype=np.uint8)
         doc_offsets = np.ascontiguousarray(doc_offsets, dtype=np.uint64)
         D = doc_offsets.size - 1
-        p = _params(False, sep)
-        flags = N.AHA_GREP_INVERT if invert else 0
+        p, flags, _alive, table = self._grep_params(sep, invert, classes, rule, None)
+        if rows is not None:
+            if table is None:
+                raise ValueError("classes and rows belong to a rule: give rule=")
+            rows = self._host_rows(rows, D, table)
         nk, nb = C.c_uint64(0), C.c_uint64(0)
         L = N.lib()
-        self._check(L.aha_ac_grep_batch(self._h, _ptr(corpus), _ptr(doc_offsets), D, C.byref(p), flags, None, None, 0, None, 0,
+        self._check(L.aha_ac_grep_batch(self._h, _ptr(corpus), _ptr(doc_offsets), D, p, flags, None, None, 0, None, 0,
                                         C.byref(nk), C.byref(nb), None))
         cap_docs, cap_bytes = int(nk.value), int(nb.value) if text else 0
         kept = np.zeros(max(cap_docs, 1), dtype=np.uint64)
         doo = np.zeros(cap_docs + 1, dtype=np.uint64)
         out = np.zeros(max(cap_bytes, 1), dtype=np.uint8)
-        self._check(L.aha_ac_grep_batch(self._h, _ptr(corpus), _ptr(doc_offsets), D, C.byref(p), flags, _ptr(kept), _ptr(doo),
+        if rows is not None and rows.size:
+            _alive[0].rows = rows.ctypes.data
+        self._check(L.aha_ac_grep_batch(self._h, _ptr(corpus), _ptr(doc_offsets), D, p, flags, _ptr(kept), _ptr(doo),
                                         cap_docs, _ptr(out) if text else None, cap_bytes, C.byref(nk), C.byref(nb), None))
         return kept[: int(nk.value)], out[: int(nb.value) if text else 0], doo[: int(nk.value) + 1]
 
     def grep_batch_device(self, corpus, doc_offsets, kept_docs=None, doc_out_offsets=None, out=None, sep=None, invert=False,
-                          cap_docs=None, cap_bytes=None, stream=None):
+                          cap_docs=None, cap_bytes=None, stream=None, classes=None, rule=None, rows=None):
         """Device-resident grep on torch CUDA tensors: uint8 corpus, int64/uint64 doc offsets, kept_docs int64/uint64
         [cap_docs] or None, doc_out_offsets int64/uint64 [cap_docs + 1] or None, out uint8 [cap_bytes] (any alignment) or None
         (no bytes are copied).  -> (n_kept, n_out_bytes, n_hits); raises AhaError(AHA_E_CAPACITY) when a buffer is too small
-        (e.n_required = the documents needed, e.bytes_required = the bytes needed); nothing is written then."""
+        (e.n_required = the documents needed, e.bytes_required = the bytes needed); nothing is written then.
+        rule (a Rule of AC.rule, or its spec with classes=): the documents whose class counts pass the rule; rows: a
+        contiguous int32 CUDA tensor of shape (D, C) that receives the class counts (as uint32), as class_counts_batch_device
+        writes them."""
         import torch
 
         assert corpus.is_cuda and corpus.dtype == torch.uint8 and corpus.is_contiguous()
@@ -1108,11 +1213,18 @@ class AC:
         else:
             cap_bytes = 0
         D = doc_offsets.numel() - 1
-        p = _params(False, sep)
+        p, flags, _alive, table = self._grep_params(sep, invert, classes, rule, None)
+        if rows is not None:
+            if table is None:
+                raise ValueError("classes and rows belong to a rule: give rule=")
+            if not (rows.is_cuda and rows.dtype == torch.int32 and rows.is_contiguous() and tuple(rows.shape) == (D, table.n_classes)):
+                raise ValueError("rows must be a contiguous int32 CUDA tensor of shape (D, C) = (%d, %d)" % (D, table.n_classes))
+            if D:
+                _alive[0].rows = rows.data_ptr()
         nk, nb, nh = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         s = stream if stream is not None else torch.cuda.current_stream(corpus.device).cuda_stream
         rc = N.lib().aha_ac_grep_batch_device(
-            self._h, corpus.data_ptr(), doc_offsets.data_ptr(), D, corpus.numel(), C.byref(p), N.AHA_GREP_INVERT if invert else 0,
+            self._h, corpus.data_ptr(), doc_offsets.data_ptr(), D, corpus.numel(), p, flags,
             kept_docs.data_ptr() if kept_docs is not None else None,
             doc_out_offsets.data_ptr() if doc_out_offsets is not None else None, cap_docs,
             out.data_ptr() if out is not None else None, cap_bytes, C.byref(nk), C.byref(nb), C.byref(nh), C.c_void_p(s))
@@ -1121,34 +1233,44 @@ class AC:
         self._check(rc)
         return int(nk.value), int(nb.value), int(nh.value)
 
-    def grep_corpus(self, corpus, sep=None, invert=False, text=True):
+    def grep_corpus(self, corpus, sep=None, invert=False, text=True, classes=None, rule=None, rows=None):
         """grep_batch of a batch that already lives in HBM (DeviceCorpus), downloaded:
-        -> (kept_docs uint64[n_kept], uint8 array, doc_out_offsets uint64[n_kept+1], n_hits)."""
+        -> (kept_docs uint64[n_kept], uint8 array, doc_out_offsets uint64[n_kept+1], n_hits).  rule, classes, rows: as in
+        grep_batch (rows a uint32 array of shape (D, C), downloaded into)."""
         D = corpus.n_docs
-        p = _params(False, sep)
-        flags = N.AHA_GREP_INVERT if invert else 0
+        p, flags, _alive, table = self._grep_params(sep, invert, classes, rule, None)
+        if rows is not None:
+            if table is None:
+                raise ValueError("classes and rows belong to a rule: give rule=")
+            rows = self._host_rows(rows, D, table)
         dev = corpus.device
         nk, nb, nh = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         L = N.lib()
-        self._check(L.aha_ac_grep_batch_device(self._h, corpus.ptr, corpus.doc_ptr, D, corpus.n_bytes, C.byref(p), flags, None, None,
+        self._check(L.aha_ac_grep_batch_device(self._h, corpus.ptr, corpus.doc_ptr, D, corpus.n_bytes, p, flags, None, None,
                                                0, None, 0, C.byref(nk), C.byref(nb), C.byref(nh), None))
         cap_docs, cap_bytes = int(nk.value), int(nb.value) if text else 0
         kept, doo = DeviceBuffer(dev, max(cap_docs, 1) * 8), DeviceBuffer(dev, (cap_docs + 1) * 8)
         out = DeviceBuffer(dev, max(cap_bytes, 1)) if text else None
-        self._check(L.aha_ac_grep_batch_device(self._h, corpus.ptr, corpus.doc_ptr, D, corpus.n_bytes, C.byref(p), flags, kept.ptr,
+        d_rows = DeviceBuffer(dev, rows.size * 4) if rows is not None and rows.size else None
+        if d_rows is not None:
+            _alive[0].rows = d_rows.ptr
+        self._check(L.aha_ac_grep_batch_device(self._h, corpus.ptr, corpus.doc_ptr, D, corpus.n_bytes, p, flags, kept.ptr,
                                                doo.ptr, cap_docs, out.ptr if text else None, cap_bytes, C.byref(nk), C.byref(nb),
                                                C.byref(nh), None))
+        if d_rows is not None:
+            d_rows.download(rows)
         got = out.download(np.zeros(max(cap_bytes, 1), dtype=np.uint8))[:cap_bytes] if text else np.zeros(0, dtype=np.uint8)
         return (kept.download(np.zeros(max(cap_docs, 1), dtype=np.uint64))[:cap_docs], got,
                 doo.download(np.zeros(cap_docs + 1, dtype=np.uint64)), int(nh.value))
 
-    def grep(self, seq, delim="\n", invert=False, sep=None):
+    def grep(self, seq, delim="\n", invert=False, sep=None, classes=None, rule=None, rows=None):
         """The records of seq -- split at delim, each with its delimiter -- that have a hit of match(record, sep), as a
-        list; invert: those that have none.  bytes in, bytes out; str in, str out.  records plus grep_batch."""
+        list; invert: those that have none.  bytes in, bytes out; str in, str out.  records plus grep_batch.  rule, classes,
+        rows: as in grep_batch, over the records (rows has one row per record of AC.records(seq, None, delim))."""
         b = _b(seq)
         corpus = np.frombuffer(b, dtype=np.uint8)
         rec, _ = self.records(corpus, None, delim)
-        _, out, doo = self.grep_batch(corpus, rec, sep=sep, invert=invert)
+        _, out, doo = self.grep_batch(corpus, rec, sep=sep, invert=invert, classes=classes, rule=rule, rows=rows)
         raw = out.tobytes()
         parts = [raw[int(doo[i]):int(doo[i + 1])] for i in range(doo.size - 1)]
         return [x.decode("utf-8") for x in parts] if isinstance(seq, str) else parts

@@ -1762,12 +1762,34 @@ int32_t aha_ac_records_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *
   return AHA_OK;
 }
 
+// AHA_GREP_RULE: params is the first member of an aha_grep_params; its table, terms and sizes (before any device work)
+static int32_t grep_rule_args(aha_ac *ac, const aha_match_params *params) {
+  auto bad = [](const char *what) {
+    tls_err = what;
+    return AHA_E_INVALID;
+  };
+  if (!params || params->struct_size < sizeof(aha_grep_params))
+    return bad("AHA_GREP_RULE: params must point to an aha_grep_params with match.struct_size = sizeof(aha_grep_params)");
+  const aha_grep_params *gp = reinterpret_cast<const aha_grep_params *>(params);
+  if (!gp->classes) return bad("AHA_GREP_RULE: no class table");
+  if (gp->classes->owner != ac->serial) return bad("the class table was made for another handle");
+  if (!gp->terms || gp->n_terms == 0 || gp->n_terms > kRuleMaxTerms) return bad("AHA_GREP_RULE: a rule has 1 to 64 terms");
+  if (gp->reserved) return bad("AHA_GREP_RULE: reserved is 0");
+  for (uint32_t i = 0; i < gp->n_terms; i++) {
+    if (gp->terms[i].op > AHA_RULE_LT) return bad("AHA_GREP_RULE: a term's op is AHA_RULE_GE or AHA_RULE_LT");
+    if (gp->terms[i].class_id >= gp->classes->n_classes) return bad("AHA_GREP_RULE: a term names a class the table does not have");
+  }
+  return AHA_OK;
+}
+
 // the argument checks both grep entries share: before any device work, so they hold on a host-only handle.  out / corpus: the
 // two address ranges that must not overlap (there is no in-place form)
 static int32_t grep_args(aha_ac *ac, const uint8_t *corpus, uint64_t n_bytes, const uint64_t *doc_offsets, const aha_match_params *params,
                          uint32_t flags, const uint64_t *kept_docs, const uint64_t *doc_out_offsets, uint64_t cap_docs,
                          const uint8_t *out, uint64_t cap_bytes, uint64_t *n_kept) {
-  if (!ac || !n_kept || !doc_offsets || (flags & ~AHA_GREP_INVERT)) return AHA_E_INVALID;
+  if (!ac || !n_kept || !doc_offsets || (flags & ~(AHA_GREP_INVERT | AHA_GREP_RULE))) return AHA_E_INVALID;
+  if (flags & AHA_GREP_RULE)
+    if (int32_t rc = grep_rule_args(ac, params)) return rc;
   if (int32_t rc = no_longest_form(ac, params, "grep calls have no match_longest form")) return rc;
   if (params && params->struct_size >= offsetof(aha_match_params, char_offsets) + sizeof(params->char_offsets) && params->char_offsets) {
     tls_err = "grep calls take byte offsets only";
@@ -1793,6 +1815,14 @@ int32_t aha_ac_grep_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uint
                          n_kept);
   if (rc) return rc;
   Lease lease(ac);
+  if (flags & AHA_GREP_RULE) {
+    // the caller's rows take the table at once only where no capacity can fail the call behind it
+    const aha_grep_params *gp = reinterpret_cast<const aha_grep_params *>(params);
+    const bool per_doc = d_kept_docs || d_doc_out_offsets;
+    const bool rows_early = (!per_doc || cap_docs >= n_docs) && (!d_out || cap_bytes >= n_bytes);
+    return device_grep_rule(ac, lease.get(), d_corpus, d_doc_offsets, n_docs, n_bytes, gp, gp->rows, flags, d_kept_docs,
+                            d_doc_out_offsets, cap_docs, d_out, cap_bytes, n_kept, n_out_bytes, n_hits, stream, false, rows_early);
+  }
   return device_grep(ac, lease.get(), d_corpus, d_doc_offsets, n_docs, n_bytes, params, flags, d_kept_docs, d_doc_out_offsets, cap_docs,
                      d_out, cap_bytes, n_kept, n_out_bytes, n_hits, stream, false);
 }
@@ -1812,18 +1842,27 @@ int32_t aha_ac_grep_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc
   Lease lease(ac);
   Scratch *sc = lease.get();
   HostBatch B;
-  // per document: the kept documents' indices, cap_docs of them, then their offsets, cap_docs + 1
+  // per document: the kept documents' indices, cap_docs of them, then their offsets, cap_docs + 1; behind them the rows of a
+  // rule grep call whose caller wants them
   const bool per_doc = kept_docs || doc_out_offsets;
-  if ((rc = stage_host_batch(ac, sc, corpus, doc_offsets, n_docs, per_doc ? (2 * cap_docs + 1) * 8 : 0, out ? std::max<uint64_t>(cap_bytes, 1) : 0,
+  const aha_grep_params *gp = (flags & AHA_GREP_RULE) ? reinterpret_cast<const aha_grep_params *>(params) : nullptr;
+  const uint64_t per_doc_bytes = per_doc ? (2 * cap_docs + 1) * 8 : 0;
+  const uint64_t n_rows = gp && gp->rows ? n_docs * gp->classes->n_classes : 0;
+  if ((rc = stage_host_batch(ac, sc, corpus, doc_offsets, n_docs, per_doc_bytes + n_rows * 4, out ? std::max<uint64_t>(cap_bytes, 1) : 0,
                              B)))
     return rc;
+  uint32_t *d_rows = n_rows ? (uint32_t *)((uint8_t *)B.d_per_doc + per_doc_bytes) : nullptr;
   uint64_t *d_kept = kept_docs ? (uint64_t *)B.d_per_doc : nullptr;
   uint64_t *d_doo = doc_out_offsets ? (uint64_t *)B.d_per_doc + cap_docs : nullptr;
   uint8_t *d_out = (uint8_t *)B.d_per_call;
   hipStream_t s = B.s;
   uint64_t nk = 0, nb = 0, nh = 0;
-  rc = device_grep(ac, sc, B.d_corpus, B.d_doc, n_docs, n_bytes, params, flags, d_kept, d_doo, cap_docs, d_out, d_out ? cap_bytes : 0, &nk,
-                   &nb, &nh, s, true);  // the offsets were checked on the host above
+  if (gp)  // (d_rows is staging: the table may go there before the verdict)
+    rc = device_grep_rule(ac, sc, B.d_corpus, B.d_doc, n_docs, n_bytes, gp, d_rows, flags, d_kept, d_doo, cap_docs, d_out,
+                          d_out ? cap_bytes : 0, &nk, &nb, &nh, s, true, true);
+  else
+    rc = device_grep(ac, sc, B.d_corpus, B.d_doc, n_docs, n_bytes, params, flags, d_kept, d_doo, cap_docs, d_out, d_out ? cap_bytes : 0,
+                     &nk, &nb, &nh, s, true);  // the offsets were checked on the host above
   if (rc == AHA_E_CAPACITY) {  // (both required numbers and the count, as the device entry gives them)
     *n_kept = nk;
     if (n_out_bytes) *n_out_bytes = nb;
@@ -1833,6 +1872,7 @@ int32_t aha_ac_grep_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc
   if (kept_docs && nk) HIPCHK(ac, hipMemcpyAsync(kept_docs, d_kept, nk * 8, hipMemcpyDeviceToHost, s));
   if (doc_out_offsets) HIPCHK(ac, hipMemcpyAsync(doc_out_offsets, d_doo, (nk + 1) * 8, hipMemcpyDeviceToHost, s));
   if (out && nb) HIPCHK(ac, hipMemcpyAsync(out, d_out, nb, hipMemcpyDeviceToHost, s));
+  if (n_rows) HIPCHK(ac, hipMemcpyAsync(gp->rows, d_rows, n_rows * 4, hipMemcpyDeviceToHost, s));
   HIPCHK(ac, hipStreamSynchronize(s));
   *n_kept = nk;
   if (n_out_bytes) *n_out_bytes = nb;

@@ -94,6 +94,9 @@ static void doccount_setup(aha_ac *ac) {
   // (tests: a few hits, so that a batch takes several ranges or a document goes through its key counts; 1 block)
   ac->cls_hit_bytes = env("AHA_CLASS_HIT_BYTES", ac->dc_hit_bytes, 12, kV2MaxRegionBytes);
   ac->cls_blocks = (uint32_t)env("AHA_CLASS_BLOCKS", 0, 1, 1u << 20);
+  // rule grep: the bound of the class-count table a call keeps in scratch where the caller gives no rows (tests: a few bytes,
+  // so that the refusal is reached).  1 GiB: 4 M documents of 64 classes, well under the device's memory
+  ac->rule_table_bytes = env("AHA_RULE_TABLE_BYTES", 1ull << 30, 4, 1ull << 36);
 }
 
 void v2_setup(aha_ac *ac) {
@@ -1895,6 +1898,73 @@ int32_t device_records(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const u
   return device_records_emit(ac, sc, d_doc_offsets, n_docs, n_bytes, d_rec_offsets, d_doc_rec_offsets, stream);
 }
 
+// The keep, S and T masks over documents, their three block ranks and the one-entry table in grpbuf: what fills the masks
+// (kgr_flag from the hit offsets, or a rule over the class counts) is the caller's business, the tail below takes them.
+struct GrepMasks {
+  uint32_t *keep, *S, *T;
+  uint64_t *blk_k, *blk_s, *blk_t;
+  RepEntry *ent;
+};
+static bool grep_masks(Scratch *sc, uint64_t D, GrepMasks &M) {
+  const uint64_t n_words = (D + 31) / 32, n_blk = select_rank_blocks(D);
+  uint32_t *masks = (uint32_t *)grp_reserve(sc, kGrpDocMasks, std::max<uint64_t>(n_words, 1) * 3 * 4);
+  uint64_t *blks = (uint64_t *)grp_reserve(sc, kGrpDocBlocks, (n_blk + 1) * 3 * 8);
+  M.ent = (RepEntry *)grp_reserve(sc, kGrpTable, sizeof(RepEntry));
+  if (!masks || !blks || !M.ent) return false;
+  M.keep = masks, M.S = masks + n_words, M.T = masks + 2 * n_words;
+  M.blk_k = blks, M.blk_s = blks + (n_blk + 1), M.blk_t = blks + 2 * (n_blk + 1);
+  return true;
+}
+
+// Grep's tail, from the three masks on (steps 2 to 4 of device_grep below): their ranks, the runs, the scan, the verdict, then
+// -- once both numbers fit -- the kept documents and the copy.  *kept and *total are the required numbers either way; *fits
+// says whether anything was written to the caller.
+static int32_t grep_tail(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t D, uint64_t n_bytes,
+                         const GrepMasks &M, uint64_t *d_kept_docs, uint64_t *d_doc_out_offsets, uint64_t cap_docs, uint8_t *d_out,
+                         uint64_t cap_bytes, uint64_t *kept_out, uint64_t *total_out, bool *fits_out, hipStream_t s) {
+  auto nomem = [&]() {
+    tls_err = "hipMalloc failed for the scratch of a grep call";
+    return AHA_E_HIP;
+  };
+  const uint32_t blocks = grep_grid(ac);
+  const uint64_t n_blk = select_rank_blocks(D);
+  select_launch_rank(M.keep, D, M.blk_k, blocks, s);
+  select_launch_rank(M.S, D, M.blk_s, blocks, s);
+  select_launch_rank(M.T, D, M.blk_t, blocks, s);
+  HIPCHK(ac, hipGetLastError());
+  uint64_t kept = 0, n_runs = 0;
+  HIPCHK(ac, hipMemcpyAsync(&kept, M.blk_k + n_blk, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipMemcpyAsync(&n_runs, M.blk_s + n_blk, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  const uint64_t n_sum = replace_scan_blocks(n_runs);
+  aha_hit *sel = (aha_hit *)grp_reserve(sc, kGrpSel, std::max<uint64_t>(n_runs, 1) * sizeof(aha_hit));
+  uint64_t *A = (uint64_t *)grp_reserve(sc, kGrpStart, std::max<uint64_t>(n_runs, 1) * 8);
+  int64_t *shift = (int64_t *)grp_reserve(sc, kGrpShift, (n_runs + 1) * 8);
+  int64_t *sums = (int64_t *)grp_reserve(sc, kGrpSums, (n_sum + 1) * 8);
+  if (!sel || !A || !shift || !sums) return nomem();
+  grep_launch_runs(M.S, M.T, D, M.blk_s, M.blk_t, d_doc_offsets, n_runs, A, shift, sel, M.ent, blocks, s);
+  replace_launch_scan(shift, n_runs, sums, blocks, s);
+  HIPCHK(ac, hipGetLastError());
+  int64_t change = 0;
+  HIPCHK(ac, hipMemcpyAsync(&change, shift + n_runs, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  const uint64_t total = (uint64_t)((int64_t)n_bytes + change);
+  const bool per_doc = d_kept_docs || d_doc_out_offsets;
+  const bool fits = !(per_doc && kept > cap_docs) && !(d_out && total > cap_bytes);
+  if (fits) {
+    if (per_doc)
+      grep_launch_emit_docs(M.keep, M.S, D, M.blk_k, M.blk_s, d_doc_offsets, shift, n_runs, d_kept_docs, d_doc_out_offsets, blocks, s);
+    if (d_out)
+      replace_launch_copy(d_corpus, sel, A, shift, n_runs, M.ent, 1, (const uint8_t *)M.ent, d_out, total, blocks, s);
+    HIPCHK(ac, hipGetLastError());
+    HIPCHK(ac, hipStreamSynchronize(s));
+  }
+  *kept_out = kept;
+  *total_out = total;
+  *fits_out = fits;
+  return AHA_OK;
+}
+
 // One device-resident batch filtered (aha_ac_grep_batch_device).
 //   1. device_count without key counts: the documents' hit offsets into scratch, the total, the offsets validated.
 //   2. The keep, S and T masks over documents (scan_grep.hip kgr_flag) and their ranks by select's ranker: the kept documents
@@ -1902,7 +1972,7 @@ int32_t device_records(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const u
 //   3. Per dropped run its first byte and its change of length (minus its bytes); replace's scan gives shift; the total comes
 //      back to the host, where the verdict is given.  Nothing has been written to the caller so far.
 //   4. The kept documents' indices and offsets, and replace's copy fed with the runs as deleted hits.
-// A failing call writes none of the caller's buffers.
+// A failing call writes none of the caller's buffers.  Steps 2 (from the ranks on) to 4 are grep_tail, which rule grep shares.
 int32_t device_grep(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
                     const aha_match_params *params, uint32_t flags, uint64_t *d_kept_docs, uint64_t *d_doc_out_offsets,
                     uint64_t cap_docs, uint8_t *d_out, uint64_t cap_bytes, uint64_t *n_kept, uint64_t *n_out_bytes,
@@ -1928,46 +1998,14 @@ int32_t device_grep(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint
     return rc;
   const bool prof = ac->profiling.load();
   const auto t0 = std::chrono::steady_clock::now();
-  const uint32_t blocks = grep_grid(ac);
-  const uint64_t n_words = (D + 31) / 32, n_blk = select_rank_blocks(D);
-  uint32_t *masks = (uint32_t *)grp_reserve(sc, kGrpDocMasks, std::max<uint64_t>(n_words, 1) * 3 * 4);
-  uint64_t *blks = (uint64_t *)grp_reserve(sc, kGrpDocBlocks, (n_blk + 1) * 3 * 8);
-  RepEntry *ent = (RepEntry *)grp_reserve(sc, kGrpTable, sizeof(RepEntry));
-  if (!masks || !blks || !ent) return nomem();
-  uint32_t *keep = masks, *S = masks + n_words, *T = masks + 2 * n_words;
-  uint64_t *blk_k = blks, *blk_s = blks + (n_blk + 1), *blk_t = blks + 2 * (n_blk + 1);
-  grep_launch_flag(d_dho, D, (flags & AHA_GREP_INVERT) != 0, keep, S, T, blocks, s);
-  select_launch_rank(keep, D, blk_k, blocks, s);
-  select_launch_rank(S, D, blk_s, blocks, s);
-  select_launch_rank(T, D, blk_t, blocks, s);
-  HIPCHK(ac, hipGetLastError());
-  uint64_t kept = 0, n_runs = 0;
-  HIPCHK(ac, hipMemcpyAsync(&kept, blk_k + n_blk, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(ac, hipMemcpyAsync(&n_runs, blk_s + n_blk, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(ac, hipStreamSynchronize(s));
-  const uint64_t n_sum = replace_scan_blocks(n_runs);
-  aha_hit *sel = (aha_hit *)grp_reserve(sc, kGrpSel, std::max<uint64_t>(n_runs, 1) * sizeof(aha_hit));
-  uint64_t *A = (uint64_t *)grp_reserve(sc, kGrpStart, std::max<uint64_t>(n_runs, 1) * 8);
-  int64_t *shift = (int64_t *)grp_reserve(sc, kGrpShift, (n_runs + 1) * 8);
-  int64_t *sums = (int64_t *)grp_reserve(sc, kGrpSums, (n_sum + 1) * 8);
-  if (!sel || !A || !shift || !sums) return nomem();
-  grep_launch_runs(S, T, D, blk_s, blk_t, d_doc_offsets, n_runs, A, shift, sel, ent, blocks, s);
-  replace_launch_scan(shift, n_runs, sums, blocks, s);
-  HIPCHK(ac, hipGetLastError());
-  int64_t change = 0;
-  HIPCHK(ac, hipMemcpyAsync(&change, shift + n_runs, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(ac, hipStreamSynchronize(s));
-  const uint64_t total = (uint64_t)((int64_t)n_bytes + change);
-  const bool per_doc = d_kept_docs || d_doc_out_offsets;
-  const bool fits = !(per_doc && kept > cap_docs) && !(d_out && total > cap_bytes);
-  if (fits) {
-    if (per_doc)
-      grep_launch_emit_docs(keep, S, D, blk_k, blk_s, d_doc_offsets, shift, n_runs, d_kept_docs, d_doc_out_offsets, blocks, s);
-    if (d_out)
-      replace_launch_copy(d_corpus, sel, A, shift, n_runs, ent, 1, (const uint8_t *)ent, d_out, total, blocks, s);
-    HIPCHK(ac, hipGetLastError());
-    HIPCHK(ac, hipStreamSynchronize(s));
-  }
+  GrepMasks M;
+  if (!grep_masks(sc, D, M)) return nomem();
+  grep_launch_flag(d_dho, D, (flags & AHA_GREP_INVERT) != 0, M.keep, M.S, M.T, grep_grid(ac), s);
+  uint64_t kept = 0, total = 0;
+  bool fits = false;
+  if ((rc = grep_tail(ac, sc, d_corpus, d_doc_offsets, D, n_bytes, M, d_kept_docs, d_doc_out_offsets, cap_docs, d_out, cap_bytes, &kept,
+                      &total, &fits, s)))
+    return rc;
   *n_kept = kept;
   if (n_out_bytes) *n_out_bytes = total;
   if (n_hits_out) *n_hits_out = n_hits;
@@ -2072,5 +2110,81 @@ int32_t device_class_counts(aha_ac *ac, Scratch *sc, const aha_classes *table, c
   call.book.finish(n_hits, ranges.size(), nullptr);
   return AHA_OK;
 }
+
+// ---- rule grep (aha_ac_grep_batch* with AHA_GREP_RULE) ------------------------------------------------------------------
+// One device-resident batch filtered by a rule over its class counts (DESIGN.md 4.16 "Rule grep").  gp was checked by capi.cpp.
+//   1. device_class_counts as it is: the D x C table into d_rows where the caller gave it and the call cannot fail any more
+//      (rows_early: the capacities cover every outcome, or d_rows is the host entry's staging buffer), else into
+//      grpbuf[kGrpRows], which AHA_RULE_TABLE_BYTES bounds.
+//   2. kgq_keep: the keep mask from the rule; kgq_edges: S and T from keep (scan_greprule.hip).
+//   3. grep_tail.  Once it is known to fit, a table in scratch is copied into d_rows.
+// A failing call writes none of the caller's buffers, d_rows included.
+int32_t device_grep_rule(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                         uint64_t n_bytes, const aha_grep_params *gp, uint32_t *d_rows, uint32_t flags, uint64_t *d_kept_docs,
+                         uint64_t *d_doc_out_offsets, uint64_t cap_docs, uint8_t *d_out, uint64_t cap_bytes, uint64_t *n_kept,
+                         uint64_t *n_out_bytes, uint64_t *n_hits_out, void *stream, bool offsets_checked, bool rows_early) {
+  if (!ac || !gp || !gp->classes || !gp->terms || !n_kept || !d_doc_offsets) return AHA_E_INVALID;
+  if (gp->n_terms == 0 || gp->n_terms > kRuleMaxTerms || (flags & ~(AHA_GREP_INVERT | AHA_GREP_RULE))) return AHA_E_INVALID;
+  if ((cap_docs && !d_kept_docs && !d_doc_out_offsets) || (cap_bytes && !d_out)) return AHA_E_INVALID;
+  if (ac->device < 0) return no_device();
+  DeviceGuard g(ac->device);
+  hipStream_t s = (hipStream_t)stream;
+  const aha_classes *table = gp->classes;
+  const uint64_t D = n_docs, C = table->n_classes;
+  *n_kept = 0;
+  if (n_out_bytes) *n_out_bytes = 0;
+  if (n_hits_out) *n_hits_out = 0;
+  auto nomem = [&]() {
+    tls_err = "hipMalloc failed for the scratch of a grep call";
+    return AHA_E_HIP;
+  };
+  const bool direct = d_rows && rows_early;
+  uint32_t *tab = d_rows;
+  if (!direct) {
+    if (D * C * 4 > ac->rule_table_bytes) {
+      tls_err = "rule grep: the class-count table of " + std::to_string(D) + " x " + std::to_string(C) +
+                " entries exceeds AHA_RULE_TABLE_BYTES (" + std::to_string(ac->rule_table_bytes) +
+                "): pass rows with capacities for every document and byte, or smaller batches";
+      return AHA_E_TOO_LARGE;
+    }
+    tab = (uint32_t *)grp_reserve(sc, kGrpRows, std::max<uint64_t>(D * C * 4, 4));
+    if (!tab) return nomem();
+  }
+  int32_t rc;
+  uint64_t n_hits = 0;
+  if ((rc = device_class_counts(ac, sc, table, d_corpus, d_doc_offsets, D, n_bytes, &gp->match, tab, &n_hits, stream, offsets_checked)))
+    return rc;
+  const bool prof = ac->profiling.load();
+  const auto t0 = std::chrono::steady_clock::now();
+  GrepMasks M;
+  if (!grep_masks(sc, D, M)) return nomem();
+  const uint32_t blocks = grep_grid(ac);
+  greprule_launch_keep(tab, (uint32_t)C, d_doc_offsets, D, gp->terms, gp->n_terms, (flags & AHA_GREP_INVERT) != 0, M.keep, blocks, s);
+  greprule_launch_edges(M.keep, D, M.S, M.T, blocks, s);
+  uint64_t kept = 0, total = 0;
+  bool fits = false;
+  if ((rc = grep_tail(ac, sc, d_corpus, d_doc_offsets, D, n_bytes, M, d_kept_docs, d_doc_out_offsets, cap_docs, d_out, cap_bytes, &kept,
+                      &total, &fits, s)))
+    return rc;
+  if (fits && d_rows && !direct && D) {
+    HIPCHK(ac, hipMemcpyAsync(d_rows, tab, D * C * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(ac, hipStreamSynchronize(s));
+  }
+  *n_kept = kept;
+  if (n_out_bytes) *n_out_bytes = total;
+  if (n_hits_out) *n_hits_out = n_hits;
+  if (prof) {  // engine, n_hits, repeats: the class-count call's; ms_write: everything after its match
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    std::lock_guard<std::mutex> lk(ac->last_mu);
+    ac->last.ms_write += (float)ms;
+    ac->last.n_hits = n_hits;
+  }
+  if (!fits) {
+    tls_err = "output buffer too small";
+    return AHA_E_CAPACITY;
+  }
+  return AHA_OK;
+}
+
 
 }  // namespace ahai

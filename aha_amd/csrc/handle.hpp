@@ -166,6 +166,7 @@ enum GrepSlot {
   kGrpShift,      // grep: per dropped run the change of length in front of it, the total change behind the last
   kGrpSums,       // grep: the scan's block sums
   kGrpTable,      // grep: the one-entry replacement table (the empty replacement)
+  kGrpRows,       // rule grep: the D x C class counts where the caller gives no rows (bounded by AHA_RULE_TABLE_BYTES)
   kGrpCount
 };
 // fgrpbuf: feed grep calls (feed.cpp feed_grep; scan_feedgrep.hip).  The fragments come from device_records, whose mask
@@ -341,6 +342,7 @@ struct aha_ac {
   uint64_t sel_hit_bytes = 0;  // select calls: the bound of a range's hit buffer (AHA_SELECT_HIT_BYTES)
   uint32_t rep_blocks = 0;  // replace calls: the cap of the scan's and the copy's grids (AHA_REPLACE_BLOCKS; 0: the default)
   uint32_t grep_blocks = 0;  // records and grep calls: the cap of their grids (AHA_GREP_BLOCKS; 0: the default)
+  uint64_t rule_table_bytes = 0;  // rule grep: the bound of the class-count table in scratch (AHA_RULE_TABLE_BYTES)
   uint64_t cls_hit_bytes = 0;  // class-counts calls: the bound of a range's hit buffer (AHA_CLASS_HIT_BYTES)
   uint32_t cls_blocks = 0;  // ... and the cap of their kernels' grids (AHA_CLASS_BLOCKS; 0: the default)
   uint32_t seg2 = 0;  // slots below it: the root's and the depth-1 states' rows
@@ -579,6 +581,13 @@ int32_t device_grep(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint
                     const aha_match_params *params, uint32_t flags, uint64_t *d_kept_docs, uint64_t *d_doc_out_offsets,
                     uint64_t cap_docs, uint8_t *d_out, uint64_t cap_bytes, uint64_t *n_kept, uint64_t *n_out_bytes, uint64_t *n_hits,
                     void *stream, bool offsets_checked);
+// the same filtered by a rule over the class counts (AHA_GREP_RULE; gp checked by capi.cpp grep_rule_args): device_class_counts
+// into d_rows or scratch, the keep mask from the rule and S and T from keep (scan_greprule.hip), then grep's tail.
+// rows_early: d_rows may be written before the verdict (it is not the caller's buffer, or the call cannot fail on capacity)
+int32_t device_grep_rule(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                         uint64_t n_bytes, const aha_grep_params *gp, uint32_t *d_rows, uint32_t flags, uint64_t *d_kept_docs,
+                         uint64_t *d_doc_out_offsets, uint64_t cap_docs, uint8_t *d_out, uint64_t cap_bytes, uint64_t *n_kept,
+                         uint64_t *n_out_bytes, uint64_t *n_hits, void *stream, bool offsets_checked, bool rows_early);
 // one device-resident batch as a dense table of hits per (document, key class) (aha_ac_class_counts_batch_device):
 // device_count for the hits per document, the match of every range of whole documents into scratch, one add per (hit, class)
 // into d_out[n_docs][table->n_classes] (scan_classcount.hip)

@@ -362,6 +362,16 @@ void grep_launch_emit_docs(const uint32_t *keep, const uint32_t *S, uint64_t n_d
                            const uint64_t *doc_off, const int64_t *shift, uint64_t n_runs, uint64_t *kept_docs, uint64_t *doc_out,
                            uint32_t max_blocks, void *stream);
 
+// rule grep (scan_greprule.hip; engine.cpp device_grep_rule).  rows: the class counts, n_classes words per document.
+// terms: HOST memory, at most kRuleMaxTerms, in any order and with any group ids (they travel as a kernel argument).
+// keep[0, ceil(n_docs / 32)): bit d = (the rule passes for document d) != invert, whole words, the bits from n_docs on 0
+constexpr uint32_t kRuleMaxTerms = 64;
+constexpr uint32_t kRuleChunkClasses = 32;  // columns of the table a wave stages through LDS at a time, for its 64 rows
+void greprule_launch_keep(const uint32_t *rows, uint32_t n_classes, const uint64_t *doc_off, uint64_t n_docs,
+                          const aha_rule_term *terms, uint32_t n_terms, bool invert, uint32_t *keep, uint32_t max_blocks, void *stream);
+// S / T from keep alone, ceil(n_docs / 32) whole words each: a run of dropped documents starts / ends at the bit
+void greprule_launch_edges(const uint32_t *keep, uint64_t n_docs, uint32_t *S, uint32_t *T, uint32_t max_blocks, void *stream);
+
 // class-counts path (scan_classcount.hip; engine.cpp device_class_counts), over one range of whole documents: its n_hits hits in
 // `hits` (hit_off[d] - hit_off[0]: the first hit of document d of its nd), key k's classes cls_ids[cls_off[k] .. cls_off[k+1]),
 // out: the row of the range's first document (n_classes words per document, cleared before the call's first range).

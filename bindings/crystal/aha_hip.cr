@@ -238,6 +238,27 @@ lib LibAhaHip
                                cap_docs : UInt64, d_out : UInt8*, cap_bytes : UInt64, n_kept : UInt64*, n_out_bytes : UInt64*,
                                n_hits : UInt64*, stream : Void*) : Int32
   type Classes = Void*
+  # rule grep: with GREP_RULE (beside GREP_INVERT) `params` of the grep entries points to a GrepParams -- cast its address to
+  # MatchParams* --, and the documents are kept by the rule over their class counts.  A term: count[class_id] OP num, or with
+  # den_bytes > 0 "num hits per den_bytes bytes"; the terms of a group are AND-ed, the groups OR-ed; 1 to 64 terms
+  GREP_RULE = 4_u32
+  RULE_GE   = 0_u32 # lhs >= rhs
+  RULE_LT   = 1_u32 # lhs <  rhs
+  struct RuleTerm
+    class_id : UInt32
+    op : UInt16
+    group : UInt16
+    num : UInt32
+    den_bytes : UInt32
+  end
+  struct GrepParams
+    match : MatchParams # first member: match.struct_size = sizeof(GrepParams)
+    classes : Classes   # of this handle
+    terms : RuleTerm*   # host memory, in both entries
+    n_terms : UInt32    # 1 .. 64
+    reserved : UInt32   # 0
+    rows : UInt32*      # optional D x C table, as class counts writes it (host entry: host memory; device entry: HBM)
+  end
   fun aha_classes_create(ac : Ac, class_ids : UInt32*, offsets : UInt64*, n_classes : UInt32, out : Classes*) : Int32
   fun aha_classes_free(table : Classes) : Void
   fun aha_ac_class_counts_batch(ac : Ac, table : Classes, corpus : UInt8*, doc_offsets : UInt64*, n_docs : UInt64,
@@ -656,6 +677,49 @@ module Aha
       doo = Array(UInt64).new(nk + 1, 0_u64)
       out_bytes = Bytes.new(nb)
       rc = LibAhaHip.aha_ac_grep_batch(@handle, bytes.to_unsafe, rec.to_unsafe, n_rec, pointerof(params), flags,
+        Pointer(UInt64).null, doo.to_unsafe, nk, nb > 0 ? out_bytes.to_unsafe : Pointer(UInt8).null, nb, pointerof(nk),
+        pointerof(nb), Pointer(UInt64).null)
+      raise String.new(LibAhaHip.aha_last_error(@handle)) if rc != 0
+      Array.new(nk.to_i32) { |i| out_bytes[doo[i], doo[i + 1] - doo[i]] }
+    end
+
+    # The records of seq whose class counts pass a rule (aha_ac_grep_batch with GREP_RULE over the records); invert: those that
+    # do not.  table: a LibAhaHip::Classes of this handle (aha_classes_create); terms: {class_id, op, group, num, den_bytes}
+    # each, op RULE_GE or RULE_LT.  A record passes when some group has all its terms true.
+    def grep_rule(seq : String | Bytes, table : LibAhaHip::Classes,
+                  terms : Array({UInt32, UInt32, UInt16, UInt32, UInt32}), delim : UInt8 = 10_u8, invert : Bool = false,
+                  sep : BitArray? = nil) : Array(Bytes)
+      bytes = seq.is_a?(String) ? seq.to_slice : seq
+      rec = records(bytes, delim)
+      n_rec = (rec.size - 1).to_u64
+      packed = terms.map do |t|
+        rt = LibAhaHip::RuleTerm.new
+        rt.class_id = t[0]
+        rt.op = t[1].to_u16
+        rt.group = t[2]
+        rt.num = t[3]
+        rt.den_bytes = t[4]
+        rt
+      end
+      gp = LibAhaHip::GrepParams.new
+      gp.match = AC.params(false, sep)
+      gp.match.struct_size = sizeof(LibAhaHip::GrepParams).to_u32
+      gp.classes = table
+      gp.terms = packed.to_unsafe
+      gp.n_terms = packed.size.to_u32
+      gp.reserved = 0_u32
+      gp.rows = Pointer(UInt32).null
+      params = pointerof(gp).as(LibAhaHip::MatchParams*)
+      flags = LibAhaHip::GREP_RULE | (invert ? LibAhaHip::GREP_INVERT : 0_u32)
+      nk = 0_u64
+      nb = 0_u64
+      rc = LibAhaHip.aha_ac_grep_batch(@handle, bytes.to_unsafe, rec.to_unsafe, n_rec, params, flags,
+        Pointer(UInt64).null, Pointer(UInt64).null, 0_u64, Pointer(UInt8).null, 0_u64, pointerof(nk), pointerof(nb),
+        Pointer(UInt64).null)
+      raise String.new(LibAhaHip.aha_last_error(@handle)) if rc != 0
+      doo = Array(UInt64).new(nk + 1, 0_u64)
+      out_bytes = Bytes.new(nb)
+      rc = LibAhaHip.aha_ac_grep_batch(@handle, bytes.to_unsafe, rec.to_unsafe, n_rec, params, flags,
         Pointer(UInt64).null, doo.to_unsafe, nk, nb > 0 ? out_bytes.to_unsafe : Pointer(UInt8).null, nb, pointerof(nk),
         pointerof(nb), Pointer(UInt64).null)
       raise String.new(LibAhaHip.aha_last_error(@handle)) if rc != 0

@@ -523,6 +523,59 @@ class AC {
     return class_counts_batch(seq, {0, seq.size()}, table);
   }
 
+  // Rule grep (aha_ac_grep_batch with AHA_GREP_RULE): the documents whose class counts pass a rule -- invert: those that do not
+  // -- compacted on the device as grep_batch compacts them.  A rule is 1 to 64 terms (aha_rule_term): count[class_id] OP num, or
+  // with den_bytes > 0 "num hits per den_bytes bytes of the document"; OP is AHA_RULE_GE or AHA_RULE_LT; a document passes when
+  // some group has all its terms true.  rows (optional): the D x C table as class_counts_batch returns it.
+  //   auto m = aha::AC::compile({"he", "she", "hers"});
+  //   auto t = m.classes({{0}, {0, 1}, {}}, 2);
+  //   m.grep_rule_batch("ushershe", {0, 6, 8}, t, {AC::term(0, AHA_RULE_GE, 2)})                                == "ushers"
+  //   m.grep_rule_batch("ushershe", {0, 6, 8}, t, {AC::term(0, AHA_RULE_GE, 1), AC::term(1, AHA_RULE_LT, 1)})   == "he"
+  //   m.grep_rule_batch("ushershe", {0, 6, 8}, t, {AC::term(0, AHA_RULE_GE, 1, 3)})                             == "ushershe"
+  static aha_rule_term term(uint32_t class_id, uint32_t op, uint32_t num, uint32_t den_bytes = 0, uint16_t group = 0) {
+    aha_rule_term t{};
+    t.class_id = class_id;
+    t.op = (uint16_t)op;
+    t.group = group;
+    t.num = num;
+    t.den_bytes = den_bytes;
+    return t;
+  }
+  std::string grep_rule_batch(std::string_view corpus, const std::vector<uint64_t> &doc_offsets, const Classes &table,
+                              const std::vector<aha_rule_term> &terms, bool invert = false, std::vector<uint64_t> *kept_docs = nullptr,
+                              std::vector<uint64_t> *doc_out_offsets = nullptr, std::vector<uint32_t> *rows = nullptr,
+                              uint64_t *n_hits = nullptr) const {
+    if (doc_offsets.empty()) throw Error(AHA_E_INVALID, "doc_offsets holds D + 1 entries");
+    aha_grep_params gp{};
+    gp.match.struct_size = sizeof(gp);
+    gp.classes = table.handle();
+    gp.terms = terms.data();
+    gp.n_terms = (uint32_t)terms.size();
+    const uint64_t D = doc_offsets.size() - 1;
+    const uint8_t *text = reinterpret_cast<const uint8_t *>(corpus.data());
+    const uint32_t flags = AHA_GREP_RULE | (invert ? AHA_GREP_INVERT : 0u);
+    uint64_t nk = 0, nb = 0, nh = 0;
+    int32_t rc = aha_ac_grep_batch(h_, text, doc_offsets.data(), D, &gp.match, flags, nullptr, nullptr, 0, nullptr, 0, &nk, &nb, &nh);
+    std::vector<uint64_t> kept(nk + 1), doo(nk + 1);
+    std::vector<uint32_t> table_rows(rows ? D * table.n_classes() : 0);
+    std::string out(nb, '\0');
+    if (rc == AHA_OK) {
+      gp.rows = table_rows.empty() ? nullptr : table_rows.data();
+      rc = aha_ac_grep_batch(h_, text, doc_offsets.data(), D, &gp.match, flags, kept.data(), doo.data(), nk,
+                             nb ? reinterpret_cast<uint8_t *>(&out[0]) : nullptr, nb, &nk, &nb, &nh);
+    }
+    if (rc != AHA_OK) {
+      const char *m = aha_last_error(h_);
+      throw Error(rc, (m && *m) ? m : aha_strerror(rc));
+    }
+    kept.resize(nk);
+    if (kept_docs) *kept_docs = std::move(kept);
+    if (doc_out_offsets) *doc_out_offsets = std::move(doo);
+    if (rows) *rows = std::move(table_rows);
+    if (n_hits) *n_hits = nh;
+    return out;
+  }
+
   // Which bytes of the batch lie inside a hit of match_batch, without the hit list (aha_ac_cover_batch): bit j of the batch is
   // word j >> 5, bit j & 31 of what is returned; doc_covered (optional): covered bytes per document.
   std::vector<uint32_t> cover_batch(std::string_view corpus, const std::vector<uint64_t> &doc_offsets,

@@ -874,9 +874,65 @@ int32_t aha_ac_replace_batch_device(aha_ac *ac, const aha_repl *table, const uin
  * of these calls' kernels, the reused rank, scan and copy launches included.
  * aha_ac_last_timing (grep): engine = the engine that traversed, n_hits = all hits, ms_write = everything after the count.
  * The host entries stage the batch on the device; a host sizing call followed by the real call runs the device work twice.
- * Out of scope so far: char offsets, match_longest, groups, multi-byte delimiters, a minimum hit count, an in-place form
- * (feeds: aha_feed_grep_batch* below). */
+ * Out of scope so far: char offsets, match_longest, groups, multi-byte delimiters, an in-place form (feeds:
+ * aha_feed_grep_batch* below).
+ *
+ * RULE GREP (AHA_GREP_RULE, flag 4, combinable with AHA_GREP_INVERT: flags 5; 2 and 3 stay refused).  `params` points to an
+ * aha_grep_params whose first member is the call's aha_match_params with match.struct_size = sizeof(aha_grep_params); the
+ * documents are kept by a rule over their CLASS COUNTS (aha_ac_class_counts_batch* below) instead of "at least one hit".
+ * count[d][c] = what aha_ac_class_counts_batch writes for the same batch, match params, handle and class table (a separator
+ * filter and a folded handle included); len_d = doc_offsets[d+1] - doc_offsets[d].  A term is
+ *   den_bytes == 0:  count[d][class_id] OP num
+ *   den_bytes  > 0:  (uint64)count[d][class_id] * den_bytes OP (uint64)num * len_d     ("num hits per den_bytes bytes")
+ * with OP >= (AHA_RULE_GE) or < (AHA_RULE_LT); both products fit 64 bits (counts are below 2^32, documents below 2^31
+ * bytes); an empty document follows the formula (0 >= 0 holds, 0 < 0 does not).  A document PASSES when some `group` value has
+ * all its terms true: OR over groups, AND inside a group; group ids are arbitrary and terms need not be sorted.  Document d is
+ * KEPT when passes(d) != invert.  Everything else is grep's contract above, word for word: kept_docs, doc_out_offsets, out,
+ * cap_docs, cap_bytes, AHA_E_CAPACITY with both required numbers and nothing written, out == NULL never launches the copy,
+ * *n_hits = all hits of the batch, two calls give identical bytes, the handle's back-off state is read and never written.
+ * rows (optional): the D x C table itself, as class counts writes it -- host memory in the host entry, HBM in the device
+ * entry; every entry is written and nothing outside it, and nothing on a capacity failure.  terms is host memory in both
+ * entries (it travels as a kernel argument).
+ * AHA_E_INVALID before any device work and with every buffer untouched: match.struct_size < sizeof(aha_grep_params), a NULL
+ * table or a table made for another handle, NULL terms, n_terms == 0 or n_terms > 64, reserved != 0, an op above 1, a
+ * class_id >= the table's n_classes, and everything grep refuses; a host-only handle answers AHA_E_NO_DEVICE after these.
+ * Without AHA_GREP_RULE the call is the one above, whatever struct_size says.
+ * Where rows is NULL the table lives in device scratch, at most AHA_RULE_TABLE_BYTES (read when the handle is compiled;
+ * default 1 GiB): a batch whose D x C x 4 exceeds it fails with AHA_E_TOO_LARGE and writes nothing (give rows, or smaller
+ * batches).  In the device entry rows takes the table at once only where no capacity can fail the call any more (cap_docs >= D
+ * or no per-document buffer, cap_bytes >= N or no out); otherwise the table is built in the same bounded scratch and copied
+ * into rows once the call is known to fit.
+ * Example: the class-counts example below -- keys "he", "she", "hers" with classes {0}, {0, 1}, {} over the documents "ushers"
+ * and "he" -- has the rows {2, 1} and {1, 0}.  The rule {c0 >= 2} keeps document 0; {c0 >= 1 AND c1 < 1} keeps document 1;
+ * {c0 >= 1 per 3 bytes} keeps both (2 * 3 >= 1 * 6 and 1 * 3 >= 1 * 2).
+ * Pipeline (scan_greprule.hip, DESIGN.md 4.16 "Rule grep"): the class-counts call as it is, into rows or scratch; kgq_keep, a
+ * wave per 64 documents, stages the columns the rule names through LDS, 32 at a time, evaluates the rule (a kernel argument)
+ * and writes the keep mask by ballot; kgq_edges, a lane per mask word, derives S and T from keep alone; then grep's tail above,
+ * unchanged.  aha_ac_last_timing: engine, n_hits and repeats as class counts reports them, ms_write = everything after the
+ * class-counts call's match.
+ * Out of scope so far: weighted sums and comparisons between two classes, tables restricted to the classes a rule names,
+ * slabs of documents, feeds, groups, char offsets, match_longest, a rule object on the device. */
 #define AHA_GREP_INVERT 1u /* keep the documents WITHOUT a hit */
+#define AHA_GREP_RULE 4u   /* params points to an aha_grep_params; keep = the rule over the class counts (2u is refused) */
+#define AHA_RULE_GE 0u     /* lhs >= rhs */
+#define AHA_RULE_LT 1u     /* lhs <  rhs */
+typedef struct aha_classes aha_classes;
+typedef struct {
+  uint32_t class_id;
+  uint16_t op;        /* AHA_RULE_GE | AHA_RULE_LT */
+  uint16_t group;     /* the terms of one group are AND-ed, the groups OR-ed */
+  uint32_t num;
+  uint32_t den_bytes; /* 0: a plain count; else "num per den_bytes bytes" */
+} aha_rule_term;      /* 16 bytes */
+typedef struct {
+  aha_match_params match;     /* first member: match.struct_size = sizeof(aha_grep_params) */
+  const aha_classes *classes; /* of this handle */
+  const aha_rule_term *terms; /* host memory, in both entries */
+  uint32_t n_terms;           /* 1 .. 64 */
+  uint32_t reserved;          /* 0 */
+  uint32_t *rows;             /* optional D x C table, as class counts writes it: host memory in the host entry, HBM in the
+                                 device entry */
+} aha_grep_params;
 int32_t aha_ac_records_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc_offsets, uint64_t n_docs, uint8_t delim,
                              uint32_t flags /* 0 */, uint64_t *rec_offsets /* cap_records + 1 */, uint64_t cap_records,
                              uint64_t *doc_rec_offsets /* D+1 or NULL */, uint64_t *n_records);
@@ -934,9 +990,9 @@ int32_t aha_ac_grep_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uint
  * is compiled) caps the grids of these calls' kernels.
  * aha_ac_last_timing: engine = the engine that traversed, n_hits = all hits, ms_write = everything after the match, repeats =
  * the ranges before the last.  The host entry stages the batch on the device and downloads out.
- * Out of scope so far: feeds, groups, weights, accumulating into an existing table, char offsets, match_longest, conditions
- * on the row (grep by class, minimum counts). */
-typedef struct aha_classes aha_classes;
+ * Keeping documents by a rule over their row is grep's business: AHA_GREP_RULE above.
+ * Out of scope so far: feeds, groups, weights, accumulating into an existing table, char offsets, match_longest. */
+/* (aha_classes is declared above, with aha_grep_params) */
 int32_t aha_classes_create(aha_ac *ac, const uint32_t *class_ids /* offsets[K] */,
                            const uint64_t *offsets /* K+1, offsets[0] == 0, ascending */, uint32_t n_classes, aha_classes **out);
 void aha_classes_free(aha_classes *table);
@@ -1165,8 +1221,8 @@ int32_t aha_feed_replace_batch_device(aha_feed *f, const aha_repl *table, const 
  * open tail counts as dropped); grep's rank, runs, scan, emit and copy as they are; kfd_commit and kfg_commit.  Device scratch:
  * a records call's and a count call's, 17 bytes and 3 bits per fragment, 28 bytes per dropped run, 56 bytes and 4 W per piece;
  * 32 bytes of state per sequence.  AHA_GREP_BLOCKS caps the grids.
- * Out of scope so far: separator-filter feeds, char feeds, match_longest, a device-side hold buffer, a minimum hit count,
- * context lines. */
+ * Out of scope so far: separator-filter feeds, char feeds, match_longest, a device-side hold buffer, rules over class counts
+ * (AHA_GREP_RULE is a batch call), context lines. */
 #define AHA_FEED_GREP_FINAL 2u /* the pieces named in this call are the last of their sequences (beside AHA_GREP_INVERT, bit 0) */
 int32_t aha_feed_grep_batch(aha_feed *f, const uint8_t *corpus, const uint64_t *piece_offsets, const uint32_t *seq_ids,
                             uint64_t n_pieces, uint8_t delim, uint32_t flags /* AHA_GREP_INVERT | AHA_FEED_GREP_FINAL */,
