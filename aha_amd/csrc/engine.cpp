@@ -97,7 +97,11 @@ static void doccount_setup(aha_ac *ac) {
   // rule grep: the bound of the class-count table a call keeps in scratch where the caller gives no rows (tests: a few bytes,
   // so that the refusal is reached).  1 GiB: 4 M documents of 64 classes, well under the device's memory
   ac->rule_table_bytes = env("AHA_RULE_TABLE_BYTES", 1ull << 30, 4, 1ull << 36);
+  // the passes after the traversal: the cap of their grids (tests: 1 and 3, so that every lane strides)
+  ac->post_blocks = (uint32_t)env("AHA_POST_BLOCKS", 0, 1, 1u << 20);
 }
+
+uint32_t post_grid(const aha_ac *ac) { return ac->post_blocks ? ac->post_blocks : 8u * std::max<uint32_t>(ac->v2_grid, 64u); }
 
 void v2_setup(aha_ac *ac) {
   doccount_setup(ac);
@@ -267,7 +271,7 @@ static void *cover_reserve(Scratch *sc, CoverSlot slot, size_t bytes) { return r
 static int32_t stage_text(aha_ac *ac, const uint8_t **text, uint64_t n_bytes, void *dst, int fold, const uint64_t *doc_off,
                           uint64_t n_docs, hipStream_t s) {
   if (fold) {
-    const uint32_t max_blocks = 8u * std::max<uint32_t>(ac->v2_grid, 64u);
+    const uint32_t max_blocks = post_grid(ac);
     if (fold == 4)
       foldk_launch_copy(*text, (uint8_t *)dst, n_bytes, doc_off, n_docs, max_blocks, s);
     else if (fold == 3)
@@ -584,7 +588,7 @@ static int32_t launch_v2(aha_ac *ac, Scratch *sc, MatchArgs &M1, const V2Plan &P
         tls_err = "hipMalloc failed for the scratch of a cover call";
         return AHA_E_HIP;
       }
-      if (M1.cover_clear) cover_launch_clear(M1.cover_mask, (N + 31) / 32, abortf, 8u * ac->v2_grid, s);
+      if (M1.cover_clear) cover_launch_clear(M1.cover_mask, (N + 31) / 32, abortf, ac->post_blocks ? ac->post_blocks : 8u * ac->v2_grid, s);
     }
     if (unit && ac->unit_fused) {
       v2_launch_hit_scan(M, s);
@@ -1227,7 +1231,7 @@ int32_t device_cover(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
     return rc;
   const bool prof = ac->profiling.load();
   const auto t0 = std::chrono::steady_clock::now();
-  const uint32_t blocks = 8u * std::max<uint32_t>(ac->v2_grid, 64u);
+  const uint32_t blocks = post_grid(ac);
   uint64_t total = 0;
   if (n_bytes) {
     HIPCHK(ac, hipMemsetAsync(d_total, 0, 8, s));
@@ -1631,7 +1635,7 @@ int32_t device_select_to(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const
   }
   const size_t n_ranges = ranges.size();  // 0: no hit at all
   if (n_ranges) bounds.back() = D;
-  const uint32_t blocks = 8u * std::max<uint32_t>(ac->v2_grid, 64u);
+  const uint32_t blocks = post_grid(ac);
   uint64_t total = 0;
   // what a worked range leaves in scratch for the emit
   struct Range {
@@ -1793,7 +1797,7 @@ int32_t device_replace(aha_ac *ac, Scratch *sc, const aha_repl *table, const uin
   int64_t *sums = (int64_t *)rep_reserve(sc, kRepSums, (n_blk + 1) * 8);
   uint64_t *d_doo = (uint64_t *)rep_reserve(sc, kRepDocOut, (D + 1) * 8);
   if (!A || !shift || !sums || !d_doo) return nomem();
-  const uint32_t blocks = ac->rep_blocks ? ac->rep_blocks : 8u * std::max<uint32_t>(ac->v2_grid, 64u);
+  const uint32_t blocks = ac->rep_blocks ? ac->rep_blocks : post_grid(ac);
   replace_launch_delta(d_sel, n, d_dso, d_doc_offsets, D, table->d_ent, table->n_keys, A, shift, blocks, s);
   replace_launch_scan(shift, n, sums, blocks, s);
   replace_launch_doc_offsets(d_doc_offsets, d_dso, shift, D, d_doo, blocks, s);
@@ -1824,7 +1828,7 @@ int32_t device_replace(aha_ac *ac, Scratch *sc, const aha_repl *table, const uin
 
 // ---- records and grep calls (aha_ac_records_batch*, aha_ac_grep_batch*) ------------------------------------------------
 static void *grp_reserve(Scratch *sc, GrepSlot slot, size_t bytes) { return reserve_ptr(sc->grpbuf[slot], bytes, kGrowEighth); }
-uint32_t grep_grid(const aha_ac *ac) { return ac->grep_blocks ? ac->grep_blocks : 8u * std::max<uint32_t>(ac->v2_grid, 64u); }
+uint32_t grep_grid(const aha_ac *ac) { return ac->grep_blocks ? ac->grep_blocks : post_grid(ac); }
 
 // The first half of a records call: the record-end mask and its rank into grpbuf, the total read back.
 int32_t device_records_settle(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
@@ -2023,7 +2027,7 @@ int32_t device_grep(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint
 }
 
 // ---- class counts (aha_ac_class_counts_batch*) -----------------------------------------------------------------------
-uint32_t class_grid(const aha_ac *ac) { return ac->cls_blocks ? ac->cls_blocks : 8u * std::max<uint32_t>(ac->v2_grid, 64u); }
+uint32_t class_grid(const aha_ac *ac) { return ac->cls_blocks ? ac->cls_blocks : post_grid(ac); }
 static void *cls_reserve(Scratch *sc, ClassSlot slot, size_t bytes) { return reserve_ptr(sc->clsbuf[slot], bytes, kGrowEighth); }
 
 // One device-resident batch as hits per (document, key class) (aha_ac_class_counts_batch_device): d_out[D][C], every entry written.

@@ -220,7 +220,7 @@ int32_t feed_windows(aha_feed *f, Scratch *sc, FeedArgs &F, hipStream_t s, bool 
     // sequence's context in view -- and the windows cut from the fold of ctx || P; both matches read them as they are
     F.ftext = (uint8_t *)reserve(f, kFold, F.n_bytes + 64);
     if (!F.ftext) return no_memory("folded pieces");
-    const uint32_t max_blocks = 8u * std::max<uint32_t>(ac->v2_grid, 64u);
+    const uint32_t max_blocks = post_grid(ac);
     if (f->fold == 4)
       foldk_launch_copy(F.text, F.ftext, F.n_bytes, F.off, D, max_blocks, s);
     else if (f->fold == 3)
@@ -365,7 +365,7 @@ int32_t feed_cover(aha_feed *f, Scratch *sc, FeedArgs &F, hipStream_t s, uint32_
   uint64_t *d_total = (uint64_t *)f->buf[kMisc].p + 2;
   f->h_pin[0] = 0;
   if (F.n_bytes) {
-    const uint32_t blocks = 8u * std::max<uint32_t>(ac->v2_grid, 64u);
+    const uint32_t blocks = post_grid(ac);
     HIPCHK(ac, hipMemsetAsync(d_total, 0, 8, s));
     cover_launch_total(F.mask, n_words, d_total, blocks, s);
     if (d_piece_covered && F.D) cover_launch_doc_covered(F.mask, F.off, F.D, d_piece_covered, blocks, s);
@@ -386,7 +386,7 @@ int32_t no_scratch() {
   return AHA_E_HIP;
 }
 
-uint32_t select_blocks(const aha_ac *ac) { return 8u * std::max<uint32_t>(ac->v2_grid, 64u); }
+uint32_t select_blocks(const aha_ac *ac) { return post_grid(ac); }
 
 // the part of a select call that writes scratch only, shared with a replace call: the windows and the main pass with the true
 // hits into scratch, the extended positions, L, the masks, the walk and the rank.  -> S (everything but hold and out),
@@ -788,7 +788,7 @@ int32_t sep_refused(const char *what) {
   return AHA_E_INVALID;
 }
 
-uint32_t sep_blocks(const aha_ac *ac) { return 8u * std::max<uint32_t>(ac->v2_grid, 64u); }
+uint32_t sep_blocks(const aha_ac *ac) { return post_grid(ac); }
 
 // the keep mask of P.n_true hits and its rank; *n_kept = the total (one read-back)
 int32_t feed_sep_rank(aha_feed *f, Scratch *sc, const FeedArgs &F, FeedSepArgs &P, bool finish, hipStream_t s, uint64_t *n_kept) {

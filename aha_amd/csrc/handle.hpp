@@ -342,6 +342,7 @@ struct aha_ac {
   uint64_t sel_hit_bytes = 0;  // select calls: the bound of a range's hit buffer (AHA_SELECT_HIT_BYTES)
   uint32_t rep_blocks = 0;  // replace calls: the cap of the scan's and the copy's grids (AHA_REPLACE_BLOCKS; 0: the default)
   uint32_t grep_blocks = 0;  // records and grep calls: the cap of their grids (AHA_GREP_BLOCKS; 0: the default)
+  uint32_t post_blocks = 0;  // the passes after the traversal: the cap of their grids (AHA_POST_BLOCKS; 0: the default)
   uint64_t rule_table_bytes = 0;  // rule grep: the bound of the class-count table in scratch (AHA_RULE_TABLE_BYTES)
   uint64_t cls_hit_bytes = 0;  // class-counts calls: the bound of a range's hit buffer (AHA_CLASS_HIT_BYTES)
   uint32_t cls_blocks = 0;  // ... and the cap of their kernels' grids (AHA_CLASS_BLOCKS; 0: the default)
@@ -574,6 +575,9 @@ int32_t device_records_settle(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, 
                               uint64_t n_bytes, uint8_t delim, uint64_t *n_records, void *stream);
 int32_t device_records_emit(aha_ac *ac, Scratch *sc, const uint64_t *d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
                             uint64_t *d_rec_offsets, uint64_t *d_doc_rec_offsets, void *stream);
+// the cap of the grids of the passes after the traversal: fold copies, cover, select, the feeds' (AHA_POST_BLOCKS); the fallback
+// of the families' own caps
+uint32_t post_grid(const aha_ac *ac);
 uint32_t grep_grid(const aha_ac *ac);  // the cap of the records and grep grids (AHA_GREP_BLOCKS)
 // one device-resident batch filtered (aha_ac_grep_batch_device): device_count for the hits per document, the kept documents and
 // the dropped runs from them (scan_grep.hip), replace's scan and copy over the runs (scan_replace.hip)
