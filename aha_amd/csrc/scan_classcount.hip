@@ -2,7 +2,7 @@
 // document's keys added up by key class.  The hit list of a range of whole documents lies in scratch, document
 // by document (engine.cpp device_class_counts); the caller's table out[D][C] is clear when the first kernel runs.
 //   kcc_add        a workgroup takes slices of kCcSlice consecutive hits, grid-stride.  The slice's first and last document come
-//                  from the search ksl_longest uses (the largest d with hit_off[d] - hit_off[0] <= i: it steps over documents
+//                  from owner_of (post_common.hpp: the largest d with hit_off[d] - hit_off[0] <= i; it steps over documents
 //                  without hits).  Where (documents of the slice) x C fits kCcTable words, the slice is summed in LDS -- slot
 //                  (d - d_lo) * C + c -- and every non-zero slot is flushed with one global add; a document's hits may straddle
 //                  slices, so a row can be flushed by several workgroups.  Otherwise (many tiny documents, a wide C) every
@@ -17,25 +17,15 @@
 #include <algorithm>
 
 #include "image.hpp"
+#include "post_common.hpp"
 
 namespace aha {
 namespace {
 
+using post::grid_for;
+
 constexpr int kCcThreads = 256;
 static_assert(kCcSlice % kCcThreads == 0, "a slice is a whole number of rounds of the workgroup");
-
-// the largest d in [0, n) with off[d] - sub <= x (off ascends, off[0] - sub <= x): scan_select.hip sl_owner
-__device__ __forceinline__ uint64_t cc_owner(const uint64_t *off, uint64_t n, uint64_t sub, uint64_t x) {
-  uint64_t lo = 1, hi = n;
-  while (lo < hi) {
-    const uint64_t mid = (lo + hi) >> 1;
-    if (off[mid] - sub <= x)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  return lo - 1;
-}
 
 // one (document, class) pair per live lane, as its slot: add(slot, n) is called once for the slot of the wave's first live lane,
 // with the number of lanes that hold it, and once with 1 for every other live lane.  All 64 lanes reach this call.
@@ -64,7 +54,7 @@ __global__ __launch_bounds__(kCcThreads) void kcc_add(const int32_t *hits, uint6
   const uint64_t n_slices = (n_hits + kCcSlice - 1) / kCcSlice;
   for (uint64_t slice = blockIdx.x; slice < n_slices; slice += gridDim.x) {
     const uint64_t i0 = slice * kCcSlice, i1 = min(i0 + (uint64_t)kCcSlice, n_hits);
-    const uint64_t d_lo = cc_owner(hit_off, nd, h0, i0), d_hi = cc_owner(hit_off, nd, h0, i1 - 1);
+    const uint64_t d_lo = owner_of(hit_off, nd, i0, h0), d_hi = owner_of(hit_off, nd, i1 - 1, h0);
     const uint64_t span = d_hi - d_lo + 1;
     const bool lds = span * C <= kCcTable;  // (span <= nd < 2^32 and C <= 2^16: no overflow)
     const uint32_t n_slots = lds ? (uint32_t)(span * C) : 0u;
@@ -80,7 +70,7 @@ __global__ __launch_bounds__(kCcThreads) void kcc_add(const int32_t *hits, uint6
       uint64_t row = 0, j0 = 0;
       uint32_t n = 0;
       if (value < n_keys) {
-        row = cc_owner(hit_off + d_lo, span, h0, i);
+        row = owner_of(hit_off + d_lo, span, i, h0);  // (hit_off[d_lo] - h0 <= i0 <= i)
         j0 = cls_off[value];
         n = (uint32_t)(cls_off[value + 1] - j0);
       }
@@ -120,18 +110,14 @@ void classcount_launch_add(const void *hits, uint64_t n_hits, const uint64_t *hi
                            const uint32_t *cls_ids, uint32_t n_keys, uint32_t n_classes, uint32_t *out, uint32_t max_blocks,
                            void *stream) {
   if (!n_hits) return;
-  const uint64_t n_slices = (n_hits + kCcSlice - 1) / kCcSlice;
-  const dim3 grid((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_slices, max_blocks)));
-  hipLaunchKernelGGL(kcc_add, grid, dim3(kCcThreads), 0, (hipStream_t)stream, (const int32_t *)hits, n_hits, hit_off, nd, cls_off,
+  hipLaunchKernelGGL(kcc_add, dim3(grid_for(n_hits, kCcSlice, max_blocks)), dim3(kCcThreads), 0, (hipStream_t)stream, (const int32_t *)hits, n_hits, hit_off, nd, cls_off,
                      cls_ids, n_keys, n_classes, out);
 }
 
 void classcount_launch_fold_keys(const uint64_t *key_counts, uint32_t n_keys, const uint64_t *cls_off, const uint32_t *cls_ids,
                                  uint32_t *row, uint32_t max_blocks, void *stream) {
   if (!n_keys) return;
-  const uint64_t blocks = ((uint64_t)n_keys + kCcThreads - 1) / kCcThreads;
-  const dim3 grid((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(blocks, max_blocks)));
-  hipLaunchKernelGGL(kcc_fold_keys, grid, dim3(kCcThreads), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(kcc_fold_keys, dim3(grid_for(n_keys, kCcThreads, max_blocks)), dim3(kCcThreads), 0, (hipStream_t)stream,
                      reinterpret_cast<const unsigned long long *>(key_counts), n_keys, cls_off, cls_ids, row);
 }
 

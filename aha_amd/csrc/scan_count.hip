@@ -19,6 +19,7 @@
 #include "count_table.hpp"
 #include "devcommon.hpp"
 #include "image.hpp"
+#include "post_common.hpp"
 #include "unit.hpp"
 
 namespace aha {
@@ -79,9 +80,7 @@ __global__ __launch_bounds__(kCtThreads) void kc_visits(DevAut A, V2Args M, cons
       __syncthreads();  // (the table is clear; s_total of the group before is read)
       if (threadIdx.x < 64) {
         const uint64_t c = g * 64 + threadIdx.x;
-        uint32_t tot = c < M.n_chunks ? min(M.ev_cnt[c], stride) : 0u;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) tot += __shfl_xor(tot, d, 64);
+        const uint32_t tot = wave_sum(c < M.n_chunks ? min(M.ev_cnt[c], stride) : 0u);
         if (threadIdx.x == 0) s_total = tot;
       }
       __syncthreads();
@@ -135,7 +134,7 @@ __global__ __launch_bounds__(kCtThreads) void kc_chain(const uint2 *key_ln, uint
 void count_launch_visits(const DevAut &A, const V2Args &M, const uint2 *uend, unsigned long long *visits, uint32_t max_blocks,
                          void *stream) {
   const uint64_t units = uend ? (M.n_chunks + 63) / 64 : M.n_chunks;
-  const dim3 grid((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(units, max_blocks)));
+  const dim3 grid(post::grid_for(units, 1, max_blocks));
   if (uend)
     hipLaunchKernelGGL(kc_visits<kSrcUnit>, grid, dim3(kCtThreads), 0, (hipStream_t)stream, A, M, uend, visits);
   else
@@ -144,8 +143,7 @@ void count_launch_visits(const DevAut &A, const V2Args &M, const uint2 *uend, un
 
 void count_launch_chain(const uint2 *key_ln, uint32_t n_keys, const unsigned long long *visits, unsigned long long *out,
                         const unsigned long long *abortf, void *stream) {
-  const uint64_t blocks = ((uint64_t)n_keys + kCtThreads - 1) / kCtThreads;
-  const dim3 grid((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(blocks, 1024)));
+  const dim3 grid(post::grid_for(n_keys, kCtThreads, 1024));
   hipLaunchKernelGGL(kc_chain, grid, dim3(kCtThreads), 0, (hipStream_t)stream, key_ln, n_keys, visits, out, abortf);
 }
 

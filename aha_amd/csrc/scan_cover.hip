@@ -24,10 +24,13 @@
 #include "cover_span.hpp"
 #include "devcommon.hpp"
 #include "image.hpp"
+#include "post_common.hpp"
 #include "unit.hpp"
 
 namespace aha {
 namespace {
+
+using post::grid_for;
 
 constexpr int kCvThreads = 256;
 constexpr uint32_t kCvTileWords = 8192;                // 32 KiB of LDS
@@ -120,9 +123,7 @@ __global__ __launch_bounds__(kCvThreads) void kv_spans(DevAut A, V2Args M, const
       const uint32_t bb = M.unit_bb, bmask = (1u << bb) - 1u;
       for (uint64_t q = c0 / 64; q * 64 < c1; q++) {  // the traversal's groups of 64 chunks, all waves on each
         const uint64_t c = q * 64 + lane;
-        uint32_t total = c < M.n_chunks ? min(M.ev_cnt[c], stride) : 0u;  // (every wave sums the group's events for itself)
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) total += __shfl_xor(total, d, 64);
+        const uint32_t total = wave_sum(c < M.n_chunks ? min(M.ev_cnt[c], stride) : 0u);  // (every wave sums the group's events for itself)
         const uint32_t *src = M.evg + q * 64 * stride * 3;
         for (uint32_t i = threadIdx.x; i < total; i += kCvThreads) {
           const uint32_t x = src[(size_t)i * 3], y = src[(size_t)i * 3 + 1], z = src[(size_t)i * 3 + 2];
@@ -194,9 +195,7 @@ __device__ __forceinline__ uint64_t cv_popcount_range(const uint32_t *mask, uint
       cnt += (uint32_t)__popc(v);
     }
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
-  return cnt;
+  return wave_sum(cnt);
 }
 
 // doc_covered[d] = set bits of the document's range (documents are not word-aligned): a wave per document
@@ -214,19 +213,14 @@ __global__ __launch_bounds__(256) void kv_doc_covered(const uint32_t *mask, cons
 __global__ __launch_bounds__(256) void kv_total(const uint32_t *words, uint64_t n, unsigned long long *total) {
   uint64_t cnt = 0;
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) cnt += (uint32_t)__popc(words[i]);
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
+  cnt = wave_sum(cnt);
   if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(total, (unsigned long long)cnt);
-}
-
-uint32_t blocks_of(uint64_t items, uint32_t max_blocks) {
-  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + 255) / 256, max_blocks));
 }
 
 }  // namespace
 
 void cover_launch_clear(uint32_t *words, uint64_t n_words, const unsigned long long *abortf, uint32_t max_blocks, void *stream) {
-  hipLaunchKernelGGL(kv_clear, dim3(blocks_of((n_words + 3) / 4 + 8, max_blocks)), dim3(256), 0, (hipStream_t)stream, words, n_words,
+  hipLaunchKernelGGL(kv_clear, dim3(grid_for((n_words + 3) / 4 + 8, 256, max_blocks)), dim3(256), 0, (hipStream_t)stream, words, n_words,
                      abortf);
 }
 
@@ -238,7 +232,7 @@ void cover_launch_spans(const DevAut &A, const V2Args &M, const uint2 *uend, uin
   uint64_t G = std::max<uint64_t>(1, std::min<uint64_t>(kCvTileBytes / M.S, 256));
   if (uend) G = std::max<uint64_t>(64, G / 64 * 64);
   const uint64_t n_groups = (M.n_chunks + G - 1) / G;
-  const dim3 grid((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_groups, max_blocks)));
+  const dim3 grid(grid_for(n_groups, 1, max_blocks));
   if (uend)
     hipLaunchKernelGGL(kv_spans<kSrcUnit>, grid, dim3(kCvThreads), 0, s, A, M, uend, cdoc, mask, bit0, (uint32_t)G);
   else
@@ -247,18 +241,18 @@ void cover_launch_spans(const DevAut &A, const V2Args &M, const uint2 *uend, uin
 
 void cover_launch_redact(const uint8_t *src, uint8_t *dst, const uint32_t *mask, uint64_t n_bytes, uint8_t fill, uint32_t max_blocks,
                          void *stream) {
-  hipLaunchKernelGGL(kv_redact, dim3(blocks_of((n_bytes + 15) / 16, max_blocks)), dim3(256), 0, (hipStream_t)stream, src, dst, mask,
+  hipLaunchKernelGGL(kv_redact, dim3(grid_for((n_bytes + 15) / 16, 256, max_blocks)), dim3(256), 0, (hipStream_t)stream, src, dst, mask,
                      n_bytes, (uint32_t)fill);
 }
 
 void cover_launch_doc_covered(const uint32_t *mask, const uint64_t *doc_off, uint64_t n_docs, uint64_t *doc_covered,
                               uint32_t max_blocks, void *stream) {
-  hipLaunchKernelGGL(kv_doc_covered, dim3(blocks_of(n_docs * 64, max_blocks)), dim3(256), 0, (hipStream_t)stream, mask, doc_off, n_docs,
+  hipLaunchKernelGGL(kv_doc_covered, dim3(grid_for(n_docs * 64, 256, max_blocks)), dim3(256), 0, (hipStream_t)stream, mask, doc_off, n_docs,
                      reinterpret_cast<unsigned long long *>(doc_covered));
 }
 
 void cover_launch_total(const uint32_t *mask, uint64_t n_words, uint64_t *total, uint32_t max_blocks, void *stream) {
-  hipLaunchKernelGGL(kv_total, dim3(blocks_of(n_words, max_blocks)), dim3(256), 0, (hipStream_t)stream, mask, n_words,
+  hipLaunchKernelGGL(kv_total, dim3(grid_for(n_words, 256, max_blocks)), dim3(256), 0, (hipStream_t)stream, mask, n_words,
                      reinterpret_cast<unsigned long long *>(total));
 }
 

@@ -22,6 +22,7 @@
 
 #include "count_table.hpp"
 #include "image.hpp"
+#include "post_common.hpp"
 
 namespace aha {
 namespace {
@@ -32,12 +33,7 @@ constexpr uint32_t kDcPad = 0xFFFFFFFFu;  // above every key id: the sort's padd
 // exclusive prefix of v over the workgroup's 256 threads and the total; s_w: 4 words of LDS
 __device__ __forceinline__ uint32_t dc_block_scan(uint32_t v, uint32_t *s_w, uint32_t *total) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t o = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += o;
-  }
+  const uint32_t inc = wave_incl_scan(v);
   __syncthreads();  // (s_w of the round before is read)
   if (lane == 63) s_w[wave] = inc;
   __syncthreads();

@@ -41,9 +41,12 @@
 #include "count_table.hpp"
 #include "cover_span.hpp"
 #include "feed.hpp"
+#include "post_common.hpp"
 
 namespace aha {
 namespace {
+
+using post::grid_for;
 
 constexpr int kFdThreads = 256;
 constexpr int kFdScanThreads = 1024;
@@ -98,34 +101,18 @@ __device__ __forceinline__ uint64_t scan_item(const FeedArgs &F, uint64_t i) {
   return kMode == 0 ? win_len(F, i) : (kMode == 1 ? kept_hits(F, i) : true_hits(F, i));
 }
 
-// one block of kFdScanThreads: exclusive scan of n per-piece values into out[0..n], out[n] = the total.  Each thread takes a
-// contiguous run; the run sums are scanned in LDS.
+// one block of kFdScanThreads: exclusive scan of n per-piece values into out[0..n], out[n] = the total
 template <int kMode>
 __global__ void __launch_bounds__(kFdScanThreads) kfd_scan(FeedArgs F) {
   __shared__ uint64_t s[kFdScanThreads];
   if (*F.verdict) return;
   const uint64_t n = kMode == 0 ? 3 * F.D : F.D;
   uint64_t *out = kMode == 0 ? F.woff : F.pho;  // (kMode 2: the true hits per piece of a call on a feed with a separator filter)
-  const uint64_t per = (n + kFdScanThreads - 1) / kFdScanThreads;
-  const uint64_t i0 = min(n, threadIdx.x * per), i1 = min(n, i0 + per);
-  uint64_t mine = 0;
-  for (uint64_t i = i0; i < i1; i++) mine += scan_item<kMode>(F, i);
-  s[threadIdx.x] = mine;
-  __syncthreads();
-  for (int k = 1; k < kFdScanThreads; k <<= 1) {
-    const uint64_t v = threadIdx.x >= (unsigned)k ? s[threadIdx.x - k] : 0;
-    __syncthreads();
-    s[threadIdx.x] += v;
-    __syncthreads();
-  }
-  uint64_t run = s[threadIdx.x] - mine;
-  for (uint64_t i = i0; i < i1; i++) {
-    out[i] = run;
-    run += scan_item<kMode>(F, i);
-  }
+  const uint64_t total =
+      block_run_scan<kFdScanThreads>(n, [&](uint64_t i) { return scan_item<kMode>(F, i); }, [&](uint64_t i, uint64_t run) { out[i] = run; }, s);
   if (threadIdx.x == kFdScanThreads - 1) {
-    out[n] = s[threadIdx.x];
-    if (kMode == 0) *F.win_total = s[threadIdx.x];
+    out[n] = total;
+    if (kMode == 0) *F.win_total = total;
   }
 }
 
@@ -383,17 +370,11 @@ __global__ void __launch_bounds__(kFdThreads) kfd_cover_windows(FeedArgs F) {
       const int lead = __ffsll(todo) - 1;
       const uint64_t dl = (uint64_t)__shfl((uint32_t)d, lead, 64) | (uint64_t)__shfl((uint32_t)(d >> 32), lead, 64) << 32;
       const bool mine = bk != 0 && d == dl;
-      uint32_t v = mine ? bk : 0u;
-#pragma unroll
-      for (int k = 32; k >= 1; k >>= 1) v = max(v, (uint32_t)__shfl_xor(v, k, 64));
+      const uint32_t v = wave_max(mine ? bk : 0u);
       if (lane == lead) atomicMax(&F.back[dl], v);
       todo &= ~__ballot(mine);
     }
   }
-}
-
-uint32_t grid_for(uint64_t units, uint64_t per_block, uint32_t cap) {
-  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((units + per_block - 1) / per_block, cap));
 }
 
 }  // namespace

@@ -25,9 +25,12 @@
 #include <algorithm>
 
 #include "feed.hpp"
+#include "post_common.hpp"
 
 namespace aha {
 namespace {
+
+using post::grid_for;
 
 constexpr int kFgThreads = 256;
 constexpr int kFgScanThreads = 1024;
@@ -44,31 +47,15 @@ __device__ __forceinline__ uint64_t fg_win_len(const FeedArgs &F, const FeedGrep
   return part == 0 ? c + g : (part == 1 ? c : g);
 }
 
-// one block: the exclusive scan of the 3 D window lengths into F.woff[0 .. 3 D], the total into *F.win_total too.  Each thread
-// takes a contiguous run; the run sums are scanned in LDS (scan_feed.hip kfd_scan).
+// one block: the exclusive scan of the 3 D window lengths into F.woff[0 .. 3 D], the total into *F.win_total too
 __global__ void __launch_bounds__(kFgScanThreads) kfg_layout(FeedArgs F, FeedGrepArgs G) {
   __shared__ uint64_t s[kFgScanThreads];
   const uint64_t n = 3 * F.D;
-  const uint64_t per = (n + kFgScanThreads - 1) / kFgScanThreads;
-  const uint64_t i0 = min(n, threadIdx.x * per), i1 = min(n, i0 + per);
-  uint64_t mine = 0;
-  for (uint64_t i = i0; i < i1; i++) mine += fg_win_len(F, G, i);
-  s[threadIdx.x] = mine;
-  __syncthreads();
-  for (int k = 1; k < kFgScanThreads; k <<= 1) {
-    const uint64_t v = threadIdx.x >= (unsigned)k ? s[threadIdx.x - k] : 0;
-    __syncthreads();
-    s[threadIdx.x] += v;
-    __syncthreads();
-  }
-  uint64_t run = s[threadIdx.x] - mine;
-  for (uint64_t i = i0; i < i1; i++) {
-    F.woff[i] = run;
-    run += fg_win_len(F, G, i);
-  }
+  const uint64_t total =
+      block_run_scan<kFgScanThreads>(n, [&](uint64_t i) { return fg_win_len(F, G, i); }, [&](uint64_t i, uint64_t run) { F.woff[i] = run; }, s);
   if (threadIdx.x == kFgScanThreads - 1) {
-    F.woff[n] = s[threadIdx.x];
-    *F.win_total = s[threadIdx.x];
+    F.woff[n] = total;
+    *F.win_total = total;
   }
 }
 
@@ -179,10 +166,6 @@ __global__ void __launch_bounds__(kFgThreads) kfg_commit(FeedArgs F, FeedGrepArg
     if (G.hold) G.hold[d] = (uint32_t)hold;
     if (G.rec_bases) G.rec_bases[d] = q.recs;
   }
-}
-
-uint32_t grid_for(uint64_t units, uint64_t per_block, uint32_t cap) {
-  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((units + per_block - 1) / per_block, std::max<uint32_t>(cap, 1)));
 }
 
 }  // namespace

@@ -5,7 +5,7 @@
 // sequence T from n0 to n1 bytes; the call finds the cursor at c0 and leaves it at c1 (feedsel_cursor, feed.hpp), and every hit
 // it settles lies inside [c0, c1).  The piece's result is T[c0 .. c1) with those hits replaced, so the call stages that text:
 //   kfr_layout   per piece hold0 = n0 - c0, the staged length c1 - c0 = hold0 + |P| - hold1 with hold1 = n1 - c1; ext_off = the
-//                exclusive scan of the lengths, bias = ext_off + hold0.  One block, the form of kfs_layout.
+//                exclusive scan of the lengths, bias = ext_off + hold0.  One block (block_run_scan, post_common.hpp).
 //   kfr_stage    ext[ext_off[d] ..) = the last hold0 bytes of the sequence's context -- old[lc - hold0 .. lc) of its current
 //                bank, lc = min(W, n0): the caller's bytes on a folded handle too (kfd_commit fills the banks from the caller's
 //                text) --, then the piece's bytes up to c1.  Driven by the staged positions, as krp_copy by the output: a wave
@@ -21,25 +21,15 @@
 #include <algorithm>
 
 #include "feed.hpp"
+#include "post_common.hpp"
 
 namespace aha {
 namespace {
 
+using post::grid_for;
+
 constexpr int kFrScanThreads = 1024;
 constexpr uint64_t kFrTile = 1024;  // staged bytes of one wave's tile: 16 per lane
-
-// the largest d in [0, n) with off[d] <= x (off ascends, off[0] = 0 <= x): pieces that stage nothing are stepped over
-__device__ __forceinline__ uint64_t fr_owner(const uint64_t *off, uint64_t n, uint64_t x) {
-  uint64_t lo = 1, hi = n;
-  while (lo < hi) {
-    const uint64_t mid = (lo + hi) >> 1;
-    if (off[mid] <= x)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  return lo - 1;
-}
 
 // what piece d stages: -> hold0 (its return value is the staged length c1 - c0)
 __device__ __forceinline__ uint64_t fr_piece(const FeedArgs &F, const FeedSelArgs &S, uint64_t d, uint32_t *hold0) {
@@ -55,36 +45,23 @@ __device__ __forceinline__ uint64_t fr_piece(const FeedArgs &F, const FeedSelArg
   return h0 + L - (n1 - min(c1, n1));
 }
 
-// one block: hold0[d], ext_off[0 .. D] = the exclusive scan of the staged lengths, bias.  Each thread takes a contiguous run
-// of pieces.
+// one block: hold0[d], ext_off[0 .. D] = the exclusive scan of the staged lengths, bias
 __global__ void __launch_bounds__(kFrScanThreads) kfr_layout(FeedArgs F, FeedSelArgs S, FeedRepArgs R) {
   __shared__ uint64_t s[kFrScanThreads];
-  const uint64_t n = F.D;
-  const uint64_t per = (n + kFrScanThreads - 1) / kFrScanThreads;
-  const uint64_t i0 = min(n, threadIdx.x * per), i1 = min(n, i0 + per);
-  uint64_t mine = 0;
-  for (uint64_t d = i0; d < i1; d++) {
-    uint32_t h0;
-    mine += fr_piece(F, S, d, &h0);
-    R.hold0[d] = h0;
-  }
-  s[threadIdx.x] = mine;
-  __syncthreads();
-  for (int k = 1; k < kFrScanThreads; k <<= 1) {
-    const uint64_t v = threadIdx.x >= (unsigned)k ? s[threadIdx.x - k] : 0;
-    __syncthreads();
-    s[threadIdx.x] += v;
-    __syncthreads();
-  }
-  uint64_t run = s[threadIdx.x] - mine;
-  for (uint64_t d = i0; d < i1; d++) {
-    uint32_t h0;
-    const uint64_t len = fr_piece(F, S, d, &h0);
-    R.ext_off[d] = run;
-    R.bias[d] = run + h0;
-    run += len;
-  }
-  if (threadIdx.x == kFrScanThreads - 1) R.ext_off[n] = R.bias[n] = s[threadIdx.x];
+  const uint64_t total = block_run_scan<kFrScanThreads>(
+      F.D,
+      [&](uint64_t d) {
+        uint32_t h0;
+        const uint64_t len = fr_piece(F, S, d, &h0);
+        R.hold0[d] = h0;
+        return len;
+      },
+      [&](uint64_t d, uint64_t run) {
+        R.ext_off[d] = run;
+        R.bias[d] = run + R.hold0[d];  // (this lane's own store)
+      },
+      s);
+  if (threadIdx.x == kFrScanThreads - 1) R.ext_off[F.D] = R.bias[F.D] = total;
 }
 
 // where piece d's staged bytes come from: the first hold0 of them from the context row, the rest from the piece
@@ -110,7 +87,7 @@ __device__ __forceinline__ FrSrc fr_src(const FeedArgs &F, const FeedRepArgs &R,
 
 // staged bytes [q, q + cnt), cnt <= 16, piece by piece; one 16-byte store where the lane has all 16 (ext + q is aligned)
 __device__ __forceinline__ void fr_lane(const FeedArgs &F, const FeedRepArgs &R, uint64_t q, uint32_t cnt) {
-  uint64_t d = fr_owner(R.ext_off, F.D, q);
+  uint64_t d = owner_of(R.ext_off, F.D, q);  // (ext_off[0] = 0; pieces that stage nothing are stepped over)
   FrSrc s = fr_src(F, R, d);
   uint32_t w[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
@@ -143,7 +120,7 @@ __global__ __launch_bounds__(256) void kfr_stage(FeedArgs F, FeedRepArgs R) {
     bool fast = false;
     const uint8_t *from = nullptr;
     if (q0 + kFrTile <= total) {
-      const uint64_t d = fr_owner(R.ext_off, F.D, q0);
+      const uint64_t d = owner_of(R.ext_off, F.D, q0);
       const uint64_t b0 = R.bias[d];  // the piece's own bytes start here
       fast = q0 >= b0 && q0 + kFrTile <= R.ext_off[d + 1];
       from = F.text + F.off[d] + (q0 - b0);
@@ -186,7 +163,7 @@ void feedrep_launch_layout(const FeedArgs &F, const FeedSelArgs &S, const FeedRe
 void feedrep_launch_stage(const FeedArgs &F, const FeedRepArgs &R, uint64_t max_bytes, uint32_t max_blocks, void *stream) {
   if (!max_bytes || !F.D) return;
   const uint64_t n_tiles = (max_bytes + kFrTile - 1) / kFrTile;
-  const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n_tiles + 3) / 4, max_blocks));
+  const uint32_t grid = grid_for(n_tiles, 4, max_blocks);
   hipLaunchKernelGGL(kfr_stage, dim3(grid), dim3(256), 0, (hipStream_t)stream, F, R);
 }
 }  // namespace aha

@@ -31,57 +31,29 @@
 #include <algorithm>
 
 #include "feed.hpp"
+#include "post_common.hpp"
 
 namespace aha {
 namespace {
 
+using post::grid_for;
+
 constexpr int kFsThreads = 256;
 constexpr int kFsScanThreads = 1024;
-constexpr uint32_t kFsBlockWords = 64;  // mask words of one rank block (scan_select.hip kSlBlockWords)
-
-__device__ __forceinline__ bool fs_bit(const uint32_t *mask, uint64_t p) { return (mask[p >> 5] >> (uint32_t)(p & 31)) & 1u; }
-
-// the largest d in [0, n) with off[d] <= x (off ascends, off[0] = 0)
-__device__ __forceinline__ uint64_t fs_owner(const uint64_t *off, uint64_t n, uint64_t x) {
-  uint64_t lo = 1, hi = n;
-  while (lo < hi) {
-    const uint64_t mid = (lo + hi) >> 1;
-    if (off[mid] <= x)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  return lo - 1;
-}
-
 __device__ __forceinline__ uint64_t fs_back(const FeedArgs &F, const FeedSelArgs &S, uint64_t d) { return min((uint64_t)F.W, S.n0[d]); }
 
-// one block: n0[d], eoff[0 .. D] = the exclusive scan of min(W, n0[d]) + |P_d|.  Each thread takes a contiguous run of pieces.
+// one block: n0[d], eoff[0 .. D] = the exclusive scan of min(W, n0[d]) + |P_d|
 __global__ void __launch_bounds__(kFsScanThreads) kfs_layout(FeedArgs F, FeedSelArgs S) {
   __shared__ uint64_t s[kFsScanThreads];
-  const uint64_t n = F.D;
-  const uint64_t per = (n + kFsScanThreads - 1) / kFsScanThreads;
-  const uint64_t i0 = min(n, threadIdx.x * per), i1 = min(n, i0 + per);
-  uint64_t mine = 0;
-  for (uint64_t d = i0; d < i1; d++) {
-    const uint64_t n0 = F.seqs[F.ids[d]].bytes;
-    S.n0[d] = n0;
-    mine += min((uint64_t)F.W, n0) + (F.off[d + 1] - F.off[d]);
-  }
-  s[threadIdx.x] = mine;
-  __syncthreads();
-  for (int k = 1; k < kFsScanThreads; k <<= 1) {
-    const uint64_t v = threadIdx.x >= (unsigned)k ? s[threadIdx.x - k] : 0;
-    __syncthreads();
-    s[threadIdx.x] += v;
-    __syncthreads();
-  }
-  uint64_t run = s[threadIdx.x] - mine;
-  for (uint64_t d = i0; d < i1; d++) {
-    S.eoff[d] = run;
-    run += min((uint64_t)F.W, S.n0[d]) + (F.off[d + 1] - F.off[d]);
-  }
-  if (threadIdx.x == kFsScanThreads - 1) S.eoff[n] = s[threadIdx.x];
+  const uint64_t total = block_run_scan<kFsScanThreads>(
+      F.D,
+      [&](uint64_t d) {
+        const uint64_t n0 = F.seqs[F.ids[d]].bytes;
+        S.n0[d] = n0;
+        return min((uint64_t)F.W, n0) + (F.off[d + 1] - F.off[d]);
+      },
+      [&](uint64_t d, uint64_t run) { S.eoff[d] = run; }, s);
+  if (threadIdx.x == kFsScanThreads - 1) S.eoff[F.D] = total;
 }
 
 // a thread per piece and tail entry
@@ -104,7 +76,7 @@ __global__ void __launch_bounds__(kFsThreads) kfs_longest(FeedArgs F, FeedSelArg
     const int64_t st = S.hits[3 * i], en = S.hits[3 * i + 1];
     const uint32_t value = (uint32_t)S.hits[3 * i + 2];
     if (en <= st) continue;
-    const uint64_t d = fs_owner(S.pho, F.D, i);
+    const uint64_t d = owner_of(S.pho, F.D, i);
     const int64_t wb = (int64_t)fs_back(F, S, d), x = st + wb;
     const uint64_t e0 = S.eoff[d], E = S.eoff[d + 1] - e0;
     if (x < 0 || (uint64_t)(x + (en - st)) > E) continue;  // (never: a hit lies inside its piece's extended positions)
@@ -117,8 +89,8 @@ __global__ void __launch_bounds__(kFsThreads) kfs_walk(FeedArgs F, FeedSelArgs S
   const uint64_t nb = S.NE;
   for (uint64_t p0 = blockIdx.x * (uint64_t)kFsThreads + threadIdx.x; p0 < nb; p0 += (uint64_t)gridDim.x * kFsThreads) {
     if (!S.L[p0]) continue;
-    if (p0 && !fs_bit(S.start, p0) && fs_bit(S.cover, p0 - 1)) continue;  // inside a run: its walker comes by
-    const uint64_t d = fs_owner(S.eoff, F.D, p0);
+    if (p0 && !bit_at(S.start, p0) && bit_at(S.cover, p0 - 1)) continue;  // inside a run: its walker comes by
+    const uint64_t d = owner_of(S.eoff, F.D, p0);
     const uint64_t e0 = S.eoff[d], e1 = S.eoff[d + 1], E = e1 - e0;
     const uint64_t front = e0 + (S.final ? E : (E > F.W ? E - F.W : 0));
     uint64_t p = p0, last = 0;
@@ -127,41 +99,24 @@ __global__ void __launch_bounds__(kFsThreads) kfs_walk(FeedArgs F, FeedSelArgs S
       p += (uint64_t)(S.L[p] >> 32);
       last = p;
       // the next start of the run: covered bytes without a hit of their own are stepped over
-      while (p < e1 && fs_bit(S.cover, p) && !S.L[p]) p++;
-      if (p >= e1 || !fs_bit(S.cover, p)) break;
+      while (p < e1 && bit_at(S.cover, p) && !S.L[p]) p++;
+      if (p >= e1 || !bit_at(S.cover, p)) break;
     }
     if (last) atomicMax(S.cend + d, (unsigned long long)(last - e0));
   }
 }
 
-// the selection in position order: a wave per rank block, a lane per word (ksl_emit, with the piece's own origin)
+// the selection in position order (ksl_emit, with the piece's own origin)
 __global__ void __launch_bounds__(kFsThreads) kfs_emit(FeedArgs F, FeedSelArgs S) {
-  const int lane = threadIdx.x & 63;
-  const uint64_t n_words = (S.NE + 31) / 32, n_blk = (n_words + kFsBlockWords - 1) / kFsBlockWords;
-  const uint64_t wave = ((uint64_t)blockIdx.x * kFsThreads + threadIdx.x) >> 6, n_waves = (uint64_t)gridDim.x * (kFsThreads / 64);
-  for (uint64_t b = wave; b < n_blk; b += n_waves) {
-    const uint64_t w = b * kFsBlockWords + lane;
-    uint32_t bits = w < n_words ? S.select[w] : 0u;
-    const uint32_t c = (uint32_t)__popc(bits);
-    uint32_t incl = c;  // set bits of the lanes up to this one
-#pragma unroll
-    for (int k = 1; k < 64; k <<= 1) {
-      const uint32_t v = __shfl_up(incl, k, 64);
-      if (lane >= k) incl += v;
-    }
-    uint64_t at = S.blk[b] + (incl - c);
-    while (bits) {
-      const uint64_t p = w * 32 + (uint32_t)__ffs(bits) - 1u;
-      bits &= bits - 1u;
-      const unsigned long long v = S.L[p];
-      const uint64_t d = fs_owner(S.eoff, F.D, p);
-      const int64_t st = (int64_t)(p - S.eoff[d]) - (int64_t)fs_back(F, S, d);
-      S.out[at * 3] = (int32_t)st;
-      S.out[at * 3 + 1] = (int32_t)(st + (int64_t)(v >> 32));
-      S.out[at * 3 + 2] = (int32_t)(uint32_t)v;
-      at++;
-    }
-  }
+  for_ranked_bits<kFsThreads>(S.select, (S.NE + 31) / 32, rank_blocks(S.NE), S.blk, [&](uint64_t w, uint32_t i, uint64_t at) {
+    const uint64_t p = w * 32 + i;
+    const unsigned long long v = S.L[p];
+    const uint64_t d = owner_of(S.eoff, F.D, p);
+    const int64_t st = (int64_t)(p - S.eoff[d]) - (int64_t)fs_back(F, S, d);
+    S.out[at * 3] = (int32_t)st;
+    S.out[at * 3 + 1] = (int32_t)(st + (int64_t)(v >> 32));
+    S.out[at * 3 + 2] = (int32_t)(uint32_t)v;
+  });
 }
 
 // a workgroup per piece, behind kfd_commit (F.seqs[id].bytes is the new length there; n0 is the old one)
@@ -189,10 +144,6 @@ __global__ void __launch_bounds__(kFsThreads) kfs_commit(FeedArgs F, FeedSelArgs
   }
 }
 
-uint32_t grid_for(uint64_t units, uint64_t per_block, uint32_t cap) {
-  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((units + per_block - 1) / per_block, cap));
-}
-
 }  // namespace
 
 void feedsel_launch_layout(const FeedArgs &F, const FeedSelArgs &S, void *stream) {
@@ -210,8 +161,7 @@ void feedsel_launch_walk(const FeedArgs &F, const FeedSelArgs &S, uint32_t max_b
 }
 
 void feedsel_launch_emit(const FeedArgs &F, const FeedSelArgs &S, uint32_t max_blocks, void *stream) {
-  const uint64_t n_blk = ((S.NE + 31) / 32 + kFsBlockWords - 1) / kFsBlockWords;
-  hipLaunchKernelGGL(kfs_emit, dim3(grid_for(n_blk * 64, kFsThreads, max_blocks)), dim3(kFsThreads), 0, (hipStream_t)stream, F, S);
+  hipLaunchKernelGGL(kfs_emit, dim3(grid_for(rank_blocks(S.NE) * 64, kFsThreads, max_blocks)), dim3(kFsThreads), 0, (hipStream_t)stream, F, S);
 }
 
 void feedsel_launch_commit(const FeedArgs &F, const FeedSelArgs &S, void *stream) {

@@ -10,7 +10,7 @@
 //   kfp_flag          one bit per true hit: end < |P|, the byte at `end` passes, and the byte at start - 1 -- in the piece, or in
 //                     the sequence's context bank for a negative index -- passes or the hit starts the sequence.  A lane per
 //                     hit, a ballot per wave, one 64-bit store per 64 hits: no atomics, no clear in front
-//   (select_launch_rank, scan_select.hip: the kept hits before every 2048, the total behind them -- the host's capacity check)
+//   (select_launch_rank, scan_select.hip: the kept hits before every rank block of 2048, the total behind them -- the host's capacity check)
 //   kfp_compact       the kept hits into the caller's buffer in the order of the list: a lane per true hit, a wave per mask word
 //   (select_launch_rank_docs: piece_hit_offsets = the rank at every piece's first true hit)
 //   kfp_count         a count call: the kept hits' values into the feed's K-word vector, summed per workgroup in the LDS table
@@ -26,29 +26,18 @@
 #include "count_table.hpp"
 #include "feed.hpp"
 #include "fold.hpp"
+#include "post_common.hpp"
 
 namespace aha {
 namespace {
 
+using post::grid_for;
+
 constexpr int kFpThreads = 256;
-constexpr uint32_t kFpBlockWords = 64;  // 32-bit mask words of one rank block (scan_select.hip's kSlBlockWords)
 
 __device__ __forceinline__ bool fp_pass(const FeedSepArgs &P, uint8_t c) {
   const uint32_t b = P.fold ? fold8(c) : c;
   return !((P.blocked[b >> 5] >> (b & 31u)) & 1u);
-}
-
-// the largest d in [0, n) with off[d] <= x (off ascends, off[0] = 0)
-__device__ __forceinline__ uint64_t fp_owner(const uint64_t *off, uint64_t n, uint64_t x) {
-  uint64_t lo = 1, hi = n;
-  while (lo < hi) {
-    const uint64_t mid = (lo + hi) >> 1;
-    if (off[mid] <= x)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  return lo - 1;
 }
 
 __global__ void __launch_bounds__(kFpThreads) kfp_flag(FeedArgs F, FeedSepArgs P) {
@@ -56,10 +45,10 @@ __global__ void __launch_bounds__(kFpThreads) kfp_flag(FeedArgs F, FeedSepArgs P
   const uint64_t n = P.n_true;
   for (uint64_t i0 = blockIdx.x * (uint64_t)kFpThreads + (threadIdx.x & ~63u); i0 < n; i0 += (uint64_t)gridDim.x * kFpThreads) {
     const uint64_t i = i0 + lane;
-    const uint64_t d0 = fp_owner(P.tho, F.D, i0);  // (the wave's hits lie in few pieces: one search serves the lanes of the first)
+    const uint64_t d0 = owner_of(P.tho, F.D, i0);  // (the wave's hits lie in few pieces: one search serves the lanes of the first)
     bool keep = false;
     if (i < n) {
-      const uint64_t d = i < P.tho[d0 + 1] ? d0 : fp_owner(P.tho, F.D, i);
+      const uint64_t d = i < P.tho[d0 + 1] ? d0 : owner_of(P.tho, F.D, i);
       const uint64_t a = F.off[d], L = F.off[d + 1] - a;
       const int64_t st = P.hits[3 * i], en = P.hits[3 * i + 1];
       if (en >= 0 && (uint64_t)en < L && fp_pass(P, F.text[a + (uint64_t)en])) {
@@ -87,10 +76,10 @@ __global__ void __launch_bounds__(kFpThreads) kfp_flag_finish(FeedArgs F, FeedSe
   const uint64_t n = P.n_true;
   for (uint64_t i0 = blockIdx.x * (uint64_t)kFpThreads + (threadIdx.x & ~63u); i0 < n; i0 += (uint64_t)gridDim.x * kFpThreads) {
     const uint64_t i = i0 + lane;
-    const uint64_t d0 = fp_owner(P.tho, F.D, i0);  // (the wave's hits lie in few pieces: one search serves the lanes of the first)
+    const uint64_t d0 = owner_of(P.tho, F.D, i0);  // (the wave's hits lie in few pieces: one search serves the lanes of the first)
     bool keep = false;
     if (i < n) {
-      const uint64_t d = i < P.tho[d0 + 1] ? d0 : fp_owner(P.tho, F.D, i);
+      const uint64_t d = i < P.tho[d0 + 1] ? d0 : owner_of(P.tho, F.D, i);
       const uint64_t w0 = F.woff[d];
       const int64_t lc = (int64_t)(F.woff[d + 1] - w0);
       const int64_t st = P.hits[3 * i], en = P.hits[3 * i + 1];
@@ -117,10 +106,8 @@ __global__ void __launch_bounds__(kFpThreads) kfp_compact(FeedSepArgs P) {
     const uint64_t w = i0 >> 6;
     const unsigned long long m = P.keep[w];
     if (!m) continue;  // (wave-uniform)
-    const uint64_t b = w / (kFpBlockWords / 2), w0 = b * (kFpBlockWords / 2);
-    uint32_t c = (lane < (int)(kFpBlockWords / 2) && w0 + (uint64_t)lane < w) ? (uint32_t)__popcll(P.keep[w0 + lane]) : 0u;
-#pragma unroll
-    for (int k = 32; k >= 1; k >>= 1) c += __shfl_xor(c, k, 64);
+    const uint64_t b = w / (kRankBlockWords / 2), w0 = b * (kRankBlockWords / 2);
+    const uint32_t c = wave_sum((lane < (int)(kRankBlockWords / 2) && w0 + (uint64_t)lane < w) ? (uint32_t)__popcll(P.keep[w0 + lane]) : 0u);
     if ((m >> lane) & 1ull) {
       const uint64_t i = i0 + lane;
       const uint64_t at = P.blk[b] + c + (uint64_t)__popcll(m & ((1ull << lane) - 1ull));
@@ -176,22 +163,18 @@ __global__ void __launch_bounds__(kFpThreads) kfp_restart(FeedArgs F, FeedSepArg
   }
 }
 
-uint32_t blocks_of(uint64_t items, uint32_t max_blocks) {
-  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + kFpThreads - 1) / kFpThreads, max_blocks));
-}
-
 }  // namespace
 
 void feedsep_launch_flag(const FeedArgs &F, const FeedSepArgs &P, uint32_t max_blocks, void *stream) {
-  hipLaunchKernelGGL(kfp_flag, dim3(blocks_of(P.n_true, max_blocks)), dim3(kFpThreads), 0, (hipStream_t)stream, F, P);
+  hipLaunchKernelGGL(kfp_flag, dim3(grid_for(P.n_true, kFpThreads, max_blocks)), dim3(kFpThreads), 0, (hipStream_t)stream, F, P);
 }
 
 void feedsep_launch_flag_finish(const FeedArgs &F, const FeedSepArgs &P, uint32_t max_blocks, void *stream) {
-  hipLaunchKernelGGL(kfp_flag_finish, dim3(blocks_of(P.n_true, max_blocks)), dim3(kFpThreads), 0, (hipStream_t)stream, F, P);
+  hipLaunchKernelGGL(kfp_flag_finish, dim3(grid_for(P.n_true, kFpThreads, max_blocks)), dim3(kFpThreads), 0, (hipStream_t)stream, F, P);
 }
 
 void feedsep_launch_compact(const FeedSepArgs &P, bool finish, uint32_t max_blocks, void *stream) {
-  const dim3 grid(blocks_of(P.n_true, max_blocks));
+  const dim3 grid(grid_for(P.n_true, kFpThreads, max_blocks));
   if (finish)
     hipLaunchKernelGGL(kfp_compact<true>, grid, dim3(kFpThreads), 0, (hipStream_t)stream, P);
   else
@@ -200,16 +183,16 @@ void feedsep_launch_compact(const FeedSepArgs &P, bool finish, uint32_t max_bloc
 
 void feedsep_launch_count(const FeedArgs &F, const FeedSepArgs &P, uint32_t max_blocks, void *stream) {
   // (a table of 48 KiB per workgroup: at least 16 Ki hits each)
-  const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((P.n_true + 16383) / 16384, std::min<uint32_t>(max_blocks, 1024u)));
+  const uint32_t grid = grid_for(P.n_true, 16384, std::min<uint32_t>(max_blocks, 1024u));
   hipLaunchKernelGGL(kfp_count, dim3(grid), dim3(kFpThreads), 0, (hipStream_t)stream, F, P);
 }
 
 void feedsep_launch_count_finish(const FeedArgs &F, uint32_t max_blocks, void *stream) {
-  hipLaunchKernelGGL(kfp_count_finish, dim3(blocks_of(F.K, std::min<uint32_t>(max_blocks, 1024u))), dim3(kFpThreads), 0, (hipStream_t)stream, F);
+  hipLaunchKernelGGL(kfp_count_finish, dim3(grid_for(F.K, kFpThreads, std::min<uint32_t>(max_blocks, 1024u))), dim3(kFpThreads), 0, (hipStream_t)stream, F);
 }
 
 void feedsep_launch_restart(const FeedArgs &F, const FeedSepArgs &P, void *stream) {
-  hipLaunchKernelGGL(kfp_restart, dim3(blocks_of(F.D, 1024u)), dim3(kFpThreads), 0, (hipStream_t)stream, F, P);
+  hipLaunchKernelGGL(kfp_restart, dim3(grid_for(F.D, kFpThreads, 1024u)), dim3(kFpThreads), 0, (hipStream_t)stream, F, P);
 }
 
 }  // namespace aha

@@ -1,5 +1,6 @@
 // scan_grep.hip -- the records and grep paths (aha_ac_records_batch*, aha_ac_grep_batch*).
-// Records: one pass over the text finds where records end; the rank of that mask (scan_select.hip's ranker) numbers them.
+// Records: one pass over the text finds where records end; the rank of that mask (select_launch_rank) numbers them.  The
+// ranked masks here are walked by post_common.hpp's for_ranked_bits.
 //   kgr_ends         the record-end mask, one bit per text byte: bit p = (corpus[p] == delim).  A lane owns one mask word, 32
 //                    text bytes, as two aligned 16-byte loads.  The corpus may start anywhere: the loads are aligned to the
 //                    ADDRESS, so the words they give are `head` bits behind the mask's words (head = the bytes in front of
@@ -8,7 +9,7 @@
 //                    [corpus, corpus + N) is touched.
 //   kgr_doc_ends     a lane per document: a document's end is a record's end, bit doc_offsets[d] - 1 (a boundary behind a
 //                    delimiter sets a set bit: counted once; an empty document sets its predecessor's bit again).
-//   kgr_emit_ends    every set bit p in position order: rec_offsets[rank + 1] = p + 1; a wave per rank block, a lane per word.
+//   kgr_emit_ends    every set bit p in position order: rec_offsets[rank + 1] = p + 1.
 // Grep: hits per document (the count call) -> which documents stay -> the dropped runs as "deleted hits" for replace's copy.
 //   kgr_flag         a lane per document, three masks over documents by wave ballot: keep; S = dropped and the predecessor
 //                    is kept or there is none (a run of dropped documents starts); T = dropped and the successor is kept or
@@ -25,11 +26,12 @@
 #include <algorithm>
 
 #include "image.hpp"
+#include "post_common.hpp"
 
 namespace aha {
 namespace {
 
-constexpr uint32_t kGrBlockWords = 64;  // mask words of one rank block (scan_select.hip kSlBlockWords): a wave, a word per lane
+using post::grid_for;
 
 // bit k = (byte k of w == the byte b4 repeats), k in [0, 4)
 __device__ __forceinline__ uint32_t gr_eq4(uint32_t w, uint32_t b4) {
@@ -90,32 +92,10 @@ __global__ __launch_bounds__(256) void kgr_doc_ends(const uint64_t *doc_off, uin
   }
 }
 
-// the set bits before this lane's word of block b, from the block's own words: the exclusive scan over the wave
-__device__ __forceinline__ uint32_t gr_before(uint32_t c, int lane) {
-  uint32_t incl = c;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t v = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += v;
-  }
-  return incl - c;
-}
-
 __global__ __launch_bounds__(256) void kgr_emit_ends(const uint32_t *mask, uint64_t n_words, uint64_t n_blk, const unsigned long long *blk,
                                                      unsigned long long *rec_off) {
-  const int lane = threadIdx.x & 63;
-  const uint64_t wave = ((uint64_t)blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = (uint64_t)gridDim.x * 4;
-  if (wave == 0 && lane == 0) rec_off[0] = 0;
-  for (uint64_t b = wave; b < n_blk; b += n_waves) {
-    const uint64_t w = b * kGrBlockWords + lane;
-    uint32_t bits = w < n_words ? mask[w] : 0u;
-    uint64_t at = blk[b] + gr_before((uint32_t)__popc(bits), lane);
-    while (bits) {
-      const uint64_t p = w * 32 + (uint32_t)__ffs(bits) - 1u;
-      bits &= bits - 1u;
-      rec_off[++at] = p + 1;
-    }
-  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) rec_off[0] = 0;
+  for_ranked_bits(mask, n_words, n_blk, blk, [&](uint64_t w, uint32_t i, uint64_t at) { rec_off[at + 1] = w * 32 + i + 1; });
 }
 
 // dho[0 .. D]: the documents' hit offsets.  keep / S / T: ceil(D / 32) words each, whole words are written
@@ -150,25 +130,8 @@ __global__ __launch_bounds__(256) void kgr_flag(const uint64_t *dho, uint64_t n_
 __global__ __launch_bounds__(256) void kgr_runs(const uint32_t *S, const uint32_t *T, uint64_t n_words, uint64_t n_blk,
                                                 const unsigned long long *blk_s, const unsigned long long *blk_t, const uint64_t *doc_off,
                                                 uint64_t *start, long long *end) {
-  const int lane = threadIdx.x & 63;
-  const uint64_t wave = ((uint64_t)blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = (uint64_t)gridDim.x * 4;
-  for (uint64_t b = wave; b < n_blk; b += n_waves) {
-    const uint64_t w = b * kGrBlockWords + lane;
-    uint32_t bits = w < n_words ? S[w] : 0u;
-    uint64_t at = blk_s[b] + gr_before((uint32_t)__popc(bits), lane);
-    while (bits) {
-      const uint64_t d = w * 32 + (uint32_t)__ffs(bits) - 1u;
-      bits &= bits - 1u;
-      start[at++] = doc_off[d];
-    }
-    bits = w < n_words ? T[w] : 0u;
-    at = blk_t[b] + gr_before((uint32_t)__popc(bits), lane);
-    while (bits) {
-      const uint64_t d = w * 32 + (uint32_t)__ffs(bits) - 1u;
-      bits &= bits - 1u;
-      end[at++] = (long long)doc_off[d + 1];
-    }
-  }
+  for_ranked_bits(S, n_words, n_blk, blk_s, [&](uint64_t w, uint32_t i, uint64_t at) { start[at] = doc_off[w * 32 + i]; });
+  for_ranked_bits(T, n_words, n_blk, blk_t, [&](uint64_t w, uint32_t i, uint64_t at) { end[at] = (long long)doc_off[w * 32 + i + 1]; });
 }
 
 // shift[j]: end[j] -> delta[j]; sel[j] = a hit of key 0; ent[0] = the empty replacement
@@ -195,11 +158,11 @@ __global__ __launch_bounds__(256) void kgr_emit_docs(const uint32_t *keep, const
   const uint64_t wave = ((uint64_t)blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = (uint64_t)gridDim.x * 4;
   if (wave == 0 && lane == 0 && doc_out) doc_out[blk_k[n_blk]] = (unsigned long long)((long long)doc_off[n_docs] + shift[n_runs]);
   for (uint64_t b = wave; b < n_blk; b += n_waves) {
-    const uint64_t w = b * kGrBlockWords + lane;
+    const uint64_t w = b * kRankBlockWords + lane;
     uint32_t bits = w < n_words ? keep[w] : 0u;
     const uint32_t sbits = w < n_words ? S[w] : 0u;
-    uint64_t at = blk_k[b] + gr_before((uint32_t)__popc(bits), lane);
-    const uint64_t runs = blk_s[b] + gr_before((uint32_t)__popc(sbits), lane);  // the runs that start in front of this word
+    uint64_t at = blk_k[b] + wave_excl_scan((uint32_t)__popc(bits));
+    const uint64_t runs = blk_s[b] + wave_excl_scan((uint32_t)__popc(sbits));  // the runs that start in front of this word
     while (bits) {
       const uint32_t i = (uint32_t)__ffs(bits) - 1u;
       bits &= bits - 1u;
@@ -212,10 +175,6 @@ __global__ __launch_bounds__(256) void kgr_emit_docs(const uint32_t *keep, const
   }
 }
 
-uint32_t blocks_of(uint64_t items, uint32_t max_blocks) {
-  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + 255) / 256, max_blocks));
-}
-
 }  // namespace
 
 void grep_launch_ends(const uint8_t *corpus, uint64_t n_bytes, uint8_t delim, const uint64_t *doc_off, uint64_t n_docs, uint32_t *mask,
@@ -223,44 +182,44 @@ void grep_launch_ends(const uint8_t *corpus, uint64_t n_bytes, uint8_t delim, co
   if (!n_bytes) return;
   const uint64_t n_words = (n_bytes + 31) / 32;
   const uint32_t head = (uint32_t)std::min<uint64_t>((16 - (reinterpret_cast<uintptr_t>(corpus) & 15)) & 15, n_bytes);
-  hipLaunchKernelGGL(kgr_ends, dim3(blocks_of(n_words, max_blocks)), dim3(256), 0, (hipStream_t)stream, corpus, n_bytes, head,
+  hipLaunchKernelGGL(kgr_ends, dim3(grid_for(n_words, 256, max_blocks)), dim3(256), 0, (hipStream_t)stream, corpus, n_bytes, head,
                      (uint32_t)delim, n_words, mask);
   if (n_docs)
-    hipLaunchKernelGGL(kgr_doc_ends, dim3(blocks_of(n_docs, max_blocks)), dim3(256), 0, (hipStream_t)stream, doc_off, n_docs, n_bytes,
+    hipLaunchKernelGGL(kgr_doc_ends, dim3(grid_for(n_docs, 256, max_blocks)), dim3(256), 0, (hipStream_t)stream, doc_off, n_docs, n_bytes,
                        mask);
 }
 
 void grep_launch_emit_ends(const uint32_t *mask, uint64_t n_bytes, const uint64_t *blk, uint64_t *rec_off, uint32_t max_blocks,
                            void *stream) {
-  const uint64_t n_words = (n_bytes + 31) / 32, n_blk = select_rank_blocks(n_bytes);
-  hipLaunchKernelGGL(kgr_emit_ends, dim3(blocks_of(n_blk * 64, max_blocks)), dim3(256), 0, (hipStream_t)stream, mask, n_words, n_blk,
+  const uint64_t n_words = (n_bytes + 31) / 32, n_blk = rank_blocks(n_bytes);
+  hipLaunchKernelGGL(kgr_emit_ends, dim3(grid_for(n_blk * 64, 256, max_blocks)), dim3(256), 0, (hipStream_t)stream, mask, n_words, n_blk,
                      reinterpret_cast<const unsigned long long *>(blk), reinterpret_cast<unsigned long long *>(rec_off));
 }
 
 void grep_launch_flag(const uint64_t *dho, uint64_t n_docs, bool invert, uint32_t *keep, uint32_t *S, uint32_t *T, uint32_t max_blocks,
                       void *stream) {
   if (!n_docs) return;
-  hipLaunchKernelGGL(kgr_flag, dim3(blocks_of(n_docs, max_blocks)), dim3(256), 0, (hipStream_t)stream, dho, n_docs, invert ? 1u : 0u,
+  hipLaunchKernelGGL(kgr_flag, dim3(grid_for(n_docs, 256, max_blocks)), dim3(256), 0, (hipStream_t)stream, dho, n_docs, invert ? 1u : 0u,
                      keep, S, T);
 }
 
 void grep_launch_runs(const uint32_t *S, const uint32_t *T, uint64_t n_docs, const uint64_t *blk_s, const uint64_t *blk_t,
                       const uint64_t *doc_off, uint64_t n_runs, uint64_t *start, int64_t *shift, void *sel, RepEntry *ent,
                       uint32_t max_blocks, void *stream) {
-  const uint64_t n_words = (n_docs + 31) / 32, n_blk = select_rank_blocks(n_docs);
+  const uint64_t n_words = (n_docs + 31) / 32, n_blk = rank_blocks(n_docs);
   if (n_runs)
-    hipLaunchKernelGGL(kgr_runs, dim3(blocks_of(n_blk * 64, max_blocks)), dim3(256), 0, (hipStream_t)stream, S, T, n_words, n_blk,
+    hipLaunchKernelGGL(kgr_runs, dim3(grid_for(n_blk * 64, 256, max_blocks)), dim3(256), 0, (hipStream_t)stream, S, T, n_words, n_blk,
                        reinterpret_cast<const unsigned long long *>(blk_s), reinterpret_cast<const unsigned long long *>(blk_t), doc_off,
                        start, reinterpret_cast<long long *>(shift));
-  hipLaunchKernelGGL(kgr_delta, dim3(blocks_of(n_runs, max_blocks)), dim3(256), 0, (hipStream_t)stream, start,
+  hipLaunchKernelGGL(kgr_delta, dim3(grid_for(n_runs, 256, max_blocks)), dim3(256), 0, (hipStream_t)stream, start,
                      reinterpret_cast<long long *>(shift), n_runs, (int32_t *)sel, ent);
 }
 
 void grep_launch_emit_docs(const uint32_t *keep, const uint32_t *S, uint64_t n_docs, const uint64_t *blk_k, const uint64_t *blk_s,
                            const uint64_t *doc_off, const int64_t *shift, uint64_t n_runs, uint64_t *kept_docs, uint64_t *doc_out,
                            uint32_t max_blocks, void *stream) {
-  const uint64_t n_words = (n_docs + 31) / 32, n_blk = select_rank_blocks(n_docs);
-  hipLaunchKernelGGL(kgr_emit_docs, dim3(blocks_of(std::max<uint64_t>(n_blk, 1) * 64, max_blocks)), dim3(256), 0, (hipStream_t)stream,
+  const uint64_t n_words = (n_docs + 31) / 32, n_blk = rank_blocks(n_docs);
+  hipLaunchKernelGGL(kgr_emit_docs, dim3(grid_for(std::max<uint64_t>(n_blk, 1) * 64, 256, max_blocks)), dim3(256), 0, (hipStream_t)stream,
                      keep, S, n_words, n_blk, reinterpret_cast<const unsigned long long *>(blk_k),
                      reinterpret_cast<const unsigned long long *>(blk_s), doc_off, n_docs, reinterpret_cast<const long long *>(shift),
                      n_runs, reinterpret_cast<unsigned long long *>(kept_docs), reinterpret_cast<unsigned long long *>(doc_out));

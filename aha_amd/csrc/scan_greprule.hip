@@ -17,9 +17,12 @@
 #include <algorithm>
 
 #include "image.hpp"
+#include "post_common.hpp"
 
 namespace aha {
 namespace {
+
+using post::grid_for;
 
 struct RuleArg {
   aha_rule_term t[kRuleMaxTerms];  // sorted by class_id / kRuleChunkClasses; group: the dense index of the caller's group
@@ -86,10 +89,6 @@ __global__ __launch_bounds__(256) void kgq_edges(const uint32_t *keep, uint64_t 
   }
 }
 
-uint32_t blocks_of(uint64_t items, uint32_t max_blocks) {
-  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + 255) / 256, max_blocks));
-}
-
 }  // namespace
 
 void greprule_launch_keep(const uint32_t *rows, uint32_t n_classes, const uint64_t *doc_off, uint64_t n_docs,
@@ -111,13 +110,13 @@ void greprule_launch_keep(const uint32_t *rows, uint32_t n_classes, const uint64
   std::stable_sort(R.t, R.t + n_terms, [](const aha_rule_term &a, const aha_rule_term &b) {
     return a.class_id / kRuleChunkClasses < b.class_id / kRuleChunkClasses;
   });
-  hipLaunchKernelGGL(kgq_keep, dim3(blocks_of(n_docs, max_blocks)), dim3(256), 0, (hipStream_t)stream, rows, n_classes, doc_off, n_docs,
+  hipLaunchKernelGGL(kgq_keep, dim3(grid_for(n_docs, 256, max_blocks)), dim3(256), 0, (hipStream_t)stream, rows, n_classes, doc_off, n_docs,
                      R, n_terms, groups, invert ? 1u : 0u, keep);
 }
 
 void greprule_launch_edges(const uint32_t *keep, uint64_t n_docs, uint32_t *S, uint32_t *T, uint32_t max_blocks, void *stream) {
   if (!n_docs) return;
-  hipLaunchKernelGGL(kgq_edges, dim3(blocks_of((n_docs + 31) / 32, max_blocks)), dim3(256), 0, (hipStream_t)stream, keep, n_docs, S, T);
+  hipLaunchKernelGGL(kgq_edges, dim3(grid_for((n_docs + 31) / 32, 256, max_blocks)), dim3(256), 0, (hipStream_t)stream, keep, n_docs, S, T);
 }
 
 }  // namespace aha

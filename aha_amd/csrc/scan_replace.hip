@@ -17,26 +17,16 @@
 #include <algorithm>
 
 #include "image.hpp"
+#include "post_common.hpp"
 
 namespace aha {
 namespace {
 
+using post::grid_for;
+
 constexpr int kRpScanThreads = 256;  // lanes of the one workgroup over the block sums
 constexpr int kRpItems = kRpScanBlock / 256;  // items per lane of a block
 constexpr uint64_t kRpTile = 1024;  // output bytes of one wave's tile: 16 per lane
-
-// the largest d in [0, n) with off[d] <= x (off ascends, off[0] = 0 <= x): documents without a selection are stepped over
-__device__ __forceinline__ uint64_t rp_owner(const uint64_t *off, uint64_t n, uint64_t x) {
-  uint64_t lo = 1, hi = n;
-  while (lo < hi) {
-    const uint64_t mid = (lo + hi) >> 1;
-    if (off[mid] <= x)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  return lo - 1;
-}
 
 __global__ __launch_bounds__(256) void krp_delta(const int32_t *sel, uint64_t n, const uint64_t *dso, const uint64_t *doc_off,
                                                  uint64_t n_docs, const RepEntry *ent, uint32_t n_keys, uint64_t *start,
@@ -44,7 +34,7 @@ __global__ __launch_bounds__(256) void krp_delta(const int32_t *sel, uint64_t n,
   for (uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += (uint64_t)gridDim.x * 256) {
     const int32_t s = sel[j * 3], e = sel[j * 3 + 1];
     const uint32_t v = (uint32_t)sel[j * 3 + 2];
-    start[j] = doc_off[rp_owner(dso, n_docs, j)] + (uint64_t)s;
+    start[j] = doc_off[owner_of(dso, n_docs, j)] + (uint64_t)s;  // (dso[0] = 0; documents without a selection are stepped over)
     const bool keep = v >= n_keys || ent[v].keep;  // (never beyond the keys: a hit's value is a key)
     shift[j] = keep ? 0ll : (long long)ent[v].len - (long long)(e - s);
   }
@@ -59,8 +49,7 @@ __global__ __launch_bounds__(256) void krp_scan_sums(const long long *x, uint64_
 #pragma unroll
     for (int k = 0; k < kRpItems; k++)
       if (i0 + k < n) c += x[i0 + k];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
+    c = wave_sum(c);
     if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) sums[b] = s_part[0] + s_part[1] + s_part[2] + s_part[3];
@@ -68,29 +57,12 @@ __global__ __launch_bounds__(256) void krp_scan_sums(const long long *x, uint64_
   }
 }
 
-// sums[0, n_blk] in place: the blocks' sums -> the sum before every block, sums[n_blk] = the total.  One workgroup; a lane
-// takes a contiguous piece.
+// sums[0, n_blk] in place: the blocks' sums -> the sum before every block, sums[n_blk] = the total.  One workgroup.
 __global__ __launch_bounds__(kRpScanThreads) void krp_scan_top(long long *sums, uint64_t n_blk) {
   __shared__ long long s_sum[kRpScanThreads];
-  const uint64_t per = (n_blk + kRpScanThreads - 1) / kRpScanThreads;
-  const uint64_t b0 = min((uint64_t)threadIdx.x * per, n_blk), b1 = min(b0 + per, n_blk);
-  long long sum = 0;
-  for (uint64_t b = b0; b < b1; b++) sum += sums[b];
-  s_sum[threadIdx.x] = sum;
-  __syncthreads();
-  for (int d = 1; d < kRpScanThreads; d <<= 1) {  // inclusive scan of the pieces' sums
-    const long long v = (int)threadIdx.x >= d ? s_sum[threadIdx.x - d] : 0ll;
-    __syncthreads();
-    s_sum[threadIdx.x] += v;
-    __syncthreads();
-  }
-  long long run = s_sum[threadIdx.x] - sum;
-  for (uint64_t b = b0; b < b1; b++) {
-    const long long c = sums[b];
-    sums[b] = run;
-    run += c;
-  }
-  if (threadIdx.x == kRpScanThreads - 1) sums[n_blk] = s_sum[kRpScanThreads - 1];
+  const long long total = block_run_scan<kRpScanThreads>(
+      n_blk, [&](uint64_t b) { return sums[b]; }, [&](uint64_t b, long long run) { sums[b] = run; }, s_sum);
+  if (threadIdx.x == kRpScanThreads - 1) sums[n_blk] = total;
 }
 
 // x[0, n) in place: the items -> the sum of the items in front of each; x[n] = the total
@@ -105,12 +77,7 @@ __global__ __launch_bounds__(256) void krp_scan_add(long long *x, uint64_t n, ui
       v[k] = i0 + k < n ? x[i0 + k] : 0ll;
       c += v[k];
     }
-    long long incl = c;  // the items of the lanes up to this one
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const long long u = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += u;
-    }
+    const long long incl = wave_incl_scan(c);  // the items of the lanes up to this one
     if (lane == 63) s_wave[wave] = incl;
     __syncthreads();
     long long run = sums[b] + incl - c;
@@ -252,22 +219,18 @@ __global__ __launch_bounds__(256) void krp_copy(RpArgs a, uint64_t head, uint64_
   }
 }
 
-uint32_t blocks_of(uint64_t items, uint32_t max_blocks) {
-  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + 255) / 256, max_blocks));
-}
-
 }  // namespace
 
 void replace_launch_delta(const void *sel, uint64_t n, const uint64_t *dso, const uint64_t *doc_off, uint64_t n_docs,
                           const RepEntry *ent, uint32_t n_keys, uint64_t *start, int64_t *shift, uint32_t max_blocks, void *stream) {
   if (!n) return;
-  hipLaunchKernelGGL(krp_delta, dim3(blocks_of(n, max_blocks)), dim3(256), 0, (hipStream_t)stream, (const int32_t *)sel, n, dso,
+  hipLaunchKernelGGL(krp_delta, dim3(grid_for(n, 256, max_blocks)), dim3(256), 0, (hipStream_t)stream, (const int32_t *)sel, n, dso,
                      doc_off, n_docs, ent, n_keys, start, reinterpret_cast<long long *>(shift));
 }
 
 void replace_launch_scan(int64_t *shift, uint64_t n, int64_t *sums, uint32_t max_blocks, void *stream) {
   const uint64_t n_blk = replace_scan_blocks(n);
-  const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_blk, max_blocks));
+  const uint32_t grid = grid_for(n_blk, 1, max_blocks);
   long long *x = reinterpret_cast<long long *>(shift), *sm = reinterpret_cast<long long *>(sums);
   if (n_blk) hipLaunchKernelGGL(krp_scan_sums, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, n, n_blk, sm);
   hipLaunchKernelGGL(krp_scan_top, dim3(1), dim3(kRpScanThreads), 0, (hipStream_t)stream, sm, n_blk);
@@ -276,7 +239,7 @@ void replace_launch_scan(int64_t *shift, uint64_t n, int64_t *sums, uint32_t max
 
 void replace_launch_doc_offsets(const uint64_t *doc_off, const uint64_t *dso, const int64_t *shift, uint64_t n_docs,
                                 uint64_t *doc_out, uint32_t max_blocks, void *stream) {
-  hipLaunchKernelGGL(krp_doc_offsets, dim3(blocks_of(n_docs + 1, max_blocks)), dim3(256), 0, (hipStream_t)stream, doc_off, dso,
+  hipLaunchKernelGGL(krp_doc_offsets, dim3(grid_for(n_docs + 1, 256, max_blocks)), dim3(256), 0, (hipStream_t)stream, doc_off, dso,
                      reinterpret_cast<const long long *>(shift), n_docs, doc_out);
 }
 
@@ -287,7 +250,7 @@ void replace_launch_copy(const uint8_t *text, const void *sel, const uint64_t *s
   const uint64_t head = std::min<uint64_t>((16 - (reinterpret_cast<uintptr_t>(out) & 15)) & 15, total);
   const uint64_t n_tiles = (total - head + kRpTile - 1) / kRpTile;
   const RpArgs a{text, (const int32_t *)sel, start, reinterpret_cast<const long long *>(shift), n, ent, n_keys, blob, out, total};
-  const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n_tiles + 3) / 4, max_blocks));
+  const uint32_t grid = grid_for(n_tiles, 4, max_blocks);
   hipLaunchKernelGGL(krp_copy, dim3(grid), dim3(256), 0, (hipStream_t)stream, a, head, n_tiles);
 }
 

@@ -21,27 +21,14 @@
 
 #include "cover_span.hpp"
 #include "image.hpp"
+#include "post_common.hpp"
 
 namespace aha {
 namespace {
 
-constexpr uint32_t kSlBlockWords = 64;  // mask words of one rank block: a wave, a word per lane
+using post::grid_for;
+
 constexpr int kSlScanThreads = 1024;
-
-__device__ __forceinline__ bool sl_bit(const uint32_t *mask, uint64_t p) { return (mask[p >> 5] >> (uint32_t)(p & 31)) & 1u; }
-
-// the largest d in [0, n) with off[d] - sub <= x (off ascends, off[0] - sub = 0 <= x)
-__device__ __forceinline__ uint64_t sl_owner(const uint64_t *off, uint64_t n, uint64_t sub, uint64_t x) {
-  uint64_t lo = 1, hi = n;
-  while (lo < hi) {
-    const uint64_t mid = (lo + hi) >> 1;
-    if (off[mid] - sub <= x)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  return lo - 1;
-}
 
 // hits[0, n_hits): the range's hits, document by document; hit_off[d] - hit_off[0]: the first hit of document d
 __global__ __launch_bounds__(256) void ksl_longest(const int32_t *hits, uint64_t n_hits, const uint64_t *hit_off, const uint64_t *rel,
@@ -51,7 +38,7 @@ __global__ __launch_bounds__(256) void ksl_longest(const int32_t *hits, uint64_t
     const int32_t start = hits[i * 3], end = hits[i * 3 + 1];
     const uint32_t value = (uint32_t)hits[i * 3 + 2];
     if (start < 0 || end <= start) continue;
-    const uint64_t d = sl_owner(hit_off, nd, h0, i);
+    const uint64_t d = owner_of(hit_off, nd, i, h0);  // (hit_off[0] - h0 = 0 <= i)
     const uint64_t p = rel[d] + (uint64_t)start;
     if (p + (uint64_t)(end - start) > min(rel[d + 1], nb)) continue;  // (never: a hit lies inside its document)
     atomicMax(L + p, (unsigned long long)(uint32_t)(end - start) << 32 | value);
@@ -75,14 +62,14 @@ __global__ __launch_bounds__(256) void ksl_walk(const unsigned long long *L, uin
                                                 uint32_t *select) {
   for (uint64_t p0 = (uint64_t)blockIdx.x * 256 + threadIdx.x; p0 < nb; p0 += (uint64_t)gridDim.x * 256) {
     if (!L[p0]) continue;
-    if (p0 && !sl_bit(doc_start, p0) && sl_bit(cover, p0 - 1)) continue;  // inside a run: its walker comes by
+    if (p0 && !bit_at(doc_start, p0) && bit_at(cover, p0 - 1)) continue;  // inside a run: its walker comes by
     uint64_t p = p0;
     for (;;) {
       atomicOr(select + (p >> 5), 1u << (uint32_t)(p & 31));
       p += (uint64_t)(L[p] >> 32);
       // the next start of the run: covered bytes without a hit of their own are stepped over
-      while (p < nb && !sl_bit(doc_start, p) && sl_bit(cover, p) && !L[p]) p++;
-      if (p >= nb || sl_bit(doc_start, p) || !sl_bit(cover, p)) break;
+      while (p < nb && !bit_at(doc_start, p) && bit_at(cover, p) && !L[p]) p++;
+      if (p >= nb || bit_at(doc_start, p) || !bit_at(cover, p)) break;
     }
   }
 }
@@ -92,37 +79,18 @@ __global__ __launch_bounds__(256) void ksl_rank_blocks(const uint32_t *select, u
   const int lane = threadIdx.x & 63;
   const uint64_t wave = ((uint64_t)blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = (uint64_t)gridDim.x * 4;
   for (uint64_t b = wave; b < n_blk; b += n_waves) {
-    const uint64_t w = b * kSlBlockWords + lane;
-    uint32_t c = w < n_words ? (uint32_t)__popc(select[w]) : 0u;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
+    const uint64_t w = b * kRankBlockWords + lane;
+    const uint32_t c = wave_sum(w < n_words ? (uint32_t)__popc(select[w]) : 0u);
     if (lane == 0) blk[b] = c;
   }
 }
 
-// blk[0, n_blk] in place: the counts -> the set bits before every block, blk[n_blk] = the total.  One workgroup; a lane takes
-// a contiguous piece.
+// blk[0, n_blk] in place: the counts -> the set bits before every block, blk[n_blk] = the total.  One workgroup.
 __global__ __launch_bounds__(kSlScanThreads) void ksl_rank_scan(unsigned long long *blk, uint64_t n_blk) {
   __shared__ unsigned long long s_sum[kSlScanThreads];
-  const uint64_t per = (n_blk + kSlScanThreads - 1) / kSlScanThreads;
-  const uint64_t b0 = min((uint64_t)threadIdx.x * per, n_blk), b1 = min(b0 + per, n_blk);
-  unsigned long long sum = 0;
-  for (uint64_t b = b0; b < b1; b++) sum += blk[b];
-  s_sum[threadIdx.x] = sum;
-  __syncthreads();
-  for (int d = 1; d < kSlScanThreads; d <<= 1) {  // inclusive scan of the pieces' sums
-    const unsigned long long v = (int)threadIdx.x >= d ? s_sum[threadIdx.x - d] : 0ull;
-    __syncthreads();
-    s_sum[threadIdx.x] += v;
-    __syncthreads();
-  }
-  unsigned long long run = s_sum[threadIdx.x] - sum;
-  for (uint64_t b = b0; b < b1; b++) {
-    const unsigned long long c = blk[b];
-    blk[b] = run;
-    run += c;
-  }
-  if (threadIdx.x == kSlScanThreads - 1) blk[n_blk] = s_sum[kSlScanThreads - 1];
+  const unsigned long long total = block_run_scan<kSlScanThreads>(
+      n_blk, [&](uint64_t b) { return blk[b]; }, [&](uint64_t b, unsigned long long run) { blk[b] = run; }, s_sum);
+  if (threadIdx.x == kSlScanThreads - 1) blk[n_blk] = total;
 }
 
 // out[d] = base + the set bits below position rel[d], for the range's documents d in [0, nd): a wave per document
@@ -131,90 +99,69 @@ __global__ __launch_bounds__(256) void ksl_rank_docs(const uint32_t *select, con
   const int lane = threadIdx.x & 63;
   const uint64_t wave = ((uint64_t)blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = (uint64_t)gridDim.x * 4;
   for (uint64_t d = wave; d < nd; d += n_waves) {
-    const uint64_t x = rel[d], b = x / (kSlBlockWords * 32), w = b * kSlBlockWords + lane, wx = x >> 5;
+    const uint64_t x = rel[d], b = x / (kRankBlockWords * 32), w = b * kRankBlockWords + lane, wx = x >> 5;
     uint32_t c = 0;
     if (w < wx)
       c = (uint32_t)__popc(select[w]);
     else if (w == wx && (x & 31))
       c = (uint32_t)__popc(select[w] & ~(~0u << (uint32_t)(x & 31)));
-#pragma unroll
-    for (int k = 32; k >= 1; k >>= 1) c += __shfl_xor(c, k, 64);
+    c = wave_sum(c);
     if (lane == 0) out[d] = base + blk[b] + c;
   }
 }
 
-// the selection in position order: a wave per block, a lane per word
+// the selection in position order
 __global__ __launch_bounds__(256) void ksl_emit(const uint32_t *select, uint64_t n_words, uint64_t n_blk, const unsigned long long *blk,
                                                 const unsigned long long *L, const uint64_t *rel, uint64_t nd, int32_t *out) {
-  const int lane = threadIdx.x & 63;
-  const uint64_t wave = ((uint64_t)blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = (uint64_t)gridDim.x * 4;
-  for (uint64_t b = wave; b < n_blk; b += n_waves) {
-    const uint64_t w = b * kSlBlockWords + lane;
-    uint32_t bits = w < n_words ? select[w] : 0u;
-    const uint32_t c = (uint32_t)__popc(bits);
-    uint32_t incl = c;  // set bits of the lanes up to this one
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t v = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += v;
-    }
-    uint64_t at = blk[b] + (incl - c);
-    while (bits) {
-      const uint64_t p = w * 32 + (uint32_t)__ffs(bits) - 1u;
-      bits &= bits - 1u;
-      const unsigned long long v = L[p];
-      const uint64_t s = p - rel[sl_owner(rel, nd, 0, p)];
-      out[at * 3] = (int32_t)s;
-      out[at * 3 + 1] = (int32_t)(s + (uint64_t)(v >> 32));
-      out[at * 3 + 2] = (int32_t)(uint32_t)v;
-      at++;
-    }
-  }
-}
-
-uint32_t blocks_of(uint64_t items, uint32_t max_blocks) {
-  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + 255) / 256, max_blocks));
+  for_ranked_bits(select, n_words, n_blk, blk, [&](uint64_t w, uint32_t i, uint64_t at) {
+    const uint64_t p = w * 32 + i;
+    const unsigned long long v = L[p];
+    const uint64_t s = p - rel[owner_of(rel, nd, p)];  // (rel[0] = 0)
+    out[at * 3] = (int32_t)s;
+    out[at * 3 + 1] = (int32_t)(s + (uint64_t)(v >> 32));
+    out[at * 3 + 2] = (int32_t)(uint32_t)v;
+  });
 }
 
 }  // namespace
 
-uint64_t select_rank_blocks(uint64_t n_bytes) { return ((n_bytes + 31) / 32 + kSlBlockWords - 1) / kSlBlockWords; }
+uint64_t select_rank_blocks(uint64_t n_bytes) { return rank_blocks(n_bytes); }
 
 void select_launch_longest(const void *hits, uint64_t n_hits, const uint64_t *hit_off, const uint64_t *rel, uint64_t nd, uint64_t nb,
                            uint64_t *L, uint32_t max_blocks, void *stream) {
-  hipLaunchKernelGGL(ksl_longest, dim3(blocks_of(n_hits, max_blocks)), dim3(256), 0, (hipStream_t)stream, (const int32_t *)hits, n_hits,
+  hipLaunchKernelGGL(ksl_longest, dim3(grid_for(n_hits, 256, max_blocks)), dim3(256), 0, (hipStream_t)stream, (const int32_t *)hits, n_hits,
                      hit_off, rel, nd, nb, reinterpret_cast<unsigned long long *>(L));
 }
 
 void select_launch_marks(const uint64_t *L, uint64_t nb, const uint64_t *rel, uint64_t nd, uint32_t *cover, uint32_t *doc_start,
                          uint32_t max_blocks, void *stream) {
-  hipLaunchKernelGGL(ksl_marks, dim3(blocks_of(std::max(nb, nd), max_blocks)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(ksl_marks, dim3(grid_for(std::max(nb, nd), 256, max_blocks)), dim3(256), 0, (hipStream_t)stream,
                      reinterpret_cast<const unsigned long long *>(L), nb, rel, nd, cover, doc_start);
 }
 
 void select_launch_walk(const uint64_t *L, uint64_t nb, const uint32_t *cover, const uint32_t *doc_start, uint32_t *select,
                         uint32_t max_blocks, void *stream) {
-  hipLaunchKernelGGL(ksl_walk, dim3(blocks_of(nb, max_blocks)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(ksl_walk, dim3(grid_for(nb, 256, max_blocks)), dim3(256), 0, (hipStream_t)stream,
                      reinterpret_cast<const unsigned long long *>(L), nb, cover, doc_start, select);
 }
 
 void select_launch_rank(const uint32_t *select, uint64_t nb, uint64_t *blk, uint32_t max_blocks, void *stream) {
-  const uint64_t n_words = (nb + 31) / 32, n_blk = select_rank_blocks(nb);
+  const uint64_t n_words = (nb + 31) / 32, n_blk = rank_blocks(nb);
   unsigned long long *b = reinterpret_cast<unsigned long long *>(blk);
-  hipLaunchKernelGGL(ksl_rank_blocks, dim3(blocks_of(n_blk * 64, max_blocks)), dim3(256), 0, (hipStream_t)stream, select, n_words, n_blk, b);
+  hipLaunchKernelGGL(ksl_rank_blocks, dim3(grid_for(n_blk * 64, 256, max_blocks)), dim3(256), 0, (hipStream_t)stream, select, n_words, n_blk, b);
   hipLaunchKernelGGL(ksl_rank_scan, dim3(1), dim3(kSlScanThreads), 0, (hipStream_t)stream, b, n_blk);
 }
 
 void select_launch_rank_docs(const uint32_t *select, const uint64_t *blk, const uint64_t *rel, uint64_t nd, uint64_t base,
                              uint64_t *out, uint32_t max_blocks, void *stream) {
-  hipLaunchKernelGGL(ksl_rank_docs, dim3(blocks_of(nd * 64, max_blocks)), dim3(256), 0, (hipStream_t)stream, select,
+  hipLaunchKernelGGL(ksl_rank_docs, dim3(grid_for(nd * 64, 256, max_blocks)), dim3(256), 0, (hipStream_t)stream, select,
                      reinterpret_cast<const unsigned long long *>(blk), rel, nd, base, reinterpret_cast<unsigned long long *>(out));
 }
 
 void select_launch_emit(const uint32_t *select, uint64_t nb, const uint64_t *blk, const uint64_t *L, const uint64_t *rel, uint64_t nd,
                         void *out, uint32_t max_blocks, void *stream) {
-  const uint64_t n_words = (nb + 31) / 32, n_blk = select_rank_blocks(nb);
-  hipLaunchKernelGGL(ksl_emit, dim3(blocks_of(n_blk * 64, max_blocks)), dim3(256), 0, (hipStream_t)stream, select, n_words, n_blk,
+  const uint64_t n_words = (nb + 31) / 32, n_blk = rank_blocks(nb);
+  hipLaunchKernelGGL(ksl_emit, dim3(grid_for(n_blk * 64, 256, max_blocks)), dim3(256), 0, (hipStream_t)stream, select, n_words, n_blk,
                      reinterpret_cast<const unsigned long long *>(blk), reinterpret_cast<const unsigned long long *>(L), rel, nd,
                      (int32_t *)out);
 }
