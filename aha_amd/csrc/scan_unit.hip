@@ -318,7 +318,8 @@ __global__ __launch_bounds__(kV2Threads) void ku_traverse(UnitDev U, V2Args M) {
               uint32_t n_code, n_L;
               bool n_later;
               const uint32_t Lb = CHARS ? (L & 0xFFu) : L;  // (CHARS: bit 8 = the unit is a character)
-              decode(rel + Lb, n_code, n_L, n_later);  // rows are padded: rel + 3 + 8 bytes stay inside LDS
+              uint32_t rel_adv = rel + Lb;  // where the lane stands when the unit is consumed
+              decode(rel_adv, n_code, n_L, n_later);  // rows are padded: rel + 3 + 8 bytes stay inside LDS
               // Every select below picks between values that are already computed (plain locals): that keeps them
               // v_cndmask instead of nested divergent branches, which cost more than the work they skip.
               // ---- the root's transitions (LDS) on the unit (symbol 0 -- a bad unit or one outside the alphabet -- has
@@ -326,45 +327,64 @@ __global__ __launch_bounds__(kV2Threads) void ku_traverse(UnitDev U, V2Args M) {
               // fails to
               const uint32_t rt = rl[code];
               const uint32_t rf = rl[pc];
-              if (HB)
-                asm volatile("s_waitcnt vmcnt(0)" : "+v"(enw), "+v"(hdw) : : "memory");
-              else
-                asm volatile("s_waitcnt vmcnt(0)" : "+v"(enw) : : "memory");
-              const uint32_t enx = (uint32_t)enw, eny = (uint32_t)(enw >> 32);
-              const bool symhit = probe & u_sym(eny) == se & !grp;  // (a group record's second word is a slot number)
-              const bool hit = symhit & !hdr;
-              // a big state continues on this high symbol: its child's entry is the slot `first child of the group + set
-              // bits below the symbol's`; the next trip probes it as the state "slot ^ symbol" and consumes the unit
-              const bool redir = grp & probe & ((enx >> (code & 31u)) & 1u) != 0u;
-              const uint32_t rE = (__builtin_popcount(enx & ~(~0u << (code & 31u))) + eny ^ code) | u_all_filter(BB);
+              // ---- in the probe's shadow: whatever the resolve needs that is no function of the probe's answer -- where a miss
+              // goes (the root's table, F1's one-character state or the header), the masks of a group record, where the lane
+              // stands and whether it reports once the unit is consumed.  The wait statement names them as operands, so they
+              // are computed in front of it: behind it every instruction lengthens the chain from one probe to the next
+              // (tests/test_trip_chain_isa.py counts what is left there).
               // a miss: the fail link is the root (or the unit matches nothing) -> the root's table answers in this trip;
               // else the unit is tried again in the fail state: root[the symbol that led here] (F1), or the state's header,
               // fetched by the next trip (falling into a state reports nothing: END is not carried)
-              const bool viaroot = !symhit & !redir & (!u_nfr(E) | !good);
-              // (HB: the header has come with the probe; else it is fetched by the next trip: "header pending")
-              const uint32_t ft = u_f1(E) ? (rf & 0x7FFFFFFFu) : (HB ? hdw : (Bq | u_all_filter(BB) | 0x20000000u));
-              uint32_t missE = viaroot ? rt : ft;
+              const bool viaroot0 = !u_nfr(E) | !good;
+              // (HB: the header comes with the probe -- `own0`: the miss does not need it; else it is fetched by the next
+              // trip: "header pending")
+              const bool own0 = viaroot0 | u_f1(E);
+              const uint32_t ft0 = u_f1(E) ? (rf & 0x7FFFFFFFu) : (Bq | u_all_filter(BB) | 0x20000000u);
+              uint32_t miss0 = viaroot0 ? rt : (HB ? (rf & 0x7FFFFFFFu) : ft0);
+              const uint32_t cb = code & 31u;
+              uint32_t lowm = ~(~0u << cb);                    // a group record: the symbols below this one
+              uint32_t gbit = (grp & probe) ? (1u << cb) : 0u;  // ... and this one's bit, in the lanes that asked for one
+              const bool pg = probe & !grp;  // (a group record's second word is a slot number)
+              const bool pgh = pg & !hdr;
+              const int32_t last = (int32_t)rel_adv - 1;  // row index of the unit's last byte
+              // is_end? -> fetch later (ac.cr:183-185); this lane reports the end positions in [a, e)
+              uint32_t wm = (last >= a_rel & last < e_rel) ? ~0u : 0u;
+              // (CHARS: characters that START in the lane's chunk; the rest of a chunk's bytes are continuation bytes)
+              uint32_t isl0 = (CHARS && (int32_t)rel >= a_rel) ? (L >> 8) : 0u;
+              if (CHARS) asm volatile("" : "+v"(isl0));
+              if (HB)
+                asm volatile("s_waitcnt vmcnt(0)" : "+v"(enw), "+v"(hdw), "+v"(miss0), "+v"(rel_adv), "+v"(lowm), "+v"(gbit), "+v"(wm), "+v"(n_code), "+v"(n_L) : : "memory");
+              else
+                asm volatile("s_waitcnt vmcnt(0)" : "+v"(enw), "+v"(miss0), "+v"(rel_adv), "+v"(lowm), "+v"(gbit), "+v"(wm), "+v"(n_code), "+v"(n_L) : : "memory");
+              // ---- on the chain: the probe's answer picks among them
+              const uint32_t enx = (uint32_t)enw, eny = (uint32_t)(enw >> 32);
+              const bool symeq = u_sym(eny) == se;
+              const bool symhit = symeq & pg;
+              const bool hit = symeq & pgh;
+              // a big state continues on this high symbol: its child's entry is the slot `first child of the group + set
+              // bits below the symbol's`; the next trip probes it as the state "slot ^ symbol" and consumes the unit
+              const bool redir = (enx & gbit) != 0u;
+              const uint32_t rE = (__builtin_popcount(enx & lowm) + eny ^ code) | u_all_filter(BB);
+              const bool viaroot = !(symhit | redir) & viaroot0;
+              uint32_t missE = HB ? (own0 ? miss0 : hdw) : miss0;
               missE = redir ? rE : missE;
               E = symhit ? enx : missE;
               const bool consumed = hit | viaroot;
               const bool end = consumed & u_end(E);
               const uint32_t c4 = hit ? u_c4(eny) : 1u;
               pc = consumed ? code : pc;
-              const uint32_t adv = consumed ? Lb : 0u;
-              if (CHARS) {  // characters that START in the lane's chunk (the rest of a chunk's bytes are continuation bytes)
-                const uint32_t isl = (consumed & (int32_t)rel >= a_rel) ? (L >> 8) : 0u;
+              if (CHARS) {
+                const uint32_t isl = consumed ? isl0 : 0u;
                 lc += isl;
                 lead_total += isl;
               }
-              rel += adv;
+              rel = consumed ? rel_adv : rel;
               const bool park = consumed & n_later;  // the next unit waits for the next round
               lim2 = park ? rel : lim2;
               lim = park ? rel : lim;
               code = consumed ? n_code : code;  // (a trip that falls to the fail state tries the same unit again)
               L = consumed ? n_L : L;
-              const int32_t last = (int32_t)rel - 1;  // row index of the unit's last byte
-              // is_end? -> fetch later (ac.cr:183-185); this lane reports the end positions in [a, e)
-              evc = (end & last >= a_rel & last < e_rel) ? c4 : 0u;
+              evc = end ? (c4 & wm) : 0u;  // (end: the unit is consumed, so rel is rel_adv)
             }
             return evc;
           };
