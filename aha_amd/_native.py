@@ -36,6 +36,7 @@ AHA_OPT_FOLD_KANA = 32
 AHA_COUNT_ACCUMULATE = 1
 AHA_GREP_INVERT = 1
 AHA_GREP_RULE = 4
+AHA_GREP_CONTEXT = 8
 AHA_RULE_GE = 0
 AHA_RULE_LT = 1
 AHA_RULE_MAX_TERMS = 64
@@ -69,6 +70,12 @@ class aha_grep_params(C.Structure):
     """AHA_GREP_RULE: what `params` of a grep call points to; match.struct_size = sizeof(aha_grep_params)"""
     _fields_ = [("match", aha_match_params), ("classes", C.c_void_p), ("terms", C.POINTER(aha_rule_term)),
                 ("n_terms", C.c_uint32), ("reserved", C.c_uint32), ("rows", C.c_void_p)]
+
+
+class aha_excerpt_params(C.Structure):
+    """AHA_GREP_CONTEXT: what `params` of a grep call points to; match.struct_size = sizeof(aha_excerpt_params), 64 bytes"""
+    _fields_ = [("match", aha_match_params), ("before", C.c_uint32), ("after", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
 
 
 class aha_ac_info_t(C.Structure):

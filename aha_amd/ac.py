@@ -1275,6 +1275,125 @@ class AC:
         parts = [raw[int(doo[i]):int(doo[i + 1])] for i in range(doo.size - 1)]
         return [x.decode("utf-8") for x in parts] if isinstance(seq, str) else parts
 
+    # -- excerpts: the text around every hit, cut out on the device (aha_ac_grep_batch* with AHA_GREP_CONTEXT) --------------
+    @staticmethod
+    def _excerpt_params(before, after, sep):
+        """-> (params pointer, what must stay alive over the call); the contexts are checked before the library is called"""
+        after = before if after is None else after
+        for name, v in (("before", before), ("after", after)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError("%s is a byte count: %r" % (name, v))
+            if not 0 <= int(v) <= 0x7FFFFFFF:
+                raise ValueError("%s is 0 .. 0x7FFFFFFF: %r" % (name, v))
+        ep = N.aha_excerpt_params()
+        ep.match = _params(False, sep)
+        ep.match.struct_size = C.sizeof(N.aha_excerpt_params)
+        ep.before, ep.after, ep.flags, ep.reserved = int(before), int(after), 0, 0
+        return C.cast(C.pointer(ep), C.POINTER(N.aha_match_params)), ep
+
+    def excerpts_batch(self, corpus, doc_offsets, before, after=None, sep=None, text=True):
+        """The hits of match_batch(corpus, doc_offsets, sep) in their context: `before` bytes in front of every hit and `after`
+        (None: before) behind it, clipped to the document, snapped outwards to UTF-8 character boundaries, neighbouring
+        contexts of one document merged: -> (starts uint64[R], uint8 array, out_offsets uint64[R+1], doc_excerpt_offsets
+        uint64[D+1]).  Excerpt r starts at corpus byte starts[r], its bytes are out[out_offsets[r]:out_offsets[r+1]]; document
+        d's excerpts are doc_excerpt_offsets[d]:doc_excerpt_offsets[d+1].  text False: no bytes are copied.  A sizing call
+        first."""
+        p, _alive = self._excerpt_params(before, after, sep)
+        if isinstance(corpus, (bytes, bytearray)):
+            corpus = np.frombuffer(bytes(corpus), dtype=np.uint8)
+        corpus = np.ascontiguousarray(corpus, dtype=np.uint8)
+        doc_offsets = np.ascontiguousarray(doc_offsets, dtype=np.uint64)
+        D = doc_offsets.size - 1
+        nk, nb = C.c_uint64(0), C.c_uint64(0)
+        L = N.lib()
+        flags = N.AHA_GREP_CONTEXT
+        self._check(L.aha_ac_grep_batch(self._h, _ptr(corpus), _ptr(doc_offsets), D, p, flags, None, None, 0, None, 0,
+                                        C.byref(nk), C.byref(nb), None))
+        cap, cap_bytes = int(nk.value), int(nb.value) if text else 0
+        starts = np.zeros(max(cap, 1), dtype=np.uint64)
+        oo = np.zeros(cap + 1, dtype=np.uint64)
+        out = np.zeros(max(cap_bytes, 1), dtype=np.uint8)
+        self._check(L.aha_ac_grep_batch(self._h, _ptr(corpus), _ptr(doc_offsets), D, p, flags, _ptr(starts), _ptr(oo), cap,
+                                        _ptr(out) if text else None, cap_bytes, C.byref(nk), C.byref(nb), None))
+        starts = starts[: int(nk.value)]
+        deo = np.searchsorted(starts, doc_offsets, side="left").astype(np.uint64)
+        return starts, out[: int(nb.value) if text else 0], oo[: int(nk.value) + 1], deo
+
+    def excerpts_batch_device(self, corpus, doc_offsets, starts=None, out_offsets=None, out=None, *, before, after=None,
+                              sep=None, cap=None, cap_bytes=None, stream=None):
+        """Device-resident excerpts on torch CUDA tensors: uint8 corpus (any alignment), int64/uint64 doc offsets, starts
+        int64/uint64 [cap] or None, out_offsets int64/uint64 [cap + 1] or None, out uint8 [cap_bytes] (any alignment) or None
+        (no bytes are copied).  -> (R, n_out_bytes, n_hits); raises AhaError(AHA_E_CAPACITY) when a buffer is too small
+        (e.n_required = the excerpts, e.bytes_required = the bytes needed); nothing is written then."""
+        import torch
+
+        p, _alive = self._excerpt_params(before, after, sep)
+        assert corpus.is_cuda and corpus.dtype == torch.uint8 and corpus.is_contiguous()
+        assert doc_offsets.is_cuda and doc_offsets.dtype in (torch.int64, torch.uint64)
+        for name, t in (("starts", starts), ("out_offsets", out_offsets)):
+            if t is not None and not (t.is_cuda and t.dtype in (torch.int64, torch.uint64) and t.is_contiguous()):
+                raise ValueError(name + " must be a contiguous int64/uint64 CUDA tensor")
+        room = []
+        if starts is not None:
+            room.append(starts.numel())
+        if out_offsets is not None:
+            if out_offsets.numel() < 1:
+                raise ValueError("out_offsets must have at least one entry")
+            room.append(out_offsets.numel() - 1)
+        cap = 0 if not room else min(room) if cap is None else min([int(cap)] + room)
+        if out is not None:
+            if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.dim() == 1):
+                raise ValueError("out must be a contiguous one-dimensional uint8 CUDA tensor")
+            cap_bytes = out.numel() if cap_bytes is None else min(int(cap_bytes), out.numel())
+        else:
+            cap_bytes = 0
+        D = doc_offsets.numel() - 1
+        nk, nb, nh = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        s = stream if stream is not None else torch.cuda.current_stream(corpus.device).cuda_stream
+        rc = N.lib().aha_ac_grep_batch_device(
+            self._h, corpus.data_ptr(), doc_offsets.data_ptr(), D, corpus.numel(), p, N.AHA_GREP_CONTEXT,
+            starts.data_ptr() if starts is not None else None,
+            out_offsets.data_ptr() if out_offsets is not None else None, cap,
+            out.data_ptr() if out is not None else None, cap_bytes, C.byref(nk), C.byref(nb), C.byref(nh), C.c_void_p(s))
+        if rc == N.AHA_E_CAPACITY:
+            raise self._grep_capacity_error(rc, nk, nb)
+        self._check(rc)
+        return int(nk.value), int(nb.value), int(nh.value)
+
+    def excerpts_corpus(self, corpus, before, after=None, sep=None, text=True):
+        """excerpts_batch of a batch that already lives in HBM (DeviceCorpus), downloaded:
+        -> (starts uint64[R], uint8 array, out_offsets uint64[R+1], n_hits)."""
+        p, _alive = self._excerpt_params(before, after, sep)
+        D, dev = corpus.n_docs, corpus.device
+        nk, nb, nh = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        L = N.lib()
+        flags = N.AHA_GREP_CONTEXT
+        self._check(L.aha_ac_grep_batch_device(self._h, corpus.ptr, corpus.doc_ptr, D, corpus.n_bytes, p, flags, None, None,
+                                               0, None, 0, C.byref(nk), C.byref(nb), C.byref(nh), None))
+        cap, cap_bytes = int(nk.value), int(nb.value) if text else 0
+        st, oo = DeviceBuffer(dev, max(cap, 1) * 8), DeviceBuffer(dev, (cap + 1) * 8)
+        out = DeviceBuffer(dev, max(cap_bytes, 1)) if text else None
+        self._check(L.aha_ac_grep_batch_device(self._h, corpus.ptr, corpus.doc_ptr, D, corpus.n_bytes, p, flags, st.ptr,
+                                               oo.ptr, cap, out.ptr if text else None, cap_bytes, C.byref(nk), C.byref(nb),
+                                               C.byref(nh), None))
+        got = out.download(np.zeros(max(cap_bytes, 1), dtype=np.uint8))[:cap_bytes] if text else np.zeros(0, dtype=np.uint8)
+        return (st.download(np.zeros(max(cap, 1), dtype=np.uint64))[:cap], got,
+                oo.download(np.zeros(cap + 1, dtype=np.uint64)), int(nh.value))
+
+    def excerpts(self, seq, before, after=None, sep=None):
+        """The hits of match(seq, sep) in their context, as a list of (start, text).  bytes in: start is a byte offset and
+        text is bytes.  str in: start is a character offset and text is a str (the contexts stay byte counts; no excerpt
+        begins or ends inside a character)."""
+        b = _b(seq)
+        corpus = np.frombuffer(b, dtype=np.uint8)
+        starts, out, oo, _ = self.excerpts_batch(corpus, np.array([0, len(b)], dtype=np.uint64), before, after, sep=sep)
+        raw = out.tobytes()
+        parts = [raw[int(oo[i]):int(oo[i + 1])] for i in range(starts.size)]
+        if not isinstance(seq, str):
+            return [(int(s), x) for s, x in zip(starts, parts)]
+        lead = np.concatenate([[0], np.cumsum((corpus & 0xC0) != 0x80)])  # the characters that start in front of a byte
+        return [(int(lead[int(s)]), x.decode("utf-8")) for s, x in zip(starts, parts)]
+
     # -- cover: which bytes lie inside a hit, and a redacted copy (aha_ac_cover_batch*) ---------------
     def _cover_host(self, corpus, doc_offsets, sep, want_mask, want_redacted, fill):
         if isinstance(corpus, (bytes, bytearray)):

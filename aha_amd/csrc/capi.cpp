@@ -1782,14 +1782,32 @@ static int32_t grep_rule_args(aha_ac *ac, const aha_match_params *params) {
   return AHA_OK;
 }
 
+// AHA_GREP_CONTEXT: the flag stands alone; params is the first member of an aha_excerpt_params (before any device work)
+static int32_t grep_context_args(const aha_match_params *params, uint32_t flags) {
+  auto bad = [](const char *what) {
+    tls_err = what;
+    return AHA_E_INVALID;
+  };
+  if (flags != AHA_GREP_CONTEXT) return bad("AHA_GREP_CONTEXT combines with no other flag");
+  if (!params || params->struct_size < sizeof(aha_excerpt_params))
+    return bad("AHA_GREP_CONTEXT: params must point to an aha_excerpt_params with match.struct_size = sizeof(aha_excerpt_params)");
+  const aha_excerpt_params *ep = reinterpret_cast<const aha_excerpt_params *>(params);
+  if (ep->flags || ep->reserved) return bad("AHA_GREP_CONTEXT: flags and reserved are 0");
+  if (ep->before > 0x7FFFFFFFu || ep->after > 0x7FFFFFFFu) return bad("AHA_GREP_CONTEXT: before and after are at most 0x7FFFFFFF");
+  return AHA_OK;
+}
+
 // the argument checks both grep entries share: before any device work, so they hold on a host-only handle.  out / corpus: the
 // two address ranges that must not overlap (there is no in-place form)
 static int32_t grep_args(aha_ac *ac, const uint8_t *corpus, uint64_t n_bytes, const uint64_t *doc_offsets, const aha_match_params *params,
                          uint32_t flags, const uint64_t *kept_docs, const uint64_t *doc_out_offsets, uint64_t cap_docs,
                          const uint8_t *out, uint64_t cap_bytes, uint64_t *n_kept) {
-  if (!ac || !n_kept || !doc_offsets || (flags & ~(AHA_GREP_INVERT | AHA_GREP_RULE))) return AHA_E_INVALID;
-  if (flags & AHA_GREP_RULE)
+  if (!ac || !n_kept || !doc_offsets || (flags & ~(AHA_GREP_INVERT | AHA_GREP_RULE | AHA_GREP_CONTEXT))) return AHA_E_INVALID;
+  if (flags & AHA_GREP_CONTEXT) {
+    if (int32_t rc = grep_context_args(params, flags)) return rc;
+  } else if (flags & AHA_GREP_RULE) {
     if (int32_t rc = grep_rule_args(ac, params)) return rc;
+  }
   if (int32_t rc = no_longest_form(ac, params, "grep calls have no match_longest form")) return rc;
   if (params && params->struct_size >= offsetof(aha_match_params, char_offsets) + sizeof(params->char_offsets) && params->char_offsets) {
     tls_err = "grep calls take byte offsets only";
@@ -1815,6 +1833,9 @@ int32_t aha_ac_grep_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uint
                          n_kept);
   if (rc) return rc;
   Lease lease(ac);
+  if (flags & AHA_GREP_CONTEXT)
+    return device_excerpts(ac, lease.get(), d_corpus, d_doc_offsets, n_docs, n_bytes, reinterpret_cast<const aha_excerpt_params *>(params),
+                           d_kept_docs, d_doc_out_offsets, cap_docs, d_out, cap_bytes, n_kept, n_out_bytes, n_hits, stream, false);
   if (flags & AHA_GREP_RULE) {
     // the caller's rows take the table at once only where no capacity can fail the call behind it
     const aha_grep_params *gp = reinterpret_cast<const aha_grep_params *>(params);
@@ -1857,7 +1878,10 @@ int32_t aha_ac_grep_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc
   uint8_t *d_out = (uint8_t *)B.d_per_call;
   hipStream_t s = B.s;
   uint64_t nk = 0, nb = 0, nh = 0;
-  if (gp)  // (d_rows is staging: the table may go there before the verdict)
+  if (flags & AHA_GREP_CONTEXT)  // (kept_docs takes the excerpts' starts, doc_out_offsets their offsets into out)
+    rc = device_excerpts(ac, sc, B.d_corpus, B.d_doc, n_docs, n_bytes, reinterpret_cast<const aha_excerpt_params *>(params), d_kept,
+                         d_doo, cap_docs, d_out, d_out ? cap_bytes : 0, &nk, &nb, &nh, s, true);
+  else if (gp)  // (d_rows is staging: the table may go there before the verdict)
     rc = device_grep_rule(ac, sc, B.d_corpus, B.d_doc, n_docs, n_bytes, gp, d_rows, flags, d_kept, d_doo, cap_docs, d_out,
                           d_out ? cap_bytes : 0, &nk, &nb, &nh, s, true, true);
   else

@@ -2026,6 +2026,120 @@ int32_t device_grep(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint
   return AHA_OK;
 }
 
+// The excerpts of one device-resident batch (aha_ac_grep_batch_device with AHA_GREP_CONTEXT; scan_excerpt.hip).
+//   1. device_count with a cover mask in scratch and without hit offsets: M, the total, the offsets validated.
+//   2. S and T over bytes -- where a covered run of one document starts and ends -- and their ranks by select's ranker: the run
+//      count comes back to the host.
+//   3. Per run its document and its window, clipped and snapped; the first and last masks over runs and their ranks: the
+//      excerpt count R comes back to the host.
+//   4. The R + 1 stretches outside the excerpts as deleted hits; replace's scan gives shift; the total comes back to the host,
+//      where the verdict is given.  Nothing has been written to the caller so far.
+//   5. The excerpts' starts and offsets, and replace's copy.
+// A failing call writes none of the caller's buffers.  Scratch beyond the count call's: 3 N / 8 bytes of masks, 16 bytes per
+// 2048 text bytes of block ranks, 24 bytes + 2 bits (and their block ranks) per run, 28 bytes per excerpt and the scan's sums.
+int32_t device_excerpts(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                        uint64_t n_bytes, const aha_excerpt_params *ep, uint64_t *d_starts, uint64_t *d_out_offsets, uint64_t cap_docs,
+                        uint8_t *d_out, uint64_t cap_bytes, uint64_t *n_kept, uint64_t *n_out_bytes, uint64_t *n_hits_out, void *stream,
+                        bool offsets_checked) {
+  if (!ac || !n_kept || !d_doc_offsets || !ep) return AHA_E_INVALID;
+  if ((cap_docs && !d_starts && !d_out_offsets) || (cap_bytes && !d_out)) return AHA_E_INVALID;
+  if (ac->device < 0) return no_device();
+  DeviceGuard g(ac->device);
+  hipStream_t s = (hipStream_t)stream;
+  const uint64_t D = n_docs;
+  *n_kept = 0;
+  if (n_out_bytes) *n_out_bytes = 0;
+  if (n_hits_out) *n_hits_out = 0;
+  auto nomem = [&]() {
+    tls_err = "hipMalloc failed for the scratch of an excerpts call";
+    return AHA_E_HIP;
+  };
+  const uint32_t blocks = grep_grid(ac);
+  const uint64_t n_words = (n_bytes + 31) / 32, n_blk = select_rank_blocks(n_bytes);
+  uint32_t *masks = (uint32_t *)grp_reserve(sc, kGrpExMasks, std::max<uint64_t>(n_words, 1) * 3 * 4);
+  uint64_t *blks = (uint64_t *)grp_reserve(sc, kGrpExBlocks, (n_blk + 1) * 2 * 8);
+  if (!masks || !blks) return nomem();
+  uint32_t *Mk = masks, *S = masks + n_words, *T = masks + 2 * n_words;
+  uint64_t *blk_s = blks, *blk_t = blks + (n_blk + 1);
+  int32_t rc;
+  uint64_t n_hits = 0;
+  if ((rc = device_count(ac, sc, d_corpus, d_doc_offsets, D, n_bytes, &ep->match, 0, nullptr, nullptr, &n_hits, stream, offsets_checked,
+                         n_bytes ? Mk : nullptr)))
+    return rc;
+  const bool prof = ac->profiling.load();
+  const auto t0 = std::chrono::steady_clock::now();
+  uint64_t n_runs = 0, n_exc = 0, total = 0;
+  if (n_bytes && n_hits) {
+    excerpt_launch_edges(Mk, n_bytes, d_doc_offsets, D, S, T, blocks, s);
+    select_launch_rank(S, n_bytes, blk_s, blocks, s);
+    select_launch_rank(T, n_bytes, blk_t, blocks, s);
+    HIPCHK(ac, hipGetLastError());
+    HIPCHK(ac, hipMemcpyAsync(&n_runs, blk_s + n_blk, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(ac, hipStreamSynchronize(s));
+  }
+  uint64_t *A = nullptr;
+  int64_t *shift = nullptr;
+  aha_hit *sel = nullptr;
+  RepEntry *ent = nullptr;
+  if (n_runs) {
+    const uint64_t r_words = (n_runs + 31) / 32, r_blk = select_rank_blocks(n_runs);
+    uint64_t *runs = (uint64_t *)grp_reserve(sc, kGrpExRuns, n_runs * 3 * 8);
+    uint32_t *rmasks = (uint32_t *)grp_reserve(sc, kGrpExRunMasks, r_words * 2 * 4);
+    uint64_t *rblks = (uint64_t *)grp_reserve(sc, kGrpExRunBlocks, (r_blk + 1) * 2 * 8);
+    if (!runs || !rmasks || !rblks) return nomem();
+    uint64_t *doc = runs, *w0 = runs + n_runs, *w1 = runs + 2 * n_runs;
+    uint32_t *first = rmasks, *last = rmasks + r_words;
+    uint64_t *blk_f = rblks, *blk_l = rblks + (r_blk + 1);
+    excerpt_launch_windows(S, T, n_bytes, blk_s, blk_t, d_corpus, d_doc_offsets, D, ep->before, ep->after, n_runs, doc, w0, w1, first,
+                           last, blocks, s);
+    select_launch_rank(first, n_runs, blk_f, blocks, s);
+    select_launch_rank(last, n_runs, blk_l, blocks, s);
+    HIPCHK(ac, hipGetLastError());
+    HIPCHK(ac, hipMemcpyAsync(&n_exc, blk_f + r_blk, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(ac, hipStreamSynchronize(s));
+    const uint64_t n_gaps = n_exc + 1, n_sum = replace_scan_blocks(n_gaps);
+    sel = (aha_hit *)grp_reserve(sc, kGrpSel, n_gaps * sizeof(aha_hit));
+    A = (uint64_t *)grp_reserve(sc, kGrpStart, n_gaps * 8);
+    shift = (int64_t *)grp_reserve(sc, kGrpShift, (n_gaps + 1) * 8);
+    int64_t *sums = (int64_t *)grp_reserve(sc, kGrpSums, (n_sum + 1) * 8);
+    ent = (RepEntry *)grp_reserve(sc, kGrpTable, sizeof(RepEntry));
+    if (!sel || !A || !shift || !sums || !ent) return nomem();
+    excerpt_launch_gaps(first, last, n_runs, blk_f, blk_l, w0, w1, n_bytes, n_exc, A, shift, sel, ent, blocks, s);
+    replace_launch_scan(shift, n_gaps, sums, blocks, s);
+    HIPCHK(ac, hipGetLastError());
+    int64_t change = 0;
+    HIPCHK(ac, hipMemcpyAsync(&change, shift + n_gaps, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(ac, hipStreamSynchronize(s));
+    total = (uint64_t)((int64_t)n_bytes + change);
+  }
+  const bool per_exc = d_starts || d_out_offsets;
+  const bool fits = !(per_exc && n_exc > cap_docs) && !(d_out && total > cap_bytes);
+  if (fits) {
+    if (n_exc) {
+      if (per_exc) excerpt_launch_emit(A, shift, n_exc, d_starts, d_out_offsets, blocks, s);
+      if (d_out) replace_launch_copy(d_corpus, sel, A, shift, n_exc + 1, ent, 1, (const uint8_t *)ent, d_out, total, blocks, s);
+      HIPCHK(ac, hipGetLastError());
+    } else if (d_out_offsets) {
+      HIPCHK(ac, hipMemsetAsync(d_out_offsets, 0, 8, s));  // (entry R is the total)
+    }
+    HIPCHK(ac, hipStreamSynchronize(s));
+  }
+  *n_kept = n_exc;
+  if (n_out_bytes) *n_out_bytes = total;
+  if (n_hits_out) *n_hits_out = n_hits;
+  if (prof) {  // ms_write: everything after the count
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    std::lock_guard<std::mutex> lk(ac->last_mu);
+    ac->last.ms_write += (float)ms;
+    ac->last.n_hits = n_hits;
+  }
+  if (!fits) {
+    tls_err = "output buffer too small";
+    return AHA_E_CAPACITY;
+  }
+  return AHA_OK;
+}
+
 // ---- class counts (aha_ac_class_counts_batch*) -----------------------------------------------------------------------
 uint32_t class_grid(const aha_ac *ac) { return ac->cls_blocks ? ac->cls_blocks : post_grid(ac); }
 static void *cls_reserve(Scratch *sc, ClassSlot slot, size_t bytes) { return reserve_ptr(sc->clsbuf[slot], bytes, kGrowEighth); }

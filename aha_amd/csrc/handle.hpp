@@ -167,6 +167,11 @@ enum GrepSlot {
   kGrpSums,       // grep: the scan's block sums
   kGrpTable,      // grep: the one-entry replacement table (the empty replacement)
   kGrpRows,       // rule grep: the D x C class counts where the caller gives no rows (bounded by AHA_RULE_TABLE_BYTES)
+  kGrpExMasks,    // excerpts: the cover mask M, then S and T, one bit per text byte each
+  kGrpExBlocks,   // excerpts: the block ranks of S and T, each with its total behind it
+  kGrpExRuns,     // excerpts: per covered run its document, w0 and w1, 24 bytes
+  kGrpExRunMasks, // excerpts: the first and last masks, one bit per run each
+  kGrpExRunBlocks,// excerpts: their two block ranks, each with its total behind it (the gap rows: kGrpSel .. kGrpTable)
   kGrpCount
 };
 // fgrpbuf: feed grep calls (feed.cpp feed_grep; scan_feedgrep.hip).  The fragments come from device_records, whose mask
@@ -592,6 +597,13 @@ int32_t device_grep_rule(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const
                          uint64_t n_bytes, const aha_grep_params *gp, uint32_t *d_rows, uint32_t flags, uint64_t *d_kept_docs,
                          uint64_t *d_doc_out_offsets, uint64_t cap_docs, uint8_t *d_out, uint64_t cap_bytes, uint64_t *n_kept,
                          uint64_t *n_out_bytes, uint64_t *n_hits, void *stream, bool offsets_checked, bool rows_early);
+// the excerpts of one device-resident batch (AHA_GREP_CONTEXT; ep checked by capi.cpp grep_context_args): device_count with a
+// cover mask in scratch, the covered runs, their windows and the merge (scan_excerpt.hip), replace's scan and copy over the gaps
+// between the excerpts.  d_starts takes grep's d_kept_docs, d_out_offsets its d_doc_out_offsets
+int32_t device_excerpts(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                        uint64_t n_bytes, const aha_excerpt_params *ep, uint64_t *d_starts, uint64_t *d_out_offsets, uint64_t cap_docs,
+                        uint8_t *d_out, uint64_t cap_bytes, uint64_t *n_kept, uint64_t *n_out_bytes, uint64_t *n_hits, void *stream,
+                        bool offsets_checked);
 // one device-resident batch as a dense table of hits per (document, key class) (aha_ac_class_counts_batch_device):
 // device_count for the hits per document, the match of every range of whole documents into scratch, one add per (hit, class)
 // into d_out[n_docs][table->n_classes] (scan_classcount.hip)

@@ -362,6 +362,26 @@ void grep_launch_emit_docs(const uint32_t *keep, const uint32_t *S, uint64_t n_d
                            const uint64_t *doc_off, const int64_t *shift, uint64_t n_runs, uint64_t *kept_docs, uint64_t *doc_out,
                            uint32_t max_blocks, void *stream);
 
+// excerpts path (scan_excerpt.hip; engine.cpp device_excerpts), from the cover mask M of the batch (one bit per text byte).
+// Masks are ranked by select_launch_rank; the gaps go to replace_launch_scan and replace_launch_copy as grep's dropped runs do.
+// S / T: ceil(n_bytes / 32) whole words each: a covered run of one document starts / ends at the bit
+void excerpt_launch_edges(const uint32_t *M, uint64_t n_bytes, const uint64_t *doc_off, uint64_t n_docs, uint32_t *S, uint32_t *T,
+                          uint32_t max_blocks, void *stream);
+// run j, delimited by the j-th bits of S and T: its document, its window [w0[j], w1[j]) (excerpt_window.hpp; corpus: the
+// caller's bytes, any alignment), and the masks over runs first / last, ceil(n_runs / 32) whole words each
+void excerpt_launch_windows(const uint32_t *S, const uint32_t *T, uint64_t n_bytes, const uint64_t *blk_s, const uint64_t *blk_t,
+                            const uint8_t *corpus, const uint64_t *doc_off, uint64_t n_docs, uint32_t before, uint32_t after,
+                            uint64_t n_runs, uint64_t *doc, uint64_t *w0, uint64_t *w1, uint32_t *first, uint32_t *last,
+                            uint32_t max_blocks, void *stream);
+// the n_exc + 1 stretches outside the excerpts as replace's copy takes them: start[j], shift[j] = delta[j] (n_exc + 2 words:
+// the scan's), sel[j] (12 bytes each), ent[0] = the empty replacement
+void excerpt_launch_gaps(const uint32_t *first, const uint32_t *last, uint64_t n_runs, const uint64_t *blk_f, const uint64_t *blk_l,
+                         const uint64_t *w0, const uint64_t *w1, uint64_t n_bytes, uint64_t n_exc, uint64_t *start, int64_t *shift,
+                         void *sel, RepEntry *ent, uint32_t max_blocks, void *stream);
+// starts[r] for r in [0, n_exc), out_off[r] for r in [0, n_exc] from the scanned shift (either may be null)
+void excerpt_launch_emit(const uint64_t *start, const int64_t *shift, uint64_t n_exc, uint64_t *starts, uint64_t *out_off,
+                         uint32_t max_blocks, void *stream);
+
 // rule grep (scan_greprule.hip; engine.cpp device_grep_rule).  rows: the class counts, n_classes words per document.
 // terms: HOST memory, at most kRuleMaxTerms, in any order and with any group ids (they travel as a kernel argument).
 // keep[0, ceil(n_docs / 32)): bit d = (the rule passes for document d) != invert, whole words, the bits from n_docs on 0

@@ -259,6 +259,17 @@ lib LibAhaHip
     reserved : UInt32   # 0
     rows : UInt32*      # optional D x C table, as class counts writes it (host entry: host memory; device entry: HBM)
   end
+  # excerpts: with GREP_CONTEXT (alone) `params` of the grep entries points to an ExcerptParams -- cast its address to
+  # MatchParams* --, and the result is the text around every hit: kept_docs takes the excerpts' first bytes (corpus offsets),
+  # doc_out_offsets their offsets into out.  Contexts are byte counts, clipped to the document and snapped to UTF-8 boundaries
+  GREP_CONTEXT = 8_u32
+  struct ExcerptParams
+    match : MatchParams # first member: match.struct_size = sizeof(ExcerptParams)
+    before : UInt32     # bytes of context in front of a hit, 0 .. 0x7FFFFFFF
+    after : UInt32      # bytes of context behind a hit, 0 .. 0x7FFFFFFF
+    flags : UInt32      # 0
+    reserved : UInt32   # 0
+  end
   fun aha_classes_create(ac : Ac, class_ids : UInt32*, offsets : UInt64*, n_classes : UInt32, out : Classes*) : Int32
   fun aha_classes_free(table : Classes) : Void
   fun aha_ac_class_counts_batch(ac : Ac, table : Classes, corpus : UInt8*, doc_offsets : UInt64*, n_docs : UInt64,
@@ -724,6 +735,36 @@ module Aha
         pointerof(nb), Pointer(UInt64).null)
       raise String.new(LibAhaHip.aha_last_error(@handle)) if rc != 0
       Array.new(nk.to_i32) { |i| out_bytes[doo[i], doo[i + 1] - doo[i]] }
+    end
+
+    # The hits of match(seq, sep) in their context (aha_ac_grep_batch with GREP_CONTEXT over the one document seq): `before`
+    # bytes in front of every hit and `after` behind it, snapped outwards to UTF-8 character boundaries, neighbouring contexts
+    # merged; {first byte, bytes} per excerpt, ascending.
+    def excerpts(seq : String | Bytes, before : UInt32, after : UInt32 = before, sep : BitArray? = nil) : Array({UInt64, Bytes})
+      bytes = seq.is_a?(String) ? seq.to_slice : seq
+      offs = [0_u64, bytes.size.to_u64]
+      ep = LibAhaHip::ExcerptParams.new
+      ep.match = AC.params(false, sep)
+      ep.match.struct_size = sizeof(LibAhaHip::ExcerptParams).to_u32
+      ep.before = before
+      ep.after = after
+      ep.flags = 0_u32
+      ep.reserved = 0_u32
+      params = pointerof(ep).as(LibAhaHip::MatchParams*)
+      nk = 0_u64
+      nb = 0_u64
+      rc = LibAhaHip.aha_ac_grep_batch(@handle, bytes.to_unsafe, offs.to_unsafe, 1_u64, params, LibAhaHip::GREP_CONTEXT,
+        Pointer(UInt64).null, Pointer(UInt64).null, 0_u64, Pointer(UInt8).null, 0_u64, pointerof(nk), pointerof(nb),
+        Pointer(UInt64).null)
+      raise String.new(LibAhaHip.aha_last_error(@handle)) if rc != 0
+      starts = Array(UInt64).new(nk + 1, 0_u64)
+      oo = Array(UInt64).new(nk + 1, 0_u64)
+      out_bytes = Bytes.new(nb)
+      rc = LibAhaHip.aha_ac_grep_batch(@handle, bytes.to_unsafe, offs.to_unsafe, 1_u64, params, LibAhaHip::GREP_CONTEXT,
+        starts.to_unsafe, oo.to_unsafe, nk, nb > 0 ? out_bytes.to_unsafe : Pointer(UInt8).null, nb, pointerof(nk),
+        pointerof(nb), Pointer(UInt64).null)
+      raise String.new(LibAhaHip.aha_last_error(@handle)) if rc != 0
+      Array.new(nk.to_i32) { |i| {starts[i], out_bytes[oo[i], oo[i + 1] - oo[i]]} }
     end
 
     private def run(seq : Bytes, chars : Bool, sep : BitArray?, longest : Int32 = 0, &block)

@@ -576,6 +576,74 @@ class AC {
     return out;
   }
 
+  // Excerpts (aha_ac_grep_batch with AHA_GREP_CONTEXT): the hits of match_batch in their context -- `before` bytes in front of
+  // every hit and `after` behind it, clipped to the document, snapped outwards to UTF-8 character boundaries, neighbouring
+  // contexts of one document merged -- cut out on the device.  Excerpt r starts at corpus byte starts[r]; its bytes are
+  // out.substr(out_offsets[r], out_offsets[r + 1] - out_offsets[r]).
+  //   auto m = aha::AC::compile({"ab"});
+  //   auto e = m.excerpts_batch("xxabxxxxabxab", {0, 11, 13}, 1, 2);   // starts {1, 7, 11}, out "xabxxxabxab", n_hits 3
+  //   m.excerpts_batch("xxabxxxxabxab", {0, 11, 13}, 1, 3).starts      == {1, 11}
+  struct Excerpts {
+    std::vector<uint64_t> starts;       // R
+    std::vector<uint64_t> out_offsets;  // R + 1
+    std::string out;
+    uint64_t n_hits = 0;
+    std::string_view operator[](size_t r) const {
+      return std::string_view(out).substr(out_offsets[r], out_offsets[r + 1] - out_offsets[r]);
+    }
+    size_t size() const { return starts.size(); }
+  };
+  static aha_excerpt_params excerpt_params(uint32_t before, uint32_t after) {
+    aha_excerpt_params ep{};
+    ep.match.struct_size = sizeof(ep);
+    ep.before = before;
+    ep.after = after;
+    return ep;
+  }
+  Excerpts excerpts_batch(std::string_view corpus, const std::vector<uint64_t> &doc_offsets, uint32_t before, uint32_t after) const {
+    if (doc_offsets.empty()) throw Error(AHA_E_INVALID, "doc_offsets holds D + 1 entries");
+    const aha_excerpt_params ep = excerpt_params(before, after);
+    const uint64_t D = doc_offsets.size() - 1;
+    const uint8_t *text = reinterpret_cast<const uint8_t *>(corpus.data());
+    uint64_t nk = 0, nb = 0, nh = 0;
+    int32_t rc = aha_ac_grep_batch(h_, text, doc_offsets.data(), D, &ep.match, AHA_GREP_CONTEXT, nullptr, nullptr, 0, nullptr, 0, &nk,
+                                   &nb, &nh);
+    Excerpts e;
+    e.starts.resize(nk + 1);
+    e.out_offsets.resize(nk + 1);
+    e.out.assign(nb, '\0');
+    if (rc == AHA_OK)
+      rc = aha_ac_grep_batch(h_, text, doc_offsets.data(), D, &ep.match, AHA_GREP_CONTEXT, e.starts.data(), e.out_offsets.data(), nk,
+                             nb ? reinterpret_cast<uint8_t *>(&e.out[0]) : nullptr, nb, &nk, &nb, &nh);
+    if (rc != AHA_OK) {
+      const char *m = aha_last_error(h_);
+      throw Error(rc, (m && *m) ? m : aha_strerror(rc));
+    }
+    e.starts.resize(nk);
+    e.n_hits = nh;
+    return e;
+  }
+  // The device-resident form over HBM pointers of the handle's device (d_starts [cap], d_out_offsets [cap + 1], d_out
+  // [cap_bytes]; any may be null): R, the bytes and the hits come back; AHA_E_CAPACITY throws with nothing written (*n_required
+  // and *bytes_required, where given, hold the two required numbers either way).
+  uint64_t excerpts_batch_device(const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
+                                 uint32_t before, uint32_t after, uint64_t *d_starts, uint64_t *d_out_offsets, uint64_t cap,
+                                 uint8_t *d_out, uint64_t cap_bytes, uint64_t *n_out_bytes = nullptr, uint64_t *n_hits = nullptr,
+                                 void *stream = nullptr, uint64_t *n_required = nullptr) const {
+    const aha_excerpt_params ep = excerpt_params(before, after);
+    uint64_t nk = 0, nb = 0, nh = 0;
+    const int32_t rc = aha_ac_grep_batch_device(h_, d_corpus, d_doc_offsets, n_docs, n_bytes, &ep.match, AHA_GREP_CONTEXT, d_starts,
+                                                d_out_offsets, cap, d_out, cap_bytes, &nk, &nb, &nh, stream);
+    if (n_required) *n_required = nk;
+    if (n_out_bytes) *n_out_bytes = nb;
+    if (n_hits) *n_hits = nh;
+    if (rc != AHA_OK) {
+      const char *m = aha_last_error(h_);
+      throw Error(rc, (m && *m) ? m : aha_strerror(rc));
+    }
+    return nk;
+  }
+
   // Which bytes of the batch lie inside a hit of match_batch, without the hit list (aha_ac_cover_batch): bit j of the batch is
   // word j >> 5, bit j & 31 of what is returned; doc_covered (optional): covered bytes per document.
   std::vector<uint32_t> cover_batch(std::string_view corpus, const std::vector<uint64_t> &doc_offsets,

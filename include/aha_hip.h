@@ -875,7 +875,7 @@ int32_t aha_ac_replace_batch_device(aha_ac *ac, const aha_repl *table, const uin
  * aha_ac_last_timing (grep): engine = the engine that traversed, n_hits = all hits, ms_write = everything after the count.
  * The host entries stage the batch on the device; a host sizing call followed by the real call runs the device work twice.
  * Out of scope so far: char offsets, match_longest, groups, multi-byte delimiters, an in-place form (feeds:
- * aha_feed_grep_batch* below).
+ * aha_feed_grep_batch* below; the hits in their context instead of whole documents: EXCERPTS below).
  *
  * RULE GREP (AHA_GREP_RULE, flag 4, combinable with AHA_GREP_INVERT: flags 5; 2 and 3 stay refused).  `params` points to an
  * aha_grep_params whose first member is the call's aha_match_params with match.struct_size = sizeof(aha_grep_params); the
@@ -911,9 +911,65 @@ int32_t aha_ac_replace_batch_device(aha_ac *ac, const aha_repl *table, const uin
  * unchanged.  aha_ac_last_timing: engine, n_hits and repeats as class counts reports them, ms_write = everything after the
  * class-counts call's match.
  * Out of scope so far: weighted sums and comparisons between two classes, tables restricted to the classes a rule names,
- * slabs of documents, feeds, groups, char offsets, match_longest, a rule object on the device. */
+ * slabs of documents, feeds, groups, char offsets, match_longest, a rule object on the device.
+ *
+ * EXCERPTS (AHA_GREP_CONTEXT, flag 8, alone: flags == 8 exactly).  The text around every hit, cut out on the device: `before`
+ * bytes in front of every hit and `after` bytes behind it, neighbouring contexts merged into one piece and nothing else copied
+ * (grep -o with a byte context, keyword in context, a search-result snippet).  `params` points to an aha_excerpt_params whose
+ * first member is the call's aha_match_params with match.struct_size = sizeof(aha_excerpt_params).
+ * Document d is the bytes [a, b) of the corpus; H_d = the hits aha_ac_match_batch reports for d with the same match params on
+ * the same handle, in byte offsets (a separator filter and every fold option included).  For a hit (start, end) of H_d, in
+ * 64-bit arithmetic:
+ *   w0 = snapL(max(a, a + start - before))        w1 = snapR(min(b, a + end + after))
+ *   snapL(x): at most three times, if x > a and (corpus[x] & 0xC0) == 0x80 then x -= 1
+ *   snapR(x): at most three times, if x < b and (corpus[x] & 0xC0) == 0x80 then x += 1
+ * The rule is bytewise and reads the caller's own bytes.  On valid UTF-8 no excerpt begins or ends inside a character; on
+ * anything else the rule is still defined, and a run of stray continuation bytes moves an edge by at most 3.
+ * E = the union of all [w0, w1).  The EXCERPTS are the maximal intervals of E that lie inside one document: windows of one
+ * document that overlap or touch ([x, y) and [y, z)) are one excerpt; two excerpts that meet at a document boundary stay two.
+ * They are numbered in ascending position, r = 0 .. R-1, [p_r, q_r).  In grep's parameters:
+ *   kept_docs[r]        p_r, the excerpt's first byte as an offset into the corpus (not into its document), ascending
+ *   doc_out_offsets[r]  where excerpt r lies in out; entry R is the total
+ *   out                 the excerpts' bytes one behind the other -- the caller's bytes, on a folded handle the original spelling
+ *   *n_kept = R, *n_out_bytes = the sum of q_r - p_r, *n_hits = all hits of the batch
+ * Everything else is grep's contract word for word: cap_docs and cap_bytes bound the buffers, AHA_E_CAPACITY reports both
+ * required numbers and writes none of the caller's buffers, the sizing call succeeds, out == NULL never launches the copy, two
+ * calls give identical bytes, N = 0, D = 0 and empty documents are valid, the handle's back-off state is read and never
+ * written, aha_ac_last_timing reports ms_write as everything after the count.  The document of excerpt r is the d with
+ * doc_offsets[d] <= p_r < doc_offsets[d+1] (excerpts are never empty, so the search is unambiguous); the library does not
+ * compute it on the device.  rec_offsets of aha_ac_records_batch* are valid doc_offsets: contexts clipped to lines.
+ * AHA_E_INVALID before any device work, with every buffer and every count untouched: flags that contain AHA_GREP_CONTEXT
+ * together with any other bit, match.struct_size < sizeof(aha_excerpt_params), params == NULL, the struct's own flags != 0 or
+ * reserved != 0, before or after above 0x7FFFFFFF, and everything plain grep refuses.  A bad sep_size answers
+ * AHA_E_SEP_SIZE; a host-only handle answers AHA_E_NO_DEVICE after all of these.  Without the flag the two entry points
+ * behave exactly as above, whatever struct_size says.
+ * Examples.
+ *   1. Key "ab"; documents "xxabxxxxabx" and "ab" (offsets 0, 11, 13).  before = 1, after = 2: the windows are [1,6), [7,11)
+ *      and [11,13); starts {1, 7, 11}, out = "xabxx" "xabx" "ab", offsets {0, 5, 9, 11}, n_hits = 3 -- the second and third
+ *      excerpts touch at the document boundary and stay two.  before = 1, after = 3: [1,7) and [7,11) touch inside one
+ *      document and merge; starts {1, 11}, out = "xabxxxxabx" "ab".
+ *   2. Key U+662F over the single document U+6211 U+662F U+4E2D (9 bytes, hit [3,6)), before = after = 1: w0 goes 2 -> 1 -> 0
+ *      and w1 goes 7 -> 8 -> 9: one excerpt, the whole document.
+ *   3. before = after = 0: the excerpts are the maximal covered runs of the cover call, split at document boundaries;
+ *      n_out_bytes equals the cover call's n_covered.
+ *   4. before = after = 0x7FFFFFFF: the excerpts are exactly the non-empty documents plain grep keeps; out equals grep's out
+ *      and the starts equal doc_offsets[kept_docs].
+ * Pipeline (aha_amd/csrc/scan_excerpt.hip, DESIGN.md 4.16 "Excerpts"): the count call with a cover mask M in scratch; a lane
+ * per mask word writes S and T (a covered run starts / ends at the bit), a lane per inner document boundary splits the runs
+ * that cross it; both are ranked as select's masks; the j-th bits delimit run j, whose document (a binary search), w0 and w1
+ * (excerpt_window.hpp, at most six text bytes) are written; first[j] = j is the first run of its document or w0[j] >
+ * w1[j-1], last[j] the same seen from j + 1, by wave ballot, ranked again; the R + 1 stretches outside the excerpts become
+ * deleted hits for replace's scan and copy; the verdict is given on the host before anything is written.  No pass looks at a
+ * hit: the snaps are monotone, so a run's window is the union of its hits' windows.
+ * Device scratch beside the count call's: N / 8 bytes for M, 2 N / 8 for S and T and 16 bytes per 2048 text bytes for their
+ * block ranks; 24 bytes and 2 bits per run and their block ranks; 28 bytes per excerpt and the scan's block sums.
+ * AHA_GREP_BLOCKS caps the grids.
+ * Out of scope so far: contexts counted in characters or in lines, a separator string between excerpts, combining with
+ * AHA_GREP_RULE or invert, match_longest, char offsets, feeds and groups, the excerpt's document index written on the device,
+ * an in-place form. */
 #define AHA_GREP_INVERT 1u /* keep the documents WITHOUT a hit */
 #define AHA_GREP_RULE 4u   /* params points to an aha_grep_params; keep = the rule over the class counts (2u is refused) */
+#define AHA_GREP_CONTEXT 8u /* params points to an aha_excerpt_params; the result is the excerpts, not documents */
 #define AHA_RULE_GE 0u     /* lhs >= rhs */
 #define AHA_RULE_LT 1u     /* lhs <  rhs */
 typedef struct aha_classes aha_classes;
@@ -933,6 +989,13 @@ typedef struct {
   uint32_t *rows;             /* optional D x C table, as class counts writes it: host memory in the host entry, HBM in the
                                  device entry */
 } aha_grep_params;
+typedef struct {
+  aha_match_params match; /* first member: match.struct_size = sizeof(aha_excerpt_params) */
+  uint32_t before;        /* bytes of context in front of a hit, 0 .. 0x7FFFFFFF */
+  uint32_t after;         /* bytes of context behind a hit,     0 .. 0x7FFFFFFF */
+  uint32_t flags;         /* 0 */
+  uint32_t reserved;      /* 0 */
+} aha_excerpt_params;     /* 64 bytes */
 int32_t aha_ac_records_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc_offsets, uint64_t n_docs, uint8_t delim,
                              uint32_t flags /* 0 */, uint64_t *rec_offsets /* cap_records + 1 */, uint64_t cap_records,
                              uint64_t *doc_rec_offsets /* D+1 or NULL */, uint64_t *n_records);
