@@ -37,6 +37,8 @@ AHA_COUNT_ACCUMULATE = 1
 AHA_GREP_INVERT = 1
 AHA_GREP_RULE = 4
 AHA_GREP_CONTEXT = 8
+AHA_SELECT_TOKENS = 4
+AHA_SELECT_GAP_RUNS = 8
 AHA_RULE_GE = 0
 AHA_RULE_LT = 1
 AHA_RULE_MAX_TERMS = 64

@@ -713,10 +713,10 @@ class AC:
                 int(nh.value))
 
     # -- select: leftmost-longest, non-overlapping hits per document (aha_ac_select_batch*) ----------
-    def select_batch(self, corpus, doc_offsets, sep=None, cap=None):
+    def select_batch(self, corpus, doc_offsets, sep=None, cap=None, flags=0):
         """Per document the leftmost-longest, non-overlapping hits of match_batch(corpus, doc_offsets, sep), byte offsets:
         -> (hits HIT_DTYPE, doc_sel_offsets uint64[D+1]); hits[doc_sel_offsets[d]:doc_sel_offsets[d+1]] is document d's
-        selection, ascending by start.  cap None: a sizing call first."""
+        selection, ascending by start.  cap None: a sizing call first.  flags: AHA_SELECT_* (tokens_batch)."""
         if isinstance(corpus, (bytes, bytearray)):
             corpus = np.frombuffer(bytes(corpus), dtype=np.uint8)
         corpus = np.ascontiguousarray(corpus, dtype=np.uint8)
@@ -727,14 +727,14 @@ class AC:
         n = C.c_uint64(0)
         L = N.lib()
         if cap is None:
-            rc = L.aha_ac_select_batch(self._h, _ptr(corpus), _ptr(doc_offsets), D, C.byref(p), 0, None, 0, _ptr(dso),
+            rc = L.aha_ac_select_batch(self._h, _ptr(corpus), _ptr(doc_offsets), D, C.byref(p), flags, None, 0, _ptr(dso),
                                        C.byref(n), None)
             if rc != N.AHA_E_CAPACITY:
                 self._check(rc)
                 return np.zeros(0, dtype=HIT_DTYPE), dso
             cap = int(n.value)
         out = np.zeros(max(int(cap), 1), dtype=HIT_DTYPE)
-        rc = L.aha_ac_select_batch(self._h, _ptr(corpus), _ptr(doc_offsets), D, C.byref(p), 0, _ptr(out), int(cap), _ptr(dso),
+        rc = L.aha_ac_select_batch(self._h, _ptr(corpus), _ptr(doc_offsets), D, C.byref(p), flags, _ptr(out), int(cap), _ptr(dso),
                                    C.byref(n), None)
         if rc == N.AHA_E_CAPACITY:
             e = AhaError(rc, N.lib().aha_strerror(rc).decode())
@@ -763,7 +763,7 @@ class AC:
         out = substitute(b, hits, repl, self.n_keys)
         return out.decode("utf-8") if isinstance(seq, str) else out
 
-    def select_batch_device(self, corpus, doc_offsets, out, doc_sel_offsets=None, sep=None, cap=None, stream=None):
+    def select_batch_device(self, corpus, doc_offsets, out, doc_sel_offsets=None, sep=None, cap=None, stream=None, flags=0):
         """Device-resident select on torch CUDA tensors: uint8 corpus, int64/uint64 doc offsets, out int32 [cap, 3]
         ({start, end, value} rows) or None (a sizing call), doc_sel_offsets int64/uint64 [D+1] or None.
         -> (n_selected, n_hits); raises AhaError(AHA_E_CAPACITY) when out is too small (e.n_required = the hits needed);
@@ -787,7 +787,7 @@ class AC:
         n, nh = C.c_uint64(0), C.c_uint64(0)
         s = stream if stream is not None else torch.cuda.current_stream(corpus.device).cuda_stream
         rc = N.lib().aha_ac_select_batch_device(
-            self._h, corpus.data_ptr(), doc_offsets.data_ptr(), D, corpus.numel(), C.byref(p), 0,
+            self._h, corpus.data_ptr(), doc_offsets.data_ptr(), D, corpus.numel(), C.byref(p), flags,
             out.data_ptr() if out is not None and cap else None, cap,
             doc_sel_offsets.data_ptr() if doc_sel_offsets is not None else None, C.byref(n), C.byref(nh), C.c_void_p(s))
         if rc == N.AHA_E_CAPACITY:
@@ -797,7 +797,7 @@ class AC:
         self._check(rc)
         return int(n.value), int(nh.value)
 
-    def select_corpus(self, corpus, sep=None):
+    def select_corpus(self, corpus, sep=None, flags=0):
         """The selection of a batch that already lives in HBM (DeviceCorpus), downloaded:
         -> (hits HIT_DTYPE, doc_sel_offsets uint64[D+1], n_hits)."""
         D = corpus.n_docs
@@ -806,17 +806,57 @@ class AC:
         dso = DeviceBuffer(dev, (D + 1) * 8)
         n, nh = C.c_uint64(0), C.c_uint64(0)
         L = N.lib()
-        rc = L.aha_ac_select_batch_device(self._h, corpus.ptr, corpus.doc_ptr, D, corpus.n_bytes, C.byref(p), 0, None, 0,
+        rc = L.aha_ac_select_batch_device(self._h, corpus.ptr, corpus.doc_ptr, D, corpus.n_bytes, C.byref(p), flags, None, 0,
                                           dso.ptr, C.byref(n), C.byref(nh), None)
         if rc != N.AHA_E_CAPACITY:
             self._check(rc)
             return np.zeros(0, dtype=HIT_DTYPE), dso.download(np.zeros(D + 1, dtype=np.uint64)), int(nh.value)
         cap = int(n.value)
         out = DeviceBuffer(dev, cap * 12)
-        rc = L.aha_ac_select_batch_device(self._h, corpus.ptr, corpus.doc_ptr, D, corpus.n_bytes, C.byref(p), 0, out.ptr, cap,
+        rc = L.aha_ac_select_batch_device(self._h, corpus.ptr, corpus.doc_ptr, D, corpus.n_bytes, C.byref(p), flags, out.ptr, cap,
                                           dso.ptr, C.byref(n), C.byref(nh), None)
         self._check(rc)
         return (out.download(np.zeros(cap, dtype=HIT_DTYPE)), dso.download(np.zeros(D + 1, dtype=np.uint64)), int(nh.value))
+
+    # -- tokens: dictionary segmentation (forward maximum matching) through the select entries (AHA_SELECT_TOKENS) ----------
+    @staticmethod
+    def _token_flags(gap_runs):
+        return N.AHA_SELECT_TOKENS | (N.AHA_SELECT_GAP_RUNS if gap_runs else 0)
+
+    def tokens_batch(self, corpus, doc_offsets, sep=None, gap_runs=False, cap=None):
+        """Every document as a gap-free sequence of tokens: the hits of select_batch(corpus, doc_offsets, sep) with their key
+        index as value, and between them one token per character (gap_runs: one per gap) with value -1.  Byte offsets:
+        -> (tokens HIT_DTYPE, doc_tok_offsets uint64[D+1]).  cap None: a sizing call first."""
+        return self.select_batch(corpus, doc_offsets, sep=sep, cap=cap, flags=self._token_flags(gap_runs))
+
+    def tokens_batch_device(self, corpus, doc_offsets, out, doc_tok_offsets=None, sep=None, gap_runs=False, cap=None, stream=None):
+        """Device-resident tokens on torch CUDA tensors, as select_batch_device: out int32 [cap, 3] ({start, end, value} rows;
+        column 2 is the id stream, -1 for a token that is no key) or None (a sizing call).  -> (n_tokens, n_hits)."""
+        return self.select_batch_device(corpus, doc_offsets, out, doc_sel_offsets=doc_tok_offsets, sep=sep, cap=cap, stream=stream,
+                                        flags=self._token_flags(gap_runs))
+
+    def tokens_corpus(self, corpus, sep=None, gap_runs=False):
+        """The tokens of a batch that already lives in HBM (DeviceCorpus), downloaded:
+        -> (tokens HIT_DTYPE, doc_tok_offsets uint64[D+1], n_hits)."""
+        return self.select_corpus(corpus, sep=sep, flags=self._token_flags(gap_runs))
+
+    def tokens(self, seq, sep=None, gap_runs=False):
+        """The tokens of one sequence.  bytes in: a list of Hit (byte offsets, value -1 for a token that is no key); str in: a
+        list of (text, value) -- the slices are cut from the UTF-8 bytes and decoded, so a key that ends inside a character
+        (byte-level keys) gives replacement characters, never an exception."""
+        b = _b(seq)
+        toks, _ = self.tokens_batch(np.frombuffer(b, dtype=np.uint8), np.array([0, len(b)], dtype=np.uint64), sep=sep,
+                                    gap_runs=gap_runs)
+        if isinstance(seq, str):
+            return [(b[s:e].decode("utf-8", errors="replace"), v) for s, e, v in toks.tolist()]
+        return [Hit(s, e, v) for s, e, v in toks.tolist()]
+
+    def segment(self, seq, sep=None, gap_runs=False):
+        """Just the pieces of tokens(seq): str in, a list of str; bytes in, a list of bytes."""
+        if isinstance(seq, str):
+            return [t for t, _ in self.tokens(seq, sep=sep, gap_runs=gap_runs)]
+        b = _b(seq)
+        return [b[t.start:t.end] for t in self.tokens(b, sep=sep, gap_runs=gap_runs)]
 
     # -- replace: the substituted copy of a batch, built on the device (aha_ac_replace_batch*) ----------
     def replacements(self, repl):

@@ -1379,10 +1379,12 @@ int32_t aha_ac_cover_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *do
 }
 
 // ---- select calls (aha_ac_select_batch*) ---------------------------------------------------------------------------
-// the argument checks both entries share: before any device work, so they hold on a host-only handle
+// the argument checks both entries share: before any device work, so they hold on a host-only handle.  flags: none, or
+// AHA_SELECT_TOKENS with or without AHA_SELECT_GAP_RUNS (the tokens of every document instead of the selection)
 static int32_t select_args(aha_ac *ac, const uint64_t *doc_offsets, const aha_match_params *params, uint32_t flags,
                            uint64_t *n_selected) {
-  if (!ac || !n_selected || !doc_offsets || flags) return AHA_E_INVALID;
+  if (!ac || !n_selected || !doc_offsets) return AHA_E_INVALID;
+  if ((flags & ~(AHA_SELECT_TOKENS | AHA_SELECT_GAP_RUNS)) || ((flags & AHA_SELECT_GAP_RUNS) && !(flags & AHA_SELECT_TOKENS))) return AHA_E_INVALID;
   if (int32_t rc = no_longest_form(ac, params, "select calls have no match_longest form")) return rc;
   if (params && params->struct_size >= offsetof(aha_match_params, char_offsets) + sizeof(params->char_offsets) && params->char_offsets) {
     tls_err = "select calls give byte offsets only";
@@ -1400,11 +1402,11 @@ int32_t aha_ac_select_batch_device(aha_ac *ac, const uint8_t *d_corpus, const ui
   if (cap && !d_out) return AHA_E_INVALID;
   Lease lease(ac);
   return device_select(ac, lease.get(), d_corpus, d_doc_offsets, n_docs, n_bytes, params, d_out, cap, d_doc_sel_offsets, n_selected,
-                       n_hits, stream, false);
+                       n_hits, stream, false, flags);
 }
 
 // The host entry: the batch goes up in one piece into the staging buffers of the leased scratch set, over its private stream;
-// the selection and the offsets come back once the call has succeeded.
+// the selection (the tokens) and the offsets come back once the call has succeeded.
 int32_t aha_ac_select_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc_offsets, uint64_t n_docs,
                             const aha_match_params *params, uint32_t flags, aha_hit *out, uint64_t cap, uint64_t *doc_sel_offsets,
                             uint64_t *n_selected, uint64_t *n_hits) {
@@ -1423,7 +1425,7 @@ int32_t aha_ac_select_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *d
   hipStream_t s = B.s;
   uint64_t ns = 0, nh = 0;
   rc = device_select(ac, sc, B.d_corpus, B.d_doc, n_docs, n_bytes, params, d_out, cap, d_dso, &ns, &nh, s,
-                     true);  // the offsets were checked on the host above
+                     true, flags);  // the offsets were checked on the host above
   if (rc == AHA_E_CAPACITY) *n_selected = ns;
   if (rc != AHA_OK) return rc;
   if (ns) HIPCHK(ac, hipMemcpyAsync(out, d_out, ns * sizeof(aha_hit), hipMemcpyDeviceToHost, s));

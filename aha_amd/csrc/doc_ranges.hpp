@@ -57,4 +57,33 @@ bool doc_ranges(const uint64_t *hit_off, uint64_t n_docs, uint64_t bound, Cost c
   return true;
 }
 
+// The tiling of a token call (engine.cpp device_select_to with AHA_SELECT_TOKENS), whose ranges take every document, hits or
+// none, and whose work per range grows with the text as well: bounds[0] = 0 < bounds[1] < .. < bounds.back() = n_docs (range r
+// is [bounds[r], bounds[r + 1]); n_docs == 0: bounds = {0}, no range).  A range takes documents while its hits cost at most
+// `bound` bytes (12 each) AND its text costs at most `bound` bytes (8 each: the L table of the select passes, the largest
+// scratch a text byte holds); a document beyond either is a range of its own.
+// doc_off[0 .. n_docs]: the documents' offsets into the text.  All documents within both bounds: the one range [0, n_docs).
+// false: no memory for `bounds`.
+inline bool doc_tiles(const uint64_t *hit_off, const uint64_t *doc_off, uint64_t n_docs, uint64_t bound, std::vector<uint64_t> &bounds) {
+  try {
+    bounds.assign(1, 0);
+    for (uint64_t d0 = 0; d0 < n_docs;) {
+      // (differences of ascending offsets: no wrap.)  Documents without a byte cost nothing and come along, so every range
+      // holds text unless the whole batch has none; the first document with text is taken whatever it costs
+      uint64_t d1 = d0;
+      bool any = false;
+      for (; d1 < n_docs; d1++) {
+        if (doc_off[d1 + 1] == doc_off[d1]) continue;
+        if (any && (hit_off[d1 + 1] - hit_off[d0] > bound / 12 || doc_off[d1 + 1] - doc_off[d0] > bound / 8)) break;
+        any = true;
+      }
+      bounds.push_back(d1);
+      d0 = d1;
+    }
+  } catch (...) {
+    return false;
+  }
+  return true;
+}
+
 }  // namespace aha

@@ -1327,16 +1327,26 @@ struct RangeCall {
 
   // The documents [d0, d1) as a batch: the caller's arrays where that is the whole batch; else the text from the range's first
   // byte, the offsets relative to it in rel_slot.
+  // the documents' offsets on the host, fetched once
+  int32_t host_offsets() {
+    hipStream_t s = (hipStream_t)stream;
+    if (!off.empty()) return AHA_OK;
+    try {
+      off.resize(D + 1);
+    } catch (...) {
+      return AHA_E_NOMEM;
+    }
+    HIPCHK(ac, hipMemcpyAsync(off.data(), d_doc_offsets, (D + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(ac, hipStreamSynchronize(s));
+    return AHA_OK;
+  }
+
   int32_t batch(uint64_t d0, uint64_t d1, RangeBatch &B) {
     hipStream_t s = (hipStream_t)stream;
     B = RangeBatch{d_corpus, d_doc_offsets, d1 - d0, n_bytes};
     if (d0 == 0 && d1 == D) return AHA_OK;
+    if (int32_t rc = host_offsets()) return rc;
     try {
-      if (off.empty()) {
-        off.resize(D + 1);
-        HIPCHK(ac, hipMemcpyAsync(off.data(), d_doc_offsets, (D + 1) * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(ac, hipStreamSynchronize(s));
-      }
       rel.resize(B.nd + 1);
     } catch (...) {
       return AHA_E_NOMEM;
@@ -1585,18 +1595,25 @@ static void *sel_reserve(Scratch *sc, SelectSlot slot, size_t bytes) { return re
 // again, then the emit) -- the price of the rare case, instead of a second buffer of the selection's size.
 int32_t device_select(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
                       uint64_t n_bytes, const aha_match_params *params, aha_hit *d_out, uint64_t cap, uint64_t *d_doc_sel_offsets,
-                      uint64_t *n_selected, uint64_t *n_hits_out, void *stream, bool offsets_checked) {
+                      uint64_t *n_selected, uint64_t *n_hits_out, void *stream, bool offsets_checked, uint32_t flags) {
   return device_select_to(ac, sc, d_corpus, d_doc_offsets, n_docs, n_bytes, params, d_out, cap, d_doc_sel_offsets, n_selected,
-                          n_hits_out, stream, offsets_checked, nullptr);
+                          n_hits_out, stream, offsets_checked, nullptr, flags);
 }
 
 // device_select with a say in where the selection goes (handle.hpp SelectSink).  sink == null: the public entries, as above.
 // With a sink every range's selection is emitted behind the ranges' before it as soon as the range has been worked -- one count
 // and one match per range whatever the number of ranges -- and d_out, cap and d_doc_sel_offsets are not used.
+// With AHA_SELECT_TOKENS in flags (no sink): the tokens of every document instead (scan_tokens.hip; DESIGN.md 4.14 "Tokens").
+// Step 3 goes on behind the walk: S, the bytes inside a selected hit; T, the token starts, from S, the masks and the caller's
+// own bytes of the range; the rank is T's, and step 4 emits the tokens.  The ranges tile ALL documents, hits or none
+// (doc_ranges.hpp doc_tiles), bounded by their text as well as by their hits; a range without a hit is not matched.
 int32_t device_select_to(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
                          uint64_t n_bytes, const aha_match_params *params, aha_hit *d_out, uint64_t cap, uint64_t *d_doc_sel_offsets,
-                         uint64_t *n_selected, uint64_t *n_hits_out, void *stream, bool offsets_checked, const SelectSink *sink) {
+                         uint64_t *n_selected, uint64_t *n_hits_out, void *stream, bool offsets_checked, const SelectSink *sink,
+                         uint32_t flags) {
   if (!ac || !n_selected || !d_doc_offsets) return AHA_E_INVALID;
+  const bool tokens = (flags & AHA_SELECT_TOKENS) != 0, gap_runs = (flags & AHA_SELECT_GAP_RUNS) != 0;
+  if (tokens && sink) return AHA_E_INVALID;
   if (ac->device < 0) return no_device();
   if (cap && !d_out) return AHA_E_INVALID;
   DeviceGuard g(ac->device);
@@ -1627,14 +1644,21 @@ int32_t device_select_to(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const
   call.book.begin();
   // the ranges, tiled: each from the end of the one before it (the first from 0), the last to D -- the walk takes every document,
   // hitless ones cost nothing, and a document beyond the bound is matched like any other (no solo form)
-  if (!doc_ranges(hd.data(), D, ac->sel_hit_bytes, [](uint64_t h) { return h * sizeof(aha_hit); }, ranges)) return AHA_E_NOMEM;
-  try {
-    for (const DocRange &g : ranges) bounds.push_back(g.d1);
-  } catch (...) {
-    return AHA_E_NOMEM;
+  if (tokens) {  // ... every document, hits or none, the text bounded too; no byte at all: no range, no token
+    if (n_bytes) {
+      if ((rc = call.host_offsets())) return rc;
+      if (!doc_tiles(hd.data(), call.off.data(), D, ac->sel_hit_bytes, bounds)) return AHA_E_NOMEM;
+    }
+  } else {
+    if (!doc_ranges(hd.data(), D, ac->sel_hit_bytes, [](uint64_t h) { return h * sizeof(aha_hit); }, ranges)) return AHA_E_NOMEM;
+    try {
+      for (const DocRange &g : ranges) bounds.push_back(g.d1);
+    } catch (...) {
+      return AHA_E_NOMEM;
+    }
+    if (!ranges.empty()) bounds.back() = D;
   }
-  const size_t n_ranges = ranges.size();  // 0: no hit at all
-  if (n_ranges) bounds.back() = D;
+  const size_t n_ranges = bounds.size() - 1;  // 0: no hit at all (a token call: no byte at all)
   const uint32_t blocks = post_grid(ac);
   uint64_t total = 0;
   // what a worked range leaves in scratch for the emit
@@ -1642,7 +1666,8 @@ int32_t device_select_to(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const
     const uint64_t *d_rel;
     uint64_t nd, nb;
     uint64_t *L, *blk;
-    uint32_t *select;
+    uint32_t *select;  // the ranked mask: the select mask, a token call's T
+    uint32_t *doc_start, *hit_start;  // a token call: the document-start mask; the select mask
   } R{};
   // steps 2 and 3 for the documents [d0, d1); *sel = the range's selected hits
   auto work = [&](uint64_t d0, uint64_t d1, uint64_t *sel) -> int32_t {
@@ -1655,23 +1680,39 @@ int32_t device_select_to(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const
     uint32_t *masks = (uint32_t *)sel_reserve(sc, kSelMasks, 3 * n_words * 4);
     uint64_t *blk = (uint64_t *)sel_reserve(sc, kSelBlocks, (n_blk + 1) * 8);
     if (!L || !masks || !blk) return nomem();
+    uint32_t *S = nullptr, *T = nullptr;
+    if (tokens) {
+      S = (uint32_t *)sel_reserve(sc, kSelSpans, n_words * 4);
+      T = (uint32_t *)sel_reserve(sc, kSelTokens, n_words * 4);
+      if (!S || !T) return nomem();
+    }
     aha_hit *d_hits = nullptr;
-    if ((rc = call.match(B, rh, &d_hits))) return rc;
+    if (rh || !tokens) {  // (a token call works ranges without a hit: nothing to match)
+      if ((rc = call.match(B, rh, &d_hits))) return rc;
+    }
     uint32_t *cover = masks, *doc_start = masks + n_words, *select = masks + 2 * n_words;
     HIPCHK(ac, hipMemsetAsync(L, 0, nb * 8, s));
     HIPCHK(ac, hipMemsetAsync(masks, 0, 3 * n_words * 4, s));
-    select_launch_longest(d_hits, rh, d_dho + d0, d_rel, nd, nb, L, blocks, s);
+    if (rh || !tokens) select_launch_longest(d_hits, rh, d_dho + d0, d_rel, nd, nb, L, blocks, s);
     select_launch_marks(L, nb, d_rel, nd, cover, doc_start, blocks, s);
     select_launch_walk(L, nb, cover, doc_start, select, blocks, s);
-    select_launch_rank(select, nb, blk, blocks, s);
+    if (tokens) {
+      HIPCHK(ac, hipMemsetAsync(S, 0, n_words * 4, s));
+      tokens_launch_spans(L, nb, select, S, blocks, s);
+      tokens_launch_starts(B.text, nb, select, S, doc_start, gap_runs, T, blocks, s);
+    }
+    select_launch_rank(tokens ? T : select, nb, blk, blocks, s);
     HIPCHK(ac, hipGetLastError());
     HIPCHK(ac, hipMemcpyAsync(sel, blk + n_blk, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(ac, hipStreamSynchronize(s));
-    R = Range{d_rel, nd, nb, L, blk, select};
+    R = Range{d_rel, nd, nb, L, blk, tokens ? T : select, doc_start, select};
     return AHA_OK;
   };
   auto emit = [&](uint64_t base) -> int32_t {
-    select_launch_emit(R.select, R.nb, R.blk, R.L, R.d_rel, R.nd, d_out + base, blocks, s);
+    if (tokens)
+      tokens_launch_emit(R.select, R.nb, R.blk, R.hit_start, R.doc_start, R.L, R.d_rel, R.nd, d_out + base, blocks, s);
+    else
+      select_launch_emit(R.select, R.nb, R.blk, R.L, R.d_rel, R.nd, d_out + base, blocks, s);
     HIPCHK(ac, hipGetLastError());
     return AHA_OK;
   };

@@ -106,6 +106,8 @@ enum SelectSlot {
   kSelMasks,    // the cover, document-start and select masks, one bit per text byte each
   kSelBlocks,   // the selected hits before every 64 words of the select mask, the range's total behind them
   kSelDocOff,   // the documents' offsets into the selection, until the call is known to succeed
+  kSelSpans,    // token calls: S, the bytes inside a selected hit, one bit per text byte
+  kSelTokens,   // token calls: T, the token starts, one bit per text byte
   kSelCount
 };
 // repbuf: replace calls (engine.cpp device_replace)
@@ -549,20 +551,25 @@ int32_t device_cover(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
 // scratch, the leftmost-longest non-overlapping hits of every document from it (scan_select.hip)
 int32_t device_select(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
                       uint64_t n_bytes, const aha_match_params *params, aha_hit *d_out, uint64_t cap, uint64_t *d_doc_sel_offsets,
-                      uint64_t *n_selected, uint64_t *n_hits, void *stream, bool offsets_checked);
+                      uint64_t *n_selected, uint64_t *n_hits, void *stream, bool offsets_checked, uint32_t flags = 0);
 // What device_select_to does with the selection.  Without a sink (device_select, the public entries): the caller's buffer where
 // the total fits, the documents' offsets to the caller's array.  With one (device_replace): `place(kept, upto, &at)` is asked,
 // range by range, for a buffer that holds `upto` hits and still has the first `kept` ones (it returns the call's error, with
 // tls_err set, where it has none); every range is emitted as soon as it has been worked, so no range is matched twice; the
 // documents' offsets stay in selbuf[kSelDocOff], D + 1 of them.  The call's timing (profiling) is handed to `timing` and not
 // published: the caller publishes once, with its own share added.
+// flags: AHA_SELECT_TOKENS (| AHA_SELECT_GAP_RUNS) -- the tokens of every document instead of the selection (scan_tokens.hip);
+// the ranges then tile all documents whether they have hits or not, and a range is bounded by its text (8 bytes of L each)
+// as well as by its hits.
+// Only without a sink.
 struct SelectSink {
   std::function<int32_t(uint64_t kept, uint64_t upto, aha_hit **at)> place;
   aha_timing *timing = nullptr;
 };
 int32_t device_select_to(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
                          uint64_t n_bytes, const aha_match_params *params, aha_hit *d_out, uint64_t cap, uint64_t *d_doc_sel_offsets,
-                         uint64_t *n_selected, uint64_t *n_hits, void *stream, bool offsets_checked, const SelectSink *sink);
+                         uint64_t *n_selected, uint64_t *n_hits, void *stream, bool offsets_checked, const SelectSink *sink,
+                         uint32_t flags = 0);
 // one device-resident batch substituted (aha_ac_replace_batch_device): device_select_to with the selection into scratch, then the
 // scan over the changes of length and the output-driven copy (scan_replace.hip)
 int32_t device_replace(aha_ac *ac, Scratch *sc, const aha_repl *table, const uint8_t *d_corpus, const uint64_t *d_doc_offsets,

@@ -320,6 +320,17 @@ void select_launch_rank_docs(const uint32_t *select, const uint64_t *blk, const 
 void select_launch_emit(const uint32_t *select, uint64_t nb, const uint64_t *blk, const uint64_t *L, const uint64_t *rel, uint64_t nd,
                         void *out, uint32_t max_blocks, void *stream);
 
+// token path (scan_tokens.hip; engine.cpp device_select_to with AHA_SELECT_TOKENS), over one range after select_launch_walk;
+// nb > 0.  S / T: ceil(nb / 32) whole words each; S clear.
+// S: the bytes inside a selected hit
+void tokens_launch_spans(const uint64_t *L, uint64_t nb, const uint32_t *select, uint32_t *S, uint32_t max_blocks, void *stream);
+// T: where a token starts (token_rule.hpp); text: the caller's bytes of the range, any alignment, not read with gap_runs
+void tokens_launch_starts(const uint8_t *text, uint64_t nb, const uint32_t *select, const uint32_t *S, const uint32_t *doc_start,
+                          bool gap_runs, uint32_t *T, uint32_t max_blocks, void *stream);
+// out[0, total): the tokens of the ranked T (blk: select_launch_rank over T) as {start, end, value or -1}, relative to their documents
+void tokens_launch_emit(const uint32_t *T, uint64_t nb, const uint64_t *blk, const uint32_t *select, const uint32_t *doc_start,
+                        const uint64_t *L, const uint64_t *rel, uint64_t nd, void *out, uint32_t max_blocks, void *stream);
+
 // replace path (scan_replace.hip; engine.cpp device_replace), over the whole batch: its selection sel[0, n) (document by
 // document, dso[0 .. n_docs] the documents' offsets into it, dso[n_docs] = n) and the replacement table on the device.
 struct RepEntry {   // one key of a replacement table

@@ -137,6 +137,50 @@ __device__ __forceinline__ void for_ranked_bits(const uint32_t *words, uint64_t 
   }
 }
 
+// The same walk with the lanes strided over the RANKS of a block instead of owning a word each: in every trip the wave's lanes
+// hold 64 consecutive ranks, so what f stores at out[rank] is stored side by side -- for passes that write a row per set bit of
+// a dense mask, where a lane that walks its own word's bits scatters the wave's stores over 64 places.  The block's words and
+// their exclusive counts go through LDS (lds: 128 words per wave of the workgroup); the word of rank j is the last whose
+// count is at most j, the bit its (j - count)-th set one.  Only the waves of a workgroup that reach a block touch their part
+// of lds: wave-level ordering, no workgroup barrier.
+template <int THREADS = 256, class F>
+__device__ __forceinline__ void for_ranked_slots(const uint32_t *words, uint64_t n_words, uint64_t n_blk, const unsigned long long *blk,
+                                                 uint32_t *lds, F f) {
+  const int lane = threadIdx.x & 63;
+  uint32_t *w_bits = lds + (threadIdx.x >> 6) * (2 * kRankBlockWords), *w_pre = w_bits + kRankBlockWords;
+  const uint64_t wave = ((uint64_t)blockIdx.x * THREADS + threadIdx.x) >> 6, n_waves = (uint64_t)gridDim.x * (THREADS / 64);
+  for (uint64_t b = wave; b < n_blk; b += n_waves) {
+    const uint64_t w = b * kRankBlockWords + lane;
+    const uint32_t bits = w < n_words ? words[w] : 0u;
+    const uint32_t incl = wave_incl_scan((uint32_t)__popc(bits));
+    const uint32_t n = wave_last(incl);
+    w_bits[lane] = bits;
+    w_pre[lane] = incl - (uint32_t)__popc(bits);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const uint64_t base = blk[b];
+    for (uint32_t j = (uint32_t)lane; j < n; j += 64) {
+      uint32_t l = 0;
+#pragma unroll
+      for (uint32_t step = kRankBlockWords / 2; step; step >>= 1)
+        if (w_pre[l + step] <= j) l += step;
+      const uint32_t word = w_bits[l];
+      uint32_t k = j - w_pre[l], i = 0;
+#pragma unroll
+      for (uint32_t step = 16; step; step >>= 1) {  // the k-th set bit of word: the half that holds it, five times
+        const uint32_t c = (uint32_t)__popc((word >> i) & ((1u << step) - 1u));
+        if (k >= c) {
+          k -= c;
+          i += step;
+        }
+      }
+      f(b * kRankBlockWords + l, i, base + j);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();  // (the next block's words overwrite these)
+  }
+}
+
 // --------------------------------------------------------------------- host
 // the workgroups of a launch whose kernel strides: ceil(units / per_block), at least 1, at most cap.  (In a namespace of its
 // own: scan_v2.hip, which sees this header through devcommon.hpp, has a grid_for of its own with other parameter types; the

@@ -389,6 +389,8 @@ module Aha
   class AC
     E_DUP_KEY  = -4
     E_CAPACITY = -6
+    SELECT_TOKENS   = 4_u32 # AHA_SELECT_TOKENS: the tokens of every document instead of the selection
+    SELECT_GAP_RUNS = 8_u32 # AHA_SELECT_GAP_RUNS: a gap is one token, not one per character
 
     getter handle : LibAhaHip::Ac
 
@@ -565,7 +567,7 @@ module Aha
 
     # Per document the leftmost-longest, non-overlapping hits of match_batch(docs, sep: sep), ascending by start, as
     # {start, end, value} in byte offsets (Aha::AC has no such method; CedarX#gsub walks the text the same way).
-    def select_batch(docs : Array(String) | Array(Bytes), sep : BitArray? = nil) : Array(Array({Int32, Int32, Int32}))
+    def select_batch(docs : Array(String) | Array(Bytes), sep : BitArray? = nil, flags : UInt32 = 0_u32) : Array(Array({Int32, Int32, Int32}))
       corpus = IO::Memory.new
       offs = Array(UInt64).new(docs.size + 1)
       offs << 0_u64
@@ -576,11 +578,11 @@ module Aha
       params = AC.params(false, sep)
       dso = Array(UInt64).new(docs.size + 1, 0_u64)
       rc = LibAhaHip.aha_ac_select_batch(@handle, corpus.to_slice.to_unsafe, offs.to_unsafe, docs.size.to_u64,
-        pointerof(params), 0_u32, Pointer(LibAhaHip::Hit).null, 0_u64, dso.to_unsafe, out n, Pointer(UInt64).null)
+        pointerof(params), flags, Pointer(LibAhaHip::Hit).null, 0_u64, dso.to_unsafe, out n, Pointer(UInt64).null)
       hits = Pointer(LibAhaHip::Hit).malloc(n + 1)
       if rc == E_CAPACITY # n is the required count; nothing was written
         rc = LibAhaHip.aha_ac_select_batch(@handle, corpus.to_slice.to_unsafe, offs.to_unsafe, docs.size.to_u64,
-          pointerof(params), 0_u32, hits, n, dso.to_unsafe, out n2, Pointer(UInt64).null)
+          pointerof(params), flags, hits, n, dso.to_unsafe, out n2, Pointer(UInt64).null)
       end
       raise String.new(LibAhaHip.aha_last_error(@handle)) if rc != 0
       Array.new(docs.size) do |d|
@@ -590,6 +592,13 @@ module Aha
 
     def select(seq : String | Bytes, sep : BitArray? = nil) : Array({Int32, Int32, Int32})
       select_batch([seq.is_a?(String) ? seq.to_slice : seq], sep)[0]
+    end
+
+    # The tokens of seq (aha_ac_select_batch with AHA_SELECT_TOKENS): the selected hits with their key index as value and,
+    # between them, one token per character (gap_runs: one per gap) with value -1; {start, end, value} in byte offsets, gap-free.
+    def tokens(seq : String | Bytes, sep : BitArray? = nil, gap_runs : Bool = false) : Array({Int32, Int32, Int32})
+      flags = SELECT_TOKENS | (gap_runs ? SELECT_GAP_RUNS : 0_u32)
+      select_batch([seq.is_a?(String) ? seq.to_slice : seq], sep, flags)[0]
     end
 
     # A replacement table of this handle (aha_repl_create): validated and uploaded once, used by any number of replace_batch

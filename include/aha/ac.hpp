@@ -289,6 +289,43 @@ class AC {
   // selection, ascending by start, is [(*doc_sel_offsets)[d], (*doc_sel_offsets)[d + 1]) of what is returned.  A sizing call first.
   std::vector<Hit> select_batch(std::string_view corpus, const std::vector<uint64_t> &doc_offsets,
                                 std::vector<uint64_t> *doc_sel_offsets = nullptr, uint64_t *n_hits = nullptr) const {
+    return select_flags(corpus, doc_offsets, 0, doc_sel_offsets, n_hits);
+  }
+  std::vector<Hit> select(std::string_view seq) const { return select_batch(seq, {0, seq.size()}); }
+
+  // Every document as a gap-free sequence of tokens (aha_ac_select_batch with AHA_SELECT_TOKENS; byte offsets): the hits of
+  // select_batch with their key index as value and, between them, one token per character (gap_runs: one per gap) with value
+  // -1.  Document d's tokens are [(*doc_tok_offsets)[d], (*doc_tok_offsets)[d + 1]) of what is returned.  A sizing call first.
+  std::vector<Hit> tokens_batch(std::string_view corpus, const std::vector<uint64_t> &doc_offsets, bool gap_runs = false,
+                                std::vector<uint64_t> *doc_tok_offsets = nullptr, uint64_t *n_hits = nullptr) const {
+    return select_flags(corpus, doc_offsets, AHA_SELECT_TOKENS | (gap_runs ? AHA_SELECT_GAP_RUNS : 0u), doc_tok_offsets, n_hits);
+  }
+  std::vector<Hit> tokens(std::string_view seq, bool gap_runs = false) const { return tokens_batch(seq, {0, seq.size()}, gap_runs); }
+
+  // The device-resident form (aha_ac_select_batch_device with AHA_SELECT_TOKENS): d_ pointers are memory of the handle's
+  // device, d_out holds cap tokens (null with cap 0: a sizing call), d_doc_tok_offsets D + 1 entries or null.  Returns the
+  // number of tokens; throws Error(AHA_E_CAPACITY) where cap is too small (*n_required = the tokens needed; nothing written).
+  uint64_t tokens_batch_device(const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs, uint64_t n_bytes, Hit *d_out,
+                               uint64_t cap, uint64_t *d_doc_tok_offsets = nullptr, bool gap_runs = false,
+                               uint64_t *n_required = nullptr, uint64_t *n_hits = nullptr, void *stream = nullptr) const {
+    aha_match_params p{};
+    p.struct_size = sizeof(p);
+    uint64_t n = 0, nh = 0;
+    const int32_t rc = aha_ac_select_batch_device(h_, d_corpus, d_doc_offsets, n_docs, n_bytes, &p,
+                                                  AHA_SELECT_TOKENS | (gap_runs ? AHA_SELECT_GAP_RUNS : 0u), d_out, cap,
+                                                  d_doc_tok_offsets, &n, &nh, stream);
+    if (n_required) *n_required = n;
+    if (rc != AHA_OK) {
+      const char *m = aha_last_error(h_);
+      throw Error(rc, (m && *m) ? m : aha_strerror(rc));
+    }
+    if (n_hits) *n_hits = nh;
+    return n;
+  }
+
+ private:
+  std::vector<Hit> select_flags(std::string_view corpus, const std::vector<uint64_t> &doc_offsets, uint32_t flags,
+                                std::vector<uint64_t> *doc_sel_offsets, uint64_t *n_hits) const {
     if (doc_offsets.empty()) throw Error(AHA_E_INVALID, "doc_offsets holds D + 1 entries");
     aha_match_params p{};
     p.struct_size = sizeof(p);
@@ -297,10 +334,10 @@ class AC {
     std::vector<uint64_t> dso(D + 1);
     std::vector<Hit> sel;
     uint64_t n = 0, nh = 0;
-    int32_t rc = aha_ac_select_batch(h_, text, doc_offsets.data(), D, &p, 0, nullptr, 0, dso.data(), &n, &nh);
+    int32_t rc = aha_ac_select_batch(h_, text, doc_offsets.data(), D, &p, flags, nullptr, 0, dso.data(), &n, &nh);
     if (rc == AHA_E_CAPACITY) {
       sel.resize(n);
-      rc = aha_ac_select_batch(h_, text, doc_offsets.data(), D, &p, 0, sel.data(), sel.size(), dso.data(), &n, &nh);
+      rc = aha_ac_select_batch(h_, text, doc_offsets.data(), D, &p, flags, sel.data(), sel.size(), dso.data(), &n, &nh);
     }
     if (rc != AHA_OK) {
       const char *m = aha_last_error(h_);
@@ -310,7 +347,8 @@ class AC {
     if (n_hits) *n_hits = nh;
     return sel;
   }
-  std::vector<Hit> select(std::string_view seq) const { return select_batch(seq, {0, seq.size()}); }
+
+ public:
 
   // A replacement table of this handle (aha_repl_create): per key its replacement, or keep -- validated and uploaded once,
   // immutable, freed with the object (before or after the handle).

@@ -744,7 +744,7 @@ int32_t aha_ac_cover_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uin
  * *n_selected = all selected hits; *n_hits (optional) = the match call's hit count.  cap is in hits.
  * AHA_E_CAPACITY: *n_selected is the required count and NONE of the caller's buffers is written (out == NULL with cap == 0
  * is a sizing call).  Every failing call leaves the caller's buffers untouched.
- * params->char_offsets != 0, params->longest != 0, any flag bit (flags is 0), n_selected == NULL, a NULL handle:
+ * params->char_offsets != 0, params->longest != 0, any flag bit but the token bits below, n_selected == NULL, a NULL handle:
  * AHA_E_INVALID; sep_size > 256: AHA_E_SEP_SIZE; a host-only handle: AHA_E_NO_DEVICE; all before any device work.  Bad
  * offsets: AHA_E_INVALID / AHA_E_TOO_LONG (the device entry finds them on the device).  N = 0, D = 0 and empty documents are
  * valid.  Like the count, cover and document-count calls it reads the handle's back-off state and never writes it.
@@ -762,13 +762,47 @@ int32_t aha_ac_cover_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uin
  * Out of scope so far: char offsets, groups (the substituted copy: the replace calls below; sequences in pieces: the feed
  * select calls below). */
 int32_t aha_ac_select_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc_offsets, uint64_t n_docs,
-                            const aha_match_params *params, uint32_t flags /* 0 */, aha_hit *out, uint64_t cap,
+                            const aha_match_params *params, uint32_t flags /* 0 or AHA_SELECT_* */, aha_hit *out, uint64_t cap,
                             uint64_t *doc_sel_offsets /* D+1 or NULL */, uint64_t *n_selected, uint64_t *n_hits /* or NULL */);
 /* Device-resident form: d_ pointers are HBM on the handle's device; *n_selected, *n_hits are host memory; blocks until final. */
 int32_t aha_ac_select_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
                                    uint64_t n_bytes, const aha_match_params *params, uint32_t flags, aha_hit *d_out, uint64_t cap,
                                    uint64_t *d_doc_sel_offsets /* D+1 or NULL */, uint64_t *n_selected,
                                    uint64_t *n_hits /* or NULL */, void *stream);
+
+/* ---- tokens: dictionary segmentation (forward maximum matching) of every document, through the select entries -----------
+ * No entry point of their own: the two select calls above with AHA_SELECT_TOKENS in flags.  flags == 0 is select as it was.
+ * AHA_SELECT_GAP_RUNS without AHA_SELECT_TOKENS, bits 1 and 2 and every other bit: AHA_E_INVALID, like every refusal of
+ * select (char_offsets, longest, NULL arguments, a host-only handle ...), all before any device work.
+ * For document d with bytes b[0..n) -- the CALLER's bytes, also on a folded handle -- and the selection S_d exactly as the
+ * flag-less call reports it on the same handle with the same params (a separator filter is allowed):
+ *   - position p is INSIDE when start <= p < end for some hit of S_d;
+ *   - p is a TOKEN START iff (a) p is the start of a hit of S_d, or (b) p is not inside and p == 0, or p - 1 is inside, or --
+ *     without AHA_SELECT_GAP_RUNS only -- (b[p] & 0xC0) != 0x80 (the lead-byte rule of AHA_FEED_CHARS);
+ *   - a token runs from its start to the next token start, to n for the last one;
+ *   - value = the key index for a token of kind (a), whose end is the hit's end; -1 for kind (b).
+ * So a token is the longest key that starts here or, where none starts, one character; with AHA_SELECT_GAP_RUNS a whole gap
+ * between two selected hits is ONE token.  The rule is bytewise and total: invalid UTF-8 is legal input, a stray run of
+ * continuation bytes joins the token in front of it, a document cut in the middle of a character starts a token there, and so
+ * does a hit that starts on a continuation byte (byte-level keys).  The tokens of a non-empty document partition it: the
+ * first starts at 0, each ends where the next starts, the last ends at n; an empty document has none.
+ * out[doc_sel_offsets[d] .. doc_sel_offsets[d+1]) = the tokens of document d as {start, end, value} relative to it, documents
+ * in order; *n_selected = all tokens, cap is in tokens, *n_hits = the match's hit count.  AHA_E_CAPACITY, the sizing call
+ * (out == NULL, cap == 0), "a failing call writes none of the caller's buffers", determinism, threading and neutrality
+ * towards the handle's back-off state are select's.  A batch without any hit is still tokenized; D = 0, N = 0 and batches
+ * of empty documents succeed with 0 tokens.
+ * Pipeline (aha_amd/csrc/scan_tokens.hip, DESIGN.md 4.14 "Tokens"): select's passes up to the walk; S = the selected spans
+ * ORed into a mask; T = the token starts, per mask word from the select, S and document-start words and the word's 32 text
+ * bytes (aha_amd/csrc/token_rule.hpp); the rank of T; the emit, in which a token's start and value come from its own bit and
+ * its end from the next one.  Device scratch: select's + 2 N / 8 bytes (S, T), nothing per token.  The ranges of whole
+ * documents tile ALL documents here, hits or none, and a range holds at most AHA_SELECT_HIT_BYTES bytes of hits and at most an
+ * eighth as many bytes of text (8 bytes of scratch per text byte; a document beyond either is a range of its own); a range
+ * without a hit is not matched.
+ * aha_ac_last_timing: as for select; ms_write = everything after the match.
+ * Out of scope: character offsets, groups, tokens of match_longest, a feed form (tokens of sequences in pieces), and id
+ * remapping for unknown characters, which callers do on the value column. */
+#define AHA_SELECT_TOKENS   4u  /* out receives the tokens of every document instead of the selection */
+#define AHA_SELECT_GAP_RUNS 8u  /* only with AHA_SELECT_TOKENS: a gap is ONE token, not one per character */
 
 /* ---- replace: the substituted copy of a batch, built on the device (pure additions to ABI 8) --------------------------------
  * The same batch, params, validation and errors as aha_ac_select_batch / _device; S_d = the selection of document d as those
