@@ -91,9 +91,11 @@ __global__ __launch_bounds__(kV2Threads) void ku_traverse(UnitDev U, V2Args M) {
   // per-wave clocks show; on another placement the words below would cost speed, never a result): the
   // issue arbiter serves the oldest wave of a SIMD first, so with equal priorities the four finish one after the other --
   // at 0.76, 0.81, 0.88 and 1.0 of the kernel on cfg 3 -- and a SIMD runs short of waves for the last quarter (14 % of the
-  // wave slots stand empty, profiles/wave_groups.txt).  Every round a wave notes its progress here and takes the priority
+  // wave slots stand empty, profiles/wave_groups.txt).  A wave notes its progress here and takes the priority
   // "number of waves of my SIMD that are ahead of me": they finish within 1 % of each other, the kernel 8.5 % sooner.
-  // Nobody waits for these words; a stale one costs a round at the wrong priority.
+  // Nobody waits for these words; a stale one costs a few rounds at the wrong priority.  Once per input line -- every fourth
+  // round -- is often enough: in every round the write, the read, its wait, four readfirstlane and the branch tree to an
+  // immediate s_setprio were ~40 instructions at the head of the round's chain (profiles/round_head.txt: -2.0 % on the step).
   uint32_t *prog = reinterpret_cast<uint32_t *>(smem + u_lds_prog(U.n_syms));
   if (threadIdx.x < kV2Threads / 64) prog[threadIdx.x] = 0u;
   __syncthreads();
@@ -117,7 +119,7 @@ __global__ __launch_bounds__(kV2Threads) void ku_traverse(UnitDev U, V2Args M) {
   const uint32_t wave_u = (uint32_t)__builtin_amdgcn_readfirstlane(wave);
   uint32_t *my_prog = prog + (wave_u & 3u) * 4u + (wave_u >> 2);
   const uint4 *simd_prog = reinterpret_cast<const uint4 *>(prog + (wave_u & 3u) * 4u);
-  uint32_t n_rounds = 0;  // rounds this wave has done, over all its tiles
+  uint32_t n_lines = 0;  // input lines this wave has requested (a line is four rounds), over all its tiles
 
   const uint64_t n_tiles = (M.n_chunks + kV2Threads - 1) / kV2Threads;
   for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
@@ -142,7 +144,7 @@ __global__ __launch_bounds__(kV2Threads) void ku_traverse(UnitDev U, V2Args M) {
     uint32_t lc = 0, lc_exact = 0;  // CHARS: characters of the chunk so far, or (lc_exact) of the document that started in it
     uint32_t E = 0, seq = 0;  // the state as one word (unit.hpp): base | filter << 22 | F1 | NFR | END; 0 = the root
     uint32_t pc = 0;          // the symbol that led to it
-    uint4 q1 = make_uint4(0, 0, 0, 0), q2 = q1, q3 = q1;  // the rest of the input line whose first piece was staged last
+    uint4 q0 = make_uint4(0, 0, 0, 0), q1 = q0, q2 = q0, q3 = q0;  // the line queue: the pieces requested and not yet staged
     uint32_t w[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // the window's bytes (the LDS row is rewritten from them)
     if (live) {
       dn = first_boundary(M.doc_off, D, (uint64_t)a);
@@ -157,42 +159,83 @@ __global__ __launch_bounds__(kV2Threads) void ku_traverse(UnitDev U, V2Args M) {
       }
     }
 
-    // Round r: the window holds the pieces r, r + 1, r + 2 of the lane's chunk (piece r + 2 is loaded now; the walk
-    // starts in piece -R, which the first round loads).  One round beyond the chunk: a unit that starts in the last
-    // bytes of the chunk continues in the next one.
-    // (the first piece loaded starts a 64-byte line, so that the line queue below is filled: R is rounded up to whole lines)
-    for (int r = -((R + 3) / 4) * 4 - 2; r <= rounds; r++) {
-      {  // the wave's issue priority for this round: the waves of its SIMD that have done more rounds (s_setprio takes an immediate)
-        n_rounds++;
-        if (lane == 0) *my_prog = n_rounds;
-        const uint4 pm = *simd_prog;
-        const uint32_t ahead = ((uint32_t)__builtin_amdgcn_readfirstlane(pm.x) > n_rounds) + ((uint32_t)__builtin_amdgcn_readfirstlane(pm.y) > n_rounds) +
-                               ((uint32_t)__builtin_amdgcn_readfirstlane(pm.z) > n_rounds) + ((uint32_t)__builtin_amdgcn_readfirstlane(pm.w) > n_rounds);
-        if (ahead == 0u)
-          __builtin_amdgcn_s_setprio(0);
-        else if (ahead == 1u)
-          __builtin_amdgcn_s_setprio(1);
-        else if (ahead == 2u)
-          __builtin_amdgcn_s_setprio(2);
-        else
-          __builtin_amdgcn_s_setprio(3);
+    // An input line is 64 bytes, four pieces; chunk starts are multiples of 64, so the piece's phase in its line is the same in
+    // every lane and a function of r alone.  The line is requested whole -- four 16-byte loads back to back, nothing of them
+    // touched in the round that asks -- into the queue q0..q3, ONE ROUND BEFORE its first piece is staged: in the round that
+    // takes the last queued piece.  Its latency falls into that round's trips (the first trip's hand-written wait covers it).
+    // The loads are plain C++ beside the probe's hidden asm loads (below), which is safe both ways: (1) a probe is always
+    // retired by the hand-written vmcnt(0) of its own trip, so none is in flight when a line is requested and hipcc's count of
+    // what is outstanding is exact there; (2) probes issued later are YOUNGER than the line's loads, memory returns in order
+    // and vmcnt(n) lets the n youngest stay out, so the wait hipcc puts in front of the queue's first use -- computed without
+    // the probes -- waits for more than it needs, never for less; (3) the probe's "memory" clobber keeps hipcc from moving
+    // the line's loads across a trip.  A round without a trip between request and use simply waits at hipcc's own wait.
+    // Lanes whose line lies outside the text -- before its start in the first chunk's warm-up, behind its end -- keep the zeros
+    // load16 gives there; the one line that holds the text's end and bytes behind it is patched through load16 in a rare
+    // wave-voted branch behind the loads.  (Left to one branch per piece, hipcc merged each load with the byte-wise path's
+    // values right behind it: four loads, four vmcnt(0), one HBM miss and three L2 round trips in sequence every four rounds.)
+    // The tile's first line is requested by a round of its own in front of the first -- it stages zeros and has no trip: a
+    // second copy of the request in front of the loop cost the trip loop three scalar registers it does not have.
+    auto request = [&](int64_t g) {
+      const int64_t room = N - g;  // (g is a multiple of 64 -- chunk starts are --, so no line holds the text's first byte and bytes before it)
+      const bool in = g >= 0 & room >= 4 * kUPiece;
+      q0 = q1 = q2 = q3 = make_uint4(0, 0, 0, 0);  // (what load16 gives outside the text)
+      if (in) {
+        const uint4 *p = reinterpret_cast<const uint4 *>(M.text + g);
+        q0 = p[0];
+        q1 = p[1];
+        q2 = p[2];
+        q3 = p[3];
       }
+      const bool edge = g >= 0 & room > 0 & room < 4 * kUPiece;  // the line holds the text's last byte, and bytes behind it
+      if (wany(edge)) {
+        if (edge) {
+          q0 = load16(M.text, g, N);
+          q1 = load16(M.text, g + kUPiece, N);
+          q2 = load16(M.text, g + 2 * kUPiece, N);
+          q3 = load16(M.text, g + 3 * kUPiece, N);
+        }
+      }
+    };
+    // The wave's issue priority, set once per input line (in the round that requests one): the waves of its SIMD that have
+    // requested more lines (s_setprio takes an immediate).  The progress word is written and the SIMD's four words are read
+    // in front of the line's loads, and looked at behind them: nothing waits for LDS at the round's head.
+    auto prio_note = [&]() -> uint4 {
+      n_lines++;
+      if (lane == 0) *my_prog = n_lines;
+      return *simd_prog;
+    };
+    auto prio_set = [&](const uint4 pm) {
+      const uint32_t ahead = ((uint32_t)__builtin_amdgcn_readfirstlane(pm.x) > n_lines) + ((uint32_t)__builtin_amdgcn_readfirstlane(pm.y) > n_lines) +
+                             ((uint32_t)__builtin_amdgcn_readfirstlane(pm.z) > n_lines) + ((uint32_t)__builtin_amdgcn_readfirstlane(pm.w) > n_lines);
+      if (ahead == 0u)
+        __builtin_amdgcn_s_setprio(0);
+      else if (ahead == 1u)
+        __builtin_amdgcn_s_setprio(1);
+      else if (ahead == 2u)
+        __builtin_amdgcn_s_setprio(2);
+      else
+        __builtin_amdgcn_s_setprio(3);
+    };
+
+    // Round r: the window holds the pieces r, r + 1, r + 2 of the lane's chunk (piece r + 2 is staged now; the walk
+    // starts in piece -R, which the first round stages).  One round beyond the chunk: a unit that starts in the last
+    // bytes of the chunk continues in the next one.
+    // (the first piece staged starts a 64-byte line, so that the line queue is filled whole: R is rounded up to whole lines)
+    const int r0 = -((R + 3) / 4) * 4 - 3;  // (one round in front of the first: it requests the tile's first line and stages nothing)
+    for (int r = r0; r <= rounds; r++) {
       const int64_t pb = a + (int64_t)r * kUPiece;
-      const int64_t pl = pb + 2 * kUPiece;  // the piece loaded in this round
+      const int64_t pl = pb + 2 * kUPiece;  // the piece staged in this round
       const int64_t pend = min(pb + kUWin, e);
       {
-        // a 64-byte line is four pieces: the round that starts a line loads all of it (three pieces wait in registers),
-        // so every input line is requested once while it is in flight.  Chunk starts are multiples of 64: uniform.
-        uint4 v;
-        if ((pl & 63) == 0) {
-          v = load16(M.text, pl, N);
-          q1 = load16(M.text, pl + 16, N);
-          q2 = load16(M.text, pl + 32, N);
-          q3 = load16(M.text, pl + 48, N);
-        } else {
-          v = q1;
-          q1 = q2;
-          q2 = q3;
+        const int phase = (r + 2) & 3;  // of the piece staged in this round, in its line
+        const uint4 v = q0;
+        q0 = q1;
+        q1 = q2;
+        q2 = q3;
+        if (phase == 3) {  // the queue is empty: the next line
+          const uint4 pm = prio_note();
+          request(pl + kUPiece);
+          prio_set(pm);
         }
 #pragma unroll
         for (int i = 0; i < 9; i++) w[i] = w[i + 4];

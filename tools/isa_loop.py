@@ -1,5 +1,6 @@
 import re,sys
-# usage: isa_loop.py file.s mangled-substring  -> stats of the innermost loop that holds the first ASMSTART global_load
+# usage: isa_loop.py file.s mangled-substring [--round]  -> stats of the innermost loop that holds the first ASMSTART global_load
+# --round: also the loop around it that requests the text (ku_traverse's round), outside that innermost loop -- see below
 src=open(sys.argv[1]).read().splitlines()
 key=sys.argv[2]
 # function range
@@ -47,3 +48,68 @@ for l in body:
 print(lab,'loop instructions:',len(body),cls)
 print('v_cndmask_b32_e32 reading an SALU-written VCC:',len(slow))
 for s in slow: print('   ',s)
+
+if '--round' in sys.argv[3:]:
+    # The round: the innermost loop around the trip loop whose text holds a 16-byte load.  Counted is the CHEAPEST static way
+    # once round it -- from its header to the trip loop's header and from the trip loop back to its header, every instruction
+    # 1, those of the trip loop's text 0, a conditional branch free to go either way (so a block that is skipped when exec is
+    # empty is not counted, and a rare path never is) -- that passes no 16-byte load (a round that starts no line) or four of
+    # them (one that does).  A tripwire against a round head that grows, not a cycle count.
+    def is_ins(i):
+        t=fn[i].split(';')[0].strip()
+        return bool(t) and not t.endswith(':') and not t.startswith('.') and not t.startswith('#')
+    lab_at={fn[i].split(':')[0]:i for i in range(len(fn)) if re.match(r'\.LBB\d+_\d+:',fn[i])}
+    def loop_of(i):  # (header, back edge) of the loop whose header label stands in line i
+        l=fn[i].split(':')[0]
+        b=[j for j,t in enumerate(fn) if re.search(r's_c?branch\w*\s+'+re.escape(l)+r'\b',t)]
+        return (i,max(b)) if b and max(b)>i else None
+    outer=[lp for lp in (loop_of(i) for i in sorted(lab_at.values())) if lp and lp[0]<hs and lp[1]>be]
+    rh,rb=max((lp for lp in outer if any('global_load_dwordx4' in t for t in fn[lp[0]:lp[1]+1])),key=lambda lp:lp[0])
+    def succ(i):
+        t=fn[i].split(';')[0].split()
+        out=[]
+        if is_ins(i) and t[0].startswith('s_cbranch') or is_ins(i) and t[0]=='s_branch': out.append(lab_at[t[1]])
+        if not (is_ins(i) and t[0] in ('s_branch','s_endpgm')) and i+1<len(fn): out.append(i+1)
+        return out
+    def cost(i): return 1 if is_ins(i) and not hs<=i<=be else 0
+    def is_ld(i): return is_ins(i) and fn[i].split()[0]=='global_load_dwordx4'
+    import heapq
+    def walk(src,dst,want):  # cheapest way from line src to line dst inside the round that passes `want` 16-byte loads; its lines
+        best={(src,0):0}; pq=[(0,src,0,(src,))]
+        while pq:
+            d,i,k,path=heapq.heappop(pq)
+            if d>best.get((i,k),1<<30): continue
+            for j in succ(i):
+                k2=min(4,k+(1 if is_ld(i) else 0))
+                if j==dst and k2==want: return d+cost(i),path
+                if not rh<=j<=rb or j==rh: continue
+                d2=d+cost(i)
+                if d2<best.get((j,k2),1<<30):
+                    best[(j,k2)]=d2; heapq.heappush(pq,(d2,j,k2,path+(j,)))
+        return None,()
+    tail,tp=walk(hs,rh,0)
+    for name,want in (('no line',0),('line',4)):
+        head,hp=walk(rh,hs,want)
+        ops=[fn[i].split()[0] for i in hp+tp if cost(i)]
+        print('round',fn[rh].split(':')[0],name+':',head+tail,'instructions outside the trip loop (head',head,'tail',str(tail)+')',
+              {k:sum(1 for o in ops if o.startswith(k)) for k in ('v_','s_','ds_','global_','v_cvt_f64','s_waitcnt','s_setprio')})
+    # the line's request: a run of four 16-byte loads in one basic block, and what stands between the first and the last
+    ld=[i for i in range(rh,rb+1) if is_ld(i)]
+    runs=[ld[j:j+4] for j in range(len(ld)-3) if all(is_ins(i) or not fn[i].strip() or fn[i].lstrip().startswith(';') for i in range(ld[j],ld[j+3]))
+          and not any(is_ins(i) and fn[i].split()[0].startswith(('s_cbranch','s_branch')) for i in range(ld[j],ld[j+3]))]
+    print('runs of four 16-byte loads in one block:',len(runs),'vmcnt waits inside:',
+          sum(1 for r in runs for i in range(r[0],r[3]) if 'vmcnt' in fn[i]))
+    # s_setprio only behind the round's first scalar branch (the line branch), on the side that reaches the loads
+    br=next(i for i in range(rh,rb+1) if is_ins(i) and fn[i].split()[0].startswith('s_cbranch_scc'))
+    def reach(src):
+        seen={src}; st=[src]
+        while st:
+            i=st.pop()
+            for j in succ(i):
+                if rh<j<=rb and not hs<=j<=be and j not in seen: seen.add(j); st.append(j)
+        return seen
+    sides=[reach(j) for j in succ(br)]
+    prio=[i for i in range(len(fn)) if is_ins(i) and fn[i].split()[0]=='s_setprio']
+    quiet=[s for s in sides if not any(is_ld(i) for i in s)]
+    print('s_setprio:',len(prio),'outside the round:',sum(1 for i in prio if not rh<=i<=rb),
+          'sides of the line branch without a load:',len(quiet),'s_setprio on them:',sum(1 for s in quiet for i in s if i in prio))
