@@ -45,6 +45,8 @@ AHA_RULE_MAX_TERMS = 64
 AHA_FEED_CHARS = 1
 AHA_FEED_FOLD = 4
 AHA_FEED_SELECT_FINAL = 1
+AHA_FEED_SELECT_TOKENS = 4  # (the values of AHA_SELECT_TOKENS / AHA_SELECT_GAP_RUNS)
+AHA_FEED_SELECT_GAP_RUNS = 8
 AHA_FEED_REPLACE_FINAL = AHA_FEED_SELECT_FINAL
 AHA_FEED_GREP_FINAL = 2
 AHA_IMG_SLOTS, AHA_IMG_END_KEY, AHA_IMG_KEY_LN, AHA_IMG_KEY_CNT, AHA_IMG_KEY_KC = 0, 1, 2, 3, 4

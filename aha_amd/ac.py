@@ -1985,8 +1985,11 @@ class Feed:
         "piece_bases" uint64[D], "piece_hold" uint32[D]: the bytes at the end of the sequence whose fate is still open,
         "n_hits"}.  Byte feeds only, and only for sequences fed through select calls alone since their last reset.
         cap None: a sizing call first (a call that does not fit changes nothing)."""
+        return self._select_host(corpus, piece_offsets, seq_ids, N.AHA_FEED_SELECT_FINAL if final else 0, cap, "piece_sel_offsets")
+
+    def _select_host(self, corpus, piece_offsets, seq_ids, flags, cap, key):
+        """aha_feed_select_batch with `flags`; key: the info name of the pieces' offsets into the result"""
         corpus, piece_offsets, seq_ids, D = self._pieces_host(corpus, piece_offsets, seq_ids)
-        flags = N.AHA_FEED_SELECT_FINAL if final else 0
         pso = np.zeros(D + 1, dtype=np.uint64)
         bases = np.zeros(max(D, 1), dtype=np.uint64)
         hold = np.zeros(max(D, 1), dtype=np.uint32)
@@ -1997,7 +2000,7 @@ class Feed:
                                          _ptr(bases), _ptr(hold), C.byref(n), C.byref(nh))
             if rc != N.AHA_E_CAPACITY:
                 self._check(rc)
-                return np.zeros(0, dtype=HIT_DTYPE), {"piece_sel_offsets": pso, "piece_bases": bases[:D], "piece_hold": hold[:D],
+                return np.zeros(0, dtype=HIT_DTYPE), {key: pso, "piece_bases": bases[:D], "piece_hold": hold[:D],
                                                       "n_hits": int(nh.value)}
             cap = int(n.value)
         out = np.zeros(max(int(cap), 1), dtype=HIT_DTYPE)
@@ -2006,11 +2009,10 @@ class Feed:
         if rc == N.AHA_E_CAPACITY:
             raise self._capacity(rc, n, "n_required")
         self._check(rc)
-        return out[: int(n.value)], {"piece_sel_offsets": pso, "piece_bases": bases[:D], "piece_hold": hold[:D],
-                                     "n_hits": int(nh.value)}
+        return out[: int(n.value)], {key: pso, "piece_bases": bases[:D], "piece_hold": hold[:D], "n_hits": int(nh.value)}
 
     def select_batch_device(self, corpus, piece_offsets, seq_ids, out, piece_sel_offsets=None, piece_bases=None,
-                            piece_hold=None, final=False, cap=None, stream=None):
+                            piece_hold=None, final=False, cap=None, stream=None, _flags=0):
         """Device-resident form on torch CUDA tensors: uint8 corpus, int64/uint64 piece offsets, int32/uint32 sequence ids,
         out int32 [cap, 3] or None (a sizing call), piece_sel_offsets / piece_bases int64/uint64 [D+1] / [D] or None,
         piece_hold int32/uint32 [D] or None.  -> (n_selected, n_hits); raises AhaError(AHA_E_CAPACITY) when out is too small
@@ -2029,7 +2031,8 @@ class Feed:
         n, nh = C.c_uint64(0), C.c_uint64(0)
         rc = N.lib().aha_feed_select_batch_device(
             self._h, corpus.data_ptr(), piece_offsets.data_ptr(), seq_ids.data_ptr(), D, n_bytes,
-            N.AHA_FEED_SELECT_FINAL if final else 0, _dptr(out) if cap else None, cap, _dptr(piece_sel_offsets), _dptr(piece_bases),
+            (N.AHA_FEED_SELECT_FINAL if final else 0) | _flags, _dptr(out) if cap else None, cap, _dptr(piece_sel_offsets),
+            _dptr(piece_bases),
             _dptr(piece_hold), C.byref(n), C.byref(nh), C.c_void_p(s))
         if rc == N.AHA_E_CAPACITY:
             raise self._capacity(rc, n, "n_required")
@@ -2043,6 +2046,44 @@ class Feed:
                                        np.array([seq], dtype=np.uint32), final=final)
         base = int(info["piece_bases"][0])
         return [Hit(s + base, e + base, v) for s, e, v in hits.tolist()]
+
+    # -- feed tokens: dictionary segmentation of sequences in pieces (aha_feed_select_batch* with AHA_FEED_SELECT_TOKENS) ---
+    @staticmethod
+    def _token_flags(final, gap_runs):
+        return (N.AHA_FEED_SELECT_FINAL if final else 0) | N.AHA_FEED_SELECT_TOKENS | (N.AHA_FEED_SELECT_GAP_RUNS if gap_runs else 0)
+
+    def tokens_batch(self, corpus, piece_offsets, seq_ids, final=False, gap_runs=False, cap=None):
+        """The tokens that this call settles (aha_feed_select_batch with AHA_FEED_SELECT_TOKENS): per sequence the feed keeps a
+        token cursor t behind which everything has been reported; the call reports the tokens of the sequence from t up to
+        the select cursor it leaves, without the last where nothing yet says that it ends there (a character whose next lead
+        byte has not arrived).  With gap_runs gaps are not cut into characters and are handed out in parts as they come;
+        with final=True everything is reported and the named sequences start again from length 0.  -> (tokens HIT_DTYPE, info)
+        with offsets relative to the piece, value = the key or -1, and info = {"piece_tok_offsets" uint64[D+1], "piece_bases"
+        uint64[D], "piece_hold" uint32[D]: the bytes behind t, "n_hits"}.  The tokens of a sequence's calls, made absolute
+        and concatenated, are AC.tokens_batch of the whole (with gap_runs: after joining -1 tokens that touch).  Byte feeds
+        only, and only for sequences fed through token calls alone since their last reset or final call.  cap None: a sizing
+        call first (a call that does not fit changes nothing)."""
+        return self._select_host(corpus, piece_offsets, seq_ids, self._token_flags(final, gap_runs), cap, "piece_tok_offsets")
+
+    def tokens_batch_device(self, corpus, piece_offsets, seq_ids, out, piece_tok_offsets=None, piece_bases=None, piece_hold=None,
+                            final=False, gap_runs=False, cap=None, stream=None):
+        """Device-resident form on torch CUDA tensors, as select_batch_device: out int32 [cap, 3] or None (a sizing call).
+        -> (n_tokens, n_hits); raises AhaError(AHA_E_CAPACITY) when out is too small (e.n_required = the tokens needed); nothing
+        is written then and the feed is unchanged."""
+        return self.select_batch_device(corpus, piece_offsets, seq_ids, out, piece_tok_offsets, piece_bases, piece_hold, final=final,
+                                        cap=cap, stream=stream, _flags=self._token_flags(False, gap_runs))
+
+    def tokens(self, seq, piece, final=False, gap_runs=False):
+        """The next piece of one sequence: the tokens it settles, as Hits with absolute offsets (value -1: no key)."""
+        b = _b(piece)
+        toks, info = self.tokens_batch(np.frombuffer(b, dtype=np.uint8), np.array([0, len(b)], dtype=np.uint64),
+                                       np.array([seq], dtype=np.uint32), final=final, gap_runs=gap_runs)
+        base = int(info["piece_bases"][0])
+        return [Hit(s + base, e + base, v) for s, e, v in toks.tolist()]
+
+    def segmenter(self, gap_runs=False):
+        """A Segmenter over this feed: push(seq, piece) / finish(seq) give the tokens of every sequence with their bytes."""
+        return Segmenter(self, gap_runs)
 
     # -- feed replace: the substituted stream of sequences in pieces, built on the device (aha_feed_replace_batch*) --------
     def replace_batch(self, corpus, piece_offsets, seq_ids, repl_or_table, final=False):
@@ -2277,6 +2318,40 @@ class Replacer:
 
     def finish(self, seq):
         """The bytes still open for seq, substituted; the sequence starts again from length 0."""
+        return self._step(seq, b"", True)
+
+
+class Segmenter:
+    """Dictionary segmentation of sequences that arrive in pieces (Feed.segmenter), host arithmetic on Feed.tokens_batch.
+    push(seq, piece) returns the tokens that can no longer change as [(token bytes, key or -1)], finish(seq) the rest, and
+    b"".join of all token bytes is the sequence.  In character mode the tokens are those of AC.segment of the whole sequence;
+    with gap_runs the parts of a gap are handed out as they come.  The bytes behind the token cursor (piece_hold) are held on
+    the host: a character that arrives byte by byte has no length limit, the feed's state per sequence has."""
+
+    def __init__(self, feed, gap_runs=False):
+        self._feed, self._gap_runs = feed, bool(gap_runs)
+        self._held = {}  # seq -> the source bytes behind the token cursor
+
+    def _step(self, seq, piece, final):
+        b = _b(piece)
+        toks, info = self._feed.tokens_batch(np.frombuffer(b, dtype=np.uint8), np.array([0, len(b)], dtype=np.uint64),
+                                             np.array([seq], dtype=np.uint32), final=final, gap_runs=self._gap_runs)
+        # held || piece = the sequence from the old token cursor on; the piece's first byte is at len(held) of it
+        held = self._held.get(seq, b"")
+        src = held + b
+        hold = int(info["piece_hold"][0])
+        out = [(src[s + len(held):e + len(held)], v) for s, e, v in toks.tolist()]
+        if hold:
+            self._held[seq] = src[len(src) - hold:]
+        else:
+            self._held.pop(seq, None)
+        return out
+
+    def push(self, seq, piece):
+        return self._step(seq, piece, False)
+
+    def finish(self, seq):
+        """The tokens still open for seq; the sequence starts again from length 0."""
         return self._step(seq, b"", True)
 
 

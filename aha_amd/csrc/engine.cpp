@@ -99,6 +99,8 @@ static void doccount_setup(aha_ac *ac) {
   ac->rule_table_bytes = env("AHA_RULE_TABLE_BYTES", 1ull << 30, 4, 1ull << 36);
   // the passes after the traversal: the cap of their grids (tests: 1 and 3, so that every lane strides)
   ac->post_blocks = (uint32_t)env("AHA_POST_BLOCKS", 0, 1, 1u << 20);
+  // feed token calls: how long a token may stay open, so that int32 offsets hold it (tests: a few bytes)
+  ac->feed_token_open = (uint32_t)env("AHA_FEED_TOKEN_OPEN", 0x3FFFFFFFull, 1, 0x3FFFFFFFull);
 }
 
 uint32_t post_grid(const aha_ac *ac) { return ac->post_blocks ? ac->post_blocks : 8u * std::max<uint32_t>(ac->v2_grid, 64u); }

@@ -23,6 +23,12 @@
 //   scan_feedselect.hip    the pieces' extended positions, L from the sequences' tails and the hits, the masks, the walk up to the
 //                          frontier, the rank (one read-back: the total) -- above cap -> AHA_E_CAPACITY, nothing committed
 //   kfs_emit, kfd_commit + kfs_commit   the selection, the offsets; then the feed's state and, behind it, the select state
+// A token call (aha_feed_select_batch* with AHA_FEED_SELECT_TOKENS) is a select call up to the rank (feed_select_settle), then
+//   scan_feedtokens.hip    per piece the cursors it finds and leaves; the inside mask (ktk_spans) and the token starts over the
+//                          extended positions, their rank; per piece the edge decision (feedtok_edge.hpp), the token counts
+//                          scanned (one read-back: the total and the verdict) -- a token open beyond the bound -> AHA_E_TOO_LONG,
+//                          above cap -> AHA_E_CAPACITY, nothing committed
+//   kft_emit, kfd_commit + kfs_commit + kft_commit   the tokens, the offsets; then the feed's state, the select state, the token state
 // A replace call (aha_feed_replace_batch*) is a select call up to the rank (feed_select_settle), then
 //   kfs_emit               the settled selection into scratch instead of a caller buffer
 //   scan_feedreplace.hip   per piece the open bytes in front of it and the cursor it will leave; the staged text T[c0 .. c1) of
@@ -133,6 +139,8 @@ struct aha_feed {
   // select and replace calls: allocated by the feed's first one (8 W + 16 bytes per sequence)
   FeedSelSeq *d_sel = nullptr;
   unsigned long long *d_tail = nullptr;
+  // token calls: allocated by the feed's first one (16 bytes per sequence)
+  FeedTokSeq *d_tok = nullptr;
   // grep calls: allocated by the feed's first one (32 bytes per sequence); the delimiter its first successful one fixed
   FeedGrepSeq *d_grep = nullptr;
   int grep_delim = -1;
@@ -204,6 +212,11 @@ int32_t feed_windows(aha_feed *f, Scratch *sc, FeedArgs &F, hipStream_t s, bool 
   }
   if (bad & 4u) {
     tls_err = "feed select: bytes of a named sequence went through a match, count or cover call; select works again after its reset";
+    return AHA_E_INVALID;
+  }
+  if (bad & 16u) {
+    tls_err = "feed select with tokens: bytes of a named sequence went through a call that reports no tokens; tokens work again after "
+              "its reset or its FINAL call";
     return AHA_E_INVALID;
   }
   if (bad & 2u) {
@@ -422,6 +435,7 @@ int32_t feed_select_settle(aha_feed *f, Scratch *sc, FeedArgs &F, uint32_t flags
   S = FeedSelArgs{};
   S.sseq = f->d_sel;
   S.tail = f->d_tail;
+  S.tseq = f->d_tok;
   S.final = (flags & AHA_FEED_SELECT_FINAL) ? 1u : 0u;
   S.eoff = (uint64_t *)fs_reserve(kFsExtOff, (D + 1) * 8);
   S.n0 = (uint64_t *)fs_reserve(kFsBases, std::max<uint64_t>(D, 1) * 8);
@@ -520,6 +534,91 @@ int32_t feed_select(aha_feed *f, Scratch *sc, FeedArgs &F, uint32_t flags, aha_h
   if (d_pso) HIPCHK(ac, hipMemcpyAsync(d_pso, S.pso, (D + 1) * 8, hipMemcpyDeviceToDevice, s));
   feed_launch_commit(F, s);
   feedsel_launch_commit(F, S, s);
+  HIPCHK(ac, hipGetLastError());
+  HIPCHK(ac, hipStreamSynchronize(s));
+  return AHA_OK;
+}
+
+// a whole token call on device-resident pieces (AHA_FEED_SELECT_TOKENS; scan_feedtokens.hip): a select call's settle, the piece
+// bounds, the inside and start masks over the extended positions, their rank, the edge decisions and the pieces' offsets, one
+// read-back of the token total and the verdict.  Everything up to it writes scratch only; then the tokens, the offsets, the two
+// commits of a select call and the token state.
+int32_t feed_tokens(aha_feed *f, Scratch *sc, FeedArgs &F, uint32_t flags, aha_hit *d_out, uint64_t cap, uint64_t *d_pto,
+                    uint32_t *d_hold, hipStream_t s, uint64_t *n_tokens, uint64_t *n_hits) {
+  aha_ac *ac = f->ac;
+  const uint64_t D = F.D;
+  if (!f->d_tok) {  // the feed's first token call: no sequence has token state yet
+    const size_t bytes = (size_t)f->n_seqs * sizeof(FeedTokSeq);
+    void *a = nullptr;
+    if (hipMalloc(&a, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      return no_memory("token state");
+    }
+    hipError_t e = hipMemsetAsync(a, 0, bytes, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+      (void)hipFree(a);
+      HIPCHK(ac, e);
+    }
+    f->d_tok = (FeedTokSeq *)a;
+  }
+  F.tok = f->d_tok;
+  FeedSelArgs S{};
+  uint64_t n_sel = 0;
+  int32_t rc = feed_select_settle(f, sc, F, flags & AHA_FEED_SELECT_FINAL, S, s, &n_sel, n_hits);
+  if (rc) return rc;
+  auto ft_reserve = [sc](FeedTokenSlot slot, size_t bytes) { return reserve_ptr(sc->ftokbuf[slot], bytes, kGrowEighth); };
+  const uint64_t NE = S.NE, n_words = (NE + 31) / 32, n_blk = select_rank_blocks(NE);
+  FeedTokArgs K{};
+  K.tseq = f->d_tok;
+  K.gap_runs = (flags & AHA_FEED_SELECT_GAP_RUNS) ? 1u : 0u;
+  K.bound = ac->feed_token_open;
+  K.piece = (FeedTokPiece *)ft_reserve(kFtPieces, std::max<uint64_t>(D, 1) * sizeof(FeedTokPiece));
+  K.raw = (uint64_t *)ft_reserve(kFtRawOff, (D + 1) * 8);
+  K.pto = (uint64_t *)ft_reserve(kFtTokOff, (D + 1) * 8);
+  uint64_t *tot = (uint64_t *)ft_reserve(kFtTotal, 16);
+  if (!K.piece || !K.raw || !K.pto || !tot) return no_scratch();
+  K.total = tot;
+  K.verdict = (uint32_t *)(tot + 1);
+  HIPCHK(ac, hipMemsetAsync(tot, 0, 16, s));
+  const uint32_t blocks = select_blocks(ac);
+  feedtok_launch_bounds(F, S, K, blocks, s);
+  if (NE) {
+    uint32_t *masks = (uint32_t *)ft_reserve(kFtMasks, 2 * n_words * 4);
+    K.blk = (unsigned long long *)ft_reserve(kFtBlocks, (n_blk + 1) * 8);
+    if (!masks || !K.blk) return no_scratch();
+    K.inside = masks;
+    K.starts = masks + n_words;
+    HIPCHK(ac, hipMemsetAsync(K.inside, 0, n_words * 4, s));
+    tokens_launch_spans((const uint64_t *)S.L, NE, S.select, K.inside, blocks, s);
+    feedtok_launch_starts(F, S, K, blocks, s);
+    select_launch_rank(K.starts, NE, (uint64_t *)K.blk, blocks, s);
+    select_launch_rank_docs(K.starts, (const uint64_t *)K.blk, S.eoff, D + 1, 0, K.raw, blocks, s);
+  } else {
+    HIPCHK(ac, hipMemsetAsync(K.raw, 0, (D + 1) * 8, s));
+  }
+  feedtok_launch_edge(F, S, K, blocks, s);
+  HIPCHK(ac, hipGetLastError());
+  HIPCHK(ac, hipMemcpyAsync(f->h_pin, tot, 16, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  const uint64_t total = f->h_pin[0];
+  if ((uint32_t)f->h_pin[1] & 1u) {
+    tls_err = "feed select with tokens: a token would stay open for more than 2^30 - 1 bytes (a run of continuation bytes); a FINAL "
+              "call or AHA_FEED_SELECT_GAP_RUNS closes it";
+    return AHA_E_TOO_LONG;
+  }
+  *n_tokens = total;
+  if (total > cap) {
+    tls_err = "output buffer too small";
+    return AHA_E_CAPACITY;
+  }
+  K.out = reinterpret_cast<int32_t *>(d_out);
+  K.hold = d_hold;
+  if (total) feedtok_launch_emit(F, S, K, blocks, s);
+  if (d_pto) HIPCHK(ac, hipMemcpyAsync(d_pto, K.pto, (D + 1) * 8, hipMemcpyDeviceToDevice, s));
+  feed_launch_commit(F, s);
+  feedsel_launch_commit(F, S, s);  // (S.hold is null: a token call's hold is the token cursor's)
+  feedtok_launch_commit(F, S, K, blocks, s);
   HIPCHK(ac, hipGetLastError());
   HIPCHK(ac, hipStreamSynchronize(s));
   return AHA_OK;
@@ -1290,7 +1389,9 @@ int32_t bytes_only_refused(const aha_feed *f, const char *what) {
 
 int32_t feed_select_args(const aha_feed *f, const uint64_t *piece_offsets, const uint32_t *seq_ids, uint64_t n_pieces, uint32_t flags,
                          const aha_hit *out, uint64_t cap, const uint64_t *n_selected, bool no_corpus) {
-  if (!f || !n_selected || !piece_offsets || (n_pieces && !seq_ids) || (cap && !out) || no_corpus || (flags & ~AHA_FEED_SELECT_FINAL))
+  if (!f || !n_selected || !piece_offsets || (n_pieces && !seq_ids) || (cap && !out) || no_corpus ||
+      (flags & ~(AHA_FEED_SELECT_FINAL | AHA_FEED_SELECT_TOKENS | AHA_FEED_SELECT_GAP_RUNS)) ||
+      ((flags & AHA_FEED_SELECT_GAP_RUNS) && !(flags & AHA_FEED_SELECT_TOKENS)))
     return AHA_E_INVALID;
   if (bad_feed(f)) return AHA_E_NO_DEVICE;
   return bytes_only_refused(f, "select");
@@ -1448,6 +1549,7 @@ void aha_feed_free(aha_feed *f) {
     if (f->d_ctx) (void)hipFree(f->d_ctx);
     if (f->d_sel) (void)hipFree(f->d_sel);
     if (f->d_tail) (void)hipFree(f->d_tail);
+    if (f->d_tok) (void)hipFree(f->d_tok);
     if (f->d_grep) (void)hipFree(f->d_grep);
     if (f->d_long) (void)hipFree(f->d_long);
     if (f->h_pin) (void)hipHostFree(f->h_pin);
@@ -1467,6 +1569,8 @@ int32_t aha_feed_reset(aha_feed *f, uint32_t seq) {
   if ((rc = clear_seqs(f, f->d_seqs, sizeof(FeedSeq), 2 * sizeof(uint64_t), seq))) return rc;
   // the select state too: a sequence of length 0 has no open hits (its tail is never read) and its cursor is 0
   if ((rc = clear_seqs(f, f->d_sel, sizeof(FeedSelSeq), sizeof(FeedSelSeq), seq))) return rc;
+  // ... and the token state: no token is open
+  if ((rc = clear_seqs(f, f->d_tok, sizeof(FeedTokSeq), sizeof(FeedTokSeq), seq))) return rc;
   // ... and the grep state: no record is open, none is closed
   if ((rc = clear_seqs(f, f->d_grep, sizeof(FeedGrepSeq), sizeof(FeedGrepSeq), seq))) return rc;
   // ... and a longest feed's carried state: the root, nothing pending
@@ -1664,7 +1768,8 @@ int32_t aha_feed_select_batch_device(aha_feed *f, const uint8_t *d_corpus, const
   FeedArgs F = feed_args(d_corpus, d_piece_offsets, d_seq_ids, n_pieces, n_bytes, nullptr, d_piece_bases);
   *n_selected = 0;
   if (n_hits) *n_hits = 0;
-  return feed_select(f, call.sc(), F, flags, d_out, cap, d_piece_sel_offsets, d_piece_hold, (hipStream_t)stream, n_selected, n_hits);
+  auto *run = (flags & AHA_FEED_SELECT_TOKENS) ? feed_tokens : feed_select;
+  return run(f, call.sc(), F, flags, d_out, cap, d_piece_sel_offsets, d_piece_hold, (hipStream_t)stream, n_selected, n_hits);
 }
 
 int32_t aha_feed_select_batch(aha_feed *f, const uint8_t *corpus, const uint64_t *piece_offsets, const uint32_t *seq_ids,
@@ -1676,14 +1781,16 @@ int32_t aha_feed_select_batch(aha_feed *f, const uint8_t *corpus, const uint64_t
   Staged B;
   if ((rc = stage_pieces(f, call, corpus, piece_offsets, seq_ids, n_pieces, {kWantHold}, B))) return rc;
   const uint64_t D = n_pieces;
-  // (the selection is at most the caller's cap, and at most one hit per extended position)
-  aha_hit *d_out = (aha_hit *)reserve(f, kHOut, std::min<uint64_t>(cap, B.n_bytes + D * f->W) * sizeof(aha_hit));
+  // (the selection is at most the caller's cap, and at most one hit per extended position; a token call adds a carried token
+  // per piece)
+  aha_hit *d_out = (aha_hit *)reserve(f, kHOut, std::min<uint64_t>(cap, B.n_bytes + D * f->W + D) * sizeof(aha_hit));
   if (!d_out) return no_memory("staging buffers");
   FeedArgs F = feed_args(B.corpus, B.off, B.ids, D, B.n_bytes, nullptr, B.bases);
   *n_selected = 0;
   if (n_hits) *n_hits = 0;
   uint64_t total = 0;
-  rc = feed_select(f, call->sc(), F, flags, d_out, cap, B.pho, B.hold, f->hs, &total, n_hits);
+  auto *run = (flags & AHA_FEED_SELECT_TOKENS) ? feed_tokens : feed_select;
+  rc = run(f, call->sc(), F, flags, d_out, cap, B.pho, B.hold, f->hs, &total, n_hits);
   if (rc == AHA_E_CAPACITY) *n_selected = total;
   if (rc) return rc;
   if ((rc = fetch(f, {{out, d_out, total * sizeof(aha_hit)}, {piece_sel_offsets, B.pho, (D + 1) * 8}, {piece_bases, B.bases, D * 8},

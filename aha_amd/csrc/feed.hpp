@@ -1,5 +1,6 @@
 // feed.hpp -- what feed.cpp (the feed entry points of the C ABI) and its kernels (scan_feed.hip, scan_feedselect.hip,
-// scan_feedreplace.hip, scan_feedsep.hip, scan_feedgrep.hip, scan_feedlongest.hip, scan_feedfold.hip) share.  Library-internal.
+// scan_feedreplace.hip, scan_feedsep.hip, scan_feedgrep.hip, scan_feedlongest.hip, scan_feedfold.hip, scan_feedtokens.hip) share.
+// Library-internal.
 #pragma once
 #include <cstdint>
 
@@ -19,6 +20,13 @@ struct FeedSeq {
 struct FeedSelSeq {
   unsigned long long seen;    // bytes that went through select or replace calls since open / reset / a FINAL call
   unsigned long long cursor;  // c: everything in front of it is final -- inside a reported hit or in no selected hit ever
+};
+
+// what a feed keeps per sequence for token calls (aha_feed_select_batch* with AHA_FEED_SELECT_TOKENS), allocated by the feed's
+// first one (16 bytes).  A token call is a select call too: it keeps the select state as a select call does
+struct FeedTokSeq {
+  unsigned long long seen;  // bytes that went through token calls since open / reset / a FINAL call
+  unsigned long long t;     // the token cursor, t <= c: everything in front of it has been reported as tokens
 };
 
 // what a feed keeps per sequence for grep calls (aha_feed_grep_batch*), allocated by the feed's first one (32 bytes).  The
@@ -53,7 +61,8 @@ struct FeedArgs {
   int32_t chars;
   FeedSeq *seqs;               // [n_seqs]
   uint8_t *ctx;                // [2][n_seqs][W]
-  uint32_t *verdict;           // [1]: bit 0 invalid offsets or ids, bit 1 a piece too long, bit 2 / 3 the select / grep state is behind
+  uint32_t *verdict;           // [1]: bit 0 invalid offsets or ids, bit 1 a piece too long, bit 2 / 3 / 4 the select / grep / token
+                               // state is behind
   uint64_t *win_total;         // [1]: bytes of the window batch
   uint8_t *win;                // the window batch [X_0..X_{D-1} | ctx_0.. | P'_0..]
   uint64_t *woff;              // [3D+1] its document offsets
@@ -78,6 +87,8 @@ struct FeedArgs {
   uint32_t *back;              // [D] bytes in front of the piece inside a hit that ends in it, or null (cleared by the host)
   // select calls (aha_feed_select_batch*): kfd_check refuses a sequence whose bytes did not all go through select calls
   const FeedSelSeq *sel;       // [n_seqs], or null (every other call); verdict bit 2
+  // token calls: kfd_check also refuses a sequence of length > 0 whose bytes did not all go through token calls
+  const FeedTokSeq *tok;       // [n_seqs], or null (every other call); verdict bit 4
   // calls on a feed with a separator filter (aha_feed_open_params; scan_feedsep.hip): the call's true hits also hold the hits
   // that end on the context's last byte -- the last edge[d] hits of ctx_d alone
   uint64_t *edge;              // [D], or null (every call on a plain feed)
@@ -139,6 +150,33 @@ struct FeedSelArgs {
   uint64_t *pso;               // [D+1] the pieces' offsets into the selection (scratch until the call is known to succeed)
   uint32_t *hold;              // [D] the caller's piece_hold, or null
   int32_t *out;                // the caller's hits
+  FeedTokSeq *tseq;            // [n_seqs] the token state, or null (no token call yet): a FINAL call clears the sequence's
+};
+
+// what a token call keeps per piece between its passes (32 bytes; scan_feedtokens.hip)
+constexpr uint32_t kFeedTokCarried = 1u;  // t0 < c0: the piece's tokens begin with the open token carried in
+constexpr uint32_t kFeedTokOpen = 2u;     // the last token of T[t0 .. c1) stays open: it is not reported
+struct FeedTokPiece {
+  unsigned long long t0, t1;  // the token cursor the call finds and leaves
+  uint32_t c0, c1;            // the select cursor the call finds and leaves, as extended positions of the piece
+  uint32_t flags;             // kFeedTokCarried | kFeedTokOpen
+  uint32_t count;             // tokens the call reports for the piece
+};
+
+// what the kernels of a token call take beside FeedArgs and FeedSelArgs (scan_feedtokens.hip)
+struct FeedTokArgs {
+  FeedTokSeq *tseq;            // [n_seqs]
+  uint32_t gap_runs;           // AHA_FEED_SELECT_GAP_RUNS
+  uint64_t bound;              // a non-final call may leave at most this many bytes behind the token cursor (AHA_FEED_TOKEN_OPEN)
+  FeedTokPiece *piece;         // [D]
+  uint32_t *inside, *starts;   // S and T of scan_tokens.hip: ceil(NE / 32) whole words each; S clear
+  unsigned long long *blk;     // the rank blocks of T
+  uint64_t *raw;               // [D+1] the starts in front of every piece's extended positions
+  uint64_t *pto;               // [D+1] the pieces' offsets into the tokens (scratch until the call is known to succeed)
+  uint64_t *total;             // [1] pto[D]
+  uint32_t *verdict;           // [1] bit 0: a token would stay open beyond the bound
+  uint32_t *hold;              // [D] the caller's piece_hold, or null
+  int32_t *out;                // the caller's tokens
 };
 
 // what the kernels of a replace call take beside FeedArgs and FeedSelArgs (scan_feedreplace.hip).  Piece d stages
@@ -198,6 +236,15 @@ void feedsel_launch_longest(const FeedArgs &F, const FeedSelArgs &S, uint32_t ma
 void feedsel_launch_walk(const FeedArgs &F, const FeedSelArgs &S, uint32_t max_blocks, void *stream);     // select, cend
 void feedsel_launch_emit(const FeedArgs &F, const FeedSelArgs &S, uint32_t max_blocks, void *stream);     // out
 void feedsel_launch_commit(const FeedArgs &F, const FeedSelArgs &S, void *stream);   // behind feed_launch_commit: tails, cursors, hold
+// token calls (scan_feedtokens.hip), in this order behind feed_select_settle; the spans between bounds and starts are
+// tokens_launch_spans (scan_tokens.hip), the ranks between starts and edge select_launch_rank and select_launch_rank_docs
+void feedtok_launch_bounds(const FeedArgs &F, const FeedSelArgs &S, const FeedTokArgs &K, uint32_t max_blocks, void *stream);  // piece
+void feedtok_launch_starts(const FeedArgs &F, const FeedSelArgs &S, const FeedTokArgs &K, uint32_t max_blocks, void *stream);  // T
+// t1, the counts, the verdict (kft_edge); pto and the total (kft_offsets)
+void feedtok_launch_edge(const FeedArgs &F, const FeedSelArgs &S, const FeedTokArgs &K, uint32_t max_blocks, void *stream);
+void feedtok_launch_emit(const FeedArgs &F, const FeedSelArgs &S, const FeedTokArgs &K, uint32_t max_blocks, void *stream);  // out
+// behind feedsel_launch_commit: the token state, hold
+void feedtok_launch_commit(const FeedArgs &F, const FeedSelArgs &S, const FeedTokArgs &K, uint32_t max_blocks, void *stream);
 // replace calls (scan_feedreplace.hip): behind the walk and kfs_emit into scratch, in front of both commits
 void feedrep_launch_layout(const FeedArgs &F, const FeedSelArgs &S, const FeedRepArgs &R, void *stream);  // hold0, ext_off, bias
 // ext; max_bytes: a bound of ext_off[D] known to the host (it sizes the grid)

@@ -133,6 +133,16 @@ enum FeedSelectSlot {
   kFsSelOff,   // the pieces' offsets into the selection, until the call is known to succeed
   kFsCount
 };
+// ftokbuf: feed token calls (feed.cpp feed_tokens; scan_feedtokens.hip), beside a feed select call's fselbuf
+enum FeedTokenSlot {
+  kFtMasks,    // S, the bytes inside a selected hit, and T, the token starts, one bit per extended position each
+  kFtBlocks,   // the token starts before every 64 words of T, the total behind them
+  kFtPieces,   // per piece the cursors it finds and leaves, its flags and its token count (FeedTokPiece)
+  kFtRawOff,   // the token starts in front of every piece's extended positions
+  kFtTokOff,   // the pieces' offsets into the tokens, until the call is known to succeed
+  kFtTotal,    // the call's token total and its verdict (one read-back)
+  kFtCount
+};
 // frepbuf: feed replace calls (feed.cpp feed_replace; scan_feedreplace.hip, scan_replace.hip)
 enum FeedReplaceSlot {
   kFrRows,    // the settled selection, piece by piece, relative to the piece (kfs_emit into scratch), 12 bytes each
@@ -226,6 +236,7 @@ struct Scratch {
   Buf selbuf[kSelCount];
   Buf repbuf[kRepCount];
   Buf fselbuf[kFsCount];
+  Buf ftokbuf[kFtCount];
   Buf frepbuf[kFrCount];
   Buf fsepbuf[kFpCount];
   Buf grpbuf[kGrpCount];
@@ -243,6 +254,7 @@ struct Scratch {
     for (auto &b : sc.selbuf) fn(b);
     for (auto &b : sc.repbuf) fn(b);
     for (auto &b : sc.fselbuf) fn(b);
+    for (auto &b : sc.ftokbuf) fn(b);
     for (auto &b : sc.frepbuf) fn(b);
     for (auto &b : sc.fsepbuf) fn(b);
     for (auto &b : sc.grpbuf) fn(b);
@@ -350,6 +362,8 @@ struct aha_ac {
   uint32_t rep_blocks = 0;  // replace calls: the cap of the scan's and the copy's grids (AHA_REPLACE_BLOCKS; 0: the default)
   uint32_t grep_blocks = 0;  // records and grep calls: the cap of their grids (AHA_GREP_BLOCKS; 0: the default)
   uint32_t post_blocks = 0;  // the passes after the traversal: the cap of their grids (AHA_POST_BLOCKS; 0: the default)
+  // feed token calls: the bytes a non-final call may leave behind a sequence's token cursor (AHA_FEED_TOKEN_OPEN; tests lower it)
+  uint32_t feed_token_open = 0x3FFFFFFFu;
   uint64_t rule_table_bytes = 0;  // rule grep: the bound of the class-count table in scratch (AHA_RULE_TABLE_BYTES)
   uint64_t cls_hit_bytes = 0;  // class-counts calls: the bound of a range's hit buffer (AHA_CLASS_HIT_BYTES)
   uint32_t cls_blocks = 0;  // ... and the cap of their kernels' grids (AHA_CLASS_BLOCKS; 0: the default)
@@ -443,7 +457,7 @@ uint64_t scratch_bytes(const Scratch *sc);
 // THE allocator of the grow-only buffers: b holds at least `bytes` afterwards, or nothing (the HIP error is returned, the
 // runtime's sticky one cleared).  What a new buffer gets beyond `bytes` is its family's rule:
 enum Grow {
-  kGrowEighth,   // bytes + bytes / 8 + 256 (v2buf, covbuf, selbuf, repbuf, fselbuf, frepbuf, fsepbuf, grpbuf, fgrpbuf, clsbuf, flngbuf)
+  kGrowEighth,   // bytes + bytes / 8 + 256 (v2buf, covbuf, selbuf, repbuf, fselbuf, ftokbuf, frepbuf, fsepbuf, grpbuf, fgrpbuf, clsbuf, flngbuf)
   kGrowQuarter,  // bytes + bytes / 4 + 4096 (cntbuf, hostbuf)
   kGrowOrExact   // an eighth, else exactly `bytes`; `bytes` is what it records (dcbuf: what is known to be there)
 };

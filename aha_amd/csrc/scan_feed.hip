@@ -75,6 +75,8 @@ __global__ void kfd_check(FeedArgs F) {
       bad |= 1u;
     else if (F.sel && F.sel[id].seen != F.seqs[id].bytes)  // a select call: bytes of the sequence went past its select state
       bad |= 4u;
+    else if (F.tok && F.seqs[id].bytes && F.tok[id].seen != F.seqs[id].bytes)  // a token call: ... past its token state
+      bad |= 16u;
     else if (F.grep && F.grep[id].seen != F.seqs[id].bytes)  // a grep call: bytes of the sequence went past its grep state
       bad |= 8u;
   }

@@ -138,6 +138,7 @@ __global__ void __launch_bounds__(kFsThreads) kfs_commit(FeedArgs F, FeedSelArgs
       if (S.final) {  // as after aha_feed_reset: a sequence of length 0 has an empty context
         F.seqs[id].bytes = 0;
         F.seqs[id].chars = 0;
+        if (S.tseq) S.tseq[id] = FeedTokSeq{0ull, 0ull};  // ... and no token is open (scan_feedtokens.hip)
       }
       if (S.hold) S.hold[d] = S.final ? 0u : (uint32_t)(n1 - c);
     }

@@ -16,7 +16,8 @@
 //                L[p] where p is a selected hit's start, else -1 -- and, where p > 0, out[r - 1].end: the token in front ends
 //                where this one starts, at its document's end where p starts a document.  The range's last token ends with the
 //                range.  Every field is written exactly once: no atomics.
-// Out of scope: character offsets, groups, tokens of match_longest, a feed form, id remapping (include/aha_hip.h).
+// The feed form (tokens of sequences in pieces) is scan_feedtokens.hip, which shares ktk_spans.
+// Out of scope: character offsets, groups, tokens of match_longest, id remapping (include/aha_hip.h).
 // Vector loads, stores and atomics and plain C++ only.
 #include <hip/hip_runtime.h>
 

@@ -320,6 +320,8 @@ lib LibAhaHip
                                   n_hits : UInt64*, stream : Void*) : Int32
   # feed select: the leftmost-longest, non-overlapping hits of the same pieces as far as they are settled (byte feeds)
   FEED_SELECT_FINAL = 1_u32
+  FEED_SELECT_TOKENS   = 4_u32 # AHA_FEED_SELECT_TOKENS: the tokens the call settles instead of the selection
+  FEED_SELECT_GAP_RUNS = 8_u32 # AHA_FEED_SELECT_GAP_RUNS: only with FEED_SELECT_TOKENS, gaps are not cut into characters
   fun aha_feed_select_batch(f : Feed, corpus : UInt8*, piece_offsets : UInt64*, seq_ids : UInt32*, n_pieces : UInt64,
                             flags : UInt32, out : Hit*, cap : UInt64, piece_sel_offsets : UInt64*, piece_bases : UInt64*,
                             piece_hold : UInt32*, n_selected : UInt64*, n_hits : UInt64*) : Int32
@@ -1006,10 +1008,24 @@ module Aha
     # Byte feeds only, and only for sequences fed through select since their reset.  (Uncompiled, as the rest of this class;
     # tests/test_feed_select_host.py checks that the lib block binds both entry points.)
     def select(seq : Int, piece : Bytes | String, final : Bool = false) : {Array(Hit), UInt32}
+      select_flags(seq, piece, final ? LibAhaHip::FEED_SELECT_FINAL : 0_u32)
+    end
+
+    # The tokens (dictionary segmentation, as AC#tokens of the whole sequence) that the next piece of one sequence settles
+    # (aha_feed_select_batch with AHA_FEED_SELECT_TOKENS), with absolute offsets: {tokens, hold} -- value: the key or -1;
+    # hold: the bytes behind the token cursor, which no token holds yet (a character whose next lead byte has not arrived).
+    # gap_runs: gaps are not cut into characters and come in parts.  final: everything is reported and the sequence starts
+    # again from length 0.  Byte feeds only, and only for sequences fed through token calls since their reset or final call.
+    def tokens(seq : Int, piece : Bytes | String, final : Bool = false, gap_runs : Bool = false) : {Array(Hit), UInt32}
+      flags = LibAhaHip::FEED_SELECT_TOKENS | (final ? LibAhaHip::FEED_SELECT_FINAL : 0_u32) |
+              (gap_runs ? LibAhaHip::FEED_SELECT_GAP_RUNS : 0_u32)
+      select_flags(seq, piece, flags)
+    end
+
+    private def select_flags(seq : Int, piece : Bytes | String, flags : UInt32) : {Array(Hit), UInt32}
       bytes = piece.is_a?(String) ? piece.to_slice : piece
       offs = [0_u64, bytes.size.to_u64]
       ids = [seq.to_u32]
-      flags = final ? LibAhaHip::FEED_SELECT_FINAL : 0_u32
       cap = 64_u64
       loop do
         buf = Slice(LibAhaHip::Hit).new(cap.to_i32)

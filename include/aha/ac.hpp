@@ -1022,11 +1022,15 @@ class Feed {
   // may be negative, end may be <= 0).  Byte feeds only, and only for sequences fed through select calls since their reset.
   std::vector<Hit> select_batch(std::string_view corpus, const std::vector<uint64_t> &piece_offsets,
                                 const std::vector<uint32_t> &seq_ids, bool final = false, Select *info = nullptr) {
+    return select_flags(corpus, piece_offsets, seq_ids, final ? AHA_FEED_SELECT_FINAL : 0u, info);
+  }
+  // aha_feed_select_batch with `flags`: the selection, or with AHA_FEED_SELECT_TOKENS the tokens
+  std::vector<Hit> select_flags(std::string_view corpus, const std::vector<uint64_t> &piece_offsets,
+                                const std::vector<uint32_t> &seq_ids, uint32_t flags, Select *info) {
     if (piece_offsets.empty()) throw Error(AHA_E_INVALID, "piece_offsets holds D + 1 entries");
     const uint64_t D = piece_offsets.size() - 1;
     if (seq_ids.size() != D) throw Error(AHA_E_INVALID, "one sequence id per piece");
     if (corpus.size() < piece_offsets.back()) throw Error(AHA_E_INVALID, "the corpus is shorter than the last offset");
-    const uint32_t flags = final ? AHA_FEED_SELECT_FINAL : 0u;
     Select c;
     c.piece_sel_offsets.assign(D + 1, 0);
     c.bases.assign(D, 0);
@@ -1057,6 +1061,29 @@ class Feed {
       h.end += (int32_t)c.bases[0];
     }
     return hits;
+  }
+  // The tokens that this call settles (aha_feed_select_batch with AHA_FEED_SELECT_TOKENS): dictionary segmentation, as
+  // AC::tokens_batch of the whole sequence, of sequences in pieces.  Per sequence the feed keeps a token cursor behind which
+  // everything has been reported; the call reports the tokens from there up to the select cursor it leaves, without the last
+  // where nothing yet says that it ends there.  value = the key or -1; gap_runs: gaps are not cut into characters and come in
+  // parts; final: everything is reported and the named sequences start again from length 0.  info->piece_sel_offsets are the
+  // pieces' offsets into the tokens, info->piece_hold the bytes behind the token cursor (it may exceed Lmax - 1).  Byte feeds
+  // only, and only for sequences fed through token calls since their reset or final call.
+  std::vector<Hit> tokens_batch(std::string_view corpus, const std::vector<uint64_t> &piece_offsets,
+                                const std::vector<uint32_t> &seq_ids, bool final = false, bool gap_runs = false,
+                                Select *info = nullptr) {
+    return select_flags(corpus, piece_offsets, seq_ids,
+                        (final ? AHA_FEED_SELECT_FINAL : 0u) | AHA_FEED_SELECT_TOKENS | (gap_runs ? AHA_FEED_SELECT_GAP_RUNS : 0u), info);
+  }
+  // the next piece of one sequence: the tokens it settles, with absolute offsets (they must fit Int32)
+  std::vector<Hit> tokens(uint32_t seq, std::string_view piece, bool final = false, bool gap_runs = false) {
+    Select c;
+    auto toks = tokens_batch(piece, {0, piece.size()}, {seq}, final, gap_runs, &c);
+    for (auto &t : toks) {
+      t.start += (int32_t)c.bases[0];
+      t.end += (int32_t)c.bases[0];
+    }
+    return toks;
   }
   // What a replace call of pieces gives beside the bytes (aha_feed_replace_batch).
   struct Replace {

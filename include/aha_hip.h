@@ -799,8 +799,8 @@ int32_t aha_ac_select_batch_device(aha_ac *ac, const uint8_t *d_corpus, const ui
  * eighth as many bytes of text (8 bytes of scratch per text byte; a document beyond either is a range of its own); a range
  * without a hit is not matched.
  * aha_ac_last_timing: as for select; ms_write = everything after the match.
- * Out of scope: character offsets, groups, tokens of match_longest, a feed form (tokens of sequences in pieces), and id
- * remapping for unknown characters, which callers do on the value column. */
+ * Feeds: aha_feed_select_batch* with AHA_FEED_SELECT_TOKENS below.  Out of scope: character offsets, groups, tokens of
+ * match_longest, and id remapping for unknown characters, which callers do on the value column. */
 #define AHA_SELECT_TOKENS   4u  /* out receives the tokens of every document instead of the selection */
 #define AHA_SELECT_GAP_RUNS 8u  /* only with AHA_SELECT_TOKENS: a gap is ONE token, not one per character */
 
@@ -1199,6 +1199,65 @@ int32_t aha_feed_select_batch_device(aha_feed *f, const uint8_t *d_corpus, const
                                      aha_hit *d_out, uint64_t cap, uint64_t *d_piece_sel_offsets /* D+1 or NULL */,
                                      uint64_t *d_piece_bases /* D or NULL */, uint32_t *d_piece_hold /* D or NULL */,
                                      uint64_t *n_selected, uint64_t *n_hits /* or NULL */, void *stream);
+
+/* Feed tokens: dictionary segmentation (AHA_SELECT_TOKENS: forward maximum matching) of sequences that arrive in pieces.  No
+ * new entry point: the two feed select entries with AHA_FEED_SELECT_TOKENS (bit 2 of flags) report tokens instead of the
+ * selection; AHA_FEED_SELECT_GAP_RUNS (bit 3, only with bit 2) leaves gaps whole instead of cutting them into characters.  The
+ * values are those of the batch call's flags.  flags & ~(1 | 4 | 8), or 8 without 4: AHA_E_INVALID before any device work; bit
+ * 1 stays refused.  Without bit 2 the entries behave exactly as above.  aha_feed_replace_batch* takes FINAL only.
+ * T, S(T), W, F(n) and the select cursor c as for feed select.  A token call IS a select call for the feed's select state: it
+ * keeps seen bytes, cursor and tails as a select call with the same FINAL bit does.  Beside them the feed keeps a token cursor
+ * t <= c per sequence, 0 at open, at reset and after FINAL: everything in front of t has been reported as tokens, and [t, c) is
+ * the front part of a gap token (value -1) that is still open; t == c: none.  A selected hit is a whole token the moment it is
+ * reported.  A call takes a sequence from n0 to n1 bytes, finds (c0, t0) and leaves (c1, t1): c1 is the cursor feed select
+ * leaves, max(c0, end of the last hit the call settles, F(n1)), n1 under FINAL; S1 = the hits of S(T[0..n1)) with a start in
+ * [t0, F(n1)) ([t0, n1) under FINAL), all inside [t0, c1); Tok1 = the tokens the batch rule (aha_ac_select_batch with
+ * AHA_SELECT_TOKENS and the call's GAP_RUNS bit) gives for T[t0..c1) as one document under S1, shifted by t0.  c1 is a certain
+ * boundary iff the call is FINAL, or GAP_RUNS is set, or c1 is the end of the last hit of S1, or c1 < n1 and
+ * (T[c1] & 0xC0) != 0x80.  If c1 is certain the call reports all of Tok1 and t1 = c1; otherwise Tok1 without its last token,
+ * and t1 = that token's start (a gap token that ends at c1, and nothing yet says that it ends there).  Tok1 empty: nothing,
+ * t1 = t0.  The reported tokens tile [t0, t1).
+ * Tokens are aha_hit {start, end, value} relative to the piece's first byte (start may be far below -W: a character whose bytes
+ * arrive one by one), value = the key or -1.  piece_bases[d] = n0; piece_hold[d] = n1 - t1 (0 after FINAL; it may exceed W: the
+ * select cursor's own hold is not reported by a token call); piece_sel_offsets = the tokens of each piece; *n_selected = the
+ * tokens of the call, cap is in tokens; *n_hits as for feed select.
+ * The stream laws: cut a sequence anywhere into pieces, empty ones included, feed them through token calls with the same
+ * GAP_RUNS bit, the last with FINAL, turn the tokens to absolute offsets and concatenate.  Character mode: the result is the
+ * batch token call on the whole sequence as one document, token for token, bit for bit, invalid UTF-8 included.  GAP_RUNS: the
+ * same after joining -1 tokens that touch -- a gap is handed out up to c1 at every call and never held (the batch call never
+ * has two gap tokens that touch, so the join is unambiguous).
+ * Examples (absolute offsets).  Keys ab (0), abcde (1), W = 4: "xab" -> [], hold 3; "cd" -> [(0,1,-1)] (relative (-3,-2,-1)),
+ * hold 4; "eab" -> [(1,6,1)], hold 2; FINAL, empty -> [(6,8,0)], hold 0.  Key U+662F over U+6211 U+662F U+4E2D (9 bytes, W = 2)
+ * cut 4 | 4 | 1: [], hold 4; [(0,3,-1),(3,6,0)], hold 2; [], hold 3 (byte 7 is a continuation byte: the character from 6
+ * stays open); FINAL -> [(6,9,-1)].  Key a (W = 0), "xa\xC3" | "\xA9" | "y": [(0,1,-1),(1,2,0)], hold 1; [], hold 2;
+ * [(2,4,-1)], hold 1; FINAL -> [(4,5,-1)].  GAP_RUNS, key ab, "zzzzzz" | "zzab" | "zz" FINAL: [(0,5,-1)], hold 1;
+ * [(5,8,-1),(8,10,0)], hold 0; [(10,12,-1)] -- joined, the gap is (0,8,-1).
+ * State and mixing: 16 bytes per sequence (bytes seen by token calls, t), allocated by the feed's first token call;
+ * aha_feed_reset clears it with the select state.  A token call is valid for a sequence iff the sequence has length 0 (it is
+ * fresh then, with t = 0) or all of its bytes since open, reset or FINAL went through token calls; otherwise AHA_E_INVALID,
+ * found on the device beside select's own check (aha_last_error names "tokens"), and nothing changes.  Select and replace
+ * calls are valid after token calls -- the select state is theirs -- and leave the token state as it is (their FINAL restarts
+ * the sequence and with it t); after one of them the sequence takes token calls again from its next reset or FINAL.  Calls
+ * with and without GAP_RUNS may alternate on one sequence: each applies its own bit from t0 on (the laws are stated for a
+ * constant bit).
+ * Everything feed select refuses is refused the same way (AHA_FEED_CHARS, a separator filter, a longest feed, a feed folded
+ * beyond ASCII).  On an AHA_OPT_FOLD_ASCII handle the lead-byte rule reads the caller's bytes.  Every failing call changes
+ * nothing, AHA_E_CAPACITY included (*n_selected = the required token count; out == NULL with cap == 0 is a sizing call).
+ * start and end are int32 and a run of stray continuation bytes keeps a character-mode token open without bound: a call that
+ * would leave n1 - t1 > 0x3FFFFFFF answers AHA_E_TOO_LONG (found on the device before anything is written; nothing changes).
+ * A FINAL call closes the token and GAP_RUNS never holds, so neither meets the bound.  (The bound is read from
+ * AHA_FEED_TOKEN_OPEN when the handle is compiled: tests lower it.)
+ * Pipeline (feed.cpp feed_tokens, scan_feedtokens.hip; DESIGN.md 4.10 "Feed tokens"): a select call up to its rank; then per
+ * piece c0, c1 and t0; the inside mask of the settled selection (ktk_spans); the start mask by the rule of token_rule.hpp with
+ * c0 for the document's start where t0 == c0, the continuation bits from the sequence's context bank and from the piece
+ * (16-byte loads aligned to the address, nothing outside [corpus, corpus + N) read; with GAP_RUNS no text at all); its rank;
+ * per piece the edge decision (feedtok_edge.hpp) and the token count; the pieces' offsets and the total (one read-back with
+ * the verdict); then the tokens by ranked slots, the two commits of a select call and the token state.  Device memory beyond a
+ * feed select call's: 2 bits per extended position, their rank blocks and 48 bytes per piece.  Nothing per token.
+ * Out of scope: token calls on char, separator-filter, longest and folded feeds; groups; character offsets; a device-side
+ * hold buffer; id remapping. */
+#define AHA_FEED_SELECT_TOKENS 4u   /* out receives the tokens this call settles instead of the selection */
+#define AHA_FEED_SELECT_GAP_RUNS 8u /* only with AHA_FEED_SELECT_TOKENS: gaps are not cut into characters */
 
 /* Feed replace: the substituted stream of sequences that arrive in pieces, built on the device (pure additions to ABI 8).  The
  * same pieces and flags as aha_feed_select_batch*, on a BYTE feed, and a replacement table of the feed's handle as for
