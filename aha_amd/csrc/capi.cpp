@@ -39,20 +39,11 @@ void free_scratch(Scratch *sc, bool all) {
     b = Buf();
   });
   sc->dc_rows_clear = false;
-  void **scratch[] = {(void **)&sc->d_counts, (void **)&sc->d_leads, (void **)&sc->d_blk_hits, (void **)&sc->d_blk_leads,
-                      (void **)&sc->d_docg};
-  for (void **p : scratch) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-  }
-  sc->cap_chunks = sc->cap_blocks = sc->cap_docs = 0;
   // the counter block went with v2buf[kCursor]: a block allocated later -- even at the same address -- holds words nobody knows
   sc->reset_cursor();
   if (!all) return;
-  if (sc->d_totals) (void)hipFree(sc->d_totals);
   if (sc->h_totals) (void)hipHostFree(sc->h_totals);
   if (sc->h_v2) (void)hipHostFree(sc->h_v2);
-  sc->d_totals = nullptr;
   sc->h_totals = nullptr;
   sc->h_v2 = nullptr;
   sc->h_v2_dev = nullptr;
@@ -68,7 +59,6 @@ void free_scratch(Scratch *sc, bool all) {
 uint64_t scratch_bytes(const Scratch *sc) {
   uint64_t n = 0;
   Scratch::each_buf(*sc, [&n](const Buf &b) { n += b.bytes; });
-  n += sc->cap_chunks * 8 + sc->cap_blocks * 16 + sc->cap_docs * 8;
   return n;
 }
 
@@ -144,42 +134,6 @@ int32_t upload_image(aha_ac *ac, const Image &img) {
   if ((rc = upload(ac, ln, &d.key_ln))) return rc;
   if ((rc = upload(ac, a.key_cnt, &d.key_cnt))) return rc;
   if ((rc = upload(ac, a.key_kc, &d.key_kc))) return rc;
-  return AHA_OK;
-}
-
-int32_t ensure_scratch(aha_ac *ac, Scratch *sc, uint64_t n_chunks, uint64_t n_blocks, uint64_t n_docs) {
-  if (n_chunks > sc->cap_chunks) {
-    if (sc->d_counts) (void)hipFree(sc->d_counts);
-    if (sc->d_leads) (void)hipFree(sc->d_leads);
-    sc->d_counts = sc->d_leads = nullptr;
-    sc->cap_chunks = 0;
-    uint64_t n = n_chunks + n_chunks / 8 + 1024;
-    HIPCHK(ac, hipMalloc((void **)&sc->d_counts, n * sizeof(uint32_t)));
-    HIPCHK(ac, hipMalloc((void **)&sc->d_leads, n * sizeof(uint32_t)));
-    sc->cap_chunks = n;
-  }
-  if (n_blocks > sc->cap_blocks) {
-    if (sc->d_blk_hits) (void)hipFree(sc->d_blk_hits);
-    if (sc->d_blk_leads) (void)hipFree(sc->d_blk_leads);
-    sc->d_blk_hits = sc->d_blk_leads = nullptr;
-    sc->cap_blocks = 0;
-    uint64_t n = n_blocks + n_blocks / 8 + 64;
-    HIPCHK(ac, hipMalloc((void **)&sc->d_blk_hits, n * sizeof(uint64_t)));
-    HIPCHK(ac, hipMalloc((void **)&sc->d_blk_leads, n * sizeof(uint64_t)));
-    sc->cap_blocks = n;
-  }
-  if (n_docs + 1 > sc->cap_docs) {
-    if (sc->d_docg) (void)hipFree(sc->d_docg);
-    sc->d_docg = nullptr;
-    sc->cap_docs = 0;
-    uint64_t n = n_docs + 1 + n_docs / 8 + 64;
-    HIPCHK(ac, hipMalloc((void **)&sc->d_docg, n * sizeof(uint64_t)));
-    sc->cap_docs = n;
-  }
-  if (!sc->d_totals) {
-    HIPCHK(ac, hipMalloc((void **)&sc->d_totals, 2 * sizeof(uint64_t)));
-    HIPCHK(ac, hipHostMalloc((void **)&sc->h_totals, 2 * sizeof(uint64_t), hipHostMallocDefault));
-  }
   return AHA_OK;
 }
 
@@ -866,10 +820,13 @@ int32_t aha_ac_last_timing(const aha_ac *ac, aha_timing *t) {
   return AHA_OK;
 }
 
-static int32_t match_batch_device_impl(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets,
-                                       uint64_t n_docs, uint64_t n_bytes, const aha_match_params *params,
-                                       aha_hit *d_out, uint64_t cap, uint64_t *d_doc_hit_offsets, uint64_t *n_hits,
-                                       void *stream, bool offsets_checked, const PackOut *pk = nullptr);
+// a device entry's arguments as a batch: nobody has looked at the offsets yet; the ABI's stream is cast here, once
+static Batch abi_batch(const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
+                       const aha_match_params *params, void *stream) {
+  return unchecked_batch(d_corpus, d_doc_offsets, n_docs, n_bytes, params, (hipStream_t)stream);
+}
+static int32_t match_batch_device_impl(aha_ac *ac, Scratch *sc, const Batch &B, const HitOut &out, uint64_t *n_hits,
+                                       const PackOut *pk = nullptr);
 
 int32_t aha_ac_match_batch_device(aha_ac *ac, const uint8_t *d_corpus,
                                   const uint64_t *d_doc_offsets, uint64_t n_docs,
@@ -879,14 +836,13 @@ int32_t aha_ac_match_batch_device(aha_ac *ac, const uint8_t *d_corpus,
   if (!ac || !n_hits || !d_doc_offsets) return AHA_E_INVALID;
   if (ac->device < 0) return no_device();
   Lease lease(ac);
-  return match_batch_device_impl(ac, lease.get(), d_corpus, d_doc_offsets, n_docs, n_bytes, params, d_out, cap,
-                                 d_doc_hit_offsets, n_hits, stream, false);
+  return match_batch_device_impl(ac, lease.get(), abi_batch(d_corpus, d_doc_offsets, n_docs, n_bytes, params, stream),
+                                 HitOut{d_out, cap, d_doc_hit_offsets}, n_hits);
 }
 
-static int32_t match_batch_device_impl(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets,
-                                       uint64_t n_docs, uint64_t n_bytes, const aha_match_params *params,
-                                       aha_hit *d_out, uint64_t cap, uint64_t *d_doc_hit_offsets, uint64_t *n_hits,
-                                       void *stream, bool offsets_checked, const PackOut *pk) {
+static int32_t match_batch_device_impl(aha_ac *ac, Scratch *sc, const Batch &B, const HitOut &out, uint64_t *n_hits,
+                                       const PackOut *pk) {
+  const uint64_t cap = out.cap;
   if (pk) {
     if (!ac || !pk->d_words || !pk->d_n_words) return AHA_E_INVALID;
     if (stream_fmt(ac).len_bits == 0 && ac->aut.n_keys > (1u << 20)) {
@@ -898,17 +854,15 @@ static int32_t match_batch_device_impl(aha_ac *ac, Scratch *sc, const uint8_t *d
       return AHA_E_CAPACITY;
     }
   }
-  bool packed = false;
-  int32_t rc = device_match(ac, sc, d_corpus, d_doc_offsets, n_docs, n_bytes, params, d_out, cap, d_doc_hit_offsets, n_hits,
-                                 stream, offsets_checked, pk, &packed);
-  if (rc == AHA_OK && pk && !packed) {
+  int32_t rc = device_match(ac, sc, B, out, n_hits);
+  if (rc == AHA_OK && pk) {
     // the three pack kernels over the hits, behind the match on the same stream (the expansion writing the words itself was
     // built and measured in round 5: +0.40 ms on the match against the pack's 0.25, profiles/r05_fused_exchange_stream.txt)
     DeviceGuard g(ac->device);
-    launch_hits_pack4(reinterpret_cast<const int32_t *>(d_out), *n_hits, pk->d_words,
-                      reinterpret_cast<unsigned long long *>(pk->d_n_words), stream_fmt(ac), stream);
+    launch_hits_pack4(reinterpret_cast<const int32_t *>(out.d_out), *n_hits, pk->d_words,
+                      reinterpret_cast<unsigned long long *>(pk->d_n_words), stream_fmt(ac), B.stream);
     HIPCHK(ac, hipGetLastError());
-    HIPCHK(ac, hipStreamSynchronize((hipStream_t)stream));
+    HIPCHK(ac, hipStreamSynchronize(B.stream));
   }
   return rc;
 }
@@ -921,8 +875,8 @@ int32_t aha_ac_match_batch_device_stream(aha_ac *ac, const uint8_t *d_corpus, co
   if (ac->device < 0) return no_device();
   Lease lease(ac);
   const PackOut pk{d_words, cap_words, d_n_words};
-  return match_batch_device_impl(ac, lease.get(), d_corpus, d_doc_offsets, n_docs, n_bytes, params, d_out, cap, d_doc_hit_offsets,
-                                 n_hits, stream, false, &pk);
+  return match_batch_device_impl(ac, lease.get(), abi_batch(d_corpus, d_doc_offsets, n_docs, n_bytes, params, stream),
+                                 HitOut{d_out, cap, d_doc_hit_offsets}, n_hits, &pk);
 }
 
 // Host-buffer entry (what `Aha::AC#match(Bytes)`, src/aha/ac.cr:280-286, and a batch of them bind to).  The corpus is
@@ -997,27 +951,24 @@ static int32_t no_longest_form(aha_ac *ac, const aha_match_params *params, const
 
 // The prologue of the one-shot host entries (document counts, cover): the staging buffers of the leased scratch set -- the
 // text, its offsets, per_doc and per_call bytes for what comes back (0: not asked for) -- and the batch up in one piece over
-// the set's private stream B.s.
+// the set's private stream B.stream: a checked batch (check_host_batch has looked at the offsets), in hostbuf[kHostCorpus] and
+// hostbuf[kHostDocs].  H: what the batch lacks, the two result buffers.
 struct HostBatch {
-  uint8_t *d_corpus;
-  uint64_t *d_doc;
   void *d_per_doc, *d_per_call;
-  hipStream_t s;
 };
 static int32_t stage_host_batch(aha_ac *ac, Scratch *sc, const uint8_t *corpus, const uint64_t *doc_offsets, uint64_t n_docs,
-                                size_t per_doc, size_t per_call, HostBatch &B) {
+                                const aha_match_params *params, size_t per_doc, size_t per_call, Batch &B, HostBatch &H) {
   const uint64_t n_bytes = doc_offsets[n_docs];
-  B.d_corpus = (uint8_t *)host_reserve(sc, kHostCorpus, n_bytes + 64);
-  B.d_doc = (uint64_t *)host_reserve(sc, kHostDocs, (n_docs + 1) * 8);
-  B.d_per_doc = per_doc ? host_reserve(sc, kHostOffsets, per_doc) : nullptr;
-  B.d_per_call = per_call ? host_reserve(sc, kHostOut, per_call) : nullptr;
-  if (!B.d_corpus || !B.d_doc || (per_doc && !B.d_per_doc) || (per_call && !B.d_per_call) || !host_streams(sc)) {
+  uint8_t *d_corpus = (uint8_t *)host_reserve(sc, kHostCorpus, n_bytes + 64);
+  uint64_t *d_doc = (uint64_t *)host_reserve(sc, kHostDocs, (n_docs + 1) * 8);
+  H.d_per_doc = per_doc ? host_reserve(sc, kHostOffsets, per_doc) : nullptr;
+  H.d_per_call = per_call ? host_reserve(sc, kHostOut, per_call) : nullptr;
+  if (!d_corpus || !d_doc || (per_doc && !H.d_per_doc) || (per_call && !H.d_per_call) || !host_streams(sc)) {
     tls_err = "hipMalloc / hipStreamCreate failed for the staging buffers";
     return AHA_E_HIP;
   }
-  uint8_t *d_corpus = B.d_corpus;  // (the names HIPCHK quotes in aha_last_error, as the entries had them)
-  uint64_t *d_doc = B.d_doc;
-  hipStream_t s = B.s = sc->hs[1];
+  hipStream_t s = sc->hs[1];
+  B = checked_batch(d_corpus, d_doc, n_docs, n_bytes, params, s);
   HIPCHK(ac, hipMemcpyAsync(d_doc, doc_offsets, (n_docs + 1) * 8, hipMemcpyHostToDevice, s));
   if (n_bytes) HIPCHK(ac, hipMemcpyAsync(d_corpus, corpus, n_bytes, hipMemcpyHostToDevice, s));
   HIPCHK(ac, hipStreamSynchronize(s));
@@ -1201,11 +1152,9 @@ static int32_t match_batch_host(aha_ac *ac, const uint8_t *corpus, const uint64_
     const uint64_t D = bounds[k + 1] - bounds[k], nb = doc_offsets[bounds[k + 1]] - doc_offsets[bounds[k]];
     const uint64_t room = (!overflow && cap > total) ? cap - total : 0;
     uint64_t nh = 0;
-    int32_t rc = cq ? device_count(ac, sc, d_corpus + dev_off[k], d_doc + bounds[k] + k, D, nb, params, k ? AHA_COUNT_ACCUMULATE : 0u,
-                                   d_kc, d_dho + bounds[k] + k, &nh, s_match, true)
-                    : match_batch_device_impl(ac, sc, d_corpus + dev_off[k], d_doc + bounds[k] + k, D, nb, params,
-                                              room ? d_out + total : nullptr, room, d_dho + bounds[k] + k, &nh, s_match,
-                                              true);  // the offsets were checked on the host above
+    const Batch B = checked_batch(d_corpus + dev_off[k], d_doc + bounds[k] + k, D, nb, params, s_match);  // (checked on the host above)
+    int32_t rc = cq ? device_count(ac, sc, B, k ? AHA_COUNT_ACCUMULATE : 0u, d_kc, d_dho + bounds[k] + k, &nh)
+                    : match_batch_device_impl(ac, sc, B, HitOut{room ? d_out + total : nullptr, room, d_dho + bounds[k] + k}, &nh);
     if (rc != AHA_OK && rc != AHA_E_CAPACITY) {
       P.fail(rc, tls_err);
       break;
@@ -1270,8 +1219,8 @@ int32_t aha_ac_count_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uin
   if (int32_t rc = no_longest_form(ac, params, nullptr)) return rc;
   if (ac->device < 0) return no_device();
   Lease lease(ac);
-  return device_count(ac, lease.get(), d_corpus, d_doc_offsets, n_docs, n_bytes, params, flags, d_key_counts, d_doc_hit_offsets,
-                      n_hits, stream, false);
+  return device_count(ac, lease.get(), abi_batch(d_corpus, d_doc_offsets, n_docs, n_bytes, params, stream), flags, d_key_counts,
+                      d_doc_hit_offsets, n_hits);
 }
 
 // ---- document counts (aha_ac_doc_counts_batch*) --------------------------------------------------------------------
@@ -1290,8 +1239,8 @@ int32_t aha_ac_doc_counts_batch_device(aha_ac *ac, const uint8_t *d_corpus, cons
   if (rc) return rc;
   if (cap && !d_out) return AHA_E_INVALID;
   Lease lease(ac);
-  return device_doc_counts(ac, lease.get(), d_corpus, d_doc_offsets, n_docs, n_bytes, params, d_out, cap, d_doc_pair_offsets,
-                           n_pairs, n_hits, stream, false);
+  return device_doc_counts(ac, lease.get(), abi_batch(d_corpus, d_doc_offsets, n_docs, n_bytes, params, stream), d_out, cap,
+                           d_doc_pair_offsets, n_pairs, n_hits);
 }
 
 // The host entry: the batch goes up in one piece into the staging buffers of the leased scratch set (the match entry's), over
@@ -1303,18 +1252,17 @@ int32_t aha_ac_doc_counts_batch(aha_ac *ac, const uint8_t *corpus, const uint64_
   if (rc) return rc;
   if (cap && !out) return AHA_E_INVALID;
   if ((rc = check_host_batch(corpus, doc_offsets, n_docs))) return rc;
-  const uint64_t n_bytes = doc_offsets[n_docs];
   *n_pairs = 0;
   DeviceGuard g(ac->device);
   Lease lease(ac);
   Scratch *sc = lease.get();
-  HostBatch B;
-  if ((rc = stage_host_batch(ac, sc, corpus, doc_offsets, n_docs, (n_docs + 1) * 8, cap * sizeof(aha_key_count), B))) return rc;
-  uint64_t *d_dpo = (uint64_t *)B.d_per_doc;
-  aha_key_count *d_out = (aha_key_count *)B.d_per_call;
-  hipStream_t s = B.s;
-  rc = device_doc_counts(ac, sc, B.d_corpus, B.d_doc, n_docs, n_bytes, params, d_out, cap, d_dpo, n_pairs, n_hits, s,
-                         true);  // the offsets were checked on the host above
+  Batch B;
+  HostBatch H;
+  if ((rc = stage_host_batch(ac, sc, corpus, doc_offsets, n_docs, params, (n_docs + 1) * 8, cap * sizeof(aha_key_count), B, H))) return rc;
+  uint64_t *d_dpo = (uint64_t *)H.d_per_doc;
+  aha_key_count *d_out = (aha_key_count *)H.d_per_call;
+  hipStream_t s = B.stream;
+  rc = device_doc_counts(ac, sc, B, d_out, cap, d_dpo, n_pairs, n_hits);
   if (rc != AHA_OK && rc != AHA_E_CAPACITY) return rc;
   const std::string err = tls_err;
   const uint64_t n_back = std::min(*n_pairs, cap);
@@ -1342,8 +1290,8 @@ int32_t aha_ac_cover_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uin
   int32_t rc = cover_args(ac, d_doc_offsets, params, flags, n_covered);
   if (rc) return rc;
   Lease lease(ac);
-  return device_cover(ac, lease.get(), d_corpus, d_doc_offsets, n_docs, n_bytes, params, flags, d_mask, d_redacted, fill,
-                      d_doc_covered, n_covered, n_hits, stream, false);
+  return device_cover(ac, lease.get(), abi_batch(d_corpus, d_doc_offsets, n_docs, n_bytes, params, stream), flags, d_mask, d_redacted,
+                      fill, d_doc_covered, n_covered, n_hits);
 }
 
 // The host entry: the batch goes up in one piece into the staging buffers of the leased scratch set, over its private stream; it
@@ -1358,16 +1306,17 @@ int32_t aha_ac_cover_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *do
   DeviceGuard g(ac->device);
   Lease lease(ac);
   Scratch *sc = lease.get();
-  HostBatch B;
-  if ((rc = stage_host_batch(ac, sc, corpus, doc_offsets, n_docs, doc_covered ? (n_docs + 1) * 8 : 0, mask ? n_words * 4 + 16 : 0, B)))
+  Batch B;
+  HostBatch H;
+  if ((rc = stage_host_batch(ac, sc, corpus, doc_offsets, n_docs, params, doc_covered ? (n_docs + 1) * 8 : 0,
+                             mask ? n_words * 4 + 16 : 0, B, H)))
     return rc;
-  uint8_t *d_corpus = B.d_corpus;
-  uint64_t *d_cov = (uint64_t *)B.d_per_doc;
-  uint32_t *d_mask = (uint32_t *)B.d_per_call;
-  hipStream_t s = B.s;
+  uint8_t *d_corpus = (uint8_t *)sc->hostbuf[kHostCorpus].p;  // (B.text, writable: the staged copy is redacted in place)
+  uint64_t *d_cov = (uint64_t *)H.d_per_doc;
+  uint32_t *d_mask = (uint32_t *)H.d_per_call;
+  hipStream_t s = B.stream;
   uint64_t nc = 0, nh = 0;
-  rc = device_cover(ac, sc, d_corpus, B.d_doc, n_docs, n_bytes, params, flags, d_mask, redacted ? d_corpus : nullptr, fill, d_cov, &nc,
-                    &nh, s, true);  // the offsets were checked on the host above
+  rc = device_cover(ac, sc, B, flags, d_mask, redacted ? d_corpus : nullptr, fill, d_cov, &nc, &nh);
   if (rc != AHA_OK) return rc;
   if (mask && n_words) HIPCHK(ac, hipMemcpyAsync(mask, d_mask, n_words * 4, hipMemcpyDeviceToHost, s));
   if (redacted && n_bytes) HIPCHK(ac, hipMemcpyAsync(redacted, d_corpus, n_bytes, hipMemcpyDeviceToHost, s));
@@ -1401,8 +1350,8 @@ int32_t aha_ac_select_batch_device(aha_ac *ac, const uint8_t *d_corpus, const ui
   if (rc) return rc;
   if (cap && !d_out) return AHA_E_INVALID;
   Lease lease(ac);
-  return device_select(ac, lease.get(), d_corpus, d_doc_offsets, n_docs, n_bytes, params, d_out, cap, d_doc_sel_offsets, n_selected,
-                       n_hits, stream, false, flags);
+  return device_select(ac, lease.get(), abi_batch(d_corpus, d_doc_offsets, n_docs, n_bytes, params, stream),
+                       HitOut{d_out, cap, d_doc_sel_offsets}, n_selected, n_hits, flags);
 }
 
 // The host entry: the batch goes up in one piece into the staging buffers of the leased scratch set, over its private stream;
@@ -1414,18 +1363,17 @@ int32_t aha_ac_select_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *d
   if (rc) return rc;
   if (cap && !out) return AHA_E_INVALID;
   if ((rc = check_host_batch(corpus, doc_offsets, n_docs))) return rc;
-  const uint64_t n_bytes = doc_offsets[n_docs];
   DeviceGuard g(ac->device);
   Lease lease(ac);
   Scratch *sc = lease.get();
-  HostBatch B;
-  if ((rc = stage_host_batch(ac, sc, corpus, doc_offsets, n_docs, (n_docs + 1) * 8, cap * sizeof(aha_hit), B))) return rc;
-  uint64_t *d_dso = (uint64_t *)B.d_per_doc;
-  aha_hit *d_out = (aha_hit *)B.d_per_call;
-  hipStream_t s = B.s;
+  Batch B;
+  HostBatch H;
+  if ((rc = stage_host_batch(ac, sc, corpus, doc_offsets, n_docs, params, (n_docs + 1) * 8, cap * sizeof(aha_hit), B, H))) return rc;
+  uint64_t *d_dso = (uint64_t *)H.d_per_doc;
+  aha_hit *d_out = (aha_hit *)H.d_per_call;
+  hipStream_t s = B.stream;
   uint64_t ns = 0, nh = 0;
-  rc = device_select(ac, sc, B.d_corpus, B.d_doc, n_docs, n_bytes, params, d_out, cap, d_dso, &ns, &nh, s,
-                     true, flags);  // the offsets were checked on the host above
+  rc = device_select(ac, sc, B, HitOut{d_out, cap, d_dso}, &ns, &nh, flags);
   if (rc == AHA_E_CAPACITY) *n_selected = ns;
   if (rc != AHA_OK) return rc;
   if (ns) HIPCHK(ac, hipMemcpyAsync(out, d_out, ns * sizeof(aha_hit), hipMemcpyDeviceToHost, s));
@@ -1563,8 +1511,8 @@ int32_t aha_ac_replace_batch_device(aha_ac *ac, const aha_repl *table, const uin
   int32_t rc = replace_args(ac, table, d_corpus, n_bytes, d_doc_offsets, params, flags, d_out, cap_bytes, n_out_bytes);
   if (rc) return rc;
   Lease lease(ac);
-  return device_replace(ac, lease.get(), table, d_corpus, d_doc_offsets, n_docs, n_bytes, params, d_out, cap_bytes,
-                        d_doc_out_offsets, n_out_bytes, n_selected, n_hits, stream, false);
+  return device_replace(ac, lease.get(), table, abi_batch(d_corpus, d_doc_offsets, n_docs, n_bytes, params, stream), d_out, cap_bytes,
+                        d_doc_out_offsets, n_out_bytes, n_selected, n_hits);
 }
 
 // The host entry: the batch goes up in one piece into the staging buffers of the leased scratch set, over its private stream;
@@ -1576,18 +1524,17 @@ int32_t aha_ac_replace_batch(aha_ac *ac, const aha_repl *table, const uint8_t *c
   int32_t rc = replace_args(ac, table, corpus, doc_offsets[n_docs], doc_offsets, params, flags, out, cap_bytes, n_out_bytes);
   if (rc) return rc;
   if ((rc = check_host_batch(corpus, doc_offsets, n_docs))) return rc;
-  const uint64_t n_bytes = doc_offsets[n_docs];
   DeviceGuard g(ac->device);
   Lease lease(ac);
   Scratch *sc = lease.get();
-  HostBatch B;
-  if ((rc = stage_host_batch(ac, sc, corpus, doc_offsets, n_docs, (n_docs + 1) * 8, cap_bytes, B))) return rc;
-  uint64_t *d_doo = (uint64_t *)B.d_per_doc;
-  uint8_t *d_out = (uint8_t *)B.d_per_call;
-  hipStream_t s = B.s;
+  Batch B;
+  HostBatch H;
+  if ((rc = stage_host_batch(ac, sc, corpus, doc_offsets, n_docs, params, (n_docs + 1) * 8, cap_bytes, B, H))) return rc;
+  uint64_t *d_doo = (uint64_t *)H.d_per_doc;
+  uint8_t *d_out = (uint8_t *)H.d_per_call;
+  hipStream_t s = B.stream;
   uint64_t nb = 0, ns = 0, nh = 0;
-  rc = device_replace(ac, sc, table, B.d_corpus, B.d_doc, n_docs, n_bytes, params, d_out, cap_bytes, d_doo, &nb, &ns, &nh, s,
-                      true);  // the offsets were checked on the host above
+  rc = device_replace(ac, sc, table, B, d_out, cap_bytes, d_doo, &nb, &ns, &nh);
   if (rc == AHA_E_CAPACITY) {  // (the required size and the counts, as the device entry gives them)
     *n_out_bytes = nb;
     if (n_selected) *n_selected = ns;
@@ -1687,7 +1634,7 @@ int32_t aha_ac_class_counts_batch_device(aha_ac *ac, const aha_classes *table, c
   int32_t rc = class_counts_args(ac, table, d_doc_offsets, n_docs, params, flags, d_out);
   if (rc) return rc;
   Lease lease(ac);
-  return device_class_counts(ac, lease.get(), table, d_corpus, d_doc_offsets, n_docs, n_bytes, params, d_out, n_hits, stream, false);
+  return device_class_counts(ac, lease.get(), table, abi_batch(d_corpus, d_doc_offsets, n_docs, n_bytes, params, stream), d_out, n_hits);
 }
 
 // The host entry: the batch goes up in one piece into the staging buffers of the leased scratch set, over its private stream;
@@ -1697,17 +1644,17 @@ int32_t aha_ac_class_counts_batch(aha_ac *ac, const aha_classes *table, const ui
   int32_t rc = class_counts_args(ac, table, doc_offsets, n_docs, params, flags, out);
   if (rc) return rc;
   if ((rc = check_host_batch(corpus, doc_offsets, n_docs))) return rc;
-  const uint64_t n_bytes = doc_offsets[n_docs], n_out = n_docs * table->n_classes;
+  const uint64_t n_out = n_docs * table->n_classes;
   DeviceGuard g(ac->device);
   Lease lease(ac);
   Scratch *sc = lease.get();
-  HostBatch B;
-  if ((rc = stage_host_batch(ac, sc, corpus, doc_offsets, n_docs, 0, n_out * 4, B))) return rc;
-  uint32_t *d_out = (uint32_t *)B.d_per_call;
-  hipStream_t s = B.s;
+  Batch B;
+  HostBatch H;
+  if ((rc = stage_host_batch(ac, sc, corpus, doc_offsets, n_docs, params, 0, n_out * 4, B, H))) return rc;
+  uint32_t *d_out = (uint32_t *)H.d_per_call;
+  hipStream_t s = B.stream;
   uint64_t nh = 0;
-  rc = device_class_counts(ac, sc, table, B.d_corpus, B.d_doc, n_docs, n_bytes, params, d_out, &nh, s,
-                           true);  // the offsets were checked on the host above
+  rc = device_class_counts(ac, sc, table, B, d_out, &nh);
   if (rc != AHA_OK) return rc;
   if (n_out) HIPCHK(ac, hipMemcpyAsync(out, d_out, n_out * 4, hipMemcpyDeviceToHost, s));
   HIPCHK(ac, hipStreamSynchronize(s));
@@ -1731,8 +1678,8 @@ int32_t aha_ac_records_batch_device(aha_ac *ac, const uint8_t *d_corpus, const u
   int32_t rc = records_args(ac, d_doc_offsets, flags, d_rec_offsets, cap_records, n_records);
   if (rc) return rc;
   Lease lease(ac);
-  return device_records(ac, lease.get(), d_corpus, d_doc_offsets, n_docs, n_bytes, delim, d_rec_offsets, cap_records,
-                        d_doc_rec_offsets, n_records, stream, false);
+  return device_records(ac, lease.get(), abi_batch(d_corpus, d_doc_offsets, n_docs, n_bytes, nullptr, stream), delim, d_rec_offsets,
+                        cap_records, d_doc_rec_offsets, n_records);
 }
 
 // The host entry: the batch goes up in one piece into the staging buffers of the leased scratch set, over its private stream;
@@ -1743,18 +1690,18 @@ int32_t aha_ac_records_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *
   int32_t rc = records_args(ac, doc_offsets, flags, rec_offsets, cap_records, n_records);
   if (rc) return rc;
   if ((rc = check_host_batch(corpus, doc_offsets, n_docs))) return rc;
-  const uint64_t n_bytes = doc_offsets[n_docs];
   DeviceGuard g(ac->device);
   Lease lease(ac);
   Scratch *sc = lease.get();
-  HostBatch B;
-  if ((rc = stage_host_batch(ac, sc, corpus, doc_offsets, n_docs, (n_docs + 1) * 8, rec_offsets ? (cap_records + 1) * 8 : 0, B)))
+  Batch B;
+  HostBatch H;
+  if ((rc = stage_host_batch(ac, sc, corpus, doc_offsets, n_docs, nullptr, (n_docs + 1) * 8, rec_offsets ? (cap_records + 1) * 8 : 0, B,
+                             H)))
     return rc;
-  uint64_t *d_dro = (uint64_t *)B.d_per_doc, *d_rec = (uint64_t *)B.d_per_call;
-  hipStream_t s = B.s;
+  uint64_t *d_dro = (uint64_t *)H.d_per_doc, *d_rec = (uint64_t *)H.d_per_call;
+  hipStream_t s = B.stream;
   uint64_t nr = 0;
-  rc = device_records(ac, sc, B.d_corpus, B.d_doc, n_docs, n_bytes, delim, d_rec, d_rec ? cap_records : 0, d_dro, &nr, s,
-                      true);  // the offsets were checked on the host above
+  rc = device_records(ac, sc, B, delim, d_rec, d_rec ? cap_records : 0, d_dro, &nr);
   if (rc == AHA_E_CAPACITY) *n_records = nr;
   if (rc != AHA_OK) return rc;
   if (rec_offsets) HIPCHK(ac, hipMemcpyAsync(rec_offsets, d_rec, (nr + 1) * 8, hipMemcpyDeviceToHost, s));
@@ -1835,19 +1782,19 @@ int32_t aha_ac_grep_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uint
                          n_kept);
   if (rc) return rc;
   Lease lease(ac);
+  const Batch B = abi_batch(d_corpus, d_doc_offsets, n_docs, n_bytes, params, stream);
   if (flags & AHA_GREP_CONTEXT)
-    return device_excerpts(ac, lease.get(), d_corpus, d_doc_offsets, n_docs, n_bytes, reinterpret_cast<const aha_excerpt_params *>(params),
-                           d_kept_docs, d_doc_out_offsets, cap_docs, d_out, cap_bytes, n_kept, n_out_bytes, n_hits, stream, false);
+    return device_excerpts(ac, lease.get(), B, reinterpret_cast<const aha_excerpt_params *>(params), d_kept_docs, d_doc_out_offsets,
+                           cap_docs, d_out, cap_bytes, n_kept, n_out_bytes, n_hits);
   if (flags & AHA_GREP_RULE) {
     // the caller's rows take the table at once only where no capacity can fail the call behind it
     const aha_grep_params *gp = reinterpret_cast<const aha_grep_params *>(params);
     const bool per_doc = d_kept_docs || d_doc_out_offsets;
-    const bool rows_early = (!per_doc || cap_docs >= n_docs) && (!d_out || cap_bytes >= n_bytes);
-    return device_grep_rule(ac, lease.get(), d_corpus, d_doc_offsets, n_docs, n_bytes, gp, gp->rows, flags, d_kept_docs,
-                            d_doc_out_offsets, cap_docs, d_out, cap_bytes, n_kept, n_out_bytes, n_hits, stream, false, rows_early);
+    const bool cannot_fail = (!per_doc || cap_docs >= n_docs) && (!d_out || cap_bytes >= n_bytes);
+    return device_grep_rule(ac, lease.get(), B, gp, gp->rows, cannot_fail ? RuleRows::kEarly : RuleRows::kLate, flags, d_kept_docs,
+                            d_doc_out_offsets, cap_docs, d_out, cap_bytes, n_kept, n_out_bytes, n_hits);
   }
-  return device_grep(ac, lease.get(), d_corpus, d_doc_offsets, n_docs, n_bytes, params, flags, d_kept_docs, d_doc_out_offsets, cap_docs,
-                     d_out, cap_bytes, n_kept, n_out_bytes, n_hits, stream, false);
+  return device_grep(ac, lease.get(), B, flags, d_kept_docs, d_doc_out_offsets, cap_docs, d_out, cap_bytes, n_kept, n_out_bytes, n_hits);
 }
 
 // The host entry: the batch goes up in one piece into the staging buffers of the leased scratch set, over its private stream;
@@ -1860,35 +1807,34 @@ int32_t aha_ac_grep_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc
                          n_kept);
   if (rc) return rc;
   if ((rc = check_host_batch(corpus, doc_offsets, n_docs))) return rc;
-  const uint64_t n_bytes = doc_offsets[n_docs];
   DeviceGuard g(ac->device);
   Lease lease(ac);
   Scratch *sc = lease.get();
-  HostBatch B;
+  Batch B;
+  HostBatch H;
   // per document: the kept documents' indices, cap_docs of them, then their offsets, cap_docs + 1; behind them the rows of a
   // rule grep call whose caller wants them
   const bool per_doc = kept_docs || doc_out_offsets;
   const aha_grep_params *gp = (flags & AHA_GREP_RULE) ? reinterpret_cast<const aha_grep_params *>(params) : nullptr;
   const uint64_t per_doc_bytes = per_doc ? (2 * cap_docs + 1) * 8 : 0;
   const uint64_t n_rows = gp && gp->rows ? n_docs * gp->classes->n_classes : 0;
-  if ((rc = stage_host_batch(ac, sc, corpus, doc_offsets, n_docs, per_doc_bytes + n_rows * 4, out ? std::max<uint64_t>(cap_bytes, 1) : 0,
-                             B)))
+  if ((rc = stage_host_batch(ac, sc, corpus, doc_offsets, n_docs, params, per_doc_bytes + n_rows * 4,
+                             out ? std::max<uint64_t>(cap_bytes, 1) : 0, B, H)))
     return rc;
-  uint32_t *d_rows = n_rows ? (uint32_t *)((uint8_t *)B.d_per_doc + per_doc_bytes) : nullptr;
-  uint64_t *d_kept = kept_docs ? (uint64_t *)B.d_per_doc : nullptr;
-  uint64_t *d_doo = doc_out_offsets ? (uint64_t *)B.d_per_doc + cap_docs : nullptr;
-  uint8_t *d_out = (uint8_t *)B.d_per_call;
-  hipStream_t s = B.s;
+  uint32_t *d_rows = n_rows ? (uint32_t *)((uint8_t *)H.d_per_doc + per_doc_bytes) : nullptr;
+  uint64_t *d_kept = kept_docs ? (uint64_t *)H.d_per_doc : nullptr;
+  uint64_t *d_doo = doc_out_offsets ? (uint64_t *)H.d_per_doc + cap_docs : nullptr;
+  uint8_t *d_out = (uint8_t *)H.d_per_call;
+  hipStream_t s = B.stream;
   uint64_t nk = 0, nb = 0, nh = 0;
   if (flags & AHA_GREP_CONTEXT)  // (kept_docs takes the excerpts' starts, doc_out_offsets their offsets into out)
-    rc = device_excerpts(ac, sc, B.d_corpus, B.d_doc, n_docs, n_bytes, reinterpret_cast<const aha_excerpt_params *>(params), d_kept,
-                         d_doo, cap_docs, d_out, d_out ? cap_bytes : 0, &nk, &nb, &nh, s, true);
+    rc = device_excerpts(ac, sc, B, reinterpret_cast<const aha_excerpt_params *>(params), d_kept, d_doo, cap_docs, d_out,
+                         d_out ? cap_bytes : 0, &nk, &nb, &nh);
   else if (gp)  // (d_rows is staging: the table may go there before the verdict)
-    rc = device_grep_rule(ac, sc, B.d_corpus, B.d_doc, n_docs, n_bytes, gp, d_rows, flags, d_kept, d_doo, cap_docs, d_out,
-                          d_out ? cap_bytes : 0, &nk, &nb, &nh, s, true, true);
+    rc = device_grep_rule(ac, sc, B, gp, d_rows, RuleRows::kEarly, flags, d_kept, d_doo, cap_docs, d_out, d_out ? cap_bytes : 0, &nk,
+                          &nb, &nh);
   else
-    rc = device_grep(ac, sc, B.d_corpus, B.d_doc, n_docs, n_bytes, params, flags, d_kept, d_doo, cap_docs, d_out, d_out ? cap_bytes : 0,
-                     &nk, &nb, &nh, s, true);  // the offsets were checked on the host above
+    rc = device_grep(ac, sc, B, flags, d_kept, d_doo, cap_docs, d_out, d_out ? cap_bytes : 0, &nk, &nb, &nh);
   if (rc == AHA_E_CAPACITY) {  // (both required numbers and the count, as the device entry gives them)
     *n_kept = nk;
     if (n_out_bytes) *n_out_bytes = nb;

@@ -7,6 +7,7 @@
 #include "doc_ranges.hpp"
 
 #include <chrono>
+#include <optional>
 
 namespace ahai {
 
@@ -204,19 +205,18 @@ void v2_setup(aha_ac *ac) {
   }
 }
 
-// a slot of v2buf (handle.hpp V2Slot), grow-only
-static int32_t v2_reserve(Scratch *sc, V2Slot slot, size_t bytes) {
-  Buf &b = sc->v2buf[slot];
-  if (b.bytes >= bytes) return AHA_OK;
-  // a new counter block (see Scratch::cursor_dirty): cleared in full by the next call, whatever its address
-  if (slot == kCursor) sc->reset_cursor();
+// a grow-only slot that answers for itself: the allocator's error as the call's
+static int32_t reserve_or_text(Buf &b, size_t bytes) {
   const hipError_t e = reserve(b, bytes, kGrowEighth);
-  if (e != hipSuccess) {
-      // (the text HIPCHK gave this allocation before it went through reserve(): kept as it was for aha_last_error)
-    tls_err = std::string("hipMalloc(&b.p, want): ") + hipGetErrorString(e);
-    return AHA_E_HIP;
-  }
-  return AHA_OK;
+  if (e == hipSuccess) return AHA_OK;
+  tls_err = std::string("hipMalloc(&b.p, want): ") + hipGetErrorString(e);
+  return AHA_E_HIP;
+}
+// a slot of v2buf (handle.hpp V2Slot)
+static int32_t v2_reserve(Scratch *sc, V2Slot slot, size_t bytes) {
+  // a new counter block (see Scratch::cursor_dirty): cleared in full by the next call, whatever its address
+  if (slot == kCursor && sc->v2buf[slot].bytes < bytes) sc->reset_cursor();
+  return reserve_or_text(sc->v2buf[slot], bytes);
 }
 
 // Pipeline of one call, a function of the call alone (the handle keeps no history):
@@ -327,16 +327,28 @@ static void two_pass_chunks(const aha_ac *ac, MatchArgs &M, uint32_t chunk0, uin
   while (M.chunk < lmax_mul * ac->aut.max_key_len && M.chunk < (1u << 20)) M.chunk *= 2;
   M.n_chunks = (M.n_bytes + M.chunk - 1) / M.chunk;
 }
-// ... and its scratch for `units` counters (chunks or documents) and M.n_docs documents, bound to M
+// the two-pass engine's totals (handle.hpp TwoPassSlot) and the pinned words they come back in: what match_longest's NUL look
+// needs before the rest is bound
+static int32_t two_pass_totals(aha_ac *ac, Scratch *sc) {
+  if (int32_t rc = reserve_or_text(sc->tpbuf[kTpTotals], 2 * sizeof(uint64_t))) return rc;
+  if (!sc->h_totals) HIPCHK(ac, hipHostMalloc((void **)&sc->h_totals, 2 * sizeof(uint64_t), hipHostMallocDefault));
+  return AHA_OK;
+}
+static uint64_t *d_totals(Scratch *sc) { return (uint64_t *)sc->tpbuf[kTpTotals].p; }
+// ... and its scratch for `units` counters (chunks or documents) and M.n_docs documents, reserved and bound to M
 static int32_t bind_two_pass(aha_ac *ac, Scratch *sc, MatchArgs &M, uint64_t units, uint64_t *n_blocks) {
   *n_blocks = (units + kBlock - 1) / kBlock;
-  if (int32_t rc = ensure_scratch(ac, sc, units, *n_blocks, M.n_docs)) return rc;
-  M.counts = sc->d_counts;
-  M.leads = sc->d_leads;
-  M.blk_hits = sc->d_blk_hits;
-  M.blk_leads = sc->d_blk_leads;
-  M.docg = sc->d_docg;
-  M.totals = sc->d_totals;
+  const size_t sizes[kTpCount] = {units * 4, units * 4, *n_blocks * 8, *n_blocks * 8, (M.n_docs + 1) * 8, 0};  // (kTpTotals: below)
+  for (int i = 0; i < kTpTotals; i++)
+    if (int32_t rc = reserve_or_text(sc->tpbuf[i], sizes[i])) return rc;
+  if (int32_t rc = two_pass_totals(ac, sc)) return rc;
+  auto at = [sc](TwoPassSlot slot) { return sc->tpbuf[slot].p; };
+  M.counts = (uint32_t *)at(kTpCounts);
+  M.leads = (uint32_t *)at(kTpLeads);
+  M.blk_hits = (uint64_t *)at(kTpBlkHits);
+  M.blk_leads = (uint64_t *)at(kTpBlkLeads);
+  M.docg = (uint64_t *)at(kTpDocG);
+  M.totals = d_totals(sc);
   return AHA_OK;
 }
 // One pass's aha_timing from the events of its scratch set, published: ms_total ev[0] .. ev[4], ms_count ev[0] .. ev[count_end],
@@ -739,8 +751,8 @@ int32_t ready_events(aha_ac *ac, Scratch *sc) {
   return AHA_OK;
 }
 
-// the offsets live in HBM: one small kernel and an 4-byte read-back before anything indexes with them (device_match and
-// device_count, where no single-traversal pass validates them on the device)
+// the offsets live in HBM: one small kernel and an 4-byte read-back before anything indexes with them (open_call, where no
+// single-traversal pass validates them on the device; device_records)
 static int32_t check_docs_now(aha_ac *ac, Scratch *sc, const uint64_t *d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
                               hipStream_t s) {
   int32_t rc2;
@@ -755,129 +767,147 @@ static int32_t check_docs_now(aha_ac *ac, Scratch *sc, const uint64_t *d_doc_off
   return (bad & 3u) ? bad_offsets(bad & 1u) : AHA_OK;
 }
 
-int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
-                     uint64_t n_bytes, const aha_match_params *params, aha_hit *d_out, uint64_t cap, uint64_t *d_doc_hit_offsets,
-                     uint64_t *n_hits, void *stream, bool offsets_checked, const PackOut *pk, bool *packed, bool quiet, bool neutral,
-                     bool as_is) {
-  if (!ac || !n_hits || !d_doc_offsets) return AHA_E_INVALID;
-  if (ac->device < 0) return no_device();
-  if (cap && !d_out) return AHA_E_INVALID;
-  DeviceGuard g(ac->device);
-  hipStream_t s = (hipStream_t)stream;
+// What device_match and device_count open with.  The checks of the arguments they share (args_ok: the family's own, given its
+// place among them), the device, the parameters into M, the events; `decide(M, longest)` is the family's say once the parameters
+// are known -- below 0 its refusal, 1 where a single-traversal pass will validate unchecked offsets on the device in front of
+// its traversal (match_v2), 0 where the verdict is read back here (check_docs_now) --; d_zero[0 .. zero_bytes) is cleared once
+// the offsets stand (a count call's key counts); an empty batch is answered (`done`), any other gets its text (take_text).
+struct Opening {
+  std::optional<DeviceGuard> g;
   MatchArgs M{};
   int longest = 0;
-  int32_t rc = fill_params(ac, params, M, &longest);
+  bool done = false;  // an empty batch: the documents' hit offsets are cleared, the stream has run, the call returns AHA_OK
+};
+template <class Decide>
+static int32_t open_call(aha_ac *ac, Scratch *sc, const Batch &B, bool args_ok, uint64_t *d_doc_hit_off, uint64_t *n_hits, CallOpt opt,
+                         Decide decide, void *d_zero, size_t zero_bytes, Opening &O) {
+  if (!ac || !n_hits || !B.doc_off) return AHA_E_INVALID;
+  if (ac->device < 0) return no_device();
+  if (!args_ok) return AHA_E_INVALID;
+  O.g.emplace(ac->device);
+  hipStream_t s = B.stream;
+  MatchArgs &M = O.M;
+  int32_t rc = fill_params(ac, B.params, M, &O.longest);
   if (rc) return rc;
+  const int32_t defer = decide(M, O.longest);
+  if (defer < 0) return defer;
   if ((rc = ready_events(ac, sc))) return rc;
-  if (quiet) M.no_filter = M.no_pair = 1;  // (neither engine that keeps a history of hand-backs)
-  M.neutral = neutral ? 1 : 0;
+  if (has(opt, CallOpt::kQuiet)) M.no_filter = M.no_pair = 1;  // (neither engine that keeps a history of hand-backs)
+  M.neutral = has(opt, CallOpt::kNeutral) ? 1 : 0;
   *n_hits = 0;
-  auto check_now = [&]() { return check_docs_now(ac, sc, d_doc_offsets, n_docs, n_bytes, s); };
-  auto fits = [&]() {  // the call's verdict once the hits are counted
-    if (*n_hits <= cap) return (int32_t)AHA_OK;
-    tls_err = "output buffer too small";
-    return (int32_t)AHA_E_CAPACITY;
-  };
-  // The single-traversal pipelines validate on the device in front of their traversal (match_v2); every other path -- an
-  // empty batch, match_longest, the two-pass engine -- reads the verdict back first.
-  const bool defer_check = !offsets_checked && ac->v2_ok && !longest && n_bytes != 0;
-  if (!offsets_checked && !defer_check && (rc = check_now())) return rc;
-  M.check_docs = defer_check ? 1 : 0;
-  if (n_bytes == 0) {
-    if (d_doc_hit_offsets)
-      HIPCHK(ac, hipMemsetAsync(d_doc_hit_offsets, 0, (n_docs + 1) * sizeof(uint64_t), s));
+  if (!B.checked && !defer && (rc = check_docs_now(ac, sc, B.doc_off, B.n_docs, B.n_bytes, s))) return rc;
+  M.check_docs = (!B.checked && defer) ? 1 : 0;
+  if (d_zero) HIPCHK(ac, hipMemsetAsync(d_zero, 0, zero_bytes, s));
+  if (B.n_bytes == 0) {
+    if (d_doc_hit_off) HIPCHK(ac, hipMemsetAsync(d_doc_hit_off, 0, (B.n_docs + 1) * sizeof(uint64_t), s));
     HIPCHK(ac, hipStreamSynchronize(s));
+    O.done = true;
     return AHA_OK;
   }
-  if (!d_corpus) return AHA_E_INVALID;
-  M.doc_off = d_doc_offsets;
-  M.n_docs = n_docs;
-  M.n_bytes = n_bytes;
-  M.out = d_out;
-  M.cap = cap;
-  M.doc_hit_off = d_doc_hit_offsets;
-  if ((rc = take_text(ac, sc, d_corpus, n_bytes, M, s, as_is))) return rc;
-  if (longest) {
-    if ((rc = stage_folded(ac, sc, M, s))) return rc;
-    d_corpus = M.text;
-    // match_longest: count -> scan -> write, like the two-pass engine (kernels.hip)
-    int mode = longest == 1 ? 1 : (M.chars ? 3 : 2);
-    if ((rc = ensure_scratch(ac, sc, 1, 1, n_docs))) return rc;
-    if (mode == 2) {
-      // the chunked form is exact only for text without NUL bytes (kernels.hip, k_has_nul): look first
-      HIPCHK(ac, hipMemsetAsync(sc->d_totals, 0, 2 * sizeof(uint64_t), s));
-      launch_has_nul(d_corpus, n_bytes, sc->d_totals + 1, s);
-      HIPCHK(ac, hipMemcpyAsync(sc->h_totals, sc->d_totals, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-      HIPCHK(ac, hipStreamSynchronize(s));
-      M.has_nul = sc->h_totals[1] ? 1 : 0;  // the chunks' warm-ups then reach back past the NULs they cross (kernels.hip)
-    }
-    two_pass_chunks(ac, M, 1024, 16);  // the warm-up is 2 * Lmax
-    uint64_t n_blocks;
-    if ((rc = bind_two_pass(ac, sc, M, mode == 2 ? M.n_chunks : n_docs + 1, &n_blocks))) return rc;
-    const int chars = M.chars;
-    if ((rc = ensure_stale(ac))) return rc;
-    launch_longest(ac->dev_longest, M, mode, false, s);
-    if (mode == 2 && M.has_nul) {  // a chunk whose warm-up would not end (a NUL every few bytes) gave up: document by document
-      HIPCHK(ac, hipMemcpyAsync(sc->h_totals, sc->d_totals, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-      HIPCHK(ac, hipStreamSynchronize(s));
-      if (sc->h_totals[1] == 2) {
-        mode = 3;
-        if ((rc = bind_two_pass(ac, sc, M, n_docs + 1, &n_blocks))) return rc;
-        launch_longest(ac->dev_longest, M, mode, false, s);
-      }
-    }
-    M.chars = 0;  // the block scan has no lead counts to scan here
-    launch_scan_blocks(M, n_blocks, s);
-    M.chars = chars;
-    launch_longest(ac->dev_longest, M, mode, true, s);
-    HIPCHK(ac, hipGetLastError());
-    HIPCHK(ac, hipMemcpyAsync(sc->h_totals, sc->d_totals, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  if (!B.text) return AHA_E_INVALID;
+  M.doc_off = B.doc_off;
+  M.n_docs = B.n_docs;
+  M.n_bytes = B.n_bytes;
+  return take_text(ac, sc, B.text, B.n_bytes, M, s, has(opt, CallOpt::kAsIs));
+}
+
+// the verdict of a match once the hits are counted
+static int32_t fits(uint64_t n_hits, uint64_t cap) {
+  if (n_hits <= cap) return AHA_OK;
+  tls_err = "output buffer too small";
+  return AHA_E_CAPACITY;
+}
+
+// match_longest: count -> scan -> write, like the two-pass engine (kernels.hip)
+static int32_t match_longest_pass(aha_ac *ac, Scratch *sc, MatchArgs &M, int longest, hipStream_t s, uint64_t *n_hits) {
+  int32_t rc;
+  if ((rc = stage_folded(ac, sc, M, s))) return rc;
+  int mode = longest == 1 ? 1 : (M.chars ? 3 : 2);
+  if ((rc = two_pass_totals(ac, sc))) return rc;
+  if (mode == 2) {
+    // the chunked form is exact only for text without NUL bytes (kernels.hip, k_has_nul): look first
+    HIPCHK(ac, hipMemsetAsync(d_totals(sc), 0, 2 * sizeof(uint64_t), s));
+    launch_has_nul(M.text, M.n_bytes, d_totals(sc) + 1, s);
+    HIPCHK(ac, hipMemcpyAsync(sc->h_totals, d_totals(sc), 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     HIPCHK(ac, hipStreamSynchronize(s));
-    *n_hits = sc->h_totals[0];
-    return fits();
+    M.has_nul = sc->h_totals[1] ? 1 : 0;  // the chunks' warm-ups then reach back past the NULs they cross (kernels.hip)
   }
-  uint32_t repeats = 0;  // passes thrown away (aha_timing.repeats)
-  if (ac->v2_ok) {
-    // a handle whose batches keep coming back from the prefix-filter engine (text dense with key starts) skips it for 2, 4,
-    // .. 64 calls before it tries again: a batch that is handed back has paid for the filter and part of the walks
-    const int pm = M.chars ? 1 : 0;  // (calls with char offsets keep their own count)
-    if (ac->pf_ok && neutral) {  // (as the next match call would, without counting down)
-      if (ac->pf_skip[pm].load(std::memory_order_relaxed)) M.no_filter = 1;
-    } else if (ac->pf_ok && !quiet) {  // (calls on one handle may run side by side: the count goes down by compare-exchange, never below 0)
-      uint32_t v = ac->pf_skip[pm].load(std::memory_order_relaxed);
-      while (v && !ac->pf_skip[pm].compare_exchange_weak(v, v - 1, std::memory_order_relaxed)) {
-      }
-      if (v) M.no_filter = 1;
+  two_pass_chunks(ac, M, 1024, 16);  // the warm-up is 2 * Lmax
+  uint64_t n_blocks;
+  if ((rc = bind_two_pass(ac, sc, M, mode == 2 ? M.n_chunks : M.n_docs + 1, &n_blocks))) return rc;
+  const int chars = M.chars;
+  if ((rc = ensure_stale(ac))) return rc;
+  launch_longest(ac->dev_longest, M, mode, false, s);
+  if (mode == 2 && M.has_nul) {  // a chunk whose warm-up would not end (a NUL every few bytes) gave up: document by document
+    HIPCHK(ac, hipMemcpyAsync(sc->h_totals, d_totals(sc), 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(ac, hipStreamSynchronize(s));
+    if (sc->h_totals[1] == 2) {
+      mode = 3;
+      if ((rc = bind_two_pass(ac, sc, M, M.n_docs + 1, &n_blocks))) return rc;
+      launch_longest(ac->dev_longest, M, mode, false, s);
     }
-    const bool tried = ac->pf_ok && !M.no_filter;
+  }
+  M.chars = 0;  // the block scan has no lead counts to scan here
+  launch_scan_blocks(M, n_blocks, s);
+  M.chars = chars;
+  launch_longest(ac->dev_longest, M, mode, true, s);
+  HIPCHK(ac, hipGetLastError());
+  HIPCHK(ac, hipMemcpyAsync(sc->h_totals, d_totals(sc), 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  *n_hits = sc->h_totals[0];
+  return fits(*n_hits, M.cap);
+}
+
+// The single-traversal ladder: the prefix filter's back-off, the pass, once more behind a hand-back, full-size regions behind
+// an overflow, slabs.  AHA_OK, an error, or 1: the two-pass engine takes the batch (*repeats: the passes thrown away so far).
+static int32_t single_traversal_ladder(aha_ac *ac, Scratch *sc, MatchArgs &M, CallOpt opt, hipStream_t s, uint64_t *n_hits,
+                                       uint32_t *repeats) {
+  const bool quiet = has(opt, CallOpt::kQuiet), neutral = has(opt, CallOpt::kNeutral);
+  // a handle whose batches keep coming back from the prefix-filter engine (text dense with key starts) skips it for 2, 4,
+  // .. 64 calls before it tries again: a batch that is handed back has paid for the filter and part of the walks
+  const int pm = M.chars ? 1 : 0;  // (calls with char offsets keep their own count)
+  if (ac->pf_ok && neutral) {  // (as the next match call would, without counting down)
+    if (ac->pf_skip[pm].load(std::memory_order_relaxed)) M.no_filter = 1;
+  } else if (ac->pf_ok && !quiet) {  // (calls on one handle may run side by side: the count goes down by compare-exchange, never below 0)
+    uint32_t v = ac->pf_skip[pm].load(std::memory_order_relaxed);
+    while (v && !ac->pf_skip[pm].compare_exchange_weak(v, v - 1, std::memory_order_relaxed)) {
+    }
+    if (v) M.no_filter = 1;
+  }
+  const bool tried = ac->pf_ok && !M.no_filter;
+  int32_t rc = match_v2(ac, sc, M, s, n_hits, kRegions);
+  if (rc == 3) {  // the prefix-filter engine handed the batch back: once more on the byte-level engine
+    (*repeats)++;
+    M.no_filter = 1;
+    if (!neutral) {
+      const uint32_t streak = std::min(ac->pf_streak[pm].fetch_add(1, std::memory_order_relaxed) + 1, 6u);
+      ac->pf_skip[pm].store(1u << streak, std::memory_order_relaxed);
+    }
     rc = match_v2(ac, sc, M, s, n_hits, kRegions);
-    if (rc == 3) {  // the prefix-filter engine handed the batch back: once more on the byte-level engine
-      repeats++;
-      M.no_filter = 1;
-      if (!neutral) {
-        const uint32_t streak = std::min(ac->pf_streak[pm].fetch_add(1, std::memory_order_relaxed) + 1, 6u);
-        ac->pf_skip[pm].store(1u << streak, std::memory_order_relaxed);
-      }
-      rc = match_v2(ac, sc, M, s, n_hits, kRegions);
-    } else if (tried && rc == AHA_OK && !neutral) {
-      ac->pf_streak[pm].store(0, std::memory_order_relaxed);
-    }
-    if (rc == 2) {  // denser than cap said: regions of one event per byte
-      repeats++;
-      rc = match_v2(ac, sc, M, s, n_hits, kFullRegions);
-    }
-    if (rc == 3) {
-      M.no_filter = 1;
-      rc = match_v2(ac, sc, M, s, n_hits, kFullRegions);
-    }
-    if (rc == 2) rc = match_v2(ac, sc, M, s, n_hits, kSlabs);  // (not reached: full-size regions cannot overflow)
-    if (rc == AHA_OK && repeats) note_repeats(ac, repeats);
-    if (rc < 0) return rc;
-    if (rc == AHA_OK) return fits();
-    *n_hits = 0;  // rc == 1: fall through to the two-pass engine
-    repeats++;
-    if (M.check_docs && (rc = check_now())) return rc;  // (no single-traversal pass has looked at the offsets)
+  } else if (tried && rc == AHA_OK && !neutral) {
+    ac->pf_streak[pm].store(0, std::memory_order_relaxed);
   }
+  if (rc == 2) {  // denser than cap said: regions of one event per byte
+    (*repeats)++;
+    rc = match_v2(ac, sc, M, s, n_hits, kFullRegions);
+  }
+  if (rc == 3) {
+    M.no_filter = 1;
+    rc = match_v2(ac, sc, M, s, n_hits, kFullRegions);
+  }
+  if (rc == 2) rc = match_v2(ac, sc, M, s, n_hits, kSlabs);  // (not reached: full-size regions cannot overflow)
+  if (rc == AHA_OK && *repeats) note_repeats(ac, *repeats);
+  if (rc < 0) return rc;
+  if (rc == AHA_OK) return fits(*n_hits, M.cap);
+  *n_hits = 0;  // rc == 1: the two-pass engine
+  (*repeats)++;
+  if (M.check_docs && (rc = check_docs_now(ac, sc, M.doc_off, M.n_docs, M.n_bytes, s))) return rc;  // (no single-traversal pass has looked at the offsets)
+  return 1;
+}
+
+// The two-pass engine: count -> scan -> write over chunks with a warm-up (kernels.hip); every batch fits it.
+static int32_t two_pass_pass(aha_ac *ac, Scratch *sc, MatchArgs &M, uint32_t repeats, hipStream_t s, uint64_t *n_hits) {
+  int32_t rc;
   if ((rc = stage_folded(ac, sc, M, s))) return rc;
   two_pass_chunks(ac, M, ac->chunk, 8);  // warm-up is Lmax-1 bytes per chunk
   uint64_t n_blocks;
@@ -894,7 +924,7 @@ int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
   launch_write(ac->dev, M, s);
   if (prof) HIPCHK(ac, hipEventRecord(sc->ev[4], s));
   HIPCHK(ac, hipGetLastError());
-  HIPCHK(ac, hipMemcpyAsync(sc->h_totals, sc->d_totals, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipMemcpyAsync(sc->h_totals, d_totals(sc), 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
   HIPCHK(ac, hipStreamSynchronize(s));
   *n_hits = sc->h_totals[0];
   if (prof) {
@@ -907,7 +937,25 @@ int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
     t.repeats = repeats;
     publish_event_timing(ac, sc, t, 1, 1, 2, 2, 3);
   }
-  return fits();
+  return fits(*n_hits, M.cap);
+}
+
+// One device-resident batch matched: the opening, then the engine that takes it.  The single-traversal pipelines validate
+// unchecked offsets on the device in front of their traversal; every other path -- an empty batch, match_longest, the two-pass
+// engine -- reads the verdict back first.
+int32_t device_match(aha_ac *ac, Scratch *sc, const Batch &B, const HitOut &out, uint64_t *n_hits, CallOpt opt) {
+  Opening O;
+  auto decide = [&](const MatchArgs &, int longest) { return (int32_t)(ac->v2_ok && !longest && B.n_bytes != 0); };
+  int32_t rc = open_call(ac, sc, B, !(out.cap && !out.d_out), out.d_doc_hit_off, n_hits, opt, decide, nullptr, 0, O);
+  if (rc || O.done) return rc;
+  MatchArgs &M = O.M;
+  M.out = out.d_out;
+  M.cap = out.cap;
+  M.doc_hit_off = out.d_doc_hit_off;
+  if (O.longest) return match_longest_pass(ac, sc, M, O.longest, B.stream, n_hits);
+  uint32_t repeats = 0;  // passes thrown away (aha_timing.repeats)
+  if (ac->v2_ok && (rc = single_traversal_ladder(ac, sc, M, opt, B.stream, n_hits, &repeats)) != 1) return rc;
+  return two_pass_pass(ac, sc, M, repeats, B.stream, n_hits);
 }
 
 // ---- count calls (aha_ac_count_batch*) ------------------------------------------------------------------------------
@@ -931,7 +979,7 @@ static int32_t count_two_pass(aha_ac *ac, Scratch *sc, MatchArgs M, hipStream_t 
   if (M.doc_hit_off) launch_count_doc_offsets(M, s);
   if (prof) HIPCHK(ac, hipEventRecord(sc->ev[4], s));
   HIPCHK(ac, hipGetLastError());
-  HIPCHK(ac, hipMemcpyAsync(sc->h_totals, sc->d_totals, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipMemcpyAsync(sc->h_totals, d_totals(sc), 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
   HIPCHK(ac, hipStreamSynchronize(s));
   *n_hits = sc->h_totals[0];
   if (prof) {
@@ -965,6 +1013,36 @@ static int32_t count_single(aha_ac *ac, Scratch *sc, MatchArgs &M, hipStream_t s
 
 static void *count_reserve(Scratch *sc, CountSlot slot, size_t bytes) { return reserve_ptr(sc->cntbuf[slot], bytes, kGrowQuarter); }
 
+// The documents [d0, d1) of B cut out as a checked batch of their own: the text from the range's first byte, the offsets
+// relative to it in rel_slot.  `off` is the host's copy of B.doc_off; `rel` is the host's side of the upload and stays the
+// host's until B.stream has run.  The kernels read aligned 16-byte pieces: where text_slot is given and the range's first byte
+// is not aligned, the range is copied there, folded on the way by mode `fold` (stage_text) -- R.text then differs from
+// B.text + off[d0].  No memory for a slot: nomem_text, AHA_E_HIP.
+static int32_t slice(aha_ac *ac, const Batch &B, const uint64_t *off, uint64_t d0, uint64_t d1, std::vector<uint64_t> &rel, Buf &rel_slot,
+                     Buf *text_slot, Grow grow, int fold, const char *nomem_text, Batch &R) {
+  auto nomem = [&] {
+    tls_err = nomem_text;
+    return AHA_E_HIP;
+  };
+  const uint64_t nd = d1 - d0, nb = off[d1] - off[d0];
+  try {
+    rel.resize(nd + 1);
+  } catch (...) {
+    return AHA_E_NOMEM;
+  }
+  for (uint64_t d = 0; d <= nd; d++) rel[d] = off[d0 + d] - off[d0];
+  uint64_t *d_rel = (uint64_t *)reserve_ptr(rel_slot, (nd + 1) * 8, grow);
+  if (!d_rel) return nomem();
+  HIPCHK(ac, hipMemcpyAsync(d_rel, rel.data(), (nd + 1) * 8, hipMemcpyHostToDevice, B.stream));
+  R = checked_batch(B.text + off[d0], d_rel, nd, nb, B.params, B.stream);
+  if (text_slot && nb && reinterpret_cast<uintptr_t>(R.text) % 16 != 0) {
+    void *t = reserve_ptr(*text_slot, nb + 64, grow);
+    if (!t) return nomem();
+    if (int32_t rc = stage_text(ac, &R.text, nb, t, fold, d_rel, nd, B.stream)) return rc;
+  }
+  return AHA_OK;
+}
+
 // A batch whose full-size regions are beyond the bound or cannot be allocated (HBM held elsewhere): counted in ranges of whole
 // documents, one after another, each through the same pipeline -- the key counts add up in the caller's vector as they do
 // for running totals, the documents' offsets are rebased on the host.  A range that still does not fit is halved; a single
@@ -972,6 +1050,8 @@ static void *count_reserve(Scratch *sc, CountSlot slot, size_t bytes) { return r
 // two-pass engine's counting form here.
 static int32_t count_ranges(aha_ac *ac, Scratch *sc, const MatchArgs &M0, hipStream_t s, uint64_t *n_hits) {
   const uint64_t D = M0.n_docs;
+  const Batch B0 = checked_batch(M0.text, M0.doc_off, D, M0.n_bytes, nullptr, s);  // (the text as take_text left it)
+  const char *nomem_text = "hipMalloc failed for a document range of a count call";
   std::vector<uint64_t> off, hd, tmp, rel;
   try {
     off.resize(D + 1);
@@ -984,10 +1064,6 @@ static int32_t count_ranges(aha_ac *ac, Scratch *sc, const MatchArgs &M0, hipStr
   uint64_t limit = std::max<uint64_t>(M0.n_bytes / 2, 1), base = 0;
   uint32_t ranges = 0;
   int32_t rc;
-  auto nomem = [] {
-    tls_err = "hipMalloc failed for a document range of a count call";
-    return AHA_E_HIP;
-  };
   // a cover call: the ranges share one mask (they run one after another on the stream, so a word two of them touch is safe);
   // it is cleared once, here -- the offsets have been validated
   if (M0.cover_mask) HIPCHK(ac, hipMemsetAsync(M0.cover_mask, 0, (size_t)((M0.n_bytes + 31) / 32) * 4, s));
@@ -996,34 +1072,30 @@ static int32_t count_ranges(aha_ac *ac, Scratch *sc, const MatchArgs &M0, hipStr
     while (d1 < D && off[d1 + 1] - off[d0] <= limit) d1++;
     const uint64_t nd = d1 - d0, nb = off[d1] - off[d0];
     try {
-      rel.resize(nd + 1);
       tmp.resize(nd + 1);
     } catch (...) {
       return AHA_E_NOMEM;
     }
-    for (uint64_t d = 0; d <= nd; d++) rel[d] = off[d0 + d] - off[d0];
-    uint64_t *d_rel = (uint64_t *)count_reserve(sc, kCntRel, (nd + 1) * 8);
     uint64_t *d_dho = M0.doc_hit_off ? (uint64_t *)count_reserve(sc, kCntDho, (nd + 1) * 8) : nullptr;
-    if (!d_rel || (M0.doc_hit_off && !d_dho)) return nomem();
-    HIPCHK(ac, hipMemcpyAsync(d_rel, rel.data(), (nd + 1) * 8, hipMemcpyHostToDevice, s));
-    // the range as a batch of its own
+    if (M0.doc_hit_off && !d_dho) {
+      tls_err = nomem_text;
+      return AHA_E_HIP;
+    }
+    // the range as a batch of its own.  (A folded handle whose text is still the caller's: an unaligned range is folded on the
+    // way, an aligned one stays the caller's -- the prefix-filter engine folds in its loads, the others stage it)
+    Batch R;
+    if ((rc = slice(ac, B0, off.data(), d0, d1, rel, sc->cntbuf[kCntRel], &sc->cntbuf[kCntText], kGrowQuarter, M0.fold, nomem_text, R)))
+      return rc;
     MatchArgs Mr = M0;
-    Mr.text = M0.text + off[d0];
-    Mr.doc_off = d_rel;
+    Mr.text = R.text;
+    Mr.doc_off = R.doc_off;
     Mr.n_docs = nd;
     Mr.n_bytes = nb;
     Mr.doc_hit_off = d_dho;
     Mr.check_docs = 0;
     Mr.cover_bit0 = M0.cover_bit0 + off[d0];
     Mr.cover_clear = 0;
-    // (a folded handle whose text is still the caller's: an unaligned range is folded on the way, an aligned one stays the
-    // caller's -- the prefix-filter engine folds in its loads, the others stage it)
-    if (nb && reinterpret_cast<uintptr_t>(Mr.text) % 16 != 0) {
-      void *t = count_reserve(sc, kCntText, nb + 64);
-      if (!t) return nomem();
-      if ((rc = stage_text(ac, &Mr.text, nb, t, M0.fold, d_rel, nd, s))) return rc;
-      Mr.fold = 0;
-    }
+    if (R.text != M0.text + off[d0]) Mr.fold = 0;  // (staged, and folded on the way)
     uint64_t nh = 0;
     rc = AHA_OK;
     if (nb == 0) {
@@ -1074,7 +1146,7 @@ int32_t device_feed_longest_count(aha_ac *ac, Scratch *sc, const FeedArgs &F, Fe
   M.n_bytes = F.n_bytes;
   if ((rc = take_text(ac, sc, F.text, F.n_bytes, M, s))) return rc;
   if ((rc = stage_folded(ac, sc, M, s))) return rc;
-  if ((rc = ensure_scratch(ac, sc, 1, 1, F.D))) return rc;
+  if ((rc = two_pass_totals(ac, sc))) return rc;
   L.end = (FeedLongSeq *)reserve_ptr(sc->flngbuf[kFlEnd], std::max<uint64_t>(F.D, 1) * sizeof(FeedLongSeq), kGrowEighth);
   if (!L.end) {
     tls_err = "hipMalloc failed for the scratch of a call on a longest feed";
@@ -1089,9 +1161,9 @@ int32_t device_feed_longest_count(aha_ac *ac, Scratch *sc, const FeedArgs &F, Fe
   }
   if (P.chunks) {
     // the chunked form is exact only for text without NUL bytes (kernels.hip, k_has_nul): look first
-    HIPCHK(ac, hipMemsetAsync(sc->d_totals, 0, 2 * sizeof(uint64_t), s));
-    launch_has_nul(M.text, F.n_bytes, sc->d_totals + 1, s);
-    HIPCHK(ac, hipMemcpyAsync(sc->h_totals, sc->d_totals, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(ac, hipMemsetAsync(d_totals(sc), 0, 2 * sizeof(uint64_t), s));
+    launch_has_nul(M.text, F.n_bytes, d_totals(sc) + 1, s);
+    HIPCHK(ac, hipMemcpyAsync(sc->h_totals, d_totals(sc), 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     HIPCHK(ac, hipStreamSynchronize(s));
     M.has_nul = sc->h_totals[1] ? 1 : 0;
   }
@@ -1100,7 +1172,7 @@ int32_t device_feed_longest_count(aha_ac *ac, Scratch *sc, const FeedArgs &F, Fe
   if ((rc = ensure_stale(ac))) return rc;
   feedlong_launch_walk(ac->dev_longest, M, F, L, P.chunks, P.intersectable, false, s);
   if (P.chunks && M.has_nul) {  // a chunk whose warm-up would not end (a NUL every few bytes) gave up: piece by piece
-    HIPCHK(ac, hipMemcpyAsync(sc->h_totals, sc->d_totals, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(ac, hipMemcpyAsync(sc->h_totals, d_totals(sc), 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     HIPCHK(ac, hipStreamSynchronize(s));
     if (sc->h_totals[1] == 2) {
       P.chunks = false;
@@ -1110,7 +1182,7 @@ int32_t device_feed_longest_count(aha_ac *ac, Scratch *sc, const FeedArgs &F, Fe
   }
   launch_scan_blocks(M, n_blocks, s);
   HIPCHK(ac, hipGetLastError());
-  HIPCHK(ac, hipMemcpyAsync(sc->h_totals, sc->d_totals, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipMemcpyAsync(sc->h_totals, d_totals(sc), 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
   HIPCHK(ac, hipStreamSynchronize(s));
   *n_hits = sc->h_totals[0];
   return AHA_OK;
@@ -1132,44 +1204,28 @@ int32_t device_feed_longest_write(aha_ac *ac, const FeedArgs &F, const FeedLongA
 // two-pass engine's counting form where a match of the batch takes that engine, and for a separator filter (a test per hit).
 // Byte offsets throughout: char offsets change no count.  The handle's history (the prefix filter's back-off, the pair
 // engine's give-ups) is read, never written: the next match call behaves as if this call had not happened.
-int32_t device_count(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
-                     uint64_t n_bytes, const aha_match_params *params, uint32_t flags, uint64_t *d_key_counts,
-                     uint64_t *d_doc_hit_offsets, uint64_t *n_hits, void *stream, bool offsets_checked, uint32_t *cover_mask,
-                     bool as_is) {
-  if (!ac || !n_hits || !d_doc_offsets) return AHA_E_INVALID;
-  if (ac->device < 0) return no_device();
-  if (flags & ~AHA_COUNT_ACCUMULATE) return AHA_E_INVALID;
-  DeviceGuard g(ac->device);
-  hipStream_t s = (hipStream_t)stream;
-  MatchArgs M{};
-  int longest = 0;
-  int32_t rc = fill_params(ac, params, M, &longest);
-  if (rc) return rc;
-  if (longest) {  // (the entry points refuse it with their own texts before any device work: capi.cpp no_longest_form)
-    tls_err = "count calls have no match_longest form";
-    return AHA_E_INVALID;
-  }
-  if ((rc = ready_events(ac, sc))) return rc;
-  *n_hits = 0;
-  M.chars = 0;
-  const uint32_t K = ac->aut.n_keys;
-  auto check_now = [&]() { return check_docs_now(ac, sc, d_doc_offsets, n_docs, n_bytes, s); };
-  const bool single = ac->v2_ok && !M.sep && n_bytes != 0;
-  const bool defer_check = !offsets_checked && single;
-  if (!offsets_checked && !defer_check && (rc = check_now())) return rc;
-  M.check_docs = defer_check ? 1 : 0;
+int32_t device_count(aha_ac *ac, Scratch *sc, const Batch &B, uint32_t flags, uint64_t *d_key_counts, uint64_t *d_doc_hit_offsets,
+                     uint64_t *n_hits, CallOpt opt, uint32_t *cover_mask) {
+  Opening O;
+  bool single = false;
+  auto decide = [&](const MatchArgs &M, int longest) {
+    if (longest) {  // (the entry points refuse it with their own texts before any device work: capi.cpp no_longest_form)
+      tls_err = "count calls have no match_longest form";
+      return (int32_t)AHA_E_INVALID;
+    }
+    single = ac->v2_ok && !M.sep && B.n_bytes != 0;
+    return (int32_t)single;
+  };
   // the caller's counts: cleared unless it keeps running totals (then only added to, by the passes that run to their end)
-  if (d_key_counts && !(flags & AHA_COUNT_ACCUMULATE)) HIPCHK(ac, hipMemsetAsync(d_key_counts, 0, (size_t)K * 8, s));
-  if (n_bytes == 0) {
-    if (d_doc_hit_offsets) HIPCHK(ac, hipMemsetAsync(d_doc_hit_offsets, 0, (n_docs + 1) * sizeof(uint64_t), s));
-    HIPCHK(ac, hipStreamSynchronize(s));
-    return AHA_OK;
-  }
-  if (!d_corpus) return AHA_E_INVALID;
-  M.doc_off = d_doc_offsets;
-  M.n_docs = n_docs;
-  M.n_bytes = n_bytes;
-  if ((rc = take_text(ac, sc, d_corpus, n_bytes, M, s, as_is))) return rc;
+  const bool clear = d_key_counts && !(flags & AHA_COUNT_ACCUMULATE);
+  int32_t rc = open_call(ac, sc, B, !(flags & ~AHA_COUNT_ACCUMULATE), d_doc_hit_offsets, n_hits, opt, decide, clear ? d_key_counts : nullptr,
+                         ac ? (size_t)ac->aut.n_keys * 8 : 0, O);
+  if (rc || O.done) return rc;
+  hipStream_t s = B.stream;
+  MatchArgs &M = O.M;
+  const uint32_t K = ac->aut.n_keys;
+  auto check_now = [&]() { return check_docs_now(ac, sc, B.doc_off, B.n_docs, B.n_bytes, s); };
+  M.chars = 0;
   M.out = nullptr;
   M.cap = 0;
   M.doc_hit_off = d_doc_hit_offsets;
@@ -1208,13 +1264,13 @@ int32_t device_count(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
 // k_count's cover mode).  Then, over the finished mask and only where asked for: the redacted copy, the documents' covered
 // bytes; the total always.  Scratch beyond the count call's: N / 8 bytes where the caller gives no mask, 8 bytes per chunk,
 // nothing per hit.
-int32_t device_cover(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
-                     uint64_t n_bytes, const aha_match_params *params, uint32_t flags, uint32_t *d_mask, uint8_t *d_redacted,
-                     uint8_t fill, uint64_t *d_doc_covered, uint64_t *n_covered, uint64_t *n_hits_out, void *stream, bool offsets_checked) {
-  if (!ac || !n_covered || !d_doc_offsets || flags) return AHA_E_INVALID;
+int32_t device_cover(aha_ac *ac, Scratch *sc, const Batch &B, uint32_t flags, uint32_t *d_mask, uint8_t *d_redacted, uint8_t fill,
+                     uint64_t *d_doc_covered, uint64_t *n_covered, uint64_t *n_hits_out) {
+  if (!ac || !n_covered || !B.doc_off || flags) return AHA_E_INVALID;
   if (ac->device < 0) return no_device();
   DeviceGuard g(ac->device);
-  hipStream_t s = (hipStream_t)stream;
+  hipStream_t s = B.stream;
+  const uint64_t n_docs = B.n_docs, n_bytes = B.n_bytes;
   *n_covered = 0;
   if (n_hits_out) *n_hits_out = 0;
   const uint64_t n_words = (n_bytes + 31) / 32;
@@ -1228,9 +1284,7 @@ int32_t device_cover(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
   if (!d_total) return nomem();
   int32_t rc;
   uint64_t n_hits = 0;
-  if ((rc = device_count(ac, sc, d_corpus, d_doc_offsets, n_docs, n_bytes, params, 0, nullptr, nullptr, &n_hits, stream, offsets_checked,
-                         mask)))
-    return rc;
+  if ((rc = device_count(ac, sc, B, 0, nullptr, nullptr, &n_hits, CallOpt::kNone, mask))) return rc;
   const bool prof = ac->profiling.load();
   const auto t0 = std::chrono::steady_clock::now();
   const uint32_t blocks = post_grid(ac);
@@ -1238,8 +1292,8 @@ int32_t device_cover(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uin
   if (n_bytes) {
     HIPCHK(ac, hipMemsetAsync(d_total, 0, 8, s));
     cover_launch_total(mask, n_words, d_total, blocks, s);
-    if (d_redacted) cover_launch_redact(d_corpus, d_redacted, mask, n_bytes, fill, blocks, s);
-    if (d_doc_covered && n_docs) cover_launch_doc_covered(mask, d_doc_offsets, n_docs, d_doc_covered, blocks, s);
+    if (d_redacted) cover_launch_redact(B.text, d_redacted, mask, n_bytes, fill, blocks, s);
+    if (d_doc_covered && n_docs) cover_launch_doc_covered(mask, B.doc_off, n_docs, d_doc_covered, blocks, s);
     HIPCHK(ac, hipGetLastError());
     HIPCHK(ac, hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, s));
   } else if (d_doc_covered && n_docs) {
@@ -1301,21 +1355,11 @@ struct RangeBook {
   }
 };
 
-struct RangeBatch {  // a range as a batch of its own
-  const uint8_t *text;
-  const uint64_t *d_rel;
-  uint64_t nd, nb;
-};
-
 // What the ranges of one call share: the caller's batch, the family's slots and their growth, its name in the messages.
 struct RangeCall {
   aha_ac *ac;
   Scratch *sc;
-  const uint8_t *d_corpus;
-  const uint64_t *d_doc_offsets;
-  uint64_t D, n_bytes;
-  const aha_match_params *params;
-  void *stream;
+  Batch B;
   Buf &rel_slot, &text_slot, &hits_slot;
   Grow grow;
   const char *family, *nomem_text;
@@ -1327,57 +1371,38 @@ struct RangeCall {
     return AHA_E_HIP;
   }
 
-  // The documents [d0, d1) as a batch: the caller's arrays where that is the whole batch; else the text from the range's first
-  // byte, the offsets relative to it in rel_slot.
   // the documents' offsets on the host, fetched once
   int32_t host_offsets() {
-    hipStream_t s = (hipStream_t)stream;
     if (!off.empty()) return AHA_OK;
     try {
-      off.resize(D + 1);
+      off.resize(B.n_docs + 1);
     } catch (...) {
       return AHA_E_NOMEM;
     }
-    HIPCHK(ac, hipMemcpyAsync(off.data(), d_doc_offsets, (D + 1) * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(ac, hipStreamSynchronize(s));
+    HIPCHK(ac, hipMemcpyAsync(off.data(), B.doc_off, (B.n_docs + 1) * 8, hipMemcpyDeviceToHost, B.stream));
+    HIPCHK(ac, hipStreamSynchronize(B.stream));
     return AHA_OK;
   }
 
-  int32_t batch(uint64_t d0, uint64_t d1, RangeBatch &B) {
-    hipStream_t s = (hipStream_t)stream;
-    B = RangeBatch{d_corpus, d_doc_offsets, d1 - d0, n_bytes};
-    if (d0 == 0 && d1 == D) return AHA_OK;
+  // The documents [d0, d1) as a checked batch: the caller's arrays where that is the whole batch, else their slice.
+  // (the kernels read aligned 16-byte pieces; a folded handle's match and count make their own folded -- and aligned -- copy,
+  // so only an unfolded handle's unaligned range is staged here)
+  int32_t batch(uint64_t d0, uint64_t d1, Batch &R) {
+    R = B;
+    R.checked = true;  // (the count call in front has looked at the offsets)
+    if (d0 == 0 && d1 == B.n_docs) return AHA_OK;
     if (int32_t rc = host_offsets()) return rc;
-    try {
-      rel.resize(B.nd + 1);
-    } catch (...) {
-      return AHA_E_NOMEM;
-    }
-    B.nb = off[d1] - off[d0];
-    for (uint64_t d = 0; d <= B.nd; d++) rel[d] = off[d0 + d] - off[d0];
-    uint64_t *r = (uint64_t *)reserve_ptr(rel_slot, (B.nd + 1) * 8, grow);
-    if (!r) return nomem();
-    HIPCHK(ac, hipMemcpyAsync(r, rel.data(), (B.nd + 1) * 8, hipMemcpyHostToDevice, s));
-    B.d_rel = r;
-    B.text = d_corpus + off[d0];
-    // (the kernels read aligned 16-byte pieces; a folded handle's match and count make their own folded -- and aligned -- copy)
-    if (!ac->fold() && reinterpret_cast<uintptr_t>(B.text) % 16 != 0) {
-      void *t = reserve_ptr(text_slot, B.nb + 64, grow);
-      if (!t) return nomem();
-      if (int32_t rc = stage_text(ac, &B.text, B.nb, t, 0, nullptr, 0, s)) return rc;
-    }
-    HIPCHK(ac, hipStreamSynchronize(s));  // (rel is the host's until the copy has run)
+    if (int32_t rc = slice(ac, B, off.data(), d0, d1, rel, rel_slot, ac->fold() ? nullptr : &text_slot, grow, 0, nomem_text, R)) return rc;
+    HIPCHK(ac, hipStreamSynchronize(B.stream));  // (rel is the host's until the copy has run)
     return AHA_OK;
   }
 
   // The range's rh hits (the count's figure) into hits_slot: every engine, the handle's back-off state read and never written.
-  int32_t match(const RangeBatch &B, uint64_t rh, aha_hit **d_hits) {
+  int32_t match(const Batch &R, uint64_t rh, aha_hit **d_hits) {
     if (!(*d_hits = (aha_hit *)reserve_ptr(hits_slot, rh * sizeof(aha_hit), grow))) return nomem();
     const auto t_m0 = std::chrono::steady_clock::now();
     uint64_t got = 0;
-    if (int32_t rc = device_match(ac, sc, B.text, B.d_rel, B.nd, B.nb, params, *d_hits, rh, nullptr, &got, stream, true, nullptr,
-                                  nullptr, false, true))
-      return rc;
+    if (int32_t rc = device_match(ac, sc, R, HitOut{*d_hits, rh, nullptr}, &got, CallOpt::kNeutral)) return rc;
     if (got != rh) {
       tls_err = std::string(family) + ": the match and the count of a range disagree";
       return AHA_E_HIP;
@@ -1401,31 +1426,31 @@ static void *dc_reserve(Scratch *sc, DocCountSlot slot, size_t bytes) {
 //      the host adds them up (the offsets, the capacity check), kdc_gather writes the pairs below the capacity.
 // A single document whose hits are beyond the bound is never matched: a count call over it alone gives its key counts -- the
 // dense form's row --, which are compacted like one.
-int32_t device_doc_counts(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
-                          uint64_t n_bytes, const aha_match_params *params, aha_key_count *d_out, uint64_t cap,
-                          uint64_t *d_doc_pair_offsets, uint64_t *n_pairs, uint64_t *n_hits_out, void *stream, bool offsets_checked) {
-  if (!ac || !n_pairs || !d_doc_offsets) return AHA_E_INVALID;
+int32_t device_doc_counts(aha_ac *ac, Scratch *sc, const Batch &B0, aha_key_count *d_out, uint64_t cap, uint64_t *d_doc_pair_offsets,
+                          uint64_t *n_pairs, uint64_t *n_hits_out) {
+  if (!ac || !n_pairs || !B0.doc_off) return AHA_E_INVALID;
   if (ac->device < 0) return no_device();
   if (cap && !d_out) return AHA_E_INVALID;
   DeviceGuard g(ac->device);
-  hipStream_t s = (hipStream_t)stream;
-  const uint64_t D = n_docs, K = ac->aut.n_keys;
+  hipStream_t s = B0.stream;
+  const uint64_t D = B0.n_docs, K = ac->aut.n_keys;
   *n_pairs = 0;
   if (n_hits_out) *n_hits_out = 0;
   // byte offsets throughout: char offsets change no count
   aha_match_params pb;
   memset(&pb, 0, sizeof(pb));
-  if (params) memcpy(&pb, params, std::min<size_t>(params->struct_size, sizeof(pb)));
+  if (B0.params) memcpy(&pb, B0.params, std::min<size_t>(B0.params->struct_size, sizeof(pb)));
   pb.char_offsets = 0;
-  const aha_match_params *p = params ? &pb : nullptr;
-  RangeCall call{ac, sc, d_corpus, d_doc_offsets, D, n_bytes, p, stream, sc->dcbuf[kDcRel], sc->dcbuf[kDcText], sc->dcbuf[kDcHits],
+  Batch B = B0;
+  B.params = B0.params ? &pb : nullptr;
+  RangeCall call{ac, sc, B, sc->dcbuf[kDcRel], sc->dcbuf[kDcText], sc->dcbuf[kDcHits],
                  kGrowOrExact, "document counts", "hipMalloc failed for the scratch of a document-count call", RangeBook{ac, false}};
   auto nomem = [&]() { return call.nomem(); };
   int32_t rc;
   uint64_t *d_dho = (uint64_t *)dc_reserve(sc, kDcHitOff, (D + 1) * 8);
   if (!d_dho) return nomem();
   uint64_t n_hits = 0;
-  if ((rc = device_count(ac, sc, d_corpus, d_doc_offsets, D, n_bytes, p, 0, nullptr, d_dho, &n_hits, stream, offsets_checked))) return rc;
+  if ((rc = device_count(ac, sc, B, 0, nullptr, d_dho, &n_hits))) return rc;
   if (n_hits_out) *n_hits_out = n_hits;
   std::vector<uint64_t> hd, dpo, po;
   std::vector<uint32_t> np;
@@ -1452,8 +1477,8 @@ int32_t device_doc_counts(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, cons
   for (const DocRange &g : ranges) {
     const uint64_t d0 = g.d0, d1 = g.d1, nd = d1 - d0, rh = hd[d1] - hd[d0];
     for (uint64_t d = done; d < d0; d++) dpo[d + 1] = total;
-    RangeBatch B;
-    if ((rc = call.batch(d0, d1, B))) return rc;
+    Batch R;
+    if ((rc = call.batch(d0, d1, R))) return rc;
     uint32_t *d_np = (uint32_t *)dc_reserve(sc, kDcPairsPerDoc, nd * 4);
     if (!d_np) return nomem();
     HIPCHK(ac, hipMemsetAsync(d_np, 0, nd * 4, s));
@@ -1471,7 +1496,7 @@ int32_t device_doc_counts(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, cons
       DcItem *d_items = (DcItem *)dc_reserve(sc, kDcItems, sizeof(DcItem));
       if (!row || !tmp || !d_items) return nomem();
       uint64_t got = 0;
-      if ((rc = device_count(ac, sc, B.text, B.d_rel, 1, B.nb, p, 0, (uint64_t *)row, nullptr, &got, stream, true))) return rc;
+      if ((rc = device_count(ac, sc, R, 0, (uint64_t *)row, nullptr, &got))) return rc;
       call.book.matched(t_m0);
       items.assign(1, DcItem{0, tmp, 0, 0});
       HIPCHK(ac, hipMemcpyAsync(d_items, items.data(), sizeof(DcItem), hipMemcpyHostToDevice, s));
@@ -1479,7 +1504,7 @@ int32_t device_doc_counts(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, cons
       srcs[0] = tmp;
     } else {
       aha_hit *d_hits = nullptr;
-      if ((rc = call.match(B, rh, &d_hits))) return rc;
+      if ((rc = call.match(R, rh, &d_hits))) return rc;
       // the work items: [sort | range | dense documents (a row each, in groups) | slices of the dense documents' hits]
       uint32_t n_form[3] = {0, 0, 0};
       uint64_t range_pairs = 0, n_slices = 0;
@@ -1595,11 +1620,9 @@ static void *sel_reserve(Scratch *sc, SelectSlot slot, size_t bytes) { return re
 // A failing call writes none of the caller's buffers, so nothing is emitted before the total of ALL ranges is known: with one
 // range its L and select mask are still in scratch then; with more, the ranges are worked through a second time (steps 2 and 3
 // again, then the emit) -- the price of the rare case, instead of a second buffer of the selection's size.
-int32_t device_select(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
-                      uint64_t n_bytes, const aha_match_params *params, aha_hit *d_out, uint64_t cap, uint64_t *d_doc_sel_offsets,
-                      uint64_t *n_selected, uint64_t *n_hits_out, void *stream, bool offsets_checked, uint32_t flags) {
-  return device_select_to(ac, sc, d_corpus, d_doc_offsets, n_docs, n_bytes, params, d_out, cap, d_doc_sel_offsets, n_selected,
-                          n_hits_out, stream, offsets_checked, nullptr, flags);
+int32_t device_select(aha_ac *ac, Scratch *sc, const Batch &B, const HitOut &out, uint64_t *n_selected, uint64_t *n_hits_out,
+                      uint32_t flags) {
+  return device_select_to(ac, sc, B, out, n_selected, n_hits_out, nullptr, flags);
 }
 
 // device_select with a say in where the selection goes (handle.hpp SelectSink).  sink == null: the public entries, as above.
@@ -1609,21 +1632,22 @@ int32_t device_select(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const ui
 // Step 3 goes on behind the walk: S, the bytes inside a selected hit; T, the token starts, from S, the masks and the caller's
 // own bytes of the range; the rank is T's, and step 4 emits the tokens.  The ranges tile ALL documents, hits or none
 // (doc_ranges.hpp doc_tiles), bounded by their text as well as by their hits; a range without a hit is not matched.
-int32_t device_select_to(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
-                         uint64_t n_bytes, const aha_match_params *params, aha_hit *d_out, uint64_t cap, uint64_t *d_doc_sel_offsets,
-                         uint64_t *n_selected, uint64_t *n_hits_out, void *stream, bool offsets_checked, const SelectSink *sink,
-                         uint32_t flags) {
-  if (!ac || !n_selected || !d_doc_offsets) return AHA_E_INVALID;
+int32_t device_select_to(aha_ac *ac, Scratch *sc, const Batch &B, const HitOut &out, uint64_t *n_selected, uint64_t *n_hits_out,
+                         const SelectSink *sink, uint32_t flags) {
+  if (!ac || !n_selected || !B.doc_off) return AHA_E_INVALID;
+  aha_hit *d_out = out.d_out;  // (a sink gives its own, range by range)
+  uint64_t cap = out.cap;
+  uint64_t *const d_doc_sel_offsets = out.d_doc_hit_off;
   const bool tokens = (flags & AHA_SELECT_TOKENS) != 0, gap_runs = (flags & AHA_SELECT_GAP_RUNS) != 0;
   if (tokens && sink) return AHA_E_INVALID;
   if (ac->device < 0) return no_device();
   if (cap && !d_out) return AHA_E_INVALID;
   DeviceGuard g(ac->device);
-  hipStream_t s = (hipStream_t)stream;
-  const uint64_t D = n_docs;
+  hipStream_t s = B.stream;
+  const uint64_t D = B.n_docs, n_bytes = B.n_bytes;
   *n_selected = 0;
   if (n_hits_out) *n_hits_out = 0;
-  RangeCall call{ac, sc, d_corpus, d_doc_offsets, D, n_bytes, params, stream, sc->selbuf[kSelRel], sc->selbuf[kSelText],
+  RangeCall call{ac, sc, B, sc->selbuf[kSelRel], sc->selbuf[kSelText],
                  sc->selbuf[kSelHits], kGrowEighth, "select", "hipMalloc failed for the scratch of a select call", RangeBook{ac, true}};
   auto nomem = [&]() { return call.nomem(); };
   int32_t rc;
@@ -1631,8 +1655,7 @@ int32_t device_select_to(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const
   uint64_t *d_dso = (uint64_t *)sel_reserve(sc, kSelDocOff, (D + 1) * 8);
   if (!d_dho || !d_dso) return nomem();
   uint64_t n_hits = 0;
-  if ((rc = device_count(ac, sc, d_corpus, d_doc_offsets, D, n_bytes, params, 0, nullptr, d_dho, &n_hits, stream, offsets_checked)))
-    return rc;
+  if ((rc = device_count(ac, sc, B, 0, nullptr, d_dho, &n_hits))) return rc;
   std::vector<uint64_t> hd, bounds;
   std::vector<DocRange> ranges;
   try {
@@ -1674,10 +1697,10 @@ int32_t device_select_to(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const
   // steps 2 and 3 for the documents [d0, d1); *sel = the range's selected hits
   auto work = [&](uint64_t d0, uint64_t d1, uint64_t *sel) -> int32_t {
     const uint64_t rh = hd[d1] - hd[d0];
-    RangeBatch B;
-    if ((rc = call.batch(d0, d1, B))) return rc;
-    const uint64_t *d_rel = B.d_rel;
-    const uint64_t nd = B.nd, nb = B.nb, n_words = (nb + 31) / 32, n_blk = select_rank_blocks(nb);
+    Batch Rb;
+    if ((rc = call.batch(d0, d1, Rb))) return rc;
+    const uint64_t *d_rel = Rb.doc_off;
+    const uint64_t nd = Rb.n_docs, nb = Rb.n_bytes, n_words = (nb + 31) / 32, n_blk = select_rank_blocks(nb);
     uint64_t *L = (uint64_t *)sel_reserve(sc, kSelLongest, nb * 8);
     uint32_t *masks = (uint32_t *)sel_reserve(sc, kSelMasks, 3 * n_words * 4);
     uint64_t *blk = (uint64_t *)sel_reserve(sc, kSelBlocks, (n_blk + 1) * 8);
@@ -1690,7 +1713,7 @@ int32_t device_select_to(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const
     }
     aha_hit *d_hits = nullptr;
     if (rh || !tokens) {  // (a token call works ranges without a hit: nothing to match)
-      if ((rc = call.match(B, rh, &d_hits))) return rc;
+      if ((rc = call.match(Rb, rh, &d_hits))) return rc;
     }
     uint32_t *cover = masks, *doc_start = masks + n_words, *select = masks + 2 * n_words;
     HIPCHK(ac, hipMemsetAsync(L, 0, nb * 8, s));
@@ -1701,7 +1724,7 @@ int32_t device_select_to(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const
     if (tokens) {
       HIPCHK(ac, hipMemsetAsync(S, 0, n_words * 4, s));
       tokens_launch_spans(L, nb, select, S, blocks, s);
-      tokens_launch_starts(B.text, nb, select, S, doc_start, gap_runs, T, blocks, s);
+      tokens_launch_starts(Rb.text, nb, select, S, doc_start, gap_runs, T, blocks, s);
     }
     select_launch_rank(tokens ? T : select, nb, blk, blocks, s);
     HIPCHK(ac, hipGetLastError());
@@ -1786,16 +1809,14 @@ static void *rep_reserve(Scratch *sc, ReplaceSlot slot, size_t bytes) { return r
 //      documents' offsets into the result (scan_replace.hip).  The last of them is the total: it comes back to the host.
 //   3. Once the total is known to fit: the copy, then the documents' offsets to the caller.
 // A failing call writes none of the caller's buffers.
-int32_t device_replace(aha_ac *ac, Scratch *sc, const aha_repl *table, const uint8_t *d_corpus, const uint64_t *d_doc_offsets,
-                       uint64_t n_docs, uint64_t n_bytes, const aha_match_params *params, uint8_t *d_out, uint64_t cap_bytes,
-                       uint64_t *d_doc_out_offsets, uint64_t *n_out_bytes, uint64_t *n_selected, uint64_t *n_hits_out, void *stream,
-                       bool offsets_checked) {
-  if (!ac || !table || !n_out_bytes || !d_doc_offsets) return AHA_E_INVALID;
+int32_t device_replace(aha_ac *ac, Scratch *sc, const aha_repl *table, const Batch &B, uint8_t *d_out, uint64_t cap_bytes,
+                       uint64_t *d_doc_out_offsets, uint64_t *n_out_bytes, uint64_t *n_selected, uint64_t *n_hits_out) {
+  if (!ac || !table || !n_out_bytes || !B.doc_off) return AHA_E_INVALID;
   if (ac->device < 0 || !table->d_ent) return no_device();
   if (cap_bytes && !d_out) return AHA_E_INVALID;
   DeviceGuard g(ac->device);
-  hipStream_t s = (hipStream_t)stream;
-  const uint64_t D = n_docs;
+  hipStream_t s = B.stream;
+  const uint64_t D = B.n_docs;
   *n_out_bytes = 0;
   auto nomem = [&]() {
     tls_err = "hipMalloc failed for the scratch of a replace call";
@@ -1828,9 +1849,7 @@ int32_t device_replace(aha_ac *ac, Scratch *sc, const aha_repl *table, const uin
     return AHA_OK;
   };
   uint64_t n = 0, n_hits = 0;
-  if ((rc = device_select_to(ac, sc, d_corpus, d_doc_offsets, D, n_bytes, params, nullptr, 0, nullptr, &n, &n_hits, stream,
-                             offsets_checked, &sink)))
-    return rc;
+  if ((rc = device_select_to(ac, sc, B, HitOut{nullptr, 0, nullptr}, &n, &n_hits, &sink))) return rc;
   const auto t_sel1 = std::chrono::steady_clock::now();
   const uint64_t *d_dso = (const uint64_t *)sc->selbuf[kSelDocOff].p;
   const aha_hit *d_sel = (const aha_hit *)sc->repbuf[kRepSel].p;
@@ -1841,15 +1860,15 @@ int32_t device_replace(aha_ac *ac, Scratch *sc, const aha_repl *table, const uin
   uint64_t *d_doo = (uint64_t *)rep_reserve(sc, kRepDocOut, (D + 1) * 8);
   if (!A || !shift || !sums || !d_doo) return nomem();
   const uint32_t blocks = ac->rep_blocks ? ac->rep_blocks : post_grid(ac);
-  replace_launch_delta(d_sel, n, d_dso, d_doc_offsets, D, table->d_ent, table->n_keys, A, shift, blocks, s);
+  replace_launch_delta(d_sel, n, d_dso, B.doc_off, D, table->d_ent, table->n_keys, A, shift, blocks, s);
   replace_launch_scan(shift, n, sums, blocks, s);
-  replace_launch_doc_offsets(d_doc_offsets, d_dso, shift, D, d_doo, blocks, s);
+  replace_launch_doc_offsets(B.doc_off, d_dso, shift, D, d_doo, blocks, s);
   HIPCHK(ac, hipGetLastError());
   uint64_t total = 0;
   HIPCHK(ac, hipMemcpyAsync(&total, d_doo + D, 8, hipMemcpyDeviceToHost, s));
   HIPCHK(ac, hipStreamSynchronize(s));
   if (total <= cap_bytes) {
-    replace_launch_copy(d_corpus, d_sel, A, shift, n, table->d_ent, table->n_keys, (const uint8_t *)table->d_blob, d_out, total,
+    replace_launch_copy(B.text, d_sel, A, shift, n, table->d_ent, table->n_keys, (const uint8_t *)table->d_blob, d_out, total,
                         blocks, s);
     HIPCHK(ac, hipGetLastError());
     if (d_doc_out_offsets) HIPCHK(ac, hipMemcpyAsync(d_doc_out_offsets, d_doo, (D + 1) * 8, hipMemcpyDeviceToDevice, s));
@@ -1874,9 +1893,9 @@ static void *grp_reserve(Scratch *sc, GrepSlot slot, size_t bytes) { return rese
 uint32_t grep_grid(const aha_ac *ac) { return ac->grep_blocks ? ac->grep_blocks : post_grid(ac); }
 
 // The first half of a records call: the record-end mask and its rank into grpbuf, the total read back.
-int32_t device_records_settle(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
-                              uint64_t n_bytes, uint8_t delim, uint64_t *n_records, void *stream) {
-  hipStream_t s = (hipStream_t)stream;
+int32_t device_records_settle(aha_ac *ac, Scratch *sc, const Batch &B, uint8_t delim, uint64_t *n_records) {
+  hipStream_t s = B.stream;
+  const uint64_t n_bytes = B.n_bytes;
   *n_records = 0;
   if (!n_bytes) return AHA_OK;
   const uint32_t blocks = grep_grid(ac);
@@ -1888,7 +1907,7 @@ int32_t device_records_settle(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, 
     return AHA_E_HIP;
   }
   uint64_t total = 0;
-  grep_launch_ends(d_corpus, n_bytes, delim, d_doc_offsets, n_docs, mask, blocks, s);
+  grep_launch_ends(B.text, n_bytes, delim, B.doc_off, B.n_docs, mask, blocks, s);
   select_launch_rank(mask, n_bytes, blk, blocks, s);
   HIPCHK(ac, hipGetLastError());
   HIPCHK(ac, hipMemcpyAsync(&total, blk + n_blk, 8, hipMemcpyDeviceToHost, s));
@@ -1898,15 +1917,15 @@ int32_t device_records_settle(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, 
 }
 
 // The second half, once the total is known to fit: every set bit as a record's end, the documents' offsets into the records.
-int32_t device_records_emit(aha_ac *ac, Scratch *sc, const uint64_t *d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
-                            uint64_t *d_rec_offsets, uint64_t *d_doc_rec_offsets, void *stream) {
-  hipStream_t s = (hipStream_t)stream;
+int32_t device_records_emit(aha_ac *ac, Scratch *sc, const Batch &B, uint64_t *d_rec_offsets, uint64_t *d_doc_rec_offsets) {
+  hipStream_t s = B.stream;
+  const uint64_t n_docs = B.n_docs, n_bytes = B.n_bytes;
   if (n_bytes) {
     const uint32_t blocks = grep_grid(ac);
     const uint32_t *mask = (const uint32_t *)sc->grpbuf[kGrpEnds].p;
     const uint64_t *blk = (const uint64_t *)sc->grpbuf[kGrpEndBlocks].p;
     if (d_rec_offsets) grep_launch_emit_ends(mask, n_bytes, blk, d_rec_offsets, blocks, s);
-    if (d_doc_rec_offsets) select_launch_rank_docs(mask, blk, d_doc_offsets, n_docs + 1, 0, d_doc_rec_offsets, blocks, s);
+    if (d_doc_rec_offsets) select_launch_rank_docs(mask, blk, B.doc_off, n_docs + 1, 0, d_doc_rec_offsets, blocks, s);
     HIPCHK(ac, hipGetLastError());
   } else {
     if (d_rec_offsets) HIPCHK(ac, hipMemsetAsync(d_rec_offsets, 0, 8, s));
@@ -1923,26 +1942,24 @@ int32_t device_records_emit(aha_ac *ac, Scratch *sc, const uint64_t *d_doc_offse
 //   3. Once it fits: every set bit as a record's end, and the documents' offsets into the records -- the rank of their first
 //      byte (select's per-position rank).
 // A failing call writes none of the caller's buffers.  Scratch: N / 8 bytes of mask, 8 bytes per 2048 text bytes.
-int32_t device_records(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
-                       uint64_t n_bytes, uint8_t delim, uint64_t *d_rec_offsets, uint64_t cap_records, uint64_t *d_doc_rec_offsets,
-                       uint64_t *n_records, void *stream, bool offsets_checked) {
-  if (!ac || !n_records || !d_doc_offsets) return AHA_E_INVALID;
+int32_t device_records(aha_ac *ac, Scratch *sc, const Batch &B, uint8_t delim, uint64_t *d_rec_offsets, uint64_t cap_records,
+                       uint64_t *d_doc_rec_offsets, uint64_t *n_records) {
+  if (!ac || !n_records || !B.doc_off) return AHA_E_INVALID;
   if (cap_records && !d_rec_offsets) return AHA_E_INVALID;
   if (ac->device < 0) return no_device();
   DeviceGuard g(ac->device);
-  hipStream_t s = (hipStream_t)stream;
   *n_records = 0;
   int32_t rc;
-  if (!offsets_checked && (rc = check_docs_now(ac, sc, d_doc_offsets, n_docs, n_bytes, s))) return rc;
-  if (n_bytes && !d_corpus) return AHA_E_INVALID;
+  if (!B.checked && (rc = check_docs_now(ac, sc, B.doc_off, B.n_docs, B.n_bytes, B.stream))) return rc;
+  if (B.n_bytes && !B.text) return AHA_E_INVALID;
   uint64_t total = 0;
-  if ((rc = device_records_settle(ac, sc, d_corpus, d_doc_offsets, n_docs, n_bytes, delim, &total, stream))) return rc;
+  if ((rc = device_records_settle(ac, sc, B, delim, &total))) return rc;
   *n_records = total;
   if (total > cap_records) {
     tls_err = "output buffer too small";
     return AHA_E_CAPACITY;
   }
-  return device_records_emit(ac, sc, d_doc_offsets, n_docs, n_bytes, d_rec_offsets, d_doc_rec_offsets, stream);
+  return device_records_emit(ac, sc, B, d_rec_offsets, d_doc_rec_offsets);
 }
 
 // The keep, S and T masks over documents, their three block ranks and the one-entry table in grpbuf: what fills the masks
@@ -1966,9 +1983,12 @@ static bool grep_masks(Scratch *sc, uint64_t D, GrepMasks &M) {
 // Grep's tail, from the three masks on (steps 2 to 4 of device_grep below): their ranks, the runs, the scan, the verdict, then
 // -- once both numbers fit -- the kept documents and the copy.  *kept and *total are the required numbers either way; *fits
 // says whether anything was written to the caller.
-static int32_t grep_tail(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t D, uint64_t n_bytes,
-                         const GrepMasks &M, uint64_t *d_kept_docs, uint64_t *d_doc_out_offsets, uint64_t cap_docs, uint8_t *d_out,
-                         uint64_t cap_bytes, uint64_t *kept_out, uint64_t *total_out, bool *fits_out, hipStream_t s) {
+static int32_t grep_tail(aha_ac *ac, Scratch *sc, const Batch &B, const GrepMasks &M, uint64_t *d_kept_docs, uint64_t *d_doc_out_offsets,
+                         uint64_t cap_docs, uint8_t *d_out, uint64_t cap_bytes, uint64_t *kept_out, uint64_t *total_out, bool *fits_out) {
+  hipStream_t s = B.stream;
+  const uint8_t *d_corpus = B.text;
+  const uint64_t *d_doc_offsets = B.doc_off;
+  const uint64_t D = B.n_docs, n_bytes = B.n_bytes;
   auto nomem = [&]() {
     tls_err = "hipMalloc failed for the scratch of a grep call";
     return AHA_E_HIP;
@@ -2020,16 +2040,14 @@ static int32_t grep_tail(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const
 //      back to the host, where the verdict is given.  Nothing has been written to the caller so far.
 //   4. The kept documents' indices and offsets, and replace's copy fed with the runs as deleted hits.
 // A failing call writes none of the caller's buffers.  Steps 2 (from the ranks on) to 4 are grep_tail, which rule grep shares.
-int32_t device_grep(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
-                    const aha_match_params *params, uint32_t flags, uint64_t *d_kept_docs, uint64_t *d_doc_out_offsets,
-                    uint64_t cap_docs, uint8_t *d_out, uint64_t cap_bytes, uint64_t *n_kept, uint64_t *n_out_bytes,
-                    uint64_t *n_hits_out, void *stream, bool offsets_checked) {
-  if (!ac || !n_kept || !d_doc_offsets || (flags & ~AHA_GREP_INVERT)) return AHA_E_INVALID;
+int32_t device_grep(aha_ac *ac, Scratch *sc, const Batch &B, uint32_t flags, uint64_t *d_kept_docs, uint64_t *d_doc_out_offsets,
+                    uint64_t cap_docs, uint8_t *d_out, uint64_t cap_bytes, uint64_t *n_kept, uint64_t *n_out_bytes, uint64_t *n_hits_out) {
+  if (!ac || !n_kept || !B.doc_off || (flags & ~AHA_GREP_INVERT)) return AHA_E_INVALID;
   if ((cap_docs && !d_kept_docs && !d_doc_out_offsets) || (cap_bytes && !d_out)) return AHA_E_INVALID;
   if (ac->device < 0) return no_device();
   DeviceGuard g(ac->device);
-  hipStream_t s = (hipStream_t)stream;
-  const uint64_t D = n_docs;
+  hipStream_t s = B.stream;
+  const uint64_t D = B.n_docs;
   *n_kept = 0;
   if (n_out_bytes) *n_out_bytes = 0;
   if (n_hits_out) *n_hits_out = 0;
@@ -2041,8 +2059,7 @@ int32_t device_grep(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint
   if (!d_dho) return nomem();
   int32_t rc;
   uint64_t n_hits = 0;
-  if ((rc = device_count(ac, sc, d_corpus, d_doc_offsets, D, n_bytes, params, 0, nullptr, d_dho, &n_hits, stream, offsets_checked)))
-    return rc;
+  if ((rc = device_count(ac, sc, B, 0, nullptr, d_dho, &n_hits))) return rc;
   const bool prof = ac->profiling.load();
   const auto t0 = std::chrono::steady_clock::now();
   GrepMasks M;
@@ -2050,9 +2067,7 @@ int32_t device_grep(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint
   grep_launch_flag(d_dho, D, (flags & AHA_GREP_INVERT) != 0, M.keep, M.S, M.T, grep_grid(ac), s);
   uint64_t kept = 0, total = 0;
   bool fits = false;
-  if ((rc = grep_tail(ac, sc, d_corpus, d_doc_offsets, D, n_bytes, M, d_kept_docs, d_doc_out_offsets, cap_docs, d_out, cap_bytes, &kept,
-                      &total, &fits, s)))
-    return rc;
+  if ((rc = grep_tail(ac, sc, B, M, d_kept_docs, d_doc_out_offsets, cap_docs, d_out, cap_bytes, &kept, &total, &fits))) return rc;
   *n_kept = kept;
   if (n_out_bytes) *n_out_bytes = total;
   if (n_hits_out) *n_hits_out = n_hits;
@@ -2080,16 +2095,19 @@ int32_t device_grep(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint
 //   5. The excerpts' starts and offsets, and replace's copy.
 // A failing call writes none of the caller's buffers.  Scratch beyond the count call's: 3 N / 8 bytes of masks, 16 bytes per
 // 2048 text bytes of block ranks, 24 bytes + 2 bits (and their block ranks) per run, 28 bytes per excerpt and the scan's sums.
-int32_t device_excerpts(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
-                        uint64_t n_bytes, const aha_excerpt_params *ep, uint64_t *d_starts, uint64_t *d_out_offsets, uint64_t cap_docs,
-                        uint8_t *d_out, uint64_t cap_bytes, uint64_t *n_kept, uint64_t *n_out_bytes, uint64_t *n_hits_out, void *stream,
-                        bool offsets_checked) {
-  if (!ac || !n_kept || !d_doc_offsets || !ep) return AHA_E_INVALID;
+int32_t device_excerpts(aha_ac *ac, Scratch *sc, const Batch &B0, const aha_excerpt_params *ep, uint64_t *d_starts,
+                        uint64_t *d_out_offsets, uint64_t cap_docs, uint8_t *d_out, uint64_t cap_bytes, uint64_t *n_kept,
+                        uint64_t *n_out_bytes, uint64_t *n_hits_out) {
+  if (!ac || !n_kept || !B0.doc_off || !ep) return AHA_E_INVALID;
   if ((cap_docs && !d_starts && !d_out_offsets) || (cap_bytes && !d_out)) return AHA_E_INVALID;
   if (ac->device < 0) return no_device();
   DeviceGuard g(ac->device);
-  hipStream_t s = (hipStream_t)stream;
-  const uint64_t D = n_docs;
+  Batch B = B0;
+  B.params = &ep->match;
+  hipStream_t s = B.stream;
+  const uint8_t *d_corpus = B.text;
+  const uint64_t *d_doc_offsets = B.doc_off;
+  const uint64_t D = B.n_docs, n_bytes = B.n_bytes;
   *n_kept = 0;
   if (n_out_bytes) *n_out_bytes = 0;
   if (n_hits_out) *n_hits_out = 0;
@@ -2106,9 +2124,7 @@ int32_t device_excerpts(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const 
   uint64_t *blk_s = blks, *blk_t = blks + (n_blk + 1);
   int32_t rc;
   uint64_t n_hits = 0;
-  if ((rc = device_count(ac, sc, d_corpus, d_doc_offsets, D, n_bytes, &ep->match, 0, nullptr, nullptr, &n_hits, stream, offsets_checked,
-                         n_bytes ? Mk : nullptr)))
-    return rc;
+  if ((rc = device_count(ac, sc, B, 0, nullptr, nullptr, &n_hits, CallOpt::kNone, n_bytes ? Mk : nullptr))) return rc;
   const bool prof = ac->profiling.load();
   const auto t0 = std::chrono::steady_clock::now();
   uint64_t n_runs = 0, n_exc = 0, total = 0;
@@ -2194,18 +2210,16 @@ static void *cls_reserve(Scratch *sc, ClassSlot slot, size_t bytes) { return res
 //   3. The ranges of doc_ranges.hpp (one, as a rule), each matched into the call's scratch (RangeCall, above), then kcc_add over
 //      the hit list (scan_classcount.hip).  A single document beyond the bound is never matched: a count call over it alone
 //      gives its key counts, which kcc_fold_keys adds into its row through the table.
-int32_t device_class_counts(aha_ac *ac, Scratch *sc, const aha_classes *table, const uint8_t *d_corpus, const uint64_t *d_doc_offsets,
-                            uint64_t n_docs, uint64_t n_bytes, const aha_match_params *params, uint32_t *d_out, uint64_t *n_hits_out,
-                            void *stream, bool offsets_checked) {
-  if (!ac || !table || !d_doc_offsets) return AHA_E_INVALID;
+int32_t device_class_counts(aha_ac *ac, Scratch *sc, const aha_classes *table, const Batch &B, uint32_t *d_out, uint64_t *n_hits_out) {
+  if (!ac || !table || !B.doc_off) return AHA_E_INVALID;
   if (ac->device < 0 || !table->d_off) return no_device();
-  if (n_docs && !d_out) return AHA_E_INVALID;
+  if (B.n_docs && !d_out) return AHA_E_INVALID;
   DeviceGuard g(ac->device);
-  hipStream_t s = (hipStream_t)stream;
-  const uint64_t D = n_docs, C = table->n_classes;
+  hipStream_t s = B.stream;
+  const uint64_t D = B.n_docs, C = table->n_classes;
   const uint32_t K = ac->aut.n_keys;
   if (n_hits_out) *n_hits_out = 0;
-  RangeCall call{ac, sc, d_corpus, d_doc_offsets, D, n_bytes, params, stream, sc->clsbuf[kClsRel], sc->clsbuf[kClsText],
+  RangeCall call{ac, sc, B, sc->clsbuf[kClsRel], sc->clsbuf[kClsText],
                  sc->clsbuf[kClsHits], kGrowEighth, "class counts", "hipMalloc failed for the scratch of a class-counts call",
                  RangeBook{ac, true}};
   auto nomem = [&]() { return call.nomem(); };
@@ -2213,8 +2227,7 @@ int32_t device_class_counts(aha_ac *ac, Scratch *sc, const aha_classes *table, c
   uint64_t *d_dho = (uint64_t *)cls_reserve(sc, kClsHitOff, (D + 1) * 8);
   if (!d_dho) return nomem();
   uint64_t n_hits = 0;
-  if ((rc = device_count(ac, sc, d_corpus, d_doc_offsets, D, n_bytes, params, 0, nullptr, d_dho, &n_hits, stream, offsets_checked)))
-    return rc;
+  if ((rc = device_count(ac, sc, B, 0, nullptr, d_dho, &n_hits))) return rc;
   call.book.begin();
   // the ranges: the whole batch where all hits are known to fit the bound (the hit offsets stay on the device then)
   std::vector<DocRange> ranges;
@@ -2227,7 +2240,7 @@ int32_t device_class_counts(aha_ac *ac, Scratch *sc, const aha_classes *table, c
       hd.resize(D + 1);
       call.off.resize(D + 1);
       HIPCHK(ac, hipMemcpyAsync(hd.data(), d_dho, (D + 1) * 8, hipMemcpyDeviceToHost, s));
-      HIPCHK(ac, hipMemcpyAsync(call.off.data(), d_doc_offsets, (D + 1) * 8, hipMemcpyDeviceToHost, s));
+      HIPCHK(ac, hipMemcpyAsync(call.off.data(), B.doc_off, (D + 1) * 8, hipMemcpyDeviceToHost, s));
       HIPCHK(ac, hipStreamSynchronize(s));
       uint64_t bad = 0;
       if (class_counts_overflow(hd.data(), D, &bad)) {
@@ -2243,15 +2256,15 @@ int32_t device_class_counts(aha_ac *ac, Scratch *sc, const aha_classes *table, c
   const uint32_t blocks = class_grid(ac);
   for (size_t r = 0; r < ranges.size(); r++) {
     const uint64_t d0 = ranges[r].d0, d1 = ranges[r].d1, rh = hd.empty() ? n_hits : hd[d1] - hd[d0];
-    RangeBatch B;
-    if ((rc = call.batch(d0, d1, B))) return rc;
-    const uint64_t nd = B.nd;
+    Batch R;
+    if ((rc = call.batch(d0, d1, R))) return rc;
+    const uint64_t nd = R.n_docs;
     if (ranges[r].solo) {
       const auto t_m0 = std::chrono::steady_clock::now();
       uint64_t got = 0;
       uint64_t *row = (uint64_t *)cls_reserve(sc, kClsSoloRow, std::max<uint64_t>(K, 1) * 8);
       if (!row) return nomem();
-      if ((rc = device_count(ac, sc, B.text, B.d_rel, nd, B.nb, params, 0, row, nullptr, &got, stream, true))) return rc;
+      if ((rc = device_count(ac, sc, R, 0, row, nullptr, &got))) return rc;
       call.book.matched(t_m0);
       if (got != rh) {
         tls_err = "class counts: the two counts of a document disagree";
@@ -2260,7 +2273,7 @@ int32_t device_class_counts(aha_ac *ac, Scratch *sc, const aha_classes *table, c
       classcount_launch_fold_keys(row, K, table->d_off, table->d_ids, d_out + d0 * C, blocks, s);
     } else {
       aha_hit *d_hits = nullptr;
-      if ((rc = call.match(B, rh, &d_hits))) return rc;
+      if ((rc = call.match(R, rh, &d_hits))) return rc;
       classcount_launch_add(d_hits, rh, d_dho + d0, nd, table->d_off, table->d_ids, K, (uint32_t)C, d_out + d0 * C, blocks, s);
     }
     HIPCHK(ac, hipGetLastError());
@@ -2275,23 +2288,24 @@ int32_t device_class_counts(aha_ac *ac, Scratch *sc, const aha_classes *table, c
 // ---- rule grep (aha_ac_grep_batch* with AHA_GREP_RULE) ------------------------------------------------------------------
 // One device-resident batch filtered by a rule over its class counts (DESIGN.md 4.16 "Rule grep").  gp was checked by capi.cpp.
 //   1. device_class_counts as it is: the D x C table into d_rows where the caller gave it and the call cannot fail any more
-//      (rows_early: the capacities cover every outcome, or d_rows is the host entry's staging buffer), else into
+//      (RuleRows::kEarly: the capacities cover every outcome, or d_rows is the host entry's staging buffer), else into
 //      grpbuf[kGrpRows], which AHA_RULE_TABLE_BYTES bounds.
 //   2. kgq_keep: the keep mask from the rule; kgq_edges: S and T from keep (scan_greprule.hip).
 //   3. grep_tail.  Once it is known to fit, a table in scratch is copied into d_rows.
 // A failing call writes none of the caller's buffers, d_rows included.
-int32_t device_grep_rule(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
-                         uint64_t n_bytes, const aha_grep_params *gp, uint32_t *d_rows, uint32_t flags, uint64_t *d_kept_docs,
-                         uint64_t *d_doc_out_offsets, uint64_t cap_docs, uint8_t *d_out, uint64_t cap_bytes, uint64_t *n_kept,
-                         uint64_t *n_out_bytes, uint64_t *n_hits_out, void *stream, bool offsets_checked, bool rows_early) {
-  if (!ac || !gp || !gp->classes || !gp->terms || !n_kept || !d_doc_offsets) return AHA_E_INVALID;
+int32_t device_grep_rule(aha_ac *ac, Scratch *sc, const Batch &B0, const aha_grep_params *gp, uint32_t *d_rows, RuleRows rows,
+                         uint32_t flags, uint64_t *d_kept_docs, uint64_t *d_doc_out_offsets, uint64_t cap_docs, uint8_t *d_out,
+                         uint64_t cap_bytes, uint64_t *n_kept, uint64_t *n_out_bytes, uint64_t *n_hits_out) {
+  if (!ac || !gp || !gp->classes || !gp->terms || !n_kept || !B0.doc_off) return AHA_E_INVALID;
   if (gp->n_terms == 0 || gp->n_terms > kRuleMaxTerms || (flags & ~(AHA_GREP_INVERT | AHA_GREP_RULE))) return AHA_E_INVALID;
   if ((cap_docs && !d_kept_docs && !d_doc_out_offsets) || (cap_bytes && !d_out)) return AHA_E_INVALID;
   if (ac->device < 0) return no_device();
   DeviceGuard g(ac->device);
-  hipStream_t s = (hipStream_t)stream;
+  Batch B = B0;
+  B.params = &gp->match;
+  hipStream_t s = B.stream;
   const aha_classes *table = gp->classes;
-  const uint64_t D = n_docs, C = table->n_classes;
+  const uint64_t D = B.n_docs, C = table->n_classes;
   *n_kept = 0;
   if (n_out_bytes) *n_out_bytes = 0;
   if (n_hits_out) *n_hits_out = 0;
@@ -2299,7 +2313,7 @@ int32_t device_grep_rule(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const
     tls_err = "hipMalloc failed for the scratch of a grep call";
     return AHA_E_HIP;
   };
-  const bool direct = d_rows && rows_early;
+  const bool direct = d_rows && rows == RuleRows::kEarly;
   uint32_t *tab = d_rows;
   if (!direct) {
     if (D * C * 4 > ac->rule_table_bytes) {
@@ -2313,20 +2327,17 @@ int32_t device_grep_rule(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const
   }
   int32_t rc;
   uint64_t n_hits = 0;
-  if ((rc = device_class_counts(ac, sc, table, d_corpus, d_doc_offsets, D, n_bytes, &gp->match, tab, &n_hits, stream, offsets_checked)))
-    return rc;
+  if ((rc = device_class_counts(ac, sc, table, B, tab, &n_hits))) return rc;
   const bool prof = ac->profiling.load();
   const auto t0 = std::chrono::steady_clock::now();
   GrepMasks M;
   if (!grep_masks(sc, D, M)) return nomem();
   const uint32_t blocks = grep_grid(ac);
-  greprule_launch_keep(tab, (uint32_t)C, d_doc_offsets, D, gp->terms, gp->n_terms, (flags & AHA_GREP_INVERT) != 0, M.keep, blocks, s);
+  greprule_launch_keep(tab, (uint32_t)C, B.doc_off, D, gp->terms, gp->n_terms, (flags & AHA_GREP_INVERT) != 0, M.keep, blocks, s);
   greprule_launch_edges(M.keep, D, M.S, M.T, blocks, s);
   uint64_t kept = 0, total = 0;
   bool fits = false;
-  if ((rc = grep_tail(ac, sc, d_corpus, d_doc_offsets, D, n_bytes, M, d_kept_docs, d_doc_out_offsets, cap_docs, d_out, cap_bytes, &kept,
-                      &total, &fits, s)))
-    return rc;
+  if ((rc = grep_tail(ac, sc, B, M, d_kept_docs, d_doc_out_offsets, cap_docs, d_out, cap_bytes, &kept, &total, &fits))) return rc;
   if (fits && d_rows && !direct && D) {
     HIPCHK(ac, hipMemcpyAsync(d_rows, tab, D * C * 4, hipMemcpyDeviceToDevice, s));
     HIPCHK(ac, hipStreamSynchronize(s));

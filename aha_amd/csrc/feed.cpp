@@ -251,14 +251,14 @@ int32_t feed_windows(aha_feed *f, Scratch *sc, FeedArgs &F, hipStream_t s, bool 
   aha_match_params p{};
   p.struct_size = sizeof(p);
   p.char_offsets = wide ? 0 : F.chars;
-  bool packed = false;
+  const Batch win = checked_batch(F.win, F.woff, 3 * D, n_win, &p, s);  // (offsets the feed's own kernels wrote)
   *n_w = 0;
   if (hits) {
     // the window batch: at most 4 W bytes per piece (6 W: a cover call); its hit scratch grows to what it needed once
     for (int attempt = 0;; attempt++) {
       const uint64_t cap_w = f->buf[kWhits].bytes / sizeof(aha_hit);
-      int32_t rc = device_match(ac, sc, F.win, F.woff, 3 * D, n_win, &p, cap_w ? (aha_hit *)f->buf[kWhits].p : nullptr, cap_w,
-                                wdho, n_w, s, true, nullptr, &packed, true, false, f->fold != 0);
+      const HitOut hits_w{cap_w ? (aha_hit *)f->buf[kWhits].p : nullptr, cap_w, wdho};
+      int32_t rc = device_match(ac, sc, win, hits_w, n_w, CallOpt::kQuiet | as_is_if(f->fold));
       if (rc == AHA_E_CAPACITY && attempt == 0) {
         if (!reserve(f, kWhits, std::max<uint64_t>(*n_w, 1024) * sizeof(aha_hit))) return no_memory("window hits");
         continue;
@@ -268,7 +268,7 @@ int32_t feed_windows(aha_feed *f, Scratch *sc, FeedArgs &F, hipStream_t s, bool 
     }
   } else {
     // (a count call never writes the handle's back-off state, so it needs no quiet form)
-    int32_t rc = device_count(ac, sc, F.win, F.woff, 3 * D, n_win, &p, 0, nullptr, wdho, n_w, s, true, nullptr, f->fold != 0);
+    int32_t rc = device_count(ac, sc, win, 0, nullptr, wdho, n_w, as_is_if(f->fold));
     if (rc) return rc;
   }
   F.whits = (const int32_t *)f->buf[kWhits].p;
@@ -287,6 +287,10 @@ int32_t feed_windows(aha_feed *f, Scratch *sc, FeedArgs &F, hipStream_t s, bool 
 // the text of a call's main pass: the caller's pieces, or on a folded feed their folded copy (feed_windows made it), which the
 // engines then take as it is -- one staged pass per call, not two
 const uint8_t *main_text(const aha_feed *f, const FeedArgs &F) { return f->fold ? F.ftext : F.text; }
+// ... as a batch: the pieces are its documents, their offsets were checked when they were staged
+static Batch main_batch(const aha_feed *f, const FeedArgs &F, const aha_match_params *p, hipStream_t s) {
+  return checked_batch(main_text(f, F), F.off, F.D, F.n_bytes, p, s);
+}
 
 // the part of a match call before anything is written for the caller: the windows, then the main pass.  *total = the call's
 // hits; AHA_E_CAPACITY when they are more than cap.
@@ -298,14 +302,12 @@ int32_t feed_prepare(aha_feed *f, Scratch *sc, FeedArgs &F, uint64_t cap, hipStr
   aha_match_params p{};
   p.struct_size = sizeof(p);
   p.char_offsets = F.chars;
-  bool packed = false;
   // the main pass: what the caller's buffer can take plus the hits it drops
   const uint64_t cap_m = cap + nz;
   aha_hit *mh = cap_m ? (aha_hit *)reserve(f, kMhits, cap_m * sizeof(aha_hit)) : nullptr;
   if (cap_m && !mh) return no_memory("hits");
   uint64_t n_m = 0;
-  rc = device_match(ac, sc, main_text(f, F), F.off, F.D, F.n_bytes, &p, mh, cap_m, (uint64_t *)F.mdho, &n_m, s, true, nullptr, &packed,
-                    false, false, f->fold != 0);
+  rc = device_match(ac, sc, main_batch(f, F, &p, s), HitOut{mh, cap_m, (uint64_t *)F.mdho}, &n_m, as_is_if(f->fold));
   if (rc && rc != AHA_E_CAPACITY) return rc;
   F.mhits = (const int32_t *)mh;
   *total = (nx - ny) + (n_m - nz);
@@ -336,8 +338,7 @@ int32_t feed_count(aha_feed *f, Scratch *sc, FeedArgs &F, hipStream_t s, uint64_
   aha_match_params p{};
   p.struct_size = sizeof(p);
   uint64_t n_m = 0;
-  rc = device_count(ac, sc, main_text(f, F), F.off, F.D, F.n_bytes, &p, 0, (uint64_t *)F.kc, (uint64_t *)F.mdho, &n_m, s, true, nullptr,
-                    f->fold != 0);
+  rc = device_count(ac, sc, main_batch(f, F, &p, s), 0, (uint64_t *)F.kc, (uint64_t *)F.mdho, &n_m, as_is_if(f->fold));
   if (rc) return rc;
   *total = (nx - ny) + (n_m - nz);
   F.total = *total;
@@ -366,8 +367,7 @@ int32_t feed_cover(aha_feed *f, Scratch *sc, FeedArgs &F, hipStream_t s, uint32_
   aha_match_params p{};
   p.struct_size = sizeof(p);
   uint64_t n_m = 0;
-  rc = device_count(ac, sc, main_text(f, F), F.off, F.D, F.n_bytes, &p, 0, nullptr, (uint64_t *)F.mdho, &n_m, s, true, F.mask,
-                    f->fold != 0);
+  rc = device_count(ac, sc, main_batch(f, F, &p, s), 0, nullptr, (uint64_t *)F.mdho, &n_m, as_is_if(f->fold), F.mask);
   if (rc) return rc;
   *total = (nx - ny) + (n_m - nz);
   F.total = *total;
@@ -454,8 +454,8 @@ int32_t feed_select_settle(aha_feed *f, Scratch *sc, FeedArgs &F, uint32_t flags
   if (!f->buf[kMhits].bytes && !reserve(f, kMhits, 1024 * sizeof(aha_hit))) return no_memory("hits");
   for (int attempt = 0;; attempt++) {
     const uint64_t cap_m = f->buf[kMhits].bytes / sizeof(aha_hit);
-    rc = device_match(ac, sc, F.text, F.off, D, F.n_bytes, &p, cap_m ? (aha_hit *)f->buf[kMhits].p : nullptr, cap_m,
-                      (uint64_t *)F.mdho, &n_m, s, true, nullptr, nullptr, false, true);
+    const HitOut hits_m{cap_m ? (aha_hit *)f->buf[kMhits].p : nullptr, cap_m, (uint64_t *)F.mdho};
+    rc = device_match(ac, sc, checked_batch(F.text, F.off, D, F.n_bytes, &p, s), hits_m, &n_m, CallOpt::kNeutral);
     if (rc == AHA_E_CAPACITY && attempt == 0) {
       if (!reserve(f, kMhits, std::max<uint64_t>(n_m, 1024) * sizeof(aha_hit))) return no_memory("hits");
       continue;
@@ -759,11 +759,12 @@ int32_t feed_grep(aha_feed *f, Scratch *sc, FeedArgs &F, uint8_t delim, uint32_t
   // the fragments: a records call over the pieces, its offsets sized from its total
   int32_t rc;
   uint64_t R = 0;
-  if ((rc = device_records_settle(ac, sc, F.text, F.off, D, F.n_bytes, delim, &R, s))) return rc;
+  const Batch pieces = checked_batch(F.text, F.off, D, F.n_bytes, nullptr, s);
+  if ((rc = device_records_settle(ac, sc, pieces, delim, &R))) return rc;
   uint64_t *frag = (uint64_t *)fg_reserve(kFgFragOff, (R + 1) * 8);
   uint64_t *pro = (uint64_t *)fg_reserve(kFgPieceFrag, (D + 1) * 8);
   if (!frag || !pro) return nomem();
-  if ((rc = device_records_emit(ac, sc, F.off, D, F.n_bytes, frag, pro, s))) return rc;
+  if ((rc = device_records_emit(ac, sc, pieces, frag, pro))) return rc;
   F.woff = (uint64_t *)fg_reserve(kFgWinOff, (3 * D + 1) * 8);
   uint64_t *wdho = (uint64_t *)fg_reserve(kFgWinHitOff, (3 * D + 1) * 8);
   uint64_t *fdho = (uint64_t *)fg_reserve(kFgFragHitOff, (R + 1) * 8);
@@ -805,8 +806,8 @@ int32_t feed_grep(aha_feed *f, Scratch *sc, FeedArgs &F, uint8_t delim, uint32_t
   aha_match_params p{};
   p.struct_size = sizeof(p);
   uint64_t n_w = 0, n_m = 0;
-  if ((rc = device_count(ac, sc, F.win, F.woff, 3 * D, n_win, &p, 0, nullptr, wdho, &n_w, s, true))) return rc;
-  if ((rc = device_count(ac, sc, F.text, frag, R, F.n_bytes, &p, 0, nullptr, fdho, &n_m, s, true))) return rc;
+  if ((rc = device_count(ac, sc, checked_batch(F.win, F.woff, 3 * D, n_win, &p, s), 0, nullptr, wdho, &n_w))) return rc;
+  if ((rc = device_count(ac, sc, checked_batch(F.text, frag, R, F.n_bytes, &p, s), 0, nullptr, fdho, &n_m))) return rc;
   // grep's steps over the fragments (engine.cpp device_grep)
   uint64_t *blk_k = blks, *blk_s = blks + (n_blk + 1), *blk_t = blks + 2 * (n_blk + 1);
   feedgrep_launch_flag(F, G, blocks, s);
@@ -938,8 +939,8 @@ int32_t feed_sep_true(aha_feed *f, Scratch *sc, FeedArgs &F, hipStream_t s, Feed
   if (!f->buf[kMhits].bytes && !reserve(f, kMhits, 1024 * sizeof(aha_hit))) return no_memory("hits");
   for (int attempt = 0;; attempt++) {
     const uint64_t cap_m = f->buf[kMhits].bytes / sizeof(aha_hit);
-    rc = device_match(ac, sc, F.text, F.off, D, F.n_bytes, &p, cap_m ? (aha_hit *)f->buf[kMhits].p : nullptr, cap_m,
-                      (uint64_t *)F.mdho, &n_m, s, true, nullptr, nullptr, false, true);
+    const HitOut hits_m{cap_m ? (aha_hit *)f->buf[kMhits].p : nullptr, cap_m, (uint64_t *)F.mdho};
+    rc = device_match(ac, sc, checked_batch(F.text, F.off, D, F.n_bytes, &p, s), hits_m, &n_m, CallOpt::kNeutral);
     if (rc == AHA_E_CAPACITY && attempt == 0) {
       if (!reserve(f, kMhits, std::max<uint64_t>(n_m, 1024) * sizeof(aha_hit))) return no_memory("hits");
       continue;

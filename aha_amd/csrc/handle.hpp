@@ -15,6 +15,7 @@
 #include <new>
 #include <thread>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "automaton.hpp"
 #include "cedar_replay.hpp"
@@ -219,13 +220,20 @@ enum ClassSlot {
   kClsSoloRow,  // one document's key counts (a document beyond the hit buffer's bound)
   kClsCount
 };
+// tpbuf: the two-pass engine and match_longest (engine.cpp bind_two_pass; kernels.hip, scan_feedlongest.hip)
+enum TwoPassSlot {
+  kTpCounts,    // hits per counter: a chunk, or a document of match_longest's per-document modes
+  kTpLeads,     // char offsets: continuation bytes per chunk
+  kTpBlkHits,   // block sums of the scan over the hits
+  kTpBlkLeads,  // ... and over the leads
+  kTpDocG,      // char offsets: per document, the lead count before it
+  kTpTotals,    // 2 double words: the call's hits; match_longest's NUL look and its chunks' give-up
+  kTpCount
+};
 // Device scratch of ONE match call (grow-only, reused by later calls that lease the same set).
 struct Scratch {
   std::mutex mu;  // held by the call that leased the set
-  uint32_t *d_counts = nullptr, *d_leads = nullptr;
-  uint64_t *d_blk_hits = nullptr, *d_blk_leads = nullptr, *d_docg = nullptr, *d_totals = nullptr;
-  uint64_t cap_chunks = 0, cap_blocks = 0, cap_docs = 0;
-  uint64_t *h_totals = nullptr;  // pinned
+  uint64_t *h_totals = nullptr;  // pinned: tpbuf[kTpTotals] read back
   hipEvent_t ev[6] = {};
   bool ev_ready = false;
   Buf v2buf[kV2Count];
@@ -243,6 +251,7 @@ struct Scratch {
   Buf fgrpbuf[kFgCount];
   Buf clsbuf[kClsCount];
   Buf flngbuf[kFlCount];
+  Buf tpbuf[kTpCount];
   // every family above, for free_scratch and scratch_bytes (S: Scratch or const Scratch): a new family is one more line here
   template <class S, class Fn>
   static void each_buf(S &sc, Fn fn) {
@@ -261,6 +270,7 @@ struct Scratch {
     for (auto &b : sc.fgrpbuf) fn(b);
     for (auto &b : sc.clsbuf) fn(b);
     for (auto &b : sc.flngbuf) fn(b);
+    for (auto &b : sc.tpbuf) fn(b);
   }
   bool dc_rows_clear = false;  // every word of dcbuf[kDcRows] is zero (kdc_compact clears what kdc_add wrote; a call that failed may not have)
   hipStream_t hs[3] = {};  // host-buffer entry: private non-blocking streams for upload, match, download
@@ -457,7 +467,7 @@ uint64_t scratch_bytes(const Scratch *sc);
 // THE allocator of the grow-only buffers: b holds at least `bytes` afterwards, or nothing (the HIP error is returned, the
 // runtime's sticky one cleared).  What a new buffer gets beyond `bytes` is its family's rule:
 enum Grow {
-  kGrowEighth,   // bytes + bytes / 8 + 256 (v2buf, covbuf, selbuf, repbuf, fselbuf, ftokbuf, frepbuf, fsepbuf, grpbuf, fgrpbuf, clsbuf, flngbuf)
+  kGrowEighth,   // bytes + bytes / 8 + 256 (v2buf, covbuf, selbuf, repbuf, fselbuf, ftokbuf, frepbuf, fsepbuf, grpbuf, fgrpbuf, clsbuf, flngbuf, tpbuf)
   kGrowQuarter,  // bytes + bytes / 4 + 4096 (cntbuf, hostbuf)
   kGrowOrExact   // an eighth, else exactly `bytes`; `bytes` is what it records (dcbuf: what is known to be there)
 };
@@ -505,7 +515,6 @@ int32_t upload_late(aha_ac *ac, const std::vector<T> &v, const T **out) {
 }
 
 int32_t upload_image(aha_ac *ac, const Image &img);
-int32_t ensure_scratch(aha_ac *ac, Scratch *sc, uint64_t n_chunks, uint64_t n_blocks, uint64_t n_docs);
 int32_t fill_params(aha_ac *ac, const aha_match_params *p, MatchArgs &M, int *longest);
 
 struct DeviceGuard {
@@ -536,36 +545,66 @@ struct PackOut {
   uint64_t cap_words;
   uint64_t *d_n_words;
 };
-// one device-resident batch through whichever engine takes it (retries, hand-backs, the two-pass engine as the last resort).
-// neutral: every engine, but the back-off state is only read (the match inside a document-count call).
-// quiet: neither the prefix-filter nor the pair engine, so the handle's back-off state is neither read nor written (a feed's
-// window batch, feed.cpp: an internal batch must not change which engine the caller's next call takes)
-// as_is: the text is already as the engines take it -- folded by a folded feed (feed.cpp, scan_feedfold.hip) -- so a folded
-// handle's staged pass is left out; only an unaligned view is still copied.  No other caller passes it.
-int32_t device_match(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
-                     uint64_t n_bytes, const aha_match_params *params, aha_hit *d_out, uint64_t cap, uint64_t *d_doc_hit_offsets,
-                     uint64_t *n_hits, void *stream, bool offsets_checked, const PackOut *pk, bool *packed, bool quiet = false,
-                     bool neutral = false, bool as_is = false);
-// one device-resident batch counted (aha_ac_count_batch_device): the match's engine, the count passes instead of the expansion
-int32_t device_count(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
-                     uint64_t n_bytes, const aha_match_params *params, uint32_t flags, uint64_t *d_key_counts,
-                     uint64_t *d_doc_hit_offsets, uint64_t *n_hits, void *stream, bool offsets_checked, uint32_t *cover_mask = nullptr,
-                     bool as_is = false);
+// A device-resident batch: what every device_* call below works on.
+struct Batch {
+  const uint8_t *text;             // the documents' bytes, one behind the other (null only where n_bytes == 0)
+  const uint64_t *doc_off;         // the n_docs + 1 offsets into text, device memory: [0] = 0, ascending, [n_docs] = n_bytes
+  uint64_t n_docs, n_bytes;
+  const aha_match_params *params;  // null: the defaults (records calls: not looked at)
+  hipStream_t stream;              // everything the call does is ordered on it (the ABI's void *, cast once there)
+  bool checked;                    // whoever made the batch has validated doc_off; false: the call validates it on the device
+};
+// ... made by name, so that no call site spells `checked` as a bare true or false
+inline Batch checked_batch(const uint8_t *text, const uint64_t *doc_off, uint64_t n_docs, uint64_t n_bytes, const aha_match_params *params,
+                           hipStream_t stream) {
+  return Batch{text, doc_off, n_docs, n_bytes, params, stream, true};
+}
+inline Batch unchecked_batch(const uint8_t *text, const uint64_t *doc_off, uint64_t n_docs, uint64_t n_bytes,
+                             const aha_match_params *params, hipStream_t stream) {
+  return Batch{text, doc_off, n_docs, n_bytes, params, stream, false};
+}
+// How device_match and device_count treat the handle's back-off state and the text.  Combined with |; nothing converts to it.
+enum class CallOpt : uint32_t {
+  kNone = 0,
+  // every engine, but the back-off state is only read (the match inside a document-count call)
+  kNeutral = 1,
+  // neither the prefix-filter nor the pair engine, so the handle's back-off state is neither read nor written (a feed's window
+  // batch, feed.cpp: an internal batch must not change which engine the caller's next call takes)
+  kQuiet = 2,
+  // the text is already as the engines take it -- folded by a folded feed (feed.cpp, scan_feedfold.hip) -- so a folded handle's
+  // staged pass is left out; only an unaligned view is still copied.  No other caller passes it.
+  kAsIs = 4
+};
+constexpr CallOpt operator|(CallOpt a, CallOpt b) { return (CallOpt)((uint32_t)a | (uint32_t)b); }
+constexpr bool has(CallOpt o, CallOpt f) { return ((uint32_t)o & (uint32_t)f) != 0; }
+constexpr CallOpt as_is_if(int fold) { return fold ? CallOpt::kAsIs : CallOpt::kNone; }  // (a feed's fold mode)
+static_assert(!std::is_constructible<CallOpt, bool>::value && !std::is_convertible<bool, CallOpt>::value &&
+                  !std::is_convertible<int, CallOpt>::value,
+              "a bool in an option's place must not compile");
+// where a match leaves its hits: d_out[0 .. cap), and per document its first hit's index where doc_hit_off is given
+struct HitOut {
+  aha_hit *d_out;
+  uint64_t cap;
+  uint64_t *d_doc_hit_off;
+};
+// one device-resident batch through whichever engine takes it (retries, hand-backs, the two-pass engine as the last resort)
+int32_t device_match(aha_ac *ac, Scratch *sc, const Batch &B, const HitOut &out, uint64_t *n_hits, CallOpt opt = CallOpt::kNone);
+// one device-resident batch counted (aha_ac_count_batch_device): the match's engine, the count passes instead of the expansion.
+// Of the options only kAsIs applies: a count call never writes the back-off state.
+int32_t device_count(aha_ac *ac, Scratch *sc, const Batch &B, uint32_t flags, uint64_t *d_key_counts, uint64_t *d_doc_hit_offsets,
+                     uint64_t *n_hits, CallOpt opt = CallOpt::kNone, uint32_t *cover_mask = nullptr);
 // one device-resident batch as {key, count} pairs per document (aha_ac_doc_counts_batch_device): a count call for the hits per
 // document, the match into scratch, the per-document reduction (scan_doccount.hip)
-int32_t device_doc_counts(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
-                          uint64_t n_bytes, const aha_match_params *params, aha_key_count *d_out, uint64_t cap,
-                          uint64_t *d_doc_pair_offsets, uint64_t *n_pairs, uint64_t *n_hits, void *stream, bool offsets_checked);
+int32_t device_doc_counts(aha_ac *ac, Scratch *sc, const Batch &B, aha_key_count *d_out, uint64_t cap, uint64_t *d_doc_pair_offsets,
+                          uint64_t *n_pairs, uint64_t *n_hits);
 // one device-resident batch covered (aha_ac_cover_batch_device): the count call's pipeline without key counts, one span per
 // event into the mask (scan_cover.hip), then the redacted copy and the documents' covered bytes where asked for
-int32_t device_cover(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
-                     uint64_t n_bytes, const aha_match_params *params, uint32_t flags, uint32_t *d_mask, uint8_t *d_redacted,
-                     uint8_t fill, uint64_t *d_doc_covered, uint64_t *n_covered, uint64_t *n_hits, void *stream, bool offsets_checked);
+int32_t device_cover(aha_ac *ac, Scratch *sc, const Batch &B, uint32_t flags, uint32_t *d_mask, uint8_t *d_redacted, uint8_t fill,
+                     uint64_t *d_doc_covered, uint64_t *n_covered, uint64_t *n_hits);
 // one device-resident batch selected (aha_ac_select_batch_device): a count call for the hits per document, the match into
 // scratch, the leftmost-longest non-overlapping hits of every document from it (scan_select.hip)
-int32_t device_select(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
-                      uint64_t n_bytes, const aha_match_params *params, aha_hit *d_out, uint64_t cap, uint64_t *d_doc_sel_offsets,
-                      uint64_t *n_selected, uint64_t *n_hits, void *stream, bool offsets_checked, uint32_t flags = 0);
+int32_t device_select(aha_ac *ac, Scratch *sc, const Batch &B, const HitOut &out, uint64_t *n_selected, uint64_t *n_hits,
+                      uint32_t flags = 0);
 // What device_select_to does with the selection.  Without a sink (device_select, the public entries): the caller's buffer where
 // the total fits, the documents' offsets to the caller's array.  With one (device_replace): `place(kept, upto, &at)` is asked,
 // range by range, for a buffer that holds `upto` hits and still has the first `kept` ones (it returns the call's error, with
@@ -580,57 +619,50 @@ struct SelectSink {
   std::function<int32_t(uint64_t kept, uint64_t upto, aha_hit **at)> place;
   aha_timing *timing = nullptr;
 };
-int32_t device_select_to(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
-                         uint64_t n_bytes, const aha_match_params *params, aha_hit *d_out, uint64_t cap, uint64_t *d_doc_sel_offsets,
-                         uint64_t *n_selected, uint64_t *n_hits, void *stream, bool offsets_checked, const SelectSink *sink,
-                         uint32_t flags = 0);
+int32_t device_select_to(aha_ac *ac, Scratch *sc, const Batch &B, const HitOut &out, uint64_t *n_selected, uint64_t *n_hits,
+                         const SelectSink *sink, uint32_t flags = 0);
 // one device-resident batch substituted (aha_ac_replace_batch_device): device_select_to with the selection into scratch, then the
 // scan over the changes of length and the output-driven copy (scan_replace.hip)
-int32_t device_replace(aha_ac *ac, Scratch *sc, const aha_repl *table, const uint8_t *d_corpus, const uint64_t *d_doc_offsets,
-                       uint64_t n_docs, uint64_t n_bytes, const aha_match_params *params, uint8_t *d_out, uint64_t cap_bytes,
-                       uint64_t *d_doc_out_offsets, uint64_t *n_out_bytes, uint64_t *n_selected, uint64_t *n_hits, void *stream,
-                       bool offsets_checked);
+int32_t device_replace(aha_ac *ac, Scratch *sc, const aha_repl *table, const Batch &B, uint8_t *d_out, uint64_t cap_bytes,
+                       uint64_t *d_doc_out_offsets, uint64_t *n_out_bytes, uint64_t *n_selected, uint64_t *n_hits);
 // one device-resident batch split into records (aha_ac_records_batch_device): the record-end mask in one pass over the text,
 // its rank, the offsets once the count is known to fit (scan_grep.hip)
-int32_t device_records(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
-                       uint64_t n_bytes, uint8_t delim, uint64_t *d_rec_offsets, uint64_t cap_records, uint64_t *d_doc_rec_offsets,
-                       uint64_t *n_records, void *stream, bool offsets_checked);
+int32_t device_records(aha_ac *ac, Scratch *sc, const Batch &B, uint8_t delim, uint64_t *d_rec_offsets, uint64_t cap_records,
+                       uint64_t *d_doc_rec_offsets, uint64_t *n_records);
 // its two halves, split at the total (a feed grep call sizes the fragments' offsets from it): the mask and its rank into
-// grpbuf, *n_records read back; then, with grpbuf untouched in between, the offsets (either may be null).  No argument checks.
-int32_t device_records_settle(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
-                              uint64_t n_bytes, uint8_t delim, uint64_t *n_records, void *stream);
-int32_t device_records_emit(aha_ac *ac, Scratch *sc, const uint64_t *d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
-                            uint64_t *d_rec_offsets, uint64_t *d_doc_rec_offsets, void *stream);
+// grpbuf, *n_records read back; then, with grpbuf untouched in between, the offsets (either may be null).  No argument checks,
+// and B.checked is not looked at.
+int32_t device_records_settle(aha_ac *ac, Scratch *sc, const Batch &B, uint8_t delim, uint64_t *n_records);
+int32_t device_records_emit(aha_ac *ac, Scratch *sc, const Batch &B, uint64_t *d_rec_offsets, uint64_t *d_doc_rec_offsets);
 // the cap of the grids of the passes after the traversal: fold copies, cover, select, the feeds' (AHA_POST_BLOCKS); the fallback
 // of the families' own caps
 uint32_t post_grid(const aha_ac *ac);
 uint32_t grep_grid(const aha_ac *ac);  // the cap of the records and grep grids (AHA_GREP_BLOCKS)
 // one device-resident batch filtered (aha_ac_grep_batch_device): device_count for the hits per document, the kept documents and
 // the dropped runs from them (scan_grep.hip), replace's scan and copy over the runs (scan_replace.hip)
-int32_t device_grep(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
-                    const aha_match_params *params, uint32_t flags, uint64_t *d_kept_docs, uint64_t *d_doc_out_offsets,
-                    uint64_t cap_docs, uint8_t *d_out, uint64_t cap_bytes, uint64_t *n_kept, uint64_t *n_out_bytes, uint64_t *n_hits,
-                    void *stream, bool offsets_checked);
-// the same filtered by a rule over the class counts (AHA_GREP_RULE; gp checked by capi.cpp grep_rule_args): device_class_counts
-// into d_rows or scratch, the keep mask from the rule and S and T from keep (scan_greprule.hip), then grep's tail.
-// rows_early: d_rows may be written before the verdict (it is not the caller's buffer, or the call cannot fail on capacity)
-int32_t device_grep_rule(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
-                         uint64_t n_bytes, const aha_grep_params *gp, uint32_t *d_rows, uint32_t flags, uint64_t *d_kept_docs,
-                         uint64_t *d_doc_out_offsets, uint64_t cap_docs, uint8_t *d_out, uint64_t cap_bytes, uint64_t *n_kept,
-                         uint64_t *n_out_bytes, uint64_t *n_hits, void *stream, bool offsets_checked, bool rows_early);
-// the excerpts of one device-resident batch (AHA_GREP_CONTEXT; ep checked by capi.cpp grep_context_args): device_count with a
-// cover mask in scratch, the covered runs, their windows and the merge (scan_excerpt.hip), replace's scan and copy over the gaps
-// between the excerpts.  d_starts takes grep's d_kept_docs, d_out_offsets its d_doc_out_offsets
-int32_t device_excerpts(aha_ac *ac, Scratch *sc, const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs,
-                        uint64_t n_bytes, const aha_excerpt_params *ep, uint64_t *d_starts, uint64_t *d_out_offsets, uint64_t cap_docs,
-                        uint8_t *d_out, uint64_t cap_bytes, uint64_t *n_kept, uint64_t *n_out_bytes, uint64_t *n_hits, void *stream,
-                        bool offsets_checked);
+int32_t device_grep(aha_ac *ac, Scratch *sc, const Batch &B, uint32_t flags, uint64_t *d_kept_docs, uint64_t *d_doc_out_offsets,
+                    uint64_t cap_docs, uint8_t *d_out, uint64_t cap_bytes, uint64_t *n_kept, uint64_t *n_out_bytes, uint64_t *n_hits);
+// the same filtered by a rule over the class counts (AHA_GREP_RULE; gp checked by capi.cpp grep_rule_args; the match parameters
+// are gp->match, B.params is not looked at): device_class_counts into d_rows or scratch, the keep mask from the rule and S and T
+// from keep (scan_greprule.hip), then grep's tail.
+enum class RuleRows {
+  kLate,  // d_rows is the caller's and the call may still fail on capacity: the table goes to scratch, then to d_rows
+  kEarly  // d_rows may be written before the verdict (it is not the caller's buffer, or the call cannot fail on capacity)
+};
+int32_t device_grep_rule(aha_ac *ac, Scratch *sc, const Batch &B, const aha_grep_params *gp, uint32_t *d_rows, RuleRows rows,
+                         uint32_t flags, uint64_t *d_kept_docs, uint64_t *d_doc_out_offsets, uint64_t cap_docs, uint8_t *d_out,
+                         uint64_t cap_bytes, uint64_t *n_kept, uint64_t *n_out_bytes, uint64_t *n_hits);
+// the excerpts of one device-resident batch (AHA_GREP_CONTEXT; ep checked by capi.cpp grep_context_args; the match parameters
+// are ep->match, B.params is not looked at): device_count with a cover mask in scratch, the covered runs, their windows and the
+// merge (scan_excerpt.hip), replace's scan and copy over the gaps between the excerpts.  d_starts takes grep's d_kept_docs,
+// d_out_offsets its d_doc_out_offsets
+int32_t device_excerpts(aha_ac *ac, Scratch *sc, const Batch &B, const aha_excerpt_params *ep, uint64_t *d_starts,
+                        uint64_t *d_out_offsets, uint64_t cap_docs, uint8_t *d_out, uint64_t cap_bytes, uint64_t *n_kept,
+                        uint64_t *n_out_bytes, uint64_t *n_hits);
 // one device-resident batch as a dense table of hits per (document, key class) (aha_ac_class_counts_batch_device):
 // device_count for the hits per document, the match of every range of whole documents into scratch, one add per (hit, class)
 // into d_out[n_docs][table->n_classes] (scan_classcount.hip)
-int32_t device_class_counts(aha_ac *ac, Scratch *sc, const aha_classes *table, const uint8_t *d_corpus, const uint64_t *d_doc_offsets,
-                            uint64_t n_docs, uint64_t n_bytes, const aha_match_params *params, uint32_t *d_out, uint64_t *n_hits,
-                            void *stream, bool offsets_checked);
+int32_t device_class_counts(aha_ac *ac, Scratch *sc, const aha_classes *table, const Batch &B, uint32_t *d_out, uint64_t *n_hits);
 // the pieces of a call on a longest feed (feed.cpp feed_long_prepare; scan_feedlongest.hip), walked as the documents of a
 // two-pass match_longest batch that start from the feed's carried states.  _count: the text as the kernels take it (folded on a
 // folded handle), the NUL look and the chunks in mode 2, pass 1 and the block scan; *n_hits = the call's hits (one read-back),

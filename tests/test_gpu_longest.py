@@ -2,7 +2,7 @@
 image, keys long enough to grow the chunk and its warm-up, batches with more than one scan tile of documents or chunks,
 several host ranges, NUL bytes that the chunked form must find, and every entry that accepts `longest`.
 
-The path is engine.cpp device_match's `if (longest)` branch: mode 1 (longest = 1) is a thread per document; mode 2
+The path is engine.cpp match_longest_pass (what device_match hands a `longest` call to): mode 1 (longest = 1) is a thread per document; mode 2
 (longest = 2, byte offsets) a thread per chunk with a 2 * Lmax warm-up (k_longest_chunks); mode 3 (longest = 2 with char
 offsets, or a mode-2 batch whose warm-ups give up at NULs) a thread per document again.  None of the engine variants of
 test_gpu_parity.py applies, so nothing here runs under them.  Every case compares with the oracle's match_longest, one
@@ -36,7 +36,7 @@ def cached(key, make):
 
 
 def longest_chunk(L):
-    """device_match's chunk for match_longest: the first power of two >= max(1024, 16 L), at most 1 MiB.  The warm-up
+    """match_longest_pass's chunk: the first power of two >= max(1024, 16 L), at most 1 MiB.  The warm-up
     of a chunk is 2 L bytes."""
     c = 1024
     while c < 16 * L and c < MiB:
