@@ -37,6 +37,7 @@ AHA_COUNT_ACCUMULATE = 1
 AHA_GREP_INVERT = 1
 AHA_GREP_RULE = 4
 AHA_GREP_CONTEXT = 8
+AHA_GREP_LINES = 16
 AHA_SELECT_TOKENS = 4
 AHA_SELECT_GAP_RUNS = 8
 AHA_RULE_GE = 0
@@ -80,6 +81,12 @@ class aha_excerpt_params(C.Structure):
     """AHA_GREP_CONTEXT: what `params` of a grep call points to; match.struct_size = sizeof(aha_excerpt_params), 64 bytes"""
     _fields_ = [("match", aha_match_params), ("before", C.c_uint32), ("after", C.c_uint32), ("flags", C.c_uint32),
                 ("reserved", C.c_uint32)]
+
+
+class aha_grep_lines_params(C.Structure):
+    """AHA_GREP_LINES: what `params` of a grep call points to; match.struct_size = sizeof(aha_grep_lines_params), 88 bytes"""
+    _fields_ = [("match", aha_match_params), ("before", C.c_uint32), ("after", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32), ("group_offsets", C.c_void_p), ("n_groups", C.c_uint64), ("is_match", C.c_void_p)]
 
 
 class aha_ac_info_t(C.Structure):

@@ -1118,6 +1118,57 @@ class AC:
         gp.rows = rows_ptr
         return C.cast(C.pointer(gp), C.POINTER(N.aha_match_params)), flags | N.AHA_GREP_RULE, (gp, rule), rule.classes
 
+    # -- context lines: the records around a matching record (aha_ac_grep_batch* with AHA_GREP_LINES) -------------------------
+    @staticmethod
+    def _lines_spec(before, after, context, groups, matched, rule):
+        """-> None where none of the context keywords is given (the call is plain grep's), else (before, after); checked
+        before the library is called"""
+        plain = lambda v: not isinstance(v, bool) and isinstance(v, (int, np.integer)) and int(v) == 0
+        if context is None and groups is None and matched is None and plain(before) and plain(after):
+            return None
+        if rule is not None:
+            raise ValueError("before, after, context, groups and matched do not combine with rule=")
+        if context is not None:
+            if not (plain(before) and plain(after)):
+                raise ValueError("context sets both sides: give it, or before and after")
+            before = after = context
+        for name, v in (("before", before), ("after", after)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError("%s is a record count: %r" % (name, v))
+            if not 0 <= int(v) <= 0x7FFFFFFF:
+                raise ValueError("%s is 0 .. 0x7FFFFFFF: %r" % (name, v))
+        return int(before), int(after)
+
+    @staticmethod
+    def _lines_params(sep, invert, spec, groups_ptr, n_groups):
+        """-> (params pointer, flags, the aha_grep_lines_params: it must stay alive over the call, is_match is set on it)"""
+        lp = N.aha_grep_lines_params()
+        lp.match = _params(False, sep)
+        lp.match.struct_size = C.sizeof(N.aha_grep_lines_params)
+        lp.before, lp.after, lp.flags, lp.reserved = spec[0], spec[1], 0, 0
+        lp.group_offsets, lp.n_groups, lp.is_match = (groups_ptr, n_groups, None) if n_groups else (None, 0, None)
+        flags = N.AHA_GREP_LINES | (N.AHA_GREP_INVERT if invert else 0)
+        return C.cast(C.pointer(lp), C.POINTER(N.aha_match_params)), flags, lp
+
+    @staticmethod
+    def _host_groups(groups):
+        """groups of a host call -> a contiguous uint64 array of G + 1 entries, or None"""
+        if groups is None:
+            return None
+        g = np.ascontiguousarray(groups, dtype=np.uint64)
+        if g.ndim != 1 or g.size < 1:
+            raise ValueError("groups is a one-dimensional array of G + 1 record offsets")
+        return g
+
+    @staticmethod
+    def _host_matched(matched):
+        if matched is None:
+            return None
+        if not (isinstance(matched, np.ndarray) and matched.dtype == np.uint8 and matched.ndim == 1 and matched.flags.c_contiguous
+                and matched.flags.writeable):
+            raise ValueError("matched must be a contiguous writeable one-dimensional uint8 array")
+        return matched
+
     @staticmethod
     def _host_rows(rows, D, table):
         if rows is None:
@@ -1191,18 +1242,28 @@ class AC:
         e.bytes_required = int(n_bytes.value)
         return e
 
-    def grep_batch(self, corpus, doc_offsets, sep=None, invert=False, text=True, classes=None, rule=None, rows=None):
+    def grep_batch(self, corpus, doc_offsets, sep=None, invert=False, text=True, classes=None, rule=None, rows=None, before=0,
+                   after=0, context=None, groups=None, matched=None):
         """The documents with at least one hit of match_batch(corpus, doc_offsets, sep) -- invert: those without one --
         compacted on the device: -> (kept_docs uint64[n_kept], uint8 array, doc_out_offsets uint64[n_kept+1]); kept document
         i is document kept_docs[i] and its bytes are out[doc_out_offsets[i]:doc_out_offsets[i+1]].  text False: no bytes are
         copied (an empty array comes back).  A sizing call first.
         rule (a Rule of AC.rule, or its spec with classes=): the documents whose class counts pass the rule instead -- invert:
-        those that do not; rows (a uint32 array of shape (D, C)) then receives class_counts_batch of the batch."""
+        those that do not; rows (a uint32 array of shape (D, C)) then receives class_counts_batch of the batch.
+        before, after (context: both): grep -B, -A, -C -- that many documents (records) in front of and behind a matching one
+        are kept with it, inside the groups (uint64[G + 1] offsets into the documents, such as records()'s doc_rec_offsets;
+        None: one group); matched (a uint8 array of at least n_kept entries) receives 1 where the kept document matched, 0
+        where it is context.  Not with rule=."""
+        spec = self._lines_spec(before, after, context, groups, matched, rule)
         if isinstance(corpus, (bytes, bytearray)):
             corpus = np.frombuffer(bytes(corpus), dtype=np.uint8)
         corpus = np.ascontiguousarray(corpus, dtype=np.uint8)
         doc_offsets = np.ascontiguousarray(doc_offsets, dtype=np.uint64)
         D = doc_offsets.size - 1
+        if spec is not None:
+            if classes is not None or rows is not None:
+                raise ValueError("classes and rows belong to a rule: give rule=")
+            return self._grep_lines_host(corpus, doc_offsets, D, sep, invert, text, spec, groups, matched)
         p, flags, _alive, table = self._grep_params(sep, invert, classes, rule, None)
         if rows is not None:
             if table is None:
@@ -1222,23 +1283,58 @@ class AC:
                                         cap_docs, _ptr(out) if text else None, cap_bytes, C.byref(nk), C.byref(nb), None))
         return kept[: int(nk.value)], out[: int(nb.value) if text else 0], doo[: int(nk.value) + 1]
 
+    def _grep_lines_host(self, corpus, doc_offsets, D, sep, invert, text, spec, groups, matched):
+        """grep_batch with context lines: the same two calls, the second with is_match where matched was given"""
+        g = self._host_groups(groups)
+        matched = self._host_matched(matched)
+        p, flags, lp = self._lines_params(sep, invert, spec, g.ctypes.data if g is not None else None, g.size - 1 if g is not None else 0)
+        nk, nb = C.c_uint64(0), C.c_uint64(0)
+        L = N.lib()
+        self._check(L.aha_ac_grep_batch(self._h, _ptr(corpus), _ptr(doc_offsets), D, p, flags, None, None, 0, None, 0,
+                                        C.byref(nk), C.byref(nb), None))
+        cap_docs, cap_bytes = int(nk.value), int(nb.value) if text else 0
+        if matched is not None and matched.size < cap_docs:
+            raise ValueError("matched has %d entries, the call keeps %d documents" % (matched.size, cap_docs))
+        kept = np.zeros(max(cap_docs, 1), dtype=np.uint64)
+        doo = np.zeros(cap_docs + 1, dtype=np.uint64)
+        out = np.zeros(max(cap_bytes, 1), dtype=np.uint8)
+        if matched is not None and cap_docs:
+            lp.is_match = matched.ctypes.data
+        self._check(L.aha_ac_grep_batch(self._h, _ptr(corpus), _ptr(doc_offsets), D, p, flags, _ptr(kept), _ptr(doo),
+                                        cap_docs, _ptr(out) if text else None, cap_bytes, C.byref(nk), C.byref(nb), None))
+        return kept[: int(nk.value)], out[: int(nb.value) if text else 0], doo[: int(nk.value) + 1]
+
     def grep_batch_device(self, corpus, doc_offsets, kept_docs=None, doc_out_offsets=None, out=None, sep=None, invert=False,
-                          cap_docs=None, cap_bytes=None, stream=None, classes=None, rule=None, rows=None):
+                          cap_docs=None, cap_bytes=None, stream=None, classes=None, rule=None, rows=None, before=0, after=0,
+                          context=None, groups=None, matched=None):
         """Device-resident grep on torch CUDA tensors: uint8 corpus, int64/uint64 doc offsets, kept_docs int64/uint64
         [cap_docs] or None, doc_out_offsets int64/uint64 [cap_docs + 1] or None, out uint8 [cap_bytes] (any alignment) or None
         (no bytes are copied).  -> (n_kept, n_out_bytes, n_hits); raises AhaError(AHA_E_CAPACITY) when a buffer is too small
         (e.n_required = the documents needed, e.bytes_required = the bytes needed); nothing is written then.
         rule (a Rule of AC.rule, or its spec with classes=): the documents whose class counts pass the rule; rows: a
         contiguous int32 CUDA tensor of shape (D, C) that receives the class counts (as uint32), as class_counts_batch_device
-        writes them."""
+        writes them.
+        before, after, context: as in grep_batch; groups: an int64/uint64 CUDA tensor of G + 1 record offsets (such as
+        records_device's doc_rec_offsets) or None; matched: a uint8 CUDA tensor that receives 1 where the kept document
+        matched and 0 where it is context (it bounds cap_docs as kept_docs does).  Not with rule=."""
         import torch
 
+        spec = self._lines_spec(before, after, context, groups, matched, rule)
+        if spec is not None and (classes is not None or rows is not None):
+            raise ValueError("classes and rows belong to a rule: give rule=")
         assert corpus.is_cuda and corpus.dtype == torch.uint8 and corpus.is_contiguous()
         assert doc_offsets.is_cuda and doc_offsets.dtype in (torch.int64, torch.uint64)
-        for name, t in (("kept_docs", kept_docs), ("doc_out_offsets", doc_out_offsets)):
+        for name, t in (("kept_docs", kept_docs), ("doc_out_offsets", doc_out_offsets), ("groups", groups)):
             if t is not None and not (t.is_cuda and t.dtype in (torch.int64, torch.uint64) and t.is_contiguous()):
                 raise ValueError(name + " must be a contiguous int64/uint64 CUDA tensor")
+        if groups is not None and (groups.dim() != 1 or groups.numel() < 1):
+            raise ValueError("groups is a one-dimensional tensor of G + 1 record offsets")
+        if matched is not None and not (matched.is_cuda and matched.dtype == torch.uint8 and matched.is_contiguous()
+                                        and matched.dim() == 1):
+            raise ValueError("matched must be a contiguous one-dimensional uint8 CUDA tensor")
         room = []
+        if matched is not None:
+            room.append(matched.numel())
         if kept_docs is not None:
             room.append(kept_docs.numel())
         if doc_out_offsets is not None:
@@ -1253,7 +1349,14 @@ class AC:
         else:
             cap_bytes = 0
         D = doc_offsets.numel() - 1
-        p, flags, _alive, table = self._grep_params(sep, invert, classes, rule, None)
+        if spec is not None:
+            p, flags, _alive = self._lines_params(sep, invert, spec, groups.data_ptr() if groups is not None else None,
+                                                  groups.numel() - 1 if groups is not None else 0)
+            if matched is not None and cap_docs:
+                _alive.is_match = matched.data_ptr()
+            table = None
+        else:
+            p, flags, _alive, table = self._grep_params(sep, invert, classes, rule, None)
         if rows is not None:
             if table is None:
                 raise ValueError("classes and rows belong to a rule: give rule=")
@@ -1273,17 +1376,33 @@ class AC:
         self._check(rc)
         return int(nk.value), int(nb.value), int(nh.value)
 
-    def grep_corpus(self, corpus, sep=None, invert=False, text=True, classes=None, rule=None, rows=None):
+    def grep_corpus(self, corpus, sep=None, invert=False, text=True, classes=None, rule=None, rows=None, before=0, after=0,
+                    context=None, groups=None, matched=None):
         """grep_batch of a batch that already lives in HBM (DeviceCorpus), downloaded:
         -> (kept_docs uint64[n_kept], uint8 array, doc_out_offsets uint64[n_kept+1], n_hits).  rule, classes, rows: as in
-        grep_batch (rows a uint32 array of shape (D, C), downloaded into)."""
+        grep_batch (rows a uint32 array of shape (D, C), downloaded into).  before, after, context, groups, matched: as in
+        grep_batch (groups a host array, uploaded; matched a host array, downloaded into)."""
+        spec = self._lines_spec(before, after, context, groups, matched, rule)
         D = corpus.n_docs
-        p, flags, _alive, table = self._grep_params(sep, invert, classes, rule, None)
+        dev = corpus.device
+        d_groups = d_matched = None
+        if spec is not None:
+            if classes is not None or rows is not None:
+                raise ValueError("classes and rows belong to a rule: give rule=")
+            g = self._host_groups(groups)
+            matched = self._host_matched(matched)
+            if g is not None and g.size > 1:
+                d_groups = DeviceBuffer(dev, g.nbytes)
+                d_groups.upload(g)
+            p, flags, _alive = self._lines_params(sep, invert, spec, d_groups.ptr if d_groups is not None else None,
+                                                  g.size - 1 if g is not None else 0)
+            table = None
+        else:
+            p, flags, _alive, table = self._grep_params(sep, invert, classes, rule, None)
         if rows is not None:
             if table is None:
                 raise ValueError("classes and rows belong to a rule: give rule=")
             rows = self._host_rows(rows, D, table)
-        dev = corpus.device
         nk, nb, nh = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         L = N.lib()
         self._check(L.aha_ac_grep_batch_device(self._h, corpus.ptr, corpus.doc_ptr, D, corpus.n_bytes, p, flags, None, None,
@@ -1294,25 +1413,49 @@ class AC:
         d_rows = DeviceBuffer(dev, rows.size * 4) if rows is not None and rows.size else None
         if d_rows is not None:
             _alive[0].rows = d_rows.ptr
+        if spec is not None and matched is not None:
+            if matched.size < cap_docs:
+                raise ValueError("matched has %d entries, the call keeps %d documents" % (matched.size, cap_docs))
+            if cap_docs:
+                d_matched = DeviceBuffer(dev, cap_docs)
+                _alive.is_match = d_matched.ptr
         self._check(L.aha_ac_grep_batch_device(self._h, corpus.ptr, corpus.doc_ptr, D, corpus.n_bytes, p, flags, kept.ptr,
                                                doo.ptr, cap_docs, out.ptr if text else None, cap_bytes, C.byref(nk), C.byref(nb),
                                                C.byref(nh), None))
         if d_rows is not None:
             d_rows.download(rows)
+        if d_matched is not None:
+            d_matched.download(matched[:cap_docs])
         got = out.download(np.zeros(max(cap_bytes, 1), dtype=np.uint8))[:cap_bytes] if text else np.zeros(0, dtype=np.uint8)
         return (kept.download(np.zeros(max(cap_docs, 1), dtype=np.uint64))[:cap_docs], got,
                 doo.download(np.zeros(cap_docs + 1, dtype=np.uint64)), int(nh.value))
 
-    def grep(self, seq, delim="\n", invert=False, sep=None, classes=None, rule=None, rows=None):
+    def grep(self, seq, delim="\n", invert=False, sep=None, classes=None, rule=None, rows=None, before=0, after=0, context=None,
+             groups=None, matched=None, separator=None):
         """The records of seq -- split at delim, each with its delimiter -- that have a hit of match(record, sep), as a
         list; invert: those that have none.  bytes in, bytes out; str in, str out.  records plus grep_batch.  rule, classes,
-        rows: as in grep_batch, over the records (rows has one row per record of AC.records(seq, None, delim))."""
+        rows: as in grep_batch, over the records (rows has one row per record of AC.records(seq, None, delim)).
+        before, after, context, groups, matched: as in grep_batch, over the records -- grep -B, -A, -C.  separator (a str or
+        bytes such as "--\\n"; None: nothing) is inserted as an entry of its own between two kept records that are not
+        neighbours or lie in different groups."""
+        spec = self._lines_spec(before, after, context, groups, matched, rule)
         b = _b(seq)
         corpus = np.frombuffer(b, dtype=np.uint8)
         rec, _ = self.records(corpus, None, delim)
-        _, out, doo = self.grep_batch(corpus, rec, sep=sep, invert=invert, classes=classes, rule=rule, rows=rows)
+        if spec is None:
+            _, out, doo = self.grep_batch(corpus, rec, sep=sep, invert=invert, classes=classes, rule=rule, rows=rows)
+            kept = None
+        else:
+            kept, out, doo = self.grep_batch(corpus, rec, sep=sep, invert=invert, classes=classes, rows=rows, before=spec[0],
+                                             after=spec[1], groups=groups, matched=matched)
         raw = out.tobytes()
         parts = [raw[int(doo[i]):int(doo[i + 1])] for i in range(doo.size - 1)]
+        if separator is not None and kept is not None and kept.size > 1:
+            g = self._host_groups(groups)
+            own = np.searchsorted(g, kept, side="right") if g is not None else np.zeros(kept.size, dtype=np.int64)
+            cut = (kept[1:] != kept[:-1] + 1) | (own[1:] != own[:-1])
+            mark = _b(separator)
+            parts = [x for i, part in enumerate(parts) for x in ((mark, part) if i and cut[i - 1] else (part,))]
         return [x.decode("utf-8") for x in parts] if isinstance(seq, str) else parts
 
     # -- excerpts: the text around every hit, cut out on the device (aha_ac_grep_batch* with AHA_GREP_CONTEXT) --------------

@@ -1746,13 +1746,36 @@ static int32_t grep_context_args(const aha_match_params *params, uint32_t flags)
   return AHA_OK;
 }
 
+// AHA_GREP_LINES: combines with AHA_GREP_INVERT only; params is the first member of an aha_grep_lines_params (before any device
+// work).  Its two pointers are not followed here: host memory in one entry, HBM in the other
+static int32_t grep_lines_args(const aha_match_params *params, uint32_t flags, uint64_t cap_docs) {
+  auto bad = [](const char *what) {
+    tls_err = what;
+    return AHA_E_INVALID;
+  };
+  if (flags & ~(AHA_GREP_LINES | AHA_GREP_INVERT)) return bad("AHA_GREP_LINES combines with AHA_GREP_INVERT only");
+  if (!params || params->struct_size < sizeof(aha_grep_lines_params))
+    return bad("AHA_GREP_LINES: params must point to an aha_grep_lines_params with match.struct_size = sizeof(aha_grep_lines_params)");
+  const aha_grep_lines_params *lp = reinterpret_cast<const aha_grep_lines_params *>(params);
+  if (lp->flags || lp->reserved) return bad("AHA_GREP_LINES: flags and reserved are 0");
+  if (lp->before > 0x7FFFFFFFu || lp->after > 0x7FFFFFFFu) return bad("AHA_GREP_LINES: before and after are at most 0x7FFFFFFF");
+  if (!lp->group_offsets != !lp->n_groups) return bad("AHA_GREP_LINES: group_offsets has n_groups + 1 entries, or is NULL with n_groups = 0");
+  if (lp->is_match && !cap_docs) return bad("AHA_GREP_LINES: is_match has cap_docs entries, and cap_docs is 0");
+  return AHA_OK;
+}
+
 // the argument checks both grep entries share: before any device work, so they hold on a host-only handle.  out / corpus: the
 // two address ranges that must not overlap (there is no in-place form)
 static int32_t grep_args(aha_ac *ac, const uint8_t *corpus, uint64_t n_bytes, const uint64_t *doc_offsets, const aha_match_params *params,
                          uint32_t flags, const uint64_t *kept_docs, const uint64_t *doc_out_offsets, uint64_t cap_docs,
                          const uint8_t *out, uint64_t cap_bytes, uint64_t *n_kept) {
-  if (!ac || !n_kept || !doc_offsets || (flags & ~(AHA_GREP_INVERT | AHA_GREP_RULE | AHA_GREP_CONTEXT))) return AHA_E_INVALID;
-  if (flags & AHA_GREP_CONTEXT) {
+  if (!ac || !n_kept || !doc_offsets || (flags & ~(AHA_GREP_INVERT | AHA_GREP_RULE | AHA_GREP_CONTEXT | AHA_GREP_LINES)))
+    return AHA_E_INVALID;
+  const aha_grep_lines_params *lp = nullptr;
+  if (flags & AHA_GREP_LINES) {
+    if (int32_t rc = grep_lines_args(params, flags, cap_docs)) return rc;
+    lp = reinterpret_cast<const aha_grep_lines_params *>(params);
+  } else if (flags & AHA_GREP_CONTEXT) {
     if (int32_t rc = grep_context_args(params, flags)) return rc;
   } else if (flags & AHA_GREP_RULE) {
     if (int32_t rc = grep_rule_args(ac, params)) return rc;
@@ -1762,7 +1785,7 @@ static int32_t grep_args(aha_ac *ac, const uint8_t *corpus, uint64_t n_bytes, co
     tls_err = "grep calls take byte offsets only";
     return AHA_E_INVALID;
   }
-  if ((cap_docs && !kept_docs && !doc_out_offsets) || (cap_bytes && !out)) return AHA_E_INVALID;
+  if ((cap_docs && !kept_docs && !doc_out_offsets && !(lp && lp->is_match)) || (cap_bytes && !out)) return AHA_E_INVALID;
   if (cap_bytes && n_bytes && corpus) {
     const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), c0 = reinterpret_cast<uintptr_t>(corpus);
     if (o0 < c0 + n_bytes && c0 < o0 + cap_bytes) {
@@ -1783,6 +1806,11 @@ int32_t aha_ac_grep_batch_device(aha_ac *ac, const uint8_t *d_corpus, const uint
   if (rc) return rc;
   Lease lease(ac);
   const Batch B = abi_batch(d_corpus, d_doc_offsets, n_docs, n_bytes, params, stream);
+  if (flags & AHA_GREP_LINES) {
+    const aha_grep_lines_params *lp = reinterpret_cast<const aha_grep_lines_params *>(params);
+    return device_grep_lines(ac, lease.get(), B, lp, lp->group_offsets, lp->is_match, flags, d_kept_docs, d_doc_out_offsets, cap_docs,
+                             d_out, cap_bytes, n_kept, n_out_bytes, n_hits);
+  }
   if (flags & AHA_GREP_CONTEXT)
     return device_excerpts(ac, lease.get(), B, reinterpret_cast<const aha_excerpt_params *>(params), d_kept_docs, d_doc_out_offsets,
                            cap_docs, d_out, cap_bytes, n_kept, n_out_bytes, n_hits);
@@ -1818,16 +1846,25 @@ int32_t aha_ac_grep_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc
   const aha_grep_params *gp = (flags & AHA_GREP_RULE) ? reinterpret_cast<const aha_grep_params *>(params) : nullptr;
   const uint64_t per_doc_bytes = per_doc ? (2 * cap_docs + 1) * 8 : 0;
   const uint64_t n_rows = gp && gp->rows ? n_docs * gp->classes->n_classes : 0;
-  if ((rc = stage_host_batch(ac, sc, corpus, doc_offsets, n_docs, params, per_doc_bytes + n_rows * 4,
+  // ... or, of a call with context lines, the group offsets on their way up and is_match on its way back
+  const aha_grep_lines_params *lp = (flags & AHA_GREP_LINES) ? reinterpret_cast<const aha_grep_lines_params *>(params) : nullptr;
+  const uint64_t group_bytes = lp && lp->group_offsets ? (lp->n_groups + 1) * 8 : 0;
+  const uint64_t flag_bytes = lp && lp->is_match ? cap_docs : 0;
+  if ((rc = stage_host_batch(ac, sc, corpus, doc_offsets, n_docs, params, per_doc_bytes + n_rows * 4 + group_bytes + flag_bytes,
                              out ? std::max<uint64_t>(cap_bytes, 1) : 0, B, H)))
     return rc;
   uint32_t *d_rows = n_rows ? (uint32_t *)((uint8_t *)H.d_per_doc + per_doc_bytes) : nullptr;
+  uint64_t *d_groups = group_bytes ? (uint64_t *)((uint8_t *)H.d_per_doc + per_doc_bytes) : nullptr;
+  uint8_t *d_flags = flag_bytes ? (uint8_t *)H.d_per_doc + per_doc_bytes + group_bytes : nullptr;
   uint64_t *d_kept = kept_docs ? (uint64_t *)H.d_per_doc : nullptr;
   uint64_t *d_doo = doc_out_offsets ? (uint64_t *)H.d_per_doc + cap_docs : nullptr;
   uint8_t *d_out = (uint8_t *)H.d_per_call;
   hipStream_t s = B.stream;
   uint64_t nk = 0, nb = 0, nh = 0;
-  if (flags & AHA_GREP_CONTEXT)  // (kept_docs takes the excerpts' starts, doc_out_offsets their offsets into out)
+  if (d_groups) HIPCHK(ac, hipMemcpyAsync(d_groups, lp->group_offsets, group_bytes, hipMemcpyHostToDevice, s));
+  if (lp)
+    rc = device_grep_lines(ac, sc, B, lp, d_groups, d_flags, flags, d_kept, d_doo, cap_docs, d_out, d_out ? cap_bytes : 0, &nk, &nb, &nh);
+  else if (flags & AHA_GREP_CONTEXT)  // (kept_docs takes the excerpts' starts, doc_out_offsets their offsets into out)
     rc = device_excerpts(ac, sc, B, reinterpret_cast<const aha_excerpt_params *>(params), d_kept, d_doo, cap_docs, d_out,
                          d_out ? cap_bytes : 0, &nk, &nb, &nh);
   else if (gp)  // (d_rows is staging: the table may go there before the verdict)
@@ -1845,6 +1882,7 @@ int32_t aha_ac_grep_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc
   if (doc_out_offsets) HIPCHK(ac, hipMemcpyAsync(doc_out_offsets, d_doo, (nk + 1) * 8, hipMemcpyDeviceToHost, s));
   if (out && nb) HIPCHK(ac, hipMemcpyAsync(out, d_out, nb, hipMemcpyDeviceToHost, s));
   if (n_rows) HIPCHK(ac, hipMemcpyAsync(gp->rows, d_rows, n_rows * 4, hipMemcpyDeviceToHost, s));
+  if (d_flags && nk) HIPCHK(ac, hipMemcpyAsync(lp->is_match, d_flags, nk, hipMemcpyDeviceToHost, s));
   HIPCHK(ac, hipStreamSynchronize(s));
   *n_kept = nk;
   if (n_out_bytes) *n_out_bytes = nb;

@@ -1982,9 +1982,11 @@ static bool grep_masks(Scratch *sc, uint64_t D, GrepMasks &M) {
 
 // Grep's tail, from the three masks on (steps 2 to 4 of device_grep below): their ranks, the runs, the scan, the verdict, then
 // -- once both numbers fit -- the kept documents and the copy.  *kept and *total are the required numbers either way; *fits
-// says whether anything was written to the caller.
+// says whether anything was written to the caller.  more_per_doc: the caller has a per-document buffer of its own that cap_docs
+// bounds (context lines' is_match), so the verdict looks at cap_docs without kept_docs or doc_out_offsets too.
 static int32_t grep_tail(aha_ac *ac, Scratch *sc, const Batch &B, const GrepMasks &M, uint64_t *d_kept_docs, uint64_t *d_doc_out_offsets,
-                         uint64_t cap_docs, uint8_t *d_out, uint64_t cap_bytes, uint64_t *kept_out, uint64_t *total_out, bool *fits_out) {
+                         uint64_t cap_docs, uint8_t *d_out, uint64_t cap_bytes, uint64_t *kept_out, uint64_t *total_out, bool *fits_out,
+                         bool more_per_doc = false) {
   hipStream_t s = B.stream;
   const uint8_t *d_corpus = B.text;
   const uint64_t *d_doc_offsets = B.doc_off;
@@ -2017,7 +2019,7 @@ static int32_t grep_tail(aha_ac *ac, Scratch *sc, const Batch &B, const GrepMask
   HIPCHK(ac, hipStreamSynchronize(s));
   const uint64_t total = (uint64_t)((int64_t)n_bytes + change);
   const bool per_doc = d_kept_docs || d_doc_out_offsets;
-  const bool fits = !(per_doc && kept > cap_docs) && !(d_out && total > cap_bytes);
+  const bool fits = !((per_doc || more_per_doc) && kept > cap_docs) && !(d_out && total > cap_bytes);
   if (fits) {
     if (per_doc)
       grep_launch_emit_docs(M.keep, M.S, D, M.blk_k, M.blk_s, d_doc_offsets, shift, n_runs, d_kept_docs, d_doc_out_offsets, blocks, s);
@@ -2358,5 +2360,119 @@ int32_t device_grep_rule(aha_ac *ac, Scratch *sc, const Batch &B0, const aha_gre
   return AHA_OK;
 }
 
+// ---- context lines (aha_ac_grep_batch* with AHA_GREP_LINES) --------------------------------------------------------------
+// Group offsets live in HBM: k_check_docs over (group_offsets, G, D) and a 4-byte read-back before anything indexes with them.
+// Only its order verdict counts: the 2 GiB limit per span is for documents in bytes, a group may hold any number of records.
+static int32_t check_groups_now(aha_ac *ac, Scratch *sc, const uint64_t *d_groups, uint64_t n_groups, uint64_t n_docs, hipStream_t s) {
+  int32_t rc2;
+  if ((rc2 = v2_reserve(sc, kCursor, kCursorBytes))) return rc2;
+  if ((rc2 = ensure_h_v2(ac, sc))) return rc2;
+  uint32_t *flag = (uint32_t *)sc->v2buf[kCursor].p + 64;  // (check_docs_now's word)
+  HIPCHK(ac, hipMemsetAsync(flag, 0, 4, s));
+  launch_check_docs(d_groups, n_groups, n_docs, flag, nullptr, s);
+  HIPCHK(ac, hipMemcpyAsync(sc->h_v2, flag, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(ac, hipStreamSynchronize(s));
+  if ((uint32_t)sc->h_v2[0] & 1u) {
+    tls_err = "group offsets: need group_offsets[0] = 0, ascending, group_offsets[n_groups] = n_docs";
+    return AHA_E_INVALID;
+  }
+  return AHA_OK;
+}
+
+// One device-resident batch filtered with context (DESIGN.md 4.16 "Context lines").  lp was checked by capi.cpp.
+//   1. device_count without key counts: the records' hit offsets into scratch, the total, the offsets validated; the group
+//      offsets validated (check_groups_now).
+//   2. kgr_flag as it is, its keep mask into a slot of its own: m.  (Its S and T land in grep's slots and are overwritten in 5.)
+//   3. Sm and Tm over records -- where a run of matching records of one group starts and ends (kgl_edges, kgl_group_edges) --
+//      and their ranks: the run count comes back to the host.
+//   4. Per run its group and its window, then the toggles of the merged windows' ends (kgl_windows, kgl_toggle); the toggle
+//      mask's rank; kgl_fill writes grep's keep mask.  Without a run the keep mask is cleared instead.
+//   5. kgq_edges and grep_tail as rule grep calls them.  Once the call is known to fit, kgl_emit_match over the ranked keep mask.
+// A failing call writes none of the caller's buffers.  Scratch beyond grep's: 4 bits per record of masks, 24 bytes per 2048
+// records of block ranks, 24 bytes per matching run.
+int32_t device_grep_lines(aha_ac *ac, Scratch *sc, const Batch &B0, const aha_grep_lines_params *lp, const uint64_t *d_groups,
+                          uint8_t *d_is_match, uint32_t flags, uint64_t *d_kept_docs, uint64_t *d_doc_out_offsets, uint64_t cap_docs,
+                          uint8_t *d_out, uint64_t cap_bytes, uint64_t *n_kept, uint64_t *n_out_bytes, uint64_t *n_hits_out) {
+  if (!ac || !lp || !n_kept || !B0.doc_off || (flags & ~(AHA_GREP_INVERT | AHA_GREP_LINES))) return AHA_E_INVALID;
+  if ((cap_docs && !d_kept_docs && !d_doc_out_offsets && !d_is_match) || (cap_bytes && !d_out)) return AHA_E_INVALID;
+  if ((d_is_match && !cap_docs) || (!d_groups != !lp->n_groups)) return AHA_E_INVALID;
+  if (ac->device < 0) return no_device();
+  DeviceGuard g(ac->device);
+  Batch B = B0;
+  B.params = &lp->match;
+  hipStream_t s = B.stream;
+  const uint64_t D = B.n_docs, G = lp->n_groups;
+  *n_kept = 0;
+  if (n_out_bytes) *n_out_bytes = 0;
+  if (n_hits_out) *n_hits_out = 0;
+  auto nomem = [&]() {
+    tls_err = "hipMalloc failed for the scratch of a grep call";
+    return AHA_E_HIP;
+  };
+  uint64_t *d_dho = (uint64_t *)grp_reserve(sc, kGrpHitOff, (D + 1) * 8);
+  if (!d_dho) return nomem();
+  int32_t rc;
+  uint64_t n_hits = 0;
+  if ((rc = device_count(ac, sc, B, 0, nullptr, d_dho, &n_hits))) return rc;
+  if (d_groups && (rc = check_groups_now(ac, sc, d_groups, G, D, s))) return rc;
+  const bool prof = ac->profiling.load();
+  const auto t0 = std::chrono::steady_clock::now();
+  GrepMasks M;
+  if (!grep_masks(sc, D, M)) return nomem();
+  const uint32_t blocks = grep_grid(ac);
+  const uint64_t n_words = (D + 31) / 32, n_blk = select_rank_blocks(D);
+  const uint64_t t_words = (D + 1 + 31) / 32, t_blk = select_rank_blocks(D + 1);
+  uint32_t *lmasks = (uint32_t *)grp_reserve(sc, kGrpLnMasks, (3 * n_words + t_words) * 4);
+  uint64_t *lblks = (uint64_t *)grp_reserve(sc, kGrpLnBlocks, (2 * (n_blk + 1) + (t_blk + 1)) * 8);
+  if (!lmasks || !lblks) return nomem();
+  uint32_t *m = lmasks, *Sm = lmasks + n_words, *Tm = lmasks + 2 * n_words, *tog = lmasks + 3 * n_words;
+  uint64_t *blk_sm = lblks, *blk_tm = lblks + (n_blk + 1), *blk_x = lblks + 2 * (n_blk + 1);
+  uint64_t n_runs = 0;
+  if (D) {
+    grep_launch_flag(d_dho, D, (flags & AHA_GREP_INVERT) != 0, m, M.S, M.T, blocks, s);
+    greplines_launch_edges(m, D, d_groups, G, Sm, Tm, blocks, s);
+    select_launch_rank(Sm, D, blk_sm, blocks, s);
+    select_launch_rank(Tm, D, blk_tm, blocks, s);
+    HIPCHK(ac, hipGetLastError());
+    HIPCHK(ac, hipMemcpyAsync(&n_runs, blk_sm + n_blk, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(ac, hipStreamSynchronize(s));
+    if (n_runs) {
+      uint64_t *runs = (uint64_t *)grp_reserve(sc, kGrpLnRuns, n_runs * 3 * 8);
+      if (!runs) return nomem();
+      HIPCHK(ac, hipMemsetAsync(tog, 0, t_words * 4, s));
+      greplines_launch_windows(Sm, Tm, D, blk_sm, blk_tm, d_groups, G, lp->before, lp->after, n_runs, runs, runs + n_runs,
+                               runs + 2 * n_runs, tog, blocks, s);
+      select_launch_rank(tog, D + 1, blk_x, blocks, s);
+      greplines_launch_fill(tog, blk_x, D, M.keep, blocks, s);
+    } else {
+      HIPCHK(ac, hipMemsetAsync(M.keep, 0, n_words * 4, s));
+    }
+    greprule_launch_edges(M.keep, D, M.S, M.T, blocks, s);
+    HIPCHK(ac, hipGetLastError());
+  }
+  uint64_t kept = 0, total = 0;
+  bool fits = false;
+  if ((rc = grep_tail(ac, sc, B, M, d_kept_docs, d_doc_out_offsets, cap_docs, d_out, cap_bytes, &kept, &total, &fits, d_is_match != nullptr)))
+    return rc;
+  if (fits && d_is_match && kept) {
+    greplines_launch_emit_match(M.keep, M.blk_k, D, m, d_is_match, blocks, s);
+    HIPCHK(ac, hipGetLastError());
+    HIPCHK(ac, hipStreamSynchronize(s));
+  }
+  *n_kept = kept;
+  if (n_out_bytes) *n_out_bytes = total;
+  if (n_hits_out) *n_hits_out = n_hits;
+  if (prof) {  // ms_write: everything after the count
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    std::lock_guard<std::mutex> lk(ac->last_mu);
+    ac->last.ms_write += (float)ms;
+    ac->last.n_hits = n_hits;
+  }
+  if (!fits) {
+    tls_err = "output buffer too small";
+    return AHA_E_CAPACITY;
+  }
+  return AHA_OK;
+}
 
 }  // namespace ahai

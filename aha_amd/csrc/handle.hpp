@@ -185,6 +185,9 @@ enum GrepSlot {
   kGrpExRuns,     // excerpts: per covered run its document, w0 and w1, 24 bytes
   kGrpExRunMasks, // excerpts: the first and last masks, one bit per run each
   kGrpExRunBlocks,// excerpts: their two block ranks, each with its total behind it (the gap rows: kGrpSel .. kGrpTable)
+  kGrpLnMasks,    // context lines: the match mask m, Sm and Tm, one bit per record each, and the toggle mask of D + 1 bits
+  kGrpLnBlocks,   // context lines: the block ranks of Sm, Tm and the toggle mask, each with its total behind it
+  kGrpLnRuns,     // context lines: per matching run its group, w0 and w1, 24 bytes
   kGrpCount
 };
 // fgrpbuf: feed grep calls (feed.cpp feed_grep; scan_feedgrep.hip).  The fragments come from device_records, whose mask
@@ -659,6 +662,13 @@ int32_t device_grep_rule(aha_ac *ac, Scratch *sc, const Batch &B, const aha_grep
 int32_t device_excerpts(aha_ac *ac, Scratch *sc, const Batch &B, const aha_excerpt_params *ep, uint64_t *d_starts,
                         uint64_t *d_out_offsets, uint64_t cap_docs, uint8_t *d_out, uint64_t cap_bytes, uint64_t *n_kept,
                         uint64_t *n_out_bytes, uint64_t *n_hits);
+// grep with context lines (AHA_GREP_LINES; lp checked by capi.cpp grep_lines_args; the match parameters are lp->match, B.params
+// is not looked at): grep's match mask dilated by lp->before and lp->after records inside the groups (scan_greplines.hip), rule
+// grep's edges, then grep's tail.  d_groups (lp->n_groups + 1 entries or null) and d_is_match (cap_docs bytes or null) are
+// device memory whatever lp->group_offsets and lp->is_match point to
+int32_t device_grep_lines(aha_ac *ac, Scratch *sc, const Batch &B, const aha_grep_lines_params *lp, const uint64_t *d_groups,
+                          uint8_t *d_is_match, uint32_t flags, uint64_t *d_kept_docs, uint64_t *d_doc_out_offsets, uint64_t cap_docs,
+                          uint8_t *d_out, uint64_t cap_bytes, uint64_t *n_kept, uint64_t *n_out_bytes, uint64_t *n_hits);
 // one device-resident batch as a dense table of hits per (document, key class) (aha_ac_class_counts_batch_device):
 // device_count for the hits per document, the match of every range of whole documents into scratch, one add per (hit, class)
 // into d_out[n_docs][table->n_classes] (scan_classcount.hip)

@@ -403,6 +403,24 @@ void greprule_launch_keep(const uint32_t *rows, uint32_t n_classes, const uint64
 // S / T from keep alone, ceil(n_docs / 32) whole words each: a run of dropped documents starts / ends at the bit
 void greprule_launch_edges(const uint32_t *keep, uint64_t n_docs, uint32_t *S, uint32_t *T, uint32_t max_blocks, void *stream);
 
+// context lines (scan_greplines.hip; engine.cpp device_grep_lines), from the match mask m of the batch (one bit per record, the
+// bits from n_docs on 0).  goff: the checked group offsets, n_groups + 1 entries, or null (one group).  Masks are ranked by
+// select_launch_rank.
+// Sm / Tm: ceil(n_docs / 32) whole words each: a run of matching records of one group starts / ends at the bit
+void greplines_launch_edges(const uint32_t *m, uint64_t n_docs, const uint64_t *goff, uint64_t n_groups, uint32_t *Sm, uint32_t *Tm,
+                            uint32_t max_blocks, void *stream);
+// run j, delimited by the j-th bits of Sm and Tm: its group and its window [w0[j], w1[j]) in records; then the two ends of every
+// chunk (the merged windows of one group) XOR-ed into tog, ceil((n_docs + 1) / 32) words that the caller cleared
+void greplines_launch_windows(const uint32_t *Sm, const uint32_t *Tm, uint64_t n_docs, const uint64_t *blk_s, const uint64_t *blk_t,
+                              const uint64_t *goff, uint64_t n_groups, uint32_t before, uint32_t after, uint64_t n_runs, uint64_t *grp,
+                              uint64_t *w0, uint64_t *w1, uint32_t *tog, uint32_t max_blocks, void *stream);
+// keep[0, ceil(n_docs / 32)): bit r = an odd number of toggles lies at or in front of r (blk_x: tog ranked over n_docs + 1 bits)
+void greplines_launch_fill(const uint32_t *tog, const uint64_t *blk_x, uint64_t n_docs, uint32_t *keep, uint32_t max_blocks,
+                           void *stream);
+// is_match[i] = bit d of m for the i-th set bit d of the ranked keep mask
+void greplines_launch_emit_match(const uint32_t *keep, const uint64_t *blk_k, uint64_t n_docs, const uint32_t *m, uint8_t *is_match,
+                                 uint32_t max_blocks, void *stream);
+
 // class-counts path (scan_classcount.hip; engine.cpp device_class_counts), over one range of whole documents: its n_hits hits in
 // `hits` (hit_off[d] - hit_off[0]: the first hit of document d of its nd), key k's classes cls_ids[cls_off[k] .. cls_off[k+1]),
 // out: the row of the range's first document (n_classes words per document, cleared before the call's first range).

@@ -270,6 +270,19 @@ lib LibAhaHip
     flags : UInt32      # 0
     reserved : UInt32   # 0
   end
+  # context lines: with GREP_LINES (beside GREP_INVERT) `params` of the grep entries points to a GrepLinesParams -- cast its
+  # address to MatchParams* --, and the records around a matching record are kept with it (grep -B, -A, -C), inside the groups
+  GREP_LINES = 16_u32
+  struct GrepLinesParams
+    match : MatchParams     # first member: match.struct_size = sizeof(GrepLinesParams), 88 bytes
+    before : UInt32         # records of context in front of a matching record, 0 .. 0x7FFFFFFF
+    after : UInt32          # records of context behind it, 0 .. 0x7FFFFFFF
+    flags : UInt32          # 0
+    reserved : UInt32       # 0
+    group_offsets : UInt64* # G + 1 entries or null (host entry: host memory; device entry: HBM)
+    n_groups : UInt64       # G; 0 with null
+    is_match : UInt8*       # optional, cap_docs entries: 1 where the kept record matched, 0 where it is context
+  end
   fun aha_classes_create(ac : Ac, class_ids : UInt32*, offsets : UInt64*, n_classes : UInt32, out : Classes*) : Int32
   fun aha_classes_free(table : Classes) : Void
   fun aha_ac_class_counts_batch(ac : Ac, table : Classes, corpus : UInt8*, doc_offsets : UInt64*, n_docs : UInt64,
@@ -683,10 +696,18 @@ module Aha
 
     # The records of seq that have a hit of match(record, sep: sep), each with its delimiter; invert: those that have none
     # (aha_ac_records_batch, then aha_ac_grep_batch over the records; Aha::AC has no such method).
-    def grep(seq : String | Bytes, delim : UInt8 = 10_u8, invert : Bool = false, sep : BitArray? = nil) : Array(Bytes)
+    # before, after (context: both): grep -B, -A, -C -- that many records around a matching one are kept with it
+    # (aha_ac_grep_batch with GREP_LINES; the sequence is one group).  Without them the call is plain grep's.
+    def grep(seq : String | Bytes, delim : UInt8 = 10_u8, invert : Bool = false, sep : BitArray? = nil, before : UInt32 = 0_u32,
+             after : UInt32 = 0_u32, context : UInt32? = nil) : Array(Bytes)
       bytes = seq.is_a?(String) ? seq.to_slice : seq
       rec = records(bytes, delim)
       n_rec = (rec.size - 1).to_u64
+      if c = context
+        raise ArgumentError.new("context sets both sides: give it, or before and after") if before != 0 || after != 0
+        before = after = c
+      end
+      return grep_lines(bytes, rec, n_rec, invert, sep, before, after) if before != 0 || after != 0
       params = AC.params(false, sep)
       flags = invert ? LibAhaHip::GREP_INVERT : 0_u32
       nk = 0_u64
@@ -701,6 +722,35 @@ module Aha
       rc = LibAhaHip.aha_ac_grep_batch(@handle, bytes.to_unsafe, rec.to_unsafe, n_rec, pointerof(params), flags,
         Pointer(UInt64).null, doo.to_unsafe, nk, nb > 0 ? out_bytes.to_unsafe : Pointer(UInt8).null, nb, pointerof(nk),
         pointerof(nb), Pointer(UInt64).null)
+      raise String.new(LibAhaHip.aha_last_error(@handle)) if rc != 0
+      Array.new(nk.to_i32) { |i| out_bytes[doo[i], doo[i + 1] - doo[i]] }
+    end
+
+    # grep's context form over the records rec of bytes (one group): the sizing call, then the kept records' bytes
+    private def grep_lines(bytes : Bytes, rec : Array(UInt64), n_rec : UInt64, invert : Bool, sep : BitArray?, before : UInt32,
+                           after : UInt32) : Array(Bytes)
+      lp = LibAhaHip::GrepLinesParams.new
+      lp.match = AC.params(false, sep)
+      lp.match.struct_size = sizeof(LibAhaHip::GrepLinesParams).to_u32
+      lp.before = before
+      lp.after = after
+      lp.flags = 0_u32
+      lp.reserved = 0_u32
+      lp.group_offsets = Pointer(UInt64).null
+      lp.n_groups = 0_u64
+      lp.is_match = Pointer(UInt8).null
+      params = pointerof(lp).as(LibAhaHip::MatchParams*)
+      flags = LibAhaHip::GREP_LINES | (invert ? LibAhaHip::GREP_INVERT : 0_u32)
+      nk = 0_u64
+      nb = 0_u64
+      rc = LibAhaHip.aha_ac_grep_batch(@handle, bytes.to_unsafe, rec.to_unsafe, n_rec, params, flags, Pointer(UInt64).null,
+        Pointer(UInt64).null, 0_u64, Pointer(UInt8).null, 0_u64, pointerof(nk), pointerof(nb), Pointer(UInt64).null)
+      raise String.new(LibAhaHip.aha_last_error(@handle)) if rc != 0
+      doo = Array(UInt64).new(nk + 1, 0_u64)
+      out_bytes = Bytes.new(nb)
+      rc = LibAhaHip.aha_ac_grep_batch(@handle, bytes.to_unsafe, rec.to_unsafe, n_rec, params, flags, Pointer(UInt64).null,
+        doo.to_unsafe, nk, nb > 0 ? out_bytes.to_unsafe : Pointer(UInt8).null, nb, pointerof(nk), pointerof(nb),
+        Pointer(UInt64).null)
       raise String.new(LibAhaHip.aha_last_error(@handle)) if rc != 0
       Array.new(nk.to_i32) { |i| out_bytes[doo[i], doo[i + 1] - doo[i]] }
     end

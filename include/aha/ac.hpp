@@ -682,6 +682,93 @@ class AC {
     return nk;
   }
 
+  // Context lines (aha_ac_grep_batch with AHA_GREP_LINES): grep -B, -A and -C over the documents (records) of a batch.  A
+  // document is kept when it has a hit (invert: when it has none) or lies at most `before` documents in front of / `after`
+  // behind such a document of its group; groups (G + 1 offsets into the documents, such as the doc_rec_offsets of records();
+  // empty: one group) bound the context, so it never crosses a file.
+  //   auto m = aha::AC::compile({"ab"});
+  //   aha::AC::LinesOptions o;
+  //   o.before = 1;
+  //   auto l = m.grep_lines_batch("x\nab\ny\nz\nab\nw\n", {0, 2, 5, 7, 9, 12, 14}, o);
+  //   // l.kept_docs {0, 1, 3, 4}, l.is_match {0, 1, 0, 1}, l.out "x\nab\nz\nab\n"
+  struct LinesOptions {
+    uint32_t before = 0, after = 0;
+    bool invert = false;
+    std::vector<uint64_t> groups;  // empty: the whole batch is one group
+  };
+  struct Lines {
+    std::vector<uint64_t> kept_docs;        // n_kept, ascending
+    std::vector<uint64_t> doc_out_offsets;  // n_kept + 1
+    std::vector<uint8_t> is_match;          // n_kept: 1 where the kept document matched, 0 where it is context
+    std::string out;
+    uint64_t n_hits = 0;
+    std::string_view operator[](size_t i) const {
+      return std::string_view(out).substr(doc_out_offsets[i], doc_out_offsets[i + 1] - doc_out_offsets[i]);
+    }
+    size_t size() const { return kept_docs.size(); }
+  };
+  static aha_grep_lines_params grep_lines_params(uint32_t before, uint32_t after, const uint64_t *group_offsets, uint64_t n_groups,
+                                                 uint8_t *is_match) {
+    aha_grep_lines_params lp{};
+    lp.match.struct_size = sizeof(lp);
+    lp.before = before;
+    lp.after = after;
+    lp.group_offsets = n_groups ? group_offsets : nullptr;
+    lp.n_groups = n_groups;
+    lp.is_match = is_match;
+    return lp;
+  }
+  Lines grep_lines_batch(std::string_view corpus, const std::vector<uint64_t> &doc_offsets, const LinesOptions &opt) const {
+    if (doc_offsets.empty()) throw Error(AHA_E_INVALID, "doc_offsets holds D + 1 entries");
+    const uint64_t D = doc_offsets.size() - 1, G = opt.groups.empty() ? 0 : opt.groups.size() - 1;
+    aha_grep_lines_params lp = grep_lines_params(opt.before, opt.after, opt.groups.data(), G, nullptr);
+    const uint32_t flags = AHA_GREP_LINES | (opt.invert ? AHA_GREP_INVERT : 0u);
+    const uint8_t *text = reinterpret_cast<const uint8_t *>(corpus.data());
+    uint64_t nk = 0, nb = 0, nh = 0;
+    int32_t rc = aha_ac_grep_batch(h_, text, doc_offsets.data(), D, &lp.match, flags, nullptr, nullptr, 0, nullptr, 0, &nk, &nb, &nh);
+    Lines l;
+    l.kept_docs.resize(nk + 1);
+    l.doc_out_offsets.resize(nk + 1);
+    l.is_match.resize(nk + 1);
+    l.out.assign(nb, '\0');
+    if (rc == AHA_OK) {
+      lp.is_match = nk ? l.is_match.data() : nullptr;
+      rc = aha_ac_grep_batch(h_, text, doc_offsets.data(), D, &lp.match, flags, l.kept_docs.data(), l.doc_out_offsets.data(), nk,
+                             nb ? reinterpret_cast<uint8_t *>(&l.out[0]) : nullptr, nb, &nk, &nb, &nh);
+    }
+    if (rc != AHA_OK) {
+      const char *m = aha_last_error(h_);
+      throw Error(rc, (m && *m) ? m : aha_strerror(rc));
+    }
+    l.kept_docs.resize(nk);
+    l.is_match.resize(nk);
+    l.n_hits = nh;
+    return l;
+  }
+  // The device-resident form over HBM pointers of the handle's device (d_kept_docs [cap_docs], d_doc_out_offsets [cap_docs + 1],
+  // d_is_match [cap_docs], d_out [cap_bytes]; any may be null; d_group_offsets [n_groups + 1] or null): n_kept, the bytes and the
+  // hits come back; AHA_E_CAPACITY throws with nothing written (*n_required and *n_out_bytes, where given, hold the two required
+  // numbers either way).  opt.groups is not looked at.
+  uint64_t grep_lines_batch_device(const uint8_t *d_corpus, const uint64_t *d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
+                                   const LinesOptions &opt, const uint64_t *d_group_offsets, uint64_t n_groups, uint64_t *d_kept_docs,
+                                   uint64_t *d_doc_out_offsets, uint8_t *d_is_match, uint64_t cap_docs, uint8_t *d_out,
+                                   uint64_t cap_bytes, uint64_t *n_out_bytes = nullptr, uint64_t *n_hits = nullptr,
+                                   void *stream = nullptr, uint64_t *n_required = nullptr) const {
+    const aha_grep_lines_params lp = grep_lines_params(opt.before, opt.after, d_group_offsets, n_groups, d_is_match);
+    const uint32_t flags = AHA_GREP_LINES | (opt.invert ? AHA_GREP_INVERT : 0u);
+    uint64_t nk = 0, nb = 0, nh = 0;
+    const int32_t rc = aha_ac_grep_batch_device(h_, d_corpus, d_doc_offsets, n_docs, n_bytes, &lp.match, flags, d_kept_docs,
+                                                d_doc_out_offsets, cap_docs, d_out, cap_bytes, &nk, &nb, &nh, stream);
+    if (n_required) *n_required = nk;
+    if (n_out_bytes) *n_out_bytes = nb;
+    if (n_hits) *n_hits = nh;
+    if (rc != AHA_OK) {
+      const char *m = aha_last_error(h_);
+      throw Error(rc, (m && *m) ? m : aha_strerror(rc));
+    }
+    return nk;
+  }
+
   // Which bytes of the batch lie inside a hit of match_batch, without the hit list (aha_ac_cover_batch): bit j of the batch is
   // word j >> 5, bit j & 31 of what is returned; doc_covered (optional): covered bytes per document.
   std::vector<uint32_t> cover_batch(std::string_view corpus, const std::vector<uint64_t> &doc_offsets,

@@ -998,12 +998,60 @@ int32_t aha_ac_replace_batch_device(aha_ac *ac, const aha_repl *table, const uin
  * Device scratch beside the count call's: N / 8 bytes for M, 2 N / 8 for S and T and 16 bytes per 2048 text bytes for their
  * block ranks; 24 bytes and 2 bits per run and their block ranks; 28 bytes per excerpt and the scan's block sums.
  * AHA_GREP_BLOCKS caps the grids.
- * Out of scope so far: contexts counted in characters or in lines, a separator string between excerpts, combining with
- * AHA_GREP_RULE or invert, match_longest, char offsets, feeds and groups, the excerpt's document index written on the device,
- * an in-place form. */
+ * Out of scope so far: contexts counted in characters or in lines (whole neighbouring records: CONTEXT LINES below), a
+ * separator string between excerpts, combining with AHA_GREP_RULE or invert, match_longest, char offsets, feeds and groups, the
+ * excerpt's document index written on the device, an in-place form.
+ *
+ * CONTEXT LINES (AHA_GREP_LINES, flag 16, combinable with AHA_GREP_INVERT: flags 16 and 17).  grep -A n, -B n and -C n: the
+ * records around a matching record are kept with it, and context never crosses a group (a file).  `params` points to an
+ * aha_grep_lines_params whose first member is the call's aha_match_params with match.struct_size =
+ * sizeof(aha_grep_lines_params).  group_offsets and is_match are host memory in the host entry and HBM in the device entry.
+ * The call's "documents" are the records r = 0 .. D-1; any doc_offsets is allowed, not only lines.  The records
+ * [group_offsets[g], group_offsets[g+1]) form group g of G; the doc_rec_offsets that aha_ac_records_batch* writes is a valid
+ * group_offsets with G = the number of documents, which is the intended use.  NULL means one group, [0, D).  Empty groups are
+ * allowed and hold nothing; n_groups may exceed D + 1.  Empty records count as records.
+ *   m_r = (h_r >= 1) != invert: exactly plain grep's keep for the same params, flags and handle (a separator filter and every
+ *   fold option included).  Record r of group [lo, hi) is KEPT when some s in that group has m_s and r - after <= s <= r + before,
+ *   in 64-bit arithmetic.  Stated from the match: m_s keeps [max(lo, s - before), min(hi, s + 1 + after)).
+ * Everything else is grep's contract word for word: kept_docs holds the ascending indices, doc_out_offsets[0 .. n_kept] and out
+ * the kept records' own bytes (the original spelling on a folded handle); cap_docs, cap_bytes, the sizing call and
+ * AHA_E_CAPACITY with both required numbers and nothing written -- is_match included -- behave as in grep; out == NULL never
+ * launches the copy; *n_hits = all hits of the batch; two calls give identical bytes; N = 0 and D = 0 are valid; the handle's
+ * back-off state is read and never written; aha_ac_last_timing reports ms_write as everything after the count.
+ * is_match (optional, cap_docs entries): is_match[i] = m of record kept_docs[i], grep's ':' against '-'.  It is written only
+ * where the call fits, and a non-NULL is_match counts as a per-document buffer in the cap_docs verdict.
+ * grep's "--" line is not produced on the device: a chunk ends behind kept record i exactly when kept_docs[i+1] !=
+ * kept_docs[i] + 1 or the two lie in different groups.
+ * Identities.  before = after = 0 equals plain grep with the same flags byte for byte, with is_match all 1.  before = after =
+ * 0x7FFFFFFF with G groups keeps exactly the groups that hold a matching record, whole.  With NULL groups and at least one
+ * match every record is kept.
+ * AHA_E_INVALID before any device work, with every buffer and every count untouched: flag 16 together with 2, 4, 8 or an
+ * unknown bit, params == NULL, match.struct_size < sizeof(aha_grep_lines_params), the struct's flags != 0 or reserved != 0,
+ * before or after above 0x7FFFFFFF, group_offsets == NULL with n_groups != 0 or the reverse, is_match != NULL with cap_docs ==
+ * 0, and everything plain grep refuses.  A bad sep_size answers AHA_E_SEP_SIZE; a host-only handle answers AHA_E_NO_DEVICE
+ * after all of these.  Without the flag the two entry points behave exactly as above, whatever struct_size says.
+ * The group offsets are validated on the device before anything indexes with them: first entry 0, ascending (equal neighbours
+ * allowed), last entry D; a violation answers AHA_E_INVALID as bad doc_offsets do, and nothing is written.  A group may hold any
+ * number of records.
+ * Example.  Keys "ab"; the one document "x\nab\ny\nz\nab\nw\n" split by records into six lines (offsets 0, 2, 5, 7, 9, 12,
+ * 14); lines 1 and 4 match.  before = 1, after = 0, no groups: kept {0, 1, 3, 4}, is_match {0, 1, 0, 1}, out =
+ * "x\nab\nz\nab\n".  The same with group_offsets = {0, 4, 6}: line 3 lies in the other group, so it is not context of line 4:
+ * kept {0, 1, 4}.  With AHA_GREP_INVERT, before = after = 0: kept {0, 2, 3, 5}.
+ * Pipeline (aha_amd/csrc/scan_greplines.hip, DESIGN.md 4.16 "Context lines"): grep's count and flag passes give m; a lane per
+ * mask word writes Sm and Tm (a run of matching records starts / ends at the bit), a lane per inner group boundary splits the
+ * runs that cross it; both are ranked; the j-th bits delimit run j, whose group (a binary search) and window are written; the
+ * first and last run of every merged window XOR one bit each into a toggle mask of D + 1 bits (two windows of different groups
+ * that touch cancel there, and both sides are kept); the toggle mask is ranked and a prefix XOR per word fills the keep mask;
+ * rule grep's edges and grep's tail take it from there.  Every lane does O(1) work whatever before and after are.
+ * Device scratch beside plain grep's: 4 bits per record of masks, 24 bytes per 2048 records of block ranks, 24 bytes per
+ * matching run.  AHA_GREP_BLOCKS caps the grids.
+ * Out of scope so far: feeds (aha_feed_grep_batch* has no context lines yet: the follow-up), groups of GPUs, combining with
+ * AHA_GREP_RULE or AHA_GREP_CONTEXT, char offsets and match_longest, a separator written on the device, contexts in characters,
+ * an in-place form, a copy kernel of grep's own. */
 #define AHA_GREP_INVERT 1u /* keep the documents WITHOUT a hit */
 #define AHA_GREP_RULE 4u   /* params points to an aha_grep_params; keep = the rule over the class counts (2u is refused) */
 #define AHA_GREP_CONTEXT 8u /* params points to an aha_excerpt_params; the result is the excerpts, not documents */
+#define AHA_GREP_LINES 16u /* params points to an aha_grep_lines_params; the records around a matching record are kept too */
 #define AHA_RULE_GE 0u     /* lhs >= rhs */
 #define AHA_RULE_LT 1u     /* lhs <  rhs */
 typedef struct aha_classes aha_classes;
@@ -1030,6 +1078,17 @@ typedef struct {
   uint32_t flags;         /* 0 */
   uint32_t reserved;      /* 0 */
 } aha_excerpt_params;     /* 64 bytes */
+typedef struct {
+  aha_match_params match;        /* first member: match.struct_size = sizeof(aha_grep_lines_params) */
+  uint32_t before;               /* records of context in front of a matching record, 0 .. 0x7FFFFFFF (grep -B) */
+  uint32_t after;                /* records of context behind it,                     0 .. 0x7FFFFFFF (grep -A) */
+  uint32_t flags;                /* 0 */
+  uint32_t reserved;             /* 0 */
+  const uint64_t *group_offsets; /* G + 1 entries or NULL: the records [group_offsets[g], group_offsets[g+1]) form group g */
+  uint64_t n_groups;             /* G; 0 with NULL */
+  uint8_t *is_match;             /* optional, cap_docs entries: 1 where the kept record matched, 0 where it is context */
+} aha_grep_lines_params;         /* 88 bytes: match 0, before 48, after 52, flags 56, reserved 60, group_offsets 64,
+                                    n_groups 72, is_match 80 */
 int32_t aha_ac_records_batch(aha_ac *ac, const uint8_t *corpus, const uint64_t *doc_offsets, uint64_t n_docs, uint8_t delim,
                              uint32_t flags /* 0 */, uint64_t *rec_offsets /* cap_records + 1 */, uint64_t cap_records,
                              uint64_t *doc_rec_offsets /* D+1 or NULL */, uint64_t *n_records);
@@ -1378,7 +1437,7 @@ int32_t aha_feed_replace_batch_device(aha_feed *f, const aha_repl *table, const 
  * a records call's and a count call's, 17 bytes and 3 bits per fragment, 28 bytes per dropped run, 56 bytes and 4 W per piece;
  * 32 bytes of state per sequence.  AHA_GREP_BLOCKS caps the grids.
  * Out of scope so far: separator-filter feeds, char feeds, match_longest, a device-side hold buffer, rules over class counts
- * (AHA_GREP_RULE is a batch call), context lines. */
+ * (AHA_GREP_RULE is a batch call), context lines (AHA_GREP_LINES is a batch call too; a feed form is the follow-up). */
 #define AHA_FEED_GREP_FINAL 2u /* the pieces named in this call are the last of their sequences (beside AHA_GREP_INVERT, bit 0) */
 int32_t aha_feed_grep_batch(aha_feed *f, const uint8_t *corpus, const uint64_t *piece_offsets, const uint32_t *seq_ids,
                             uint64_t n_pieces, uint8_t delim, uint32_t flags /* AHA_GREP_INVERT | AHA_FEED_GREP_FINAL */,
